@@ -11,7 +11,10 @@ Inputs (depth + colour of every frame) are generated on the device before the
 timed region and stay resident in HBM.  The frame loop is native
 (vh_reconstruction_run, include/vh_api.h): one host call enqueues all frames.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps, what the last one computed (ray-cast maps, canonical scene; dump_outputs())
+as DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
 
 N > 1: one process per GPU (started by torch.distributed.run, or by this script
 itself when WORLD_SIZE is not set), one independent scene per GPU (orbit
@@ -64,6 +67,8 @@ def parse_args(argv=None):
     p.add_argument("--preroll-seconds", type=float, default=0.3, help="untimed device pre-roll before the warm-up (clocks, code objects)")
     p.add_argument("--no-extra-legs", action="store_true", help="skip the dense-scene integrate leg, the host-fed leg and cfg1")
     p.add_argument("--python-loop", action="store_true", help="drive the frames from Python (two ctypes calls per frame) instead of the native loop")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one computed (rank 0: ray-cast maps, "
+                                                                        "scene) to DIR/<name>.npy, float32 / float64, at most 64 MB (dump_outputs())")
     p.add_argument("--standin", action="store_true", help="TEST ONLY: a CPU stand-in workload (no GPU, no engine) to exercise the multi-rank harness")
     p.add_argument("--standin-fail", default="", help="TEST ONLY: 'R:before-init' or 'R:before-barrier' -- rank R of a --standin run exits with an error there")
     return p.parse_args(argv)
@@ -407,6 +412,85 @@ def preroll(wl, seconds):
     return done
 
 
+DUMP_SEED = 1729  # any fixed value: every run samples the same pixels and blocks
+DUMP_RAY_BYTES = 32_000_000  # the four ray-cast maps and their masks, 104 B per pixel: whole at 640x480, sampled at 1920x1080
+DUMP_POSITION_BYTES = 12_000_000  # block positions, 24 B per block
+DUMP_VOXEL_BLOCKS = 1024  # blocks whose voxels are written, 512 x 5 float32 each (10.5 MB)
+
+
+def dump_sample(n, limit, stream):
+    """-> sorted indices of a fixed seeded sample of `limit` of range(n), or None when all n fit"""
+    if n <= limit:
+        return None
+    import numpy as np
+    return np.sort(np.random.default_rng([DUMP_SEED, stream]).choice(n, limit, replace=False))
+
+
+def dump_finite(a):
+    """-> (a with 0 where it is not finite, float32 mask of a's shape: 1 where a is finite).  The ray caster writes -inf
+    (the reference's MINF) where a pixel has no value: no hit, or no normal at a silhouette."""
+    import numpy as np
+    ok = np.isfinite(a)
+    return np.where(ok, a, 0).astype(a.dtype), ok.astype(np.float32)
+
+
+def dump_outputs(wl, out_dir):
+    """What the timed path computed in its last step, as a caller of the frame loop receives it, as out_dir/<name>.npy:
+      raycast_{depth,depth4,normals,colors}  the ray caster's maps of the last frame (rendered from the previous pose):
+                                             [H, W(, 4)] float32, 0 where the map holds no value; above DUMP_RAY_BYTES a
+                                             fixed seeded sample of pixels, [P(, 4)], whose flat indices are in
+                                             raycast_pixel_index (float64)
+      raycast_{depth,...}_valid              float32 of the map's shape: 1 where it holds a value, 0 where the engine wrote
+                                             -inf (dump_finite())
+      scene_counts                           [allocated blocks, free heap slots], float64
+      scene_block_positions                  the allocated blocks' positions in (x, y, z) order, [n, 3] float64 (a fixed
+                                             seeded sample of them above DUMP_POSITION_BYTES)
+      scene_voxel_{block_positions,sdf,weight,color}  the voxels of a fixed seeded sample of DUMP_VOXEL_BLOCKS of those
+                                             blocks: [K, 3] float64, [K, 512] float32, [K, 512] float32, [K, 512, 3] float32
+    The scene is in its canonical form (voxelhashing_amd.canonical): which slot and heap block an entry got depends on
+    scheduling and is not written.  Every value written is finite.
+    The inputs are the same in every run, but the workload's online alloc is not fully deterministic: S1 is point-
+    symmetric about the origin, and of two new blocks that share a bucket, which one waits a frame is a matter of
+    scheduling ("Fragile by design").  So from run to run a few blocks near the origin can hold one
+    integration more or less, and the ray-cast maps in front of them differ in their last bits.  -> bytes written"""
+    import numpy as np
+    from voxelhashing_amd import canonical, lib, vhtypes as T
+    wl.recon.synchronize()
+    wl.torch.cuda.synchronize()
+    out = {}
+    ray = wl.ray.download()
+    H, W = ray["depth"].shape
+    pix = dump_sample(H * W, DUMP_RAY_BYTES // 104, 0)
+    for m in ("depth", "depth4", "normals", "colors"):
+        a = ray[m] if pix is None else ray[m].reshape(H * W, *ray[m].shape[2:])[pix]
+        out[f"raycast_{m}"], out[f"raycast_{m}_valid"] = dump_finite(a)
+    if pix is not None:
+        out["raycast_pixel_index"] = pix.astype(np.float64)
+    d = wl.scene.download(with_voxels=False)
+    snap = canonical.snapshot(d["hash"], None, d["heap"], d["heap_counter"], d["params"], with_voxels=False)
+    pos, ptrs = snap["positions"], snap["ptrs"]
+    assert len(ptrs) == 0 or (ptrs.min() >= 0 and ptrs.max() < d["params"].m_numSDFBlocks * T.SDF_BLOCK_VOXELS), "heap pointer out of range"
+    out["scene_counts"] = np.array([snap["num_occupied"], snap["heap_free"]], dtype=np.float64)
+    rows = dump_sample(len(pos), DUMP_POSITION_BYTES // 24, 1)
+    out["scene_block_positions"] = (pos if rows is None else pos[rows]).astype(np.float64)
+    blocks = dump_sample(len(pos), DUMP_VOXEL_BLOCKS, 2)
+    blocks = np.arange(len(pos)) if blocks is None else blocks
+    base = wl.scene.getHashData().d_SDFBlocks
+    vox = np.stack([lib.download(base + int(ptrs[b]) * T.VOXEL_DTYPE.itemsize, T.VOXEL_DTYPE, T.SDF_BLOCK_VOXELS, wl.scene.stream)
+                    for b in blocks]) if len(blocks) else np.zeros((0, T.SDF_BLOCK_VOXELS), dtype=T.VOXEL_DTYPE)
+    out["scene_voxel_block_positions"] = pos[blocks].astype(np.float64)
+    out["scene_voxel_sdf"] = vox["sdf"].astype(np.float32)
+    out["scene_voxel_weight"] = vox["weight"].astype(np.float32)
+    out["scene_voxel_color"] = vox["color"].astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64_000_000, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return total
+
+
 def stage_bytes(cfg_hp, cp, n_occ, stage, packed=True):
     """ALGORITHMIC bytes per launch (E = 20 B entry payload, V = 8 B voxel).  SURVEY.md section 8(d) prices the reference's
     integrate kernel at No*(E + 512*V*2) + 20*W*H: every block's entry, its voxels read and written, and the frame (4 B
@@ -744,6 +828,9 @@ def main(argv=None):
                                        frames_pipelined=int(st1.get("streamingFramesPipelined", 0) - st0.get("streamingFramesPipelined", 0)), blocks_out=int(st1["blocksStreamedOut"] - st0["blocksStreamedOut"]),
                                        blocks_in=int(st1["blocksStreamedIn"] - st0["blocksStreamedIn"]),
                                        blocks_per_second=round((st1["blocksStreamedOut"] - st0["blocksStreamedOut"] + st1["blocksStreamedIn"] - st0["blocksStreamedIn"]) / elapsed, 1))
+        if args.dump_outputs:
+            n = dump_outputs(wl, args.dump_outputs)
+            print(f"bench.py: the last timed step's outputs, {n / 1e6:.1f} MB, in {args.dump_outputs}", file=sys.stderr)
     wl.close()
     del wl
     torch.cuda.empty_cache()

@@ -39,7 +39,8 @@ class OracleWorkload:
 
 def main():
     out_path, warmup, steps = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
-    rank, world, local_rank, dist = bench.dist_setup(world_hint := int(os.environ["WORLD_SIZE"]))
+    # gloo also where a GPU is present: the workload is the CPU oracle, and a rank may not own a device of its own
+    rank, world, local_rank, dist = bench.dist_setup(world_hint := int(os.environ["WORLD_SIZE"]), force_cpu=True)
     assert dist is not None and dist.get_backend() == "gloo" and world == world_hint
     dev = torch.device("cpu")
     wl = OracleWorkload(rank, warmup + steps)

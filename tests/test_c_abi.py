@@ -110,10 +110,16 @@ def test_product_package_never_touches_the_oracle():
 def test_every_entry_point_refuses_null_arguments():
     """all pointers NULL, all numbers 0: an error code, never a crash and never a launch (the arguments are checked
     before anything touches the device).  vh_bind_input_depth_color_textures is the reference's texture binding: a
-    documented no-op."""
+    documented no-op.  vh_device_synchronize() has no arguments and vh_stream_synchronize(NULL) waits for the null
+    stream: valid calls, which succeed where there is a device and fail with an error code where there is none."""
     import ctypes as C
     from voxelhashing_amd import lib
     L = lib.load()
+    # asked of the library's own HIP runtime (not torch's, which may be a second one in this process): one byte
+    p = C.c_void_p()
+    have_device = L.vh_malloc(C.byref(p), 1) == 0
+    if have_device:
+        lib.check(L.vh_free(p), "vh_free")
     checked = 0
     for name, (res, args) in lib.PROTOTYPES.items():
         if res is not C.c_int:
@@ -122,6 +128,8 @@ def test_every_entry_point_refuses_null_arguments():
         rc = getattr(L, name)(*vals)
         if name == "vh_bind_input_depth_color_textures":
             assert rc == 0
+        elif name in ("vh_device_synchronize", "vh_stream_synchronize"):
+            assert (rc == 0) == have_device, (name, rc)
         else:
             assert rc != 0, name
         checked += 1

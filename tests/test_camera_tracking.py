@@ -91,14 +91,14 @@ s_distThres[1] = 0.2f;
     assert ts.s_maxLevels == 2 and ts.numLevelsFound == 2 and list(ts.s_maxOuterIter)[:3] == [8, 6, 0]
     assert ts.s_maxInnerIter[0] == 2 and ts.s_maxInnerIter[1] == 0 and ts.s_distThres[1] == np.float32(0.2)
     assert ts.s_distTransThres[0] == 0.5 and ts.s_residualEarlyOut[0] == np.float32(0.01)
-    path = "/root/reference/zParametersTrackingDefault.txt"
-    if os.path.exists(path):  # the reference's own file, read as data
-        lib.check(L.vh_tracking_state_read(path.encode(), C.byref(ts)), "read")
-        assert ts.s_maxLevels == 3 and ts.numLevelsFound == 4 and list(ts.s_maxOuterIter)[:4] == [8, 6, 4, 4]
-        assert all(ts.s_distThres[i] == np.float32(0.15) and ts.s_normalThres[i] == np.float32(0.97) for i in range(4))
-        want = T.make_tracking_state()
-        for name in ("s_maxOuterIter", "s_maxInnerIter", "s_distThres", "s_normalThres", "s_angleTransThres", "s_distTransThres", "s_residualEarlyOut"):
-            assert list(getattr(ts, name))[:3] == list(getattr(want, name))[:3], name
+    # the reference's own file, kept byte for byte under tests/golden/reference (read as data)
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "zParametersTrackingDefault.txt")
+    lib.check(L.vh_tracking_state_read(path.encode(), C.byref(ts)), "read")
+    assert ts.s_maxLevels == 3 and ts.numLevelsFound == 4 and list(ts.s_maxOuterIter)[:4] == [8, 6, 4, 4]
+    assert all(ts.s_distThres[i] == np.float32(0.15) and ts.s_normalThres[i] == np.float32(0.97) for i in range(4))
+    want = T.make_tracking_state()
+    for name in ("s_maxOuterIter", "s_maxInnerIter", "s_distThres", "s_normalThres", "s_angleTransThres", "s_distTransThres", "s_residualEarlyOut"):
+        assert list(getattr(ts, name))[:3] == list(getattr(want, name))[:3], name
 
 
 # ---------------------------------------------------------------------------- GPU

@@ -30,7 +30,13 @@ def test_two_rank_weak_scaling_harness():
                        MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), OMP_NUM_THREADS="1")
             procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "dist_worker.py"), out, str(warmup), str(steps)],
                                           env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-        logs = [p.communicate(timeout=300)[0].decode() for p in procs]
+        try:
+            logs = [p.communicate(timeout=300)[0].decode() for p in procs]
+        finally:  # a rank left waiting in the rendezvous does not outlive the test
+            for p in procs:
+                if p.poll() is None:
+                    p.kill()
+                    p.wait()
         assert all(p.returncode == 0 for p in procs), "\n".join(logs)
         res = json.load(open(out))
     assert res["world"] == 2

@@ -1,6 +1,6 @@
 """Marching cubes: extractIsoSurfacePass1/Pass2 + extractIsoSurfaceAtPosition.
 
-CPU: the case tables are self-consistent (and equal to the reference's where /root/reference is present), the oracle
+CPU: the case tables are self-consistent and equal to the reference's (kept under tests/golden/reference), the oracle
 restatement has the expected geometry on analytic scenes and reproduces the committed vectors.
 GPU: the HIP path (through the C ABI) produces the oracle's triangle SET bit for bit -- the order in the buffer
 comes from atomics on both sides -- with and without the box, per chunk through the streaming grid, and reports
@@ -58,22 +58,20 @@ def test_case_tables_are_consistent_and_match_the_header():
 
 
 def test_case_tables_equal_the_tables_the_reference_embeds():
-    """DSC/Tables.h carries Paul Bourke's published tables; read as DATA where the reference tree is mounted."""
-    path = "/root/reference/DepthSensingCUDA/Source/Tables.h"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
+    """DSC/Tables.h carries Paul Bourke's published tables; its numbers are kept as data in
+    tests/golden/reference/mc_tables.npz (tests/golden/make_reference_fixtures.py)."""
     import gen_mc_tables as G
     tri, edge = G.tables()
-    text = open(path).read()
-    nums = [int(x) for x in re.findall(r"-?\d+", re.search(r"triTable\[256\]\[16\]\s*=\s*\{(.*?)\};", text, re.S).group(1))]
+    g = np.load(os.path.join(GOLDEN, "reference", "mc_tables.npz"))
+    nums = [int(x) for x in g["tri_table"].ravel()]
     assert len(nums) == 4096
     for c in range(256):
         ref = [x for x in nums[16 * c:16 * c + 16] if x != -1]
         mine = [(tri[c] >> (4 * k)) & 0xF for k in range(16)]
         mine = mine[:mine.index(0xF)] if 0xF in mine else mine
         assert mine == ref, f"case {c}"
-    ref_edges = [int(x, 16) for x in re.findall(r"0x[0-9a-fA-F]+", re.search(r"edgeTable\[256\]\s*=\s*\{(.*?)\};", text, re.S).group(1))]
-    assert ref_edges == edge
+    ref_edges = [int(x) for x in g["edge_table"]]
+    assert len(ref_edges) == 256 and ref_edges == edge
 
 
 def test_oracle_plane_surface(oracle_lib):

@@ -75,11 +75,8 @@ s_SDFVoxelSize = .004f
 
 @pytest.mark.parametrize("name", ["zParametersDefault.txt", "zParametersManolisScan.txt", "zParametersTrackingDefault.txt"])
 def test_reference_parameter_files(name):
-    """the reference's own files, where its tree is mounted (read as data)"""
-    path = os.path.join("/root/reference", name)
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
-    L, g = read(path)
+    """the reference's own files, kept byte for byte under tests/golden/reference (read as data)"""
+    L, g = read(os.path.join(ROOT, "tests", "golden", "reference", name))
     if name == "zParametersTrackingDefault.txt":
         assert g.numKeysFound == 0 or g.s_hashNumBuckets == 0  # the tracking file holds GlobalCameraTrackingState keys
         return

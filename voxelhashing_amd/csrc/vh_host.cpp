@@ -95,18 +95,21 @@ int vh_free_host(void* hostPtr)
 }
 int vh_memcpy_h2d(void* dst, const void* src, size_t bytes, vhStream_t stream)
 {
+    if (!dst || !src) return VH_ERR_BAD_ARGUMENT;
     VH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
     VH_HIP(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
 int vh_memcpy_d2h(void* dst, const void* src, size_t bytes, vhStream_t stream)
 {
+    if (!dst || !src) return VH_ERR_BAD_ARGUMENT;
     VH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
     VH_HIP(hipStreamSynchronize((hipStream_t)stream));
     return VH_OK;
 }
 int vh_memset(void* dst, int value, size_t bytes, vhStream_t stream)
 {
+    if (!dst) return VH_ERR_BAD_ARGUMENT;
     VH_HIP(hipMemsetAsync(dst, value, bytes, (hipStream_t)stream));
     return VH_OK;
 }
