@@ -756,4 +756,37 @@ private:
     VhIcpState m_lastState;
 };
 
+// ---------------------------------------------------------------------------
+// CUDACameraTrackingMultiResRGBD (DSC/CUDACameraTrackingMultiResRGBD.{h,cpp}): coarse-to-fine ICP with a point-to-plane
+// and a photometric term per pixel, linearised in Euler angles.  Where the geometry leaves a motion unconstrained (a
+// wall, a floor, a table top) the model's intensity gradients still pin it.  The per-level settings travel as one
+// VhTrackingStateRGBD; the sensor's depth-range maximum comes from the DepthCameraParams.
+class CUDACameraTrackingMultiResRGBD {
+public:
+    CUDACameraTrackingMultiResRGBD(unsigned int imageWidth, unsigned int imageHeight, unsigned int levels, vhStream_t stream = nullptr);
+    ~CUDACameraTrackingMultiResRGBD();
+    CUDACameraTrackingMultiResRGBD(const CUDACameraTrackingMultiResRGBD&) = delete;
+    CUDACameraTrackingMultiResRGBD& operator=(const CUDACameraTrackingMultiResRGBD&) = delete;
+
+    // applyCT :239-327.  dInputColor: the sensor's float4 colour map (getColorMapFilteredFloat4); dModel*: the ray
+    // caster's d_depth4, d_normals and d_colors.  Returns lastTransform * delta; a matrix of -inf when tracking was lost.
+    vh::mat4f applyCT(float* dInput, float* dInputNormals, float* dInputColor, float* dModel, float* dModelNormals, float* dModelColor,
+                      const vh::mat4f& lastTransform, const VhTrackingStateRGBD& settings, const vh::mat4f& deltaTransformEstimate,
+                      const DepthCameraParams& depthCameraParams);
+    static bool isTrackingLost(const vh::mat4f& m);
+    const VhIcpStateRGBD& getLastState() const { return m_lastState; }
+    unsigned int getLevels() const { return m_levels; }
+
+private:
+    unsigned int m_levels;
+    vhStream_t m_stream;
+    std::vector<unsigned int> m_imageWidth, m_imageHeight;
+    std::vector<float*> d_input, d_inputNormal, d_inputIntensity, d_inputIntensityFiltered;
+    std::vector<float*> d_model, d_modelNormal, d_modelIntensity, d_modelIntensityFiltered, d_modelIntensityAndDerivatives;
+    float* d_partials;
+    VhIcpStateRGBD* d_state;
+    float* d_deltaEstimate;
+    VhIcpStateRGBD m_lastState;
+};
+
 #endif // VH_HPP

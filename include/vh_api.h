@@ -491,6 +491,43 @@ int vh_camera_tracking_apply_ct(VhCameraTracking* t, float* d_input4, float* d_i
                                 const float lastTransform[16], const VhTrackingState* settings, const float deltaTransformEstimate[16],
                                 const VhDepthCameraParams* cp, float transformOut[16], int* trackingLost, VhIcpState* state);
 
+/* ---- RGB-D camera tracking: depth + photometric multi-resolution ICP (CUDACameraTrackingMultiResRGBD).  Launcher
+ * level, in the style of the f5 block above; a level starts with vh_icp_begin_level(&d_state->icp), and every
+ * vh_icp_rgbd_solve is one outer iteration of align (the reference's RGB-D align has no inner loop).
+ *   vh_compute_intensity_and_derivatives  computeIntensityAndDerivatives        DSC/CameraUtil.cu:1492-1538
+ *   vh_icp_rgbd_build_linear_system       computeNormalEquations (per-wave terms) DSC/CUDABuildLinearSystemRGBD.cu:106-220
+ *   vh_icp_rgbd_solve                     reductionSystemCPU + computeBestRigidAlignment + delinearizeTransformation +
+ *                                         checkRigidTransformation + the early-out of align
+ *                                                                        DSC/CUDABuildLinearSystemRGBD.cpp:46-86,
+ *                                                                        DSC/CUDACameraTrackingMultiResRGBD.cpp:166-237,329-350 */
+int vh_compute_intensity_and_derivatives(const float* d_intensity, uint32_t width, uint32_t height, float* d_intensityAndDerivatives4, vhStream_t stream);
+int vh_icp_rgbd_begin(VhIcpStateRGBD* d_state, const float* d_deltaEstimate16, vhStream_t stream);
+uint32_t vh_icp_rgbd_num_partials(uint32_t width, uint32_t height, uint32_t level); /* rows of 30 floats the build step writes */
+int vh_icp_rgbd_build_linear_system(uint32_t width, uint32_t height, float* d_partials, const float* d_input4, const float* d_inputNormals4,
+                                    const float* d_inputIntensity, const float* d_target4, const float* d_targetNormals4,
+                                    const float* d_targetIntensityAndDerivatives4, const VhIcpRGBDParams* params, const VhIcpStateRGBD* d_state,
+                                    vhStream_t stream);
+int vh_icp_rgbd_solve(VhIcpStateRGBD* d_state, const float* d_partials, uint32_t numPartials, float angleThres, float distThres, float earlyOutResidual,
+                      vhStream_t stream);
+/* GlobalCameraTrackingState::readMembers with the four RGB-D keys (s_weightsDepth, s_weightsColor, s_colorGradientMin,
+ * s_colorThres); the other members exactly as vh_tracking_state_read returns them */
+int vh_tracking_state_rgbd_read(const char* filename, VhTrackingStateRGBD* out);
+int vh_tracking_state_rgbd_parse(const char* text, VhTrackingStateRGBD* out);
+
+/* handle level: CUDACameraTrackingMultiResRGBD (DSC/CUDACameraTrackingMultiResRGBD.h:23-75) */
+typedef struct VhCameraTrackingRGBD VhCameraTrackingRGBD;
+int vh_camera_tracking_rgbd_create(uint32_t imageWidth, uint32_t imageHeight, uint32_t levels, vhStream_t stream, VhCameraTrackingRGBD** out);
+void vh_camera_tracking_rgbd_destroy(VhCameraTrackingRGBD* t);
+/* applyCT(dInputPos, dInputNormal, dInputColor, dTargetPos, dTargetNormal, dTargetColor, lastTransform, <per-level
+ * settings>, deltaTransformEstimate, ...) :239-327.  The input colour is the sensor's float4 colour map (what
+ * integrate() reads), the target maps are the ray caster's d_depth4, d_normals and d_colors.  Returns
+ * lastTransform * delta in transformOut, every entry -inf if tracking was lost (trackingLost = 1); state (may be NULL)
+ * receives the final VhIcpStateRGBD. */
+int vh_camera_tracking_rgbd_apply_ct(VhCameraTrackingRGBD* t, float* d_input4, float* d_inputNormals4, float* d_inputColor4, float* d_model4,
+                                     float* d_modelNormals4, float* d_modelColor4, const float lastTransform[16], const VhTrackingStateRGBD* settings,
+                                     const float deltaTransformEstimate[16], const VhDepthCameraParams* cp, float transformOut[16], int* trackingLost,
+                                     VhIcpStateRGBD* state);
+
 /* ---- marching cubes -------------------------------------------------------------------------
  * launcher level: resetMarchingCubesCUDA / extractIsoSurfacePass1CUDA / extractIsoSurfacePass2CUDA
  * (DSC/CUDAMarchingCubesSDF.cu:29-40, 94-105, 132-143).  The reference passes a RayCastData only for its member

@@ -344,6 +344,25 @@ typedef struct VhTrackingState {
     uint32_t numLevelsFound; /* how many levels of s_maxOuterIter the file held */
 } VhTrackingState;
 
+/* The same plus the four per-level keys of the RGB-D tracker (DSC/GlobalCameraTrackingState.h:17-20); a key the file
+ * does not hold takes setDefault's value (:67-71) on every level. */
+typedef struct VhTrackingStateRGBD {
+    VhTrackingState base;
+    float s_weightsDepth[VH_TRACKING_MAX_LEVELS];
+    float s_weightsColor[VH_TRACKING_MAX_LEVELS];
+    float s_colorGradientMin[VH_TRACKING_MAX_LEVELS];
+    float s_colorThres[VH_TRACKING_MAX_LEVELS];
+} VhTrackingStateRGBD;
+
+/* What one RGB-D build step needs besides the maps: CameraTrackingParameters (DSC/CameraTrackingInput.h:5-15) and the
+ * level's intrinsics (fx, fy, mx, my divided by 2^level, DSC/CUDACameraTrackingMultiResRGBD.cpp:295-297). */
+typedef struct VhIcpRGBDParams {
+    float fx, fy, mx, my;
+    float weightDepth, weightColor, distThres, normalThres;
+    float sensorMaxDepth, colorGradientMin, colorThres;
+    uint32_t level; /* picks the lane window: 12 at level 0, max(1, 12 / (4 level)) above (CUDABuildLinearSystemRGBD.cpp:31-32) */
+} VhIcpRGBDParams;
+
 /* Header of a recorded sequence (`.sens`, ml::SensorData, DSC/sensorData/sensorData.h:608-830): what
  * SensorDataReader::createFirstConnected hands to RGBDSensor::init and the intrinsics / extrinsics setters. */
 typedef struct VhSensorDataInfo {
@@ -371,6 +390,16 @@ typedef struct VhIcpState {
     uint32_t iterations;    /* linear systems solved so far */
     uint32_t pad[8];
 } VhIcpState;
+
+/* Device-resident state of one RGB-D solve (vh_icp_rgbd_*): a VhIcpState with the same meaning, plus the point the next
+ * build step linearises at.  The reference recomputes both from deltaTransform before every build
+ * (DSC/CUDACameraTrackingMultiResRGBD.cpp:204-208); here the solve step leaves them behind. */
+typedef struct VhIcpStateRGBD {
+    VhIcpState icp;
+    float angles[3];      /* anglesOld = delta's rotation as eulerAngles(2, 1, 0): R = Rz(a0) Ry(a1) Rx(a2) */
+    float translation[3]; /* translationOld = delta's translation column */
+    uint32_t pad[2];
+} VhIcpStateRGBD;
 
 /* Error codes of the C ABI: 0 ok; <0 = -(hipError_t); >0 logical. */
 enum {

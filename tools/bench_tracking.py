@@ -2,9 +2,10 @@
 """Measures the closed loop with camera tracking on: sensor pre-processing -> raycast at the last
 pose -> projective ICP (3 levels, the reference's default settings) -> integrate at the tracked pose, on the S3 scene
 at 640x480 / 4 cm voxels (cfg2's sizes).  Wall time per frame including the one read-back of the pose, HIP-event time of
-applyCT alone, and the drift against the true trajectory.  One JSON line.
+applyCT alone, and the drift against the true trajectory.  One JSON line; with --rgbd a second one for the RGB-D
+tracker (CUDACameraTrackingMultiResRGBD, the reference's default settings with their colour keys) on the same frames.
 
-    python tools/bench_tracking.py [--frames 120] [--width 640 --height 480]
+    python tools/bench_tracking.py [--frames 120] [--width 640 --height 480] [--rgbd]
 """
 import argparse
 import ctypes as C
@@ -25,14 +26,14 @@ def main():
     ap.add_argument("--frames", type=int, default=120)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--rgbd", action="store_true", help="also measure the RGB-D tracker on the same frames (second line)")
     ap.add_argument("--trajectory", action="store_true", help="poses from the true trajectory, no ICP: the host-fed (PCIe-inclusive) rate of the plain loop")
     args = ap.parse_args()
     import torch
     from oracle import oracle as O
-    from voxelhashing_amd import engine as E, lib, synth, vhtypes as T
+    from voxelhashing_amd import synth, vhtypes as T
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
-    L = lib.load()
     W, H = args.width, args.height
     hp = T.make_hash_params(500000, 1 << 18, **synth.PARAM_SETS["P4"])
     cp = T.make_depth_camera_params(W, H)
@@ -45,11 +46,23 @@ def main():
         rgbx = np.ascontiguousarray(np.clip(c * 255.0, 0, 255).astype(np.uint8))
         rgbx[..., 3] = 255
         frames.append((d, rgbx))
+    for kind in (["f5", "rgbd"] if args.rgbd and not args.trajectory else ["f5"]):
+        run(args, kind, frames, truth, hp, cp, rp, W, H)
+
+
+def run(args, kind, frames, truth, hp, cp, rp, W, H):
+    import torch
+    from voxelhashing_amd import engine as E, lib, vhtypes as T
+    L = lib.load()
     scene = E.CUDASceneRepHashSDF(hp, T.make_scene_options(offline=False, gc=False))
     ray = E.CUDARayCastSDF(rp)
     sensor = E.CUDARGBDSensor((W, H), (W, H), (W, H), cp.fx, cp.fy, cp.mx, cp.my, cp.m_sensorDepthWorldMin, cp.m_sensorDepthWorldMax)
-    tracker = E.CUDACameraTrackingMultiRes(W, H, 3)
-    ts = T.make_tracking_state()
+    if kind == "rgbd":
+        tracker = E.CUDACameraTrackingMultiResRGBD(W, H, 3)
+        ts = T.make_tracking_state_rgbd()
+    else:
+        tracker = E.CUDACameraTrackingMultiRes(W, H, 3)
+        ts = T.make_tracking_state()
     a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
     lib.check(L.vh_rgbd_sensor_get_maps(sensor.handle, C.byref(a), C.byref(b), C.byref(c)), "maps")
     cam = sensor.getDepthCameraData()
@@ -70,11 +83,14 @@ def main():
             scene.integrate(pose, frame, cp, None)
             continue
         e0.record()
-        new_pose, lost = tracker.applyCT(a, b, rd.d_depth4, rd.d_normals, pose, ts, None, cp)
+        if kind == "rgbd":
+            new_pose, lost = tracker.applyCT(a, b, cam.d_colorData, rd.d_depth4, rd.d_normals, rd.d_colors, pose, ts, None, cp)
+        else:
+            new_pose, lost = tracker.applyCT(a, b, rd.d_depth4, rd.d_normals, pose, ts, None, cp)
         e1.record()
         e1.synchronize()
         icp_ms += e0.elapsed_time(e1)
-        iters += tracker.state.iterations
+        iters += tracker.state.icp.iterations if kind == "rgbd" else tracker.state.iterations
         if lost:
             lost_frames += 1
         else:
@@ -90,12 +106,13 @@ def main():
                               ms_per_frame=round(1e3 * dt / n, 3), upload_bytes_per_frame=int(frames[0][0].nbytes + frames[0][1].nbytes),
                               config=dict(workload=f"S3 orbit, {W}x{H}, P4 voxels, float depth + RGBX bytes from pageable host memory every frame"))))
         return
-    print(json.dumps(dict(metric="tracked frames/sec: sensor pre-processing + raycast + ICP + integrate", value=round(n / dt, 1), unit="frames/s",
+    what = "RGB-D ICP (depth + photometric)" if kind == "rgbd" else "ICP"
+    settings = "reference default tracking settings with their colour keys" if kind == "rgbd" else "reference default tracking settings"
+    print(json.dumps(dict(metric=f"tracked frames/sec: sensor pre-processing + raycast + {what} + integrate", value=round(n / dt, 1), unit="frames/s",
                           ms_per_frame=round(1e3 * dt / n, 3), icp_ms_per_frame=round(icp_ms / n, 3), icp_systems_per_frame=round(iters / n, 2), lost_frames=lost_frames,
                           drift_m=round(float(np.linalg.norm(rel[:3, 3])), 5),
                           drift_deg=round(float(np.degrees(np.arccos(np.clip(0.5 * (np.trace(rel[:3, :3]) - 1), -1, 1)))), 4), path_m=round(float(path), 3),
-                          config=dict(workload=f"S3 orbit, {W}x{H}, P4 voxels, 3 pyramid levels, reference default tracking settings, host-fed frames"))))
-
+                          config=dict(workload=f"S3 orbit, {W}x{H}, P4 voxels, 3 pyramid levels, {settings}, host-fed frames", **({"tracker": "rgbd"} if kind == "rgbd" else {})))))
 
 if __name__ == "__main__":
     main()

@@ -2,7 +2,7 @@
 """Plays `.sens` sequences through the frame loop the way the reference application does (parameter file, tracking
 parameter file, optional mesh at the end) and prints one JSON line with the timing.
 
-    python tools/replay.py --params zParameters.txt [--tracking zParametersTracking.txt] [--sens a.sens b.sens]
+    python tools/replay.py --params zParameters.txt [--tracking zParametersTracking.txt] [--rgbd-tracking] [--sens a.sens b.sens]
                            [--mesh scan.ply] [--max-frames N] [--record out.sens]
 
 Without --sens the files named by s_binaryDumpSensorFile[i] in the parameter file are played."""
@@ -20,6 +20,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--params", required=True)
     ap.add_argument("--tracking", default=None)
+    ap.add_argument("--rgbd-tracking", action="store_true", help="track with depth + colour (CUDACameraTrackingMultiResRGBD) instead of depth alone")
     ap.add_argument("--sens", nargs="*", default=None)
     ap.add_argument("--mesh", default=None)
     ap.add_argument("--record", default=None, help="write what was processed, with the poses used, to this .sens file")
@@ -32,15 +33,16 @@ def main():
     g = R.read_app_state(args.params)
     if args.record:
         g.s_recordData = 1
-    t = R.read_tracking_state(args.tracking) if args.tracking else None
-    rec = R.Reconstruction(g, t, args.sens or None)
+    read = R.read_tracking_state_rgbd if args.rgbd_tracking else R.read_tracking_state
+    t = read(args.tracking) if args.tracking else None
+    rec = R.Reconstruction(g, t, args.sens or None, use_rgbd_tracking=args.rgbd_tracking)
     t0 = time.perf_counter()
     n = rec.run(args.max_frames)
     rec.scene.synchronize()
     dt = time.perf_counter() - t0
     out = dict(frames=n, seconds=round(dt, 3), frames_per_s=round(n / dt, 1) if dt > 0 else None, lost_frames=rec.lost_frames,
                blocks=rec.scene.getNumOccupiedBlocks(), heap_free=rec.scene.getHeapFreeCount(),
-               pose_source="recorded trajectory" if g.s_binaryDumpSensorUseTrajectory and not g.s_binaryDumpSensorUseTrajectoryOnlyInit else "projective ICP")
+               pose_source="recorded trajectory" if g.s_binaryDumpSensorUseTrajectory and not g.s_binaryDumpSensorUseTrajectoryOnlyInit else ("RGB-D ICP" if args.rgbd_tracking else "projective ICP"))
     if args.record:
         out["recorded"] = rec.saveRecordedFramesToFile(args.record)
     if args.mesh:

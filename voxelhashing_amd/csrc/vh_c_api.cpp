@@ -585,4 +585,29 @@ int vh_camera_tracking_apply_ct(VhCameraTracking* t, float* d_input4, float* d_i
     });
 }
 
+// ---- CUDACameraTrackingMultiResRGBD -------------------------------------------------
+
+int vh_camera_tracking_rgbd_create(uint32_t imageWidth, uint32_t imageHeight, uint32_t levels, vhStream_t stream, VhCameraTrackingRGBD** out)
+{
+    if (!out) return VH_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    return guarded([&] { *out = new VhCameraTrackingRGBD(imageWidth, imageHeight, levels, stream); });
+}
+void vh_camera_tracking_rgbd_destroy(VhCameraTrackingRGBD* t) { delete t; }
+int vh_camera_tracking_rgbd_apply_ct(VhCameraTrackingRGBD* t, float* d_input4, float* d_inputNormals4, float* d_inputColor4, float* d_model4,
+                                     float* d_modelNormals4, float* d_modelColor4, const float lastTransform[16], const VhTrackingStateRGBD* settings,
+                                     const float deltaTransformEstimate[16], const VhDepthCameraParams* cp, float transformOut[16], int* trackingLost,
+                                     VhIcpStateRGBD* state)
+{
+    if (!t || !lastTransform || !settings || !cp || !transformOut) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] {
+        const vh::mat4f est = deltaTransformEstimate ? toMat(deltaTransformEstimate) : vh::mat4f::identity();
+        const vh::mat4f r = t->impl.applyCT(d_input4, d_inputNormals4, d_inputColor4, d_model4, d_modelNormals4, d_modelColor4, toMat(lastTransform),
+                                            *settings, est, *cp);
+        std::memcpy(transformOut, r.m, sizeof(r.m));
+        if (trackingLost) *trackingLost = CUDACameraTrackingMultiResRGBD::isTrackingLost(r) ? 1 : 0;
+        if (state) *state = t->impl.getLastState();
+    });
+}
+
 } // extern "C"

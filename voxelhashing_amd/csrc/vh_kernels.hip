@@ -3472,50 +3472,27 @@ __global__ __launch_bounds__(64) void k_icp_build_system(uint32_t W, uint32_t H,
     }
 }
 
-// One wave: reductionSystemCPU (.cpp:52-92) over the wave partials in their order, then what computeBestRigidAlignment,
-// delinearizeTransformation and align do with the system on the host (DSC/CUDACameraTrackingMultiRes.cpp:186-253,
-// 306-318).  The 6x6 symmetric system is solved through its eigen-decomposition (cyclic Jacobi, double precision):
-// x = V diag(1/l_i) V^T b with eigenvalues below 6 eps * l_max dropped, which is what Eigen's JacobiSVD::solve returns
-// for a symmetric positive semi-definite matrix; the condition number is l_max / l_min.
-__global__ __launch_bounds__(64) void k_icp_solve(VhIcpState* st, const float* partials, uint32_t nPartials, float angleThres, float distThres, float earlyOut, uint32_t lastInner)
+// reductionSystemCPU (.cpp:52-92) for term t: the wave partials summed in their order; eight loads in flight
+VHD float icp_sum_term(const float* partials, uint32_t nPartials, uint32_t t)
 {
-    __shared__ float sTerms[kIcpTerms];
-    if (st->lost || st->done) return;
-    const uint32_t t = threadIdx.x;
-    if (t < kIcpTerms) {
-        // one term per lane, summed over the waves in their order (as reductionSystemCPU does); eight loads in flight
-        float sum = 0.0f;
-        uint32_t k = 0;
-        for (; k + 8u <= nPartials; k += 8u) {
-            float v[8];
+    float sum = 0.0f;
+    uint32_t k = 0;
+    for (; k + 8u <= nPartials; k += 8u) {
+        float v[8];
 #pragma unroll
-            for (uint32_t j = 0; j < 8u; j++) v[j] = partials[(size_t)(k + j) * kIcpTerms + t];
+        for (uint32_t j = 0; j < 8u; j++) v[j] = partials[(size_t)(k + j) * kIcpTerms + t];
 #pragma unroll
-            for (uint32_t j = 0; j < 8u; j++) sum += v[j];
-        }
-        for (; k < nPartials; k++) sum += partials[(size_t)k * kIcpTerms + t];
-        sTerms[t] = sum;
+        for (uint32_t j = 0; j < 8u; j++) sum += v[j];
     }
-    __syncthreads();
-    if (t != 0u) return;
-    double A[6][6], b[6];
-    {
-        uint32_t at = 0;
-        bool zero = true;
-        for (uint32_t r = 0; r < 6u; r++) {
-            for (uint32_t c = r; c < 6u; c++) {
-                A[r][c] = A[c][r] = (double)sTerms[at + c - r];
-                if (sTerms[at + c - r] != 0.0f) zero = false;
-            }
-            at += 6u - r;
-            b[r] = (double)sTerms[21u + r];
-        }
-        st->sumRegError = sTerms[27];
-        st->sumRegWeight = sTerms[28];
-        st->numCorr = (uint32_t)sTerms[29];
-        st->iterations += 1u;
-        if (zero) { st->lost = 1u; return; } // ATA.isZero(): no correspondence at all
-    }
+    for (; k < nPartials; k++) sum += partials[(size_t)k * kIcpTerms + t];
+    return sum;
+}
+
+// The 6x6 symmetric system solved through its eigen-decomposition (cyclic Jacobi, double precision):
+// x = V diag(1/l_i) V^T b with eigenvalues below 6 eps * l_max dropped, which is what Eigen's JacobiSVD::solve returns
+// for a symmetric positive semi-definite matrix.  A is destroyed; returns the condition number l_max / l_min.
+VHD float icp_solve_6x6(double (&A)[6][6], const double (&b)[6], double (&xs)[6])
+{
     // cyclic Jacobi on A (symmetric): A -> diag, V accumulates the rotations
     double V[6][6];
     for (int i = 0; i < 6; i++)
@@ -3552,8 +3529,7 @@ __global__ __launch_bounds__(64) void k_icp_solve(VhIcpState* st, const float* p
     }
     double lmax = 0.0, lmin = 1e300;
     for (int i = 0; i < 6; i++) { const double l = fabs(A[i][i]); lmax = l > lmax ? l : lmax; lmin = l < lmin ? l : lmin; }
-    st->matrixCondition = (float)(lmax / lmin);
-    double xs[6] = { 0, 0, 0, 0, 0, 0 };
+    for (int k = 0; k < 6; k++) xs[k] = 0.0;
     for (int i = 0; i < 6; i++) {
         const double l = fabs(A[i][i]);
         if (l <= 6.0 * 1.1920928955078125e-7 * lmax) continue; // rank decision of JacobiSVD (threshold = diagSize * epsilon)
@@ -3562,6 +3538,47 @@ __global__ __launch_bounds__(64) void k_icp_solve(VhIcpState* st, const float* p
         proj /= A[i][i];
         for (int k = 0; k < 6; k++) xs[k] += V[k][i] * proj;
     }
+    return (float)(lmax / lmin);
+}
+
+// The 30 summed terms -> A (both triangles), b; false when every term of A is zero (ATA.isZero())
+VHD bool icp_system_from_terms(const float* terms, double (&A)[6][6], double (&b)[6])
+{
+    uint32_t at = 0;
+    bool zero = true;
+    for (uint32_t r = 0; r < 6u; r++) {
+        for (uint32_t c = r; c < 6u; c++) {
+            A[r][c] = A[c][r] = (double)terms[at + c - r];
+            if (terms[at + c - r] != 0.0f) zero = false;
+        }
+        at += 6u - r;
+        b[r] = (double)terms[21u + r];
+    }
+    return !zero;
+}
+
+// One wave: reductionSystemCPU (.cpp:52-92) over the wave partials in their order, then what computeBestRigidAlignment,
+// delinearizeTransformation and align do with the system on the host (DSC/CUDACameraTrackingMultiRes.cpp:186-253,
+// 306-318), the solve by icp_solve_6x6.
+__global__ __launch_bounds__(64) void k_icp_solve(VhIcpState* st, const float* partials, uint32_t nPartials, float angleThres, float distThres, float earlyOut, uint32_t lastInner)
+{
+    __shared__ float sTerms[kIcpTerms];
+    if (st->lost || st->done) return;
+    const uint32_t t = threadIdx.x;
+    if (t < kIcpTerms) sTerms[t] = icp_sum_term(partials, nPartials, t); // one term per lane
+    __syncthreads();
+    if (t != 0u) return;
+    double A[6][6], b[6];
+    {
+        const bool nonzero = icp_system_from_terms(sTerms, A, b);
+        st->sumRegError = sTerms[27];
+        st->sumRegWeight = sTerms[28];
+        st->numCorr = (uint32_t)sTerms[29];
+        st->iterations += 1u;
+        if (!nonzero) { st->lost = 1u; return; } // ATA.isZero(): no correspondence at all
+    }
+    double xs[6];
+    st->matrixCondition = icp_solve_6x6(A, b, xs);
     // delinearizeTransformation :186-207: R = Rz(x0) Ry(x1) Rx(x2), t = x[3..5]; mean 0, meanStDev 1
     const float x0 = (float)xs[0], x1 = (float)xs[1], x2 = (float)xs[2];
     const float tx = (float)xs[3], ty = (float)xs[4], tz = (float)xs[5];
@@ -3589,6 +3606,305 @@ __global__ __launch_bounds__(64) void k_icp_solve(VhIcpState* st, const float* p
         if (fabsf(st->lastError - st->sumRegError) < earlyOut) st->done = 1u;
         st->lastError = st->sumRegError;
     }
+}
+
+// ---------------------------------------------------------------------------
+// RGB-D camera tracking: CUDACameraTrackingMultiResRGBD (DSC/CUDACameraTrackingMultiResRGBD.cpp) with
+// scanNormalEquationsDevice (DSC/CUDABuildLinearSystemRGBD.cu:106-201).  One fused kernel per iteration projects the
+// input pixels, looks the model up and sums a point-to-plane row and a photometric row; one wave then solves the
+// system, takes the Gauss-Newton step in Euler angles and leaves the next linearisation point in the VhIcpStateRGBD.
+// Like f5, the whole multi-level solve runs on the stream and the host reads the state once per frame.
+// ---------------------------------------------------------------------------
+
+// computeIntensityAndDerivativesDevice, DSC/CameraUtil.cu:1492-1529: (I, dI/du, dI/dv, 1) by the 3x3 Sobel stencil / 8;
+// MINF on the border and wherever one of the nine taps is MINF.  Only exact products and one exact division: the
+// result is the same bits as the reference's arithmetic in float.
+__global__ __launch_bounds__(256) void k_intensity_and_derivatives(float4* out, const float* in, uint32_t W, uint32_t H)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= W * H) return;
+    const uint32_t x = i % W, y = i / W;
+    const float mi = minf();
+    float4 o = make_float4(mi, mi, mi, mi);
+    if (x > 0u && x + 1u < W && y > 0u && y + 1u < H) {
+        float v[3][3]; // v[a][b] = pos_ab of the reference: pixel (x - 1 + a, y - 1 + b)
+        bool ok = true;
+#pragma unroll
+        for (uint32_t a = 0; a < 3u; a++)
+#pragma unroll
+            for (uint32_t b = 0; b < 3u; b++) {
+                v[a][b] = in[(y - 1u + b) * W + (x - 1u + a)];
+                ok = ok && v[a][b] != mi;
+            }
+        if (ok) {
+            float resU = (-1.0f) * v[0][0] + (1.0f) * v[2][0] + (-2.0f) * v[0][1] + (2.0f) * v[2][1] + (-1.0f) * v[0][2] + (1.0f) * v[2][2];
+            resU /= 8.0f;
+            float resV = (-1.0f) * v[0][0] + (-2.0f) * v[1][0] + (-1.0f) * v[2][0] + (1.0f) * v[0][2] + (2.0f) * v[1][2] + (1.0f) * v[2][2];
+            resV /= 8.0f;
+            o = make_float4(v[1][1], resU, resV, 1.0f);
+        }
+    }
+    out[i] = o;
+}
+
+constexpr float kPiF = 3.14159265358979323846f; // Scalar(M_PI) in float
+
+// MatrixBase::eulerAngles(2, 1, 0) of the Eigen the reference vendors (Geometry/EulerAngles.h, 3.2.2), restated for
+// this axis triple on a row-major 3x3 R: R = Rz(e0) Ry(e1) Rx(e2) with e0 in [0, pi].  A negative first angle is moved
+// up by pi and the other two follow (so a small negative z-rotation comes back near (pi, pi, pi)); the Gauss-Newton
+// step is taken in these angles, so the branch matters, not only the rotation they stand for.
+VHD void euler_angles_zyx(const float* R, float* e)
+{
+    float e0 = atan2f(R[3], R[0]);
+    const float c2 = sqrtf(R[8] * R[8] + R[7] * R[7]);
+    float e1;
+    if (e0 < 0.0f) {
+        e0 = e0 + kPiF;
+        e1 = atan2f(-R[6], -c2);
+    } else {
+        e1 = atan2f(-R[6], c2);
+    }
+    const float s1 = sinf(e0), c1 = cosf(e0);
+    e[0] = e0;
+    e[1] = e1;
+    e[2] = atan2f(s1 * R[2] - c1 * R[5], c1 * R[4] - s1 * R[1]);
+}
+
+// Eigen::AngleAxisf(R).angle() (Geometry/AngleAxis.h:159-189 over the quaternion of Quaternion.h:724-760, Shoemake's
+// construction): 2 acos(w), 0 when the quaternion's vector part is below dummy_precision (1e-5)
+VHD float angle_axis_angle(const float* R)
+{
+    const float tr = R[0] + R[4] + R[8];
+    float q[4]; // x, y, z, w
+    if (tr > 0.0f) {
+        float t = sqrtf(tr + 1.0f);
+        q[3] = 0.5f * t;
+        t = 0.5f / t;
+        q[0] = (R[7] - R[5]) * t;
+        q[1] = (R[2] - R[6]) * t;
+        q[2] = (R[3] - R[1]) * t;
+    } else {
+        int i = 0;
+        if (R[4] > R[0]) i = 1;
+        if (R[8] > R[4 * i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        float t = sqrtf(R[4 * i] - R[4 * j] - R[4 * k] + 1.0f);
+        q[i] = 0.5f * t;
+        t = 0.5f / t;
+        q[3] = (R[3 * k + j] - R[3 * j + k]) * t;
+        q[j] = (R[3 * j + i] + R[3 * i + j]) * t;
+        q[k] = (R[3 * k + i] + R[3 * i + k]) * t;
+    }
+    const float n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2];
+    if (n2 < 1e-5f * 1e-5f) return 0.0f;
+    return 2.0f * acosf(fminf(fmaxf(-1.0f, q[3]), 1.0f));
+}
+
+// anglesOld / translationOld of computeBestRigidAlignment (:204-208) from a row-major 4x4
+VHD void rgbd_linearisation_point(VhIcpStateRGBD* st, const float* m)
+{
+    const float R[9] = { m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10] };
+    euler_angles_zyx(R, st->angles);
+    st->translation[0] = m[3];
+    st->translation[1] = m[7];
+    st->translation[2] = m[11];
+}
+
+__global__ void k_icp_rgbd_begin(VhIcpStateRGBD* st, const float* d_deltaEstimate)
+{
+    const uint32_t t = threadIdx.x;
+    if (t < 16u) st->icp.delta[t] = d_deltaEstimate[t];
+    if (t == 0u) {
+        VhIcpState& s = st->icp;
+        s.lost = 0u; s.done = 0u; s.lastError = -1.0f; s.iterations = 0u; s.sumRegError = 0.0f; s.sumRegWeight = 0.0f; s.numCorr = 0u; s.matrixCondition = 0.0f;
+        float m[16];
+        for (int k = 0; k < 16; k++) m[k] = d_deltaEstimate[k];
+        rgbd_linearisation_point(st, m);
+    }
+}
+
+// evalRMat and its three derivatives, DSC/ICPUtil.h:30-126, with (alpha, beta, gamma) = (angles.z, angles.y, angles.x):
+// R = Rz(gamma) Ry(beta) Rx(alpha).  Row-major 3x3.
+VHD void eval_r(float ca, float cb, float cg, float sa, float sb, float sg, float* R)
+{
+    R[0] = cg * cb; R[1] = -sg * ca + cg * sb * sa; R[2] = sg * sa + cg * sb * ca;
+    R[3] = sg * cb; R[4] = cg * ca + sg * sb * sa;  R[5] = -cg * sa + sg * sb * ca;
+    R[6] = -sb;     R[7] = cb * sa;                 R[8] = cb * ca;
+}
+VHD void eval_r_dalpha(float ca, float cb, float cg, float sa, float sb, float sg, float* R)
+{
+    R[0] = 0.0f; R[1] = sg * sa + cg * sb * ca;  R[2] = sg * ca - cg * sb * sa;
+    R[3] = 0.0f; R[4] = -cg * sa + sg * sb * ca; R[5] = -cg * ca - sg * sb * sa;
+    R[6] = 0.0f; R[7] = cb * ca;                 R[8] = -cb * sa;
+}
+VHD void eval_r_dbeta(float ca, float cb, float cg, float sa, float sb, float sg, float* R)
+{
+    R[0] = -cg * sb; R[1] = cg * cb * sa; R[2] = cg * cb * ca;
+    R[3] = -sg * sb; R[4] = sg * cb * sa; R[5] = sg * cb * ca;
+    R[6] = -cb;      R[7] = -sb * sa;     R[8] = -sb * ca;
+}
+VHD void eval_r_dgamma(float ca, float cb, float cg, float sa, float sb, float sg, float* R)
+{
+    R[0] = -sg * cb; R[1] = -cg * ca - sg * sb * sa; R[2] = cg * sa - sg * sb * ca;
+    R[3] = cg * cb;  R[4] = -sg * ca + cg * sb * sa; R[5] = sg * sa + cg * sb * ca;
+    R[6] = 0.0f;     R[7] = 0.0f;                    R[8] = 0.0f;
+}
+VHD F3 mat3_mul(const float* M, F3 v)
+{
+    return mk3(M[0] * v.x + M[1] * v.y + M[2] * v.z, M[3] * v.x + M[4] * v.y + M[5] * v.z, M[6] * v.x + M[7] * v.y + M[8] * v.z);
+}
+
+// lane window of the RGB-D build step (CUDABuildLinearSystemRGBD.cpp:31-32)
+__host__ __device__ inline uint32_t icp_rgbd_window(uint32_t level) { return level == 0u ? kIcpWindow : (kIcpWindow / (4u * level) > 1u ? kIcpWindow / (4u * level) : 1u); }
+
+// addToLocalSystem (.cu:78-104): one row J (6) with residual r and weight w into the lane's 30 terms
+VHD void rgbd_add_row(float (&acc)[kIcpTerms], const float (&J)[6], float r, float w)
+{
+    uint32_t at = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 6u; i++) {
+#pragma unroll
+        for (uint32_t j = i; j < 6u; j++) acc[at + j - i] += J[i] * J[j] * w;
+        at += 6u - i;
+        acc[21u + i] -= J[i] * r * w; // -J^T F
+    }
+    acc[27] += w * (r * r);
+    acc[28] += w;
+    acc[29] += 1.0f;
+}
+
+// scanNormalEquationsDevice :106-201.  Lane x sums pixels [win x, win x + win) in order, the 64 lanes of the wave are
+// reduced with the +32 ... +1 tree (the reference's warpReduce) and lane 0 writes the wave's 30 terms: the shape and
+// order of k_icp_build_system.
+//
+// Fenced reference defect: the reference converts floor(u), floor(v) of the projection to int for the bilinear lookup
+// whatever their size; a point projected far off screen makes that an out-of-range float -> int conversion.  Such a
+// pixel can never pair up (its nearest-neighbour lookup, truncating u + 0.5, lies outside the image and returns MINF),
+// so it is rejected before any conversion: u + 0.5 and v + 0.5 must lie in (-1, W) and (-1, H).
+__global__ __launch_bounds__(64) void k_icp_rgbd_build_system(uint32_t W, uint32_t H, uint32_t window, float* partials, const float4* inPos,
+                                                              const float4* inNormal, const float* inIntensity, const float4* tgtPos,
+                                                              const float4* tgtNormal, const float4* tgtIntensity4, VhIcpRGBDParams prm,
+                                                              const VhIcpStateRGBD* st)
+{
+    if (st->icp.lost || st->icp.done) return;
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+    const float mi = minf();
+    // evalRMat(anglesOld) and the derivatives, once per lane (angles.x = gamma, .y = beta, .z = alpha)
+    const float ga = st->angles[0], be = st->angles[1], al = st->angles[2];
+    const float ca = cosf(al), cb = cosf(be), cg = cosf(ga), sa = sinf(al), sb = sinf(be), sg = sinf(ga);
+    float R[9], Ralpha[9], Rbeta[9], Rgamma[9];
+    eval_r(ca, cb, cg, sa, sb, sg, R);
+    eval_r_dgamma(ca, cb, cg, sa, sb, sg, Ralpha); // the reference's assignment (:133-135): Ralpha = evalR_dGamma, ...
+    eval_r_dbeta(ca, cb, cg, sa, sb, sg, Rbeta);
+    eval_r_dalpha(ca, cb, cg, sa, sb, sg, Rgamma);
+    const F3 tOld = mk3(st->translation[0], st->translation[1], st->translation[2]);
+    float acc[kIcpTerms];
+#pragma unroll
+    for (uint32_t k = 0; k < kIcpTerms; k++) acc[k] = 0.0f;
+    for (uint32_t w = 0; w < window; w++) {
+        const uint32_t idx = window * x + w;
+        if (!(idx % W < W && idx / W < H)) continue;
+        const float4 p4 = inPos[idx], n4 = inNormal[idx];
+        const float iIn = inIntensity[idx];
+        if (p4.x == mi || p4.y == mi || p4.z == mi || n4.x == mi || n4.y == mi || n4.z == mi || iIn == mi) continue;
+        const F3 p = mk3(p4.x, p4.y, p4.z);
+        const F3 rp = mat3_mul(R, p), nT = mat3_mul(R, mk3(n4.x, n4.y, n4.z));
+        const F3 pT = mk3(rp.x + tOld.x, rp.y + tOld.y, rp.z + tOld.z);
+        // pProjTrans = I pInputTransformed, I = [fx 0 mx; 0 fy my; 0 0 1]
+        const F3 pp = mk3(prm.fx * pT.x + 0.0f * pT.y + prm.mx * pT.z, 0.0f * pT.x + prm.fy * pT.y + prm.my * pT.z, 0.0f * pT.x + 0.0f * pT.y + 1.0f * pT.z);
+        if (!(pp.z > 0.0f)) continue;
+        const float u = pp.x / pp.z, v = pp.y / pp.z; // dehomogenize
+        const float un = u + 0.5f, vn = v + 0.5f;
+        if (!(un > -1.0f && un < (float)W && vn > -1.0f && vn < (float)H)) continue; // the fence (above)
+        // getValueNearestNeighbour, ICPUtil.h:188-197
+        const int ui = f2i(un), vi = f2i(vn);
+        if (ui < 0 || ui >= (int)W || vi < 0 || vi >= (int)H) continue;
+        const float4 tp = tgtPos[(uint32_t)vi * W + (uint32_t)ui], tn = tgtNormal[(uint32_t)vi * W + (uint32_t)ui];
+        // bilinearInterpolationFloat4, ICPUtil.h:129-156 (the same arithmetic as bilinear_float4)
+        const float4 it = bilinear_float4(u, v, tgtIntensity4, W, H);
+        if (tp.x == mi || tp.y == mi || tp.z == mi || tn.x == mi || tn.y == mi || tn.z == mi || it.x == mi || it.y == mi || it.z == mi) continue;
+        const F3 phiA = mat3_mul(Ralpha, pT), phiB = mat3_mul(Rbeta, pT), phiG = mat3_mul(Rgamma, pT);
+        const F3 diff = mk3(tp.x - pT.x, tp.y - pT.y, tp.z - pT.z);
+        const float dDist = sqrtf(diff.x * diff.x + diff.y * diff.y + diff.z * diff.z);
+        const float dNormal = tn.x * nT.x + tn.y * nT.y + tn.z * nT.z;
+        if (!(dDist <= prm.distThres && dNormal >= prm.normalThres)) continue; // both rows need it
+        {   // point to plane, :156-168 (z of the UNtransformed input point in the weight)
+            const float wD = fmaxf(0.0f, 0.5f * ((1.0f - dDist / prm.distThres) + (1.0f - p.z / prm.sensorMaxDepth)));
+            const float J[6] = { -(tn.x * phiA.x + tn.y * phiA.y + tn.z * phiA.z), -(tn.x * phiB.x + tn.y * phiB.y + tn.z * phiB.z),
+                                 -(tn.x * phiG.x + tn.y * phiG.y + tn.z * phiG.z), -tn.x, -tn.y, -tn.z };
+            const float r = tn.x * diff.x + tn.y * diff.y + tn.z * diff.z;
+            rgbd_add_row(acc, J, r, prm.weightDepth * wD);
+        }
+        // colour, :170-185: J = dI (1x2) * dehomogenizeDerivative (2x3) * K (3x3) * phi
+        const float dI = it.x - iIn;
+        const float gu = it.y, gv = it.z;
+        const float absDI = sqrtf(dI * dI); // norm1D of the 1x1 residual
+        if (absDI <= prm.colorThres && sqrtf(gu * gu + gv * gv) > prm.colorGradientMin) {
+            const float wC = fmaxf(0.0f, 1.0f - absDI / prm.colorThres);
+            const float iz = 1.0f / pp.z, wSq = pp.z * pp.z;
+            const float d0 = gu * iz, d1 = gv * iz, d2 = gu * (-pp.x / wSq) + gv * (-pp.y / wSq); // dI PI
+            const F3 g = mk3(d0 * prm.fx, d1 * prm.fy, d0 * prm.mx + d1 * prm.my + d2);         // (dI PI) K
+            const float J[6] = { g.x * phiA.x + g.y * phiA.y + g.z * phiA.z, g.x * phiB.x + g.y * phiB.y + g.z * phiB.z,
+                                 g.x * phiG.x + g.y * phiG.y + g.z * phiG.z, g.x, g.y, g.z };
+            rgbd_add_row(acc, J, dI, prm.weightColor * wC);
+        }
+    }
+    const uint32_t lane = lane_id();
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (uint32_t k = 0; k < kIcpTerms; k++) {
+            const float other = __shfl_down(acc[k], off);
+            if ((int)lane < off) acc[k] += other;
+        }
+    }
+    if (lane == 0u) {
+#pragma unroll
+        for (uint32_t k = 0; k < kIcpTerms; k++) partials[(size_t)blockIdx.x * kIcpTerms + k] = acc[k];
+    }
+}
+
+// One wave: reductionSystemCPU (CUDABuildLinearSystemRGBD.cpp:46-86), then computeBestRigidAlignment,
+// delinearizeTransformation and checkRigidTransformation (DSC/CUDACameraTrackingMultiResRGBD.cpp:166-237) and the
+// residual early-out of align (:329-350).  Unlike f5, the solution is an increment of the absolute Euler angles and
+// translation of delta (xNew = [anglesOld; translationOld] + x), and the rigidity check is on the new delta itself.
+// ATA.isZero() and a failed check both set lost; the reference would go on iterating with a matrix of -inf there.
+__global__ __launch_bounds__(64) void k_icp_rgbd_solve(VhIcpStateRGBD* st, const float* partials, uint32_t nPartials, float angleThres, float distThres, float earlyOut)
+{
+    __shared__ float sTerms[kIcpTerms];
+    VhIcpState& s = st->icp;
+    if (s.lost || s.done) return;
+    const uint32_t t = threadIdx.x;
+    if (t < kIcpTerms) sTerms[t] = icp_sum_term(partials, nPartials, t);
+    __syncthreads();
+    if (t != 0u) return;
+    double A[6][6], b[6];
+    const bool nonzero = icp_system_from_terms(sTerms, A, b);
+    s.sumRegError = sTerms[27];
+    s.sumRegWeight = sTerms[28];
+    s.numCorr = (uint32_t)sTerms[29];
+    s.iterations += 1u;
+    if (!nonzero) { s.lost = 1u; return; }
+    double xs[6];
+    s.matrixCondition = icp_solve_6x6(A, b, xs);
+    float x[6];
+    for (int k = 0; k < 3; k++) x[k] = st->angles[k] + (float)xs[k];
+    for (int k = 0; k < 3; k++) x[3 + k] = st->translation[k] + (float)xs[3 + k];
+    // delinearizeTransformation :177-194: R = Rz(x0) Ry(x1) Rx(x2), t = x[3..5]; mean 0, meanStDev 1
+    const float cz = cosf(x[0]), sz = sinf(x[0]), cy = cosf(x[1]), sy = sinf(x[1]), cx = cosf(x[2]), sx = sinf(x[2]);
+    const float R[9] = { cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx,
+                         sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx,
+                         -sy, cy * sx, cy * cx };
+    // checkRigidTransformation :166-175 (a NaN fails it, as in f5)
+    const float angle = angle_axis_angle(R);
+    const float tnorm = sqrtf(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
+    if (!(angle <= angleThres) || !(tnorm <= distThres)) { s.lost = 1u; return; }
+    const float M[16] = { R[0], R[1], R[2], x[3], R[3], R[4], R[5], x[4], R[6], R[7], R[8], x[5], 0.0f, 0.0f, 0.0f, 1.0f };
+    for (int k = 0; k < 16; k++) s.delta[k] = M[k];
+    rgbd_linearisation_point(st, M);
+    // align :345-350, after every outer iteration
+    if (fabsf(s.lastError - s.sumRegError) < earlyOut) s.done = 1u;
+    s.lastError = s.sumRegError;
 }
 
 // ---------------------------------------------------------------------------
@@ -4451,6 +4767,44 @@ int vh_icp_solve(VhIcpState* d_state, const float* d_partials, uint32_t numParti
 {
     if (!d_state || !d_partials) return VH_ERR_BAD_ARGUMENT;
     k_icp_solve<<<1, 64, 0, (hipStream_t)stream>>>(d_state, d_partials, numPartials, angleThres, distThres, earlyOutResidual, lastInnerIteration ? 1u : 0u);
+    return vh_last_launch_error();
+}
+
+int vh_compute_intensity_and_derivatives(const float* d_intensity, uint32_t width, uint32_t height, float* d_intensityAndDerivatives4, vhStream_t stream)
+{
+    if (!d_intensity || !d_intensityAndDerivatives4) return VH_ERR_BAD_ARGUMENT;
+    if (width * height == 0) return VH_OK;
+    k_intensity_and_derivatives<<<cdiv(width * height, 256u), 256, 0, (hipStream_t)stream>>>(reinterpret_cast<float4*>(d_intensityAndDerivatives4), d_intensity, width, height);
+    return vh_last_launch_error();
+}
+int vh_icp_rgbd_begin(VhIcpStateRGBD* d_state, const float* d_deltaEstimate, vhStream_t stream)
+{
+    if (!d_state || !d_deltaEstimate) return VH_ERR_BAD_ARGUMENT;
+    k_icp_rgbd_begin<<<1, 64, 0, (hipStream_t)stream>>>(d_state, d_deltaEstimate);
+    return vh_last_launch_error();
+}
+uint32_t vh_icp_rgbd_num_partials(uint32_t width, uint32_t height, uint32_t level) { return cdiv(width * height, 64u * icp_rgbd_window(level)); }
+int vh_icp_rgbd_build_linear_system(uint32_t width, uint32_t height, float* d_partials, const float* d_input4, const float* d_inputNormals4,
+                                    const float* d_inputIntensity, const float* d_target4, const float* d_targetNormals4,
+                                    const float* d_targetIntensityAndDerivatives4, const VhIcpRGBDParams* params, const VhIcpStateRGBD* d_state,
+                                    vhStream_t stream)
+{
+    if (!d_partials || !d_input4 || !d_inputNormals4 || !d_inputIntensity || !d_target4 || !d_targetNormals4 || !d_targetIntensityAndDerivatives4 ||
+        !params || !d_state)
+        return VH_ERR_BAD_ARGUMENT;
+    if (width * height == 0) return VH_OK;
+    const uint32_t window = icp_rgbd_window(params->level);
+    k_icp_rgbd_build_system<<<vh_icp_rgbd_num_partials(width, height, params->level), 64, 0, (hipStream_t)stream>>>(
+        width, height, window, d_partials, reinterpret_cast<const float4*>(d_input4), reinterpret_cast<const float4*>(d_inputNormals4), d_inputIntensity,
+        reinterpret_cast<const float4*>(d_target4), reinterpret_cast<const float4*>(d_targetNormals4),
+        reinterpret_cast<const float4*>(d_targetIntensityAndDerivatives4), *params, d_state);
+    return vh_last_launch_error();
+}
+int vh_icp_rgbd_solve(VhIcpStateRGBD* d_state, const float* d_partials, uint32_t numPartials, float angleThres, float distThres, float earlyOutResidual,
+                      vhStream_t stream)
+{
+    if (!d_state || !d_partials) return VH_ERR_BAD_ARGUMENT;
+    k_icp_rgbd_solve<<<1, 64, 0, (hipStream_t)stream>>>(d_state, d_partials, numPartials, angleThres, distThres, earlyOutResidual);
     return vh_last_launch_error();
 }
 

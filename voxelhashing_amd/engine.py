@@ -752,3 +752,37 @@ class CUDACameraTrackingMultiRes:
         check(self.L.vh_camera_tracking_apply_ct(self.handle, d_input, d_inputNormals, d_model, d_modelNormals, f16(lastTransform), C.byref(settings),
                                                  est, C.byref(cameraParams), out, C.byref(lost), C.byref(self.state)), "applyCT")
         return np.array(out, dtype=np.float32).reshape(4, 4), bool(lost.value)
+
+
+class CUDACameraTrackingMultiResRGBD:
+    """Mirror of DSC/CUDACameraTrackingMultiResRGBD.h:23-75 over the C ABI (device pointers in, 4x4 pose out)."""
+
+    def __init__(self, imageWidth, imageHeight, levels, stream=None):
+        self.L = load()
+        h = C.c_void_p()
+        check(self.L.vh_camera_tracking_rgbd_create(imageWidth, imageHeight, levels, stream, C.byref(h)), "vh_camera_tracking_rgbd_create")
+        self.handle = h
+        self.state = T.IcpStateRGBD()
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.L.vh_camera_tracking_rgbd_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def applyCT(self, d_input, d_inputNormals, d_inputColor, d_model, d_modelNormals, d_modelColor, lastTransform, settings, deltaTransformEstimate,
+                cameraParams):
+        """-> (4x4 float32 pose = lastTransform * delta, lost flag); the final VhIcpStateRGBD is kept in self.state.
+        d_inputColor: the sensor's float4 colour map; d_model*: the ray cast's d_depth4, d_normals, d_colors."""
+        out = (C.c_float * 16)()
+        lost = C.c_int(0)
+        est = f16(deltaTransformEstimate) if deltaTransformEstimate is not None else None
+        check(self.L.vh_camera_tracking_rgbd_apply_ct(self.handle, d_input, d_inputNormals, d_inputColor, d_model, d_modelNormals, d_modelColor,
+                                                      f16(lastTransform), C.byref(settings), est, C.byref(cameraParams), out, C.byref(lost),
+                                                      C.byref(self.state)), "applyCT")
+        return np.array(out, dtype=np.float32).reshape(4, 4), bool(lost.value)

@@ -134,6 +134,17 @@ PROTOTYPES = {
     "vh_camera_tracking_create": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _VP, P(_VP)]),
     "vh_camera_tracking_destroy": (None, [_VP]),
     "vh_camera_tracking_apply_ct": (C.c_int, [_VP, _VP, _VP, _VP, _VP, P(C.c_float), P(T.TrackingState), P(C.c_float), P(T.DepthCameraParams), P(C.c_float), P(C.c_int), P(T.IcpState)]),
+    "vh_compute_intensity_and_derivatives": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP, _VP]),
+    "vh_icp_rgbd_begin": (C.c_int, [_VP, _VP, _VP]),
+    "vh_icp_rgbd_num_partials": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "vh_icp_rgbd_build_linear_system": (C.c_int, [C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, P(T.IcpRGBDParams), _VP, _VP]),
+    "vh_icp_rgbd_solve": (C.c_int, [_VP, _VP, C.c_uint32, C.c_float, C.c_float, C.c_float, _VP]),
+    "vh_tracking_state_rgbd_read": (C.c_int, [C.c_char_p, P(T.TrackingStateRGBD)]),
+    "vh_tracking_state_rgbd_parse": (C.c_int, [C.c_char_p, P(T.TrackingStateRGBD)]),
+    "vh_camera_tracking_rgbd_create": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _VP, P(_VP)]),
+    "vh_camera_tracking_rgbd_destroy": (None, [_VP]),
+    "vh_camera_tracking_rgbd_apply_ct": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, P(C.c_float), P(T.TrackingStateRGBD), P(C.c_float), P(T.DepthCameraParams),
+                                                   P(C.c_float), P(C.c_int), P(T.IcpStateRGBD)]),
     "vh_app_state_read": (C.c_int, [C.c_char_p, P(T.AppState)]),
     "vh_app_state_parse": (C.c_int, [C.c_char_p, P(T.AppState)]),
     "vh_hash_params_from_app_state": (None, [P(T.AppState), P(T.HashParams)]),

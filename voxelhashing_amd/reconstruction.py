@@ -39,14 +39,39 @@ def read_tracking_state(path_or_text):
     return t
 
 
+def read_tracking_state_rgbd(path_or_text):
+    """the tracking parameter file with the RGB-D tracker's four colour keys (VhTrackingStateRGBD)"""
+    L = load()
+    t = T.TrackingStateRGBD()
+    if isinstance(path_or_text, bytes):
+        check(L.vh_tracking_state_rgbd_parse(path_or_text, C.byref(t)), "vh_tracking_state_rgbd_parse")
+    else:
+        check(L.vh_tracking_state_rgbd_read(str(path_or_text).encode(), C.byref(t)), "vh_tracking_state_rgbd_read")
+    return t
+
+
 class Reconstruction:
     """One scene fed from `.sens` files.  `frame()` is one pass of the reference's render callback with
     reconstruction enabled: read a frame, pre-process it, ray-cast the model at the last pose, find the new pose
-    (recorded trajectory or projective ICP), stream, integrate."""
+    (recorded trajectory or projective ICP), stream, integrate.
 
-    def __init__(self, app_state, tracking_state=None, sens_files=None, stream=None):
+    use_rgbd_tracking (off by default) is the reference's useRGBDTracking (DSC/DepthSensing.cpp:816): the pose comes
+    from CUDACameraTrackingMultiResRGBD, fed with the sensor's colour map and the ray cast's colours as well.  Its
+    tracking_state is then a TrackingStateRGBD (read_tracking_state_rgbd); a plain TrackingState keeps the colour keys'
+    defaults."""
+
+    def __init__(self, app_state, tracking_state=None, sens_files=None, stream=None, use_rgbd_tracking=False):
         self.L = load()
         self.gas = app_state
+        self.tracking_rgbd = None
+        if use_rgbd_tracking:
+            if isinstance(tracking_state, T.TrackingStateRGBD):
+                self.tracking_rgbd = tracking_state
+            else:
+                self.tracking_rgbd = T.make_tracking_state_rgbd()
+                if tracking_state is not None:
+                    self.tracking_rgbd.base = tracking_state
+            tracking_state = self.tracking_rgbd.base
         self.tracking = tracking_state if tracking_state is not None else T.make_tracking_state()
         if sens_files is None:
             sens_files = [bytes(app_state.s_binaryDumpSensorFile[i].value).decode() for i in range(app_state.s_numBinaryDumpSensorFiles)]
@@ -84,6 +109,9 @@ class Reconstruction:
             self.chunk_grid = E.CUDASceneRepChunkGrid(self.scene, tuple(g.s_streamingVoxelExtents), tuple(g.s_streamingGridDimensions),
                                                       tuple(g.s_streamingMinGridPos), g.s_streamingInitialChunkListSize, False, g.s_streamingOutParts)
         self.tracker = E.CUDACameraTrackingMultiRes(self.adapter_size[0], self.adapter_size[1], self.tracking.s_maxLevels, stream=stream)
+        self.tracker_rgbd = None
+        if self.tracking_rgbd is not None:
+            self.tracker_rgbd = E.CUDACameraTrackingMultiResRGBD(self.adapter_size[0], self.adapter_size[1], self.tracking.s_maxLevels, stream=stream)
         self.marching_cubes = None
         cam = self.sensor.getDepthCameraData()
         self.frame_data = E.DepthFrame(self.cp, depth_ptr=cam.d_depthData, color_ptr=cam.d_colorData)
@@ -149,7 +177,11 @@ class Reconstruction:
                 a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
                 check(self.L.vh_rgbd_sensor_get_maps(self.sensor.handle, C.byref(a), C.byref(b), C.byref(c)), "maps")
                 rd = self.ray.getRayCastData()
-                transformation, lost = self.tracker.applyCT(a, b, rd.d_depth4, rd.d_normals, self.scene.getLastRigidTransform(), self.tracking, None, self.cp)
+                if self.tracker_rgbd is not None:
+                    transformation, lost = self.tracker_rgbd.applyCT(a, b, self.sensor.getDepthCameraData().d_colorData, rd.d_depth4, rd.d_normals, rd.d_colors,
+                                                                     self.scene.getLastRigidTransform(), self.tracking_rgbd, None, self.cp)
+                else:
+                    transformation, lost = self.tracker.applyCT(a, b, rd.d_depth4, rd.d_normals, self.scene.getLastRigidTransform(), self.tracking, None, self.cp)
                 if lost:
                     self.lost_frames += 1
                     return self._done(None)  # "!!! TRACKING LOST !!!": the frame is not integrated

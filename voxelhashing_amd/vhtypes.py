@@ -183,6 +183,26 @@ class IcpState(C.Structure):
     ]
 
 
+class TrackingStateRGBD(C.Structure):
+    """VhTrackingStateRGBD: the f5 settings plus the four per-level keys of the RGB-D tracker"""
+    _fields_ = [
+        ("base", TrackingState), ("s_weightsDepth", C.c_float * 8), ("s_weightsColor", C.c_float * 8),
+        ("s_colorGradientMin", C.c_float * 8), ("s_colorThres", C.c_float * 8),
+    ]
+
+
+class IcpRGBDParams(C.Structure):
+    _fields_ = [
+        ("fx", C.c_float), ("fy", C.c_float), ("mx", C.c_float), ("my", C.c_float),
+        ("weightDepth", C.c_float), ("weightColor", C.c_float), ("distThres", C.c_float), ("normalThres", C.c_float),
+        ("sensorMaxDepth", C.c_float), ("colorGradientMin", C.c_float), ("colorThres", C.c_float), ("level", C.c_uint32),
+    ]
+
+
+class IcpStateRGBD(C.Structure):
+    _fields_ = [("icp", IcpState), ("angles", C.c_float * 3), ("translation", C.c_float * 3), ("pad", C.c_uint32 * 2)]
+
+
 def make_tracking_state(levels=3, outer=(8, 6, 4), inner=(1, 1, 1), dist=0.15, normal=0.97, angle_trans=1.0, dist_trans=1.0, early_out=0.01):
     """the reference's zParametersTrackingDefault.txt"""
     t = TrackingState()
@@ -193,6 +213,19 @@ def make_tracking_state(levels=3, outer=(8, 6, 4), inner=(1, 1, 1), dist=0.15, n
         t.s_distThres[i], t.s_normalThres[i] = dist, normal
         t.s_angleTransThres[i], t.s_distTransThres[i], t.s_residualEarlyOut[i] = angle_trans, dist_trans, early_out
     t.numLevelsFound = levels
+    return t
+
+
+def make_tracking_state_rgbd(levels=3, weights_depth=(1.0, 0.5, 0.5), weights_color=(0.0, 0.5, 0.5), color_gradient_min=0.005, color_thres=0.1, **f5):
+    """the reference's zParametersTrackingDefault.txt with its colour keys (colour weight 0 on level 0, 0.5 above);
+    the f5 keys as make_tracking_state takes them"""
+    t = TrackingStateRGBD()
+    t.base = make_tracking_state(levels, **f5)
+    for i in range(8):  # VH_TRACKING_MAX_LEVELS; setDefault (DSC/GlobalCameraTrackingState.h:67-71) beyond the levels given
+        t.s_weightsDepth[i], t.s_weightsColor[i], t.s_colorGradientMin[i], t.s_colorThres[i] = 1.0, 1.0, 0.005, 0.1
+    for i in range(levels):
+        t.s_weightsDepth[i], t.s_weightsColor[i] = weights_depth[i], weights_color[i]
+        t.s_colorGradientMin[i], t.s_colorThres[i] = color_gradient_min, color_thres
     return t
 
 
