@@ -789,4 +789,60 @@ private:
     VhIcpStateRGBD m_lastState;
 };
 
+// ---------------------------------------------------------------------------
+// DX11RGBDRenderer (DSC/DX11RGBDRenderer.h): a depth map drawn as a mesh, two triangles per pixel quad, into four
+// screen-size maps.  The D3D pipeline becomes three compute passes (vh_view_raster / vh_view_resolve); the maps stay on
+// the device and are overwritten by the next call.
+class RGBDRenderer {
+public:
+    explicit RGBDRenderer(vhStream_t stream = nullptr);
+    ~RGBDRenderer();
+    RGBDRenderer(const RGBDRenderer&) = delete;
+    RGBDRenderer& operator=(const RGBDRenderer&) = delete;
+
+    // RenderDepthMap :197-275 minus the device context
+    void RenderDepthMap(const float* d_depthMap, const float* d_colorMap, unsigned int width, unsigned int height, const vh::mat4f& intrinsicDepthToWorld,
+                        const vh::mat4f& modelview, const vh::mat4f& intrinsicWorldToDepth, unsigned int screenWidth, unsigned int screenHeight,
+                        float depthThreshOffset, float depthThreshLin);
+    float* getDepth() const { return d_depth; }
+    float* getPositions() const { return d_positions; }
+    float* getNormals() const { return d_normals; }
+    float* getColors() const { return d_colors; }
+    unsigned int getWidth() const { return m_screenWidth; }
+    unsigned int getHeight() const { return m_screenHeight; }
+
+private:
+    void resize(unsigned int width, unsigned int height, unsigned int screenWidth, unsigned int screenHeight);
+    vhStream_t m_stream;
+    unsigned int m_width = 0, m_height = 0, m_screenWidth = 0, m_screenHeight = 0;
+    uint64_t* d_keys = nullptr;
+    uint32_t* d_largeList = nullptr;
+    float *d_depth = nullptr, *d_positions = nullptr, *d_normals = nullptr, *d_colors = nullptr;
+};
+
+// DX11PhongLighting (DSC/DX11PhongLighting.h): PhongPS over three float4 maps into a float4 target, and on request its
+// RGBA8 form as renderToFile writes it.  The light is the ConstantBufferLight (vh_phong_light_from_render_state).
+class PhongLighting {
+public:
+    explicit PhongLighting(const VhPhongLight& light, vhStream_t stream = nullptr);
+    ~PhongLighting();
+    PhongLighting(const PhongLighting&) = delete;
+    PhongLighting& operator=(const PhongLighting&) = delete;
+
+    // render(float4* d_positions, float4* d_normals, float4* d_colors, useMaterial, width, height) :42
+    void render(const float* d_positions, const float* d_normals, const float* d_colors, bool useMaterial, unsigned int width, unsigned int height,
+                bool rgba8 = false);
+    void setLight(const VhPhongLight& light) { m_light = light; }
+    const VhPhongLight& getLight() const { return m_light; }
+    float* getColors() const { return d_colors; }
+    uint8_t* getColorsRGBA8() const { return d_rgba8; }
+
+private:
+    VhPhongLight m_light;
+    vhStream_t m_stream;
+    unsigned int m_numPixels = 0;
+    float* d_colors = nullptr;
+    uint8_t* d_rgba8 = nullptr;
+};
+
 #endif // VH_HPP

@@ -567,6 +567,57 @@ int vh_marching_cubes_get_mesh(VhMarchingCubes* mc, float* vertices3, float* col
 /* saveMesh(filename, transform, overwriteExistingFile) .cpp:89-145; transform may be NULL */
 int vh_marching_cubes_save_mesh(VhMarchingCubes* mc, const char* filename, const float transform[16], int overwriteExistingFile);
 
+/* ---- shaded view of the model: DX11RGBDRenderer::RenderDepthMap + DX11PhongLighting::render as compute passes
+ * (csrc/vh_view.hip; DESIGN.md section 4, "Rendering").
+ * launcher level.  A depth map (width x height, one quad per pixel, two triangles per quad, primitive id 2 quad + t) is
+ * rasterised into a screen of 64-bit keys (float_bits(z) << 32 | primitive id, atomicMin = LESS with the first-drawn
+ * primitive winning ties); vh_view_resolve turns the keys into the four maps of RGBDRendererRawDepthPS.
+ *   d_keys       screenWidth * screenHeight uint64, all ones before the first raster (vh_memset 0xff); every resolve
+ *                leaves them so
+ *   d_largeList  vh_view_large_list_words(width, height) uint32, zero before the first raster; every resolve leaves it so
+ *   outputs      screen-size maps: depth (f32, clear -inf), position / normal / colour (float4, clear (-inf, -inf, -inf, 1))
+ * The colour map (float4, may be NULL for the raster) is the model's colours; both launchers must see the same depth map
+ * and params.  Screens narrower or lower than 2 pixels are rejected (the shader divides by screen size - 1). */
+uint32_t vh_view_large_list_words(uint32_t width, uint32_t height);
+int vh_view_raster(const float* d_depth, const VhViewParams* params, uint64_t* d_keys, uint32_t* d_largeList, vhStream_t stream);
+int vh_view_resolve(const float* d_depth, const float* d_color4, const VhViewParams* params, uint64_t* d_keys, uint32_t* d_largeList,
+                    float* d_outDepth, float* d_outPosition4, float* d_outNormal4, float* d_outColor4, vhStream_t stream);
+/* PhongPS (Shaders/PhongLighting.hlsl:49-86) on numPixels float4 maps.  out4 (float4) and/or outRGBA8 (D3D FLOAT->UNORM:
+ * NaN -> 0, clamp to [0, 1], x 255, round to nearest even) may be NULL; alphaRule sets the RGBA8 alpha to 255 where any
+ * of r, g, b is > 0 (renderToFile, DSC/DepthSensing.cpp:1199-1202). */
+int vh_phong(const float* d_positions4, const float* d_normals4, const float* d_colors4, uint32_t numPixels, int useMaterial, const VhPhongLight* light,
+             float* d_out4, uint8_t* d_outRGBA8, int alphaRule, vhStream_t stream);
+
+/* the rendering keys of a zParameters*.txt (VhRenderState); vh_phong_light_from_render_state is ConstantBufferLight::SetDefault */
+int vh_read_render_state(const char* filename, VhRenderState* out);
+int vh_parse_render_state(const char* text, VhRenderState* out);
+void vh_phong_light_from_render_state(const VhRenderState* rs, VhPhongLight* out);
+
+/* 8-bit RGBA, non-interlaced, lossless PNG of width x height pixels (row stride width * 4), deflated by the system zlib at
+ * `level` (0-9, or -1 for zlib's default). */
+int vh_write_png_rgba8(const char* filename, uint32_t width, uint32_t height, const uint8_t* rgba, int level);
+
+/* handle level: DX11RGBDRenderer (DSC/DX11RGBDRenderer.h) and DX11PhongLighting (DSC/DX11PhongLighting.h) without the D3D
+ * context.  The renderer owns its four screen maps and the key buffer; the Phong pass owns a float4 and an RGBA8 target. */
+typedef struct VhRGBDRenderer VhRGBDRenderer;
+int vh_rgbd_renderer_create(vhStream_t stream, VhRGBDRenderer** out);
+void vh_rgbd_renderer_destroy(VhRGBDRenderer* r);
+/* RenderDepthMap(d_depthMap, d_colorMap, width, height, intrinsicDepthToWorld, modelview, intrinsicWorldToDepth,
+ * screenWidth, screenHeight, depthThreshOffset, depthThreshLin) :197-275 */
+int vh_rgbd_renderer_render_depth_map(VhRGBDRenderer* r, const float* d_depthMap, const float* d_colorMap4, uint32_t width, uint32_t height,
+                                      const float intrinsicDepthToWorld[16], const float modelview[16], const float intrinsicWorldToDepth[16],
+                                      uint32_t screenWidth, uint32_t screenHeight, float depthThreshOffset, float depthThreshLin);
+/* the maps of the last RenderDepthMap (device pointers) and their size */
+int vh_rgbd_renderer_get_maps(VhRGBDRenderer* r, float** depth, float** positions4, float** normals4, float** colors4, uint32_t size[2]);
+typedef struct VhPhongLighting VhPhongLighting;
+int vh_phong_lighting_create(const VhPhongLight* light, vhStream_t stream, VhPhongLighting** out);
+void vh_phong_lighting_destroy(VhPhongLighting* p);
+/* render(d_positions, d_normals, d_colors, useMaterial, width, height) :42; the float4 target and, on request, its RGBA8
+ * form with renderToFile's alpha rule */
+int vh_phong_lighting_render(VhPhongLighting* p, const float* d_positions4, const float* d_normals4, const float* d_colors4, int useMaterial,
+                             uint32_t width, uint32_t height, int rgba8);
+int vh_phong_lighting_get_colors(VhPhongLighting* p, float** colors4, uint8_t** rgba8);
+
 #ifdef __cplusplus
 }
 #endif

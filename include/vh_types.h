@@ -401,6 +401,39 @@ typedef struct VhIcpStateRGBD {
     uint32_t pad[2];
 } VhIcpStateRGBD;
 
+/* The rendering block of a zParameters*.txt (DSC/GlobalAppState.h:60-100, zParametersDefault.txt:69-109) as filled by
+ * vh_read_render_state.  A key the file does not hold is value-initialised (0 / false / ""), as in VhAppState. */
+typedef struct VhRenderState {
+    float s_materialShininess;
+    float s_materialAmbient[4], s_materialDiffuse[4], s_materialSpecular[4];
+    float s_lightAmbient[4], s_lightDiffuse[4], s_lightSpecular[4];
+    float s_lightDirection[3];
+    uint32_t s_useColorForRendering;
+    float s_renderingDepthDiscontinuityThresOffset, s_renderingDepthDiscontinuityThresLin;
+    uint32_t s_renderToFile;
+    char s_renderToFileDir[256];
+    uint32_t numKeysFound; /* how many of the 13 members above the file held */
+} VhRenderState;
+
+/* DX11PhongLighting::ConstantBufferLight (DSC/DX11PhongLighting.h:12-37), the light and material of k_phong. */
+typedef struct VhPhongLight {
+    float lightAmbient[4], lightDiffuse[4], lightSpecular[4];
+    float lightDirection[3];
+    float materialShininess;
+    float materialAmbient[4], materialSpecular[4], materialDiffuse[4];
+} VhPhongLight;
+
+/* One RenderDepthMap call (DSC/DX11RGBDRenderer.h:197-275, cbRGBDRenderer of Shaders/RGBDRenderer.hlsl): the matrices
+ * row-major as the host holds them (the shader's mul(v, M) is M v). */
+typedef struct VhViewParams {
+    float intrinsicInverse[16]; /* depth pixel * d -> camera */
+    float modelview[16];        /* camera -> view */
+    float intrinsicNew[16];     /* view -> screen pixels */
+    uint32_t depthWidth, depthHeight, screenWidth, screenHeight;
+    float depthThreshOffset, depthThreshLin;
+    uint32_t pad[2];
+} VhViewParams;
+
 /* Error codes of the C ABI: 0 ok; <0 = -(hipError_t); >0 logical. */
 enum {
     VH_OK = 0,

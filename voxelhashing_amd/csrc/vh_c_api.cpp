@@ -610,4 +610,58 @@ int vh_camera_tracking_rgbd_apply_ct(VhCameraTrackingRGBD* t, float* d_input4, f
     });
 }
 
+// ---- DX11RGBDRenderer / DX11PhongLighting -------------------------------------------
+
+int vh_rgbd_renderer_create(vhStream_t stream, VhRGBDRenderer** out)
+{
+    if (!out) return VH_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    return guarded([&] { *out = new VhRGBDRenderer(stream); });
+}
+void vh_rgbd_renderer_destroy(VhRGBDRenderer* r) { delete r; }
+int vh_rgbd_renderer_render_depth_map(VhRGBDRenderer* r, const float* d_depthMap, const float* d_colorMap4, uint32_t width, uint32_t height,
+                                      const float intrinsicDepthToWorld[16], const float modelview[16], const float intrinsicWorldToDepth[16],
+                                      uint32_t screenWidth, uint32_t screenHeight, float depthThreshOffset, float depthThreshLin)
+{
+    if (!r || !intrinsicDepthToWorld || !modelview || !intrinsicWorldToDepth) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] {
+        r->impl.RenderDepthMap(d_depthMap, d_colorMap4, width, height, toMat(intrinsicDepthToWorld), toMat(modelview), toMat(intrinsicWorldToDepth),
+                               screenWidth, screenHeight, depthThreshOffset, depthThreshLin);
+    });
+}
+int vh_rgbd_renderer_get_maps(VhRGBDRenderer* r, float** depth, float** positions4, float** normals4, float** colors4, uint32_t size[2])
+{
+    if (!r) return VH_ERR_BAD_ARGUMENT;
+    if (depth) *depth = r->impl.getDepth();
+    if (positions4) *positions4 = r->impl.getPositions();
+    if (normals4) *normals4 = r->impl.getNormals();
+    if (colors4) *colors4 = r->impl.getColors();
+    if (size) {
+        size[0] = r->impl.getWidth();
+        size[1] = r->impl.getHeight();
+    }
+    return VH_OK;
+}
+
+int vh_phong_lighting_create(const VhPhongLight* light, vhStream_t stream, VhPhongLighting** out)
+{
+    if (!light || !out) return VH_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    return guarded([&] { *out = new VhPhongLighting(*light, stream); });
+}
+void vh_phong_lighting_destroy(VhPhongLighting* p) { delete p; }
+int vh_phong_lighting_render(VhPhongLighting* p, const float* d_positions4, const float* d_normals4, const float* d_colors4, int useMaterial,
+                             uint32_t width, uint32_t height, int rgba8)
+{
+    if (!p) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { p->impl.render(d_positions4, d_normals4, d_colors4, useMaterial == 1, width, height, rgba8 != 0); });
+}
+int vh_phong_lighting_get_colors(VhPhongLighting* p, float** colors4, uint8_t** rgba8)
+{
+    if (!p) return VH_ERR_BAD_ARGUMENT;
+    if (colors4) *colors4 = p->impl.getColors();
+    if (rgba8) *rgba8 = p->impl.getColorsRGBA8();
+    return VH_OK;
+}
+
 } // extern "C"

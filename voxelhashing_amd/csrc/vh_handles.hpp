@@ -17,6 +17,8 @@ struct VhSensorData { vh::SensorData impl; };
 struct VhSensorDataReader { vh::SensorDataReader impl; };
 struct VhCameraTracking { CUDACameraTrackingMultiRes impl; VhCameraTracking(unsigned int w, unsigned int h, unsigned int l, vhStream_t s) : impl(w, h, l, s) {} };
 struct VhCameraTrackingRGBD { CUDACameraTrackingMultiResRGBD impl; VhCameraTrackingRGBD(unsigned int w, unsigned int h, unsigned int l, vhStream_t s) : impl(w, h, l, s) {} };
+struct VhRGBDRenderer { RGBDRenderer impl; explicit VhRGBDRenderer(vhStream_t s) : impl(s) {} };
+struct VhPhongLighting { PhongLighting impl; VhPhongLighting(const VhPhongLight& l, vhStream_t s) : impl(l, s) {} };
 struct VhChunkGrid {
     CUDASceneRepChunkGrid impl;
     VhChunkGrid(CUDASceneRepHashSDF* s, const vh::vec3f& e, const vh::vec3i& d, const vh::vec3i& m, unsigned int l, bool en, unsigned int parts)

@@ -101,6 +101,17 @@ struct Reader {
         std::stringstream ss(t);
         ss >> out[0] >> out[1] >> out[2];
     }
+    void vec4(const char* name, float out[4]) // vec4f, the same way
+    {
+        std::string s;
+        out[0] = out[1] = out[2] = out[3] = 0.0f;
+        if (!get(name, s)) return;
+        std::string t;
+        for (char c : s)
+            if (c != 'f') t.push_back(c);
+        std::stringstream ss(t);
+        ss >> out[0] >> out[1] >> out[2] >> out[3];
+    }
 };
 
 void fill(const Values& values, VhAppState* out)
@@ -168,6 +179,27 @@ void fill(const Values& values, VhAppState* out)
     out->numKeysFound = r.found;
 }
 
+// the rendering block, DSC/GlobalAppState.h:60-100
+void fillRender(const Values& values, VhRenderState* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    Reader r{ values, 0 };
+    r.f32("s_materialShininess", out->s_materialShininess);
+    r.vec4("s_materialAmbient", out->s_materialAmbient);
+    r.vec4("s_materialDiffuse", out->s_materialDiffuse);
+    r.vec4("s_materialSpecular", out->s_materialSpecular);
+    r.vec4("s_lightAmbient", out->s_lightAmbient);
+    r.vec4("s_lightDiffuse", out->s_lightDiffuse);
+    r.vec4("s_lightSpecular", out->s_lightSpecular);
+    r.vec3("s_lightDirection", out->s_lightDirection);
+    r.boolean("s_useColorForRendering", out->s_useColorForRendering);
+    r.f32("s_renderingDepthDiscontinuityThresOffset", out->s_renderingDepthDiscontinuityThresOffset);
+    r.f32("s_renderingDepthDiscontinuityThresLin", out->s_renderingDepthDiscontinuityThresLin);
+    r.boolean("s_renderToFile", out->s_renderToFile);
+    r.text("s_renderToFileDir", out->s_renderToFileDir, sizeof(out->s_renderToFileDir));
+    out->numKeysFound = r.found;
+}
+
 const float kIdentity[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
 
 } // namespace
@@ -193,6 +225,41 @@ int vh_app_state_parse(const char* text, VhAppState* out)
     parseStream(in, values);
     fill(values, out);
     return VH_OK;
+}
+
+int vh_read_render_state(const char* filename, VhRenderState* out)
+{
+    if (!filename || !out) return VH_ERR_BAD_ARGUMENT;
+    std::ifstream f(filename);
+    if (!f.is_open()) return VH_ERR_IO;
+    Values values;
+    parseStream(f, values);
+    fillRender(values, out);
+    return VH_OK;
+}
+
+int vh_parse_render_state(const char* text, VhRenderState* out)
+{
+    if (!text || !out) return VH_ERR_BAD_ARGUMENT;
+    std::istringstream in(text);
+    Values values;
+    parseStream(in, values);
+    fillRender(values, out);
+    return VH_OK;
+}
+
+// DX11PhongLighting::ConstantBufferLight::SetDefault, DSC/DX11PhongLighting.h:25-36
+void vh_phong_light_from_render_state(const VhRenderState* rs, VhPhongLight* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    std::memcpy(out->lightAmbient, rs->s_lightAmbient, sizeof(out->lightAmbient));
+    std::memcpy(out->lightDiffuse, rs->s_lightDiffuse, sizeof(out->lightDiffuse));
+    std::memcpy(out->lightSpecular, rs->s_lightSpecular, sizeof(out->lightSpecular));
+    std::memcpy(out->lightDirection, rs->s_lightDirection, sizeof(out->lightDirection));
+    std::memcpy(out->materialAmbient, rs->s_materialAmbient, sizeof(out->materialAmbient));
+    std::memcpy(out->materialSpecular, rs->s_materialSpecular, sizeof(out->materialSpecular));
+    std::memcpy(out->materialDiffuse, rs->s_materialDiffuse, sizeof(out->materialDiffuse));
+    out->materialShininess = rs->s_materialShininess;
 }
 
 void vh_hash_params_from_app_state(const VhAppState* gas, VhHashParams* p)

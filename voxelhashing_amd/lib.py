@@ -145,6 +145,23 @@ PROTOTYPES = {
     "vh_camera_tracking_rgbd_destroy": (None, [_VP]),
     "vh_camera_tracking_rgbd_apply_ct": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, P(C.c_float), P(T.TrackingStateRGBD), P(C.c_float), P(T.DepthCameraParams),
                                                    P(C.c_float), P(C.c_int), P(T.IcpStateRGBD)]),
+    "vh_view_large_list_words": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "vh_view_raster": (C.c_int, [_VP, P(T.ViewParams), _VP, _VP, _VP]),
+    "vh_view_resolve": (C.c_int, [_VP, _VP, P(T.ViewParams), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "vh_phong": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_int, P(T.PhongLight), _VP, _VP, C.c_int, _VP]),
+    "vh_read_render_state": (C.c_int, [C.c_char_p, P(T.RenderState)]),
+    "vh_parse_render_state": (C.c_int, [C.c_char_p, P(T.RenderState)]),
+    "vh_phong_light_from_render_state": (None, [P(T.RenderState), P(T.PhongLight)]),
+    "vh_write_png_rgba8": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, _VP, C.c_int]),
+    "vh_rgbd_renderer_create": (C.c_int, [_VP, P(_VP)]),
+    "vh_rgbd_renderer_destroy": (None, [_VP]),
+    "vh_rgbd_renderer_render_depth_map": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, P(C.c_float), P(C.c_float), P(C.c_float), C.c_uint32,
+                                                    C.c_uint32, C.c_float, C.c_float]),
+    "vh_rgbd_renderer_get_maps": (C.c_int, [_VP, P(_VP), P(_VP), P(_VP), P(_VP), P(C.c_uint32)]),
+    "vh_phong_lighting_create": (C.c_int, [P(T.PhongLight), _VP, P(_VP)]),
+    "vh_phong_lighting_destroy": (None, [_VP]),
+    "vh_phong_lighting_render": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_uint32, C.c_uint32, C.c_int]),
+    "vh_phong_lighting_get_colors": (C.c_int, [_VP, P(_VP), P(_VP)]),
     "vh_app_state_read": (C.c_int, [C.c_char_p, P(T.AppState)]),
     "vh_app_state_parse": (C.c_int, [C.c_char_p, P(T.AppState)]),
     "vh_hash_params_from_app_state": (None, [P(T.AppState), P(T.HashParams)]),

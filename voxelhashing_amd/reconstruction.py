@@ -50,6 +50,72 @@ def read_tracking_state_rgbd(path_or_text):
     return t
 
 
+def read_render_state(path_or_text):
+    """the rendering keys of a zParameters*.txt (RenderState: light, material, discontinuity thresholds, s_renderToFile)"""
+    L = load()
+    r = T.RenderState()
+    if isinstance(path_or_text, bytes):
+        check(L.vh_parse_render_state(path_or_text, C.byref(r)), "vh_parse_render_state")
+    else:
+        check(L.vh_read_render_state(str(path_or_text).encode(), C.byref(r)), "vh_read_render_state")
+    return r
+
+
+def adapter_color_intrinsics(color_intrinsic, color_size, adapter_size):
+    """CUDARGBDAdapter's colour intrinsics (DSC/CUDARGBDAdapter.cpp:61-66): the sensor's, rescaled to the adapter size"""
+    m = np.array(color_intrinsic, dtype=np.float32).reshape(4, 4).copy()
+    (cw, ch), (W, H) = color_size, adapter_size
+    f = np.float32
+    m[0, 0] *= f(W) / f(cw)
+    m[1, 1] *= f(H) / f(ch)
+    m[0, 2] *= f(W - 1) / f(cw - 1) if cw > 1 else f(1)
+    m[1, 2] *= f(H - 1) / f(ch - 1) if ch > 1 else f(1)
+    return m
+
+
+def rgbx_alpha_rule(rgbx):
+    """renderToFile's alpha rule (DSC/DepthSensing.cpp:1199-1202): alpha = 255 where any of r, g, b is > 0"""
+    out = np.array(rgbx, dtype=np.uint8, copy=True)
+    out[(out[..., :3] > 0).any(axis=-1), 3] = 255
+    return out
+
+
+def depth_image_rgba8(depth):
+    """renderToFile's input_depth image: mLib's ColorImageR32G32B32A32(DepthImage) (baseImage.h:822-845; per-image min / max
+    over the values that are not -inf, hue 240 (1 - x), S = 1, V = 0.5, baseImageHelper.h:68-115), the alpha rule, 0 where
+    the depth is 0 or -inf, then FreeImageWrapper's (unsigned char)(255 c) per channel.  A NaN hue (every valid depth
+    equal) is taken as 0."""
+    f = np.float32
+    d = np.asarray(depth, dtype=np.float32)
+    valid = d != -np.inf
+    out = np.zeros(d.shape + (4,), dtype=np.float32)
+    if valid.any():
+        lo, hi = d[valid].min(), d[valid].max()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            x = f(1) - (d - lo) / (hi - lo)
+        x = np.where(x < 0, f(0), np.where(x > 1, f(1), x))
+        x = np.where(np.isnan(x), f(0), x).astype(np.float32)
+        hd = (f(240) * x) / f(60)
+        h = hd.astype(np.uint32)
+        fr = hd - h.astype(np.float32)
+        V = f(0.5)
+        p = V * (f(1) - f(1))
+        q = V * (f(1) - fr)
+        t = V * (f(1) - (f(1) - fr))
+        pp = np.full_like(q, p)
+        vv = np.full_like(q, V)
+        # convertHSVtoRGB: sector h of six, h > 4 (never reached for a hue <= 240) is (V, p, q)
+        cases = [((h == 0) | (h == 6), (vv, t, pp)), (h == 1, (q, vv, pp)), (h == 2, (pp, vv, t)), (h == 3, (pp, q, vv)), (h == 4, (t, pp, vv))]
+        rgb = np.stack((vv, pp, q), -1)
+        for cond, c in cases:
+            rgb = np.where(cond[..., None], np.stack(c, -1), rgb)
+        out[..., :3] = rgb
+        out[..., 3] = 1.0
+        out[~valid] = 0.0
+    out[(d == 0) | (d == -np.inf)] = 0.0
+    return (out * f(255)).astype(np.uint8)
+
+
 class Reconstruction:
     """One scene fed from `.sens` files.  `frame()` is one pass of the reference's render callback with
     reconstruction enabled: read a frame, pre-process it, ray-cast the model at the last pose, find the new pose
@@ -58,9 +124,14 @@ class Reconstruction:
     use_rgbd_tracking (off by default) is the reference's useRGBDTracking (DSC/DepthSensing.cpp:816): the pose comes
     from CUDACameraTrackingMultiResRGBD, fed with the sensor's colour map and the ray cast's colours as well.  Its
     tracking_state is then a TrackingStateRGBD (read_tracking_state_rgbd); a plain TrackingState keeps the colour keys'
-    defaults."""
+    defaults.
 
-    def __init__(self, app_state, tracking_state=None, sens_files=None, stream=None, use_rgbd_tracking=False):
+    render_state (a RenderState, read_render_state; None by default) carries the rendering keys.  When its
+    s_renderToFile is set, every frame read ends with the reference's renderToFile (DSC/DepthSensing.cpp:1150-1255):
+    the model ray-cast at the last pose, drawn as a mesh and lit, into s_renderToFileDir/reconstruction/%06d.png
+    (material) and reconstruction_color/%06d.png (colour), plus the input as input_color/ and input_depth/ images."""
+
+    def __init__(self, app_state, tracking_state=None, sens_files=None, stream=None, use_rgbd_tracking=False, render_state=None):
         self.L = load()
         self.gas = app_state
         self.tracking_rgbd = None
@@ -119,6 +190,13 @@ class Reconstruction:
         self.trajectory = []   # the pose every processed frame was integrated at (recordTrajectory)
         self.recorded = None
         self.lost_frames = 0
+        self.render_state = render_state
+        self.renderer = self.phong = None
+        if render_state is not None and render_state.s_renderToFile:
+            self.renderer = E.RGBDRenderer(stream=stream)
+            self.phong = E.PhongLighting(E.phong_light_from_render_state(render_state), stream=stream)
+            self.render_color_intrinsics = adapter_color_intrinsics(h.m_colorIntrinsic[:], (max(h.m_colorWidth, 1), max(h.m_colorHeight, 1)),
+                                                                    self.adapter_size)
 
     # -- the sensor side ------------------------------------------------------------------------------------------
     def _next_frame(self):
@@ -146,11 +224,17 @@ class Reconstruction:
     # -- reconstruction(), DepthSensing.cpp:720-924 ---------------------------------------------------------------
     def frame(self):
         """-> the camera-to-world pose the frame was integrated at, or None when the input is exhausted"""
-        g = self.gas
         got = self._next_frame()
         if got is None:
             return None
         depth, color = got
+        pose = self._reconstruct(depth, color)
+        if self.renderer is not None:
+            self.renderToFile(depth, color)
+        return pose
+
+    def _reconstruct(self, depth, color):
+        g = self.gas
         self.sensor.process(depth, color)
         self.frame_number += 1
         if g.s_recordData:
@@ -201,6 +285,29 @@ class Reconstruction:
         else:
             self.scene.setLastRigidTransformAndCompactify(transformation, self.cp)
         return self._done(np.ascontiguousarray(transformation, dtype=np.float32).reshape(4, 4))
+
+    def renderToFile(self, depth, color):
+        """DSC/DepthSensing.cpp:1159-1255 for the frame just processed: one raster of the ray cast, shaded twice"""
+        base = bytes(self.render_state.s_renderToFileDir).decode() or "."
+        dirs = {k: os.path.join(base, k) for k in ("input_color", "input_depth", "reconstruction", "reconstruction_color")}
+        for d in dirs.values():
+            os.makedirs(d, exist_ok=True)
+        last = self.scene.getLastRigidTransform()
+        self.scene.setLastRigidTransformAndCompactify(last, self.cp)
+        self.ray.render(self.scene.getHashData(), self.scene.getHashParams(), self.cp, last)
+        rd, rp = self.ray.getRayCastData(), self.ray.getRayCastParams()
+        W, H = self.adapter_size
+        rs = self.render_state
+        self.renderer.RenderDepthMap(rd.d_depth, rd.d_colors, rp.m_width, rp.m_height, np.array(rp.m_intrinsicsInverse[:], dtype=np.float32),
+                                     np.eye(4, dtype=np.float32), self.render_color_intrinsics, W, H, rs.s_renderingDepthDiscontinuityThresOffset,
+                                     rs.s_renderingDepthDiscontinuityThresLin)
+        m = self.renderer.getMaps()
+        name = "%06d.png" % self.frame_number
+        for colored, sub in ((False, "reconstruction"), (True, "reconstruction_color")):
+            self.phong.render(m["positions"], m["normals"], m["colors"], colored, W, H, rgba8=True)
+            E.write_png_rgba8(os.path.join(dirs[sub], name), self.phong.download(rgba8=True))
+        E.write_png_rgba8(os.path.join(dirs["input_color"], name), rgbx_alpha_rule(color))
+        E.write_png_rgba8(os.path.join(dirs["input_depth"], name), depth_image_rgba8(depth))
 
     def _done(self, pose):
         if self.gas.s_recordData:

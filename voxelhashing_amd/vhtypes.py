@@ -203,6 +203,45 @@ class IcpStateRGBD(C.Structure):
     _fields_ = [("icp", IcpState), ("angles", C.c_float * 3), ("translation", C.c_float * 3), ("pad", C.c_uint32 * 2)]
 
 
+class RenderState(C.Structure):
+    """VhRenderState: the rendering block of a zParameters*.txt"""
+    _fields_ = [
+        ("s_materialShininess", C.c_float), ("s_materialAmbient", C.c_float * 4), ("s_materialDiffuse", C.c_float * 4),
+        ("s_materialSpecular", C.c_float * 4), ("s_lightAmbient", C.c_float * 4), ("s_lightDiffuse", C.c_float * 4),
+        ("s_lightSpecular", C.c_float * 4), ("s_lightDirection", C.c_float * 3), ("s_useColorForRendering", C.c_uint32),
+        ("s_renderingDepthDiscontinuityThresOffset", C.c_float), ("s_renderingDepthDiscontinuityThresLin", C.c_float),
+        ("s_renderToFile", C.c_uint32), ("s_renderToFileDir", C.c_char * 256), ("numKeysFound", C.c_uint32),
+    ]
+
+
+class PhongLight(C.Structure):
+    """VhPhongLight: DX11PhongLighting::ConstantBufferLight"""
+    _fields_ = [
+        ("lightAmbient", C.c_float * 4), ("lightDiffuse", C.c_float * 4), ("lightSpecular", C.c_float * 4),
+        ("lightDirection", C.c_float * 3), ("materialShininess", C.c_float),
+        ("materialAmbient", C.c_float * 4), ("materialSpecular", C.c_float * 4), ("materialDiffuse", C.c_float * 4),
+    ]
+
+
+class ViewParams(C.Structure):
+    """VhViewParams: one RenderDepthMap call (matrices row-major)"""
+    _fields_ = [
+        ("intrinsicInverse", C.c_float * 16), ("modelview", C.c_float * 16), ("intrinsicNew", C.c_float * 16),
+        ("depthWidth", C.c_uint32), ("depthHeight", C.c_uint32), ("screenWidth", C.c_uint32), ("screenHeight", C.c_uint32),
+        ("depthThreshOffset", C.c_float), ("depthThreshLin", C.c_float), ("pad", C.c_uint32 * 2),
+    ]
+
+
+def make_view_params(intrinsic_inverse, modelview, intrinsic_new, depth_size, screen_size, thres_offset=0.012, thres_lin=0.001):
+    p = ViewParams()
+    for name, m in (("intrinsicInverse", intrinsic_inverse), ("modelview", modelview), ("intrinsicNew", intrinsic_new)):
+        getattr(p, name)[:] = [float(v) for v in np.asarray(m, dtype=np.float32).reshape(16)]
+    p.depthWidth, p.depthHeight = depth_size
+    p.screenWidth, p.screenHeight = screen_size
+    p.depthThreshOffset, p.depthThreshLin = thres_offset, thres_lin
+    return p
+
+
 def make_tracking_state(levels=3, outer=(8, 6, 4), inner=(1, 1, 1), dist=0.15, normal=0.97, angle_trans=1.0, dist_trans=1.0, early_out=0.01):
     """the reference's zParametersTrackingDefault.txt"""
     t = TrackingState()
