@@ -88,10 +88,40 @@ def build_system(inp, corr, corr_n, delta):
     return ata, atb, float(np.sum(wgt * dn * dn)), float(np.sum(wgt)), int(sel.sum())
 
 
+def pixel_terms(inp, corr, corr_n, delta):
+    """build_system's per-pixel contributions -> (H*W, 30) float64 in the kernel's term order (21 upper-triangle ATA
+    terms, 6 ATb, residual, weight, count), zero where a pixel has no correspondence; for error bounds on the sums"""
+    m = np.asarray(delta, dtype=np.float32).reshape(16)
+    h, w = inp.shape[:2]
+    sel = ((corr[..., 0] != MINF) & (inp[..., 0] != MINF) & (corr_n[..., 0] != MINF)).reshape(-1)
+    out = np.zeros((h * w, 30))
+    q = _mul_p(m, inp.reshape(-1, 4)[sel, :3]).astype(np.float64)
+    p, n = corr.reshape(-1, 4)[sel, :3].astype(np.float64), corr_n.reshape(-1, 4)[sel, :3].astype(np.float64)
+    wgt = corr_n.reshape(-1, 4)[sel, 3].astype(np.float64)
+    row = np.stack([n[:, 0] * q[:, 1] - n[:, 1] * q[:, 0], n[:, 2] * q[:, 0] - n[:, 0] * q[:, 2],
+                    n[:, 1] * q[:, 2] - n[:, 2] * q[:, 1], -n[:, 0], -n[:, 1], -n[:, 2]], 1)
+    b = np.sum(n * (q - p), axis=1)
+    at = 0
+    for r in range(6):
+        for c in range(r, 6):
+            out[sel, at + c - r] = wgt * row[:, r] * row[:, c]
+        at += 6 - r
+        out[sel, 21 + r] = wgt * row[:, r] * b
+    dn = np.sum((p - q) * n, axis=1)
+    out[sel, 27], out[sel, 28], out[sel, 29] = wgt * dn * dn, wgt, 1.0
+    return out
+
+
+def is_zero(ata):
+    """ATA.isZero() of a Matrix6x6f: every |a_ij| <= dummy_precision = 1e-5f (Core/CwiseNullaryOp.h:482-489); NaN is not zero"""
+    return bool(np.all(np.abs(np.asarray(ata, np.float32)) <= np.float32(1e-5)))
+
+
 def solve(ata, atb):
-    """JacobiSVD(ATA).solve(ATb) with Eigen's rank threshold; condition = s_max / s_min"""
+    """JacobiSVD(ATA).solve(ATb) with Eigen's rank threshold (rank() keeps s >= 6 eps s_max, SVD/JacobiSVD.h:683-691);
+    condition = s_max / s_min"""
     u, s, vt = np.linalg.svd(ata)
-    keep = s > 6.0 * np.finfo(np.float32).eps * s[0]
+    keep = (s >= 6.0 * np.finfo(np.float32).eps * s[0]) & (s > 0)
     x = (vt.T[:, keep] / s[keep]) @ (u.T[keep] @ atb)
     return x, float(s[0] / s[5]) if s[5] > 0 else float("inf")
 
@@ -127,7 +157,7 @@ def apply_ct(inp, inp_n, model, model_n, last_transform, ts, delta_estimate, cp,
                 ata, atb, err, wsum, ncorr = build_system(ins[level][0], corr, corr_n, delta.reshape(16))
                 info["iterations"] += 1
                 info.update(sumRegError=err, sumRegWeight=wsum, numCorr=ncorr)
-                if not np.any(ata):
+                if is_zero(ata):
                     return None, info
                 x, cond = solve(ata, atb)
                 info["matrixCondition"] = cond

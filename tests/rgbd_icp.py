@@ -352,7 +352,7 @@ def apply_ct(inp, inp_n, inp_col, model, model_n, model_col, last_transform, ts,
             info["iterations"] += 1
             info.update(sumRegError=float(t[27]), sumRegWeight=float(t[28]), numCorr=int(t[29]))
             ata, atb = terms_to_system(t)
-            if not np.any(t[:21]):
+            if icp.is_zero(t[:21]):  # ATA.isZero(): the 21 distinct entries of the symmetric ATA
                 return None, info
             x, cond = icp.solve(ata, atb)
             info["matrixCondition"] = cond

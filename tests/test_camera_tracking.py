@@ -136,10 +136,21 @@ class GpuRig:
 
 @pytest.mark.gpu
 def test_gpu_apply_ct_equals_oracle_and_ground_truth(vh, oracle_lib):
+    apply_ct_equals_oracle_and_ground_truth(oracle_lib, 160, 120)
+
+
+@pytest.mark.gpu
+@pytest.mark.slow
+def test_gpu_apply_ct_at_sensor_size(vh, oracle_lib):
+    """the same bar at 640x480, the size tools/bench_tracking.py measures: 400 wave partials per level-0 system"""
+    apply_ct_equals_oracle_and_ground_truth(oracle_lib, 640, 480)
+
+
+def apply_ct_equals_oracle_and_ground_truth(oracle_lib, W, H):
     from oracle import icp
     from voxelhashing_amd import engine as E
     O = oracle_lib
-    hp, cp, rp = setup_small()
+    hp, cp, rp = setup_small(W, H)
     poses = [synth.orbit_pose(k, n_frames=400) for k in range(4)]
     rig = GpuRig(E, hp, cp, rp)
     for p in poses[:3]:
@@ -227,3 +238,82 @@ def test_gpu_closed_loop_tracking_and_fusion(vh, oracle_lib):
     path = sum(pose_error(truth[k - 1], truth[k])[0] for k in range(1, len(truth)))
     assert dt < 0.01 and da < 0.3 and dt < 0.03 * path, (dt, da, path)  # < 1 cm / 0.3 degrees after 43 cm of motion
     assert rig.scene.getNumOccupiedBlocks() > 100
+
+
+def padded(a, n_pixels, fill):
+    """a (H, W, 4) map as a flat float32 array of n_pixels pixels: the pixels past W*H hold `fill`, a valid pixel, so a
+    build kernel that read past the image would add rows (and would still read inside its buffer)"""
+    flat = np.ascontiguousarray(a, np.float32).reshape(-1, 4)
+    out = np.empty((n_pixels, 4), np.float32)
+    out[:len(flat)] = flat
+    out[len(flat):] = fill
+    return out
+
+
+def assert_sums_within_float32_bound(got_terms, want, abs_sum, window, nP, what):
+    """every one of the 30 terms against the float64 sum of the per-pixel contributions, bounded by the float32 error of
+    its summation: a lane's window, the products that make a contribution (6 roundings), the in-order sum of nP
+    partials and the wave's 6-level tree with slack (8), each a relative 2^-24 of the sum of |contribution|"""
+    bound = (window + 6 + nP + 8) * 2.0 ** -24 * abs_sum
+    err = np.abs(np.asarray(got_terms, np.float64) - want)
+    assert np.all(err <= bound), (what, int(np.argmax(err - bound)), err.max(), bound[np.argmax(err - bound)])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,H", [(640, 480), (202, 154)])
+def test_gpu_icp_steps_match_oracle_on_every_level(vh, oracle_lib, W, H):
+    """correspondences with levelFactor 1, 2, 4 on the oracle's pyramid: bit-exact; the build step's wave row counts
+    exactly, its sums within the float32 bound of every term.  202x154 gives 101x77 and 50x38: odd widths and no level
+    a whole number of 64 * 12 pixel waves.  The target is the previous frame's own maps (launcher level: any float4
+    maps do)."""
+    from oracle import icp
+    from voxelhashing_amd import lib
+    O = oracle_lib
+    L = vh
+    cp = T.make_depth_camera_params(W, H)
+    poses = [synth.orbit_pose(k, n_frames=400) for k in range(3)]
+    _, cam, nrm = maps_for(O, TRACK_SPHERES, poses[2], cp)
+    _, tcam, tnrm = maps_for(O, TRACK_SPHERES, poses[1], cp)
+    ins = [(cam, nrm)] + icp.pyramid(cam, 3)
+    tgts = [(tcam, tnrm)] + icp.pyramid(tcam, 3)
+    up = lambda a: lib.DeviceBuffer.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    for tx in (0.0, 0.004):
+        delta = np.eye(4, dtype=np.float32)
+        delta[:3, 3] = [tx, -0.5 * tx, 0.25 * tx]  # translation only: the rotation stays exactly the identity
+        d_state, d_delta = lib.DeviceBuffer(C.sizeof(T.IcpState)), up(delta)
+        lib.check(L.vh_icp_begin(d_state.ptr, d_delta.ptr, None))
+        for level in range(3):
+            (i, inn), (t, tn) = ins[level], tgts[level]
+            h, w = i.shape[:2]
+            assert (w, h) == (W >> level, H >> level)
+            nP = L.vh_icp_num_partials(w, h)
+            assert nP == -(-(w * h) // (64 * 12))
+            npx = nP * 64 * 12
+            wc, wn = icp.correspondences(i, inn, t, tn, delta.reshape(16), 0.15, 0.97, float(2 ** level), cp)
+            ok = wc[..., 0] != MINF
+            assert ok.sum() > 0.2 * w * h, (level, ok.sum())
+            fill_c, fill_n = wc[ok][0], wn[ok][0]
+            fill_i = i[ok][0]
+            d_in, d_inn, d_t, d_tn = up(padded(i, npx, fill_i)), up(inn), up(t), up(tn)
+            d_c, d_cn = up(padded(wc, npx, fill_c)), up(padded(wn, npx, fill_n))
+            lib.check(L.vh_icp_projective_correspondences(d_in.ptr, d_inn.ptr, d_t.ptr, d_tn.ptr, d_c.ptr, d_cn.ptr, w, h, 0.15, 0.97,
+                                                          float(2 ** level), d_state.ptr, C.byref(cp), None))
+            corr = d_c.download(np.float32, npx * 4).reshape(npx, 4)
+            corr_n = d_cn.download(np.float32, npx * 4).reshape(npx, 4)
+            assert np.array_equal(corr[w * h:], padded(wc, npx, fill_c)[w * h:]), "correspondences wrote past the image"
+            corr, corr_n = corr[:w * h].reshape(h, w, 4), corr_n[:w * h].reshape(h, w, 4)
+            what = f"{W}x{H} level {level} tx {tx}"
+            assert np.array_equal(corr.view(np.uint32), wc.view(np.uint32)), what
+            assert np.array_equal(corr_n[..., :3].view(np.uint32), wn[..., :3].view(np.uint32)), what
+            # the pair weight goes through a division and cam_to_proj_z, written in another order: 1e-5 relative
+            assert np.allclose(corr_n[..., 3][ok], wn[..., 3][ok], rtol=1e-5, atol=1e-7), what
+            d_part = lib.DeviceBuffer(nP * 30 * 4)
+            lib.check(L.vh_icp_build_linear_system(w, h, d_part.ptr, d_in.ptr, d_c.ptr, d_cn.ptr, d_state.ptr, None))
+            part = d_part.download(np.float32, nP * 30).reshape(nP, 30)
+            contrib = icp.pixel_terms(i, corr, corr_n, delta.reshape(16))
+            padc = np.zeros((npx, 30))
+            padc[:w * h] = contrib
+            rows = padc[:, 29].reshape(nP, 64 * 12).sum(1)
+            assert np.array_equal(part[:, 29], rows.astype(np.float32)), what  # which pixels each wave summed: exactly
+            import icp_reference as R
+            assert_sums_within_float32_bound(R.reduce_partials(part), contrib.sum(0), np.abs(contrib).sum(0), 12, nP, what)

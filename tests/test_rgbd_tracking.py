@@ -299,8 +299,19 @@ def test_gpu_rgbd_build_step_matches_restatement(vh, oracle_lib):
 
 @pytest.mark.gpu
 def test_gpu_apply_ct_equals_restatement(vh, oracle_lib):
+    apply_ct_equals_restatement(160, 120)
+
+
+@pytest.mark.gpu
+@pytest.mark.slow
+def test_gpu_apply_ct_at_sensor_size(vh, oracle_lib):
+    """the same bar at 640x480, the size tools/bench_tracking.py --rgbd measures"""
+    apply_ct_equals_restatement(640, 480)
+
+
+def apply_ct_equals_restatement(W, H):
     from voxelhashing_amd import engine as E
-    cp = T.make_depth_camera_params(160, 120)
+    cp = T.make_depth_camera_params(W, H)
     rig = PlaneRig(E, cp)
     poses = [G.plane_pose(0.01 * k) for k in range(3)]
     # a voxel's colour is a running 50/50 average that starts from black (combineVoxel), so the model is integrated
@@ -406,3 +417,59 @@ def test_gpu_replay_with_rgbd_tracking(vh, oracle_lib, tmp_path):
     # the switch is off by default: the same files without it run the depth-only tracker
     out = json.loads(subprocess.check_output(cmd[:6] + cmd[7:9], timeout=600).decode().strip().splitlines()[-1])
     assert out["frames"] == len(truth) and out["pose_source"] == "projective ICP", out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,H", [(640, 480), (202, 154)])
+def test_gpu_rgbd_build_step_on_every_level(vh, oracle_lib, W, H):
+    """vh_icp_rgbd_build_linear_system on levels 0, 1, 2 (lane windows 12, 3, 1) of the restatement's pyramids, as applyCT
+    builds them: the number of waves against the reference's formula, the per-wave row counts exactly, every one of the
+    30 sums within the float32 error bound of its summation.  202x154 gives 101x77 and 50x38: odd widths, and no level
+    a whole number of waves.  The identity and a translation-only estimate keep the Euler angles exactly 0, so which
+    rows pair up is exact."""
+    from voxelhashing_amd import lib
+    from test_camera_tracking import assert_sums_within_float32_bound
+    cp = T.make_depth_camera_params(W, H)
+    _, _, (i, inn, ic), (m, mn, mc) = plane_maps(cp, 0.0, 0.02)
+    pyr = G.pyramids(i, inn, ic, m, mn, mc, 3)
+    ts = all_colour_settings()
+    up = lambda a: lib.DeviceBuffer.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    for tx in (0.0, 0.006):
+        delta = np.eye(4, dtype=np.float32)
+        delta[:3, 3] = [tx, 0.5 * tx, 0.0]
+        d_state = lib.DeviceBuffer(C.sizeof(T.IcpStateRGBD))
+        lib.check(vh.vh_icp_rgbd_begin(d_state.ptr, up(delta).ptr, None))
+        for level in range(3):
+            pi, pn, pii, pm, pmn, pmiad = pyr[level]
+            h, w = pi.shape[:2]
+            assert (w, h) == (W >> level, H >> level)
+            win = G.window(level)
+            assert win == (12, 3, 1)[level]
+            nP = vh.vh_icp_rgbd_num_partials(w, h, level)
+            # CUDABuildLinearSystemRGBD.cpp:31-35: max(1, 12 / (4 level)) above level 0, ceil(W H / (window 64)) in float
+            assert nP == int(np.ceil(np.float32(w * h) / np.float32(win * 64))), (level, nP)
+            npx = nP * 64 * win
+            p = G.level_params(ts, level, cp)
+            prm = T.IcpRGBDParams(fx=p["fx"], fy=p["fy"], mx=p["mx"], my=p["my"], weightDepth=p["weightDepth"], weightColor=p["weightColor"],
+                                  distThres=p["distThres"], normalThres=p["normalThres"], sensorMaxDepth=p["sensorMaxDepth"],
+                                  colorGradientMin=p["colorGradientMin"], colorThres=p["colorThres"], level=level)
+            dterm, cterm, dmask, cmask = G.pixel_terms(pi, pn, pii, pm, pmn, pmiad, np.zeros(3, np.float32), delta[:3, 3].copy(), p)
+            # at 50x38 the Gauss-filtered texture is too smooth for colour rows: there the depth rows carry the test
+            assert dmask.sum() > 0.3 * w * h and (cmask.sum() > 0.05 * w * h or w * h < 2000), (level, dmask.sum(), cmask.sum())
+            # past the image the inputs hold a pixel that pairs up: a kernel reading there would add rows
+            k = int(np.nonzero(dmask)[0][0])
+            pad = lambda a, c: np.concatenate([a.reshape(-1, c), np.repeat(a.reshape(-1, c)[k:k + 1], npx - w * h, 0)]) if npx > w * h else a.reshape(-1, c)
+            bufs = [up(pad(pi, 4)), up(pad(pn, 4)), up(pad(pii, 1)), up(pm), up(pmn), up(pmiad)]
+            d_part = lib.DeviceBuffer(nP * 30 * 4)
+            lib.check(vh.vh_icp_rgbd_build_linear_system(w, h, d_part.ptr, *[b.ptr for b in bufs], C.byref(prm), d_state.ptr, None))
+            part = d_part.download(np.float32, nP * 30).reshape(nP, 30)
+            want = G.build_partials(h, w, level, dterm, cterm)
+            what = f"{W}x{H} level {level} tx {tx}"
+            assert np.array_equal(part[:, 29], want[:, 29]), what
+            contrib = dterm.astype(np.float64) + cterm.astype(np.float64)
+            sign = np.ones(30)
+            sign[21:27] = -1.0  # the kernel subtracts the J^T F products
+            want_sum = (contrib * sign).sum(0)
+            abs_sum = np.abs(dterm.astype(np.float64)).sum(0) + np.abs(cterm.astype(np.float64)).sum(0)
+            import icp_reference as R
+            assert_sums_within_float32_bound(R.reduce_partials(part), want_sum, abs_sum, win, nP, what)

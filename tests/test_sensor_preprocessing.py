@@ -124,6 +124,27 @@ def test_gpu_exp_filters_match_oracle_within_tolerance(vh, oracle_lib, sigma_d, 
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("sigma_d", [0.5, 3.0, 4.0])  # radius ceil(2 sigma_d) = 1, 6, 8: all take the 32x8 tiled kernel
+def test_gpu_tiled_gauss_filter_on_ragged_tiles(vh, oracle_lib, sigma_d):
+    """vh_gauss_filter_float_map on images that are not a whole number of 32x8 tiles -- the sizes of the RGB-D
+    intensity pyramid at 202x154 (101x77, 50x38) and smaller ones down to one pixel: the halo past the right and
+    bottom edges must be skipped like the reference's bounds test.  Validity exactly, values to 1e-5 relative (the
+    weights' expf, as in test_gpu_exp_filters_match_oracle_within_tolerance)."""
+    from voxelhashing_amd import engine as E
+    O = oracle_lib
+    for k, (w, h) in enumerate(((101, 77), (50, 38), (33, 9), (7, 5), (1, 1))):
+        depth = make_depth(w, h, 20 + k, holes=0.1 if w * h > 1 else 0.0)
+        for sigma_r in (0.1, 10.0):  # 10: every valid tap in the window counts
+            a = E.image_op("gauss_filter_float_map", depth, w, h, sigma_d, sigma_r)
+            b = O.image_op("gauss_filter_float_map", depth, w, h, sigma_d, sigma_r)
+            what = f"{w}x{h} sigma_d {sigma_d} sigma_r {sigma_r}"
+            assert np.array_equal(a == MINF, b == MINF), what
+            ok = b != MINF
+            assert ok.any(), what
+            assert np.allclose(a[ok], b[ok], rtol=1e-5, atol=0.0), f"{what}: max rel {np.max(np.abs(a[ok] - b[ok]) / np.abs(b[ok])):.2e}"
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("filt", [False, True])
 def test_gpu_sensor_pipeline_feeds_integrate(vh, oracle_lib, filt):
     """CUDARGBDSensor::process == the oracle's steps in the reference's order; its DepthCameraData drives integrate()"""

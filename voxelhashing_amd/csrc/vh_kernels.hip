@@ -3489,7 +3489,7 @@ VHD float icp_sum_term(const float* partials, uint32_t nPartials, uint32_t t)
 }
 
 // The 6x6 symmetric system solved through its eigen-decomposition (cyclic Jacobi, double precision):
-// x = V diag(1/l_i) V^T b with eigenvalues below 6 eps * l_max dropped, which is what Eigen's JacobiSVD::solve returns
+// x = V diag(1/l_i) V^T b with eigenvalues below 6 eps * l_max (and exact zeros) dropped, which is what Eigen's JacobiSVD::solve returns
 // for a symmetric positive semi-definite matrix.  A is destroyed; returns the condition number l_max / l_min.
 VHD float icp_solve_6x6(double (&A)[6][6], const double (&b)[6], double (&xs)[6])
 {
@@ -3532,7 +3532,9 @@ VHD float icp_solve_6x6(double (&A)[6][6], const double (&b)[6], double (&xs)[6]
     for (int k = 0; k < 6; k++) xs[k] = 0.0;
     for (int i = 0; i < 6; i++) {
         const double l = fabs(A[i][i]);
-        if (l <= 6.0 * 1.1920928955078125e-7 * lmax) continue; // rank decision of JacobiSVD (threshold = diagSize * epsilon)
+        // JacobiSVD::rank() (SVD/JacobiSVD.h:683-691, threshold() :733-738): a singular value counts unless it is exactly
+        // zero or strictly below diagSize * epsilon * s_0; one sitting on the threshold is kept
+        if (l == 0.0 || l < 6.0 * 1.1920928955078125e-7 * lmax) continue;
         double proj = 0.0;
         for (int k = 0; k < 6; k++) proj += V[k][i] * b[k];
         proj /= A[i][i];
@@ -3541,7 +3543,10 @@ VHD float icp_solve_6x6(double (&A)[6][6], const double (&b)[6], double (&xs)[6]
     return (float)(lmax / lmin);
 }
 
-// The 30 summed terms -> A (both triangles), b; false when every term of A is zero (ATA.isZero())
+// The 30 summed terms -> A (both triangles), b; false when ATA.isZero(): Eigen's DenseBase::isZero with the default
+// dummy_precision of float (Core/CwiseNullaryOp.h:482-489, Core/MathFunctions.h:653-657, Core/NumTraits.h:94), i.e.
+// |a_ij| <= 1e-5f for every entry.  A NaN entry is not "zero" (the comparison is false): the solve goes on and the
+// rigidity check rejects the NaN step.
 VHD bool icp_system_from_terms(const float* terms, double (&A)[6][6], double (&b)[6])
 {
     uint32_t at = 0;
@@ -3549,7 +3554,7 @@ VHD bool icp_system_from_terms(const float* terms, double (&A)[6][6], double (&b
     for (uint32_t r = 0; r < 6u; r++) {
         for (uint32_t c = r; c < 6u; c++) {
             A[r][c] = A[c][r] = (double)terms[at + c - r];
-            if (terms[at + c - r] != 0.0f) zero = false;
+            if (!(fabsf(terms[at + c - r]) <= 1e-5f)) zero = false;
         }
         at += 6u - r;
         b[r] = (double)terms[21u + r];
@@ -3575,7 +3580,7 @@ __global__ __launch_bounds__(64) void k_icp_solve(VhIcpState* st, const float* p
         st->sumRegWeight = sTerms[28];
         st->numCorr = (uint32_t)sTerms[29];
         st->iterations += 1u;
-        if (!nonzero) { st->lost = 1u; return; } // ATA.isZero(): no correspondence at all
+        if (!nonzero) { st->lost = 1u; return; } // ATA.isZero(): every |a_ij| <= 1e-5
     }
     double xs[6];
     st->matrixCondition = icp_solve_6x6(A, b, xs);
