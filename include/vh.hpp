@@ -700,6 +700,15 @@ public:
     void process(const float* h_depthFloat, const unsigned char* h_colorRGBX); // CUDARGBDSensor::process :147 (blocks until done)
     void setFiterDepthValues(bool b = true, float sigmaD = 1.0f, float sigmaR = 1.0f);     // (sic) .h:37
     void setFiterIntensityValues(bool b = true, float sigmaD = 1.0f, float sigmaR = 1.0f); // (sic) .h:40
+    // s_bUseCameraCalibration (CUDARGBDSensor.cpp:198-217): process() renders the depth map into the colour camera
+    // (RenderDepthMap with the adapter's inverse depth intrinsics, depthExtrinsics as the modelview and the adapter's
+    // colour intrinsics; render target 0 into d_depthData).  Colour intrinsics at the colour sensor's resolution.  An
+    // identity extrinsic leaves it off ("already aligned", RGBDSensor.cpp:150-153).  The DepthCameraParams keep the depth
+    // intrinsics, as in the reference (.cpp:133-140).
+    void setCameraCalibration(bool enabled, float colorFx, float colorFy, float colorMx, float colorMy, const vh::mat4f& depthExtrinsics,
+                              float thresOffset, float thresLin);
+    bool getCameraCalibration() const { return m_bUseCameraCalibration; } // what took effect
+    const VhViewParams& getRemapParams() const { return m_remapParams; }
 
     const DepthCameraData& getDepthCameraData() const { return m_depthCameraData; }       // .h:78
     const DepthCameraParams& getDepthCameraParams() const { return m_depthCameraParams; } // .h:82
@@ -724,6 +733,10 @@ private:
     unsigned char* d_colorMapRaw;
     float *d_colorMapFloat4, *d_colorMapResampledFloat4, *d_cameraSpaceFloat4, *d_normalMapFloat4;
     float *d_depthData, *d_colorData; // what m_depthCameraData points to
+    bool m_bUseCameraCalibration = false;
+    VhViewParams m_remapParams;          // the RenderDepthMap arguments of the remap
+    uint64_t* d_remapKeys = nullptr;     // adapter-size key buffer, all ones between frames
+    uint32_t* d_remapLargeList = nullptr; // vh_view_large_list_words(adapter size), counter 0 between frames
 };
 
 

@@ -425,6 +425,20 @@ int vh_rgbd_sensor_get_depth_camera_data(VhRGBDSensor* s, VhDepthCameraData* out
 int vh_rgbd_sensor_get_depth_camera_params(VhRGBDSensor* s, VhDepthCameraParams* out);
 /* device maps at adapter resolution: {camera space float4, normals float4, intensity float} */
 int vh_rgbd_sensor_get_maps(VhRGBDSensor* s, float** d_cameraSpace4, float** d_normals4, float** d_intensity);
+/* s_bUseCameraCalibration (DSC/CUDARGBDSensor.cpp:198-217): process() renders the (filtered) depth map into the colour
+ * camera with vh_view_raster + vh_view_resolve_depth instead of copying it.  colorIntrinsics = {fx, fy, mx, my} at the
+ * colour sensor's resolution; depthExtrinsics (row-major) is the modelview; the thresholds are
+ * s_remappingDepthDiscontinuityThres{Offset,Lin}.  An identity extrinsic leaves it off (RGBDSensor.cpp:150-153). */
+int vh_rgbd_sensor_set_camera_calibration(VhRGBDSensor* s, int enabled, const float colorIntrinsics[4], const float depthExtrinsics[16],
+                                          float thresOffset, float thresLin);
+/* host only: the VhViewParams of that remap.  sizes as vh_rgbd_sensor_create's; depthIntrinsics / colorIntrinsics =
+ * {fx, fy, mx, my} at the sensors' resolutions.  The adapter rescales both to the adapter size; intrinsicInverse is
+ * the inverse of the adapter's depth intrinsics (cofactors, mLib's order), modelview the extrinsic as given, screen =
+ * depth map = adapter size. */
+int vh_rgbd_sensor_remap_params(const uint32_t sizes[6], const float depthIntrinsics[4], const float colorIntrinsics[4], const float depthExtrinsics[16],
+                                float thresOffset, float thresLin, VhViewParams* out);
+/* whether the remap is on, and the VhViewParams process() draws with (adapter matrices; may be NULL) */
+int vh_rgbd_sensor_get_camera_calibration(VhRGBDSensor* s, int* enabled, VhViewParams* params);
 
 /* ---- recorded sequences: the `.sens` container and its reader.
  *   VhSensorData        ml::SensorData (load / save / frames)          DSC/sensorData/sensorData.h:608-830
@@ -582,6 +596,10 @@ uint32_t vh_view_large_list_words(uint32_t width, uint32_t height);
 int vh_view_raster(const float* d_depth, const VhViewParams* params, uint64_t* d_keys, uint32_t* d_largeList, vhStream_t stream);
 int vh_view_resolve(const float* d_depth, const float* d_color4, const VhViewParams* params, uint64_t* d_keys, uint32_t* d_largeList,
                     float* d_outDepth, float* d_outPosition4, float* d_outNormal4, float* d_outColor4, vhStream_t stream);
+/* render target 0 alone: the depth map of vh_view_resolve (the source depth interpolated, -inf where nothing is drawn)
+ * written into d_outDepth, with the same key / list reset.  CUDARGBDSensor's remap into the colour camera.  d_outDepth
+ * is screen size and must not be the source depth map. */
+int vh_view_resolve_depth(const float* d_depth, const VhViewParams* params, uint64_t* d_keys, uint32_t* d_largeList, float* d_outDepth, vhStream_t stream);
 /* PhongPS (Shaders/PhongLighting.hlsl:49-86) on numPixels float4 maps.  out4 (float4) and/or outRGBA8 (D3D FLOAT->UNORM:
  * NaN -> 0, clamp to [0, 1], x 255, round to nearest even) may be NULL; alphaRule sets the RGBA8 alpha to 255 where any
  * of r, g, b is > 0 (renderToFile, DSC/DepthSensing.cpp:1199-1202). */
@@ -591,6 +609,9 @@ int vh_phong(const float* d_positions4, const float* d_normals4, const float* d_
 /* the rendering keys of a zParameters*.txt (VhRenderState); vh_phong_light_from_render_state is ConstantBufferLight::SetDefault */
 int vh_read_render_state(const char* filename, VhRenderState* out);
 int vh_parse_render_state(const char* text, VhRenderState* out);
+/* the camera-calibration keys of a zParameters*.txt (VhCalibrationState), read by the same rules */
+int vh_read_calibration_state(const char* filename, VhCalibrationState* out);
+int vh_parse_calibration_state(const char* text, VhCalibrationState* out);
 void vh_phong_light_from_render_state(const VhRenderState* rs, VhPhongLight* out);
 
 /* 8-bit RGBA, non-interlaced, lossless PNG of width x height pixels (row stride width * 4), deflated by the system zlib at

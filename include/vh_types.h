@@ -415,6 +415,14 @@ typedef struct VhRenderState {
     uint32_t numKeysFound; /* how many of the 13 members above the file held */
 } VhRenderState;
 
+/* The camera-calibration keys of a zParameters*.txt (DSC/GlobalAppState.h:82-85, zParametersDefault.txt:86-89) as
+ * filled by vh_read_calibration_state.  Absent keys are value-initialised, as in VhAppState. */
+typedef struct VhCalibrationState {
+    uint32_t s_bUseCameraCalibration;
+    float s_remappingDepthDiscontinuityThresOffset, s_remappingDepthDiscontinuityThresLin;
+    uint32_t numKeysFound; /* how many of the 3 members above the file held */
+} VhCalibrationState;
+
 /* DX11PhongLighting::ConstantBufferLight (DSC/DX11PhongLighting.h:12-37), the light and material of k_phong. */
 typedef struct VhPhongLight {
     float lightAmbient[4], lightDiffuse[4], lightSpecular[4];

@@ -3,11 +3,13 @@
 parameter file, optional mesh at the end) and prints one JSON line with the timing.
 
     python tools/replay.py --params zParameters.txt [--tracking zParametersTracking.txt] [--rgbd-tracking] [--sens a.sens b.sens]
-                           [--mesh scan.ply] [--max-frames N] [--record out.sens] [--render-to DIR]
+                           [--mesh scan.ply] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
 
 Without --sens the files named by s_binaryDumpSensorFile[i] in the parameter file are played.  The rendering keys
 (light, material, discontinuity thresholds, s_renderToFile, s_renderToFileDir) come from --params; --render-to switches
-s_renderToFile on and writes the images under DIR."""
+s_renderToFile on and writes the images under DIR.  The camera-calibration keys (s_bUseCameraCalibration and the
+remapping thresholds) come from --params too; --camera-calibration switches s_bUseCameraCalibration on, so the depth
+map is rendered into the colour camera with the `.sens` file's extrinsic (unless that is the identity)."""
 import argparse
 import json
 import os
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--record", default=None, help="write what was processed, with the poses used, to this .sens file")
     ap.add_argument("--max-frames", type=int, default=None)
     ap.add_argument("--render-to", default=None, help="renderToFile: the shaded model and the input of every frame as PNGs under this directory")
+    ap.add_argument("--camera-calibration", action="store_true", help="s_bUseCameraCalibration: remap depth into the colour camera")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -42,7 +45,10 @@ def main():
     if args.render_to:
         rs.s_renderToFile = 1
         rs.s_renderToFileDir = args.render_to.encode()
-    rec = R.Reconstruction(g, t, args.sens or None, use_rgbd_tracking=args.rgbd_tracking, render_state=rs)
+    cs = R.read_calibration_state(args.params)
+    if args.camera_calibration:
+        cs.s_bUseCameraCalibration = 1
+    rec = R.Reconstruction(g, t, args.sens or None, use_rgbd_tracking=args.rgbd_tracking, render_state=rs, calibration_state=cs)
     t0 = time.perf_counter()
     n = rec.run(args.max_frames)
     rec.scene.synchronize()
@@ -50,6 +56,8 @@ def main():
     out = dict(frames=n, seconds=round(dt, 3), frames_per_s=round(n / dt, 1) if dt > 0 else None, lost_frames=rec.lost_frames,
                blocks=rec.scene.getNumOccupiedBlocks(), heap_free=rec.scene.getHeapFreeCount(),
                pose_source="recorded trajectory" if g.s_binaryDumpSensorUseTrajectory and not g.s_binaryDumpSensorUseTrajectoryOnlyInit else ("RGB-D ICP" if args.rgbd_tracking else "projective ICP"))
+    if cs.s_bUseCameraCalibration:
+        out["camera_calibration"] = rec.camera_calibration
     if rs.s_renderToFile:
         out["render_to"] = bytes(rs.s_renderToFileDir).decode()
     if args.record:

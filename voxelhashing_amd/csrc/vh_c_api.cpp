@@ -562,6 +562,23 @@ int vh_rgbd_sensor_get_maps(VhRGBDSensor* s, float** d_cameraSpace4, float** d_n
     return VH_OK;
 }
 
+int vh_rgbd_sensor_set_camera_calibration(VhRGBDSensor* s, int enabled, const float colorIntrinsics[4], const float depthExtrinsics[16],
+                                          float thresOffset, float thresLin)
+{
+    if (!s || !colorIntrinsics || !depthExtrinsics) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] {
+        s->impl.setCameraCalibration(enabled != 0, colorIntrinsics[0], colorIntrinsics[1], colorIntrinsics[2], colorIntrinsics[3], toMat(depthExtrinsics),
+                                     thresOffset, thresLin);
+    });
+}
+int vh_rgbd_sensor_get_camera_calibration(VhRGBDSensor* s, int* enabled, VhViewParams* params)
+{
+    if (!s) return VH_ERR_BAD_ARGUMENT;
+    if (enabled) *enabled = s->impl.getCameraCalibration() ? 1 : 0;
+    if (params) *params = s->impl.getRemapParams();
+    return VH_OK;
+}
+
 // ---- CUDACameraTrackingMultiRes -----------------------------------------------------
 
 int vh_camera_tracking_create(uint32_t imageWidth, uint32_t imageHeight, uint32_t levels, vhStream_t stream, VhCameraTracking** out)

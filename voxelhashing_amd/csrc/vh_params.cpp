@@ -200,6 +200,17 @@ void fillRender(const Values& values, VhRenderState* out)
     out->numKeysFound = r.found;
 }
 
+// the camera-calibration keys, DSC/GlobalAppState.h:82-85
+void fillCalibration(const Values& values, VhCalibrationState* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    Reader r{ values, 0 };
+    r.boolean("s_bUseCameraCalibration", out->s_bUseCameraCalibration);
+    r.f32("s_remappingDepthDiscontinuityThresOffset", out->s_remappingDepthDiscontinuityThresOffset);
+    r.f32("s_remappingDepthDiscontinuityThresLin", out->s_remappingDepthDiscontinuityThresLin);
+    out->numKeysFound = r.found;
+}
+
 const float kIdentity[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
 
 } // namespace
@@ -249,6 +260,27 @@ int vh_parse_render_state(const char* text, VhRenderState* out)
 }
 
 // DX11PhongLighting::ConstantBufferLight::SetDefault, DSC/DX11PhongLighting.h:25-36
+int vh_read_calibration_state(const char* filename, VhCalibrationState* out)
+{
+    if (!filename || !out) return VH_ERR_BAD_ARGUMENT;
+    std::ifstream f(filename);
+    if (!f.is_open()) return VH_ERR_IO;
+    Values values;
+    parseStream(f, values);
+    fillCalibration(values, out);
+    return VH_OK;
+}
+
+int vh_parse_calibration_state(const char* text, VhCalibrationState* out)
+{
+    if (!text || !out) return VH_ERR_BAD_ARGUMENT;
+    std::istringstream in(text);
+    Values values;
+    parseStream(in, values);
+    fillCalibration(values, out);
+    return VH_OK;
+}
+
 void vh_phong_light_from_render_state(const VhRenderState* rs, VhPhongLight* out)
 {
     std::memset(out, 0, sizeof(*out));

@@ -1,7 +1,9 @@
 // vh_sensor.cpp -- the per-frame image path between a depth sensor and integrate(): CUDARGBDAdapter::process
 // (DSC/CUDARGBDAdapter.cpp:93-137) followed by CUDARGBDSensor::process (DSC/CUDARGBDSensor.cpp:147-257), as one
 // host class over the kernels of vh_kernels.hip ("sensor pre-processing").  The D3D11 remapping branch
-// (s_bUseCameraCalibration, :198-217) and the disabled erosion loop (:224-237) are not part of it.
+// (s_bUseCameraCalibration, :198-217) is the depth map drawn into the colour camera by the view passes of vh_view.hip
+// (vh_view_raster + vh_view_resolve_depth, render target 0 straight into d_depthData); setCameraCalibration switches it
+// on.  The disabled erosion loop (:224-237) is not part of it.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -20,6 +22,38 @@ inline void checkHip(hipError_t e, const char* what)
 }
 template <class T> void devAlloc(T*& p, size_t n, const char* what) { checkHip(hipMalloc((void**)&p, sizeof(T) * (n ? n : 1)), what); }
 } // namespace
+
+extern "C" int vh_rgbd_sensor_remap_params(const uint32_t sizes[6], const float depthIntrinsics[4], const float colorIntrinsics[4],
+                                           const float depthExtrinsics[16], float thresOffset, float thresLin, VhViewParams* out)
+{
+    if (!sizes || !depthIntrinsics || !colorIntrinsics || !depthExtrinsics || !out) return VH_ERR_BAD_ARGUMENT;
+    for (int i = 0; i < 6; i++)
+        if (sizes[i] < 2) return VH_ERR_BAD_ARGUMENT;
+    const uint32_t dw = sizes[0], dh = sizes[1], cw = sizes[2], ch = sizes[3], W = sizes[4], H = sizes[5];
+    // the adapter's intrinsics (DSC/CUDARGBDAdapter.cpp:54-66): the sensor's, rescaled to the adapter size.  The depth
+    // ones are the constructor's DepthCameraParams, bit for bit.
+    vh::mat4f depthK = vh::mat4f::identity(), colorK = vh::mat4f::identity();
+    depthK.m[0] = depthIntrinsics[0] * ((float)W / (float)dw);
+    depthK.m[5] = depthIntrinsics[1] * ((float)H / (float)dh);
+    depthK.m[2] = depthIntrinsics[2] * ((float)(W - 1) / (float)(dw - 1));
+    depthK.m[6] = depthIntrinsics[3] * ((float)(H - 1) / (float)(dh - 1));
+    colorK.m[0] = colorIntrinsics[0] * ((float)W / (float)cw);
+    colorK.m[5] = colorIntrinsics[1] * ((float)H / (float)ch);
+    colorK.m[2] = colorIntrinsics[2] * ((float)(W - 1) / (float)(cw - 1));
+    colorK.m[6] = colorIntrinsics[3] * ((float)(H - 1) / (float)(ch - 1));
+    // getDepthIntrinsicsInv(): mLib's Matrix4x4::getInverse, the same cofactors in the same order as mat4f::getInverse
+    const vh::mat4f depthKInv = depthK.getInverse();
+    VhViewParams& p = *out;
+    std::memset(&p, 0, sizeof(p));
+    std::memcpy(p.intrinsicInverse, depthKInv.m, sizeof(p.intrinsicInverse));
+    std::memcpy(p.modelview, depthExtrinsics, sizeof(p.modelview)); // getDepthExtrinsics(), not its inverse
+    std::memcpy(p.intrinsicNew, colorK.m, sizeof(p.intrinsicNew));
+    p.depthWidth = p.screenWidth = W; // the custom render target is the adapter size (CUDARGBDSensor.cpp:130-131)
+    p.depthHeight = p.screenHeight = H;
+    p.depthThreshOffset = thresOffset;
+    p.depthThreshLin = thresLin;
+    return VH_OK;
+}
 
 CUDARGBDSensor::CUDARGBDSensor(const Config& c, vhStream_t stream) : m_cfg(c), m_stream(stream), m_frameNumber(0)
 {
@@ -44,6 +78,7 @@ CUDARGBDSensor::CUDARGBDSensor(const Config& c, vhStream_t stream) : m_cfg(c), m
     d_colorMapRaw = nullptr;
     d_colorMapFloat4 = d_colorMapResampledFloat4 = d_cameraSpaceFloat4 = d_normalMapFloat4 = nullptr;
     std::memset(&m_depthCameraData, 0, sizeof(m_depthCameraData));
+    std::memset(&m_remapParams, 0, sizeof(m_remapParams));
     devAlloc(d_depthMapFloat, nDepthIn, "d_depthMapFloat");
     devAlloc(d_depthMapResampledFloat, nOut, "d_depthMapResampledFloat");
     devAlloc(d_colorMapRaw, 4 * nColorIn, "d_colorMapRaw");
@@ -68,7 +103,7 @@ CUDARGBDSensor::~CUDARGBDSensor()
 {
     (void)hipStreamSynchronize((hipStream_t)m_stream);
     void* all[] = { d_depthMapFloat, d_depthMapResampledFloat, d_colorMapRaw, d_colorMapFloat4, d_colorMapResampledFloat4, d_depthMapFilteredFloat,
-                    d_cameraSpaceFloat4, d_normalMapFloat4, d_intensityMapFilteredFloat, d_depthData, d_colorData };
+                    d_cameraSpaceFloat4, d_normalMapFloat4, d_intensityMapFilteredFloat, d_depthData, d_colorData, d_remapKeys, d_remapLargeList };
     for (void* p : all)
         if (p) (void)hipFree(p);
 }
@@ -80,6 +115,33 @@ void CUDARGBDSensor::setFiterDepthValues(bool b, float sigmaD, float sigmaR)
 void CUDARGBDSensor::setFiterIntensityValues(bool b, float sigmaD, float sigmaR)
 {
     m_bFilterIntensityValues = b; m_fBilateralFilterSigmaDIntensity = sigmaD; m_fBilateralFilterSigmaRIntensity = sigmaR;
+}
+
+void CUDARGBDSensor::setCameraCalibration(bool enabled, float colorFx, float colorFy, float colorMx, float colorMy, const vh::mat4f& depthExtrinsics,
+                                          float thresOffset, float thresLin)
+{
+    const Config& c = m_cfg;
+    const unsigned int W = c.adapterWidth, H = c.adapterHeight;
+    // mLib's operator==: entry by entry, exact.  Equal to the identity means already aligned: the remap stays off
+    bool identity = true;
+    const vh::mat4f I = vh::mat4f::identity();
+    for (int i = 0; i < 16; i++) identity = identity && depthExtrinsics.m[i] == I.m[i];
+    m_bUseCameraCalibration = false;
+    if (!enabled || identity) return;
+    const uint32_t sizes[6] = { c.depthWidth, c.depthHeight, c.colorWidth, c.colorHeight, W, H };
+    const float depthIntrinsics[4] = { c.fx, c.fy, c.mx, c.my }, colorIntrinsics[4] = { colorFx, colorFy, colorMx, colorMy };
+    check(vh_rgbd_sensor_remap_params(sizes, depthIntrinsics, colorIntrinsics, depthExtrinsics.m, thresOffset, thresLin, &m_remapParams), "remap params");
+    // allocated once, all ones and a zero counter: every resolve leaves them so
+    const hipStream_t s = (hipStream_t)m_stream;
+    if (!d_remapKeys) {
+        devAlloc(d_remapKeys, (size_t)W * H, "remap keys");
+        checkHip(hipMemsetAsync(d_remapKeys, 0xff, sizeof(uint64_t) * (size_t)W * H, s), "remap keys");
+    }
+    if (!d_remapLargeList) {
+        devAlloc(d_remapLargeList, vh_view_large_list_words(W, H), "remap list");
+        checkHip(hipMemsetAsync(d_remapLargeList, 0, sizeof(uint32_t), s), "remap list");
+    }
+    m_bUseCameraCalibration = true;
 }
 
 void CUDARGBDSensor::process(const float* h_depthFloat, const unsigned char* h_colorRGBX)
@@ -101,7 +163,12 @@ void CUDARGBDSensor::process(const float* h_depthFloat, const unsigned char* h_c
     if (m_bFilterDepthValues) check(vh_gauss_filter_float_map(d_depthMapFilteredFloat, d_depthMapResampledFloat, m_fBilateralFilterSigmaD, m_fBilateralFilterSigmaR, W, H, m_stream), "gaussFilterFloatMap");
     else check(vh_copy_float_map(d_depthMapFilteredFloat, d_depthMapResampledFloat, W, H, m_stream), "copyFloatMap");
     // (the reference also calls setInvalidFloatMap on d_depthData here and overwrites it right away, :188-219)
-    check(vh_copy_float_map(d_depthData, d_depthMapFilteredFloat, W, H, m_stream), "copyFloatMap");
+    if (m_bUseCameraCalibration) { // RenderDepthMap into the custom render target, then copyToCuda(d_depthData, 0)
+        check(vh_view_raster(d_depthMapFilteredFloat, &m_remapParams, d_remapKeys, d_remapLargeList, m_stream), "remap: raster");
+        check(vh_view_resolve_depth(d_depthMapFilteredFloat, &m_remapParams, d_remapKeys, d_remapLargeList, d_depthData, m_stream), "remap: resolve");
+    } else {
+        check(vh_copy_float_map(d_depthData, d_depthMapFilteredFloat, W, H, m_stream), "copyFloatMap");
+    }
     check(vh_convert_color_to_intensity_float(d_intensityMapFilteredFloat, d_colorData, W, H, m_stream), "convertColorToIntensityFloat");
     check(vh_convert_depth_float_to_camera_space_float4(d_cameraSpaceFloat4, d_depthData, &m_depthCameraParams, W, H, m_stream), "convertDepthFloatToCameraSpaceFloat4");
     check(vh_compute_normals(d_normalMapFloat4, d_cameraSpaceFloat4, W, H, m_stream), "computeNormals");

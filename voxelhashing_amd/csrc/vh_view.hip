@@ -13,6 +13,8 @@
 //   k_view_raster_large  one workgroup per listed triangle, its 256 lanes over the box.
 //   k_view_resolve       one lane per screen pixel: the winning primitive's vertices again (the same device function),
 //                        the four maps, and the key / list reset, so the next view needs no clear launch.
+//   k_view_resolve_depth the same lane and reset, render target 0 only (the source depth): CUDARGBDSensor's remap of
+//                        the depth map into the colour camera (s_bUseCameraCalibration).
 //   k_phong              one lane per pixel: PhongPS, float4 and/or RGBA8.
 //
 // MUST be compiled with -ffp-contract=off: the restatement is bit-exact only with every multiply and add rounded.
@@ -260,6 +262,31 @@ __global__ __launch_bounds__(256) void k_view_resolve(const float* depth, const 
     outColor[idx] = col;
 }
 
+// Render target 0 alone (RGBDRendererRawDepthPS's res.depth = In.fDepth, clear -inf), written straight into the
+// caller's map.  The vertices come from the same device function as above; with no colour and only X, Y and the source
+// depth read, the compiler drops the neighbour loads and the normal, so a covered pixel costs three depth-map taps.
+__global__ __launch_bounds__(256) void k_view_resolve_depth(const float* depth, VhViewParams p, uint64_t* keys, uint32_t* large, float* outDepth)
+{
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx == 0) large[0] = 0; // k_view_raster_large, the list's last reader, has finished
+    if (idx >= p.screenWidth * p.screenHeight) return;
+    const uint64_t key = keys[idx];
+    float d = -INFINITY;
+    if (key != kEmptyKey) {
+        keys[idx] = kEmptyKey;
+        ViewVertex v[3];
+        view_triangle_vertices(depth, nullptr, p, (uint32_t)key, v);
+        ViewTri tri;
+        view_setup(v, tri);
+        int64_t e[3];
+        view_cover(tri, (int64_t)(idx % p.screenWidth) * 256 + 128, (int64_t)(idx / p.screenWidth) * 256 + 128, e);
+        float b[3];
+        view_bary(tri, e, b);
+        d = interp(v[0].depth, v[1].depth, v[2].depth, b);
+    }
+    outDepth[idx] = d;
+}
+
 // ---------------------------------------------------------------------------
 // PhongPS, Shaders/PhongLighting.hlsl:49-86
 // ---------------------------------------------------------------------------
@@ -357,6 +384,14 @@ int vh_view_resolve(const float* d_depth, const float* d_color4, const VhViewPar
     k_view_resolve<<<cdiv(params->screenWidth * params->screenHeight, 256u), 256, 0, (hipStream_t)stream>>>(
         d_depth, reinterpret_cast<const float4*>(d_color4), *params, d_keys, d_largeList, d_outDepth, reinterpret_cast<float4*>(d_outPosition4),
         reinterpret_cast<float4*>(d_outNormal4), reinterpret_cast<float4*>(d_outColor4));
+    return vh_last_launch_error();
+}
+
+int vh_view_resolve_depth(const float* d_depth, const VhViewParams* params, uint64_t* d_keys, uint32_t* d_largeList, float* d_outDepth, vhStream_t stream)
+{
+    if (!d_depth || !d_keys || !d_largeList || !d_outDepth || d_outDepth == d_depth || !viewParamsValid(params)) return VH_ERR_BAD_ARGUMENT;
+    k_view_resolve_depth<<<cdiv(params->screenWidth * params->screenHeight, 256u), 256, 0, (hipStream_t)stream>>>(d_depth, *params, d_keys, d_largeList,
+                                                                                                                   d_outDepth);
     return vh_last_launch_error();
 }
 

@@ -694,6 +694,19 @@ class CUDARGBDSensor:
     def setFiterIntensityValues(self, b=True, sigmaD=1.0, sigmaR=1.0):
         check(self.L.vh_rgbd_sensor_set_filter_intensity_values(self.handle, int(b), sigmaD, sigmaR), "setFiterIntensityValues")
 
+    def setCameraCalibration(self, enabled, colorFx, colorFy, colorMx, colorMy, depthExtrinsics, thresOffset, thresLin):
+        """s_bUseCameraCalibration: remap the depth map into the colour camera (colour intrinsics at the colour sensor's
+        resolution, the depth extrinsic as the modelview); an identity extrinsic leaves it off"""
+        ci = (C.c_float * 4)(colorFx, colorFy, colorMx, colorMy)
+        check(self.L.vh_rgbd_sensor_set_camera_calibration(self.handle, int(bool(enabled)), ci, f16(depthExtrinsics), thresOffset, thresLin),
+              "setCameraCalibration")
+
+    def getCameraCalibration(self):
+        """-> (whether the remap took effect, the ViewParams process() draws with)"""
+        on, p = C.c_int(), T.ViewParams()
+        check(self.L.vh_rgbd_sensor_get_camera_calibration(self.handle, C.byref(on), C.byref(p)), "getCameraCalibration")
+        return bool(on.value), p
+
     def process(self, depth_float, color_rgbx):
         d = np.ascontiguousarray(depth_float, dtype=np.float32)
         c = np.ascontiguousarray(color_rgbx, dtype=np.uint8)
@@ -721,6 +734,11 @@ class CUDARGBDSensor:
             normals=download(b.value, np.float32, W * H * 4).reshape(H, W, 4),
             intensity=download(c.value, np.float32, W * H).reshape(H, W),
         )
+
+
+def view_resolve_depth(d_depth, params, d_keys, d_large_list, d_out_depth, stream=None):
+    """vh_view_resolve_depth: render target 0 of the keys vh_view_raster left (device pointers; params a ViewParams)"""
+    check(load().vh_view_resolve_depth(d_depth, C.byref(params), d_keys, d_large_list, d_out_depth, stream), "vh_view_resolve_depth")
 
 
 class CUDACameraTrackingMultiRes:

@@ -148,7 +148,10 @@ PROTOTYPES = {
     "vh_view_large_list_words": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "vh_view_raster": (C.c_int, [_VP, P(T.ViewParams), _VP, _VP, _VP]),
     "vh_view_resolve": (C.c_int, [_VP, _VP, P(T.ViewParams), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "vh_view_resolve_depth": (C.c_int, [_VP, P(T.ViewParams), _VP, _VP, _VP, _VP]),
     "vh_phong": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_int, P(T.PhongLight), _VP, _VP, C.c_int, _VP]),
+    "vh_read_calibration_state": (C.c_int, [C.c_char_p, P(T.CalibrationState)]),
+    "vh_parse_calibration_state": (C.c_int, [C.c_char_p, P(T.CalibrationState)]),
     "vh_read_render_state": (C.c_int, [C.c_char_p, P(T.RenderState)]),
     "vh_parse_render_state": (C.c_int, [C.c_char_p, P(T.RenderState)]),
     "vh_phong_light_from_render_state": (None, [P(T.RenderState), P(T.PhongLight)]),
@@ -191,6 +194,9 @@ PROTOTYPES = {
     "vh_rgbd_sensor_get_depth_camera_data": (C.c_int, [_VP, P(T.DepthCameraData)]),
     "vh_rgbd_sensor_get_depth_camera_params": (C.c_int, [_VP, P(T.DepthCameraParams)]),
     "vh_rgbd_sensor_get_maps": (C.c_int, [_VP, P(_VP), P(_VP), P(_VP)]),
+    "vh_rgbd_sensor_set_camera_calibration": (C.c_int, [_VP, C.c_int, P(C.c_float), P(C.c_float), C.c_float, C.c_float]),
+    "vh_rgbd_sensor_get_camera_calibration": (C.c_int, [_VP, P(C.c_int), P(T.ViewParams)]),
+    "vh_rgbd_sensor_remap_params": (C.c_int, [P(C.c_uint32), P(C.c_float), P(C.c_float), P(C.c_float), C.c_float, C.c_float, P(T.ViewParams)]),
     "vh_marching_cubes_data_alloc": (C.c_int, [P(T.MarchingCubesData), P(T.MarchingCubesParams)]),
     "vh_marching_cubes_data_free": (None, [P(T.MarchingCubesData)]),
     "vh_marching_cubes_update_params": (C.c_int, [P(T.MarchingCubesData), P(T.MarchingCubesParams), _VP]),

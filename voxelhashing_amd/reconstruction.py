@@ -7,6 +7,7 @@ Everything is configured the way the application is: a GlobalAppState parameter 
 tracking parameter file.  The D3D window, the GUI and the live sensors are out of scope."""
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
@@ -59,6 +60,38 @@ def read_render_state(path_or_text):
     else:
         check(L.vh_read_render_state(str(path_or_text).encode(), C.byref(r)), "vh_read_render_state")
     return r
+
+
+def read_calibration_state(path_or_text):
+    """the camera-calibration keys of a zParameters*.txt (CalibrationState: s_bUseCameraCalibration and the two remapping
+    discontinuity thresholds)"""
+    L = load()
+    c = T.CalibrationState()
+    if isinstance(path_or_text, bytes):
+        check(L.vh_parse_calibration_state(path_or_text, C.byref(c)), "vh_parse_calibration_state")
+    else:
+        check(L.vh_read_calibration_state(str(path_or_text).encode(), C.byref(c)), "vh_read_calibration_state")
+    return c
+
+
+IDENTITY_EXTRINSICS_WARNING = ("Warning: forcing s_bUseCameraCalibration to be false because the m_depthExtrinsics are the identity "
+                               "(i.e., already aligned)")
+
+
+def camera_calibration(header, calibration_state):
+    """RGBDSensor::initializeDepthExtrinsics (RGBDSensor.cpp:146-156) for a `.sens` header: None when the key is off or
+    the depth extrinsic is the identity (then with the reference's warning, on stderr), else the arguments of
+    CUDARGBDSensor.setCameraCalibration: the colour intrinsics (fx, fy, mx, my) at the colour sensor's resolution, the
+    depth extrinsic and the two thresholds"""
+    if calibration_state is None or not calibration_state.s_bUseCameraCalibration:
+        return None
+    ext = np.array(header.m_depthExtrinsic[:], dtype=np.float32).reshape(4, 4)
+    if np.array_equal(ext, np.eye(4, dtype=np.float32)):  # mLib's operator==: exact, entry by entry
+        print(IDENTITY_EXTRINSICS_WARNING, file=sys.stderr)
+        return None
+    ci = np.array(header.m_colorIntrinsic[:], dtype=np.float32).reshape(4, 4)
+    return (float(ci[0, 0]), float(ci[1, 1]), float(ci[0, 2]), float(ci[1, 2]), ext,
+            calibration_state.s_remappingDepthDiscontinuityThresOffset, calibration_state.s_remappingDepthDiscontinuityThresLin)
 
 
 def adapter_color_intrinsics(color_intrinsic, color_size, adapter_size):
@@ -129,9 +162,15 @@ class Reconstruction:
     render_state (a RenderState, read_render_state; None by default) carries the rendering keys.  When its
     s_renderToFile is set, every frame read ends with the reference's renderToFile (DSC/DepthSensing.cpp:1150-1255):
     the model ray-cast at the last pose, drawn as a mesh and lit, into s_renderToFileDir/reconstruction/%06d.png
-    (material) and reconstruction_color/%06d.png (colour), plus the input as input_color/ and input_depth/ images."""
+    (material) and reconstruction_color/%06d.png (colour), plus the input as input_color/ and input_depth/ images.
 
-    def __init__(self, app_state, tracking_state=None, sens_files=None, stream=None, use_rgbd_tracking=False, render_state=None):
+    calibration_state (a CalibrationState, read_calibration_state; None by default) carries s_bUseCameraCalibration.  When
+    it is set and the `.sens` depth extrinsic is not the identity, the sensor renders every depth map into the colour
+    camera before anything uses it (CUDARGBDSensor.cpp:198-217); an identity extrinsic leaves it off with the reference's
+    warning.  camera_calibration tells which took effect."""
+
+    def __init__(self, app_state, tracking_state=None, sens_files=None, stream=None, use_rgbd_tracking=False, render_state=None,
+                 calibration_state=None):
         self.L = load()
         self.gas = app_state
         self.tracking_rgbd = None
@@ -162,6 +201,10 @@ class Reconstruction:
             self.sensor.setFiterDepthValues(True, g.s_depthSigmaD, g.s_depthSigmaR)
         if g.s_colorFilter:
             self.sensor.setFiterIntensityValues(True, g.s_colorSigmaD, g.s_colorSigmaR)
+        calib = camera_calibration(h, calibration_state)
+        if calib is not None:
+            self.sensor.setCameraCalibration(True, *calib)
+        self.camera_calibration = self.sensor.getCameraCalibration()[0]
         self.cp = self.sensor.getDepthCameraParams()
         hp, opt, rp, mp = T.HashParams(), T.SceneOptions(), T.RayCastParams(), T.MarchingCubesParams()
         self.L.vh_hash_params_from_app_state(C.byref(g), C.byref(hp))

@@ -214,6 +214,14 @@ class RenderState(C.Structure):
     ]
 
 
+class CalibrationState(C.Structure):
+    """VhCalibrationState: the camera-calibration keys of a zParameters*.txt"""
+    _fields_ = [
+        ("s_bUseCameraCalibration", C.c_uint32), ("s_remappingDepthDiscontinuityThresOffset", C.c_float),
+        ("s_remappingDepthDiscontinuityThresLin", C.c_float), ("numKeysFound", C.c_uint32),
+    ]
+
+
 class PhongLight(C.Structure):
     """VhPhongLight: DX11PhongLighting::ConstantBufferLight"""
     _fields_ = [
