@@ -321,7 +321,7 @@ public:
     void pipelineStreamIn(const StreamDecision& d); // enqueues the insert of what the worker has uploaded
     // the job for the worker: take in what this frame's stream-out pass copies, then (haveNext) choose for the next frame
     void pipelineAsk(bool haveNext, const vh::vec3f& nextPosCamera, float nextRadius);
-    // waits for the worker's job and looks at the outcome of finished inserts (repairs failures).  undo: a choice that has
+    // waits for the worker's job and looks at the outcome of finished inserts (files failures back into the grid).  undo: a choice that has
     // been made for a coming frame is put back into the grid (whoever looks at the host grid or takes the reference's order
     // of calls next must find it as the reference would have it at this point; the next frame then chooses again)
     void pipelineDrain(bool undo = true);
@@ -390,8 +390,7 @@ private:
     void destroy();
     void setBit(unsigned int index);
     void resetBit(unsigned int index);
-    void takeBackFailedInserts(unsigned int nFailed, unsigned int heapCountPrev);
-    void takeBackFailedInserts(unsigned int nFailed, unsigned int heapCountPrev, const SDFBlockDesc* descs, const vh::SDFBlock* blocks, unsigned int& nIn);
+    bool refileFailedInserts(int slot, const SDFBlockDesc* descs, const vh::SDFBlock* blocks, unsigned int& nIn);
     unsigned int integrateInHash(const vh::vec3f& posCamera, float radius, bool useParts, SDFBlockDesc* hDescs, vh::SDFBlock* hBlocks,
                                  SDFBlockDesc* dDescs, vh::SDFBlock* dBlocks, unsigned int capacity, unsigned int* chunkBit);
     // the pipeline (see above)
@@ -421,7 +420,7 @@ private:
     unsigned int m_plFrame;                         // frames the pipeline has run (slot = frame & 1)
     bool m_plOutThisFrame;                          // pipelineStreamOut() of the current frame launched a pass
     uint32_t m_plOutTag, m_plOutMost;
-    struct { bool pending; uint32_t tag; unsigned int nIn, chunkBit; } m_plInsert[2]; // per staging slot: an insert whose outcome has not been looked at
+    struct { bool pending; uint32_t tag; unsigned int nIn; } m_plInsert[2]; // per staging slot: an insert whose outcome has not been looked at
     std::atomic<unsigned long long> m_plBlocksOut, m_plBlocksIn;
     SDFBlockDesc* d_plOutDesc[2];      // pass 1 -> pass 2 (device)
     SDFBlockDesc* h_plOutDesc[2];      // mapped pinned: pass 2 writes the blocks it moves straight to the host
@@ -434,11 +433,14 @@ private:
     vh::SDFBlock* h_plInBlocks[2];
     SDFBlockDesc* d_plInDesc[2];
     vh::SDFBlock* d_plInBlocks[2];
-    uint32_t* h_plInMirror[2];         // mapped pinned {failed, heap counter before, tag, exhausted}, per staging slot
-    uint32_t* hd_plInMirror[2];
     uint32_t m_plTag;
     void streamInLaunches();
     unsigned int m_numFailedInserts;
+    // the outcome of a stream-in pass (vh_stream_in_device), mapped pinned {failed, 0, tag, exhausted, failed indices ...}: one
+    // per pipeline slot, and kSyncInSlot for the passes of streamInLaunches()
+    enum { kSyncInSlot = 2 };
+    uint32_t* h_inMirror[3];
+    uint32_t* hd_inMirror[3];
 
     unsigned int m_maxNumberOfSDFBlocksIntegrateFromGlobalHash;
 
@@ -446,7 +448,6 @@ private:
     vh::SDFBlock* h_SDFBlockOutput;     // pinned
     SDFBlockDesc* h_SDFBlockDescInput;  // pinned staging for the worker's H2D
     vh::SDFBlock* h_SDFBlockInput;      // pinned
-    uint32_t* h_counter;                // pinned
     uint32_t* h_mirror;                 // mapped pinned: {word 0, word 1, tag} published by the device (vh_publish_words)
     uint32_t* d_mirror;                 // its device alias
     uint32_t m_mirrorTag;
@@ -462,7 +463,7 @@ private:
     vh::SDFBlock* d_SDFBlockOutput;
     vh::SDFBlock* d_SDFBlockInput;
     unsigned int* d_SDFBlockCounter;
-    unsigned int* d_insertFailed; // {count, indices ...} of the blocks a stream-in pass could not insert
+    unsigned int* d_insertFailed; // vh_stream_in_device's scratch: {count, {index, SDF block} ...} of the blocks that found no slot
     unsigned int* d_bitMask;
     void* m_copyStream; // hipStream_t of the worker thread
     int m_device;       // HIP device the scene lives on (the worker thread binds to it)

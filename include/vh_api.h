@@ -200,9 +200,14 @@ int vh_stream_out_pass2(const VhHashData* hd, const VhHashParams* hp, const VhSD
  * mostBlocks blocks and reads the count on the device.
  * vh_publish_count: {*d_counter, 0, tag} into mapped host memory (tag last, system scope), to be enqueued behind the copies of
  * the pass's output.
- * vh_stream_in_device: chunkToGlobalHashPass1CUDA + Pass2CUDA + the heap counter's update with the counter read on the device;
- * clears bit `chunkBit` of d_bitMask (0xffffffff: none); publishes {blocks that found no slot (listed in d_failed[1..]), heap
- * counter before the pass, tag, 1 if the heap held too few free blocks -- then nothing was inserted} to d_mapped. */
+ * vh_stream_in_device: chunkToGlobalHashPass1CUDA + Pass2CUDA + the heap counter's update with the counter read on the device,
+ * in three launches after which the device state is final.  Clears bit `chunkBit` of d_bitMask (d_bitMask may be NULL,
+ * chunkBit 0xffffffff: none).  A block that finds no slot (its bucket and its list full, or a second overflow of one bucket
+ * within the pass; the reference has no such case handling, DSC/VoxelUtilHashSDF.h:682-713) keeps no voxels: its SDF block
+ * goes back onto the heap, cleared, and the chunk's bit is set again.  d_failed: device scratch of 1 + 2n words, zero on
+ * entry and zero again afterwards.  Publishes {blocks that found no slot, 0, tag, 1 if the heap held too few free blocks --
+ * then nothing was done, and d_state[VH_STATE_HEAP_UNDERFLOW] is raised -- then their indices into d_descs} to d_mapped
+ * (room for 4 + n words; tag last, system scope). */
 int vh_stream_out_device(const VhHashData* hd, const VhHashParams* hp, uint32_t threadsPerPart, uint32_t start, float radius,
                          const float camPos[3], uint32_t* d_outputCounter, VhSDFBlockDesc* d_descs, VhVoxel* d_blocks,
                          uint32_t mostBlocks, int32_t lockToken, uint32_t* d_bitMask, vhStream_t stream);
@@ -213,11 +218,6 @@ int vh_stream_in_device(const VhHashData* hd, const VhHashParams* hp, uint32_t n
 /* chunkToGlobalHashPass1CUDA(params, hashData, n, heapCountPrev, descs, blocks)           :162 */
 int vh_stream_in_pass1(const VhHashData* hd, const VhHashParams* hp, uint32_t n, uint32_t heapCountPrev,
                        const VhSDFBlockDesc* d_descs, int32_t lockToken, vhStream_t stream);
-/* the same, reporting which blocks could not be inserted (their bucket and its list were full, or two blocks of the
- * pass overflowed one bucket): d_failed[0], zeroed by the caller, counts them, d_failed[1 ..] lists their indices into
- * d_descs (room for n).  The reference has no such case handling (its overflow branch is an unported remnant). */
-int vh_stream_in_pass1_report(const VhHashData* hd, const VhHashParams* hp, uint32_t n, uint32_t heapCountPrev,
-                              const VhSDFBlockDesc* d_descs, int32_t lockToken, uint32_t* d_failed, vhStream_t stream);
 /* chunkToGlobalHashPass2CUDA(params, hashData, n, heapCountPrev, descs, blocks)           :192 */
 int vh_stream_in_pass2(const VhHashData* hd, const VhHashParams* hp, uint32_t n, uint32_t heapCountPrev,
                        const VhSDFBlockDesc* d_descs, const VhVoxel* d_blocks, vhStream_t stream);

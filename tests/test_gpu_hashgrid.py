@@ -282,3 +282,66 @@ def test_blocks_that_find_no_slot_in_a_pipelined_frame_go_back_too(E, tmp_path):
     grid.debugCheckForDuplicates()
     recon.close()
     grid.close()
+
+
+@pytest.mark.timeout(300)
+def test_blocks_that_find_no_slot_while_gc_frees_blocks_go_back_too(E, tmp_path):
+    """A crowded chunk inserted by the pipelined streaming step in the frame in which garbage collection frees many blocks:
+    frame 0 (the chunk outside its sphere) sees a wall and allocates blocks of weight 1; frame 1 (the chunk inside) sees
+    nothing, and starving takes those blocks to weight 0, so the frame's GC frees them all -- on the same stream, after the
+    insert and before the host has looked at its outcome.  Their ids go onto the heap right above the counter, into the
+    slots the insert took.  The outcome of a failed insert must not depend on those slots: nothing lost, nothing leaked,
+    no block shared, and later frames bring every block in."""
+    from collections import Counter
+    rng = np.random.default_rng(13)
+    ext, dims, minp = (4.0, 4.0, 4.0), (9, 9, 9), (-4, -4, -4)
+    nb, nblocks = 127, 1024
+    hp, cp, rp = small_config(64, 48, num_buckets=nb, num_sdf_blocks=nblocks, weight_sample=1, streaming_extents=ext, streaming_dims=dims,
+                              streaming_min=minp)
+    scene = E.CUDASceneRepHashSDF(hp, T.make_scene_options(offline=False, gc=True, starve=1, streaming_out_parts=1))
+    ray = E.CUDARayCastSDF(rp)
+    grid = E.CUDASceneRepChunkGrid(scene, ext, dims, minp, LIST, True, 1)  # worker thread running
+    voxel = hp.m_virtualVoxelSize
+    # chunk (0, 0, -1): behind every camera of the sequence (never seen, so never starved), 4 m from the origin
+    behind = chunk_of((0, 0, -10), voxel, ext, minp, dims)
+    cand = [(x, y, z) for x in range(-6, 7) for y in range(-6, 7) for z in range(-20, 0) if chunk_of((x, y, z), voxel, ext, minp, dims) == behind]
+    bucket = Counter(bucket_of(p, nb) for p in cand).most_common(1)[0][0]
+    pos = np.array([p for p in cand if bucket_of(p, nb) == bucket][:14], dtype=np.int32)
+    assert len(pos) == 14
+    vox = make_blocks(rng, len(pos))
+    path = str(tmp_path / "crowded.hashgrid")
+    maxp = tuple(m + d for m, d in zip(minp, dims))
+    write_file(path, voxel, {behind: (pos, vox)}, ext=ext, dims=dims, minp=minp, maxp=maxp)
+    grid.loadFromFile(path, np.array([100.0, 0.0, 0.0], np.float32), 1.0)  # (a sphere far away: nothing comes in yet)
+    W, H = cp.m_imageWidth, cp.m_imageHeight
+    wall = E.DepthFrame(cp, depth=np.full((H, W), 2.5, np.float32), color=np.full((H, W, 4), 0.5, np.float32))
+    blank = E.DepthFrame(cp, depth=np.full((H, W), -np.inf, np.float32), color=np.full((H, W, 4), -np.inf, np.float32))
+    n = 16
+
+    def pose_at(x, z):
+        m = np.eye(4, dtype=np.float32)
+        m[0, 3], m[2, 3] = x, z
+        return m.reshape(16)
+
+    # sphere of 8 m around the camera: the chunk (centre 4 m behind the origin, bounding radius 3.46 m) is out of it at
+    # z = 1 and inside it at z = 0; the wall (z = 3.5, chunk (0, 0, 1)) is in every camera's view and sphere
+    poses = [pose_at(0.0, 1.0)] + [pose_at(0.01 * k, 0.0) for k in range(1, n)]
+    recon = E.Reconstruction(scene, ray, grid, cp, E.Reconstruction.defaultOptions(s_streamingEnabled=1, s_streamingPos=(0.0, 0.0, 0.0), s_streamingRadius=8.0,
+                                                                                  s_allocAhead=1, s_maxFramesInFlight=4))
+    seq = E.Reconstruction.makeFrames(poses, [wall.depth_ptr] + [blank.depth_ptr] * (n - 1), [wall.color_ptr] + [blank.color_ptr] * (n - 1))
+    recon.run(seq)
+    recon.synchronize()
+    st = recon.getStats()
+    assert st["frames"] == n and st["streamingFramesPipelined"] == n - 1, st
+    assert grid.getNumFailedInserts() > 0, "the pipelined pass was meant to overflow one bucket twice"
+    assert grid.getStatistics()["blocks"] == 0, "every block must have come in by now"
+    assert st["blocksStreamedIn"] == 14 and st["blocksStreamedOut"] == 0, st
+    s = scene.state()  # invariants: no block both free and used, none lost, free ones zero
+    order = canonical.lexsort_pos(pos)
+    assert np.array_equal(s["positions"], pos[order]), "the wall's blocks were meant to be freed by frame 1's GC"
+    assert s["voxels"].tobytes() == np.ascontiguousarray(vox[order]).tobytes()
+    assert s["heap_free"] == nblocks - 14
+    assert scene.debugHash()["duplicates"] == 0
+    grid.debugCheckForDuplicates()
+    recon.close()
+    grid.close()

@@ -86,7 +86,7 @@ CUDASceneRepChunkGrid::CUDASceneRepChunkGrid(CUDASceneRepHashSDF* sceneRepHashSD
     m_streamOutParts = streamOutParts ? streamOutParts : 1;
     m_maxNumberOfSDFBlocksIntegrateFromGlobalHash = 100000; // DSC/CUDASceneRepChunkGrid.h:162
     h_SDFBlockDescOutput = nullptr; h_SDFBlockOutput = nullptr;
-    h_SDFBlockDescInput = nullptr; h_SDFBlockInput = nullptr; h_counter = nullptr;
+    h_SDFBlockDescInput = nullptr; h_SDFBlockInput = nullptr;
     h_mirror = nullptr; d_mirror = nullptr; m_mirrorTag = 0;
     h_probe = nullptr; d_probe = nullptr; m_probeTag = 0; d_probeCounter = nullptr;
     d_SDFBlockDescOutput = nullptr; d_SDFBlockDescInput = nullptr;
@@ -104,7 +104,8 @@ CUDASceneRepChunkGrid::CUDASceneRepChunkGrid(CUDASceneRepHashSDF* sceneRepHashSD
     m_plDecisionPos = { 0.0f, 0.0f, 0.0f };
     m_plDecisionRadius = 0.0f;
     m_plFrame = 0; m_plOutThisFrame = false; m_plOutTag = 0; m_plOutMost = 0;
-    for (int i = 0; i < 2; i++) { m_plInsert[i].pending = false; m_plInsert[i].tag = 0; m_plInsert[i].nIn = 0; m_plInsert[i].chunkBit = 0xffffffffu; h_plInMirror[i] = nullptr; hd_plInMirror[i] = nullptr; }
+    for (int i = 0; i < 2; i++) { m_plInsert[i].pending = false; m_plInsert[i].tag = 0; m_plInsert[i].nIn = 0; }
+    for (int i = 0; i < 3; i++) { h_inMirror[i] = nullptr; hd_inMirror[i] = nullptr; }
     m_plBlocksOut = 0; m_plBlocksIn = 0; m_plTag = 0;
     for (int i = 0; i < 2; i++) {
         d_plOutDesc[i] = nullptr; h_plOutDesc[i] = nullptr; h_plOutBlocks[i] = nullptr; hd_plOutDesc[i] = nullptr; hd_plOutBlocks[i] = nullptr;
@@ -134,7 +135,6 @@ void CUDASceneRepChunkGrid::create(const vh::vec3f& voxelExtends, const vh::vec3
     checkHip(hipHostMalloc((void**)&h_SDFBlockOutput, sizeof(vh::SDFBlock) * n, hipHostMallocDefault), "hipHostMalloc");
     checkHip(hipHostMalloc((void**)&h_SDFBlockDescInput, sizeof(SDFBlockDesc) * n, hipHostMallocDefault), "hipHostMalloc");
     checkHip(hipHostMalloc((void**)&h_SDFBlockInput, sizeof(vh::SDFBlock) * n, hipHostMallocDefault), "hipHostMalloc");
-    checkHip(hipHostMalloc((void**)&h_counter, sizeof(uint32_t) * 2, hipHostMallocDefault), "hipHostMalloc");
     checkHip(hipHostMalloc((void**)&h_mirror, sizeof(uint32_t) * 4, hipHostMallocMapped), "hipHostMalloc");
     h_mirror[0] = h_mirror[1] = h_mirror[2] = h_mirror[3] = 0u;
     checkHip(hipHostGetDevicePointer((void**)&d_mirror, h_mirror, 0), "hipHostGetDevicePointer");
@@ -148,7 +148,14 @@ void CUDASceneRepChunkGrid::create(const vh::vec3f& voxelExtends, const vh::vec3
     checkHip(hipMalloc((void**)&d_SDFBlockOutput, sizeof(vh::SDFBlock) * n), "hipMalloc");
     checkHip(hipMalloc((void**)&d_SDFBlockInput, sizeof(vh::SDFBlock) * n), "hipMalloc");
     checkHip(hipMalloc((void**)&d_SDFBlockCounter, sizeof(unsigned int)), "hipMalloc");
-    checkHip(hipMalloc((void**)&d_insertFailed, sizeof(unsigned int) * (1 + (size_t)m_maxNumberOfSDFBlocksIntegrateFromGlobalHash)), "hipMalloc");
+    checkHip(hipMalloc((void**)&d_insertFailed, sizeof(unsigned int) * (1 + 2 * n)), "hipMalloc");
+    checkHip(hipMemset(d_insertFailed, 0, sizeof(unsigned int)), "hipMemset");
+    for (int i = 0; i < 3; i++) {
+        const size_t words = 4 + (i == kSyncInSlot ? n : (size_t)kPipelineBlocks);
+        checkHip(hipHostMalloc((void**)&h_inMirror[i], sizeof(uint32_t) * words, hipHostMallocMapped), "hipHostMalloc");
+        std::memset(h_inMirror[i], 0, sizeof(uint32_t) * words);
+        checkHip(hipHostGetDevicePointer((void**)&hd_inMirror[i], h_inMirror[i], 0), "hipHostGetDevicePointer");
+    }
     checkHip(hipMalloc((void**)&d_bitMask, sizeof(unsigned int) * m_bitMask.size()), "hipMalloc");
     checkHip(hipGetDevice(&m_device), "hipGetDevice"); // one instance is bound to one device
     hipStream_t cs;
@@ -167,10 +174,11 @@ void CUDASceneRepChunkGrid::destroy()
     if (m_sceneRepHashSDF) (void)hipStreamSynchronize((hipStream_t)m_sceneRepHashSDF->getStream());
     if (m_copyStream) { (void)hipStreamSynchronize((hipStream_t)m_copyStream); (void)hipStreamDestroy((hipStream_t)m_copyStream); }
     (void)hipHostFree(h_SDFBlockDescOutput); (void)hipHostFree(h_SDFBlockOutput);
-    (void)hipHostFree(h_SDFBlockDescInput); (void)hipHostFree(h_SDFBlockInput); (void)hipHostFree(h_counter); (void)hipHostFree(h_mirror); (void)hipHostFree(h_probe); (void)hipFree(d_probeCounter);
+    (void)hipHostFree(h_SDFBlockDescInput); (void)hipHostFree(h_SDFBlockInput); (void)hipHostFree(h_mirror); (void)hipHostFree(h_probe); (void)hipFree(d_probeCounter);
     (void)hipFree(d_SDFBlockDescOutput); (void)hipFree(d_SDFBlockDescInput);
     (void)hipFree(d_SDFBlockOutput); (void)hipFree(d_SDFBlockInput);
     (void)hipFree(d_SDFBlockCounter); (void)hipFree(d_insertFailed); (void)hipFree(d_bitMask);
+    for (int i = 0; i < 3; i++) (void)hipHostFree(h_inMirror[i]);
 }
 
 // ---------------------------------------------------------------------------
@@ -694,60 +702,46 @@ void CUDASceneRepChunkGrid::streamInToGPUPass1GPU(bool multiThreaded)
 // the device side of a stream-in pass the worker (or streamInToGPUPass0CPU) has prepared
 void CUDASceneRepChunkGrid::streamInLaunches()
 {
-    if (s_nStreamdInBlocks != 0) {
-        const HashParams& hp = m_sceneRepHashSDF->getHashParams();
-        HashData& hd = m_sceneRepHashSDF->getHashData();
-        vhStream_t stream = m_sceneRepHashSDF->getStream();
-        unsigned int heapCountPrev = 0; // index of the top free block
-        readBack(hd.d_heapCounter, nullptr, &heapCountPrev, nullptr);
-        if (s_nStreamdInBlocks > heapCountPrev + 1u) throw vh::Error(VH_ERR_HEAP_EXHAUSTED, "stream-in: not enough free SDF blocks");
-        const int32_t token = m_sceneRepHashSDF->nextLockToken();
-        m_sceneRepHashSDF->noteTableEdited();
-        hipStream_t hs = (hipStream_t)stream;
-        checkHip(hipMemsetAsync(d_insertFailed, 0, sizeof(unsigned int), hs), "clear failed inserts");
-        check(vh_stream_in_pass1_report(&hd, &hp, s_nStreamdInBlocks, heapCountPrev, d_SDFBlockDescInput, token, d_insertFailed, stream), "chunkToGlobalHashPass1CUDA");
-        check(vh_stream_in_pass2(&hd, &hp, s_nStreamdInBlocks, heapCountPrev, d_SDFBlockDescInput, (const VhVoxel*)d_SDFBlockInput, stream), "chunkToGlobalHashPass2CUDA");
-        // update heap counter (pinned source: stays valid until the copy ran)
-        h_counter[0] = heapCountPrev - s_nStreamdInBlocks;
-        checkHip(hipMemcpyAsync(hd.d_heapCounter, &h_counter[0], sizeof(unsigned int), hipMemcpyHostToDevice, hs), "heapCounter");
-        unsigned int nFailed = 0;
-        readBack(d_insertFailed, nullptr, &nFailed, nullptr); // (also: the copy above has read h_counter[0] by then)
-        if (nFailed != 0) takeBackFailedInserts(nFailed, heapCountPrev);
-    }
-}
-
-// Blocks of the last stream-in pass that found no slot (their bucket and its list full, or a second overflow of one
-// bucket within the pass): the reference has no defined behaviour for them (DSC/VoxelUtilHashSDF.h:682-713).  Here they
-// go back to where they came from -- the host chunk grid -- and their SDF blocks back to the heap, cleared, so that no
-// block is lost and the pool still is the union of heap and table.  They come in again with a later pass.
-void CUDASceneRepChunkGrid::takeBackFailedInserts(unsigned int nFailed, unsigned int heapCountPrev)
-{
-    takeBackFailedInserts(nFailed, heapCountPrev, h_SDFBlockDescInput, h_SDFBlockInput, s_nStreamdInBlocks);
-}
-
-void CUDASceneRepChunkGrid::takeBackFailedInserts(unsigned int nFailed, unsigned int heapCountPrev, const SDFBlockDesc* descs, const vh::SDFBlock* blocks, unsigned int& nIn)
-{
+    if (s_nStreamdInBlocks == 0) return;
+    const HashParams& hp = m_sceneRepHashSDF->getHashParams();
     HashData& hd = m_sceneRepHashSDF->getHashData();
-    hipStream_t hs = (hipStream_t)m_sceneRepHashSDF->getStream();
-    std::vector<unsigned int> idx(nFailed), blockIds(nFailed);
-    checkHip(hipMemcpy(idx.data(), d_insertFailed + 1, sizeof(unsigned int) * nFailed, hipMemcpyDeviceToHost), "failed insert list");
-    unsigned int counter = 0;
-    checkHip(hipMemcpy(&counter, hd.d_heapCounter, sizeof(unsigned int), hipMemcpyDeviceToHost), "heapCounter");
-    for (unsigned int k = 0; k < nFailed; k++) {
-        const unsigned int i = idx[k];
-        if (i >= nIn) throw vh::Error(VH_ERR_INSERT_FAILED, "stream-in: corrupt list of failed inserts");
-        // the heap slot the pass took for this block (chunkToGlobalHashPass1Kernel: heap[heapCountPrev - i])
-        checkHip(hipMemcpy(&blockIds[k], hd.d_heap + (heapCountPrev - i), sizeof(unsigned int), hipMemcpyDeviceToHost), "heap slot");
-        checkHip(hipMemsetAsync(hd.d_SDFBlocks + (size_t)blockIds[k] * VH_SDF_BLOCK_VOXELS, 0, sizeof(vh::SDFBlock), hs), "clear block");
-        integrateInChunkGrid(&descs[i], &blocks[i], 1); // the staging copy is still there
+    vhStream_t stream = m_sceneRepHashSDF->getStream();
+    const int32_t token = m_sceneRepHashSDF->nextLockToken();
+    m_sceneRepHashSDF->noteTableEdited();
+    const uint32_t tag = ++m_plTag ? m_plTag : ++m_plTag;
+    // (no chunk bit: the host's copy of the bit mask is the one that counts here)
+    check(vh_stream_in_device(&hd, &hp, s_nStreamdInBlocks, d_SDFBlockDescInput, (const VhVoxel*)d_SDFBlockInput, token, d_insertFailed, nullptr,
+                              0xffffffffu, hd_inMirror[kSyncInSlot], tag, stream), "chunkToGlobalHashPass1CUDA + Pass2CUDA");
+    checkHip(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
+    if (((volatile uint32_t*)h_inMirror[kSyncInSlot])[2] != tag) throw vh::Error(-(int)hipErrorUnknown, "stream-in: the device did not publish its pass");
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (refileFailedInserts(kSyncInSlot, h_SDFBlockDescInput, h_SDFBlockInput, s_nStreamdInBlocks))
+        throw vh::Error(VH_ERR_HEAP_EXHAUSTED, "stream-in: not enough free SDF blocks");
+}
+
+// The outcome of a stream-in pass as vh_stream_in_device published it for `slot`.  Blocks that found no slot (their bucket
+// and its list full, or a second overflow of one bucket within the pass) -- all of the pass's blocks if the heap held too few
+// free ones -- go back to where they came from: the host chunk grid, from the pass's staging copy.  The device has already
+// returned their SDF blocks to the heap, cleared, and set the chunk's bit again, so no block is lost and the pool still is
+// the union of heap and table.  They come in again with a later pass.  Returns true if the heap was exhausted.
+bool CUDASceneRepChunkGrid::refileFailedInserts(int slot, const SDFBlockDesc* descs, const vh::SDFBlock* blocks, unsigned int& nIn)
+{
+    const volatile uint32_t* m = h_inMirror[slot];
+    const bool exhausted = m[3] != 0u;
+    const unsigned int nFailed = exhausted ? nIn : m[0];
+    if (exhausted) {
+        integrateInChunkGrid(descs, blocks, nIn);
+    } else {
+        if (nFailed > nIn) throw vh::Error(VH_ERR_INSERT_FAILED, "stream-in: corrupt list of failed inserts");
+        for (unsigned int k = 0; k < nFailed; k++) {
+            const unsigned int i = m[4 + k];
+            if (i >= nIn) throw vh::Error(VH_ERR_INSERT_FAILED, "stream-in: corrupt list of failed inserts");
+            integrateInChunkGrid(&descs[i], &blocks[i], 1);
+        }
     }
-    // appendHeap, DSC/VoxelUtilHashSDF.h:525-529, nFailed times
-    checkHip(hipMemcpyAsync(hd.d_heap + counter + 1, blockIds.data(), sizeof(unsigned int) * nFailed, hipMemcpyHostToDevice, hs), "heap");
-    counter += nFailed;
-    checkHip(hipMemcpyAsync(hd.d_heapCounter, &counter, sizeof(unsigned int), hipMemcpyHostToDevice, hs), "heapCounter");
-    checkHip(hipStreamSynchronize(hs), "hipStreamSynchronize");
     nIn -= nFailed;
     m_numFailedInserts += nFailed;
+    return exhausted;
 }
 
 // DSC/CUDASceneRepChunkGrid.cpp:268-311
@@ -858,11 +852,6 @@ void CUDASceneRepChunkGrid::pipelineStart()
         checkHip(hipMalloc((void**)&d_plInDesc[i], sizeof(SDFBlockDesc) * n), "hipMalloc");
         checkHip(hipMalloc((void**)&d_plInBlocks[i], sizeof(vh::SDFBlock) * n), "hipMalloc");
     }
-    for (int i = 0; i < 2; i++) {
-        checkHip(hipHostMalloc((void**)&h_plInMirror[i], sizeof(uint32_t) * 4, hipHostMallocMapped), "hipHostMalloc");
-        h_plInMirror[i][0] = h_plInMirror[i][1] = h_plInMirror[i][2] = h_plInMirror[i][3] = 0u;
-        checkHip(hipHostGetDevicePointer((void**)&hd_plInMirror[i], h_plInMirror[i], 0), "hipHostGetDevicePointer");
-    }
     m_plQuit = false;
     m_plThread = std::thread(&CUDASceneRepChunkGrid::pipelineWorker, this);
     m_plStarted = true;
@@ -884,7 +873,6 @@ void CUDASceneRepChunkGrid::pipelineStop()
         d_plOutDesc[i] = nullptr; h_plOutDesc[i] = nullptr; h_plOutBlocks[i] = nullptr; h_plOutMirror[i] = nullptr;
         h_plInDesc[i] = nullptr; h_plInBlocks[i] = nullptr; d_plInDesc[i] = nullptr; d_plInBlocks[i] = nullptr;
     }
-    for (int i = 0; i < 2; i++) { (void)hipHostFree(h_plInMirror[i]); h_plInMirror[i] = nullptr; }
 }
 
 // the worker: one job per frame
@@ -944,11 +932,11 @@ bool CUDASceneRepChunkGrid::pipelineHasDecision(const vh::vec3f& posCamera, floa
            m_plDecisionRadius == radius;
 }
 
-// the outcome of the previous frame's insert (published by k_stream_in_commit): failures are repaired here, by the main thread
+// the outcome of the previous frame's insert (published by k_stream_in_commit): failures go back into the grid here, by the main thread
 void CUDASceneRepChunkGrid::pipelineCheckInsert(int slot, bool block)
 {
     if (!m_plInsert[slot].pending) return;
-    volatile uint32_t* m = h_plInMirror[slot];
+    volatile uint32_t* m = h_inMirror[slot];
     if (m[2] != m_plInsert[slot].tag) {
         if (!block) return;
         checkHip(hipStreamSynchronize((hipStream_t)m_sceneRepHashSDF->getStream()), "hipStreamSynchronize");
@@ -956,28 +944,9 @@ void CUDASceneRepChunkGrid::pipelineCheckInsert(int slot, bool block)
     }
     std::atomic_thread_fence(std::memory_order_acquire);
     m_plInsert[slot].pending = false;
-    const unsigned int nFailed = m[0], heapCountPrev = m[1], exhausted = m[3];
     unsigned int nIn = m_plInsert[slot].nIn;
-    if (exhausted) {
-        // the heap held too few free blocks: nothing was inserted, the chunk goes back into the grid (its bit is set again there;
-        // the device's copy of the mask was not touched)
-        integrateInChunkGrid(h_plInDesc[slot], h_plInBlocks[slot], nIn);
-        m_numFailedInserts += nIn;
-        nIn = 0;
-    } else if (nFailed != 0) {
-        checkHip(hipStreamSynchronize((hipStream_t)m_sceneRepHashSDF->getStream()), "hipStreamSynchronize");
-        takeBackFailedInserts(nFailed, heapCountPrev, h_plInDesc[slot], h_plInBlocks[slot], nIn);
-        // The blocks that went back set their chunk's bit in the host's copy; the device's copy had it cleared by the pass: set
-        // there too.  (That one bit, not an upload of the host's copy: a stream-out pass enqueued since may have set bits on
-        // the device that the host will only learn of when its blocks arrive.  The device is idle: the stream was synchronised.)
-        const unsigned int bit = m_plInsert[slot].chunkBit;
-        if (bit != 0xffffffffu) {
-            unsigned int word = 0;
-            checkHip(hipMemcpy(&word, d_bitMask + (bit >> 5), sizeof(word), hipMemcpyDeviceToHost), "bit mask word");
-            word |= 1u << (bit & 31u);
-            checkHip(hipMemcpy(d_bitMask + (bit >> 5), &word, sizeof(word), hipMemcpyHostToDevice), "bit mask word");
-        }
-    }
+    // (on exhaustion the chunk's bit is set again in the host's copy; the device's copy was not touched)
+    (void)refileFailedInserts(slot, h_plInDesc[slot], h_plInBlocks[slot], nIn);
     m_plBlocksIn += nIn;
 }
 
@@ -1049,8 +1018,8 @@ void CUDASceneRepChunkGrid::pipelineStreamIn(const StreamDecision& d)
     m_sceneRepHashSDF->noteTableEdited();
     const uint32_t tag = ++m_plTag ? m_plTag : ++m_plTag;
     check(vh_stream_in_device(&hd, &hp, d.nIn, d_plInDesc[d.slot], (const VhVoxel*)d_plInBlocks[d.slot], token, d_insertFailed, d_bitMask, d.chunkBit,
-                              hd_plInMirror[d.slot], tag, m_sceneRepHashSDF->getStream()), "vh_stream_in_device");
-    m_plInsert[d.slot].pending = true; m_plInsert[d.slot].tag = tag; m_plInsert[d.slot].nIn = d.nIn; m_plInsert[d.slot].chunkBit = d.chunkBit;
+                              hd_inMirror[d.slot], tag, m_sceneRepHashSDF->getStream()), "vh_stream_in_device");
+    m_plInsert[d.slot].pending = true; m_plInsert[d.slot].tag = tag; m_plInsert[d.slot].nIn = d.nIn;
 }
 
 void CUDASceneRepChunkGrid::pipelineAsk(bool haveNext, const vh::vec3f& nextPosCamera, float nextRadius)
@@ -1058,7 +1027,7 @@ void CUDASceneRepChunkGrid::pipelineAsk(bool haveNext, const vh::vec3f& nextPosC
     pipelineStart();
     if (!haveNext && !m_plOutThisFrame) { m_plFrame++; return; } // nothing for the worker to do
     // The worker will stage the next frame's chunk in the buffer an insert of two frames back was made from: if that insert
-    // failed, its repair needs the buffer as it is -- look at its outcome first (the device passed it most of a frame ago)
+    // failed, its blocks go back into the grid from the buffer as it is -- look at its outcome first (the device passed it most of a frame ago)
     if (haveNext) pipelineCheckInsert((int)((m_plFrame + 1u) & 1u), true);
     {
         std::lock_guard<std::mutex> l(m_plMutex);

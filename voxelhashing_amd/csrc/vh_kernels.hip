@@ -4072,8 +4072,12 @@ __global__ void k_publish_count(const uint32_t* counter, uint32_t* mapped, uint3
 
 // The stream-in pass for a caller that does not read the heap counter back: chunkToGlobalHashPass1Kernel / Pass2Kernel
 // with the counter looked up on the device, the chunk's bit cleared in the device's copy of the bit mask, and a third
-// launch that takes the blocks off the heap and tells the host (mapped memory) how it went:
-//   {blocks that found no slot, heap counter before the pass, 1 if the heap held too few free blocks (nothing was done), tag}
+// launch that settles the pass.  A block that finds no slot is listed as {index in the pass, SDF block it took} in
+// failed[1 ..] and its heap slot is marked, so that pass 2 leaves the block zero; the commit returns those blocks to the
+// heap and sets the chunk's bit again.  After the three launches the device state is final, and the host learns (mapped
+// memory) which blocks of its staging copy to file back into its grid:
+//   {blocks that found no slot, 0, tag, 1 if the heap held too few free blocks (nothing was done), their indices ...}
+constexpr uint32_t kStreamInNoSlot = 0xffffffffu;
 __global__ __launch_bounds__(64) void k_stream_in_pass1_dev(VhHashData hd, VhHashParams hp, uint32_t n, const VhSDFBlockDesc* descs, int32_t lockToken,
                                                             uint32_t* failed, uint32_t* bitMask, uint32_t chunkBit)
 {
@@ -4082,11 +4086,14 @@ __global__ __launch_bounds__(64) void k_stream_in_pass1_dev(VhHashData hd, VhHas
     const uint32_t heapCountPrev = hd.d_heapCounter[0];
     if (n > heapCountPrev + 1u) return; // (k_stream_in_commit reports it; the host puts the blocks back into its grid)
     if (i == 0u && bitMask && chunkBit != 0xffffffffu) atomicAnd(&bitMask[chunkBit >> 5], ~(1u << (chunkBit & 31u)));
-    const uint32_t ptr = hd.d_heap[heapCountPrev - i] * VH_SDF_BLOCK_VOXELS;
+    const uint32_t id = hd.d_heap[heapCountPrev - i];
     const VhSDFBlockDesc dsc = descs[i];
-    if (!insert_hash_entry(hd, hp, mki3(dsc.pos[0], dsc.pos[1], dsc.pos[2]), (int)ptr, lockToken)) {
+    if (!insert_hash_entry(hd, hp, mki3(dsc.pos[0], dsc.pos[1], dsc.pos[2]), (int)(id * VH_SDF_BLOCK_VOXELS), lockToken)) {
         atomicAdd(&hd.d_state[VH_STATE_INSERT_FAILED], 1u);
-        failed[1u + atomicAdd(&failed[0], 1u)] = i;
+        const uint32_t k = atomicAdd(&failed[0], 1u);
+        failed[1u + 2u * k] = i;
+        failed[2u + 2u * k] = id;
+        hd.d_heap[heapCountPrev - i] = kStreamInNoSlot; // (above the counter once the pass is committed)
     }
 }
 __global__ __launch_bounds__(256) void k_stream_in_pass2_dev(VhHashData hd, uint32_t n, const VhVoxel* blocks)
@@ -4095,17 +4102,30 @@ __global__ __launch_bounds__(256) void k_stream_in_pass2_dev(VhHashData hd, uint
     if (b >= n) return;
     const uint32_t heapCountPrev = hd.d_heapCounter[0];
     if (n > heapCountPrev + 1u) return;
-    const uint32_t ptr = hd.d_heap[heapCountPrev - b] * VH_SDF_BLOCK_VOXELS;
-    *(reinterpret_cast<uint4*>(&hd.d_SDFBlocks[ptr]) + threadIdx.x) = reinterpret_cast<const uint4*>(blocks)[(size_t)b * 256 + threadIdx.x];
+    const uint32_t id = hd.d_heap[heapCountPrev - b];
+    if (id == kStreamInNoSlot) return; // (a free block: zero already)
+    *(reinterpret_cast<uint4*>(&hd.d_SDFBlocks[id * VH_SDF_BLOCK_VOXELS]) + threadIdx.x) = reinterpret_cast<const uint4*>(blocks)[(size_t)b * 256 + threadIdx.x];
 }
-__global__ void k_stream_in_commit(VhHashData hd, uint32_t n, const uint32_t* failed, uint32_t* mapped, uint32_t tag)
+__global__ void k_stream_in_commit(VhHashData hd, uint32_t n, uint32_t* failed, uint32_t* bitMask, uint32_t chunkBit, uint32_t* mapped, uint32_t tag)
 {
     const uint32_t heapCountPrev = hd.d_heapCounter[0];
     const bool exhausted = n > heapCountPrev + 1u;
-    if (!exhausted) hd.d_heapCounter[0] = heapCountPrev - n;
-    else atomicAdd(&hd.d_state[VH_STATE_HEAP_UNDERFLOW], 1u);
-    mapped[0] = failed[0];
-    mapped[1] = heapCountPrev;
+    const uint32_t nFailed = failed[0];
+    if (!exhausted) {
+        // consumeHeap n times, then appendHeap (DSC/VoxelUtilHashSDF.h:525-529) of the blocks that found no slot
+        const uint32_t counter = heapCountPrev - n;
+        for (uint32_t k = 0; k < nFailed; k++) {
+            hd.d_heap[counter + 1u + k] = failed[2u + 2u * k];
+            mapped[4u + k] = failed[1u + 2u * k];
+        }
+        hd.d_heapCounter[0] = counter + nFailed;
+        if (nFailed != 0u && bitMask && chunkBit != 0xffffffffu) atomicOr(&bitMask[chunkBit >> 5], 1u << (chunkBit & 31u));
+    } else {
+        atomicAdd(&hd.d_state[VH_STATE_HEAP_UNDERFLOW], 1u);
+    }
+    failed[0] = 0u; // (for the next pass)
+    mapped[0] = nFailed;
+    mapped[1] = 0u;
     mapped[3] = exhausted ? 1u : 0u;
     __atomic_thread_fence(__ATOMIC_RELEASE);
     __hip_atomic_store(&mapped[2], tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -4113,17 +4133,13 @@ __global__ void k_stream_in_commit(VhHashData hd, uint32_t n, const uint32_t* fa
 
 // chunkToGlobalHashPass1Kernel :143-160
 __global__ __launch_bounds__(64) void k_stream_in_pass1(VhHashData hd, VhHashParams hp, uint32_t n, uint32_t heapCountPrev,
-                                                        const VhSDFBlockDesc* descs, int32_t lockToken, uint32_t* failed)
+                                                        const VhSDFBlockDesc* descs, int32_t lockToken)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t ptr = hd.d_heap[heapCountPrev - i] * VH_SDF_BLOCK_VOXELS;
     const VhSDFBlockDesc dsc = descs[i];
-    if (!insert_hash_entry(hd, hp, mki3(dsc.pos[0], dsc.pos[1], dsc.pos[2]), (int)ptr, lockToken)) {
-        atomicAdd(&hd.d_state[VH_STATE_INSERT_FAILED], 1u);
-        // which ones: failed[0] counts them, failed[1 ...] lists their indices (the caller takes them back)
-        if (failed) failed[1u + atomicAdd(&failed[0], 1u)] = i;
-    }
+    if (!insert_hash_entry(hd, hp, mki3(dsc.pos[0], dsc.pos[1], dsc.pos[2]), (int)ptr, lockToken)) atomicAdd(&hd.d_state[VH_STATE_INSERT_FAILED], 1u);
 }
 
 // chunkToGlobalHashPass2Kernel :181-189
@@ -4876,30 +4892,23 @@ int vh_stream_in_device(const VhHashData* hd, const VhHashParams* hp, uint32_t n
     if (!hd || !hp || !d_descs || !d_blocks || !d_failed || !d_mapped) return VH_ERR_BAD_ARGUMENT;
     if (hp->m_hashNumBuckets < 2) return VH_ERR_BAD_ARGUMENT;
     hipStream_t s = (hipStream_t)stream;
-    VH_HIP(hipMemsetAsync(d_failed, 0, sizeof(uint32_t), s));
     if (n != 0) {
         k_stream_in_pass1_dev<<<cdiv(n, 64), 64, 0, s>>>(*hd, *hp, n, d_descs, lockToken, d_failed, d_bitMask, chunkBit);
         k_stream_in_pass2_dev<<<n, 256, 0, s>>>(*hd, n, d_blocks);
     }
-    k_stream_in_commit<<<1, 1, 0, s>>>(*hd, n, d_failed, d_mapped, tag);
-    return vh_last_launch_error();
-}
-
-int vh_stream_in_pass1_report(const VhHashData* hd, const VhHashParams* hp, uint32_t n, uint32_t heapCountPrev,
-                              const VhSDFBlockDesc* d_descs, int32_t lockToken, uint32_t* d_failed, vhStream_t stream)
-{
-    if (!hd || !hp || !d_descs) return VH_ERR_BAD_ARGUMENT;
-    if (n == 0) return VH_OK;
-    if (n > heapCountPrev + 1u) return VH_ERR_HEAP_EXHAUSTED;
-    if (hp->m_hashNumBuckets < 2) return VH_ERR_BAD_ARGUMENT;
-    k_stream_in_pass1<<<cdiv(n, 64), 64, 0, (hipStream_t)stream>>>(*hd, *hp, n, heapCountPrev, d_descs, lockToken, d_failed);
+    k_stream_in_commit<<<1, 1, 0, s>>>(*hd, n, d_failed, d_bitMask, chunkBit, d_mapped, tag);
     return vh_last_launch_error();
 }
 
 int vh_stream_in_pass1(const VhHashData* hd, const VhHashParams* hp, uint32_t n, uint32_t heapCountPrev,
                        const VhSDFBlockDesc* d_descs, int32_t lockToken, vhStream_t stream)
 {
-    return vh_stream_in_pass1_report(hd, hp, n, heapCountPrev, d_descs, lockToken, nullptr, stream);
+    if (!hd || !hp || !d_descs) return VH_ERR_BAD_ARGUMENT;
+    if (n == 0) return VH_OK;
+    if (n > heapCountPrev + 1u) return VH_ERR_HEAP_EXHAUSTED;
+    if (hp->m_hashNumBuckets < 2) return VH_ERR_BAD_ARGUMENT;
+    k_stream_in_pass1<<<cdiv(n, 64), 64, 0, (hipStream_t)stream>>>(*hd, *hp, n, heapCountPrev, d_descs, lockToken);
+    return vh_last_launch_error();
 }
 
 int vh_stream_in_pass2(const VhHashData* hd, const VhHashParams* hp, uint32_t n, uint32_t heapCountPrev,

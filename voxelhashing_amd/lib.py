@@ -66,7 +66,6 @@ PROTOTYPES = {
     "vh_publish_count": (C.c_int, [_VP, _VP, C.c_uint32, _VP]),
     "vh_stream_in_device": (C.c_int, [P(T.HashData), P(T.HashParams), C.c_uint32, _VP, _VP, C.c_int32, _VP, _VP, C.c_uint32, _VP, C.c_uint32, _VP]),
     "vh_stream_in_pass1": (C.c_int, [P(T.HashData), P(T.HashParams), C.c_uint32, C.c_uint32, _VP, C.c_int32, _VP]),
-    "vh_stream_in_pass1_report": (C.c_int, [P(T.HashData), P(T.HashParams), C.c_uint32, C.c_uint32, _VP, C.c_int32, _VP, _VP]),
     "vh_stream_in_pass2": (C.c_int, [P(T.HashData), P(T.HashParams), C.c_uint32, C.c_uint32, _VP, _VP, _VP]),
     "vh_synth_frame": (C.c_int, [_VP, C.c_int, C.c_int, _F16, P(T.DepthCameraParams), _VP, _VP, _VP]),
     "vh_debug_hash_ops": (C.c_int, [P(T.HashData), P(T.HashParams), _VP, _VP, C.c_uint32, _VP]),
