@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py -- never by the product package.
-PARITY UNPINNED: see oracle/vh_oracle.h.
+Parity status: see oracle/vh_oracle.h.
 """
 import ctypes as C
 import os
@@ -82,6 +82,22 @@ def lib(omp=False):
     L.vho_camera_to_screen_int.argtypes = [P(T.DepthCameraParams), P(C.c_float), P(C.c_int32)]
     L.vho_combine_voxel.argtypes = [P(T.HashParams), T.Voxel, T.Voxel]
     L.vho_combine_voxel.restype = T.Voxel
+    f, i32 = C.c_float, C.c_int32
+    for _n, _a, _r in (
+            ("vho_world_to_sdf_block", [P(T.HashParams), P(f), P(i32)], None),
+            ("vho_sdf_block_to_world", [P(T.HashParams), P(i32), P(f)], None),
+            ("vho_virtual_voxel_pos_to_local_index", [P(i32)], C.c_int),
+            ("vho_get_truncation", [P(T.HashParams), f], f),
+            ("vho_camera_to_screen_float", [P(T.DepthCameraParams), P(f), P(f)], None),
+            ("vho_camera_to_proj_z", [P(T.DepthCameraParams), f], f),
+            ("vho_proj_to_camera_z", [P(T.DepthCameraParams), f], f),
+            ("vho_depth_to_skeleton", [P(T.DepthCameraParams), C.c_uint32, C.c_uint32, f, P(f)], None),
+            ("vho_trilinear", [P(T.HashData), P(T.HashParams), P(f), P(f), P(C.c_uint8)], C.c_int),
+            ("vho_intersect_bisection", [P(T.HashData), P(T.HashParams), P(f), P(f), f, f, f, f, P(f), P(C.c_uint8)],
+             C.c_int),
+            ("vho_gradient_for_point", [P(T.HashData), P(T.HashParams), P(f), P(f)], None)):
+        getattr(L, _n).argtypes = _a
+        getattr(L, _n).restype = _r
     L.vho_scene_integrate.argtypes = [P(T.HashData), P(T.HashParams), P(T.SceneOptions), P(C.c_uint32), P(C.c_float),
                                       P(T.DepthCameraData), P(T.DepthCameraParams), C.c_void_p]
     L.vho_raycast_render.argtypes = [P(T.HashData), P(T.HashParams), P(T.RayCastData), P(T.DepthCameraParams),

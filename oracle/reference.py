@@ -1,0 +1,170 @@
+"""ctypes wrapper of oracle/_ref/libvh_ref.so: the reference's own voxel-hashing code, compiled for the CPU.
+
+TEST INFRASTRUCTURE ONLY, like oracle.py.  `__graft_entry__.build()` makes the library (oracle/ref/Makefile) when the
+reference tree is present; nothing here reads that tree.  Every function takes the same structs as its vho_* twin in
+oracle/vh_oracle.c, so a test runs both on two copies of one state (`RefScene` shares an OracleScene's buffers).
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from voxelhashing_amd import vhtypes as T
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+PATH = os.path.join(_HERE, "_ref", "libvh_ref.so")
+_LIB = []
+
+
+def available():
+    return os.path.exists(PATH)
+
+
+def lib():
+    if _LIB:
+        return _LIB[0]
+    L = C.CDLL(PATH)
+    P, f, i32, u32, vp = C.POINTER, C.c_float, C.c_int32, C.c_uint32, C.c_void_p
+    HD, HP, CP, RP = P(T.HashData), P(T.HashParams), P(T.DepthCameraParams), P(T.RayCastParams)
+    sig = {
+        "vhr_compute_hash_pos": ([HP, P(i32)], u32),
+        "vhr_world_to_virtual_voxel_pos": ([HP, P(f), P(i32)], None),
+        "vhr_virtual_voxel_pos_to_sdf_block": ([P(i32), P(i32)], None),
+        "vhr_world_to_sdf_block": ([HP, P(f), P(i32)], None),
+        "vhr_sdf_block_to_world": ([HP, P(i32), P(f)], None),
+        "vhr_virtual_voxel_pos_to_world": ([HP, P(i32), P(f)], None),
+        "vhr_virtual_voxel_pos_to_local_index": ([P(i32)], C.c_int),
+        "vhr_linearize_voxel_pos": ([P(i32)], u32),
+        "vhr_delinearize_voxel_index": ([u32, P(i32)], None),
+        "vhr_is_block_in_frustum": ([HP, CP, P(i32)], C.c_int),
+        "vhr_get_truncation": ([HP, f], f),
+        "vhr_combine_voxel": ([HP, T.Voxel, T.Voxel], T.Voxel),
+        "vhr_camera_to_screen_float": ([CP, P(f), P(f)], None),
+        "vhr_camera_to_screen_int": ([CP, P(f), P(i32)], None),
+        "vhr_camera_to_proj": ([CP, P(f), P(f)], None),
+        "vhr_camera_to_proj_z": ([CP, f], f),
+        "vhr_depth_to_skeleton": ([CP, u32, u32, f, P(f)], None),
+        "vhr_proj_to_camera_z": ([CP, f], f),
+        "vhr_get_hash_entry": ([HD, HP, P(i32)], T.HashEntry),
+        "vhr_alloc_block": ([HD, HP, P(i32)], None),
+        "vhr_delete_hash_entry_element": ([HD, HP, P(i32)], C.c_int),
+        "vhr_insert_hash_entry_bucket": ([HD, HP, P(T.HashEntry)], C.c_int),
+        "vhr_reset": ([HD, HP], None),
+        "vhr_reset_bucket_mutex": ([HD, HP], None),
+        "vhr_mat4_inverse": ([P(f), P(f)], None),
+        "vhr_alloc": ([HD, HP, P(T.DepthCameraData), CP, vp, C.c_int], None),
+        "vhr_integrate": ([HD, HP, P(T.DepthCameraData), CP], None),
+        "vhr_starve": ([HD, HP], None),
+        "vhr_gc_free": ([HD, HP], None),
+        "vhr_render": ([HD, HP, P(T.RayCastData), CP, RP], None),
+        "vhr_compute_normals": ([vp, vp, u32, u32], None),
+        "vhr_trilinear": ([HD, HP, P(f), P(f), P(C.c_uint8)], C.c_int),
+        "vhr_intersect_bisection": ([HD, HP, P(f), P(f), f, f, f, f, P(f), P(C.c_uint8)], C.c_int),
+        "vhr_gradient_for_point": ([HD, HP, P(f), P(f)], None),
+    }
+    for name, (args, res) in sig.items():
+        fn = getattr(L, name)
+        fn.argtypes = args
+        fn.restype = res
+    _LIB.append(L)
+    return L
+
+
+def compute_normals(depth4):
+    H, W, _ = depth4.shape
+    d4 = np.ascontiguousarray(depth4, dtype=np.float32)
+    out = np.empty_like(d4)
+    lib().vhr_compute_normals(out.ctypes.data, d4.ctypes.data, W, H)
+    return out
+
+
+def mat4_inverse(m):
+    m = np.ascontiguousarray(m, dtype=np.float32).reshape(16)
+    out = np.empty(16, dtype=np.float32)
+    lib().vhr_mat4_inverse(m.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_float)))
+    return out
+
+
+class RefScene:
+    """The reference's kernels on the buffers and parameters of an oracle.OracleScene (which owns them)."""
+
+    def __init__(self, scene):
+        self.s = scene
+        self.L = lib()
+
+    # -- a scene run by the reference's code alone: reset, transform, mutex, offline alloc, compactify ----------
+    def reset(self):
+        self.s.hp.m_numOccupiedBlocks = 0
+        self.L.vhr_reset(C.byref(self.s.hd), C.byref(self.s.hp))
+
+    def set_transform(self, transform):
+        m = np.ascontiguousarray(transform, dtype=np.float32).reshape(16)
+        self.s.hp.m_rigidTransform = (C.c_float * 16)(*m.tolist())
+        self.s.hp.m_rigidTransformInverse = (C.c_float * 16)(*mat4_inverse(m).tolist())
+
+    def reset_mutex(self):
+        self.L.vhr_reset_bucket_mutex(C.byref(self.s.hd), C.byref(self.s.hp))
+
+    def alloc_offline(self, depth, color, raster=False):
+        """CUDASceneRepHashSDF::alloc with offline processing: passes until the heap stops moving"""
+        prev = None
+        while prev != self.s.heap_free_count():
+            prev = self.s.heap_free_count()
+            self.reset_mutex()
+            self.alloc(depth, color, raster=raster)
+
+    def compactify(self):
+        """the set compactifyHashAllInOneKernel lists (it needs a barrier, so it is not run): the live entries whose
+        block passes the reference's frustum test, in table order (the kernel's order is a matter of scheduling)"""
+        s = self.s
+        table = s.hash_table()
+        live = np.nonzero(table["ptr"] != T.FREE_ENTRY)[0]
+        keep = [i for i in live if self.L.vhr_is_block_in_frustum(
+            C.byref(s.hp), C.byref(s.cp), np.ascontiguousarray(table["pos"][i]).ctypes.data_as(C.POINTER(C.c_int32)))]
+        out = s.array("d_hashCompactified", T.HASH_ENTRY_DTYPE, len(keep))
+        out[:] = table[keep]
+        s.array("d_hashCompactifiedCounter", np.int32, 1)[0] = len(keep)
+        s.hp.m_numOccupiedBlocks = len(keep)
+        return len(keep)
+
+    def alloc(self, depth, color=None, bitmask=None, raster=True):
+        cam = self.s._cam(depth, color)
+        bm = None if bitmask is None else bitmask.ctypes.data
+        self.L.vhr_alloc(C.byref(self.s.hd), C.byref(self.s.hp), C.byref(cam), C.byref(self.s.cp), bm, int(raster))
+
+    def integrate_depth_map(self, depth, color):
+        cam = self.s._cam(depth, color)
+        self.L.vhr_integrate(C.byref(self.s.hd), C.byref(self.s.hp), C.byref(cam), C.byref(self.s.cp))
+
+    def starve(self):
+        self.L.vhr_starve(C.byref(self.s.hd), C.byref(self.s.hp))
+
+    def gc_free(self):
+        self.L.vhr_gc_free(C.byref(self.s.hd), C.byref(self.s.hp))
+
+    def render(self, ray_params):
+        s = self.s
+        self.L.vhr_render(C.byref(s.hd), C.byref(s.hp), C.byref(s.rd), C.byref(s.cp), C.byref(ray_params))
+        return dict(depth=s.rc_depth.copy(), depth4=s.rc_depth4.copy(), normals=s.rc_normals.copy(),
+                    colors=s.rc_colors.copy())
+
+    def alloc_block(self, pos):
+        p = np.asarray(pos, dtype=np.int32)
+        self.L.vhr_alloc_block(C.byref(self.s.hd), C.byref(self.s.hp), p.ctypes.data_as(C.POINTER(C.c_int32)))
+
+    def delete_block(self, pos):
+        p = np.asarray(pos, dtype=np.int32)
+        return self.L.vhr_delete_hash_entry_element(C.byref(self.s.hd), C.byref(self.s.hp),
+                                                    p.ctypes.data_as(C.POINTER(C.c_int32)))
+
+    def insert_entry_bucket(self, pos, ptr):
+        e = T.HashEntry()
+        e.pos = (C.c_int32 * 3)(*[int(v) for v in pos])
+        e.ptr = int(ptr)
+        e.offset = 0
+        return self.L.vhr_insert_hash_entry_bucket(C.byref(self.s.hd), C.byref(self.s.hp), C.byref(e))
+
+    def get_entry(self, pos):
+        p = np.asarray(pos, dtype=np.int32)
+        e = self.L.vhr_get_hash_entry(C.byref(self.s.hd), C.byref(self.s.hp), p.ctypes.data_as(C.POINTER(C.c_int32)))
+        return (tuple(e.pos), e.ptr, e.offset)

@@ -21,7 +21,7 @@
  * same file built with -fopenmp, is bench.py's all-core CPU baseline
  * (SURVEY.md 8(d)); a test holds it to the serial build's results.
  *
- * PARITY UNPINNED (see vh_oracle.h).
+ * Parity status: see vh_oracle.h.
  */
 #include "vh_oracle.h"
 
@@ -1163,6 +1163,44 @@ void vho_camera_to_screen_int(const VhDepthCameraParams* cp, const float p[3], i
     out[0] = f2i(sx + 0.5f); out[1] = f2i(sy + 0.5f);
 }
 VhVoxel vho_combine_voxel(const VhHashParams* hp, VhVoxel v0, VhVoxel v1) { return combine_voxel(hp, v0, v1); }
+void vho_world_to_sdf_block(const VhHashParams* hp, const float p[3], int32_t out[3])
+{
+    i3 r = world_to_block(hp, mk3(p[0], p[1], p[2]));
+    out[0] = r.x; out[1] = r.y; out[2] = r.z;
+}
+void vho_sdf_block_to_world(const VhHashParams* hp, const int32_t b[3], float out[3])
+{
+    f3 r = block_to_world(hp, mki3(b[0], b[1], b[2]));
+    out[0] = r.x; out[1] = r.y; out[2] = r.z;
+}
+int vho_virtual_voxel_pos_to_local_index(const int32_t v[3]) { return vvp_to_local_index(mki3(v[0], v[1], v[2])); }
+float vho_get_truncation(const VhHashParams* hp, float z) { return get_truncation(hp, z); }
+void vho_camera_to_screen_float(const VhDepthCameraParams* cp, const float p[3], float out[2])
+{
+    cam_to_screen_float(cp, mk3(p[0], p[1], p[2]), &out[0], &out[1]);
+}
+float vho_camera_to_proj_z(const VhDepthCameraParams* cp, float z) { return cam_to_proj_z(cp, z); }
+float vho_proj_to_camera_z(const VhDepthCameraParams* cp, float z) { return proj_to_cam_z(cp, z); }
+void vho_depth_to_skeleton(const VhDepthCameraParams* cp, uint32_t ux, uint32_t uy, float depth, float out[3])
+{
+    f3 r = depth_to_skeleton(cp, ux, uy, depth);
+    out[0] = r.x; out[1] = r.y; out[2] = r.z;
+}
+int vho_trilinear(const VhHashData* hd, const VhHashParams* hp, const float pos[3], float* dist, uint8_t color[3])
+{
+    return trilinear(hd, hp, mk3(pos[0], pos[1], pos[2]), dist, color);
+}
+int vho_intersect_bisection(const VhHashData* hd, const VhHashParams* hp, const float camPos[3], const float dir[3],
+                            float d0, float r0, float d1, float r1, float* alpha, uint8_t color[3])
+{
+    return intersect_bisection(hd, hp, mk3(camPos[0], camPos[1], camPos[2]), mk3(dir[0], dir[1], dir[2]),
+                               d0, r0, d1, r1, alpha, color);
+}
+void vho_gradient_for_point(const VhHashData* hd, const VhHashParams* hp, const float pos[3], float out[3])
+{
+    f3 r = gradient_for_point(hd, hp, mk3(pos[0], pos[1], pos[2]));
+    out[0] = r.x; out[1] = r.y; out[2] = r.z;
+}
 
 /* ------------------------------------------------------------------------- */
 /* host classes                                                              */

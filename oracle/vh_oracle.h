@@ -6,13 +6,15 @@
  * function in vh_oracle.c).  Only tests/, __graft_entry__.smoke() and the
  * cpu_baseline leg of bench.py may load it; the product library never does.
  *
- * PARITY UNPINNED: the reference ships no tests, golden vectors or fixtures for
- * this path and cannot be built in this image without
- * writing stand-ins for the CUDA toolkit headers it includes (cuda_runtime.h,
- * texture references), which the build rules forbid.  The only reference-run
- * facts available are the block/hit counts recorded in SURVEY.md section 6 and
- * section 8(c); tests/test_oracle_known_answers.py checks the oracle against
- * those.  Everything else is pinned by this restatement alone.
+ * PARITY: pinned bit for bit to the reference's own code compiled for the CPU
+ * (oracle/_ref/libvh_ref.so, recipe in oracle/ref/, tests/test_reference_pinning.py)
+ * for the hash, the voxel/block/world conversions, the frustum test, the
+ * projection, combineVoxel, the ray caster's sampling, the table operations
+ * and the alloc / integrate / starve / GC-free / render / normals kernels
+ * (DESIGN.md section 2 lists what is and is not pinned).  Compactify, GC
+ * identify, streaming, marching cubes and the sensor maps are pinned by this
+ * restatement, the reference-run counts of SURVEY.md section 6 / section 8(c)
+ * (tests/test_oracle_known_answers.py) and the checks of DESIGN.md section 2.
  *
  * All pointers in VhHashData / VhDepthCameraData / VhRayCastData are HOST
  * pointers here.  The extension buffers of VhHashData are ignored.
@@ -77,6 +79,19 @@ void vho_virtual_voxel_pos_to_sdf_block(const int32_t v[3], int32_t out[3]);
 int vho_is_block_in_frustum(const VhHashParams* hp, const VhDepthCameraParams* cp, const int32_t blk[3]);
 void vho_camera_to_screen_int(const VhDepthCameraParams* cp, const float p[3], int32_t out[2]);
 VhVoxel vho_combine_voxel(const VhHashParams* hp, VhVoxel v0, VhVoxel v1);
+void vho_world_to_sdf_block(const VhHashParams* hp, const float p[3], int32_t out[3]);
+void vho_sdf_block_to_world(const VhHashParams* hp, const int32_t b[3], float out[3]);
+int vho_virtual_voxel_pos_to_local_index(const int32_t v[3]);
+float vho_get_truncation(const VhHashParams* hp, float z);
+void vho_camera_to_screen_float(const VhDepthCameraParams* cp, const float p[3], float out[2]);
+float vho_camera_to_proj_z(const VhDepthCameraParams* cp, float z);
+float vho_proj_to_camera_z(const VhDepthCameraParams* cp, float z);
+void vho_depth_to_skeleton(const VhDepthCameraParams* cp, uint32_t ux, uint32_t uy, float depth, float out[3]);
+/* the ray caster's sampling (DSC/RayCastSDFUtil.h:97-195); dist / alpha / color are written as the reference's are */
+int vho_trilinear(const VhHashData* hd, const VhHashParams* hp, const float pos[3], float* dist, uint8_t color[3]);
+int vho_intersect_bisection(const VhHashData* hd, const VhHashParams* hp, const float camPos[3], const float dir[3],
+                            float d0, float r0, float d1, float r1, float* alpha, uint8_t color[3]);
+void vho_gradient_for_point(const VhHashData* hd, const VhHashParams* hp, const float pos[3], float out[3]);
 
 /* CUDASceneRepHashSDF::integrate (DSC/CUDASceneRepHashSDF.h:64-83) on an
  * oracle scene: hp is updated in place (transform, inverse, numOccupied).

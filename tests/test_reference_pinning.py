@@ -1,0 +1,589 @@
+"""The oracle against the reference's own code, compiled for the CPU (oracle/_ref/libvh_ref.so, made by
+`__graft_entry__.build()` through oracle/ref/ when the reference tree is present).
+
+The HIP kernels equal oracle/vh_oracle.c bit for bit (the rest of the suite); these tests close the other link: each
+vho_* function against its reference twin, on seeded random inputs and on the cliffs, and the reference's integrate,
+alloc, starve, GC-free, render and normals kernels on the same hash state as the oracle's.  Both builds follow one
+numerical contract (IEEE fp32, one rounding per operation, no FMA contraction, serial thread order), so every
+comparison is bit for bit.  The one documented difference that reaches these functions -- a float -> int conversion
+out of the int range, which the host build of the reference does with x86's rules (INT_MIN) and the oracle with the
+device's (saturate, NaN -> 0) -- is asserted exactly where it applies.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle import oracle as O
+from oracle import reference as R
+from voxelhashing_amd import synth, vhtypes as T
+
+pytestmark = pytest.mark.skipif(not R.available(), reason="oracle/_ref/libvh_ref.so is not built (build() makes it "
+                                "where the reference tree is present)")
+
+f32 = np.float32
+P = C.POINTER
+FP, IP, U8P = P(C.c_float), P(C.c_int32), P(C.c_uint8)
+
+
+@pytest.fixture(scope="module")
+def libs():
+    O.build()
+    return O.lib(), R.lib()
+
+
+def fp(a):
+    return a.ctypes.data_as(FP)
+
+
+def ip(a):
+    return a.ctypes.data_as(IP)
+
+
+def hparams(name="P4", buckets=500000, blocks=1 << 14, **kw):
+    return T.make_hash_params(buckets, blocks, **synth.PARAM_SETS[name], **kw)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def cliffs(vs, n):
+    """world coordinates at and one ulp around +-(k + 1/2) voxels, on both sides of the origin"""
+    k = np.arange(-n, n + 1, dtype=np.float32)
+    half = (k + f32(0.5)) * f32(vs)
+    out = [half, np.nextafter(half, f32(np.inf)), np.nextafter(half, f32(-np.inf)), k * f32(vs),
+           np.array([0.0, -0.0, f32(vs) * f32(0.5), -f32(vs) * f32(0.5)], dtype=np.float32)]
+    return np.concatenate(out).astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# device functions
+# ---------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("buckets", [500000, 1 << 18, 2000000, 7, 1])
+def test_compute_hash_pos(libs, buckets):
+    Lo, Lr = libs
+    hp = hparams(buckets=buckets)
+    rng = np.random.default_rng(buckets)
+    pts = [rng.integers(-2000, 2000, size=(4000, 3)), rng.integers(-2 ** 31, 2 ** 31, size=(2000, 3)),
+           np.array([[2 ** 31 - 1, -2 ** 31, 0], [-2 ** 31, -2 ** 31, -2 ** 31], [1, -1, 0], [0, 0, 0]])]
+    pts = np.concatenate(pts).astype(np.int32)
+    # (x, y, z) and (-x, -y, z): one bucket whenever x and y have equally many trailing zeros
+    mirror = pts.copy()
+    mirror[:, :2] = -mirror[:, :2].astype(np.int64)
+    pts = np.concatenate([pts, mirror.astype(np.int32)])
+    got = np.array([Lo.vho_compute_hash_pos(C.byref(hp), ip(np.ascontiguousarray(p))) for p in pts])
+    want = np.array([Lr.vhr_compute_hash_pos(C.byref(hp), ip(np.ascontiguousarray(p))) for p in pts])
+    assert np.array_equal(got, want)
+    assert (want < buckets).all()
+    if buckets == 500000:
+        n = len(pts) // 2
+        tz = lambda v: (int(v) & -int(v)).bit_length() if v else 33
+        same = [i for i in range(n) if tz(pts[i, 0]) == tz(pts[i, 1])]
+        assert len(same) > 100 and all(want[i] == want[n + i] for i in same)
+
+
+@pytest.mark.parametrize("name", ["P4", "P1", "P04"])
+def test_world_to_voxel_and_block(libs, name):
+    Lo, Lr = libs
+    hp = hparams(name)
+    vs = hp.m_virtualVoxelSize
+    rng = np.random.default_rng(7)
+    c = cliffs(vs, 40)
+    rand = rng.uniform(-30.0, 30.0, size=6000).astype(np.float32)
+    coords = np.concatenate([c, rand])
+    pts = np.stack([coords, np.roll(coords, 1), -coords], axis=1).astype(np.float32)
+    for p in pts:
+        p = np.ascontiguousarray(p)
+        a, b = np.zeros(3, np.int32), np.zeros(3, np.int32)
+        Lo.vho_world_to_virtual_voxel_pos(C.byref(hp), fp(p), ip(a))
+        Lr.vhr_world_to_virtual_voxel_pos(C.byref(hp), fp(p), ip(b))
+        assert np.array_equal(a, b), (p, a, b)
+        Lo.vho_world_to_sdf_block(C.byref(hp), fp(p), ip(a))
+        Lr.vhr_world_to_sdf_block(C.byref(hp), fp(p), ip(b))
+        assert np.array_equal(a, b), (p, a, b)
+    # the rounding is half away from zero: +-1/2 voxel lands on +-1, one ulp inside on 0
+    for s in (1.0, -1.0):
+        p = np.array([s * f32(vs) * f32(0.5)] * 3, np.float32)
+        q = np.nextafter(p, f32(0))
+        a, b = np.zeros(3, np.int32), np.zeros(3, np.int32)
+        Lr.vhr_world_to_virtual_voxel_pos(C.byref(hp), fp(p), ip(a))
+        Lr.vhr_world_to_virtual_voxel_pos(C.byref(hp), fp(q), ip(b))
+        assert list(a) == [int(s)] * 3 and list(b) == [0, 0, 0]
+
+
+def test_voxel_to_block_index_and_back(libs):
+    Lo, Lr = libs
+    hp = hparams("P4")
+    rng = np.random.default_rng(11)
+    vs = np.concatenate([np.stack(np.meshgrid(*[np.arange(-20, 21)] * 3), -1).reshape(-1, 3),
+                         rng.integers(-2 ** 27, 2 ** 27, size=(3000, 3))]).astype(np.int32)
+    for v in vs:
+        v = np.ascontiguousarray(v)
+        a, b = np.zeros(3, np.int32), np.zeros(3, np.int32)
+        Lo.vho_virtual_voxel_pos_to_sdf_block(ip(v), ip(a))
+        Lr.vhr_virtual_voxel_pos_to_sdf_block(ip(v), ip(b))
+        assert np.array_equal(a, b), (v, a, b)
+        assert Lo.vho_virtual_voxel_pos_to_local_index(ip(v)) == Lr.vhr_virtual_voxel_pos_to_local_index(ip(v))
+        wa, wb = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        Lo.vho_sdf_block_to_world(C.byref(hp), ip(a), fp(wa))
+        Lr.vhr_sdf_block_to_world(C.byref(hp), ip(a), fp(wb))
+        assert np.array_equal(bits(wa), bits(wb))
+    for idx in range(512):
+        d = np.zeros(3, np.int32)
+        Lr.vhr_delinearize_voxel_index(idx, ip(d))
+        assert list(d) == [idx % 8, (idx // 8) % 8, idx // 64]
+        assert Lr.vhr_linearize_voxel_pos(ip(d)) == idx
+
+
+def _pose(rng, spread=1.0):
+    a = rng.uniform(-np.pi, np.pi, 3)
+    cx, sx, cy, sy, cz, sz = np.cos(a[0]), np.sin(a[0]), np.cos(a[1]), np.sin(a[1]), np.cos(a[2]), np.sin(a[2])
+    Rm = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]]) \
+        @ np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    M = np.eye(4)
+    M[:3, :3] = Rm
+    M[:3, 3] = rng.uniform(-spread, spread, 3)
+    return M.astype(np.float32)
+
+
+@pytest.mark.parametrize("size", [(64, 48), (160, 120), (640, 480)])
+def test_block_in_frustum(libs, size):
+    Lo, Lr = libs
+    hp = hparams("P4")
+    cp = T.make_depth_camera_params(*size)
+    rng = np.random.default_rng(size[0])
+    inside = 0
+    for k in range(6):
+        M = _pose(rng) if k else np.eye(4, dtype=np.float32)
+        m = np.ascontiguousarray(M.reshape(16))
+        hp.m_rigidTransform = (C.c_float * 16)(*m.tolist())
+        hp.m_rigidTransformInverse = (C.c_float * 16)(*O.mat4_inverse(m).tolist())
+        # every block of a box around the camera: the image border and both depth limits are crossed many times
+        c = np.floor(M[:3, 3] / (8 * hp.m_virtualVoxelSize)).astype(int)
+        r = int(np.ceil(cp.m_sensorDepthWorldMax / (8 * hp.m_virtualVoxelSize))) + 1
+        g = np.arange(-r, r + 1, 2 if size[0] == 640 else 1)
+        for blk in np.stack(np.meshgrid(g, g, g), -1).reshape(-1, 3) + c:
+            blk = np.ascontiguousarray(blk, dtype=np.int32)
+            a = Lo.vho_is_block_in_frustum(C.byref(hp), C.byref(cp), ip(blk))
+            b = Lr.vhr_is_block_in_frustum(C.byref(hp), C.byref(cp), ip(blk))
+            assert a == b, (k, blk)
+            inside += b
+    assert inside > 100
+
+
+@pytest.mark.parametrize("size", [(64, 48), (640, 480)])
+def test_projection_and_back_projection(libs, size):
+    Lo, Lr = libs
+    cp = T.make_depth_camera_params(*size)
+    W, H = size
+    rng = np.random.default_rng(W)
+    n = 20000
+    z = np.concatenate([rng.uniform(0.05, 12.0, n - 6), [cp.m_sensorDepthWorldMin, cp.m_sensorDepthWorldMax,
+                                                          1e-3, 1.0, 4.0, 8.0]]).astype(np.float32)
+    u = rng.uniform(-0.6, W - 0.4, n).astype(np.float32)
+    v = rng.uniform(-0.6, H - 0.4, n).astype(np.float32)
+    pts = np.stack([(u - f32(cp.mx)) / f32(cp.fx) * z, (v - f32(cp.my)) / f32(cp.fy) * z, z], 1).astype(np.float32)
+    for p in pts:
+        p = np.ascontiguousarray(p)
+        a, b = np.zeros(2, np.float32), np.zeros(2, np.float32)
+        Lo.vho_camera_to_screen_float(C.byref(cp), fp(p), fp(a))
+        Lr.vhr_camera_to_screen_float(C.byref(cp), fp(p), fp(b))
+        assert np.array_equal(bits(a), bits(b))
+        ia, ib = np.zeros(2, np.int32), np.zeros(2, np.int32)
+        Lo.vho_camera_to_screen_int(C.byref(cp), fp(p), ip(ia))
+        Lr.vhr_camera_to_screen_int(C.byref(cp), fp(p), ip(ib))
+        assert np.array_equal(ia, ib), (p, ia, ib)
+    # the inverse on every pixel of the image's border and a grid inside, at the depth limits and between
+    for uy in sorted(set([0, 1, H // 2, H - 2, H - 1])):
+        for ux in range(W):
+            for d in (cp.m_sensorDepthWorldMin, 0.77, cp.m_sensorDepthWorldMax):
+                a, b = np.zeros(3, np.float32), np.zeros(3, np.float32)
+                Lo.vho_depth_to_skeleton(C.byref(cp), ux, uy, d, fp(a))
+                Lr.vhr_depth_to_skeleton(C.byref(cp), ux, uy, d, fp(b))
+                assert np.array_equal(bits(a), bits(b))
+    for zz in np.concatenate([z[:500], np.linspace(0, 1, 101, dtype=np.float32)]):
+        assert bits(Lo.vho_camera_to_proj_z(C.byref(cp), zz)) == bits(Lr.vhr_camera_to_proj_z(C.byref(cp), zz))
+        assert bits(Lo.vho_proj_to_camera_z(C.byref(cp), zz)) == bits(Lr.vhr_proj_to_camera_z(C.byref(cp), zz))
+
+
+def test_projection_out_of_int_range_is_off_screen_in_both(libs):
+    """The documented difference: a projected coordinate outside the int range (or NaN) converts to INT_MIN in the
+    host build of the reference and saturates (NaN -> 0) in the oracle, as on the device.  Both land off screen
+    except NaN, which only arises at z == 0 with x == 0, a point no kernel projects (it is behind the near plane)."""
+    Lo, Lr = libs
+    cp = T.make_depth_camera_params(640, 480)
+    for p in ([1e30, 1.0, 1e-3], [-1e30, -1.0, 1e-3], [3e6, -3e6, 1e-3]):
+        p = np.array(p, np.float32)
+        a, b = np.zeros(2, np.int32), np.zeros(2, np.int32)
+        Lo.vho_camera_to_screen_int(C.byref(cp), fp(p), ip(a))
+        Lr.vhr_camera_to_screen_int(C.byref(cp), fp(p), ip(b))
+        sx = np.array([p[0] * f32(cp.fx) / p[2] + f32(cp.mx), p[1] * f32(cp.fy) / p[2] + f32(cp.my)], np.float32) + f32(0.5)
+        for k in range(2):
+            ak, bk, dim = int(a[k]), int(b[k]), [cp.m_imageWidth, cp.m_imageHeight][k]
+            if abs(float(sx[k])) < 2 ** 31:
+                assert ak == bk
+            else:
+                assert bk == -2 ** 31 and ak == (2 ** 31 - 1 if sx[k] > 0 else -2 ** 31)
+                # as the unsigned screen position of integrate: off screen either way
+                assert (ak & 0xFFFFFFFF) >= dim and (bk & 0xFFFFFFFF) >= dim
+
+
+@pytest.mark.parametrize("wmax", [255, 100, 1])
+def test_combine_voxel(libs, wmax):
+    Lo, Lr = libs
+    hp = hparams("P4")
+    hp.m_integrationWeightMax = wmax
+    rng = np.random.default_rng(wmax)
+    ws = list(range(0, 256, 3)) + [254, 255]
+    n = 0
+    for w0 in ws:
+        for w1 in (0, 1, 2, 3, 10, 128, 254, 255):
+            v0, v1 = T.Voxel(), T.Voxel()
+            v0.sdf, v1.sdf = float(rng.normal(0, 0.1)), float(rng.normal(0, 0.1))
+            v0.color = (C.c_uint8 * 3)(*rng.integers(0, 256, 3).tolist())
+            v1.color = (C.c_uint8 * 3)(*[255, 0, int(rng.integers(0, 256))])
+            v0.weight, v1.weight = w0, w1
+            a = Lo.vho_combine_voxel(C.byref(hp), v0, v1)
+            b = Lr.vhr_combine_voxel(C.byref(hp), v0, v1)
+            assert bytes(a) == bytes(b), (w0, w1, bytes(a), bytes(b))
+            assert b.weight == min(wmax, w0 + w1)
+            n += 1
+    # the colour average rounds halves up: (a + b) / 2 + 1/2, truncated
+    for c0, c1 in ((0, 1), (1, 2), (254, 255), (0, 255), (7, 7)):
+        v0, v1 = T.Voxel(), T.Voxel()
+        v0.weight = v1.weight = 1
+        v0.color = (C.c_uint8 * 3)(c0, c1, c0)
+        v1.color = (C.c_uint8 * 3)(c1, c0, c0)
+        a, b = Lo.vho_combine_voxel(C.byref(hp), v0, v1), Lr.vhr_combine_voxel(C.byref(hp), v0, v1)
+        assert bytes(a) == bytes(b) and b.color[0] == (c0 + c1 + 1) // 2
+
+
+def _sphere_scene(name="P4", size=(160, 120), frames=2, off=(7.3, 5.1, 3.7)):
+    hp = hparams(name, buckets=1 << 16, blocks=1 << 14)
+    cp = T.make_depth_camera_params(*size)
+    sc = O.OracleScene(hp, cp, options=T.make_scene_options(offline=True, gc=False))
+    spheres = synth.S1_SPHERES.copy()
+    spheres[:, :3] += np.array(off)
+    poses = []
+    for k in range(frames):
+        q = np.array(synth.orbit_pose(k, 90), dtype=np.float32).copy()
+        q[3] += f32(off[0]); q[7] += f32(off[1]); q[11] += f32(off[2])
+        poses.append(q)
+        d, c = O.synth_frame(spheres, 0, q, cp)
+        sc.integrate(q, d, c)
+    return sc, spheres, poses
+
+
+@pytest.mark.parametrize("off", [(7.3, 5.1, 3.7), (-7.3, -5.1, -3.7)])  # positive and negative axes
+def test_trilinear_bisection_gradient(libs, off):
+    Lo, Lr = libs
+    sc, spheres, poses = _sphere_scene(off=off)
+    hd, hp = sc.hd, sc.hp
+    vs = hp.m_virtualVoxelSize
+    rng = np.random.default_rng(5)
+    # points near the surface of the first sphere, points on voxel centres and faces, and points at the edge of the
+    # allocated band, where a tap's block is missing
+    cx, cy, cz, r = spheres[0]
+    dirs = rng.normal(size=(6000, 3))
+    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
+    rad = r + rng.uniform(-0.35, 0.35, size=(6000, 1))
+    pts = (np.array([cx, cy, cz]) + dirs * rad).astype(np.float32)
+    snapped = (np.round(pts[:1500] / vs) * vs).astype(np.float32)
+    faces = ((np.floor(pts[1500:3000] / vs) + 0.5) * vs).astype(np.float32)
+    pts = np.concatenate([pts, snapped, faces, np.nextafter(faces, f32(np.inf))])
+    valid = invalid = 0
+    for p in pts:
+        p = np.ascontiguousarray(p)
+        da, db = np.zeros(1, np.float32), np.zeros(1, np.float32)
+        ca, cb = np.zeros(3, np.uint8), np.zeros(3, np.uint8)
+        a = Lo.vho_trilinear(C.byref(hd), C.byref(hp), fp(p), fp(da), ca.ctypes.data_as(U8P))
+        b = Lr.vhr_trilinear(C.byref(hd), C.byref(hp), fp(p), fp(db), cb.ctypes.data_as(U8P))
+        assert a == b and bits(da) == bits(db), (p, a, b, da, db)
+        if b:
+            assert np.array_equal(ca, cb)
+            valid += 1
+        else:
+            invalid += 1
+        ga, gb = np.zeros(3, np.float32), np.zeros(3, np.float32)
+        Lo.vho_gradient_for_point(C.byref(hd), C.byref(hp), fp(p), fp(ga))
+        Lr.vhr_gradient_for_point(C.byref(hd), C.byref(hp), fp(p), fp(gb))
+        assert np.array_equal(bits(ga), bits(gb)), (p, ga, gb)
+    assert valid > 1000 and invalid > 500
+    # a missing neighbour makes the sample invalid: a point whose dual cell straddles an allocated and a free block
+    table = sc.hash_table()
+    live = {tuple(e["pos"]) for e in table if e["ptr"] != T.FREE_ENTRY}
+    edge = next(b for b in sorted(live) if (b[0] + 1, b[1], b[2]) not in live)
+    p = ((np.array(edge) * 8 + np.array([7.9, 3.5, 3.5])) * vs).astype(np.float32)
+    d = np.zeros(1, np.float32)
+    assert Lr.vhr_trilinear(C.byref(hd), C.byref(hp), fp(p), fp(d), np.zeros(3, np.uint8).ctypes.data_as(U8P)) == 0
+    assert Lo.vho_trilinear(C.byref(hd), C.byref(hp), fp(p), fp(d), np.zeros(3, np.uint8).ctypes.data_as(U8P)) == 0
+    # bisection along rays from the camera through the sphere: the reference's three steps, bit for bit
+    cam = np.ascontiguousarray(poses[-1].reshape(4, 4)[:3, 3], dtype=np.float32)
+    hits = 0
+    for q in pts[:3000:3]:
+        dvec = (q - cam).astype(np.float32)
+        dvec = np.ascontiguousarray((dvec / np.float32(np.linalg.norm(dvec))).astype(np.float32))
+        t = f32(np.linalg.norm(q - cam))
+        r0, r1 = f32(t - f32(0.6) * f32(vs)), f32(t + f32(0.6) * f32(vs))
+        d0, d1 = f32(0.03), f32(-0.02)
+        aa, ab = np.zeros(1, np.float32), np.zeros(1, np.float32)
+        ca, cb = np.zeros(3, np.uint8), np.zeros(3, np.uint8)
+        a = Lo.vho_intersect_bisection(C.byref(hd), C.byref(hp), fp(cam), fp(dvec), d0, r0, d1, r1, fp(aa),
+                                       ca.ctypes.data_as(U8P))
+        b = Lr.vhr_intersect_bisection(C.byref(hd), C.byref(hp), fp(cam), fp(dvec), d0, r0, d1, r1, fp(ab),
+                                       cb.ctypes.data_as(U8P))
+        assert a == b and bits(aa) == bits(ab) and np.array_equal(ca, cb), (q, a, b, aa, ab)
+        hits += b
+    assert hits > 100
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# hash table operations
+# ---------------------------------------------------------------------------------------------------------------
+
+def _tables(buckets, blocks, max_list=7):
+    hp = T.make_hash_params(buckets, blocks, **synth.PARAM_SETS["P4"], max_collision_list=max_list)
+    cp = T.make_depth_camera_params(64, 48)
+    a, b = O.OracleScene(hp, cp), O.OracleScene(hp, cp)
+    return a, b, R.RefScene(b)
+
+
+def _assert_same_table(a, b, what):
+    assert np.array_equal(a.hash_table().view(np.uint8), b.hash_table().view(np.uint8)), what
+    assert np.array_equal(a.heap(), b.heap()), what
+    assert np.array_equal(a.array("d_heapCounter", np.uint32, 1), b.array("d_heapCounter", np.uint32, 1)), what
+    assert np.array_equal(a.array("d_hashBucketMutex", np.int32, a.hp.m_hashNumBuckets),
+                          b.array("d_hashBucketMutex", np.int32, b.hp.m_hashNumBuckets)), what
+
+
+def _positions_in_bucket(lib, hp, bucket, n, start=0):
+    out, x = [], start
+    while len(out) < n:
+        for y in range(-3, 4):
+            p = np.array([x, y, (x * 7 + y) % 5 - 2], np.int32)
+            if lib.vho_compute_hash_pos(C.byref(hp), ip(p)) == bucket:
+                out.append(p)
+        x += 1
+    return out[:n]
+
+
+@pytest.mark.parametrize("bucket", [3, 7])  # 7 is the last bucket: its list wraps past the end of the table
+def test_hash_table_sequences(libs, bucket):
+    Lo, _ = libs
+    a, b, rb = _tables(buckets=8, blocks=64, max_list=20)
+    hp = a.hp
+    ps = _positions_in_bucket(Lo, hp, bucket, 16)
+
+    def step(op, p, what):
+        if op == "alloc":
+            a.alloc_block(p)
+            rb.alloc_block(p)
+        elif op == "delete":
+            assert a.delete_block(p) == rb.delete_block(p), what
+        a.reset_mutex()
+        b.reset_mutex()
+        _assert_same_table(a, b, what)
+        assert a.get_entry(p) == rb.get_entry(p), what
+
+    # ten fill the bucket, the next six spill into its linked list (the last one of them past the table's end for
+    # bucket 7), a repeat changes nothing
+    for k, p in enumerate(ps):
+        step("alloc", p, f"alloc {k}")
+    step("alloc", ps[12], "repeat")
+    live = [tuple(e["pos"]) for e in a.hash_table() if e["ptr"] != T.FREE_ENTRY]
+    assert len(live) == 16
+    last = a.hash_table()[(bucket + 1) * 10 - 1]
+    assert last["offset"] != 0, "the bucket's last slot heads a list"
+    # deletions: from the middle of the list, of the list's head in the bucket (the next element moves up), from
+    # inside the bucket, a position that is absent, and the list's tail
+    step("delete", ps[12], "middle of the list")
+    step("delete", ps[9], "head of the list")
+    step("delete", ps[4], "inside the bucket")
+    step("delete", np.array([999, 999, 999], np.int32), "absent")
+    step("delete", ps[15], "tail of the list")
+    # re-allocation reuses freed slots and heap entries in the same order
+    for k in (4, 9, 12, 15):
+        step("alloc", ps[k], f"re-alloc {k}")
+    # other buckets too, and every lookup
+    for p in _positions_in_bucket(Lo, hp, (bucket + 1) % 8, 12, start=50):
+        step("alloc", p, "neighbour bucket")
+    for p in ps:
+        assert a.get_entry(p) == rb.get_entry(p)
+
+
+def test_heap_to_exhaustion(libs):
+    """Every block of the heap handed out, to the last one: both leave the counter at 0xFFFFFFFF.  One more alloc
+    would make the reference read d_heap[0xFFFFFFFF] (a fenced defect), so it is not made."""
+    Lo, _ = libs
+    a, b, rb = _tables(buckets=16, blocks=40)
+    rng = np.random.default_rng(3)
+    n = 0
+    while n < 40:
+        p = rng.integers(-50, 50, 3).astype(np.int32)
+        if a.get_entry(p)[1] != T.FREE_ENTRY:
+            continue
+        a.alloc_block(p)
+        rb.alloc_block(p)
+        a.reset_mutex()
+        b.reset_mutex()
+        _assert_same_table(a, b, f"alloc {n}")
+        n = 40 - (int(a.array("d_heapCounter", np.uint32, 1)[0]) + 1) % (1 << 32)
+    assert int(b.array("d_heapCounter", np.uint32, 1)[0]) == 0xFFFFFFFF
+    live = [e for e in b.hash_table() if e["ptr"] != T.FREE_ENTRY]
+    assert sorted(e["ptr"] // 512 for e in live) == list(range(40))
+
+
+def test_insert_hash_entry_bucket_part(libs):
+    """insertHashEntry while the home bucket has room (its list branch is a fenced defect)"""
+    Lo, _ = libs
+    a, b, rb = _tables(buckets=8, blocks=64)
+    ps = _positions_in_bucket(Lo, a.hp, 5, 10)
+    for k, p in enumerate(ps):
+        assert a.insert_entry(p, 512 * (63 - k)) == 1
+        assert rb.insert_entry_bucket(p, 512 * (63 - k)) == 1
+        _assert_same_table(a, b, f"insert {k}")
+    assert rb.insert_entry_bucket(_positions_in_bucket(Lo, a.hp, 5, 11)[10], 0) == -1
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# kernels on one hash state
+# ---------------------------------------------------------------------------------------------------------------
+
+def _copy_state(src, dst):
+    for field, dt, n in (("d_hash", T.HASH_ENTRY_DTYPE, src.num_entries()),
+                         ("d_SDFBlocks", T.VOXEL_DTYPE, src.hp.m_numSDFBlocks * 512),
+                         ("d_heap", np.uint32, src.hp.m_numSDFBlocks), ("d_heapCounter", np.uint32, 1),
+                         ("d_hashBucketMutex", np.int32, src.hp.m_hashNumBuckets)):
+        dst.array(field, dt, n)[:] = src.array(field, dt, n)
+    C.memmove(C.byref(dst.hp), C.byref(src.hp), C.sizeof(src.hp))
+
+
+def _assert_same_scene(a, b, what):
+    _assert_same_table(a, b, what)
+    assert np.array_equal(a.sdf_blocks().view(np.uint8), b.sdf_blocks().view(np.uint8)), what
+
+
+def _maps_equal(x, y, what):
+    for m in ("depth", "depth4", "colors", "normals"):
+        assert np.array_equal(bits(x[m]), bits(y[m])), f"{what}: map {m}"
+
+
+@pytest.mark.parametrize("name,size,off", [("P4", (64, 48), (7.3, 5.1, 3.7)), ("P4", (160, 120), (7.3, 5.1, 3.7)),
+                                          ("P1", (64, 48), (7.3, 5.1, 3.7)), ("P1", (160, 120), (7.3, 5.1, 3.7)),
+                                          ("P4", (160, 120), (-7.3, -5.1, -3.7)), ("P1", (64, 48), (-0.3, 0.2, -6.1))])
+def test_kernels_on_one_state(libs, name, size, off):
+    hp = hparams(name, buckets=1 << 15, blocks=1 << 13)
+    cp = T.make_depth_camera_params(*size)
+    a, b = O.OracleScene(hp, cp), O.OracleScene(hp, cp)
+    rb = R.RefScene(b)
+    off = np.array(off)
+    spheres = synth.S1_SPHERES.copy()
+    spheres[:, :3] += off
+    hits = 0
+    for k in range(4):
+        q = np.array(synth.orbit_pose(k, 90), dtype=np.float32).copy()
+        q[3] += f32(off[0]); q[7] += f32(off[1]); q[11] += f32(off[2])
+        d, c = O.synth_frame(spheres, 0, q, cp)
+        a.set_transform(q)
+        b.set_transform(q)
+        # alloc in raster order: the same pass, so the same slots and heap order
+        a.reset_mutex(); a.alloc(d, c)
+        b.reset_mutex(); rb.alloc(d, c, raster=True)
+        _assert_same_scene(a, b, f"frame {k}: alloc")
+        a.compactify(); b.compactify()
+        a.integrate_depth_map(d, c); rb.integrate_depth_map(d, c)
+        _assert_same_scene(a, b, f"frame {k}: integrate")
+        if k == 2:
+            a.starve(); rb.starve()
+            _assert_same_scene(a, b, f"frame {k}: starve")
+        a.gc_identify(); b.gc_identify()
+        a.reset_mutex(); b.reset_mutex()
+        a.gc_free(); rb.gc_free()
+        _assert_same_scene(a, b, f"frame {k}: gc free")
+        # ray casts of this state: the oracle's render sets the view; the reference renders with those parameters
+        want = a.render(q)
+        got = rb.render(a.rp)
+        got["normals"] = R.compute_normals(got["depth4"])
+        _maps_equal(want, got, f"frame {k}")
+        hits = max(hits, int((want["depth"] != -np.inf).sum()))
+    assert hits > size[0] * size[1] // 10
+    # the same frames with the reference's own launcher (8x8 tiles, a different thread order) and alloc passes until
+    # nothing changes: the same block set as the oracle's fixed point
+    c2, d2 = O.OracleScene(hp, cp), O.OracleScene(hp, cp)
+    r2 = R.RefScene(d2)
+    for k in range(2):
+        q = np.array(synth.orbit_pose(k, 90), dtype=np.float32).copy()
+        q[3] += f32(off[0]); q[7] += f32(off[1]); q[11] += f32(off[2])
+        d, c = O.synth_frame(spheres, 0, q, cp)
+        for s, alloc in ((c2, c2.alloc), (d2, lambda dd, cc: r2.alloc(dd, cc, raster=False))):
+            s.set_transform(q)
+            prev = -1
+            while s.heap_free_count() != prev:
+                prev = s.heap_free_count()
+                s.reset_mutex()
+                alloc(d, c)
+        blocks = lambda s: sorted(tuple(e["pos"]) for e in s.hash_table() if e["ptr"] != T.FREE_ENTRY)
+        assert blocks(c2) == blocks(d2), f"frame {k}: offline block set"
+
+
+def _render_variant(name, size, tweak):
+    sc, spheres, poses = _sphere_scene(name, size, frames=2)
+    base = sc.render(poses[-1])
+    rp = sc.rp
+    q = poses[-1].copy()
+    tweak(rp, q, sc, base)
+    want = sc.render(q)
+    b = O.OracleScene(sc.hp, sc.cp, ray_params=sc.rp)
+    _copy_state(sc, b)
+    got = R.RefScene(b).render(sc.rp)
+    if not sc.rp.m_useGradients:
+        got["normals"] = R.compute_normals(got["depth4"])
+    return want, got, int((base["depth"] != -np.inf).sum())
+
+
+def _start_inside(rp, q, sc, base):
+    # rays start at the median depth of the surface: inside the band of allocated blocks around it, in front of the
+    # surface for the far half of the pixels (which still hit) and behind it for the near half (which no longer do)
+    d = base["depth"][base["depth"] != -np.inf]
+    rp.m_minDepth = float(np.median(d))
+
+
+def _graze(rp, q, sc, base):
+    # the camera on a block corner, looking down +z: the centre rays run along block faces
+    vs8 = 8 * sc.hp.m_virtualVoxelSize
+    q[:] = np.eye(4, dtype=np.float32).reshape(16)
+    q[3], q[7], q[11] = [f32(np.round(v / vs8) * vs8) for v in (7.3, 5.1, 3.7 - 2.2)]
+
+
+def _depth_limits(rp, q, sc, base):
+    rp.m_minDepth = 1.2
+    rp.m_maxDepth = 2.05  # ends just behind the front surfaces: rays that reach the limit with no crossing
+
+
+def _gradients(rp, q, sc, base):
+    rp.m_useGradients = 1
+
+
+# hits the variant must keep, as a fraction of the unchanged view's: (at least, below)
+_HITS = {_start_inside: (0.25, 0.9), _graze: (0.1, 10.0), _depth_limits: (0.5, 1.0), _gradients: (1.0, 1.01)}
+
+
+@pytest.mark.parametrize("variant", [_start_inside, _graze, _depth_limits, _gradients], ids=lambda f: f.__name__[1:])
+@pytest.mark.parametrize("name,size", [("P4", (64, 48)), ("P1", (160, 120))])
+def test_render_variants(libs, variant, name, size):
+    want, got, base_hits = _render_variant(name, size, variant)
+    _maps_equal(want, got, variant.__name__)
+    hits = int((want["depth"] != -np.inf).sum())
+    lo, hi = _HITS[variant]
+    assert lo * base_hits <= hits < hi * base_hits, (hits, base_hits)
+
+
+def test_compute_normals(libs):
+    rng = np.random.default_rng(9)
+    for H, W in ((48, 64), (1, 5), (3, 3), (120, 160)):
+        d4 = rng.normal(size=(H, W, 4)).astype(np.float32)
+        d4[rng.random((H, W)) < 0.1, 0] = -np.inf
+        d4[H // 2, :, :3] = d4[H // 2, :1, :3]  # a row of equal points: zero-length normals
+        assert np.array_equal(bits(O.compute_normals(d4)), bits(R.compute_normals(d4)))
