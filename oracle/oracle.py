@@ -333,13 +333,19 @@ class OracleScene:
 
 def image_op(name, src, width, height, *args, out_channels=1, out_size=None, prefill=None):
     """oracle twin of voxelhashing_amd.engine.image_op"""
-    L = lib()
+    return call_image_op(lib(), "vho_", name, src, width, height, *args, out_channels=out_channels, out_size=out_size,
+                         prefill=prefill)
+
+
+def call_image_op(L, prefix, name, src, width, height, *args, out_channels=1, out_size=None, prefill=None):
+    """run L.<prefix><name> on one source image: the dispatcher of this module's image_op and of
+    oracle/reference.py's, whose functions take the same arguments"""
     src = np.ascontiguousarray(src)
     ow, oh = out_size if out_size else (width, height)
     out = np.zeros(ow * oh * out_channels, dtype=np.float32)
     if prefill is not None:
         out[:] = np.ascontiguousarray(prefill, dtype=np.float32).ravel()
-    fn = getattr(L, "vho_" + name)
+    fn = getattr(L, prefix + name)
     if name in ("resample_float_map", "resample_float4_map"):
         fn(out.ctypes.data, ow, oh, src.ctypes.data, width, height)
     elif name == "convert_depth_float_to_camera_space_float4":

@@ -3,11 +3,15 @@
  * programming guide's documented semantics.  It is just enough for the
  * reference's voxel-hashing sources to compile as plain host C++ (with
  * -D__CUDACC__) so that oracle/ref/vh_ref_wrap.cpp can run their device
- * functions and barrier-free kernels serially on the CPU.
+ * functions and kernels serially on the CPU.
  *
  * Contract (the oracle's, see oracle/vh_oracle.c):
- *   - kernels run one thread after the other (vhr_launch below); atomics are
- *     plain read-modify-writes;
+ *   - kernels run one workgroup after the other, blocks z, y, x, and within a
+ *     workgroup one thread after the other, threads z, y, x (vhr_launch below).
+ *     A workgroup whose threads reach __syncthreads runs them as cooperative
+ *     fibers (oracle/ref/vhr_launch.cpp): each thread runs up to the barrier,
+ *     and when all have arrived they resume, in the same order.  Atomics are
+ *     plain read-modify-writes; __shared__ is `static` (one workgroup at a time);
  *   - rsqrtf is 1/sqrtf (correctly rounded), not the device's approximation;
  *   - textures use point filtering, unnormalised coordinates, clamp addressing.
  * Float -> int conversions are whatever the host compiler emits for a C++ cast
@@ -70,27 +74,32 @@ struct dim3 {
 extern thread_local uint3 threadIdx, blockIdx;
 extern thread_local dim3 blockDim, gridDim;
 
-/* Runs every thread of a launch in order: blocks z, y, x, then threads z, y, x
- * within a block.  Kernels must not use __syncthreads (see below). */
+/* One workgroup of the current launch (blockIdx set): every thread in order, threads z, y, x.  The first thread runs
+ * on a fiber; if it returns without reaching a barrier, the others run one after the other on the caller's stack
+ * (no fiber).  If it stops at __syncthreads, every thread gets a fiber and the workgroup runs barrier by barrier.
+ * A barrier reached by only some of the threads aborts.  vhr_launch.cpp. */
+typedef void (*vhr_thread_fn)(void*);
+void vhr_run_workgroup(vhr_thread_fn fn, void* ctx, dim3 block);
+void vhr_barrier();
+
+template <class F> inline void vhr_call(void* f) { (*static_cast<F*>(f))(); }
+
+/* Runs every workgroup of a launch in order: blocks z, y, x (vhr_run_workgroup). */
 template <class K, class... A>
 inline void vhr_launch(dim3 grid, dim3 block, K kernel, const A&... args)
 {
     gridDim = grid;
     blockDim = block;
+    auto body = [&]() { kernel(args...); };
     for (unsigned int bz = 0; bz < grid.z; bz++)
     for (unsigned int by = 0; by < grid.y; by++)
-    for (unsigned int bx = 0; bx < grid.x; bx++)
-    for (unsigned int tz = 0; tz < block.z; tz++)
-    for (unsigned int ty = 0; ty < block.y; ty++)
-    for (unsigned int tx = 0; tx < block.x; tx++) {
+    for (unsigned int bx = 0; bx < grid.x; bx++) {
         blockIdx.x = bx; blockIdx.y = by; blockIdx.z = bz;
-        threadIdx.x = tx; threadIdx.y = ty; threadIdx.z = tz;
-        kernel(args...);
+        vhr_run_workgroup(&vhr_call<decltype(body)>, &body, block);
     }
 }
 
-/* A serial emulation cannot honour a barrier: a kernel that reaches one is out of scope. */
-inline void __syncthreads() { fprintf(stderr, "vh_ref: __syncthreads is not emulated\n"); abort(); }
+inline void __syncthreads() { vhr_barrier(); }
 inline void __threadfence() {}
 
 /* ---- bit casts ---- */

@@ -7,8 +7,8 @@ Copies the files listed in FILES from the reference tree into OUT_DIR (oracle/_r
 the mechanical edits a host C++ compiler needs.  Every edit is a rule about syntax; this script holds no text of the
 reference:
 
-  * a kernel launch `k<<<grid, block>>>(args);` becomes `vhr_launch(grid, block, k, args);`, the serial launch
-    emulator of oracle/ref/include/cuda_runtime.h;
+  * a kernel launch `k<<<grid, block>>>(args);` becomes `vhr_launch(grid, block, k, args);`, the launch emulator of
+    oracle/ref/include/cuda_runtime.h;
   * `__align__(n) struct Name` becomes `struct __align__(n) Name`: the stand-in spells __align__ as a GNU attribute,
     which applies to the type only after the class key (nvcc's spelling is MSVC's __declspec, which goes before it);
   * an out-of-class definition of a member of an explicit class-template specialisation (`inline ... X<3, 1>::...`)
@@ -26,7 +26,8 @@ import sys
 FILES = [("DepthSensingCUDA/Source", n) for n in (
     "VoxelUtilHashSDF.h", "RayCastSDFUtil.h", "DepthCameraUtil.h", "CUDAHashParams.h", "CUDARayCastParams.h",
     "CUDADepthCameraParams.h", "cuda_SimpleMatrixUtil.h", "cudaUtil.h",
-    "CUDASceneRepHashSDF.cu", "CUDARayCastSDF.cu", "CameraUtil.cu")] + [
+    "CUDASceneRepHashSDF.cu", "CUDARayCastSDF.cu", "CameraUtil.cu", "CUDASceneRepChunkGrid.cu",
+    "CUDAMarchingCubesSDF.cu", "MarchingCubesSDFUtil.h", "Tables.h")] + [
     ("DepthSensingCUDA/Include/cutil/inc", "cutil_math.h")]
 
 # `name <<< a, b >>> ( args ) ;` -- nvcc accepts blanks between the angle brackets, so the tokens are matched one by one

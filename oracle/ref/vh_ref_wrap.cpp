@@ -4,11 +4,12 @@
  * TEST INFRASTRUCTURE ONLY, like the oracle.  The reference's headers and .cu files are staged into oracle/_ref/src
  * at build time (oracle/ref/stage.py) and compiled as host C++ against the stand-ins in oracle/ref/include; this
  * file sets the reference's __constant__ parameter blocks from the project's structs (include/vh_types.h, the same
- * layouts, asserted below) and calls its device functions and barrier-free kernels on host buffers.  The arguments
+ * layouts, asserted below) and calls its device functions and kernels -- with barriers or without -- on host buffers.  The arguments
  * mirror the oracle's vho_* functions so that a test can run both on two copies of one state.
  *
- * Kernels run through the serial launch emulator (vhr_launch): every thread of a launch in order, blocks z-y-x then
- * threads z-y-x.  Kernels with __syncthreads (compactify, GC identify) are not wrapped.
+ * Kernels run through the launch emulator (vhr_launch): every thread of a launch in order, blocks z-y-x then
+ * threads z-y-x; a workgroup that reaches __syncthreads (compactify, GC identify) runs barrier by barrier on fibers
+ * (oracle/ref/vhr_launch.cpp).
  */
 #include "cuda_runtime.h"
 #include "cutil_math.h"
@@ -16,6 +17,7 @@
 #include "VoxelUtilHashSDF.h"
 #include "DepthCameraUtil.h"
 #include "RayCastSDFUtil.h"
+#include "MarchingCubesSDFUtil.h"
 
 #include <cstddef>
 #include <vector>
@@ -33,6 +35,12 @@ extern "C" void updateConstantHashParams(const HashParams& p) { c_hashParams = p
 extern "C" void updateConstantRayCastParams(const RayCastParams& p) { c_rayCastParams = p; }
 extern "C" void updateConstantDepthCameraParams(const DepthCameraParams& p) { c_depthCameraParams = p; }
 
+/* CUDASceneRepChunkGrid.cu defines this in the .cu file itself; the same declaration, asserted below */
+struct SDFBlockDesc {
+    int3 pos;
+    int ptr;
+};
+
 /* Defined in the staged .cu files: two kernels, and launchers with C linkage.  Our declarations, by type only. */
 __global__ void allocKernel(HashData, DepthCameraData, const unsigned int*);
 __global__ void computeNormalsDevice(float4*, float4*, unsigned int, unsigned int);
@@ -45,6 +53,28 @@ void integrateDepthMapCUDA(HashData&, const HashParams&, const DepthCameraData&,
 void starveVoxelsKernelCUDA(HashData&, const HashParams&);
 void garbageCollectFreeCUDA(HashData&, const HashParams&);
 void renderCS(const HashData&, const RayCastData&, const DepthCameraData&, const RayCastParams&);
+unsigned int compactifyHashAllInOneCUDA(HashData&, const HashParams&);
+void garbageCollectIdentifyCUDA(HashData&, const HashParams&);
+void integrateFromGlobalHashPass1CUDA(const HashParams&, const HashData&, uint, uint, float, const float3&, uint*,
+                                      SDFBlockDesc*);
+void integrateFromGlobalHashPass2CUDA(const HashParams&, const HashData&, uint, const SDFBlockDesc*, Voxel*, unsigned int);
+void chunkToGlobalHashPass1CUDA(const HashParams&, const HashData&, uint, uint, const SDFBlockDesc*, const Voxel*);
+void chunkToGlobalHashPass2CUDA(const HashParams&, const HashData&, uint, uint, const SDFBlockDesc*, const Voxel*);
+void resetMarchingCubesCUDA(MarchingCubesData&);
+void extractIsoSurfaceCUDA(const HashData&, const RayCastData&, const MarchingCubesParams&, MarchingCubesData&);
+void extractIsoSurfacePass1CUDA(const HashData&, const RayCastData&, const MarchingCubesParams&, MarchingCubesData&);
+void extractIsoSurfacePass2CUDA(const HashData&, const RayCastData&, const MarchingCubesParams&, MarchingCubesData&,
+                                unsigned int);
+void convertColorRawToFloat4(float4*, unsigned char*, unsigned int, unsigned int);
+void resampleFloatMap(float*, unsigned int, unsigned int, float*, unsigned int, unsigned int);
+void resampleFloat4Map(float4*, unsigned int, unsigned int, float4*, unsigned int, unsigned int);
+void convertColorToIntensityFloat(float*, float4*, unsigned int, unsigned int);
+void convertDepthFloatToCameraSpaceFloat4(float4*, float*, float4x4, unsigned int, unsigned int, const DepthCameraData&);
+void gaussFilterFloatMap(float*, float*, float, float, unsigned int, unsigned int);
+void gaussFilterFloat4Map(float4*, float4*, float, float, unsigned int, unsigned int);
+void bilateralFilterFloatMap(float*, float*, float, float, unsigned int, unsigned int);
+void erodeDepthMap(float*, float*, int, unsigned int, unsigned int, float, float);
+void computeIntensityAndDerivatives(float*, unsigned int, unsigned int, float4*);
 }
 
 /* the project's structs are the reference's, byte for byte */
@@ -60,6 +90,13 @@ static_assert(sizeof(RayCastParams) == sizeof(VhRayCastParams), "RayCastParams l
 static_assert(offsetof(RayCastParams, m_useGradients) == offsetof(VhRayCastParams, m_useGradients), "RayCastParams layout");
 static_assert(sizeof(DepthCameraParams) == sizeof(VhDepthCameraParams), "DepthCameraParams layout");
 static_assert(offsetof(DepthCameraParams, m_sensorDepthWorldMax) == offsetof(VhDepthCameraParams, m_sensorDepthWorldMax), "DepthCameraParams layout");
+static_assert(sizeof(SDFBlockDesc) == sizeof(VhSDFBlockDesc), "SDFBlockDesc layout");
+static_assert(offsetof(SDFBlockDesc, ptr) == offsetof(VhSDFBlockDesc, ptr), "SDFBlockDesc layout");
+static_assert(sizeof(MarchingCubesParams) == sizeof(VhMarchingCubesParams), "MarchingCubesParams layout");
+static_assert(offsetof(MarchingCubesParams, m_maxNumTriangles) == offsetof(VhMarchingCubesParams, m_maxNumTriangles), "MarchingCubesParams layout");
+static_assert(offsetof(MarchingCubesParams, m_threshMarchingCubes2) == offsetof(VhMarchingCubesParams, m_threshMarchingCubes2), "MarchingCubesParams layout");
+static_assert(sizeof(MarchingCubesData::Triangle) == sizeof(VhTriangle), "Triangle layout");
+static_assert(offsetof(MarchingCubesData::Vertex, c) == offsetof(VhVertex, c), "Vertex layout");
 
 static void set_hash_params(const VhHashParams* hp) { memcpy(&c_hashParams, hp, sizeof(c_hashParams)); }
 static void set_camera_params(const VhDepthCameraParams* cp) { memcpy(&c_depthCameraParams, cp, sizeof(c_depthCameraParams)); }
@@ -393,6 +430,167 @@ void vhr_gradient_for_point(const VhHashData* hd, const VhHashParams* hp, const 
     set_hash_params(hp);
     RayCastData r;
     put3(out, r.gradientForPoint(hash_data(hd), f3(pos)));
+}
+
+/* ---- kernels with barriers ---- */
+
+/* compactifyHashAllInOneCUDA: the count, also left in hp->m_numOccupiedBlocks */
+uint32_t vhr_compactify(VhHashData* hd, VhHashParams* hp, const VhDepthCameraParams* cp)
+{
+    set_hash_params(hp);
+    set_camera_params(cp);
+    HashData h = hash_data(hd);
+    HashParams p = c_hashParams;
+    const unsigned int n = compactifyHashAllInOneCUDA(h, p);
+    hp->m_numOccupiedBlocks = n;
+    return n;
+}
+
+/* garbageCollectIdentifyCUDA over hd->d_hashCompactified[0 .. hp->m_numOccupiedBlocks); the threshold reads cp */
+void vhr_gc_identify(VhHashData* hd, const VhHashParams* hp, const VhDepthCameraParams* cp)
+{
+    set_hash_params(hp);
+    set_camera_params(cp);
+    HashData h = hash_data(hd);
+    HashParams p = c_hashParams;
+    garbageCollectIdentifyCUDA(h, p);
+}
+
+/* ---- streaming (CUDASceneRepChunkGrid.cu) ---- */
+
+/* integrateFromGlobalHashPass1CUDA: returns the number of descriptors; out must hold every one the pass writes */
+uint32_t vhr_stream_out_pass1(VhHashData* hd, const VhHashParams* hp, uint32_t threadsPerPart, uint32_t start,
+                              float radius, const float camPos[3], VhSDFBlockDesc* out, uint32_t outCapacity)
+{
+    set_hash_params(hp);
+    HashData h = hash_data(hd);
+    HashParams p = c_hashParams;
+    uint32_t counter = 0;
+    const float3 c = f3(camPos);
+    /* room for every thread of the launch: threadsPerPart rounded up to whole workgroups of 64 */
+    std::vector<SDFBlockDesc> buf(((size_t)threadsPerPart + 63) / 64 * 64 + 1);
+    integrateFromGlobalHashPass1CUDA(p, h, threadsPerPart, start, radius, c, &counter, buf.data());
+    memcpy(out, buf.data(), sizeof(SDFBlockDesc) * (counter < outCapacity ? counter : outCapacity));
+    return counter;
+}
+
+void vhr_stream_out_pass2(VhHashData* hd, const VhHashParams* hp, const VhSDFBlockDesc* descs, VhVoxel* out, uint32_t n)
+{
+    set_hash_params(hp);
+    HashData h = hash_data(hd);
+    HashParams p = c_hashParams;
+    integrateFromGlobalHashPass2CUDA(p, h, n, reinterpret_cast<const SDFBlockDesc*>(descs), reinterpret_cast<Voxel*>(out), n);
+}
+
+/* chunkToGlobalHashPass1CUDA.  Its insertHashEntry's list branch is a fenced defect: callers
+ * give it only entries whose bucket has room. */
+void vhr_stream_in_pass1(VhHashData* hd, const VhHashParams* hp, uint32_t n, uint32_t heapCountPrev,
+                         const VhSDFBlockDesc* descs)
+{
+    set_hash_params(hp);
+    HashData h = hash_data(hd);
+    HashParams p = c_hashParams;
+    chunkToGlobalHashPass1CUDA(p, h, n, heapCountPrev, reinterpret_cast<const SDFBlockDesc*>(descs), nullptr);
+}
+
+void vhr_stream_in_pass2(VhHashData* hd, const VhHashParams* hp, uint32_t n, uint32_t heapCountPrev,
+                         const VhSDFBlockDesc* descs, const VhVoxel* blocks)
+{
+    set_hash_params(hp);
+    HashData h = hash_data(hd);
+    HashParams p = c_hashParams;
+    chunkToGlobalHashPass2CUDA(p, h, n, heapCountPrev, reinterpret_cast<const SDFBlockDesc*>(descs),
+                               reinterpret_cast<const Voxel*>(blocks));
+}
+
+/* ---- marching cubes (CUDAMarchingCubesSDF.cu) ----
+ * resetMarchingCubesCUDA, then extractIsoSurfacePass1CUDA + Pass2CUDA (twoPass != 0) or the one-kernel
+ * extractIsoSurfaceCUDA, with room for maxTriangles triangles (mp->m_maxNumTriangles is replaced by it).  Returns the
+ * reference's triangle counter, which it clamps to the capacity. */
+uint32_t vhr_extract_iso_surface(const VhHashData* hd, const VhHashParams* hp, const VhMarchingCubesParams* mp,
+                                 VhTriangle* out, uint32_t maxTriangles, int twoPass)
+{
+    set_hash_params(hp);
+    MarchingCubesParams params;
+    memcpy(&params, mp, sizeof(params));
+    params.m_maxNumTriangles = maxTriangles;
+    const uint32_t entries = hp->m_hashNumBuckets * HASH_BUCKET_SIZE;
+    std::vector<uint> occupied(entries ? entries : 1);
+    uint numOccupied = 0, numTriangles = 0;
+    MarchingCubesData d;
+    d.d_params = &params;
+    d.d_numOccupiedBlocks = &numOccupied;
+    d.d_occupiedBlocks = occupied.data();
+    d.d_numTriangles = &numTriangles;
+    d.d_triangles = reinterpret_cast<MarchingCubesData::Triangle*>(out);
+    d.m_bIsOnGPU = true;
+    HashData h = hash_data(hd);
+    RayCastData r;
+    resetMarchingCubesCUDA(d);
+    if (twoPass) {
+        extractIsoSurfacePass1CUDA(h, r, params, d);
+        extractIsoSurfacePass2CUDA(h, r, params, d, numOccupied);
+    } else {
+        extractIsoSurfaceCUDA(h, r, params, d);
+    }
+    return numTriangles;
+}
+
+/* ---- sensor maps (CameraUtil.cu) ---- */
+void vhr_convert_color_raw_to_float4(float* out4, const uint8_t* rgbx, uint32_t w, uint32_t h)
+{
+    convertColorRawToFloat4(reinterpret_cast<float4*>(out4), const_cast<uint8_t*>(rgbx), w, h);
+}
+
+void vhr_resample_float_map(float* out, uint32_t ow, uint32_t oh, const float* in, uint32_t w, uint32_t h)
+{
+    resampleFloatMap(out, ow, oh, const_cast<float*>(in), w, h);
+}
+
+void vhr_resample_float4_map(float* out4, uint32_t ow, uint32_t oh, const float* in4, uint32_t w, uint32_t h)
+{
+    resampleFloat4Map(reinterpret_cast<float4*>(out4), ow, oh, reinterpret_cast<float4*>(const_cast<float*>(in4)), w, h);
+}
+
+void vhr_convert_color_to_intensity_float(float* out, const float* in4, uint32_t w, uint32_t h)
+{
+    convertColorToIntensityFloat(out, reinterpret_cast<float4*>(const_cast<float*>(in4)), w, h);
+}
+
+/* the kernel ignores its intrinsicsInv argument (it back-projects through c_depthCameraParams) */
+void vhr_convert_depth_float_to_camera_space_float4(float* out4, const float* in, const VhDepthCameraParams* cp,
+                                                    uint32_t w, uint32_t h)
+{
+    set_camera_params(cp);
+    DepthCameraData cam;
+    convertDepthFloatToCameraSpaceFloat4(reinterpret_cast<float4*>(out4), const_cast<float*>(in), float4x4(), w, h, cam);
+}
+
+void vhr_gauss_filter_float_map(float* out, const float* in, float sigmaD, float sigmaR, uint32_t w, uint32_t h)
+{
+    gaussFilterFloatMap(out, const_cast<float*>(in), sigmaD, sigmaR, w, h);
+}
+
+void vhr_gauss_filter_float4_map(float* out4, const float* in4, float sigmaD, float sigmaR, uint32_t w, uint32_t h)
+{
+    gaussFilterFloat4Map(reinterpret_cast<float4*>(out4), reinterpret_cast<float4*>(const_cast<float*>(in4)), sigmaD,
+                         sigmaR, w, h);
+}
+
+void vhr_bilateral_filter_float_map(float* out, const float* in, float sigmaD, float sigmaR, uint32_t w, uint32_t h)
+{
+    bilateralFilterFloatMap(out, const_cast<float*>(in), sigmaD, sigmaR, w, h);
+}
+
+void vhr_erode_depth_map(float* out, const float* in, int structureSize, uint32_t w, uint32_t h, float dThresh,
+                         float fracReq)
+{
+    erodeDepthMap(out, const_cast<float*>(in), structureSize, w, h, dThresh, fracReq);
+}
+
+void vhr_compute_intensity_and_derivatives(float* out4, const float* in, uint32_t w, uint32_t h)
+{
+    computeIntensityAndDerivatives(const_cast<float*>(in), w, h, reinterpret_cast<float4*>(out4));
 }
 
 } /* extern "C" */

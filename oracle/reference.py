@@ -61,6 +61,23 @@ def lib():
         "vhr_trilinear": ([HD, HP, P(f), P(f), P(C.c_uint8)], C.c_int),
         "vhr_intersect_bisection": ([HD, HP, P(f), P(f), f, f, f, f, P(f), P(C.c_uint8)], C.c_int),
         "vhr_gradient_for_point": ([HD, HP, P(f), P(f)], None),
+        "vhr_compactify": ([HD, HP, CP], u32),
+        "vhr_gc_identify": ([HD, HP, CP], None),
+        "vhr_stream_out_pass1": ([HD, HP, u32, u32, f, P(f), vp, u32], u32),
+        "vhr_stream_out_pass2": ([HD, HP, vp, vp, u32], None),
+        "vhr_stream_in_pass1": ([HD, HP, u32, u32, vp], None),
+        "vhr_stream_in_pass2": ([HD, HP, u32, u32, vp, vp], None),
+        "vhr_extract_iso_surface": ([HD, HP, P(T.MarchingCubesParams), vp, u32, C.c_int], u32),
+        "vhr_convert_color_raw_to_float4": ([vp, vp, u32, u32], None),
+        "vhr_resample_float_map": ([vp, u32, u32, vp, u32, u32], None),
+        "vhr_resample_float4_map": ([vp, u32, u32, vp, u32, u32], None),
+        "vhr_convert_color_to_intensity_float": ([vp, vp, u32, u32], None),
+        "vhr_convert_depth_float_to_camera_space_float4": ([vp, vp, CP, u32, u32], None),
+        "vhr_gauss_filter_float_map": ([vp, vp, f, f, u32, u32], None),
+        "vhr_gauss_filter_float4_map": ([vp, vp, f, f, u32, u32], None),
+        "vhr_bilateral_filter_float_map": ([vp, vp, f, f, u32, u32], None),
+        "vhr_erode_depth_map": ([vp, vp, C.c_int, u32, u32, f, f], None),
+        "vhr_compute_intensity_and_derivatives": ([vp, vp, u32, u32], None),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -75,6 +92,22 @@ def compute_normals(depth4):
     d4 = np.ascontiguousarray(depth4, dtype=np.float32)
     out = np.empty_like(d4)
     lib().vhr_compute_normals(out.ctypes.data, d4.ctypes.data, W, H)
+    return out
+
+
+def image_op(name, src, width, height, *args, out_channels=1, out_size=None, prefill=None):
+    """the reference's CameraUtil.cu map `name`, with oracle.image_op's signature (vhr_<name> here, vho_<name> there)"""
+    from oracle import oracle as O
+    return O.call_image_op(lib(), "vhr_", name, src, width, height, *args, out_channels=out_channels,
+                           out_size=out_size, prefill=prefill)
+
+
+def compute_intensity_and_derivatives(intensity):
+    """computeIntensityAndDerivatives: (H, W) intensity -> (H, W, 4) intensity, d/du, d/dv, 1"""
+    H, W = intensity.shape
+    src = np.ascontiguousarray(intensity, dtype=np.float32)
+    out = np.empty((H, W, 4), dtype=np.float32)
+    lib().vhr_compute_intensity_and_derivatives(out.ctypes.data, src.ctypes.data, W, H)
     return out
 
 
@@ -114,18 +147,98 @@ class RefScene:
             self.alloc(depth, color, raster=raster)
 
     def compactify(self):
-        """the set compactifyHashAllInOneKernel lists (it needs a barrier, so it is not run): the live entries whose
-        block passes the reference's frustum test, in table order (the kernel's order is a matter of scheduling)"""
+        """compactifyHashAllInOneCUDA: the live entries whose block passes the frustum test, in table order (serial
+        workgroups); the count is also left in m_numOccupiedBlocks"""
         s = self.s
+        n = int(self.L.vhr_compactify(C.byref(s.hd), C.byref(s.hp), C.byref(s.cp)))
+        # the kernel's set is the frustum rule applied to the live entries
         table = s.hash_table()
         live = np.nonzero(table["ptr"] != T.FREE_ENTRY)[0]
         keep = [i for i in live if self.L.vhr_is_block_in_frustum(
             C.byref(s.hp), C.byref(s.cp), np.ascontiguousarray(table["pos"][i]).ctypes.data_as(C.POINTER(C.c_int32)))]
-        out = s.array("d_hashCompactified", T.HASH_ENTRY_DTYPE, len(keep))
-        out[:] = table[keep]
-        s.array("d_hashCompactifiedCounter", np.int32, 1)[0] = len(keep)
-        s.hp.m_numOccupiedBlocks = len(keep)
-        return len(keep)
+        assert n == len(keep) and int(s.array("d_hashCompactifiedCounter", np.int32, 1)[0]) == n
+        assert np.array_equal(s.array("d_hashCompactified", T.HASH_ENTRY_DTYPE, n), table[keep])
+        return n
+
+    def integrate(self, transform, depth, color, bitmask=None):
+        """CUDASceneRepHashSDF::integrate with the reference's kernels, on the OracleScene's options and frame counter:
+        alloc (in raster order, the oracle's thread order; offline: passes until the heap stops moving), compactify,
+        integrate, and with GC on: starve every opt.s_garbageCollectionStarve frames, GC identify, GC free.  Returns
+        the number of blocks GC freed."""
+        s = self.s
+        freed = 0
+        self.set_transform(transform)
+        if s.opt.s_offlineProcessing:
+            prev = None
+            while prev != s.heap_free_count():
+                prev = s.heap_free_count()
+                self.reset_mutex()
+                self.alloc(depth, color, bitmask, raster=True)
+        else:
+            self.reset_mutex()
+            self.alloc(depth, color, bitmask, raster=True)
+        self.compactify()
+        self.integrate_depth_map(depth, color)
+        if s.opt.s_garbageCollectionEnabled:
+            k, starve = s.frames.value, s.opt.s_garbageCollectionStarve
+            if k > 0 and starve != 0 and k % starve == 0:
+                self.starve()
+            self.gc_identify()
+            self.reset_mutex()
+            live = int((s.hash_table()["ptr"] != T.FREE_ENTRY).sum())
+            self.gc_free()
+            freed = live - int((s.hash_table()["ptr"] != T.FREE_ENTRY).sum())
+        s.frames.value += 1
+        return freed
+
+    def gc_identify(self):
+        self.L.vhr_gc_identify(C.byref(self.s.hd), C.byref(self.s.hp), C.byref(self.s.cp))
+
+    def stream_out_pass1(self, threads_per_part, start, radius, cam_pos, capacity=100000):
+        out = np.zeros(capacity, dtype=T.DESC_DTYPE)
+        cpv = np.ascontiguousarray(cam_pos, dtype=np.float32)
+        n = self.L.vhr_stream_out_pass1(C.byref(self.s.hd), C.byref(self.s.hp), threads_per_part, start,
+                                        C.c_float(radius), cpv.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data,
+                                        capacity)
+        return out[:n].copy()
+
+    def stream_out_pass2(self, descs):
+        descs = np.ascontiguousarray(descs, dtype=T.DESC_DTYPE)
+        out = np.zeros((len(descs), T.SDF_BLOCK_VOXELS), dtype=T.VOXEL_DTYPE)
+        self.L.vhr_stream_out_pass2(C.byref(self.s.hd), C.byref(self.s.hp), descs.ctypes.data, out.ctypes.data,
+                                    len(descs))
+        return out
+
+    def stream_in(self, descs, blocks):
+        """chunkToGlobalHashPass1CUDA + Pass2CUDA, then the heap counter moved down by len(descs) as
+        CUDASceneRepChunkGrid::streamInToGPUChunk does.  Only for entries whose bucket has room: the reference's
+        insertHashEntry corrupts the table in its list branch.  Returns 0 (the reference's pass
+        reports no failed insert)."""
+        s = self.s
+        descs = np.ascontiguousarray(descs, dtype=T.DESC_DTYPE)
+        blocks = np.ascontiguousarray(blocks, dtype=T.VOXEL_DTYPE)
+        n = len(descs)
+        table = s.hash_table()
+        for d in descs:
+            b = int(self.L.vhr_compute_hash_pos(C.byref(s.hp), np.ascontiguousarray(d["pos"], dtype=np.int32)
+                                                .ctypes.data_as(C.POINTER(C.c_int32))))
+            bucket = table[b * T.HASH_BUCKET_SIZE:(b + 1) * T.HASH_BUCKET_SIZE]
+            assert (bucket["ptr"] == T.FREE_ENTRY).any(), f"stream in: bucket {b} is full (the reference's list branch)"
+        hc = s.array("d_heapCounter", np.uint32, 1)
+        prev = int(hc[0])
+        self.L.vhr_stream_in_pass1(C.byref(s.hd), C.byref(s.hp), n, prev, descs.ctypes.data)
+        self.L.vhr_stream_in_pass2(C.byref(s.hd), C.byref(s.hp), n, prev, descs.ctypes.data, blocks.ctypes.data)
+        hc[0] = prev - n
+        return 0
+
+    def extract_iso_surface(self, mc_params, max_triangles=None, two_pass=True):
+        """resetMarchingCubesCUDA + extractIsoSurfacePass1/2CUDA (two_pass) or extractIsoSurfaceCUDA -> triangles
+        (T.TRIANGLE_DTYPE) and the reference's counter (clamped to the capacity)"""
+        cap = int(max_triangles if max_triangles is not None else mc_params.m_maxNumTriangles)
+        out = np.zeros(max(cap, 1), dtype=T.TRIANGLE_DTYPE)
+        n = int(self.L.vhr_extract_iso_surface(C.byref(self.s.hd), C.byref(self.s.hp), C.byref(mc_params),
+                                               out.ctypes.data, cap, int(two_pass)))
+        return out[:min(n, cap)].copy(), n
 
     def alloc(self, depth, color=None, bitmask=None, raster=True):
         cam = self.s._cam(depth, color)

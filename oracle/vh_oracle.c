@@ -1542,7 +1542,8 @@ void vho_convert_depth_float_to_camera_space_float4(float* out4, const float* in
 }
 
 static inline float gauss_d(float sigma, int x, int y) { return expf(-((float)(x * x + y * y) / (2.0f * sigma * sigma))); } /* :436-439 */
-static inline double gauss_r(float sigma, float dist) { return exp(-(double)(dist * dist) / (2.0 * (double)sigma * (double)sigma)); } /* :426-429 */
+/* gaussR evaluates in double and returns float: the weight below is a float product */
+static inline float gauss_r(float sigma, float dist) { return (float)exp(-(double)(dist * dist) / (2.0 * (double)sigma * (double)sigma)); } /* :426-429 */
 
 /* gaussFilterFloatMapDevice :555-593 */
 void vho_gauss_filter_float_map(float* out, const float* in, float sigmaD, float sigmaR, uint32_t W, uint32_t H)
@@ -1608,7 +1609,7 @@ void vho_bilateral_filter_float_map(float* out, const float* in, float sigmaD, f
                         if (m >= 0 && n >= 0 && m < (int)W && n < (int)H) {
                             const float cur = in[n * (int)W + m];
                             if (cur != MINF) {
-                                const float weight = (float)((double)gauss_d(sigmaD, m - x, n - y) * gauss_r(sigmaR, cur - center));
+                                const float weight = gauss_d(sigmaD, m - x, n - y) * gauss_r(sigmaR, cur - center);
                                 sumWeight += weight;
                                 sum += weight * cur;
                             }

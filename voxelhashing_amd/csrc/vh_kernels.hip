@@ -3218,7 +3218,8 @@ __global__ __launch_bounds__(256) void k_depth_to_camera_space(float4* out, cons
 
 // gaussD :436-439 (float exp), gaussR :426-429 (double arithmetic as written)
 VHD float gauss_d(float sigma, int x, int y) { return expf(-((float)(x * x + y * y) / (2.0f * sigma * sigma))); }
-VHD double gauss_r(float sigma, float dist) { return exp(-(double)(dist * dist) / (2.0 * (double)sigma * (double)sigma)); }
+/* gaussR (DSC/CameraUtil.cu:426-429) evaluates in double and returns float: the bilateral weight is a float product */
+VHD float gauss_r(float sigma, float dist) { return (float)exp(-(double)(dist * dist) / (2.0 * (double)sigma * (double)sigma)); }
 
 // gaussFilterFloatMapDevice :555-593
 __global__ __launch_bounds__(256) void k_gauss_filter_float(float* out, const float* in, float sigmaD, float sigmaR, uint32_t W, uint32_t H)
@@ -3330,7 +3331,7 @@ __global__ __launch_bounds__(256) void k_bilateral_filter_float(float* out, cons
                 if (m >= 0 && n >= 0 && m < (int)W && n < (int)H) {
                     const float cur = in[(uint32_t)n * W + (uint32_t)m];
                     if (cur != mi) {
-                        const float weight = (float)((double)gauss_d(sigmaD, m - x, n - y) * gauss_r(sigmaR, cur - center));
+                        const float weight = gauss_d(sigmaD, m - x, n - y) * gauss_r(sigmaR, cur - center);
                         sumWeight += weight;
                         sum += weight * cur;
                     }
