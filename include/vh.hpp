@@ -502,6 +502,8 @@ private:
 typedef VhReconstructionOptions ReconstructionOptions;
 typedef VhSequenceFrame SequenceFrame;
 typedef VhReconstructionStats ReconstructionStats;
+typedef VhRawFrameFormat RawFrameFormat;
+typedef VhRawSequenceFrame RawSequenceFrame;
 
 class Reconstruction {
 public:
@@ -514,6 +516,11 @@ public:
     static ReconstructionOptions defaultOptions();
     // next: the frame that will follow frames[n-1] in a later call, if the caller knows it (only its pose is read)
     void run(const SequenceFrame* frames, unsigned int n, const SequenceFrame* next = nullptr);
+    // raw frames (VhRawFrameFormat): 16-bit depth + 8-bit colour at the sensor's sizes, on the host (s_framesOnHost) or on
+    // the device; converted, resampled and filtered into a staging slot on the copy stream.  The format is set once,
+    // before the first frame.
+    void setRawFormat(const RawFrameFormat& format);
+    void runRaw(const RawSequenceFrame* frames, unsigned int n, const RawSequenceFrame* next = nullptr);
     void synchronize();
     void reset();
     const ReconstructionStats& getStats();
@@ -548,6 +555,14 @@ private:
     unsigned int m_uploads;                       // frames uploaded so far (the slot is m_uploads % kStagingSlots)
     std::vector<std::pair<void*, void*>> m_uploadTimers; // event pairs on the copy stream, not yet read
     std::vector<void*> m_timerPool;
+    // raw frames: the sensor's images of a slot (host-fed), and the maps the filters read (one pair: the copy stream runs
+    // one frame at a time)
+    bool m_raw, m_rawRun;
+    RawFrameFormat m_rawFormat;
+    unsigned short* d_rawDepth[kStagingSlots];
+    float* d_unfilteredDepth;
+    float* d_unfilteredColor;
+    std::vector<SequenceFrame> m_rawFrames;
 };
 
 // ---------------------------------------------------------------------------

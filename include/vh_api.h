@@ -368,6 +368,14 @@ int vh_reconstruction_run(VhReconstruction* r, const VhSequenceFrame* frames, ui
  * will follow frames[n-1] (only its pose is read; NULL: unknown).  With streaming on, the loop then asks the device
  * about that frame's streaming step behind the last frame's alloc pass, as it does inside a call (not in the reference) */
 int vh_reconstruction_run_ahead(VhReconstruction* r, const VhSequenceFrame* frames, uint32_t n, const VhSequenceFrame* next);
+/* raw frames (VhRawFrameFormat, VhRawSequenceFrame in vh_types.h): 16-bit depth and 8-bit colour at the sensor's sizes,
+ * in host memory (s_framesOnHost = 1: copied by the loop's two copy streams) or in device memory (0: read in place).
+ * The format is set once, before the first frame; the loop's copy stream turns every frame into float maps at adapter
+ * size in a staging slot (vh_ingest_frame, then the Gauss filters that are on) beside the previous frames' work.
+ * Raw and prepared frames may not be mixed in one loop. */
+int vh_reconstruction_set_raw_format(VhReconstruction* r, const VhRawFrameFormat* format);
+int vh_reconstruction_run_raw(VhReconstruction* r, const VhRawSequenceFrame* frames, uint32_t n);
+int vh_reconstruction_run_raw_ahead(VhReconstruction* r, const VhRawSequenceFrame* frames, uint32_t n, const VhRawSequenceFrame* next);
 /* waits for everything the loop has enqueued (all its streams) */
 int vh_reconstruction_synchronize(VhReconstruction* r);
 int vh_reconstruction_get_stats(VhReconstruction* r, VhReconstructionStats* out);
@@ -385,6 +393,14 @@ int vh_convert_color_raw_to_float4(float* d_output4, const uint8_t* d_inputRGBX,
  * as hipHostGetDevicePointer returns them): depth copied, RGBX colour converted to float4 on the way.  width*height
  * must be a multiple of 4.  hostRGBX / d_color4 may be NULL. */
 int vh_upload_frame(const float* hostDepth, const uint8_t* hostRGBX, float* d_depth, float* d_color4, uint32_t width, uint32_t height, vhStream_t stream);
+/* not in the reference: a raw sensor frame in device memory (16-bit depth in units of 1/depthShift m; colorChannels = 3: RGB,
+ * 4: RGBX, 0: no colour, then d_color4 / d_colorRaw may be NULL) to float depth + float4 colour at width x height in one
+ * pass: SensorDataReader::processDepth's conversion, vh_convert_color_raw_to_float4, vh_resample_float_map and
+ * vh_resample_float4_map (the colour is copied, not resampled, when its size is width x height), bit for bit.  All sizes
+ * at least 2 x 2; d_depth and d_color4 16-byte aligned, RGBX colour 4-byte aligned. */
+int vh_ingest_frame(float* d_depth, float* d_color4, uint32_t width, uint32_t height, const uint16_t* d_depthRaw, uint32_t depthWidth,
+                    uint32_t depthHeight, const uint8_t* d_colorRaw, uint32_t colorWidth, uint32_t colorHeight, uint32_t colorChannels,
+                    float depthShift, vhStream_t stream);
 int vh_resample_float_map(float* d_output, uint32_t outputWidth, uint32_t outputHeight, const float* d_input,
                           uint32_t inputWidth, uint32_t inputHeight, vhStream_t stream);                                       /* :1120 */
 int vh_resample_float4_map(float* d_output4, uint32_t outputWidth, uint32_t outputHeight, const float* d_input4,

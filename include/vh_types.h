@@ -271,6 +271,27 @@ typedef struct VhSequenceFrame {
     const void* color;        /* device: float4 per pixel (may be NULL); host: RGBX bytes, 4 per pixel */
 } VhSequenceFrame;
 
+/* Raw frames: what a sensor or a `.sens` recording delivers before SensorDataReader::processDepth and
+ * CUDARGBDAdapter::process have touched it.  Set once, before the first frame (vh_reconstruction_set_raw_format); the
+ * loop then makes d_depthData / d_colorData at adapter size (the VhDepthCameraParams it was created with) on the device
+ * with vh_ingest_frame, and, when a filter is on, vh_gauss_filter_float_map / vh_gauss_filter_float4_map behind it, as
+ * CUDARGBDSensor::process does (DSC/CUDARGBDSensor.cpp:159-186). */
+typedef struct VhRawFrameFormat {
+    uint32_t depthWidth, depthHeight; /* the sensor's depth image */
+    uint32_t colorWidth, colorHeight; /* the sensor's colour image (ignored when colorChannels = 0) */
+    float depthShift;                 /* depth in metres = sample / depthShift (ml::SensorData::m_depthShift: 1000 = millimetres) */
+    uint32_t colorChannels;           /* 0: no colour, 3: RGB, 4: RGBX; bytes per pixel */
+    uint8_t s_depthFilter, s_colorFilter, pad0[2];
+    float s_depthSigmaD, s_depthSigmaR, s_colorSigmaD, s_colorSigmaR;
+} VhRawFrameFormat;
+
+/* one raw frame: s_framesOnHost says where the images live (host memory, pinned for an asynchronous copy; or device memory) */
+typedef struct VhRawSequenceFrame {
+    float rigidTransform[16]; /* as VhSequenceFrame's */
+    const uint16_t* depth;    /* depthWidth*depthHeight samples; 0 = no measurement, which becomes 0.0f as in the reference */
+    const uint8_t* color;     /* colorWidth*colorHeight*colorChannels bytes; may be NULL */
+} VhRawSequenceFrame;
+
 typedef struct VhReconstructionStats {
     uint64_t frames;             /* frames processed since creation / reset */
     uint64_t invalidFrames;      /* skipped: invalid pose */

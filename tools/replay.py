@@ -4,12 +4,18 @@ parameter file, optional mesh at the end) and prints one JSON line with the timi
 
     python tools/replay.py --params zParameters.txt [--tracking zParametersTracking.txt] [--rgbd-tracking] [--sens a.sens b.sens]
                            [--mesh scan.ply] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
+                           [--native [--batch N]]
 
 Without --sens the files named by s_binaryDumpSensorFile[i] in the parameter file are played.  The rendering keys
 (light, material, discontinuity thresholds, s_renderToFile, s_renderToFileDir) come from --params; --render-to switches
 s_renderToFile on and writes the images under DIR.  The camera-calibration keys (s_bUseCameraCalibration and the
 remapping thresholds) come from --params too; --camera-calibration switches s_bUseCameraCalibration on, so the depth
-map is rendered into the colour camera with the `.sens` file's extrinsic (unless that is the identity)."""
+map is rendered into the colour camera with the `.sens` file's extrinsic (unless that is the identity).
+
+--native plays the files through the native frame loop fed with raw frames (Reconstruction.run_native): batches of
+16-bit depth + RGB frames decoded into pinned memory, converted, resampled and filtered on the device, no host wait per
+frame.  It is for recorded poses (s_binaryDumpSensorUseTrajectory = true, ...OnlyInit = false) and says why when the
+configuration needs the Python loop (ICP tracking, --record, --render-to, camera calibration)."""
 import argparse
 import json
 import os
@@ -31,6 +37,8 @@ def main():
     ap.add_argument("--max-frames", type=int, default=None)
     ap.add_argument("--render-to", default=None, help="renderToFile: the shaded model and the input of every frame as PNGs under this directory")
     ap.add_argument("--camera-calibration", action="store_true", help="s_bUseCameraCalibration: remap depth into the colour camera")
+    ap.add_argument("--native", action="store_true", help="play through the native frame loop, fed with raw frames")
+    ap.add_argument("--batch", type=int, default=64, help="--native: frames decoded and handed over per call")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -49,13 +57,25 @@ def main():
     if args.camera_calibration:
         cs.s_bUseCameraCalibration = 1
     rec = R.Reconstruction(g, t, args.sens or None, use_rgbd_tracking=args.rgbd_tracking, render_state=rs, calibration_state=cs)
+    if args.native:  # the loop, its pinned buffers and the file, before the clock (the Python loop's reader has loaded its file above)
+        try:
+            rec.prepare_native(args.batch)
+        except ValueError as e:
+            raise SystemExit(str(e))
     t0 = time.perf_counter()
-    n = rec.run(args.max_frames)
-    rec.scene.synchronize()
+    if args.native:
+        n = rec.run_native(args.max_frames, batch=args.batch)
+        rec.native.synchronize()
+    else:
+        n = rec.run(args.max_frames)
+        rec.scene.synchronize()
     dt = time.perf_counter() - t0
     out = dict(frames=n, seconds=round(dt, 3), frames_per_s=round(n / dt, 1) if dt > 0 else None, lost_frames=rec.lost_frames,
                blocks=rec.scene.getNumOccupiedBlocks(), heap_free=rec.scene.getHeapFreeCount(),
                pose_source="recorded trajectory" if g.s_binaryDumpSensorUseTrajectory and not g.s_binaryDumpSensorUseTrajectoryOnlyInit else ("RGB-D ICP" if args.rgbd_tracking else "projective ICP"))
+    if args.native:  # the loop's statistics ("frames" above is frames read; the loop's own count leaves out invalidFrames)
+        out["loop"] = "native"
+        out.update({k: (round(v, 6) if isinstance(v, float) else v) for k, v in rec.native.getStats().items() if k != "frames"})
     if cs.s_bUseCameraCalibration:
         out["camera_calibration"] = rec.camera_calibration
     if rs.s_renderToFile:

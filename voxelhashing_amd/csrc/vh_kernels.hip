@@ -11,6 +11,8 @@
 // MUST be compiled with -ffp-contract=off (see vh_device.hpp).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <cstdint>
 #include <cstring>
 
 #include "../../include/vh_api.h"
@@ -3057,15 +3059,18 @@ __global__ __launch_bounds__(512) void k_mc_pass2(VhHashData hd, VhHashParams hp
 // ---------------------------------------------------------------------------
 
 // convertColorRawToFloatDevice :137-152 (RGBX bytes; black means "no colour")
+VHD float4 color_raw_to_float4(uint32_t c)
+{
+    const uint32_t r = c & 0xffu, g = (c >> 8) & 0xffu, b = (c >> 16) & 0xffu, w = c >> 24;
+    const float mi = minf();
+    return (r == 0u && g == 0u && b == 0u) ? make_float4(mi, mi, mi, mi)
+                                           : make_float4((float)r / 255.0f, (float)g / 255.0f, (float)b / 255.0f, (float)(w / 255u));
+}
 __global__ __launch_bounds__(256) void k_convert_color_raw_to_float4(float4* out, const uint32_t* in, uint32_t n)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint32_t c = in[i];
-    const uint32_t r = c & 0xffu, g = (c >> 8) & 0xffu, b = (c >> 16) & 0xffu, w = c >> 24;
-    const float mi = minf();
-    out[i] = (r == 0u && g == 0u && b == 0u) ? make_float4(mi, mi, mi, mi)
-                                             : make_float4((float)r / 255.0f, (float)g / 255.0f, (float)b / 255.0f, (float)(w / 255u));
+    out[i] = color_raw_to_float4(in[i]);
 }
 
 // A sensor frame straight from (pinned, device-visible) host memory: the depth copied, the colour converted on the way
@@ -3121,22 +3126,28 @@ __global__ __launch_bounds__(256) void k_upload_frame(const uint4* hostDepth, co
     }
 }
 
-// bilinearInterpolationFloat :1071-1098 (invalid taps drop out of the weights)
-VHD float bilinear_float(float x, float y, const float* in, uint32_t W, uint32_t H)
+// bilinearInterpolationFloat :1071-1098 (invalid taps drop out of the weights).  fetch(i) is source pixel i: a load, or a
+// load and a conversion (k_ingest_frame)
+template <class Fetch>
+VHD float bilinear_float_taps(float x, float y, Fetch fetch, uint32_t W, uint32_t H)
 {
     const int px = (int)floorf(x), py = (int)floorf(y);
     const float alpha = x - (float)px, beta = y - (float)py;
     const float mi = minf();
     float s0 = 0.0f, w0 = 0.0f, s1 = 0.0f, w1 = 0.0f;
-    if ((uint32_t)px < W && (uint32_t)py < H) { const float v = in[(uint32_t)py * W + (uint32_t)px]; if (v != mi) { s0 += (1.0f - alpha) * v; w0 += (1.0f - alpha); } }
-    if ((uint32_t)(px + 1) < W && (uint32_t)py < H) { const float v = in[(uint32_t)py * W + (uint32_t)(px + 1)]; if (v != mi) { s0 += alpha * v; w0 += alpha; } }
-    if ((uint32_t)px < W && (uint32_t)(py + 1) < H) { const float v = in[(uint32_t)(py + 1) * W + (uint32_t)px]; if (v != mi) { s1 += (1.0f - alpha) * v; w1 += (1.0f - alpha); } }
-    if ((uint32_t)(px + 1) < W && (uint32_t)(py + 1) < H) { const float v = in[(uint32_t)(py + 1) * W + (uint32_t)(px + 1)]; if (v != mi) { s1 += alpha * v; w1 += alpha; } }
+    if ((uint32_t)px < W && (uint32_t)py < H) { const float v = fetch((uint32_t)py * W + (uint32_t)px); if (v != mi) { s0 += (1.0f - alpha) * v; w0 += (1.0f - alpha); } }
+    if ((uint32_t)(px + 1) < W && (uint32_t)py < H) { const float v = fetch((uint32_t)py * W + (uint32_t)(px + 1)); if (v != mi) { s0 += alpha * v; w0 += alpha; } }
+    if ((uint32_t)px < W && (uint32_t)(py + 1) < H) { const float v = fetch((uint32_t)(py + 1) * W + (uint32_t)px); if (v != mi) { s1 += (1.0f - alpha) * v; w1 += (1.0f - alpha); } }
+    if ((uint32_t)(px + 1) < W && (uint32_t)(py + 1) < H) { const float v = fetch((uint32_t)(py + 1) * W + (uint32_t)(px + 1)); if (v != mi) { s1 += alpha * v; w1 += alpha; } }
     const float p0 = s0 / w0, p1 = s1 / w1;
     float ss = 0.0f, ww = 0.0f;
     if (w0 > 0.0f) { ss += (1.0f - beta) * p0; ww += (1.0f - beta); }
     if (w1 > 0.0f) { ss += beta * p1; ww += beta; }
     return ww > 0.0f ? ss / ww : mi;
+}
+VHD float bilinear_float(float x, float y, const float* in, uint32_t W, uint32_t H)
+{
+    return bilinear_float_taps(x, y, [in](uint32_t i) { return in[i]; }, W, H);
 }
 
 VHD float4 f4_scale(float a, float4 v) { return make_float4(a * v.x, a * v.y, a * v.z, a * v.w); }
@@ -3144,7 +3155,8 @@ VHD float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y,
 VHD float4 f4_div(float4 a, float b) { return make_float4(a.x / b, a.y / b, a.z / b, a.w / b); }
 
 // bilinearInterpolationFloat4 :1136-1166
-VHD float4 bilinear_float4(float x, float y, const float4* in, uint32_t W, uint32_t H)
+template <class Fetch>
+VHD float4 bilinear_float4_taps(float x, float y, Fetch fetch, uint32_t W, uint32_t H)
 {
     const int px = (int)floorf(x), py = (int)floorf(y);
     const float alpha = x - (float)px, beta = y - (float)py;
@@ -3153,7 +3165,7 @@ VHD float4 bilinear_float4(float x, float y, const float4* in, uint32_t W, uint3
     float w0 = 0.0f, w1 = 0.0f;
     auto tap = [&](int tx, int ty, float wgt, float4& s, float& w) {
         if ((uint32_t)tx < W && (uint32_t)ty < H) {
-            const float4 v = in[(uint32_t)ty * W + (uint32_t)tx];
+            const float4 v = fetch((uint32_t)ty * W + (uint32_t)tx);
             if (v.x != mi && v.y != mi && v.z != mi) { s = f4_add(s, f4_scale(wgt, v)); w += wgt; }
         }
     };
@@ -3168,20 +3180,79 @@ VHD float4 bilinear_float4(float x, float y, const float4* in, uint32_t W, uint3
     if (w1 > 0.0f) { ss = f4_add(ss, f4_scale(beta, p1)); ww += beta; }
     return ww > 0.0f ? f4_div(ss, ww) : make_float4(mi, mi, mi, mi);
 }
+VHD float4 bilinear_float4(float x, float y, const float4* in, uint32_t W, uint32_t H)
+{
+    return bilinear_float4_taps(x, y, [in](uint32_t i) { return in[i]; }, W, H);
+}
 
 // resampleFloatMapDevice :1100-1118 / resampleFloat4MapDevice :1168-1186 (pixels whose nearest source pixel lies
 // outside the source keep their old value, as in the reference)
+// the source coordinates of output pixel (x, y); false: the nearest source pixel lies outside the source
+VHD bool resample_coords(int x, int y, uint32_t inW, uint32_t inH, uint32_t outW, uint32_t outH, float& sx, float& sy)
+{
+    const float scaleWidth = (float)(inW - 1) / (float)(outW - 1), scaleHeight = (float)(inH - 1) / (float)(outH - 1);
+    const uint32_t xInput = (uint32_t)((float)x * scaleWidth + 0.5f), yInput = (uint32_t)((float)y * scaleHeight + 0.5f);
+    sx = (float)x * scaleWidth;
+    sy = (float)y * scaleHeight;
+    return xInput < inW && yInput < inH;
+}
 template <class T>
 __global__ __launch_bounds__(256) void k_resample(T* out, const T* in, uint32_t inW, uint32_t inH, uint32_t outW, uint32_t outH)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= outW * outH) return;
-    const int x = (int)(i % outW), y = (int)(i / outW);
-    const float scaleWidth = (float)(inW - 1) / (float)(outW - 1), scaleHeight = (float)(inH - 1) / (float)(outH - 1);
-    const uint32_t xInput = (uint32_t)((float)x * scaleWidth + 0.5f), yInput = (uint32_t)((float)y * scaleHeight + 0.5f);
-    if (xInput < inW && yInput < inH) {
-        if constexpr (sizeof(T) == 4) out[i] = bilinear_float((float)x * scaleWidth, (float)y * scaleHeight, in, inW, inH);
-        else out[i] = bilinear_float4((float)x * scaleWidth, (float)y * scaleHeight, in, inW, inH);
+    float sx, sy;
+    if (resample_coords((int)(i % outW), (int)(i / outW), inW, inH, outW, outH, sx, sy)) {
+        if constexpr (sizeof(T) == 4) out[i] = bilinear_float(sx, sy, in, inW, inH);
+        else out[i] = bilinear_float4(sx, sy, in, inW, inH);
+    }
+}
+
+// Not in the reference: a raw sensor frame -- 16-bit depth in units of 1/depthShift m, 8-bit RGB or RGBX colour, at the
+// sensor's sizes -- to integrate's input at adapter size in one pass: SensorDataReader::processDepth's conversion
+// (DSC/SensorDataReader.cpp:125-140: u16 / depthShift, a 0 sample stays 0.0f; RGB -> RGBX with X = 1),
+// convertColorRawToFloat4, resampleFloatMap and resampleFloat4Map (or the colour copy when the colour size is the
+// adapter's, DSC/CUDARGBDAdapter.cpp:107-131), with the conversions inside the tap fetch of the bilinear functions
+// above: the same operations in the same order, so the same bits.  For widths and heights from 2 up the nearest
+// source pixel is always inside the source (resample_coords), so every output pixel is written.
+// The output (20 B per adapter pixel) is most of the traffic; the taps come from L2.  A workgroup owns 1024 consecutive
+// output pixels: lane t writes depth pixels 4t..4t+3 as one 16-byte store and colour pixels t, t+256, t+512, t+768
+// (a float4 each), so every store instruction of a wave covers one contiguous kilobyte.
+constexpr uint32_t kIngestPixelsPerGroup = 1024;
+template <int CH, bool COPY_COLOR>
+__global__ __launch_bounds__(256) void k_ingest_frame(float* __restrict__ outDepth, float4* __restrict__ outColor, const uint16_t* __restrict__ depth,
+                                                      const uint8_t* __restrict__ color, uint32_t depthW, uint32_t depthH, uint32_t colorW, uint32_t colorH,
+                                                      uint32_t outW, uint32_t outH, float depthShift)
+{
+    const uint32_t n = outW * outH, base = blockIdx.x * kIngestPixelsPerGroup;
+    auto depthTap = [depth, depthShift](uint32_t i) { return (float)depth[i] / depthShift; };
+    auto depthAt = [&](uint32_t i) {
+        float sx, sy;
+        (void)resample_coords((int)(i % outW), (int)(i / outW), depthW, depthH, outW, outH, sx, sy);
+        return bilinear_float_taps(sx, sy, depthTap, depthW, depthH);
+    };
+    const uint32_t i0 = base + 4u * threadIdx.x;
+    if (i0 + 4u <= n) {
+        *reinterpret_cast<float4*>(outDepth + i0) = make_float4(depthAt(i0), depthAt(i0 + 1u), depthAt(i0 + 2u), depthAt(i0 + 3u));
+    } else {
+        for (uint32_t i = i0; i < n; i++) outDepth[i] = depthAt(i);
+    }
+    if constexpr (CH != 0) {
+        auto colorTap = [color](uint32_t i) {
+            if constexpr (CH == 4) return color_raw_to_float4(reinterpret_cast<const uint32_t*>(color)[i]);
+            else return color_raw_to_float4((uint32_t)color[3u * i] | ((uint32_t)color[3u * i + 1u] << 8) | ((uint32_t)color[3u * i + 2u] << 16) | (1u << 24));
+        };
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) {
+            const uint32_t i = base + k * 256u + threadIdx.x;
+            if (i >= n) break;
+            if constexpr (COPY_COLOR) outColor[i] = colorTap(i);
+            else {
+                float sx, sy;
+                (void)resample_coords((int)(i % outW), (int)(i / outW), colorW, colorH, outW, outH, sx, sy);
+                outColor[i] = bilinear_float4_taps(sx, sy, colorTap, colorW, colorH);
+            }
+        }
     }
 }
 
@@ -4662,6 +4733,27 @@ int vh_upload_frame(const float* hostDepth, const uint8_t* hostRGBX, float* d_de
     const uint32_t want = cdiv(nQuads, 256u * kUploadInFlight);
     k_upload_frame<<<want < kUploadGroups ? want : kUploadGroups, 256, 0, (hipStream_t)stream>>>(reinterpret_cast<const uint4*>(hostDepth), reinterpret_cast<const uint4*>(hostRGBX),
                                                                             reinterpret_cast<uint4*>(d_depth), reinterpret_cast<float4*>(d_color4), nQuads);
+    return vh_last_launch_error();
+}
+
+int vh_ingest_frame(float* d_depth, float* d_color4, uint32_t width, uint32_t height, const uint16_t* d_depthRaw, uint32_t depthWidth, uint32_t depthHeight,
+                    const uint8_t* d_colorRaw, uint32_t colorWidth, uint32_t colorHeight, uint32_t colorChannels, float depthShift, vhStream_t stream)
+{
+    if (!d_depth || !d_depthRaw || width < 2 || height < 2 || depthWidth < 2 || depthHeight < 2) return VH_ERR_BAD_ARGUMENT;
+    if (!(depthShift > 0.0f) || !std::isfinite(depthShift)) return VH_ERR_BAD_ARGUMENT;
+    if (colorChannels != 0 && colorChannels != 3 && colorChannels != 4) return VH_ERR_BAD_ARGUMENT;
+    if (colorChannels != 0 && (!d_color4 || !d_colorRaw || colorWidth < 2 || colorHeight < 2)) return VH_ERR_BAD_ARGUMENT;
+    // 16-byte stores; the 32-bit pixel index of the other image kernels
+    if (((uintptr_t)d_depth | (uintptr_t)d_color4) % 16u || (uintptr_t)d_depthRaw % 2u || (colorChannels == 4 && (uintptr_t)d_colorRaw % 4u)) return VH_ERR_BAD_ARGUMENT;
+    if ((uint64_t)width * height > 0x7fffffffull || (uint64_t)depthWidth * depthHeight > 0x7fffffffull || (uint64_t)colorWidth * colorHeight * 4ull > 0x7fffffffull) return VH_ERR_BAD_ARGUMENT;
+    const bool copyColor = colorWidth == width && colorHeight == height;
+    const uint32_t groups = cdiv(width * height, kIngestPixelsPerGroup);
+    float4* c4 = reinterpret_cast<float4*>(d_color4);
+#define VH_INGEST(CH, COPY) k_ingest_frame<CH, COPY><<<groups, 256, 0, (hipStream_t)stream>>>(d_depth, c4, d_depthRaw, d_colorRaw, depthWidth, depthHeight, colorWidth, colorHeight, width, height, depthShift)
+    if (colorChannels == 0) VH_INGEST(0, false);
+    else if (colorChannels == 3) { if (copyColor) VH_INGEST(3, true); else VH_INGEST(3, false); }
+    else { if (copyColor) VH_INGEST(4, true); else VH_INGEST(4, false); }
+#undef VH_INGEST
     return vh_last_launch_error();
 }
 

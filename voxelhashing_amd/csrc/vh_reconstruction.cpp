@@ -17,6 +17,11 @@
 //     to CUDARGBDAdapter::process, DSC/CUDARGBDAdapter.cpp:107-131) are uploaded by two copy streams (one copy engine
 //     each: depth, colour) into a ring of kStagingSlots = 4 staging slots, beside the previous frames' work, and the
 //     colour is converted there (convertColorRawToFloat4);
+//   * raw frames (setRawFormat / runRaw): 16-bit depth + RGB or RGBX bytes at the sensor's sizes, what a sensor or a
+//     `.sens` file holds before SensorDataReader::processDepth and CUDARGBDAdapter::process.  From the host they travel
+//     by the same two copy streams (5 or 6 bytes per sensor pixel instead of 8), from device memory they are read in
+//     place; the copy stream then runs vh_ingest_frame (conversion + resampling to adapter size in one pass) and the
+//     Gauss filters of CUDARGBDSensor::process that are on, into the staging slot;
 //   * s_maxFramesInFlight: the host stays at most that many frames ahead of the device (polled through the mapped
 //     frame counter the fused integrate pass writes: no event).
 #include <hip/hip_runtime.h>
@@ -93,6 +98,10 @@ Reconstruction::Reconstruction(CUDASceneRepHashSDF* sceneRep, CUDARayCastSDF* ra
         m_slotSceneFrame[i] = 0;
     }
     m_uploads = 0;
+    m_raw = m_rawRun = false;
+    std::memset(&m_rawFormat, 0, sizeof(m_rawFormat));
+    for (int i = 0; i < kStagingSlots; i++) d_rawDepth[i] = nullptr;
+    d_unfilteredDepth = d_unfilteredColor = nullptr;
     m_probePending = false;
     std::memset(m_probePose, 0, sizeof(m_probePose));
     if (m_opt.s_framesOnHost) {
@@ -125,9 +134,59 @@ Reconstruction::~Reconstruction()
         if (d_stageDepth[i]) (void)hipFree(d_stageDepth[i]);
         if (d_stageColorRaw[i]) (void)hipFree(d_stageColorRaw[i]);
         if (d_stageColor[i]) (void)hipFree(d_stageColor[i]);
+        if (d_rawDepth[i]) (void)hipFree(d_rawDepth[i]);
     }
+    if (d_unfilteredDepth) (void)hipFree(d_unfilteredDepth);
+    if (d_unfilteredColor) (void)hipFree(d_unfilteredColor);
     if (m_copyStream) (void)hipStreamDestroy((hipStream_t)m_copyStream);
     if (m_copyStream2) (void)hipStreamDestroy((hipStream_t)m_copyStream2);
+}
+
+// Raw mode owns the copy streams and the staging ring in both residencies: the ingest kernel writes the slot's maps
+// whether the sensor's images came over the link or were on the device already.
+void Reconstruction::setRawFormat(const RawFrameFormat& f)
+{
+    if (m_raw) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: the format is already set");
+    if (m_stats.frames || m_stats.invalidFrames || m_uploads) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: frames have been processed already");
+    const unsigned int W = m_cp.m_imageWidth, H = m_cp.m_imageHeight;
+    // the resampler's scale is (in - 1) / (out - 1)
+    if (W < 2 || H < 2) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: the adapter size must be at least 2x2");
+    if (f.depthWidth < 2 || f.depthHeight < 2) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: the depth size must be at least 2x2");
+    if (f.colorChannels != 0 && f.colorChannels != 3 && f.colorChannels != 4) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: colorChannels must be 0, 3 or 4");
+    if (f.colorChannels && (f.colorWidth < 2 || f.colorHeight < 2)) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: the colour size must be at least 2x2");
+    if (!(f.depthShift > 0.0f) || !std::isfinite(f.depthShift)) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: depthShift must be positive and finite");
+    auto sigmaOk = [](float s) { return s > 0.0f && std::isfinite(s); };
+    if (f.s_depthFilter && !(sigmaOk(f.s_depthSigmaD) && sigmaOk(f.s_depthSigmaR))) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: the depth filter needs positive sigmas");
+    if (f.s_colorFilter && !(sigmaOk(f.s_colorSigmaD) && sigmaOk(f.s_colorSigmaR))) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: the colour filter needs positive sigmas");
+    const size_t n = (size_t)W * H, nDepth = (size_t)f.depthWidth * f.depthHeight;
+    const size_t colorBytes = f.colorChannels ? (size_t)f.colorChannels * f.colorWidth * f.colorHeight : 0;
+    if (!m_copyStream) {
+        hipStream_t cs = nullptr;
+        checkHip(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking), "hipStreamCreate");
+        m_copyStream = (void*)cs;
+    }
+    if (!m_copyStream2) {
+        hipStream_t cs2 = nullptr;
+        checkHip(hipStreamCreateWithFlags(&cs2, hipStreamNonBlocking), "hipStreamCreate");
+        m_copyStream2 = (void*)cs2;
+    }
+    for (int i = 0; i < kStagingSlots; i++) {
+        if (!d_stageDepth[i]) checkHip(hipMalloc((void**)&d_stageDepth[i], sizeof(float) * n), "staging depth");
+        if (!d_stageColor[i]) checkHip(hipMalloc((void**)&d_stageColor[i], sizeof(float) * 4 * n), "staging colour");
+        if (!m_slotReady[i]) m_slotReady[i] = (void*)newEvent(false);
+        if (!m_slotReady2[i]) m_slotReady2[i] = (void*)newEvent(false);
+        if (m_opt.s_framesOnHost) { // the sensor's images, as they come over the link
+            if (!d_rawDepth[i]) checkHip(hipMalloc((void**)&d_rawDepth[i], sizeof(uint16_t) * nDepth), "staging depth (raw)");
+            if (d_stageColorRaw[i]) { (void)hipFree(d_stageColorRaw[i]); d_stageColorRaw[i] = nullptr; }
+            checkHip(hipMalloc((void**)&d_stageColorRaw[i], colorBytes ? colorBytes : 1), "staging colour (raw)");
+        }
+    }
+    // what the filters read (vh_sensor.cpp: d_depthMapResampledFloat, d_colorMapResampledFloat4)
+    if (f.s_depthFilter && !d_unfilteredDepth) checkHip(hipMalloc((void**)&d_unfilteredDepth, sizeof(float) * n), "unfiltered depth");
+    if (f.s_colorFilter && f.colorChannels && !d_unfilteredColor) checkHip(hipMalloc((void**)&d_unfilteredColor, sizeof(float) * 4 * n), "unfiltered colour");
+    m_stats.uploadBytes = sizeof(uint16_t) * nDepth + colorBytes;
+    m_rawFormat = f;
+    m_raw = true;
 }
 
 void Reconstruction::synchronize()
@@ -221,7 +280,7 @@ DepthCameraData Reconstruction::upload(const SequenceFrame& f)
     // two to three times as long (vh_kernels.hip, k_upload_frame; VH_UPLOAD_KERNEL=1 selects that path for measurement).
     static const bool useKernel = std::getenv("VH_UPLOAD_KERNEL") != nullptr;
     void *devDepth = nullptr, *devColor = nullptr;
-    const bool mapped = useKernel && (n % 4u) == 0u && hipHostGetDevicePointer(&devDepth, const_cast<float*>(f.depth), 0) == hipSuccess &&
+    const bool mapped = !m_rawRun && useKernel && (n % 4u) == 0u && hipHostGetDevicePointer(&devDepth, const_cast<float*>(f.depth), 0) == hipSuccess &&
                         (!f.color || hipHostGetDevicePointer(&devColor, const_cast<void*>(f.color), 0) == hipSuccess);
     if (useKernel && !mapped) (void)hipGetLastError();
     if (timed) {
@@ -229,7 +288,31 @@ DepthCameraData Reconstruction::upload(const SequenceFrame& f)
         t1 = timerEvent();
         checkHip(hipEventRecord((hipEvent_t)t0, cs), "hipEventRecord");
     }
-    if (mapped) {
+    const bool hasColor = m_rawRun ? (m_rawFormat.colorChannels != 0u && f.color != nullptr) : f.color != nullptr;
+    if (m_rawRun) {
+        // SensorDataReader::processDepth's conversion + CUDARGBDAdapter::process + the filters of CUDARGBDSensor::process
+        // (vh_sensor.cpp:154-164), all on the copy stream: the main stream only waits for the slot's "ready" event
+        const RawFrameFormat& rf = m_rawFormat;
+        const unsigned int W = m_cp.m_imageWidth, H = m_cp.m_imageHeight;
+        const uint16_t* depthRaw = reinterpret_cast<const uint16_t*>(f.depth);
+        const uint8_t* colorRaw = hasColor ? static_cast<const uint8_t*>(f.color) : nullptr;
+        if (m_opt.s_framesOnHost) { // two copies, two streams, as below
+            hipStream_t cs2 = (hipStream_t)m_copyStream2;
+            checkHip(hipMemcpyAsync(d_rawDepth[slot], depthRaw, sizeof(uint16_t) * (size_t)rf.depthWidth * rf.depthHeight, hipMemcpyHostToDevice, cs2), "upload depth");
+            checkHip(hipEventRecord((hipEvent_t)m_slotReady2[slot], cs2), "hipEventRecord");
+            if (colorRaw) checkHip(hipMemcpyAsync(d_stageColorRaw[slot], colorRaw, (size_t)rf.colorChannels * rf.colorWidth * rf.colorHeight, hipMemcpyHostToDevice, cs), "upload colour");
+            checkHip(hipStreamWaitEvent(cs, (hipEvent_t)m_slotReady2[slot], 0), "hipStreamWaitEvent");
+            depthRaw = d_rawDepth[slot];
+            if (colorRaw) colorRaw = d_stageColorRaw[slot];
+        }
+        const bool filterColor = colorRaw && rf.s_colorFilter;
+        float* depthOut = rf.s_depthFilter ? d_unfilteredDepth : d_stageDepth[slot];
+        float* colorOut = filterColor ? d_unfilteredColor : d_stageColor[slot];
+        check(vh_ingest_frame(depthOut, colorRaw ? colorOut : nullptr, W, H, depthRaw, rf.depthWidth, rf.depthHeight, colorRaw, rf.colorWidth, rf.colorHeight,
+                              colorRaw ? rf.colorChannels : 0u, rf.depthShift, m_copyStream), "vh_ingest_frame");
+        if (filterColor) check(vh_gauss_filter_float4_map(d_stageColor[slot], d_unfilteredColor, rf.s_colorSigmaD, rf.s_colorSigmaR, W, H, m_copyStream), "gaussFilterFloat4Map");
+        if (rf.s_depthFilter) check(vh_gauss_filter_float_map(d_stageDepth[slot], d_unfilteredDepth, rf.s_depthSigmaD, rf.s_depthSigmaR, W, H, m_copyStream), "gaussFilterFloatMap");
+    } else if (mapped) {
         check(vh_upload_frame((const float*)devDepth, (const uint8_t*)devColor, d_stageDepth[slot], d_stageColor[slot], m_cp.m_imageWidth, m_cp.m_imageHeight, m_copyStream), "vh_upload_frame");
     } else {
         // two copies, two streams: each gets a copy engine of its own
@@ -245,7 +328,7 @@ DepthCameraData Reconstruction::upload(const SequenceFrame& f)
     if (timed) {
         // the pair spans the whole upload: the depth copy runs on the other stream, so this one waits for it first
         // (t0 was recorded before either copy was enqueued; both streams were idle or busy with earlier uploads)
-        if (!mapped) checkHip(hipStreamWaitEvent(cs, (hipEvent_t)m_slotReady2[slot], 0), "hipStreamWaitEvent");
+        if (!mapped && !m_rawRun) checkHip(hipStreamWaitEvent(cs, (hipEvent_t)m_slotReady2[slot], 0), "hipStreamWaitEvent");
         checkHip(hipEventRecord((hipEvent_t)t1, cs), "hipEventRecord");
         m_uploadTimers.emplace_back(t0, t1);
     }
@@ -256,7 +339,7 @@ DepthCameraData Reconstruction::upload(const SequenceFrame& f)
     DepthCameraData cam;
     std::memset(&cam, 0, sizeof(cam));
     cam.d_depthData = d_stageDepth[slot];
-    cam.d_colorData = f.color ? d_stageColor[slot] : nullptr;
+    cam.d_colorData = hasColor ? d_stageColor[slot] : nullptr;
     return cam;
 }
 
@@ -276,7 +359,7 @@ void Reconstruction::frame(const SequenceFrame& f, const SequenceFrame* next)
     if (!f.depth) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction: frame without a depth map");
 
     DepthCameraData cam;
-    if (m_opt.s_framesOnHost) cam = upload(f);
+    if (m_opt.s_framesOnHost || m_rawRun) cam = upload(f);
     else {
         std::memset(&cam, 0, sizeof(cam));
         cam.d_depthData = const_cast<float*>(f.depth);
@@ -418,6 +501,7 @@ void Reconstruction::frame(const SequenceFrame& f, const SequenceFrame* next)
 void Reconstruction::run(const SequenceFrame* frames, unsigned int n, const SequenceFrame* after)
 {
     if (n && !frames) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::run: null frames");
+    if (m_raw && !m_rawRun) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::run: this loop takes raw frames (runRaw)");
     const double t0 = now();
     double waited = 0.0;
     const double streamWait0 = m_stats.hostWaitSeconds;
@@ -439,6 +523,27 @@ void Reconstruction::run(const SequenceFrame* frames, unsigned int n, const Sequ
     const double total = now() - t0, streamWait = m_stats.hostWaitSeconds - streamWait0;
     m_stats.hostWaitSeconds += waited;
     m_stats.hostEnqueueSeconds += total - waited - streamWait;
+}
+
+void Reconstruction::runRaw(const RawSequenceFrame* frames, unsigned int n, const RawSequenceFrame* after)
+{
+    if (!m_raw) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::runRaw: no raw format has been set (setRawFormat)");
+    if (n && !frames) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::runRaw: null frames");
+    // frame() reads poses and pointers; upload() knows what the pointers are
+    m_rawFrames.resize((size_t)n + 1);
+    auto put = [](SequenceFrame& s, const RawSequenceFrame& r) {
+        std::memcpy(s.rigidTransform, r.rigidTransform, sizeof(s.rigidTransform));
+        s.depth = reinterpret_cast<const float*>(r.depth);
+        s.color = r.color;
+    };
+    for (unsigned int i = 0; i < n; i++) put(m_rawFrames[i], frames[i]);
+    if (after) put(m_rawFrames[n], *after);
+    struct Mode {
+        bool& on;
+        ~Mode() { on = false; }
+    } mode{ m_rawRun };
+    m_rawRun = true;
+    run(m_rawFrames.data(), n, after ? &m_rawFrames[n] : nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -476,6 +581,21 @@ int vh_reconstruction_run_ahead(VhReconstruction* r, const VhSequenceFrame* fram
 {
     if (!r || (n && !frames)) return VH_ERR_BAD_ARGUMENT;
     return guarded([&] { r->impl.run(frames, n, next); });
+}
+int vh_reconstruction_set_raw_format(VhReconstruction* r, const VhRawFrameFormat* format)
+{
+    if (!r || !format) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { r->impl.setRawFormat(*format); });
+}
+int vh_reconstruction_run_raw(VhReconstruction* r, const VhRawSequenceFrame* frames, uint32_t n)
+{
+    if (!r || (n && !frames)) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { r->impl.runRaw(frames, n); });
+}
+int vh_reconstruction_run_raw_ahead(VhReconstruction* r, const VhRawSequenceFrame* frames, uint32_t n, const VhRawSequenceFrame* next)
+{
+    if (!r || (n && !frames)) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { r->impl.runRaw(frames, n, next); });
 }
 int vh_reconstruction_synchronize(VhReconstruction* r)
 {

@@ -411,6 +411,47 @@ class Reconstruction:
         else:
             check(self.L.vh_reconstruction_run(self.handle, ptr, n), "Reconstruction::run")
 
+    # ---- raw frames: 16-bit depth + 8-bit colour at the sensor's sizes -------------------------------------------
+    def setRawFormat(self, depth_size, color_size=None, depth_shift=1000.0, color_channels=3, depth_filter=None, color_filter=None):
+        """Once, before the first frame.  depth_size / color_size: (width, height) of the sensor's images;
+        color_channels: 3 (RGB), 4 (RGBX) or 0 (no colour); depth_filter / color_filter: None, or (sigmaD, sigmaR) of the
+        Gauss filter CUDARGBDSensor::process applies (s_depthFilter / s_colorFilter of the parameter file)"""
+        f = T.RawFrameFormat()
+        f.depthWidth, f.depthHeight = int(depth_size[0]), int(depth_size[1])
+        if color_size is not None:
+            f.colorWidth, f.colorHeight = int(color_size[0]), int(color_size[1])
+        f.depthShift = depth_shift
+        f.colorChannels = int(color_channels)
+        if depth_filter is not None:
+            f.s_depthFilter, (f.s_depthSigmaD, f.s_depthSigmaR) = 1, depth_filter
+        if color_filter is not None:
+            f.s_colorFilter, (f.s_colorSigmaD, f.s_colorSigmaR) = 1, color_filter
+        check(self.L.vh_reconstruction_set_raw_format(self.handle, C.byref(f)), "Reconstruction::setRawFormat")
+        self._raw_format = f
+
+    @staticmethod
+    def makeRawFrames(poses, depth_ptrs, color_ptrs):
+        """-> ctypes array of VhRawSequenceFrame (host pointers for s_framesOnHost, else device pointers)"""
+        n = len(poses)
+        arr = (T.RawSequenceFrame * n)()
+        for k in range(n):
+            arr[k].rigidTransform[:] = [float(v) for v in np.asarray(poses[k], dtype=np.float32).reshape(-1)]
+            arr[k].depth = depth_ptrs[k]
+            arr[k].color = color_ptrs[k] if color_ptrs is not None else None
+        return arr
+
+    def runRaw(self, frames, first=0, count=None, lookahead=False):
+        """run() for a VhRawSequenceFrame array (makeRawFrames); needs setRawFormat"""
+        n = len(frames) - first if count is None else count
+        if n <= 0:
+            return
+        ptr = C.cast(C.byref(frames, first * C.sizeof(T.RawSequenceFrame)), C.POINTER(T.RawSequenceFrame))
+        if lookahead and first + n < len(frames):
+            nxt = C.cast(C.byref(frames, (first + n) * C.sizeof(T.RawSequenceFrame)), C.POINTER(T.RawSequenceFrame))
+            check(self.L.vh_reconstruction_run_raw_ahead(self.handle, ptr, n, nxt), "Reconstruction::runRaw")
+        else:
+            check(self.L.vh_reconstruction_run_raw(self.handle, ptr, n), "Reconstruction::runRaw")
+
     def synchronize(self):
         check(self.L.vh_reconstruction_synchronize(self.handle), "Reconstruction::synchronize")
 
@@ -663,6 +704,27 @@ def image_op(name, src, width, height, *args, out_channels=1, out_size=None, pre
         check(fn(d_out.ptr, d_in.ptr, width, height, None), name)
     out = d_out.download(np.float32, n_out)
     return out.reshape((oh, ow, out_channels)) if out_channels > 1 else out.reshape((oh, ow))
+
+
+def ingest_frame(depth_u16, color_u8, adapter_size, depth_shift=1000.0, stream=None):
+    """vh_ingest_frame on host arrays: depth [h, w] u16, colour [h', w', 3 or 4] u8 or None, adapter_size (width, height)
+    -> (depth [H, W] f32, colour [H, W, 4] f32 or None) as the device made them"""
+    W, H = int(adapter_size[0]), int(adapter_size[1])
+    d = np.ascontiguousarray(depth_u16, dtype=np.uint16)
+    d_in = DeviceBuffer.from_numpy(d, stream)
+    d_out = DeviceBuffer(4 * W * H)
+    c_in = c_out = None
+    cw = ch = channels = 0
+    if color_u8 is not None:
+        c = np.ascontiguousarray(color_u8, dtype=np.uint8)
+        ch, cw, channels = c.shape
+        c_in = DeviceBuffer.from_numpy(c, stream)
+        c_out = DeviceBuffer(16 * W * H)
+    check(load().vh_ingest_frame(d_out.ptr, c_out.ptr if c_out else None, W, H, d_in.ptr, d.shape[1], d.shape[0], c_in.ptr if c_in else None, cw, ch,
+                                 channels, depth_shift, stream), "vh_ingest_frame")
+    depth = d_out.download(np.float32, W * H, stream).reshape(H, W)
+    color = c_out.download(np.float32, 4 * W * H, stream).reshape(H, W, 4) if c_out else None
+    return depth, color
 
 
 class CUDARGBDSensor:

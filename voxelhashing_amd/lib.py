@@ -105,12 +105,16 @@ PROTOTYPES = {
     "vh_reconstruction_destroy": (None, [_VP]),
     "vh_reconstruction_run": (C.c_int, [_VP, P(T.SequenceFrame), C.c_uint32]),
     "vh_reconstruction_run_ahead": (C.c_int, [_VP, P(T.SequenceFrame), C.c_uint32, P(T.SequenceFrame)]),
+    "vh_reconstruction_set_raw_format": (C.c_int, [_VP, P(T.RawFrameFormat)]),
+    "vh_reconstruction_run_raw": (C.c_int, [_VP, P(T.RawSequenceFrame), C.c_uint32]),
+    "vh_reconstruction_run_raw_ahead": (C.c_int, [_VP, P(T.RawSequenceFrame), C.c_uint32, P(T.RawSequenceFrame)]),
     "vh_reconstruction_synchronize": (C.c_int, [_VP]),
     "vh_reconstruction_debug_fail_render": (C.c_int, [_VP, C.c_uint32]),
     "vh_reconstruction_get_stats": (C.c_int, [_VP, P(T.ReconstructionStats)]),
     "vh_reconstruction_reset": (C.c_int, [_VP]),
     "vh_convert_color_raw_to_float4": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _VP]),
     "vh_upload_frame": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP]),
+    "vh_ingest_frame": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _VP]),
     "vh_resample_float_map": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP]),
     "vh_resample_float4_map": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP]),
     "vh_copy_float_map": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _VP]),

@@ -149,6 +149,49 @@ def depth_image_rgba8(depth):
     return (out * f(255)).astype(np.uint8)
 
 
+def native_refusal(app_state, render_state=None, camera_calibration=False, use_rgbd_tracking=False):
+    """Why the native frame loop cannot play this configuration, as text, or None when it can.  The native loop
+    (engine.Reconstruction) integrates every frame at the pose the file holds: s_binaryDumpSensorUseTrajectory = true,
+    s_binaryDumpSensorUseTrajectoryOnlyInit = false.  Needs no device."""
+    g = app_state
+    if not g.s_binaryDumpSensorUseTrajectory or use_rgbd_tracking:
+        return "the poses come from ICP tracking (s_binaryDumpSensorUseTrajectory = false): the native loop has no tracker"
+    if g.s_binaryDumpSensorUseTrajectoryOnlyInit:
+        return "s_binaryDumpSensorUseTrajectoryOnlyInit = true tracks from the recorded pose: the native loop has no tracker"
+    if not g.s_trackingEnabled:
+        return "s_trackingEnabled = false integrates every frame at the identity, not at the recorded pose"
+    if g.s_recordData:
+        return "s_recordData = true records the float frames of the Python loop"
+    if render_state is not None and render_state.s_renderToFile:
+        return "s_renderToFile = true draws every frame between two frames of the loop"
+    if camera_calibration:
+        return "s_bUseCameraCalibration = true remaps depth into the colour camera, which the native loop's ingest does not"
+    return None
+
+
+def decode_batch(sensor_data, first, count, depth_out=None, color_out=None):
+    """Frames [first, first + count) of a SensorData as the file holds them -> (depth [count, h, w] u16, colour
+    [count, h', w', 3] u8 or None when the file has no colour, poses [count, 16] f32).  depth_out / color_out: arrays
+    of at least these shapes to decode into (pinned memory for the native loop).  Needs no device."""
+    i = sensor_data.info()
+    if first < 0 or count < 0 or first + count > i.m_numFrames:
+        raise IndexError("frame range outside the sequence")
+    has_color = i.m_colorWidth * i.m_colorHeight > 0
+    depth = depth_out[:count] if depth_out is not None else np.empty((count, i.m_depthHeight, i.m_depthWidth), dtype=np.uint16)
+    color = None
+    if has_color:
+        color = color_out[:count] if color_out is not None else np.empty((count, i.m_colorHeight, i.m_colorWidth, 3), dtype=np.uint8)
+    if depth.shape[1:] != (i.m_depthHeight, i.m_depthWidth) or depth.dtype != np.uint16 or not depth.flags.c_contiguous:
+        raise ValueError("depth_out does not fit the sequence")
+    if color is not None and (color.shape[1:] != (i.m_colorHeight, i.m_colorWidth, 3) or color.dtype != np.uint8 or not color.flags.c_contiguous):
+        raise ValueError("color_out does not fit the sequence")
+    poses = np.empty((count, 16), dtype=np.float32)
+    for k in range(count):
+        check(sensor_data.L.vh_sensor_data_get_frame(sensor_data.handle, first + k, depth[k].ctypes.data, color[k].ctypes.data if color is not None else None,
+                                                     poses[k].ctypes.data_as(C.POINTER(C.c_float)), None), "vh_sensor_data_get_frame")
+    return depth, color, poses
+
+
 class Reconstruction:
     """One scene fed from `.sens` files.  `frame()` is one pass of the reference's render callback with
     reconstruction enabled: read a frame, pre-process it, ray-cast the model at the last pose, find the new pose
@@ -229,6 +272,9 @@ class Reconstruction:
         self.marching_cubes = None
         cam = self.sensor.getDepthCameraData()
         self.frame_data = E.DepthFrame(self.cp, depth_ptr=cam.d_depthData, color_ptr=cam.d_colorData)
+        self.calibration_state = calibration_state
+        self.use_rgbd_tracking = bool(use_rgbd_tracking)
+        self.native = None     # the native frame loop, once run_native has played frames
         self.frame_number = 0  # g_RGBDAdapter.getFrameNumber()
         self.trajectory = []   # the pose every processed frame was integrated at (recordTrajectory)
         self.recorded = None
@@ -267,6 +313,8 @@ class Reconstruction:
     # -- reconstruction(), DepthSensing.cpp:720-924 ---------------------------------------------------------------
     def frame(self):
         """-> the camera-to-world pose the frame was integrated at, or None when the input is exhausted"""
+        if self.native is not None:
+            raise RuntimeError("this sequence is being played by the native loop (run_native)")
         got = self._next_frame()
         if got is None:
             return None
@@ -367,6 +415,106 @@ class Reconstruction:
                 break
             n += 1
         return n
+
+    # -- the same sequence through the native frame loop ------------------------------------------------------------
+    def prepare_native(self, batch=64):
+        """what run_native needs before its first frame: the native loop with the raw format of the first file, two sets of
+        pinned buffers of `batch` frames, the file loaded.  run_native calls it; a caller that times the frames alone
+        calls it first (the Python loop's reader loads its file in the constructor too)."""
+        from .lib import PinnedArray
+        if self.native is not None:
+            return
+        why = native_refusal(self.gas, self.render_state, self.camera_calibration, self.use_rgbd_tracking)
+        if why is None and self.frame_number:
+            why = "frames of this sequence have been played by the Python loop already"
+        if why is not None:
+            raise ValueError("run_native: " + why)
+        g, h = self.gas, self.reader.header
+        batch = max(int(batch), 1)
+        has_color = h.m_colorWidth * h.m_colorHeight > 0
+        opt = E.Reconstruction.defaultOptions(s_framesOnHost=1, s_streamingEnabled=1 if self.chunk_grid is not None else 0,
+                                              s_integrationEnabled=1 if g.s_integrationEnabled else 0, s_offlineProcessing=1 if g.s_offlineProcessing else 0,
+                                              s_streamingPos=list(g.s_streamingPos), s_streamingRadius=g.s_streamingRadius)
+        native = E.Reconstruction(self.scene, self.ray, self.chunk_grid, self.cp, opt)
+        native.setRawFormat((h.m_depthWidth, h.m_depthHeight), (h.m_colorWidth, h.m_colorHeight) if has_color else None, h.m_depthShift,
+                            3 if has_color else 0, (g.s_depthSigmaD, g.s_depthSigmaR) if g.s_depthFilter else None,
+                            (g.s_colorSigmaD, g.s_colorSigmaR) if g.s_colorFilter else None)
+        self._native_sets = [(PinnedArray((batch, h.m_depthHeight, h.m_depthWidth), np.uint16),
+                              PinnedArray((batch, h.m_colorHeight, h.m_colorWidth, 3), np.uint8) if has_color else None) for _ in range(2)]
+        self._native_sens = SD.SensorData.loadFromFile(self.sens_files[self.file_idx])
+        self._native_at = 0
+        self.native = native
+
+    def run_native(self, max_frames=None, batch=64):
+        """Plays the `.sens` files through the native frame loop (engine.Reconstruction) fed with raw frames: a batch of
+        frames is decoded into pinned memory (16-bit depth, RGB) while the device works on the batch before, and handed
+        over with one call, the next frame's pose as look-ahead.  The device converts, resamples and filters them
+        (vh_ingest_frame) as CUDARGBDSensor.process does for the Python loop.  For recorded poses only: raises
+        ValueError with the reason otherwise (native_refusal).  -> number of frames read"""
+        h = self.reader.header
+        batch = max(int(batch), 1)
+        has_color = h.m_colorWidth * h.m_colorHeight > 0
+        self.prepare_native(batch)
+        if self._native_sets[0][0].shape[0] < batch:
+            raise ValueError("run_native: the batch size is fixed by the first call")
+
+        def same_format(i):
+            return ((i.m_depthWidth, i.m_depthHeight, i.m_colorWidth, i.m_colorHeight, i.m_depthShift) ==
+                    (h.m_depthWidth, h.m_depthHeight, h.m_colorWidth, h.m_colorHeight, h.m_depthShift))
+
+        def advance():
+            """-> False when the input is exhausted (loadNextSensFile, SensorDataReader.cpp:147-165)"""
+            while self._native_at >= self._native_sens.info().m_numFrames:
+                if self.file_idx + 1 >= len(self.sens_files):
+                    return False
+                self.file_idx += 1
+                self._native_sens.close()
+                self._native_sens = SD.SensorData.loadFromFile(self.sens_files[self.file_idx])
+                self._native_at = 0
+                if not same_format(self._native_sens.info()):
+                    raise ValueError("run_native: " + self.sens_files[self.file_idx] + " has another frame format than the first file")
+            return True
+
+        def decode(which, budget):
+            """the next frames, at most a batch and `budget`, of the current file into buffer set `which` -> frame array or None"""
+            if budget <= 0 or not advance():
+                return None
+            n = min(batch, budget, self._native_sens.info().m_numFrames - self._native_at)
+            d, c = self._native_sets[which]
+            _, _, poses = decode_batch(self._native_sens, self._native_at, n, d.array, c.array if c is not None else None)
+            self._native_at += n
+            ds, cs = d.array[0].nbytes, (c.array[0].nbytes if c is not None else 0)
+            return poses, E.Reconstruction.makeRawFrames(list(poses) + [poses[-1]], [d.ptr + k * ds for k in range(n)] + [d.ptr],
+                                                         [c.ptr + k * cs for k in range(n)] + [c.ptr] if c is not None else None)
+
+        def peek_pose(budget):
+            """the pose of the frame decode() would bring next, or None"""
+            if budget <= 0 or not advance():
+                return None
+            pose = np.empty(16, dtype=np.float32)
+            check(self.L.vh_sensor_data_get_frame(self._native_sens.handle, self._native_at, None, None, pose.ctypes.data_as(C.POINTER(C.c_float)), None),
+                  "vh_sensor_data_get_frame")
+            return pose
+
+        read, which = 0, 0
+        left = lambda: (max_frames - read) if max_frames is not None else batch
+        cur = decode(which, left())
+        while cur is not None:
+            poses, frames = cur
+            n = len(poses)
+            read += n
+            ahead = peek_pose(left())
+            if ahead is not None:
+                frames[n].rigidTransform[:] = [float(v) for v in ahead]
+            self.native.runRaw(frames, 0, n, lookahead=ahead is not None)
+            for p in poses:
+                if not (p[0] == MINF or np.isnan(p[0])):
+                    self.trajectory.append(p.reshape(4, 4).copy())
+            self.frame_number += n
+            which = 1 - which
+            cur = decode(which, left())  # while the device works on the batch just handed over
+            self.native.synchronize()    # whose buffers are free after this
+        return read
 
     # -- around the loop ------------------------------------------------------------------------------------------
     def saveRecordedFramesToFile(self, filename=None):

@@ -333,6 +333,23 @@ class SequenceFrame(C.Structure):
     _fields_ = [("rigidTransform", C.c_float * 16), ("depth", C.c_void_p), ("color", C.c_void_p)]
 
 
+class RawFrameFormat(C.Structure):
+    """VhRawFrameFormat: what the raw frames of a native loop look like (set once, before the first frame)"""
+    _fields_ = [
+        ("depthWidth", C.c_uint32), ("depthHeight", C.c_uint32),
+        ("colorWidth", C.c_uint32), ("colorHeight", C.c_uint32),
+        ("depthShift", C.c_float),
+        ("colorChannels", C.c_uint32),
+        ("s_depthFilter", C.c_uint8), ("s_colorFilter", C.c_uint8), ("pad0", C.c_uint8 * 2),
+        ("s_depthSigmaD", C.c_float), ("s_depthSigmaR", C.c_float), ("s_colorSigmaD", C.c_float), ("s_colorSigmaR", C.c_float),
+    ]
+
+
+class RawSequenceFrame(C.Structure):
+    """VhRawSequenceFrame: pose, u16 depth, RGB / RGBX bytes"""
+    _fields_ = [("rigidTransform", C.c_float * 16), ("depth", C.c_void_p), ("color", C.c_void_p)]
+
+
 class ReconstructionStats(C.Structure):
     _fields_ = [
         ("frames", C.c_uint64),
