@@ -521,6 +521,18 @@ public:
     // before the first frame.
     void setRawFormat(const RawFrameFormat& format);
     void runRaw(const RawSequenceFrame* frames, unsigned int n, const RawSequenceFrame* next = nullptr);
+    // Camera tracking inside the loop (plain projective ICP): once, before the first frame.  From then on run() / runRaw()
+    // ignore the frames' rigidTransform and do what reconstruction() does with s_binaryDumpSensorUseTrajectory = false,
+    // s_trackingEnabled = true (DSC/DepthSensing.cpp:750-879): frame 0 at the identity; later frames ray-cast the model at
+    // the scene's last pose, align the input to it and integrate at lastRigidTransform * delta; a lost frame is not
+    // integrated.  The host waits once per tracked frame, for the ICP result in mapped host memory.
+    void setTracking(const VhTrackingState& settings);
+    bool isTracking() const { return m_tracking; }
+    // frames integrated at a pose the loop tracked itself / frames on which tracking was lost, since creation or reset
+    unsigned long long getNumTrackedFrames() const { return m_trackedFrames; }
+    unsigned long long getNumLostFrames() const { return m_lostFrames; }
+    // the pose every frame fed since creation / reset was integrated at, 16 floats each; -inf for a frame that was not
+    const std::vector<float>& getPoses() const { return m_poses; }
     void synchronize();
     void reset();
     const ReconstructionStats& getStats();
@@ -563,6 +575,26 @@ private:
     float* d_unfilteredDepth;
     float* d_unfilteredColor;
     std::vector<SequenceFrame> m_rawFrames;
+    // the streaming step in the reference's order of calls (:881-900) around p -> the bit mask for alloc
+    const unsigned int* streamAround(const vh::vec3f& p);
+    std::vector<float> m_poses;
+    // tracking: the input's camera-space positions, normals and coarser levels per staging slot (they depend on the frame
+    // alone: made on the copy stream behind the ingest), the model's coarser levels, the solve's device state
+    bool m_tracking;
+    unsigned long long m_trackedFrames, m_lostFrames;
+    VhTrackingState m_trackingState;
+    std::vector<unsigned int> m_levelWidth, m_levelHeight;
+    std::vector<float*> d_trkInput[kStagingSlots], d_trkInputNormal[kStagingSlots];
+    std::vector<float*> d_trkModel, d_trkModelNormal, d_trkCorr, d_trkCorrNormal; // level 0 of the model: the ray caster's maps
+    float* d_trkPartials;
+    VhIcpState* d_trkState;
+    float* d_trkIdentity;
+    uint32_t* d_trkTicket;
+    VhIcpResult* h_trkResult; // mapped host memory
+    VhIcpResult* d_trkResult; // its device alias
+    uint32_t m_trkTag;
+    void inputPyramid(unsigned int slot, const float* d_depth, vhStream_t stream);
+    void frameTracked(const SequenceFrame& f);
 };
 
 // ---------------------------------------------------------------------------

@@ -376,6 +376,24 @@ int vh_reconstruction_run_ahead(VhReconstruction* r, const VhSequenceFrame* fram
 int vh_reconstruction_set_raw_format(VhReconstruction* r, const VhRawFrameFormat* format);
 int vh_reconstruction_run_raw(VhReconstruction* r, const VhRawSequenceFrame* frames, uint32_t n);
 int vh_reconstruction_run_raw_ahead(VhReconstruction* r, const VhRawSequenceFrame* frames, uint32_t n, const VhRawSequenceFrame* next);
+/* Camera tracking inside the loop (plain projective ICP, CUDACameraTrackingMultiRes): once, before the first frame;
+ * needs a ray caster, s_renderEnabled and a pyramid of settings->s_maxLevels levels that the adapter size can hold.
+ * From then on the rigidTransform of the frames is ignored and every frame does what reconstruction() does with
+ * s_binaryDumpSensorUseTrajectory = false, s_trackingEnabled = true (DSC/DepthSensing.cpp:750-879): frame 0 at the
+ * identity; later frames ray-cast the model at the scene's last pose, align the input to it from the identity estimate
+ * (one vh_icp_step per outer iteration on levels with s_maxInnerIter = 1) and integrate at lastRigidTransform * delta.  A
+ * frame on which tracking is lost is not integrated (vh_reconstruction_get_tracking_stats).  The host waits once per tracked frame, for the ICP
+ * result in mapped host memory; it makes no blocking HIP call. */
+int vh_reconstruction_set_tracking(VhReconstruction* r, const VhTrackingState* settings);
+/* the poses of frames [first, first + n) fed since creation / reset, 16 floats each: the pose the frame was integrated
+ * at; every entry -inf for a frame that was not (tracking lost, invalid recorded pose).  Untracked loops report the
+ * recorded poses.  Waits for nothing: the poses are the host's. */
+int vh_reconstruction_get_poses(VhReconstruction* r, uint32_t first, uint32_t n, float* out);
+/* trackedFrames: frames whose pose came from ICP inside the loop and that were integrated; lostFrames: frames on which
+ * that tracking was lost (not integrated, the scene keeps its last pose).  Since creation / reset; both 0 without
+ * tracking.  They are not members of VhReconstructionStats because its size is pinned (tests/test_raw_frames_host.py):
+ * engine.Reconstruction.getStats() reports them beside its members. */
+int vh_reconstruction_get_tracking_stats(VhReconstruction* r, uint64_t* trackedFrames, uint64_t* lostFrames);
 /* waits for everything the loop has enqueued (all its streams) */
 int vh_reconstruction_synchronize(VhReconstruction* r);
 int vh_reconstruction_get_stats(VhReconstruction* r, VhReconstructionStats* out);
@@ -506,6 +524,17 @@ int vh_icp_build_linear_system(uint32_t width, uint32_t height, float* d_partial
                                const float* d_corrNormals4, const VhIcpState* d_state, vhStream_t stream);
 int vh_icp_solve(VhIcpState* d_state, const float* d_partials, uint32_t numPartials, float angleThres, float distThres, float earlyOutResidual,
                  int lastInnerIteration, vhStream_t stream);
+/* One outer iteration of a level whose s_maxInnerIter is 1 in ONE launch: what vh_icp_projective_correspondences +
+ * vh_icp_build_linear_system + vh_icp_solve(lastInnerIteration = 1) do, the VhIcpState afterwards equal to theirs bit
+ * for bit; no correspondence maps.  d_partials: 30 * vh_icp_num_partials(width, height) floats.  d_ticket: a device word
+ * of the caller's that is 0 before every launch -- clear it on the stream (vh_memset) where vh_icp_begin runs; the step
+ * leaves it 0.  publish (may be NULL): mapped host memory that receives the state's result after this step, its tag
+ * last (VhIcpResult); a step the state skips (lost / level done) publishes the state as it stands. */
+int vh_icp_step(const float* d_input4, const float* d_inputNormals4, const float* d_target4, const float* d_targetNormals4, uint32_t width, uint32_t height,
+                float distThres, float normalThres, float levelFactor, const VhDepthCameraParams* cp, float* d_partials, uint32_t* d_ticket,
+                VhIcpState* d_state, float angleTransThres, float distTransThres, float earlyOutResidual, VhIcpResult* publish, uint32_t tag, vhStream_t stream);
+/* the same publication by a one-wave kernel, for a solve whose last step is not a vh_icp_step */
+int vh_icp_publish(const VhIcpState* d_state, VhIcpResult* publish, uint32_t tag, vhStream_t stream);
 /* GlobalCameraTrackingState::readMembers on zParametersTracking*.txt (DSC/GlobalCameraTrackingState.h:14-60) */
 int vh_tracking_state_read(const char* filename, VhTrackingState* out);
 int vh_tracking_state_parse(const char* text, VhTrackingState* out);

@@ -412,6 +412,20 @@ typedef struct VhIcpState {
     uint32_t pad[8];
 } VhIcpState;
 
+/* What the last vh_icp_step of a solve leaves in mapped host memory for a host that polls instead of copying: the
+ * VhIcpState's result, then `tag` with a system-scope release store. */
+typedef struct VhIcpResult {
+    float delta[16];
+    uint32_t lost;
+    float sumRegError;
+    float sumRegWeight;
+    uint32_t numCorr;
+    float matrixCondition;
+    uint32_t iterations;
+    uint32_t pad;
+    uint32_t tag;
+} VhIcpResult;
+
 /* Device-resident state of one RGB-D solve (vh_icp_rgbd_*): a VhIcpState with the same meaning, plus the point the next
  * build step linearises at.  The reference recomputes both from deltaTransform before every build
  * (DSC/CUDACameraTrackingMultiResRGBD.cpp:204-208); here the solve step leaves them behind. */

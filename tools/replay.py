@@ -4,7 +4,7 @@ parameter file, optional mesh at the end) and prints one JSON line with the timi
 
     python tools/replay.py --params zParameters.txt [--tracking zParametersTracking.txt] [--rgbd-tracking] [--sens a.sens b.sens]
                            [--mesh scan.ply] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
-                           [--native [--batch N]]
+                           [--native [--batch N] [--native-tracking]]
 
 Without --sens the files named by s_binaryDumpSensorFile[i] in the parameter file are played.  The rendering keys
 (light, material, discontinuity thresholds, s_renderToFile, s_renderToFileDir) come from --params; --render-to switches
@@ -15,7 +15,9 @@ map is rendered into the colour camera with the `.sens` file's extrinsic (unless
 --native plays the files through the native frame loop fed with raw frames (Reconstruction.run_native): batches of
 16-bit depth + RGB frames decoded into pinned memory, converted, resampled and filtered on the device, no host wait per
 frame.  It is for recorded poses (s_binaryDumpSensorUseTrajectory = true, ...OnlyInit = false) and says why when the
-configuration needs the Python loop (ICP tracking, --record, --render-to, camera calibration)."""
+configuration needs the Python loop (ICP tracking, --record, --render-to, camera calibration).  With --native-tracking the
+native loop tracks the camera itself where the parameter file asks for it (s_binaryDumpSensorUseTrajectory = false, plain
+projective ICP): one host wait per frame, for the pose; the RGB-D tracker still needs the Python loop."""
 import argparse
 import json
 import os
@@ -39,6 +41,7 @@ def main():
     ap.add_argument("--camera-calibration", action="store_true", help="s_bUseCameraCalibration: remap depth into the colour camera")
     ap.add_argument("--native", action="store_true", help="play through the native frame loop, fed with raw frames")
     ap.add_argument("--batch", type=int, default=64, help="--native: frames decoded and handed over per call")
+    ap.add_argument("--native-tracking", action="store_true", help="--native: let the native loop track the camera (plain ICP) when the poses are not recorded")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -59,12 +62,12 @@ def main():
     rec = R.Reconstruction(g, t, args.sens or None, use_rgbd_tracking=args.rgbd_tracking, render_state=rs, calibration_state=cs)
     if args.native:  # the loop, its pinned buffers and the file, before the clock (the Python loop's reader has loaded its file above)
         try:
-            rec.prepare_native(args.batch)
+            rec.prepare_native(args.batch, tracking=args.native_tracking)
         except ValueError as e:
             raise SystemExit(str(e))
     t0 = time.perf_counter()
     if args.native:
-        n = rec.run_native(args.max_frames, batch=args.batch)
+        n = rec.run_native(args.max_frames, batch=args.batch, tracking=args.native_tracking)
         rec.native.synchronize()
     else:
         n = rec.run(args.max_frames)

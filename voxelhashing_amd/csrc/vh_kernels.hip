@@ -3634,23 +3634,16 @@ VHD bool icp_system_from_terms(const float* terms, double (&A)[6][6], double (&b
     return !zero;
 }
 
-// One wave: reductionSystemCPU (.cpp:52-92) over the wave partials in their order, then what computeBestRigidAlignment,
-// delinearizeTransformation and align do with the system on the host (DSC/CUDACameraTrackingMultiRes.cpp:186-253,
-// 306-318), the solve by icp_solve_6x6.
-__global__ __launch_bounds__(64) void k_icp_solve(VhIcpState* st, const float* partials, uint32_t nPartials, float angleThres, float distThres, float earlyOut, uint32_t lastInner)
+// What computeBestRigidAlignment, delinearizeTransformation and align do with the summed system on the host
+// (DSC/CUDACameraTrackingMultiRes.cpp:186-253, 306-318), the solve by icp_solve_6x6.  One lane; `terms` are the 30 sums.
+VHD void icp_solve_step(VhIcpState* st, const float* terms, float angleThres, float distThres, float earlyOut, uint32_t lastInner)
 {
-    __shared__ float sTerms[kIcpTerms];
-    if (st->lost || st->done) return;
-    const uint32_t t = threadIdx.x;
-    if (t < kIcpTerms) sTerms[t] = icp_sum_term(partials, nPartials, t); // one term per lane
-    __syncthreads();
-    if (t != 0u) return;
     double A[6][6], b[6];
     {
-        const bool nonzero = icp_system_from_terms(sTerms, A, b);
-        st->sumRegError = sTerms[27];
-        st->sumRegWeight = sTerms[28];
-        st->numCorr = (uint32_t)sTerms[29];
+        const bool nonzero = icp_system_from_terms(terms, A, b);
+        st->sumRegError = terms[27];
+        st->sumRegWeight = terms[28];
+        st->numCorr = (uint32_t)terms[29];
         st->iterations += 1u;
         if (!nonzero) { st->lost = 1u; return; } // ATA.isZero(): every |a_ij| <= 1e-5
     }
@@ -3683,6 +3676,167 @@ __global__ __launch_bounds__(64) void k_icp_solve(VhIcpState* st, const float* p
         if (fabsf(st->lastError - st->sumRegError) < earlyOut) st->done = 1u;
         st->lastError = st->sumRegError;
     }
+}
+
+// One wave: reductionSystemCPU (.cpp:52-92) over the wave partials in their order, then icp_solve_step.
+__global__ __launch_bounds__(64) void k_icp_solve(VhIcpState* st, const float* partials, uint32_t nPartials, float angleThres, float distThres, float earlyOut, uint32_t lastInner)
+{
+    __shared__ float sTerms[kIcpTerms];
+    if (st->lost || st->done) return;
+    const uint32_t t = threadIdx.x;
+    if (t < kIcpTerms) sTerms[t] = icp_sum_term(partials, nPartials, t); // one term per lane
+    __syncthreads();
+    if (t != 0u) return;
+    icp_solve_step(st, sTerms, angleThres, distThres, earlyOut, lastInner);
+}
+
+// The state's result into mapped host memory, the tag last (system-scope release: the host polls the tag and then reads
+// the words before it; the idiom of k_publish_words).  One lane.
+VHD void icp_publish(const VhIcpState* __restrict__ st, VhIcpResult* __restrict__ out, uint32_t tag)
+{
+    const VhIcpState s = *st; // (all loads in flight before the first store)
+#pragma unroll
+    for (int k = 0; k < 16; k++) out->delta[k] = s.delta[k];
+    out->lost = s.lost;
+    out->sumRegError = s.sumRegError;
+    out->sumRegWeight = s.sumRegWeight;
+    out->numCorr = s.numCorr;
+    out->matrixCondition = s.matrixCondition;
+    out->iterations = s.iterations;
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+    __hip_atomic_store(&out->tag, tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__global__ void k_icp_publish(const VhIcpState* st, VhIcpResult* out, uint32_t tag)
+{
+    if (blockIdx.x == 0u && threadIdx.x == 0u) icp_publish(st, out, tag);
+}
+
+// One outer iteration of a level whose s_maxInnerIter is 1, in one launch: k_icp_correspondences, k_icp_build_system and
+// k_icp_solve.  A wave owns the 768 pixels k_icp_build_system gives it; for each it computes the pair as
+// k_icp_correspondences does (the same expressions in the same order) and adds it to the 30 running sums, so the
+// correspondence maps are never written.  The wave's terms go to `partials` as before; the wave that draws the last
+// ticket sums the partials in their order and takes the step.  Every pixel's arithmetic and every order of summation is
+// that of the three kernels: the VhIcpState after the launch is theirs bit for bit.
+//
+// The hand-off of the partials crosses XCDs: plain stores, the wave waits for them, an agent-scope release fence, a
+// relaxed agent-scope ticket; the last arriver takes an agent-scope acquire before its plain loads.  No wave waits for
+// another.  Every wave has read delta / lost / done before it draws its ticket, and only the last arriver writes the
+// state, after all tickets are drawn.  *ticket is 0 when the launch starts (the caller clears it on the stream where it
+// runs vh_icp_begin) and the last arriver leaves it 0.
+// publish (may be null): mapped host memory that receives the state after this step, under `tag`.  A step that is
+// skipped (lost / done) changes nothing, so its first wave publishes the state as it stands.
+// A workgroup is ONE wave (64 threads): the ticket is broadcast with a shuffle and the last arriver's __syncthreads()
+// is its own.
+__global__ __launch_bounds__(64) void k_icp_step(const float4* input, const float4* inputNormals, const float4* target, const float4* targetNormals,
+                                                 uint32_t W, uint32_t H, float pairDistThres, float normalThres, float levelFactor, VhDepthCameraParams cp,
+                                                 float* partials, uint32_t* ticket, VhIcpState* st, float angleThres, float distThres, float earlyOut,
+                                                 VhIcpResult* publish, uint32_t tag)
+{
+    __shared__ float sTerms[kIcpTerms];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t skip = st->lost | st->done;
+    float D[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) D[k] = st->delta[k];
+    if (skip) {
+        if (publish && blockIdx.x == 0u && lane == 0u) icp_publish(st, publish, tag);
+        return;
+    }
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, nPixels = W * H;
+    const float mi = minf();
+    float acc[kIcpTerms];
+#pragma unroll
+    for (uint32_t k = 0; k < kIcpTerms; k++) acc[k] = 0.0f;
+    // Six pixels at a time: their input loads go out together, then their model loads (a lane that took its 12 pixels one
+    // after the other would wait for 24 dependent round trips); the sums take the pixels in their order all the same.
+    constexpr uint32_t kBatch = 6u;
+    for (uint32_t w0 = 0; w0 < kIcpWindow; w0 += kBatch) {
+        float4 p[kBatch], n[kBatch], tp[kBatch], tn[kBatch];
+        F3 pt[kBatch], nt[kBatch];
+        bool ok[kBatch];
+        uint32_t at[kBatch];
+#pragma unroll
+        for (uint32_t j = 0; j < kBatch; j++) {
+            const uint32_t idx = kIcpWindow * x + w0 + j;
+            ok[j] = idx < nPixels;
+            at[j] = ok[j] ? idx : 0u; // (a pixel past the end reads pixel 0 and is dropped)
+            p[j] = input[at[j]];
+            n[j] = inputNormals[at[j]];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kBatch; j++) {
+            at[j] = 0u;
+            pt[j] = nt[j] = mk3(0.0f, 0.0f, 0.0f);
+            ok[j] = ok[j] && p[j].x != mi && n[j].x != mi;
+            if (ok[j]) { // k_icp_correspondences
+                pt[j] = mat_mul_p(D, mk3(p[j].x, p[j].y, p[j].z));
+                nt[j] = mat_mul_d(D, mk3(n[j].x, n[j].y, n[j].z));
+                int sx = f2i((pt[j].x * cp.fx / pt[j].z + cp.mx) + 0.5f), sy = f2i((pt[j].y * cp.fy / pt[j].z + cp.my) + 0.5f);
+                sx = f2i((float)sx / levelFactor); sy = f2i((float)sy / levelFactor);
+                ok[j] = sx >= 0 && sy >= 0 && sx < (int)W && sy < (int)H;
+                if (ok[j]) at[j] = (uint32_t)sy * W + (uint32_t)sx;
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kBatch; j++) { // (a pixel without a pair reads pixel 0 and is dropped)
+            tp[j] = target[at[j]];
+            tn[j] = targetNormals[at[j]];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kBatch; j++) {
+            if (!(ok[j] && tp[j].x != mi && tn[j].x != mi)) continue;
+            const float dx = pt[j].x - tp[j].x, dy = pt[j].y - tp[j].y, dz = pt[j].z - tp[j].z;
+            const float d = sqrtf(dx * dx + dy * dy + dz * dz);
+            const float dNormal = nt[j].x * tn[j].x + nt[j].y * tn[j].y + nt[j].z * tn[j].z;
+            if (!(d <= pairDistThres && dNormal >= normalThres)) continue;
+            const float weight = fmaxf(0.0f, 0.5f * ((1.0f - d / pairDistThres) + (1.0f - cam_to_proj_z(cp, pt[j].z))));
+            // k_icp_build_system (the moving point is pt: the same product)
+            const F3 q = pt[j], pT = mk3(tp[j].x, tp[j].y, tp[j].z), nn = mk3(tn[j].x, tn[j].y, tn[j].z);
+            const float row[6] = { nn.x * q.y - nn.y * q.x, nn.z * q.x - nn.x * q.z, nn.y * q.z - nn.z * q.y, -nn.x, -nn.y, -nn.z };
+            const float b = nn.x * (q.x - pT.x) + nn.y * (q.y - pT.y) + nn.z * (q.z - pT.z);
+            uint32_t o = 0;
+#pragma unroll
+            for (uint32_t r = 0; r < 6u; r++) {
+#pragma unroll
+                for (uint32_t c = r; c < 6u; c++) acc[o + c - r] += weight * row[r] * row[c];
+                o += 6u - r;
+                acc[21u + r] += weight * row[r] * b;
+            }
+            const float dN = (pT.x - q.x) * nn.x + (pT.y - q.y) * nn.y + (pT.z - q.z) * nn.z;
+            acc[27] += weight * dN * dN;
+            acc[28] += weight;
+            acc[29] += 1.0f;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (uint32_t k = 0; k < kIcpTerms; k++) {
+            const float other = __shfl_down(acc[k], off);
+            if ((int)lane < off) acc[k] += other;
+        }
+    }
+    uint32_t drawn = 0u;
+    if (lane == 0u) {
+#pragma unroll
+        for (uint32_t k = 0; k < kIcpTerms; k++) partials[(size_t)blockIdx.x * kIcpTerms + k] = acc[k];
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    drawn = (uint32_t)__shfl((int)drawn, 0);
+    if (drawn != gridDim.x - 1u) return;
+    // the last arriver: every wave's partials are out
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane < kIcpTerms) sTerms[lane] = icp_sum_term(partials, gridDim.x, lane); // one term per lane
+    __syncthreads();
+    if (lane != 0u) return;
+    icp_solve_step(st, sTerms, angleThres, distThres, earlyOut, 1u);
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (publish) icp_publish(st, publish, tag);
 }
 
 // ---------------------------------------------------------------------------
@@ -4881,6 +5035,25 @@ int vh_icp_solve(VhIcpState* d_state, const float* d_partials, uint32_t numParti
 {
     if (!d_state || !d_partials) return VH_ERR_BAD_ARGUMENT;
     k_icp_solve<<<1, 64, 0, (hipStream_t)stream>>>(d_state, d_partials, numPartials, angleThres, distThres, earlyOutResidual, lastInnerIteration ? 1u : 0u);
+    return vh_last_launch_error();
+}
+
+int vh_icp_step(const float* d_input4, const float* d_inputNormals4, const float* d_target4, const float* d_targetNormals4, uint32_t width, uint32_t height,
+                float distThres, float normalThres, float levelFactor, const VhDepthCameraParams* cp, float* d_partials, uint32_t* d_ticket,
+                VhIcpState* d_state, float angleTransThres, float distTransThres, float earlyOutResidual, VhIcpResult* publish, uint32_t tag, vhStream_t stream)
+{
+    if (!d_input4 || !d_inputNormals4 || !d_target4 || !d_targetNormals4 || !cp || !d_partials || !d_ticket || !d_state) return VH_ERR_BAD_ARGUMENT;
+    if (width * height == 0) return VH_ERR_BAD_ARGUMENT; // (no wave would draw the last ticket)
+    k_icp_step<<<vh_icp_num_partials(width, height), 64, 0, (hipStream_t)stream>>>(
+        reinterpret_cast<const float4*>(d_input4), reinterpret_cast<const float4*>(d_inputNormals4), reinterpret_cast<const float4*>(d_target4),
+        reinterpret_cast<const float4*>(d_targetNormals4), width, height, distThres, normalThres, levelFactor, *cp, d_partials, d_ticket, d_state,
+        angleTransThres, distTransThres, earlyOutResidual, publish, tag);
+    return vh_last_launch_error();
+}
+int vh_icp_publish(const VhIcpState* d_state, VhIcpResult* publish, uint32_t tag, vhStream_t stream)
+{
+    if (!d_state || !publish) return VH_ERR_BAD_ARGUMENT;
+    k_icp_publish<<<1, 64, 0, (hipStream_t)stream>>>(d_state, publish, tag);
     return vh_last_launch_error();
 }
 

@@ -24,6 +24,9 @@
 //     Gauss filters of CUDARGBDSensor::process that are on, into the staging slot;
 //   * s_maxFramesInFlight: the host stays at most that many frames ahead of the device (polled through the mapped
 //     frame counter the fused integrate pass writes: no event).
+//   * setTracking: the pose of a frame comes from projective ICP against the ray cast of the model (:750-879 with
+//     s_binaryDumpSensorUseTrajectory = false), enqueued on the loop's stream with one launch per iteration
+//     (vh_icp_step); the host learns the pose from mapped host memory (frameTracked() below).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -104,6 +107,14 @@ Reconstruction::Reconstruction(CUDASceneRepHashSDF* sceneRep, CUDARayCastSDF* ra
     d_unfilteredDepth = d_unfilteredColor = nullptr;
     m_probePending = false;
     std::memset(m_probePose, 0, sizeof(m_probePose));
+    m_tracking = false;
+    m_trackedFrames = m_lostFrames = 0;
+    std::memset(&m_trackingState, 0, sizeof(m_trackingState));
+    d_trkPartials = d_trkIdentity = nullptr;
+    d_trkState = nullptr;
+    d_trkTicket = nullptr;
+    h_trkResult = d_trkResult = nullptr;
+    m_trkTag = 0;
     if (m_opt.s_framesOnHost) {
         const size_t n = (size_t)cp.m_imageWidth * cp.m_imageHeight;
         hipStream_t cs = nullptr;
@@ -138,6 +149,18 @@ Reconstruction::~Reconstruction()
     }
     if (d_unfilteredDepth) (void)hipFree(d_unfilteredDepth);
     if (d_unfilteredColor) (void)hipFree(d_unfilteredColor);
+    for (int i = 0; i < kStagingSlots; i++)
+        for (auto* v : { &d_trkInput[i], &d_trkInputNormal[i] })
+            for (float* q : *v)
+                if (q) (void)hipFree(q);
+    for (auto* v : { &d_trkModel, &d_trkModelNormal, &d_trkCorr, &d_trkCorrNormal })
+        for (float* q : *v)
+            if (q) (void)hipFree(q);
+    if (d_trkPartials) (void)hipFree(d_trkPartials);
+    if (d_trkState) (void)hipFree(d_trkState);
+    if (d_trkIdentity) (void)hipFree(d_trkIdentity);
+    if (d_trkTicket) (void)hipFree(d_trkTicket);
+    if (h_trkResult) (void)hipHostFree(h_trkResult);
     if (m_copyStream) (void)hipStreamDestroy((hipStream_t)m_copyStream);
     if (m_copyStream2) (void)hipStreamDestroy((hipStream_t)m_copyStream2);
 }
@@ -189,6 +212,54 @@ void Reconstruction::setRawFormat(const RawFrameFormat& f)
     m_raw = true;
 }
 
+// The tracker's buffers (CUDACameraTrackingMultiRes' constructor, vh_tracking.cpp): the input's levels once per staging
+// slot, because they are made on the copy stream while the main stream still aligns the frame before.
+void Reconstruction::setTracking(const VhTrackingState& ts)
+{
+    if (m_tracking) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setTracking: tracking is already set");
+    if (m_stats.frames || m_stats.invalidFrames || m_uploads || m_frameNumber) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setTracking: frames have been processed already");
+    if (!m_rayCast || !m_opt.s_renderEnabled) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setTracking: tracking aligns to the ray cast (needs a ray caster and s_renderEnabled)");
+    const unsigned int W = m_cp.m_imageWidth, H = m_cp.m_imageHeight, levels = ts.s_maxLevels;
+    if (levels == 0 || levels > VH_TRACKING_MAX_LEVELS || (W >> (levels - 1)) < 2 || (H >> (levels - 1)) < 2)
+        throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setTracking: bad pyramid");
+    auto floats = [](size_t n, const char* what) {
+        float* q = nullptr;
+        checkHip(hipMalloc((void**)&q, sizeof(float) * (n ? n : 1)), what);
+        return q;
+    };
+    unsigned int fac = 1;
+    for (unsigned int i = 0; i < levels; i++) {
+        m_levelWidth.push_back(W / fac);
+        m_levelHeight.push_back(H / fac);
+        const size_t n = 4 * (size_t)m_levelWidth[i] * m_levelHeight[i];
+        for (int slot = 0; slot < (int)kStagingSlots; slot++) { // (frames read in place use the first set only)
+            d_trkInput[slot].push_back(floats(n, "tracking input"));
+            d_trkInputNormal[slot].push_back(floats(n, "tracking input normals"));
+        }
+        d_trkModel.push_back(i ? floats(n, "tracking model") : nullptr);
+        d_trkModelNormal.push_back(i ? floats(n, "tracking model normals") : nullptr);
+        const bool three = ts.s_maxInnerIter[i] != 1u; // such a level keeps the three-kernel sequence and its maps
+        d_trkCorr.push_back(three ? floats(n, "tracking correspondences") : nullptr);
+        d_trkCorrNormal.push_back(three ? floats(n, "tracking correspondence normals") : nullptr);
+        fac *= 2;
+    }
+    d_trkPartials = floats(30 * (size_t)vh_icp_num_partials(W, H), "tracking partials");
+    checkHip(hipMalloc((void**)&d_trkState, sizeof(VhIcpState)), "VhIcpState");
+    checkHip(hipMalloc((void**)&d_trkTicket, sizeof(uint32_t)), "tracking ticket");
+    d_trkIdentity = floats(16, "deltaEstimate");
+    checkHip(hipHostMalloc((void**)&h_trkResult, sizeof(VhIcpResult), hipHostMallocMapped), "tracking result");
+    std::memset(h_trkResult, 0, sizeof(VhIcpResult));
+    checkHip(hipHostGetDevicePointer((void**)&d_trkResult, h_trkResult, 0), "tracking result");
+    // the estimate every solve starts from (:816-826 pass the identity), once
+    hipStream_t ms = (hipStream_t)m_sceneRep->getStream();
+    const vh::mat4f I = vh::mat4f::identity();
+    checkHip(hipMemcpyAsync(d_trkIdentity, I.m, sizeof(I.m), hipMemcpyHostToDevice, ms), "deltaEstimate");
+    checkHip(hipMemsetAsync(d_trkTicket, 0, sizeof(uint32_t), ms), "tracking ticket");
+    checkHip(hipStreamSynchronize(ms), "Reconstruction::setTracking");
+    m_trackingState = ts;
+    m_tracking = true;
+}
+
 void Reconstruction::synchronize()
 {
     if (m_copyStream) checkHip(hipStreamSynchronize((hipStream_t)m_copyStream), "hipStreamSynchronize");
@@ -208,6 +279,8 @@ void Reconstruction::reset()
     m_frameNumber = 0;
     m_probePending = false;
     for (int i = 0; i < kStagingSlots; i++) m_slotSceneFrame[i] = 0;
+    m_poses.clear();
+    m_trackedFrames = m_lostFrames = 0;
 }
 
 const ReconstructionStats& Reconstruction::getStats()
@@ -249,7 +322,10 @@ DepthCameraData Reconstruction::upload(const SequenceFrame& f)
     const unsigned int slot = m_uploads % kStagingSlots;
     const size_t n = (size_t)m_cp.m_imageWidth * m_cp.m_imageHeight;
     hipStream_t cs = (hipStream_t)m_copyStream, ms = (hipStream_t)m_sceneRep->getStream();
-    if (m_slotSceneFrame[slot] != 0) {
+    // With tracking the host has seen the ICP result of the frame before this one, so that frame's ray cast has run, and
+    // that is behind the integrate of the frame before it: every frame two or more back is done with its slot, and the
+    // slot's last frame is four back.  (A lost frame uploads without integrating: the scene's counter does not count it.)
+    if (m_slotSceneFrame[slot] != 0 && !m_tracking) {
         // the slot's last frame was the scene's frame number m_slotSceneFrame[slot]: done once a later frame's pass has started
         const unsigned int need = m_slotSceneFrame[slot] + 1u;
         const double w0 = now();
@@ -332,6 +408,10 @@ DepthCameraData Reconstruction::upload(const SequenceFrame& f)
         checkHip(hipEventRecord((hipEvent_t)t1, cs), "hipEventRecord");
         m_uploadTimers.emplace_back(t0, t1);
     }
+    if (m_tracking) { // what the tracker needs of the input depends on the frame alone: here, beside the previous frame's work
+        if (!mapped && !m_rawRun) checkHip(hipStreamWaitEvent(cs, (hipEvent_t)m_slotReady2[slot], 0), "hipStreamWaitEvent");
+        inputPyramid(slot, d_stageDepth[slot], m_copyStream);
+    }
     checkHip(hipEventRecord((hipEvent_t)m_slotReady[slot], cs), "hipEventRecord");
     checkHip(hipStreamWaitEvent(ms, (hipEvent_t)m_slotReady[slot], 0), "hipStreamWaitEvent");
     m_slotSceneFrame[slot] = m_sceneRep->getNumIntegratedFrames() + 1u; // the scene frame this upload feeds
@@ -354,6 +434,7 @@ void Reconstruction::frame(const SequenceFrame& f, const SequenceFrame* next)
     std::memcpy(transformation.m, f.rigidTransform, sizeof(transformation.m));
     if (!poseValid(transformation.m)) {
         m_stats.invalidFrames++;
+        m_poses.insert(m_poses.end(), 16, -std::numeric_limits<float>::infinity());
         return; // "INVALID FRAME"
     }
     if (!f.depth) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction: frame without a depth map");
@@ -444,28 +525,7 @@ void Reconstruction::frame(const SequenceFrame& f, const SequenceFrame* next)
         m_stats.streamingFramesPipelined++;
         if (quiet) m_stats.streamingStepsSkipped++;
     } else if (streaming) { // :881-900
-        const double t0 = now();
-        unsigned int nStreamedBlocks = 0;
-        if (m_opt.s_offlineProcessing) {
-            for (unsigned int i = 0; i < m_sceneRep->getOptions().s_streamingOutParts; i++) {
-                m_chunkGrid->streamOutToCPU(p, m_opt.s_streamingRadius, CUDASceneRepChunkGrid::s_useParts, nStreamedBlocks);
-                m_stats.blocksStreamedOut += nStreamedBlocks;
-            }
-            m_chunkGrid->streamInToGPUAll(p, m_opt.s_streamingRadius, CUDASceneRepChunkGrid::s_useParts, nStreamedBlocks);
-            m_stats.blocksStreamedIn += nStreamedBlocks;
-        } else if (threaded) {
-            m_chunkGrid->streamOutToCPUPass0GPU(p, m_opt.s_streamingRadius, CUDASceneRepChunkGrid::s_useParts, true);
-            m_stats.blocksStreamedOut += m_chunkGrid->getNumStreamedOutBlocks();
-            m_chunkGrid->streamInToGPUPass1GPU(true);
-            m_stats.blocksStreamedIn += m_chunkGrid->getNumStreamedInBlocks();
-        } else {
-            m_chunkGrid->streamOutToCPU(p, m_opt.s_streamingRadius, CUDASceneRepChunkGrid::s_useParts, nStreamedBlocks);
-            m_stats.blocksStreamedOut += nStreamedBlocks;
-            m_chunkGrid->streamInToGPU(p, m_opt.s_streamingRadius, CUDASceneRepChunkGrid::s_useParts, nStreamedBlocks);
-            m_stats.blocksStreamedIn += nStreamedBlocks;
-        }
-        d_bitMask = m_chunkGrid->getBitMaskGPU();
-        m_stats.hostWaitSeconds += now() - t0; // read-backs of the streaming counters: the host waits for the device here
+        d_bitMask = streamAround(p);
     }
 
     // the question for the next frame, behind this frame's alloc
@@ -496,6 +556,148 @@ void Reconstruction::frame(const SequenceFrame& f, const SequenceFrame* next)
     if (pipelined && (ask || step == kPipelined)) m_chunkGrid->pipelineAsk(ask, np, m_opt.s_streamingRadius);
     m_frameNumber++;
     m_stats.frames++;
+    m_poses.insert(m_poses.end(), transformation.m, transformation.m + 16);
+}
+
+// :881-900, the reference's order of calls: the host reads the streaming counters back
+const unsigned int* Reconstruction::streamAround(const vh::vec3f& p)
+{
+    const bool threaded = !m_opt.s_offlineProcessing && !m_chunkGrid->getTerminatedThread();
+    const double t0 = now();
+    unsigned int nStreamedBlocks = 0;
+    if (m_opt.s_offlineProcessing) {
+        for (unsigned int i = 0; i < m_sceneRep->getOptions().s_streamingOutParts; i++) {
+            m_chunkGrid->streamOutToCPU(p, m_opt.s_streamingRadius, CUDASceneRepChunkGrid::s_useParts, nStreamedBlocks);
+            m_stats.blocksStreamedOut += nStreamedBlocks;
+        }
+        m_chunkGrid->streamInToGPUAll(p, m_opt.s_streamingRadius, CUDASceneRepChunkGrid::s_useParts, nStreamedBlocks);
+        m_stats.blocksStreamedIn += nStreamedBlocks;
+    } else if (threaded) {
+        m_chunkGrid->streamOutToCPUPass0GPU(p, m_opt.s_streamingRadius, CUDASceneRepChunkGrid::s_useParts, true);
+        m_stats.blocksStreamedOut += m_chunkGrid->getNumStreamedOutBlocks();
+        m_chunkGrid->streamInToGPUPass1GPU(true);
+        m_stats.blocksStreamedIn += m_chunkGrid->getNumStreamedInBlocks();
+    } else {
+        m_chunkGrid->streamOutToCPU(p, m_opt.s_streamingRadius, CUDASceneRepChunkGrid::s_useParts, nStreamedBlocks);
+        m_stats.blocksStreamedOut += nStreamedBlocks;
+        m_chunkGrid->streamInToGPU(p, m_opt.s_streamingRadius, CUDASceneRepChunkGrid::s_useParts, nStreamedBlocks);
+        m_stats.blocksStreamedIn += nStreamedBlocks;
+    }
+    m_stats.hostWaitSeconds += now() - t0; // read-backs of the streaming counters: the host waits for the device here
+    return m_chunkGrid->getBitMaskGPU();
+}
+
+// CUDARGBDSensor::process :173-174 (camera-space positions, normals) and the input half of applyCT's pyramids
+// (DSC/CUDACameraTrackingMultiRes.cpp:256-263) for one frame, on `stream`
+void Reconstruction::inputPyramid(unsigned int slot, const float* d_depth, vhStream_t stream)
+{
+    std::vector<float*>&in = d_trkInput[slot], &inN = d_trkInputNormal[slot];
+    check(vh_convert_depth_float_to_camera_space_float4(in[0], d_depth, &m_cp, m_levelWidth[0], m_levelHeight[0], stream), "convertDepthFloatToCameraSpaceFloat4");
+    check(vh_compute_normals(inN[0], in[0], m_levelWidth[0], m_levelHeight[0], stream), "computeNormals");
+    for (size_t i = 0; i + 1 < in.size(); i++) {
+        check(vh_resample_float4_map(in[i + 1], m_levelWidth[i + 1], m_levelHeight[i + 1], in[i], m_levelWidth[i], m_levelHeight[i], stream), "resampleFloat4Map");
+        check(vh_compute_normals(inN[i + 1], in[i + 1], m_levelWidth[i + 1], m_levelHeight[i + 1], stream), "computeNormals");
+    }
+}
+
+// One frame with tracking: reconstruction() :750-879 with s_binaryDumpSensorUseTrajectory = false.  Everything is
+// enqueued on the loop's stream without a blocking call; the host then waits once, for the tag the solve's last step
+// stores into mapped host memory behind the result, because the pose decides what streaming and integrate are asked.
+void Reconstruction::frameTracked(const SequenceFrame& f)
+{
+    if (!f.depth) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction: frame without a depth map");
+    const VhTrackingState& ts = m_trackingState;
+    vhStream_t stream = m_sceneRep->getStream();
+    DepthCameraData cam;
+    unsigned int slot = 0;
+    if (m_opt.s_framesOnHost || m_rawRun) {
+        cam = upload(f);
+        slot = (m_uploads - 1u) % kStagingSlots;
+    } else {
+        std::memset(&cam, 0, sizeof(cam));
+        cam.d_depthData = const_cast<float*>(f.depth);
+        cam.d_colorData = const_cast<float*>(static_cast<const float*>(f.color));
+        inputPyramid(0, cam.d_depthData, stream);
+    }
+    const float minf = -std::numeric_limits<float>::infinity();
+    vh::mat4f transformation = vh::mat4f::identity();
+    if (m_frameNumber > 0) { // :750 "getFrameNumber() > 1" with frames counted from 1
+        const vh::mat4f lastTransform = m_sceneRep->getLastRigidTransform();
+        m_rayCast->render(m_sceneRep->getHashData(), m_sceneRep->getHashParams(), m_cp, lastTransform, nullptr); // :763
+        const RayCastData& rd = m_rayCast->getRayCastData();
+        const size_t levels = m_levelWidth.size();
+        std::vector<float*>&in = d_trkInput[slot], &inN = d_trkInputNormal[slot];
+        d_trkModel[0] = rd.d_depth4;
+        d_trkModelNormal[0] = rd.d_normals;
+        struct Borrowed { // (level 0 of the model is the ray caster's: the destructor frees what the vectors hold)
+            std::vector<float*>&a, &b;
+            ~Borrowed() { a[0] = b[0] = nullptr; }
+        } borrowed{ d_trkModel, d_trkModelNormal };
+        for (size_t i = 0; i + 1 < levels; i++) { // the model half of the pyramids, :256-263
+            check(vh_resample_float4_map(d_trkModel[i + 1], m_levelWidth[i + 1], m_levelHeight[i + 1], d_trkModel[i], m_levelWidth[i], m_levelHeight[i], stream), "resampleFloat4Map");
+            check(vh_compute_normals(d_trkModelNormal[i + 1], d_trkModel[i + 1], m_levelWidth[i + 1], m_levelHeight[i + 1], stream), "computeNormals");
+        }
+        checkHip(hipMemsetAsync(d_trkTicket, 0, sizeof(uint32_t), (hipStream_t)stream), "tracking ticket");
+        check(vh_icp_begin(d_trkState, d_trkIdentity, stream), "vh_icp_begin");
+        // the step that is the frame's last publishes the result itself: a publishing kernel behind it would be one more
+        // launch in a chain of dependent launches, and the step's last wave holds the state in its hands anyway
+        int lastLevel = -1;
+        for (int level = 0; level < (int)levels && lastLevel < 0; level++)
+            if (ts.s_maxOuterIter[level]) lastLevel = level;
+        const uint32_t tag = ++m_trkTag;
+        bool published = false;
+        // coarse to fine, :265-279; align :291-321 with the loop exits taken on the device
+        for (int level = (int)levels - 1; level >= 0; level--) {
+            const unsigned int W = m_levelWidth[level], H = m_levelHeight[level];
+            const float levelFactor = std::pow(2.0f, (float)level);
+            check(vh_icp_begin_level(d_trkState, stream), "vh_icp_begin_level");
+            for (unsigned int outer = 0; outer < ts.s_maxOuterIter[level]; outer++) {
+                const unsigned int inner = ts.s_maxInnerIter[level];
+                if (inner == 1u) {
+                    const bool last = level == lastLevel && outer + 1 == ts.s_maxOuterIter[level];
+                    check(vh_icp_step(in[level], inN[level], d_trkModel[level], d_trkModelNormal[level], W, H, ts.s_distThres[level], ts.s_normalThres[level],
+                                      levelFactor, &m_cp, d_trkPartials, d_trkTicket, d_trkState, ts.s_angleTransThres[level], ts.s_distTransThres[level],
+                                      ts.s_residualEarlyOut[level], last ? d_trkResult : nullptr, tag, stream), "vh_icp_step");
+                    published = published || last;
+                    continue;
+                }
+                check(vh_icp_projective_correspondences(in[level], inN[level], d_trkModel[level], d_trkModelNormal[level], d_trkCorr[level], d_trkCorrNormal[level],
+                                                        W, H, ts.s_distThres[level], ts.s_normalThres[level], levelFactor, d_trkState, &m_cp, stream), "projectiveCorrespondences");
+                for (unsigned int i = 0; i < inner; i++) {
+                    check(vh_icp_build_linear_system(W, H, d_trkPartials, in[level], d_trkCorr[level], d_trkCorrNormal[level], d_trkState, stream), "buildLinearSystem");
+                    check(vh_icp_solve(d_trkState, d_trkPartials, vh_icp_num_partials(W, H), ts.s_angleTransThres[level], ts.s_distTransThres[level],
+                                       ts.s_residualEarlyOut[level], i + 1 == inner, stream), "vh_icp_solve");
+                }
+            }
+        }
+        if (!published) check(vh_icp_publish(d_trkState, d_trkResult, tag, stream), "vh_icp_publish"); // (the last level is a three-kernel one, or no level iterates)
+        // the one wait of the frame
+        const double w0 = now();
+        while (__atomic_load_n(&h_trkResult->tag, __ATOMIC_ACQUIRE) != tag) {
+            std::this_thread::yield();
+            if (now() - w0 > 30.0) throw vh::Error(VH_ERR_TIMEOUT, "Reconstruction: no tracking result from the device for 30 s");
+        }
+        m_stats.hostWaitSeconds += now() - w0;
+        if (h_trkResult->lost) { // "!!! TRACKING LOST !!!": the frame is not integrated, the scene keeps its pose
+            m_lostFrames++;
+            m_frameNumber++;
+            m_poses.insert(m_poses.end(), 16, minf);
+            return;
+        }
+        vh::mat4f delta;
+        std::memcpy(delta.m, h_trkResult->delta, sizeof(delta.m));
+        transformation = lastTransform * delta;
+        m_trackedFrames++;
+    }
+    const unsigned int* d_bitMask = nullptr;
+    if (m_opt.s_streamingEnabled && m_chunkGrid)
+        d_bitMask = streamAround(transformation.transformPoint({ m_opt.s_streamingPos[0], m_opt.s_streamingPos[1], m_opt.s_streamingPos[2] }));
+    // the pose is not known before the ray cast: alloc cannot ride in its launch, whatever s_allocAhead says
+    if (m_opt.s_integrationEnabled) m_sceneRep->integrate(transformation, cam, m_cp, d_bitMask); // :903
+    else m_sceneRep->setLastRigidTransformAndCompactify(transformation, m_cp);                   // :907
+    m_frameNumber++;
+    m_stats.frames++;
+    m_poses.insert(m_poses.end(), transformation.m, transformation.m + 16);
 }
 
 void Reconstruction::run(const SequenceFrame* frames, unsigned int n, const SequenceFrame* after)
@@ -518,7 +720,8 @@ void Reconstruction::run(const SequenceFrame* frames, unsigned int n, const Sequ
             }
             waited += now() - w0;
         }
-        frame(frames[i], i + 1 < n ? &frames[i + 1] : after);
+        if (m_tracking) frameTracked(frames[i]); // (the pose of the next frame is not known ahead: nothing to look at)
+        else frame(frames[i], i + 1 < n ? &frames[i + 1] : after);
     }
     const double total = now() - t0, streamWait = m_stats.hostWaitSeconds - streamWait0;
     m_stats.hostWaitSeconds += waited;
@@ -596,6 +799,27 @@ int vh_reconstruction_run_raw_ahead(VhReconstruction* r, const VhRawSequenceFram
 {
     if (!r || (n && !frames)) return VH_ERR_BAD_ARGUMENT;
     return guarded([&] { r->impl.runRaw(frames, n, next); });
+}
+int vh_reconstruction_set_tracking(VhReconstruction* r, const VhTrackingState* settings)
+{
+    if (!r || !settings) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { r->impl.setTracking(*settings); });
+}
+int vh_reconstruction_get_poses(VhReconstruction* r, uint32_t first, uint32_t n, float* out)
+{
+    if (!r || (n && !out)) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] {
+        const std::vector<float>& poses = r->impl.getPoses();
+        if ((size_t)first + n > poses.size() / 16) throw vh::Error(VH_ERR_BAD_ARGUMENT, "vh_reconstruction_get_poses: frame range outside the frames fed");
+        if (n) std::memcpy(out, poses.data() + 16 * (size_t)first, sizeof(float) * 16 * n);
+    });
+}
+int vh_reconstruction_get_tracking_stats(VhReconstruction* r, uint64_t* trackedFrames, uint64_t* lostFrames)
+{
+    if (!r || !trackedFrames || !lostFrames) return VH_ERR_BAD_ARGUMENT;
+    *trackedFrames = r->impl.getNumTrackedFrames();
+    *lostFrames = r->impl.getNumLostFrames();
+    return VH_OK;
 }
 int vh_reconstruction_synchronize(VhReconstruction* r)
 {

@@ -452,6 +452,24 @@ class Reconstruction:
         else:
             check(self.L.vh_reconstruction_run_raw(self.handle, ptr, n), "Reconstruction::runRaw")
 
+    # ---- camera tracking inside the loop ----------------------------------------------------------------------------
+    def setTracking(self, tracking_state):
+        """Once, before the first frame: from then on run() / runRaw() ignore the frames' poses; every frame after the first
+        is aligned to the ray cast of the model by projective ICP (tracking_state: a TrackingState) and integrated at
+        lastRigidTransform * delta, a frame on which tracking is lost is not integrated.  Needs a ray caster."""
+        check(self.L.vh_reconstruction_set_tracking(self.handle, C.byref(tracking_state)), "Reconstruction::setTracking")
+
+    def getPoses(self, first=0, count=None):
+        """-> [count, 4, 4] float32: the pose each frame fed since creation / reset was integrated at, all -inf for a frame
+        that was not (tracking lost, invalid recorded pose).  count=None: up to the last frame fed (asks getStats)."""
+        if count is None:
+            st = self.getStats()
+            count = st["frames"] + st["invalidFrames"] + st["lostFrames"] - first
+        out = np.empty((max(int(count), 0), 4, 4), dtype=np.float32)
+        if len(out):
+            check(self.L.vh_reconstruction_get_poses(self.handle, int(first), len(out), out.ctypes.data_as(C.POINTER(C.c_float))), "Reconstruction::getPoses")
+        return out
+
     def synchronize(self):
         check(self.L.vh_reconstruction_synchronize(self.handle), "Reconstruction::synchronize")
 
@@ -464,7 +482,16 @@ class Reconstruction:
     def getStats(self):
         st = T.ReconstructionStats()
         check(self.L.vh_reconstruction_get_stats(self.handle, C.byref(st)), "Reconstruction::getStats")
-        return {k: getattr(st, k) for k, _ in T.ReconstructionStats._fields_}
+        out = {k: getattr(st, k) for k, _ in T.ReconstructionStats._fields_}
+        out["trackedFrames"], out["lostFrames"] = self.getTrackingStats()
+        return out
+
+    def getTrackingStats(self):
+        """-> (trackedFrames, lostFrames): frames integrated at a pose the loop tracked itself, frames on which tracking was
+        lost; both 0 without setTracking.  Waits for nothing."""
+        a, b = C.c_uint64(), C.c_uint64()
+        check(self.L.vh_reconstruction_get_tracking_stats(self.handle, C.byref(a), C.byref(b)), "Reconstruction::getTrackingStats")
+        return a.value, b.value
 
 
 class LauncherScene:

@@ -149,14 +149,18 @@ def depth_image_rgba8(depth):
     return (out * f(255)).astype(np.uint8)
 
 
-def native_refusal(app_state, render_state=None, camera_calibration=False, use_rgbd_tracking=False):
+def native_refusal(app_state, render_state=None, camera_calibration=False, use_rgbd_tracking=False, tracking=False):
     """Why the native frame loop cannot play this configuration, as text, or None when it can.  The native loop
     (engine.Reconstruction) integrates every frame at the pose the file holds: s_binaryDumpSensorUseTrajectory = true,
-    s_binaryDumpSensorUseTrajectoryOnlyInit = false.  Needs no device."""
+    s_binaryDumpSensorUseTrajectoryOnlyInit = false.  tracking=True: the caller lets the loop track the camera itself
+    (engine.Reconstruction.setTracking), which admits s_binaryDumpSensorUseTrajectory = false with the plain ICP tracker.
+    Needs no device."""
     g = app_state
-    if not g.s_binaryDumpSensorUseTrajectory or use_rgbd_tracking:
+    if tracking and use_rgbd_tracking:
+        return "the poses come from the RGB-D tracker: the native loop tracks with plain projective ICP only"
+    if (not g.s_binaryDumpSensorUseTrajectory and not tracking) or use_rgbd_tracking:
         return "the poses come from ICP tracking (s_binaryDumpSensorUseTrajectory = false): the native loop has no tracker"
-    if g.s_binaryDumpSensorUseTrajectoryOnlyInit:
+    if g.s_binaryDumpSensorUseTrajectory and g.s_binaryDumpSensorUseTrajectoryOnlyInit:  # (without the trajectory the key means nothing)
         return "s_binaryDumpSensorUseTrajectoryOnlyInit = true tracks from the recorded pose: the native loop has no tracker"
     if not g.s_trackingEnabled:
         return "s_trackingEnabled = false integrates every frame at the identity, not at the recorded pose"
@@ -417,14 +421,14 @@ class Reconstruction:
         return n
 
     # -- the same sequence through the native frame loop ------------------------------------------------------------
-    def prepare_native(self, batch=64):
+    def prepare_native(self, batch=64, tracking=False):
         """what run_native needs before its first frame: the native loop with the raw format of the first file, two sets of
         pinned buffers of `batch` frames, the file loaded.  run_native calls it; a caller that times the frames alone
         calls it first (the Python loop's reader loads its file in the constructor too)."""
         from .lib import PinnedArray
         if self.native is not None:
             return
-        why = native_refusal(self.gas, self.render_state, self.camera_calibration, self.use_rgbd_tracking)
+        why = native_refusal(self.gas, self.render_state, self.camera_calibration, self.use_rgbd_tracking, tracking=tracking)
         if why is None and self.frame_number:
             why = "frames of this sequence have been played by the Python loop already"
         if why is not None:
@@ -441,20 +445,26 @@ class Reconstruction:
                             (g.s_colorSigmaD, g.s_colorSigmaR) if g.s_colorFilter else None)
         self._native_sets = [(PinnedArray((batch, h.m_depthHeight, h.m_depthWidth), np.uint16),
                               PinnedArray((batch, h.m_colorHeight, h.m_colorWidth, 3), np.uint8) if has_color else None) for _ in range(2)]
+        # the loop tracks where the Python loop would (_reconstruct): the file's poses are not used
+        self._native_tracked = bool(tracking) and not g.s_binaryDumpSensorUseTrajectory
+        if self._native_tracked:
+            native.setTracking(self.tracking)
         self._native_sens = SD.SensorData.loadFromFile(self.sens_files[self.file_idx])
         self._native_at = 0
         self.native = native
 
-    def run_native(self, max_frames=None, batch=64):
+    def run_native(self, max_frames=None, batch=64, tracking=False):
         """Plays the `.sens` files through the native frame loop (engine.Reconstruction) fed with raw frames: a batch of
         frames is decoded into pinned memory (16-bit depth, RGB) while the device works on the batch before, and handed
         over with one call, the next frame's pose as look-ahead.  The device converts, resamples and filters them
-        (vh_ingest_frame) as CUDARGBDSensor.process does for the Python loop.  For recorded poses only: raises
-        ValueError with the reason otherwise (native_refusal).  -> number of frames read"""
+        (vh_ingest_frame) as CUDARGBDSensor.process does for the Python loop.  For recorded poses, and with tracking=True
+        for poses from the plain ICP tracker (s_binaryDumpSensorUseTrajectory = false: the loop tracks the camera itself,
+        trajectory and lost_frames are filled as the Python loop fills them); raises ValueError with the reason otherwise
+        (native_refusal).  -> number of frames read"""
         h = self.reader.header
         batch = max(int(batch), 1)
         has_color = h.m_colorWidth * h.m_colorHeight > 0
-        self.prepare_native(batch)
+        self.prepare_native(batch, tracking)
         if self._native_sets[0][0].shape[0] < batch:
             raise ValueError("run_native: the batch size is fixed by the first call")
 
@@ -507,6 +517,13 @@ class Reconstruction:
             if ahead is not None:
                 frames[n].rigidTransform[:] = [float(v) for v in ahead]
             self.native.runRaw(frames, 0, n, lookahead=ahead is not None)
+            if self._native_tracked:  # the poses are the loop's own (the host has them when runRaw returns)
+                for p in self.native.getPoses(self.frame_number, n):
+                    if p[0, 0] == MINF:
+                        self.lost_frames += 1
+                    else:
+                        self.trajectory.append(p.copy())
+                poses = ()
             for p in poses:
                 if not (p[0] == MINF or np.isnan(p[0])):
                     self.trajectory.append(p.reshape(4, 4).copy())

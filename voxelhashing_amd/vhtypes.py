@@ -183,6 +183,14 @@ class IcpState(C.Structure):
     ]
 
 
+class IcpResult(C.Structure):
+    """VhIcpResult: what the last vh_icp_step of a solve leaves in mapped host memory, the tag last"""
+    _fields_ = [
+        ("delta", C.c_float * 16), ("lost", C.c_uint32), ("sumRegError", C.c_float), ("sumRegWeight", C.c_float), ("numCorr", C.c_uint32),
+        ("matrixCondition", C.c_float), ("iterations", C.c_uint32), ("pad", C.c_uint32), ("tag", C.c_uint32),
+    ]
+
+
 class TrackingStateRGBD(C.Structure):
     """VhTrackingStateRGBD: the f5 settings plus the four per-level keys of the RGB-D tracker"""
     _fields_ = [
