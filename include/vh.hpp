@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "vh_api.h"
+#include "vh_owners.hpp"
 
 typedef VhHashEntry HashEntry;
 typedef VhVoxel Voxel;
@@ -43,11 +44,6 @@ typedef VhRayCastData RayCastData;
 typedef VhSDFBlockDesc SDFBlockDesc;
 
 namespace vh {
-
-struct Error : public std::runtime_error {
-    int code;
-    Error(int c, const std::string& what) : std::runtime_error(what), code(c) {}
-};
 
 struct vec3f { float x, y, z; };
 struct vec3i { int x, y, z; };
@@ -66,6 +62,35 @@ struct mat4f {
 
 struct SDFBlock { // DSC/CUDASceneRepChunkGrid.h:11-21
     Voxel data[VH_SDF_BLOCK_VOXELS];
+};
+
+// The plain projective-ICP solve (DSC/CUDACameraTrackingMultiRes.cpp:241-321) as its two hosts enqueue it:
+// CUDACameraTrackingMultiRes::applyCT and Reconstruction's tracked frame (vh_tracking.cpp).
+// The maps of one call, per level; owns nothing (level 0 is usually somebody else's: the sensor's, the ray caster's).
+struct IcpPyramid {
+    float* map[VH_TRACKING_MAX_LEVELS];
+    float* normal[VH_TRACKING_MAX_LEVELS];
+};
+// level 0 as given, the levels from 1 on from their owners (whose element 0 is not looked at)
+IcpPyramid icpPyramid(float* map0, float* normal0, const std::vector<DevicePtr<float>>& maps, const std::vector<DevicePtr<float>>& normals);
+// the device scratch of a solve, and its enqueue
+struct IcpSolver {
+    IcpSolver(unsigned int imageWidth, unsigned int imageHeight, unsigned int levels, const char* who); // throws who + ": bad pyramid"
+    std::vector<unsigned int> width, height;                            // per level
+    std::vector<DevicePtr<float>> model, modelNormal;                   // levels >= 1 (element 0 stays empty)
+    std::vector<DevicePtr<float>> correspondence, correspondenceNormal; // what a three-kernel level keeps between its kernels
+    DevicePtr<float> partials;
+    DevicePtr<float> estimate;     // the 4x4 delta a solve starts from: the caller writes it
+    DevicePtr<VhIcpState> state;   // where a solve leaves its outcome
+    DevicePtr<uint32_t> ticket;    // vh_icp_step's count of finished workgroups
+    // level i + 1 of a pyramid from its level i (resampleFloat4Map + computeNormals, :256-263)
+    void coarserLevel(const IcpPyramid& p, unsigned int i, vhStream_t stream) const;
+    // Coarse to fine from `estimate` (:265-321, the loop exits taken on the device).  fusedStep: an iteration of a level
+    // with s_maxInnerIter == 1 is one launch (vh_icp_step) instead of three.  d_result: the outcome is also published
+    // there (mapped host memory) with `tag` stored behind it -- by the last step itself if that is a fused one, by
+    // vh_icp_publish otherwise.
+    void align(const IcpPyramid& input, const IcpPyramid& model, const VhTrackingState& settings, const DepthCameraParams& depthCameraParams,
+               bool fusedStep, VhIcpResult* d_result, uint32_t tag, vhStream_t stream) const;
 };
 
 } // namespace vh
@@ -135,7 +160,6 @@ public:
 
 private:
     void create(const HashParams& params);
-    void destroy();
     void alloc(const DepthCameraData&, const DepthCameraParams&, const unsigned int* d_bitMask, bool jobPrepared); // :247
     void compactifyHashEntries(const DepthCameraParams&);                                        // :282
     void integrateFused(const DepthCameraData&, const DepthCameraParams&);
@@ -144,22 +168,23 @@ private:
     void pollOccupiedCount(bool block);
 
     HashParams m_hashParams;
-    HashData m_hashData;
+    HashData m_hashData; // filled by the C ABI's allocator (vh_hash_data_alloc); m_hashDataOwner gives it back
+    struct HashDataFree { void operator()(HashData* hd) const noexcept; };
+    std::unique_ptr<HashData, HashDataFree> m_hashDataOwner;
     VhSceneOptions m_options;
     vhStream_t m_stream;
     unsigned int m_numIntegratedFrames;
     int32_t m_lockEpoch;
-    uint32_t* h_occupied;     // mapped pinned words: the fused integrate kernel mirrors {block count, frame number} here
-    void* m_occupiedEvent;    // device alias of h_occupied
+    vh::Mapped<uint32_t> m_occupied; // the fused integrate kernel mirrors {block count, frame number} here
     bool m_occupiedPending;   // a frame was enqueued since the host value was last known exact
     bool m_counterCleared;    // d_hashCompactifiedCounter is known to be 0 (k_alloc clears it)
-    VhStageTimer* m_timer;
+    std::unique_ptr<VhStageTimer> m_timer;
     unsigned int m_tableEpoch;
     VhFrameJob m_job;         // alloc + compactify of the frame in progress
     int m_aheadPending;       // 0 none, 1 job prepared by integrateAhead()
-    void* d_packedFrame;      // the frame as the alloc pass packs it for the pass over the voxels (8 bytes per pixel)
+    vh::DevicePtr<unsigned char> d_packedFrame; // the frame as the alloc pass packs it for the pass over the voxels (8 bytes per pixel)
     size_t m_packedPixels;
-    uint32_t* d_riderDone;    // VH_RIDER_DONE_WORDS words (see VhFrameJob::d_riderDone)
+    vh::DevicePtr<uint32_t> d_riderDone; // VH_RIDER_DONE_WORDS words (see VhFrameJob::d_riderDone)
     uint32_t m_riderTotals[2]; // VhFrameJob::listDoneTotal, listClassTotal as of the last launch
     void keepRiderTotals();
     unsigned int m_riderMostBlocks;
@@ -197,17 +222,18 @@ public:
 
 private:
     RayCastParams m_params;
-    RayCastData m_data;
+    RayCastData m_data; // the four maps below, as the kernels and the callers take them
+    vh::DevicePtr<float> d_depth, d_depth4, d_normals, d_colors;
     vhStream_t m_stream;
-    VhStageTimer* m_timer;
+    std::unique_ptr<VhStageTimer> m_timer;
     bool m_timeMarchOnly;
     unsigned int m_timeStride, m_renderCalls;
-    uint32_t* d_tileHeads;     // {min, max camera depth, block count, 0} per 8x8-pixel tile
-    VhTileBlock* d_tileBlocks; // up to VH_TILE_LIST_CAPACITY_LARGE blocks per tile
-    uint32_t *h_longestList, *d_longestList; // mapped host word: longest tile list the ray caster met lately
+    vh::DevicePtr<uint32_t> d_tileHeads;     // {min, max camera depth, block count, 0} per 8x8-pixel tile
+    vh::DevicePtr<VhTileBlock> d_tileBlocks; // up to VH_TILE_LIST_CAPACITY_LARGE blocks per tile
+    vh::Mapped<uint32_t> m_longestList;      // longest tile list the ray caster met lately
     bool m_largeTables;        // current choice of table size
     uint32_t m_quietFrames, m_tileCapacity;
-    uint32_t* d_schedule;      // tiles by cost class, for the launch order of the next render()
+    vh::DevicePtr<uint32_t> d_schedule; // tiles by cost class, for the launch order of the next render()
     uint32_t m_phase;          // render() calls with intervals so far
     unsigned int m_preSplatsUsed;
     bool m_useIntervals;
@@ -327,7 +353,7 @@ public:
     void pipelineDrain(bool undo = true);
     void pipelineReturn(const StreamDecision& d, const vh::vec3f& posCamera, float radius); // hands an unused pipelineDecision() back
     unsigned int pipelineCapacity() const { return (unsigned int)kPipelineBlocks; }
-    unsigned int* getBitMaskDevice() { return d_bitMask; } // (current while the pipeline runs: no upload)
+    unsigned int* getBitMaskDevice() { return d_bitMask.get(); } // (current while the pipeline runs: no upload)
     void pipelineTotals(unsigned long long* blocksOut, unsigned long long* blocksIn); // drains; blocks moved by the pipeline so far
     // blocks that stream-in passes could not insert and that went back to the host grid (not in the reference)
     unsigned int getNumFailedInserts() const { return m_numFailedInserts; }
@@ -387,7 +413,6 @@ private:
     void workerLoop();
     void create(const vh::vec3f& voxelExtends, const vh::vec3i& gridDimensions, const vh::vec3i& minGridPos,
                 unsigned int initialChunkListSize, bool streamingEnabled);
-    void destroy();
     void setBit(unsigned int index);
     void resetBit(unsigned int index);
     bool refileFailedInserts(int slot, const SDFBlockDesc* descs, const vh::SDFBlock* blocks, unsigned int& nIn);
@@ -422,50 +447,44 @@ private:
     uint32_t m_plOutTag, m_plOutMost;
     struct { bool pending; uint32_t tag; unsigned int nIn; } m_plInsert[2]; // per staging slot: an insert whose outcome has not been looked at
     std::atomic<unsigned long long> m_plBlocksOut, m_plBlocksIn;
-    SDFBlockDesc* d_plOutDesc[2];      // pass 1 -> pass 2 (device)
-    SDFBlockDesc* h_plOutDesc[2];      // mapped pinned: pass 2 writes the blocks it moves straight to the host
-    vh::SDFBlock* h_plOutBlocks[2];
-    SDFBlockDesc* hd_plOutDesc[2];     // their device aliases
-    vh::SDFBlock* hd_plOutBlocks[2];
-    uint32_t* h_plOutMirror[2];        // mapped pinned {count, 0, tag}
-    uint32_t* hd_plOutMirror[2];
-    SDFBlockDesc* h_plInDesc[2];       // pinned staging of the worker's upload
-    vh::SDFBlock* h_plInBlocks[2];
-    SDFBlockDesc* d_plInDesc[2];
-    vh::SDFBlock* d_plInBlocks[2];
+    vh::DevicePtr<SDFBlockDesc> d_plOutDesc[2];  // pass 1 -> pass 2 (device)
+    vh::Mapped<SDFBlockDesc> m_plOutDesc[2];     // pass 2 writes the blocks it moves straight to the host
+    vh::Mapped<vh::SDFBlock> m_plOutBlocks[2];
+    vh::Mapped<uint32_t> m_plOutMirror[2];       // {count, 0, tag}
+    vh::PinnedPtr<SDFBlockDesc> h_plInDesc[2];   // pinned staging of the worker's upload
+    vh::PinnedPtr<vh::SDFBlock> h_plInBlocks[2];
+    vh::DevicePtr<SDFBlockDesc> d_plInDesc[2];
+    vh::DevicePtr<vh::SDFBlock> d_plInBlocks[2];
     uint32_t m_plTag;
     void streamInLaunches();
     unsigned int m_numFailedInserts;
     // the outcome of a stream-in pass (vh_stream_in_device), mapped pinned {failed, 0, tag, exhausted, failed indices ...}: one
     // per pipeline slot, and kSyncInSlot for the passes of streamInLaunches()
     enum { kSyncInSlot = 2 };
-    uint32_t* h_inMirror[3];
-    uint32_t* hd_inMirror[3];
+    vh::Mapped<uint32_t> m_inMirror[3];
 
     unsigned int m_maxNumberOfSDFBlocksIntegrateFromGlobalHash;
 
-    SDFBlockDesc* h_SDFBlockDescOutput; // pinned
-    vh::SDFBlock* h_SDFBlockOutput;     // pinned
-    SDFBlockDesc* h_SDFBlockDescInput;  // pinned staging for the worker's H2D
-    vh::SDFBlock* h_SDFBlockInput;      // pinned
-    uint32_t* h_mirror;                 // mapped pinned: {word 0, word 1, tag} published by the device (vh_publish_words)
-    uint32_t* d_mirror;                 // its device alias
+    vh::PinnedPtr<SDFBlockDesc> h_SDFBlockDescOutput;
+    vh::PinnedPtr<vh::SDFBlock> h_SDFBlockOutput;
+    vh::PinnedPtr<SDFBlockDesc> h_SDFBlockDescInput; // staging for the worker's H2D
+    vh::PinnedPtr<vh::SDFBlock> h_SDFBlockInput;
+    vh::Mapped<uint32_t> m_mirror;      // {word 0, word 1, tag} published by the device (vh_publish_words)
     uint32_t m_mirrorTag;
-    uint32_t* h_probe;                  // mapped pinned: {count, 0, tag} of the stream-out probe
-    uint32_t* d_probe;                  // its device alias
+    vh::Mapped<uint32_t> m_probe;       // {count, 0, tag} of the stream-out probe
     uint32_t m_probeTag;
-    unsigned int* d_probeCounter;
+    vh::DevicePtr<unsigned int> d_probeCounter;
     std::unique_lock<std::mutex> m_streamInLock; // held between streamInWait() and streamInFinish()
     // values of up to two device words once the stream has reached this point, without a blocking driver call
     void readBack(const unsigned int* d_word0, const unsigned int* d_word1, unsigned int* out0, unsigned int* out1);
-    SDFBlockDesc* d_SDFBlockDescOutput;
-    SDFBlockDesc* d_SDFBlockDescInput;
-    vh::SDFBlock* d_SDFBlockOutput;
-    vh::SDFBlock* d_SDFBlockInput;
-    unsigned int* d_SDFBlockCounter;
-    unsigned int* d_insertFailed; // vh_stream_in_device's scratch: {count, {index, SDF block} ...} of the blocks that found no slot
-    unsigned int* d_bitMask;
-    void* m_copyStream; // hipStream_t of the worker thread
+    vh::DevicePtr<SDFBlockDesc> d_SDFBlockDescOutput;
+    vh::DevicePtr<SDFBlockDesc> d_SDFBlockDescInput;
+    vh::DevicePtr<vh::SDFBlock> d_SDFBlockOutput;
+    vh::DevicePtr<vh::SDFBlock> d_SDFBlockInput;
+    vh::DevicePtr<unsigned int> d_SDFBlockCounter;
+    vh::DevicePtr<unsigned int> d_insertFailed; // vh_stream_in_device's scratch: {count, {index, SDF block} ...} of the blocks that found no slot
+    vh::DevicePtr<unsigned int> d_bitMask;
+    vh::Stream m_copyStream; // of the worker thread; declared behind the staging buffers, so it goes before them
     int m_device;       // HIP device the scene lives on (the worker thread binds to it)
 
     vh::vec3f m_voxelExtents;
@@ -556,42 +575,38 @@ private:
     unsigned int m_frameNumber;
     // frames on the host: a ring of staging slots fed by a copy stream
     enum { kStagingSlots = 4 };
-    void* m_copyStream;
-    float* d_stageDepth[kStagingSlots];
-    unsigned char* d_stageColorRaw[kStagingSlots];
-    float* d_stageColor[kStagingSlots];
-    void* m_copyStream2;                          // the depth copy runs on a stream (a copy engine) of its own
-    void* m_slotReady[kStagingSlots];             // copy stream -> main stream
-    void* m_slotReady2[kStagingSlots];
+    // (the destructor's body waits for all three streams before any member below goes)
+    vh::Stream m_copyStream;
+    vh::Stream m_copyStream2;                     // the depth copy runs on a stream (a copy engine) of its own
+    vh::DevicePtr<float> d_stageDepth[kStagingSlots];
+    vh::DevicePtr<unsigned char> d_stageColorRaw[kStagingSlots];
+    vh::DevicePtr<float> d_stageColor[kStagingSlots];
+    vh::Event m_slotReady[kStagingSlots];         // copy stream -> main stream
+    vh::Event m_slotReady2[kStagingSlots];
     unsigned int m_slotSceneFrame[kStagingSlots]; // the scene's frame count when the slot's frame was enqueued, + 1 (0: never used)
     unsigned int m_uploads;                       // frames uploaded so far (the slot is m_uploads % kStagingSlots)
-    std::vector<std::pair<void*, void*>> m_uploadTimers; // event pairs on the copy stream, not yet read
-    std::vector<void*> m_timerPool;
+    std::vector<std::pair<vh::Event, vh::Event>> m_uploadTimers; // event pairs on the copy stream, not yet read
+    std::vector<vh::Event> m_timerPool;
     // raw frames: the sensor's images of a slot (host-fed), and the maps the filters read (one pair: the copy stream runs
     // one frame at a time)
     bool m_raw, m_rawRun;
     RawFrameFormat m_rawFormat;
-    unsigned short* d_rawDepth[kStagingSlots];
-    float* d_unfilteredDepth;
-    float* d_unfilteredColor;
+    vh::DevicePtr<unsigned short> d_rawDepth[kStagingSlots];
+    vh::DevicePtr<float> d_unfilteredDepth;
+    vh::DevicePtr<float> d_unfilteredColor;
     std::vector<SequenceFrame> m_rawFrames;
     // the streaming step in the reference's order of calls (:881-900) around p -> the bit mask for alloc
     const unsigned int* streamAround(const vh::vec3f& p);
     std::vector<float> m_poses;
-    // tracking: the input's camera-space positions, normals and coarser levels per staging slot (they depend on the frame
-    // alone: made on the copy stream behind the ingest), the model's coarser levels, the solve's device state
+    // tracking: the solve (m_icp->estimate holds the identity), and what is the loop's own: the input's camera-space
+    // positions, normals and coarser levels per staging slot (they depend on the frame alone: made on the copy stream
+    // behind the ingest), the solve's outcome in mapped host memory and the tag the host waits for
     bool m_tracking;
     unsigned long long m_trackedFrames, m_lostFrames;
     VhTrackingState m_trackingState;
-    std::vector<unsigned int> m_levelWidth, m_levelHeight;
-    std::vector<float*> d_trkInput[kStagingSlots], d_trkInputNormal[kStagingSlots];
-    std::vector<float*> d_trkModel, d_trkModelNormal, d_trkCorr, d_trkCorrNormal; // level 0 of the model: the ray caster's maps
-    float* d_trkPartials;
-    VhIcpState* d_trkState;
-    float* d_trkIdentity;
-    uint32_t* d_trkTicket;
-    VhIcpResult* h_trkResult; // mapped host memory
-    VhIcpResult* d_trkResult; // its device alias
+    std::unique_ptr<vh::IcpSolver> m_icp;
+    std::vector<vh::DevicePtr<float>> d_trkInput[kStagingSlots], d_trkInputNormal[kStagingSlots];
+    vh::Mapped<VhIcpResult> m_trkResult;
     uint32_t m_trkTag;
     void inputPyramid(unsigned int slot, const float* d_depth, vhStream_t stream);
     void frameTracked(const SequenceFrame& f);
@@ -655,7 +670,9 @@ public:
 
 private:
     MarchingCubesParams m_params;
-    MarchingCubesData m_data;
+    MarchingCubesData m_data; // filled by the C ABI's allocator (vh_marching_cubes_data_alloc); m_dataOwner gives it back
+    struct DataFree { void operator()(MarchingCubesData* d) const noexcept; };
+    std::unique_ptr<MarchingCubesData, DataFree> m_dataOwner;
     vh::MeshData m_meshData;
     vhStream_t m_stream;
     bool m_offline;
@@ -760,11 +777,11 @@ public:
 
     const DepthCameraData& getDepthCameraData() const { return m_depthCameraData; }       // .h:78
     const DepthCameraParams& getDepthCameraParams() const { return m_depthCameraParams; } // .h:82
-    float* getCameraSpacePositionsFloat4() { return d_cameraSpaceFloat4; }                // .h:50
-    float* getNormalMapFloat4() { return d_normalMapFloat4; }                             // .h:53
-    float* getDepthMapColorSpaceFloat() { return d_depthData; }                           // .h:44
-    float* getColorMapFilteredFloat4() { return d_colorData; }                            // .h:47
-    float* getIntensityMapFilteredFloat() { return d_intensityMapFilteredFloat; }
+    float* getCameraSpacePositionsFloat4() { return d_cameraSpaceFloat4.get(); }          // .h:50
+    float* getNormalMapFloat4() { return d_normalMapFloat4.get(); }                       // .h:53
+    float* getDepthMapColorSpaceFloat() { return d_depthData.get(); }                     // .h:44
+    float* getColorMapFilteredFloat4() { return d_colorData.get(); }                      // .h:47
+    float* getIntensityMapFilteredFloat() { return d_intensityMapFilteredFloat.get(); }
     unsigned int getDepthWidth() const { return m_cfg.adapterWidth; }
     unsigned int getDepthHeight() const { return m_cfg.adapterHeight; }
     unsigned int getFrameNumber() const { return m_frameNumber; }
@@ -777,14 +794,14 @@ private:
     float m_fBilateralFilterSigmaD, m_fBilateralFilterSigmaR, m_fBilateralFilterSigmaDIntensity, m_fBilateralFilterSigmaRIntensity;
     DepthCameraParams m_depthCameraParams;
     DepthCameraData m_depthCameraData;
-    float *d_depthMapFloat, *d_depthMapResampledFloat, *d_depthMapFilteredFloat, *d_intensityMapFilteredFloat;
-    unsigned char* d_colorMapRaw;
-    float *d_colorMapFloat4, *d_colorMapResampledFloat4, *d_cameraSpaceFloat4, *d_normalMapFloat4;
-    float *d_depthData, *d_colorData; // what m_depthCameraData points to
+    vh::DevicePtr<float> d_depthMapFloat, d_depthMapResampledFloat, d_depthMapFilteredFloat, d_intensityMapFilteredFloat;
+    vh::DevicePtr<unsigned char> d_colorMapRaw;
+    vh::DevicePtr<float> d_colorMapFloat4, d_colorMapResampledFloat4, d_cameraSpaceFloat4, d_normalMapFloat4;
+    vh::DevicePtr<float> d_depthData, d_colorData; // what m_depthCameraData points to
     bool m_bUseCameraCalibration = false;
-    VhViewParams m_remapParams;          // the RenderDepthMap arguments of the remap
-    uint64_t* d_remapKeys = nullptr;     // adapter-size key buffer, all ones between frames
-    uint32_t* d_remapLargeList = nullptr; // vh_view_large_list_words(adapter size), counter 0 between frames
+    VhViewParams m_remapParams;               // the RenderDepthMap arguments of the remap
+    vh::DevicePtr<uint64_t> d_remapKeys;      // adapter-size key buffer, all ones between frames
+    vh::DevicePtr<uint32_t> d_remapLargeList; // vh_view_large_list_words(adapter size), counter 0 between frames
 };
 
 
@@ -809,11 +826,8 @@ public:
 private:
     unsigned int m_levels;
     vhStream_t m_stream;
-    std::vector<unsigned int> m_imageWidth, m_imageHeight;
-    std::vector<float*> d_correspondence, d_correspondenceNormal, d_input, d_inputNormal, d_model, d_modelNormal;
-    float* d_partials;
-    VhIcpState* d_state;
-    float* d_deltaEstimate;
+    vh::IcpSolver m_icp;
+    std::vector<vh::DevicePtr<float>> d_input, d_inputNormal; // levels >= 1: the finest level is the caller's maps
     VhIcpState m_lastState;
 };
 
@@ -842,11 +856,11 @@ private:
     unsigned int m_levels;
     vhStream_t m_stream;
     std::vector<unsigned int> m_imageWidth, m_imageHeight;
-    std::vector<float*> d_input, d_inputNormal, d_inputIntensity, d_inputIntensityFiltered;
-    std::vector<float*> d_model, d_modelNormal, d_modelIntensity, d_modelIntensityFiltered, d_modelIntensityAndDerivatives;
-    float* d_partials;
-    VhIcpStateRGBD* d_state;
-    float* d_deltaEstimate;
+    std::vector<vh::DevicePtr<float>> d_input, d_inputNormal, d_inputIntensity, d_inputIntensityFiltered; // (levels >= 1 of the first two)
+    std::vector<vh::DevicePtr<float>> d_model, d_modelNormal, d_modelIntensity, d_modelIntensityFiltered, d_modelIntensityAndDerivatives;
+    vh::DevicePtr<float> d_partials;
+    vh::DevicePtr<VhIcpStateRGBD> d_state;
+    vh::DevicePtr<float> d_deltaEstimate;
     VhIcpStateRGBD m_lastState;
 };
 
@@ -865,10 +879,10 @@ public:
     void RenderDepthMap(const float* d_depthMap, const float* d_colorMap, unsigned int width, unsigned int height, const vh::mat4f& intrinsicDepthToWorld,
                         const vh::mat4f& modelview, const vh::mat4f& intrinsicWorldToDepth, unsigned int screenWidth, unsigned int screenHeight,
                         float depthThreshOffset, float depthThreshLin);
-    float* getDepth() const { return d_depth; }
-    float* getPositions() const { return d_positions; }
-    float* getNormals() const { return d_normals; }
-    float* getColors() const { return d_colors; }
+    float* getDepth() const { return d_depth.get(); }
+    float* getPositions() const { return d_positions.get(); }
+    float* getNormals() const { return d_normals.get(); }
+    float* getColors() const { return d_colors.get(); }
     unsigned int getWidth() const { return m_screenWidth; }
     unsigned int getHeight() const { return m_screenHeight; }
 
@@ -876,9 +890,9 @@ private:
     void resize(unsigned int width, unsigned int height, unsigned int screenWidth, unsigned int screenHeight);
     vhStream_t m_stream;
     unsigned int m_width = 0, m_height = 0, m_screenWidth = 0, m_screenHeight = 0;
-    uint64_t* d_keys = nullptr;
-    uint32_t* d_largeList = nullptr;
-    float *d_depth = nullptr, *d_positions = nullptr, *d_normals = nullptr, *d_colors = nullptr;
+    vh::DevicePtr<uint64_t> d_keys;
+    vh::DevicePtr<uint32_t> d_largeList;
+    vh::DevicePtr<float> d_depth, d_positions, d_normals, d_colors;
 };
 
 // DX11PhongLighting (DSC/DX11PhongLighting.h): PhongPS over three float4 maps into a float4 target, and on request its
@@ -895,15 +909,15 @@ public:
                 bool rgba8 = false);
     void setLight(const VhPhongLight& light) { m_light = light; }
     const VhPhongLight& getLight() const { return m_light; }
-    float* getColors() const { return d_colors; }
-    uint8_t* getColorsRGBA8() const { return d_rgba8; }
+    float* getColors() const { return d_colors.get(); }
+    uint8_t* getColorsRGBA8() const { return d_rgba8.get(); }
 
 private:
     VhPhongLight m_light;
     vhStream_t m_stream;
     unsigned int m_numPixels = 0;
-    float* d_colors = nullptr;
-    uint8_t* d_rgba8 = nullptr;
+    vh::DevicePtr<float> d_colors;
+    vh::DevicePtr<uint8_t> d_rgba8;
 };
 
 #endif // VH_HPP

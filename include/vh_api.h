@@ -42,8 +42,7 @@ const char* vh_last_error_message(void);
 /* ---- device memory helpers (thin hipMalloc/hipMemcpy wrappers for FFI users) */
 int vh_malloc(void** devPtr, size_t bytes);
 int vh_free(void* devPtr);
-/* pinned, device-visible host memory (hipHostMalloc): what vh_upload_frame and the frame loop's host-fed mode read
- * straight over the link */
+/* pinned, device-visible host memory (hipHostMalloc): what the frame loop's host-fed mode reads straight over the link */
 int vh_malloc_host(void** hostPtr, size_t bytes);
 int vh_free_host(void* hostPtr);
 int vh_memcpy_h2d(void* dst, const void* src, size_t bytes, vhStream_t stream);
@@ -407,10 +406,6 @@ int vh_reconstruction_reset(VhReconstruction* r);
  * Device pointers; float4 maps are passed as float* (4 per pixel); MINF marks an invalid pixel.  The filters read
  * their whole neighbourhood, so they do not work in place. */
 int vh_convert_color_raw_to_float4(float* d_output4, const uint8_t* d_inputRGBX, uint32_t width, uint32_t height, vhStream_t stream); /* :154 */
-/* not in the reference: a sensor frame read by a kernel straight from pinned, device-visible host memory (the pointers
- * as hipHostGetDevicePointer returns them): depth copied, RGBX colour converted to float4 on the way.  width*height
- * must be a multiple of 4.  hostRGBX / d_color4 may be NULL. */
-int vh_upload_frame(const float* hostDepth, const uint8_t* hostRGBX, float* d_depth, float* d_color4, uint32_t width, uint32_t height, vhStream_t stream);
 /* not in the reference: a raw sensor frame in device memory (16-bit depth in units of 1/depthShift m; colorChannels = 3: RGB,
  * 4: RGBX, 0: no colour, then d_color4 / d_colorRaw may be NULL) to float depth + float4 colour at width x height in one
  * pass: SensorDataReader::processDepth's conversion, vh_convert_color_raw_to_float4, vh_resample_float_map and

@@ -95,6 +95,72 @@ def test_cpp_host_header_compiles_standalone():
         subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), src])
 
 
+OWNERS_PROGRAM = r"""
+#include "vh.hpp"
+#include <cstdio>
+// counting deleters in place of the library's: the program does not link it
+static int g_device = 0, g_pinned = 0, g_event = 0, g_stream = 0;
+void vh::DeviceFree::operator()(void*) const noexcept { g_device++; }
+void vh::PinnedFree::operator()(void*) const noexcept { g_pinned++; }
+void vh::EventDestroy::operator()(void*) const noexcept { g_event++; }
+void vh::StreamDestroy::operator()(void*) const noexcept { g_stream++; }
+static int g_made = 0;
+void* vh::pinnedAllocBytes(size_t, bool, const char*) { static char host[64]; g_made++; return host; }
+void* vh::deviceAlias(void* host, const char*) { return (char*)host + 1; }
+#define EXPECT(cond) do { if (!(cond)) { std::printf("line %d: %s\n", __LINE__, #cond); return 1; } } while (0)
+template <class Owner, class T> static int rules(int& count, T* a, T* b)
+{
+    count = 0;
+    { Owner o(a); }
+    EXPECT(count == 1);                       // once on scope exit
+    { Owner o(a); EXPECT(o.release() == a); }
+    EXPECT(count == 1);                       // not at all after release()
+    { Owner o(a); o = Owner(b); EXPECT(count == 2 && o.get() == b); }
+    EXPECT(count == 3);                       // once for the old value on assignment, once for the new one at the end
+    { Owner o(a); Owner p(std::move(o)); EXPECT(!o && p.get() == a); }
+    EXPECT(count == 4);                       // a moved-from owner frees nothing
+    { Owner o; }
+    EXPECT(count == 4);                       // nor does an empty one
+    return 0;
+}
+int main()
+{
+    float f[2];
+    uint32_t w[2];
+    int x[2];
+    if (rules<vh::DevicePtr<float>>(g_device, &f[0], &f[1])) return 1;
+    if (rules<vh::PinnedPtr<uint32_t>>(g_pinned, &w[0], &w[1])) return 1;
+    if (rules<vh::Event>(g_event, (void*)&x[0], (void*)&x[1])) return 1;
+    if (rules<vh::Stream>(g_stream, (void*)&x[0], (void*)&x[1])) return 1;
+    g_pinned = 0;
+    {
+        vh::Mapped<uint32_t> m(4, "mapped");  // the host pointer and its device alias travel together
+        EXPECT(m.host() && (char*)m.device() == (char*)m.host() + 1);
+        vh::Mapped<uint32_t> n(std::move(m));
+        EXPECT(!m.host() && !m.device() && n.host() && n.device());
+        n = vh::Mapped<uint32_t>(4, "mapped");
+        EXPECT(g_pinned == 1 && g_made == 2);
+        vh::Mapped<uint32_t> empty;
+        EXPECT(!empty.host() && !empty.device());
+    }
+    EXPECT(g_pinned == 2);
+    std::printf("ok\n");
+    return 0;
+}
+"""
+
+
+def test_owners_free_exactly_once():
+    """the owning types of include/vh_owners.hpp (device and pinned memory, events, streams, mapped words): freed once on
+    scope exit, not after release(), once for the old value on assignment, never by a moved-from or empty owner"""
+    with tempfile.TemporaryDirectory() as d:
+        src, exe = os.path.join(d, "t.cpp"), os.path.join(d, "t")
+        open(src, "w").write(OWNERS_PROGRAM)
+        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
+        res = subprocess.run([exe], stdout=subprocess.PIPE)
+        assert res.returncode == 0 and res.stdout.decode().strip() == "ok", res.stdout.decode()
+
+
 def test_product_package_never_touches_the_oracle():
     pkg = os.path.join(ROOT, "voxelhashing_amd")
     bad = []

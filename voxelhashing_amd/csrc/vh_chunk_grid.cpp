@@ -26,14 +26,6 @@
 
 namespace {
 
-inline void check(int code, const char* what)
-{
-    if (code != 0) throw vh::Error(code, std::string(what) + ": " + vh_error_string(code));
-}
-inline void checkHip(hipError_t e, const char* what)
-{
-    if (e != hipSuccess) throw vh::Error(-(int)e, std::string(what) + ": " + hipGetErrorString(e));
-}
 inline int signi(float v) { return (0.0f < v) - (v < 0.0f); }
 inline float length3(float x, float y, float z) { return std::sqrt(x * x + y * y + z * z); }
 
@@ -85,13 +77,7 @@ CUDASceneRepChunkGrid::CUDASceneRepChunkGrid(CUDASceneRepHashSDF* sceneRepHashSD
     m_numFailedInserts = 0;
     m_streamOutParts = streamOutParts ? streamOutParts : 1;
     m_maxNumberOfSDFBlocksIntegrateFromGlobalHash = 100000; // DSC/CUDASceneRepChunkGrid.h:162
-    h_SDFBlockDescOutput = nullptr; h_SDFBlockOutput = nullptr;
-    h_SDFBlockDescInput = nullptr; h_SDFBlockInput = nullptr;
-    h_mirror = nullptr; d_mirror = nullptr; m_mirrorTag = 0;
-    h_probe = nullptr; d_probe = nullptr; m_probeTag = 0; d_probeCounter = nullptr;
-    d_SDFBlockDescOutput = nullptr; d_SDFBlockDescInput = nullptr;
-    d_SDFBlockOutput = nullptr; d_SDFBlockInput = nullptr;
-    d_SDFBlockCounter = nullptr; d_insertFailed = nullptr; d_bitMask = nullptr; m_copyStream = nullptr;
+    m_mirrorTag = 0; m_probeTag = 0;
     s_terminateThread = true; // by default the thread is disabled
     s_nStreamdInBlocks = 0; s_nStreamdOutBlocks = 0;
     s_posCamera = { 0.0f, 0.0f, 0.0f };
@@ -105,17 +91,10 @@ CUDASceneRepChunkGrid::CUDASceneRepChunkGrid(CUDASceneRepHashSDF* sceneRepHashSD
     m_plDecisionRadius = 0.0f;
     m_plFrame = 0; m_plOutThisFrame = false; m_plOutTag = 0; m_plOutMost = 0;
     for (int i = 0; i < 2; i++) { m_plInsert[i].pending = false; m_plInsert[i].tag = 0; m_plInsert[i].nIn = 0; }
-    for (int i = 0; i < 3; i++) { h_inMirror[i] = nullptr; hd_inMirror[i] = nullptr; }
     m_plBlocksOut = 0; m_plBlocksIn = 0; m_plTag = 0;
-    for (int i = 0; i < 2; i++) {
-        d_plOutDesc[i] = nullptr; h_plOutDesc[i] = nullptr; h_plOutBlocks[i] = nullptr; hd_plOutDesc[i] = nullptr; hd_plOutBlocks[i] = nullptr;
-        h_plOutMirror[i] = nullptr; hd_plOutMirror[i] = nullptr;
-        h_plInDesc[i] = nullptr; h_plInBlocks[i] = nullptr; d_plInDesc[i] = nullptr; d_plInBlocks[i] = nullptr;
-    }
     create(voxelExtends, gridDimensions, minGridPos, initialChunkListSize, streamingEnabled);
 }
 
-CUDASceneRepChunkGrid::~CUDASceneRepChunkGrid() { destroy(); }
 
 // DSC/CUDASceneRepChunkGrid.h:366-393
 void CUDASceneRepChunkGrid::create(const vh::vec3f& voxelExtends, const vh::vec3i& gridDimensions, const vh::vec3i& minGridPos,
@@ -131,54 +110,45 @@ void CUDASceneRepChunkGrid::create(const vh::vec3f& voxelExtends, const vh::vec3
     m_bitMask.assign((nBits + 31) / 32, 0u);
 
     const size_t n = m_maxNumberOfSDFBlocksIntegrateFromGlobalHash;
-    checkHip(hipHostMalloc((void**)&h_SDFBlockDescOutput, sizeof(SDFBlockDesc) * n, hipHostMallocDefault), "hipHostMalloc");
-    checkHip(hipHostMalloc((void**)&h_SDFBlockOutput, sizeof(vh::SDFBlock) * n, hipHostMallocDefault), "hipHostMalloc");
-    checkHip(hipHostMalloc((void**)&h_SDFBlockDescInput, sizeof(SDFBlockDesc) * n, hipHostMallocDefault), "hipHostMalloc");
-    checkHip(hipHostMalloc((void**)&h_SDFBlockInput, sizeof(vh::SDFBlock) * n, hipHostMallocDefault), "hipHostMalloc");
-    checkHip(hipHostMalloc((void**)&h_mirror, sizeof(uint32_t) * 4, hipHostMallocMapped), "hipHostMalloc");
-    h_mirror[0] = h_mirror[1] = h_mirror[2] = h_mirror[3] = 0u;
-    checkHip(hipHostGetDevicePointer((void**)&d_mirror, h_mirror, 0), "hipHostGetDevicePointer");
-    checkHip(hipHostMalloc((void**)&h_probe, sizeof(uint32_t) * 4, hipHostMallocMapped), "hipHostMalloc");
-    h_probe[0] = h_probe[1] = h_probe[2] = h_probe[3] = 0u;
-    checkHip(hipHostGetDevicePointer((void**)&d_probe, h_probe, 0), "hipHostGetDevicePointer");
-    checkHip(hipMalloc((void**)&d_probeCounter, sizeof(unsigned int)), "hipMalloc");
-    checkHip(hipMemset(d_probeCounter, 0, sizeof(unsigned int)), "hipMemset");
-    checkHip(hipMalloc((void**)&d_SDFBlockDescOutput, sizeof(SDFBlockDesc) * n), "hipMalloc");
-    checkHip(hipMalloc((void**)&d_SDFBlockDescInput, sizeof(SDFBlockDesc) * n), "hipMalloc");
-    checkHip(hipMalloc((void**)&d_SDFBlockOutput, sizeof(vh::SDFBlock) * n), "hipMalloc");
-    checkHip(hipMalloc((void**)&d_SDFBlockInput, sizeof(vh::SDFBlock) * n), "hipMalloc");
-    checkHip(hipMalloc((void**)&d_SDFBlockCounter, sizeof(unsigned int)), "hipMalloc");
-    checkHip(hipMalloc((void**)&d_insertFailed, sizeof(unsigned int) * (1 + 2 * n)), "hipMalloc");
-    checkHip(hipMemset(d_insertFailed, 0, sizeof(unsigned int)), "hipMemset");
+    h_SDFBlockDescOutput = vh::pinnedAlloc<SDFBlockDesc>(n, "hipHostMalloc");
+    h_SDFBlockOutput = vh::pinnedAlloc<vh::SDFBlock>(n, "hipHostMalloc");
+    h_SDFBlockDescInput = vh::pinnedAlloc<SDFBlockDesc>(n, "hipHostMalloc");
+    h_SDFBlockInput = vh::pinnedAlloc<vh::SDFBlock>(n, "hipHostMalloc");
+    m_mirror = vh::Mapped<uint32_t>(4, "hipHostMalloc");
+    std::memset(m_mirror.host(), 0, sizeof(uint32_t) * 4);
+    m_probe = vh::Mapped<uint32_t>(4, "hipHostMalloc");
+    std::memset(m_probe.host(), 0, sizeof(uint32_t) * 4);
+    d_probeCounter = vh::deviceAlloc<unsigned int>(1, "hipMalloc");
+    checkHip(hipMemset(d_probeCounter.get(), 0, sizeof(unsigned int)), "hipMemset");
+    d_SDFBlockDescOutput = vh::deviceAlloc<SDFBlockDesc>(n, "hipMalloc");
+    d_SDFBlockDescInput = vh::deviceAlloc<SDFBlockDesc>(n, "hipMalloc");
+    d_SDFBlockOutput = vh::deviceAlloc<vh::SDFBlock>(n, "hipMalloc");
+    d_SDFBlockInput = vh::deviceAlloc<vh::SDFBlock>(n, "hipMalloc");
+    d_SDFBlockCounter = vh::deviceAlloc<unsigned int>(1, "hipMalloc");
+    d_insertFailed = vh::deviceAlloc<unsigned int>(1 + 2 * n, "hipMalloc");
+    checkHip(hipMemset(d_insertFailed.get(), 0, sizeof(unsigned int)), "hipMemset");
     for (int i = 0; i < 3; i++) {
         const size_t words = 4 + (i == kSyncInSlot ? n : (size_t)kPipelineBlocks);
-        checkHip(hipHostMalloc((void**)&h_inMirror[i], sizeof(uint32_t) * words, hipHostMallocMapped), "hipHostMalloc");
-        std::memset(h_inMirror[i], 0, sizeof(uint32_t) * words);
-        checkHip(hipHostGetDevicePointer((void**)&hd_inMirror[i], h_inMirror[i], 0), "hipHostGetDevicePointer");
+        m_inMirror[i] = vh::Mapped<uint32_t>(words, "hipHostMalloc");
+        std::memset(m_inMirror[i].host(), 0, sizeof(uint32_t) * words);
     }
-    checkHip(hipMalloc((void**)&d_bitMask, sizeof(unsigned int) * m_bitMask.size()), "hipMalloc");
+    d_bitMask = vh::deviceAlloc<unsigned int>(m_bitMask.size(), "hipMalloc");
     checkHip(hipGetDevice(&m_device), "hipGetDevice"); // one instance is bound to one device
-    hipStream_t cs;
-    checkHip(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking), "hipStreamCreate");
-    m_copyStream = cs;
+    m_copyStream = vh::makeStream("hipStreamCreate");
 
     if (streamingEnabled) startMultiThreading();
 }
 
-void CUDASceneRepChunkGrid::destroy()
+// Both workers are stopped and both streams are idle before the members go: the staging buffers they use, then the copy
+// stream (the members' reverse order of declaration).
+CUDASceneRepChunkGrid::~CUDASceneRepChunkGrid()
 {
     try { pipelineDrain(); } catch (...) {}
     pipelineStop();
     stopMultiThreading();
     clearGrid();
     if (m_sceneRepHashSDF) (void)hipStreamSynchronize((hipStream_t)m_sceneRepHashSDF->getStream());
-    if (m_copyStream) { (void)hipStreamSynchronize((hipStream_t)m_copyStream); (void)hipStreamDestroy((hipStream_t)m_copyStream); }
-    (void)hipHostFree(h_SDFBlockDescOutput); (void)hipHostFree(h_SDFBlockOutput);
-    (void)hipHostFree(h_SDFBlockDescInput); (void)hipHostFree(h_SDFBlockInput); (void)hipHostFree(h_mirror); (void)hipHostFree(h_probe); (void)hipFree(d_probeCounter);
-    (void)hipFree(d_SDFBlockDescOutput); (void)hipFree(d_SDFBlockDescInput);
-    (void)hipFree(d_SDFBlockOutput); (void)hipFree(d_SDFBlockInput);
-    (void)hipFree(d_SDFBlockCounter); (void)hipFree(d_insertFailed); (void)hipFree(d_bitMask);
-    for (int i = 0; i < 3; i++) (void)hipHostFree(h_inMirror[i]);
+    if (m_copyStream) (void)hipStreamSynchronize((hipStream_t)m_copyStream.get());
 }
 
 // ---------------------------------------------------------------------------
@@ -358,10 +328,10 @@ unsigned int* CUDASceneRepChunkGrid::getBitMaskGPU()
     if (m_bitMaskDirty) {
         hipStream_t s = (hipStream_t)m_sceneRepHashSDF->getStream();
         // pageable source: the copy is staged before the call returns, so the lock can be dropped afterwards
-        checkHip(hipMemcpyAsync(d_bitMask, m_bitMask.data(), sizeof(unsigned int) * m_bitMask.size(), hipMemcpyHostToDevice, s), "getBitMaskGPU");
+        checkHip(hipMemcpyAsync(d_bitMask.get(), m_bitMask.data(), sizeof(unsigned int) * m_bitMask.size(), hipMemcpyHostToDevice, s), "getBitMaskGPU");
         m_bitMaskDirty = false;
     }
-    return d_bitMask;
+    return d_bitMask.get();
 }
 
 void CUDASceneRepChunkGrid::getStatistics(unsigned int out[3]) const
@@ -427,8 +397,8 @@ void CUDASceneRepChunkGrid::readBack(const unsigned int* d_word0, const unsigned
 {
     vhStream_t stream = m_sceneRepHashSDF->getStream();
     const uint32_t tag = ++m_mirrorTag ? m_mirrorTag : ++m_mirrorTag; // never 0
-    check(vh_publish_words(d_word0, d_word1, d_mirror, tag, stream), "vh_publish_words");
-    volatile uint32_t* m = h_mirror;
+    check(vh_publish_words(d_word0, d_word1, m_mirror.device(), tag, stream), "vh_publish_words");
+    volatile uint32_t* m = m_mirror.host();
     const auto t0 = std::chrono::steady_clock::now();
     unsigned int spins = 0;
     while (m[2] != tag) {
@@ -462,7 +432,7 @@ void CUDASceneRepChunkGrid::streamOutToCPUPass0GPU(const vh::vec3f& posCamera, f
     vhStream_t stream = m_sceneRepHashSDF->getStream();
     const int32_t token = m_sceneRepHashSDF->nextLockToken(); // = resetHashBucketMutexCUDA
     m_sceneRepHashSDF->noteTableEdited();
-    check(vh_memset(d_SDFBlockCounter, 0, sizeof(unsigned int), stream), "clearSDFBlockCounter");
+    check(vh_memset(d_SDFBlockCounter.get(), 0, sizeof(unsigned int), stream), "clearSDFBlockCounter");
 
     const unsigned int numEntries = hp.m_hashNumBuckets * hp.m_hashBucketSize;
     unsigned int threadsPerPart = (numEntries + m_streamOutParts - 1) / m_streamOutParts;
@@ -470,10 +440,10 @@ void CUDASceneRepChunkGrid::streamOutToCPUPass0GPU(const vh::vec3f& posCamera, f
     const unsigned int start = useParts ? m_currentPart * threadsPerPart : 0;
 
     const float cam[3] = { posCamera.x, posCamera.y, posCamera.z };
-    check(vh_stream_out_pass1(&hd, &hp, threadsPerPart, start, radius, cam, d_SDFBlockCounter, d_SDFBlockDescOutput,
+    check(vh_stream_out_pass1(&hd, &hp, threadsPerPart, start, radius, cam, d_SDFBlockCounter.get(), d_SDFBlockDescOutput.get(),
                               m_maxNumberOfSDFBlocksIntegrateFromGlobalHash, token, stream), "integrateFromGlobalHashPass1CUDA");
     unsigned int nSDFBlockDescs = 0;
-    readBack(d_SDFBlockCounter, nullptr, &nSDFBlockDescs, nullptr);
+    readBack(d_SDFBlockCounter.get(), nullptr, &nSDFBlockDescs, nullptr);
     if (nSDFBlockDescs >= m_maxNumberOfSDFBlocksIntegrateFromGlobalHash) {
         if (multiThreaded) hEventOutProduce.set();
         throw vh::Error(VH_ERR_STAGING_OVERFLOW,
@@ -482,10 +452,10 @@ void CUDASceneRepChunkGrid::streamOutToCPUPass0GPU(const vh::vec3f& posCamera, f
     if (useParts) m_currentPart = (m_currentPart + 1) % m_streamOutParts;
 
     if (nSDFBlockDescs != 0) {
-        check(vh_stream_out_pass2(&hd, &hp, d_SDFBlockDescOutput, (VhVoxel*)d_SDFBlockOutput, nSDFBlockDescs, stream), "integrateFromGlobalHashPass2CUDA");
+        check(vh_stream_out_pass2(&hd, &hp, d_SDFBlockDescOutput.get(), (VhVoxel*)d_SDFBlockOutput.get(), nSDFBlockDescs, stream), "integrateFromGlobalHashPass2CUDA");
         hipStream_t s = (hipStream_t)stream;
-        checkHip(hipMemcpyAsync(h_SDFBlockDescOutput, d_SDFBlockDescOutput, sizeof(SDFBlockDesc) * nSDFBlockDescs, hipMemcpyDeviceToHost, s), "D2H descs");
-        checkHip(hipMemcpyAsync(h_SDFBlockOutput, d_SDFBlockOutput, sizeof(vh::SDFBlock) * nSDFBlockDescs, hipMemcpyDeviceToHost, s), "D2H blocks");
+        checkHip(hipMemcpyAsync(h_SDFBlockDescOutput.get(), d_SDFBlockDescOutput.get(), sizeof(SDFBlockDesc) * nSDFBlockDescs, hipMemcpyDeviceToHost, s), "D2H descs");
+        checkHip(hipMemcpyAsync(h_SDFBlockOutput.get(), d_SDFBlockOutput.get(), sizeof(vh::SDFBlock) * nSDFBlockDescs, hipMemcpyDeviceToHost, s), "D2H blocks");
         checkHip(hipStreamSynchronize(s), "hipStreamSynchronize");
     }
     s_nStreamdOutBlocks = nSDFBlockDescs;
@@ -505,13 +475,13 @@ void CUDASceneRepChunkGrid::probeStreamOut(const vh::vec3f& posCamera, float rad
     const unsigned int start = useParts ? m_currentPart * threadsPerPart : 0; // the part the NEXT pass 0 scans
     const float cam[3] = { posCamera.x, posCamera.y, posCamera.z };
     m_probeTag = ++m_probeTag ? m_probeTag : 1u;
-    check(vh_stream_out_probe(&hd, &hp, threadsPerPart, start, radius, cam, d_probeCounter, d_probe, m_probeTag, m_sceneRepHashSDF->getStream()),
+    check(vh_stream_out_probe(&hd, &hp, threadsPerPart, start, radius, cam, d_probeCounter.get(), m_probe.device(), m_probeTag, m_sceneRepHashSDF->getStream()),
           "vh_stream_out_probe");
 }
 
 unsigned int CUDASceneRepChunkGrid::probeResult()
 {
-    volatile uint32_t* m = h_probe;
+    volatile uint32_t* m = m_probe.host();
     const auto t0 = std::chrono::steady_clock::now();
     unsigned int spins = 0;
     while (m[2] != m_probeTag) {
@@ -570,7 +540,7 @@ void CUDASceneRepChunkGrid::streamInAbort()
     if (!m_streamInLock.owns_lock()) return;
     try {
         // what the worker took out of the grid for this pass is still in its staging buffers (integrateInHash)
-        if (s_nStreamdInBlocks != 0) integrateInChunkGrid(h_SDFBlockDescInput, h_SDFBlockInput, s_nStreamdInBlocks);
+        if (s_nStreamdInBlocks != 0) integrateInChunkGrid(h_SDFBlockDescInput.get(), h_SDFBlockInput.get(), s_nStreamdInBlocks);
     } catch (...) {
     }
     s_nStreamdInBlocks = 0;
@@ -587,7 +557,7 @@ void CUDASceneRepChunkGrid::streamOutToCPUPass1CPU(bool multiThreaded)
         lock.lock();
         if (s_terminateThread) return; // avoid duplicate insertions when stop multi-threading is called
     }
-    if (s_nStreamdOutBlocks != 0) integrateInChunkGrid(h_SDFBlockDescOutput, h_SDFBlockOutput, s_nStreamdOutBlocks);
+    if (s_nStreamdOutBlocks != 0) integrateInChunkGrid(h_SDFBlockDescOutput.get(), h_SDFBlockOutput.get(), s_nStreamdOutBlocks);
     if (multiThreaded) hEventOutProduce.set();
 }
 
@@ -710,12 +680,12 @@ void CUDASceneRepChunkGrid::streamInLaunches()
     m_sceneRepHashSDF->noteTableEdited();
     const uint32_t tag = ++m_plTag ? m_plTag : ++m_plTag;
     // (no chunk bit: the host's copy of the bit mask is the one that counts here)
-    check(vh_stream_in_device(&hd, &hp, s_nStreamdInBlocks, d_SDFBlockDescInput, (const VhVoxel*)d_SDFBlockInput, token, d_insertFailed, nullptr,
-                              0xffffffffu, hd_inMirror[kSyncInSlot], tag, stream), "chunkToGlobalHashPass1CUDA + Pass2CUDA");
+    check(vh_stream_in_device(&hd, &hp, s_nStreamdInBlocks, d_SDFBlockDescInput.get(), (const VhVoxel*)d_SDFBlockInput.get(), token, d_insertFailed.get(), nullptr,
+                              0xffffffffu, m_inMirror[kSyncInSlot].device(), tag, stream), "chunkToGlobalHashPass1CUDA + Pass2CUDA");
     checkHip(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
-    if (((volatile uint32_t*)h_inMirror[kSyncInSlot])[2] != tag) throw vh::Error(-(int)hipErrorUnknown, "stream-in: the device did not publish its pass");
+    if (((volatile uint32_t*)m_inMirror[kSyncInSlot].host())[2] != tag) throw vh::Error(-(int)hipErrorUnknown, "stream-in: the device did not publish its pass");
     std::atomic_thread_fence(std::memory_order_acquire);
-    if (refileFailedInserts(kSyncInSlot, h_SDFBlockDescInput, h_SDFBlockInput, s_nStreamdInBlocks))
+    if (refileFailedInserts(kSyncInSlot, h_SDFBlockDescInput.get(), h_SDFBlockInput.get(), s_nStreamdInBlocks))
         throw vh::Error(VH_ERR_HEAP_EXHAUSTED, "stream-in: not enough free SDF blocks");
 }
 
@@ -726,7 +696,7 @@ void CUDASceneRepChunkGrid::streamInLaunches()
 // the union of heap and table.  They come in again with a later pass.  Returns true if the heap was exhausted.
 bool CUDASceneRepChunkGrid::refileFailedInserts(int slot, const SDFBlockDesc* descs, const vh::SDFBlock* blocks, unsigned int& nIn)
 {
-    const volatile uint32_t* m = h_inMirror[slot];
+    const volatile uint32_t* m = m_inMirror[slot].host();
     const bool exhausted = m[3] != 0u;
     const unsigned int nFailed = exhausted ? nIn : m[0];
     if (exhausted) {
@@ -747,7 +717,7 @@ bool CUDASceneRepChunkGrid::refileFailedInserts(int slot, const SDFBlockDesc* de
 // DSC/CUDASceneRepChunkGrid.cpp:268-311
 unsigned int CUDASceneRepChunkGrid::integrateInHash(const vh::vec3f& posCamera, float radius, bool useParts)
 {
-    return integrateInHash(posCamera, radius, useParts, h_SDFBlockDescInput, h_SDFBlockInput, d_SDFBlockDescInput, d_SDFBlockInput,
+    return integrateInHash(posCamera, radius, useParts, h_SDFBlockDescInput.get(), h_SDFBlockInput.get(), d_SDFBlockDescInput.get(), d_SDFBlockInput.get(),
                            m_maxNumberOfSDFBlocksIntegrateFromGlobalHash, nullptr);
 }
 
@@ -762,7 +732,7 @@ unsigned int CUDASceneRepChunkGrid::integrateInHash(const vh::vec3f& posCamera, 
                                    std::max(camChunk.z - chunkRadius.z, m_minGridPos.z) };
     const vh::vec3i endChunk = { std::min(camChunk.x + chunkRadius.x, m_maxGridPos.x - 1), std::min(camChunk.y + chunkRadius.y, m_maxGridPos.y - 1),
                                  std::min(camChunk.z + chunkRadius.z, m_maxGridPos.z - 1) };
-    hipStream_t cs = (hipStream_t)m_copyStream;
+    hipStream_t cs = (hipStream_t)m_copyStream.get();
 
     unsigned int nSDFBlocks = 0;
     std::lock_guard<std::mutex> l(m_gridMutex);
@@ -839,18 +809,15 @@ void CUDASceneRepChunkGrid::pipelineStart()
     if (m_plStarted) return;
     const size_t n = kPipelineBlocks;
     for (int i = 0; i < 2; i++) {
-        checkHip(hipMalloc((void**)&d_plOutDesc[i], sizeof(SDFBlockDesc) * n), "hipMalloc");
-        checkHip(hipHostMalloc((void**)&h_plOutDesc[i], sizeof(SDFBlockDesc) * n, hipHostMallocMapped), "hipHostMalloc");
-        checkHip(hipHostMalloc((void**)&h_plOutBlocks[i], sizeof(vh::SDFBlock) * n, hipHostMallocMapped), "hipHostMalloc");
-        checkHip(hipHostGetDevicePointer((void**)&hd_plOutDesc[i], h_plOutDesc[i], 0), "hipHostGetDevicePointer");
-        checkHip(hipHostGetDevicePointer((void**)&hd_plOutBlocks[i], h_plOutBlocks[i], 0), "hipHostGetDevicePointer");
-        checkHip(hipHostMalloc((void**)&h_plOutMirror[i], sizeof(uint32_t) * 4, hipHostMallocMapped), "hipHostMalloc");
-        h_plOutMirror[i][0] = h_plOutMirror[i][1] = h_plOutMirror[i][2] = h_plOutMirror[i][3] = 0u;
-        checkHip(hipHostGetDevicePointer((void**)&hd_plOutMirror[i], h_plOutMirror[i], 0), "hipHostGetDevicePointer");
-        checkHip(hipHostMalloc((void**)&h_plInDesc[i], sizeof(SDFBlockDesc) * n, hipHostMallocDefault), "hipHostMalloc");
-        checkHip(hipHostMalloc((void**)&h_plInBlocks[i], sizeof(vh::SDFBlock) * n, hipHostMallocDefault), "hipHostMalloc");
-        checkHip(hipMalloc((void**)&d_plInDesc[i], sizeof(SDFBlockDesc) * n), "hipMalloc");
-        checkHip(hipMalloc((void**)&d_plInBlocks[i], sizeof(vh::SDFBlock) * n), "hipMalloc");
+        d_plOutDesc[i] = vh::deviceAlloc<SDFBlockDesc>(n, "hipMalloc");
+        m_plOutDesc[i] = vh::Mapped<SDFBlockDesc>(n, "hipHostMalloc");
+        m_plOutBlocks[i] = vh::Mapped<vh::SDFBlock>(n, "hipHostMalloc");
+        m_plOutMirror[i] = vh::Mapped<uint32_t>(4, "hipHostMalloc");
+        std::memset(m_plOutMirror[i].host(), 0, sizeof(uint32_t) * 4);
+        h_plInDesc[i] = vh::pinnedAlloc<SDFBlockDesc>(n, "hipHostMalloc");
+        h_plInBlocks[i] = vh::pinnedAlloc<vh::SDFBlock>(n, "hipHostMalloc");
+        d_plInDesc[i] = vh::deviceAlloc<SDFBlockDesc>(n, "hipMalloc");
+        d_plInBlocks[i] = vh::deviceAlloc<vh::SDFBlock>(n, "hipMalloc");
     }
     m_plQuit = false;
     m_plThread = std::thread(&CUDASceneRepChunkGrid::pipelineWorker, this);
@@ -867,12 +834,6 @@ void CUDASceneRepChunkGrid::pipelineStop()
     m_plCv.notify_all();
     if (m_plThread.joinable()) m_plThread.join();
     m_plStarted = false;
-    for (int i = 0; i < 2; i++) {
-        (void)hipFree(d_plOutDesc[i]); (void)hipHostFree(h_plOutDesc[i]); (void)hipHostFree(h_plOutBlocks[i]); (void)hipHostFree(h_plOutMirror[i]);
-        (void)hipHostFree(h_plInDesc[i]); (void)hipHostFree(h_plInBlocks[i]); (void)hipFree(d_plInDesc[i]); (void)hipFree(d_plInBlocks[i]);
-        d_plOutDesc[i] = nullptr; h_plOutDesc[i] = nullptr; h_plOutBlocks[i] = nullptr; h_plOutMirror[i] = nullptr;
-        h_plInDesc[i] = nullptr; h_plInBlocks[i] = nullptr; d_plInDesc[i] = nullptr; d_plInBlocks[i] = nullptr;
-    }
 }
 
 // the worker: one job per frame
@@ -897,7 +858,7 @@ void CUDASceneRepChunkGrid::pipelineWorker()
         try {
             if (job.haveOut) {
                 // the blocks that left: in the mapped staging buffer once the device has published the pass's tag
-                volatile uint32_t* m = h_plOutMirror[job.outSlot];
+                volatile uint32_t* m = m_plOutMirror[job.outSlot].host();
                 const auto t0 = std::chrono::steady_clock::now();
                 unsigned int spins = 0;
                 while (m[2] != job.outTag) {
@@ -908,13 +869,13 @@ void CUDASceneRepChunkGrid::pipelineWorker()
                 const unsigned int n = m[0];
                 if (n > job.outMost)
                     throw vh::Error(VH_ERR_STAGING_OVERFLOW, "streaming pipeline: the stream-out pass found more blocks than its probe (blocks are lost)");
-                if (n != 0) integrateInChunkGrid(h_plOutDesc[job.outSlot], h_plOutBlocks[job.outSlot], n);
+                if (n != 0) integrateInChunkGrid(m_plOutDesc[job.outSlot].host(), m_plOutBlocks[job.outSlot].host(), n);
                 m_plBlocksOut += n;
             }
             StreamDecision d = { 0u, 0xffffffffu, job.inSlot };
             if (job.haveNext) {
-                d.nIn = integrateInHash(job.nextPos, job.nextRadius, true, h_plInDesc[job.inSlot], h_plInBlocks[job.inSlot], d_plInDesc[job.inSlot],
-                                        d_plInBlocks[job.inSlot], kPipelineBlocks, &d.chunkBit);
+                d.nIn = integrateInHash(job.nextPos, job.nextRadius, true, h_plInDesc[job.inSlot].get(), h_plInBlocks[job.inSlot].get(), d_plInDesc[job.inSlot].get(),
+                                        d_plInBlocks[job.inSlot].get(), kPipelineBlocks, &d.chunkBit);
             }
             m_plDecision = d;
         } catch (const vh::Error& e) {
@@ -936,7 +897,7 @@ bool CUDASceneRepChunkGrid::pipelineHasDecision(const vh::vec3f& posCamera, floa
 void CUDASceneRepChunkGrid::pipelineCheckInsert(int slot, bool block)
 {
     if (!m_plInsert[slot].pending) return;
-    volatile uint32_t* m = h_inMirror[slot];
+    volatile uint32_t* m = m_inMirror[slot].host();
     if (m[2] != m_plInsert[slot].tag) {
         if (!block) return;
         checkHip(hipStreamSynchronize((hipStream_t)m_sceneRepHashSDF->getStream()), "hipStreamSynchronize");
@@ -946,7 +907,7 @@ void CUDASceneRepChunkGrid::pipelineCheckInsert(int slot, bool block)
     m_plInsert[slot].pending = false;
     unsigned int nIn = m_plInsert[slot].nIn;
     // (on exhaustion the chunk's bit is set again in the host's copy; the device's copy was not touched)
-    (void)refileFailedInserts(slot, h_plInDesc[slot], h_plInBlocks[slot], nIn);
+    (void)refileFailedInserts(slot, h_plInDesc[slot].get(), h_plInBlocks[slot].get(), nIn);
     m_plBlocksIn += nIn;
 }
 
@@ -992,12 +953,12 @@ bool CUDASceneRepChunkGrid::pipelineStreamOut(const vh::vec3f& posCamera, float 
         const unsigned int start = useParts ? m_currentPart * threadsPerPart : 0;
         const float cam[3] = { posCamera.x, posCamera.y, posCamera.z };
         // pass 1 lists into device memory (pass 2 reads the list back); pass 2 writes blocks AND descriptors to the host
-        check(vh_stream_out_device(&hd, &hp, threadsPerPart, start, radius, cam, d_SDFBlockCounter, d_plOutDesc[slot], (VhVoxel*)hd_plOutBlocks[slot],
-                                   mostBlocks, token, d_bitMask, stream), "vh_stream_out_device");
-        checkHip(hipMemcpyAsync(h_plOutDesc[slot], d_plOutDesc[slot], sizeof(SDFBlockDesc) * mostBlocks, hipMemcpyDeviceToHost, (hipStream_t)stream), "descs to host");
+        check(vh_stream_out_device(&hd, &hp, threadsPerPart, start, radius, cam, d_SDFBlockCounter.get(), d_plOutDesc[slot].get(), (VhVoxel*)m_plOutBlocks[slot].device(),
+                                   mostBlocks, token, d_bitMask.get(), stream), "vh_stream_out_device");
+        checkHip(hipMemcpyAsync(m_plOutDesc[slot].host(), d_plOutDesc[slot].get(), sizeof(SDFBlockDesc) * mostBlocks, hipMemcpyDeviceToHost, (hipStream_t)stream), "descs to host");
         m_plOutTag = ++m_plTag ? m_plTag : ++m_plTag;
         m_plOutMost = mostBlocks;
-        check(vh_publish_count(d_SDFBlockCounter, hd_plOutMirror[slot], m_plOutTag, stream), "vh_publish_count");
+        check(vh_publish_count(d_SDFBlockCounter.get(), m_plOutMirror[slot].device(), m_plOutTag, stream), "vh_publish_count");
         m_plOutThisFrame = true;
     } else {
         (void)m_sceneRepHashSDF->nextLockToken(); // (the pass draws one: keep the sequence of tokens the same)
@@ -1017,8 +978,8 @@ void CUDASceneRepChunkGrid::pipelineStreamIn(const StreamDecision& d)
     const int32_t token = m_sceneRepHashSDF->nextLockToken();
     m_sceneRepHashSDF->noteTableEdited();
     const uint32_t tag = ++m_plTag ? m_plTag : ++m_plTag;
-    check(vh_stream_in_device(&hd, &hp, d.nIn, d_plInDesc[d.slot], (const VhVoxel*)d_plInBlocks[d.slot], token, d_insertFailed, d_bitMask, d.chunkBit,
-                              hd_inMirror[d.slot], tag, m_sceneRepHashSDF->getStream()), "vh_stream_in_device");
+    check(vh_stream_in_device(&hd, &hp, d.nIn, d_plInDesc[d.slot].get(), (const VhVoxel*)d_plInBlocks[d.slot].get(), token, d_insertFailed.get(), d_bitMask.get(), d.chunkBit,
+                              m_inMirror[d.slot].device(), tag, m_sceneRepHashSDF->getStream()), "vh_stream_in_device");
     m_plInsert[d.slot].pending = true; m_plInsert[d.slot].tag = tag; m_plInsert[d.slot].nIn = d.nIn;
 }
 
@@ -1070,7 +1031,7 @@ void CUDASceneRepChunkGrid::pipelineDrain(bool undo)
     if (undo && m_plDecisionValid) {
         // a choice nobody will use: the chunk goes back into the grid (its bit with it; the device's copy still has it set)
         m_plDecisionValid = false;
-        if (m_plDecision.nIn != 0u) integrateInChunkGrid(h_plInDesc[m_plDecision.slot], h_plInBlocks[m_plDecision.slot], m_plDecision.nIn);
+        if (m_plDecision.nIn != 0u) integrateInChunkGrid(h_plInDesc[m_plDecision.slot].get(), h_plInBlocks[m_plDecision.slot].get(), m_plDecision.nIn);
     }
     pipelineCheckInsert(0, undo);
     pipelineCheckInsert(1, undo);

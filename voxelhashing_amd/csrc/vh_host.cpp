@@ -21,18 +21,52 @@
 #include "vh_host_util.hpp"
 #include "vh_stage_timer.hpp"
 
-namespace {
+// ---------------------------------------------------------------------------
+// the owners of include/vh_owners.hpp
+// ---------------------------------------------------------------------------
 
-inline void check(int code, const char* what)
+namespace vh {
+
+void DeviceFree::operator()(void* p) const noexcept { (void)hipFree(p); }
+void PinnedFree::operator()(void* p) const noexcept { (void)hipHostFree(p); }
+void EventDestroy::operator()(void* e) const noexcept { (void)hipEventDestroy((hipEvent_t)e); }
+void StreamDestroy::operator()(void* s) const noexcept { (void)hipStreamDestroy((hipStream_t)s); }
+
+void* deviceAllocBytes(size_t bytes, const char* what)
 {
-    if (code != 0) throw vh::Error(code, std::string(what) + ": " + vh_error_string(code));
+    void* p = nullptr;
+    checkHip(hipMalloc(&p, bytes), what);
+    return p;
 }
-inline void checkHip(hipError_t e, const char* what)
+void* pinnedAllocBytes(size_t bytes, bool mapped, const char* what)
 {
-    if (e != hipSuccess) throw vh::Error(-(int)e, std::string(what) + ": " + hipGetErrorString(e));
+    void* p = nullptr;
+    checkHip(hipHostMalloc(&p, bytes, mapped ? hipHostMallocMapped : hipHostMallocDefault), what);
+    return p;
+}
+void* deviceAlias(void* mappedHost, const char* what)
+{
+    void* d = nullptr;
+    checkHip(hipHostGetDevicePointer(&d, mappedHost, 0), what);
+    return d;
+}
+Event makeEvent(bool timing)
+{
+    hipEvent_t e = nullptr;
+    if (hipEventCreateWithFlags(&e, (timing ? 0u : hipEventDisableTiming) | hipEventReleaseToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        checkHip(timing ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
+    }
+    return Event((void*)e);
+}
+Stream makeStream(const char* what)
+{
+    hipStream_t s = nullptr;
+    checkHip(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), what);
+    return Stream((void*)s);
 }
 
-} // namespace
+} // namespace vh
 
 // ---------------------------------------------------------------------------
 // utility C ABI
@@ -304,23 +338,21 @@ CUDASceneRepHashSDF::CUDASceneRepHashSDF(const HashParams& params, const VhScene
     create(params);
 }
 
-CUDASceneRepHashSDF::~CUDASceneRepHashSDF() { destroy(); }
+// (the stream must be done with the buffers before the members give them back)
+CUDASceneRepHashSDF::~CUDASceneRepHashSDF() { (void)hipStreamSynchronize((hipStream_t)m_stream); }
+void CUDASceneRepHashSDF::HashDataFree::operator()(HashData* hd) const noexcept { (void)vh_hash_data_free(hd); }
 
 void CUDASceneRepHashSDF::create(const HashParams& params)
 {
     m_hashParams = params;
     m_numIntegratedFrames = 0;
     m_lockEpoch = 0;
-    h_occupied = nullptr;
-    m_occupiedEvent = nullptr;
     m_occupiedPending = false;
     m_counterCleared = false;
-    m_timer = new VhStageTimer(3);
+    m_timer.reset(new VhStageTimer(3));
     m_aheadPending = 0;
     m_tableEpoch = 0;
-    d_packedFrame = nullptr;
     m_packedPixels = 0;
-    d_riderDone = nullptr;
     std::memset(m_riderTotals, 0, sizeof(m_riderTotals));
     // (scenes of more blocks in view than this keep the pass over the voxels in a launch of its own.  Up to 2048 blocks the
     // rider has a workgroup for every block and saves 4.8 us a frame at 350 blocks, 5 us at 1200; with more a workgroup takes
@@ -331,27 +363,14 @@ void CUDASceneRepHashSDF::create(const HashParams& params)
     std::memset(&m_job, 0, sizeof(m_job));
     std::memset(&m_hashData, 0, sizeof(m_hashData));
     check(vh_hash_data_alloc(&m_hashData, &m_hashParams), "HashData::allocate");
+    m_hashDataOwner.reset(&m_hashData);
     // the counters the riders of computeNormals' launch count themselves off on (never reset: the totals are compared)
-    checkHip(hipMalloc((void**)&d_riderDone, VH_RIDER_DONE_WORDS * sizeof(uint32_t)), "rider counters");
-    checkHip(hipMemsetAsync(d_riderDone, 0, VH_RIDER_DONE_WORDS * sizeof(uint32_t), (hipStream_t)m_stream), "hipMemsetAsync");
+    d_riderDone = vh::deviceAlloc<uint32_t>(VH_RIDER_DONE_WORDS, "rider counters");
+    checkHip(hipMemsetAsync(d_riderDone.get(), 0, VH_RIDER_DONE_WORDS * sizeof(uint32_t), (hipStream_t)m_stream), "hipMemsetAsync");
     // mapped pinned word the fused integrate kernel mirrors the in-frustum block count into
-    checkHip(hipHostMalloc((void**)&h_occupied, 2 * sizeof(uint32_t), hipHostMallocMapped), "hipHostMalloc");
-    h_occupied[0] = h_occupied[1] = 0;
-    void* dptr = nullptr;
-    checkHip(hipHostGetDevicePointer(&dptr, h_occupied, 0), "hipHostGetDevicePointer");
-    m_occupiedEvent = dptr; // device alias of h_occupied
+    m_occupied = vh::Mapped<uint32_t>(2, "hipHostMalloc");
+    m_occupied.host()[0] = m_occupied.host()[1] = 0;
     reset();
-}
-
-void CUDASceneRepHashSDF::destroy()
-{
-    (void)hipStreamSynchronize((hipStream_t)m_stream);
-    delete m_timer;
-    m_timer = nullptr;
-    if (d_packedFrame) { (void)hipFree(d_packedFrame); d_packedFrame = nullptr; }
-    if (d_riderDone) { (void)hipFree(d_riderDone); d_riderDone = nullptr; }
-    if (h_occupied) (void)hipHostFree(h_occupied);
-    vh_hash_data_free(&m_hashData);
 }
 
 // DSC/CUDASceneRepHashSDF.h:101-109
@@ -365,7 +384,7 @@ void CUDASceneRepHashSDF::reset()
     m_tableEpoch++;
     m_occupiedPending = true; // reset() waits for the device before it clears the mapped words
     pollOccupiedCount(true);
-    h_occupied[0] = h_occupied[1] = 0;
+    m_occupied.host()[0] = m_occupied.host()[1] = 0;
     m_hashParams.m_numOccupiedBlocks = 0;
     m_counterCleared = false;
     m_lockEpoch = 0;
@@ -413,7 +432,7 @@ void CUDASceneRepHashSDF::pollOccupiedCount(bool block)
     }
     // the fused integrate kernel stores the count of its frame into the mapped word; without blocking this is
     // the count of the most recent frame whose kernel has run
-    m_hashParams.m_numOccupiedBlocks = ((volatile uint32_t*)h_occupied)[0];
+    m_hashParams.m_numOccupiedBlocks = ((volatile uint32_t*)m_occupied.host())[0];
 }
 
 const HashParams& CUDASceneRepHashSDF::getHashParams()
@@ -440,19 +459,15 @@ unsigned int CUDASceneRepHashSDF::getHeapFreeCount()
     return count + 1;
 }
 
-unsigned int CUDASceneRepHashSDF::getNumFramesStartedOnDevice() const { return ((volatile uint32_t*)h_occupied)[1]; }
+unsigned int CUDASceneRepHashSDF::getNumFramesStartedOnDevice() const { return ((volatile uint32_t*)m_occupied.host())[1]; }
 
 // the alloc + compactify passes of the frame whose pose has just been set, as a job
 void CUDASceneRepHashSDF::prepareJob(const DepthCameraData& cam, const DepthCameraParams& cp, const unsigned int* d_bitMask)
 {
     const size_t pixels = (size_t)cp.m_imageWidth * cp.m_imageHeight;
     if (pixels > m_packedPixels) { // the packed frame follows the image size (first frame, or a larger adapter image)
-        if (d_packedFrame) {
-            checkHip(hipStreamSynchronize((hipStream_t)m_stream), "hipStreamSynchronize");
-            checkHip(hipFree(d_packedFrame), "hipFree");
-            d_packedFrame = nullptr;
-        }
-        checkHip(hipMalloc(&d_packedFrame, 8 * pixels), "packed frame");
+        if (d_packedFrame) checkHip(hipStreamSynchronize((hipStream_t)m_stream), "hipStreamSynchronize");
+        d_packedFrame = vh::deviceAlloc<unsigned char>(8 * pixels, "packed frame");
         m_packedPixels = pixels;
     }
     std::memset(&m_job, 0, sizeof(m_job));
@@ -461,11 +476,11 @@ void CUDASceneRepHashSDF::prepareJob(const DepthCameraData& cam, const DepthCame
     m_job.cam = cam;
     m_job.cp = cp;
     m_job.d_bitMask = d_bitMask;
-    m_job.d_packedFrame = d_packedFrame;
+    m_job.d_packedFrame = d_packedFrame.get();
     m_job.lockToken = nextLockToken();
     m_job.frameNumber = m_numIntegratedFrames;
     m_job.tableEpoch = m_tableEpoch;
-    m_job.d_riderDone = d_riderDone;
+    m_job.d_riderDone = d_riderDone.get();
     m_job.listDoneTotal = m_riderTotals[0]; m_job.listClassTotal = m_riderTotals[1];
 }
 
@@ -508,7 +523,7 @@ void CUDASceneRepHashSDF::integrateFused(const DepthCameraData& cam, const Depth
     const bool packedIsCurrent = m_job.allocLaunched && m_job.d_packedFrame && m_job.cam.d_depthData == cam.d_depthData &&
                                  m_job.cam.d_colorData == cam.d_colorData && m_job.cp.m_imageWidth == cp.m_imageWidth &&
                                  m_job.cp.m_imageHeight == cp.m_imageHeight;
-    check(vh_integrate_fused(&m_hashData, &m_hashParams, &cam, &cp, flags, nextLockToken(), (uint32_t*)m_occupiedEvent,
+    check(vh_integrate_fused(&m_hashData, &m_hashParams, &cam, &cp, flags, nextLockToken(), m_occupied.device(),
                              m_numIntegratedFrames + 1u, packedIsCurrent ? m_job.d_packedFrame : nullptr, m_stream), "integrate (fused)");
     m_occupiedPending = true;
 }
@@ -528,7 +543,7 @@ VhFrameJob* CUDASceneRepHashSDF::integrateAhead(const vh::mat4f& lastRigidTransf
     if (m_riderMostBlocks != 0u && m_hashParams.m_numOccupiedBlocks <= m_riderMostBlocks) {
         m_job.fusedFlags = fusedFlags();
         m_job.fusedLockToken = nextLockToken();
-        m_job.d_countMirror = (uint32_t*)m_occupiedEvent;
+        m_job.d_countMirror = m_occupied.device();
         m_job.mirrorTag = m_numIntegratedFrames + 1u;
         m_job.fusedPrepared = 1;
     }
@@ -717,58 +732,44 @@ void CUDASceneRepHashSDF::debugHash(unsigned int report[4])
 // ---------------------------------------------------------------------------
 
 CUDARayCastSDF::CUDARayCastSDF(const RayCastParams& params, vhStream_t stream)
-    : m_params(params), m_stream(stream), m_timer(nullptr), m_timeMarchOnly(false), m_timeStride(1), m_renderCalls(0)
+    : m_params(params), m_stream(stream), m_timeMarchOnly(false), m_timeStride(1), m_renderCalls(0)
 {
     std::memset(&m_data, 0, sizeof(m_data));
     const size_t n = (size_t)params.m_width * params.m_height;
     // RayCastData::allocate, DSC/RayCastSDFUtil.h:56-61
-    checkHip(hipMalloc((void**)&m_data.d_depth, sizeof(float) * n), "RayCastData::allocate");
-    checkHip(hipMalloc((void**)&m_data.d_depth4, sizeof(float) * 4 * n), "RayCastData::allocate");
-    checkHip(hipMalloc((void**)&m_data.d_normals, sizeof(float) * 4 * n), "RayCastData::allocate");
-    checkHip(hipMalloc((void**)&m_data.d_colors, sizeof(float) * 4 * n), "RayCastData::allocate");
-    d_tileHeads = nullptr;
-    d_tileBlocks = nullptr;
+    d_depth = vh::deviceAlloc<float>(n, "RayCastData::allocate");
+    d_depth4 = vh::deviceAlloc<float>(4 * n, "RayCastData::allocate");
+    d_normals = vh::deviceAlloc<float>(4 * n, "RayCastData::allocate");
+    d_colors = vh::deviceAlloc<float>(4 * n, "RayCastData::allocate");
+    m_data.d_depth = d_depth.get();
+    m_data.d_depth4 = d_depth4.get();
+    m_data.d_normals = d_normals.get();
+    m_data.d_colors = d_colors.get();
     m_useIntervals = true;
     const size_t tiles = (size_t)((params.m_width + 7) / 8) * ((params.m_height + 7) / 8);
-    checkHip(hipMalloc((void**)&d_tileHeads, sizeof(uint32_t) * 4 * (tiles ? tiles : 1)), "tile heads");
-    checkHip(hipMalloc((void**)&d_tileBlocks, sizeof(VhTileBlock) * VH_TILE_LIST_CAPACITY_LARGE * (tiles ? tiles : 1)), "tile block lists");
-    h_longestList = nullptr;
-    d_longestList = nullptr;
+    d_tileHeads = vh::deviceAlloc<uint32_t>(4 * (tiles ? tiles : 1), "tile heads");
+    d_tileBlocks = vh::deviceAlloc<VhTileBlock>(VH_TILE_LIST_CAPACITY_LARGE * (tiles ? tiles : 1), "tile block lists");
     m_largeTables = false;
     m_quietFrames = 0;
-    checkHip(hipHostMalloc((void**)&h_longestList, sizeof(uint32_t), hipHostMallocMapped), "hipHostMalloc");
-    *h_longestList = 0;
-    checkHip(hipHostGetDevicePointer((void**)&d_longestList, h_longestList, 0), "hipHostGetDevicePointer");
-    check(vh_ray_interval_clear(d_tileHeads, params.m_width, params.m_height, m_stream), "vh_ray_interval_clear");
-    d_schedule = nullptr;
+    m_longestList = vh::Mapped<uint32_t>(1, "hipHostMalloc");
+    *m_longestList.host() = 0;
+    check(vh_ray_interval_clear(d_tileHeads.get(), params.m_width, params.m_height, m_stream), "vh_ray_interval_clear");
     m_phase = 0;
     m_preSplatsUsed = 0;
     std::memset(&m_preSplat, 0, sizeof(m_preSplat));
     const size_t schedBytes = vh_render_schedule_bytes(params.m_width, params.m_height);
-    checkHip(hipMalloc((void**)&d_schedule, schedBytes), "render schedule");
-    checkHip(hipMemsetAsync(d_schedule, 0, schedBytes, (hipStream_t)m_stream), "render schedule");
+    d_schedule = vh::DevicePtr<uint32_t>(static_cast<uint32_t*>(vh::deviceAllocBytes(schedBytes, "render schedule")));
+    checkHip(hipMemsetAsync(d_schedule.get(), 0, schedBytes, (hipStream_t)m_stream), "render schedule");
 }
 
-CUDARayCastSDF::~CUDARayCastSDF()
-{
-    (void)hipStreamSynchronize((hipStream_t)m_stream);
-    delete m_timer;
-    if (m_data.d_depth) (void)hipFree(m_data.d_depth);
-    if (m_data.d_depth4) (void)hipFree(m_data.d_depth4);
-    if (m_data.d_normals) (void)hipFree(m_data.d_normals);
-    if (m_data.d_colors) (void)hipFree(m_data.d_colors);
-    if (d_tileHeads) (void)hipFree(d_tileHeads);
-    if (d_tileBlocks) (void)hipFree(d_tileBlocks);
-    if (d_schedule) (void)hipFree(d_schedule);
-    if (h_longestList) (void)hipHostFree(h_longestList);
-}
+CUDARayCastSDF::~CUDARayCastSDF() { (void)hipStreamSynchronize((hipStream_t)m_stream); }
 
 void CUDARayCastSDF::setTiming(bool on, bool marchOnly, unsigned int stride)
 {
     m_timeMarchOnly = marchOnly;
     m_timeStride = stride ? stride : 1u;
-    if (on && !m_timer) m_timer = new VhStageTimer(4);
-    if (!on && m_timer) { delete m_timer; m_timer = nullptr; }
+    if (on && !m_timer) m_timer.reset(new VhStageTimer(4));
+    if (!on) m_timer.reset();
 }
 
 double CUDARayCastSDF::getEventPairOverheadMs()
@@ -809,7 +810,7 @@ void CUDARayCastSDF::render(const HashData& hashData, const HashParams& hashPara
                              std::memcmp(m_preSplat.pose, lastRigidTransform.m, sizeof(m_preSplat.pose)) == 0;
     if (m_preSplat.valid && !preSplatted) {
         // a splat made ahead that this call cannot use: its tile heads and lists must not leak into the fresh one
-        check(vh_ray_interval_clear(d_tileHeads, m_params.m_width, m_params.m_height, m_stream), "vh_ray_interval_clear");
+        check(vh_ray_interval_clear(d_tileHeads.get(), m_params.m_width, m_params.m_height, m_stream), "vh_ray_interval_clear");
         m_phase = m_preSplat.phase;
     }
     m_preSplat.valid = false;
@@ -822,11 +823,11 @@ void CUDARayCastSDF::render(const HashData& hashData, const HashParams& hashPara
         ++m_phase;
         // Table size for this frame, from what the ray caster reported two frames ago (mapped host word, no
         // synchronisation): large tables as soon as a list outgrew the small ones, back after 30 frames without one.
-        const uint32_t longest = *(volatile uint32_t*)h_longestList;
+        const uint32_t longest = *(volatile uint32_t*)m_longestList.host();
         if (longest > (uint32_t)VH_TILE_LIST_CAPACITY) { m_largeTables = true; m_quietFrames = 0; }
         else if (m_largeTables && ++m_quietFrames > 30) m_largeTables = false;
         m_tileCapacity = m_largeTables ? VH_TILE_LIST_CAPACITY_LARGE : VH_TILE_LIST_CAPACITY;
-        check(vh_ray_interval_splat(&hashData, &hashParams, &cp, &m_params, d_tileHeads, d_tileBlocks, m_tileCapacity, d_schedule, m_phase, d_longestList, m_stream), "rayIntervalSplatCUDA");
+        check(vh_ray_interval_splat(&hashData, &hashParams, &cp, &m_params, d_tileHeads.get(), d_tileBlocks.get(), m_tileCapacity, d_schedule.get(), m_phase, m_longestList.device(), m_stream), "rayIntervalSplatCUDA");
         if (timedAll) m_timer->stop(ST_SPLAT, (hipStream_t)m_stream);
     }
     if (timedAll) { // what an event pair reads with nothing between its two records: the share of a bracketed launch that is not the kernel
@@ -842,7 +843,7 @@ void CUDARayCastSDF::render(const HashData& hashData, const HashParams& hashPara
     if (!m_params.m_useGradients) out.d_normals = nullptr;
 #endif
     if (m_useIntervals) {
-        check(vh_render_intervals_co(&hashData, &hashParams, &out, &cp, &m_params, d_tileHeads, d_tileBlocks, m_tileCapacity, d_schedule, m_phase, coLaunch, m_stream), "renderCS");
+        check(vh_render_intervals_co(&hashData, &hashParams, &out, &cp, &m_params, d_tileHeads.get(), d_tileBlocks.get(), m_tileCapacity, d_schedule.get(), m_phase, coLaunch, m_stream), "renderCS");
     } else {
         check(vh_render(&hashData, &hashParams, &out, &cp, &m_params, m_stream), "renderCS");
     }
@@ -858,12 +859,12 @@ void CUDARayCastSDF::render(const HashData& hashData, const HashParams& hashPara
             RayCastParams next = m_params;
             std::memcpy(next.m_viewMatrix, coLaunch->hashParams.m_rigidTransformInverse, sizeof(next.m_viewMatrix));
             std::memcpy(next.m_viewMatrixInverse, coLaunch->hashParams.m_rigidTransform, sizeof(next.m_viewMatrixInverse));
-            const uint32_t longest = *(volatile uint32_t*)h_longestList;
+            const uint32_t longest = *(volatile uint32_t*)m_longestList.host();
             if (longest > (uint32_t)VH_TILE_LIST_CAPACITY) { m_largeTables = true; m_quietFrames = 0; }
             else if (m_largeTables && ++m_quietFrames > 30) m_largeTables = false;
             const uint32_t capacity = m_largeTables ? VH_TILE_LIST_CAPACITY_LARGE : VH_TILE_LIST_CAPACITY;
-            check(vh_compute_normals_co2(m_data.d_normals, m_data.d_depth4, m_params.m_width, m_params.m_height, coLaunch, &next, d_tileHeads, d_tileBlocks,
-                                         capacity, d_schedule, m_phase + 1u, d_longestList, m_stream), "computeNormals");
+            check(vh_compute_normals_co2(m_data.d_normals, m_data.d_depth4, m_params.m_width, m_params.m_height, coLaunch, &next, d_tileHeads.get(), d_tileBlocks.get(),
+                                         capacity, d_schedule.get(), m_phase + 1u, m_longestList.device(), m_stream), "computeNormals");
             m_preSplat.valid = true;
             std::memcpy(m_preSplat.pose, coLaunch->hashParams.m_rigidTransform, sizeof(m_preSplat.pose));
             m_preSplat.table = (const void*)hashData.d_hash;

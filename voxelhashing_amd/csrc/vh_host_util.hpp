@@ -3,6 +3,21 @@
 
 #include <hip/hip_runtime.h>
 
+#include <string>
+
+#include "../../include/vh_api.h"
+#include "../../include/vh_owners.hpp"
+
+// the host classes throw: an error code of the C ABI, or a HIP error, with the name of what failed
+inline void check(int code, const char* what)
+{
+    if (code != 0) throw vh::Error(code, std::string(what) + ": " + vh_error_string(code));
+}
+inline void checkHip(hipError_t e, const char* what)
+{
+    if (e != hipSuccess) throw vh::Error(-(int)e, std::string(what) + ": " + hipGetErrorString(e));
+}
+
 // C-ABI convention: 0 ok, <0 = -(hipError_t), >0 = VH_ERR_*
 #define VH_HIP(expr)                                 \
     do {                                             \

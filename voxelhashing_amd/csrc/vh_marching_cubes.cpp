@@ -19,19 +19,6 @@
 #include "../../include/vh.hpp"
 #include "vh_host_util.hpp"
 
-namespace {
-
-inline void check(int code, const char* what)
-{
-    if (code != 0) throw vh::Error(code, std::string(what) + ": " + vh_error_string(code));
-}
-inline void checkHip(hipError_t e, const char* what)
-{
-    if (e != hipSuccess) throw vh::Error(-(int)e, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-} // namespace
-
 // ---------------------------------------------------------------------------
 // launcher-level buffers
 // ---------------------------------------------------------------------------
@@ -44,12 +31,19 @@ int vh_marching_cubes_data_alloc(VhMarchingCubesData* data, const VhMarchingCube
     if (!data || !params || params->m_maxNumTriangles == 0) return VH_ERR_BAD_ARGUMENT;
     std::memset(data, 0, sizeof(*data));
     const size_t maxBlocks = (size_t)params->m_hashNumBuckets * params->m_hashBucketSize;
-    VH_HIP(hipMalloc((void**)&data->d_params, sizeof(VhMarchingCubesParams)));
-    VH_HIP(hipMalloc((void**)&data->d_numOccupiedBlocks, sizeof(uint32_t)));
-    VH_HIP(hipMalloc((void**)&data->d_occupiedBlocks, sizeof(uint32_t) * (maxBlocks ? maxBlocks : 1)));
-    VH_HIP(hipMalloc((void**)&data->d_triangles, sizeof(VhTriangle) * (size_t)params->m_maxNumTriangles));
-    VH_HIP(hipMalloc((void**)&data->d_numTriangles, sizeof(uint32_t)));
-    VH_HIP(hipMemcpy(data->d_params, params, sizeof(*params), hipMemcpyHostToDevice));
+    const int r = [&]() -> int {
+        VH_HIP(hipMalloc((void**)&data->d_params, sizeof(VhMarchingCubesParams)));
+        VH_HIP(hipMalloc((void**)&data->d_numOccupiedBlocks, sizeof(uint32_t)));
+        VH_HIP(hipMalloc((void**)&data->d_occupiedBlocks, sizeof(uint32_t) * (maxBlocks ? maxBlocks : 1)));
+        VH_HIP(hipMalloc((void**)&data->d_triangles, sizeof(VhTriangle) * (size_t)params->m_maxNumTriangles));
+        VH_HIP(hipMalloc((void**)&data->d_numTriangles, sizeof(uint32_t)));
+        VH_HIP(hipMemcpy(data->d_params, params, sizeof(*params), hipMemcpyHostToDevice));
+        return VH_OK;
+    }();
+    if (r != VH_OK) { // (what was allocated before the failure goes back)
+        vh_marching_cubes_data_free(data);
+        return r;
+    }
     data->m_bIsOnGPU = 1;
     return VH_OK;
 }
@@ -244,14 +238,12 @@ CUDAMarchingCubesHashSDF::CUDAMarchingCubesHashSDF(const MarchingCubesParams& pa
 {
     std::memset(&m_data, 0, sizeof(m_data));
     check(vh_marching_cubes_data_alloc(&m_data, &m_params), "MarchingCubesData::allocate");
+    m_dataOwner.reset(&m_data);
     check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
 }
 
-CUDAMarchingCubesHashSDF::~CUDAMarchingCubesHashSDF()
-{
-    (void)hipStreamSynchronize((hipStream_t)m_stream);
-    vh_marching_cubes_data_free(&m_data);
-}
+CUDAMarchingCubesHashSDF::~CUDAMarchingCubesHashSDF() { (void)hipStreamSynchronize((hipStream_t)m_stream); }
+void CUDAMarchingCubesHashSDF::DataFree::operator()(MarchingCubesData* d) const noexcept { vh_marching_cubes_data_free(d); }
 
 unsigned int CUDAMarchingCubesHashSDF::getNumTriangles()
 {

@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/vh_api.h"
+#include "vh_params.hpp"
 
 namespace {
 
@@ -28,10 +29,12 @@ void uncomment(std::string& s)
     }
 }
 
-typedef std::map<std::string, std::string> Values;
+typedef vh::ParamValues Values;
+
+} // namespace
 
 // addParameterFile, parameterFile.h:22-60 (a later line overrides an earlier one)
-void parseStream(std::istream& in, Values& values)
+void vh::parseStream(std::istream& in, Values& values)
 {
     std::string line;
     while (std::getline(in, line)) {
@@ -48,6 +51,8 @@ void parseStream(std::istream& in, Values& values)
         values[name] = value;
     }
 }
+
+namespace {
 
 struct Reader {
     const Values& v;
@@ -223,7 +228,7 @@ int vh_app_state_read(const char* filename, VhAppState* out)
     std::ifstream f(filename);
     if (!f.is_open()) return VH_ERR_IO;
     Values values;
-    parseStream(f, values);
+    vh::parseStream(f, values);
     fill(values, out);
     return VH_OK;
 }
@@ -233,7 +238,7 @@ int vh_app_state_parse(const char* text, VhAppState* out)
     if (!text || !out) return VH_ERR_BAD_ARGUMENT;
     std::istringstream in(text);
     Values values;
-    parseStream(in, values);
+    vh::parseStream(in, values);
     fill(values, out);
     return VH_OK;
 }
@@ -244,7 +249,7 @@ int vh_read_render_state(const char* filename, VhRenderState* out)
     std::ifstream f(filename);
     if (!f.is_open()) return VH_ERR_IO;
     Values values;
-    parseStream(f, values);
+    vh::parseStream(f, values);
     fillRender(values, out);
     return VH_OK;
 }
@@ -254,7 +259,7 @@ int vh_parse_render_state(const char* text, VhRenderState* out)
     if (!text || !out) return VH_ERR_BAD_ARGUMENT;
     std::istringstream in(text);
     Values values;
-    parseStream(in, values);
+    vh::parseStream(in, values);
     fillRender(values, out);
     return VH_OK;
 }
@@ -266,7 +271,7 @@ int vh_read_calibration_state(const char* filename, VhCalibrationState* out)
     std::ifstream f(filename);
     if (!f.is_open()) return VH_ERR_IO;
     Values values;
-    parseStream(f, values);
+    vh::parseStream(f, values);
     fillCalibration(values, out);
     return VH_OK;
 }
@@ -276,7 +281,7 @@ int vh_parse_calibration_state(const char* text, VhCalibrationState* out)
     if (!text || !out) return VH_ERR_BAD_ARGUMENT;
     std::istringstream in(text);
     Values values;
-    parseStream(in, values);
+    vh::parseStream(in, values);
     fillCalibration(values, out);
     return VH_OK;
 }

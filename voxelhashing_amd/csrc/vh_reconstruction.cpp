@@ -31,7 +31,6 @@
 
 #include <chrono>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <thread>
@@ -41,28 +40,9 @@
 
 namespace {
 
-inline void check(int code, const char* what)
-{
-    if (code != 0) throw vh::Error(code, std::string(what) + ": " + vh_error_string(code));
-}
-inline void checkHip(hipError_t e, const char* what)
-{
-    if (e != hipSuccess) throw vh::Error(-(int)e, std::string(what) + ": " + hipGetErrorString(e));
-}
 inline double now()
 {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-inline hipEvent_t newEvent(bool timing)
-{
-    hipEvent_t e = nullptr;
-    // device-scope release: these events order streams of one device (or time them); nothing on the host reads memory
-    // behind them (a default event makes the queue write back its caches: ~6 us of idle queue per record)
-    if (hipEventCreateWithFlags(&e, (timing ? 0u : hipEventDisableTiming) | hipEventReleaseToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        checkHip(timing ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
-    }
-    return e;
 }
 
 } // namespace
@@ -86,7 +66,7 @@ ReconstructionOptions Reconstruction::defaultOptions()
 
 Reconstruction::Reconstruction(CUDASceneRepHashSDF* sceneRep, CUDARayCastSDF* rayCast, CUDASceneRepChunkGrid* chunkGrid,
                                const DepthCameraParams& cp, const ReconstructionOptions& options)
-    : m_sceneRep(sceneRep), m_rayCast(rayCast), m_chunkGrid(chunkGrid), m_cp(cp), m_opt(options), m_frameNumber(0), m_copyStream(nullptr), m_copyStream2(nullptr)
+    : m_sceneRep(sceneRep), m_rayCast(rayCast), m_chunkGrid(chunkGrid), m_cp(cp), m_opt(options), m_frameNumber(0)
 {
     m_debugFailRender = 0;
     m_pipelineOutSeen = m_pipelineInSeen = 0;
@@ -95,74 +75,35 @@ Reconstruction::Reconstruction(CUDASceneRepHashSDF* sceneRep, CUDARayCastSDF* ra
     if (options.s_streamingEnabled && !chunkGrid) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction: streaming needs a chunk grid");
     if (options.s_renderEnabled && !rayCast) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction: rendering needs a ray caster");
     std::memset(&m_stats, 0, sizeof(m_stats));
-    for (int i = 0; i < kStagingSlots; i++) {
-        d_stageDepth[i] = nullptr; d_stageColorRaw[i] = nullptr; d_stageColor[i] = nullptr;
-        m_slotReady[i] = m_slotReady2[i] = nullptr;
-        m_slotSceneFrame[i] = 0;
-    }
+    for (int i = 0; i < kStagingSlots; i++) m_slotSceneFrame[i] = 0;
     m_uploads = 0;
     m_raw = m_rawRun = false;
     std::memset(&m_rawFormat, 0, sizeof(m_rawFormat));
-    for (int i = 0; i < kStagingSlots; i++) d_rawDepth[i] = nullptr;
-    d_unfilteredDepth = d_unfilteredColor = nullptr;
     m_probePending = false;
     std::memset(m_probePose, 0, sizeof(m_probePose));
     m_tracking = false;
     m_trackedFrames = m_lostFrames = 0;
     std::memset(&m_trackingState, 0, sizeof(m_trackingState));
-    d_trkPartials = d_trkIdentity = nullptr;
-    d_trkState = nullptr;
-    d_trkTicket = nullptr;
-    h_trkResult = d_trkResult = nullptr;
     m_trkTag = 0;
     if (m_opt.s_framesOnHost) {
         const size_t n = (size_t)cp.m_imageWidth * cp.m_imageHeight;
-        hipStream_t cs = nullptr;
-        checkHip(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking), "hipStreamCreate");
-        m_copyStream = (void*)cs;
-        hipStream_t cs2 = nullptr;
-        checkHip(hipStreamCreateWithFlags(&cs2, hipStreamNonBlocking), "hipStreamCreate");
-        m_copyStream2 = (void*)cs2;
+        m_copyStream = vh::makeStream("hipStreamCreate");
+        m_copyStream2 = vh::makeStream("hipStreamCreate");
         for (int i = 0; i < kStagingSlots; i++) {
-            checkHip(hipMalloc((void**)&d_stageDepth[i], sizeof(float) * (n ? n : 1)), "staging depth");
-            checkHip(hipMalloc((void**)&d_stageColorRaw[i], 4 * (n ? n : 1)), "staging colour (raw)");
-            checkHip(hipMalloc((void**)&d_stageColor[i], sizeof(float) * 4 * (n ? n : 1)), "staging colour");
-            m_slotReady[i] = (void*)newEvent(false);
-            m_slotReady2[i] = (void*)newEvent(false);
+            d_stageDepth[i] = vh::deviceAlloc<float>(n, "staging depth");
+            d_stageColorRaw[i] = vh::deviceAlloc<unsigned char>(4 * (n ? n : 1), "staging colour (raw)");
+            d_stageColor[i] = vh::deviceAlloc<float>(4 * (n ? n : 1), "staging colour");
+            m_slotReady[i] = vh::makeEvent(false);
+            m_slotReady2[i] = vh::makeEvent(false);
         }
         m_stats.uploadBytes = (sizeof(float) + 4) * n;
     }
 }
 
+// (synchronize() waits for the copy streams and the main stream: then the members go, buffers and events before the streams)
 Reconstruction::~Reconstruction()
 {
     try { synchronize(); } catch (...) {}
-    for (auto& p : m_uploadTimers) { (void)hipEventDestroy((hipEvent_t)p.first); (void)hipEventDestroy((hipEvent_t)p.second); }
-    for (void* e : m_timerPool) (void)hipEventDestroy((hipEvent_t)e);
-    for (int i = 0; i < kStagingSlots; i++) {
-        if (m_slotReady[i]) (void)hipEventDestroy((hipEvent_t)m_slotReady[i]);
-        if (m_slotReady2[i]) (void)hipEventDestroy((hipEvent_t)m_slotReady2[i]);
-        if (d_stageDepth[i]) (void)hipFree(d_stageDepth[i]);
-        if (d_stageColorRaw[i]) (void)hipFree(d_stageColorRaw[i]);
-        if (d_stageColor[i]) (void)hipFree(d_stageColor[i]);
-        if (d_rawDepth[i]) (void)hipFree(d_rawDepth[i]);
-    }
-    if (d_unfilteredDepth) (void)hipFree(d_unfilteredDepth);
-    if (d_unfilteredColor) (void)hipFree(d_unfilteredColor);
-    for (int i = 0; i < kStagingSlots; i++)
-        for (auto* v : { &d_trkInput[i], &d_trkInputNormal[i] })
-            for (float* q : *v)
-                if (q) (void)hipFree(q);
-    for (auto* v : { &d_trkModel, &d_trkModelNormal, &d_trkCorr, &d_trkCorrNormal })
-        for (float* q : *v)
-            if (q) (void)hipFree(q);
-    if (d_trkPartials) (void)hipFree(d_trkPartials);
-    if (d_trkState) (void)hipFree(d_trkState);
-    if (d_trkIdentity) (void)hipFree(d_trkIdentity);
-    if (d_trkTicket) (void)hipFree(d_trkTicket);
-    if (h_trkResult) (void)hipHostFree(h_trkResult);
-    if (m_copyStream) (void)hipStreamDestroy((hipStream_t)m_copyStream);
-    if (m_copyStream2) (void)hipStreamDestroy((hipStream_t)m_copyStream2);
 }
 
 // Raw mode owns the copy streams and the staging ring in both residencies: the ingest kernel writes the slot's maps
@@ -183,30 +124,41 @@ void Reconstruction::setRawFormat(const RawFrameFormat& f)
     if (f.s_colorFilter && !(sigmaOk(f.s_colorSigmaD) && sigmaOk(f.s_colorSigmaR))) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: the colour filter needs positive sigmas");
     const size_t n = (size_t)W * H, nDepth = (size_t)f.depthWidth * f.depthHeight;
     const size_t colorBytes = f.colorChannels ? (size_t)f.colorChannels * f.colorWidth * f.colorHeight : 0;
-    if (!m_copyStream) {
-        hipStream_t cs = nullptr;
-        checkHip(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking), "hipStreamCreate");
-        m_copyStream = (void*)cs;
-    }
-    if (!m_copyStream2) {
-        hipStream_t cs2 = nullptr;
-        checkHip(hipStreamCreateWithFlags(&cs2, hipStreamNonBlocking), "hipStreamCreate");
-        m_copyStream2 = (void*)cs2;
-    }
+    // everything that is not there yet, into locals: a failure leaves the loop as it was
+    vh::Stream cs, cs2;
+    vh::DevicePtr<float> depth[kStagingSlots], color[kStagingSlots], unfilteredDepth, unfilteredColor;
+    vh::Event ready[kStagingSlots], ready2[kStagingSlots];
+    vh::DevicePtr<unsigned short> rawDepth[kStagingSlots];
+    vh::DevicePtr<unsigned char> colorRaw[kStagingSlots];
+    if (!m_copyStream) cs = vh::makeStream("hipStreamCreate");
+    if (!m_copyStream2) cs2 = vh::makeStream("hipStreamCreate");
     for (int i = 0; i < kStagingSlots; i++) {
-        if (!d_stageDepth[i]) checkHip(hipMalloc((void**)&d_stageDepth[i], sizeof(float) * n), "staging depth");
-        if (!d_stageColor[i]) checkHip(hipMalloc((void**)&d_stageColor[i], sizeof(float) * 4 * n), "staging colour");
-        if (!m_slotReady[i]) m_slotReady[i] = (void*)newEvent(false);
-        if (!m_slotReady2[i]) m_slotReady2[i] = (void*)newEvent(false);
+        if (!d_stageDepth[i]) depth[i] = vh::deviceAlloc<float>(n, "staging depth");
+        if (!d_stageColor[i]) color[i] = vh::deviceAlloc<float>(4 * n, "staging colour");
+        if (!m_slotReady[i]) ready[i] = vh::makeEvent(false);
+        if (!m_slotReady2[i]) ready2[i] = vh::makeEvent(false);
         if (m_opt.s_framesOnHost) { // the sensor's images, as they come over the link
-            if (!d_rawDepth[i]) checkHip(hipMalloc((void**)&d_rawDepth[i], sizeof(uint16_t) * nDepth), "staging depth (raw)");
-            if (d_stageColorRaw[i]) { (void)hipFree(d_stageColorRaw[i]); d_stageColorRaw[i] = nullptr; }
-            checkHip(hipMalloc((void**)&d_stageColorRaw[i], colorBytes ? colorBytes : 1), "staging colour (raw)");
+            rawDepth[i] = vh::deviceAlloc<unsigned short>(nDepth, "staging depth (raw)");
+            colorRaw[i] = vh::deviceAlloc<unsigned char>(colorBytes, "staging colour (raw)");
         }
     }
     // what the filters read (vh_sensor.cpp: d_depthMapResampledFloat, d_colorMapResampledFloat4)
-    if (f.s_depthFilter && !d_unfilteredDepth) checkHip(hipMalloc((void**)&d_unfilteredDepth, sizeof(float) * n), "unfiltered depth");
-    if (f.s_colorFilter && f.colorChannels && !d_unfilteredColor) checkHip(hipMalloc((void**)&d_unfilteredColor, sizeof(float) * 4 * n), "unfiltered colour");
+    if (f.s_depthFilter) unfilteredDepth = vh::deviceAlloc<float>(n, "unfiltered depth");
+    if (f.s_colorFilter && f.colorChannels) unfilteredColor = vh::deviceAlloc<float>(4 * n, "unfiltered colour");
+    if (cs) m_copyStream = std::move(cs);
+    if (cs2) m_copyStream2 = std::move(cs2);
+    for (int i = 0; i < kStagingSlots; i++) {
+        if (depth[i]) d_stageDepth[i] = std::move(depth[i]);
+        if (color[i]) d_stageColor[i] = std::move(color[i]);
+        if (ready[i]) m_slotReady[i] = std::move(ready[i]);
+        if (ready2[i]) m_slotReady2[i] = std::move(ready2[i]);
+        if (m_opt.s_framesOnHost) {
+            d_rawDepth[i] = std::move(rawDepth[i]);
+            d_stageColorRaw[i] = std::move(colorRaw[i]); // (in place of the constructor's, which is sized for RGBX at adapter size)
+        }
+    }
+    d_unfilteredDepth = std::move(unfilteredDepth);
+    d_unfilteredColor = std::move(unfilteredColor);
     m_stats.uploadBytes = sizeof(uint16_t) * nDepth + colorBytes;
     m_rawFormat = f;
     m_raw = true;
@@ -219,51 +171,38 @@ void Reconstruction::setTracking(const VhTrackingState& ts)
     if (m_tracking) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setTracking: tracking is already set");
     if (m_stats.frames || m_stats.invalidFrames || m_uploads || m_frameNumber) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setTracking: frames have been processed already");
     if (!m_rayCast || !m_opt.s_renderEnabled) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setTracking: tracking aligns to the ray cast (needs a ray caster and s_renderEnabled)");
-    const unsigned int W = m_cp.m_imageWidth, H = m_cp.m_imageHeight, levels = ts.s_maxLevels;
-    if (levels == 0 || levels > VH_TRACKING_MAX_LEVELS || (W >> (levels - 1)) < 2 || (H >> (levels - 1)) < 2)
-        throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setTracking: bad pyramid");
-    auto floats = [](size_t n, const char* what) {
-        float* q = nullptr;
-        checkHip(hipMalloc((void**)&q, sizeof(float) * (n ? n : 1)), what);
-        return q;
-    };
-    unsigned int fac = 1;
-    for (unsigned int i = 0; i < levels; i++) {
-        m_levelWidth.push_back(W / fac);
-        m_levelHeight.push_back(H / fac);
-        const size_t n = 4 * (size_t)m_levelWidth[i] * m_levelHeight[i];
+    // into locals first: a failure leaves the loop without tracking and without half a set of buffers
+    std::unique_ptr<vh::IcpSolver> icp(new vh::IcpSolver(m_cp.m_imageWidth, m_cp.m_imageHeight, ts.s_maxLevels, "Reconstruction::setTracking"));
+    std::vector<vh::DevicePtr<float>> input[kStagingSlots], inputNormal[kStagingSlots];
+    for (unsigned int i = 0; i < ts.s_maxLevels; i++) {
+        const size_t n = 4 * (size_t)icp->width[i] * icp->height[i];
         for (int slot = 0; slot < (int)kStagingSlots; slot++) { // (frames read in place use the first set only)
-            d_trkInput[slot].push_back(floats(n, "tracking input"));
-            d_trkInputNormal[slot].push_back(floats(n, "tracking input normals"));
+            input[slot].push_back(vh::deviceAlloc<float>(n, "tracking input"));
+            inputNormal[slot].push_back(vh::deviceAlloc<float>(n, "tracking input normals"));
         }
-        d_trkModel.push_back(i ? floats(n, "tracking model") : nullptr);
-        d_trkModelNormal.push_back(i ? floats(n, "tracking model normals") : nullptr);
-        const bool three = ts.s_maxInnerIter[i] != 1u; // such a level keeps the three-kernel sequence and its maps
-        d_trkCorr.push_back(three ? floats(n, "tracking correspondences") : nullptr);
-        d_trkCorrNormal.push_back(three ? floats(n, "tracking correspondence normals") : nullptr);
-        fac *= 2;
     }
-    d_trkPartials = floats(30 * (size_t)vh_icp_num_partials(W, H), "tracking partials");
-    checkHip(hipMalloc((void**)&d_trkState, sizeof(VhIcpState)), "VhIcpState");
-    checkHip(hipMalloc((void**)&d_trkTicket, sizeof(uint32_t)), "tracking ticket");
-    d_trkIdentity = floats(16, "deltaEstimate");
-    checkHip(hipHostMalloc((void**)&h_trkResult, sizeof(VhIcpResult), hipHostMallocMapped), "tracking result");
-    std::memset(h_trkResult, 0, sizeof(VhIcpResult));
-    checkHip(hipHostGetDevicePointer((void**)&d_trkResult, h_trkResult, 0), "tracking result");
+    vh::Mapped<VhIcpResult> result(1, "tracking result");
+    std::memset(result.host(), 0, sizeof(VhIcpResult));
     // the estimate every solve starts from (:816-826 pass the identity), once
     hipStream_t ms = (hipStream_t)m_sceneRep->getStream();
     const vh::mat4f I = vh::mat4f::identity();
-    checkHip(hipMemcpyAsync(d_trkIdentity, I.m, sizeof(I.m), hipMemcpyHostToDevice, ms), "deltaEstimate");
-    checkHip(hipMemsetAsync(d_trkTicket, 0, sizeof(uint32_t), ms), "tracking ticket");
+    checkHip(hipMemcpyAsync(icp->estimate.get(), I.m, sizeof(I.m), hipMemcpyHostToDevice, ms), "deltaEstimate");
+    checkHip(hipMemsetAsync(icp->ticket.get(), 0, sizeof(uint32_t), ms), "tracking ticket");
     checkHip(hipStreamSynchronize(ms), "Reconstruction::setTracking");
+    m_icp = std::move(icp);
+    for (int slot = 0; slot < (int)kStagingSlots; slot++) {
+        d_trkInput[slot] = std::move(input[slot]);
+        d_trkInputNormal[slot] = std::move(inputNormal[slot]);
+    }
+    m_trkResult = std::move(result);
     m_trackingState = ts;
     m_tracking = true;
 }
 
 void Reconstruction::synchronize()
 {
-    if (m_copyStream) checkHip(hipStreamSynchronize((hipStream_t)m_copyStream), "hipStreamSynchronize");
-    if (m_copyStream2) checkHip(hipStreamSynchronize((hipStream_t)m_copyStream2), "hipStreamSynchronize");
+    if (m_copyStream) checkHip(hipStreamSynchronize((hipStream_t)m_copyStream.get()), "hipStreamSynchronize");
+    if (m_copyStream2) checkHip(hipStreamSynchronize((hipStream_t)m_copyStream2.get()), "hipStreamSynchronize");
     // the scene's side stream joins the main stream in integrateFinish(): the main stream is the last to finish
     checkHip(hipStreamSynchronize((hipStream_t)m_sceneRep->getStream()), "hipStreamSynchronize");
     if (m_chunkGrid) m_chunkGrid->pipelineDrain(false); // (the grid's worker has taken in what the last frame moved out; its choice for the next frame stands)
@@ -286,12 +225,12 @@ void Reconstruction::reset()
 const ReconstructionStats& Reconstruction::getStats()
 {
     if (!m_uploadTimers.empty()) {
-        checkHip(hipStreamSynchronize((hipStream_t)m_copyStream), "hipStreamSynchronize");
+        checkHip(hipStreamSynchronize((hipStream_t)m_copyStream.get()), "hipStreamSynchronize");
         for (auto& p : m_uploadTimers) {
             float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, (hipEvent_t)p.first, (hipEvent_t)p.second) == hipSuccess) { m_stats.uploadMs += ms; m_stats.uploadsTimed++; }
-            m_timerPool.push_back(p.first);
-            m_timerPool.push_back(p.second);
+            if (hipEventElapsedTime(&ms, (hipEvent_t)p.first.get(), (hipEvent_t)p.second.get()) == hipSuccess) { m_stats.uploadMs += ms; m_stats.uploadsTimed++; }
+            m_timerPool.push_back(std::move(p.first));
+            m_timerPool.push_back(std::move(p.second));
         }
         m_uploadTimers.clear();
     }
@@ -321,7 +260,7 @@ DepthCameraData Reconstruction::upload(const SequenceFrame& f)
 {
     const unsigned int slot = m_uploads % kStagingSlots;
     const size_t n = (size_t)m_cp.m_imageWidth * m_cp.m_imageHeight;
-    hipStream_t cs = (hipStream_t)m_copyStream, ms = (hipStream_t)m_sceneRep->getStream();
+    hipStream_t cs = (hipStream_t)m_copyStream.get(), ms = (hipStream_t)m_sceneRep->getStream();
     // With tracking the host has seen the ICP result of the frame before this one, so that frame's ray cast has run, and
     // that is behind the integrate of the frame before it: every frame two or more back is done with its slot, and the
     // slot's last frame is four back.  (A lost frame uploads without integrating: the scene's counter does not count it.)
@@ -344,25 +283,21 @@ DepthCameraData Reconstruction::upload(const SequenceFrame& f)
         if (waited) m_stats.hostWaitSeconds += now() - w0;
     }
     auto timerEvent = [&]() {
-        if (!m_timerPool.empty()) { void* e = m_timerPool.back(); m_timerPool.pop_back(); return e; }
-        return (void*)newEvent(true);
+        if (m_timerPool.empty()) return vh::makeEvent(true);
+        vh::Event e = std::move(m_timerPool.back());
+        m_timerPool.pop_back();
+        return e;
     };
     const bool timed = (m_uploads % 8u) == 0u; // (a timed pair idles the copy stream twice)
-    void *t0 = nullptr, *t1 = nullptr;
+    vh::Event t0, t1;
     // The frame travels by the copy engines (hipMemcpyAsync: depth on one stream, colour on another, so that each gets
-    // an engine), then the colour is converted as in the sensor path.  Reading the pinned frame from a kernel instead
-    // (vh_upload_frame: one pass, no raw-colour staging) was measured slower for the loop as a whole: while uncached
-    // reads of host memory are in flight every other kernel's memory accesses queue behind them, and k_render takes
-    // two to three times as long (vh_kernels.hip, k_upload_frame; VH_UPLOAD_KERNEL=1 selects that path for measurement).
-    static const bool useKernel = std::getenv("VH_UPLOAD_KERNEL") != nullptr;
-    void *devDepth = nullptr, *devColor = nullptr;
-    const bool mapped = !m_rawRun && useKernel && (n % 4u) == 0u && hipHostGetDevicePointer(&devDepth, const_cast<float*>(f.depth), 0) == hipSuccess &&
-                        (!f.color || hipHostGetDevicePointer(&devColor, const_cast<void*>(f.color), 0) == hipSuccess);
-    if (useKernel && !mapped) (void)hipGetLastError();
+    // an engine), then the colour is converted as in the sensor path.  A kernel that read the pinned frame itself (one
+    // pass, no raw-colour staging) was measured slower for the loop as a whole: while uncached reads of host memory are
+    // in flight every other kernel's memory accesses queue behind them, and k_render took two to three times as long.
     if (timed) {
         t0 = timerEvent();
         t1 = timerEvent();
-        checkHip(hipEventRecord((hipEvent_t)t0, cs), "hipEventRecord");
+        checkHip(hipEventRecord((hipEvent_t)t0.get(), cs), "hipEventRecord");
     }
     const bool hasColor = m_rawRun ? (m_rawFormat.colorChannels != 0u && f.color != nullptr) : f.color != nullptr;
     if (m_rawRun) {
@@ -373,53 +308,51 @@ DepthCameraData Reconstruction::upload(const SequenceFrame& f)
         const uint16_t* depthRaw = reinterpret_cast<const uint16_t*>(f.depth);
         const uint8_t* colorRaw = hasColor ? static_cast<const uint8_t*>(f.color) : nullptr;
         if (m_opt.s_framesOnHost) { // two copies, two streams, as below
-            hipStream_t cs2 = (hipStream_t)m_copyStream2;
-            checkHip(hipMemcpyAsync(d_rawDepth[slot], depthRaw, sizeof(uint16_t) * (size_t)rf.depthWidth * rf.depthHeight, hipMemcpyHostToDevice, cs2), "upload depth");
-            checkHip(hipEventRecord((hipEvent_t)m_slotReady2[slot], cs2), "hipEventRecord");
-            if (colorRaw) checkHip(hipMemcpyAsync(d_stageColorRaw[slot], colorRaw, (size_t)rf.colorChannels * rf.colorWidth * rf.colorHeight, hipMemcpyHostToDevice, cs), "upload colour");
-            checkHip(hipStreamWaitEvent(cs, (hipEvent_t)m_slotReady2[slot], 0), "hipStreamWaitEvent");
-            depthRaw = d_rawDepth[slot];
-            if (colorRaw) colorRaw = d_stageColorRaw[slot];
+            hipStream_t cs2 = (hipStream_t)m_copyStream2.get();
+            checkHip(hipMemcpyAsync(d_rawDepth[slot].get(), depthRaw, sizeof(uint16_t) * (size_t)rf.depthWidth * rf.depthHeight, hipMemcpyHostToDevice, cs2), "upload depth");
+            checkHip(hipEventRecord((hipEvent_t)m_slotReady2[slot].get(), cs2), "hipEventRecord");
+            if (colorRaw) checkHip(hipMemcpyAsync(d_stageColorRaw[slot].get(), colorRaw, (size_t)rf.colorChannels * rf.colorWidth * rf.colorHeight, hipMemcpyHostToDevice, cs), "upload colour");
+            checkHip(hipStreamWaitEvent(cs, (hipEvent_t)m_slotReady2[slot].get(), 0), "hipStreamWaitEvent");
+            depthRaw = d_rawDepth[slot].get();
+            if (colorRaw) colorRaw = d_stageColorRaw[slot].get();
         }
         const bool filterColor = colorRaw && rf.s_colorFilter;
-        float* depthOut = rf.s_depthFilter ? d_unfilteredDepth : d_stageDepth[slot];
-        float* colorOut = filterColor ? d_unfilteredColor : d_stageColor[slot];
+        float* depthOut = rf.s_depthFilter ? d_unfilteredDepth.get() : d_stageDepth[slot].get();
+        float* colorOut = filterColor ? d_unfilteredColor.get() : d_stageColor[slot].get();
         check(vh_ingest_frame(depthOut, colorRaw ? colorOut : nullptr, W, H, depthRaw, rf.depthWidth, rf.depthHeight, colorRaw, rf.colorWidth, rf.colorHeight,
-                              colorRaw ? rf.colorChannels : 0u, rf.depthShift, m_copyStream), "vh_ingest_frame");
-        if (filterColor) check(vh_gauss_filter_float4_map(d_stageColor[slot], d_unfilteredColor, rf.s_colorSigmaD, rf.s_colorSigmaR, W, H, m_copyStream), "gaussFilterFloat4Map");
-        if (rf.s_depthFilter) check(vh_gauss_filter_float_map(d_stageDepth[slot], d_unfilteredDepth, rf.s_depthSigmaD, rf.s_depthSigmaR, W, H, m_copyStream), "gaussFilterFloatMap");
-    } else if (mapped) {
-        check(vh_upload_frame((const float*)devDepth, (const uint8_t*)devColor, d_stageDepth[slot], d_stageColor[slot], m_cp.m_imageWidth, m_cp.m_imageHeight, m_copyStream), "vh_upload_frame");
+                              colorRaw ? rf.colorChannels : 0u, rf.depthShift, m_copyStream.get()), "vh_ingest_frame");
+        if (filterColor) check(vh_gauss_filter_float4_map(d_stageColor[slot].get(), d_unfilteredColor.get(), rf.s_colorSigmaD, rf.s_colorSigmaR, W, H, m_copyStream.get()), "gaussFilterFloat4Map");
+        if (rf.s_depthFilter) check(vh_gauss_filter_float_map(d_stageDepth[slot].get(), d_unfilteredDepth.get(), rf.s_depthSigmaD, rf.s_depthSigmaR, W, H, m_copyStream.get()), "gaussFilterFloatMap");
     } else {
         // two copies, two streams: each gets a copy engine of its own
-        hipStream_t cs2 = (hipStream_t)m_copyStream2;
-        checkHip(hipMemcpyAsync(d_stageDepth[slot], f.depth, sizeof(float) * n, hipMemcpyHostToDevice, cs2), "upload depth");
-        checkHip(hipEventRecord((hipEvent_t)m_slotReady2[slot], cs2), "hipEventRecord");
-        checkHip(hipStreamWaitEvent(ms, (hipEvent_t)m_slotReady2[slot], 0), "hipStreamWaitEvent");
+        hipStream_t cs2 = (hipStream_t)m_copyStream2.get();
+        checkHip(hipMemcpyAsync(d_stageDepth[slot].get(), f.depth, sizeof(float) * n, hipMemcpyHostToDevice, cs2), "upload depth");
+        checkHip(hipEventRecord((hipEvent_t)m_slotReady2[slot].get(), cs2), "hipEventRecord");
+        checkHip(hipStreamWaitEvent(ms, (hipEvent_t)m_slotReady2[slot].get(), 0), "hipStreamWaitEvent");
         if (f.color) {
-            checkHip(hipMemcpyAsync(d_stageColorRaw[slot], f.color, 4 * n, hipMemcpyHostToDevice, cs), "upload colour");
-            check(vh_convert_color_raw_to_float4(d_stageColor[slot], d_stageColorRaw[slot], m_cp.m_imageWidth, m_cp.m_imageHeight, m_copyStream), "convertColorRawToFloat4");
+            checkHip(hipMemcpyAsync(d_stageColorRaw[slot].get(), f.color, 4 * n, hipMemcpyHostToDevice, cs), "upload colour");
+            check(vh_convert_color_raw_to_float4(d_stageColor[slot].get(), d_stageColorRaw[slot].get(), m_cp.m_imageWidth, m_cp.m_imageHeight, m_copyStream.get()), "convertColorRawToFloat4");
         }
     }
     if (timed) {
         // the pair spans the whole upload: the depth copy runs on the other stream, so this one waits for it first
         // (t0 was recorded before either copy was enqueued; both streams were idle or busy with earlier uploads)
-        if (!mapped && !m_rawRun) checkHip(hipStreamWaitEvent(cs, (hipEvent_t)m_slotReady2[slot], 0), "hipStreamWaitEvent");
-        checkHip(hipEventRecord((hipEvent_t)t1, cs), "hipEventRecord");
-        m_uploadTimers.emplace_back(t0, t1);
+        if (!m_rawRun) checkHip(hipStreamWaitEvent(cs, (hipEvent_t)m_slotReady2[slot].get(), 0), "hipStreamWaitEvent");
+        checkHip(hipEventRecord((hipEvent_t)t1.get(), cs), "hipEventRecord");
+        m_uploadTimers.emplace_back(std::move(t0), std::move(t1));
     }
     if (m_tracking) { // what the tracker needs of the input depends on the frame alone: here, beside the previous frame's work
-        if (!mapped && !m_rawRun) checkHip(hipStreamWaitEvent(cs, (hipEvent_t)m_slotReady2[slot], 0), "hipStreamWaitEvent");
-        inputPyramid(slot, d_stageDepth[slot], m_copyStream);
+        if (!m_rawRun) checkHip(hipStreamWaitEvent(cs, (hipEvent_t)m_slotReady2[slot].get(), 0), "hipStreamWaitEvent");
+        inputPyramid(slot, d_stageDepth[slot].get(), m_copyStream.get());
     }
-    checkHip(hipEventRecord((hipEvent_t)m_slotReady[slot], cs), "hipEventRecord");
-    checkHip(hipStreamWaitEvent(ms, (hipEvent_t)m_slotReady[slot], 0), "hipStreamWaitEvent");
+    checkHip(hipEventRecord((hipEvent_t)m_slotReady[slot].get(), cs), "hipEventRecord");
+    checkHip(hipStreamWaitEvent(ms, (hipEvent_t)m_slotReady[slot].get(), 0), "hipStreamWaitEvent");
     m_slotSceneFrame[slot] = m_sceneRep->getNumIntegratedFrames() + 1u; // the scene frame this upload feeds
     m_uploads++;
     DepthCameraData cam;
     std::memset(&cam, 0, sizeof(cam));
-    cam.d_depthData = d_stageDepth[slot];
-    cam.d_colorData = hasColor ? d_stageColor[slot] : nullptr;
+    cam.d_depthData = d_stageDepth[slot].get();
+    cam.d_colorData = hasColor ? d_stageColor[slot].get() : nullptr;
     return cam;
 }
 
@@ -591,13 +524,10 @@ const unsigned int* Reconstruction::streamAround(const vh::vec3f& p)
 // (DSC/CUDACameraTrackingMultiRes.cpp:256-263) for one frame, on `stream`
 void Reconstruction::inputPyramid(unsigned int slot, const float* d_depth, vhStream_t stream)
 {
-    std::vector<float*>&in = d_trkInput[slot], &inN = d_trkInputNormal[slot];
-    check(vh_convert_depth_float_to_camera_space_float4(in[0], d_depth, &m_cp, m_levelWidth[0], m_levelHeight[0], stream), "convertDepthFloatToCameraSpaceFloat4");
-    check(vh_compute_normals(inN[0], in[0], m_levelWidth[0], m_levelHeight[0], stream), "computeNormals");
-    for (size_t i = 0; i + 1 < in.size(); i++) {
-        check(vh_resample_float4_map(in[i + 1], m_levelWidth[i + 1], m_levelHeight[i + 1], in[i], m_levelWidth[i], m_levelHeight[i], stream), "resampleFloat4Map");
-        check(vh_compute_normals(inN[i + 1], in[i + 1], m_levelWidth[i + 1], m_levelHeight[i + 1], stream), "computeNormals");
-    }
+    const vh::IcpPyramid in = vh::icpPyramid(d_trkInput[slot][0].get(), d_trkInputNormal[slot][0].get(), d_trkInput[slot], d_trkInputNormal[slot]);
+    check(vh_convert_depth_float_to_camera_space_float4(in.map[0], d_depth, &m_cp, m_icp->width[0], m_icp->height[0], stream), "convertDepthFloatToCameraSpaceFloat4");
+    check(vh_compute_normals(in.normal[0], in.map[0], m_icp->width[0], m_icp->height[0], stream), "computeNormals");
+    for (unsigned int i = 0; i + 1 < m_icp->width.size(); i++) m_icp->coarserLevel(in, i, stream);
 }
 
 // One frame with tracking: reconstruction() :750-879 with s_binaryDumpSensorUseTrajectory = false.  Everything is
@@ -606,7 +536,6 @@ void Reconstruction::inputPyramid(unsigned int slot, const float* d_depth, vhStr
 void Reconstruction::frameTracked(const SequenceFrame& f)
 {
     if (!f.depth) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction: frame without a depth map");
-    const VhTrackingState& ts = m_trackingState;
     vhStream_t stream = m_sceneRep->getStream();
     DepthCameraData cam;
     unsigned int slot = 0;
@@ -625,67 +554,27 @@ void Reconstruction::frameTracked(const SequenceFrame& f)
         const vh::mat4f lastTransform = m_sceneRep->getLastRigidTransform();
         m_rayCast->render(m_sceneRep->getHashData(), m_sceneRep->getHashParams(), m_cp, lastTransform, nullptr); // :763
         const RayCastData& rd = m_rayCast->getRayCastData();
-        const size_t levels = m_levelWidth.size();
-        std::vector<float*>&in = d_trkInput[slot], &inN = d_trkInputNormal[slot];
-        d_trkModel[0] = rd.d_depth4;
-        d_trkModelNormal[0] = rd.d_normals;
-        struct Borrowed { // (level 0 of the model is the ray caster's: the destructor frees what the vectors hold)
-            std::vector<float*>&a, &b;
-            ~Borrowed() { a[0] = b[0] = nullptr; }
-        } borrowed{ d_trkModel, d_trkModelNormal };
-        for (size_t i = 0; i + 1 < levels; i++) { // the model half of the pyramids, :256-263
-            check(vh_resample_float4_map(d_trkModel[i + 1], m_levelWidth[i + 1], m_levelHeight[i + 1], d_trkModel[i], m_levelWidth[i], m_levelHeight[i], stream), "resampleFloat4Map");
-            check(vh_compute_normals(d_trkModelNormal[i + 1], d_trkModel[i + 1], m_levelWidth[i + 1], m_levelHeight[i + 1], stream), "computeNormals");
-        }
-        checkHip(hipMemsetAsync(d_trkTicket, 0, sizeof(uint32_t), (hipStream_t)stream), "tracking ticket");
-        check(vh_icp_begin(d_trkState, d_trkIdentity, stream), "vh_icp_begin");
-        // the step that is the frame's last publishes the result itself: a publishing kernel behind it would be one more
-        // launch in a chain of dependent launches, and the step's last wave holds the state in its hands anyway
-        int lastLevel = -1;
-        for (int level = 0; level < (int)levels && lastLevel < 0; level++)
-            if (ts.s_maxOuterIter[level]) lastLevel = level;
+        const vh::IcpPyramid in = vh::icpPyramid(d_trkInput[slot][0].get(), d_trkInputNormal[slot][0].get(), d_trkInput[slot], d_trkInputNormal[slot]);
+        const vh::IcpPyramid mdl = vh::icpPyramid(rd.d_depth4, rd.d_normals, m_icp->model, m_icp->modelNormal);
+        for (unsigned int i = 0; i + 1 < m_icp->width.size(); i++) m_icp->coarserLevel(mdl, i, stream); // the model half of the pyramids, :256-263
         const uint32_t tag = ++m_trkTag;
-        bool published = false;
-        // coarse to fine, :265-279; align :291-321 with the loop exits taken on the device
-        for (int level = (int)levels - 1; level >= 0; level--) {
-            const unsigned int W = m_levelWidth[level], H = m_levelHeight[level];
-            const float levelFactor = std::pow(2.0f, (float)level);
-            check(vh_icp_begin_level(d_trkState, stream), "vh_icp_begin_level");
-            for (unsigned int outer = 0; outer < ts.s_maxOuterIter[level]; outer++) {
-                const unsigned int inner = ts.s_maxInnerIter[level];
-                if (inner == 1u) {
-                    const bool last = level == lastLevel && outer + 1 == ts.s_maxOuterIter[level];
-                    check(vh_icp_step(in[level], inN[level], d_trkModel[level], d_trkModelNormal[level], W, H, ts.s_distThres[level], ts.s_normalThres[level],
-                                      levelFactor, &m_cp, d_trkPartials, d_trkTicket, d_trkState, ts.s_angleTransThres[level], ts.s_distTransThres[level],
-                                      ts.s_residualEarlyOut[level], last ? d_trkResult : nullptr, tag, stream), "vh_icp_step");
-                    published = published || last;
-                    continue;
-                }
-                check(vh_icp_projective_correspondences(in[level], inN[level], d_trkModel[level], d_trkModelNormal[level], d_trkCorr[level], d_trkCorrNormal[level],
-                                                        W, H, ts.s_distThres[level], ts.s_normalThres[level], levelFactor, d_trkState, &m_cp, stream), "projectiveCorrespondences");
-                for (unsigned int i = 0; i < inner; i++) {
-                    check(vh_icp_build_linear_system(W, H, d_trkPartials, in[level], d_trkCorr[level], d_trkCorrNormal[level], d_trkState, stream), "buildLinearSystem");
-                    check(vh_icp_solve(d_trkState, d_trkPartials, vh_icp_num_partials(W, H), ts.s_angleTransThres[level], ts.s_distTransThres[level],
-                                       ts.s_residualEarlyOut[level], i + 1 == inner, stream), "vh_icp_solve");
-                }
-            }
-        }
-        if (!published) check(vh_icp_publish(d_trkState, d_trkResult, tag, stream), "vh_icp_publish"); // (the last level is a three-kernel one, or no level iterates)
+        // one launch per iteration where a level allows it; the last step stores the result and the tag into mapped memory
+        m_icp->align(in, mdl, m_trackingState, m_cp, true, m_trkResult.device(), tag, stream);
         // the one wait of the frame
         const double w0 = now();
-        while (__atomic_load_n(&h_trkResult->tag, __ATOMIC_ACQUIRE) != tag) {
+        while (__atomic_load_n(&m_trkResult.host()->tag, __ATOMIC_ACQUIRE) != tag) {
             std::this_thread::yield();
             if (now() - w0 > 30.0) throw vh::Error(VH_ERR_TIMEOUT, "Reconstruction: no tracking result from the device for 30 s");
         }
         m_stats.hostWaitSeconds += now() - w0;
-        if (h_trkResult->lost) { // "!!! TRACKING LOST !!!": the frame is not integrated, the scene keeps its pose
+        if (m_trkResult.host()->lost) { // "!!! TRACKING LOST !!!": the frame is not integrated, the scene keeps its pose
             m_lostFrames++;
             m_frameNumber++;
             m_poses.insert(m_poses.end(), 16, minf);
             return;
         }
         vh::mat4f delta;
-        std::memcpy(delta.m, h_trkResult->delta, sizeof(delta.m));
+        std::memcpy(delta.m, m_trkResult.host()->delta, sizeof(delta.m));
         transformation = lastTransform * delta;
         m_trackedFrames++;
     }

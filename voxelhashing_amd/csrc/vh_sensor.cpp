@@ -11,18 +11,6 @@
 #include "../../include/vh.hpp"
 #include "vh_host_util.hpp"
 
-namespace {
-inline void check(int code, const char* what)
-{
-    if (code != 0) throw vh::Error(code, std::string(what) + ": " + vh_error_string(code));
-}
-inline void checkHip(hipError_t e, const char* what)
-{
-    if (e != hipSuccess) throw vh::Error(-(int)e, std::string(what) + ": " + hipGetErrorString(e));
-}
-template <class T> void devAlloc(T*& p, size_t n, const char* what) { checkHip(hipMalloc((void**)&p, sizeof(T) * (n ? n : 1)), what); }
-} // namespace
-
 extern "C" int vh_rgbd_sensor_remap_params(const uint32_t sizes[6], const float depthIntrinsics[4], const float colorIntrinsics[4],
                                            const float depthExtrinsics[16], float thresOffset, float thresLin, VhViewParams* out)
 {
@@ -74,39 +62,28 @@ CUDARGBDSensor::CUDARGBDSensor(const Config& c, vhStream_t stream) : m_cfg(c), m
 
     const size_t nDepthIn = (size_t)c.depthWidth * c.depthHeight, nColorIn = (size_t)c.colorWidth * c.colorHeight;
     const size_t nOut = (size_t)c.adapterWidth * c.adapterHeight;
-    d_depthMapFloat = d_depthMapResampledFloat = d_depthMapFilteredFloat = d_intensityMapFilteredFloat = nullptr;
-    d_colorMapRaw = nullptr;
-    d_colorMapFloat4 = d_colorMapResampledFloat4 = d_cameraSpaceFloat4 = d_normalMapFloat4 = nullptr;
     std::memset(&m_depthCameraData, 0, sizeof(m_depthCameraData));
     std::memset(&m_remapParams, 0, sizeof(m_remapParams));
-    devAlloc(d_depthMapFloat, nDepthIn, "d_depthMapFloat");
-    devAlloc(d_depthMapResampledFloat, nOut, "d_depthMapResampledFloat");
-    devAlloc(d_colorMapRaw, 4 * nColorIn, "d_colorMapRaw");
-    devAlloc(d_colorMapFloat4, 4 * nColorIn, "d_colorMapFloat4");
-    devAlloc(d_colorMapResampledFloat4, 4 * nOut, "d_colorMapResampledFloat4");
-    devAlloc(d_depthMapFilteredFloat, nOut, "d_depthMapFilteredFloat");
-    devAlloc(d_cameraSpaceFloat4, 4 * nOut, "d_cameraSpaceFloat4");
-    devAlloc(d_normalMapFloat4, 4 * nOut, "d_normalMapFloat4");
-    devAlloc(d_intensityMapFilteredFloat, nOut, "d_intensityMapFilteredFloat");
-    d_depthData = d_colorData = nullptr;
-    devAlloc(d_depthData, nOut, "DepthCameraData::d_depthData");
-    devAlloc(d_colorData, 4 * nOut, "DepthCameraData::d_colorData");
-    m_depthCameraData.d_depthData = d_depthData;
-    m_depthCameraData.d_colorData = d_colorData;
+    d_depthMapFloat = vh::deviceAlloc<float>(nDepthIn, "d_depthMapFloat");
+    d_depthMapResampledFloat = vh::deviceAlloc<float>(nOut, "d_depthMapResampledFloat");
+    d_colorMapRaw = vh::deviceAlloc<unsigned char>(4 * nColorIn, "d_colorMapRaw");
+    d_colorMapFloat4 = vh::deviceAlloc<float>(4 * nColorIn, "d_colorMapFloat4");
+    d_colorMapResampledFloat4 = vh::deviceAlloc<float>(4 * nOut, "d_colorMapResampledFloat4");
+    d_depthMapFilteredFloat = vh::deviceAlloc<float>(nOut, "d_depthMapFilteredFloat");
+    d_cameraSpaceFloat4 = vh::deviceAlloc<float>(4 * nOut, "d_cameraSpaceFloat4");
+    d_normalMapFloat4 = vh::deviceAlloc<float>(4 * nOut, "d_normalMapFloat4");
+    d_intensityMapFilteredFloat = vh::deviceAlloc<float>(nOut, "d_intensityMapFilteredFloat");
+    d_depthData = vh::deviceAlloc<float>(nOut, "DepthCameraData::d_depthData");
+    d_colorData = vh::deviceAlloc<float>(4 * nOut, "DepthCameraData::d_colorData");
+    m_depthCameraData.d_depthData = d_depthData.get();
+    m_depthCameraData.d_colorData = d_colorData.get();
     // a resampled pixel whose nearest source pixel is outside the source is left untouched by the reference:
     // start from "invalid" instead of from uninitialised memory
-    check(vh_set_invalid_float_map(d_depthMapResampledFloat, c.adapterWidth, c.adapterHeight, m_stream), "setInvalidFloatMap");
-    checkHip(hipMemsetAsync(d_colorMapResampledFloat4, 0, sizeof(float) * 4 * nOut, (hipStream_t)m_stream), "clear colour");
+    check(vh_set_invalid_float_map(d_depthMapResampledFloat.get(), c.adapterWidth, c.adapterHeight, m_stream), "setInvalidFloatMap");
+    checkHip(hipMemsetAsync(d_colorMapResampledFloat4.get(), 0, sizeof(float) * 4 * nOut, (hipStream_t)m_stream), "clear colour");
 }
 
-CUDARGBDSensor::~CUDARGBDSensor()
-{
-    (void)hipStreamSynchronize((hipStream_t)m_stream);
-    void* all[] = { d_depthMapFloat, d_depthMapResampledFloat, d_colorMapRaw, d_colorMapFloat4, d_colorMapResampledFloat4, d_depthMapFilteredFloat,
-                    d_cameraSpaceFloat4, d_normalMapFloat4, d_intensityMapFilteredFloat, d_depthData, d_colorData, d_remapKeys, d_remapLargeList };
-    for (void* p : all)
-        if (p) (void)hipFree(p);
-}
+CUDARGBDSensor::~CUDARGBDSensor() { (void)hipStreamSynchronize((hipStream_t)m_stream); }
 
 void CUDARGBDSensor::setFiterDepthValues(bool b, float sigmaD, float sigmaR)
 {
@@ -134,12 +111,12 @@ void CUDARGBDSensor::setCameraCalibration(bool enabled, float colorFx, float col
     // allocated once, all ones and a zero counter: every resolve leaves them so
     const hipStream_t s = (hipStream_t)m_stream;
     if (!d_remapKeys) {
-        devAlloc(d_remapKeys, (size_t)W * H, "remap keys");
-        checkHip(hipMemsetAsync(d_remapKeys, 0xff, sizeof(uint64_t) * (size_t)W * H, s), "remap keys");
+        d_remapKeys = vh::deviceAlloc<uint64_t>((size_t)W * H, "remap keys");
+        checkHip(hipMemsetAsync(d_remapKeys.get(), 0xff, sizeof(uint64_t) * (size_t)W * H, s), "remap keys");
     }
     if (!d_remapLargeList) {
-        devAlloc(d_remapLargeList, vh_view_large_list_words(W, H), "remap list");
-        checkHip(hipMemsetAsync(d_remapLargeList, 0, sizeof(uint32_t), s), "remap list");
+        d_remapLargeList = vh::deviceAlloc<uint32_t>(vh_view_large_list_words(W, H), "remap list");
+        checkHip(hipMemsetAsync(d_remapLargeList.get(), 0, sizeof(uint32_t), s), "remap list");
     }
     m_bUseCameraCalibration = true;
 }
@@ -151,27 +128,27 @@ void CUDARGBDSensor::process(const float* h_depthFloat, const unsigned char* h_c
     const unsigned int W = c.adapterWidth, H = c.adapterHeight;
     hipStream_t s = (hipStream_t)m_stream;
     // ---- CUDARGBDAdapter::process :107-131
-    checkHip(hipMemcpyAsync(d_colorMapRaw, h_colorRGBX, 4 * (size_t)c.colorWidth * c.colorHeight, hipMemcpyHostToDevice, s), "upload colour");
-    check(vh_convert_color_raw_to_float4(d_colorMapFloat4, d_colorMapRaw, c.colorWidth, c.colorHeight, m_stream), "convertColorRawToFloat4");
-    if (c.colorWidth == W && c.colorHeight == H) check(vh_copy_float4_map(d_colorMapResampledFloat4, d_colorMapFloat4, W, H, m_stream), "copyFloat4Map");
-    else check(vh_resample_float4_map(d_colorMapResampledFloat4, W, H, d_colorMapFloat4, c.colorWidth, c.colorHeight, m_stream), "resampleFloat4Map");
-    checkHip(hipMemcpyAsync(d_depthMapFloat, h_depthFloat, sizeof(float) * (size_t)c.depthWidth * c.depthHeight, hipMemcpyHostToDevice, s), "upload depth");
-    check(vh_resample_float_map(d_depthMapResampledFloat, W, H, d_depthMapFloat, c.depthWidth, c.depthHeight, m_stream), "resampleFloatMap");
+    checkHip(hipMemcpyAsync(d_colorMapRaw.get(), h_colorRGBX, 4 * (size_t)c.colorWidth * c.colorHeight, hipMemcpyHostToDevice, s), "upload colour");
+    check(vh_convert_color_raw_to_float4(d_colorMapFloat4.get(), d_colorMapRaw.get(), c.colorWidth, c.colorHeight, m_stream), "convertColorRawToFloat4");
+    if (c.colorWidth == W && c.colorHeight == H) check(vh_copy_float4_map(d_colorMapResampledFloat4.get(), d_colorMapFloat4.get(), W, H, m_stream), "copyFloat4Map");
+    else check(vh_resample_float4_map(d_colorMapResampledFloat4.get(), W, H, d_colorMapFloat4.get(), c.colorWidth, c.colorHeight, m_stream), "resampleFloat4Map");
+    checkHip(hipMemcpyAsync(d_depthMapFloat.get(), h_depthFloat, sizeof(float) * (size_t)c.depthWidth * c.depthHeight, hipMemcpyHostToDevice, s), "upload depth");
+    check(vh_resample_float_map(d_depthMapResampledFloat.get(), W, H, d_depthMapFloat.get(), c.depthWidth, c.depthHeight, m_stream), "resampleFloatMap");
     // ---- CUDARGBDSensor::process :159-248
-    if (m_bFilterIntensityValues) check(vh_gauss_filter_float4_map(d_colorData, d_colorMapResampledFloat4, m_fBilateralFilterSigmaDIntensity, m_fBilateralFilterSigmaRIntensity, W, H, m_stream), "gaussFilterFloat4Map");
-    else check(vh_copy_float4_map(d_colorData, d_colorMapResampledFloat4, W, H, m_stream), "copyFloat4Map");
-    if (m_bFilterDepthValues) check(vh_gauss_filter_float_map(d_depthMapFilteredFloat, d_depthMapResampledFloat, m_fBilateralFilterSigmaD, m_fBilateralFilterSigmaR, W, H, m_stream), "gaussFilterFloatMap");
-    else check(vh_copy_float_map(d_depthMapFilteredFloat, d_depthMapResampledFloat, W, H, m_stream), "copyFloatMap");
+    if (m_bFilterIntensityValues) check(vh_gauss_filter_float4_map(d_colorData.get(), d_colorMapResampledFloat4.get(), m_fBilateralFilterSigmaDIntensity, m_fBilateralFilterSigmaRIntensity, W, H, m_stream), "gaussFilterFloat4Map");
+    else check(vh_copy_float4_map(d_colorData.get(), d_colorMapResampledFloat4.get(), W, H, m_stream), "copyFloat4Map");
+    if (m_bFilterDepthValues) check(vh_gauss_filter_float_map(d_depthMapFilteredFloat.get(), d_depthMapResampledFloat.get(), m_fBilateralFilterSigmaD, m_fBilateralFilterSigmaR, W, H, m_stream), "gaussFilterFloatMap");
+    else check(vh_copy_float_map(d_depthMapFilteredFloat.get(), d_depthMapResampledFloat.get(), W, H, m_stream), "copyFloatMap");
     // (the reference also calls setInvalidFloatMap on d_depthData here and overwrites it right away, :188-219)
     if (m_bUseCameraCalibration) { // RenderDepthMap into the custom render target, then copyToCuda(d_depthData, 0)
-        check(vh_view_raster(d_depthMapFilteredFloat, &m_remapParams, d_remapKeys, d_remapLargeList, m_stream), "remap: raster");
-        check(vh_view_resolve_depth(d_depthMapFilteredFloat, &m_remapParams, d_remapKeys, d_remapLargeList, d_depthData, m_stream), "remap: resolve");
+        check(vh_view_raster(d_depthMapFilteredFloat.get(), &m_remapParams, d_remapKeys.get(), d_remapLargeList.get(), m_stream), "remap: raster");
+        check(vh_view_resolve_depth(d_depthMapFilteredFloat.get(), &m_remapParams, d_remapKeys.get(), d_remapLargeList.get(), d_depthData.get(), m_stream), "remap: resolve");
     } else {
-        check(vh_copy_float_map(d_depthData, d_depthMapFilteredFloat, W, H, m_stream), "copyFloatMap");
+        check(vh_copy_float_map(d_depthData.get(), d_depthMapFilteredFloat.get(), W, H, m_stream), "copyFloatMap");
     }
-    check(vh_convert_color_to_intensity_float(d_intensityMapFilteredFloat, d_colorData, W, H, m_stream), "convertColorToIntensityFloat");
-    check(vh_convert_depth_float_to_camera_space_float4(d_cameraSpaceFloat4, d_depthData, &m_depthCameraParams, W, H, m_stream), "convertDepthFloatToCameraSpaceFloat4");
-    check(vh_compute_normals(d_normalMapFloat4, d_cameraSpaceFloat4, W, H, m_stream), "computeNormals");
+    check(vh_convert_color_to_intensity_float(d_intensityMapFilteredFloat.get(), d_colorData.get(), W, H, m_stream), "convertColorToIntensityFloat");
+    check(vh_convert_depth_float_to_camera_space_float4(d_cameraSpaceFloat4.get(), d_depthData.get(), &m_depthCameraParams, W, H, m_stream), "convertDepthFloatToCameraSpaceFloat4");
+    check(vh_compute_normals(d_normalMapFloat4.get(), d_cameraSpaceFloat4.get(), W, H, m_stream), "computeNormals");
     // the source buffers are the caller's: they may be reused as soon as this returns
     checkHip(hipStreamSynchronize(s), "CUDARGBDSensor::process");
     m_frameNumber++;

@@ -6,53 +6,41 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/vh_api.h"
+#include "../../include/vh_owners.hpp"
 
 #include <cstdint>
 #include <utility>
 #include <vector>
 
 struct VhStageTimer {
-    explicit VhStageTimer(int nStages) : totalMs(nStages, 0.0), count(nStages, 0), open(nStages, nullptr), pending(nStages) {}
-    ~VhStageTimer()
+    explicit VhStageTimer(int nStages) : totalMs(nStages, 0.0), count(nStages, 0), open(nStages), pending(nStages) {}
+    vh::Event get()
     {
-        for (auto& v : pending)
-            for (auto& p : v) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-        for (hipEvent_t e : pool) (void)hipEventDestroy(e);
-        for (hipEvent_t e : open)
-            if (e) (void)hipEventDestroy(e);
-    }
-    hipEvent_t get()
-    {
-        if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
-        hipEvent_t e = nullptr;
-        // timing only: device-scope release (a default event record makes the queue write back its caches and idles it
-        // for ~6 us, which distorts the frame rate being measured)
-        if (hipEventCreateWithFlags(&e, hipEventReleaseToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipEventCreate(&e);
-        }
+        // timing only: a device-scope release event (a default event record idles the queue for ~6 us, which distorts
+        // the frame rate being measured)
+        if (pool.empty()) return vh::makeEvent(true);
+        vh::Event e = std::move(pool.back());
+        pool.pop_back();
         return e;
     }
     void start(int stage, hipStream_t s)
     {
-        hipEvent_t e = get();
-        (void)hipEventRecord(e, s);
-        open[stage] = e;
+        open[stage] = get();
+        (void)hipEventRecord((hipEvent_t)open[stage].get(), s);
     }
     void stop(int stage, hipStream_t s)
     {
-        hipEvent_t e = get();
-        (void)hipEventRecord(e, s);
-        pending[stage].push_back(std::make_pair(open[stage], e));
-        open[stage] = nullptr;
+        vh::Event e = get();
+        (void)hipEventRecord((hipEvent_t)e.get(), s);
+        pending[stage].emplace_back(std::move(open[stage]), std::move(e));
     }
     // the NEXT kernel this thread launches (one of those that go through VH_LAUNCH_TIMED: the ray caster, computeNormals,
     // the fused integrate pass) is timed by its own dispatch time stamps: no record before or behind it
     void arm(int stage)
     {
-        hipEvent_t a = get(), b = get();
-        (void)vh_time_next_launch((void*)a, (void*)b);
-        pending[stage].push_back(std::make_pair(a, b));
+        vh::Event a = get(), b = get();
+        (void)vh_time_next_launch(a.get(), b.get());
+        pending[stage].emplace_back(std::move(a), std::move(b));
     }
     // waits for the stream and folds all finished pairs into the totals
     void resolve(hipStream_t s)
@@ -61,9 +49,9 @@ struct VhStageTimer {
         for (size_t st = 0; st < pending.size(); st++) {
             for (auto& p : pending[st]) {
                 float ms = 0.0f;
-                if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) { totalMs[st] += ms; count[st]++; }
-                pool.push_back(p.first);
-                pool.push_back(p.second);
+                if (hipEventElapsedTime(&ms, (hipEvent_t)p.first.get(), (hipEvent_t)p.second.get()) == hipSuccess) { totalMs[st] += ms; count[st]++; }
+                pool.push_back(std::move(p.first));
+                pool.push_back(std::move(p.second));
             }
             pending[st].clear();
         }
@@ -74,7 +62,7 @@ struct VhStageTimer {
     }
     std::vector<double> totalMs;
     std::vector<uint64_t> count;
-    std::vector<hipEvent_t> open;
-    std::vector<std::vector<std::pair<hipEvent_t, hipEvent_t>>> pending;
-    std::vector<hipEvent_t> pool;
+    std::vector<vh::Event> open;
+    std::vector<std::vector<std::pair<vh::Event, vh::Event>>> pending;
+    std::vector<vh::Event> pool;
 };

@@ -13,58 +13,103 @@
 
 #include "../../include/vh.hpp"
 #include "vh_host_util.hpp"
+#include "vh_params.hpp"
 
-namespace {
-inline void check(int code, const char* what)
+// ---------------------------------------------------------------------------
+// vh::IcpSolver: the plain solve, enqueued here for both its hosts
+// ---------------------------------------------------------------------------
+
+vh::IcpPyramid vh::icpPyramid(float* map0, float* normal0, const std::vector<DevicePtr<float>>& maps, const std::vector<DevicePtr<float>>& normals)
 {
-    if (code != 0) throw vh::Error(code, std::string(what) + ": " + vh_error_string(code));
-}
-inline void checkHip(hipError_t e, const char* what)
-{
-    if (e != hipSuccess) throw vh::Error(-(int)e, std::string(what) + ": " + hipGetErrorString(e));
-}
-float* allocFloats(size_t n, const char* what)
-{
-    float* p = nullptr;
-    checkHip(hipMalloc((void**)&p, sizeof(float) * (n ? n : 1)), what);
+    IcpPyramid p = {};
+    p.map[0] = map0;
+    p.normal[0] = normal0;
+    for (size_t i = 1; i < maps.size(); i++) { p.map[i] = maps[i].get(); p.normal[i] = normals[i].get(); }
     return p;
 }
-} // namespace
 
-CUDACameraTrackingMultiRes::CUDACameraTrackingMultiRes(unsigned int imageWidth, unsigned int imageHeight, unsigned int levels, vhStream_t stream)
-    : m_levels(levels), m_stream(stream), d_partials(nullptr), d_state(nullptr), d_deltaEstimate(nullptr)
+vh::IcpSolver::IcpSolver(unsigned int imageWidth, unsigned int imageHeight, unsigned int levels, const char* who)
 {
     if (levels == 0 || levels > VH_TRACKING_MAX_LEVELS || (imageWidth >> (levels - 1)) < 2 || (imageHeight >> (levels - 1)) < 2)
-        throw vh::Error(VH_ERR_BAD_ARGUMENT, "CUDACameraTrackingMultiRes: bad pyramid");
-    std::memset(&m_lastState, 0, sizeof(m_lastState));
+        throw vh::Error(VH_ERR_BAD_ARGUMENT, std::string(who) + ": bad pyramid");
     unsigned int fac = 1;
     for (unsigned int i = 0; i < levels; i++) { // :39-95
-        m_imageWidth.push_back(imageWidth / fac);
-        m_imageHeight.push_back(imageHeight / fac);
-        const size_t n = 4 * (size_t)m_imageWidth[i] * m_imageHeight[i];
-        d_correspondence.push_back(allocFloats(n, "d_correspondence"));
-        d_correspondenceNormal.push_back(allocFloats(n, "d_correspondenceNormal"));
-        d_input.push_back(i ? allocFloats(n, "d_input") : nullptr); // the finest level is the caller's maps
-        d_inputNormal.push_back(i ? allocFloats(n, "d_inputNormal") : nullptr);
-        d_model.push_back(i ? allocFloats(n, "d_model") : nullptr);
-        d_modelNormal.push_back(i ? allocFloats(n, "d_modelNormal") : nullptr);
+        width.push_back(imageWidth / fac);
+        height.push_back(imageHeight / fac);
+        const size_t n = 4 * (size_t)width[i] * height[i];
+        correspondence.push_back(deviceAlloc<float>(n, "d_correspondence"));
+        correspondenceNormal.push_back(deviceAlloc<float>(n, "d_correspondenceNormal"));
+        model.push_back(i ? deviceAlloc<float>(n, "d_model") : nullptr); // the finest level is the caller's maps
+        modelNormal.push_back(i ? deviceAlloc<float>(n, "d_modelNormal") : nullptr);
         fac *= 2;
     }
-    d_partials = allocFloats(30 * (size_t)vh_icp_num_partials(imageWidth, imageHeight), "d_partials");
-    checkHip(hipMalloc((void**)&d_state, sizeof(VhIcpState)), "VhIcpState");
-    d_deltaEstimate = allocFloats(16, "deltaEstimate");
+    partials = deviceAlloc<float>(30 * (size_t)vh_icp_num_partials(imageWidth, imageHeight), "d_partials");
+    state = deviceAlloc<VhIcpState>(1, "VhIcpState");
+    estimate = deviceAlloc<float>(16, "deltaEstimate");
+    ticket = deviceAlloc<uint32_t>(1, "tracking ticket");
 }
 
-CUDACameraTrackingMultiRes::~CUDACameraTrackingMultiRes()
+void vh::IcpSolver::coarserLevel(const IcpPyramid& p, unsigned int i, vhStream_t stream) const
 {
-    (void)hipStreamSynchronize((hipStream_t)m_stream);
-    for (auto* v : { &d_correspondence, &d_correspondenceNormal, &d_input, &d_inputNormal, &d_model, &d_modelNormal })
-        for (float* p : *v)
-            if (p) (void)hipFree(p);
-    if (d_partials) (void)hipFree(d_partials);
-    if (d_state) (void)hipFree(d_state);
-    if (d_deltaEstimate) (void)hipFree(d_deltaEstimate);
+    check(vh_resample_float4_map(p.map[i + 1], width[i + 1], height[i + 1], p.map[i], width[i], height[i], stream), "resampleFloat4Map");
+    check(vh_compute_normals(p.normal[i + 1], p.map[i + 1], width[i + 1], height[i + 1], stream), "computeNormals");
 }
+
+void vh::IcpSolver::align(const IcpPyramid& in, const IcpPyramid& mdl, const VhTrackingState& ts, const DepthCameraParams& cp, bool fusedStep,
+                          VhIcpResult* d_result, uint32_t tag, vhStream_t stream) const
+{
+    const int levels = (int)width.size();
+    if (fusedStep) checkHip(hipMemsetAsync(ticket.get(), 0, sizeof(uint32_t), (hipStream_t)stream), "tracking ticket");
+    check(vh_icp_begin(state.get(), estimate.get(), stream), "vh_icp_begin");
+    // the step that is the solve's last publishes the result itself: a publishing kernel behind it would be one more
+    // launch in a chain of dependent launches, and the step's last wave holds the state in its hands anyway
+    int lastLevel = -1;
+    for (int level = 0; level < levels && lastLevel < 0; level++)
+        if (ts.s_maxOuterIter[level]) lastLevel = level;
+    bool published = false;
+    for (int level = levels - 1; level >= 0; level--) {
+        const unsigned int W = width[level], H = height[level];
+        const float levelFactor = std::pow(2.0f, (float)level);
+        float *corr = correspondence[level].get(), *corrN = correspondenceNormal[level].get();
+        check(vh_icp_begin_level(state.get(), stream), "vh_icp_begin_level");
+        for (unsigned int outer = 0; outer < ts.s_maxOuterIter[level]; outer++) {
+            const unsigned int inner = ts.s_maxInnerIter[level];
+            if (fusedStep && inner == 1u) {
+                const bool last = level == lastLevel && outer + 1 == ts.s_maxOuterIter[level];
+                check(vh_icp_step(in.map[level], in.normal[level], mdl.map[level], mdl.normal[level], W, H, ts.s_distThres[level], ts.s_normalThres[level],
+                                  levelFactor, &cp, partials.get(), ticket.get(), state.get(), ts.s_angleTransThres[level], ts.s_distTransThres[level],
+                                  ts.s_residualEarlyOut[level], last ? d_result : nullptr, tag, stream), "vh_icp_step");
+                published = published || (last && d_result);
+                continue;
+            }
+            check(vh_icp_projective_correspondences(in.map[level], in.normal[level], mdl.map[level], mdl.normal[level], corr, corrN, W, H, ts.s_distThres[level],
+                                                    ts.s_normalThres[level], levelFactor, state.get(), &cp, stream), "projectiveCorrespondences");
+            for (unsigned int i = 0; i < inner; i++) {
+                check(vh_icp_build_linear_system(W, H, partials.get(), in.map[level], corr, corrN, state.get(), stream), "buildLinearSystem");
+                check(vh_icp_solve(state.get(), partials.get(), vh_icp_num_partials(W, H), ts.s_angleTransThres[level], ts.s_distTransThres[level],
+                                   ts.s_residualEarlyOut[level], i + 1 == inner, stream), "vh_icp_solve");
+            }
+        }
+    }
+    if (d_result && !published) check(vh_icp_publish(state.get(), d_result, tag, stream), "vh_icp_publish"); // (the last level is a three-kernel one, or no level iterates)
+}
+
+// ---------------------------------------------------------------------------
+// CUDACameraTrackingMultiRes
+// ---------------------------------------------------------------------------
+
+CUDACameraTrackingMultiRes::CUDACameraTrackingMultiRes(unsigned int imageWidth, unsigned int imageHeight, unsigned int levels, vhStream_t stream)
+    : m_levels(levels), m_stream(stream), m_icp(imageWidth, imageHeight, levels, "CUDACameraTrackingMultiRes")
+{
+    std::memset(&m_lastState, 0, sizeof(m_lastState));
+    for (unsigned int i = 0; i < levels; i++) {
+        const size_t n = 4 * (size_t)m_icp.width[i] * m_icp.height[i];
+        d_input.push_back(i ? vh::deviceAlloc<float>(n, "d_input") : nullptr);
+        d_inputNormal.push_back(i ? vh::deviceAlloc<float>(n, "d_inputNormal") : nullptr);
+    }
+}
+
+CUDACameraTrackingMultiRes::~CUDACameraTrackingMultiRes() { (void)hipStreamSynchronize((hipStream_t)m_stream); }
 
 bool CUDACameraTrackingMultiRes::isTrackingLost(const vh::mat4f& m) { return m.m[0] == -std::numeric_limits<float>::infinity(); }
 
@@ -73,37 +118,16 @@ vh::mat4f CUDACameraTrackingMultiRes::applyCT(float* dInput, float* dInputNormal
 {
     if (!dInput || !dInputNormals || !dModel || !dModelNormals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "applyCT: null map");
     hipStream_t s = (hipStream_t)m_stream;
-    d_input[0] = dInput; d_inputNormal[0] = dInputNormals;
-    d_model[0] = dModel; d_modelNormal[0] = dModelNormals;
-    // the pyramids, :256-263
-    for (unsigned int i = 0; i + 1 < m_levels; i++) {
-        check(vh_resample_float4_map(d_input[i + 1], m_imageWidth[i + 1], m_imageHeight[i + 1], d_input[i], m_imageWidth[i], m_imageHeight[i], m_stream), "resampleFloat4Map");
-        check(vh_compute_normals(d_inputNormal[i + 1], d_input[i + 1], m_imageWidth[i + 1], m_imageHeight[i + 1], m_stream), "computeNormals");
-        check(vh_resample_float4_map(d_model[i + 1], m_imageWidth[i + 1], m_imageHeight[i + 1], d_model[i], m_imageWidth[i], m_imageHeight[i], m_stream), "resampleFloat4Map");
-        check(vh_compute_normals(d_modelNormal[i + 1], d_model[i + 1], m_imageWidth[i + 1], m_imageHeight[i + 1], m_stream), "computeNormals");
+    const vh::IcpPyramid in = vh::icpPyramid(dInput, dInputNormals, d_input, d_inputNormal);
+    const vh::IcpPyramid mdl = vh::icpPyramid(dModel, dModelNormals, m_icp.model, m_icp.modelNormal);
+    for (unsigned int i = 0; i + 1 < m_levels; i++) { // the pyramids, :256-263
+        m_icp.coarserLevel(in, i, m_stream);
+        m_icp.coarserLevel(mdl, i, m_stream);
     }
-    checkHip(hipMemcpyAsync(d_deltaEstimate, deltaTransformEstimate.m, sizeof(float) * 16, hipMemcpyHostToDevice, s), "deltaEstimate");
-    check(vh_icp_begin(d_state, d_deltaEstimate, m_stream), "vh_icp_begin");
-    // coarse to fine, :265-279; align :291-321 with the loop exits taken on the device
-    for (int level = (int)m_levels - 1; level >= 0; level--) {
-        const unsigned int W = m_imageWidth[level], H = m_imageHeight[level];
-        const float levelFactor = std::pow(2.0f, (float)level);
-        check(vh_icp_begin_level(d_state, m_stream), "vh_icp_begin_level");
-        for (unsigned int outer = 0; outer < ts.s_maxOuterIter[level]; outer++) {
-            check(vh_icp_projective_correspondences(d_input[level], d_inputNormal[level], d_model[level], d_modelNormal[level], d_correspondence[level],
-                                                    d_correspondenceNormal[level], W, H, ts.s_distThres[level], ts.s_normalThres[level], levelFactor,
-                                                    d_state, &cp, m_stream), "projectiveCorrespondences");
-            const unsigned int inner = ts.s_maxInnerIter[level];
-            for (unsigned int i = 0; i < inner; i++) {
-                check(vh_icp_build_linear_system(W, H, d_partials, d_input[level], d_correspondence[level], d_correspondenceNormal[level], d_state, m_stream), "buildLinearSystem");
-                check(vh_icp_solve(d_state, d_partials, vh_icp_num_partials(W, H), ts.s_angleTransThres[level], ts.s_distTransThres[level],
-                                   ts.s_residualEarlyOut[level], i + 1 == inner, m_stream), "vh_icp_solve");
-            }
-        }
-    }
-    checkHip(hipMemcpyAsync(&m_lastState, d_state, sizeof(VhIcpState), hipMemcpyDeviceToHost, s), "VhIcpState");
+    checkHip(hipMemcpyAsync(m_icp.estimate.get(), deltaTransformEstimate.m, sizeof(float) * 16, hipMemcpyHostToDevice, s), "deltaEstimate");
+    m_icp.align(in, mdl, ts, cp, false, nullptr, 0u, m_stream); // three kernels an iteration; the outcome is copied back
+    checkHip(hipMemcpyAsync(&m_lastState, m_icp.state.get(), sizeof(VhIcpState), hipMemcpyDeviceToHost, s), "VhIcpState");
     checkHip(hipStreamSynchronize(s), "applyCT");
-    d_input[0] = d_inputNormal[0] = d_model[0] = d_modelNormal[0] = nullptr;
     vh::mat4f out;
     if (m_lastState.lost) {
         for (float& v : out.m) v = -std::numeric_limits<float>::infinity();
@@ -119,7 +143,7 @@ vh::mat4f CUDACameraTrackingMultiRes::applyCT(float* dInput, float* dInputNormal
 // ---------------------------------------------------------------------------
 
 CUDACameraTrackingMultiResRGBD::CUDACameraTrackingMultiResRGBD(unsigned int imageWidth, unsigned int imageHeight, unsigned int levels, vhStream_t stream)
-    : m_levels(levels), m_stream(stream), d_partials(nullptr), d_state(nullptr), d_deltaEstimate(nullptr)
+    : m_levels(levels), m_stream(stream)
 {
     if (levels == 0 || levels > VH_TRACKING_MAX_LEVELS || (imageWidth >> (levels - 1)) < 2 || (imageHeight >> (levels - 1)) < 2)
         throw vh::Error(VH_ERR_BAD_ARGUMENT, "CUDACameraTrackingMultiResRGBD: bad pyramid");
@@ -130,34 +154,24 @@ CUDACameraTrackingMultiResRGBD::CUDACameraTrackingMultiResRGBD(unsigned int imag
         m_imageWidth.push_back(imageWidth / fac);
         m_imageHeight.push_back(imageHeight / fac);
         const size_t n = (size_t)m_imageWidth[i] * m_imageHeight[i];
-        d_input.push_back(i ? allocFloats(4 * n, "d_input") : nullptr); // the finest level is the caller's maps
-        d_inputNormal.push_back(i ? allocFloats(4 * n, "d_inputNormal") : nullptr);
-        d_inputIntensity.push_back(allocFloats(n, "d_inputIntensity"));
-        d_inputIntensityFiltered.push_back(i ? allocFloats(n, "d_inputIntensityFiltered") : nullptr); // level 0: the unfiltered map (:267 copies it)
-        d_model.push_back(i ? allocFloats(4 * n, "d_model") : nullptr);
-        d_modelNormal.push_back(i ? allocFloats(4 * n, "d_modelNormal") : nullptr);
-        d_modelIntensity.push_back(allocFloats(n, "d_modelIntensity"));
-        d_modelIntensityFiltered.push_back(i ? allocFloats(n, "d_modelIntensityFiltered") : nullptr);
-        d_modelIntensityAndDerivatives.push_back(allocFloats(4 * n, "d_modelIntensityAndDerivatives"));
+        d_input.push_back(i ? vh::deviceAlloc<float>(4 * n, "d_input") : nullptr); // the finest level is the caller's maps
+        d_inputNormal.push_back(i ? vh::deviceAlloc<float>(4 * n, "d_inputNormal") : nullptr);
+        d_inputIntensity.push_back(vh::deviceAlloc<float>(n, "d_inputIntensity"));
+        d_inputIntensityFiltered.push_back(i ? vh::deviceAlloc<float>(n, "d_inputIntensityFiltered") : nullptr); // level 0: the unfiltered map (:267 copies it)
+        d_model.push_back(i ? vh::deviceAlloc<float>(4 * n, "d_model") : nullptr);
+        d_modelNormal.push_back(i ? vh::deviceAlloc<float>(4 * n, "d_modelNormal") : nullptr);
+        d_modelIntensity.push_back(vh::deviceAlloc<float>(n, "d_modelIntensity"));
+        d_modelIntensityFiltered.push_back(i ? vh::deviceAlloc<float>(n, "d_modelIntensityFiltered") : nullptr);
+        d_modelIntensityAndDerivatives.push_back(vh::deviceAlloc<float>(4 * n, "d_modelIntensityAndDerivatives"));
         partials = std::max(partials, vh_icp_rgbd_num_partials(m_imageWidth[i], m_imageHeight[i], i));
         fac *= 2;
     }
-    d_partials = allocFloats(30 * (size_t)partials, "d_partials");
-    checkHip(hipMalloc((void**)&d_state, sizeof(VhIcpStateRGBD)), "VhIcpStateRGBD");
-    d_deltaEstimate = allocFloats(16, "deltaEstimate");
+    d_partials = vh::deviceAlloc<float>(30 * (size_t)partials, "d_partials");
+    d_state = vh::deviceAlloc<VhIcpStateRGBD>(1, "VhIcpStateRGBD");
+    d_deltaEstimate = vh::deviceAlloc<float>(16, "deltaEstimate");
 }
 
-CUDACameraTrackingMultiResRGBD::~CUDACameraTrackingMultiResRGBD()
-{
-    (void)hipStreamSynchronize((hipStream_t)m_stream);
-    for (auto* v : { &d_input, &d_inputNormal, &d_inputIntensity, &d_inputIntensityFiltered, &d_model, &d_modelNormal, &d_modelIntensity,
-                     &d_modelIntensityFiltered, &d_modelIntensityAndDerivatives })
-        for (float* p : *v)
-            if (p) (void)hipFree(p);
-    if (d_partials) (void)hipFree(d_partials);
-    if (d_state) (void)hipFree(d_state);
-    if (d_deltaEstimate) (void)hipFree(d_deltaEstimate);
-}
+CUDACameraTrackingMultiResRGBD::~CUDACameraTrackingMultiResRGBD() { (void)hipStreamSynchronize((hipStream_t)m_stream); }
 
 bool CUDACameraTrackingMultiResRGBD::isTrackingLost(const vh::mat4f& m) { return m.m[0] == -std::numeric_limits<float>::infinity(); }
 
@@ -167,29 +181,29 @@ vh::mat4f CUDACameraTrackingMultiResRGBD::applyCT(float* dInput, float* dInputNo
 {
     if (!dInput || !dInputNormals || !dInputColor || !dModel || !dModelNormals || !dModelColor) throw vh::Error(VH_ERR_BAD_ARGUMENT, "applyCT: null map");
     hipStream_t s = (hipStream_t)m_stream;
-    d_input[0] = dInput; d_inputNormal[0] = dInputNormals;
-    d_model[0] = dModel; d_modelNormal[0] = dModelNormals;
+    const vh::IcpPyramid in = vh::icpPyramid(dInput, dInputNormals, d_input, d_inputNormal);
+    const vh::IcpPyramid mdl = vh::icpPyramid(dModel, dModelNormals, d_model, d_modelNormal);
     const unsigned int W0 = m_imageWidth[0], H0 = m_imageHeight[0];
     // the pyramids, :264-284
-    check(vh_convert_color_to_intensity_float(d_inputIntensity[0], dInputColor, W0, H0, m_stream), "convertColorToIntensityFloat");
-    check(vh_convert_color_to_intensity_float(d_modelIntensity[0], dModelColor, W0, H0, m_stream), "convertColorToIntensityFloat");
-    check(vh_compute_intensity_and_derivatives(d_modelIntensity[0], W0, H0, d_modelIntensityAndDerivatives[0], m_stream), "computeIntensityAndDerivatives");
+    check(vh_convert_color_to_intensity_float(d_inputIntensity[0].get(), dInputColor, W0, H0, m_stream), "convertColorToIntensityFloat");
+    check(vh_convert_color_to_intensity_float(d_modelIntensity[0].get(), dModelColor, W0, H0, m_stream), "convertColorToIntensityFloat");
+    check(vh_compute_intensity_and_derivatives(d_modelIntensity[0].get(), W0, H0, d_modelIntensityAndDerivatives[0].get(), m_stream), "computeIntensityAndDerivatives");
     const float sigmaD = 3.0f, sigmaR = 1.0f;
     for (unsigned int i = 0; i + 1 < m_levels; i++) {
         const unsigned int w = m_imageWidth[i], h = m_imageHeight[i], w1 = m_imageWidth[i + 1], h1 = m_imageHeight[i + 1];
-        check(vh_resample_float4_map(d_input[i + 1], w1, h1, d_input[i], w, h, m_stream), "resampleFloat4Map");
-        check(vh_compute_normals(d_inputNormal[i + 1], d_input[i + 1], w1, h1, m_stream), "computeNormals");
-        check(vh_resample_float_map(d_inputIntensity[i + 1], w1, h1, d_inputIntensity[i], w, h, m_stream), "resampleFloatMap");
-        check(vh_gauss_filter_float_map(d_inputIntensityFiltered[i + 1], d_inputIntensity[i + 1], sigmaD, sigmaR, w1, h1, m_stream), "gaussFilterFloatMap");
-        check(vh_resample_float4_map(d_model[i + 1], w1, h1, d_model[i], w, h, m_stream), "resampleFloat4Map");
-        check(vh_compute_normals(d_modelNormal[i + 1], d_model[i + 1], w1, h1, m_stream), "computeNormals");
-        check(vh_resample_float_map(d_modelIntensity[i + 1], w1, h1, d_modelIntensity[i], w, h, m_stream), "resampleFloatMap");
-        check(vh_gauss_filter_float_map(d_modelIntensityFiltered[i + 1], d_modelIntensity[i + 1], sigmaD, sigmaR, w1, h1, m_stream), "gaussFilterFloatMap");
-        check(vh_compute_intensity_and_derivatives(d_modelIntensityFiltered[i + 1], w1, h1, d_modelIntensityAndDerivatives[i + 1], m_stream),
+        check(vh_resample_float4_map(in.map[i + 1], w1, h1, in.map[i], w, h, m_stream), "resampleFloat4Map");
+        check(vh_compute_normals(in.normal[i + 1], in.map[i + 1], w1, h1, m_stream), "computeNormals");
+        check(vh_resample_float_map(d_inputIntensity[i + 1].get(), w1, h1, d_inputIntensity[i].get(), w, h, m_stream), "resampleFloatMap");
+        check(vh_gauss_filter_float_map(d_inputIntensityFiltered[i + 1].get(), d_inputIntensity[i + 1].get(), sigmaD, sigmaR, w1, h1, m_stream), "gaussFilterFloatMap");
+        check(vh_resample_float4_map(mdl.map[i + 1], w1, h1, mdl.map[i], w, h, m_stream), "resampleFloat4Map");
+        check(vh_compute_normals(mdl.normal[i + 1], mdl.map[i + 1], w1, h1, m_stream), "computeNormals");
+        check(vh_resample_float_map(d_modelIntensity[i + 1].get(), w1, h1, d_modelIntensity[i].get(), w, h, m_stream), "resampleFloatMap");
+        check(vh_gauss_filter_float_map(d_modelIntensityFiltered[i + 1].get(), d_modelIntensity[i + 1].get(), sigmaD, sigmaR, w1, h1, m_stream), "gaussFilterFloatMap");
+        check(vh_compute_intensity_and_derivatives(d_modelIntensityFiltered[i + 1].get(), w1, h1, d_modelIntensityAndDerivatives[i + 1].get(), m_stream),
               "computeIntensityAndDerivatives");
     }
-    checkHip(hipMemcpyAsync(d_deltaEstimate, deltaTransformEstimate.m, sizeof(float) * 16, hipMemcpyHostToDevice, s), "deltaEstimate");
-    check(vh_icp_rgbd_begin(d_state, d_deltaEstimate, m_stream), "vh_icp_rgbd_begin");
+    checkHip(hipMemcpyAsync(d_deltaEstimate.get(), deltaTransformEstimate.m, sizeof(float) * 16, hipMemcpyHostToDevice, s), "deltaEstimate");
+    check(vh_icp_rgbd_begin(d_state.get(), d_deltaEstimate.get(), m_stream), "vh_icp_rgbd_begin");
     // coarse to fine, :289-321; align :329-353 with the loop exits taken on the device
     for (int level = (int)m_levels - 1; level >= 0; level--) {
         const unsigned int W = m_imageWidth[level], H = m_imageHeight[level];
@@ -204,19 +218,18 @@ vh::mat4f CUDACameraTrackingMultiResRGBD::applyCT(float* dInput, float* dInputNo
         prm.colorGradientMin = ts.s_colorGradientMin[level];
         prm.colorThres = ts.s_colorThres[level];
         prm.level = (uint32_t)level;
-        const float* inIntensity = level ? d_inputIntensityFiltered[level] : d_inputIntensity[0];
+        const float* inIntensity = level ? d_inputIntensityFiltered[level].get() : d_inputIntensity[0].get();
         const uint32_t nP = vh_icp_rgbd_num_partials(W, H, (uint32_t)level);
-        check(vh_icp_begin_level(&d_state->icp, m_stream), "vh_icp_begin_level");
+        check(vh_icp_begin_level(&d_state.get()->icp, m_stream), "vh_icp_begin_level");
         for (unsigned int outer = 0; outer < ts.base.s_maxOuterIter[level]; outer++) {
-            check(vh_icp_rgbd_build_linear_system(W, H, d_partials, d_input[level], d_inputNormal[level], inIntensity, d_model[level], d_modelNormal[level],
-                                                  d_modelIntensityAndDerivatives[level], &prm, d_state, m_stream), "computeNormalEquations");
-            check(vh_icp_rgbd_solve(d_state, d_partials, nP, ts.base.s_angleTransThres[level], ts.base.s_distTransThres[level],
+            check(vh_icp_rgbd_build_linear_system(W, H, d_partials.get(), in.map[level], in.normal[level], inIntensity, mdl.map[level], mdl.normal[level],
+                                                  d_modelIntensityAndDerivatives[level].get(), &prm, d_state.get(), m_stream), "computeNormalEquations");
+            check(vh_icp_rgbd_solve(d_state.get(), d_partials.get(), nP, ts.base.s_angleTransThres[level], ts.base.s_distTransThres[level],
                                     ts.base.s_residualEarlyOut[level], m_stream), "vh_icp_rgbd_solve");
         }
     }
-    checkHip(hipMemcpyAsync(&m_lastState, d_state, sizeof(VhIcpStateRGBD), hipMemcpyDeviceToHost, s), "VhIcpStateRGBD");
+    checkHip(hipMemcpyAsync(&m_lastState, d_state.get(), sizeof(VhIcpStateRGBD), hipMemcpyDeviceToHost, s), "VhIcpStateRGBD");
     checkHip(hipStreamSynchronize(s), "applyCT");
-    d_input[0] = d_inputNormal[0] = d_model[0] = d_modelNormal[0] = nullptr;
     vh::mat4f out;
     if (m_lastState.icp.lost) {
         for (float& v : out.m) v = -std::numeric_limits<float>::infinity();
@@ -232,31 +245,6 @@ vh::mat4f CUDACameraTrackingMultiResRGBD::applyCT(float* dInput, float* dInputNo
 // ---------------------------------------------------------------------------
 
 namespace {
-void stripT(std::string& s)
-{
-    const std::string junk = " \t\";";
-    while (!s.empty() && junk.find(s.front()) != std::string::npos) s.erase(s.begin());
-    while (!s.empty() && junk.find(s.back()) != std::string::npos) s.pop_back();
-}
-std::map<std::string, std::string> readValues(std::istream& in)
-{
-    std::map<std::string, std::string> values;
-    std::string line;
-    while (std::getline(in, line)) {
-        if (!line.empty() && line.back() == '\r') line.pop_back();
-        for (const char* c : { "//", "#", ";" }) {
-            const size_t at = line.find(c);
-            if (at != std::string::npos) line = line.substr(0, at);
-        }
-        stripT(line);
-        const size_t sep = line.find('=');
-        if (line.empty() || sep == std::string::npos) continue;
-        std::string name = line.substr(0, sep), value = line.substr(sep + 1);
-        stripT(name); stripT(value);
-        if (!name.empty()) values[name] = value;
-    }
-    return values;
-}
 void parseTracking(const std::map<std::string, std::string>& values, VhTrackingState* out)
 {
     std::memset(out, 0, sizeof(*out));
@@ -303,7 +291,9 @@ int vh_tracking_state_read(const char* filename, VhTrackingState* out)
     if (!filename || !out) return VH_ERR_BAD_ARGUMENT;
     std::ifstream f(filename);
     if (!f.is_open()) return VH_ERR_IO;
-    parseTracking(readValues(f), out);
+    vh::ParamValues values;
+    vh::parseStream(f, values);
+    parseTracking(values, out);
     return VH_OK;
 }
 
@@ -311,7 +301,9 @@ int vh_tracking_state_parse(const char* text, VhTrackingState* out)
 {
     if (!text || !out) return VH_ERR_BAD_ARGUMENT;
     std::istringstream in(text);
-    parseTracking(readValues(in), out);
+    vh::ParamValues values;
+    vh::parseStream(in, values);
+    parseTracking(values, out);
     return VH_OK;
 }
 
@@ -320,7 +312,9 @@ int vh_tracking_state_rgbd_read(const char* filename, VhTrackingStateRGBD* out)
     if (!filename || !out) return VH_ERR_BAD_ARGUMENT;
     std::ifstream f(filename);
     if (!f.is_open()) return VH_ERR_IO;
-    parseTrackingRGBD(readValues(f), out);
+    vh::ParamValues values;
+    vh::parseStream(f, values);
+    parseTrackingRGBD(values, out);
     return VH_OK;
 }
 
@@ -328,7 +322,9 @@ int vh_tracking_state_rgbd_parse(const char* text, VhTrackingStateRGBD* out)
 {
     if (!text || !out) return VH_ERR_BAD_ARGUMENT;
     std::istringstream in(text);
-    parseTrackingRGBD(readValues(in), out);
+    vh::ParamValues values;
+    vh::parseStream(in, values);
+    parseTrackingRGBD(values, out);
     return VH_OK;
 }
 

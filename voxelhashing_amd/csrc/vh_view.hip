@@ -345,20 +345,6 @@ bool viewParamsValid(const VhViewParams* p)
            (uint64_t)p->depthWidth * p->depthHeight < (1ull << 30) && (uint64_t)p->screenWidth * p->screenHeight < (1ull << 31);
 }
 
-inline void check(int code, const char* what)
-{
-    if (code != 0) throw vh::Error(code, std::string(what) + ": " + vh_error_string(code));
-}
-inline void checkHip(hipError_t e, const char* what)
-{
-    if (e != hipSuccess) throw vh::Error(-(int)e, std::string(what) + ": " + hipGetErrorString(e));
-}
-template <class T> void reallocate(T*& p, size_t n, const char* what)
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    checkHip(hipMalloc((void**)&p, sizeof(T) * (n ? n : 1)), what);
-}
 
 } // namespace
 
@@ -414,29 +400,25 @@ int vh_phong(const float* d_positions4, const float* d_normals4, const float* d_
 
 RGBDRenderer::RGBDRenderer(vhStream_t stream) : m_stream(stream) {}
 
-RGBDRenderer::~RGBDRenderer()
-{
-    for (void* p : { (void*)d_keys, (void*)d_largeList, (void*)d_depth, (void*)d_positions, (void*)d_normals, (void*)d_colors })
-        if (p) (void)hipFree(p);
-}
+RGBDRenderer::~RGBDRenderer() = default;
 
 void RGBDRenderer::resize(unsigned int width, unsigned int height, unsigned int screenWidth, unsigned int screenHeight)
 {
     const hipStream_t s = (hipStream_t)m_stream;
     if (width != m_width || height != m_height) { // OnResize: the list is sized by the depth map
-        reallocate(d_largeList, vh_view_large_list_words(width, height), "RGBDRenderer: list");
-        checkHip(hipMemsetAsync(d_largeList, 0, sizeof(uint32_t), s), "RGBDRenderer: list");
+        d_largeList = vh::deviceAlloc<uint32_t>(vh_view_large_list_words(width, height), "RGBDRenderer: list");
+        checkHip(hipMemsetAsync(d_largeList.get(), 0, sizeof(uint32_t), s), "RGBDRenderer: list");
         m_width = width;
         m_height = height;
     }
     if (screenWidth != m_screenWidth || screenHeight != m_screenHeight) {
         const size_t n = (size_t)screenWidth * screenHeight;
-        reallocate(d_keys, n, "RGBDRenderer: keys");
-        checkHip(hipMemsetAsync(d_keys, 0xff, sizeof(uint64_t) * n, s), "RGBDRenderer: keys");
-        reallocate(d_depth, n, "RGBDRenderer: depth");
-        reallocate(d_positions, 4 * n, "RGBDRenderer: positions");
-        reallocate(d_normals, 4 * n, "RGBDRenderer: normals");
-        reallocate(d_colors, 4 * n, "RGBDRenderer: colors");
+        d_keys = vh::deviceAlloc<uint64_t>(n, "RGBDRenderer: keys");
+        checkHip(hipMemsetAsync(d_keys.get(), 0xff, sizeof(uint64_t) * n, s), "RGBDRenderer: keys");
+        d_depth = vh::deviceAlloc<float>(n, "RGBDRenderer: depth");
+        d_positions = vh::deviceAlloc<float>(4 * n, "RGBDRenderer: positions");
+        d_normals = vh::deviceAlloc<float>(4 * n, "RGBDRenderer: normals");
+        d_colors = vh::deviceAlloc<float>(4 * n, "RGBDRenderer: colors");
         m_screenWidth = screenWidth;
         m_screenHeight = screenHeight;
     }
@@ -459,27 +441,23 @@ void RGBDRenderer::RenderDepthMap(const float* d_depthMap, const float* d_colorM
     p.depthThreshLin = depthThreshLin;
     if (!d_depthMap || !d_colorMap || !viewParamsValid(&p)) throw vh::Error(VH_ERR_BAD_ARGUMENT, "RenderDepthMap: bad arguments");
     resize(width, height, screenWidth, screenHeight);
-    check(vh_view_raster(d_depthMap, &p, d_keys, d_largeList, m_stream), "RenderDepthMap: raster");
-    check(vh_view_resolve(d_depthMap, d_colorMap, &p, d_keys, d_largeList, d_depth, d_positions, d_normals, d_colors, m_stream), "RenderDepthMap: resolve");
+    check(vh_view_raster(d_depthMap, &p, d_keys.get(), d_largeList.get(), m_stream), "RenderDepthMap: raster");
+    check(vh_view_resolve(d_depthMap, d_colorMap, &p, d_keys.get(), d_largeList.get(), d_depth.get(), d_positions.get(), d_normals.get(), d_colors.get(), m_stream), "RenderDepthMap: resolve");
 }
 
 PhongLighting::PhongLighting(const VhPhongLight& light, vhStream_t stream) : m_light(light), m_stream(stream) {}
 
-PhongLighting::~PhongLighting()
-{
-    if (d_colors) (void)hipFree(d_colors);
-    if (d_rgba8) (void)hipFree(d_rgba8);
-}
+PhongLighting::~PhongLighting() = default;
 
 void PhongLighting::render(const float* d_positions, const float* d_normals, const float* d_colorsIn, bool useMaterial, unsigned int width,
                            unsigned int height, bool rgba8)
 {
     const unsigned int n = width * height;
     if (n != m_numPixels) {
-        reallocate(d_colors, 4 * (size_t)n, "PhongLighting: colors");
-        reallocate(d_rgba8, 4 * (size_t)n, "PhongLighting: rgba8");
+        d_colors = vh::deviceAlloc<float>(4 * (size_t)n, "PhongLighting: colors");
+        d_rgba8 = vh::deviceAlloc<uint8_t>(4 * (size_t)n, "PhongLighting: rgba8");
         m_numPixels = n;
     }
-    check(vh_phong(d_positions, d_normals, d_colorsIn, n, useMaterial ? 1 : 0, &m_light, d_colors, rgba8 ? d_rgba8 : nullptr, 1, m_stream),
+    check(vh_phong(d_positions, d_normals, d_colorsIn, n, useMaterial ? 1 : 0, &m_light, d_colors.get(), rgba8 ? d_rgba8.get() : nullptr, 1, m_stream),
           "PhongLighting::render");
 }

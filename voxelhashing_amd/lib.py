@@ -116,7 +116,6 @@ PROTOTYPES = {
     "vh_reconstruction_get_stats": (C.c_int, [_VP, P(T.ReconstructionStats)]),
     "vh_reconstruction_reset": (C.c_int, [_VP]),
     "vh_convert_color_raw_to_float4": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _VP]),
-    "vh_upload_frame": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP]),
     "vh_ingest_frame": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _VP]),
     "vh_resample_float_map": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP]),
     "vh_resample_float4_map": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP]),
