@@ -93,6 +93,39 @@ struct IcpSolver {
                bool fusedStep, VhIcpResult* d_result, uint32_t tag, vhStream_t stream) const;
 };
 
+// The RGB-D solve (DSC/CUDACameraTrackingMultiResRGBD.cpp:239-353) as its two hosts enqueue it:
+// CUDACameraTrackingMultiResRGBD::applyCT and Reconstruction's tracked frame (vh_tracking.cpp).
+// The intensity maps the solve reads of the input, per level: the unfiltered map on level 0 (:267 copies it), the
+// Gauss-filtered one above.  Owns nothing.
+struct IcpIntensityPyramid {
+    float* intensity[VH_TRACKING_MAX_LEVELS]; // level i from level i - 1 (resampleFloatMap)
+    float* filtered[VH_TRACKING_MAX_LEVELS];  // levels >= 1 (element 0 is not looked at)
+};
+IcpIntensityPyramid icpIntensityPyramid(const std::vector<DevicePtr<float>>& intensity, const std::vector<DevicePtr<float>>& filtered);
+// what of a solve does not depend on the frame, and its enqueue
+struct IcpSolverRGBD {
+    IcpSolverRGBD(unsigned int imageWidth, unsigned int imageHeight, unsigned int levels, const char* who); // throws who + ": bad pyramid"
+    std::vector<unsigned int> width, height;                                        // per level
+    std::vector<DevicePtr<float>> model, modelNormal;                               // levels >= 1 (element 0 stays empty)
+    std::vector<DevicePtr<float>> modelIntensity, modelIntensityAndDerivatives;     // every level
+    std::vector<DevicePtr<float>> modelIntensityFiltered;                           // levels >= 1
+    DevicePtr<float> partials;
+    DevicePtr<float> estimate;        // the 4x4 delta a solve starts from: the caller writes it
+    DevicePtr<VhIcpStateRGBD> state;  // where a solve leaves its outcome
+    DevicePtr<uint32_t> ticket;       // vh_icp_rgbd_step's count of finished workgroups
+    // The input half of the pyramids (:264-284) on `stream`: level-0 intensity from the float4 colour map, then per level
+    // resampleFloat4Map + computeNormals of the positions and resampleFloatMap + gaussFilterFloatMap (3, 1) of the intensity.
+    void inputPyramid(const IcpPyramid& input, const float* d_inputColor, const IcpIntensityPyramid& intensity, vhStream_t stream) const;
+    // The model half: intensity of the ray cast's colours and its derivatives, then per level the positions, normals,
+    // intensity, Gauss filter and derivatives.
+    void modelPyramid(const IcpPyramid& model, const float* d_modelColor, vhStream_t stream) const;
+    // Coarse to fine from `estimate` (:289-353, the loop exits taken on the device).  fusedStep: an iteration is one launch
+    // (vh_icp_rgbd_step) instead of two.  d_result: the outcome is also published there (mapped host memory) with `tag`
+    // stored behind it -- by the last step itself if that is a fused one, by vh_icp_publish otherwise.
+    void align(const IcpPyramid& input, const IcpIntensityPyramid& inputIntensity, const IcpPyramid& model, const VhTrackingStateRGBD& settings,
+               const DepthCameraParams& depthCameraParams, bool fusedStep, VhIcpResult* d_result, uint32_t tag, vhStream_t stream) const;
+};
+
 } // namespace vh
 
 struct VhStageTimer; // opaque: per-stage HIP event pairs
@@ -546,6 +579,9 @@ public:
     // the scene's last pose, align the input to it and integrate at lastRigidTransform * delta; a lost frame is not
     // integrated.  The host waits once per tracked frame, for the ICP result in mapped host memory.
     void setTracking(const VhTrackingState& settings);
+    // The same with the RGB-D tracker (CUDACameraTrackingMultiResRGBD: depth + photometric ICP, one vh_icp_rgbd_step per
+    // iteration) in place of the plain one; one of the two, once.  Every frame then needs a colour map.
+    void setTrackingRGBD(const VhTrackingStateRGBD& settings);
     bool isTracking() const { return m_tracking; }
     // frames integrated at a pose the loop tracked itself / frames on which tracking was lost, since creation or reset
     unsigned long long getNumTrackedFrames() const { return m_trackedFrames; }
@@ -608,7 +644,13 @@ private:
     std::vector<vh::DevicePtr<float>> d_trkInput[kStagingSlots], d_trkInputNormal[kStagingSlots];
     vh::Mapped<VhIcpResult> m_trkResult;
     uint32_t m_trkTag;
-    void inputPyramid(unsigned int slot, const float* d_depth, vhStream_t stream);
+    // the RGB-D tracker in place of m_icp (m_tracking is set for either): its solve, and the input's intensity levels per
+    // staging slot beside the positions and normals above
+    VhTrackingStateRGBD m_trackingStateRGBD;
+    std::unique_ptr<vh::IcpSolverRGBD> m_icpRGBD;
+    std::vector<vh::DevicePtr<float>> d_trkIntensity[kStagingSlots], d_trkIntensityFiltered[kStagingSlots];
+    void checkCanTrack(const char* who) const;
+    void inputPyramid(unsigned int slot, const float* d_depth, const float* d_color, vhStream_t stream);
     void frameTracked(const SequenceFrame& f);
 };
 
@@ -855,12 +897,8 @@ public:
 private:
     unsigned int m_levels;
     vhStream_t m_stream;
-    std::vector<unsigned int> m_imageWidth, m_imageHeight;
-    std::vector<vh::DevicePtr<float>> d_input, d_inputNormal, d_inputIntensity, d_inputIntensityFiltered; // (levels >= 1 of the first two)
-    std::vector<vh::DevicePtr<float>> d_model, d_modelNormal, d_modelIntensity, d_modelIntensityFiltered, d_modelIntensityAndDerivatives;
-    vh::DevicePtr<float> d_partials;
-    vh::DevicePtr<VhIcpStateRGBD> d_state;
-    vh::DevicePtr<float> d_deltaEstimate;
+    vh::IcpSolverRGBD m_icp;
+    std::vector<vh::DevicePtr<float>> d_input, d_inputNormal, d_inputIntensity, d_inputIntensityFiltered; // (levels >= 1 of all but the third)
     VhIcpStateRGBD m_lastState;
 };
 

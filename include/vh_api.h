@@ -384,6 +384,13 @@ int vh_reconstruction_run_raw_ahead(VhReconstruction* r, const VhRawSequenceFram
  * frame on which tracking is lost is not integrated (vh_reconstruction_get_tracking_stats).  The host waits once per tracked frame, for the ICP
  * result in mapped host memory; it makes no blocking HIP call. */
 int vh_reconstruction_set_tracking(VhReconstruction* r, const VhTrackingState* settings);
+/* The same with the RGB-D tracker (depth + photometric ICP, CUDACameraTrackingMultiResRGBD; one vh_icp_rgbd_step per
+ * outer iteration) in place of the plain one: once, before the first frame, and one of the two only (either after the
+ * other is VH_ERR_BAD_ARGUMENT).  Same preconditions.  The intensity pyramid of the input is made from the frame's float4
+ * colour map (the staging slot's after ingest and the colour filter, or the caller's for resident frames) on the copy
+ * stream, the model's from the ray cast's colours on the loop's stream.  Every frame needs a colour map: a frame without
+ * one, or a raw format with colorChannels = 0, is VH_ERR_BAD_ARGUMENT. */
+int vh_reconstruction_set_tracking_rgbd(VhReconstruction* r, const VhTrackingStateRGBD* settings);
 /* the poses of frames [first, first + n) fed since creation / reset, 16 floats each: the pose the frame was integrated
  * at; every entry -inf for a frame that was not (tracking lost, invalid recorded pose).  Untracked loops report the
  * recorded poses.  Waits for nothing: the poses are the host's. */
@@ -563,6 +570,17 @@ int vh_icp_rgbd_build_linear_system(uint32_t width, uint32_t height, float* d_pa
                                     vhStream_t stream);
 int vh_icp_rgbd_solve(VhIcpStateRGBD* d_state, const float* d_partials, uint32_t numPartials, float angleThres, float distThres, float earlyOutResidual,
                       vhStream_t stream);
+/* One outer iteration of the RGB-D align in ONE launch: what vh_icp_rgbd_build_linear_system + vh_icp_rgbd_solve do, the
+ * VhIcpStateRGBD afterwards equal to theirs bit for bit.  d_partials: 30 * vh_icp_rgbd_num_partials(width, height,
+ * params->level) floats.  d_ticket: a device word of the caller's that is 0 before every launch -- clear it on the stream
+ * (vh_memset) where vh_icp_rgbd_begin runs; the step leaves it 0.  publish (may be NULL): mapped host memory that
+ * receives d_state->icp's result after this step, its tag last (VhIcpResult); a step the state skips (lost / level done)
+ * publishes the state as it stands.  A solve whose last step is not this one publishes with
+ * vh_icp_publish(&d_state->icp, ...). */
+int vh_icp_rgbd_step(uint32_t width, uint32_t height, float* d_partials, uint32_t* d_ticket, const float* d_input4, const float* d_inputNormals4,
+                     const float* d_inputIntensity, const float* d_target4, const float* d_targetNormals4, const float* d_targetIntensityAndDerivatives4,
+                     const VhIcpRGBDParams* params, VhIcpStateRGBD* d_state, float angleThres, float distThres, float earlyOutResidual, VhIcpResult* publish,
+                     uint32_t tag, vhStream_t stream);
 /* GlobalCameraTrackingState::readMembers with the four RGB-D keys (s_weightsDepth, s_weightsColor, s_colorGradientMin,
  * s_colorThres); the other members exactly as vh_tracking_state_read returns them */
 int vh_tracking_state_rgbd_read(const char* filename, VhTrackingStateRGBD* out);

@@ -13,6 +13,8 @@ the two legs alternating --repeats times (tools/bench_ingest.py's scheme): (a) t
 quantised to what a sensor records (16-bit millimetres, 0 = no measurement; RGB bytes), leg (a) gets them as the float
 depth + RGBX a SensorDataReader would hand over.  One JSON line: medians and ranges of both, icp_ms_per_frame of (a), the
 drift of both, the largest difference between the two legs' poses; exit status 1 when (b)'s median is below (a)'s.
+--native --rgbd: the same two legs with the RGB-D tracker (CUDACameraTrackingMultiResRGBD.applyCT against
+engine.Reconstruction.setTrackingRGBD), default RGB-D settings.
 """
 import argparse
 import ctypes as C
@@ -88,7 +90,11 @@ def native_against_python(args, frames, truth, hp, cp, rp, W, H):
     ray = E.CUDARayCastSDF(rp)
     loop = E.Reconstruction(scene, ray, None, cp, E.Reconstruction.defaultOptions(s_framesOnHost=1))
     loop.setRawFormat((W, H), (W, H), 1000.0, 3)
-    loop.setTracking(T.make_tracking_state())
+    kind = "rgbd" if args.rgbd else "f5"
+    if args.rgbd:
+        loop.setTrackingRGBD(T.make_tracking_state_rgbd())
+    else:
+        loop.setTracking(T.make_tracking_state())
     ds, cs = d16.array[0].nbytes, rgb.array[0].nbytes
     seq = E.Reconstruction.makeRawFrames([np.eye(4, dtype=np.float32)] * n, [d16.ptr + k * ds for k in range(n)], [rgb.ptr + k * cs for k in range(n)])
 
@@ -109,10 +115,11 @@ def native_against_python(args, frames, truth, hp, cp, rp, W, H):
     py, nat = [], []
     for _ in range(args.repeats):  # alternating
         if args.only != "native":
-            py.append(run(args, "f5", quantised, truth, hp, cp, rp, W, H, quiet=True))
+            py.append(run(args, kind, quantised, truth, hp, cp, rp, W, H, quiet=True))
         if args.only != "python":
             nat.append(native_leg())
-    out = dict(bench="tracking, Python loop against the native tracked loop", unit="frames/s", frames=n - 1, repeats=args.repeats)
+    out = dict(bench="tracking, Python loop against the native tracked loop", tracker="RGB-D ICP" if args.rgbd else "projective ICP", unit="frames/s",
+               frames=n - 1, repeats=args.repeats)
     t0 = np.asarray(truth[0], np.float64).reshape(4, 4)
     if py:
         last = py[-1]
@@ -133,7 +140,8 @@ def native_against_python(args, frames, truth, hp, cp, rp, W, H):
         out["largest_pose_difference"] = max(float(np.abs(x - np.asarray(y, np.float64).reshape(4, 4)).max())
                                              for x, y in zip(in_world, py[-1]["poses"]) if x is not None and y is not None)
         out["gate_native_not_slower"] = bool(b["median"] >= a["median"])
-    out["config"] = dict(workload=f"S3 orbit, {W}x{H}, P4 voxels, 3 pyramid levels, reference default tracking settings, frames quantised to 16-bit "
+    settings = "reference default tracking settings" + (" with their colour keys" if args.rgbd else "")
+    out["config"] = dict(workload=f"S3 orbit, {W}x{H}, P4 voxels, 3 pyramid levels, {settings}, frames quantised to 16-bit "
                                   "millimetres + RGB bytes; Python loop: float depth + RGBX from pageable host memory, native loop: raw frames from pinned "
                                   "host memory; online alloc")
     print(json.dumps(out))

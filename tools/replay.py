@@ -16,8 +16,8 @@ map is rendered into the colour camera with the `.sens` file's extrinsic (unless
 16-bit depth + RGB frames decoded into pinned memory, converted, resampled and filtered on the device, no host wait per
 frame.  It is for recorded poses (s_binaryDumpSensorUseTrajectory = true, ...OnlyInit = false) and says why when the
 configuration needs the Python loop (ICP tracking, --record, --render-to, camera calibration).  With --native-tracking the
-native loop tracks the camera itself where the parameter file asks for it (s_binaryDumpSensorUseTrajectory = false, plain
-projective ICP): one host wait per frame, for the pose; the RGB-D tracker still needs the Python loop."""
+native loop tracks the camera itself where the parameter file asks for it (s_binaryDumpSensorUseTrajectory = false): one
+host wait per frame, for the pose; with plain projective ICP, or with --rgbd-tracking with the RGB-D tracker."""
 import argparse
 import json
 import os
@@ -41,7 +41,7 @@ def main():
     ap.add_argument("--camera-calibration", action="store_true", help="s_bUseCameraCalibration: remap depth into the colour camera")
     ap.add_argument("--native", action="store_true", help="play through the native frame loop, fed with raw frames")
     ap.add_argument("--batch", type=int, default=64, help="--native: frames decoded and handed over per call")
-    ap.add_argument("--native-tracking", action="store_true", help="--native: let the native loop track the camera (plain ICP) when the poses are not recorded")
+    ap.add_argument("--native-tracking", action="store_true", help="--native: let the native loop track the camera (plain ICP, or RGB-D ICP with --rgbd-tracking) when the poses are not recorded")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -62,12 +62,12 @@ def main():
     rec = R.Reconstruction(g, t, args.sens or None, use_rgbd_tracking=args.rgbd_tracking, render_state=rs, calibration_state=cs)
     if args.native:  # the loop, its pinned buffers and the file, before the clock (the Python loop's reader has loaded its file above)
         try:
-            rec.prepare_native(args.batch, tracking=args.native_tracking)
+            rec.prepare_native(args.batch, tracking=args.native_tracking, tracking_rgbd=args.native_tracking and args.rgbd_tracking)
         except ValueError as e:
             raise SystemExit(str(e))
     t0 = time.perf_counter()
     if args.native:
-        n = rec.run_native(args.max_frames, batch=args.batch, tracking=args.native_tracking)
+        n = rec.run_native(args.max_frames, batch=args.batch, tracking=args.native_tracking, tracking_rgbd=args.native_tracking and args.rgbd_tracking)
         rec.native.synchronize()
     else:
         n = rec.run(args.max_frames)

@@ -3862,16 +3862,27 @@ VHD float angle_axis_angle(const float* R)
         q[1] = (R[2] - R[6]) * t;
         q[2] = (R[3] - R[1]) * t;
     } else {
+        // (entries are selected, not indexed, and the vector part is summed from named values: an index known only at
+        // run time would put R and q into scratch memory)
+        auto r = [&](int at) {
+            float v = R[0];
+#pragma unroll
+            for (int n = 1; n < 9; n++) v = at == n ? R[n] : v;
+            return v;
+        };
         int i = 0;
         if (R[4] > R[0]) i = 1;
-        if (R[8] > R[4 * i]) i = 2;
+        if (R[8] > r(4 * i)) i = 2;
         const int j = (i + 1) % 3, k = (j + 1) % 3;
-        float t = sqrtf(R[4 * i] - R[4 * j] - R[4 * k] + 1.0f);
-        q[i] = 0.5f * t;
+        float t = sqrtf(r(4 * i) - r(4 * j) - r(4 * k) + 1.0f);
+        const float qi = 0.5f * t;
         t = 0.5f / t;
-        q[3] = (R[3 * k + j] - R[3 * j + k]) * t;
-        q[j] = (R[3 * j + i] + R[3 * i + j]) * t;
-        q[k] = (R[3 * k + i] + R[3 * i + k]) * t;
+        q[3] = (r(3 * k + j) - r(3 * j + k)) * t;
+        const float qj = (r(3 * j + i) + r(3 * i + j)) * t;
+        const float qk = (r(3 * k + i) + r(3 * i + k)) * t;
+        q[0] = i == 0 ? qi : j == 0 ? qj : qk;
+        q[1] = i == 1 ? qi : j == 1 ? qj : qk;
+        q[2] = i == 2 ? qi : j == 2 ? qj : qk;
     }
     const float n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2];
     if (n2 < 1e-5f * 1e-5f) return 0.0f;
@@ -3959,6 +3970,10 @@ VHD void rgbd_add_row(float (&acc)[kIcpTerms], const float (&J)[6], float r, flo
 // whatever their size; a point projected far off screen makes that an out-of-range float -> int conversion.  Such a
 // pixel can never pair up (its nearest-neighbour lookup, truncating u + 0.5, lies outside the image and returns MINF),
 // so it is rejected before any conversion: u + 0.5 and v + 0.5 must lie in (-1, W) and (-1, H).
+//
+// This kernel has a twin: k_icp_rgbd_step (below) restates the per-pixel arithmetic with the loads of several pixels in
+// flight, and must leave the same bits (tests/test_gpu_native_rgbd_tracking.py compares the two after every iteration).
+// A change to an expression or to an order of summation here is a change there too.
 __global__ __launch_bounds__(64) void k_icp_rgbd_build_system(uint32_t W, uint32_t H, uint32_t window, float* partials, const float4* inPos,
                                                               const float4* inNormal, const float* inIntensity, const float4* tgtPos,
                                                               const float4* tgtNormal, const float4* tgtIntensity4, VhIcpRGBDParams prm,
@@ -4042,25 +4057,19 @@ __global__ __launch_bounds__(64) void k_icp_rgbd_build_system(uint32_t W, uint32
     }
 }
 
-// One wave: reductionSystemCPU (CUDABuildLinearSystemRGBD.cpp:46-86), then computeBestRigidAlignment,
-// delinearizeTransformation and checkRigidTransformation (DSC/CUDACameraTrackingMultiResRGBD.cpp:166-237) and the
-// residual early-out of align (:329-350).  Unlike f5, the solution is an increment of the absolute Euler angles and
-// translation of delta (xNew = [anglesOld; translationOld] + x), and the rigidity check is on the new delta itself.
-// ATA.isZero() and a failed check both set lost; the reference would go on iterating with a matrix of -inf there.
-__global__ __launch_bounds__(64) void k_icp_rgbd_solve(VhIcpStateRGBD* st, const float* partials, uint32_t nPartials, float angleThres, float distThres, float earlyOut)
+// computeBestRigidAlignment, delinearizeTransformation and checkRigidTransformation
+// (DSC/CUDACameraTrackingMultiResRGBD.cpp:166-237) and the residual early-out of align (:329-350) on the 30 summed terms.
+// Unlike f5, the solution is an increment of the absolute Euler angles and translation of delta
+// (xNew = [anglesOld; translationOld] + x), and the rigidity check is on the new delta itself.  ATA.isZero() and a failed
+// check both set lost; the reference would go on iterating with a matrix of -inf there.  One lane.
+VHD void icp_rgbd_solve_step(VhIcpStateRGBD* st, const float* terms, float angleThres, float distThres, float earlyOut)
 {
-    __shared__ float sTerms[kIcpTerms];
     VhIcpState& s = st->icp;
-    if (s.lost || s.done) return;
-    const uint32_t t = threadIdx.x;
-    if (t < kIcpTerms) sTerms[t] = icp_sum_term(partials, nPartials, t);
-    __syncthreads();
-    if (t != 0u) return;
     double A[6][6], b[6];
-    const bool nonzero = icp_system_from_terms(sTerms, A, b);
-    s.sumRegError = sTerms[27];
-    s.sumRegWeight = sTerms[28];
-    s.numCorr = (uint32_t)sTerms[29];
+    const bool nonzero = icp_system_from_terms(terms, A, b);
+    s.sumRegError = terms[27];
+    s.sumRegWeight = terms[28];
+    s.numCorr = (uint32_t)terms[29];
     s.iterations += 1u;
     if (!nonzero) { s.lost = 1u; return; }
     double xs[6];
@@ -4083,6 +4092,205 @@ __global__ __launch_bounds__(64) void k_icp_rgbd_solve(VhIcpStateRGBD* st, const
     // align :345-350, after every outer iteration
     if (fabsf(s.lastError - s.sumRegError) < earlyOut) s.done = 1u;
     s.lastError = s.sumRegError;
+}
+
+// One wave: reductionSystemCPU (CUDABuildLinearSystemRGBD.cpp:46-86) over the wave partials in their order, then
+// icp_rgbd_solve_step.
+__global__ __launch_bounds__(64) void k_icp_rgbd_solve(VhIcpStateRGBD* st, const float* partials, uint32_t nPartials, float angleThres, float distThres, float earlyOut)
+{
+    __shared__ float sTerms[kIcpTerms];
+    if (st->icp.lost || st->icp.done) return;
+    const uint32_t t = threadIdx.x;
+    if (t < kIcpTerms) sTerms[t] = icp_sum_term(partials, nPartials, t);
+    __syncthreads();
+    if (t != 0u) return;
+    icp_rgbd_solve_step(st, sTerms, angleThres, distThres, earlyOut);
+}
+
+// bilinear_float4_taps on four taps that are in registers already: tap[0..3] = (px, py), (px + 1, py), (px, py + 1),
+// (px + 1, py + 1), in[k] whether tap k lies inside the image.  The same arithmetic in the same order.
+VHD float4 bilinear_float4_loaded(float x, float y, const float4 (&tap)[4], const bool (&in)[4])
+{
+    const int px = (int)floorf(x), py = (int)floorf(y);
+    const float alpha = x - (float)px, beta = y - (float)py;
+    const float mi = minf();
+    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
+    float w0 = 0.0f, w1 = 0.0f;
+    auto add = [&](uint32_t k, float wgt, float4& s, float& w) {
+        const float4 v = tap[k];
+        if (in[k] && v.x != mi && v.y != mi && v.z != mi) { s = f4_add(s, f4_scale(wgt, v)); w += wgt; }
+    };
+    add(0u, 1.0f - alpha, s0, w0);
+    add(1u, alpha, s0, w0);
+    add(2u, 1.0f - alpha, s1, w1);
+    add(3u, alpha, s1, w1);
+    const float4 p0 = f4_div(s0, w0), p1 = f4_div(s1, w1);
+    float4 ss = make_float4(0.f, 0.f, 0.f, 0.f);
+    float ww = 0.0f;
+    if (w0 > 0.0f) { ss = f4_add(ss, f4_scale(1.0f - beta, p0)); ww += (1.0f - beta); }
+    if (w1 > 0.0f) { ss = f4_add(ss, f4_scale(beta, p1)); ww += beta; }
+    return ww > 0.0f ? f4_div(ss, ww) : make_float4(mi, mi, mi, mi);
+}
+
+// One outer iteration of the RGB-D align in one launch: k_icp_rgbd_build_system and k_icp_rgbd_solve.  A wave owns the
+// pixels k_icp_rgbd_build_system gives it (lane x: [kWindow x, kWindow x + kWindow)) and sums them in that order with
+// the same expressions; the wave's terms go to `partials`, and the wave that draws the last ticket sums the partials in
+// their order and takes the step: the VhIcpStateRGBD after the launch is the two kernels' bit for bit.
+//
+// The hand-off is k_icp_step's: plain stores, the wave waits for them, an agent-scope release fence, a relaxed
+// agent-scope ticket; the last arriver takes an agent-scope acquire before its plain loads.  No wave waits for another.
+// Every wave has read lost / done / angles / translation before it draws its ticket, and only the last arriver writes
+// the state, after all tickets are drawn.  *ticket is 0 when the launch starts and the last arriver leaves it 0.
+// publish (may be null): mapped host memory that receives st->icp after this step, under `tag`.  A step that is skipped
+// (lost / done) changes nothing, so its first wave publishes the state as it stands.
+//
+// kBatch pixels of the window at a time: their input loads go out together, then their model loads (position, normal
+// and the four bilinear taps), then the sums take them in their order.  A workgroup is ONE wave.
+template <uint32_t kWindow, uint32_t kBatch>
+__global__ __launch_bounds__(64) void k_icp_rgbd_step(uint32_t W, uint32_t H, float* partials, uint32_t* ticket, const float4* inPos, const float4* inNormal,
+                                                      const float* inIntensity, const float4* tgtPos, const float4* tgtNormal, const float4* tgtIntensity4,
+                                                      VhIcpRGBDParams prm, VhIcpStateRGBD* st, float angleThres, float distThres, float earlyOut,
+                                                      VhIcpResult* publish, uint32_t tag)
+{
+    static_assert(kWindow % kBatch == 0u, "whole batches");
+    __shared__ float sTerms[kIcpTerms];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t skip = st->icp.lost | st->icp.done;
+    const float ga = st->angles[0], be = st->angles[1], al = st->angles[2];
+    const F3 tOld = mk3(st->translation[0], st->translation[1], st->translation[2]);
+    if (skip) {
+        if (publish && blockIdx.x == 0u && lane == 0u) icp_publish(&st->icp, publish, tag);
+        return;
+    }
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, nPixels = W * H;
+    const float mi = minf();
+    // evalRMat(anglesOld) and the derivatives, once per lane (k_icp_rgbd_build_system)
+    const float ca = cosf(al), cb = cosf(be), cg = cosf(ga), sa = sinf(al), sb = sinf(be), sg = sinf(ga);
+    float R[9], Ralpha[9], Rbeta[9], Rgamma[9];
+    eval_r(ca, cb, cg, sa, sb, sg, R);
+    eval_r_dgamma(ca, cb, cg, sa, sb, sg, Ralpha);
+    eval_r_dbeta(ca, cb, cg, sa, sb, sg, Rbeta);
+    eval_r_dalpha(ca, cb, cg, sa, sb, sg, Rgamma);
+    float acc[kIcpTerms];
+#pragma unroll
+    for (uint32_t k = 0; k < kIcpTerms; k++) acc[k] = 0.0f;
+    for (uint32_t w0 = 0; w0 < kWindow; w0 += kBatch) {
+        float4 p4[kBatch], n4[kBatch], tp[kBatch], tn[kBatch], tap[kBatch][4];
+        float iIn[kBatch], u[kBatch], v[kBatch];
+        F3 pT[kBatch], nT[kBatch], pp[kBatch];
+        bool ok[kBatch], in[kBatch][4];
+        uint32_t at[kBatch], tapAt[kBatch][4];
+#pragma unroll
+        for (uint32_t j = 0; j < kBatch; j++) {
+            const uint32_t idx = kWindow * x + w0 + j;
+            ok[j] = idx < nPixels;
+            at[j] = ok[j] ? idx : 0u; // (a pixel past the end reads pixel 0 and is dropped)
+            p4[j] = inPos[at[j]];
+            n4[j] = inNormal[at[j]];
+            iIn[j] = inIntensity[at[j]];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kBatch; j++) {
+            at[j] = 0u;
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) { tapAt[j][k] = 0u; in[j][k] = false; }
+            u[j] = v[j] = 0.0f;
+            pT[j] = nT[j] = pp[j] = mk3(0.0f, 0.0f, 0.0f);
+            ok[j] = ok[j] && !(p4[j].x == mi || p4[j].y == mi || p4[j].z == mi || n4[j].x == mi || n4[j].y == mi || n4[j].z == mi || iIn[j] == mi);
+            if (!ok[j]) continue;
+            const F3 rp = mat3_mul(R, mk3(p4[j].x, p4[j].y, p4[j].z));
+            nT[j] = mat3_mul(R, mk3(n4[j].x, n4[j].y, n4[j].z));
+            pT[j] = mk3(rp.x + tOld.x, rp.y + tOld.y, rp.z + tOld.z);
+            // pProjTrans = I pInputTransformed, I = [fx 0 mx; 0 fy my; 0 0 1]
+            pp[j] = mk3(prm.fx * pT[j].x + 0.0f * pT[j].y + prm.mx * pT[j].z, 0.0f * pT[j].x + prm.fy * pT[j].y + prm.my * pT[j].z,
+                        0.0f * pT[j].x + 0.0f * pT[j].y + 1.0f * pT[j].z);
+            ok[j] = pp[j].z > 0.0f;
+            if (!ok[j]) continue;
+            u[j] = pp[j].x / pp[j].z; v[j] = pp[j].y / pp[j].z; // dehomogenize
+            const float un = u[j] + 0.5f, vn = v[j] + 0.5f;
+            ok[j] = un > -1.0f && un < (float)W && vn > -1.0f && vn < (float)H; // the fence (k_icp_rgbd_build_system)
+            if (!ok[j]) continue;
+            const int ui = f2i(un), vi = f2i(vn); // getValueNearestNeighbour
+            ok[j] = !(ui < 0 || ui >= (int)W || vi < 0 || vi >= (int)H);
+            if (!ok[j]) continue;
+            at[j] = (uint32_t)vi * W + (uint32_t)ui;
+            const int px = (int)floorf(u[j]), py = (int)floorf(v[j]); // the taps of bilinear_float4_taps
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) {
+                const int tx = px + (int)(k & 1u), ty = py + (int)(k >> 1);
+                in[j][k] = (uint32_t)tx < W && (uint32_t)ty < H;
+                if (in[j][k]) tapAt[j][k] = (uint32_t)ty * W + (uint32_t)tx;
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kBatch; j++) { // (a pixel without a pair, a tap outside the image: pixel 0, dropped)
+            tp[j] = tgtPos[at[j]];
+            tn[j] = tgtNormal[at[j]];
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) tap[j][k] = tgtIntensity4[tapAt[j][k]];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kBatch; j++) {
+            if (!ok[j]) continue;
+            const float4 it = bilinear_float4_loaded(u[j], v[j], tap[j], in[j]);
+            const float4 t4 = tp[j], tn4 = tn[j];
+            if (t4.x == mi || t4.y == mi || t4.z == mi || tn4.x == mi || tn4.y == mi || tn4.z == mi || it.x == mi || it.y == mi || it.z == mi) continue;
+            const F3 q = pT[j];
+            const F3 phiA = mat3_mul(Ralpha, q), phiB = mat3_mul(Rbeta, q), phiG = mat3_mul(Rgamma, q);
+            const F3 diff = mk3(t4.x - q.x, t4.y - q.y, t4.z - q.z);
+            const float dDist = sqrtf(diff.x * diff.x + diff.y * diff.y + diff.z * diff.z);
+            const float dNormal = tn4.x * nT[j].x + tn4.y * nT[j].y + tn4.z * nT[j].z;
+            if (!(dDist <= prm.distThres && dNormal >= prm.normalThres)) continue; // both rows need it
+            {   // point to plane (z of the UNtransformed input point in the weight)
+                const float wD = fmaxf(0.0f, 0.5f * ((1.0f - dDist / prm.distThres) + (1.0f - p4[j].z / prm.sensorMaxDepth)));
+                const float J[6] = { -(tn4.x * phiA.x + tn4.y * phiA.y + tn4.z * phiA.z), -(tn4.x * phiB.x + tn4.y * phiB.y + tn4.z * phiB.z),
+                                     -(tn4.x * phiG.x + tn4.y * phiG.y + tn4.z * phiG.z), -tn4.x, -tn4.y, -tn4.z };
+                const float r = tn4.x * diff.x + tn4.y * diff.y + tn4.z * diff.z;
+                rgbd_add_row(acc, J, r, prm.weightDepth * wD);
+            }
+            // colour: J = dI (1x2) * dehomogenizeDerivative (2x3) * K (3x3) * phi
+            const float dI = it.x - iIn[j];
+            const float gu = it.y, gv = it.z;
+            const float absDI = sqrtf(dI * dI); // norm1D of the 1x1 residual
+            if (absDI <= prm.colorThres && sqrtf(gu * gu + gv * gv) > prm.colorGradientMin) {
+                const float wC = fmaxf(0.0f, 1.0f - absDI / prm.colorThres);
+                const float iz = 1.0f / pp[j].z, wSq = pp[j].z * pp[j].z;
+                const float d0 = gu * iz, d1 = gv * iz, d2 = gu * (-pp[j].x / wSq) + gv * (-pp[j].y / wSq); // dI PI
+                const F3 g = mk3(d0 * prm.fx, d1 * prm.fy, d0 * prm.mx + d1 * prm.my + d2);                 // (dI PI) K
+                const float J[6] = { g.x * phiA.x + g.y * phiA.y + g.z * phiA.z, g.x * phiB.x + g.y * phiB.y + g.z * phiB.z,
+                                     g.x * phiG.x + g.y * phiG.y + g.z * phiG.z, g.x, g.y, g.z };
+                rgbd_add_row(acc, J, dI, prm.weightColor * wC);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (uint32_t k = 0; k < kIcpTerms; k++) {
+            const float other = __shfl_down(acc[k], off);
+            if ((int)lane < off) acc[k] += other;
+        }
+    }
+    uint32_t drawn = 0u;
+    if (lane == 0u) {
+#pragma unroll
+        for (uint32_t k = 0; k < kIcpTerms; k++) partials[(size_t)blockIdx.x * kIcpTerms + k] = acc[k];
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    drawn = (uint32_t)__shfl((int)drawn, 0);
+    if (drawn != gridDim.x - 1u) return;
+    // the last arriver: every wave's partials are out
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane < kIcpTerms) sTerms[lane] = icp_sum_term(partials, gridDim.x, lane); // one term per lane
+    __syncthreads();
+    if (lane != 0u) return;
+    icp_rgbd_solve_step(st, sTerms, angleThres, distThres, earlyOut);
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (publish) icp_publish(&st->icp, publish, tag);
 }
 
 // ---------------------------------------------------------------------------
@@ -5025,6 +5233,29 @@ int vh_icp_rgbd_solve(VhIcpStateRGBD* d_state, const float* d_partials, uint32_t
 {
     if (!d_state || !d_partials) return VH_ERR_BAD_ARGUMENT;
     k_icp_rgbd_solve<<<1, 64, 0, (hipStream_t)stream>>>(d_state, d_partials, numPartials, angleThres, distThres, earlyOutResidual);
+    return vh_last_launch_error();
+}
+int vh_icp_rgbd_step(uint32_t width, uint32_t height, float* d_partials, uint32_t* d_ticket, const float* d_input4, const float* d_inputNormals4,
+                     const float* d_inputIntensity, const float* d_target4, const float* d_targetNormals4, const float* d_targetIntensityAndDerivatives4,
+                     const VhIcpRGBDParams* params, VhIcpStateRGBD* d_state, float angleThres, float distThres, float earlyOutResidual, VhIcpResult* publish,
+                     uint32_t tag, vhStream_t stream)
+{
+    if (!d_partials || !d_ticket || !d_input4 || !d_inputNormals4 || !d_inputIntensity || !d_target4 || !d_targetNormals4 ||
+        !d_targetIntensityAndDerivatives4 || !params || !d_state)
+        return VH_ERR_BAD_ARGUMENT;
+    if (width * height == 0) return VH_ERR_BAD_ARGUMENT; // (no wave would draw the last ticket)
+    const uint32_t grid = vh_icp_rgbd_num_partials(width, height, params->level);
+#define VH_RGBD_STEP(window, batch)                                                                                                                         \
+    k_icp_rgbd_step<window, batch><<<grid, 64, 0, (hipStream_t)stream>>>(                                                                                   \
+        width, height, d_partials, d_ticket, reinterpret_cast<const float4*>(d_input4), reinterpret_cast<const float4*>(d_inputNormals4), d_inputIntensity, \
+        reinterpret_cast<const float4*>(d_target4), reinterpret_cast<const float4*>(d_targetNormals4),                                                      \
+        reinterpret_cast<const float4*>(d_targetIntensityAndDerivatives4), *params, d_state, angleThres, distThres, earlyOutResidual, publish, tag)
+    switch (icp_rgbd_window(params->level)) { // 12 / 3 / 1
+    case kIcpWindow: VH_RGBD_STEP(kIcpWindow, 6u); break;
+    case 3u: VH_RGBD_STEP(3u, 3u); break;
+    default: VH_RGBD_STEP(1u, 1u); break;
+    }
+#undef VH_RGBD_STEP
     return vh_last_launch_error();
 }
 

@@ -27,6 +27,8 @@
 //   * setTracking: the pose of a frame comes from projective ICP against the ray cast of the model (:750-879 with
 //     s_binaryDumpSensorUseTrajectory = false), enqueued on the loop's stream with one launch per iteration
 //     (vh_icp_step); the host learns the pose from mapped host memory (frameTracked() below).
+//   * setTrackingRGBD: the same frame with the RGB-D tracker (CUDACameraTrackingMultiResRGBD, vh_icp_rgbd_step): the
+//     input's intensity pyramid is made per staging slot on the copy stream, the model's behind the ray cast.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -84,6 +86,7 @@ Reconstruction::Reconstruction(CUDASceneRepHashSDF* sceneRep, CUDARayCastSDF* ra
     m_tracking = false;
     m_trackedFrames = m_lostFrames = 0;
     std::memset(&m_trackingState, 0, sizeof(m_trackingState));
+    std::memset(&m_trackingStateRGBD, 0, sizeof(m_trackingStateRGBD));
     m_trkTag = 0;
     if (m_opt.s_framesOnHost) {
         const size_t n = (size_t)cp.m_imageWidth * cp.m_imageHeight;
@@ -117,6 +120,7 @@ void Reconstruction::setRawFormat(const RawFrameFormat& f)
     if (W < 2 || H < 2) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: the adapter size must be at least 2x2");
     if (f.depthWidth < 2 || f.depthHeight < 2) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: the depth size must be at least 2x2");
     if (f.colorChannels != 0 && f.colorChannels != 3 && f.colorChannels != 4) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: colorChannels must be 0, 3 or 4");
+    if (m_icpRGBD && !f.colorChannels) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: the RGB-D tracker needs a colour image");
     if (f.colorChannels && (f.colorWidth < 2 || f.colorHeight < 2)) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: the colour size must be at least 2x2");
     if (!(f.depthShift > 0.0f) || !std::isfinite(f.depthShift)) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setRawFormat: depthShift must be positive and finite");
     auto sigmaOk = [](float s) { return s > 0.0f && std::isfinite(s); };
@@ -166,11 +170,16 @@ void Reconstruction::setRawFormat(const RawFrameFormat& f)
 
 // The tracker's buffers (CUDACameraTrackingMultiRes' constructor, vh_tracking.cpp): the input's levels once per staging
 // slot, because they are made on the copy stream while the main stream still aligns the frame before.
+void Reconstruction::checkCanTrack(const char* who) const
+{
+    if (m_tracking) throw vh::Error(VH_ERR_BAD_ARGUMENT, std::string(who) + ": tracking is already set");
+    if (m_stats.frames || m_stats.invalidFrames || m_uploads || m_frameNumber) throw vh::Error(VH_ERR_BAD_ARGUMENT, std::string(who) + ": frames have been processed already");
+    if (!m_rayCast || !m_opt.s_renderEnabled) throw vh::Error(VH_ERR_BAD_ARGUMENT, std::string(who) + ": tracking aligns to the ray cast (needs a ray caster and s_renderEnabled)");
+}
+
 void Reconstruction::setTracking(const VhTrackingState& ts)
 {
-    if (m_tracking) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setTracking: tracking is already set");
-    if (m_stats.frames || m_stats.invalidFrames || m_uploads || m_frameNumber) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setTracking: frames have been processed already");
-    if (!m_rayCast || !m_opt.s_renderEnabled) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setTracking: tracking aligns to the ray cast (needs a ray caster and s_renderEnabled)");
+    checkCanTrack("Reconstruction::setTracking");
     // into locals first: a failure leaves the loop without tracking and without half a set of buffers
     std::unique_ptr<vh::IcpSolver> icp(new vh::IcpSolver(m_cp.m_imageWidth, m_cp.m_imageHeight, ts.s_maxLevels, "Reconstruction::setTracking"));
     std::vector<vh::DevicePtr<float>> input[kStagingSlots], inputNormal[kStagingSlots];
@@ -196,6 +205,43 @@ void Reconstruction::setTracking(const VhTrackingState& ts)
     }
     m_trkResult = std::move(result);
     m_trackingState = ts;
+    m_tracking = true;
+}
+
+// The same for CUDACameraTrackingMultiResRGBD: the input's intensity levels per staging slot as well.
+void Reconstruction::setTrackingRGBD(const VhTrackingStateRGBD& ts)
+{
+    checkCanTrack("Reconstruction::setTrackingRGBD");
+    if (m_raw && !m_rawFormat.colorChannels) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction::setTrackingRGBD: the RGB-D tracker needs a colour image (the raw format has none)");
+    // into locals first: a failure leaves the loop without tracking and without half a set of buffers
+    std::unique_ptr<vh::IcpSolverRGBD> icp(new vh::IcpSolverRGBD(m_cp.m_imageWidth, m_cp.m_imageHeight, ts.base.s_maxLevels, "Reconstruction::setTrackingRGBD"));
+    std::vector<vh::DevicePtr<float>> input[kStagingSlots], inputNormal[kStagingSlots], intensity[kStagingSlots], filtered[kStagingSlots];
+    for (unsigned int i = 0; i < ts.base.s_maxLevels; i++) {
+        const size_t n = (size_t)icp->width[i] * icp->height[i];
+        for (int slot = 0; slot < (int)kStagingSlots; slot++) { // (frames read in place use the first set only)
+            input[slot].push_back(vh::deviceAlloc<float>(4 * n, "tracking input"));
+            inputNormal[slot].push_back(vh::deviceAlloc<float>(4 * n, "tracking input normals"));
+            intensity[slot].push_back(vh::deviceAlloc<float>(n, "tracking input intensity"));
+            filtered[slot].push_back(i ? vh::deviceAlloc<float>(n, "tracking input intensity (filtered)") : nullptr);
+        }
+    }
+    vh::Mapped<VhIcpResult> result(1, "tracking result");
+    std::memset(result.host(), 0, sizeof(VhIcpResult));
+    // the estimate every solve starts from (:816-826 pass the identity), once
+    hipStream_t ms = (hipStream_t)m_sceneRep->getStream();
+    const vh::mat4f I = vh::mat4f::identity();
+    checkHip(hipMemcpyAsync(icp->estimate.get(), I.m, sizeof(I.m), hipMemcpyHostToDevice, ms), "deltaEstimate");
+    checkHip(hipMemsetAsync(icp->ticket.get(), 0, sizeof(uint32_t), ms), "tracking ticket");
+    checkHip(hipStreamSynchronize(ms), "Reconstruction::setTrackingRGBD");
+    m_icpRGBD = std::move(icp);
+    for (int slot = 0; slot < (int)kStagingSlots; slot++) {
+        d_trkInput[slot] = std::move(input[slot]);
+        d_trkInputNormal[slot] = std::move(inputNormal[slot]);
+        d_trkIntensity[slot] = std::move(intensity[slot]);
+        d_trkIntensityFiltered[slot] = std::move(filtered[slot]);
+    }
+    m_trkResult = std::move(result);
+    m_trackingStateRGBD = ts;
     m_tracking = true;
 }
 
@@ -343,7 +389,7 @@ DepthCameraData Reconstruction::upload(const SequenceFrame& f)
     }
     if (m_tracking) { // what the tracker needs of the input depends on the frame alone: here, beside the previous frame's work
         if (!m_rawRun) checkHip(hipStreamWaitEvent(cs, (hipEvent_t)m_slotReady2[slot].get(), 0), "hipStreamWaitEvent");
-        inputPyramid(slot, d_stageDepth[slot].get(), m_copyStream.get());
+        inputPyramid(slot, d_stageDepth[slot].get(), hasColor ? d_stageColor[slot].get() : nullptr, m_copyStream.get()); // (the colour was made on this stream)
     }
     checkHip(hipEventRecord((hipEvent_t)m_slotReady[slot].get(), cs), "hipEventRecord");
     checkHip(hipStreamWaitEvent(ms, (hipEvent_t)m_slotReady[slot].get(), 0), "hipStreamWaitEvent");
@@ -520,13 +566,19 @@ const unsigned int* Reconstruction::streamAround(const vh::vec3f& p)
     return m_chunkGrid->getBitMaskGPU();
 }
 
-// CUDARGBDSensor::process :173-174 (camera-space positions, normals) and the input half of applyCT's pyramids
-// (DSC/CUDACameraTrackingMultiRes.cpp:256-263) for one frame, on `stream`
-void Reconstruction::inputPyramid(unsigned int slot, const float* d_depth, vhStream_t stream)
+// CUDARGBDSensor::process :173-174 (camera-space positions, normals) and the input half of applyCT's pyramids for one
+// frame, on `stream`: DSC/CUDACameraTrackingMultiRes.cpp:256-263, or with the RGB-D tracker
+// DSC/CUDACameraTrackingMultiResRGBD.cpp:264-284, which reads the frame's float4 colour map as well
+void Reconstruction::inputPyramid(unsigned int slot, const float* d_depth, const float* d_color, vhStream_t stream)
 {
     const vh::IcpPyramid in = vh::icpPyramid(d_trkInput[slot][0].get(), d_trkInputNormal[slot][0].get(), d_trkInput[slot], d_trkInputNormal[slot]);
-    check(vh_convert_depth_float_to_camera_space_float4(in.map[0], d_depth, &m_cp, m_icp->width[0], m_icp->height[0], stream), "convertDepthFloatToCameraSpaceFloat4");
-    check(vh_compute_normals(in.normal[0], in.map[0], m_icp->width[0], m_icp->height[0], stream), "computeNormals");
+    const unsigned int W = m_cp.m_imageWidth, H = m_cp.m_imageHeight;
+    check(vh_convert_depth_float_to_camera_space_float4(in.map[0], d_depth, &m_cp, W, H, stream), "convertDepthFloatToCameraSpaceFloat4");
+    check(vh_compute_normals(in.normal[0], in.map[0], W, H, stream), "computeNormals");
+    if (m_icpRGBD) {
+        m_icpRGBD->inputPyramid(in, d_color, vh::icpIntensityPyramid(d_trkIntensity[slot], d_trkIntensityFiltered[slot]), stream);
+        return;
+    }
     for (unsigned int i = 0; i + 1 < m_icp->width.size(); i++) m_icp->coarserLevel(in, i, stream);
 }
 
@@ -536,6 +588,7 @@ void Reconstruction::inputPyramid(unsigned int slot, const float* d_depth, vhStr
 void Reconstruction::frameTracked(const SequenceFrame& f)
 {
     if (!f.depth) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction: frame without a depth map");
+    if (m_icpRGBD && !f.color) throw vh::Error(VH_ERR_BAD_ARGUMENT, "Reconstruction: the RGB-D tracker needs a colour map with every frame");
     vhStream_t stream = m_sceneRep->getStream();
     DepthCameraData cam;
     unsigned int slot = 0;
@@ -546,7 +599,7 @@ void Reconstruction::frameTracked(const SequenceFrame& f)
         std::memset(&cam, 0, sizeof(cam));
         cam.d_depthData = const_cast<float*>(f.depth);
         cam.d_colorData = const_cast<float*>(static_cast<const float*>(f.color));
-        inputPyramid(0, cam.d_depthData, stream);
+        inputPyramid(0, cam.d_depthData, cam.d_colorData, stream);
     }
     const float minf = -std::numeric_limits<float>::infinity();
     vh::mat4f transformation = vh::mat4f::identity();
@@ -555,11 +608,18 @@ void Reconstruction::frameTracked(const SequenceFrame& f)
         m_rayCast->render(m_sceneRep->getHashData(), m_sceneRep->getHashParams(), m_cp, lastTransform, nullptr); // :763
         const RayCastData& rd = m_rayCast->getRayCastData();
         const vh::IcpPyramid in = vh::icpPyramid(d_trkInput[slot][0].get(), d_trkInputNormal[slot][0].get(), d_trkInput[slot], d_trkInputNormal[slot]);
-        const vh::IcpPyramid mdl = vh::icpPyramid(rd.d_depth4, rd.d_normals, m_icp->model, m_icp->modelNormal);
-        for (unsigned int i = 0; i + 1 < m_icp->width.size(); i++) m_icp->coarserLevel(mdl, i, stream); // the model half of the pyramids, :256-263
         const uint32_t tag = ++m_trkTag;
         // one launch per iteration where a level allows it; the last step stores the result and the tag into mapped memory
-        m_icp->align(in, mdl, m_trackingState, m_cp, true, m_trkResult.device(), tag, stream);
+        if (m_icpRGBD) {
+            const vh::IcpPyramid mdl = vh::icpPyramid(rd.d_depth4, rd.d_normals, m_icpRGBD->model, m_icpRGBD->modelNormal);
+            m_icpRGBD->modelPyramid(mdl, rd.d_colors, stream); // the model half of the pyramids, RGBD.cpp:264-284
+            m_icpRGBD->align(in, vh::icpIntensityPyramid(d_trkIntensity[slot], d_trkIntensityFiltered[slot]), mdl, m_trackingStateRGBD, m_cp, true,
+                             m_trkResult.device(), tag, stream);
+        } else {
+            const vh::IcpPyramid mdl = vh::icpPyramid(rd.d_depth4, rd.d_normals, m_icp->model, m_icp->modelNormal);
+            for (unsigned int i = 0; i + 1 < m_icp->width.size(); i++) m_icp->coarserLevel(mdl, i, stream); // the model half of the pyramids, :256-263
+            m_icp->align(in, mdl, m_trackingState, m_cp, true, m_trkResult.device(), tag, stream);
+        }
         // the one wait of the frame
         const double w0 = now();
         while (__atomic_load_n(&m_trkResult.host()->tag, __ATOMIC_ACQUIRE) != tag) {
@@ -693,6 +753,11 @@ int vh_reconstruction_set_tracking(VhReconstruction* r, const VhTrackingState* s
 {
     if (!r || !settings) return VH_ERR_BAD_ARGUMENT;
     return guarded([&] { r->impl.setTracking(*settings); });
+}
+int vh_reconstruction_set_tracking_rgbd(VhReconstruction* r, const VhTrackingStateRGBD* settings)
+{
+    if (!r || !settings) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { r->impl.setTrackingRGBD(*settings); });
 }
 int vh_reconstruction_get_poses(VhReconstruction* r, uint32_t first, uint32_t n, float* out)
 {

@@ -139,36 +139,133 @@ vh::mat4f CUDACameraTrackingMultiRes::applyCT(float* dInput, float* dInputNormal
 }
 
 // ---------------------------------------------------------------------------
+// vh::IcpSolverRGBD: the RGB-D solve, enqueued here for both its hosts
+// ---------------------------------------------------------------------------
+
+vh::IcpIntensityPyramid vh::icpIntensityPyramid(const std::vector<DevicePtr<float>>& intensity, const std::vector<DevicePtr<float>>& filtered)
+{
+    IcpIntensityPyramid p = {};
+    for (size_t i = 0; i < intensity.size(); i++) { p.intensity[i] = intensity[i].get(); p.filtered[i] = filtered[i].get(); }
+    return p;
+}
+
+vh::IcpSolverRGBD::IcpSolverRGBD(unsigned int imageWidth, unsigned int imageHeight, unsigned int levels, const char* who)
+{
+    if (levels == 0 || levels > VH_TRACKING_MAX_LEVELS || (imageWidth >> (levels - 1)) < 2 || (imageHeight >> (levels - 1)) < 2)
+        throw vh::Error(VH_ERR_BAD_ARGUMENT, std::string(who) + ": bad pyramid");
+    unsigned int fac = 1;
+    uint32_t nPartials = 0;
+    for (unsigned int i = 0; i < levels; i++) { // :39-94
+        width.push_back(imageWidth / fac);
+        height.push_back(imageHeight / fac);
+        const size_t n = (size_t)width[i] * height[i];
+        model.push_back(i ? deviceAlloc<float>(4 * n, "d_model") : nullptr); // the finest level is the caller's maps
+        modelNormal.push_back(i ? deviceAlloc<float>(4 * n, "d_modelNormal") : nullptr);
+        modelIntensity.push_back(deviceAlloc<float>(n, "d_modelIntensity"));
+        modelIntensityFiltered.push_back(i ? deviceAlloc<float>(n, "d_modelIntensityFiltered") : nullptr); // level 0: the unfiltered map (:267 copies it)
+        modelIntensityAndDerivatives.push_back(deviceAlloc<float>(4 * n, "d_modelIntensityAndDerivatives"));
+        nPartials = std::max(nPartials, vh_icp_rgbd_num_partials(width[i], height[i], i));
+        fac *= 2;
+    }
+    partials = deviceAlloc<float>(30 * (size_t)nPartials, "d_partials");
+    state = deviceAlloc<VhIcpStateRGBD>(1, "VhIcpStateRGBD");
+    estimate = deviceAlloc<float>(16, "deltaEstimate");
+    ticket = deviceAlloc<uint32_t>(1, "tracking ticket");
+}
+
+namespace {
+const float kIntensitySigmaD = 3.0f, kIntensitySigmaR = 1.0f; // :262-263
+}
+
+void vh::IcpSolverRGBD::inputPyramid(const IcpPyramid& in, const float* dInputColor, const IcpIntensityPyramid& it, vhStream_t stream) const
+{
+    check(vh_convert_color_to_intensity_float(it.intensity[0], dInputColor, width[0], height[0], stream), "convertColorToIntensityFloat");
+    for (unsigned int i = 0; i + 1 < width.size(); i++) {
+        const unsigned int w = width[i], h = height[i], w1 = width[i + 1], h1 = height[i + 1];
+        check(vh_resample_float4_map(in.map[i + 1], w1, h1, in.map[i], w, h, stream), "resampleFloat4Map");
+        check(vh_compute_normals(in.normal[i + 1], in.map[i + 1], w1, h1, stream), "computeNormals");
+        check(vh_resample_float_map(it.intensity[i + 1], w1, h1, it.intensity[i], w, h, stream), "resampleFloatMap");
+        check(vh_gauss_filter_float_map(it.filtered[i + 1], it.intensity[i + 1], kIntensitySigmaD, kIntensitySigmaR, w1, h1, stream), "gaussFilterFloatMap");
+    }
+}
+
+void vh::IcpSolverRGBD::modelPyramid(const IcpPyramid& mdl, const float* dModelColor, vhStream_t stream) const
+{
+    check(vh_convert_color_to_intensity_float(modelIntensity[0].get(), dModelColor, width[0], height[0], stream), "convertColorToIntensityFloat");
+    check(vh_compute_intensity_and_derivatives(modelIntensity[0].get(), width[0], height[0], modelIntensityAndDerivatives[0].get(), stream), "computeIntensityAndDerivatives");
+    for (unsigned int i = 0; i + 1 < width.size(); i++) {
+        const unsigned int w = width[i], h = height[i], w1 = width[i + 1], h1 = height[i + 1];
+        check(vh_resample_float4_map(mdl.map[i + 1], w1, h1, mdl.map[i], w, h, stream), "resampleFloat4Map");
+        check(vh_compute_normals(mdl.normal[i + 1], mdl.map[i + 1], w1, h1, stream), "computeNormals");
+        check(vh_resample_float_map(modelIntensity[i + 1].get(), w1, h1, modelIntensity[i].get(), w, h, stream), "resampleFloatMap");
+        check(vh_gauss_filter_float_map(modelIntensityFiltered[i + 1].get(), modelIntensity[i + 1].get(), kIntensitySigmaD, kIntensitySigmaR, w1, h1, stream), "gaussFilterFloatMap");
+        check(vh_compute_intensity_and_derivatives(modelIntensityFiltered[i + 1].get(), w1, h1, modelIntensityAndDerivatives[i + 1].get(), stream),
+              "computeIntensityAndDerivatives");
+    }
+}
+
+void vh::IcpSolverRGBD::align(const IcpPyramid& in, const IcpIntensityPyramid& it, const IcpPyramid& mdl, const VhTrackingStateRGBD& ts,
+                              const DepthCameraParams& cp, bool fusedStep, VhIcpResult* d_result, uint32_t tag, vhStream_t stream) const
+{
+    const int levels = (int)width.size();
+    if (fusedStep) checkHip(hipMemsetAsync(ticket.get(), 0, sizeof(uint32_t), (hipStream_t)stream), "tracking ticket");
+    check(vh_icp_rgbd_begin(state.get(), estimate.get(), stream), "vh_icp_rgbd_begin");
+    // the step that is the solve's last publishes the result itself (as in IcpSolver::align)
+    int lastLevel = -1;
+    for (int level = 0; level < levels && lastLevel < 0; level++)
+        if (ts.base.s_maxOuterIter[level]) lastLevel = level;
+    bool published = false;
+    // coarse to fine, :289-321; align :329-353 with the loop exits taken on the device
+    for (int level = levels - 1; level >= 0; level--) {
+        const unsigned int W = width[level], H = height[level];
+        const float levelFactor = std::pow(2.0f, (float)level);
+        VhIcpRGBDParams prm;
+        prm.fx = cp.fx / levelFactor; prm.fy = cp.fy / levelFactor; prm.mx = cp.mx / levelFactor; prm.my = cp.my / levelFactor;
+        prm.weightDepth = ts.s_weightsDepth[level];
+        prm.weightColor = ts.s_weightsColor[level];
+        prm.distThres = ts.base.s_distThres[level];
+        prm.normalThres = ts.base.s_normalThres[level];
+        prm.sensorMaxDepth = cp.m_sensorDepthWorldMax; // GlobalAppState::s_sensorDepthMax
+        prm.colorGradientMin = ts.s_colorGradientMin[level];
+        prm.colorThres = ts.s_colorThres[level];
+        prm.level = (uint32_t)level;
+        const float* inIntensity = level ? it.filtered[level] : it.intensity[0];
+        const uint32_t nP = vh_icp_rgbd_num_partials(W, H, (uint32_t)level);
+        check(vh_icp_begin_level(&state.get()->icp, stream), "vh_icp_begin_level");
+        for (unsigned int outer = 0; outer < ts.base.s_maxOuterIter[level]; outer++) {
+            if (fusedStep) {
+                const bool last = level == lastLevel && outer + 1 == ts.base.s_maxOuterIter[level];
+                check(vh_icp_rgbd_step(W, H, partials.get(), ticket.get(), in.map[level], in.normal[level], inIntensity, mdl.map[level], mdl.normal[level],
+                                       modelIntensityAndDerivatives[level].get(), &prm, state.get(), ts.base.s_angleTransThres[level],
+                                       ts.base.s_distTransThres[level], ts.base.s_residualEarlyOut[level], last ? d_result : nullptr, tag, stream),
+                      "vh_icp_rgbd_step");
+                published = published || (last && d_result);
+                continue;
+            }
+            check(vh_icp_rgbd_build_linear_system(W, H, partials.get(), in.map[level], in.normal[level], inIntensity, mdl.map[level], mdl.normal[level],
+                                                  modelIntensityAndDerivatives[level].get(), &prm, state.get(), stream), "computeNormalEquations");
+            check(vh_icp_rgbd_solve(state.get(), partials.get(), nP, ts.base.s_angleTransThres[level], ts.base.s_distTransThres[level],
+                                    ts.base.s_residualEarlyOut[level], stream), "vh_icp_rgbd_solve");
+        }
+    }
+    if (d_result && !published) check(vh_icp_publish(&state.get()->icp, d_result, tag, stream), "vh_icp_publish"); // (two kernels an iteration, or no level iterates)
+}
+
+// ---------------------------------------------------------------------------
 // CUDACameraTrackingMultiResRGBD (DSC/CUDACameraTrackingMultiResRGBD.cpp) over the vh_icp_rgbd_* steps
 // ---------------------------------------------------------------------------
 
 CUDACameraTrackingMultiResRGBD::CUDACameraTrackingMultiResRGBD(unsigned int imageWidth, unsigned int imageHeight, unsigned int levels, vhStream_t stream)
-    : m_levels(levels), m_stream(stream)
+    : m_levels(levels), m_stream(stream), m_icp(imageWidth, imageHeight, levels, "CUDACameraTrackingMultiResRGBD")
 {
-    if (levels == 0 || levels > VH_TRACKING_MAX_LEVELS || (imageWidth >> (levels - 1)) < 2 || (imageHeight >> (levels - 1)) < 2)
-        throw vh::Error(VH_ERR_BAD_ARGUMENT, "CUDACameraTrackingMultiResRGBD: bad pyramid");
     std::memset(&m_lastState, 0, sizeof(m_lastState));
-    unsigned int fac = 1;
-    uint32_t partials = 0;
-    for (unsigned int i = 0; i < levels; i++) { // :39-94
-        m_imageWidth.push_back(imageWidth / fac);
-        m_imageHeight.push_back(imageHeight / fac);
-        const size_t n = (size_t)m_imageWidth[i] * m_imageHeight[i];
+    for (unsigned int i = 0; i < levels; i++) {
+        const size_t n = (size_t)m_icp.width[i] * m_icp.height[i];
         d_input.push_back(i ? vh::deviceAlloc<float>(4 * n, "d_input") : nullptr); // the finest level is the caller's maps
         d_inputNormal.push_back(i ? vh::deviceAlloc<float>(4 * n, "d_inputNormal") : nullptr);
         d_inputIntensity.push_back(vh::deviceAlloc<float>(n, "d_inputIntensity"));
-        d_inputIntensityFiltered.push_back(i ? vh::deviceAlloc<float>(n, "d_inputIntensityFiltered") : nullptr); // level 0: the unfiltered map (:267 copies it)
-        d_model.push_back(i ? vh::deviceAlloc<float>(4 * n, "d_model") : nullptr);
-        d_modelNormal.push_back(i ? vh::deviceAlloc<float>(4 * n, "d_modelNormal") : nullptr);
-        d_modelIntensity.push_back(vh::deviceAlloc<float>(n, "d_modelIntensity"));
-        d_modelIntensityFiltered.push_back(i ? vh::deviceAlloc<float>(n, "d_modelIntensityFiltered") : nullptr);
-        d_modelIntensityAndDerivatives.push_back(vh::deviceAlloc<float>(4 * n, "d_modelIntensityAndDerivatives"));
-        partials = std::max(partials, vh_icp_rgbd_num_partials(m_imageWidth[i], m_imageHeight[i], i));
-        fac *= 2;
+        d_inputIntensityFiltered.push_back(i ? vh::deviceAlloc<float>(n, "d_inputIntensityFiltered") : nullptr);
     }
-    d_partials = vh::deviceAlloc<float>(30 * (size_t)partials, "d_partials");
-    d_state = vh::deviceAlloc<VhIcpStateRGBD>(1, "VhIcpStateRGBD");
-    d_deltaEstimate = vh::deviceAlloc<float>(16, "deltaEstimate");
 }
 
 CUDACameraTrackingMultiResRGBD::~CUDACameraTrackingMultiResRGBD() { (void)hipStreamSynchronize((hipStream_t)m_stream); }
@@ -182,53 +279,13 @@ vh::mat4f CUDACameraTrackingMultiResRGBD::applyCT(float* dInput, float* dInputNo
     if (!dInput || !dInputNormals || !dInputColor || !dModel || !dModelNormals || !dModelColor) throw vh::Error(VH_ERR_BAD_ARGUMENT, "applyCT: null map");
     hipStream_t s = (hipStream_t)m_stream;
     const vh::IcpPyramid in = vh::icpPyramid(dInput, dInputNormals, d_input, d_inputNormal);
-    const vh::IcpPyramid mdl = vh::icpPyramid(dModel, dModelNormals, d_model, d_modelNormal);
-    const unsigned int W0 = m_imageWidth[0], H0 = m_imageHeight[0];
-    // the pyramids, :264-284
-    check(vh_convert_color_to_intensity_float(d_inputIntensity[0].get(), dInputColor, W0, H0, m_stream), "convertColorToIntensityFloat");
-    check(vh_convert_color_to_intensity_float(d_modelIntensity[0].get(), dModelColor, W0, H0, m_stream), "convertColorToIntensityFloat");
-    check(vh_compute_intensity_and_derivatives(d_modelIntensity[0].get(), W0, H0, d_modelIntensityAndDerivatives[0].get(), m_stream), "computeIntensityAndDerivatives");
-    const float sigmaD = 3.0f, sigmaR = 1.0f;
-    for (unsigned int i = 0; i + 1 < m_levels; i++) {
-        const unsigned int w = m_imageWidth[i], h = m_imageHeight[i], w1 = m_imageWidth[i + 1], h1 = m_imageHeight[i + 1];
-        check(vh_resample_float4_map(in.map[i + 1], w1, h1, in.map[i], w, h, m_stream), "resampleFloat4Map");
-        check(vh_compute_normals(in.normal[i + 1], in.map[i + 1], w1, h1, m_stream), "computeNormals");
-        check(vh_resample_float_map(d_inputIntensity[i + 1].get(), w1, h1, d_inputIntensity[i].get(), w, h, m_stream), "resampleFloatMap");
-        check(vh_gauss_filter_float_map(d_inputIntensityFiltered[i + 1].get(), d_inputIntensity[i + 1].get(), sigmaD, sigmaR, w1, h1, m_stream), "gaussFilterFloatMap");
-        check(vh_resample_float4_map(mdl.map[i + 1], w1, h1, mdl.map[i], w, h, m_stream), "resampleFloat4Map");
-        check(vh_compute_normals(mdl.normal[i + 1], mdl.map[i + 1], w1, h1, m_stream), "computeNormals");
-        check(vh_resample_float_map(d_modelIntensity[i + 1].get(), w1, h1, d_modelIntensity[i].get(), w, h, m_stream), "resampleFloatMap");
-        check(vh_gauss_filter_float_map(d_modelIntensityFiltered[i + 1].get(), d_modelIntensity[i + 1].get(), sigmaD, sigmaR, w1, h1, m_stream), "gaussFilterFloatMap");
-        check(vh_compute_intensity_and_derivatives(d_modelIntensityFiltered[i + 1].get(), w1, h1, d_modelIntensityAndDerivatives[i + 1].get(), m_stream),
-              "computeIntensityAndDerivatives");
-    }
-    checkHip(hipMemcpyAsync(d_deltaEstimate.get(), deltaTransformEstimate.m, sizeof(float) * 16, hipMemcpyHostToDevice, s), "deltaEstimate");
-    check(vh_icp_rgbd_begin(d_state.get(), d_deltaEstimate.get(), m_stream), "vh_icp_rgbd_begin");
-    // coarse to fine, :289-321; align :329-353 with the loop exits taken on the device
-    for (int level = (int)m_levels - 1; level >= 0; level--) {
-        const unsigned int W = m_imageWidth[level], H = m_imageHeight[level];
-        const float levelFactor = std::pow(2.0f, (float)level);
-        VhIcpRGBDParams prm;
-        prm.fx = cp.fx / levelFactor; prm.fy = cp.fy / levelFactor; prm.mx = cp.mx / levelFactor; prm.my = cp.my / levelFactor;
-        prm.weightDepth = ts.s_weightsDepth[level];
-        prm.weightColor = ts.s_weightsColor[level];
-        prm.distThres = ts.base.s_distThres[level];
-        prm.normalThres = ts.base.s_normalThres[level];
-        prm.sensorMaxDepth = cp.m_sensorDepthWorldMax; // GlobalAppState::s_sensorDepthMax
-        prm.colorGradientMin = ts.s_colorGradientMin[level];
-        prm.colorThres = ts.s_colorThres[level];
-        prm.level = (uint32_t)level;
-        const float* inIntensity = level ? d_inputIntensityFiltered[level].get() : d_inputIntensity[0].get();
-        const uint32_t nP = vh_icp_rgbd_num_partials(W, H, (uint32_t)level);
-        check(vh_icp_begin_level(&d_state.get()->icp, m_stream), "vh_icp_begin_level");
-        for (unsigned int outer = 0; outer < ts.base.s_maxOuterIter[level]; outer++) {
-            check(vh_icp_rgbd_build_linear_system(W, H, d_partials.get(), in.map[level], in.normal[level], inIntensity, mdl.map[level], mdl.normal[level],
-                                                  d_modelIntensityAndDerivatives[level].get(), &prm, d_state.get(), m_stream), "computeNormalEquations");
-            check(vh_icp_rgbd_solve(d_state.get(), d_partials.get(), nP, ts.base.s_angleTransThres[level], ts.base.s_distTransThres[level],
-                                    ts.base.s_residualEarlyOut[level], m_stream), "vh_icp_rgbd_solve");
-        }
-    }
-    checkHip(hipMemcpyAsync(&m_lastState, d_state.get(), sizeof(VhIcpStateRGBD), hipMemcpyDeviceToHost, s), "VhIcpStateRGBD");
+    const vh::IcpPyramid mdl = vh::icpPyramid(dModel, dModelNormals, m_icp.model, m_icp.modelNormal);
+    const vh::IcpIntensityPyramid it = vh::icpIntensityPyramid(d_inputIntensity, d_inputIntensityFiltered);
+    m_icp.inputPyramid(in, dInputColor, it, m_stream); // the pyramids, :264-284
+    m_icp.modelPyramid(mdl, dModelColor, m_stream);
+    checkHip(hipMemcpyAsync(m_icp.estimate.get(), deltaTransformEstimate.m, sizeof(float) * 16, hipMemcpyHostToDevice, s), "deltaEstimate");
+    m_icp.align(in, it, mdl, ts, cp, false, nullptr, 0u, m_stream); // two kernels an iteration; the outcome is copied back
+    checkHip(hipMemcpyAsync(&m_lastState, m_icp.state.get(), sizeof(VhIcpStateRGBD), hipMemcpyDeviceToHost, s), "VhIcpStateRGBD");
     checkHip(hipStreamSynchronize(s), "applyCT");
     vh::mat4f out;
     if (m_lastState.icp.lost) {

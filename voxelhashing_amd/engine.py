@@ -459,6 +459,11 @@ class Reconstruction:
         lastRigidTransform * delta, a frame on which tracking is lost is not integrated.  Needs a ray caster."""
         check(self.L.vh_reconstruction_set_tracking(self.handle, C.byref(tracking_state)), "Reconstruction::setTracking")
 
+    def setTrackingRGBD(self, tracking_state_rgbd):
+        """setTracking with the RGB-D tracker (depth + photometric ICP; tracking_state_rgbd: a TrackingStateRGBD) in place
+        of the plain one: one of the two, once.  Every frame then needs a colour map."""
+        check(self.L.vh_reconstruction_set_tracking_rgbd(self.handle, C.byref(tracking_state_rgbd)), "Reconstruction::setTrackingRGBD")
+
     def getPoses(self, first=0, count=None):
         """-> [count, 4, 4] float32: the pose each frame fed since creation / reset was integrated at, all -inf for a frame
         that was not (tracking lost, invalid recorded pose).  count=None: up to the last frame fed (asks getStats)."""

@@ -109,6 +109,7 @@ PROTOTYPES = {
     "vh_reconstruction_run_raw": (C.c_int, [_VP, P(T.RawSequenceFrame), C.c_uint32]),
     "vh_reconstruction_run_raw_ahead": (C.c_int, [_VP, P(T.RawSequenceFrame), C.c_uint32, P(T.RawSequenceFrame)]),
     "vh_reconstruction_set_tracking": (C.c_int, [_VP, P(T.TrackingState)]),
+    "vh_reconstruction_set_tracking_rgbd": (C.c_int, [_VP, P(T.TrackingStateRGBD)]),
     "vh_reconstruction_get_poses": (C.c_int, [_VP, C.c_uint32, C.c_uint32, P(C.c_float)]),
     "vh_reconstruction_get_tracking_stats": (C.c_int, [_VP, P(C.c_uint64), P(C.c_uint64)]),
     "vh_reconstruction_synchronize": (C.c_int, [_VP]),
@@ -147,6 +148,8 @@ PROTOTYPES = {
     "vh_icp_rgbd_num_partials": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "vh_icp_rgbd_build_linear_system": (C.c_int, [C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, P(T.IcpRGBDParams), _VP, _VP]),
     "vh_icp_rgbd_solve": (C.c_int, [_VP, _VP, C.c_uint32, C.c_float, C.c_float, C.c_float, _VP]),
+    "vh_icp_rgbd_step": (C.c_int, [C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, P(T.IcpRGBDParams), _VP, C.c_float, C.c_float, C.c_float,
+                                   _VP, C.c_uint32, _VP]),
     "vh_tracking_state_rgbd_read": (C.c_int, [C.c_char_p, P(T.TrackingStateRGBD)]),
     "vh_tracking_state_rgbd_parse": (C.c_int, [C.c_char_p, P(T.TrackingStateRGBD)]),
     "vh_camera_tracking_rgbd_create": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _VP, P(_VP)]),

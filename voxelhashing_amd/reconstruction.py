@@ -149,16 +149,18 @@ def depth_image_rgba8(depth):
     return (out * f(255)).astype(np.uint8)
 
 
-def native_refusal(app_state, render_state=None, camera_calibration=False, use_rgbd_tracking=False, tracking=False):
+def native_refusal(app_state, render_state=None, camera_calibration=False, use_rgbd_tracking=False, tracking=False, tracking_rgbd=False):
     """Why the native frame loop cannot play this configuration, as text, or None when it can.  The native loop
     (engine.Reconstruction) integrates every frame at the pose the file holds: s_binaryDumpSensorUseTrajectory = true,
     s_binaryDumpSensorUseTrajectoryOnlyInit = false.  tracking=True: the caller lets the loop track the camera itself
     (engine.Reconstruction.setTracking), which admits s_binaryDumpSensorUseTrajectory = false with the plain ICP tracker.
-    Needs no device."""
+    tracking_rgbd=True (with tracking=True): the caller lets it do so with the RGB-D tracker as well
+    (engine.Reconstruction.setTrackingRGBD), which admits use_rgbd_tracking.  Both keywords only permit.  Needs no device."""
     g = app_state
-    if tracking and use_rgbd_tracking:
+    rgbd_allowed = bool(tracking and tracking_rgbd)
+    if tracking and use_rgbd_tracking and not rgbd_allowed:
         return "the poses come from the RGB-D tracker: the native loop tracks with plain projective ICP only"
-    if (not g.s_binaryDumpSensorUseTrajectory and not tracking) or use_rgbd_tracking:
+    if (not g.s_binaryDumpSensorUseTrajectory and not tracking) or (use_rgbd_tracking and not rgbd_allowed):
         return "the poses come from ICP tracking (s_binaryDumpSensorUseTrajectory = false): the native loop has no tracker"
     if g.s_binaryDumpSensorUseTrajectory and g.s_binaryDumpSensorUseTrajectoryOnlyInit:  # (without the trajectory the key means nothing)
         return "s_binaryDumpSensorUseTrajectoryOnlyInit = true tracks from the recorded pose: the native loop has no tracker"
@@ -421,14 +423,14 @@ class Reconstruction:
         return n
 
     # -- the same sequence through the native frame loop ------------------------------------------------------------
-    def prepare_native(self, batch=64, tracking=False):
+    def prepare_native(self, batch=64, tracking=False, tracking_rgbd=False):
         """what run_native needs before its first frame: the native loop with the raw format of the first file, two sets of
         pinned buffers of `batch` frames, the file loaded.  run_native calls it; a caller that times the frames alone
         calls it first (the Python loop's reader loads its file in the constructor too)."""
         from .lib import PinnedArray
         if self.native is not None:
             return
-        why = native_refusal(self.gas, self.render_state, self.camera_calibration, self.use_rgbd_tracking, tracking=tracking)
+        why = native_refusal(self.gas, self.render_state, self.camera_calibration, self.use_rgbd_tracking, tracking=tracking, tracking_rgbd=tracking_rgbd)
         if why is None and self.frame_number:
             why = "frames of this sequence have been played by the Python loop already"
         if why is not None:
@@ -447,24 +449,27 @@ class Reconstruction:
                               PinnedArray((batch, h.m_colorHeight, h.m_colorWidth, 3), np.uint8) if has_color else None) for _ in range(2)]
         # the loop tracks where the Python loop would (_reconstruct): the file's poses are not used
         self._native_tracked = bool(tracking) and not g.s_binaryDumpSensorUseTrajectory
-        if self._native_tracked:
+        if self._native_tracked and self.tracker_rgbd is not None:  # (as _reconstruct picks its tracker)
+            native.setTrackingRGBD(self.tracking_rgbd)
+        elif self._native_tracked:
             native.setTracking(self.tracking)
         self._native_sens = SD.SensorData.loadFromFile(self.sens_files[self.file_idx])
         self._native_at = 0
         self.native = native
 
-    def run_native(self, max_frames=None, batch=64, tracking=False):
+    def run_native(self, max_frames=None, batch=64, tracking=False, tracking_rgbd=False):
         """Plays the `.sens` files through the native frame loop (engine.Reconstruction) fed with raw frames: a batch of
         frames is decoded into pinned memory (16-bit depth, RGB) while the device works on the batch before, and handed
         over with one call, the next frame's pose as look-ahead.  The device converts, resamples and filters them
         (vh_ingest_frame) as CUDARGBDSensor.process does for the Python loop.  For recorded poses, and with tracking=True
         for poses from the plain ICP tracker (s_binaryDumpSensorUseTrajectory = false: the loop tracks the camera itself,
-        trajectory and lost_frames are filled as the Python loop fills them); raises ValueError with the reason otherwise
+        trajectory and lost_frames are filled as the Python loop fills them), with tracking_rgbd=True as well from the RGB-D
+        tracker of a use_rgbd_tracking configuration; raises ValueError with the reason otherwise
         (native_refusal).  -> number of frames read"""
         h = self.reader.header
         batch = max(int(batch), 1)
         has_color = h.m_colorWidth * h.m_colorHeight > 0
-        self.prepare_native(batch, tracking)
+        self.prepare_native(batch, tracking, tracking_rgbd)
         if self._native_sets[0][0].shape[0] < batch:
             raise ValueError("run_native: the batch size is fixed by the first call")
 
