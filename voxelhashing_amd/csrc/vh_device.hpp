@@ -559,4 +559,50 @@ VHD Vox combine_voxel(const VhHashParams& hp, Vox v0, Vox v1)
     return out;
 }
 
+// ---------------------------------------------------------------------------
+// what more than one translation unit of kernels needs
+// ---------------------------------------------------------------------------
+
+constexpr int kWave = 64;
+VHD uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
+
+// workgroups of b that cover a (host side: the launchers' grid sizes)
+inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+
+VHD float4 f4_scale(float a, float4 v) { return make_float4(a * v.x, a * v.y, a * v.z, a * v.w); }
+VHD float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+VHD float4 f4_div(float4 a, float b) { return make_float4(a.x / b, a.y / b, a.z / b, a.w / b); }
+
+// bilinearInterpolationFloat4, DSC/CameraUtil.cu:1136-1166 (and ICPUtil.h:129-156).  fetch(i, k): the pixel at index i,
+// which is tap k of (px, py), (px + 1, py), (px, py + 1), (px + 1, py + 1); it is asked for taps inside the image only.
+template <class Fetch>
+VHD float4 bilinear_float4_taps(float x, float y, Fetch fetch, uint32_t W, uint32_t H)
+{
+    const int px = (int)floorf(x), py = (int)floorf(y);
+    const float alpha = x - (float)px, beta = y - (float)py;
+    const float mi = minf();
+    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
+    float w0 = 0.0f, w1 = 0.0f;
+    auto tap = [&](uint32_t k, int tx, int ty, float wgt, float4& s, float& w) {
+        if ((uint32_t)tx < W && (uint32_t)ty < H) {
+            const float4 v = fetch((uint32_t)ty * W + (uint32_t)tx, k);
+            if (v.x != mi && v.y != mi && v.z != mi) { s = f4_add(s, f4_scale(wgt, v)); w += wgt; }
+        }
+    };
+    tap(0u, px, py, 1.0f - alpha, s0, w0);
+    tap(1u, px + 1, py, alpha, s0, w0);
+    tap(2u, px, py + 1, 1.0f - alpha, s1, w1);
+    tap(3u, px + 1, py + 1, alpha, s1, w1);
+    const float4 p0 = f4_div(s0, w0), p1 = f4_div(s1, w1);
+    float4 ss = make_float4(0.f, 0.f, 0.f, 0.f);
+    float ww = 0.0f;
+    if (w0 > 0.0f) { ss = f4_add(ss, f4_scale(1.0f - beta, p0)); ww += (1.0f - beta); }
+    if (w1 > 0.0f) { ss = f4_add(ss, f4_scale(beta, p1)); ww += beta; }
+    return ww > 0.0f ? f4_div(ss, ww) : make_float4(mi, mi, mi, mi);
+}
+VHD float4 bilinear_float4(float x, float y, const float4* in, uint32_t W, uint32_t H)
+{
+    return bilinear_float4_taps(x, y, [in](uint32_t i, uint32_t) { return in[i]; }, W, H);
+}
+
 } // namespace vhd

@@ -23,9 +23,6 @@ using namespace vhd;
 
 namespace {
 
-constexpr int kWave = 64;
-
-VHD uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
 VHD uint64_t lanemask_lt() { return (1ull << lane_id()) - 1ull; }
 
 // ---------------------------------------------------------------------------
@@ -3097,41 +3094,6 @@ VHD float bilinear_float(float x, float y, const float* in, uint32_t W, uint32_t
     return bilinear_float_taps(x, y, [in](uint32_t i) { return in[i]; }, W, H);
 }
 
-VHD float4 f4_scale(float a, float4 v) { return make_float4(a * v.x, a * v.y, a * v.z, a * v.w); }
-VHD float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-VHD float4 f4_div(float4 a, float b) { return make_float4(a.x / b, a.y / b, a.z / b, a.w / b); }
-
-// bilinearInterpolationFloat4 :1136-1166
-template <class Fetch>
-VHD float4 bilinear_float4_taps(float x, float y, Fetch fetch, uint32_t W, uint32_t H)
-{
-    const int px = (int)floorf(x), py = (int)floorf(y);
-    const float alpha = x - (float)px, beta = y - (float)py;
-    const float mi = minf();
-    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-    float w0 = 0.0f, w1 = 0.0f;
-    auto tap = [&](int tx, int ty, float wgt, float4& s, float& w) {
-        if ((uint32_t)tx < W && (uint32_t)ty < H) {
-            const float4 v = fetch((uint32_t)ty * W + (uint32_t)tx);
-            if (v.x != mi && v.y != mi && v.z != mi) { s = f4_add(s, f4_scale(wgt, v)); w += wgt; }
-        }
-    };
-    tap(px, py, 1.0f - alpha, s0, w0);
-    tap(px + 1, py, alpha, s0, w0);
-    tap(px, py + 1, 1.0f - alpha, s1, w1);
-    tap(px + 1, py + 1, alpha, s1, w1);
-    const float4 p0 = f4_div(s0, w0), p1 = f4_div(s1, w1);
-    float4 ss = make_float4(0.f, 0.f, 0.f, 0.f);
-    float ww = 0.0f;
-    if (w0 > 0.0f) { ss = f4_add(ss, f4_scale(1.0f - beta, p0)); ww += (1.0f - beta); }
-    if (w1 > 0.0f) { ss = f4_add(ss, f4_scale(beta, p1)); ww += beta; }
-    return ww > 0.0f ? f4_div(ss, ww) : make_float4(mi, mi, mi, mi);
-}
-VHD float4 bilinear_float4(float x, float y, const float4* in, uint32_t W, uint32_t H)
-{
-    return bilinear_float4_taps(x, y, [in](uint32_t i) { return in[i]; }, W, H);
-}
-
 // resampleFloatMapDevice :1100-1118 / resampleFloat4MapDevice :1168-1186 (pixels whose nearest source pixel lies
 // outside the source keep their old value, as in the reference)
 // the source coordinates of output pixel (x, y); false: the nearest source pixel lies outside the source
@@ -3185,7 +3147,7 @@ __global__ __launch_bounds__(256) void k_ingest_frame(float* __restrict__ outDep
         for (uint32_t i = i0; i < n; i++) outDepth[i] = depthAt(i);
     }
     if constexpr (CH != 0) {
-        auto colorTap = [color](uint32_t i) {
+        auto colorTap = [color](uint32_t i, uint32_t = 0u) {
             if constexpr (CH == 4) return color_raw_to_float4(reinterpret_cast<const uint32_t*>(color)[i]);
             else return color_raw_to_float4((uint32_t)color[3u * i] | ((uint32_t)color[3u * i + 1u] << 8) | ((uint32_t)color[3u * i + 2u] << 16) | (1u << 24));
         };
@@ -3376,921 +3338,6 @@ __global__ __launch_bounds__(256) void k_erode_depth(float* out, const float* in
             }
     const uint32_t sum = (uint32_t)((2 * structureSize + 1) * (2 * structureSize + 1));
     out[idx] = ((float)count / (float)sum >= fracReq) ? mi : oldDepth;
-}
-
-// ---------------------------------------------------------------------------
-// projective ICP camera tracking: projectiveCorrespondencesKernel (DSC/CUDAImageHelper.cu:70-125),
-// scanScanElementsCS + reductionSystemCPU (DSC/CUDABuildLinearSystem.cu:130-188, .cpp:52-92) and the 6x6 solve /
-// delinearisation the reference does on the host with Eigen (DSC/CUDACameraTrackingMultiRes.cpp:186-253).
-//
-// The reference copies every linear system to the host, solves it there and uploads the next transform: up to 18
-// blocking round trips per frame.  Here the transform, the residual history and the lost / early-out flags live in
-// a VhIcpState on the device; every step is a kernel on the stream that reads and updates it, a step whose level has
-// finished returns at once, and the host reads the result once per frame.
-// ---------------------------------------------------------------------------
-
-constexpr uint32_t kIcpWindow = 12;   // pixels a lane sums before the wave reduces (localWindowSize, .cpp:41)
-constexpr uint32_t kIcpTerms = 30;    // 21 upper-triangle terms of A^T A, 6 of A^T b, residual, weight, count (ARRAY_SIZE)
-
-__global__ void k_icp_begin(VhIcpState* st, const float* d_deltaEstimate)
-{
-    const uint32_t t = threadIdx.x;
-    if (t < 16u) st->delta[t] = d_deltaEstimate[t];
-    if (t == 0u) { st->lost = 0u; st->done = 0u; st->lastError = -1.0f; st->iterations = 0u; st->sumRegError = 0.0f; st->sumRegWeight = 0.0f; st->numCorr = 0u; st->matrixCondition = 0.0f; }
-}
-
-__global__ void k_icp_begin_level(VhIcpState* st)
-{
-    if (threadIdx.x == 0u) { st->done = 0u; st->lastError = -1.0f; }
-}
-
-// projectiveCorrespondencesKernel :70-125 (getBestCorrespondence1x1 = the target pixel itself)
-__global__ __launch_bounds__(256) void k_icp_correspondences(const float4* input, const float4* inputNormals, const float4* target, const float4* targetNormals,
-                                                             float4* outCorr, float4* outCorrNormals, uint32_t W, uint32_t H, float distThres,
-                                                             float normalThres, float levelFactor, const VhIcpState* st, VhDepthCameraParams cp)
-{
-    if (st->lost || st->done) return;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W * H) return;
-    const float mi = minf();
-    float4 oc = make_float4(mi, mi, mi, mi), on = oc;
-    const float4 p = input[i], n = inputNormals[i];
-    if (p.x != mi && n.x != mi) {
-        const F3 pt = mat_mul_p(st->delta, mk3(p.x, p.y, p.z)), nt = mat_mul_d(st->delta, mk3(n.x, n.y, n.z));
-        // cameraToKinectScreenInt, DSC/DepthCameraUtil.h:74-85, then the division by the level factor (both truncate)
-        int sx = f2i((pt.x * cp.fx / pt.z + cp.mx) + 0.5f), sy = f2i((pt.y * cp.fy / pt.z + cp.my) + 0.5f);
-        sx = f2i((float)sx / levelFactor); sy = f2i((float)sy / levelFactor);
-        if (sx >= 0 && sy >= 0 && sx < (int)W && sy < (int)H) {
-            const float4 tp = target[(uint32_t)sy * W + (uint32_t)sx];
-            float4 tn = targetNormals[(uint32_t)sy * W + (uint32_t)sx];
-            if (tp.x != mi && tn.x != mi) {
-                const float dx = pt.x - tp.x, dy = pt.y - tp.y, dz = pt.z - tp.z;
-                const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-                const float dNormal = nt.x * tn.x + nt.y * tn.y + nt.z * tn.z;
-                if (d <= distThres && dNormal >= normalThres) {
-                    oc = tp;
-                    tn.w = fmaxf(0.0f, 0.5f * ((1.0f - d / distThres) + (1.0f - cam_to_proj_z(cp, pt.z)))); // weight of the pair
-                    on = tn;
-                }
-            }
-        }
-    }
-    outCorr[i] = oc;
-    outCorrNormals[i] = on;
-}
-
-// scanScanElementsCS :130-188: lane x sums pixels [12x, 12x+12) in order, the 64 lanes of a wave are reduced with the
-// reference's tree (+32, +16, ... +1) and lane 0 writes the wave's 30 terms.
-__global__ __launch_bounds__(64) void k_icp_build_system(uint32_t W, uint32_t H, float* partials, const float4* input, const float4* corr,
-                                                         const float4* corrNormals, const VhIcpState* st)
-{
-    if (st->lost || st->done) return;
-    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
-    const float mi = minf();
-    float acc[kIcpTerms];
-#pragma unroll
-    for (uint32_t k = 0; k < kIcpTerms; k++) acc[k] = 0.0f;
-    for (uint32_t w = 0; w < kIcpWindow; w++) {
-        const uint32_t idx = kIcpWindow * x + w;
-        if (idx % W < W && idx / W < H) {
-            const float4 tp = corr[idx], ip = input[idx], tn = corrNormals[idx];
-            if (tp.x != mi && ip.x != mi && tn.x != mi) {
-                const F3 q = mat_mul_p(st->delta, mk3(ip.x, ip.y, ip.z)); // moving point
-                const F3 pT = mk3(tp.x, tp.y, tp.z), n = mk3(tn.x, tn.y, tn.z);
-                const float weight = tn.w;
-                // buildRowSystemMatrixPlane :70-82, buildRowRHSPlane :85-88
-                const float row[6] = { n.x * q.y - n.y * q.x, n.z * q.x - n.x * q.z, n.y * q.z - n.z * q.y, -n.x, -n.y, -n.z };
-                const float b = n.x * (q.x - pT.x) + n.y * (q.y - pT.y) + n.z * (q.z - pT.z);
-                uint32_t at = 0;
-#pragma unroll
-                for (uint32_t r = 0; r < 6u; r++) {
-#pragma unroll
-                    for (uint32_t c = r; c < 6u; c++) acc[at + c - r] += weight * row[r] * row[c];
-                    at += 6u - r;
-                    acc[21u + r] += weight * row[r] * b;
-                }
-                const float dN = (pT.x - q.x) * n.x + (pT.y - q.y) * n.y + (pT.z - q.z) * n.z;
-                acc[27] += weight * dN * dN;
-                acc[28] += weight;
-                acc[29] += 1.0f;
-            }
-        }
-    }
-    const uint32_t lane = lane_id();
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (uint32_t k = 0; k < kIcpTerms; k++) {
-            const float other = __shfl_down(acc[k], off);
-            if ((int)lane < off) acc[k] += other;
-        }
-    }
-    if (lane == 0u) {
-#pragma unroll
-        for (uint32_t k = 0; k < kIcpTerms; k++) partials[(size_t)blockIdx.x * kIcpTerms + k] = acc[k];
-    }
-}
-
-// reductionSystemCPU (.cpp:52-92) for term t: the wave partials summed in their order; eight loads in flight
-VHD float icp_sum_term(const float* partials, uint32_t nPartials, uint32_t t)
-{
-    float sum = 0.0f;
-    uint32_t k = 0;
-    for (; k + 8u <= nPartials; k += 8u) {
-        float v[8];
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++) v[j] = partials[(size_t)(k + j) * kIcpTerms + t];
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++) sum += v[j];
-    }
-    for (; k < nPartials; k++) sum += partials[(size_t)k * kIcpTerms + t];
-    return sum;
-}
-
-// The 6x6 symmetric system solved through its eigen-decomposition (cyclic Jacobi, double precision):
-// x = V diag(1/l_i) V^T b with eigenvalues below 6 eps * l_max (and exact zeros) dropped, which is what Eigen's JacobiSVD::solve returns
-// for a symmetric positive semi-definite matrix.  A is destroyed; returns the condition number l_max / l_min.
-VHD float icp_solve_6x6(double (&A)[6][6], const double (&b)[6], double (&xs)[6])
-{
-    // cyclic Jacobi on A (symmetric): A -> diag, V accumulates the rotations
-    double V[6][6];
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 6; j++) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 30; sweep++) {
-        double off = 0.0, diag = 0.0;
-        for (int i = 0; i < 6; i++) {
-            diag += A[i][i] * A[i][i];
-            for (int j = i + 1; j < 6; j++) off += A[i][j] * A[i][j];
-        }
-        if (off <= 1e-26 * diag) break; // eigenvalues to ~1e-13 relative: far below what the float results can show
-        for (int p = 0; p < 5; p++)
-            for (int q = p + 1; q < 6; q++) {
-                if (fabs(A[p][q]) < 1e-300) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-                const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-                for (int k = 0; k < 6; k++) { // columns p, q
-                    const double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - s * akq;
-                    A[k][q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < 6; k++) { // rows p, q
-                    const double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - s * aqk;
-                    A[q][k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < 6; k++) {
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
-    double lmax = 0.0, lmin = 1e300;
-    for (int i = 0; i < 6; i++) { const double l = fabs(A[i][i]); lmax = l > lmax ? l : lmax; lmin = l < lmin ? l : lmin; }
-    for (int k = 0; k < 6; k++) xs[k] = 0.0;
-    for (int i = 0; i < 6; i++) {
-        const double l = fabs(A[i][i]);
-        // JacobiSVD::rank() (SVD/JacobiSVD.h:683-691, threshold() :733-738): a singular value counts unless it is exactly
-        // zero or strictly below diagSize * epsilon * s_0; one sitting on the threshold is kept
-        if (l == 0.0 || l < 6.0 * 1.1920928955078125e-7 * lmax) continue;
-        double proj = 0.0;
-        for (int k = 0; k < 6; k++) proj += V[k][i] * b[k];
-        proj /= A[i][i];
-        for (int k = 0; k < 6; k++) xs[k] += V[k][i] * proj;
-    }
-    return (float)(lmax / lmin);
-}
-
-// The 30 summed terms -> A (both triangles), b; false when ATA.isZero(): Eigen's DenseBase::isZero with the default
-// dummy_precision of float (Core/CwiseNullaryOp.h:482-489, Core/MathFunctions.h:653-657, Core/NumTraits.h:94), i.e.
-// |a_ij| <= 1e-5f for every entry.  A NaN entry is not "zero" (the comparison is false): the solve goes on and the
-// rigidity check rejects the NaN step.
-VHD bool icp_system_from_terms(const float* terms, double (&A)[6][6], double (&b)[6])
-{
-    uint32_t at = 0;
-    bool zero = true;
-    for (uint32_t r = 0; r < 6u; r++) {
-        for (uint32_t c = r; c < 6u; c++) {
-            A[r][c] = A[c][r] = (double)terms[at + c - r];
-            if (!(fabsf(terms[at + c - r]) <= 1e-5f)) zero = false;
-        }
-        at += 6u - r;
-        b[r] = (double)terms[21u + r];
-    }
-    return !zero;
-}
-
-// What computeBestRigidAlignment, delinearizeTransformation and align do with the summed system on the host
-// (DSC/CUDACameraTrackingMultiRes.cpp:186-253, 306-318), the solve by icp_solve_6x6.  One lane; `terms` are the 30 sums.
-VHD void icp_solve_step(VhIcpState* st, const float* terms, float angleThres, float distThres, float earlyOut, uint32_t lastInner)
-{
-    double A[6][6], b[6];
-    {
-        const bool nonzero = icp_system_from_terms(terms, A, b);
-        st->sumRegError = terms[27];
-        st->sumRegWeight = terms[28];
-        st->numCorr = (uint32_t)terms[29];
-        st->iterations += 1u;
-        if (!nonzero) { st->lost = 1u; return; } // ATA.isZero(): every |a_ij| <= 1e-5
-    }
-    double xs[6];
-    st->matrixCondition = icp_solve_6x6(A, b, xs);
-    // delinearizeTransformation :186-207: R = Rz(x0) Ry(x1) Rx(x2), t = x[3..5]; mean 0, meanStDev 1
-    const float x0 = (float)xs[0], x1 = (float)xs[1], x2 = (float)xs[2];
-    const float tx = (float)xs[3], ty = (float)xs[4], tz = (float)xs[5];
-    const float cz = cosf(x0), sz = sinf(x0), cy = cosf(x1), sy = sinf(x1), cx = cosf(x2), sx = sinf(x2);
-    float R[9] = { cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx,
-                   sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx,
-                   -sy, cy * sx, cy * cx };
-    // checkRigidTransformation :176-185: angle of the rotation (Eigen::AngleAxisf) and length of the translation
-    const float trace = R[0] + R[4] + R[8];
-    const float angle = acosf(fminf(1.0f, fmaxf(-1.0f, 0.5f * (trace - 1.0f))));
-    const float tnorm = sqrtf(tx * tx + ty * ty + tz * tz);
-    if (!(angle <= angleThres) || !(tnorm <= distThres)) { st->lost = 1u; return; }
-    // deltaTransform = t * deltaTransform
-    float M[16] = { R[0], R[1], R[2], tx, R[3], R[4], R[5], ty, R[6], R[7], R[8], tz, 0.0f, 0.0f, 0.0f, 1.0f };
-    float D[16];
-    for (int k = 0; k < 16; k++) D[k] = st->delta[k];
-    for (int r = 0; r < 4; r++)
-        for (int c = 0; c < 4; c++) {
-            float acc = 0.0f;
-            for (int k = 0; k < 4; k++) acc += M[4 * r + k] * D[4 * k + c];
-            st->delta[4 * r + c] = acc;
-        }
-    // align :306-318, after the last inner iteration: leave the level when the residual stops changing
-    if (lastInner) {
-        if (fabsf(st->lastError - st->sumRegError) < earlyOut) st->done = 1u;
-        st->lastError = st->sumRegError;
-    }
-}
-
-// One wave: reductionSystemCPU (.cpp:52-92) over the wave partials in their order, then icp_solve_step.
-__global__ __launch_bounds__(64) void k_icp_solve(VhIcpState* st, const float* partials, uint32_t nPartials, float angleThres, float distThres, float earlyOut, uint32_t lastInner)
-{
-    __shared__ float sTerms[kIcpTerms];
-    if (st->lost || st->done) return;
-    const uint32_t t = threadIdx.x;
-    if (t < kIcpTerms) sTerms[t] = icp_sum_term(partials, nPartials, t); // one term per lane
-    __syncthreads();
-    if (t != 0u) return;
-    icp_solve_step(st, sTerms, angleThres, distThres, earlyOut, lastInner);
-}
-
-// The state's result into mapped host memory, the tag last (system-scope release: the host polls the tag and then reads
-// the words before it; the idiom of k_publish_words).  One lane.
-VHD void icp_publish(const VhIcpState* __restrict__ st, VhIcpResult* __restrict__ out, uint32_t tag)
-{
-    const VhIcpState s = *st; // (all loads in flight before the first store)
-#pragma unroll
-    for (int k = 0; k < 16; k++) out->delta[k] = s.delta[k];
-    out->lost = s.lost;
-    out->sumRegError = s.sumRegError;
-    out->sumRegWeight = s.sumRegWeight;
-    out->numCorr = s.numCorr;
-    out->matrixCondition = s.matrixCondition;
-    out->iterations = s.iterations;
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    __hip_atomic_store(&out->tag, tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-__global__ void k_icp_publish(const VhIcpState* st, VhIcpResult* out, uint32_t tag)
-{
-    if (blockIdx.x == 0u && threadIdx.x == 0u) icp_publish(st, out, tag);
-}
-
-// One outer iteration of a level whose s_maxInnerIter is 1, in one launch: k_icp_correspondences, k_icp_build_system and
-// k_icp_solve.  A wave owns the 768 pixels k_icp_build_system gives it; for each it computes the pair as
-// k_icp_correspondences does (the same expressions in the same order) and adds it to the 30 running sums, so the
-// correspondence maps are never written.  The wave's terms go to `partials` as before; the wave that draws the last
-// ticket sums the partials in their order and takes the step.  Every pixel's arithmetic and every order of summation is
-// that of the three kernels: the VhIcpState after the launch is theirs bit for bit.
-//
-// The hand-off of the partials crosses XCDs: plain stores, the wave waits for them, an agent-scope release fence, a
-// relaxed agent-scope ticket; the last arriver takes an agent-scope acquire before its plain loads.  No wave waits for
-// another.  Every wave has read delta / lost / done before it draws its ticket, and only the last arriver writes the
-// state, after all tickets are drawn.  *ticket is 0 when the launch starts (the caller clears it on the stream where it
-// runs vh_icp_begin) and the last arriver leaves it 0.
-// publish (may be null): mapped host memory that receives the state after this step, under `tag`.  A step that is
-// skipped (lost / done) changes nothing, so its first wave publishes the state as it stands.
-// A workgroup is ONE wave (64 threads): the ticket is broadcast with a shuffle and the last arriver's __syncthreads()
-// is its own.
-__global__ __launch_bounds__(64) void k_icp_step(const float4* input, const float4* inputNormals, const float4* target, const float4* targetNormals,
-                                                 uint32_t W, uint32_t H, float pairDistThres, float normalThres, float levelFactor, VhDepthCameraParams cp,
-                                                 float* partials, uint32_t* ticket, VhIcpState* st, float angleThres, float distThres, float earlyOut,
-                                                 VhIcpResult* publish, uint32_t tag)
-{
-    __shared__ float sTerms[kIcpTerms];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t skip = st->lost | st->done;
-    float D[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) D[k] = st->delta[k];
-    if (skip) {
-        if (publish && blockIdx.x == 0u && lane == 0u) icp_publish(st, publish, tag);
-        return;
-    }
-    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, nPixels = W * H;
-    const float mi = minf();
-    float acc[kIcpTerms];
-#pragma unroll
-    for (uint32_t k = 0; k < kIcpTerms; k++) acc[k] = 0.0f;
-    // Six pixels at a time: their input loads go out together, then their model loads (a lane that took its 12 pixels one
-    // after the other would wait for 24 dependent round trips); the sums take the pixels in their order all the same.
-    constexpr uint32_t kBatch = 6u;
-    for (uint32_t w0 = 0; w0 < kIcpWindow; w0 += kBatch) {
-        float4 p[kBatch], n[kBatch], tp[kBatch], tn[kBatch];
-        F3 pt[kBatch], nt[kBatch];
-        bool ok[kBatch];
-        uint32_t at[kBatch];
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; j++) {
-            const uint32_t idx = kIcpWindow * x + w0 + j;
-            ok[j] = idx < nPixels;
-            at[j] = ok[j] ? idx : 0u; // (a pixel past the end reads pixel 0 and is dropped)
-            p[j] = input[at[j]];
-            n[j] = inputNormals[at[j]];
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; j++) {
-            at[j] = 0u;
-            pt[j] = nt[j] = mk3(0.0f, 0.0f, 0.0f);
-            ok[j] = ok[j] && p[j].x != mi && n[j].x != mi;
-            if (ok[j]) { // k_icp_correspondences
-                pt[j] = mat_mul_p(D, mk3(p[j].x, p[j].y, p[j].z));
-                nt[j] = mat_mul_d(D, mk3(n[j].x, n[j].y, n[j].z));
-                int sx = f2i((pt[j].x * cp.fx / pt[j].z + cp.mx) + 0.5f), sy = f2i((pt[j].y * cp.fy / pt[j].z + cp.my) + 0.5f);
-                sx = f2i((float)sx / levelFactor); sy = f2i((float)sy / levelFactor);
-                ok[j] = sx >= 0 && sy >= 0 && sx < (int)W && sy < (int)H;
-                if (ok[j]) at[j] = (uint32_t)sy * W + (uint32_t)sx;
-            }
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; j++) { // (a pixel without a pair reads pixel 0 and is dropped)
-            tp[j] = target[at[j]];
-            tn[j] = targetNormals[at[j]];
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; j++) {
-            if (!(ok[j] && tp[j].x != mi && tn[j].x != mi)) continue;
-            const float dx = pt[j].x - tp[j].x, dy = pt[j].y - tp[j].y, dz = pt[j].z - tp[j].z;
-            const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-            const float dNormal = nt[j].x * tn[j].x + nt[j].y * tn[j].y + nt[j].z * tn[j].z;
-            if (!(d <= pairDistThres && dNormal >= normalThres)) continue;
-            const float weight = fmaxf(0.0f, 0.5f * ((1.0f - d / pairDistThres) + (1.0f - cam_to_proj_z(cp, pt[j].z))));
-            // k_icp_build_system (the moving point is pt: the same product)
-            const F3 q = pt[j], pT = mk3(tp[j].x, tp[j].y, tp[j].z), nn = mk3(tn[j].x, tn[j].y, tn[j].z);
-            const float row[6] = { nn.x * q.y - nn.y * q.x, nn.z * q.x - nn.x * q.z, nn.y * q.z - nn.z * q.y, -nn.x, -nn.y, -nn.z };
-            const float b = nn.x * (q.x - pT.x) + nn.y * (q.y - pT.y) + nn.z * (q.z - pT.z);
-            uint32_t o = 0;
-#pragma unroll
-            for (uint32_t r = 0; r < 6u; r++) {
-#pragma unroll
-                for (uint32_t c = r; c < 6u; c++) acc[o + c - r] += weight * row[r] * row[c];
-                o += 6u - r;
-                acc[21u + r] += weight * row[r] * b;
-            }
-            const float dN = (pT.x - q.x) * nn.x + (pT.y - q.y) * nn.y + (pT.z - q.z) * nn.z;
-            acc[27] += weight * dN * dN;
-            acc[28] += weight;
-            acc[29] += 1.0f;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (uint32_t k = 0; k < kIcpTerms; k++) {
-            const float other = __shfl_down(acc[k], off);
-            if ((int)lane < off) acc[k] += other;
-        }
-    }
-    uint32_t drawn = 0u;
-    if (lane == 0u) {
-#pragma unroll
-        for (uint32_t k = 0; k < kIcpTerms; k++) partials[(size_t)blockIdx.x * kIcpTerms + k] = acc[k];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    drawn = (uint32_t)__shfl((int)drawn, 0);
-    if (drawn != gridDim.x - 1u) return;
-    // the last arriver: every wave's partials are out
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane < kIcpTerms) sTerms[lane] = icp_sum_term(partials, gridDim.x, lane); // one term per lane
-    __syncthreads();
-    if (lane != 0u) return;
-    icp_solve_step(st, sTerms, angleThres, distThres, earlyOut, 1u);
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (publish) icp_publish(st, publish, tag);
-}
-
-// ---------------------------------------------------------------------------
-// RGB-D camera tracking: CUDACameraTrackingMultiResRGBD (DSC/CUDACameraTrackingMultiResRGBD.cpp) with
-// scanNormalEquationsDevice (DSC/CUDABuildLinearSystemRGBD.cu:106-201).  One fused kernel per iteration projects the
-// input pixels, looks the model up and sums a point-to-plane row and a photometric row; one wave then solves the
-// system, takes the Gauss-Newton step in Euler angles and leaves the next linearisation point in the VhIcpStateRGBD.
-// Like f5, the whole multi-level solve runs on the stream and the host reads the state once per frame.
-// ---------------------------------------------------------------------------
-
-// computeIntensityAndDerivativesDevice, DSC/CameraUtil.cu:1492-1529: (I, dI/du, dI/dv, 1) by the 3x3 Sobel stencil / 8;
-// MINF on the border and wherever one of the nine taps is MINF.  Only exact products and one exact division: the
-// result is the same bits as the reference's arithmetic in float.
-__global__ __launch_bounds__(256) void k_intensity_and_derivatives(float4* out, const float* in, uint32_t W, uint32_t H)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W * H) return;
-    const uint32_t x = i % W, y = i / W;
-    const float mi = minf();
-    float4 o = make_float4(mi, mi, mi, mi);
-    if (x > 0u && x + 1u < W && y > 0u && y + 1u < H) {
-        float v[3][3]; // v[a][b] = pos_ab of the reference: pixel (x - 1 + a, y - 1 + b)
-        bool ok = true;
-#pragma unroll
-        for (uint32_t a = 0; a < 3u; a++)
-#pragma unroll
-            for (uint32_t b = 0; b < 3u; b++) {
-                v[a][b] = in[(y - 1u + b) * W + (x - 1u + a)];
-                ok = ok && v[a][b] != mi;
-            }
-        if (ok) {
-            float resU = (-1.0f) * v[0][0] + (1.0f) * v[2][0] + (-2.0f) * v[0][1] + (2.0f) * v[2][1] + (-1.0f) * v[0][2] + (1.0f) * v[2][2];
-            resU /= 8.0f;
-            float resV = (-1.0f) * v[0][0] + (-2.0f) * v[1][0] + (-1.0f) * v[2][0] + (1.0f) * v[0][2] + (2.0f) * v[1][2] + (1.0f) * v[2][2];
-            resV /= 8.0f;
-            o = make_float4(v[1][1], resU, resV, 1.0f);
-        }
-    }
-    out[i] = o;
-}
-
-constexpr float kPiF = 3.14159265358979323846f; // Scalar(M_PI) in float
-
-// MatrixBase::eulerAngles(2, 1, 0) of the Eigen the reference vendors (Geometry/EulerAngles.h, 3.2.2), restated for
-// this axis triple on a row-major 3x3 R: R = Rz(e0) Ry(e1) Rx(e2) with e0 in [0, pi].  A negative first angle is moved
-// up by pi and the other two follow (so a small negative z-rotation comes back near (pi, pi, pi)); the Gauss-Newton
-// step is taken in these angles, so the branch matters, not only the rotation they stand for.
-VHD void euler_angles_zyx(const float* R, float* e)
-{
-    float e0 = atan2f(R[3], R[0]);
-    const float c2 = sqrtf(R[8] * R[8] + R[7] * R[7]);
-    float e1;
-    if (e0 < 0.0f) {
-        e0 = e0 + kPiF;
-        e1 = atan2f(-R[6], -c2);
-    } else {
-        e1 = atan2f(-R[6], c2);
-    }
-    const float s1 = sinf(e0), c1 = cosf(e0);
-    e[0] = e0;
-    e[1] = e1;
-    e[2] = atan2f(s1 * R[2] - c1 * R[5], c1 * R[4] - s1 * R[1]);
-}
-
-// Eigen::AngleAxisf(R).angle() (Geometry/AngleAxis.h:159-189 over the quaternion of Quaternion.h:724-760, Shoemake's
-// construction): 2 acos(w), 0 when the quaternion's vector part is below dummy_precision (1e-5)
-VHD float angle_axis_angle(const float* R)
-{
-    const float tr = R[0] + R[4] + R[8];
-    float q[4]; // x, y, z, w
-    if (tr > 0.0f) {
-        float t = sqrtf(tr + 1.0f);
-        q[3] = 0.5f * t;
-        t = 0.5f / t;
-        q[0] = (R[7] - R[5]) * t;
-        q[1] = (R[2] - R[6]) * t;
-        q[2] = (R[3] - R[1]) * t;
-    } else {
-        // (entries are selected, not indexed, and the vector part is summed from named values: an index known only at
-        // run time would put R and q into scratch memory)
-        auto r = [&](int at) {
-            float v = R[0];
-#pragma unroll
-            for (int n = 1; n < 9; n++) v = at == n ? R[n] : v;
-            return v;
-        };
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > r(4 * i)) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        float t = sqrtf(r(4 * i) - r(4 * j) - r(4 * k) + 1.0f);
-        const float qi = 0.5f * t;
-        t = 0.5f / t;
-        q[3] = (r(3 * k + j) - r(3 * j + k)) * t;
-        const float qj = (r(3 * j + i) + r(3 * i + j)) * t;
-        const float qk = (r(3 * k + i) + r(3 * i + k)) * t;
-        q[0] = i == 0 ? qi : j == 0 ? qj : qk;
-        q[1] = i == 1 ? qi : j == 1 ? qj : qk;
-        q[2] = i == 2 ? qi : j == 2 ? qj : qk;
-    }
-    const float n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2];
-    if (n2 < 1e-5f * 1e-5f) return 0.0f;
-    return 2.0f * acosf(fminf(fmaxf(-1.0f, q[3]), 1.0f));
-}
-
-// anglesOld / translationOld of computeBestRigidAlignment (:204-208) from a row-major 4x4
-VHD void rgbd_linearisation_point(VhIcpStateRGBD* st, const float* m)
-{
-    const float R[9] = { m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10] };
-    euler_angles_zyx(R, st->angles);
-    st->translation[0] = m[3];
-    st->translation[1] = m[7];
-    st->translation[2] = m[11];
-}
-
-__global__ void k_icp_rgbd_begin(VhIcpStateRGBD* st, const float* d_deltaEstimate)
-{
-    const uint32_t t = threadIdx.x;
-    if (t < 16u) st->icp.delta[t] = d_deltaEstimate[t];
-    if (t == 0u) {
-        VhIcpState& s = st->icp;
-        s.lost = 0u; s.done = 0u; s.lastError = -1.0f; s.iterations = 0u; s.sumRegError = 0.0f; s.sumRegWeight = 0.0f; s.numCorr = 0u; s.matrixCondition = 0.0f;
-        float m[16];
-        for (int k = 0; k < 16; k++) m[k] = d_deltaEstimate[k];
-        rgbd_linearisation_point(st, m);
-    }
-}
-
-// evalRMat and its three derivatives, DSC/ICPUtil.h:30-126, with (alpha, beta, gamma) = (angles.z, angles.y, angles.x):
-// R = Rz(gamma) Ry(beta) Rx(alpha).  Row-major 3x3.
-VHD void eval_r(float ca, float cb, float cg, float sa, float sb, float sg, float* R)
-{
-    R[0] = cg * cb; R[1] = -sg * ca + cg * sb * sa; R[2] = sg * sa + cg * sb * ca;
-    R[3] = sg * cb; R[4] = cg * ca + sg * sb * sa;  R[5] = -cg * sa + sg * sb * ca;
-    R[6] = -sb;     R[7] = cb * sa;                 R[8] = cb * ca;
-}
-VHD void eval_r_dalpha(float ca, float cb, float cg, float sa, float sb, float sg, float* R)
-{
-    R[0] = 0.0f; R[1] = sg * sa + cg * sb * ca;  R[2] = sg * ca - cg * sb * sa;
-    R[3] = 0.0f; R[4] = -cg * sa + sg * sb * ca; R[5] = -cg * ca - sg * sb * sa;
-    R[6] = 0.0f; R[7] = cb * ca;                 R[8] = -cb * sa;
-}
-VHD void eval_r_dbeta(float ca, float cb, float cg, float sa, float sb, float sg, float* R)
-{
-    R[0] = -cg * sb; R[1] = cg * cb * sa; R[2] = cg * cb * ca;
-    R[3] = -sg * sb; R[4] = sg * cb * sa; R[5] = sg * cb * ca;
-    R[6] = -cb;      R[7] = -sb * sa;     R[8] = -sb * ca;
-}
-VHD void eval_r_dgamma(float ca, float cb, float cg, float sa, float sb, float sg, float* R)
-{
-    R[0] = -sg * cb; R[1] = -cg * ca - sg * sb * sa; R[2] = cg * sa - sg * sb * ca;
-    R[3] = cg * cb;  R[4] = -sg * ca + cg * sb * sa; R[5] = sg * sa + cg * sb * ca;
-    R[6] = 0.0f;     R[7] = 0.0f;                    R[8] = 0.0f;
-}
-VHD F3 mat3_mul(const float* M, F3 v)
-{
-    return mk3(M[0] * v.x + M[1] * v.y + M[2] * v.z, M[3] * v.x + M[4] * v.y + M[5] * v.z, M[6] * v.x + M[7] * v.y + M[8] * v.z);
-}
-
-// lane window of the RGB-D build step (CUDABuildLinearSystemRGBD.cpp:31-32)
-__host__ __device__ inline uint32_t icp_rgbd_window(uint32_t level) { return level == 0u ? kIcpWindow : (kIcpWindow / (4u * level) > 1u ? kIcpWindow / (4u * level) : 1u); }
-
-// addToLocalSystem (.cu:78-104): one row J (6) with residual r and weight w into the lane's 30 terms
-VHD void rgbd_add_row(float (&acc)[kIcpTerms], const float (&J)[6], float r, float w)
-{
-    uint32_t at = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < 6u; i++) {
-#pragma unroll
-        for (uint32_t j = i; j < 6u; j++) acc[at + j - i] += J[i] * J[j] * w;
-        at += 6u - i;
-        acc[21u + i] -= J[i] * r * w; // -J^T F
-    }
-    acc[27] += w * (r * r);
-    acc[28] += w;
-    acc[29] += 1.0f;
-}
-
-// scanNormalEquationsDevice :106-201.  Lane x sums pixels [win x, win x + win) in order, the 64 lanes of the wave are
-// reduced with the +32 ... +1 tree (the reference's warpReduce) and lane 0 writes the wave's 30 terms: the shape and
-// order of k_icp_build_system.
-//
-// Fenced reference defect: the reference converts floor(u), floor(v) of the projection to int for the bilinear lookup
-// whatever their size; a point projected far off screen makes that an out-of-range float -> int conversion.  Such a
-// pixel can never pair up (its nearest-neighbour lookup, truncating u + 0.5, lies outside the image and returns MINF),
-// so it is rejected before any conversion: u + 0.5 and v + 0.5 must lie in (-1, W) and (-1, H).
-//
-// This kernel has a twin: k_icp_rgbd_step (below) restates the per-pixel arithmetic with the loads of several pixels in
-// flight, and must leave the same bits (tests/test_gpu_native_rgbd_tracking.py compares the two after every iteration).
-// A change to an expression or to an order of summation here is a change there too.
-__global__ __launch_bounds__(64) void k_icp_rgbd_build_system(uint32_t W, uint32_t H, uint32_t window, float* partials, const float4* inPos,
-                                                              const float4* inNormal, const float* inIntensity, const float4* tgtPos,
-                                                              const float4* tgtNormal, const float4* tgtIntensity4, VhIcpRGBDParams prm,
-                                                              const VhIcpStateRGBD* st)
-{
-    if (st->icp.lost || st->icp.done) return;
-    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
-    const float mi = minf();
-    // evalRMat(anglesOld) and the derivatives, once per lane (angles.x = gamma, .y = beta, .z = alpha)
-    const float ga = st->angles[0], be = st->angles[1], al = st->angles[2];
-    const float ca = cosf(al), cb = cosf(be), cg = cosf(ga), sa = sinf(al), sb = sinf(be), sg = sinf(ga);
-    float R[9], Ralpha[9], Rbeta[9], Rgamma[9];
-    eval_r(ca, cb, cg, sa, sb, sg, R);
-    eval_r_dgamma(ca, cb, cg, sa, sb, sg, Ralpha); // the reference's assignment (:133-135): Ralpha = evalR_dGamma, ...
-    eval_r_dbeta(ca, cb, cg, sa, sb, sg, Rbeta);
-    eval_r_dalpha(ca, cb, cg, sa, sb, sg, Rgamma);
-    const F3 tOld = mk3(st->translation[0], st->translation[1], st->translation[2]);
-    float acc[kIcpTerms];
-#pragma unroll
-    for (uint32_t k = 0; k < kIcpTerms; k++) acc[k] = 0.0f;
-    for (uint32_t w = 0; w < window; w++) {
-        const uint32_t idx = window * x + w;
-        if (!(idx % W < W && idx / W < H)) continue;
-        const float4 p4 = inPos[idx], n4 = inNormal[idx];
-        const float iIn = inIntensity[idx];
-        if (p4.x == mi || p4.y == mi || p4.z == mi || n4.x == mi || n4.y == mi || n4.z == mi || iIn == mi) continue;
-        const F3 p = mk3(p4.x, p4.y, p4.z);
-        const F3 rp = mat3_mul(R, p), nT = mat3_mul(R, mk3(n4.x, n4.y, n4.z));
-        const F3 pT = mk3(rp.x + tOld.x, rp.y + tOld.y, rp.z + tOld.z);
-        // pProjTrans = I pInputTransformed, I = [fx 0 mx; 0 fy my; 0 0 1]
-        const F3 pp = mk3(prm.fx * pT.x + 0.0f * pT.y + prm.mx * pT.z, 0.0f * pT.x + prm.fy * pT.y + prm.my * pT.z, 0.0f * pT.x + 0.0f * pT.y + 1.0f * pT.z);
-        if (!(pp.z > 0.0f)) continue;
-        const float u = pp.x / pp.z, v = pp.y / pp.z; // dehomogenize
-        const float un = u + 0.5f, vn = v + 0.5f;
-        if (!(un > -1.0f && un < (float)W && vn > -1.0f && vn < (float)H)) continue; // the fence (above)
-        // getValueNearestNeighbour, ICPUtil.h:188-197
-        const int ui = f2i(un), vi = f2i(vn);
-        if (ui < 0 || ui >= (int)W || vi < 0 || vi >= (int)H) continue;
-        const float4 tp = tgtPos[(uint32_t)vi * W + (uint32_t)ui], tn = tgtNormal[(uint32_t)vi * W + (uint32_t)ui];
-        // bilinearInterpolationFloat4, ICPUtil.h:129-156 (the same arithmetic as bilinear_float4)
-        const float4 it = bilinear_float4(u, v, tgtIntensity4, W, H);
-        if (tp.x == mi || tp.y == mi || tp.z == mi || tn.x == mi || tn.y == mi || tn.z == mi || it.x == mi || it.y == mi || it.z == mi) continue;
-        const F3 phiA = mat3_mul(Ralpha, pT), phiB = mat3_mul(Rbeta, pT), phiG = mat3_mul(Rgamma, pT);
-        const F3 diff = mk3(tp.x - pT.x, tp.y - pT.y, tp.z - pT.z);
-        const float dDist = sqrtf(diff.x * diff.x + diff.y * diff.y + diff.z * diff.z);
-        const float dNormal = tn.x * nT.x + tn.y * nT.y + tn.z * nT.z;
-        if (!(dDist <= prm.distThres && dNormal >= prm.normalThres)) continue; // both rows need it
-        {   // point to plane, :156-168 (z of the UNtransformed input point in the weight)
-            const float wD = fmaxf(0.0f, 0.5f * ((1.0f - dDist / prm.distThres) + (1.0f - p.z / prm.sensorMaxDepth)));
-            const float J[6] = { -(tn.x * phiA.x + tn.y * phiA.y + tn.z * phiA.z), -(tn.x * phiB.x + tn.y * phiB.y + tn.z * phiB.z),
-                                 -(tn.x * phiG.x + tn.y * phiG.y + tn.z * phiG.z), -tn.x, -tn.y, -tn.z };
-            const float r = tn.x * diff.x + tn.y * diff.y + tn.z * diff.z;
-            rgbd_add_row(acc, J, r, prm.weightDepth * wD);
-        }
-        // colour, :170-185: J = dI (1x2) * dehomogenizeDerivative (2x3) * K (3x3) * phi
-        const float dI = it.x - iIn;
-        const float gu = it.y, gv = it.z;
-        const float absDI = sqrtf(dI * dI); // norm1D of the 1x1 residual
-        if (absDI <= prm.colorThres && sqrtf(gu * gu + gv * gv) > prm.colorGradientMin) {
-            const float wC = fmaxf(0.0f, 1.0f - absDI / prm.colorThres);
-            const float iz = 1.0f / pp.z, wSq = pp.z * pp.z;
-            const float d0 = gu * iz, d1 = gv * iz, d2 = gu * (-pp.x / wSq) + gv * (-pp.y / wSq); // dI PI
-            const F3 g = mk3(d0 * prm.fx, d1 * prm.fy, d0 * prm.mx + d1 * prm.my + d2);         // (dI PI) K
-            const float J[6] = { g.x * phiA.x + g.y * phiA.y + g.z * phiA.z, g.x * phiB.x + g.y * phiB.y + g.z * phiB.z,
-                                 g.x * phiG.x + g.y * phiG.y + g.z * phiG.z, g.x, g.y, g.z };
-            rgbd_add_row(acc, J, dI, prm.weightColor * wC);
-        }
-    }
-    const uint32_t lane = lane_id();
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (uint32_t k = 0; k < kIcpTerms; k++) {
-            const float other = __shfl_down(acc[k], off);
-            if ((int)lane < off) acc[k] += other;
-        }
-    }
-    if (lane == 0u) {
-#pragma unroll
-        for (uint32_t k = 0; k < kIcpTerms; k++) partials[(size_t)blockIdx.x * kIcpTerms + k] = acc[k];
-    }
-}
-
-// computeBestRigidAlignment, delinearizeTransformation and checkRigidTransformation
-// (DSC/CUDACameraTrackingMultiResRGBD.cpp:166-237) and the residual early-out of align (:329-350) on the 30 summed terms.
-// Unlike f5, the solution is an increment of the absolute Euler angles and translation of delta
-// (xNew = [anglesOld; translationOld] + x), and the rigidity check is on the new delta itself.  ATA.isZero() and a failed
-// check both set lost; the reference would go on iterating with a matrix of -inf there.  One lane.
-VHD void icp_rgbd_solve_step(VhIcpStateRGBD* st, const float* terms, float angleThres, float distThres, float earlyOut)
-{
-    VhIcpState& s = st->icp;
-    double A[6][6], b[6];
-    const bool nonzero = icp_system_from_terms(terms, A, b);
-    s.sumRegError = terms[27];
-    s.sumRegWeight = terms[28];
-    s.numCorr = (uint32_t)terms[29];
-    s.iterations += 1u;
-    if (!nonzero) { s.lost = 1u; return; }
-    double xs[6];
-    s.matrixCondition = icp_solve_6x6(A, b, xs);
-    float x[6];
-    for (int k = 0; k < 3; k++) x[k] = st->angles[k] + (float)xs[k];
-    for (int k = 0; k < 3; k++) x[3 + k] = st->translation[k] + (float)xs[3 + k];
-    // delinearizeTransformation :177-194: R = Rz(x0) Ry(x1) Rx(x2), t = x[3..5]; mean 0, meanStDev 1
-    const float cz = cosf(x[0]), sz = sinf(x[0]), cy = cosf(x[1]), sy = sinf(x[1]), cx = cosf(x[2]), sx = sinf(x[2]);
-    const float R[9] = { cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx,
-                         sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx,
-                         -sy, cy * sx, cy * cx };
-    // checkRigidTransformation :166-175 (a NaN fails it, as in f5)
-    const float angle = angle_axis_angle(R);
-    const float tnorm = sqrtf(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
-    if (!(angle <= angleThres) || !(tnorm <= distThres)) { s.lost = 1u; return; }
-    const float M[16] = { R[0], R[1], R[2], x[3], R[3], R[4], R[5], x[4], R[6], R[7], R[8], x[5], 0.0f, 0.0f, 0.0f, 1.0f };
-    for (int k = 0; k < 16; k++) s.delta[k] = M[k];
-    rgbd_linearisation_point(st, M);
-    // align :345-350, after every outer iteration
-    if (fabsf(s.lastError - s.sumRegError) < earlyOut) s.done = 1u;
-    s.lastError = s.sumRegError;
-}
-
-// One wave: reductionSystemCPU (CUDABuildLinearSystemRGBD.cpp:46-86) over the wave partials in their order, then
-// icp_rgbd_solve_step.
-__global__ __launch_bounds__(64) void k_icp_rgbd_solve(VhIcpStateRGBD* st, const float* partials, uint32_t nPartials, float angleThres, float distThres, float earlyOut)
-{
-    __shared__ float sTerms[kIcpTerms];
-    if (st->icp.lost || st->icp.done) return;
-    const uint32_t t = threadIdx.x;
-    if (t < kIcpTerms) sTerms[t] = icp_sum_term(partials, nPartials, t);
-    __syncthreads();
-    if (t != 0u) return;
-    icp_rgbd_solve_step(st, sTerms, angleThres, distThres, earlyOut);
-}
-
-// bilinear_float4_taps on four taps that are in registers already: tap[0..3] = (px, py), (px + 1, py), (px, py + 1),
-// (px + 1, py + 1), in[k] whether tap k lies inside the image.  The same arithmetic in the same order.
-VHD float4 bilinear_float4_loaded(float x, float y, const float4 (&tap)[4], const bool (&in)[4])
-{
-    const int px = (int)floorf(x), py = (int)floorf(y);
-    const float alpha = x - (float)px, beta = y - (float)py;
-    const float mi = minf();
-    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-    float w0 = 0.0f, w1 = 0.0f;
-    auto add = [&](uint32_t k, float wgt, float4& s, float& w) {
-        const float4 v = tap[k];
-        if (in[k] && v.x != mi && v.y != mi && v.z != mi) { s = f4_add(s, f4_scale(wgt, v)); w += wgt; }
-    };
-    add(0u, 1.0f - alpha, s0, w0);
-    add(1u, alpha, s0, w0);
-    add(2u, 1.0f - alpha, s1, w1);
-    add(3u, alpha, s1, w1);
-    const float4 p0 = f4_div(s0, w0), p1 = f4_div(s1, w1);
-    float4 ss = make_float4(0.f, 0.f, 0.f, 0.f);
-    float ww = 0.0f;
-    if (w0 > 0.0f) { ss = f4_add(ss, f4_scale(1.0f - beta, p0)); ww += (1.0f - beta); }
-    if (w1 > 0.0f) { ss = f4_add(ss, f4_scale(beta, p1)); ww += beta; }
-    return ww > 0.0f ? f4_div(ss, ww) : make_float4(mi, mi, mi, mi);
-}
-
-// One outer iteration of the RGB-D align in one launch: k_icp_rgbd_build_system and k_icp_rgbd_solve.  A wave owns the
-// pixels k_icp_rgbd_build_system gives it (lane x: [kWindow x, kWindow x + kWindow)) and sums them in that order with
-// the same expressions; the wave's terms go to `partials`, and the wave that draws the last ticket sums the partials in
-// their order and takes the step: the VhIcpStateRGBD after the launch is the two kernels' bit for bit.
-//
-// The hand-off is k_icp_step's: plain stores, the wave waits for them, an agent-scope release fence, a relaxed
-// agent-scope ticket; the last arriver takes an agent-scope acquire before its plain loads.  No wave waits for another.
-// Every wave has read lost / done / angles / translation before it draws its ticket, and only the last arriver writes
-// the state, after all tickets are drawn.  *ticket is 0 when the launch starts and the last arriver leaves it 0.
-// publish (may be null): mapped host memory that receives st->icp after this step, under `tag`.  A step that is skipped
-// (lost / done) changes nothing, so its first wave publishes the state as it stands.
-//
-// kBatch pixels of the window at a time: their input loads go out together, then their model loads (position, normal
-// and the four bilinear taps), then the sums take them in their order.  A workgroup is ONE wave.
-template <uint32_t kWindow, uint32_t kBatch>
-__global__ __launch_bounds__(64) void k_icp_rgbd_step(uint32_t W, uint32_t H, float* partials, uint32_t* ticket, const float4* inPos, const float4* inNormal,
-                                                      const float* inIntensity, const float4* tgtPos, const float4* tgtNormal, const float4* tgtIntensity4,
-                                                      VhIcpRGBDParams prm, VhIcpStateRGBD* st, float angleThres, float distThres, float earlyOut,
-                                                      VhIcpResult* publish, uint32_t tag)
-{
-    static_assert(kWindow % kBatch == 0u, "whole batches");
-    __shared__ float sTerms[kIcpTerms];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t skip = st->icp.lost | st->icp.done;
-    const float ga = st->angles[0], be = st->angles[1], al = st->angles[2];
-    const F3 tOld = mk3(st->translation[0], st->translation[1], st->translation[2]);
-    if (skip) {
-        if (publish && blockIdx.x == 0u && lane == 0u) icp_publish(&st->icp, publish, tag);
-        return;
-    }
-    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, nPixels = W * H;
-    const float mi = minf();
-    // evalRMat(anglesOld) and the derivatives, once per lane (k_icp_rgbd_build_system)
-    const float ca = cosf(al), cb = cosf(be), cg = cosf(ga), sa = sinf(al), sb = sinf(be), sg = sinf(ga);
-    float R[9], Ralpha[9], Rbeta[9], Rgamma[9];
-    eval_r(ca, cb, cg, sa, sb, sg, R);
-    eval_r_dgamma(ca, cb, cg, sa, sb, sg, Ralpha);
-    eval_r_dbeta(ca, cb, cg, sa, sb, sg, Rbeta);
-    eval_r_dalpha(ca, cb, cg, sa, sb, sg, Rgamma);
-    float acc[kIcpTerms];
-#pragma unroll
-    for (uint32_t k = 0; k < kIcpTerms; k++) acc[k] = 0.0f;
-    for (uint32_t w0 = 0; w0 < kWindow; w0 += kBatch) {
-        float4 p4[kBatch], n4[kBatch], tp[kBatch], tn[kBatch], tap[kBatch][4];
-        float iIn[kBatch], u[kBatch], v[kBatch];
-        F3 pT[kBatch], nT[kBatch], pp[kBatch];
-        bool ok[kBatch], in[kBatch][4];
-        uint32_t at[kBatch], tapAt[kBatch][4];
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; j++) {
-            const uint32_t idx = kWindow * x + w0 + j;
-            ok[j] = idx < nPixels;
-            at[j] = ok[j] ? idx : 0u; // (a pixel past the end reads pixel 0 and is dropped)
-            p4[j] = inPos[at[j]];
-            n4[j] = inNormal[at[j]];
-            iIn[j] = inIntensity[at[j]];
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; j++) {
-            at[j] = 0u;
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; k++) { tapAt[j][k] = 0u; in[j][k] = false; }
-            u[j] = v[j] = 0.0f;
-            pT[j] = nT[j] = pp[j] = mk3(0.0f, 0.0f, 0.0f);
-            ok[j] = ok[j] && !(p4[j].x == mi || p4[j].y == mi || p4[j].z == mi || n4[j].x == mi || n4[j].y == mi || n4[j].z == mi || iIn[j] == mi);
-            if (!ok[j]) continue;
-            const F3 rp = mat3_mul(R, mk3(p4[j].x, p4[j].y, p4[j].z));
-            nT[j] = mat3_mul(R, mk3(n4[j].x, n4[j].y, n4[j].z));
-            pT[j] = mk3(rp.x + tOld.x, rp.y + tOld.y, rp.z + tOld.z);
-            // pProjTrans = I pInputTransformed, I = [fx 0 mx; 0 fy my; 0 0 1]
-            pp[j] = mk3(prm.fx * pT[j].x + 0.0f * pT[j].y + prm.mx * pT[j].z, 0.0f * pT[j].x + prm.fy * pT[j].y + prm.my * pT[j].z,
-                        0.0f * pT[j].x + 0.0f * pT[j].y + 1.0f * pT[j].z);
-            ok[j] = pp[j].z > 0.0f;
-            if (!ok[j]) continue;
-            u[j] = pp[j].x / pp[j].z; v[j] = pp[j].y / pp[j].z; // dehomogenize
-            const float un = u[j] + 0.5f, vn = v[j] + 0.5f;
-            ok[j] = un > -1.0f && un < (float)W && vn > -1.0f && vn < (float)H; // the fence (k_icp_rgbd_build_system)
-            if (!ok[j]) continue;
-            const int ui = f2i(un), vi = f2i(vn); // getValueNearestNeighbour
-            ok[j] = !(ui < 0 || ui >= (int)W || vi < 0 || vi >= (int)H);
-            if (!ok[j]) continue;
-            at[j] = (uint32_t)vi * W + (uint32_t)ui;
-            const int px = (int)floorf(u[j]), py = (int)floorf(v[j]); // the taps of bilinear_float4_taps
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; k++) {
-                const int tx = px + (int)(k & 1u), ty = py + (int)(k >> 1);
-                in[j][k] = (uint32_t)tx < W && (uint32_t)ty < H;
-                if (in[j][k]) tapAt[j][k] = (uint32_t)ty * W + (uint32_t)tx;
-            }
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; j++) { // (a pixel without a pair, a tap outside the image: pixel 0, dropped)
-            tp[j] = tgtPos[at[j]];
-            tn[j] = tgtNormal[at[j]];
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; k++) tap[j][k] = tgtIntensity4[tapAt[j][k]];
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; j++) {
-            if (!ok[j]) continue;
-            const float4 it = bilinear_float4_loaded(u[j], v[j], tap[j], in[j]);
-            const float4 t4 = tp[j], tn4 = tn[j];
-            if (t4.x == mi || t4.y == mi || t4.z == mi || tn4.x == mi || tn4.y == mi || tn4.z == mi || it.x == mi || it.y == mi || it.z == mi) continue;
-            const F3 q = pT[j];
-            const F3 phiA = mat3_mul(Ralpha, q), phiB = mat3_mul(Rbeta, q), phiG = mat3_mul(Rgamma, q);
-            const F3 diff = mk3(t4.x - q.x, t4.y - q.y, t4.z - q.z);
-            const float dDist = sqrtf(diff.x * diff.x + diff.y * diff.y + diff.z * diff.z);
-            const float dNormal = tn4.x * nT[j].x + tn4.y * nT[j].y + tn4.z * nT[j].z;
-            if (!(dDist <= prm.distThres && dNormal >= prm.normalThres)) continue; // both rows need it
-            {   // point to plane (z of the UNtransformed input point in the weight)
-                const float wD = fmaxf(0.0f, 0.5f * ((1.0f - dDist / prm.distThres) + (1.0f - p4[j].z / prm.sensorMaxDepth)));
-                const float J[6] = { -(tn4.x * phiA.x + tn4.y * phiA.y + tn4.z * phiA.z), -(tn4.x * phiB.x + tn4.y * phiB.y + tn4.z * phiB.z),
-                                     -(tn4.x * phiG.x + tn4.y * phiG.y + tn4.z * phiG.z), -tn4.x, -tn4.y, -tn4.z };
-                const float r = tn4.x * diff.x + tn4.y * diff.y + tn4.z * diff.z;
-                rgbd_add_row(acc, J, r, prm.weightDepth * wD);
-            }
-            // colour: J = dI (1x2) * dehomogenizeDerivative (2x3) * K (3x3) * phi
-            const float dI = it.x - iIn[j];
-            const float gu = it.y, gv = it.z;
-            const float absDI = sqrtf(dI * dI); // norm1D of the 1x1 residual
-            if (absDI <= prm.colorThres && sqrtf(gu * gu + gv * gv) > prm.colorGradientMin) {
-                const float wC = fmaxf(0.0f, 1.0f - absDI / prm.colorThres);
-                const float iz = 1.0f / pp[j].z, wSq = pp[j].z * pp[j].z;
-                const float d0 = gu * iz, d1 = gv * iz, d2 = gu * (-pp[j].x / wSq) + gv * (-pp[j].y / wSq); // dI PI
-                const F3 g = mk3(d0 * prm.fx, d1 * prm.fy, d0 * prm.mx + d1 * prm.my + d2);                 // (dI PI) K
-                const float J[6] = { g.x * phiA.x + g.y * phiA.y + g.z * phiA.z, g.x * phiB.x + g.y * phiB.y + g.z * phiB.z,
-                                     g.x * phiG.x + g.y * phiG.y + g.z * phiG.z, g.x, g.y, g.z };
-                rgbd_add_row(acc, J, dI, prm.weightColor * wC);
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (uint32_t k = 0; k < kIcpTerms; k++) {
-            const float other = __shfl_down(acc[k], off);
-            if ((int)lane < off) acc[k] += other;
-        }
-    }
-    uint32_t drawn = 0u;
-    if (lane == 0u) {
-#pragma unroll
-        for (uint32_t k = 0; k < kIcpTerms; k++) partials[(size_t)blockIdx.x * kIcpTerms + k] = acc[k];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    drawn = (uint32_t)__shfl((int)drawn, 0);
-    if (drawn != gridDim.x - 1u) return;
-    // the last arriver: every wave's partials are out
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane < kIcpTerms) sTerms[lane] = icp_sum_term(partials, gridDim.x, lane); // one term per lane
-    __syncthreads();
-    if (lane != 0u) return;
-    icp_rgbd_solve_step(st, sTerms, angleThres, distThres, earlyOut);
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (publish) icp_publish(&st->icp, publish, tag);
 }
 
 // ---------------------------------------------------------------------------
@@ -4665,8 +3712,6 @@ __global__ __launch_bounds__(256) void k_check_refined_division(uint32_t n, uint
     if (__float_as_uint(q.x) != __float_as_uint(wantP) && !(wantP == 0.0f && q.x == 0.0f)) atomicAdd(&mismatches[0], 1u);
     if (__float_as_uint(q.y) != __float_as_uint(wantB)) atomicAdd(&mismatches[1], 1u);
 }
-
-inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
 // multiply-shift constants of umod_fast for divisor d >= 2
 inline HashMod make_hash_mod(uint32_t d)
@@ -5135,129 +4180,6 @@ int vh_erode_depth_map(float* d_output, const float* d_input, int32_t structureS
     return vh_last_launch_error();
 }
 #undef VH_IMG_LAUNCH
-
-int vh_icp_begin(VhIcpState* d_state, const float* d_deltaEstimate, vhStream_t stream)
-{
-    if (!d_state || !d_deltaEstimate) return VH_ERR_BAD_ARGUMENT;
-    k_icp_begin<<<1, 64, 0, (hipStream_t)stream>>>(d_state, d_deltaEstimate);
-    return vh_last_launch_error();
-}
-int vh_icp_begin_level(VhIcpState* d_state, vhStream_t stream)
-{
-    if (!d_state) return VH_ERR_BAD_ARGUMENT;
-    k_icp_begin_level<<<1, 64, 0, (hipStream_t)stream>>>(d_state);
-    return vh_last_launch_error();
-}
-int vh_icp_projective_correspondences(const float* d_input4, const float* d_inputNormals4, const float* d_target4, const float* d_targetNormals4,
-                                      float* d_output4, float* d_outputNormals4, uint32_t width, uint32_t height, float distThres, float normalThres,
-                                      float levelFactor, const VhIcpState* d_state, const VhDepthCameraParams* cp, vhStream_t stream)
-{
-    if (!d_input4 || !d_inputNormals4 || !d_target4 || !d_targetNormals4 || !d_output4 || !d_outputNormals4 || !d_state || !cp) return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_OK;
-    k_icp_correspondences<<<cdiv(width * height, 256u), 256, 0, (hipStream_t)stream>>>(
-        reinterpret_cast<const float4*>(d_input4), reinterpret_cast<const float4*>(d_inputNormals4), reinterpret_cast<const float4*>(d_target4),
-        reinterpret_cast<const float4*>(d_targetNormals4), reinterpret_cast<float4*>(d_output4), reinterpret_cast<float4*>(d_outputNormals4), width, height,
-        distThres, normalThres, levelFactor, d_state, *cp);
-    return vh_last_launch_error();
-}
-uint32_t vh_icp_num_partials(uint32_t width, uint32_t height) { return cdiv(width * height, 64u * kIcpWindow); }
-int vh_icp_build_linear_system(uint32_t width, uint32_t height, float* d_partials, const float* d_input4, const float* d_corr4, const float* d_corrNormals4,
-                               const VhIcpState* d_state, vhStream_t stream)
-{
-    if (!d_partials || !d_input4 || !d_corr4 || !d_corrNormals4 || !d_state) return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_OK;
-    k_icp_build_system<<<vh_icp_num_partials(width, height), 64, 0, (hipStream_t)stream>>>(
-        width, height, d_partials, reinterpret_cast<const float4*>(d_input4), reinterpret_cast<const float4*>(d_corr4),
-        reinterpret_cast<const float4*>(d_corrNormals4), d_state);
-    return vh_last_launch_error();
-}
-int vh_icp_solve(VhIcpState* d_state, const float* d_partials, uint32_t numPartials, float angleThres, float distThres, float earlyOutResidual,
-                 int lastInnerIteration, vhStream_t stream)
-{
-    if (!d_state || !d_partials) return VH_ERR_BAD_ARGUMENT;
-    k_icp_solve<<<1, 64, 0, (hipStream_t)stream>>>(d_state, d_partials, numPartials, angleThres, distThres, earlyOutResidual, lastInnerIteration ? 1u : 0u);
-    return vh_last_launch_error();
-}
-
-int vh_icp_step(const float* d_input4, const float* d_inputNormals4, const float* d_target4, const float* d_targetNormals4, uint32_t width, uint32_t height,
-                float distThres, float normalThres, float levelFactor, const VhDepthCameraParams* cp, float* d_partials, uint32_t* d_ticket,
-                VhIcpState* d_state, float angleTransThres, float distTransThres, float earlyOutResidual, VhIcpResult* publish, uint32_t tag, vhStream_t stream)
-{
-    if (!d_input4 || !d_inputNormals4 || !d_target4 || !d_targetNormals4 || !cp || !d_partials || !d_ticket || !d_state) return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_ERR_BAD_ARGUMENT; // (no wave would draw the last ticket)
-    k_icp_step<<<vh_icp_num_partials(width, height), 64, 0, (hipStream_t)stream>>>(
-        reinterpret_cast<const float4*>(d_input4), reinterpret_cast<const float4*>(d_inputNormals4), reinterpret_cast<const float4*>(d_target4),
-        reinterpret_cast<const float4*>(d_targetNormals4), width, height, distThres, normalThres, levelFactor, *cp, d_partials, d_ticket, d_state,
-        angleTransThres, distTransThres, earlyOutResidual, publish, tag);
-    return vh_last_launch_error();
-}
-int vh_icp_publish(const VhIcpState* d_state, VhIcpResult* publish, uint32_t tag, vhStream_t stream)
-{
-    if (!d_state || !publish) return VH_ERR_BAD_ARGUMENT;
-    k_icp_publish<<<1, 64, 0, (hipStream_t)stream>>>(d_state, publish, tag);
-    return vh_last_launch_error();
-}
-
-int vh_compute_intensity_and_derivatives(const float* d_intensity, uint32_t width, uint32_t height, float* d_intensityAndDerivatives4, vhStream_t stream)
-{
-    if (!d_intensity || !d_intensityAndDerivatives4) return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_OK;
-    k_intensity_and_derivatives<<<cdiv(width * height, 256u), 256, 0, (hipStream_t)stream>>>(reinterpret_cast<float4*>(d_intensityAndDerivatives4), d_intensity, width, height);
-    return vh_last_launch_error();
-}
-int vh_icp_rgbd_begin(VhIcpStateRGBD* d_state, const float* d_deltaEstimate, vhStream_t stream)
-{
-    if (!d_state || !d_deltaEstimate) return VH_ERR_BAD_ARGUMENT;
-    k_icp_rgbd_begin<<<1, 64, 0, (hipStream_t)stream>>>(d_state, d_deltaEstimate);
-    return vh_last_launch_error();
-}
-uint32_t vh_icp_rgbd_num_partials(uint32_t width, uint32_t height, uint32_t level) { return cdiv(width * height, 64u * icp_rgbd_window(level)); }
-int vh_icp_rgbd_build_linear_system(uint32_t width, uint32_t height, float* d_partials, const float* d_input4, const float* d_inputNormals4,
-                                    const float* d_inputIntensity, const float* d_target4, const float* d_targetNormals4,
-                                    const float* d_targetIntensityAndDerivatives4, const VhIcpRGBDParams* params, const VhIcpStateRGBD* d_state,
-                                    vhStream_t stream)
-{
-    if (!d_partials || !d_input4 || !d_inputNormals4 || !d_inputIntensity || !d_target4 || !d_targetNormals4 || !d_targetIntensityAndDerivatives4 ||
-        !params || !d_state)
-        return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_OK;
-    const uint32_t window = icp_rgbd_window(params->level);
-    k_icp_rgbd_build_system<<<vh_icp_rgbd_num_partials(width, height, params->level), 64, 0, (hipStream_t)stream>>>(
-        width, height, window, d_partials, reinterpret_cast<const float4*>(d_input4), reinterpret_cast<const float4*>(d_inputNormals4), d_inputIntensity,
-        reinterpret_cast<const float4*>(d_target4), reinterpret_cast<const float4*>(d_targetNormals4),
-        reinterpret_cast<const float4*>(d_targetIntensityAndDerivatives4), *params, d_state);
-    return vh_last_launch_error();
-}
-int vh_icp_rgbd_solve(VhIcpStateRGBD* d_state, const float* d_partials, uint32_t numPartials, float angleThres, float distThres, float earlyOutResidual,
-                      vhStream_t stream)
-{
-    if (!d_state || !d_partials) return VH_ERR_BAD_ARGUMENT;
-    k_icp_rgbd_solve<<<1, 64, 0, (hipStream_t)stream>>>(d_state, d_partials, numPartials, angleThres, distThres, earlyOutResidual);
-    return vh_last_launch_error();
-}
-int vh_icp_rgbd_step(uint32_t width, uint32_t height, float* d_partials, uint32_t* d_ticket, const float* d_input4, const float* d_inputNormals4,
-                     const float* d_inputIntensity, const float* d_target4, const float* d_targetNormals4, const float* d_targetIntensityAndDerivatives4,
-                     const VhIcpRGBDParams* params, VhIcpStateRGBD* d_state, float angleThres, float distThres, float earlyOutResidual, VhIcpResult* publish,
-                     uint32_t tag, vhStream_t stream)
-{
-    if (!d_partials || !d_ticket || !d_input4 || !d_inputNormals4 || !d_inputIntensity || !d_target4 || !d_targetNormals4 ||
-        !d_targetIntensityAndDerivatives4 || !params || !d_state)
-        return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_ERR_BAD_ARGUMENT; // (no wave would draw the last ticket)
-    const uint32_t grid = vh_icp_rgbd_num_partials(width, height, params->level);
-#define VH_RGBD_STEP(window, batch)                                                                                                                         \
-    k_icp_rgbd_step<window, batch><<<grid, 64, 0, (hipStream_t)stream>>>(                                                                                   \
-        width, height, d_partials, d_ticket, reinterpret_cast<const float4*>(d_input4), reinterpret_cast<const float4*>(d_inputNormals4), d_inputIntensity, \
-        reinterpret_cast<const float4*>(d_target4), reinterpret_cast<const float4*>(d_targetNormals4),                                                      \
-        reinterpret_cast<const float4*>(d_targetIntensityAndDerivatives4), *params, d_state, angleThres, distThres, earlyOutResidual, publish, tag)
-    switch (icp_rgbd_window(params->level)) { // 12 / 3 / 1
-    case kIcpWindow: VH_RGBD_STEP(kIcpWindow, 6u); break;
-    case 3u: VH_RGBD_STEP(3u, 3u); break;
-    default: VH_RGBD_STEP(1u, 1u); break;
-    }
-#undef VH_RGBD_STEP
-    return vh_last_launch_error();
-}
 
 int vh_stream_out_pass1(const VhHashData* hd, const VhHashParams* hp, uint32_t threadsPerPart, uint32_t start,
                         float radius, const float camPos[3], uint32_t* d_outputCounter, VhSDFBlockDesc* d_output,

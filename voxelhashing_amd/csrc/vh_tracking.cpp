@@ -16,6 +16,47 @@
 #include "vh_params.hpp"
 
 // ---------------------------------------------------------------------------
+// what the two solves share on the host
+// ---------------------------------------------------------------------------
+
+namespace {
+void checkPyramid(unsigned int imageWidth, unsigned int imageHeight, unsigned int levels, const char* who)
+{
+    if (levels == 0 || levels > VH_TRACKING_MAX_LEVELS || (imageWidth >> (levels - 1)) < 2 || (imageHeight >> (levels - 1)) < 2)
+        throw vh::Error(VH_ERR_BAD_ARGUMENT, std::string(who) + ": bad pyramid");
+}
+// The finest level that iterates: a coarse-to-fine solve ends with that level's last iteration.  -1: no level iterates.
+int lastIteratingLevel(const VhTrackingState& ts, size_t levels)
+{
+    for (size_t level = 0; level < levels; level++)
+        if (ts.s_maxOuterIter[level]) return (int)level;
+    return -1;
+}
+// A fused step that is the solve's last publishes the result itself (d_result for it, null for every other): a publishing
+// kernel behind it would be one more dependent launch, and the step's last wave holds the state in its hands anyway ...
+VhIcpResult* publishedByStep(const VhTrackingState& ts, size_t levels, int level, unsigned int outer, VhIcpResult* d_result)
+{
+    return level == lastIteratingLevel(ts, levels) && outer + 1 == ts.s_maxOuterIter[level] ? d_result : nullptr;
+}
+// ... and a solve whose last iteration was not a fused step, or in which no level iterates, publishes afterwards
+void publishAfterwards(const VhIcpState* state, VhIcpResult* d_result, bool published, uint32_t tag, vhStream_t stream)
+{
+    if (d_result && !published) check(vh_icp_publish(state, d_result, tag, stream), "vh_icp_publish");
+}
+// what applyCT returns: -inf everywhere when tracking was lost (isTrackingLost), lastTransform * delta otherwise
+vh::mat4f trackedPose(const VhIcpState& state, const vh::mat4f& lastTransform)
+{
+    vh::mat4f delta;
+    if (state.lost) {
+        for (float& v : delta.m) v = -std::numeric_limits<float>::infinity();
+        return delta;
+    }
+    std::memcpy(delta.m, state.delta, sizeof(delta.m));
+    return lastTransform * delta;
+}
+} // namespace
+
+// ---------------------------------------------------------------------------
 // vh::IcpSolver: the plain solve, enqueued here for both its hosts
 // ---------------------------------------------------------------------------
 
@@ -30,8 +71,7 @@ vh::IcpPyramid vh::icpPyramid(float* map0, float* normal0, const std::vector<Dev
 
 vh::IcpSolver::IcpSolver(unsigned int imageWidth, unsigned int imageHeight, unsigned int levels, const char* who)
 {
-    if (levels == 0 || levels > VH_TRACKING_MAX_LEVELS || (imageWidth >> (levels - 1)) < 2 || (imageHeight >> (levels - 1)) < 2)
-        throw vh::Error(VH_ERR_BAD_ARGUMENT, std::string(who) + ": bad pyramid");
+    checkPyramid(imageWidth, imageHeight, levels, who);
     unsigned int fac = 1;
     for (unsigned int i = 0; i < levels; i++) { // :39-95
         width.push_back(imageWidth / fac);
@@ -58,16 +98,10 @@ void vh::IcpSolver::coarserLevel(const IcpPyramid& p, unsigned int i, vhStream_t
 void vh::IcpSolver::align(const IcpPyramid& in, const IcpPyramid& mdl, const VhTrackingState& ts, const DepthCameraParams& cp, bool fusedStep,
                           VhIcpResult* d_result, uint32_t tag, vhStream_t stream) const
 {
-    const int levels = (int)width.size();
     if (fusedStep) checkHip(hipMemsetAsync(ticket.get(), 0, sizeof(uint32_t), (hipStream_t)stream), "tracking ticket");
     check(vh_icp_begin(state.get(), estimate.get(), stream), "vh_icp_begin");
-    // the step that is the solve's last publishes the result itself: a publishing kernel behind it would be one more
-    // launch in a chain of dependent launches, and the step's last wave holds the state in its hands anyway
-    int lastLevel = -1;
-    for (int level = 0; level < levels && lastLevel < 0; level++)
-        if (ts.s_maxOuterIter[level]) lastLevel = level;
     bool published = false;
-    for (int level = levels - 1; level >= 0; level--) {
+    for (int level = (int)width.size() - 1; level >= 0; level--) {
         const unsigned int W = width[level], H = height[level];
         const float levelFactor = std::pow(2.0f, (float)level);
         float *corr = correspondence[level].get(), *corrN = correspondenceNormal[level].get();
@@ -75,11 +109,11 @@ void vh::IcpSolver::align(const IcpPyramid& in, const IcpPyramid& mdl, const VhT
         for (unsigned int outer = 0; outer < ts.s_maxOuterIter[level]; outer++) {
             const unsigned int inner = ts.s_maxInnerIter[level];
             if (fusedStep && inner == 1u) {
-                const bool last = level == lastLevel && outer + 1 == ts.s_maxOuterIter[level];
+                VhIcpResult* const publish = publishedByStep(ts, width.size(), level, outer, d_result);
                 check(vh_icp_step(in.map[level], in.normal[level], mdl.map[level], mdl.normal[level], W, H, ts.s_distThres[level], ts.s_normalThres[level],
                                   levelFactor, &cp, partials.get(), ticket.get(), state.get(), ts.s_angleTransThres[level], ts.s_distTransThres[level],
-                                  ts.s_residualEarlyOut[level], last ? d_result : nullptr, tag, stream), "vh_icp_step");
-                published = published || (last && d_result);
+                                  ts.s_residualEarlyOut[level], publish, tag, stream), "vh_icp_step");
+                published = published || publish;
                 continue;
             }
             check(vh_icp_projective_correspondences(in.map[level], in.normal[level], mdl.map[level], mdl.normal[level], corr, corrN, W, H, ts.s_distThres[level],
@@ -91,7 +125,7 @@ void vh::IcpSolver::align(const IcpPyramid& in, const IcpPyramid& mdl, const VhT
             }
         }
     }
-    if (d_result && !published) check(vh_icp_publish(state.get(), d_result, tag, stream), "vh_icp_publish"); // (the last level is a three-kernel one, or no level iterates)
+    publishAfterwards(state.get(), d_result, published, tag, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -128,14 +162,7 @@ vh::mat4f CUDACameraTrackingMultiRes::applyCT(float* dInput, float* dInputNormal
     m_icp.align(in, mdl, ts, cp, false, nullptr, 0u, m_stream); // three kernels an iteration; the outcome is copied back
     checkHip(hipMemcpyAsync(&m_lastState, m_icp.state.get(), sizeof(VhIcpState), hipMemcpyDeviceToHost, s), "VhIcpState");
     checkHip(hipStreamSynchronize(s), "applyCT");
-    vh::mat4f out;
-    if (m_lastState.lost) {
-        for (float& v : out.m) v = -std::numeric_limits<float>::infinity();
-        return out;
-    }
-    vh::mat4f delta;
-    std::memcpy(delta.m, m_lastState.delta, sizeof(delta.m));
-    return lastTransform * delta;
+    return trackedPose(m_lastState, lastTransform);
 }
 
 // ---------------------------------------------------------------------------
@@ -151,8 +178,7 @@ vh::IcpIntensityPyramid vh::icpIntensityPyramid(const std::vector<DevicePtr<floa
 
 vh::IcpSolverRGBD::IcpSolverRGBD(unsigned int imageWidth, unsigned int imageHeight, unsigned int levels, const char* who)
 {
-    if (levels == 0 || levels > VH_TRACKING_MAX_LEVELS || (imageWidth >> (levels - 1)) < 2 || (imageHeight >> (levels - 1)) < 2)
-        throw vh::Error(VH_ERR_BAD_ARGUMENT, std::string(who) + ": bad pyramid");
+    checkPyramid(imageWidth, imageHeight, levels, who);
     unsigned int fac = 1;
     uint32_t nPartials = 0;
     for (unsigned int i = 0; i < levels; i++) { // :39-94
@@ -207,16 +233,11 @@ void vh::IcpSolverRGBD::modelPyramid(const IcpPyramid& mdl, const float* dModelC
 void vh::IcpSolverRGBD::align(const IcpPyramid& in, const IcpIntensityPyramid& it, const IcpPyramid& mdl, const VhTrackingStateRGBD& ts,
                               const DepthCameraParams& cp, bool fusedStep, VhIcpResult* d_result, uint32_t tag, vhStream_t stream) const
 {
-    const int levels = (int)width.size();
     if (fusedStep) checkHip(hipMemsetAsync(ticket.get(), 0, sizeof(uint32_t), (hipStream_t)stream), "tracking ticket");
     check(vh_icp_rgbd_begin(state.get(), estimate.get(), stream), "vh_icp_rgbd_begin");
-    // the step that is the solve's last publishes the result itself (as in IcpSolver::align)
-    int lastLevel = -1;
-    for (int level = 0; level < levels && lastLevel < 0; level++)
-        if (ts.base.s_maxOuterIter[level]) lastLevel = level;
     bool published = false;
     // coarse to fine, :289-321; align :329-353 with the loop exits taken on the device
-    for (int level = levels - 1; level >= 0; level--) {
+    for (int level = (int)width.size() - 1; level >= 0; level--) {
         const unsigned int W = width[level], H = height[level];
         const float levelFactor = std::pow(2.0f, (float)level);
         VhIcpRGBDParams prm;
@@ -234,12 +255,12 @@ void vh::IcpSolverRGBD::align(const IcpPyramid& in, const IcpIntensityPyramid& i
         check(vh_icp_begin_level(&state.get()->icp, stream), "vh_icp_begin_level");
         for (unsigned int outer = 0; outer < ts.base.s_maxOuterIter[level]; outer++) {
             if (fusedStep) {
-                const bool last = level == lastLevel && outer + 1 == ts.base.s_maxOuterIter[level];
+                VhIcpResult* const publish = publishedByStep(ts.base, width.size(), level, outer, d_result);
                 check(vh_icp_rgbd_step(W, H, partials.get(), ticket.get(), in.map[level], in.normal[level], inIntensity, mdl.map[level], mdl.normal[level],
                                        modelIntensityAndDerivatives[level].get(), &prm, state.get(), ts.base.s_angleTransThres[level],
-                                       ts.base.s_distTransThres[level], ts.base.s_residualEarlyOut[level], last ? d_result : nullptr, tag, stream),
+                                       ts.base.s_distTransThres[level], ts.base.s_residualEarlyOut[level], publish, tag, stream),
                       "vh_icp_rgbd_step");
-                published = published || (last && d_result);
+                published = published || publish;
                 continue;
             }
             check(vh_icp_rgbd_build_linear_system(W, H, partials.get(), in.map[level], in.normal[level], inIntensity, mdl.map[level], mdl.normal[level],
@@ -248,7 +269,7 @@ void vh::IcpSolverRGBD::align(const IcpPyramid& in, const IcpIntensityPyramid& i
                                     ts.base.s_residualEarlyOut[level], stream), "vh_icp_rgbd_solve");
         }
     }
-    if (d_result && !published) check(vh_icp_publish(&state.get()->icp, d_result, tag, stream), "vh_icp_publish"); // (two kernels an iteration, or no level iterates)
+    publishAfterwards(&state.get()->icp, d_result, published, tag, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -287,14 +308,7 @@ vh::mat4f CUDACameraTrackingMultiResRGBD::applyCT(float* dInput, float* dInputNo
     m_icp.align(in, it, mdl, ts, cp, false, nullptr, 0u, m_stream); // two kernels an iteration; the outcome is copied back
     checkHip(hipMemcpyAsync(&m_lastState, m_icp.state.get(), sizeof(VhIcpStateRGBD), hipMemcpyDeviceToHost, s), "VhIcpStateRGBD");
     checkHip(hipStreamSynchronize(s), "applyCT");
-    vh::mat4f out;
-    if (m_lastState.icp.lost) {
-        for (float& v : out.m) v = -std::numeric_limits<float>::infinity();
-        return out;
-    }
-    vh::mat4f delta;
-    std::memcpy(delta.m, m_lastState.icp.delta, sizeof(delta.m));
-    return lastTransform * delta;
+    return trackedPose(m_lastState.icp, lastTransform);
 }
 
 // ---------------------------------------------------------------------------
@@ -339,50 +353,36 @@ void parseTrackingRGBD(const std::map<std::string, std::string>& values, VhTrack
         f32("s_colorThres" + idx, out->s_colorThres[i], 0.1f);
     }
 }
+// the four C entry points below: a file or a text through parseTracking or parseTrackingRGBD
+template <class State>
+int parseWith(void (*parse)(const vh::ParamValues&, State*), std::istream& in, State* out)
+{
+    vh::ParamValues values;
+    vh::parseStream(in, values);
+    parse(values, out);
+    return VH_OK;
+}
+template <class State>
+int readWith(void (*parse)(const vh::ParamValues&, State*), const char* filename, State* out)
+{
+    if (!filename || !out) return VH_ERR_BAD_ARGUMENT;
+    std::ifstream f(filename);
+    return f.is_open() ? parseWith(parse, f, out) : VH_ERR_IO;
+}
+template <class State>
+int parseTextWith(void (*parse)(const vh::ParamValues&, State*), const char* text, State* out)
+{
+    if (!text || !out) return VH_ERR_BAD_ARGUMENT;
+    std::istringstream in(text);
+    return parseWith(parse, in, out);
+}
 } // namespace
 
 extern "C" {
 
-int vh_tracking_state_read(const char* filename, VhTrackingState* out)
-{
-    if (!filename || !out) return VH_ERR_BAD_ARGUMENT;
-    std::ifstream f(filename);
-    if (!f.is_open()) return VH_ERR_IO;
-    vh::ParamValues values;
-    vh::parseStream(f, values);
-    parseTracking(values, out);
-    return VH_OK;
-}
-
-int vh_tracking_state_parse(const char* text, VhTrackingState* out)
-{
-    if (!text || !out) return VH_ERR_BAD_ARGUMENT;
-    std::istringstream in(text);
-    vh::ParamValues values;
-    vh::parseStream(in, values);
-    parseTracking(values, out);
-    return VH_OK;
-}
-
-int vh_tracking_state_rgbd_read(const char* filename, VhTrackingStateRGBD* out)
-{
-    if (!filename || !out) return VH_ERR_BAD_ARGUMENT;
-    std::ifstream f(filename);
-    if (!f.is_open()) return VH_ERR_IO;
-    vh::ParamValues values;
-    vh::parseStream(f, values);
-    parseTrackingRGBD(values, out);
-    return VH_OK;
-}
-
-int vh_tracking_state_rgbd_parse(const char* text, VhTrackingStateRGBD* out)
-{
-    if (!text || !out) return VH_ERR_BAD_ARGUMENT;
-    std::istringstream in(text);
-    vh::ParamValues values;
-    vh::parseStream(in, values);
-    parseTrackingRGBD(values, out);
-    return VH_OK;
-}
+int vh_tracking_state_read(const char* filename, VhTrackingState* out) { return readWith(parseTracking, filename, out); }
+int vh_tracking_state_parse(const char* text, VhTrackingState* out) { return parseTextWith(parseTracking, text, out); }
+int vh_tracking_state_rgbd_read(const char* filename, VhTrackingStateRGBD* out) { return readWith(parseTrackingRGBD, filename, out); }
+int vh_tracking_state_rgbd_parse(const char* text, VhTrackingStateRGBD* out) { return parseTextWith(parseTrackingRGBD, text, out); }
 
 } // extern "C"
