@@ -49,16 +49,16 @@ def make_color_rgbx(w, h, seed):
     return c
 
 
-def stream_out_replay(scene, hash_of):
-    """Stream-out pass 1 over every entry of an oracle.OracleScene with radius 0 (every live block leaves), replayed
-    slot by slot with the oracle's single operations on that scene.  -> (the oracle's heap pushes in order, the
+def stream_out_replay(scene, hash_of, leaves=None):
+    """Stream-out pass 1 over every entry of an oracle.OracleScene with radius 0 (every live block leaves; or, with
+    leaves(pos) -> bool, the blocks it says), replayed slot by slot with the oracle's single operations on that scene.  -> (the oracle's heap pushes in order, the
     reference's, the extra ids): the reference's list branch pushes again after deleteHashEntryElement, the id
     ptr / 512 of what the slot holds after the delete."""
     want_o, want_r, extras = [], [], []
     table = scene.hash_table()
     for i in range(scene.num_entries()):
         e = table[i].copy()
-        if e["ptr"] == T.FREE_ENTRY:
+        if e["ptr"] == T.FREE_ENTRY or (leaves is not None and not leaves(e["pos"])):
             continue
         own = int(e["ptr"]) // T.SDF_BLOCK_VOXELS
         if e["offset"] != 0 or hash_of(e["pos"]) != i // T.HASH_BUCKET_SIZE:

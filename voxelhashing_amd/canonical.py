@@ -58,7 +58,7 @@ def snapshot(hash_table, sdf_blocks, heap, heap_counter, hp, with_voxels=True):
 def check_invariants(hash_table, heap, heap_counter, hp, sdf_blocks=None):
     """debugHash: free-list has no duplicates; no block is both free and
     allocated; every block is free or allocated; no duplicate positions; no
-    LOCK_ENTRY left behind.  With sdf_blocks: every free block is all-zero."""
+    LOCK_ENTRY left behind.  With sdf_blocks: every free block is all-zero.  Plus check_chains: the collision lists."""
     n_blocks = hp.m_numSDFBlocks
     n_free = (int(heap_counter) + 1) & 0xFFFFFFFF  # the counter is the top index: -1 (wrapped) when empty
     assert 0 <= n_free <= n_blocks, f"heap counter out of range: {heap_counter}"
@@ -85,7 +85,74 @@ def check_invariants(hash_table, heap, heap_counter, hp, sdf_blocks=None):
     if sdf_blocks is not None and n_free:
         raw = sdf_blocks.view(np.uint64).reshape(n_blocks, T.SDF_BLOCK_VOXELS)
         assert not raw[free_ids].any(), "free SDF block is not cleared"
-    return dict(num_occupied=int(occ.sum()), heap_free=n_free)
+    chains = check_chains(hash_table, hp)
+    return dict(num_occupied=int(occ.sum()), heap_free=n_free, **chains)
+
+
+def hash_buckets(pos, num_buckets):
+    """computeHashPos (VoxelUtilHashSDF.h:217-225) of [n,3] int positions: the int products wrap, the modulo is unsigned"""
+    p = np.asarray(pos).astype(np.int64).reshape(-1, 3) & 0xFFFFFFFF
+    h = ((p[:, 0] * 73856093) ^ (p[:, 1] * 19349669) ^ (p[:, 2] * 83492791)) & 0xFFFFFFFF
+    return (h % int(num_buckets)).astype(np.int64)
+
+
+def chain_of(hash_table, hp, bucket):
+    """slots of the collision list that hangs off a bucket's last slot, in list order, as far as it can be followed
+    (it stops in front of a link that leaves the table's rules: check_chains says which)"""
+    ne = hp.m_hashNumBuckets * T.HASH_BUCKET_SIZE
+    last = bucket * T.HASH_BUCKET_SIZE + T.HASH_BUCKET_SIZE - 1
+    out, i = [], last
+    while hash_table["offset"][i] != 0 and len(out) < ne:
+        i = (last + int(hash_table["offset"][i])) % ne
+        if i in out or i == last or hash_table["ptr"][i] == T.FREE_ENTRY:
+            break
+        out.append(i)
+    return out
+
+
+def check_chains(hash_table, hp):
+    """The collision lists, which debugHash does not look at: every occupied entry is where
+    getHashEntryForSDFBlockPos (VoxelUtilHashSDF.h:424-468) finds it -- in one of the ten slots of its home bucket, or
+    on the list that starts at that bucket's last slot (an element's offset counts from the HOME bucket's last slot,
+    :447, :601-606) within the walk's m_hashMaxCollisionLinkedListSize iterations, the first of which looks at the last
+    slot itself -- and the lists are lists: a link leads to an occupied entry of the list's own bucket that is no
+    bucket's last slot (allocBlock :585 skips those), no entry is on two lists or twice on one, and an offset sits
+    only where a link can start.  -> dict(listed = entries on lists, longest = elements of the longest list,
+    heads = buckets with a list)."""
+    nb, bs = hp.m_hashNumBuckets, T.HASH_BUCKET_SIZE
+    ne = nb * bs
+    ptr, off = hash_table["ptr"], hash_table["offset"]
+    slots = np.nonzero(ptr != T.FREE_ENTRY)[0]
+    home_of = dict(zip(slots.tolist(), hash_buckets(hash_table["pos"][slots], nb).tolist()))  # occupied slot -> home bucket
+    place = {}  # slot on a list -> (the list's bucket, its place on it: 1 = the element the last slot links to)
+    heads = np.nonzero(off[bs - 1::bs])[0]
+    longest = 0
+    for b in heads.tolist():
+        last = b * bs + bs - 1
+        i, n = last, 0
+        while off[i] != 0:
+            j = (last + int(off[i])) % ne
+            assert j in home_of, f"bucket {b}: the link of slot {i} (offset {off[i]}) lands on the free slot {j}"
+            assert j % bs != bs - 1, f"bucket {b}: the link of slot {i} lands on slot {j}, the last slot of bucket {j // bs}"
+            assert j not in place or place[j][0] != b, f"bucket {b}: its list comes back to slot {j}: a cycle"
+            assert j not in place, f"slot {j} is on the lists of buckets {place.get(j, (0,))[0]} and {b}"
+            assert home_of[j] == b, f"bucket {b}: the link of slot {i} lands on slot {j}, whose entry belongs to bucket {home_of[j]}"
+            n += 1
+            place[j] = (b, n)
+            i = j
+        longest = max(longest, n)
+    for i in np.nonzero(off)[0].tolist():
+        if i % bs == bs - 1 or i in place:
+            continue
+        assert home_of.get(i) != i // bs, f"slot {i}: an entry in its own bucket, not its last slot and on no list, has offset {off[i]}"
+        assert False, f"slot {i}: offset {off[i]} on an entry that is neither a bucket's last slot nor on a list"
+    # the walk: iteration 0 looks at the last slot, iteration k at the k-th element, k < m_hashMaxCollisionLinkedListSize
+    homes = np.fromiter(home_of.values(), dtype=np.int64, count=len(home_of))
+    lost = [i for i in slots[slots // bs != homes].tolist()
+            if i not in place or place[i][0] != home_of[i] or place[i][1] >= hp.m_hashMaxCollisionLinkedListSize]
+    assert not lost, (f"{len(lost)} entries are not found from their home bucket, first: slot {lost[0]} pos {hash_table['pos'][lost[0]]} "
+                      f"home {home_of[lost[0]]} list and place {place.get(lost[0])}")
+    return dict(listed=len(place), longest=int(longest), heads=int(len(heads)))
 
 
 def check_bucket_summary(hash_table, bucket_count, bucket_bits, hp):
@@ -98,12 +165,14 @@ def check_bucket_summary(hash_table, bucket_count, bucket_bits, hp):
     assert np.array_equal(bits, want != 0), "d_bucketBits out of sync with d_bucketCount"
 
 
-def assert_same_scene(a, b, what=""):
-    """exact equality of two snapshots on the canonical forms"""
+def assert_same_scene(a, b, what="", bucket_counts=True):
+    """exact equality of two snapshots on the canonical forms.  bucket_counts=False: without the per-bucket occupancy --
+    which neighbouring slot a collision-list element takes depends on the order in which concurrent allocs ran"""
     assert a["num_occupied"] == b["num_occupied"], f"{what}: occupied {a['num_occupied']} != {b['num_occupied']}"
     assert np.array_equal(a["positions"], b["positions"]), f"{what}: block position sets differ"
     assert a["heap_free"] == b["heap_free"], f"{what}: heap free {a['heap_free']} != {b['heap_free']}"
-    assert np.array_equal(a["bucket_counts"], b["bucket_counts"]), f"{what}: per-bucket occupancy differs"
+    if bucket_counts:
+        assert np.array_equal(a["bucket_counts"], b["bucket_counts"]), f"{what}: per-bucket occupancy differs"
     if "voxels" in a and "voxels" in b:
         va, vb = a["voxels"], b["voxels"]
         assert np.array_equal(va["weight"], vb["weight"]), f"{what}: voxel weights differ"

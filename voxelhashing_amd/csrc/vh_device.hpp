@@ -412,7 +412,10 @@ VHD bool insert_hash_entry(const VhHashData& hd, const VhHashParams& hp, I3 pos,
         VhHashEntry* e = &hd.d_hash[base + j];
         int prev = atomicCAS(&e->ptr, VH_FREE_ENTRY, VH_LOCK_ENTRY);
         if (prev == VH_FREE_ENTRY) {
-            e->offset = 0;
+            // The offset is left alone: a free entry's is 0 (delete_hash_entry, reset), and the last slot's may
+            // already be a link again -- a thread of this pass that found all ten slots claimed takes the list
+            // branch below and may hang its element off the last slot before this thread has filled it in.  A
+            // store of 0 here cut that element off: in the table, found by no walk from its home bucket.
             store_quad(e, make_int4(pos.x, pos.y, pos.z, ptr));
             bucket_inc(hd, base + j);
             return true;

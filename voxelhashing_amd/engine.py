@@ -613,6 +613,24 @@ class LauncherScene:
         new = np.array([prev - n], dtype=np.uint32)
         check(self.L.vh_memcpy_h2d(self.hd.d_heapCounter, new.ctypes.data, 4, self.stream), "heapCounter")
 
+    def stream_in_settled(self, descs, blocks, lock_token):
+        """vh_stream_in_device: the pass that reads the heap counter on the device and settles itself -- a block that
+        finds no slot keeps no voxels and its SDF block is back on the heap when the call returns
+        -> (indices into descs of the blocks that found no slot, whether the heap held too few free blocks)"""
+        descs = np.ascontiguousarray(descs, dtype=T.DESC_DTYPE)
+        blocks = np.ascontiguousarray(blocks, dtype=T.VOXEL_DTYPE)
+        n = len(descs)
+        d_desc, d_blocks = DeviceBuffer.from_numpy(descs, self.stream), DeviceBuffer.from_numpy(blocks, self.stream)
+        d_failed, d_out = DeviceBuffer(4 * (1 + 2 * n)), DeviceBuffer(4 * (4 + n))
+        check(self.L.vh_memset(d_failed.ptr, 0, d_failed.nbytes, self.stream), "memset")
+        check(self.L.vh_memset(d_out.ptr, 0, d_out.nbytes, self.stream), "memset")
+        check(self.L.vh_stream_in_device(C.byref(self.hd), C.byref(self.hp), n, d_desc.ptr, d_blocks.ptr, lock_token, d_failed.ptr, None, 0xFFFFFFFF,
+                                         d_out.ptr, 1, self.stream), "vh_stream_in_device")
+        out = d_out.download(np.uint32, 4 + n, self.stream)
+        if out[2] != 1 or d_failed.download(np.uint32, 1 + 2 * n, self.stream)[0] != 0:
+            raise RuntimeError("vh_stream_in_device: the pass did not settle (no tag published, or the scratch words were not cleared)")
+        return out[4:4 + int(out[0])].astype(np.int64), bool(out[3])
+
     def download(self, with_voxels=True):
         hp, hd, s = self.hp, self.hd, self.stream
         ne = hp.m_hashNumBuckets * T.HASH_BUCKET_SIZE
