@@ -184,6 +184,14 @@ public:
     void noteTableEdited() { m_tableEpoch++; }
     unsigned int getTableEpoch() const { return m_tableEpoch; }
     void setOptions(const VhSceneOptions& o) { m_options = o; }
+    // How integrate() fuses colour (HashParams::m_colorIntegration): VH_COLOR_RUNNING_AVERAGE, the reference's running 50/50
+    // average (a surface seen once has half its brightness), or VH_COLOR_WEIGHTED_AVERAGE, the average weighted by the
+    // voxel weights the reference left commented out (DSC/VoxelUtilHashSDF.h:241), which lets the RGB-D tracker follow its
+    // own reconstruction.  Holds from the next integrate() / integrateAhead() on (not between integrateAhead() and
+    // integrateFinish(): the frame in progress has its parameters); a scene created from HashParams with the word set
+    // starts with it.  Throws on any other mode.
+    void setColorIntegration(unsigned int mode);
+    unsigned int getColorIntegration() const { return m_hashParams.m_colorIntegration; }
     const VhSceneOptions& getOptions() const { return m_options; }
     vhStream_t getStream() const { return m_stream; }
     int32_t nextLockToken(); // fresh bucket-lock epoch (replaces resetHashBucketMutexCUDA)

@@ -245,6 +245,12 @@ int vh_debug_check_fast_math(float divisor, uint32_t modulus, uint32_t n, uint32
  * the two perspective divisions of a voxel; the same for the blend's division by the weight sum): n pseudo-random
  * operand pairs inside the certified ranges against `/`.  d_mismatches[0]: projection range, [1]: blend range. */
 int vh_debug_check_refined_division(uint32_t n, uint32_t seed, uint32_t* d_mismatches, vhStream_t stream);
+/* Self-check of the colour step of VhHashParams::m_colorIntegration = 1 (the average weighted by the voxel weights): one
+ * launch runs the device function over every (c0, w0, c1, w1) with w1 >= 1, 256 * 256 * 256 * 255 cases, against the
+ * integer formula floor((2 (c0 w0 + c1 w1) + d) / (2 d)), d = w0 + w1, once with each reciprocal its callers hand it.
+ * d_out: four words.  [0] mismatches with 1.0f / d (combineVoxel), [1] with the refined reciprocal of the pass's
+ * certified blocks, [2] the first mismatching case as c0 | w0 << 8 | c1 << 16 | w1 << 24 (0xffffffff: none), [3] 0. */
+int vh_debug_check_weighted_colour(uint32_t* d_out, vhStream_t stream);
 /* measurement, not part of the path: every SIMD of the device runs `wavesPerSimd` waves (1..8), each a chain-free stream of
  * 32 * iters vector instructions (mode 0 v_fma_f32, 1 v_pk_fma_f32, 2 v_add_u32, 3 v_mul_lo_u32); per wave
  * {start, end in 100 MHz ticks, s_memtime ticks spent, HW_ID[19:0] | XCC_ID << 20} into d_stamps (4 words per wave, *numWaves waves: room for
@@ -282,6 +288,10 @@ int vh_scene_rep_get_state(VhSceneRep* s, uint32_t* out);
  * {alloc, compactify, integrate(+gc), count} (TimingLog of the reference) */
 int vh_scene_rep_get_timings(VhSceneRep* s, double out[4]);
 int vh_scene_rep_set_options(VhSceneRep* s, const VhSceneOptions* opt);
+/* setColorIntegration (include/vh.hpp): how the following integrate() calls fuse colour.  VH_COLOR_RUNNING_AVERAGE (0), the
+ * reference's running 50/50 average, or VH_COLOR_WEIGHTED_AVERAGE (1), weighted by the voxel weights; any other mode is
+ * VH_ERR_BAD_ARGUMENT.  The mode is VhHashParams::m_colorIntegration of vh_scene_rep_get_hash_params. */
+int vh_scene_rep_set_color_integration(VhSceneRep* s, uint32_t mode);
 
 /* integrateAhead / integrateFinish: the two halves of integrate() (include/vh.hpp).  *job receives the frame's alloc +
  * compactify passes for vh_raycast_render_co (NULL when the scene's options rule a co-launch out); it belongs to the

@@ -66,8 +66,15 @@ typedef struct VhHashParams {
     int32_t m_streamingGridDimensions[3];
     int32_t m_streamingMinGridPos[3];
     uint32_t m_streamingInitialChunkListSize;
-    uint32_t m_dummy[2];
+    /* The reference's two spare words (m_dummy[2]); the first is a switch the reference does not have.
+     * 0: combineVoxel's colour as the reference computes it, a running 50/50 average (DSC/VoxelUtilHashSDF.h:236-240);
+     * 1: the average weighted by the voxel weights that the reference left commented out at :241,
+     *    uchar((c0 w0 + c1 w1) / (w0 + w1) + 0.5f) per channel.  Set by CUDASceneRepHashSDF::setColorIntegration. */
+    uint32_t m_colorIntegration;
+    uint32_t m_dummy;
 } VhHashParams;
+
+enum { VH_COLOR_RUNNING_AVERAGE = 0, VH_COLOR_WEIGHTED_AVERAGE = 1 };
 
 /* DepthCameraParams, DSC/CUDADepthCameraParams.h:8-19 (32 B). */
 typedef struct VhDepthCameraParams {

@@ -2,7 +2,8 @@
 """Times the fused integrate kernel alone on a dense scene (S2: camera inside a 3 m sphere, 1 cm voxels, cfg3 tables):
 the scene is built with the frame loop, then vh_integrate_fused is launched back to back on the last frame's block list
 (flags 0: nothing is freed, so every launch sees the same list).  With VH_LIB_PATH set, a measurement build of the
-library is timed (voxelhashing_amd.build --out scratch/... -DVH_KNOCKOUT=n)."""
+library is timed (voxelhashing_amd.build --out scratch/... -DVH_KNOCKOUT=n).  --weighted-colour: with the colours fused
+weighted by the voxel weights (HashParams.m_colorIntegration = 1) instead of the running 50/50 average."""
 import argparse
 import ctypes as C
 import json
@@ -21,6 +22,7 @@ def main():
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--gc", action="store_true")
     ap.add_argument("--in-loop", action="store_true", help="no repeated launches: the time stamps of the frame loop's last integrate launch (a -DVH_KNOCKOUT=9 build)")
+    ap.add_argument("--weighted-colour", action="store_true", help="fuse colours weighted by the voxel weights (m_colorIntegration = 1)")
     a = ap.parse_args()
     import torch
     from voxelhashing_amd import engine as E, lib, synth, vhtypes as T
@@ -28,6 +30,7 @@ def main():
     cfg = dict(synth.CONFIGS[a.config], scene=a.scene)
     hp, cp, rp = synth.config_params(cfg)
     spheres, inside, radius = synth.scene(a.scene)
+    hp.m_colorIntegration = T.COLOR_WEIGHTED_AVERAGE if a.weighted_colour else T.COLOR_RUNNING_AVERAGE
     scene = E.CUDASceneRepHashSDF(hp, T.make_scene_options(offline=False, gc=True, starve=15))
     frame = E.DepthFrame(cp)
     for k in range(a.frames):
@@ -78,7 +81,7 @@ def main():
                                                                         staged2=ph[:, 3] - ph[:, 2], voxels2=ph[:, 4] - ph[:, 3], compute2=ph[:, 5] - ph[:, 4], rest=end - ph[:, 5]).items()}
         out["waves_alive_at_us"] = {str(t): int(((start <= t) & (end > t)).sum()) for t in (2, 4, 6, 8, 10, 11, 12, 13, 14, 15, 16, 18)}
         np.save(os.path.join(ROOT, "gpurun_out", "wave_stamps.npy"), raw)
-    print(json.dumps(dict(lib=os.path.basename(lib.LIB_PATH), blocks=n, **out)))
+    print(json.dumps(dict(lib=os.path.basename(lib.LIB_PATH), blocks=n, colour_rule="weighted" if hpp.m_colorIntegration else "running average", **out)))
     scene.integrateFinish(frame, cp)
 
 

@@ -5,7 +5,10 @@ at 640x480 / 4 cm voxels (cfg2's sizes).  Wall time per frame including the one 
 applyCT alone, and the drift against the true trajectory.  One JSON line; with --rgbd a second one for the RGB-D
 tracker (CUDACameraTrackingMultiResRGBD, the reference's default settings with their colour keys) on the same frames.
 
-    python tools/bench_tracking.py [--frames 120] [--width 640 --height 480] [--rgbd]
+    python tools/bench_tracking.py [--frames 120] [--width 640 --height 480] [--rgbd] [--weighted-colour]
+
+--weighted-colour: every scene fuses colours weighted by the voxel weights (HashParams.m_colorIntegration = 1) instead of
+the reference's running 50/50 average; each line names the rule as "colour_rule".
 
 --native: the same loop against the native frame loop with tracking on (engine.Reconstruction.setTracking), in ONE process,
 the two legs alternating --repeats times (tools/bench_ingest.py's scheme): (a) the Python loop exactly as timed above,
@@ -41,6 +44,7 @@ def main():
     ap.add_argument("--native", action="store_true", help="the Python loop against the native tracked loop, legs alternating (one line)")
     ap.add_argument("--repeats", type=int, default=5, help="--native: how often each leg runs")
     ap.add_argument("--only", default=None, choices=("python", "native"), help="--native: one leg alone (for a profiler run)")
+    ap.add_argument("--weighted-colour", action="store_true", help="fuse colours weighted by the voxel weights instead of the running 50/50 average")
     args = ap.parse_args()
     import torch
     from oracle import oracle as O
@@ -48,7 +52,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
     W, H = args.width, args.height
-    hp = T.make_hash_params(500000, 1 << 18, **synth.PARAM_SETS["P4"])
+    hp = T.make_hash_params(500000, 1 << 18, weighted_colour=args.weighted_colour, **synth.PARAM_SETS["P4"])
     cp = T.make_depth_camera_params(W, H)
     rp = T.make_raycast_params(hp, cp)
     spheres, inside, radius = synth.scene("S3")
@@ -63,6 +67,10 @@ def main():
         return native_against_python(args, frames, truth, hp, cp, rp, W, H)
     for kind in (["f5", "rgbd"] if args.rgbd and not args.trajectory else ["f5"]):
         run(args, kind, frames, truth, hp, cp, rp, W, H)
+
+
+def colour_rule(hp):
+    return "weighted" if hp.m_colorIntegration else "running average"
 
 
 def spread(values):
@@ -119,7 +127,7 @@ def native_against_python(args, frames, truth, hp, cp, rp, W, H):
         if args.only != "python":
             nat.append(native_leg())
     out = dict(bench="tracking, Python loop against the native tracked loop", tracker="RGB-D ICP" if args.rgbd else "projective ICP", unit="frames/s",
-               frames=n - 1, repeats=args.repeats)
+               frames=n - 1, repeats=args.repeats, colour_rule=colour_rule(hp))
     t0 = np.asarray(truth[0], np.float64).reshape(4, 4)
     if py:
         last = py[-1]
@@ -213,6 +221,7 @@ def run(args, kind, frames, truth, hp, cp, rp, W, H, quiet=False):
                           ms_per_frame=round(1e3 * dt / n, 3), icp_ms_per_frame=round(icp_ms / n, 3), icp_systems_per_frame=round(iters / n, 2), lost_frames=lost_frames,
                           drift_m=round(float(np.linalg.norm(rel[:3, 3])), 5),
                           drift_deg=round(float(np.degrees(np.arccos(np.clip(0.5 * (np.trace(rel[:3, :3]) - 1), -1, 1)))), 4), path_m=round(float(path), 3),
+                          colour_rule=colour_rule(hp),
                           config=dict(workload=f"S3 orbit, {W}x{H}, P4 voxels, 3 pyramid levels, {settings}, host-fed frames", **({"tracker": "rgbd"} if kind == "rgbd" else {}))))
     if not quiet:
         print(json.dumps(line))

@@ -4,7 +4,7 @@ parameter file, optional mesh at the end) and prints one JSON line with the timi
 
     python tools/replay.py --params zParameters.txt [--tracking zParametersTracking.txt] [--rgbd-tracking] [--sens a.sens b.sens]
                            [--mesh scan.ply] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
-                           [--native [--batch N] [--native-tracking]]
+                           [--native [--batch N] [--native-tracking]] [--weighted-colour]
 
 Without --sens the files named by s_binaryDumpSensorFile[i] in the parameter file are played.  The rendering keys
 (light, material, discontinuity thresholds, s_renderToFile, s_renderToFileDir) come from --params; --render-to switches
@@ -17,7 +17,11 @@ map is rendered into the colour camera with the `.sens` file's extrinsic (unless
 frame.  It is for recorded poses (s_binaryDumpSensorUseTrajectory = true, ...OnlyInit = false) and says why when the
 configuration needs the Python loop (ICP tracking, --record, --render-to, camera calibration).  With --native-tracking the
 native loop tracks the camera itself where the parameter file asks for it (s_binaryDumpSensorUseTrajectory = false): one
-host wait per frame, for the pose; with plain projective ICP, or with --rgbd-tracking with the RGB-D tracker."""
+host wait per frame, for the pose; with plain projective ICP, or with --rgbd-tracking with the RGB-D tracker.
+
+--weighted-colour fuses colours weighted by the voxel weights (CUDASceneRepHashSDF::setColorIntegration) instead of the
+reference's running 50/50 average, in either loop: what the RGB-D tracker needs to follow its own reconstruction.  It is
+not a key of the parameter file; the JSON line names the rule as "colour_rule"."""
 import argparse
 import json
 import os
@@ -42,6 +46,7 @@ def main():
     ap.add_argument("--native", action="store_true", help="play through the native frame loop, fed with raw frames")
     ap.add_argument("--batch", type=int, default=64, help="--native: frames decoded and handed over per call")
     ap.add_argument("--native-tracking", action="store_true", help="--native: let the native loop track the camera (plain ICP, or RGB-D ICP with --rgbd-tracking) when the poses are not recorded")
+    ap.add_argument("--weighted-colour", action="store_true", help="fuse colours weighted by the voxel weights instead of the reference's running 50/50 average")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -59,7 +64,8 @@ def main():
     cs = R.read_calibration_state(args.params)
     if args.camera_calibration:
         cs.s_bUseCameraCalibration = 1
-    rec = R.Reconstruction(g, t, args.sens or None, use_rgbd_tracking=args.rgbd_tracking, render_state=rs, calibration_state=cs)
+    rec = R.Reconstruction(g, t, args.sens or None, use_rgbd_tracking=args.rgbd_tracking, render_state=rs, calibration_state=cs,
+                           weighted_colour=args.weighted_colour)
     if args.native:  # the loop, its pinned buffers and the file, before the clock (the Python loop's reader has loaded its file above)
         try:
             rec.prepare_native(args.batch, tracking=args.native_tracking, tracking_rgbd=args.native_tracking and args.rgbd_tracking)
@@ -75,7 +81,8 @@ def main():
     dt = time.perf_counter() - t0
     out = dict(frames=n, seconds=round(dt, 3), frames_per_s=round(n / dt, 1) if dt > 0 else None, lost_frames=rec.lost_frames,
                blocks=rec.scene.getNumOccupiedBlocks(), heap_free=rec.scene.getHeapFreeCount(),
-               pose_source="recorded trajectory" if g.s_binaryDumpSensorUseTrajectory and not g.s_binaryDumpSensorUseTrajectoryOnlyInit else ("RGB-D ICP" if args.rgbd_tracking else "projective ICP"))
+               pose_source="recorded trajectory" if g.s_binaryDumpSensorUseTrajectory and not g.s_binaryDumpSensorUseTrajectoryOnlyInit else ("RGB-D ICP" if args.rgbd_tracking else "projective ICP"),
+               colour_rule="weighted" if rec.scene.getColorIntegration() else "running average")
     if args.native:  # the loop's statistics ("frames" above is frames read; the loop's own count leaves out invalidFrames)
         out["loop"] = "native"
         out.update({k: (round(v, 6) if isinstance(v, float) else v) for k, v in rec.native.getStats().items() if k != "frames"})

@@ -104,6 +104,11 @@ int vh_scene_rep_get_timings(VhSceneRep* s, double out[4])
     if (!s || !out) return VH_ERR_BAD_ARGUMENT;
     return guarded([&] { s->impl.getTimings(out); });
 }
+int vh_scene_rep_set_color_integration(VhSceneRep* s, uint32_t mode)
+{
+    if (!s || (mode != VH_COLOR_RUNNING_AVERAGE && mode != VH_COLOR_WEIGHTED_AVERAGE)) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { s->impl.setColorIntegration(mode); });
+}
 int vh_scene_rep_set_options(VhSceneRep* s, const VhSceneOptions* opt)
 {
     if (!s || !opt) return VH_ERR_BAD_ARGUMENT;

@@ -545,6 +545,40 @@ VHD Vox unpack_vox(uint2 w) { Vox v; v.sdf = __uint_as_float(w.x); v.cw = w.y; r
 VHD uint2 pack_vox(Vox v) { return make_uint2(__float_as_uint(v.sdf), v.cw); }
 VHD uint32_t pack_cw(uint32_t r, uint32_t g, uint32_t b, uint32_t w) { return r | (g << 8) | (b << 16) | (w << 24); }
 
+// The weighted colour average the reference left commented out (combineVoxel :241), per channel
+//   uchar((c0 w0 + c1 w1) / (w0 + w1) + 0.5f)  =  floor((2 n + d) / (2 d)),  n = c0 w0 + c1 w1,  d = w0 + w1
+// (the float32 formula and the integer one agree for every n <= 255 d, d in 1..510: tests/test_weighted_colour.py).
+// cw0, cw1: the stored voxel's and the observation's colour + weight words; den = (float)(w0 + w1); y: a float within
+// two ulp of 1 / den (the IEEE quotient, or the refined reciprocal the certified path holds for the sdf's division).
+// Returns the three colour bytes with byte 3 clear.  A zero den gives bytes no caller keeps (and no trap).
+//   * n by v_dot4_u32_u8 on {c0, c1, 0, 0} . {w0, w1, 0, 0}, accumulated onto the bit pattern of 2^23: the sum is the
+//     float 2^23 + n as it stands (n <= 130 050), no conversion;
+//   * t = 2 n + d by one fma (exact: an integer below 2^18);
+//   * x = t / 2 d is a multiple of 1 / 2 d: an integer (the ties of n / d, which round up) or at least 1 / 2 d >= 2^-10
+//     from one.  A product with a reciprocal that is an ulp low lands below the tie (thousands of pairs), so the
+//     reciprocal is raised by 2^-21: with y's two ulp and the rounding of the constant's product the factor on x lies
+//     in (1 + 0.37 * 2^-21, 1 + 1.63 * 2^-21) -- above the integer on a tie, and x < 256 moves by less than 2^-12
+//     otherwise;
+//   * floor(x) by the second fma: + (2^23 - 1/2) rounds x - 1/2 to the nearest integer, which is floor(x) for an x just
+//     above an integer or that far below the next (x > 1/2, so the sum is at least 2^23, where floats are the
+//     integers), and leaves it in the low mantissa bits: the low byte of the float is the colour byte.
+// vh_debug_check_weighted_colour runs every (c0, w0, c1, w1) through it, with either reciprocal.
+VHD uint32_t weighted_colour(uint32_t cw0, uint32_t cw1, float den, float y)
+{
+    const uint32_t ww = __builtin_amdgcn_perm(cw1, cw0, 0x0c0c0703u); // w0 | w1 << 8
+    const float dOff = den - 0x1p24f;                                 // (exact)
+    const float yh = y * (0.5f + 0x1p-22f);
+    uint32_t byte[3];
+#pragma unroll
+    for (uint32_t ch = 0; ch < 3; ch++) {
+        const uint32_t cc = __builtin_amdgcn_perm(cw1, cw0, 0x0c0c0400u + ch * 0x0101u);      // c0 | c1 << 8 of the channel
+        const float nf = __uint_as_float(__builtin_amdgcn_udot4(cc, ww, 0x4b000000u, false)); // 2^23 + n
+        const float t = __fmaf_rn(nf, 2.0f, dOff);                                            // 2 n + d
+        byte[ch] = __float_as_uint(__fmaf_rn(t, yh, 0x1p23f - 0.5f));
+    }
+    return __builtin_amdgcn_perm(byte[2], __builtin_amdgcn_perm(byte[1], byte[0], 0x0c0c0400u), 0x0c040100u);
+}
+
 // combineVoxel :229-250
 VHD Vox combine_voxel(const VhHashParams& hp, Vox v0, Vox v1)
 {
@@ -554,8 +588,10 @@ VHD Vox combine_voxel(const VhHashParams& hp, Vox v0, Vox v1)
     // average rounded up: (a | b) - (((a ^ b) >> 1) & 0x7f7f7f7f) on the packed word, all channels at once
     // (tests/test_oracle_math.py checks the identity for all 65 536 pairs against the float formula).
     const uint32_t a = v0.cw & 0x00ffffffu, c = v1.cw & 0x00ffffffu;
-    const uint32_t rgb = (a | c) - (((a ^ c) >> 1) & 0x7f7f7f7fu);
+    uint32_t rgb = (a | c) - (((a ^ c) >> 1) & 0x7f7f7f7fu);
     float w0 = (float)v0.weight(), w1 = (float)v1.weight();
+    // (m_colorIntegration is the same for every voxel of a launch: a scalar branch)
+    if (hp.m_colorIntegration != VH_COLOR_RUNNING_AVERAGE) rgb = weighted_colour(v0.cw, v1.cw, w0 + w1, 1.0f / (w0 + w1));
     out.sdf = (v0.sdf * w0 + v1.sdf * w1) / (w0 + w1);
     uint32_t w = min(hp.m_integrationWeightMax, v0.weight() + v1.weight());
     out.cw = rgb | ((w & 0xffu) << 24);

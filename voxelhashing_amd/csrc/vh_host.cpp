@@ -416,6 +416,13 @@ void CUDASceneRepHashSDF::setLastRigidTransformAndCompactify(const vh::mat4f& t,
     compactifyHashEntries(cp);
 }
 
+void CUDASceneRepHashSDF::setColorIntegration(unsigned int mode)
+{
+    if (mode != VH_COLOR_RUNNING_AVERAGE && mode != VH_COLOR_WEIGHTED_AVERAGE) throw vh::Error(VH_ERR_BAD_ARGUMENT, "setColorIntegration: no such mode");
+    if (m_aheadPending) throw vh::Error(VH_ERR_BAD_ARGUMENT, "setColorIntegration: between integrateAhead() and integrateFinish()");
+    m_hashParams.m_colorIntegration = mode;
+}
+
 const vh::mat4f CUDASceneRepHashSDF::getLastRigidTransform() const
 {
     vh::mat4f r;

@@ -817,7 +817,8 @@ VHD void integrate_block_certified(const VhHashParams& hp, const VhDepthCameraPa
         const f32x2 wOld = (f32x2){ (float)(s0.cw >> 24), (float)(s1.cw >> 24) }, wNew = (f32x2){ (float)(px[0].y >> 24), (float)(px[1].y >> 24) };
         const f32x2 num = (f32x2){ s0.sdf, s1.sdf } * wOld + clamped * wNew;
         const f32x2 den = wOld + wNew; // exact: integers up to 510
-        f32x2 q = div_refined2(num, den, rcp_refined2(den));
+        const f32x2 yDen = rcp_refined2(den);
+        f32x2 q = div_refined2(num, den, yDen);
         const bool odd0 = use0 & !((fabsf(num.x) >= 0x1p-100f) & (fabsf(num.x) < 0x1p90f));
         const bool odd1 = use1 & !((fabsf(num.y) >= 0x1p-100f) & (fabsf(num.y) < 0x1p90f));
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(odd0 | odd1) != 0ull, 0)) {
@@ -830,7 +831,10 @@ VHD void integrate_block_certified(const VhHashParams& hp, const VhDepthCameraPa
             const Vox st = k ? s1 : s0;
             // colour: the byte-wise average rounded up (combine_voxel) is v_lerp_u8 with the rounding bit set; the weight
             // byte comes in by v_perm_b32 (the top byte of the average is not used)
-            const uint32_t rgb = __builtin_amdgcn_lerp(st.cw, px[k].y, 0x01010101u);
+            // (m_colorIntegration: the average weighted by the voxel weights instead, with the reciprocal of the sdf's
+            // division; the same for every voxel of the launch, a scalar branch)
+            uint32_t rgb = __builtin_amdgcn_lerp(st.cw, px[k].y, 0x01010101u);
+            if (hp.m_colorIntegration != VH_COLOR_RUNNING_AVERAGE) rgb = weighted_colour(st.cw, px[k].y, den[k], yDen[k]);
             const uint32_t wSum = min(hp.m_integrationWeightMax, (st.cw >> 24) + (px[k].y >> 24));
             const bool use = k ? use1 : use0;
             v[k].sdf = use ? q[k] : st.sdf;
@@ -3713,6 +3717,34 @@ __global__ __launch_bounds__(256) void k_check_refined_division(uint32_t n, uint
     if (__float_as_uint(q.y) != __float_as_uint(wantB)) atomicAdd(&mismatches[1], 1u);
 }
 
+// weighted_colour (combine_voxel's and integrate_block_certified's colour step with m_colorIntegration = 1) against the
+// integer formula floor((2 n + d) / (2 d)), n = c0 w0 + c1 w1, d = w0 + w1, for EVERY (c0, w0, c1, w1) with w1 >= 1 of one
+// channel (the channels share the arithmetic; the other two carry the value's complement and its swap with c1, so a
+// mix-up of bytes shows too), with each reciprocal a caller hands it: [0] 1.0f / d (combine_voxel), [1] rcp_refined2
+// (the certified path).  Workgroup (c0, c1), thread w0, a loop over w1.  out: {mismatches [0], [1], first mismatch as
+// c0 | w0 << 8 | c1 << 16 | w1 << 24 (the smallest such word; 0xffffffff if none), 0}
+__global__ __launch_bounds__(256) void k_check_weighted_colour(uint32_t* out)
+{
+    const uint32_t c0 = blockIdx.x & 255u, c1 = blockIdx.x >> 8, w0 = threadIdx.x;
+    uint32_t bad0 = 0u, bad1 = 0u, first = 0xffffffffu;
+    for (uint32_t w1 = 1u; w1 < 256u; w1++) {
+        const uint32_t d = w0 + w1;
+        const uint32_t want = (2u * (c0 * w0 + c1 * w1) + d) / (2u * d);
+        const uint32_t o0 = 255u - c0, o1 = 255u - c1;
+        const uint32_t wantO = (2u * (o0 * w0 + o1 * w1) + d) / (2u * d), wantX = (2u * (c1 * w0 + c0 * w1) + d) / (2u * d);
+        const uint32_t cw0 = pack_cw(c0, o0, c1, w0), cw1 = pack_cw(c1, o1, c0, w1), wantRgb = pack_cw(want, wantO, wantX, 0u);
+        const float den = (float)d;
+        const f32x2 y = rcp_refined2(both(den));
+        const bool m0 = weighted_colour(cw0, cw1, den, 1.0f / den) != wantRgb, m1 = weighted_colour(cw0, cw1, den, y.x) != wantRgb;
+        bad0 += m0 ? 1u : 0u;
+        bad1 += m1 ? 1u : 0u;
+        if (m0 || m1) first = min(first, c0 | (w0 << 8) | (c1 << 16) | (w1 << 24));
+    }
+    if (bad0) atomicAdd(&out[0], bad0);
+    if (bad1) atomicAdd(&out[1], bad1);
+    if (first != 0xffffffffu) atomicMin(&out[2], first);
+}
+
 // multiply-shift constants of umod_fast for divisor d >= 2
 inline HashMod make_hash_mod(uint32_t d)
 {
@@ -4322,6 +4354,16 @@ int vh_debug_check_refined_division(uint32_t n, uint32_t seed, uint32_t* d_misma
     VH_HIP(hipMemsetAsync(d_mismatches, 0, 2 * sizeof(uint32_t), (hipStream_t)stream));
     if (n == 0) return VH_OK;
     k_check_refined_division<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(n, seed, d_mismatches);
+    return vh_last_launch_error();
+}
+
+int vh_debug_check_weighted_colour(uint32_t* d_out, vhStream_t stream)
+{
+    if (!d_out) return VH_ERR_BAD_ARGUMENT;
+    const uint32_t init[4] = { 0u, 0u, 0xffffffffu, 0u };
+    VH_HIP(hipMemcpyAsync(d_out, init, sizeof(init), hipMemcpyHostToDevice, (hipStream_t)stream));
+    VH_HIP(hipStreamSynchronize((hipStream_t)stream)); // (init is this call's own)
+    k_check_weighted_colour<<<65536, 256, 0, (hipStream_t)stream>>>(d_out);
     return vh_last_launch_error();
 }
 

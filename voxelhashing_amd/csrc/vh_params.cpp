@@ -321,6 +321,7 @@ void vh_hash_params_from_app_state(const VhAppState* gas, VhHashParams* p)
         p->m_streamingMinGridPos[i] = gas->s_streamingMinGridPos[i];
     }
     p->m_streamingInitialChunkListSize = gas->s_streamingInitialChunkListSize;
+    p->m_colorIntegration = VH_COLOR_RUNNING_AVERAGE; // no key of the parameter file: CUDASceneRepHashSDF::setColorIntegration
 }
 
 void vh_raycast_params_from_app_state(const VhAppState* gas, const float intrinsics[16], const float intrinsicsInv[16], VhRayCastParams* p)

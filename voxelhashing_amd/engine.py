@@ -142,6 +142,14 @@ class CUDASceneRepHashSDF:
         self._options = _copy_struct(options)
         check(self.L.vh_scene_rep_set_options(self.handle, C.byref(self._options)), "setOptions")
 
+    def setColorIntegration(self, mode):
+        """T.COLOR_RUNNING_AVERAGE (the reference's 50/50 colour average) or T.COLOR_WEIGHTED_AVERAGE (weighted by the
+        voxel weights), from the next integrate() on"""
+        check(self.L.vh_scene_rep_set_color_integration(self.handle, int(mode)), "setColorIntegration")
+
+    def getColorIntegration(self):
+        return int(self.getHashParams().m_colorIntegration)
+
     def getState(self):
         out = (C.c_uint32 * T.STATE_WORDS)()
         check(self.L.vh_scene_rep_get_state(self.handle, out), "getState")

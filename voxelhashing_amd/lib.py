@@ -72,6 +72,7 @@ PROTOTYPES = {
     "vh_debug_check_fast_math": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, _VP, _VP]),
     "vh_debug_valu_probe": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _VP, P(C.c_uint32), _VP]),
     "vh_debug_check_refined_division": (C.c_int, [C.c_uint32, C.c_uint32, _VP, _VP]),
+    "vh_debug_check_weighted_colour": (C.c_int, [_VP, _VP]),
     "vh_publish_words": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP]),
     "vh_stream_out_probe": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_float, _VP, _VP, _VP, C.c_uint32, _VP]),
     "vh_scene_rep_create": (C.c_int, [P(T.HashParams), P(T.SceneOptions), _VP, P(_VP)]),
@@ -87,6 +88,7 @@ PROTOTYPES = {
     "vh_scene_rep_get_state": (C.c_int, [_VP, P(C.c_uint32)]),
     "vh_scene_rep_get_timings": (C.c_int, [_VP, P(C.c_double)]),
     "vh_scene_rep_set_options": (C.c_int, [_VP, P(T.SceneOptions)]),
+    "vh_scene_rep_set_color_integration": (C.c_int, [_VP, C.c_uint32]),
     "vh_scene_rep_integrate_ahead": (C.c_int, [_VP, _F16, P(T.DepthCameraData), P(T.DepthCameraParams), _VP, P(P(T.FrameJob))]),
     "vh_scene_rep_integrate_finish": (C.c_int, [_VP, P(T.DepthCameraData), P(T.DepthCameraParams)]),
     "vh_raycast_create": (C.c_int, [P(T.RayCastParams), _VP, P(_VP)]),

@@ -216,10 +216,15 @@ class Reconstruction:
     calibration_state (a CalibrationState, read_calibration_state; None by default) carries s_bUseCameraCalibration.  When
     it is set and the `.sens` depth extrinsic is not the identity, the sensor renders every depth map into the colour
     camera before anything uses it (CUDARGBDSensor.cpp:198-217); an identity extrinsic leaves it off with the reference's
-    warning.  camera_calibration tells which took effect."""
+    warning.  camera_calibration tells which took effect.
+
+    weighted_colour (off by default; not a key of the parameter file) fuses colours weighted by the voxel weights instead
+    of the reference's running 50/50 average (CUDASceneRepHashSDF.setColorIntegration): the ray cast then shows a surface
+    at the brightness it was seen at, which the RGB-D tracker needs to follow its own reconstruction.  It belongs to the
+    scene, so frame() and run_native() integrate alike."""
 
     def __init__(self, app_state, tracking_state=None, sens_files=None, stream=None, use_rgbd_tracking=False, render_state=None,
-                 calibration_state=None):
+                 calibration_state=None, weighted_colour=False):
         self.L = load()
         self.gas = app_state
         self.tracking_rgbd = None
@@ -266,6 +271,9 @@ class Reconstruction:
         self.L.vh_marching_cubes_params_from_app_state(C.byref(g), C.byref(mp))
         self.hp, self.rp, self.mp = hp, rp, mp
         self.scene = E.CUDASceneRepHashSDF(hp, opt, stream=stream)
+        self.weighted_colour = bool(weighted_colour)
+        if self.weighted_colour:
+            self.scene.setColorIntegration(T.COLOR_WEIGHTED_AVERAGE)
         self.ray = E.CUDARayCastSDF(rp, stream=stream)
         self.chunk_grid = None
         if g.s_streamingEnabled:

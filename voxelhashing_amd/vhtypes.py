@@ -53,7 +53,8 @@ class HashParams(C.Structure):
         ("m_streamingGridDimensions", C.c_int32 * 3),
         ("m_streamingMinGridPos", C.c_int32 * 3),
         ("m_streamingInitialChunkListSize", C.c_uint32),
-        ("m_dummy", C.c_uint32 * 2),
+        ("m_colorIntegration", C.c_uint32),   # 0: running 50/50 colour average (the reference), 1: weighted by the voxel weights
+        ("m_dummy", C.c_uint32),
     ]
 
 
@@ -401,13 +402,19 @@ def mat16(m):
     return (C.c_float * 16)(*a.tolist())
 
 
+COLOR_RUNNING_AVERAGE = 0    # HashParams.m_colorIntegration
+COLOR_WEIGHTED_AVERAGE = 1
+
+
 def make_hash_params(num_buckets, num_sdf_blocks, voxel_size, truncation=None, trunc_scale=None,
                      max_integration_distance=4.0, weight_sample=10, weight_max=255,
                      max_collision_list=7, streaming_extents=(1.0, 1.0, 1.0),
                      streaming_dims=(257, 257, 257), streaming_min=(-128, -128, -128),
-                     streaming_list_size=2000):
+                     streaming_list_size=2000, weighted_colour=False):
     """HashParams as parametersFromGlobalAppState builds it.  truncation defaults
-    to 5*voxel and trunc_scale to 2.5*voxel (zParametersManolisScan.txt:31-32)."""
+    to 5*voxel and trunc_scale to 2.5*voxel (zParametersManolisScan.txt:31-32).
+    weighted_colour: fuse colours weighted by the voxel weights (m_colorIntegration = 1) instead of the reference's
+    running 50/50 average."""
     p = HashParams()
     p.m_rigidTransform = (C.c_float * 16)(*IDENTITY16)
     p.m_rigidTransformInverse = (C.c_float * 16)(*IDENTITY16)
@@ -427,6 +434,7 @@ def make_hash_params(num_buckets, num_sdf_blocks, voxel_size, truncation=None, t
     p.m_streamingGridDimensions = (C.c_int32 * 3)(*streaming_dims)
     p.m_streamingMinGridPos = (C.c_int32 * 3)(*streaming_min)
     p.m_streamingInitialChunkListSize = streaming_list_size
+    p.m_colorIntegration = COLOR_WEIGHTED_AVERAGE if weighted_colour else COLOR_RUNNING_AVERAGE
     return p
 
 
