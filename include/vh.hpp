@@ -192,6 +192,10 @@ public:
     // starts with it.  Throws on any other mode.
     void setColorIntegration(unsigned int mode);
     unsigned int getColorIntegration() const { return m_hashParams.m_colorIntegration; }
+    // Distance, colour, validity and (d_gradient != nullptr) gradient at n world points: vh_query_points (vh_api.h has the
+    // semantics) on the scene's stream.  Device pointers.  Read-only, on the blocks resident on the device (blocks
+    // streamed out to the host grid are absent); the caller must not run it beside an integrate on another stream.
+    void queryPoints(const float* d_points, unsigned int n, float* d_sdf, uint32_t* d_color, float* d_gradient, uint8_t* d_valid);
     const VhSceneOptions& getOptions() const { return m_options; }
     vhStream_t getStream() const { return m_stream; }
     int32_t nextLockToken(); // fresh bucket-lock epoch (replaces resetHashBucketMutexCUDA)
@@ -250,6 +254,12 @@ public:
                 const vh::mat4f& lastRigidTransform, VhFrameJob* coLaunch = nullptr);
     const RayCastData& getRayCastData() { return m_data; }        // :42
     const RayCastParams& getRayCastParams() const { return m_params; } // :45
+    // n rays given in world space through the model: vh_query_rays (vh_api.h has the semantics) with this caster's
+    // increment and thresholds, on its stream.  Device pointers; d_normals may be nullptr.  Read-only, on the blocks
+    // resident on the device; the caller must not run it beside an integrate on another stream.
+    void castRays(const HashData& hashData, const HashParams& hashParams, const float* d_origins, const float* d_directions,
+                  const float* d_tMin, const float* d_tMax, unsigned int n, float* d_t, float* d_normals, uint32_t* d_color,
+                  uint8_t* d_status);
 
     // marchOnly: events around the march kernel only; stride n: only every n-th render() is timed
     void setTiming(bool on, bool marchOnly = false, unsigned int stride = 1);

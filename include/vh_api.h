@@ -48,8 +48,8 @@ int vh_free_host(void* hostPtr);
 int vh_memcpy_h2d(void* dst, const void* src, size_t bytes, vhStream_t stream);
 int vh_memcpy_d2h(void* dst, const void* src, size_t bytes, vhStream_t stream); /* synchronises the stream */
 int vh_memset(void* dst, int value, size_t bytes, vhStream_t stream);
-/* measurement: the next kernel the calling thread launches through vh_render_intervals[_co], vh_compute_normals[_co, _co2] or
- * vh_integrate_fused is launched with hipExtLaunchKernel's start / stop events (two hipEvent_t created with timing):
+/* measurement: the next kernel the calling thread launches through vh_render, vh_render_intervals[_co], vh_compute_normals[_co, _co2],
+ * vh_integrate_fused, vh_query_points or vh_query_rays is launched with hipExtLaunchKernel's start / stop events (two hipEvent_t created with timing):
  * hipEventElapsedTime(start, stop) is then that kernel's own duration -- the dispatch's begin and end time stamps, what
  * rocprofv3's kernel trace reports -- with no event record in the stream.  The launch consumes the pair. */
 int vh_time_next_launch(void* startEvent, void* stopEvent);
@@ -121,6 +121,38 @@ int vh_compactify_job(VhFrameJob* job, vhStream_t stream);
  * host class does so when vh_compute_normals overwrites it right after). */
 int vh_render(const VhHashData* hd, const VhHashParams* hp, const VhRayCastData* rd,
               const VhDepthCameraParams* cp, const VhRayCastParams* rp, vhStream_t stream);
+/* ---- batch queries (not in the reference) --------------------------------------
+ * Read-only questions to the blocks that are RESIDENT ON THE DEVICE: blocks streamed out to the host grid are absent,
+ * as they are for the ray caster.  All arrays are device pointers; one thread per point / ray.  Nothing is written to
+ * the scene, but the caller must not run a query beside an integrate (or streaming pass) on another stream.
+ *
+ * vh_query_points: per point p = d_points3[3i..3i+2] (world space)
+ *   d_valid[i]      what trilinearInterpolationSimpleFastFast(p) returns (DSC/RayCastSDFUtil.h:97-116), one byte
+ *   d_sdf[i]        its distance; -inf where valid is 0 (the reference's partial sum is not reported)
+ *   d_color[i]      its colour, r | g << 8 | b << 16; 0 where valid is 0
+ *   d_gradient3     (may be NULL) gradientForPoint(p) (:174-195) at EVERY point, valid or not: its six samples ignore
+ *                   their own validity, partial sums included
+ * A point with a non-finite coordinate is valid = 0 with gradient (0, 0, 0), decided before any lookup.
+ *
+ * vh_query_rays: per ray the body of traverseCoarseGridSimpleSampleAll (:198-262) with worldCamPos = origin,
+ * worldDir = direction (used as given: the caller normalises), rayCurrent = tMin, rayEnd = tMax: the same samples
+ * t += m_rayIncrement, sign-change test, three bisection steps and two thresholds; the march resumes after a rejected
+ * crossing.  Of rp only m_rayIncrement (finite and > 0, else VH_ERR_BAD_ARGUMENT), m_thresSampleDist and m_thresDist
+ * are read.
+ *   d_status[i]  1 hit:     d_t = the bisection's alpha, d_color = the last bisection sample's colour (packed as
+ *                           above), d_normals3 (may be NULL) = -gradientForPoint(origin + alpha * direction) in WORLD
+ *                           space -- always from the gradient, whatever m_useGradients says
+ *                0 miss:    d_t = -inf, normal (-inf, -inf, -inf), colour 0
+ *                2 refused: outputs as for a miss, the ray is not marched: origin, direction, tMin or tMax not
+ *                           finite; direction (0, 0, 0); (tMax - tMin) / m_rayIncrement > VH_QUERY_MAX_SAMPLES.
+ * The march also counts its samples and stops at VH_QUERY_MAX_SAMPLES (t + increment == t cannot spin a wave).
+ * A wave lasts as long as its longest ray: rays in a coherent order (neighbours next to each other) run faster.
+ * n = 0 succeeds without a launch.  vh_time_next_launch applies to both, and to vh_render. */
+int vh_query_points(const VhHashData* hd, const VhHashParams* hp, const float* d_points3, uint32_t n, float* d_sdf, uint32_t* d_color,
+                    float* d_gradient3 /* may be NULL */, uint8_t* d_valid, vhStream_t stream);
+int vh_query_rays(const VhHashData* hd, const VhHashParams* hp, const VhRayCastParams* rp, const float* d_origins3, const float* d_directions3,
+                  const float* d_tMin, const float* d_tMax, uint32_t n, float* d_t, float* d_normals3 /* may be NULL */, uint32_t* d_color,
+                  uint8_t* d_status, vhStream_t stream);
 /* Ray-interval splatting as a compute pass: resetRayIntervalSplatCUDA / rayIntervalSplatCUDA
  * (DSC/CUDARayCastSDF.cu:88,169) + the D3D11 min/max rasterisation (DSC/DX11RayIntervalSplatting.cpp:150-220) that
  * this fork leaves disabled.  Per 8x8-pixel tile (ceil(W/8)*ceil(H/8) of them, row-major):
@@ -292,6 +324,9 @@ int vh_scene_rep_set_options(VhSceneRep* s, const VhSceneOptions* opt);
  * reference's running 50/50 average, or VH_COLOR_WEIGHTED_AVERAGE (1), weighted by the voxel weights; any other mode is
  * VH_ERR_BAD_ARGUMENT.  The mode is VhHashParams::m_colorIntegration of vh_scene_rep_get_hash_params. */
 int vh_scene_rep_set_color_integration(VhSceneRep* s, uint32_t mode);
+/* queryPoints (include/vh.hpp): vh_query_points on the scene's table and stream; device pointers, d_gradient3 may be NULL */
+int vh_scene_rep_query_points(VhSceneRep* s, const float* d_points3, uint32_t n, float* d_sdf, uint32_t* d_color, float* d_gradient3,
+                              uint8_t* d_valid);
 
 /* integrateAhead / integrateFinish: the two halves of integrate() (include/vh.hpp).  *job receives the frame's alloc +
  * compactify passes for vh_raycast_render_co (NULL when the scene's options rule a co-launch out); it belongs to the
@@ -309,6 +344,10 @@ int vh_raycast_render(VhRayCast* r, const VhHashData* hd, const VhHashParams* hp
 /* the same with a frame job riding along (may be NULL) */
 int vh_raycast_render_co(VhRayCast* r, const VhHashData* hd, const VhHashParams* hp,
                          const VhDepthCameraParams* cp, const float lastRigidTransform[16], VhFrameJob* job);
+/* castRays (include/vh.hpp): vh_query_rays with the caster's own parameters on its stream; device pointers, d_normals3 may be NULL */
+int vh_ray_cast_cast_rays(VhRayCast* r, const VhHashData* hd, const VhHashParams* hp, const float* d_origins3, const float* d_directions3,
+                          const float* d_tMin, const float* d_tMax, uint32_t n, float* d_t, float* d_normals3, uint32_t* d_color,
+                          uint8_t* d_status);
 /* getRayCastData() :42 / getRayCastParams() :45 */
 int vh_raycast_get_data(VhRayCast* r, VhRayCastData* out);
 int vh_raycast_get_params(VhRayCast* r, VhRayCastParams* out);

@@ -163,6 +163,8 @@ typedef struct VhRayCastData {
 /* ray-interval splatting (vh_ray_interval_splat): one entry of a tile's block list */
 #define VH_TILE_LIST_CAPACITY 64        /* small tile tables (default) */
 #define VH_TILE_LIST_CAPACITY_LARGE 128 /* large tile tables: fine voxels */
+/* vh_query_rays: the most samples one ray may take; a ray that asks for more is refused (status 2) */
+#define VH_QUERY_MAX_SAMPLES 65536
 typedef struct VhTileBlock {
     int32_t pos[3]; /* SDF block position */
     int32_t ptr;    /* its voxel pointer (HashEntry::ptr) */

@@ -109,6 +109,12 @@ int vh_scene_rep_set_color_integration(VhSceneRep* s, uint32_t mode)
     if (!s || (mode != VH_COLOR_RUNNING_AVERAGE && mode != VH_COLOR_WEIGHTED_AVERAGE)) return VH_ERR_BAD_ARGUMENT;
     return guarded([&] { s->impl.setColorIntegration(mode); });
 }
+int vh_scene_rep_query_points(VhSceneRep* s, const float* d_points3, uint32_t n, float* d_sdf, uint32_t* d_color, float* d_gradient3,
+                              uint8_t* d_valid)
+{
+    if (!s || !d_points3 || !d_sdf || !d_color || !d_valid) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { s->impl.queryPoints(d_points3, n, d_sdf, d_color, d_gradient3, d_valid); });
+}
 int vh_scene_rep_set_options(VhSceneRep* s, const VhSceneOptions* opt)
 {
     if (!s || !opt) return VH_ERR_BAD_ARGUMENT;
@@ -136,6 +142,13 @@ int vh_raycast_render_co(VhRayCast* r, const VhHashData* hd, const VhHashParams*
 {
     if (!r || !hd || !hp || !cp || !lastRigidTransform) return VH_ERR_BAD_ARGUMENT;
     return guarded([&] { r->impl.render(*hd, *hp, *cp, toMat(lastRigidTransform), job); });
+}
+int vh_ray_cast_cast_rays(VhRayCast* r, const VhHashData* hd, const VhHashParams* hp, const float* d_origins3, const float* d_directions3,
+                          const float* d_tMin, const float* d_tMax, uint32_t n, float* d_t, float* d_normals3, uint32_t* d_color,
+                          uint8_t* d_status)
+{
+    if (!r || !hd || !hp || !d_origins3 || !d_directions3 || !d_tMin || !d_tMax || !d_t || !d_color || !d_status) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { r->impl.castRays(*hd, *hp, d_origins3, d_directions3, d_tMin, d_tMax, n, d_t, d_normals3, d_color, d_status); });
 }
 int vh_raycast_get_data(VhRayCast* r, VhRayCastData* out)
 {

@@ -666,6 +666,11 @@ void CUDASceneRepHashSDF::getState(uint32_t out[VH_STATE_WORDS])
     check(vh_memcpy_d2h(out, m_hashData.d_state, sizeof(uint32_t) * VH_STATE_WORDS, m_stream), "getState");
 }
 
+void CUDASceneRepHashSDF::queryPoints(const float* d_points, unsigned int n, float* d_sdf, uint32_t* d_color, float* d_gradient, uint8_t* d_valid)
+{
+    check(vh_query_points(&m_hashData, &m_hashParams, d_points, n, d_sdf, d_color, d_gradient, d_valid, m_stream), "queryPoints");
+}
+
 void CUDASceneRepHashSDF::getTimings(double out[4])
 {
     m_timer->resolve((hipStream_t)m_stream);
@@ -795,6 +800,14 @@ void CUDARayCastSDF::getTimings(double out[4])
     out[1] = m_timer->totalMs[ST_NORMALS];
     out[2] = (double)m_timer->count[ST_RAYCAST];
     out[3] = m_timer->totalMs[ST_SPLAT];
+}
+
+void CUDARayCastSDF::castRays(const HashData& hashData, const HashParams& hashParams, const float* d_origins, const float* d_directions,
+                              const float* d_tMin, const float* d_tMax, unsigned int n, float* d_t, float* d_normals, uint32_t* d_color,
+                              uint8_t* d_status)
+{
+    check(vh_query_rays(&hashData, &hashParams, &m_params, d_origins, d_directions, d_tMin, d_tMax, n, d_t, d_normals, d_color, d_status, m_stream),
+          "castRays");
 }
 
 // DSC/CUDARayCastSDF.cpp:38-72 with rayIntervalSplatting :84-100 (view matrices only)

@@ -2256,6 +2256,176 @@ __global__ __launch_bounds__(256) void k_render_hash(VhHashData hd, VhHashParams
     VH_STAT_STORE
 }
 
+// ---------------------------------------------------------------------------
+// batch queries (not in the reference: vh_query_points / vh_query_rays, DESIGN.md section 4 "Queries").  Read-only;
+// one lane per point or ray, block pointers from the hash table behind the per-lane cache of k_render_hash.
+// ---------------------------------------------------------------------------
+
+VHD bool finite3(F3 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
+
+// trilinearInterpolationSimpleFastFast + gradientForPoint at given world points.  The taps come from tap_coords'
+// exact route (the reference's arithmetic: a point is a ray of direction 0 sampled at 0).
+__global__ __launch_bounds__(256) void k_query_points(VhHashData hd, VhHashParams hp, const float* __restrict__ points, uint32_t n,
+                                                      float* __restrict__ sdf, uint32_t* __restrict__ color, float* __restrict__ gradient,
+                                                      uint8_t* __restrict__ valid, HashMod hm)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const F3 p = mk3(points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2]);
+    float dist = minf();
+    uint32_t col = 0u;
+    bool ok = false;
+    F3 g = mk3(0.0f, 0.0f, 0.0f);
+    if (finite3(p)) { // decided before any lookup
+        RayQ rq;
+        rq.cam = p; rq.dir = mk3(0.0f, 0.0f, 0.0f);
+        rq.camq = rq.dirq = mk3(0.0f, 0.0f, 0.0f);
+        rq.vs = hp.m_virtualVoxelSize;
+        rq.rvs = 1.0f / rq.vs;
+        rq.halfVoxel = rq.vs / 2.0f;
+        rq.certLim = -1.0f;
+        Taps tp;
+        tap_coords(rq, 0.0f, tp);
+        HashLookup lk{ hd, hp, hm, {} };
+        cache_init(lk.bc);
+        float d = 0.0f;
+        uint32_t c = 0u;
+        ok = trilinear<true>(hd, rq.vs, lk, kPtrUnknown, tp, p, rq.rvs, d, c);
+        if (ok) { dist = d; col = c; } // the reference's partial sum of an invalid sample is not reported
+        if (gradient) g = gradient_for_point(hd, hp, p); // at every point: its six samples ignore their own validity
+    }
+    sdf[i] = dist;
+    color[i] = col;
+    valid[i] = ok ? 1 : 0;
+    if (gradient) { gradient[3 * (size_t)i] = g.x; gradient[3 * (size_t)i + 1] = g.y; gradient[3 * (size_t)i + 2] = g.z; }
+}
+
+#ifdef VH_QUERY_RAYS_WAVES // (measurement builds: the waves per SIMD k_query_rays is compiled for; default: the compiler's choice)
+#define VH_QUERY_RAYS_OCCUPANCY __attribute__((amdgpu_waves_per_eu(VH_QUERY_RAYS_WAVES, VH_QUERY_RAYS_WAVES)))
+#else
+#define VH_QUERY_RAYS_OCCUPANCY
+#endif
+
+// traverseCoarseGridSimpleSampleAll, DSC/RayCastSDFUtil.h:198-262, for rays given in world space: worldCamPos = origin,
+// worldDir = direction (as given), rayCurrent = tMin, rayEnd = tMax.  The march of march_ray without its tile interval,
+// its cost accounting and its camera: the same samples, sign-change test, bisection and thresholds, written as
+// march-until-sign-change / bisect / resume.  Lanes of a wave finish at different times (a wave lasts as long as its
+// longest ray): rays in a coherent order -- neighbours in space next to each other -- are the caller's gain.
+// The march counts its samples and stops at VH_QUERY_MAX_SAMPLES, so no caller data can spin a wave (t + inc == t).
+__global__ __launch_bounds__(256) VH_QUERY_RAYS_OCCUPANCY void k_query_rays(VhHashData hd, VhHashParams hp, float inc, float thresSampleDist, float thresDist,
+                                                    const float* __restrict__ origins, const float* __restrict__ directions,
+                                                    const float* __restrict__ tMin, const float* __restrict__ tMax, uint32_t n,
+                                                    float* __restrict__ tOut, float* __restrict__ normals, uint32_t* __restrict__ color,
+                                                    uint8_t* __restrict__ status, HashMod hm)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float mi = minf();
+    const F3 cam = mk3(origins[3 * (size_t)i], origins[3 * (size_t)i + 1], origins[3 * (size_t)i + 2]);
+    const F3 dir = mk3(directions[3 * (size_t)i], directions[3 * (size_t)i + 1], directions[3 * (size_t)i + 2]);
+    const float t0 = tMin[i], rayEnd = tMax[i];
+    float alpha = mi;
+    F3 nrm = mk3(mi, mi, mi);
+    uint32_t col = 0u;
+    uint32_t st = 0u;
+    const bool refused = !(finite3(cam) && finite3(dir) && isfinite(t0) && isfinite(rayEnd)) ||
+                         (dir.x == 0.0f && dir.y == 0.0f && dir.z == 0.0f) ||
+                         (rayEnd - t0) / inc > (float)VH_QUERY_MAX_SAMPLES;
+    if (refused) {
+        st = 2u;
+    } else {
+        RayQ rq;
+        rq.cam = cam; rq.dir = dir;
+        rq.vs = hp.m_virtualVoxelSize;
+        rq.rvs = 1.0f / rq.vs; // IEEE reciprocal for div_exact
+        rq.halfVoxel = rq.vs / 2.0f;
+        rq.camq = mk3(cam.x * rq.rvs, cam.y * rq.rvs, cam.z * rq.rvs);
+        rq.dirq = mk3(dir.x * rq.rvs, dir.y * rq.rvs, dir.z * rq.rvs);
+        {
+            // Q bounds |pos/voxel| for every sample of this ray: march and bisection parameters lie in [tMin, tMax)
+            // (march_ray has the error analysis of the margin)
+            const float Q = 1.0f + (fabsf(rq.camq.x) + fabsf(rq.camq.y) + fabsf(rq.camq.z)) +
+                            fmaxf(fabsf(t0), fabsf(rayEnd)) * (fabsf(rq.dirq.x) + fabsf(rq.dirq.y) + fabsf(rq.dirq.z));
+            const float margin = Q * (16.0f / 16777216.0f);
+            rq.certLim = (Q < 65536.0f) ? 0.5f - margin : -1.0f; // NaN/inf Q compare false: exact path
+        }
+        HashLookup lk{ hd, hp, hm, {} };
+        cache_init(lk.bc);
+        float rcur = t0;
+        float lastSdf = 0.0f, lastAlpha = 0.0f;
+        int lastValid = 0;
+        uint32_t samples = 0u;
+#pragma unroll 1
+        for (;;) {
+            // ---- march until a sign change, the end of the range or the sample cap
+            bool candidate = false;
+            float dist = 0.0f;
+#pragma unroll 1
+            for (;;) {
+                // samples whose first tap has no block are invalid (weight 0 at the first tap)
+                Taps tp;
+                int p0 = kPtrUnknown;
+                int skipped = 0;
+#pragma unroll 1
+                while (rcur < rayEnd && samples < (uint32_t)VH_QUERY_MAX_SAMPLES) {
+                    tap_coords(rq, rcur, tp);
+                    if (lk.first_tap(tp.bxa, tp.bya, tp.bza, p0)) break;
+                    skipped = 1;
+                    samples++;
+                    rcur += inc;
+                }
+                if (!(rcur < rayEnd) || samples >= (uint32_t)VH_QUERY_MAX_SAMPLES) break;
+                lastValid = skipped ? 0 : lastValid;
+                samples++;
+                uint32_t colorUnused = 0u;
+                const F3 pos = mk3(cam.x + rcur * dir.x, cam.y + rcur * dir.y, cam.z + rcur * dir.z);
+                const bool ok = trilinear<false>(hd, rq.vs, lk, p0, tp, pos, rq.rvs, dist, colorUnused);
+                if (ok & (lastValid != 0) & (lastSdf > 0.0f) & (dist < 0.0f)) { candidate = true; break; }
+                lastSdf = ok ? dist : lastSdf;
+                lastAlpha = ok ? rcur : lastAlpha;
+                lastValid = ok ? 1 : 0;
+                rcur += inc;
+            }
+            if (!candidate) break;
+
+            // ---- findIntersectionBisection :149-170 on [lastAlpha, rcur]
+            float a = lastAlpha, aDist = lastSdf, b = rcur, bDist = dist, c = 0.0f;
+            uint32_t color2 = 0u;
+            bool success = true;
+#pragma unroll 1
+            for (int k = 0; k < 3; k++) {
+                c = a + (aDist / (aDist - bDist)) * (b - a); // findIntersectionLinear :140-143
+                Taps ctp;
+                tap_coords(rq, c, ctp);
+                const F3 cpos = mk3(cam.x + c * dir.x, cam.y + c * dir.y, cam.z + c * dir.z);
+                float cDist = 0.0f;
+                if (!trilinear<true>(hd, rq.vs, lk, kPtrUnknown, ctp, cpos, rq.rvs, cDist, color2)) { success = false; break; }
+                if (aDist * cDist > 0.0f) { a = c; aDist = cDist; }
+                else { b = c; bDist = cDist; }
+            }
+            if (success && fabsf(lastSdf - dist) < thresSampleDist && fabsf(dist) < thresDist) {
+                st = 1u;
+                alpha = c;
+                col = color2;
+                if (normals) { // always from the gradient: there is no depth map to difference
+                    const F3 g = gradient_for_point(hd, hp, mk3(cam.x + c * dir.x, cam.y + c * dir.y, cam.z + c * dir.z));
+                    nrm = mk3(-g.x, -g.y, -g.z);
+                }
+                break;
+            }
+            // no accepted hit: the (valid) march sample becomes the last sample and the march goes on (:248-252)
+            lastSdf = dist;
+            lastAlpha = rcur;
+            lastValid = 1;
+            rcur += inc;
+        }
+    }
+    tOut[i] = alpha;
+    color[i] = col;
+    status[i] = (uint8_t)st;
+    if (normals) { normals[3 * (size_t)i] = nrm.x; normals[3 * (size_t)i + 1] = nrm.y; normals[3 * (size_t)i + 2] = nrm.z; }
+}
+
 // One wave per 8x8-pixel tile with the tile's head and block list from k_interval_splat: the wave builds its block
 // table in LDS, forms the tile's depth interval from the listed blocks and marches inside it.  The kernel is bound by
 // VALU issue per SIMD: what counts is instructions per sample and even loads of the SIMDs.
@@ -3907,8 +4077,34 @@ int vh_render(const VhHashData* hd, const VhHashParams* hp, const VhRayCastData*
     if (tiles == 0) return VH_OK;
     if (hp->m_hashNumBuckets < 2) return VH_ERR_BAD_ARGUMENT;
     const HashMod hm = make_hash_mod(hp->m_hashNumBuckets);
-    if (rp->m_useGradients) k_render_hash<true><<<cdiv(tiles, 4), 256, 0, (hipStream_t)stream>>>(*hd, *hp, *rd, *cp, *rp, hm);
-    else k_render_hash<false><<<cdiv(tiles, 4), 256, 0, (hipStream_t)stream>>>(*hd, *hp, *rd, *cp, *rp, hm);
+    if (rp->m_useGradients) VH_LAUNCH_TIMED(k_render_hash<true>, cdiv(tiles, 4), 256, (hipStream_t)stream, *hd, *hp, *rd, *cp, *rp, hm);
+    else VH_LAUNCH_TIMED(k_render_hash<false>, cdiv(tiles, 4), 256, (hipStream_t)stream, *hd, *hp, *rd, *cp, *rp, hm);
+    return vh_last_launch_error();
+}
+
+int vh_query_points(const VhHashData* hd, const VhHashParams* hp, const float* d_points3, uint32_t n, float* d_sdf, uint32_t* d_color,
+                    float* d_gradient3, uint8_t* d_valid, vhStream_t stream)
+{
+    if (!hd || !hp || !hd->d_hash || !d_points3 || !d_sdf || !d_color || !d_valid) return VH_ERR_BAD_ARGUMENT;
+    if (hp->m_hashNumBuckets < 2) return VH_ERR_BAD_ARGUMENT;
+    if (n == 0) return VH_OK;
+    const HashMod hm = make_hash_mod(hp->m_hashNumBuckets);
+    VH_LAUNCH_TIMED(k_query_points, cdiv(n, 256), 256, (hipStream_t)stream, *hd, *hp, d_points3, n, d_sdf, d_color, d_gradient3, d_valid, hm);
+    return vh_last_launch_error();
+}
+
+int vh_query_rays(const VhHashData* hd, const VhHashParams* hp, const VhRayCastParams* rp, const float* d_origins3, const float* d_directions3,
+                  const float* d_tMin, const float* d_tMax, uint32_t n, float* d_t, float* d_normals3, uint32_t* d_color, uint8_t* d_status,
+                  vhStream_t stream)
+{
+    if (!hd || !hp || !rp || !hd->d_hash || !d_origins3 || !d_directions3 || !d_tMin || !d_tMax || !d_t || !d_color || !d_status)
+        return VH_ERR_BAD_ARGUMENT;
+    if (!std::isfinite(rp->m_rayIncrement) || !(rp->m_rayIncrement > 0.0f)) return VH_ERR_BAD_ARGUMENT;
+    if (hp->m_hashNumBuckets < 2) return VH_ERR_BAD_ARGUMENT;
+    if (n == 0) return VH_OK;
+    const HashMod hm = make_hash_mod(hp->m_hashNumBuckets);
+    VH_LAUNCH_TIMED(k_query_rays, cdiv(n, 256), 256, (hipStream_t)stream, *hd, *hp, rp->m_rayIncrement, rp->m_thresSampleDist, rp->m_thresDist,
+                    d_origins3, d_directions3, d_tMin, d_tMax, n, d_t, d_normals3, d_color, d_status, hm);
     return vh_last_launch_error();
 }
 

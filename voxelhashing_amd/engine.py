@@ -23,6 +23,12 @@ def _copy_struct(s):
     return out
 
 
+def _unpack_rgb(packed):
+    """r | g << 8 | b << 16 -> [n, 3] u8"""
+    p = np.asarray(packed, dtype=np.uint32)
+    return np.stack([p & 0xff, (p >> 8) & 0xff, (p >> 16) & 0xff], axis=-1).astype(np.uint8)
+
+
 class DepthFrame:
     """Device-resident depth + colour image pair (DepthCameraData,
     DepthSensingCUDA/Source/DepthCameraUtil.h:17)."""
@@ -150,6 +156,19 @@ class CUDASceneRepHashSDF:
     def getColorIntegration(self):
         return int(self.getHashParams().m_colorIntegration)
 
+    def queryPoints(self, points, gradient=True):
+        """distance, colour and gradient of the model at world points [n, 3] (vh_query_points: include/vh_api.h has the
+        semantics) -> dict sdf [n] f32 (-inf where invalid), color [n, 3] u8, gradient [n, 3] f32 (None without), valid [n] bool"""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n, s = len(pts), self.stream
+        d_pts, d_sdf, d_col, d_val = DeviceBuffer.from_numpy(pts, s), DeviceBuffer(4 * n), DeviceBuffer(4 * n), DeviceBuffer(n)
+        d_grad = DeviceBuffer(12 * n) if gradient else None
+        check(self.L.vh_scene_rep_query_points(self.handle, d_pts.ptr, n, d_sdf.ptr, d_col.ptr, d_grad.ptr if gradient else None, d_val.ptr),
+              "CUDASceneRepHashSDF::queryPoints")
+        return dict(sdf=d_sdf.download(np.float32, n, s), color=_unpack_rgb(d_col.download(np.uint32, n, s)),
+                    gradient=d_grad.download(np.float32, 3 * n, s).reshape(n, 3) if gradient else None,
+                    valid=d_val.download(np.uint8, n, s).astype(bool))
+
     def getState(self):
         out = (C.c_uint32 * T.STATE_WORDS)()
         check(self.L.vh_scene_rep_get_state(self.handle, out), "getState")
@@ -225,6 +244,23 @@ class CUDARayCastSDF:
             return
         check(self.L.vh_raycast_render(self.handle, C.byref(hashData), C.byref(hashParams), C.byref(depthCameraParams),
                                        f16(lastRigidTransform)), "CUDARayCastSDF::render")
+
+    def castRays(self, hashData, hashParams, origins, directions, t_min, t_max, normals=True):
+        """rays given in world space through the model (vh_query_rays: include/vh_api.h has the semantics); origins and
+        directions [n, 3], t_min / t_max [n] or scalars -> dict t [n] f32 (-inf without a hit), normal [n, 3] f32 (world;
+        None without), color [n, 3] u8, status [n] u8 (T.QUERY_MISS / QUERY_HIT / QUERY_REFUSED)"""
+        org = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        n, s = len(org), self.stream
+        dirs = np.ascontiguousarray(np.broadcast_to(np.asarray(directions, dtype=np.float32).reshape(-1, 3), (n, 3)))
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t_min, dtype=np.float32).reshape(-1), (n,)))
+        t1 = np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, dtype=np.float32).reshape(-1), (n,)))
+        ins = [DeviceBuffer.from_numpy(a, s) for a in (org, dirs, t0, t1)]
+        d_t, d_col, d_st = DeviceBuffer(4 * n), DeviceBuffer(4 * n), DeviceBuffer(n)
+        d_nrm = DeviceBuffer(12 * n) if normals else None
+        check(self.L.vh_ray_cast_cast_rays(self.handle, C.byref(hashData), C.byref(hashParams), ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, n,
+                                           d_t.ptr, d_nrm.ptr if normals else None, d_col.ptr, d_st.ptr), "CUDARayCastSDF::castRays")
+        return dict(t=d_t.download(np.float32, n, s), normal=d_nrm.download(np.float32, 3 * n, s).reshape(n, 3) if normals else None,
+                    color=_unpack_rgb(d_col.download(np.uint32, n, s)), status=d_st.download(np.uint8, n, s))
 
     def getRayCastData(self):
         rd = T.RayCastData()

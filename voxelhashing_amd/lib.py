@@ -51,6 +51,8 @@ PROTOTYPES = {
     "vh_alloc_job": (C.c_int, [P(T.FrameJob), _VP]),
     "vh_compactify_job": (C.c_int, [P(T.FrameJob), _VP]),
     "vh_render": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.RayCastData), P(T.DepthCameraParams), P(T.RayCastParams), _VP]),
+    "vh_query_points": (C.c_int, [P(T.HashData), P(T.HashParams), _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP]),
+    "vh_query_rays": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.RayCastParams), _VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP]),
     "vh_ray_interval_clear": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP]),
     "vh_ray_interval_splat": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.DepthCameraParams), P(T.RayCastParams), _VP, _VP, C.c_uint32, _VP, C.c_uint32, _VP, _VP]),
     "vh_render_intervals": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.RayCastData), P(T.DepthCameraParams), P(T.RayCastParams), _VP, _VP, C.c_uint32, _VP, C.c_uint32, _VP]),
@@ -89,6 +91,8 @@ PROTOTYPES = {
     "vh_scene_rep_get_timings": (C.c_int, [_VP, P(C.c_double)]),
     "vh_scene_rep_set_options": (C.c_int, [_VP, P(T.SceneOptions)]),
     "vh_scene_rep_set_color_integration": (C.c_int, [_VP, C.c_uint32]),
+    "vh_scene_rep_query_points": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP]),
+    "vh_ray_cast_cast_rays": (C.c_int, [_VP, P(T.HashData), P(T.HashParams), _VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP]),
     "vh_scene_rep_integrate_ahead": (C.c_int, [_VP, _F16, P(T.DepthCameraData), P(T.DepthCameraParams), _VP, P(P(T.FrameJob))]),
     "vh_scene_rep_integrate_finish": (C.c_int, [_VP, P(T.DepthCameraData), P(T.DepthCameraParams)]),
     "vh_raycast_create": (C.c_int, [P(T.RayCastParams), _VP, P(_VP)]),

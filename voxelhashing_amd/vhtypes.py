@@ -21,6 +21,8 @@ STATE_HEAP_UNDERFLOW = 0
 STATE_INSERT_FAILED = 1
 STATE_ALLOC_LOCK_LOST = 2
 STATE_RIDER_GAVE_UP = 3
+QUERY_MAX_SAMPLES = 65536  # VH_QUERY_MAX_SAMPLES: the most samples one ray of vh_query_rays may take
+QUERY_MISS, QUERY_HIT, QUERY_REFUSED = 0, 1, 2  # status bytes of vh_query_rays
 
 MINF = np.float32(-np.inf)
 
