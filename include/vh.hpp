@@ -270,6 +270,8 @@ public:
     void setIntervalSplatting(bool on) { m_useIntervals = on; }
     // render() calls so far that ran on an interval splat made ahead (inside the previous call's computeNormals launch)
     unsigned int getNumSplatsMadeAheadUsed() const { return m_preSplatsUsed; }
+    // entries per tile list of the latest render(): VH_TILE_LIST_CAPACITY, or VH_TILE_LIST_CAPACITY_LARGE while fine voxels ask for it
+    uint32_t getTileCapacity() const { return m_tileCapacity; }
 
 private:
     RayCastParams m_params;

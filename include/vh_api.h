@@ -362,6 +362,9 @@ int vh_raycast_set_timing(VhRayCast* r, int enabled); /* 0 off, 1 every stage, 2
 int vh_raycast_set_timing_stride(VhRayCast* r, int enabled, uint32_t stride);
 /* 1 (default): render() splats ray intervals first; 0: march the full depth range as this fork of the reference does */
 int vh_raycast_set_interval_splatting(VhRayCast* r, int enabled);
+/* entries per tile list of the latest render() (VH_TILE_LIST_CAPACITY before the first): large from the second render
+ * after a list outgrew the small tables, small again after more than 30 renders without one.  Read-only. */
+int vh_raycast_get_tile_capacity(VhRayCast* r, uint32_t* out);
 
 /* CUDASceneRepChunkGrid(sceneRep, voxelExtends, gridDimensions, minGridPos, initialChunkListSize,
  *                       streamingEnabled, streamOutParts)         DSC/CUDASceneRepChunkGrid.h:155 */

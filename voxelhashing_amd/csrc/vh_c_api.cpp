@@ -162,6 +162,12 @@ int vh_raycast_get_params(VhRayCast* r, VhRayCastParams* out)
     *out = r->impl.getRayCastParams();
     return VH_OK;
 }
+int vh_raycast_get_tile_capacity(VhRayCast* r, uint32_t* out)
+{
+    if (!r || !out) return VH_ERR_BAD_ARGUMENT;
+    *out = r->impl.getTileCapacity();
+    return VH_OK;
+}
 int vh_raycast_get_timings(VhRayCast* r, double out[4])
 {
     if (!r || !out) return VH_ERR_BAD_ARGUMENT;

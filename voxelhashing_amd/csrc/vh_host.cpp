@@ -763,6 +763,7 @@ CUDARayCastSDF::CUDARayCastSDF(const RayCastParams& params, vhStream_t stream)
     d_tileBlocks = vh::deviceAlloc<VhTileBlock>(VH_TILE_LIST_CAPACITY_LARGE * (tiles ? tiles : 1), "tile block lists");
     m_largeTables = false;
     m_quietFrames = 0;
+    m_tileCapacity = VH_TILE_LIST_CAPACITY;
     m_longestList = vh::Mapped<uint32_t>(1, "hipHostMalloc");
     *m_longestList.host() = 0;
     check(vh_ray_interval_clear(d_tileHeads.get(), params.m_width, params.m_height, m_stream), "vh_ray_interval_clear");

@@ -278,6 +278,12 @@ class CUDARayCastSDF:
     def setIntervalSplatting(self, on):
         check(self.L.vh_raycast_set_interval_splatting(self.handle, 1 if on else 0), "setIntervalSplatting")
 
+    def getTileCapacity(self):
+        """entries per tile list of the latest render(): 64, or 128 while fine voxels ask for large tile tables"""
+        n = C.c_uint32()
+        check(self.L.vh_raycast_get_tile_capacity(self.handle, C.byref(n)), "getTileCapacity")
+        return n.value
+
     def getTimings(self):
         out = (C.c_double * 4)()
         check(self.L.vh_raycast_get_timings(self.handle, out), "getTimings")

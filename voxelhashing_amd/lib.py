@@ -101,6 +101,7 @@ PROTOTYPES = {
     "vh_raycast_render_co": (C.c_int, [_VP, P(T.HashData), P(T.HashParams), P(T.DepthCameraParams), _F16, P(T.FrameJob)]),
     "vh_raycast_get_data": (C.c_int, [_VP, P(T.RayCastData)]),
     "vh_raycast_get_params": (C.c_int, [_VP, P(T.RayCastParams)]),
+    "vh_raycast_get_tile_capacity": (C.c_int, [_VP, P(C.c_uint32)]),
     "vh_raycast_get_timings": (C.c_int, [_VP, P(C.c_double)]),
     "vh_raycast_get_event_pair_overhead": (C.c_int, [_VP, P(C.c_double)]),
     "vh_raycast_set_timing": (C.c_int, [_VP, C.c_int]),
