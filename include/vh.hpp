@@ -710,7 +710,7 @@ public:
     static MarchingCubesParams parameters(unsigned int marchingCubesMaxNumTriangles, float SDFMarchingCubeThreshFactor,
                                           float SDFVoxelSize, unsigned int hashNumBuckets);
 
-    void clearMeshBuffer() { m_meshData.clear(); }
+    void clearMeshBuffer() { m_meshData.clear(); m_welded = false; }
     // copies the result of the last extraction to the host and appends it to the mesh (.cpp:31-86); throws when the
     // triangle buffer overflowed.  offlineProcessing (GlobalAppState::s_offlineProcessing): merge each batch first.
     void copyTrianglesToCPU();
@@ -723,6 +723,19 @@ public:
                            const vh::vec3f& maxCorner = { 0, 0, 0 }, bool boxEnabled = false);
     void extractIsoSurfaceWithoutCopy(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner = { 0, 0, 0 },
                                       const vh::vec3f& maxCorner = { 0, 0, 0 }, bool boxEnabled = false);
+
+    // Not in the reference: the extraction with the soup welded on the device ("Indexed mesh").
+    // Runs reset, pass 1, the sourced pass 2, the weld and the download; REPLACES the mesh buffer with the indexed mesh
+    // and marks it welded, so that saveMesh skips mergeCloseVertices / removeDuplicateFaces.  Whatever appends to the
+    // buffer afterwards (copyTrianglesToCPU) clears the mark.  Throws VH_ERR_STAGING_OVERFLOW when the triangle buffer
+    // overflowed or the weld table was full and VH_ERR_BAD_ARGUMENT when a lattice coordinate left the key range; the
+    // buffer is then empty.
+    void extractIsoSurfaceIndexed(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner = { 0, 0, 0 },
+                                  const vh::vec3f& maxCorner = { 0, 0, 0 }, bool boxEnabled = false);
+    bool isWelded() const { return m_welded; }
+    void getIndexedCounts(unsigned int out[3]) const { out[0] = m_indexedCounts[0]; out[1] = m_indexedCounts[1]; out[2] = m_indexedCounts[2]; }
+    void downloadIndexed(VhVertex* vertices, uint64_t* keys, uint32_t* faces); // device mesh of the last indexed extraction
+    void downloadSources(VhTriangleSource* out, unsigned int n);               // source records of the last indexed extraction
 
     const vh::MeshData& getMeshData() const { return m_meshData; }
     const MarchingCubesData& getMarchingCubesData() const { return m_data; }
@@ -738,6 +751,14 @@ private:
     vh::MeshData m_meshData;
     vhStream_t m_stream;
     bool m_offline;
+    // indexed extraction: made by its first call
+    bool m_welded = false;                      // m_meshData is the weld's mesh, untouched since
+    vh::DevicePtr<VhTriangleSource> d_sources;  // m_maxNumTriangles records beside m_data.d_triangles
+    VhMeshWeldData m_weld;                      // from vh_mesh_weld_data_alloc; m_weldOwner gives it back
+    struct WeldFree { void operator()(VhMeshWeldData* d) const noexcept; };
+    std::unique_ptr<VhMeshWeldData, WeldFree> m_weldOwner;
+    unsigned int m_indexedCounts[3] = { 0, 0, 0 }; // {vertices, faces, status}
+    unsigned int m_numSourced = 0;                 // triangles of the last indexed extraction that are in the buffer
 };
 
 

@@ -53,6 +53,9 @@ int vh_memset(void* dst, int value, size_t bytes, vhStream_t stream);
  * hipEventElapsedTime(start, stop) is then that kernel's own duration -- the dispatch's begin and end time stamps, what
  * rocprofv3's kernel trace reports -- with no event record in the stream.  The launch consumes the pair. */
 int vh_time_next_launch(void* startEvent, void* stopEvent);
+/* the same for an entry point that launches several kernels: `skip` of the calling thread's timed launches pass first.
+ * vh_extract_iso_surface_pass2[_sourced] launch one kernel; vh_mesh_weld launches insert, number, faces (skip 0, 1, 2). */
+int vh_time_launch_after(uint32_t skip, void* startEvent, void* stopEvent);
 int vh_stream_create(vhStream_t* out);   /* a non-blocking HIP stream, for FFI users without a HIP binding */
 int vh_stream_destroy(vhStream_t stream);
 int vh_stream_synchronize(vhStream_t stream);
@@ -665,6 +668,42 @@ int vh_reset_marching_cubes(const VhMarchingCubesData* data, vhStream_t stream);
 int vh_extract_iso_surface_pass1(const VhHashData* hd, const VhHashParams* hp, const VhMarchingCubesData* data, vhStream_t stream);
 int vh_extract_iso_surface_pass2(const VhHashData* hd, const VhHashParams* hp, const VhMarchingCubesData* data,
                                  uint32_t numOccupiedBlocks, vhStream_t stream);
+/* Pass 2 that also records where each triangle came from (not in the reference): the same triangles as
+ * vh_extract_iso_surface_pass2, and beside triangle i of data->d_triangles the record d_sources[i].
+ *   d_sources          device, m_maxNumTriangles records (triangles beyond that are dropped, and so are their records)
+ *   numOccupiedBlocks  what pass 1 counted (0: nothing is launched) */
+int vh_extract_iso_surface_pass2_sourced(const VhHashData* hd, const VhHashParams* hp, const VhMarchingCubesData* data,
+                                         VhTriangleSource* d_sources, uint32_t numOccupiedBlocks, vhStream_t stream);
+
+/* ---- indexed mesh: the soup welded on the device (csrc/vh_mesh.hip; DESIGN.md section 4, "Indexed mesh") -----------
+ * The key a vertex is welded under: three 20-bit lattice coordinates biased by 2^19 (x in bits 0-19, y 20-39, z 40-59)
+ * and a code in bits 60-61 (the lattice edge's axis, or 3 for a lattice point); bits 62-63 are 0.
+ *   cell   voxel coordinates of the cell          edge  0..11, the order of vertlist
+ *   snap   0 interpolated, 1 at the edge's first end point, 2 at its second
+ * VH_ERR_BAD_ARGUMENT when edge > 11, snap > 2, or the lattice point is outside [-2^19, 2^19) in a coordinate. */
+int vh_mesh_weld_key(const int32_t cell[3], uint32_t edge, uint32_t snap, uint64_t* key);
+/* the number of slots vh_mesh_weld takes for numTriangles when told 0: the smallest power of two >= 6 numTriangles
+ * (twice the 3 n distinct keys n triangles can have), 2^6 at least */
+int vh_mesh_weld_default_slots_log2(uint32_t numTriangles, uint32_t* slotsLog2);
+/* Buffers for welds of up to maxTriangles triangles in tables of up to 1 << slotsLog2 slots (0: the default for
+ * maxTriangles).  Device memory: 16 B per slot and 40 B per possible vertex (3 maxTriangles of them). */
+int vh_mesh_weld_data_alloc(VhMeshWeldData* data, uint32_t maxTriangles, uint32_t slotsLog2);
+void vh_mesh_weld_data_free(VhMeshWeldData* data);
+/* Welds a device soup: any triangles with their source records, not only pass 2's.  Asynchronous on `stream`.
+ *   d_triangles, d_sources  numTriangles of each (may be NULL when numTriangles is 0: the mesh is then empty)
+ *   data                    from vh_mesh_weld_data_alloc; numTriangles <= its m_maxTriangles
+ *   slotsLog2               table size of this weld, <= data's; 0 = vh_mesh_weld_default_slots_log2(numTriangles)
+ * Result in data: d_counts = {vertices, faces, status}, d_vertices / d_keys (one per welded vertex), d_faces (index
+ * triples, winding kept, faces with a repeated index dropped).  A status other than 0 (VH_WELD_TABLE_FULL,
+ * VH_WELD_KEY_RANGE) leaves both counts 0. */
+int vh_mesh_weld(const VhTriangle* d_triangles, const VhTriangleSource* d_sources, uint32_t numTriangles, const VhMeshWeldData* data,
+                 uint32_t slotsLog2, vhStream_t stream);
+/* Waits for the weld and reads {vertices, faces, status}.  out is filled whenever the copy succeeded; the return value
+ * then restates the status: VH_ERR_BAD_ARGUMENT for VH_WELD_KEY_RANGE, VH_ERR_STAGING_OVERFLOW for VH_WELD_TABLE_FULL. */
+int vh_mesh_weld_get_counts(const VhMeshWeldData* data, uint32_t out[3], vhStream_t stream);
+/* Copies the mesh to the host; each of vertices, keys and faces may be NULL.  numVertices / numFaces: from the counts. */
+int vh_mesh_weld_download(const VhMeshWeldData* data, VhVertex* vertices, uint64_t* keys, uint32_t* faces, uint32_t numVertices,
+                          uint32_t numFaces, vhStream_t stream);
 
 /* handle level: CUDAMarchingCubesHashSDF (DSC/CUDAMarchingCubesHashSDF.h:8-67) */
 typedef struct VhMarchingCubes VhMarchingCubes;
@@ -680,6 +719,20 @@ int vh_marching_cubes_extract_iso_surface(VhMarchingCubes* mc, const VhHashData*
                                           const float minCorner[3], const float maxCorner[3], int boxEnabled, int copy);
 /* extractIsoSurface(chunkGrid, rayCastData, camPos, radius) .cpp:149-192 */
 int vh_marching_cubes_extract_iso_surface_chunk_grid(VhMarchingCubes* mc, VhChunkGrid* grid, const float camPos[3], float radius);
+/* extractIsoSurfaceIndexed (not in the reference): reset, pass 1, sourced pass 2, weld, download.  REPLACES the host
+ * mesh with the indexed one and marks it welded, so that saveMesh writes it as it is.
+ *   minCorner, maxCorner, boxEnabled   as vh_marching_cubes_extract_iso_surface (the corners may be NULL)
+ * VH_ERR_STAGING_OVERFLOW when the triangle buffer overflowed (as copyTrianglesToCPU) or the weld table was full,
+ * VH_ERR_BAD_ARGUMENT when a lattice coordinate left the key range; the host mesh is then empty. */
+int vh_marching_cubes_extract_iso_surface_indexed(VhMarchingCubes* mc, const VhHashData* hd, const VhHashParams* hp,
+                                                  const float minCorner[3], const float maxCorner[3], int boxEnabled);
+/* of the last indexed extraction: {vertices, faces, status} */
+int vh_marching_cubes_get_indexed_counts(VhMarchingCubes* mc, uint32_t out[3]);
+/* the device mesh of the last indexed extraction; each of vertices (position + colour), keys and faces may be NULL.
+ * The arrays hold what vh_marching_cubes_get_indexed_counts reports. */
+int vh_marching_cubes_download_indexed(VhMarchingCubes* mc, VhVertex* vertices, uint64_t* keys, uint32_t* faces);
+/* the first n source records of the last indexed extraction (n <= min(triangles produced, m_maxNumTriangles)) */
+int vh_marching_cubes_download_sources(VhMarchingCubes* mc, VhTriangleSource* out, uint32_t n);
 int vh_marching_cubes_copy_triangles_to_cpu(VhMarchingCubes* mc);
 int vh_marching_cubes_clear_mesh_buffer(VhMarchingCubes* mc);
 /* counts of the last extraction: {triangles produced, occupied blocks} */

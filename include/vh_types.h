@@ -209,6 +209,33 @@ typedef struct VhMarchingCubesData {
     uint8_t m_bIsOnGPU;
 } VhMarchingCubesData;
 
+/* Where a triangle of the soup came from (not in the reference; DESIGN.md section 4, "Indexed mesh"): the cell's voxel
+ * coordinates and, for each of its three vertices, 8 bits of `edges`: bits 0-3 the edge 0..11 in the order of
+ * vertlist (DSC/MarchingCubesSDFUtil.h:217-228), bits 4-5 the snap code of vertexInterp: 0 = interpolated,
+ * 1 = returned at its first end point, 2 = at its second.  16 B. */
+typedef struct VhTriangleSource {
+    int32_t cell[3];
+    uint32_t edges;
+} VhTriangleSource;
+
+/* status word of a weld (VhMeshWeldData::d_counts[2]) */
+#define VH_WELD_TABLE_FULL 1u /* a vertex found no slot: the table has fewer slots than there are distinct keys */
+#define VH_WELD_KEY_RANGE 2u  /* a lattice coordinate outside [-2^19, 2^19), or a malformed source record */
+
+/* Device buffers of the weld (vh_mesh_weld): an open-addressing table of numSlots = 1 << m_slotsLog2 slots, and the
+ * indexed mesh it produces.  Sized for m_maxTriangles triangles, that is 3 * m_maxTriangles vertices at worst. */
+typedef struct VhMeshWeldData {
+    uint64_t* d_slotKeys;    /* numSlots; all ones = empty */
+    uint64_t* d_slotWinner;  /* numSlots; rank << 32 | soup vertex while inserting, then the slot's vertex index */
+    uint32_t* d_vertexSlot;  /* 3 * m_maxTriangles: the slot of each soup vertex */
+    uint32_t* d_counts;      /* {vertices, faces, status} */
+    VhVertex* d_vertices;    /* 3 * m_maxTriangles */
+    uint64_t* d_keys;        /* 3 * m_maxTriangles: the key of each welded vertex */
+    uint32_t* d_faces;       /* 3 * m_maxTriangles: index triples */
+    uint32_t m_maxTriangles;
+    uint32_t m_slotsLog2;
+} VhMeshWeldData;
+
 /* The five GlobalAppState flags the reference host classes read
  * (DSC/CUDASceneRepHashSDF.h:249,251,329,331; DSC/CUDASceneRepChunkGrid.cpp:13). */
 typedef struct VhSceneOptions {

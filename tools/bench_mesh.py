@@ -4,8 +4,16 @@ S1 orbit (or cfg3's 1 cm voxels with --config cfg3), `--reps` extractions, HIP-e
 stream, and the CPU oracle on the same scene for comparison.  One JSON line.
 
     python tools/bench_mesh.py [--config cfg2] [--frames 100] [--reps 20] [--no-cpu]
+
+--indexed measures the indexed extraction instead ("Indexed mesh") at the launcher level, on the same
+scene: each kernel's own duration (vh_time_launch_after: the dispatch's time stamps; median of --reps) for the plain
+pass 2, the sourced pass 2 and the three weld kernels, the bytes each route downloads, and the wall time of the host
+merge (mergeCloseVertices + removeDuplicateFaces inside saveMesh) on the same soup.
+
+    python tools/bench_mesh.py --indexed [--config cfg3] [--frames 100] [--reps 20]
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -17,12 +25,82 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 
+def indexed_report(args, scene, hp):
+    """the two routes from the scene to a mesh, stage by stage"""
+    import tempfile
+    from voxelhashing_amd import engine as E, lib, vhtypes as T
+    L = lib.load()
+    hip = C.CDLL("libamdhip64.so")  # the runtime the library already has open: events for vh_time_launch_after
+    hip.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+    e0, e1 = C.c_void_p(), C.c_void_p()
+    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
+    hd, hpp = scene.getHashData(), scene.getHashParams()
+    mp = T.make_marching_cubes_params(hp, 1 << 22)
+    data = T.MarchingCubesData()
+    lib.check(L.vh_marching_cubes_data_alloc(C.byref(data), C.byref(mp)), "vh_marching_cubes_data_alloc")
+    sources = lib.DeviceBuffer(T.TRIANGLE_SOURCE_DTYPE.itemsize * mp.m_maxNumTriangles)
+    lib.check(L.vh_reset_marching_cubes(C.byref(data), None), "reset")
+    lib.check(L.vh_extract_iso_surface_pass1(C.byref(hd), C.byref(hpp), C.byref(data), None), "pass1")
+    nblk = int(lib.download(data.d_numOccupiedBlocks, np.uint32, 1)[0])
+
+    def timed(skip, launch, before=None):
+        us = []
+        for i in range(3 + args.reps):
+            if before:
+                before()
+            lib.check(L.vh_time_launch_after(skip, e0, e1), "vh_time_launch_after")
+            launch()
+            lib.check(L.vh_stream_synchronize(None), "synchronize")
+            ms = C.c_float()
+            assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0, "the launch did not take the events"
+            if i >= 3:
+                us.append(1e3 * ms.value)
+        return round(float(np.median(us)), 2)
+
+    reset = lambda: lib.check(L.vh_reset_marching_cubes(C.byref(data), None), "reset")  # the triangle counter
+    out = dict(blocks=nblk)
+    out["pass2_plain_us"] = timed(0, lambda: lib.check(L.vh_extract_iso_surface_pass2(C.byref(hd), C.byref(hpp), C.byref(data), nblk, None), "pass2"), reset)
+    out["pass2_sourced_us"] = timed(0, lambda: lib.check(L.vh_extract_iso_surface_pass2_sourced(C.byref(hd), C.byref(hpp), C.byref(data), sources.ptr, nblk, None), "pass2 sourced"), reset)
+    n = int(lib.download(data.d_numTriangles, np.uint32, 1)[0])
+    assert n < mp.m_maxNumTriangles
+    w = T.MeshWeldData()
+    lib.check(L.vh_mesh_weld_data_alloc(C.byref(w), n, 0), "vh_mesh_weld_data_alloc")
+    weld = lambda: lib.check(L.vh_mesh_weld(data.d_triangles, sources.ptr, n, C.byref(w), 0, None), "vh_mesh_weld")
+    for skip, name in enumerate(("weld_insert_us", "weld_number_us", "weld_faces_us")):
+        out[name] = timed(skip, weld)
+    counts = (C.c_uint32 * 3)()
+    lib.check(L.vh_mesh_weld_get_counts(C.byref(w), counts, None), "vh_mesh_weld_get_counts")
+    V, F = int(counts[0]), int(counts[1])
+    out.update(triangles=n, vertices=V, faces=F, slots_log2=int(w.m_slotsLog2),
+               weld_device_bytes=16 * (1 << w.m_slotsLog2) + 40 * 3 * n + 16 * n,
+               download_bytes_soup=72 * n, download_bytes_indexed=24 * V + 12 * F)
+    L.vh_mesh_weld_data_free(C.byref(w))
+    L.vh_marching_cubes_data_free(C.byref(data))
+    # the host merge on the same soup: saveMesh = merge + PLY; the PLY alone is timed on the indexed mesh and taken off
+    mc = E.CUDAMarchingCubesHashSDF(mp)
+    with tempfile.TemporaryDirectory() as d:
+        mc.extractIsoSurface(hd, hpp)
+        t0 = time.perf_counter()
+        mc.saveMesh(os.path.join(d, "soup.ply"), None, True)
+        t_soup = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        mc.extractIsoSurfaceIndexed(hd, hpp)
+        t_indexed = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        mc.saveMesh(os.path.join(d, "indexed.ply"), None, True)
+        t_ply = time.perf_counter() - t0
+    out.update(host_merge_s=round(t_soup - t_ply, 4), ply_write_s=round(t_ply, 4), extract_indexed_wall_s=round(t_indexed, 4))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="cfg2")
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--indexed", action="store_true", help="measure the indexed extraction stage by stage instead")
     args = ap.parse_args()
 
     import torch
@@ -39,6 +117,12 @@ def main():
     for pose in poses:
         E.synth_frame(spheres, inside, pose, cp, out=frame)
         scene.integrate(pose, frame, cp, None)
+    if args.indexed:
+        out = dict(metric="indexed mesh: kernel times (us), download sizes (bytes) and the host merge (s)",
+                   config=dict(workload=f"{args.config} after {args.frames} frames of the S1 orbit", voxel_size=hp.m_virtualVoxelSize))
+        out.update(indexed_report(args, scene, hp))
+        print(json.dumps(out))
+        return
     mp = T.make_marching_cubes_params(hp, 1 << 22)
     mc = E.CUDAMarchingCubesHashSDF(mp)
     hd, hpp = scene.getHashData(), scene.getHashParams()

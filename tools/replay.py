@@ -3,7 +3,7 @@
 parameter file, optional mesh at the end) and prints one JSON line with the timing.
 
     python tools/replay.py --params zParameters.txt [--tracking zParametersTracking.txt] [--rgbd-tracking] [--sens a.sens b.sens]
-                           [--mesh scan.ply] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
+                           [--mesh scan.ply [--indexed-mesh]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
                            [--native [--batch N] [--native-tracking]] [--weighted-colour]
 
 Without --sens the files named by s_binaryDumpSensorFile[i] in the parameter file are played.  The rendering keys
@@ -39,6 +39,7 @@ def main():
     ap.add_argument("--rgbd-tracking", action="store_true", help="track with depth + colour (CUDACameraTrackingMultiResRGBD) instead of depth alone")
     ap.add_argument("--sens", nargs="*", default=None)
     ap.add_argument("--mesh", default=None)
+    ap.add_argument("--indexed-mesh", action="store_true", help="--mesh: weld the triangles on the device instead of merging them on the host (not with streaming)")
     ap.add_argument("--record", default=None, help="write what was processed, with the poses used, to this .sens file")
     ap.add_argument("--max-frames", type=int, default=None)
     ap.add_argument("--render-to", default=None, help="renderToFile: the shaded model and the input of every frame as PNGs under this directory")
@@ -53,6 +54,8 @@ def main():
         raise SystemExit("needs a GPU (there is no CPU fallback)")
     from voxelhashing_amd import reconstruction as R
     g = R.read_app_state(args.params)
+    if args.indexed_mesh and g.s_streamingEnabled:
+        raise SystemExit("--indexed-mesh is not available with s_streamingEnabled (the chunk grid extracts per chunk)")
     if args.record:
         g.s_recordData = 1
     read = R.read_tracking_state_rgbd if args.rgbd_tracking else R.read_tracking_state
@@ -93,8 +96,8 @@ def main():
     if args.record:
         out["recorded"] = rec.saveRecordedFramesToFile(args.record)
     if args.mesh:
-        m = rec.extractIsoSurface(args.mesh)
-        out["mesh"] = dict(file=args.mesh, vertices=int(len(m["vertices"])), faces=int(len(m["faces"])))
+        m = rec.extractIsoSurface(args.mesh, indexed=args.indexed_mesh)
+        out["mesh"] = dict(file=args.mesh, indexed=bool(args.indexed_mesh), vertices=int(len(m["vertices"])), faces=int(len(m["faces"])))
     print(json.dumps(out))
 
 

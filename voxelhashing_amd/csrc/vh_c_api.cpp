@@ -354,6 +354,29 @@ int vh_marching_cubes_extract_iso_surface_chunk_grid(VhMarchingCubes* mc, VhChun
     if (!mc || !grid || !camPos) return VH_ERR_BAD_ARGUMENT;
     return guarded([&] { mc->impl.extractIsoSurface(grid->impl, toVec(camPos), radius); });
 }
+int vh_marching_cubes_extract_iso_surface_indexed(VhMarchingCubes* mc, const VhHashData* hd, const VhHashParams* hp,
+                                                  const float minCorner[3], const float maxCorner[3], int boxEnabled)
+{
+    if (!mc || !hd || !hp) return VH_ERR_BAD_ARGUMENT;
+    const vh::vec3f lo = minCorner ? toVec(minCorner) : vh::vec3f{ 0, 0, 0 }, hi = maxCorner ? toVec(maxCorner) : vh::vec3f{ 0, 0, 0 };
+    return guarded([&] { mc->impl.extractIsoSurfaceIndexed(*hd, *hp, lo, hi, boxEnabled != 0); });
+}
+int vh_marching_cubes_get_indexed_counts(VhMarchingCubes* mc, uint32_t out[3])
+{
+    if (!mc || !out) return VH_ERR_BAD_ARGUMENT;
+    mc->impl.getIndexedCounts(out);
+    return VH_OK;
+}
+int vh_marching_cubes_download_indexed(VhMarchingCubes* mc, VhVertex* vertices, uint64_t* keys, uint32_t* faces)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.downloadIndexed(vertices, keys, faces); });
+}
+int vh_marching_cubes_download_sources(VhMarchingCubes* mc, VhTriangleSource* out, uint32_t n)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.downloadSources(out, n); });
+}
 int vh_marching_cubes_copy_triangles_to_cpu(VhMarchingCubes* mc)
 {
     if (!mc) return VH_ERR_BAD_ARGUMENT;

@@ -74,10 +74,12 @@ Stream makeStream(const char* what)
 
 namespace {
 thread_local hipEvent_t t_launchStart = nullptr, t_launchStop = nullptr;
+thread_local uint32_t t_launchSkip = 0; // timed launches that pass before the pair is taken (vh_time_launch_after)
 }
 bool vh_take_launch_events(hipEvent_t* start, hipEvent_t* stop)
 {
     if (!t_launchStart || !t_launchStop) return false;
+    if (t_launchSkip != 0) { t_launchSkip--; return false; }
     *start = t_launchStart; *stop = t_launchStop;
     t_launchStart = t_launchStop = nullptr;
     return true;
@@ -152,6 +154,13 @@ int vh_time_next_launch(void* startEvent, void* stopEvent)
     if (!startEvent || !stopEvent) return VH_ERR_BAD_ARGUMENT;
     t_launchStart = (hipEvent_t)startEvent;
     t_launchStop = (hipEvent_t)stopEvent;
+    t_launchSkip = 0;
+    return VH_OK;
+}
+int vh_time_launch_after(uint32_t skip, void* startEvent, void* stopEvent)
+{
+    VH_TRY(vh_time_next_launch(startEvent, stopEvent));
+    t_launchSkip = skip;
     return VH_OK;
 }
 int vh_stream_create(vhStream_t* out)

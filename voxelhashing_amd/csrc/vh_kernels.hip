@@ -3081,8 +3081,19 @@ VHD VhVertex mc_vertex(F3 p1, F3 p2, float d1, float d2, uint32_t cw)
     return r;
 }
 
-// extractIsoSurfacePass2Kernel :107-129 + extractIsoSurfaceAtPosition
-__global__ __launch_bounds__(512) void k_mc_pass2(VhHashData hd, VhHashParams hp, VhMarchingCubesData data, uint32_t numBlocks)
+// the snap code of a VhTriangleSource: which branch of mc_vertex the pair (d1, d2) takes
+VHD uint32_t mc_snap_code(float d1, float d2)
+{
+    const float isolevel = 0.0f;
+    const bool first = fabsf(isolevel - d1) < 0.00001f, second = fabsf(isolevel - d2) < 0.00001f, flat = fabsf(d1 - d2) < 0.00001f;
+    return first ? 1u : (second ? 2u : (flat ? 1u : 0u));
+}
+
+// extractIsoSurfacePass2Kernel :107-129 + extractIsoSurfaceAtPosition.  kSourced: also write, beside triangle `at`,
+// where it came from (sources[at], what the weld of vh_mesh.hip keys its vertices by); the plain instantiation never
+// reads `sources` and is the kernel it was before the parameter existed.
+template <bool kSourced>
+__global__ __launch_bounds__(512) void k_mc_pass2(VhHashData hd, VhHashParams hp, VhMarchingCubesData data, uint32_t numBlocks, VhTriangleSource* sources)
 {
     __shared__ uint2 sVox[kMcTile * kMcTile * kMcTile];
     __shared__ int sPtr[27];
@@ -3220,6 +3231,18 @@ __global__ __launch_bounds__(512) void k_mc_pass2(VhHashData hd, VhHashParams hp
         tri.v1 = edge_vertex((uint32_t)((l >> 4) & 0xFull));
         tri.v2 = edge_vertex((uint32_t)((l >> 8) & 0xFull));
         data.d_triangles[at] = tri;
+        if constexpr (kSourced) {
+            VhTriangleSource src;
+            src.cell[0] = pi.x; src.cell[1] = pi.y; src.cell[2] = pi.z;
+            src.edges = 0u;
+#pragma unroll
+            for (uint32_t k = 0; k < 3u; k++) {
+                const uint32_t e = (uint32_t)((l >> (4u * k)) & 0xFull);
+                const uint32_t a = (uint32_t)(kEdgeA >> (3u * e)) & 7u, b = (uint32_t)(kEdgeB >> (3u * e)) & 7u;
+                src.edges |= (e | (mc_snap_code(corner_dist(a), corner_dist(b)) << 4)) << (8u * k);
+            }
+            sources[at] = src;
+        }
     }
 }
 
@@ -4290,7 +4313,16 @@ int vh_extract_iso_surface_pass2(const VhHashData* hd, const VhHashParams* hp, c
 {
     if (!hd || !hp || !data || !data->d_params || !data->d_triangles) return VH_ERR_BAD_ARGUMENT;
     if (numOccupiedBlocks == 0) return VH_OK;
-    k_mc_pass2<<<numOccupiedBlocks, 512, 0, (hipStream_t)stream>>>(*hd, *hp, *data, numOccupiedBlocks);
+    VH_LAUNCH_TIMED(k_mc_pass2<false>, numOccupiedBlocks, 512, (hipStream_t)stream, *hd, *hp, *data, numOccupiedBlocks, (VhTriangleSource*)nullptr);
+    return vh_last_launch_error();
+}
+
+int vh_extract_iso_surface_pass2_sourced(const VhHashData* hd, const VhHashParams* hp, const VhMarchingCubesData* data,
+                                         VhTriangleSource* d_sources, uint32_t numOccupiedBlocks, vhStream_t stream)
+{
+    if (!hd || !hp || !data || !data->d_params || !data->d_triangles || !d_sources) return VH_ERR_BAD_ARGUMENT;
+    if (numOccupiedBlocks == 0) return VH_OK;
+    VH_LAUNCH_TIMED(k_mc_pass2<true>, numOccupiedBlocks, 512, (hipStream_t)stream, *hd, *hp, *data, numOccupiedBlocks, d_sources);
     return vh_last_launch_error();
 }
 

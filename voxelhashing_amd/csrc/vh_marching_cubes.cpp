@@ -237,6 +237,7 @@ CUDAMarchingCubesHashSDF::CUDAMarchingCubesHashSDF(const MarchingCubesParams& pa
     : m_params(params), m_stream(stream), m_offline(false)
 {
     std::memset(&m_data, 0, sizeof(m_data));
+    std::memset(&m_weld, 0, sizeof(m_weld));
     check(vh_marching_cubes_data_alloc(&m_data, &m_params), "MarchingCubesData::allocate");
     m_dataOwner.reset(&m_data);
     check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
@@ -244,6 +245,7 @@ CUDAMarchingCubesHashSDF::CUDAMarchingCubesHashSDF(const MarchingCubesParams& pa
 
 CUDAMarchingCubesHashSDF::~CUDAMarchingCubesHashSDF() { (void)hipStreamSynchronize((hipStream_t)m_stream); }
 void CUDAMarchingCubesHashSDF::DataFree::operator()(MarchingCubesData* d) const noexcept { vh_marching_cubes_data_free(d); }
+void CUDAMarchingCubesHashSDF::WeldFree::operator()(VhMeshWeldData* d) const noexcept { vh_mesh_weld_data_free(d); }
 
 unsigned int CUDAMarchingCubesHashSDF::getNumTriangles()
 {
@@ -289,6 +291,69 @@ void CUDAMarchingCubesHashSDF::extractIsoSurface(const HashData& hashData, const
     copyTrianglesToCPU();
 }
 
+// Not in the reference.  The soup stays on the device; what comes back is the welded mesh.
+void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner,
+                                                        const vh::vec3f& maxCorner, bool boxEnabled)
+{
+    clearMeshBuffer(); // nothing partial is left behind by an error
+    m_indexedCounts[0] = m_indexedCounts[1] = m_indexedCounts[2] = 0;
+    m_numSourced = 0;
+    if (!d_sources) d_sources = vh::deviceAlloc<VhTriangleSource>(m_params.m_maxNumTriangles, "triangle sources");
+    check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
+    m_params.m_maxCorner[0] = maxCorner.x; m_params.m_maxCorner[1] = maxCorner.y; m_params.m_maxCorner[2] = maxCorner.z;
+    m_params.m_minCorner[0] = minCorner.x; m_params.m_minCorner[1] = minCorner.y; m_params.m_minCorner[2] = minCorner.z;
+    m_params.m_boxEnabled = boxEnabled ? 1u : 0u;
+    check(vh_marching_cubes_update_params(&m_data, &m_params, m_stream), "MarchingCubesData::updateParams");
+    check(vh_extract_iso_surface_pass1(&hashData, &hashParams, &m_data, m_stream), "extractIsoSurfacePass1CUDA");
+    check(vh_extract_iso_surface_pass2_sourced(&hashData, &hashParams, &m_data, d_sources.get(), getNumOccupiedBlocks(), m_stream),
+          "extractIsoSurfacePass2CUDA (sourced)");
+    const unsigned int nTriangles = getNumTriangles();
+    m_numSourced = std::min(nTriangles, m_params.m_maxNumTriangles);
+    if (nTriangles >= m_params.m_maxNumTriangles) // the test of copyTrianglesToCPU
+        throw vh::Error(VH_ERR_STAGING_OVERFLOW, "not enough memory to store triangles for chunk; increase s_marchingCubesMaxNumTriangles");
+    // the table is sized by the triangles there are, not by the buffer: it grows, and is kept for the next call
+    if (!m_weldOwner || m_weld.m_maxTriangles < nTriangles) {
+        m_weldOwner.reset();
+        check(vh_mesh_weld_data_alloc(&m_weld, nTriangles + nTriangles / 4u, 0), "vh_mesh_weld_data_alloc");
+        m_weldOwner.reset(&m_weld);
+    }
+    check(vh_mesh_weld(m_data.d_triangles, d_sources.get(), nTriangles, &m_weld, 0, m_stream), "vh_mesh_weld");
+    unsigned int counts[3] = { 0, 0, 0 };
+    const int rc = vh_mesh_weld_get_counts(&m_weld, counts, m_stream);
+    m_indexedCounts[2] = counts[2];
+    if (rc == VH_ERR_STAGING_OVERFLOW) throw vh::Error(rc, "mesh weld: the table is full");
+    if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "mesh weld: a voxel coordinate is outside the key range of +-2^19");
+    check(rc, "vh_mesh_weld_get_counts");
+    std::vector<VhVertex> verts(counts[0]);
+    vh::MeshData md;
+    md.m_FaceIndicesVertices.resize(3 * (size_t)counts[1]);
+    check(vh_mesh_weld_download(&m_weld, verts.data(), nullptr, md.m_FaceIndicesVertices.data(), counts[0], counts[1], m_stream), "vh_mesh_weld_download");
+    md.m_Vertices.resize(counts[0]);
+    md.m_Colors.resize(4 * (size_t)counts[0]);
+    for (size_t i = 0; i < verts.size(); i++) {
+        md.m_Vertices[i] = { verts[i].p[0], verts[i].p[1], verts[i].p[2] };
+        md.m_Colors[4 * i + 0] = verts[i].c[0]; md.m_Colors[4 * i + 1] = verts[i].c[1]; md.m_Colors[4 * i + 2] = verts[i].c[2]; md.m_Colors[4 * i + 3] = 1.0f;
+    }
+    m_meshData = std::move(md);
+    m_indexedCounts[0] = counts[0]; m_indexedCounts[1] = counts[1];
+    m_welded = true;
+}
+
+void CUDAMarchingCubesHashSDF::downloadIndexed(VhVertex* vertices, uint64_t* keys, uint32_t* faces)
+{
+    if (m_indexedCounts[0] == 0 && m_indexedCounts[1] == 0) return;
+    if (!m_weldOwner) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexed: no indexed extraction");
+    check(vh_mesh_weld_download(&m_weld, vertices, keys, faces, m_indexedCounts[0], m_indexedCounts[1], m_stream), "vh_mesh_weld_download");
+}
+
+void CUDAMarchingCubesHashSDF::downloadSources(VhTriangleSource* out, unsigned int n)
+{
+    if (n == 0) return;
+    if (!out || !d_sources || n > m_numSourced) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadSources");
+    checkHip(hipMemcpyAsync(out, d_sources.get(), sizeof(VhTriangleSource) * (size_t)n, hipMemcpyDeviceToHost, (hipStream_t)m_stream), "sources");
+    checkHip(hipStreamSynchronize((hipStream_t)m_stream), "sources");
+}
+
 // .cpp:31-86
 void CUDAMarchingCubesHashSDF::copyTrianglesToCPU()
 {
@@ -296,6 +361,7 @@ void CUDAMarchingCubesHashSDF::copyTrianglesToCPU()
     if (nTriangles >= m_params.m_maxNumTriangles)
         throw vh::Error(VH_ERR_STAGING_OVERFLOW, "not enough memory to store triangles for chunk; increase s_marchingCubesMaxNumTriangles");
     if (nTriangles == 0) return;
+    m_welded = false; // the buffer is about to hold something the weld did not make
     std::vector<VhTriangle> tris(nTriangles);
     downloadTriangles(tris.data(), nTriangles);
     vh::MeshData md;
@@ -337,9 +403,11 @@ void CUDAMarchingCubesHashSDF::saveMesh(const std::string& filename, const vh::m
             actual = stem + std::to_string(++num) + ext;
         }
     }
-    if (!m_meshData.hasVertexIndices()) m_meshData.makeTriangleSoupIndices();
-    m_meshData.mergeCloseVertices(0.0001f);
-    m_meshData.removeDuplicateFaces();
+    if (!m_welded) { // the indexed extraction's mesh is merged already, exactly
+        if (!m_meshData.hasVertexIndices()) m_meshData.makeTriangleSoupIndices();
+        m_meshData.mergeCloseVertices(0.0001f);
+        m_meshData.removeDuplicateFaces();
+    }
     if (transform) m_meshData.applyTransform(*transform);
     m_meshData.saveToPLY(actual);
     clearMeshBuffer();

@@ -744,6 +744,34 @@ class CUDAMarchingCubesHashSDF:
         check(self.L.vh_marching_cubes_extract_iso_surface_chunk_grid(self.handle, chunkGrid.handle, f16(camPos), radius),
               "extractIsoSurface(chunkGrid)")
 
+    def extractIsoSurfaceIndexed(self, hashData, hashParams, minCorner=(0, 0, 0), maxCorner=(0, 0, 0), boxEnabled=False):
+        """the extraction with the soup welded on the device: REPLACES the mesh buffer with the indexed mesh (mesh(),
+        saveMesh write it as it is); indexed() has it with the keys, sources() the records it was welded by"""
+        check(self.L.vh_marching_cubes_extract_iso_surface_indexed(self.handle, C.byref(hashData), C.byref(hashParams), f16(minCorner),
+                                                                   f16(maxCorner), int(boxEnabled)), "extractIsoSurfaceIndexed")
+
+    def indexed_counts(self):
+        out = (C.c_uint32 * 3)()
+        check(self.L.vh_marching_cubes_get_indexed_counts(self.handle, out), "get_indexed_counts")
+        return dict(vertices=int(out[0]), faces=int(out[1]), status=int(out[2]))
+
+    def indexed(self):
+        """device mesh of the last indexed extraction -> vertices (V,3) f32, colors (V,3) f32, keys (V,) u64, faces (F,3) u32"""
+        n = self.indexed_counts()
+        v = np.zeros(n["vertices"], dtype=T.VERTEX_DTYPE)
+        k = np.zeros(n["vertices"], dtype=np.uint64)
+        f = np.zeros((n["faces"], 3), dtype=np.uint32)
+        check(self.L.vh_marching_cubes_download_indexed(self.handle, v.ctypes.data, k.ctypes.data, f.ctypes.data), "download_indexed")
+        return dict(vertices=np.ascontiguousarray(v["p"]), colors=np.ascontiguousarray(v["c"]), keys=k, faces=f)
+
+    def sources(self):
+        """source records of the last indexed extraction, beside triangles() -> numpy array of T.TRIANGLE_SOURCE_DTYPE"""
+        n = min(self.counts()["triangles"], self._params.m_maxNumTriangles)
+        out = np.zeros(n, dtype=T.TRIANGLE_SOURCE_DTYPE)
+        if n:
+            check(self.L.vh_marching_cubes_download_sources(self.handle, out.ctypes.data, n), "download_sources")
+        return out
+
     def copyTrianglesToCPU(self):
         check(self.L.vh_marching_cubes_copy_triangles_to_cpu(self.handle), "copyTrianglesToCPU")
 
@@ -775,6 +803,45 @@ class CUDAMarchingCubesHashSDF:
     def saveMesh(self, filename, transform=None, overwriteExistingFile=False):
         t = f16(transform) if transform is not None else None
         check(self.L.vh_marching_cubes_save_mesh(self.handle, filename.encode(), t, int(overwriteExistingFile)), "saveMesh")
+
+
+def mesh_weld_key(cell, edge, snap):
+    """vh_mesh_weld_key: the 64-bit key of a vertex (host side, no GPU); raises VhError when it has none"""
+    key = C.c_uint64()
+    check(load().vh_mesh_weld_key((C.c_int32 * 3)(*[int(v) for v in cell]), int(edge), int(snap), C.byref(key)), "vh_mesh_weld_key")
+    return int(key.value)
+
+
+def mesh_weld(triangles, sources, slots_log2=0, raise_on_status=True, stream=None):
+    """vh_mesh_weld on hand-made input: a soup (T.TRIANGLE_DTYPE) and its records (T.TRIANGLE_SOURCE_DTYPE) ->
+    vertices, colors, keys, faces as CUDAMarchingCubesHashSDF.indexed(), and counts / status / code of the weld.  A full
+    table or a key out of range raises VhError, or with raise_on_status=False comes back as `code` beside empty arrays."""
+    L = load()
+    tris = np.ascontiguousarray(triangles, dtype=T.TRIANGLE_DTYPE).ravel()
+    srcs = np.ascontiguousarray(sources, dtype=T.TRIANGLE_SOURCE_DTYPE).ravel()
+    if len(tris) != len(srcs):
+        raise ValueError("one source record per triangle")
+    n = len(tris)
+    d_tris, d_srcs = DeviceBuffer.from_numpy(tris, stream), DeviceBuffer.from_numpy(srcs, stream)
+    w = T.MeshWeldData()
+    check(L.vh_mesh_weld_data_alloc(C.byref(w), n, slots_log2), "vh_mesh_weld_data_alloc")
+    slots = int(w.m_slotsLog2)
+    try:
+        check(L.vh_mesh_weld(d_tris.ptr, d_srcs.ptr, n, C.byref(w), slots_log2, stream), "vh_mesh_weld")
+        counts = (C.c_uint32 * 3)()
+        code = L.vh_mesh_weld_get_counts(C.byref(w), counts, stream)
+        if code < 0 or (code != 0 and (raise_on_status or counts[2] == 0)):
+            check(code, "vh_mesh_weld")
+        v = np.zeros(int(counts[0]), dtype=T.VERTEX_DTYPE)
+        k = np.zeros(int(counts[0]), dtype=np.uint64)
+        f = np.zeros((int(counts[1]), 3), dtype=np.uint32)
+        check(L.vh_mesh_weld_download(C.byref(w), v.ctypes.data, k.ctypes.data, f.ctypes.data, len(v), len(f), stream), "vh_mesh_weld_download")
+    finally:
+        L.vh_mesh_weld_data_free(C.byref(w))
+        d_tris.free()
+        d_srcs.free()
+    return dict(vertices=np.ascontiguousarray(v["p"]), colors=np.ascontiguousarray(v["c"]), keys=k, faces=f,
+                counts=(int(counts[0]), int(counts[1])), status=int(counts[2]), code=int(code), slots_log2=slots)
 
 
 # ---- sensor pre-processing (DSC/CameraUtil.cu) over the C ABI: numpy in, numpy out (tests, tools) ----

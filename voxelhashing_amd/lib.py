@@ -32,6 +32,7 @@ PROTOTYPES = {
     "vh_memcpy_d2h": (C.c_int, [_VP, _VP, C.c_size_t, _VP]),
     "vh_memset": (C.c_int, [_VP, C.c_int, C.c_size_t, _VP]),
     "vh_time_next_launch": (C.c_int, [_VP, _VP]),
+    "vh_time_launch_after": (C.c_int, [C.c_uint32, _VP, _VP]),
     "vh_stream_create": (C.c_int, [P(_VP)]),
     "vh_stream_destroy": (C.c_int, [_VP]),
     "vh_stream_synchronize": (C.c_int, [_VP]),
@@ -221,6 +222,18 @@ PROTOTYPES = {
     "vh_reset_marching_cubes": (C.c_int, [P(T.MarchingCubesData), _VP]),
     "vh_extract_iso_surface_pass1": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.MarchingCubesData), _VP]),
     "vh_extract_iso_surface_pass2": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.MarchingCubesData), C.c_uint32, _VP]),
+    "vh_extract_iso_surface_pass2_sourced": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.MarchingCubesData), _VP, C.c_uint32, _VP]),
+    "vh_mesh_weld_key": (C.c_int, [P(C.c_int32), C.c_uint32, C.c_uint32, P(C.c_uint64)]),
+    "vh_mesh_weld_default_slots_log2": (C.c_int, [C.c_uint32, P(C.c_uint32)]),
+    "vh_mesh_weld_data_alloc": (C.c_int, [P(T.MeshWeldData), C.c_uint32, C.c_uint32]),
+    "vh_mesh_weld_data_free": (None, [P(T.MeshWeldData)]),
+    "vh_mesh_weld": (C.c_int, [_VP, _VP, C.c_uint32, P(T.MeshWeldData), C.c_uint32, _VP]),
+    "vh_mesh_weld_get_counts": (C.c_int, [P(T.MeshWeldData), P(C.c_uint32), _VP]),
+    "vh_mesh_weld_download": (C.c_int, [P(T.MeshWeldData), _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP]),
+    "vh_marching_cubes_extract_iso_surface_indexed": (C.c_int, [_VP, P(T.HashData), P(T.HashParams), P(C.c_float), P(C.c_float), C.c_int]),
+    "vh_marching_cubes_get_indexed_counts": (C.c_int, [_VP, P(C.c_uint32)]),
+    "vh_marching_cubes_download_indexed": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "vh_marching_cubes_download_sources": (C.c_int, [_VP, _VP, C.c_uint32]),
     "vh_marching_cubes_create": (C.c_int, [P(T.MarchingCubesParams), _VP, P(_VP)]),
     "vh_marching_cubes_destroy": (None, [_VP]),
     "vh_marching_cubes_parameters": (C.c_int, [C.c_uint32, C.c_float, C.c_float, C.c_uint32, P(T.MarchingCubesParams)]),

@@ -573,9 +573,13 @@ class Reconstruction:
                 h.m_depthShift, bytes(h.m_sensorName).decode(), h.m_colorCompressionType, h.m_depthCompressionType,
                 np.array(h.m_depthExtrinsic[:]), np.array(h.m_colorExtrinsic[:]))
 
-    def extractIsoSurface(self, filename=None):
+    def extractIsoSurface(self, filename=None, indexed=False):
         """StopScanningAndExtractIsoSurfaceMC: marching cubes over the whole scene (through the chunk grid when
-        streaming is on) -> (vertices, colours, faces); written as a PLY when a file name is given"""
+        streaming is on) -> (vertices, colours, faces); written as a PLY when a file name is given.  indexed (not in the
+        reference): weld the triangles on the device instead of merging them on the host; the chunk-grid extraction
+        has no such path (its boxes overlap), so with streaming on this is refused before any GPU work."""
+        if indexed and self.chunk_grid is not None:
+            raise ValueError("indexed extraction is not available with streaming enabled (the chunk grid extracts per chunk)")
         if self.marching_cubes is None:
             self.marching_cubes = E.CUDAMarchingCubesHashSDF(self.mp)
             # offline: every batch is merged and de-duplicated as it arrives; otherwise the buffer holds the triangle
@@ -586,6 +590,8 @@ class Reconstruction:
         if self.chunk_grid is not None:
             pos = (self.scene.getLastRigidTransform().reshape(4, 4) @ np.array(list(self.gas.s_streamingPos) + [1.0], dtype=np.float32))[:3]
             mc.extractIsoSurfaceChunkGrid(self.chunk_grid, pos, self.gas.s_streamingRadius)
+        elif indexed:
+            mc.extractIsoSurfaceIndexed(self.scene.getHashData(), self.scene.getHashParams())
         else:
             mc.extractIsoSurface(self.scene.getHashData(), self.scene.getHashParams())
         mesh = mc.mesh()

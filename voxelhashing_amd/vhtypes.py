@@ -132,6 +132,25 @@ class MarchingCubesData(C.Structure):
 
 # MarchingCubesData::Triangle = 3 x {float3 p, float3 c} (72 B)
 TRIANGLE_DTYPE = np.dtype([("v", [("p", np.float32, 3), ("c", np.float32, 3)], 3)])
+VERTEX_DTYPE = np.dtype([("p", np.float32, 3), ("c", np.float32, 3)])
+
+
+class TriangleSource(C.Structure):
+    """VhTriangleSource: where a triangle of the soup came from (16 B)"""
+    _fields_ = [("cell", C.c_int32 * 3), ("edges", C.c_uint32)]
+
+
+# edges: 8 bits per vertex, bits 0-3 the edge 0..11 (vertlist order), bits 4-5 the snap code 0 / 1 / 2
+TRIANGLE_SOURCE_DTYPE = np.dtype([("cell", np.int32, 3), ("edges", np.uint32)])
+WELD_TABLE_FULL, WELD_KEY_RANGE = 1, 2  # bits of the weld's status word
+
+
+class MeshWeldData(C.Structure):
+    _fields_ = [
+        ("d_slotKeys", C.c_void_p), ("d_slotWinner", C.c_void_p), ("d_vertexSlot", C.c_void_p), ("d_counts", C.c_void_p),
+        ("d_vertices", C.c_void_p), ("d_keys", C.c_void_p), ("d_faces", C.c_void_p),
+        ("m_maxTriangles", C.c_uint32), ("m_slotsLog2", C.c_uint32),
+    ]
 
 
 class AppState(C.Structure):
