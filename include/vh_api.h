@@ -183,6 +183,12 @@ size_t vh_render_schedule_bytes(uint32_t width, uint32_t height);
 /* how many tiles of an image of this size a scheduled render marches with two waves each (the dearest ones; 0 for
  * small images): lets a test make sure it exercises that path */
 uint32_t vh_render_split_tiles(uint32_t width, uint32_t height);
+/* Voxel addressing of the interval ray caster: 1 if, for a pool of numSDFBlocks blocks, it addresses voxels with 32-bit
+ * byte offsets on the pool's base (numSDFBlocks * 4096 <= 2^32 bytes), 0 if with 64-bit addresses.  The maps are the same.
+ * vh_debug_render_force_offsets64(1) makes every later render of the process take the 64-bit form (0: back to the rule)
+ * and returns the setting it replaces: for tests that compare the two. */
+uint32_t vh_render_offsets32(uint32_t numSDFBlocks);
+uint32_t vh_debug_render_force_offsets64(uint32_t on);
 int vh_render_intervals(const VhHashData* hd, const VhHashParams* hp, const VhRayCastData* rd, const VhDepthCameraParams* cp,
                         const VhRayCastParams* rp, uint32_t* d_tileHeads, const VhTileBlock* d_tileBlocks, uint32_t tileCapacity,
                         uint32_t* d_schedule, uint32_t phase, vhStream_t stream);

@@ -11,6 +11,7 @@
 // MUST be compiled with -ffp-contract=off (see vh_device.hpp).
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -1602,6 +1603,7 @@ struct HashLookup {
     const VhHashParams& hp;
     HashMod hm;
     BlockCache bc;
+    static constexpr bool kOffsets32 = false; // (load_voxel)
     VHD int find(int bx, int by, int bz) { return cached_lookup(hd, hp, hm, bc, bx, by, bz); }
     // may the sample whose first tap lies in this block be valid?  (occupancy bit of the bucket: one cached dword)
     VHD bool first_tap(int bx, int by, int bz, int& handle)
@@ -1650,12 +1652,19 @@ struct HashLookup {
 // allocated; when the list overflowed, the table holds a part of it and a miss falls back to the hash table.
 constexpr uint32_t kTileSlotWords = 12;
 
-template <uint32_t kTileTabSlots> // 2 x the list capacity (load factor <= 1/2), a power of two
+//
+// Two lookups share the table.  TileLookupComplete serves a tile whose list took every block (all of them at 4 cm
+// voxels): LDS only, nothing of the hash table is named in it, so the march instantiated on it keeps neither the table's
+// pointers nor the bucket modulus nor the second block of a tap pair in registers.  TileLookup is the general one, for
+// the tile whose list overflowed.  render_tile picks one per wave.
+// OFFSETS32: voxel loads take a 32-bit byte offset on the pool's base (load_voxel).
+template <uint32_t kTileTabSlots, bool OFFSETS32> // 2 x the list capacity (load factor <= 1/2), a power of two
 struct TileLookup {
     const int* tab;
     bool complete;
     const VhHashData& hd;
     const VhHashParams& hp;
+    static constexpr bool kOffsets32 = OFFSETS32;
     VHD static uint32_t slot_of(int bx, int by, int bz)
     {
         // Multiply-shift hash, three full-rate 24-bit multiplies.  The blocks of a tile are a dense slab along its beam;
@@ -1716,14 +1725,59 @@ struct TileLookup {
     }
 };
 
+template <uint32_t kTileTabSlots, bool OFFSETS32>
+struct TileLookupComplete {
+    const int* tab;
+    static constexpr bool kOffsets32 = OFFSETS32;
+    // handle: the slot of the block (>= 0), or kPtrUnknown
+    VHD bool first_tap(int bx, int by, int bz, int& handle) const
+    {
+        handle = TileLookup<kTileTabSlots, OFFSETS32>::slot_find(tab, bx, by, bz);
+        if (handle >= 0) return true;
+        handle = kPtrUnknown;
+        return false;
+    }
+    // (only the first tap's block and `straddle` are read: the second block's coordinates die where straddle is formed)
+    VHD bool resolve(int handle, int bxa, int bya, int bza, int, int, int, uint32_t straddle, int (&p)[8]) const
+    {
+        const int sl = handle >= 0 ? handle : TileLookup<kTileTabSlots, OFFSETS32>::slot_find(tab, bxa, bya, bza);
+        if (sl < 0) return false; // the first tap reads the zero voxel (weight 0)
+        // the tap pair of an axis lies in one block or in two adjacent ones: combo j reads neighbour (j & straddle)
+        const int* e = &tab[(uint32_t)sl * kTileSlotWords + 3u];
+        int all = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; j++) {
+            p[j] = e[j & straddle];
+            all |= p[j];
+        }
+        return all >= 0; // voxel pointers are >= 0, VH_FREE_ENTRY is not
+    }
+};
+
 // One 8-byte load per voxel.  As an (indivisible) relaxed atomic: an ordinary load is split by the compiler into its
 // two words, and the sdf word is then fetched only after the weight test -- a second trip to memory per sample.
+//
+// OFFSETS32: the pool is at most 2^32 bytes (offsets32_ok), so the voxel's byte offset fits an unsigned 32-bit register
+// and the load takes it beside the pool's base in scalar registers: one address register per tap instead of a 64-bit
+// pair, and no 64-bit add.  The arithmetic is unsigned 32-bit on purpose (offsets with the top bit set are ordinary).
+template <bool OFFSETS32 = false>
 VHD uint2 load_voxel(const VhHashData& hd, int ptr, int lx, int ly, int lz)
 {
-    const unsigned long long v = __hip_atomic_load(
-        reinterpret_cast<const unsigned long long*>(&hd.d_SDFBlocks[(uint32_t)ptr + (uint32_t)(lz * 64 + ly * 8 + lx)]),
-        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    const unsigned long long* at;
+    if constexpr (OFFSETS32) {
+        const uint32_t off = ((uint32_t)ptr + (uint32_t)(lz * 64 + ly * 8 + lx)) * (uint32_t)sizeof(VhVoxel);
+        at = reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(hd.d_SDFBlocks) + off);
+    } else {
+        at = reinterpret_cast<const unsigned long long*>(&hd.d_SDFBlocks[(uint32_t)ptr + (uint32_t)(lz * 64 + ly * 8 + lx)]);
+    }
+    const unsigned long long v = __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
+}
+static_assert(sizeof(VhVoxel) == 8, "load_voxel");
+// may the ray caster address this pool's voxels with 32-bit byte offsets?
+static bool offsets32_ok(uint32_t numSDFBlocks)
+{
+    return (uint64_t)numSDFBlocks * (VH_SDF_BLOCK_SIZE * VH_SDF_BLOCK_SIZE * VH_SDF_BLOCK_SIZE) * sizeof(VhVoxel) <= (1ull << 32);
 }
 
 struct Taps {
@@ -1756,10 +1810,11 @@ VHD bool trilinear(const VhHashData& hd, float vs, LK& lk, int p0in, const Taps&
     const int lx0 = x0 & 7, ly0 = y0 & 7, lz0 = z0 & 7; // = local1(): two's complement & 7 is the non-negative remainder
     const int lx1 = x1 & 7, ly1 = y1 & 7, lz1 = z1 & 7;
     // the eight voxels, in flight together (reference tap order 000,100,010,001,110,011,101,111)
-    uint2 r000 = load_voxel(hd, p0, lx0, ly0, lz0), r100 = load_voxel(hd, p1, lx1, ly0, lz0);
-    uint2 r010 = load_voxel(hd, p2, lx0, ly1, lz0), r001 = load_voxel(hd, p4, lx0, ly0, lz1);
-    uint2 r110 = load_voxel(hd, p3, lx1, ly1, lz0), r011 = load_voxel(hd, p6, lx0, ly1, lz1);
-    uint2 r101 = load_voxel(hd, p5, lx1, ly0, lz1), r111 = load_voxel(hd, p7, lx1, ly1, lz1);
+    constexpr bool O32 = LK::kOffsets32;
+    uint2 r000 = load_voxel<O32>(hd, p0, lx0, ly0, lz0), r100 = load_voxel<O32>(hd, p1, lx1, ly0, lz0);
+    uint2 r010 = load_voxel<O32>(hd, p2, lx0, ly1, lz0), r001 = load_voxel<O32>(hd, p4, lx0, ly0, lz1);
+    uint2 r110 = load_voxel<O32>(hd, p3, lx1, ly1, lz0), r011 = load_voxel<O32>(hd, p6, lx0, ly1, lz1);
+    uint2 r101 = load_voxel<O32>(hd, p5, lx1, ly0, lz1), r111 = load_voxel<O32>(hd, p7, lx1, ly1, lz1);
     // one trip to memory for the eight: left alone the compiler waits for the first pair before it issues the rest
     // (three trips), and the dearest waves of a frame run at the pace of their own chain of loads
     asm volatile("" : "+v"(r000.x), "+v"(r000.y), "+v"(r100.x), "+v"(r100.y), "+v"(r010.x), "+v"(r010.y), "+v"(r001.x), "+v"(r001.y),
@@ -1808,10 +1863,11 @@ VHD bool taps_issue(const VhHashData& hd, LK& lk, int p0in, const Taps& tp, TapL
     if (!lk.resolve(p0in, tp.bxa, tp.bya, tp.bza, tp.bxb, tp.byb, tp.bzb, straddle, p)) return false;
     const int lx0 = tp.x0 & 7, ly0 = tp.y0 & 7, lz0 = tp.z0 & 7;
     const int lx1 = tp.x1 & 7, ly1 = tp.y1 & 7, lz1 = tp.z1 & 7;
-    L.r000 = load_voxel(hd, p[0], lx0, ly0, lz0); L.r100 = load_voxel(hd, p[1], lx1, ly0, lz0);
-    L.r010 = load_voxel(hd, p[2], lx0, ly1, lz0); L.r001 = load_voxel(hd, p[4], lx0, ly0, lz1);
-    L.r110 = load_voxel(hd, p[3], lx1, ly1, lz0); L.r011 = load_voxel(hd, p[6], lx0, ly1, lz1);
-    L.r101 = load_voxel(hd, p[5], lx1, ly0, lz1); L.r111 = load_voxel(hd, p[7], lx1, ly1, lz1);
+    constexpr bool O32 = LK::kOffsets32;
+    L.r000 = load_voxel<O32>(hd, p[0], lx0, ly0, lz0); L.r100 = load_voxel<O32>(hd, p[1], lx1, ly0, lz0);
+    L.r010 = load_voxel<O32>(hd, p[2], lx0, ly1, lz0); L.r001 = load_voxel<O32>(hd, p[4], lx0, ly0, lz1);
+    L.r110 = load_voxel<O32>(hd, p[3], lx1, ly1, lz0); L.r011 = load_voxel<O32>(hd, p[6], lx0, ly1, lz1);
+    L.r101 = load_voxel<O32>(hd, p[5], lx1, ly0, lz1); L.r111 = load_voxel<O32>(hd, p[7], lx1, ly1, lz1);
     return true;
 }
 VHD bool taps_finish(TapLoads& L, float vs, float rvs, F3 pos, float& dist)
@@ -1921,7 +1977,6 @@ VHD void tap_coords(const RayQ& rq, float t, Taps& tp)
         tp.bxb = vvp_to_block1(tp.x1); tp.byb = vvp_to_block1(tp.y1); tp.bzb = vvp_to_block1(tp.z1);
     }
 }
-
 
 #ifndef VH_PIPELINE_SMALL // (measurement builds: the pipelined march with the small tables too)
 #define VH_PIPELINE_SMALL 0
@@ -2429,7 +2484,16 @@ __global__ __launch_bounds__(256) VH_QUERY_RAYS_OCCUPANCY void k_query_rays(VhHa
 // One wave per 8x8-pixel tile with the tile's head and block list from k_interval_splat: the wave builds its block
 // table in LDS, forms the tile's depth interval from the listed blocks and marches inside it.  The kernel is bound by
 // VALU issue per SIMD: what counts is instructions per sample and even loads of the SIMDs.
-template <bool GRADIENTS, uint32_t CAP>
+// lane_id() from instructions the compiler does not merge with an earlier lane_id(): for code that would otherwise keep
+// the number in a register across a long stretch that has none to spare
+VHD uint32_t lane_id_again()
+{
+    uint32_t l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+
+template <bool GRADIENTS, uint32_t CAP, bool OFFSETS32>
 VHD void render_tile(const VhHashData& hd, const VhHashParams& hp, const VhRayCastData& rd, const VhDepthCameraParams& cp, const VhRayCastParams& rp,
                      uint4* heads, const int4* lists, uint32_t cap, uint32_t* sched, uint32_t phase,
                      int (*tileTab)[2u * CAP * 12u])
@@ -2438,7 +2502,8 @@ VHD void render_tile(const VhHashData& hd, const VhHashParams& hp, const VhRayCa
     // three workgroups per compute unit; for fine voxels, where a few tiles see more than 64 blocks and would
     // otherwise probe the hash table for every block the table could not hold)
     constexpr uint32_t kTileTabSlots = 2u * CAP;
-    typedef TileLookup<kTileTabSlots> Lookup;
+    typedef TileLookup<kTileTabSlots, OFFSETS32> Lookup;
+    typedef TileLookupComplete<kTileTabSlots, OFFSETS32> LookupComplete;
     static_assert(kTileSlotWords == 12u, "tileTab row size");
     const uint32_t lane = lane_id();
     const uint32_t W = rp.m_width, H = rp.m_height;
@@ -2470,7 +2535,9 @@ VHD void render_tile(const VhHashData& hd, const VhHashParams& hp, const VhRayCa
 #else
 #define VH_WAVE_STAMP(COST)
 #endif
-    int* tab = tileTab[threadIdx.x / kWave];
+    // (in a scalar register: it is wanted again after the march, and a vector register held across the march is one spilled)
+    const uint32_t waveInGroup = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    int* tab = tileTab[waveInGroup];
     // consume the head and re-arm it, so that no separate clear pass is needed
     const uint4 head = heads[tile];
     // With the large tables (three waves per SIMD: a trip to memory is not hidden by five other waves) the tile's list entries
@@ -2490,7 +2557,9 @@ VHD void render_tile(const VhHashData& hd, const VhHashParams& hp, const VhRayCa
     float tileZmin = __uint_as_float(head.x), tileZmax = __uint_as_float(head.y); // as splatted (lists == nullptr)
     if (lane == 0 && half == 0u) heads[tile] = make_uint4(0x7f800000u, 0u, 0u, 0u); // (a split tile: once both halves have read it)
     const uint32_t listed = min(head.z, min(cap, CAP));
-    const bool complete = listed == head.z;
+    // wave-uniform, and said so: the two marches below are then the two sides of a scalar branch, and what the one for
+    // overflowed lists needs does not have to outlive the other
+    const bool complete = __builtin_amdgcn_readfirstlane(listed == head.z ? 1 : 0) != 0;
 #if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 41
     stampList = head.z | (complete ? 0u : 0x10000u);
 #endif
@@ -2597,50 +2666,64 @@ VHD void render_tile(const VhHashData& hd, const VhHashParams& hp, const VhRayCa
             tileZmax = zhi;
         }
     }
+    // (the same in every lane: kept in scalar registers while the rays are set up)
+    tileZmin = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(tileZmin)));
+    tileZmax = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(tileZmax)));
 #if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 41
     stamp1 = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif
-    const uint32_t x = (tile % tilesX) * 8 + (lane & 7), y = (tile / tilesX) * 8 + (lane >> 3);
-    const bool inImage = x < W && y < H;
-    const size_t pix = (size_t)y * W + x;
+    const uint32_t tileX = (tile % tilesX) * 8, tileY = (tile / tilesX) * 8; // (scalar)
     VH_STAT_DECL
     RayHit out;
     out.hit = false;
     uint32_t cost = 0u;
-    if (inImage && tileZmin <= tileZmax) { // else: no allocated block can be read by this tile's rays, every sample is invalid
-        Lookup lk{ tab, complete, hd, hp };
-        march_ray<GRADIENTS, (CAP > (uint32_t)VH_TILE_LIST_CAPACITY) || VH_PIPELINE_SMALL>(lk, hd, hp, cp, rp, x, y, tileZmin, tileZmax, half, 0.5f * (tileZmin + tileZmax), out, cost VH_STAT_ARGS);
+    if (const uint32_t x = tileX + (lane & 7), y = tileY + (lane >> 3); x < W && y < H && tileZmin <= tileZmax) { // else: no allocated block can be read by this tile's rays, every sample is invalid
+        // (complete is the same for the whole wave: one of the two marches runs)
+        constexpr bool kPipelined = (CAP > (uint32_t)VH_TILE_LIST_CAPACITY) || VH_PIPELINE_SMALL;
+        if (complete) {
+            LookupComplete lk{ tab };
+            march_ray<GRADIENTS, kPipelined>(lk, hd, hp, cp, rp, x, y, tileZmin, tileZmax, half, 0.5f * (tileZmin + tileZmax), out, cost VH_STAT_ARGS);
+        } else {
+            Lookup lk{ tab, false, hd, hp };
+            march_ray<GRADIENTS, kPipelined>(lk, hd, hp, cp, rp, x, y, tileZmin, tileZmax, half, 0.5f * (tileZmin + tileZmax), out, cost VH_STAT_ARGS);
+        }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) cost = max(cost, (uint32_t)__shfl_xor((int)cost, off));
+    // The pixel is worked out again rather than kept: every vector register that lives across the march is one the
+    // march cannot use, and at this budget one it spills.  (lane_id_again: the same number from instructions of its own.)
+    const uint32_t laneAfter = lane_id_again();
+    const uint32_t x = tileX + (laneAfter & 7), y = tileY + (laneAfter >> 3);
+    const bool inImage = x < W && y < H;
+    const size_t pix = (size_t)y * W + x;
     if (half != 0u) {
         // the far half leaves its result in its (spent) table, the near half takes it where it found nothing itself
         int* mine = tab;
-        int* other = tileTab[(threadIdx.x / kWave) ^ 1u];
+        int* other = tileTab[waveInGroup ^ 1u];
         if (half == 2u) {
-            mine[lane * 8u + 0u] = out.hit ? 1 : 0;
-            mine[lane * 8u + 1u] = __float_as_int(out.alpha);
-            mine[lane * 8u + 2u] = (int)out.color;
-            if (GRADIENTS) { mine[lane * 8u + 3u] = __float_as_int(out.normal.x); mine[lane * 8u + 4u] = __float_as_int(out.normal.y); mine[lane * 8u + 5u] = __float_as_int(out.normal.z); }
-            if (lane == 0) mine[64u * 8u] = (int)cost;
+            mine[laneAfter * 8u + 0u] = out.hit ? 1 : 0;
+            mine[laneAfter * 8u + 1u] = __float_as_int(out.alpha);
+            mine[laneAfter * 8u + 2u] = (int)out.color;
+            if (GRADIENTS) { mine[laneAfter * 8u + 3u] = __float_as_int(out.normal.x); mine[laneAfter * 8u + 4u] = __float_as_int(out.normal.y); mine[laneAfter * 8u + 5u] = __float_as_int(out.normal.z); }
+            if (laneAfter == 0) mine[64u * 8u] = (int)cost;
         }
         __syncthreads(); // all four waves of this workgroup are halves of split tiles (schedule_tiles)
         if (half == 2u) { VH_WAVE_STAMP(cost) return; }
-        if (!out.hit && other[lane * 8u + 0u] != 0) {
+        if (!out.hit && other[laneAfter * 8u + 0u] != 0) {
             out.hit = true;
-            out.alpha = __int_as_float(other[lane * 8u + 1u]);
-            out.color = (uint32_t)other[lane * 8u + 2u];
-            if (GRADIENTS) out.normal = mk3(__int_as_float(other[lane * 8u + 3u]), __int_as_float(other[lane * 8u + 4u]), __int_as_float(other[lane * 8u + 5u]));
+            out.alpha = __int_as_float(other[laneAfter * 8u + 1u]);
+            out.color = (uint32_t)other[laneAfter * 8u + 2u];
+            if (GRADIENTS) out.normal = mk3(__int_as_float(other[laneAfter * 8u + 3u]), __int_as_float(other[laneAfter * 8u + 4u]), __int_as_float(other[laneAfter * 8u + 5u]));
         }
         cost += (uint32_t)other[64u * 8u];
-        if (lane == 0) heads[tile] = make_uint4(0x7f800000u, 0u, 0u, 0u);
+        if (laneAfter == 0) heads[tile] = make_uint4(0x7f800000u, 0u, 0u, 0u);
     }
     if (inImage) {
         store_ray(rd, cp, pix, x, y, out, GRADIENTS);
         VH_STAT_STORE
     }
     VH_WAVE_STAMP(cost)
-    if (sched && lane == 0) sched[4 + tile] = min(cost / kCostClassWidth, kCostClasses - 1u); // plain store: nobody waits for it
+    if (sched && laneAfter == 0) sched[4 + tile] = min(cost / kCostClassWidth, kCostClasses - 1u); // plain store: nobody waits for it
 }
 #undef VH_WAVE_STAMP
 #undef VH_STAT_DECL
@@ -2681,25 +2764,25 @@ VHD bool co_alloc(const CoAlloc& job)
 #ifndef VH_RENDER_WAVES
 #define VH_RENDER_WAVES 6
 #endif
-template <bool GRADIENTS>
+template <bool GRADIENTS, bool OFFSETS32>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VH_RENDER_WAVES, VH_RENDER_WAVES)))
 void k_render(VhHashData hd, VhHashParams hp, VhRayCastData rd, VhDepthCameraParams cp, VhRayCastParams rp,
               uint4* heads, const int4* lists, uint32_t cap, uint32_t* sched, uint32_t phase, CoAlloc job)
 {
     __shared__ int tileTab[256 / kWave][2u * VH_TILE_LIST_CAPACITY * kTileSlotWords];
     if (co_alloc(job)) return;
-    render_tile<GRADIENTS, VH_TILE_LIST_CAPACITY>(hd, hp, rd, cp, rp, heads, lists, cap, sched, phase, tileTab);
+    render_tile<GRADIENTS, VH_TILE_LIST_CAPACITY, OFFSETS32>(hd, hp, rd, cp, rp, heads, lists, cap, sched, phase, tileTab);
 }
 
 // large tables (48 KB of LDS per workgroup: three workgroups per compute unit)
-template <bool GRADIENTS>
+template <bool GRADIENTS, bool OFFSETS32>
 __global__ __launch_bounds__(256)
 void k_render_large(VhHashData hd, VhHashParams hp, VhRayCastData rd, VhDepthCameraParams cp, VhRayCastParams rp,
                     uint4* heads, const int4* lists, uint32_t cap, uint32_t* sched, uint32_t phase, CoAlloc job)
 {
     __shared__ int tileTab[256 / kWave][2u * VH_TILE_LIST_CAPACITY_LARGE * kTileSlotWords];
     if (co_alloc(job)) return;
-    render_tile<GRADIENTS, VH_TILE_LIST_CAPACITY_LARGE>(hd, hp, rd, cp, rp, heads, lists, cap, sched, phase, tileTab);
+    render_tile<GRADIENTS, VH_TILE_LIST_CAPACITY_LARGE, OFFSETS32>(hd, hp, rd, cp, rp, heads, lists, cap, sched, phase, tileTab);
 }
 
 // Riders of computeNormals' launch.  They come FIRST in the grid (the schedule workgroup, the splat, the compactify
@@ -4151,6 +4234,12 @@ size_t vh_render_schedule_bytes(uint32_t width, uint32_t height)
 
 uint32_t vh_render_split_tiles(uint32_t width, uint32_t height) { return split_tiles(cdiv(width, 8) * cdiv(height, 8)); }
 
+static std::atomic<int> g_forceOffsets64{ 0 };
+
+uint32_t vh_render_offsets32(uint32_t numSDFBlocks) { return (!g_forceOffsets64.load(std::memory_order_relaxed) && offsets32_ok(numSDFBlocks)) ? 1u : 0u; }
+
+uint32_t vh_debug_render_force_offsets64(uint32_t on) { return (uint32_t)g_forceOffsets64.exchange(on ? 1 : 0, std::memory_order_relaxed); }
+
 int vh_render_intervals_co(const VhHashData* hd, const VhHashParams* hp, const VhRayCastData* rd, const VhDepthCameraParams* cp,
                            const VhRayCastParams* rp, uint32_t* d_tileHeads, const VhTileBlock* d_tileBlocks, uint32_t tileCapacity,
                            uint32_t* d_schedule, uint32_t phase, VhFrameJob* fj, vhStream_t stream)
@@ -4179,13 +4268,19 @@ int vh_render_intervals_co(const VhHashData* hd, const VhHashParams* hp, const V
     }
     const dim3 grid(groups);
     hipStream_t st = (hipStream_t)stream;
-    if (rp->m_useGradients) {
-        if (large) VH_LAUNCH_TIMED(k_render_large<true>, grid, 256, st, *hd, *hp, *rd, *cp, *rp, h, l, cap, d_schedule, phase, job);
-        else VH_LAUNCH_TIMED(k_render<true>, grid, 256, st, *hd, *hp, *rd, *cp, *rp, h, l, cap, d_schedule, phase, job);
-    } else {
-        if (large) VH_LAUNCH_TIMED(k_render_large<false>, grid, 256, st, *hd, *hp, *rd, *cp, *rp, h, l, cap, d_schedule, phase, job);
-        else VH_LAUNCH_TIMED(k_render<false>, grid, 256, st, *hd, *hp, *rd, *cp, *rp, h, l, cap, d_schedule, phase, job);
+    // 32-bit voxel offsets where the pool allows them (load_voxel)
+    const bool o32 = vh_render_offsets32(hp->m_numSDFBlocks) != 0;
+#define VH_RENDER_LAUNCH(G, O)                                                                                                                  \
+    {                                                                                                                                           \
+        auto* const kern = large ? &k_render_large<G, O> : &k_render<G, O>;                                                                     \
+        VH_LAUNCH_TIMED(kern, grid, 256, st, *hd, *hp, *rd, *cp, *rp, h, l, cap, d_schedule, phase, job);                                       \
     }
+    if (rp->m_useGradients) {
+        if (o32) VH_RENDER_LAUNCH(true, true) else VH_RENDER_LAUNCH(true, false)
+    } else {
+        if (o32) VH_RENDER_LAUNCH(false, true) else VH_RENDER_LAUNCH(false, false)
+    }
+#undef VH_RENDER_LAUNCH
     return vh_last_launch_error();
 }
 

@@ -59,6 +59,8 @@ PROTOTYPES = {
     "vh_render_intervals": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.RayCastData), P(T.DepthCameraParams), P(T.RayCastParams), _VP, _VP, C.c_uint32, _VP, C.c_uint32, _VP]),
     "vh_render_schedule_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
     "vh_render_split_tiles": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "vh_render_offsets32": (C.c_uint32, [C.c_uint32]),
+    "vh_debug_render_force_offsets64": (C.c_uint32, [C.c_uint32]),
     "vh_compute_normals": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _VP]),
     "vh_render_intervals_co": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.RayCastData), P(T.DepthCameraParams), P(T.RayCastParams), _VP, _VP, C.c_uint32, _VP, C.c_uint32, P(T.FrameJob), _VP]),
     "vh_compute_normals_co": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, P(T.FrameJob), _VP]),
