@@ -418,6 +418,10 @@ public:
     void reset();                         // .h:297
     // .h:306 -- uploads the bit mask only if it changed since the last call
     unsigned int* getBitMaskGPU();
+    // read-only, for tests: drains the pipeline, then copies out the host's copy of the bit mask and the device's as they
+    // stand -- before any upload of the host's copy -- and says whether the host's copy was marked dirty
+    // (DESIGN.md "Fragile by design": the two copies agree whenever the pipeline is drained)
+    void debugDownloadBitMasks(std::vector<unsigned int>& hostCopy, std::vector<unsigned int>& deviceCopy, bool& hostDirty);
     bool containsSDFBlocksChunk(const vh::vec3i& chunk) const;                               // .h:311
     bool isChunkInSphere(const vh::vec3i& chunk, const vh::vec3f& center, float radius) const; // .h:317
     bool containsSDFBlocksChunkInRadius(const vh::vec3i& chunk, int chunkRadius) const;      // .h:348

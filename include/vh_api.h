@@ -397,6 +397,12 @@ int vh_chunk_grid_stream_out_to_cpu_all(VhChunkGrid* g);
 int vh_chunk_grid_stream_in_to_gpu_all(VhChunkGrid* g, const float posCamera[3], float radius, int useParts, uint32_t* nStreamedBlocks);
 /* getBitMaskGPU() DSC/CUDASceneRepChunkGrid.h:306 (uploads only when the mask changed) */
 int vh_chunk_grid_get_bit_mask_gpu(VhChunkGrid* g, const uint32_t** d_bitMask);
+/* Read-only, for tests: both copies of the bit mask as they stand once the streaming pipeline is drained and before any
+ * upload of the host's copy.  hostCopy / deviceCopy: `words` words each (either may be NULL); *wordsOut: the mask's size
+ * in words ((bits + 31) / 32), and nothing is copied if `words` is smaller; *hostDirty: 1 if the host's copy was marked
+ * as changed since the last upload (getBitMaskGPU() would copy it to the device). */
+int vh_chunk_grid_debug_download_bit_masks(VhChunkGrid* g, uint32_t* hostCopy, uint32_t* deviceCopy, uint32_t words,
+                                           uint32_t* wordsOut, int32_t* hostDirty);
 /* reset() :297 */
 int vh_chunk_grid_reset(VhChunkGrid* g);
 /* debugCheckForDuplicates() DSC/CUDASceneRepChunkGrid.cpp:313: 0 if no block is present twice */

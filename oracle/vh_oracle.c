@@ -594,11 +594,23 @@ static inline uint32_t linearize_chunk_pos(const VhHashParams* hp, i3 c)
     return (uint32_t)(p.z * hp->m_streamingGridDimensions[0] * hp->m_streamingGridDimensions[1] +
                       p.y * hp->m_streamingGridDimensions[0] + p.x);
 }
+static inline int chunk_in_grid(const VhHashParams* hp, i3 c)
+{
+    for (int a = 0; a < 3; a++) {
+        int q = (a == 0 ? c.x : a == 1 ? c.y : c.z) - hp->m_streamingMinGridPos[a];
+        if (q < 0 || q >= hp->m_streamingGridDimensions[a]) return 0;
+    }
+    return 1;
+}
 static inline int block_streamed_out(const VhHashParams* hp, i3 blk, const uint32_t* bitMask)
 {
     if (!bitMask) return 0; /* streaming disabled: the host always passes an all-zero mask */
     f3 pw = block_to_world(hp, blk);
-    uint32_t index = linearize_chunk_pos(hp, world_to_chunks(hp, pw));
+    i3 c = world_to_chunks(hp, pw);
+    /* fenced: the reference reads the mask at whatever index a chunk outside the grid linearises
+     * to.  The host never sets a bit for such a chunk (isValidChunk), so the block is not streamed out. */
+    if (!chunk_in_grid(hp, c)) return 0;
+    uint32_t index = linearize_chunk_pos(hp, c);
     return (bitMask[index / 32] & (0x1u << (index % 32))) != 0;
 }
 

@@ -268,6 +268,23 @@ int vh_chunk_grid_get_bit_mask_gpu(VhChunkGrid* g, const uint32_t** d_bitMask)
     if (!g || !d_bitMask) return VH_ERR_BAD_ARGUMENT;
     return guarded([&] { *d_bitMask = g->impl.getBitMaskGPU(); });
 }
+int vh_chunk_grid_debug_download_bit_masks(VhChunkGrid* g, uint32_t* hostCopy, uint32_t* deviceCopy, uint32_t words, uint32_t* wordsOut, int32_t* hostDirty)
+{
+    if (!g || !wordsOut) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] {
+        std::vector<unsigned int> h, d;
+        bool dirty = false;
+        g->impl.debugDownloadBitMasks(h, d, dirty);
+        *wordsOut = (uint32_t)h.size();
+        if (hostDirty) *hostDirty = dirty ? 1 : 0;
+        if (words < h.size()) {
+            if (hostCopy || deviceCopy) throw vh::Error(VH_ERR_STAGING_OVERFLOW, "download buffer too small");
+            return;
+        }
+        if (hostCopy) std::memcpy(hostCopy, h.data(), sizeof(uint32_t) * h.size());
+        if (deviceCopy) std::memcpy(deviceCopy, d.data(), sizeof(uint32_t) * d.size());
+    });
+}
 int vh_chunk_grid_reset(VhChunkGrid* g)
 {
     if (!g) return VH_ERR_BAD_ARGUMENT;

@@ -334,6 +334,19 @@ unsigned int* CUDASceneRepChunkGrid::getBitMaskGPU()
     return d_bitMask.get();
 }
 
+void CUDASceneRepChunkGrid::debugDownloadBitMasks(std::vector<unsigned int>& hostCopy, std::vector<unsigned int>& deviceCopy, bool& hostDirty)
+{
+    pipelineDrain();
+    std::lock_guard<std::mutex> l(m_gridMutex);
+    hostCopy = m_bitMask;
+    hostDirty = m_bitMaskDirty;
+    deviceCopy.assign(m_bitMask.size(), 0u);
+    // behind whatever the scene's stream still has to do to the device's copy (stream-out passes set bits, inserts clear them)
+    hipStream_t s = (hipStream_t)m_sceneRepHashSDF->getStream();
+    checkHip(hipMemcpyAsync(deviceCopy.data(), d_bitMask.get(), sizeof(unsigned int) * deviceCopy.size(), hipMemcpyDeviceToHost, s), "debugDownloadBitMasks");
+    checkHip(hipStreamSynchronize(s), "debugDownloadBitMasks");
+}
+
 void CUDASceneRepChunkGrid::getStatistics(unsigned int out[3]) const
 {
     const_cast<CUDASceneRepChunkGrid*>(this)->pipelineDrain();

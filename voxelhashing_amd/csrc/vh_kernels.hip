@@ -65,16 +65,29 @@ __global__ __launch_bounds__(256) void k_fill_i32(int32_t* p, int32_t v, uint32_
 // the table per distinct id, so the table sees ~1/64 of the reference's probes.
 // ---------------------------------------------------------------------------
 
-// worldToChunks :133-146, linearizeChunkPos :124-130, isSDFBlockStreamedOut :149-156
+// The chunk of a block (worldToChunks of the block's world position, DSC/CUDASceneRepHashSDF.cu:133-146 and
+// DSC/CUDASceneRepChunkGrid.cpp:126-153) and the index of its bit in the bit mask (linearizeChunkPos :124-130,
+// .h:570-598), or 0xffffffff for a chunk outside the grid.  The one place that forms either: alloc's test below and the
+// stream-out pass that keeps the device's copy of the mask both go through it, as the host's isValidChunk does.
+VHD uint32_t chunk_bit_of_block(const VhHashParams& hp, I3 blk)
+{
+    const F3 pw = block_to_world(hp.m_virtualVoxelSize, blk);
+    const F3 p = mk3(pw.x / hp.m_streamingVoxelExtents[0], pw.y / hp.m_streamingVoxelExtents[1], pw.z / hp.m_streamingVoxelExtents[2]);
+    const I3 c = mki3(f2i(p.x + (float)signi(p.x) * 0.5f), f2i(p.y + (float)signi(p.y) * 0.5f), f2i(p.z + (float)signi(p.z) * 0.5f));
+    const int qx = c.x - hp.m_streamingMinGridPos[0], qy = c.y - hp.m_streamingMinGridPos[1], qz = c.z - hp.m_streamingMinGridPos[2];
+    if (qx < 0 || qy < 0 || qz < 0 || qx >= hp.m_streamingGridDimensions[0] || qy >= hp.m_streamingGridDimensions[1] || qz >= hp.m_streamingGridDimensions[2])
+        return 0xffffffffu;
+    return (uint32_t)(qz * hp.m_streamingGridDimensions[0] * hp.m_streamingGridDimensions[1] + qy * hp.m_streamingGridDimensions[0] + qx);
+}
+
+// isSDFBlockStreamedOut :149-156, fenced: the reference linearises the chunk without a bounds test
+// and reads whatever word the index names -- another chunk's bit, or memory outside the mask.  The host can never set a
+// bit for a chunk outside the grid (isValidChunk), so such a block is not streamed out, and nothing is read for it.
 VHD bool block_streamed_out(const VhHashParams& hp, I3 blk, const uint32_t* bitMask)
 {
     if (!bitMask) return false;
-    F3 pw = block_to_world(hp.m_virtualVoxelSize, blk);
-    F3 p = mk3(pw.x / hp.m_streamingVoxelExtents[0], pw.y / hp.m_streamingVoxelExtents[1], pw.z / hp.m_streamingVoxelExtents[2]);
-    I3 c = mki3(f2i(p.x + (float)signi(p.x) * 0.5f), f2i(p.y + (float)signi(p.y) * 0.5f), f2i(p.z + (float)signi(p.z) * 0.5f));
-    I3 q = mki3(c.x - hp.m_streamingMinGridPos[0], c.y - hp.m_streamingMinGridPos[1], c.z - hp.m_streamingMinGridPos[2]);
-    uint32_t index = (uint32_t)(q.z * hp.m_streamingGridDimensions[0] * hp.m_streamingGridDimensions[1] +
-                                q.y * hp.m_streamingGridDimensions[0] + q.x);
+    const uint32_t index = chunk_bit_of_block(hp, blk);
+    if (index == 0xffffffffu) return false;
     return (bitMask[index >> 5] & (1u << (index & 31))) != 0u;
 }
 
@@ -3660,20 +3673,6 @@ __global__ __launch_bounds__(64) void k_stream_out_pass1(VhHashData hd, VhHashPa
             }
         }
     }
-}
-
-// The chunk of a block, as the host's integrateInChunkGrid works it out (worldToChunks of the block's world position,
-// linearizeChunkPos; DSC/CUDASceneRepChunkGrid.cpp:126-153, .h:570-598): the index of its bit in the bit mask, or
-// 0xffffffff for a chunk outside the grid (the host drops such a block: "Chunk out of bounds")
-VHD uint32_t chunk_bit_of_block(const VhHashParams& hp, I3 blk)
-{
-    const F3 pw = block_to_world(hp.m_virtualVoxelSize, blk);
-    const F3 p = mk3(pw.x / hp.m_streamingVoxelExtents[0], pw.y / hp.m_streamingVoxelExtents[1], pw.z / hp.m_streamingVoxelExtents[2]);
-    const I3 c = mki3(f2i(p.x + (float)signi(p.x) * 0.5f), f2i(p.y + (float)signi(p.y) * 0.5f), f2i(p.z + (float)signi(p.z) * 0.5f));
-    const int qx = c.x - hp.m_streamingMinGridPos[0], qy = c.y - hp.m_streamingMinGridPos[1], qz = c.z - hp.m_streamingMinGridPos[2];
-    if (qx < 0 || qy < 0 || qz < 0 || qx >= hp.m_streamingGridDimensions[0] || qy >= hp.m_streamingGridDimensions[1] || qz >= hp.m_streamingGridDimensions[2])
-        return 0xffffffffu;
-    return (uint32_t)(qz * hp.m_streamingGridDimensions[0] * hp.m_streamingGridDimensions[1] + qy * hp.m_streamingGridDimensions[0] + qx);
 }
 
 // k_stream_out_pass1 that also keeps the DEVICE's copy of the bit mask: the bit of every block's chunk is set here, where

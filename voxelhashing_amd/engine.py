@@ -367,6 +367,16 @@ class CUDASceneRepChunkGrid:
         check(self.L.vh_chunk_grid_get_bit_mask_gpu(self.handle, C.byref(p)), "getBitMaskGPU")
         return p
 
+    def downloadBitMasks(self):
+        """-> (host copy, device copy, host copy marked dirty): both copies of the bit mask with the pipeline drained and
+        before any upload of the host's copy (read-only; for tests)"""
+        n, dirty = C.c_uint32(), C.c_int32()
+        check(self.L.vh_chunk_grid_debug_download_bit_masks(self.handle, None, None, 0, C.byref(n), C.byref(dirty)), "downloadBitMasks")
+        host, dev = np.zeros(n.value, dtype=np.uint32), np.zeros(n.value, dtype=np.uint32)
+        check(self.L.vh_chunk_grid_debug_download_bit_masks(self.handle, host.ctypes.data, dev.ctypes.data, n.value, C.byref(n), C.byref(dirty)),
+              "downloadBitMasks")
+        return host, dev, bool(dirty.value)
+
     def reset(self):
         check(self.L.vh_chunk_grid_reset(self.handle), "reset")
 

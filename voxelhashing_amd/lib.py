@@ -260,6 +260,7 @@ PROTOTYPES = {
     "vh_chunk_grid_stream_out_to_cpu_all": (C.c_int, [_VP]),
     "vh_chunk_grid_stream_in_to_gpu_all": (C.c_int, [_VP, _F16, C.c_float, C.c_int, P(C.c_uint32)]),
     "vh_chunk_grid_get_bit_mask_gpu": (C.c_int, [_VP, P(_VP)]),
+    "vh_chunk_grid_debug_download_bit_masks": (C.c_int, [_VP, _VP, _VP, C.c_uint32, P(C.c_uint32), P(C.c_int32)]),
     "vh_chunk_grid_reset": (C.c_int, [_VP]),
     "vh_chunk_grid_debug_check_for_duplicates": (C.c_int, [_VP]),
     "vh_chunk_grid_get_statistics": (C.c_int, [_VP, P(C.c_uint32)]),
