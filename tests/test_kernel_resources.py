@@ -117,3 +117,15 @@ def test_the_tool_reads_device_assembly():
     assert (r["vgprs"], r["sgprs"], r["lds_bytes"], r["scratch_bytes"], r["vgpr_spills"], r["sgpr_spills"]) == (7, 12, 512, 24, 3, 2)
     assert r["instruction_lines"] == 5
     assert "| `foo` | 7 | 12 | 512 | 24 | 5 | 5 |" in KR.table(rows)
+
+
+def test_the_tool_lists_instruction_sequences():
+    """what --against compares: the kernel's instructions alone, without the label of the loop and its comment"""
+    seqs = KR.instruction_sequences(ASM)
+    assert seqs == {"_Z3fooPf": ["s_load_dwordx2 s[0:1], s[4:5], 0x0", "v_mov_b32_e32 v0, 0", "s_waitcnt lgkmcnt(0)",
+                                 "global_store_dword v0, v0, s[0:1]", "s_endpgm"]}
+    branch = ASM.replace("\ts_endpgm", "\ts_cbranch_scc1 .LBB0_1\n\ts_endpgm")
+    renumbered = branch.replace(".LBB0_1", ".LBB7_12")
+    assert KR.instruction_sequences(branch) == KR.instruction_sequences(renumbered)
+    assert KR.against(seqs, KR.instruction_sequences(branch)) == [("_Z3fooPf", "differs (6 → 5 lines)")]
+    assert KR.against(seqs, {}) == [("_Z3fooPf", "only here")] and KR.against({}, seqs) == [("_Z3fooPf", "only there")]

@@ -5,12 +5,17 @@ Compiles the kernel files to device assembly with the library's flags and prints
 scratch bytes, spilled registers (vector + scalar) and the number of instruction lines of the kernel's body.  The numbers
 are the code object's own metadata (the amdhsa.kernels note); the instruction lines are counted, not classified.
 
-  python tools/kernel_resources.py                       # every kernel of vh_kernels.hip
+  python tools/kernel_resources.py                       # every kernel of every .hip file the library is built from
   python tools/kernel_resources.py --match k_render      # kernels whose demangled name contains the text
   python tools/kernel_resources.py --json out.json -DVH_RENDER_WAVES=5 vh_kernels.hip vh_icp.hip
+  python tools/kernel_resources.py --against ../parent/voxelhashing_amd/csrc    # what a refactor did to each kernel
 
-`resources(asm_text)` and `library_resources(lib)` are importable: the latter reads the same metadata out of a built
-library (tests/test_kernel_resources.py).
+--against DIR compiles the same-named sources of another checkout's csrc as well (or all its .hip files when no sources
+are given: kernels may have moved between files) and says per kernel whether its instruction sequence -- comments,
+directives, labels and the numbers of local labels aside -- is identical, differs, or exists on one side only.
+
+`resources(asm_text)`, `instruction_sequences(asm_text)` and `library_resources(lib)` are importable: the last reads the
+same metadata out of a built library (tests/test_kernel_resources.py).
 """
 import argparse
 import json
@@ -82,6 +87,41 @@ def instruction_lines(text, name):
             continue
         n += 1
     return n
+
+
+def instruction_sequences(asm_text):
+    """{mangled kernel name: [instruction lines]} of every kernel, weak (template) ones included: the lines between the
+    kernel's label and the end of its body, without comments, directives and labels, local label numbers blanked"""
+    names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", asm_text, re.M)
+    end = re.compile(r"^\s*(\.Lfunc_end\d+:|\.section\b|\.amdhsa_kernel\b)")
+    out = {}
+    for name in names:
+        m = re.search(r"^" + re.escape(name) + r":\s*(;.*)?$", asm_text, re.M)
+        lines = []
+        for line in asm_text[m.end():].split("\n") if m else []:
+            if end.match(line):
+                break
+            s = line.split(";")[0].strip()
+            if not s or s[0] == "." or re.match(r"^\S+:$", s):
+                continue
+            lines.append(re.sub(r"\.L[A-Za-z_]*\d+(_\d+)?", ".L", " ".join(s.split())))
+        out[name] = lines
+    return out
+
+
+def against(here, there):
+    """[(mangled name, verdict)] for two {name: [instruction lines]}"""
+    rows = []
+    for name in sorted(set(here) | set(there)):
+        if name not in there:
+            rows.append((name, "only here"))
+        elif name not in here:
+            rows.append((name, "only there"))
+        elif here[name] == there[name]:
+            rows.append((name, "identical"))
+        else:
+            rows.append((name, "differs (%d → %d lines)" % (len(there[name]), len(here[name]))))
+    return rows
 
 
 def resources(asm_text):
@@ -226,18 +266,36 @@ def table(rows):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("sources", nargs="*", default=[], help="files under voxelhashing_amd/csrc (default: vh_kernels.hip)")
+    ap.add_argument("sources", nargs="*", default=[], help="files under voxelhashing_amd/csrc (default: every .hip file of build.SOURCES)")
     ap.add_argument("--match", default="", help="only kernels whose demangled name contains this text")
     ap.add_argument("--json", default="", help="also write the rows to this file")
     ap.add_argument("--library", default="", help="read a built library's metadata instead of compiling")
+    ap.add_argument("--against", default="", metavar="DIR", help="another checkout's csrc: compare every kernel's instruction sequence with it")
     args, extra = ap.parse_known_args()
     rows = []
     if args.library:
         rows = library_resources(args.library)
     else:
+        from voxelhashing_amd import build as vh_build
         csrc = os.path.join(ROOT, "voxelhashing_amd", "csrc")
-        for s in args.sources or ["vh_kernels.hip"]:
-            rows += resources(device_assembly(s if os.path.isabs(s) else os.path.join(csrc, s), extra))
+        sources = args.sources or [s for s in vh_build.SOURCES if s.endswith(".hip")]
+        texts = [device_assembly(s if os.path.isabs(s) else os.path.join(csrc, s), extra) for s in sources]
+        if args.against:
+            theirs = args.sources or sorted(f for f in os.listdir(args.against) if f.endswith(".hip"))
+            here, there = {}, {}
+            for t in texts:
+                here.update(instruction_sequences(t))
+            for s in theirs:
+                there.update(instruction_sequences(device_assembly(os.path.join(args.against, os.path.basename(s)), extra)))
+            verdicts = against(here, there)
+            names = demangle([n for n, _ in verdicts])
+            for n, v in verdicts:
+                if args.match in names[n]:
+                    print("%-28s %s" % (v, names[n].split("(")[0]))
+            print("%d kernels: %d identical" % (len(verdicts), sum(v == "identical" for _, v in verdicts)))
+            return
+        for t in texts:
+            rows += resources(t)
     rows = [r for r in rows if args.match in r["kernel"]]
     print(table(rows))
     if args.json:

@@ -142,6 +142,17 @@ VHD int world_to_vvp1_rb(float pos, float voxelSize, float rVoxelSize)
 struct HashMod {
     uint32_t d, m, sh;
 };
+// multiply-shift constants of umod_fast for divisor d >= 2
+inline HashMod make_hash_mod(uint32_t d)
+{
+    HashMod k;
+    k.d = d;
+    uint32_t l = 0;
+    while ((1ull << l) < (uint64_t)d) l++;
+    k.m = (uint32_t)((((1ull << 32) * ((1ull << l) - (uint64_t)d)) / d) + 1ull);
+    k.sh = l - 1;
+    return k;
+}
 VHD uint32_t umod_fast(uint32_t n, HashMod k)
 {
     const uint32_t q0 = __umulhi(k.m, n);
@@ -197,6 +208,33 @@ VHD bool block_in_frustum(const VhHashParams& hp, const VhDepthCameraParams& cp,
     float off = hp.m_virtualVoxelSize * 0.5f * ((float)VH_SDF_BLOCK_SIZE - 1.0f);
     pw.x += off; pw.y += off; pw.z += off;
     return in_frustum_approx(cp, hp.m_rigidTransformInverse, pw);
+}
+
+// The chunk of a block (worldToChunks of the block's world position, DSC/CUDASceneRepHashSDF.cu:133-146 and
+// DSC/CUDASceneRepChunkGrid.cpp:126-153) and the index of its bit in the bit mask (linearizeChunkPos :124-130,
+// .h:570-598), or 0xffffffff for a chunk outside the grid.  The one place that forms either: alloc's test
+// (vh_kernels.hip) and the stream-out pass that keeps the device's copy of the mask (vh_streaming.hip) both go through it,
+// as the host's isValidChunk does.
+VHD uint32_t chunk_bit_of_block(const VhHashParams& hp, I3 blk)
+{
+    const F3 pw = block_to_world(hp.m_virtualVoxelSize, blk);
+    const F3 p = mk3(pw.x / hp.m_streamingVoxelExtents[0], pw.y / hp.m_streamingVoxelExtents[1], pw.z / hp.m_streamingVoxelExtents[2]);
+    const I3 c = mki3(f2i(p.x + (float)signi(p.x) * 0.5f), f2i(p.y + (float)signi(p.y) * 0.5f), f2i(p.z + (float)signi(p.z) * 0.5f));
+    const int qx = c.x - hp.m_streamingMinGridPos[0], qy = c.y - hp.m_streamingMinGridPos[1], qz = c.z - hp.m_streamingMinGridPos[2];
+    if (qx < 0 || qy < 0 || qz < 0 || qx >= hp.m_streamingGridDimensions[0] || qy >= hp.m_streamingGridDimensions[1] || qz >= hp.m_streamingGridDimensions[2])
+        return 0xffffffffu;
+    return (uint32_t)(qz * hp.m_streamingGridDimensions[0] * hp.m_streamingGridDimensions[1] + qy * hp.m_streamingGridDimensions[0] + qx);
+}
+
+// isSDFBlockStreamedOut :149-156, fenced: the reference linearises the chunk without a bounds test
+// and reads whatever word the index names -- another chunk's bit, or memory outside the mask.  The host can never set a
+// bit for a chunk outside the grid (isValidChunk), so such a block is not streamed out, and nothing is read for it.
+VHD bool block_streamed_out(const VhHashParams& hp, I3 blk, const uint32_t* bitMask)
+{
+    if (!bitMask) return false;
+    const uint32_t index = chunk_bit_of_block(hp, blk);
+    if (index == 0xffffffffu) return false;
+    return (bitMask[index >> 5] & (1u << (index & 31))) != 0u;
 }
 
 // ---------------------------------------------------------------------------
@@ -604,6 +642,7 @@ VHD Vox combine_voxel(const VhHashParams& hp, Vox v0, Vox v1)
 
 constexpr int kWave = 64;
 VHD uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
+VHD uint64_t lanemask_lt() { return (1ull << lane_id()) - 1ull; }
 
 // workgroups of b that cover a (host side: the launchers' grid sizes)
 inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }

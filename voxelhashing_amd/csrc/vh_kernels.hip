@@ -1,13 +1,15 @@
-// vh_kernels.hip -- hand-written gfx950 kernels of the voxel-hash TSDF frame
-// loop and their launcher-level C ABI (include/vh_api.h).
+// vh_kernels.hip -- the frame loop's kernels: reset, alloc, compactify, integrate, garbage collection, the interval
+// splat, the ray caster, the queries and normals, with their launcher-level C ABI (include/vh_api.h).  They are one
+// translation unit because they ride on one another: k_render carries alloc, and k_compute_normals carries compactify,
+// the splat and integrate, so those device functions must be visible together.  The checks of integrate's arithmetic
+// (k_check_refined_division, k_check_weighted_colour) stay with the functions they check, and k_debug_hash_ops with the
+// kernels whose hash operations it runs one by one.  What shares only vh_device.hpp with the frame loop has a unit of
+// its own: vh_image.hip, vh_streaming.hip, vh_mc.hip, vh_util.hip.
 //
-// Reference behaviour: DSC/CUDASceneRepHashSDF.cu, DSC/CUDARayCastSDF.cu,
-// DSC/RayCastSDFUtil.h, DSC/CameraUtil.cu:669-711, DSC/CUDASceneRepChunkGrid.cu
-// (DSC/ = /root/reference/DepthSensingCUDA/Source/).  Nothing here is derived
-// from those kernels' structure: launch shapes, data movement and intra-wave
-// cooperation are designed for CDNA4 (wave64, 16-byte lanes, no textures, no
+// Reference behaviour: DSC/CUDASceneRepHashSDF.cu, DSC/CUDARayCastSDF.cu, DSC/RayCastSDFUtil.h, DSC/CameraUtil.cu:669-711
+// (DSC/ = DepthSensingCUDA/Source/ of the reference).  Nothing here is derived from those kernels' structure: launch
+// shapes, data movement and intra-wave cooperation are designed for CDNA4 (wave64, 16-byte lanes, no textures, no
 // __constant__ singletons, no host round trips).
-//
 // MUST be compiled with -ffp-contract=off (see vh_device.hpp).
 #include <hip/hip_runtime.h>
 
@@ -23,8 +25,6 @@
 using namespace vhd;
 
 namespace {
-
-VHD uint64_t lanemask_lt() { return (1ull << lane_id()) - 1ull; }
 
 // ---------------------------------------------------------------------------
 // reset (resetHeapKernel / resetHashKernel / resetHashBucketMutexKernel,
@@ -64,32 +64,6 @@ __global__ __launch_bounds__(256) void k_fill_i32(int32_t* p, int32_t v, uint32_
 // lanes ask for (neighbouring rays hit the same 8^3 block) and ONE lane probes
 // the table per distinct id, so the table sees ~1/64 of the reference's probes.
 // ---------------------------------------------------------------------------
-
-// The chunk of a block (worldToChunks of the block's world position, DSC/CUDASceneRepHashSDF.cu:133-146 and
-// DSC/CUDASceneRepChunkGrid.cpp:126-153) and the index of its bit in the bit mask (linearizeChunkPos :124-130,
-// .h:570-598), or 0xffffffff for a chunk outside the grid.  The one place that forms either: alloc's test below and the
-// stream-out pass that keeps the device's copy of the mask both go through it, as the host's isValidChunk does.
-VHD uint32_t chunk_bit_of_block(const VhHashParams& hp, I3 blk)
-{
-    const F3 pw = block_to_world(hp.m_virtualVoxelSize, blk);
-    const F3 p = mk3(pw.x / hp.m_streamingVoxelExtents[0], pw.y / hp.m_streamingVoxelExtents[1], pw.z / hp.m_streamingVoxelExtents[2]);
-    const I3 c = mki3(f2i(p.x + (float)signi(p.x) * 0.5f), f2i(p.y + (float)signi(p.y) * 0.5f), f2i(p.z + (float)signi(p.z) * 0.5f));
-    const int qx = c.x - hp.m_streamingMinGridPos[0], qy = c.y - hp.m_streamingMinGridPos[1], qz = c.z - hp.m_streamingMinGridPos[2];
-    if (qx < 0 || qy < 0 || qz < 0 || qx >= hp.m_streamingGridDimensions[0] || qy >= hp.m_streamingGridDimensions[1] || qz >= hp.m_streamingGridDimensions[2])
-        return 0xffffffffu;
-    return (uint32_t)(qz * hp.m_streamingGridDimensions[0] * hp.m_streamingGridDimensions[1] + qy * hp.m_streamingGridDimensions[0] + qx);
-}
-
-// isSDFBlockStreamedOut :149-156, fenced: the reference linearises the chunk without a bounds test
-// and reads whatever word the index names -- another chunk's bit, or memory outside the mask.  The host can never set a
-// bit for a chunk outside the grid (isValidChunk), so such a block is not streamed out, and nothing is read for it.
-VHD bool block_streamed_out(const VhHashParams& hp, I3 blk, const uint32_t* bitMask)
-{
-    if (!bitMask) return false;
-    const uint32_t index = chunk_bit_of_block(hp, blk);
-    if (index == 0xffffffffu) return false;
-    return (bitMask[index >> 5] & (1u << (index & 31))) != 0u;
-}
 
 // What integrateDepthMapKernel reads of a pixel (DSC/CUDASceneRepHashSDF.cu:436-470), formed once per pixel instead
 // of once per voxel that projects onto it: the depth, the colour as the bytes the kernel would make of it
@@ -237,7 +211,6 @@ constexpr uint32_t kIntegrateTile = 32;        // a block's screen footprint of 
 constexpr uint32_t kIntegrateTileRows = 29;    // rows 34 pixels apart (272 B: vertical neighbours fall into different banks):
 constexpr uint32_t kIntegrateTileStride = 34;  // 31.6 KB per workgroup = 25 allocation units of 1280 B, five workgroups per compute
                                                // unit (30 rows are 26 units: per-wave time stamps showed four resident, the fifth waiting)
-
 
 // What the fused integrate pass wants to know of a block before it touches a voxel, worked out once per block by the
 // compactify pass (one lane per block there; in the integrate pass it would be ~160 instructions of every wave) and
@@ -3034,880 +3007,8 @@ __global__ __launch_bounds__(256) void k_compute_normals(float4* out, const floa
 #undef VH_GROUP_STAMP
 
 // ---------------------------------------------------------------------------
-// marching cubes (DSC/CUDAMarchingCubesSDF.cu:65-143, DSC/MarchingCubesSDFUtil.h:154-311)
-//
-// Pass 1 lists the allocated hash entries (from the occupancy bits, not by reading all Ne entries); pass 2 runs one
-// 512-thread workgroup per listed block, one voxel per thread.  A voxel's eight corner samples are trilinear
-// interpolations whose 64 taps all lie in the block and a one-voxel shell around it, so the workgroup first stages
-// that 10x10x10 neighbourhood (27 block look-ups, 8 KB) in LDS and every tap is an LDS read.  Tap coordinates and
-// weights are computed with the reference's arithmetic (they decide bits of the output); a tap outside the staged
-// shell -- it cannot happen for finite coordinates, but nothing here relies on that -- takes the global path.
-// Triangles are appended with one atomic per wave; their order in the buffer differs from the reference's (and is
-// not deterministic there either).
+// the hash operations one by one, and checks of integrate's arithmetic
 // ---------------------------------------------------------------------------
-
-namespace mc_tables {
-#define VH_MC_QUAL __device__ const
-#include "../../include/vh_mc_tables.h"
-#undef VH_MC_QUAL
-} // namespace mc_tables
-
-// getHashEntryForSDFBlockPos :424-468 with the ten slots of the bucket in flight together (lookup_ptr walks them one
-// trip at a time, which is what a block that is NOT there costs whenever its bucket holds something else)
-VHD int lookup_ptr_wide(const VhHashData& hd, const VhHashParams& hp, I3 blk)
-{
-    const uint32_t ne = hp.m_hashNumBuckets * VH_HASH_BUCKET_SIZE;
-    const uint32_t h = hash_pos(hp.m_hashNumBuckets, blk);
-    if (!bucket_maybe_occupied(hd, h)) return VH_FREE_ENTRY;
-    const uint32_t base = h * VH_HASH_BUCKET_SIZE, idxLast = base + VH_HASH_BUCKET_SIZE - 1;
-    int4 qs[VH_HASH_BUCKET_SIZE];
-#pragma unroll
-    for (uint32_t j = 0; j < VH_HASH_BUCKET_SIZE; j++) qs[j] = load_quad(&hd.d_hash[base + j]);
-    uint32_t off = hd.d_hash[idxLast].offset;
-#pragma unroll
-    for (uint32_t j = 0; j < VH_HASH_BUCKET_SIZE; j++)
-        if (quad_matches(qs[j], blk)) return qs[j].w;
-    uint32_t maxIter = 0;
-#pragma unroll 1
-    while (maxIter < hp.m_hashMaxCollisionLinkedListSize) { // the list behind the last slot
-        if (off == 0) break;
-        const uint32_t i = (idxLast + off) % ne;
-        const int4 q = load_quad(&hd.d_hash[i]);
-        if (quad_matches(q, blk)) return q.w;
-        off = hd.d_hash[i].offset;
-        maxIter++;
-    }
-    return VH_FREE_ENTRY;
-}
-
-__global__ void k_mc_reset(VhMarchingCubesData d)
-{
-    if (threadIdx.x == 0 && blockIdx.x == 0) { d.d_numTriangles[0] = 0u; d.d_numOccupiedBlocks[0] = 0u; }
-}
-
-// extractIsoSurfacePass1Kernel :65-92 (its box test is commented out in the reference)
-__global__ __launch_bounds__(256) void k_mc_pass1(VhHashData hd, VhHashParams hp, VhMarchingCubesData d)
-{
-    const uint32_t nWords = (hp.m_hashNumBuckets + 31) / 32;
-    const uint32_t wordIdx = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t bits = (wordIdx < nWords) ? hd.d_bucketBits[wordIdx] : 0u;
-    while (__any(bits != 0u)) {
-        const bool has = bits != 0u;
-        const uint32_t bucket = wordIdx * 32u + (has ? (uint32_t)(__ffs((int)bits) - 1) : 0u);
-        bits &= bits - 1u;
-        int ptrs[VH_HASH_BUCKET_SIZE];
-#pragma unroll
-        for (uint32_t j = 0; j < VH_HASH_BUCKET_SIZE; j++) ptrs[j] = has ? hd.d_hash[(uint64_t)bucket * VH_HASH_BUCKET_SIZE + j].ptr : VH_FREE_ENTRY;
-#pragma unroll
-        for (uint32_t j = 0; j < VH_HASH_BUCKET_SIZE; j++) {
-            const bool keep = ptrs[j] != VH_FREE_ENTRY;
-            const uint64_t m = __ballot(keep);
-            if (m) {
-                const int leader = __ffsll((unsigned long long)m) - 1;
-                uint32_t base = 0;
-                if ((int)lane_id() == leader) base = atomicAdd(d.d_numOccupiedBlocks, (uint32_t)__popcll(m));
-                base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-                if (keep) d.d_occupiedBlocks[base + (uint32_t)__popcll(m & lanemask_lt())] = bucket * VH_HASH_BUCKET_SIZE + j;
-            }
-        }
-    }
-}
-
-constexpr int kMcTile = VH_SDF_BLOCK_SIZE + 2; // block plus a one-voxel shell
-
-struct McTile {
-    const uint2* vox; // LDS, kMcTile^3
-    I3 base;          // voxel coordinates of tile cell (0,0,0) = block base - 1
-    const VhHashData& hd;
-    const VhHashParams& hp;
-    // getVoxel(float3) :390-400: the zero voxel where there is no block
-    VHD Vox voxel_at(F3 worldPos) const
-    {
-        const I3 v = world_to_vvp(hp.m_virtualVoxelSize, worldPos);
-        const int tx = v.x - base.x, ty = v.y - base.y, tz = v.z - base.z;
-        if ((unsigned)tx < (unsigned)kMcTile && (unsigned)ty < (unsigned)kMcTile && (unsigned)tz < (unsigned)kMcTile)
-            return unpack_vox(vox[(tz * kMcTile + ty) * kMcTile + tx]);
-        const int ptr = lookup_ptr(hd, hp, vvp_to_block(v));
-        if (ptr == VH_FREE_ENTRY) return unpack_vox(make_uint2(0u, 0u));
-        const VhVoxel* g = &hd.d_SDFBlocks[(uint32_t)ptr + (uint32_t)(local1(v.z) * 64 + local1(v.y) * 8 + local1(v.x))];
-        return unpack_vox(*reinterpret_cast<const uint2*>(g));
-    }
-    // trilinearInterpolationSimpleFastFast, DSC/RayCastSDFUtil.h:97-116 (the colour it also forms is not used here)
-    VHD bool trilinear(F3 pos, float& dist) const
-    {
-        const float oSet = hp.m_virtualVoxelSize;
-        const F3 pd = mk3(pos.x - oSet / 2.0f, pos.y - oSet / 2.0f, pos.z - oSet / 2.0f);
-        const float fx = pos.x / oSet, fy = pos.y / oSet, fz = pos.z / oSet;
-        const float wx = fx - floorf(fx), wy = fy - floorf(fy), wz = fz - floorf(fz);
-        float d = 0.0f;
-#pragma unroll
-        for (uint32_t k = 0; k < 8u; k++) {
-            const uint32_t combo = (0x75634210u >> (4u * k)) & 7u; // reference tap order 000,100,010,001,110,011,101,111
-            const bool bx = combo & 1u, by = combo & 2u, bz = combo & 4u;
-            const Vox v = voxel_at(mk3(bx ? pd.x + oSet : pd.x + 0.0f, by ? pd.y + oSet : pd.y + 0.0f, bz ? pd.z + oSet : pd.z + 0.0f));
-            if (v.weight() == 0u) return false;
-            const float s = (bx ? wx : 1.0f - wx) * (by ? wy : 1.0f - wy) * (bz ? wz : 1.0f - wz);
-            d += s * v.sdf;
-        }
-        dist = d;
-        return true;
-    }
-};
-
-// vertexInterp, DSC/MarchingCubesSDFUtil.h:237-262, with c1 == c2 == the voxel's colour as at every call site
-VHD VhVertex mc_vertex(F3 p1, F3 p2, float d1, float d2, uint32_t cw)
-{
-    const float isolevel = 0.0f;
-    const float cr = (float)(cw & 0xffu), cg = (float)((cw >> 8) & 0xffu), cb = (float)((cw >> 16) & 0xffu);
-    VhVertex r;
-    const bool first = fabsf(isolevel - d1) < 0.00001f, second = fabsf(isolevel - d2) < 0.00001f, flat = fabsf(d1 - d2) < 0.00001f;
-    if (first || second || flat) {
-        const F3 p = first ? p1 : (second ? p2 : p1);
-        r.p[0] = p.x; r.p[1] = p.y; r.p[2] = p.z;
-        r.c[0] = cr / 255.f; r.c[1] = cg / 255.f; r.c[2] = cb / 255.f;
-        return r;
-    }
-    const float mu = (isolevel - d1) / (d2 - d1);
-    r.p[0] = p1.x + mu * (p2.x - p1.x);
-    r.p[1] = p1.y + mu * (p2.y - p1.y);
-    r.p[2] = p1.z + mu * (p2.z - p1.z);
-    r.c[0] = (cr + mu * 0.0f) / 255.f; // (float)(c2 - c1) is 0
-    r.c[1] = (cg + mu * 0.0f) / 255.f;
-    r.c[2] = (cb + mu * 0.0f) / 255.f;
-    return r;
-}
-
-// the snap code of a VhTriangleSource: which branch of mc_vertex the pair (d1, d2) takes
-VHD uint32_t mc_snap_code(float d1, float d2)
-{
-    const float isolevel = 0.0f;
-    const bool first = fabsf(isolevel - d1) < 0.00001f, second = fabsf(isolevel - d2) < 0.00001f, flat = fabsf(d1 - d2) < 0.00001f;
-    return first ? 1u : (second ? 2u : (flat ? 1u : 0u));
-}
-
-// extractIsoSurfacePass2Kernel :107-129 + extractIsoSurfaceAtPosition.  kSourced: also write, beside triangle `at`,
-// where it came from (sources[at], what the weld of vh_mesh.hip keys its vertices by); the plain instantiation never
-// reads `sources` and is the kernel it was before the parameter existed.
-template <bool kSourced>
-__global__ __launch_bounds__(512) void k_mc_pass2(VhHashData hd, VhHashParams hp, VhMarchingCubesData data, uint32_t numBlocks, VhTriangleSource* sources)
-{
-    __shared__ uint2 sVox[kMcTile * kMcTile * kMcTile];
-    __shared__ int sPtr[27];
-    const uint32_t t = threadIdx.x;
-    if (blockIdx.x >= numBlocks) return;
-    const uint32_t idx = data.d_occupiedBlocks[blockIdx.x];
-    const int4 q = load_quad(&hd.d_hash[idx]);
-    if (q.w == VH_FREE_ENTRY) return; // block-uniform
-    const I3 blk = mki3(q.x, q.y, q.z);
-    const I3 base = mki3(blk.x * VH_SDF_BLOCK_SIZE - 1, blk.y * VH_SDF_BLOCK_SIZE - 1, blk.z * VH_SDF_BLOCK_SIZE - 1);
-    if (t < 27u) {
-        const int dx = (int)(t % 3u) - 1, dy = (int)((t / 3u) % 3u) - 1, dz = (int)(t / 9u) - 1;
-        sPtr[t] = (dx == 0 && dy == 0 && dz == 0) ? q.w : lookup_ptr_wide(hd, hp, mki3(blk.x + dx, blk.y + dy, blk.z + dz));
-    }
-    __syncthreads();
-    for (uint32_t i = t; i < (uint32_t)(kMcTile * kMcTile * kMcTile); i += blockDim.x) {
-        const int tx = (int)(i % kMcTile), ty = (int)((i / kMcTile) % kMcTile), tz = (int)(i / (kMcTile * kMcTile));
-        // shell cells belong to the neighbour block on that side
-        const int nx = tx == 0 ? 0 : (tx == kMcTile - 1 ? 2 : 1), ny = ty == 0 ? 0 : (ty == kMcTile - 1 ? 2 : 1), nz = tz == 0 ? 0 : (tz == kMcTile - 1 ? 2 : 1);
-        const int ptr = sPtr[(nz * 3 + ny) * 3 + nx];
-        uint2 v = make_uint2(0u, 0u);
-        if (ptr != VH_FREE_ENTRY) {
-            const int lx = (tx + 7) & 7, ly = (ty + 7) & 7, lz = (tz + 7) & 7; // (t - 1) mod 8
-            v = *reinterpret_cast<const uint2*>(&hd.d_SDFBlocks[(uint32_t)ptr + (uint32_t)(lz * 64 + ly * 8 + lx)]);
-        }
-        sVox[i] = v;
-    }
-    __syncthreads();
-
-    const VhMarchingCubesParams mp = *data.d_params;
-    const McTile tile{ sVox, base, hd, hp };
-    // threadIdx of the reference's 8x8x8 block: x fastest
-    const I3 pi = mki3(base.x + 1 + (int)(t & 7u), base.y + 1 + (int)((t >> 3) & 7u), base.z + 1 + (int)(t >> 6));
-    const F3 worldPos = vvp_to_world(hp.m_virtualVoxelSize, pi);
-
-    uint32_t nTri = 0;
-    uint64_t triList = ~0ull;
-    float dist[8] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f }; // reference corner order 000,100,010,001,110,011,101,111
-    const float P = hp.m_virtualVoxelSize / 2.0f, M = -P;
-    bool ok = true;
-    if ((mp.m_boxEnabled & 0xffu) == 1u) { // isInBoxAA :264-271
-        if (worldPos.x < mp.m_minCorner[0] || worldPos.x > mp.m_maxCorner[0]) ok = false;
-        if (worldPos.y < mp.m_minCorner[1] || worldPos.y > mp.m_maxCorner[1]) ok = false;
-        if (worldPos.z < mp.m_minCorner[2] || worldPos.z > mp.m_maxCorner[2]) ok = false;
-    }
-    // The voxel itself is a tap of each of its eight corner samples (they lie half a voxel away, so their taps are
-    // the voxel and its neighbours) whenever the coordinates are far from the float -> int cliffs: an unobserved
-    // voxel (weight 0) then fails all eight, and most voxels of an allocated block are unobserved.
-    const bool tame = abs(pi.x) < (1 << 20) && abs(pi.y) < (1 << 20) && abs(pi.z) < (1 << 20);
-    if (ok && tame && (sVox[((int)(t >> 6) + 1) * kMcTile * kMcTile + ((int)((t >> 3) & 7u) + 1) * kMcTile + (int)(t & 7u) + 1].y >> 24) == 0u) ok = false;
-#pragma unroll 1
-    for (uint32_t k = 0; k < 8u; k++) {
-        if (!__any(ok)) break; // wave-uniform: nothing left to sample in this 8x8 slab of voxels
-        const uint32_t combo = (0x75634210u >> (4u * k)) & 7u;
-        float dk = 0.0f;
-        bool v = false;
-        if (ok) v = tile.trilinear(mk3(worldPos.x + ((combo & 1u) ? P : M), worldPos.y + ((combo & 2u) ? P : M), worldPos.z + ((combo & 4u) ? P : M)), dk);
-        ok = ok && v;
-        // dist[k] with a run-time k would put the array in scratch
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++) dist[j] = (j == k) ? dk : dist[j];
-    }
-    uint32_t cubeindex = 0;
-    if (ok) {
-        const float isolevel = 0.0f;
-        if (dist[2] < isolevel) cubeindex += 1;   // 010
-        if (dist[4] < isolevel) cubeindex += 2;   // 110
-        if (dist[1] < isolevel) cubeindex += 4;   // 100
-        if (dist[0] < isolevel) cubeindex += 8;   // 000
-        if (dist[5] < isolevel) cubeindex += 16;  // 011
-        if (dist[7] < isolevel) cubeindex += 32;  // 111
-        if (dist[6] < isolevel) cubeindex += 64;  // 101
-        if (dist[3] < isolevel) cubeindex += 128; // 001
-        const float thres = mp.m_threshMarchingCubes;
-        // the reference tests all 64 ordered pairs; the test is symmetric and a value passes against itself
-#pragma unroll
-        for (uint32_t k = 0; k < 8u; k++)
-#pragma unroll
-            for (uint32_t l = k + 1u; l < 8u; l++) {
-                if (dist[k] * dist[l] < 0.0f) { if (fabsf(dist[k]) + fabsf(dist[l]) > thres) ok = false; }
-                else { if (fabsf(dist[k] - dist[l]) > thres) ok = false; }
-            }
-#pragma unroll
-        for (uint32_t k = 0; k < 8u; k++) if (fabsf(dist[k]) > mp.m_threshMarchingCubes2) ok = false;
-        const uint32_t edges = mc_tables::VH_MC_EDGE[cubeindex];
-        if (edges == 0u || edges == 255u) ok = false;
-    }
-    if (ok) {
-        triList = mc_tables::VH_MC_TRI[cubeindex];
-        uint64_t l = triList;
-        while ((l & 0xFull) != 0xFull) { nTri++; l >>= 12; }
-    }
-
-    // one atomic per wave: exclusive scan of the lanes' triangle counts
-    const uint32_t lane = lane_id();
-    uint32_t incl = nTri;
-#pragma unroll
-    for (int off = 1; off < (int)kWave; off <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, off);
-        if ((int)lane >= off) incl += up;
-    }
-    const uint32_t waveTotal = (uint32_t)__shfl((int)incl, (int)kWave - 1);
-    if (waveTotal == 0u) return; // wave-uniform
-    uint32_t waveBase = 0u;
-    if (lane == kWave - 1u) waveBase = atomicAdd(data.d_numTriangles, waveTotal);
-    waveBase = (uint32_t)__shfl((int)waveBase, (int)kWave - 1);
-    uint32_t at = waveBase + incl - nTri;
-    if (nTri == 0u) return;
-
-    const Vox own = tile.voxel_at(worldPos);
-    // Bourke's edges in the reference's corner names (vertlist, :205-216): endpoints as x|y<<1|z<<2, three bits each
-    constexpr uint64_t kEdgeA = 0ull | (2ull << 0) | (3ull << 3) | (1ull << 6) | (0ull << 9) | (6ull << 12) | (7ull << 15) | (5ull << 18) | (4ull << 21) | (2ull << 24) | (3ull << 27) | (1ull << 30) | (0ull << 33);
-    constexpr uint64_t kEdgeB = 0ull | (3ull << 0) | (1ull << 3) | (0ull << 6) | (2ull << 9) | (7ull << 12) | (5ull << 15) | (4ull << 18) | (6ull << 21) | (6ull << 24) | (7ull << 27) | (5ull << 30) | (4ull << 33);
-    // corner bits x|y<<1|z<<2  ->  index in the reference's sample order 000,100,010,001,110,011,101,111
-    constexpr uint32_t kOrder = 0u | (1u << 4) | (2u << 8) | (4u << 12) | (3u << 16) | (6u << 20) | (5u << 24) | (7u << 28);
-    auto corner_dist = [&](uint32_t c) {
-        const uint32_t k = (kOrder >> (4u * c)) & 7u;
-        float r = dist[0];
-#pragma unroll
-        for (uint32_t j = 1; j < 8u; j++) r = (k == j) ? dist[j] : r;
-        return r;
-    };
-    auto corner_pos = [&](uint32_t c) {
-        return mk3(worldPos.x + ((c & 1u) ? P : M), worldPos.y + ((c & 2u) ? P : M), worldPos.z + ((c & 4u) ? P : M));
-    };
-    auto edge_vertex = [&](uint32_t e) {
-        const uint32_t a = (uint32_t)(kEdgeA >> (3u * e)) & 7u, b = (uint32_t)(kEdgeB >> (3u * e)) & 7u;
-        return mc_vertex(corner_pos(a), corner_pos(b), corner_dist(a), corner_dist(b), own.cw);
-    };
-#pragma unroll 1
-    for (uint64_t l = triList; (l & 0xFull) != 0xFull; l >>= 12, at++) {
-        if (at >= mp.m_maxNumTriangles) break; // appendTriangle :283-309 drops what does not fit; the host sees the full count
-        VhTriangle tri;
-        tri.v0 = edge_vertex((uint32_t)(l & 0xFull));
-        tri.v1 = edge_vertex((uint32_t)((l >> 4) & 0xFull));
-        tri.v2 = edge_vertex((uint32_t)((l >> 8) & 0xFull));
-        data.d_triangles[at] = tri;
-        if constexpr (kSourced) {
-            VhTriangleSource src;
-            src.cell[0] = pi.x; src.cell[1] = pi.y; src.cell[2] = pi.z;
-            src.edges = 0u;
-#pragma unroll
-            for (uint32_t k = 0; k < 3u; k++) {
-                const uint32_t e = (uint32_t)((l >> (4u * k)) & 0xFull);
-                const uint32_t a = (uint32_t)(kEdgeA >> (3u * e)) & 7u, b = (uint32_t)(kEdgeB >> (3u * e)) & 7u;
-                src.edges |= (e | (mc_snap_code(corner_dist(a), corner_dist(b)) << 4)) << (8u * k);
-            }
-            sources[at] = src;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// sensor pre-processing (DSC/CameraUtil.cu): the image kernels CUDARGBDAdapter::process and
-// CUDARGBDSensor::process run between the sensor and integrate().  One pixel per lane, rows contiguous across the
-// wave (the reference uses 16x16 tiles); all of them stream the image once.
-// ---------------------------------------------------------------------------
-
-// convertColorRawToFloatDevice :137-152 (RGBX bytes; black means "no colour")
-VHD float4 color_raw_to_float4(uint32_t c)
-{
-    const uint32_t r = c & 0xffu, g = (c >> 8) & 0xffu, b = (c >> 16) & 0xffu, w = c >> 24;
-    const float mi = minf();
-    return (r == 0u && g == 0u && b == 0u) ? make_float4(mi, mi, mi, mi)
-                                           : make_float4((float)r / 255.0f, (float)g / 255.0f, (float)b / 255.0f, (float)(w / 255u));
-}
-__global__ __launch_bounds__(256) void k_convert_color_raw_to_float4(float4* out, const uint32_t* in, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i] = color_raw_to_float4(in[i]);
-}
-
-// bilinearInterpolationFloat :1071-1098 (invalid taps drop out of the weights).  fetch(i) is source pixel i: a load, or a
-// load and a conversion (k_ingest_frame)
-template <class Fetch>
-VHD float bilinear_float_taps(float x, float y, Fetch fetch, uint32_t W, uint32_t H)
-{
-    const int px = (int)floorf(x), py = (int)floorf(y);
-    const float alpha = x - (float)px, beta = y - (float)py;
-    const float mi = minf();
-    float s0 = 0.0f, w0 = 0.0f, s1 = 0.0f, w1 = 0.0f;
-    if ((uint32_t)px < W && (uint32_t)py < H) { const float v = fetch((uint32_t)py * W + (uint32_t)px); if (v != mi) { s0 += (1.0f - alpha) * v; w0 += (1.0f - alpha); } }
-    if ((uint32_t)(px + 1) < W && (uint32_t)py < H) { const float v = fetch((uint32_t)py * W + (uint32_t)(px + 1)); if (v != mi) { s0 += alpha * v; w0 += alpha; } }
-    if ((uint32_t)px < W && (uint32_t)(py + 1) < H) { const float v = fetch((uint32_t)(py + 1) * W + (uint32_t)px); if (v != mi) { s1 += (1.0f - alpha) * v; w1 += (1.0f - alpha); } }
-    if ((uint32_t)(px + 1) < W && (uint32_t)(py + 1) < H) { const float v = fetch((uint32_t)(py + 1) * W + (uint32_t)(px + 1)); if (v != mi) { s1 += alpha * v; w1 += alpha; } }
-    const float p0 = s0 / w0, p1 = s1 / w1;
-    float ss = 0.0f, ww = 0.0f;
-    if (w0 > 0.0f) { ss += (1.0f - beta) * p0; ww += (1.0f - beta); }
-    if (w1 > 0.0f) { ss += beta * p1; ww += beta; }
-    return ww > 0.0f ? ss / ww : mi;
-}
-VHD float bilinear_float(float x, float y, const float* in, uint32_t W, uint32_t H)
-{
-    return bilinear_float_taps(x, y, [in](uint32_t i) { return in[i]; }, W, H);
-}
-
-// resampleFloatMapDevice :1100-1118 / resampleFloat4MapDevice :1168-1186 (pixels whose nearest source pixel lies
-// outside the source keep their old value, as in the reference)
-// the source coordinates of output pixel (x, y); false: the nearest source pixel lies outside the source
-VHD bool resample_coords(int x, int y, uint32_t inW, uint32_t inH, uint32_t outW, uint32_t outH, float& sx, float& sy)
-{
-    const float scaleWidth = (float)(inW - 1) / (float)(outW - 1), scaleHeight = (float)(inH - 1) / (float)(outH - 1);
-    const uint32_t xInput = (uint32_t)((float)x * scaleWidth + 0.5f), yInput = (uint32_t)((float)y * scaleHeight + 0.5f);
-    sx = (float)x * scaleWidth;
-    sy = (float)y * scaleHeight;
-    return xInput < inW && yInput < inH;
-}
-template <class T>
-__global__ __launch_bounds__(256) void k_resample(T* out, const T* in, uint32_t inW, uint32_t inH, uint32_t outW, uint32_t outH)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= outW * outH) return;
-    float sx, sy;
-    if (resample_coords((int)(i % outW), (int)(i / outW), inW, inH, outW, outH, sx, sy)) {
-        if constexpr (sizeof(T) == 4) out[i] = bilinear_float(sx, sy, in, inW, inH);
-        else out[i] = bilinear_float4(sx, sy, in, inW, inH);
-    }
-}
-
-// Not in the reference: a raw sensor frame -- 16-bit depth in units of 1/depthShift m, 8-bit RGB or RGBX colour, at the
-// sensor's sizes -- to integrate's input at adapter size in one pass: SensorDataReader::processDepth's conversion
-// (DSC/SensorDataReader.cpp:125-140: u16 / depthShift, a 0 sample stays 0.0f; RGB -> RGBX with X = 1),
-// convertColorRawToFloat4, resampleFloatMap and resampleFloat4Map (or the colour copy when the colour size is the
-// adapter's, DSC/CUDARGBDAdapter.cpp:107-131), with the conversions inside the tap fetch of the bilinear functions
-// above: the same operations in the same order, so the same bits.  For widths and heights from 2 up the nearest
-// source pixel is always inside the source (resample_coords), so every output pixel is written.
-// The output (20 B per adapter pixel) is most of the traffic; the taps come from L2.  A workgroup owns 1024 consecutive
-// output pixels: lane t writes depth pixels 4t..4t+3 as one 16-byte store and colour pixels t, t+256, t+512, t+768
-// (a float4 each), so every store instruction of a wave covers one contiguous kilobyte.
-constexpr uint32_t kIngestPixelsPerGroup = 1024;
-template <int CH, bool COPY_COLOR>
-__global__ __launch_bounds__(256) void k_ingest_frame(float* __restrict__ outDepth, float4* __restrict__ outColor, const uint16_t* __restrict__ depth,
-                                                      const uint8_t* __restrict__ color, uint32_t depthW, uint32_t depthH, uint32_t colorW, uint32_t colorH,
-                                                      uint32_t outW, uint32_t outH, float depthShift)
-{
-    const uint32_t n = outW * outH, base = blockIdx.x * kIngestPixelsPerGroup;
-    auto depthTap = [depth, depthShift](uint32_t i) { return (float)depth[i] / depthShift; };
-    auto depthAt = [&](uint32_t i) {
-        float sx, sy;
-        (void)resample_coords((int)(i % outW), (int)(i / outW), depthW, depthH, outW, outH, sx, sy);
-        return bilinear_float_taps(sx, sy, depthTap, depthW, depthH);
-    };
-    const uint32_t i0 = base + 4u * threadIdx.x;
-    if (i0 + 4u <= n) {
-        *reinterpret_cast<float4*>(outDepth + i0) = make_float4(depthAt(i0), depthAt(i0 + 1u), depthAt(i0 + 2u), depthAt(i0 + 3u));
-    } else {
-        for (uint32_t i = i0; i < n; i++) outDepth[i] = depthAt(i);
-    }
-    if constexpr (CH != 0) {
-        auto colorTap = [color](uint32_t i, uint32_t = 0u) {
-            if constexpr (CH == 4) return color_raw_to_float4(reinterpret_cast<const uint32_t*>(color)[i]);
-            else return color_raw_to_float4((uint32_t)color[3u * i] | ((uint32_t)color[3u * i + 1u] << 8) | ((uint32_t)color[3u * i + 2u] << 16) | (1u << 24));
-        };
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; k++) {
-            const uint32_t i = base + k * 256u + threadIdx.x;
-            if (i >= n) break;
-            if constexpr (COPY_COLOR) outColor[i] = colorTap(i);
-            else {
-                float sx, sy;
-                (void)resample_coords((int)(i % outW), (int)(i / outW), colorW, colorH, outW, outH, sx, sy);
-                outColor[i] = bilinear_float4_taps(sx, sy, colorTap, colorW, colorH);
-            }
-        }
-    }
-}
-
-// setInvalidFloatMapDevice :338-346
-__global__ __launch_bounds__(256) void k_set_invalid_float(float* out, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = minf();
-}
-
-// convertColorToIntensityFloatDevice :258-267
-__global__ __launch_bounds__(256) void k_color_to_intensity(float* out, const float4* in, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 c = in[i];
-    out[i] = 0.299f * c.x + 0.587f * c.y + 0.114f * c.z;
-}
-
-// convertDepthFloatToCameraSpaceFloat4Device :390-407
-__global__ __launch_bounds__(256) void k_depth_to_camera_space(float4* out, const float* in, VhDepthCameraParams cp, uint32_t W, uint32_t H)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W * H) return;
-    const float mi = minf();
-    const float depth = in[i];
-    float4 o = make_float4(mi, mi, mi, mi);
-    if (depth != mi) {
-        const F3 p = depth_to_skeleton(cp, i % W, i / W, depth);
-        o = make_float4(p.x, p.y, p.z, 1.0f);
-    }
-    out[i] = o;
-}
-
-// gaussD :436-439 (float exp), gaussR :426-429 (double arithmetic as written)
-VHD float gauss_d(float sigma, int x, int y) { return expf(-((float)(x * x + y * y) / (2.0f * sigma * sigma))); }
-/* gaussR (DSC/CameraUtil.cu:426-429) evaluates in double and returns float: the bilateral weight is a float product */
-VHD float gauss_r(float sigma, float dist) { return (float)exp(-(double)(dist * dist) / (2.0 * (double)sigma * (double)sigma)); }
-
-// gaussFilterFloatMapDevice :555-593
-__global__ __launch_bounds__(256) void k_gauss_filter_float(float* out, const float* in, float sigmaD, float sigmaR, uint32_t W, uint32_t H)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W * H) return;
-    const int x = (int)(i % W), y = (int)(i / W);
-    const int kernelRadius = (int)ceil(2.0 * (double)sigmaD);
-    const float mi = minf();
-    float sum = 0.0f, sumWeight = 0.0f;
-    const float center = in[i];
-    if (center != mi) {
-        for (int m = x - kernelRadius; m <= x + kernelRadius; m++)
-            for (int n = y - kernelRadius; n <= y + kernelRadius; n++)
-                if (m >= 0 && n >= 0 && m < (int)W && n < (int)H) {
-                    const float cur = in[(uint32_t)n * W + (uint32_t)m];
-                    if (cur != mi && fabsf(center - cur) < sigmaR) {
-                        const float weight = gauss_d(sigmaD, m - x, n - y);
-                        sumWeight += weight;
-                        sum += weight * cur;
-                    }
-                }
-    }
-    out[i] = sumWeight > 0.0f ? sum / sumWeight : mi;
-}
-
-// The same filter for radii up to kGaussMaxRadius with the neighbourhood and the weights in LDS: a workgroup owns a
-// 32x8 tile of pixels, stages the tile plus its halo once and computes the (2r+1)^2 weights once instead of once per
-// pixel (the expf is most of the per-pixel kernel's work).  Same taps in the same order, same weights: same sums.
-constexpr int kGaussMaxRadius = 8, kGaussTileW = 32, kGaussTileH = 8;
-
-__global__ __launch_bounds__(256) void k_gauss_filter_float_tiled(float* out, const float* in, float sigmaD, float sigmaR, int W, int H, int r)
-{
-    extern __shared__ float sGauss[];
-    const int tw = kGaussTileW + 2 * r, th = kGaussTileH + 2 * r, side = 2 * r + 1;
-    float* sTile = sGauss;              // tw x th, rows contiguous
-    float* sWeight = sGauss + tw * th;  // side x side, [dx + r][dy + r]
-    const int x0 = (int)blockIdx.x * kGaussTileW, y0 = (int)blockIdx.y * kGaussTileH;
-    const float mi = minf();
-    for (int i = (int)threadIdx.x; i < tw * th; i += 256) {
-        const int gx = x0 - r + i % tw, gy = y0 - r + i / tw;
-        sTile[i] = (gx >= 0 && gy >= 0 && gx < W && gy < H) ? in[(size_t)gy * W + gx] : mi; // outside the image: skipped like an invalid pixel
-    }
-    for (int i = (int)threadIdx.x; i < side * side; i += 256) sWeight[i] = gauss_d(sigmaD, i / side - r, i % side - r);
-    __syncthreads();
-    const int lx = (int)threadIdx.x % kGaussTileW, ly = (int)threadIdx.x / kGaussTileW;
-    const int x = x0 + lx, y = y0 + ly;
-    if (x >= W || y >= H) return;
-    float sum = 0.0f, sumWeight = 0.0f;
-    const float center = sTile[(ly + r) * tw + lx + r];
-    if (center != mi) {
-        for (int dx = -r; dx <= r; dx++)      // m = x + dx outer, n = y + dy inner: the reference's order of summation
-            for (int dy = -r; dy <= r; dy++) {
-                const float cur = sTile[(ly + r + dy) * tw + lx + r + dx];
-                // a tap outside the image holds MINF here; the reference skips it by its bounds test
-                if (cur != mi && fabsf(center - cur) < sigmaR) {
-                    const float weight = sWeight[(dx + r) * side + dy + r];
-                    sumWeight += weight;
-                    sum += weight * cur;
-                }
-            }
-    }
-    out[(size_t)y * W + x] = sumWeight > 0.0f ? sum / sumWeight : mi;
-}
-
-// gaussFilterFloat4MapDevice :611-651
-__global__ __launch_bounds__(256) void k_gauss_filter_float4(float4* out, const float4* in, float sigmaD, float sigmaR, uint32_t W, uint32_t H)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W * H) return;
-    const int x = (int)(i % W), y = (int)(i / W);
-    const int kernelRadius = (int)ceil(2.0 * (double)sigmaD);
-    const float mi = minf();
-    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-    float sumWeight = 0.0f;
-    const float4 center = in[i];
-    if (center.x != mi) {
-        for (int m = x - kernelRadius; m <= x + kernelRadius; m++)
-            for (int n = y - kernelRadius; n <= y + kernelRadius; n++)
-                if (m >= 0 && n >= 0 && m < (int)W && n < (int)H) {
-                    const float4 cur = in[(uint32_t)n * W + (uint32_t)m];
-                    if (cur.x != mi) {
-                        const float dx = center.x - cur.x, dy = center.y - cur.y, dz = center.z - cur.z, dw = center.w - cur.w;
-                        if (sqrtf(dx * dx + dy * dy + dz * dz + dw * dw) < sigmaR) { // length(float4), cutil_math.h
-                            const float weight = gauss_d(sigmaD, m - x, n - y);
-                            sumWeight += weight;
-                            sum = f4_add(sum, f4_scale(weight, cur));
-                        }
-                    }
-                }
-    }
-    out[i] = sumWeight > 0.0f ? f4_div(sum, sumWeight) : make_float4(mi, mi, mi, mi);
-}
-
-// bilateralFilterFloatMapDevice :446-483
-__global__ __launch_bounds__(256) void k_bilateral_filter_float(float* out, const float* in, float sigmaD, float sigmaR, uint32_t W, uint32_t H)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W * H) return;
-    const int x = (int)(i % W), y = (int)(i / W);
-    const int kernelRadius = (int)ceil(2.0 * (double)sigmaD);
-    const float mi = minf();
-    float sum = 0.0f, sumWeight = 0.0f;
-    const float center = in[i];
-    float o = mi;
-    if (center != mi) {
-        for (int m = x - kernelRadius; m <= x + kernelRadius; m++)
-            for (int n = y - kernelRadius; n <= y + kernelRadius; n++)
-                if (m >= 0 && n >= 0 && m < (int)W && n < (int)H) {
-                    const float cur = in[(uint32_t)n * W + (uint32_t)m];
-                    if (cur != mi) {
-                        const float weight = gauss_d(sigmaD, m - x, n - y) * gauss_r(sigmaR, cur - center);
-                        sumWeight += weight;
-                        sum += weight * cur;
-                    }
-                }
-        if (sumWeight > 0.0f) o = sum / sumWeight;
-    }
-    out[i] = o;
-}
-
-// erodeDepthMapDevice :1632-1670
-__global__ __launch_bounds__(256) void k_erode_depth(float* out, const float* in, int structureSize, int W, int H, float dThresh, float fracReq)
-{
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (uint32_t)(W * H)) return;
-    const int x = (int)(idx % (uint32_t)W), y = (int)(idx / (uint32_t)W);
-    const float mi = minf();
-    uint32_t count = 0;
-    const float oldDepth = in[idx];
-    for (int i = -structureSize; i <= structureSize; i++)
-        for (int j = -structureSize; j <= structureSize; j++)
-            if (x + j >= 0 && x + j < W && y + i >= 0 && y + i < H) {
-                const float depth = in[(y + i) * W + (x + j)];
-                if (depth == mi || depth == 0.0f || fabsf(depth - oldDepth) > dThresh) count++;
-            }
-    const uint32_t sum = (uint32_t)((2 * structureSize + 1) * (2 * structureSize + 1));
-    out[idx] = ((float)count / (float)sum >= fracReq) ? mi : oldDepth;
-}
-
-// ---------------------------------------------------------------------------
-// streaming (DSC/CUDASceneRepChunkGrid.cu)
-// ---------------------------------------------------------------------------
-
-// integrateFromGlobalHashPass1Kernel :27-74.  The double heap push of the
-// reference's list branch (:58-64) is not reproduced: the element delete is
-// the only push (DESIGN.md "Fenced reference defects").
-__global__ __launch_bounds__(64) void k_stream_out_pass1(VhHashData hd, VhHashParams hp, uint32_t start, float radius,
-                                                         float cx, float cy, float cz, uint32_t* outCounter,
-                                                         VhSDFBlockDesc* out, uint32_t capacity, int32_t lockToken)
-{
-    const uint32_t ne = hp.m_hashNumBuckets * VH_HASH_BUCKET_SIZE;
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x + start;
-    if (idx >= ne) return;
-    VhHashEntry* e = &hd.d_hash[idx];
-    const int4 q = load_quad(e);
-    const uint32_t off = e->offset;
-    const I3 pos = mki3(q.x, q.y, q.z);
-    const F3 pw = block_to_world(hp.m_virtualVoxelSize, pos);
-    const F3 df = mk3(pw.x - cx, pw.y - cy, pw.z - cz);
-    const float d = sqrtf(dot3(df, df));
-    if (q.w != VH_FREE_ENTRY && d >= radius) {
-        bool emit = false;
-        if (off != 0u || hash_pos(hp.m_hashNumBuckets, pos) != idx / VH_HASH_BUCKET_SIZE) {
-            emit = delete_hash_entry_element(hd, hp, pos, lockToken);
-        } else {
-            append_heap(hd, (uint32_t)q.w / VH_SDF_BLOCK_VOXELS);
-            delete_hash_entry(e);
-            bucket_dec(hd, idx);
-            emit = true;
-        }
-        if (emit) {
-            const uint32_t addr = atomicAdd(outCounter, 1u);
-            if (addr < capacity) {
-                VhSDFBlockDesc dsc;
-                dsc.pos[0] = q.x; dsc.pos[1] = q.y; dsc.pos[2] = q.z; dsc.ptr = q.w;
-                out[addr] = dsc;
-            }
-        }
-    }
-}
-
-// k_stream_out_pass1 that also keeps the DEVICE's copy of the bit mask: the bit of every block's chunk is set here, where
-// the block leaves, instead of by the host a round trip later (the host sets the same bit in its own copy when the block
-// arrives; the frame's alloc pass, which reads the mask, then need not wait for the host)
-__global__ __launch_bounds__(64) void k_stream_out_pass1_bits(VhHashData hd, VhHashParams hp, uint32_t start, float radius,
-                                                              float cx, float cy, float cz, uint32_t* outCounter,
-                                                              VhSDFBlockDesc* out, uint32_t capacity, int32_t lockToken, uint32_t* bitMask)
-{
-    const uint32_t ne = hp.m_hashNumBuckets * VH_HASH_BUCKET_SIZE;
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x + start;
-    if (idx >= ne) return;
-    VhHashEntry* e = &hd.d_hash[idx];
-    const int4 q = load_quad(e);
-    const uint32_t off = e->offset;
-    const I3 pos = mki3(q.x, q.y, q.z);
-    const F3 pw = block_to_world(hp.m_virtualVoxelSize, pos);
-    const F3 df = mk3(pw.x - cx, pw.y - cy, pw.z - cz);
-    const float d = sqrtf(dot3(df, df));
-    if (q.w != VH_FREE_ENTRY && d >= radius) {
-        bool emit = false;
-        if (off != 0u || hash_pos(hp.m_hashNumBuckets, pos) != idx / VH_HASH_BUCKET_SIZE) {
-            emit = delete_hash_entry_element(hd, hp, pos, lockToken);
-        } else {
-            append_heap(hd, (uint32_t)q.w / VH_SDF_BLOCK_VOXELS);
-            delete_hash_entry(e);
-            bucket_dec(hd, idx);
-            emit = true;
-        }
-        if (emit) {
-            const uint32_t addr = atomicAdd(outCounter, 1u);
-            if (addr < capacity) {
-                VhSDFBlockDesc dsc;
-                dsc.pos[0] = q.x; dsc.pos[1] = q.y; dsc.pos[2] = q.z; dsc.ptr = q.w;
-                out[addr] = dsc;
-                const uint32_t bit = chunk_bit_of_block(hp, pos);
-                if (bitMask && bit != 0xffffffffu) atomicOr(&bitMask[bit >> 5], 1u << (bit & 31u));
-            }
-        }
-    }
-}
-
-// The same scan without the deletes: how many blocks of the part would the pass move out?  (A frame loop that knows its
-// poses ahead asks this a frame early -- after that frame's alloc, the last pass that adds blocks -- and keeps the
-// whole streaming step out of the next frame's launches when the answer is none: Reconstruction::frame.)
-__global__ __launch_bounds__(256) void k_stream_out_probe(VhHashData hd, VhHashParams hp, uint32_t start, uint32_t n, float radius,
-                                                          float cx, float cy, float cz, uint32_t* counter)
-{
-    const uint32_t ne = hp.m_hashNumBuckets * VH_HASH_BUCKET_SIZE;
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, idx = t + start;
-    bool would = false;
-    if (t < n && idx < ne) {
-        const int4 q = load_quad(&hd.d_hash[idx]);
-        const F3 pw = block_to_world(hp.m_virtualVoxelSize, mki3(q.x, q.y, q.z));
-        const F3 df = mk3(pw.x - cx, pw.y - cy, pw.z - cz);
-        would = q.w != VH_FREE_ENTRY && sqrtf(dot3(df, df)) >= radius;
-    }
-    const unsigned long long m = __ballot(would);
-    if (m != 0ull && lane_id() == 0u) atomicAdd(counter, (uint32_t)__popcll(m));
-}
-
-// {*src, tag} into mapped host memory like k_publish_words, and the device word back to zero for the next use
-__global__ void k_publish_and_clear(uint32_t* src, uint32_t* mapped, uint32_t tag)
-{
-    mapped[0] = *src;
-    mapped[1] = 0u;
-    *src = 0u;
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    __hip_atomic_store(&mapped[2], tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// integrateFromGlobalHashPass2Kernel :97-113 (copy block out, clear source)
-__global__ __launch_bounds__(256) void k_stream_out_pass2(VhHashData hd, const VhSDFBlockDesc* descs, VhVoxel* out, uint32_t n)
-{
-    const uint32_t b = blockIdx.x;
-    if (b >= n) return;
-    const int ptr = __builtin_amdgcn_readfirstlane(descs[b].ptr);
-    uint4* src = reinterpret_cast<uint4*>(&hd.d_SDFBlocks[(uint32_t)ptr]) + threadIdx.x;
-    reinterpret_cast<uint4*>(out)[(size_t)b * 256 + threadIdx.x] = *src;
-    *src = make_uint4(0u, 0u, 0u, 0u);
-}
-
-// k_stream_out_pass2 for a caller that has not read the count: as many workgroups as blocks there can be at most, each
-// looks the count up
-__global__ __launch_bounds__(256) void k_stream_out_pass2_counted(VhHashData hd, const VhSDFBlockDesc* descs, VhVoxel* out, const uint32_t* counter, uint32_t capacity)
-{
-    const uint32_t b = blockIdx.x, n = min(*counter, capacity);
-    if (b >= n) return;
-    const int ptr = __builtin_amdgcn_readfirstlane(descs[b].ptr);
-    uint4* src = reinterpret_cast<uint4*>(&hd.d_SDFBlocks[(uint32_t)ptr]) + threadIdx.x;
-    reinterpret_cast<uint4*>(out)[(size_t)b * 256 + threadIdx.x] = *src;
-    *src = make_uint4(0u, 0u, 0u, 0u);
-}
-
-// {count of the pass, 0, tag} into mapped host memory, behind the pass's copies in the stream: a host thread that sees the
-// tag finds the copied blocks in its staging buffer
-__global__ void k_publish_count(const uint32_t* counter, uint32_t* mapped, uint32_t tag)
-{
-    mapped[0] = *counter;
-    mapped[1] = 0u;
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    __hip_atomic_store(&mapped[2], tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// The stream-in pass for a caller that does not read the heap counter back: chunkToGlobalHashPass1Kernel / Pass2Kernel
-// with the counter looked up on the device, the chunk's bit cleared in the device's copy of the bit mask, and a third
-// launch that settles the pass.  A block that finds no slot is listed as {index in the pass, SDF block it took} in
-// failed[1 ..] and its heap slot is marked, so that pass 2 leaves the block zero; the commit returns those blocks to the
-// heap and sets the chunk's bit again.  After the three launches the device state is final, and the host learns (mapped
-// memory) which blocks of its staging copy to file back into its grid:
-//   {blocks that found no slot, 0, tag, 1 if the heap held too few free blocks (nothing was done), their indices ...}
-constexpr uint32_t kStreamInNoSlot = 0xffffffffu;
-__global__ __launch_bounds__(64) void k_stream_in_pass1_dev(VhHashData hd, VhHashParams hp, uint32_t n, const VhSDFBlockDesc* descs, int32_t lockToken,
-                                                            uint32_t* failed, uint32_t* bitMask, uint32_t chunkBit)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t heapCountPrev = hd.d_heapCounter[0];
-    if (n > heapCountPrev + 1u) return; // (k_stream_in_commit reports it; the host puts the blocks back into its grid)
-    if (i == 0u && bitMask && chunkBit != 0xffffffffu) atomicAnd(&bitMask[chunkBit >> 5], ~(1u << (chunkBit & 31u)));
-    const uint32_t id = hd.d_heap[heapCountPrev - i];
-    const VhSDFBlockDesc dsc = descs[i];
-    if (!insert_hash_entry(hd, hp, mki3(dsc.pos[0], dsc.pos[1], dsc.pos[2]), (int)(id * VH_SDF_BLOCK_VOXELS), lockToken)) {
-        atomicAdd(&hd.d_state[VH_STATE_INSERT_FAILED], 1u);
-        const uint32_t k = atomicAdd(&failed[0], 1u);
-        failed[1u + 2u * k] = i;
-        failed[2u + 2u * k] = id;
-        hd.d_heap[heapCountPrev - i] = kStreamInNoSlot; // (above the counter once the pass is committed)
-    }
-}
-__global__ __launch_bounds__(256) void k_stream_in_pass2_dev(VhHashData hd, uint32_t n, const VhVoxel* blocks)
-{
-    const uint32_t b = blockIdx.x;
-    if (b >= n) return;
-    const uint32_t heapCountPrev = hd.d_heapCounter[0];
-    if (n > heapCountPrev + 1u) return;
-    const uint32_t id = hd.d_heap[heapCountPrev - b];
-    if (id == kStreamInNoSlot) return; // (a free block: zero already)
-    *(reinterpret_cast<uint4*>(&hd.d_SDFBlocks[id * VH_SDF_BLOCK_VOXELS]) + threadIdx.x) = reinterpret_cast<const uint4*>(blocks)[(size_t)b * 256 + threadIdx.x];
-}
-__global__ void k_stream_in_commit(VhHashData hd, uint32_t n, uint32_t* failed, uint32_t* bitMask, uint32_t chunkBit, uint32_t* mapped, uint32_t tag)
-{
-    const uint32_t heapCountPrev = hd.d_heapCounter[0];
-    const bool exhausted = n > heapCountPrev + 1u;
-    const uint32_t nFailed = failed[0];
-    if (!exhausted) {
-        // consumeHeap n times, then appendHeap (DSC/VoxelUtilHashSDF.h:525-529) of the blocks that found no slot
-        const uint32_t counter = heapCountPrev - n;
-        for (uint32_t k = 0; k < nFailed; k++) {
-            hd.d_heap[counter + 1u + k] = failed[2u + 2u * k];
-            mapped[4u + k] = failed[1u + 2u * k];
-        }
-        hd.d_heapCounter[0] = counter + nFailed;
-        if (nFailed != 0u && bitMask && chunkBit != 0xffffffffu) atomicOr(&bitMask[chunkBit >> 5], 1u << (chunkBit & 31u));
-    } else {
-        atomicAdd(&hd.d_state[VH_STATE_HEAP_UNDERFLOW], 1u);
-    }
-    failed[0] = 0u; // (for the next pass)
-    mapped[0] = nFailed;
-    mapped[1] = 0u;
-    mapped[3] = exhausted ? 1u : 0u;
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    __hip_atomic_store(&mapped[2], tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// chunkToGlobalHashPass1Kernel :143-160
-__global__ __launch_bounds__(64) void k_stream_in_pass1(VhHashData hd, VhHashParams hp, uint32_t n, uint32_t heapCountPrev,
-                                                        const VhSDFBlockDesc* descs, int32_t lockToken)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t ptr = hd.d_heap[heapCountPrev - i] * VH_SDF_BLOCK_VOXELS;
-    const VhSDFBlockDesc dsc = descs[i];
-    if (!insert_hash_entry(hd, hp, mki3(dsc.pos[0], dsc.pos[1], dsc.pos[2]), (int)ptr, lockToken)) atomicAdd(&hd.d_state[VH_STATE_INSERT_FAILED], 1u);
-}
-
-// chunkToGlobalHashPass2Kernel :181-189
-__global__ __launch_bounds__(256) void k_stream_in_pass2(VhHashData hd, uint32_t n, uint32_t heapCountPrev, const VhVoxel* blocks)
-{
-    const uint32_t b = blockIdx.x;
-    if (b >= n) return;
-    const uint32_t ptr = hd.d_heap[heapCountPrev - b] * VH_SDF_BLOCK_VOXELS;
-    *(reinterpret_cast<uint4*>(&hd.d_SDFBlocks[ptr]) + threadIdx.x) = reinterpret_cast<const uint4*>(blocks)[(size_t)b * 256 + threadIdx.x];
-}
-
-// ---------------------------------------------------------------------------
-// utilities
-// ---------------------------------------------------------------------------
-
-struct SynthArgs {
-    double spheres[4 * 8];
-    int nSpheres;
-    int inside;
-    float T[16];
-};
-
-// analytic sphere scene in double, rounded once to float
-__global__ __launch_bounds__(256) void k_synth(SynthArgs a, VhDepthCameraParams cp, float* depth, float4* color)
-{
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= cp.m_imageWidth * cp.m_imageHeight) return;
-    const uint32_t u = idx % cp.m_imageWidth, v = idx / cp.m_imageWidth;
-    const double ox = (double)a.T[3], oy = (double)a.T[7], oz = (double)a.T[11];
-    const double dx = ((double)u - (double)cp.mx) / (double)cp.fx;
-    const double dy = ((double)v - (double)cp.my) / (double)cp.fy;
-    const double wx = (double)a.T[0] * dx + (double)a.T[1] * dy + (double)a.T[2];
-    const double wy = (double)a.T[4] * dx + (double)a.T[5] * dy + (double)a.T[6];
-    const double wz = (double)a.T[8] * dx + (double)a.T[9] * dy + (double)a.T[10];
-    const double aa = wx * wx + wy * wy + wz * wz;
-    double bestT = 0.0;
-    int best = -1;
-    for (int s = 0; s < a.nSpheres; s++) {
-        const double cx = a.spheres[4 * s + 0], cy = a.spheres[4 * s + 1], cz = a.spheres[4 * s + 2], r = a.spheres[4 * s + 3];
-        const double ocx = ox - cx, ocy = oy - cy, ocz = oz - cz;
-        const double b = ocx * wx + ocy * wy + ocz * wz;
-        const double c = ocx * ocx + ocy * ocy + ocz * ocz - r * r;
-        const double disc = b * b - aa * c;
-        if (disc < 0.0) continue;
-        const double sq = sqrt(disc);
-        const double t = a.inside ? (-b + sq) / aa : (-b - sq) / aa;
-        if (t > 0.0 && (best < 0 || t < bestT)) { bestT = t; best = s; }
-    }
-    const float mi = minf();
-    if (best < 0) {
-        depth[idx] = mi;
-        color[idx] = make_float4(mi, mi, mi, mi);
-    } else {
-        const double cx = a.spheres[4 * best + 0], cy = a.spheres[4 * best + 1], cz = a.spheres[4 * best + 2], r = a.spheres[4 * best + 3];
-        const double px = ox + bestT * wx, py = oy + bestT * wy, pz = oz + bestT * wz;
-        double nx = (px - cx) / r, ny = (py - cy) / r, nz = (pz - cz) / r;
-        if (a.inside) { nx = -nx; ny = -ny; nz = -nz; }
-        depth[idx] = (float)bestT;
-        color[idx] = make_float4((float)(0.5 + 0.5 * nx), (float)(0.5 + 0.5 * ny), (float)(0.5 + 0.5 * nz), 1.0f);
-    }
-}
 
 // serial hash-operation interpreter (tests of the collision paths)
 __global__ void k_debug_hash_ops(VhHashData hd, VhHashParams hp, const int32_t* ops, int32_t* results, uint32_t n)
@@ -3931,36 +3032,6 @@ __global__ void k_debug_hash_ops(VhHashData hd, VhHashParams hp, const int32_t* 
         // atomics of this one did at L2 (between real launches the hardware does that)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
         results[i] = r;
-    }
-}
-
-// checks div_exact against `/` and umod_fast against `%` on pseudo-random operands
-__global__ __launch_bounds__(256) void k_check_fast_math(float b, HashMod hm, uint32_t n, uint32_t seed, uint32_t* mismatches)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    // xorshift-multiply scramble of (seed, i)
-    uint32_t s = (i + 1u) * 2654435761u ^ seed;
-    s ^= s >> 15; s *= 2246822519u; s ^= s >> 13; s *= 3266489917u; s ^= s >> 16;
-    uint32_t u = s * 747796405u + 2891336453u;
-    // dividend: mostly scene-scale positions, some raw bit patterns (any finite magnitude)
-    float a;
-    if ((i & 7u) == 7u) {
-        a = __uint_as_float(u);
-        const uint32_t ex = (u >> 23) & 0xffu;
-        if (ex == 0xffu || ex < 0x10u || ex > 0xe8u) a = (float)(int)u * 1.0e-6f; // keep a and a/b normal
-    } else {
-        a = ((float)(int)u) * (1.0f / 2147483648.0f) * (((i >> 3) & 1u) ? 400.0f : 8.0f);
-    }
-    const float rb = 1.0f / b;
-    const float q0 = a / b, q1 = div_exact(a, b, rb);
-    if (__float_as_uint(q0) != __float_as_uint(q1) && !(q0 == 0.0f && q1 == 0.0f)) atomicAdd(&mismatches[0], 1u);
-    if ((s % hm.d) != umod_fast(s, hm)) atomicAdd(&mismatches[1], 1u);
-    if ((u % hm.d) != umod_fast(u, hm)) atomicAdd(&mismatches[1], 1u);
-    if (i < 64u) { // extremes of the unsigned range
-        const uint32_t e = 0xffffffffu - i;
-        if ((e % hm.d) != umod_fast(e, hm)) atomicAdd(&mismatches[1], 1u);
-        if ((i % hm.d) != umod_fast(i, hm)) atomicAdd(&mismatches[1], 1u);
     }
 }
 
@@ -4018,18 +3089,6 @@ __global__ __launch_bounds__(256) void k_check_weighted_colour(uint32_t* out)
     if (bad0) atomicAdd(&out[0], bad0);
     if (bad1) atomicAdd(&out[1], bad1);
     if (first != 0xffffffffu) atomicMin(&out[2], first);
-}
-
-// multiply-shift constants of umod_fast for divisor d >= 2
-inline HashMod make_hash_mod(uint32_t d)
-{
-    HashMod k;
-    k.d = d;
-    uint32_t l = 0;
-    while ((1ull << l) < (uint64_t)d) l++;
-    k.m = (uint32_t)((((1ull << 32) * ((1ull << l) - (uint64_t)d)) / d) + 1ull);
-    k.sh = l - 1;
-    return k;
 }
 
 } // namespace
@@ -4387,286 +3446,12 @@ int vh_compute_normals(float* d_output4, const float* d_input4, uint32_t width, 
     return vh_compute_normals_co(d_output4, d_input4, width, height, nullptr, stream);
 }
 
-int vh_reset_marching_cubes(const VhMarchingCubesData* data, vhStream_t stream)
-{
-    if (!data || !data->d_numTriangles || !data->d_numOccupiedBlocks) return VH_ERR_BAD_ARGUMENT;
-    k_mc_reset<<<1, 64, 0, (hipStream_t)stream>>>(*data);
-    return vh_last_launch_error();
-}
-
-int vh_extract_iso_surface_pass1(const VhHashData* hd, const VhHashParams* hp, const VhMarchingCubesData* data, vhStream_t stream)
-{
-    if (!hd || !hp || !data || !data->d_occupiedBlocks) return VH_ERR_BAD_ARGUMENT;
-    const uint32_t nWords = (hp->m_hashNumBuckets + 31) / 32;
-    k_mc_pass1<<<cdiv(nWords, 256), 256, 0, (hipStream_t)stream>>>(*hd, *hp, *data);
-    return vh_last_launch_error();
-}
-
-int vh_extract_iso_surface_pass2(const VhHashData* hd, const VhHashParams* hp, const VhMarchingCubesData* data,
-                                 uint32_t numOccupiedBlocks, vhStream_t stream)
-{
-    if (!hd || !hp || !data || !data->d_params || !data->d_triangles) return VH_ERR_BAD_ARGUMENT;
-    if (numOccupiedBlocks == 0) return VH_OK;
-    VH_LAUNCH_TIMED(k_mc_pass2<false>, numOccupiedBlocks, 512, (hipStream_t)stream, *hd, *hp, *data, numOccupiedBlocks, (VhTriangleSource*)nullptr);
-    return vh_last_launch_error();
-}
-
-int vh_extract_iso_surface_pass2_sourced(const VhHashData* hd, const VhHashParams* hp, const VhMarchingCubesData* data,
-                                         VhTriangleSource* d_sources, uint32_t numOccupiedBlocks, vhStream_t stream)
-{
-    if (!hd || !hp || !data || !data->d_params || !data->d_triangles || !d_sources) return VH_ERR_BAD_ARGUMENT;
-    if (numOccupiedBlocks == 0) return VH_OK;
-    VH_LAUNCH_TIMED(k_mc_pass2<true>, numOccupiedBlocks, 512, (hipStream_t)stream, *hd, *hp, *data, numOccupiedBlocks, d_sources);
-    return vh_last_launch_error();
-}
-
-#define VH_IMG_LAUNCH(n) cdiv((uint32_t)(n), 256u), 256, 0, (hipStream_t)stream
-
-int vh_convert_color_raw_to_float4(float* d_output4, const uint8_t* d_inputRGBX, uint32_t width, uint32_t height, vhStream_t stream)
-{
-    if (!d_output4 || !d_inputRGBX) return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_OK;
-    k_convert_color_raw_to_float4<<<VH_IMG_LAUNCH(width * height)>>>(reinterpret_cast<float4*>(d_output4), reinterpret_cast<const uint32_t*>(d_inputRGBX), width * height);
-    return vh_last_launch_error();
-}
-
-int vh_ingest_frame(float* d_depth, float* d_color4, uint32_t width, uint32_t height, const uint16_t* d_depthRaw, uint32_t depthWidth, uint32_t depthHeight,
-                    const uint8_t* d_colorRaw, uint32_t colorWidth, uint32_t colorHeight, uint32_t colorChannels, float depthShift, vhStream_t stream)
-{
-    if (!d_depth || !d_depthRaw || width < 2 || height < 2 || depthWidth < 2 || depthHeight < 2) return VH_ERR_BAD_ARGUMENT;
-    if (!(depthShift > 0.0f) || !std::isfinite(depthShift)) return VH_ERR_BAD_ARGUMENT;
-    if (colorChannels != 0 && colorChannels != 3 && colorChannels != 4) return VH_ERR_BAD_ARGUMENT;
-    if (colorChannels != 0 && (!d_color4 || !d_colorRaw || colorWidth < 2 || colorHeight < 2)) return VH_ERR_BAD_ARGUMENT;
-    // 16-byte stores; the 32-bit pixel index of the other image kernels
-    if (((uintptr_t)d_depth | (uintptr_t)d_color4) % 16u || (uintptr_t)d_depthRaw % 2u || (colorChannels == 4 && (uintptr_t)d_colorRaw % 4u)) return VH_ERR_BAD_ARGUMENT;
-    if ((uint64_t)width * height > 0x7fffffffull || (uint64_t)depthWidth * depthHeight > 0x7fffffffull || (uint64_t)colorWidth * colorHeight * 4ull > 0x7fffffffull) return VH_ERR_BAD_ARGUMENT;
-    const bool copyColor = colorWidth == width && colorHeight == height;
-    const uint32_t groups = cdiv(width * height, kIngestPixelsPerGroup);
-    float4* c4 = reinterpret_cast<float4*>(d_color4);
-#define VH_INGEST(CH, COPY) k_ingest_frame<CH, COPY><<<groups, 256, 0, (hipStream_t)stream>>>(d_depth, c4, d_depthRaw, d_colorRaw, depthWidth, depthHeight, colorWidth, colorHeight, width, height, depthShift)
-    if (colorChannels == 0) VH_INGEST(0, false);
-    else if (colorChannels == 3) { if (copyColor) VH_INGEST(3, true); else VH_INGEST(3, false); }
-    else { if (copyColor) VH_INGEST(4, true); else VH_INGEST(4, false); }
-#undef VH_INGEST
-    return vh_last_launch_error();
-}
-
-int vh_resample_float_map(float* d_output, uint32_t outputWidth, uint32_t outputHeight, const float* d_input, uint32_t inputWidth, uint32_t inputHeight, vhStream_t stream)
-{
-    if (!d_output || !d_input || inputWidth == 0 || inputHeight == 0) return VH_ERR_BAD_ARGUMENT;
-    if (outputWidth * outputHeight == 0) return VH_OK;
-    k_resample<float><<<VH_IMG_LAUNCH(outputWidth * outputHeight)>>>(d_output, d_input, inputWidth, inputHeight, outputWidth, outputHeight);
-    return vh_last_launch_error();
-}
-int vh_resample_float4_map(float* d_output4, uint32_t outputWidth, uint32_t outputHeight, const float* d_input4, uint32_t inputWidth, uint32_t inputHeight, vhStream_t stream)
-{
-    if (!d_output4 || !d_input4 || inputWidth == 0 || inputHeight == 0) return VH_ERR_BAD_ARGUMENT;
-    if (outputWidth * outputHeight == 0) return VH_OK;
-    k_resample<float4><<<VH_IMG_LAUNCH(outputWidth * outputHeight)>>>(reinterpret_cast<float4*>(d_output4), reinterpret_cast<const float4*>(d_input4), inputWidth, inputHeight, outputWidth, outputHeight);
-    return vh_last_launch_error();
-}
-int vh_copy_float_map(float* d_output, const float* d_input, uint32_t width, uint32_t height, vhStream_t stream)
-{
-    if (!d_output || !d_input) return VH_ERR_BAD_ARGUMENT;
-    VH_HIP(hipMemcpyAsync(d_output, d_input, sizeof(float) * (size_t)width * height, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return VH_OK;
-}
-int vh_copy_float4_map(float* d_output4, const float* d_input4, uint32_t width, uint32_t height, vhStream_t stream)
-{
-    if (!d_output4 || !d_input4) return VH_ERR_BAD_ARGUMENT;
-    VH_HIP(hipMemcpyAsync(d_output4, d_input4, sizeof(float) * 4 * (size_t)width * height, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return VH_OK;
-}
-int vh_set_invalid_float_map(float* d_output, uint32_t width, uint32_t height, vhStream_t stream)
-{
-    if (!d_output) return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_OK;
-    k_set_invalid_float<<<VH_IMG_LAUNCH(width * height)>>>(d_output, width * height);
-    return vh_last_launch_error();
-}
-int vh_convert_color_to_intensity_float(float* d_output, const float* d_input4, uint32_t width, uint32_t height, vhStream_t stream)
-{
-    if (!d_output || !d_input4) return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_OK;
-    k_color_to_intensity<<<VH_IMG_LAUNCH(width * height)>>>(d_output, reinterpret_cast<const float4*>(d_input4), width * height);
-    return vh_last_launch_error();
-}
-int vh_convert_depth_float_to_camera_space_float4(float* d_output4, const float* d_input, const VhDepthCameraParams* cp, uint32_t width, uint32_t height, vhStream_t stream)
-{
-    if (!d_output4 || !d_input || !cp) return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_OK;
-    k_depth_to_camera_space<<<VH_IMG_LAUNCH(width * height)>>>(reinterpret_cast<float4*>(d_output4), d_input, *cp, width, height);
-    return vh_last_launch_error();
-}
-int vh_gauss_filter_float_map(float* d_output, const float* d_input, float sigmaD, float sigmaR, uint32_t width, uint32_t height, vhStream_t stream)
-{
-    if (!d_output || !d_input || d_output == d_input) return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_OK;
-    const int r = (int)ceil(2.0 * (double)sigmaD);
-    if (r >= 0 && r <= kGaussMaxRadius) {
-        const size_t lds = sizeof(float) * ((size_t)(kGaussTileW + 2 * r) * (kGaussTileH + 2 * r) + (size_t)(2 * r + 1) * (2 * r + 1));
-        const dim3 grid(cdiv(width, (uint32_t)kGaussTileW), cdiv(height, (uint32_t)kGaussTileH));
-        k_gauss_filter_float_tiled<<<grid, 256, lds, (hipStream_t)stream>>>(d_output, d_input, sigmaD, sigmaR, (int)width, (int)height, r);
-    } else {
-        k_gauss_filter_float<<<VH_IMG_LAUNCH(width * height)>>>(d_output, d_input, sigmaD, sigmaR, width, height);
-    }
-    return vh_last_launch_error();
-}
-int vh_gauss_filter_float4_map(float* d_output4, const float* d_input4, float sigmaD, float sigmaR, uint32_t width, uint32_t height, vhStream_t stream)
-{
-    if (!d_output4 || !d_input4 || d_output4 == d_input4) return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_OK;
-    k_gauss_filter_float4<<<VH_IMG_LAUNCH(width * height)>>>(reinterpret_cast<float4*>(d_output4), reinterpret_cast<const float4*>(d_input4), sigmaD, sigmaR, width, height);
-    return vh_last_launch_error();
-}
-int vh_bilateral_filter_float_map(float* d_output, const float* d_input, float sigmaD, float sigmaR, uint32_t width, uint32_t height, vhStream_t stream)
-{
-    if (!d_output || !d_input || d_output == d_input) return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_OK;
-    k_bilateral_filter_float<<<VH_IMG_LAUNCH(width * height)>>>(d_output, d_input, sigmaD, sigmaR, width, height);
-    return vh_last_launch_error();
-}
-int vh_erode_depth_map(float* d_output, const float* d_input, int32_t structureSize, uint32_t width, uint32_t height, float dThresh, float fracReq, vhStream_t stream)
-{
-    if (!d_output || !d_input || d_output == d_input || structureSize < 0) return VH_ERR_BAD_ARGUMENT;
-    if (width * height == 0) return VH_OK;
-    k_erode_depth<<<VH_IMG_LAUNCH(width * height)>>>(d_output, d_input, structureSize, (int)width, (int)height, dThresh, fracReq);
-    return vh_last_launch_error();
-}
-#undef VH_IMG_LAUNCH
-
-int vh_stream_out_pass1(const VhHashData* hd, const VhHashParams* hp, uint32_t threadsPerPart, uint32_t start,
-                        float radius, const float camPos[3], uint32_t* d_outputCounter, VhSDFBlockDesc* d_output,
-                        uint32_t outputCapacity, int32_t lockToken, vhStream_t stream)
-{
-    if (!hd || !hp || !camPos || !d_outputCounter || !d_output) return VH_ERR_BAD_ARGUMENT;
-    if (threadsPerPart == 0) return VH_OK; // DSC/CUDASceneRepChunkGrid.cu:81
-    k_stream_out_pass1<<<cdiv(threadsPerPart, 64), 64, 0, (hipStream_t)stream>>>(*hd, *hp, start, radius, camPos[0], camPos[1], camPos[2],
-                                                                                   d_outputCounter, d_output, outputCapacity, lockToken);
-    return vh_last_launch_error();
-}
-
-int vh_stream_out_probe(const VhHashData* hd, const VhHashParams* hp, uint32_t threadsPerPart, uint32_t start, float radius,
-                        const float camPos[3], uint32_t* d_counter, uint32_t* d_mapped, uint32_t tag, vhStream_t stream)
-{
-    if (!hd || !hp || !camPos || !d_counter || !d_mapped) return VH_ERR_BAD_ARGUMENT;
-    if (threadsPerPart != 0) {
-        // (the pass itself runs whole workgroups of 64: it looks at up to 63 entries beyond its part, and so must its probe --
-        // the count is used as an upper bound)
-        const uint32_t scanned = cdiv(threadsPerPart, 64) * 64u;
-        k_stream_out_probe<<<cdiv(scanned, 256), 256, 0, (hipStream_t)stream>>>(*hd, *hp, start, scanned, radius, camPos[0], camPos[1], camPos[2], d_counter);
-    }
-    k_publish_and_clear<<<1, 1, 0, (hipStream_t)stream>>>(d_counter, d_mapped, tag);
-    return vh_last_launch_error();
-}
-
-int vh_stream_out_pass2(const VhHashData* hd, const VhHashParams* hp, const VhSDFBlockDesc* d_descs,
-                        VhVoxel* d_output, uint32_t nSDFBlocks, vhStream_t stream)
-{
-    (void)hp;
-    if (!hd || !d_descs || !d_output) return VH_ERR_BAD_ARGUMENT;
-    if (nSDFBlocks == 0) return VH_OK;
-    k_stream_out_pass2<<<nSDFBlocks, 256, 0, (hipStream_t)stream>>>(*hd, d_descs, d_output, nSDFBlocks);
-    return vh_last_launch_error();
-}
-
-int vh_stream_out_device(const VhHashData* hd, const VhHashParams* hp, uint32_t threadsPerPart, uint32_t start, float radius,
-                         const float camPos[3], uint32_t* d_outputCounter, VhSDFBlockDesc* d_descs, VhVoxel* d_blocks,
-                         uint32_t mostBlocks, int32_t lockToken, uint32_t* d_bitMask, vhStream_t stream)
-{
-    if (!hd || !hp || !camPos || !d_outputCounter || !d_descs || !d_blocks) return VH_ERR_BAD_ARGUMENT;
-    hipStream_t s = (hipStream_t)stream;
-    VH_HIP(hipMemsetAsync(d_outputCounter, 0, sizeof(uint32_t), s));
-    if (threadsPerPart == 0 || mostBlocks == 0) return VH_OK;
-    k_stream_out_pass1_bits<<<cdiv(threadsPerPart, 64), 64, 0, s>>>(*hd, *hp, start, radius, camPos[0], camPos[1], camPos[2], d_outputCounter, d_descs,
-                                                                     mostBlocks, lockToken, d_bitMask);
-    k_stream_out_pass2_counted<<<mostBlocks, 256, 0, s>>>(*hd, d_descs, d_blocks, d_outputCounter, mostBlocks);
-    return vh_last_launch_error();
-}
-
-int vh_publish_count(const uint32_t* d_counter, uint32_t* d_mapped, uint32_t tag, vhStream_t stream)
-{
-    if (!d_counter || !d_mapped) return VH_ERR_BAD_ARGUMENT;
-    k_publish_count<<<1, 1, 0, (hipStream_t)stream>>>(d_counter, d_mapped, tag);
-    return vh_last_launch_error();
-}
-
-int vh_stream_in_device(const VhHashData* hd, const VhHashParams* hp, uint32_t n, const VhSDFBlockDesc* d_descs, const VhVoxel* d_blocks,
-                        int32_t lockToken, uint32_t* d_failed, uint32_t* d_bitMask, uint32_t chunkBit, uint32_t* d_mapped, uint32_t tag,
-                        vhStream_t stream)
-{
-    if (!hd || !hp || !d_descs || !d_blocks || !d_failed || !d_mapped) return VH_ERR_BAD_ARGUMENT;
-    if (hp->m_hashNumBuckets < 2) return VH_ERR_BAD_ARGUMENT;
-    hipStream_t s = (hipStream_t)stream;
-    if (n != 0) {
-        k_stream_in_pass1_dev<<<cdiv(n, 64), 64, 0, s>>>(*hd, *hp, n, d_descs, lockToken, d_failed, d_bitMask, chunkBit);
-        k_stream_in_pass2_dev<<<n, 256, 0, s>>>(*hd, n, d_blocks);
-    }
-    k_stream_in_commit<<<1, 1, 0, s>>>(*hd, n, d_failed, d_bitMask, chunkBit, d_mapped, tag);
-    return vh_last_launch_error();
-}
-
-int vh_stream_in_pass1(const VhHashData* hd, const VhHashParams* hp, uint32_t n, uint32_t heapCountPrev,
-                       const VhSDFBlockDesc* d_descs, int32_t lockToken, vhStream_t stream)
-{
-    if (!hd || !hp || !d_descs) return VH_ERR_BAD_ARGUMENT;
-    if (n == 0) return VH_OK;
-    if (n > heapCountPrev + 1u) return VH_ERR_HEAP_EXHAUSTED;
-    if (hp->m_hashNumBuckets < 2) return VH_ERR_BAD_ARGUMENT;
-    k_stream_in_pass1<<<cdiv(n, 64), 64, 0, (hipStream_t)stream>>>(*hd, *hp, n, heapCountPrev, d_descs, lockToken);
-    return vh_last_launch_error();
-}
-
-int vh_stream_in_pass2(const VhHashData* hd, const VhHashParams* hp, uint32_t n, uint32_t heapCountPrev,
-                       const VhSDFBlockDesc* d_descs, const VhVoxel* d_blocks, vhStream_t stream)
-{
-    (void)hp; (void)d_descs;
-    if (!hd || !d_blocks) return VH_ERR_BAD_ARGUMENT;
-    if (n == 0) return VH_OK;
-    if (n > heapCountPrev + 1u) return VH_ERR_HEAP_EXHAUSTED;
-    k_stream_in_pass2<<<n, 256, 0, (hipStream_t)stream>>>(*hd, n, heapCountPrev, d_blocks);
-    return vh_last_launch_error();
-}
-
-int vh_synth_frame(const double* h_spheres, int nSpheres, int inside, const float camToWorld[16],
-                   const VhDepthCameraParams* cp, float* d_depth, float* d_color4, vhStream_t stream)
-{
-    if (!h_spheres || !camToWorld || !cp || !d_depth || !d_color4 || nSpheres < 0 || nSpheres > 8) return VH_ERR_BAD_ARGUMENT;
-    SynthArgs a;
-    for (int i = 0; i < 4 * nSpheres; i++) a.spheres[i] = h_spheres[i];
-    a.nSpheres = nSpheres;
-    a.inside = inside;
-    for (int i = 0; i < 16; i++) a.T[i] = camToWorld[i];
-    const uint64_t n = (uint64_t)cp->m_imageWidth * cp->m_imageHeight;
-    if (n == 0) return VH_OK;
-    k_synth<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(a, *cp, d_depth, reinterpret_cast<float4*>(d_color4));
-    return vh_last_launch_error();
-}
-
 int vh_debug_hash_ops(const VhHashData* hd, const VhHashParams* hp, const int32_t* d_ops, int32_t* d_results,
                       uint32_t n, vhStream_t stream)
 {
     if (!hd || !hp || !d_ops || !d_results) return VH_ERR_BAD_ARGUMENT;
     if (n == 0) return VH_OK;
     k_debug_hash_ops<<<1, 64, 0, (hipStream_t)stream>>>(*hd, *hp, d_ops, d_results, n);
-    return vh_last_launch_error();
-}
-
-// {*src0, *src1, tag} into mapped host memory, the tag last and with system scope: a host that polls the tag reads
-// the two words without a stream synchronisation or a copy (each costs a blocking driver call; the streaming passes of
-// a frame need two such read-backs)
-__global__ void k_publish_words(const uint32_t* src0, const uint32_t* src1, uint32_t* mapped, uint32_t tag)
-{
-    mapped[0] = src0 ? *src0 : 0u;
-    mapped[1] = src1 ? *src1 : 0u;
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    __hip_atomic_store(&mapped[2], tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-int vh_publish_words(const uint32_t* d_src0, const uint32_t* d_src1, uint32_t* d_mapped, uint32_t tag, vhStream_t stream)
-{
-    if (!d_mapped) return VH_ERR_BAD_ARGUMENT;
-    k_publish_words<<<1, 1, 0, (hipStream_t)stream>>>(d_src0, d_src1, d_mapped, tag);
     return vh_last_launch_error();
 }
 
@@ -4686,15 +3471,6 @@ int vh_debug_check_weighted_colour(uint32_t* d_out, vhStream_t stream)
     VH_HIP(hipMemcpyAsync(d_out, init, sizeof(init), hipMemcpyHostToDevice, (hipStream_t)stream));
     VH_HIP(hipStreamSynchronize((hipStream_t)stream)); // (init is this call's own)
     k_check_weighted_colour<<<65536, 256, 0, (hipStream_t)stream>>>(d_out);
-    return vh_last_launch_error();
-}
-
-int vh_debug_check_fast_math(float divisor, uint32_t modulus, uint32_t n, uint32_t seed, uint32_t* d_mismatches, vhStream_t stream)
-{
-    if (!d_mismatches || modulus < 2 || !(divisor > 0.0f)) return VH_ERR_BAD_ARGUMENT;
-    VH_HIP(hipMemsetAsync(d_mismatches, 0, 2 * sizeof(uint32_t), (hipStream_t)stream));
-    if (n == 0) return VH_OK;
-    k_check_fast_math<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(divisor, make_hash_mod(modulus), n, seed, d_mismatches);
     return vh_last_launch_error();
 }
 

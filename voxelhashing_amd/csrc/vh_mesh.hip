@@ -2,7 +2,7 @@
 // downloads the soup and merges it on the host with mLib's mergeCloseVertices; DESIGN.md section 4, "Indexed mesh").
 //
 // Every vertex of the soup lies on an edge of the lattice of voxel corners, or on a lattice point when vertexInterp
-// snapped it, and the sourced pass 2 (vh_kernels.hip) says which.  Keyed by that (vh_mesh_key.hpp) the weld needs no
+// snapped it, and the sourced pass 2 (vh_mc.hip) says which.  Keyed by that (vh_mesh_key.hpp) the weld needs no
 // distance search: an open-addressing table with linear probing takes one slot per key, the cell with the smallest
 // (z, y, x) among those that share the key gives the vertex its bits, and the result does not depend on the order of
 // the soup.  Three launches: insert (one lane per soup vertex), number (eight slots per lane), faces (one lane per
@@ -18,8 +18,6 @@
 using namespace vhd;
 
 namespace {
-
-VHD uint64_t lanemask_lt() { return (1ull << lane_id()) - 1ull; }
 
 // the slot a key starts probing at (the 64-bit finaliser of MurmurHash3)
 VHD uint32_t weld_home(uint64_t k, uint32_t mask)

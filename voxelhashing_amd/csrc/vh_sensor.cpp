@@ -1,6 +1,6 @@
 // vh_sensor.cpp -- the per-frame image path between a depth sensor and integrate(): CUDARGBDAdapter::process
 // (DSC/CUDARGBDAdapter.cpp:93-137) followed by CUDARGBDSensor::process (DSC/CUDARGBDSensor.cpp:147-257), as one
-// host class over the kernels of vh_kernels.hip ("sensor pre-processing").  The D3D11 remapping branch
+// host class over the kernels of vh_image.hip (sensor pre-processing).  The D3D11 remapping branch
 // (s_bUseCameraCalibration, :198-217) is the depth map drawn into the colour camera by the view passes of vh_view.hip
 // (vh_view_raster + vh_view_resolve_depth, render target 0 straight into d_depthData); setCameraCalibration switches it
 // on.  The disabled erosion loop (:224-237) is not part of it.

@@ -25,6 +25,7 @@
 #include <limits>
 
 #include "../../include/vh.hpp"
+#include "vh_device.hpp"
 #include "vh_host_util.hpp"
 
 namespace {
@@ -36,7 +37,7 @@ constexpr uint64_t kLargeBox = 64;     // pixels of a clipped box above which a 
 constexpr float kGuard = 268435456.0f; // 2^20 px on the 1/256 grid: a snapped coordinate beyond it drops the triangle
 constexpr uint32_t kLargeBlocks = 1024;
 
-inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+using vhd::cdiv;
 
 struct ViewVertex {
     float X, Y, z; // screen position (pixels, y down) and D3D depth
