@@ -736,6 +736,21 @@ public:
     // buffer is then empty.
     void extractIsoSurfaceIndexed(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner = { 0, 0, 0 },
                                   const vh::vec3f& maxCorner = { 0, 0, 0 }, bool boxEnabled = false);
+    // The same box by box, for several extractions that make one mesh ("Indexed mesh over several
+    // extractions"): beginIndexed starts an accumulation, appendIndexed runs reset, pass 1, the sourced pass 2 and the
+    // overflow test of copyTrianglesToCPU in its box and appends the soup to the accumulating weld
+    // (vh_mesh_weld_accum_append), finishIndexed downloads, REPLACES the mesh buffer and marks it welded.  Boxes may
+    // overlap: a cell is taken from the first box that has it.  Errors as extractIsoSurfaceIndexed, buffer empty.
+    void beginIndexed();
+    void appendIndexed(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner = { 0, 0, 0 },
+                       const vh::vec3f& maxCorner = { 0, 0, 0 }, bool boxEnabled = false);
+    void finishIndexed();
+    // the walk of extractIsoSurface(chunkGrid, ...) with the same boxes, every chunk appended to one accumulation.  When
+    // a chunk throws, the scene is streamed back in around camPos and the streaming thread restarted as at the normal
+    // end, the mesh buffer is empty, the indexed counts are 0, and the error goes on to the caller.
+    void extractIsoSurfaceIndexed(CUDASceneRepChunkGrid& chunkGrid, const vh::vec3f& camPos, float radius);
+    // of the last accumulated extraction: the VH_WELD_ACCUM_NUM_COUNTS counts of vh_types.h; 0 after a one-shot one
+    void getIndexedStats(unsigned int out[6]) const { for (int i = 0; i < 6; i++) out[i] = m_indexedStats[i]; }
     bool isWelded() const { return m_welded; }
     void getIndexedCounts(unsigned int out[3]) const { out[0] = m_indexedCounts[0]; out[1] = m_indexedCounts[1]; out[2] = m_indexedCounts[2]; }
     void downloadIndexed(VhVertex* vertices, uint64_t* keys, uint32_t* faces); // device mesh of the last indexed extraction
@@ -763,6 +778,12 @@ private:
     std::unique_ptr<VhMeshWeldData, WeldFree> m_weldOwner;
     unsigned int m_indexedCounts[3] = { 0, 0, 0 }; // {vertices, faces, status}
     unsigned int m_numSourced = 0;                 // triangles of the last indexed extraction that are in the buffer
+    // accumulated indexed extraction: made by the first beginIndexed
+    struct AccumFree { void operator()(VhMeshWeldAccum* a) const noexcept; };
+    std::unique_ptr<VhMeshWeldAccum, AccumFree> m_accum;
+    bool m_indexedIsAccumulated = false;           // downloadIndexed reads m_accum, not m_weld
+    unsigned int m_indexedStats[6] = { 0, 0, 0, 0, 0, 0 };
+    void resetIndexed();                           // empty buffer, zero counts: the state an error leaves
 };
 
 

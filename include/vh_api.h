@@ -54,7 +54,8 @@ int vh_memset(void* dst, int value, size_t bytes, vhStream_t stream);
  * rocprofv3's kernel trace reports -- with no event record in the stream.  The launch consumes the pair. */
 int vh_time_next_launch(void* startEvent, void* stopEvent);
 /* the same for an entry point that launches several kernels: `skip` of the calling thread's timed launches pass first.
- * vh_extract_iso_surface_pass2[_sourced] launch one kernel; vh_mesh_weld launches insert, number, faces (skip 0, 1, 2). */
+ * vh_extract_iso_surface_pass2[_sourced] launch one kernel; vh_mesh_weld launches insert, number, faces (skip 0, 1, 2),
+ * vh_mesh_weld_accum_append insert, settle, faces. */
 int vh_time_launch_after(uint32_t skip, void* startEvent, void* stopEvent);
 int vh_stream_create(vhStream_t* out);   /* a non-blocking HIP stream, for FFI users without a HIP binding */
 int vh_stream_destroy(vhStream_t stream);
@@ -717,6 +718,38 @@ int vh_mesh_weld_get_counts(const VhMeshWeldData* data, uint32_t out[3], vhStrea
 int vh_mesh_weld_download(const VhMeshWeldData* data, VhVertex* vertices, uint64_t* keys, uint32_t* faces, uint32_t numVertices,
                           uint32_t numFaces, vhStream_t stream);
 
+/* ---- the accumulating weld: one indexed mesh out of several soups (csrc/vh_mesh.hip; DESIGN.md section 4, "Indexed
+ * mesh over several extractions").  begin, then any number of appends, then get_counts / download.
+ *   - a cell (VhTriangleSource::cell) belongs to the first append it occurs in: its triangles in a later append are
+ *     dropped before they contribute a key, a bid or a face (and counted); within one append all are kept
+ *   - a vertex key has one welded vertex for the whole accumulation, with the bits of the soup vertex of the smallest
+ *     rank among all kept triangles (ties inside an append: the smallest soup index); its index never changes
+ *   - faces are written as final index triples by the append that brings them; a face with a repeated index is dropped
+ * The result is vh_mesh_weld of the kept triangles concatenated in append order.
+ *   slotsLog2         the table's first size (0: 2^6 slots).  Before an append of n triangles the table is doubled until
+ *                     it holds the keys it has plus 4 n (3 n vertex keys, n cell keys) at a load of at most 1/2
+ *   reserveTriangles  the first size of the vertex and face arrays (0: the smallest); they grow as needed whatever
+ *                     `fixed` says
+ *   fixed             the table never grows: a probe that finds no slot sets VH_WELD_TABLE_FULL
+ * Device memory: 20 B per slot, 33 B per welded vertex, 12 B per face, 12 B per triangle of the largest append. */
+typedef struct VhMeshWeldAccum VhMeshWeldAccum;
+int vh_mesh_weld_accum_create(uint32_t slotsLog2, uint32_t reserveTriangles, int fixed, VhMeshWeldAccum** out);
+void vh_mesh_weld_accum_destroy(VhMeshWeldAccum* accum);
+/* empties the table and the mesh (the buffers are kept at the size they have) */
+int vh_mesh_weld_accum_begin(VhMeshWeldAccum* accum, vhStream_t stream);
+/* One soup with its records, as the sourced pass 2 writes them.  Waits for the appends before it (it reads their
+ * counts to size the table), then launches insert, settle, faces (vh_time_launch_after skip 0, 1, 2) and returns;
+ * numTriangles = 0 launches nothing.  Once the status word is set nothing more is launched.  More than
+ * VH_WELD_ACCUM_MAX_APPENDS appends: VH_ERR_BAD_ARGUMENT. */
+int vh_mesh_weld_accum_append(VhMeshWeldAccum* accum, const VhTriangle* d_triangles, const VhTriangleSource* d_sources, uint32_t numTriangles,
+                              vhStream_t stream);
+/* Waits and reads the VH_WELD_ACCUM_NUM_COUNTS counts (vh_types.h).  The return value restates the status as
+ * vh_mesh_weld_get_counts does; with a status set, vertices, faces, cells and dropped read 0. */
+int vh_mesh_weld_accum_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream);
+/* as vh_mesh_weld_download */
+int vh_mesh_weld_accum_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint64_t* keys, uint32_t* faces, uint32_t numVertices,
+                                uint32_t numFaces, vhStream_t stream);
+
 /* handle level: CUDAMarchingCubesHashSDF (DSC/CUDAMarchingCubesHashSDF.h:8-67) */
 typedef struct VhMarchingCubes VhMarchingCubes;
 int vh_marching_cubes_create(const VhMarchingCubesParams* params, vhStream_t stream, VhMarchingCubes** out);
@@ -738,6 +771,21 @@ int vh_marching_cubes_extract_iso_surface_chunk_grid(VhMarchingCubes* mc, VhChun
  * VH_ERR_BAD_ARGUMENT when a lattice coordinate left the key range; the host mesh is then empty. */
 int vh_marching_cubes_extract_iso_surface_indexed(VhMarchingCubes* mc, const VhHashData* hd, const VhHashParams* hp,
                                                   const float minCorner[3], const float maxCorner[3], int boxEnabled);
+/* The indexed extraction box by box (not in the reference): begin_indexed starts an accumulation, append_indexed runs
+ * reset, pass 1, the sourced pass 2 and the overflow test of copyTrianglesToCPU in one box and appends the soup to the
+ * accumulating weld, finish_indexed downloads and REPLACES the host mesh as vh_marching_cubes_extract_iso_surface_indexed
+ * does.  Boxes may overlap: a cell is taken from the first box that has it.  An error leaves the host mesh empty. */
+int vh_marching_cubes_begin_indexed(VhMarchingCubes* mc);
+int vh_marching_cubes_append_indexed(VhMarchingCubes* mc, const VhHashData* hd, const VhHashParams* hp, const float minCorner[3],
+                                     const float maxCorner[3], int boxEnabled);
+int vh_marching_cubes_finish_indexed(VhMarchingCubes* mc);
+/* The walk of vh_marching_cubes_extract_iso_surface_chunk_grid with the same boxes, every chunk appended to one
+ * accumulation: the indexed mesh of a streamed scene.  When a chunk fails (VH_ERR_STAGING_OVERFLOW, VH_ERR_BAD_ARGUMENT
+ * as above) the scene is streamed back in around camPos and the streaming thread restarted as at the normal end, the
+ * host mesh is empty and the indexed counts are 0. */
+int vh_marching_cubes_extract_iso_surface_indexed_chunk_grid(VhMarchingCubes* mc, VhChunkGrid* grid, const float camPos[3], float radius);
+/* of the last accumulated extraction: the VH_WELD_ACCUM_NUM_COUNTS counts of vh_types.h (all 0 after a one-shot one) */
+int vh_marching_cubes_get_indexed_stats(VhMarchingCubes* mc, uint32_t out[6]);
 /* of the last indexed extraction: {vertices, faces, status} */
 int vh_marching_cubes_get_indexed_counts(VhMarchingCubes* mc, uint32_t out[3]);
 /* the device mesh of the last indexed extraction; each of vertices (position + colour), keys and faces may be NULL.

@@ -236,6 +236,21 @@ typedef struct VhMeshWeldData {
     uint32_t m_slotsLog2;
 } VhMeshWeldData;
 
+/* What the accumulating weld (vh_mesh_weld_accum_*) reports: vertices, faces and the status word as the one-shot weld,
+ * then the cells it took, the triangles it dropped because an earlier append had their cell, and the number of times
+ * its table doubled (every doubling moves the keys: one rehash launch covers the doublings of one append). */
+enum {
+    VH_WELD_ACCUM_VERTICES = 0,
+    VH_WELD_ACCUM_FACES = 1,
+    VH_WELD_ACCUM_STATUS = 2,
+    VH_WELD_ACCUM_CELLS = 3,
+    VH_WELD_ACCUM_DROPPED = 4,
+    VH_WELD_ACCUM_REHASHES = 5,
+    VH_WELD_ACCUM_NUM_COUNTS = 6
+};
+/* appends between two vh_mesh_weld_accum_begin: a bid carries the append's ordinal above the rank and the soup index */
+#define VH_WELD_ACCUM_MAX_APPENDS (1u << 28)
+
 /* The five GlobalAppState flags the reference host classes read
  * (DSC/CUDASceneRepHashSDF.h:249,251,329,331; DSC/CUDASceneRepChunkGrid.cpp:13). */
 typedef struct VhSceneOptions {

@@ -11,6 +11,14 @@ pass 2, the sourced pass 2 and the three weld kernels, the bytes each route down
 merge (mergeCloseVertices + removeDuplicateFaces inside saveMesh) on the same soup.
 
     python tools/bench_mesh.py --indexed [--config cfg3] [--frames 100] [--reps 20]
+
+--indexed --streamed puts the same scene behind a chunk grid (the config's 1 m chunks) and measures the two routes of a
+streamed scene ("Indexed mesh over several extractions") in one process: the wall time of the soup
+walk (extractIsoSurface(chunkGrid)) and of saveMesh's merge of that soup, the wall time of the indexed walk
+(extractIsoSurfaceIndexed(chunkGrid)), the bytes each downloads, and -- at the launcher level, over the same boxes on
+the resident scene -- each append's three kernels by vh_time_launch_after (one accumulation per kernel; --reps of them).
+
+    python tools/bench_mesh.py --indexed --streamed [--config cfg3] [--frames 100] [--reps 5]
 """
 import argparse
 import ctypes as C
@@ -94,6 +102,113 @@ def indexed_report(args, scene, hp):
     return out
 
 
+def streamed_report(args, scene, hp):
+    """a streamed scene to a mesh: soup walk + host merge (what there was) against the indexed walk"""
+    import tempfile
+    from voxelhashing_amd import engine as E, lib, vhtypes as T
+    L = lib.load()
+    hd, hpp = scene.getHashData(), scene.getHashParams()
+    mp = T.make_marching_cubes_params(hp, 1 << 22)
+    ext = [hp.m_streamingVoxelExtents[i] for i in range(3)]
+    out = dict(chunk_extent_m=ext[0])
+
+    # ---- the appends' kernels, box by box on the resident scene (the boxes of the walk: chunk +- one block)
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+    e0, e1 = C.c_void_p(), C.c_void_p()
+    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
+    data = T.MarchingCubesData()
+    lib.check(L.vh_marching_cubes_data_alloc(C.byref(data), C.byref(mp)), "vh_marching_cubes_data_alloc")
+    sources = lib.DeviceBuffer(T.TRIANGLE_SOURCE_DTYPE.itemsize * mp.m_maxNumTriangles)
+    f32 = np.float32
+    pad = f32(hp.m_virtualVoxelSize) * f32(hp.m_SDFBlockSize)
+    reach = 3  # chunks each way from the origin: the S1 scene lies within 1.5 m of it
+
+    def extract_box(chunk):
+        c = np.array(chunk, dtype=np.float32) * np.array(ext, dtype=np.float32)
+        half = np.array(ext, dtype=np.float32) / f32(2.0)
+        mp.m_boxEnabled = 1
+        mp.m_minCorner[:] = [float(v) for v in c - half - pad]
+        mp.m_maxCorner[:] = [float(v) for v in c + half + pad]
+        lib.check(L.vh_reset_marching_cubes(C.byref(data), None), "reset")
+        lib.check(L.vh_marching_cubes_update_params(C.byref(data), C.byref(mp), None), "update_params")
+        lib.check(L.vh_extract_iso_surface_pass1(C.byref(hd), C.byref(hpp), C.byref(data), None), "pass1")
+        nblk = int(lib.download(data.d_numOccupiedBlocks, np.uint32, 1)[0])
+        lib.check(L.vh_extract_iso_surface_pass2_sourced(C.byref(hd), C.byref(hpp), C.byref(data), sources.ptr, nblk, None), "pass2 sourced")
+        return int(lib.download(data.d_numTriangles, np.uint32, 1)[0])
+
+    chunks = [(x, y, z) for x in range(-reach, reach + 1) for y in range(-reach, reach + 1) for z in range(-reach, reach + 1)]
+    chunks = [c for c in chunks if extract_box(c) > 0]
+    accum = C.c_void_p()
+    lib.check(L.vh_mesh_weld_accum_create(0, 0, 0, C.byref(accum)), "vh_mesh_weld_accum_create")
+    names = ("append_insert_us", "append_settle_us", "append_faces_us")
+    per_append = {n: [] for n in names}
+    counts = (C.c_uint32 * 6)()
+    for skip, name in enumerate(names):
+        for rep in range(1 + args.reps):  # the first accumulation grows the table and the arrays; the later ones reuse them
+            lib.check(L.vh_mesh_weld_accum_begin(accum, None), "vh_mesh_weld_accum_begin")
+            us = []
+            for c in chunks:
+                n = extract_box(c)
+                lib.check(L.vh_time_launch_after(skip, e0, e1), "vh_time_launch_after")
+                lib.check(L.vh_mesh_weld_accum_append(accum, data.d_triangles, sources.ptr, n, None), "vh_mesh_weld_accum_append")
+                lib.check(L.vh_stream_synchronize(None), "synchronize")
+                ms = C.c_float()
+                assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0, "the launch did not take the events"
+                us.append(1e3 * ms.value)
+            if rep == 0:
+                lib.check(L.vh_mesh_weld_accum_get_counts(accum, counts, None), "vh_mesh_weld_accum_get_counts")
+                out.setdefault("doublings_first_accumulation", int(counts[5]))
+            else:
+                per_append[name].append(us)
+    lib.check(L.vh_mesh_weld_accum_get_counts(accum, counts, None), "vh_mesh_weld_accum_get_counts")
+    L.vh_mesh_weld_accum_destroy(accum)
+    L.vh_marching_cubes_data_free(C.byref(data))
+    for name in names:
+        med = np.median(np.array(per_append[name]), axis=0)  # per append, over the accumulations
+        out[name] = dict(sum=round(float(med.sum()), 1), largest=round(float(med.max()), 1), median=round(float(np.median(med)), 1))
+    out.update(appends_timed=len(chunks), boxes_vertices=int(counts[0]), boxes_faces=int(counts[1]), boxes_dropped=int(counts[4]))
+
+    # ---- the two walks
+    pos, radius = (0.0, 0.0, 0.0), 100.0  # everything comes back in at the end of a walk
+    dims = [hp.m_streamingGridDimensions[i] for i in range(3)]
+    mn = [hp.m_streamingMinGridPos[i] for i in range(3)]
+    grid = E.CUDASceneRepChunkGrid(scene, ext, dims, mn, hp.m_streamingInitialChunkListSize, True, 4)
+    mc = E.CUDAMarchingCubesHashSDF(mp)
+    try:
+        with tempfile.TemporaryDirectory() as d:
+            walls = dict(soup_walk_s=[], soup_save_s=[], indexed_walk_s=[], indexed_save_s=[])
+            for rep in range(1 + max(args.reps, 3)):  # the first pair of walks sizes every buffer
+                t0 = time.perf_counter()
+                mc.extractIsoSurfaceChunkGrid(grid, pos, radius)
+                t1 = time.perf_counter()
+                soup_vertices = len(mc.mesh()["vertices"])
+                t2 = time.perf_counter()
+                mc.saveMesh(os.path.join(d, "soup.ply"), None, True)
+                t3 = time.perf_counter()
+                mc.extractIsoSurfaceIndexedChunkGrid(grid, pos, radius)
+                t4 = time.perf_counter()
+                stats = mc.indexed_stats()
+                t5 = time.perf_counter()
+                mc.saveMesh(os.path.join(d, "indexed.ply"), None, True)
+                t6 = time.perf_counter()
+                if rep > 0:
+                    for k, v in zip(walls, (t1 - t0, t3 - t2, t4 - t3, t6 - t5)):
+                        walls[k].append(v)
+    finally:
+        grid.close()
+    w = {k: float(np.median(v)) for k, v in walls.items()}
+    out.update(walk_pairs=len(walls["soup_walk_s"]), soup_walk_min_s=round(min(walls["soup_walk_s"]), 4), indexed_walk_min_s=round(min(walls["indexed_walk_s"]), 4))
+    n_soup = soup_vertices // 3
+    out.update(soup_walk_s=round(w["soup_walk_s"], 4), soup_merge_s=round(w["soup_save_s"] - w["indexed_save_s"], 4),
+               ply_write_s=round(w["indexed_save_s"], 4), indexed_walk_s=round(w["indexed_walk_s"], 4),
+               soup_route_s=round(w["soup_walk_s"] + w["soup_save_s"] - w["indexed_save_s"], 4),
+               soup_triangles=n_soup, download_bytes_soup=72 * n_soup,
+               download_bytes_indexed=24 * stats["vertices"] + 12 * stats["faces"], walk=stats)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="cfg2")
@@ -101,6 +216,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--indexed", action="store_true", help="measure the indexed extraction stage by stage instead")
+    ap.add_argument("--streamed", action="store_true", help="--indexed: the scene behind a chunk grid; soup walk + host merge against the indexed walk")
     args = ap.parse_args()
 
     import torch
@@ -117,6 +233,12 @@ def main():
     for pose in poses:
         E.synth_frame(spheres, inside, pose, cp, out=frame)
         scene.integrate(pose, frame, cp, None)
+    if args.indexed and args.streamed:
+        out = dict(metric="indexed mesh of a streamed scene: walls (s), per-append kernel times (us), download sizes (bytes)",
+                   config=dict(workload=f"{args.config} after {args.frames} frames of the S1 orbit, behind its chunk grid", voxel_size=hp.m_virtualVoxelSize))
+        out.update(streamed_report(args, scene, hp))
+        print(json.dumps(out))
+        return
     if args.indexed:
         out = dict(metric="indexed mesh: kernel times (us), download sizes (bytes) and the host merge (s)",
                    config=dict(workload=f"{args.config} after {args.frames} frames of the S1 orbit", voxel_size=hp.m_virtualVoxelSize))

@@ -39,7 +39,7 @@ def main():
     ap.add_argument("--rgbd-tracking", action="store_true", help="track with depth + colour (CUDACameraTrackingMultiResRGBD) instead of depth alone")
     ap.add_argument("--sens", nargs="*", default=None)
     ap.add_argument("--mesh", default=None)
-    ap.add_argument("--indexed-mesh", action="store_true", help="--mesh: weld the triangles on the device instead of merging them on the host (not with streaming)")
+    ap.add_argument("--indexed-mesh", action="store_true", help="--mesh: weld the triangles on the device instead of merging them on the host; with s_streamingEnabled the chunks' triangles are welded into one mesh as the chunk grid is walked")
     ap.add_argument("--record", default=None, help="write what was processed, with the poses used, to this .sens file")
     ap.add_argument("--max-frames", type=int, default=None)
     ap.add_argument("--render-to", default=None, help="renderToFile: the shaded model and the input of every frame as PNGs under this directory")
@@ -54,8 +54,6 @@ def main():
         raise SystemExit("needs a GPU (there is no CPU fallback)")
     from voxelhashing_amd import reconstruction as R
     g = R.read_app_state(args.params)
-    if args.indexed_mesh and g.s_streamingEnabled:
-        raise SystemExit("--indexed-mesh is not available with s_streamingEnabled (the chunk grid extracts per chunk)")
     if args.record:
         g.s_recordData = 1
     read = R.read_tracking_state_rgbd if args.rgbd_tracking else R.read_tracking_state
@@ -96,7 +94,7 @@ def main():
     if args.record:
         out["recorded"] = rec.saveRecordedFramesToFile(args.record)
     if args.mesh:
-        m = rec.extractIsoSurface(args.mesh, indexed=args.indexed_mesh)
+        m = rec.extractIsoSurfaceIndexed(args.mesh) if args.indexed_mesh else rec.extractIsoSurface(args.mesh)
         out["mesh"] = dict(file=args.mesh, indexed=bool(args.indexed_mesh), vertices=int(len(m["vertices"])), faces=int(len(m["faces"])))
     print(json.dumps(out))
 

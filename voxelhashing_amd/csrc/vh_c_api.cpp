@@ -378,6 +378,34 @@ int vh_marching_cubes_extract_iso_surface_indexed(VhMarchingCubes* mc, const VhH
     const vh::vec3f lo = minCorner ? toVec(minCorner) : vh::vec3f{ 0, 0, 0 }, hi = maxCorner ? toVec(maxCorner) : vh::vec3f{ 0, 0, 0 };
     return guarded([&] { mc->impl.extractIsoSurfaceIndexed(*hd, *hp, lo, hi, boxEnabled != 0); });
 }
+int vh_marching_cubes_begin_indexed(VhMarchingCubes* mc)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.beginIndexed(); });
+}
+int vh_marching_cubes_append_indexed(VhMarchingCubes* mc, const VhHashData* hd, const VhHashParams* hp, const float minCorner[3],
+                                     const float maxCorner[3], int boxEnabled)
+{
+    if (!mc || !hd || !hp) return VH_ERR_BAD_ARGUMENT;
+    const vh::vec3f lo = minCorner ? toVec(minCorner) : vh::vec3f{ 0, 0, 0 }, hi = maxCorner ? toVec(maxCorner) : vh::vec3f{ 0, 0, 0 };
+    return guarded([&] { mc->impl.appendIndexed(*hd, *hp, lo, hi, boxEnabled != 0); });
+}
+int vh_marching_cubes_finish_indexed(VhMarchingCubes* mc)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.finishIndexed(); });
+}
+int vh_marching_cubes_extract_iso_surface_indexed_chunk_grid(VhMarchingCubes* mc, VhChunkGrid* grid, const float camPos[3], float radius)
+{
+    if (!mc || !grid || !camPos) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.extractIsoSurfaceIndexed(grid->impl, toVec(camPos), radius); });
+}
+int vh_marching_cubes_get_indexed_stats(VhMarchingCubes* mc, uint32_t out[6])
+{
+    if (!mc || !out) return VH_ERR_BAD_ARGUMENT;
+    mc->impl.getIndexedStats(out);
+    return VH_OK;
+}
 int vh_marching_cubes_get_indexed_counts(VhMarchingCubes* mc, uint32_t out[3])
 {
     if (!mc || !out) return VH_ERR_BAD_ARGUMENT;

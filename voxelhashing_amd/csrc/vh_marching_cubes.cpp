@@ -295,9 +295,8 @@ void CUDAMarchingCubesHashSDF::extractIsoSurface(const HashData& hashData, const
 void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner,
                                                         const vh::vec3f& maxCorner, bool boxEnabled)
 {
-    clearMeshBuffer(); // nothing partial is left behind by an error
-    m_indexedCounts[0] = m_indexedCounts[1] = m_indexedCounts[2] = 0;
-    m_numSourced = 0;
+    resetIndexed(); // nothing partial is left behind by an error
+    m_indexedIsAccumulated = false;
     if (!d_sources) d_sources = vh::deviceAlloc<VhTriangleSource>(m_params.m_maxNumTriangles, "triangle sources");
     check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
     m_params.m_maxCorner[0] = maxCorner.x; m_params.m_maxCorner[1] = maxCorner.y; m_params.m_maxCorner[2] = maxCorner.z;
@@ -339,9 +338,142 @@ void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(const HashData& hashData
     m_welded = true;
 }
 
+void CUDAMarchingCubesHashSDF::AccumFree::operator()(VhMeshWeldAccum* a) const noexcept { vh_mesh_weld_accum_destroy(a); }
+
+void CUDAMarchingCubesHashSDF::resetIndexed()
+{
+    clearMeshBuffer();
+    m_indexedCounts[0] = m_indexedCounts[1] = m_indexedCounts[2] = 0;
+    for (unsigned int& v : m_indexedStats) v = 0;
+    m_numSourced = 0;
+}
+
+void CUDAMarchingCubesHashSDF::beginIndexed()
+{
+    resetIndexed();
+    m_indexedIsAccumulated = true;
+    if (!m_accum) {
+        VhMeshWeldAccum* a = nullptr;
+        check(vh_mesh_weld_accum_create(0, 0, 0, &a), "vh_mesh_weld_accum_create");
+        m_accum.reset(a);
+    }
+    check(vh_mesh_weld_accum_begin(m_accum.get(), m_stream), "vh_mesh_weld_accum_begin");
+}
+
+void CUDAMarchingCubesHashSDF::appendIndexed(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner,
+                                             const vh::vec3f& maxCorner, bool boxEnabled)
+{
+    if (!m_accum || !m_indexedIsAccumulated) throw vh::Error(VH_ERR_BAD_ARGUMENT, "appendIndexed: no beginIndexed");
+    try {
+        if (!d_sources) d_sources = vh::deviceAlloc<VhTriangleSource>(m_params.m_maxNumTriangles, "triangle sources");
+        check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
+        m_params.m_maxCorner[0] = maxCorner.x; m_params.m_maxCorner[1] = maxCorner.y; m_params.m_maxCorner[2] = maxCorner.z;
+        m_params.m_minCorner[0] = minCorner.x; m_params.m_minCorner[1] = minCorner.y; m_params.m_minCorner[2] = minCorner.z;
+        m_params.m_boxEnabled = boxEnabled ? 1u : 0u;
+        check(vh_marching_cubes_update_params(&m_data, &m_params, m_stream), "MarchingCubesData::updateParams");
+        check(vh_extract_iso_surface_pass1(&hashData, &hashParams, &m_data, m_stream), "extractIsoSurfacePass1CUDA");
+        check(vh_extract_iso_surface_pass2_sourced(&hashData, &hashParams, &m_data, d_sources.get(), getNumOccupiedBlocks(), m_stream),
+              "extractIsoSurfacePass2CUDA (sourced)");
+        const unsigned int nTriangles = getNumTriangles();
+        m_numSourced = std::min(nTriangles, m_params.m_maxNumTriangles);
+        if (nTriangles >= m_params.m_maxNumTriangles) // the test of copyTrianglesToCPU
+            throw vh::Error(VH_ERR_STAGING_OVERFLOW, "not enough memory to store triangles for chunk; increase s_marchingCubesMaxNumTriangles");
+        check(vh_mesh_weld_accum_append(m_accum.get(), m_data.d_triangles, d_sources.get(), nTriangles, m_stream), "vh_mesh_weld_accum_append");
+    } catch (...) {
+        const unsigned int sourced = m_numSourced;
+        resetIndexed();
+        m_numSourced = sourced;
+        m_indexedIsAccumulated = false; // the accumulation is over: finishIndexed wants a new beginIndexed
+        throw;
+    }
+}
+
+void CUDAMarchingCubesHashSDF::finishIndexed()
+{
+    if (!m_accum || !m_indexedIsAccumulated) throw vh::Error(VH_ERR_BAD_ARGUMENT, "finishIndexed: no beginIndexed");
+    clearMeshBuffer();
+    unsigned int stats[6] = { 0, 0, 0, 0, 0, 0 };
+    const int rc = vh_mesh_weld_accum_get_counts(m_accum.get(), stats, m_stream);
+    m_indexedCounts[0] = m_indexedCounts[1] = 0;
+    m_indexedCounts[2] = stats[VH_WELD_ACCUM_STATUS];
+    for (int i = 0; i < 6; i++) m_indexedStats[i] = 0;
+    m_indexedStats[VH_WELD_ACCUM_STATUS] = stats[VH_WELD_ACCUM_STATUS];
+    if (rc == VH_ERR_STAGING_OVERFLOW) throw vh::Error(rc, "mesh weld: the table is full");
+    if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "mesh weld: a voxel coordinate is outside the key range of +-2^19");
+    check(rc, "vh_mesh_weld_accum_get_counts");
+    const unsigned int nv = stats[VH_WELD_ACCUM_VERTICES], nf = stats[VH_WELD_ACCUM_FACES];
+    std::vector<VhVertex> verts(nv);
+    vh::MeshData md;
+    md.m_FaceIndicesVertices.resize(3 * (size_t)nf);
+    check(vh_mesh_weld_accum_download(m_accum.get(), verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_download");
+    md.m_Vertices.resize(nv);
+    md.m_Colors.resize(4 * (size_t)nv);
+    for (size_t i = 0; i < verts.size(); i++) {
+        md.m_Vertices[i] = { verts[i].p[0], verts[i].p[1], verts[i].p[2] };
+        md.m_Colors[4 * i + 0] = verts[i].c[0]; md.m_Colors[4 * i + 1] = verts[i].c[1]; md.m_Colors[4 * i + 2] = verts[i].c[2]; md.m_Colors[4 * i + 3] = 1.0f;
+    }
+    m_meshData = std::move(md);
+    m_indexedCounts[0] = nv; m_indexedCounts[1] = nf;
+    for (int i = 0; i < 6; i++) m_indexedStats[i] = stats[i];
+    m_welded = true;
+}
+
+// the walk of extractIsoSurface(chunkGrid, ...) below, box for box
+void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(CUDASceneRepChunkGrid& chunkGrid, const vh::vec3f& camPos, float radius)
+{
+    chunkGrid.stopMultiThreading();
+    const vh::vec3i minGridPos = chunkGrid.getMinGridPos(), maxGridPos = chunkGrid.getMaxGridPos();
+    bool walking = false;
+    try {
+        beginIndexed();
+        chunkGrid.streamOutToCPUAll();
+        walking = true;
+        for (int x = minGridPos.x; x < maxGridPos.x; x++)
+            for (int y = minGridPos.y; y < maxGridPos.y; y++)
+                for (int z = minGridPos.z; z < maxGridPos.z; z++) {
+                    const vh::vec3i chunk = { x, y, z };
+                    if (!chunkGrid.containsSDFBlocksChunk(chunk)) continue;
+                    chunkGrid.streamInToGPUChunkNeighborhood(chunk, 1);
+                    const vh::vec3f c = chunkGrid.getWorldPosChunk(chunk), e = chunkGrid.getVoxelExtends();
+                    const HashParams hp = chunkGrid.getHashParams();
+                    const float pad = hp.m_virtualVoxelSize * (float)hp.m_SDFBlockSize;
+                    const vh::vec3f minCorner = { c.x - e.x / 2.0f - pad, c.y - e.y / 2.0f - pad, c.z - e.z / 2.0f - pad };
+                    const vh::vec3f maxCorner = { c.x + e.x / 2.0f + pad, c.y + e.y / 2.0f + pad, c.z + e.z / 2.0f + pad };
+                    appendIndexed(chunkGrid.getHashData(), hp, minCorner, maxCorner, true);
+                    chunkGrid.streamOutToCPUAll();
+                }
+        walking = false;
+        unsigned int nStreamedBlocks = 0;
+        chunkGrid.streamInToGPUAll(camPos, radius, true, nStreamedBlocks);
+        chunkGrid.startMultiThreading();
+    } catch (...) {
+        // a chunk failed with its neighbourhood on the device: the scene goes back as the normal end puts it
+        resetIndexed();
+        m_indexedIsAccumulated = false;
+        if (walking) {
+            chunkGrid.streamOutToCPUAll();
+            unsigned int nStreamedBlocks = 0;
+            chunkGrid.streamInToGPUAll(camPos, radius, true, nStreamedBlocks);
+        }
+        chunkGrid.startMultiThreading();
+        throw;
+    }
+    try {
+        finishIndexed();
+    } catch (...) {
+        resetIndexed();
+        m_indexedIsAccumulated = false;
+        throw;
+    }
+}
+
 void CUDAMarchingCubesHashSDF::downloadIndexed(VhVertex* vertices, uint64_t* keys, uint32_t* faces)
 {
     if (m_indexedCounts[0] == 0 && m_indexedCounts[1] == 0) return;
+    if (m_indexedIsAccumulated) {
+        check(vh_mesh_weld_accum_download(m_accum.get(), vertices, keys, faces, m_indexedCounts[0], m_indexedCounts[1], m_stream), "vh_mesh_weld_accum_download");
+        return;
+    }
     if (!m_weldOwner) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexed: no indexed extraction");
     check(vh_mesh_weld_download(&m_weld, vertices, keys, faces, m_indexedCounts[0], m_indexedCounts[1], m_stream), "vh_mesh_weld_download");
 }

@@ -9,7 +9,9 @@
 // triangle).  Vertex and face order come from atomics, as the soup's does.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
+#include <memory>
 
 #include "vh_device.hpp"
 #include "vh_host_util.hpp"
@@ -136,6 +138,166 @@ __global__ __launch_bounds__(256) void k_weld_faces(uint32_t numTriangles, VhMes
     w.d_faces[3u * at] = a; w.d_faces[3u * at + 1u] = b; w.d_faces[3u * at + 2u] = c;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The accumulating weld (vh_mesh_weld_accum_*; DESIGN.md section 4, "Indexed mesh over several extractions"): one table
+// lives through several appends.  A slot is a key (a vertex key, or a cell key: bit 62), a value (the vertex's index,
+// or the ordinal of the append that owns the cell; all ones = none yet) and a bid word.  A bid is
+//   (VH_WELD_ACCUM_MAX_APPENDS - ordinal) << 35 | rank << 32 | soup vertex
+// so that atomicMin keeps the smallest (rank, soup vertex) of the LATEST append that bid: what earlier appends left in
+// the word never wins, and nothing has to be cleared between appends.  Three launches per append: insert (one lane
+// per triangle), settle (one lane per soup vertex), faces (one lane per triangle).
+
+struct WeldAccumView {
+    uint64_t* slotKeys;    // numSlots; all ones = empty
+    uint64_t* slotBids;    // numSlots
+    uint32_t* slotVals;    // numSlots
+    uint32_t* counts;      // VH_WELD_ACCUM_* (the rehash count is the host's)
+    uint32_t* vertexSlot;  // 3 n of this append: the slot of each soup vertex
+    VhVertex* vertices;    // one per welded vertex
+    uint64_t* keys;
+    uint8_t* ranks;        // the rank of the soup vertex whose bits the welded vertex has
+    uint32_t* faces;
+    uint32_t slotsLog2;
+};
+
+constexpr uint32_t kNoValue = 0xffffffffu;
+constexpr uint32_t kDroppedSlot = 0xfffffffeu; // in vertexSlot: the triangle's cell belongs to an earlier append
+
+// counts the lanes with `flag` into *counter: one atomic per wave.  Every lane of the wave calls it.
+VHD void wave_count(bool flag, uint32_t* counter)
+{
+    const uint64_t m = __ballot(flag);
+    if (m == 0ull) return;
+    if ((int)lane_id() == __ffsll((unsigned long long)m) - 1) atomicAdd(counter, (uint32_t)__popcll(m));
+}
+
+// the slot of `key`, claimed if the table does not have it; kNoSlot after numSlots steps without one
+VHD uint32_t accum_find_or_claim(unsigned long long* slotKeys, uint64_t key, uint32_t slotsLog2)
+{
+    const uint32_t numSlots = 1u << slotsLog2, mask = numSlots - 1u;
+    uint32_t slot = weld_home(key, mask);
+#pragma unroll 1
+    for (uint32_t step = 0; step < numSlots; step++) {
+        unsigned long long have = slotKeys[slot];
+        if (have == kMeshKeyEmpty) have = atomicCAS(&slotKeys[slot], (unsigned long long)kMeshKeyEmpty, (unsigned long long)key);
+        if (have == kMeshKeyEmpty || have == key) return slot;
+        slot = (slot + 1u) & mask;
+    }
+    return kNoSlot;
+}
+
+// One lane per triangle.  Claims the cell for this append (a cell an earlier append owns drops the triangle here,
+// before any of its keys is looked at), then for each of the three vertices the slot of its key, and bids for it.
+__global__ __launch_bounds__(256) void k_weld_accum_insert(const VhTriangleSource* sources, uint32_t numTriangles, WeldAccumView w, uint32_t ordinal)
+{
+    if (__builtin_amdgcn_readfirstlane((int)w.counts[VH_WELD_ACCUM_STATUS]) != 0) return; // an earlier append failed (wave-uniform)
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool valid = t < numTriangles;
+    unsigned long long* slotKeys = reinterpret_cast<unsigned long long*>(w.slotKeys);
+    uint64_t key[3] = { 0ull, 0ull, 0ull }, cellKey = 0ull;
+    uint32_t rank[3] = { 0u, 0u, 0u }, status = 0u;
+    if (valid) {
+        const VhTriangleSource src = sources[t];
+        bool ok = vh_mesh_cell_key(src.cell[0], src.cell[1], src.cell[2], &cellKey);
+#pragma unroll
+        for (uint32_t k = 0; k < 3u; k++) {
+            const uint32_t code = (src.edges >> (8u * k)) & 0xffu;
+            ok = ok && (code >> 6) == 0u && vh_mesh_key(src.cell[0], src.cell[1], src.cell[2], code & 0xfu, (code >> 4) & 3u, &key[k], &rank[k]);
+        }
+        if (!ok) status = VH_WELD_KEY_RANGE;
+    }
+    bool kept = false, first = false;
+    uint32_t slots[3] = { kNoSlot, kNoSlot, kNoSlot };
+    if (valid && status == 0u) {
+        const uint32_t cellSlot = accum_find_or_claim(slotKeys, cellKey, w.slotsLog2);
+        if (cellSlot == kNoSlot) status = VH_WELD_TABLE_FULL;
+        else {
+            const uint32_t owner = atomicCAS(&w.slotVals[cellSlot], kNoValue, ordinal);
+            first = owner == kNoValue;
+            kept = first || owner == ordinal;
+        }
+    }
+    if (kept) {
+        const uint64_t high = (uint64_t)(VH_WELD_ACCUM_MAX_APPENDS - ordinal) << 35;
+#pragma unroll 1
+        for (uint32_t k = 0; k < 3u; k++) {
+            const uint32_t slot = accum_find_or_claim(slotKeys, key[k], w.slotsLog2);
+            if (slot == kNoSlot) { status = VH_WELD_TABLE_FULL; break; }
+            atomicMin(reinterpret_cast<unsigned long long*>(&w.slotBids[slot]), (unsigned long long)(high | ((uint64_t)rank[k] << 32) | (3u * t + k)));
+            slots[k] = slot;
+        }
+    }
+    if (status != 0u) atomicOr(&w.counts[VH_WELD_ACCUM_STATUS], status);
+    if (valid) {
+        const bool dropped = status == 0u && !kept;
+#pragma unroll
+        for (uint32_t k = 0; k < 3u; k++) w.vertexSlot[3u * t + k] = dropped ? kDroppedSlot : slots[k];
+    }
+    wave_count(first, &w.counts[VH_WELD_ACCUM_CELLS]);
+}
+
+// One lane per soup vertex; only the lane whose bid stands in its slot acts.  A key without a vertex gets the next
+// index (one atomic per wave) and this soup vertex's bits; a key that has one keeps its index, and takes these bits
+// only if their rank is strictly smaller than the rank of the bits it has.  One lane per key acts and the appends
+// follow each other on the stream: nothing races.
+__global__ __launch_bounds__(256) void k_weld_accum_settle(const VhTriangle* triangles, uint32_t numVertices, WeldAccumView w, uint32_t ordinal)
+{
+    if (w.counts[VH_WELD_ACCUM_STATUS] != 0u) return; // written by the launch before this one: uniform
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t slot = i < numVertices ? w.vertexSlot[i] : kNoSlot;
+    bool mine = false;
+    uint32_t rank = 0u, index = kNoValue;
+    if (slot < kDroppedSlot) {
+        const uint64_t bid = w.slotBids[slot];
+        mine = (uint32_t)bid == i && (uint32_t)(bid >> 35) == VH_WELD_ACCUM_MAX_APPENDS - ordinal;
+        rank = (uint32_t)(bid >> 32) & 7u;
+        if (mine) index = w.slotVals[slot];
+    }
+    const bool fresh = mine && index == kNoValue;
+    const uint32_t at = wave_append(fresh, &w.counts[VH_WELD_ACCUM_VERTICES]);
+    if (!mine) return;
+    if (fresh) {
+        index = at;
+        w.slotVals[slot] = index;
+        w.keys[index] = w.slotKeys[slot];
+    } else if (rank >= (uint32_t)w.ranks[index]) return;
+    w.vertices[index] = reinterpret_cast<const VhVertex*>(triangles)[i];
+    w.ranks[index] = (uint8_t)rank;
+}
+
+// One lane per triangle: a dropped one is counted; the others look their three indices up and, unless two are the same,
+// go to the end of the one face list (one atomic per wave), winding kept.
+__global__ __launch_bounds__(256) void k_weld_accum_faces(uint32_t numTriangles, WeldAccumView w)
+{
+    if (w.counts[VH_WELD_ACCUM_STATUS] != 0u) return; // (as k_weld_accum_settle)
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t a = 0u, b = 0u, c = 0u;
+    bool dropped = false;
+    if (t < numTriangles) {
+        const uint32_t s0 = w.vertexSlot[3u * t], s1 = w.vertexSlot[3u * t + 1u], s2 = w.vertexSlot[3u * t + 2u];
+        dropped = s0 == kDroppedSlot;
+        if (!dropped) { a = w.slotVals[s0]; b = w.slotVals[s1]; c = w.slotVals[s2]; }
+    }
+    wave_count(dropped, &w.counts[VH_WELD_ACCUM_DROPPED]);
+    const bool keep = t < numTriangles && !dropped && a != b && b != c && a != c;
+    const uint32_t at = wave_append(keep, &w.counts[VH_WELD_ACCUM_FACES]);
+    if (!keep) return;
+    w.faces[3u * at] = a; w.faces[3u * at + 1u] = b; w.faces[3u * at + 2u] = c;
+}
+
+// One lane per slot of the old table: its key into the new, larger one (the keys are distinct, so the first empty slot
+// of the probe is the key's), its value with it.  Bids are not carried: the next append's are smaller than any.
+__global__ __launch_bounds__(256) void k_weld_rehash(const uint64_t* oldKeys, const uint32_t* oldVals, uint32_t oldSlotsLog2, WeldAccumView w)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= (1u << oldSlotsLog2)) return;
+    const uint64_t key = oldKeys[s];
+    if (key == kMeshKeyEmpty) return;
+    const uint32_t slot = accum_find_or_claim(reinterpret_cast<unsigned long long*>(w.slotKeys), key, w.slotsLog2);
+    if (slot == kNoSlot) atomicOr(&w.counts[VH_WELD_ACCUM_STATUS], VH_WELD_TABLE_FULL); // (a larger table always has room)
+    else w.slotVals[slot] = oldVals[s];
+}
+
 // the smallest power of two >= 6 n (twice the 3 n keys n triangles can have), 64 slots at least
 uint32_t defaultSlotsLog2(uint32_t n)
 {
@@ -242,6 +404,213 @@ int vh_mesh_weld_download(const VhMeshWeldData* data, VhVertex* vertices, uint64
     if (vertices && numVertices) VH_HIP(hipMemcpyAsync(vertices, data->d_vertices, sizeof(VhVertex) * (size_t)numVertices, hipMemcpyDeviceToHost, s));
     if (keys && numVertices) VH_HIP(hipMemcpyAsync(keys, data->d_keys, sizeof(uint64_t) * (size_t)numVertices, hipMemcpyDeviceToHost, s));
     if (faces && numFaces) VH_HIP(hipMemcpyAsync(faces, data->d_faces, sizeof(uint32_t) * 3 * (size_t)numFaces, hipMemcpyDeviceToHost, s));
+    VH_HIP(hipStreamSynchronize(s));
+    return VH_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the accumulating weld, host side
+
+struct VhMeshWeldAccum {
+    vh::DevicePtr<uint64_t> slotKeys, slotBids;
+    vh::DevicePtr<uint32_t> slotVals;
+    vh::DevicePtr<uint32_t> counts;     // VH_WELD_ACCUM_NUM_COUNTS words; the rehash count is m_rehashes
+    vh::DevicePtr<uint32_t> vertexSlot; // of the append in flight
+    vh::DevicePtr<VhVertex> vertices;
+    vh::DevicePtr<uint64_t> keys;
+    vh::DevicePtr<uint8_t> ranks;
+    vh::DevicePtr<uint32_t> faces;
+    size_t m_soupCapacity = 0, m_vertexCapacity = 0, m_faceCapacity = 0; // in soup vertices, welded vertices, faces
+    uint32_t m_slotsLog2 = 6, m_firstSlotsLog2 = 6;
+    bool m_fixed = false, m_begun = false;
+    uint32_t m_appends = 0, m_rehashes = 0;
+
+    WeldAccumView view() const
+    {
+        return WeldAccumView{ slotKeys.get(), slotBids.get(), slotVals.get(), counts.get(), vertexSlot.get(), vertices.get(), keys.get(), ranks.get(), faces.get(), m_slotsLog2 };
+    }
+};
+
+namespace {
+
+// errors of the owner types (vh::deviceAlloc throws) become codes, as at the handle level
+template <class F> int accumGuarded(F&& f)
+{
+    try {
+        return f();
+    } catch (const vh::Error& e) {
+        return e.code ? e.code : VH_ERR_BAD_ARGUMENT;
+    } catch (const std::exception&) {
+        return -(int)hipErrorOutOfMemory;
+    }
+}
+
+// a new, empty table of 1 << slotsLog2 slots; the one it replaces comes back in oldKeys / oldVals.  Nothing of `a`
+// changes when an allocation fails.
+int accumAllocTable(VhMeshWeldAccum& a, uint32_t slotsLog2, hipStream_t s, vh::DevicePtr<uint64_t>* oldKeys = nullptr, vh::DevicePtr<uint32_t>* oldVals = nullptr)
+{
+    const size_t numSlots = (size_t)1 << slotsLog2;
+    vh::DevicePtr<uint64_t> keys = vh::deviceAlloc<uint64_t>(numSlots, "weld table keys"), bids = vh::deviceAlloc<uint64_t>(numSlots, "weld table bids");
+    vh::DevicePtr<uint32_t> vals = vh::deviceAlloc<uint32_t>(numSlots, "weld table values");
+    VH_HIP(hipMemsetAsync(keys.get(), 0xff, sizeof(uint64_t) * numSlots, s));
+    VH_HIP(hipMemsetAsync(bids.get(), 0xff, sizeof(uint64_t) * numSlots, s));
+    VH_HIP(hipMemsetAsync(vals.get(), 0xff, sizeof(uint32_t) * numSlots, s));
+    VH_HIP(hipStreamSynchronize(s)); // nothing uses the old bid words any more when they go
+    a.slotKeys.swap(keys);
+    a.slotBids.swap(bids);
+    a.slotVals.swap(vals);
+    a.m_slotsLog2 = slotsLog2;
+    if (oldKeys) *oldKeys = std::move(keys);
+    if (oldVals) *oldVals = std::move(vals);
+    return VH_OK;
+}
+
+// a larger array with the first `used` elements of the old one; the stream is idle when the old one goes
+template <class T> int accumGrow(vh::DevicePtr<T>& p, size_t used, size_t capacity, const char* what, hipStream_t s)
+{
+    vh::DevicePtr<T> next = vh::deviceAlloc<T>(capacity, what);
+    if (used) VH_HIP(hipMemcpyAsync(next.get(), p.get(), sizeof(T) * used, hipMemcpyDeviceToDevice, s));
+    VH_HIP(hipStreamSynchronize(s));
+    p = std::move(next);
+    return VH_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int vh_mesh_weld_accum_create(uint32_t slotsLog2, uint32_t reserveTriangles, int fixed, VhMeshWeldAccum** out)
+{
+    if (!out) return VH_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    if (slotsLog2 == 0) slotsLog2 = 6;
+    if (slotsLog2 > 31 || reserveTriangles > 0x55555555u / 2u) return VH_ERR_BAD_ARGUMENT;
+    return accumGuarded([&]() -> int {
+        std::unique_ptr<VhMeshWeldAccum> a(new VhMeshWeldAccum);
+        a->m_fixed = fixed != 0;
+        a->m_firstSlotsLog2 = slotsLog2;
+        a->counts = vh::deviceAlloc<uint32_t>(8, "weld counts");
+        a->m_vertexCapacity = 3 * (size_t)reserveTriangles;
+        a->m_faceCapacity = reserveTriangles;
+        a->vertices = vh::deviceAlloc<VhVertex>(a->m_vertexCapacity, "welded vertices");
+        a->keys = vh::deviceAlloc<uint64_t>(a->m_vertexCapacity, "welded vertex keys");
+        a->ranks = vh::deviceAlloc<uint8_t>(a->m_vertexCapacity, "welded vertex ranks");
+        a->faces = vh::deviceAlloc<uint32_t>(3 * a->m_faceCapacity, "welded faces");
+        VH_TRY(accumAllocTable(*a, slotsLog2, nullptr));
+        VH_HIP(hipMemsetAsync(a->counts.get(), 0, sizeof(uint32_t) * 8, nullptr));
+        VH_HIP(hipStreamSynchronize(nullptr));
+        a->m_begun = true;
+        *out = a.release();
+        return VH_OK;
+    });
+}
+
+void vh_mesh_weld_accum_destroy(VhMeshWeldAccum* accum) { delete accum; }
+
+int vh_mesh_weld_accum_begin(VhMeshWeldAccum* accum, vhStream_t stream)
+{
+    if (!accum) return VH_ERR_BAD_ARGUMENT;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t numSlots = (size_t)1 << accum->m_slotsLog2;
+    VH_HIP(hipMemsetAsync(accum->counts.get(), 0, sizeof(uint32_t) * 8, s));
+    VH_HIP(hipMemsetAsync(accum->slotKeys.get(), 0xff, sizeof(uint64_t) * numSlots, s));
+    VH_HIP(hipMemsetAsync(accum->slotBids.get(), 0xff, sizeof(uint64_t) * numSlots, s));
+    VH_HIP(hipMemsetAsync(accum->slotVals.get(), 0xff, sizeof(uint32_t) * numSlots, s));
+    accum->m_appends = 0;
+    accum->m_rehashes = 0;
+    accum->m_begun = true;
+    return VH_OK;
+}
+
+int vh_mesh_weld_accum_append(VhMeshWeldAccum* accum, const VhTriangle* d_triangles, const VhTriangleSource* d_sources, uint32_t numTriangles,
+                              vhStream_t stream)
+{
+    if (!accum || !accum->m_begun) return VH_ERR_BAD_ARGUMENT;
+    if (numTriangles > 0x55555555u / 2u || (numTriangles != 0 && (!d_triangles || !d_sources))) return VH_ERR_BAD_ARGUMENT;
+    if (numTriangles == 0) return VH_OK; // nothing to take, and no launch with an empty grid
+    if (accum->m_appends >= VH_WELD_ACCUM_MAX_APPENDS - 1u) return VH_ERR_BAD_ARGUMENT;
+    hipStream_t s = (hipStream_t)stream;
+    return accumGuarded([&]() -> int {
+        VhMeshWeldAccum& a = *accum;
+        // what the appends before this one left: sizes the table and the arrays
+        uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
+        VH_HIP(hipMemcpyAsync(have, a.counts.get(), sizeof(uint32_t) * 5, hipMemcpyDeviceToHost, s));
+        VH_HIP(hipStreamSynchronize(s));
+        if (have[VH_WELD_ACCUM_STATUS] != 0u) return VH_OK; // the kernels would do nothing
+        const uint64_t n = numTriangles;
+        const uint64_t needKeys = (uint64_t)have[VH_WELD_ACCUM_VERTICES] + have[VH_WELD_ACCUM_CELLS] + 4ull * n;
+        if ((uint64_t)have[VH_WELD_ACCUM_VERTICES] + 3ull * n >= kDroppedSlot || (uint64_t)have[VH_WELD_ACCUM_FACES] + n > 0x55555555ull)
+            return VH_ERR_BAD_ARGUMENT; // vertex indices and face offsets are 32 bits
+        if (!a.m_fixed) {
+            uint32_t l = a.m_slotsLog2;
+            while (l < 31u && (1ull << l) < 2ull * needKeys) l++;
+            if ((1ull << l) < 2ull * needKeys) return VH_ERR_BAD_ARGUMENT;
+            if (l != a.m_slotsLog2) {
+                vh::DevicePtr<uint64_t> oldKeys;
+                vh::DevicePtr<uint32_t> oldVals;
+                const uint32_t oldLog2 = a.m_slotsLog2;
+                VH_TRY(accumAllocTable(a, l, s, &oldKeys, &oldVals));
+                if (have[VH_WELD_ACCUM_VERTICES] + have[VH_WELD_ACCUM_CELLS] != 0u) {
+                    k_weld_rehash<<<cdiv((size_t)1 << oldLog2, 256), 256, 0, s>>>(oldKeys.get(), oldVals.get(), oldLog2, a.view());
+                    VH_TRY(vh_last_launch_error());
+                }
+                VH_HIP(hipStreamSynchronize(s)); // the old table goes at the end of this block
+                a.m_rehashes += l - oldLog2;
+            }
+        }
+        const size_t needVertices = (size_t)have[VH_WELD_ACCUM_VERTICES] + 3 * (size_t)n, needFaces = (size_t)have[VH_WELD_ACCUM_FACES] + (size_t)n;
+        if (needVertices > a.m_vertexCapacity) {
+            const size_t cap = std::max(needVertices, 2 * a.m_vertexCapacity), used = have[VH_WELD_ACCUM_VERTICES];
+            VH_TRY(accumGrow(a.vertices, used, cap, "welded vertices", s));
+            VH_TRY(accumGrow(a.keys, used, cap, "welded vertex keys", s));
+            VH_TRY(accumGrow(a.ranks, used, cap, "welded vertex ranks", s));
+            a.m_vertexCapacity = cap;
+        }
+        if (needFaces > a.m_faceCapacity) {
+            const size_t cap = std::max(needFaces, 2 * a.m_faceCapacity);
+            VH_TRY(accumGrow(a.faces, 3 * (size_t)have[VH_WELD_ACCUM_FACES], 3 * cap, "welded faces", s));
+            a.m_faceCapacity = cap;
+        }
+        if (3 * (size_t)n > a.m_soupCapacity) {
+            VH_HIP(hipStreamSynchronize(s));
+            a.vertexSlot = vh::deviceAlloc<uint32_t>(3 * (size_t)n, "weld vertex slots");
+            a.m_soupCapacity = 3 * (size_t)n;
+        }
+        const uint32_t ordinal = ++a.m_appends; // 1 ..: all ones in a cell's value means no owner
+        const WeldAccumView w = a.view();
+        VH_LAUNCH_TIMED(k_weld_accum_insert, cdiv(n, 256), 256, s, d_sources, numTriangles, w, ordinal);
+        VH_TRY(vh_last_launch_error());
+        VH_LAUNCH_TIMED(k_weld_accum_settle, cdiv(3ull * n, 256), 256, s, d_triangles, 3u * numTriangles, w, ordinal);
+        VH_TRY(vh_last_launch_error());
+        VH_LAUNCH_TIMED(k_weld_accum_faces, cdiv(n, 256), 256, s, numTriangles, w);
+        return vh_last_launch_error();
+    });
+}
+
+int vh_mesh_weld_accum_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream)
+{
+    if (!accum || !out) return VH_ERR_BAD_ARGUMENT;
+    VH_HIP(hipMemcpyAsync(out, accum->counts.get(), sizeof(uint32_t) * 5, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    VH_HIP(hipStreamSynchronize((hipStream_t)stream));
+    out[VH_WELD_ACCUM_REHASHES] = accum->m_rehashes;
+    if (out[VH_WELD_ACCUM_STATUS] != 0u)
+        out[VH_WELD_ACCUM_VERTICES] = out[VH_WELD_ACCUM_FACES] = out[VH_WELD_ACCUM_CELLS] = out[VH_WELD_ACCUM_DROPPED] = 0u; // nothing of it is a mesh
+    if (out[VH_WELD_ACCUM_STATUS] & VH_WELD_KEY_RANGE) return VH_ERR_BAD_ARGUMENT;
+    if (out[VH_WELD_ACCUM_STATUS] & VH_WELD_TABLE_FULL) return VH_ERR_STAGING_OVERFLOW;
+    return VH_OK;
+}
+
+int vh_mesh_weld_accum_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint64_t* keys, uint32_t* faces, uint32_t numVertices,
+                                uint32_t numFaces, vhStream_t stream)
+{
+    if (!accum) return VH_ERR_BAD_ARGUMENT;
+    if (numVertices > accum->m_vertexCapacity || numFaces > accum->m_faceCapacity) return VH_ERR_BAD_ARGUMENT;
+    hipStream_t s = (hipStream_t)stream;
+    if (vertices && numVertices) VH_HIP(hipMemcpyAsync(vertices, accum->vertices.get(), sizeof(VhVertex) * (size_t)numVertices, hipMemcpyDeviceToHost, s));
+    if (keys && numVertices) VH_HIP(hipMemcpyAsync(keys, accum->keys.get(), sizeof(uint64_t) * (size_t)numVertices, hipMemcpyDeviceToHost, s));
+    if (faces && numFaces) VH_HIP(hipMemcpyAsync(faces, accum->faces.get(), sizeof(uint32_t) * 3 * (size_t)numFaces, hipMemcpyDeviceToHost, s));
     VH_HIP(hipStreamSynchronize(s));
     return VH_OK;
 }

@@ -42,3 +42,15 @@ VH_KEY_FN bool vh_mesh_key(int32_t cx, int32_t cy, int32_t cz, uint32_t edge, ui
     *rank = 7u - corner;
     return true;
 }
+
+// The key of a cell in the table of the accumulating weld (vh_mesh_weld_accum_*), which remembers the cells it has
+// taken beside the vertex keys: the cell's voxel coordinates packed as a vertex key's lattice point, and bit 62 set,
+// which no vertex key has.  Bit 63 stays 0, so the all-ones word is still no key.
+constexpr uint64_t kMeshKeyCell = 1ull << 62;
+// -> false when a coordinate is outside [-2^19, 2^19)
+VH_KEY_FN bool vh_mesh_cell_key(int32_t cx, int32_t cy, int32_t cz, uint64_t* key)
+{
+    if (cx < -kMeshKeyBias || cx >= kMeshKeyBias || cy < -kMeshKeyBias || cy >= kMeshKeyBias || cz < -kMeshKeyBias || cz >= kMeshKeyBias) return false;
+    *key = (uint64_t)(cx + kMeshKeyBias) | ((uint64_t)(cy + kMeshKeyBias) << 20) | ((uint64_t)(cz + kMeshKeyBias) << 40) | kMeshKeyCell;
+    return true;
+}

@@ -760,6 +760,33 @@ class CUDAMarchingCubesHashSDF:
         check(self.L.vh_marching_cubes_extract_iso_surface_indexed(self.handle, C.byref(hashData), C.byref(hashParams), f16(minCorner),
                                                                    f16(maxCorner), int(boxEnabled)), "extractIsoSurfaceIndexed")
 
+    def beginIndexed(self):
+        """starts an indexed extraction that is made box by box: appendIndexed any number of times, then finishIndexed"""
+        check(self.L.vh_marching_cubes_begin_indexed(self.handle), "beginIndexed")
+
+    def appendIndexed(self, hashData, hashParams, minCorner=(0, 0, 0), maxCorner=(0, 0, 0), boxEnabled=False):
+        """one extraction in a box, appended to the accumulation; boxes may overlap: a cell is taken from the first box
+        that has it"""
+        check(self.L.vh_marching_cubes_append_indexed(self.handle, C.byref(hashData), C.byref(hashParams), f16(minCorner), f16(maxCorner),
+                                                      int(boxEnabled)), "appendIndexed")
+
+    def finishIndexed(self):
+        """downloads the accumulated mesh and REPLACES the mesh buffer with it, as extractIsoSurfaceIndexed does"""
+        check(self.L.vh_marching_cubes_finish_indexed(self.handle), "finishIndexed")
+
+    def extractIsoSurfaceIndexedChunkGrid(self, chunkGrid, camPos, radius):
+        """the walk of extractIsoSurfaceChunkGrid with every chunk appended to one accumulation: the indexed mesh of a
+        streamed scene"""
+        check(self.L.vh_marching_cubes_extract_iso_surface_indexed_chunk_grid(self.handle, chunkGrid.handle, f16(camPos), radius),
+              "extractIsoSurfaceIndexed(chunkGrid)")
+
+    def indexed_stats(self):
+        """of the last accumulated extraction: vertices, faces, status, cells, dropped (triangles of cells an earlier
+        append had), rehashes (doublings of the table); all 0 after a one-shot extraction"""
+        out = (C.c_uint32 * 6)()
+        check(self.L.vh_marching_cubes_get_indexed_stats(self.handle, out), "get_indexed_stats")
+        return {k: int(out[i]) for i, k in enumerate(T.WELD_ACCUM_COUNTS)}
+
     def indexed_counts(self):
         out = (C.c_uint32 * 3)()
         check(self.L.vh_marching_cubes_get_indexed_counts(self.handle, out), "get_indexed_counts")
@@ -852,6 +879,42 @@ def mesh_weld(triangles, sources, slots_log2=0, raise_on_status=True, stream=Non
         d_srcs.free()
     return dict(vertices=np.ascontiguousarray(v["p"]), colors=np.ascontiguousarray(v["c"]), keys=k, faces=f,
                 counts=(int(counts[0]), int(counts[1])), status=int(counts[2]), code=int(code), slots_log2=slots)
+
+
+def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, raise_on_status=True, stream=None):
+    """vh_mesh_weld_accum_* on hand-made input: parts is a sequence of (soup, records), appended in order to one
+    accumulation -> vertices, colors, keys, faces as mesh_weld(), counts (vertices, faces), stats (the six counts by
+    name), status and code.  slots_log2 is the table's FIRST size (0: the smallest), reserve_triangles that of the
+    vertex and face arrays; fixed keeps the table from growing.  Errors as mesh_weld()."""
+    L = load()
+    h = C.c_void_p()
+    check(L.vh_mesh_weld_accum_create(slots_log2, reserve_triangles, int(fixed), C.byref(h)), "vh_mesh_weld_accum_create")
+    buffers = []
+    try:
+        check(L.vh_mesh_weld_accum_begin(h, stream), "vh_mesh_weld_accum_begin")
+        for triangles, sources in parts:
+            tris = np.ascontiguousarray(triangles, dtype=T.TRIANGLE_DTYPE).ravel()
+            srcs = np.ascontiguousarray(sources, dtype=T.TRIANGLE_SOURCE_DTYPE).ravel()
+            if len(tris) != len(srcs):
+                raise ValueError("one source record per triangle")
+            d_tris, d_srcs = DeviceBuffer.from_numpy(tris, stream), DeviceBuffer.from_numpy(srcs, stream)
+            buffers += [d_tris, d_srcs]
+            check(L.vh_mesh_weld_accum_append(h, d_tris.ptr, d_srcs.ptr, len(tris), stream), "vh_mesh_weld_accum_append")
+        counts = (C.c_uint32 * 6)()
+        code = L.vh_mesh_weld_accum_get_counts(h, counts, stream)
+        if code < 0 or (code != 0 and (raise_on_status or counts[2] == 0)):
+            check(code, "vh_mesh_weld_accum")
+        v = np.zeros(int(counts[0]), dtype=T.VERTEX_DTYPE)
+        k = np.zeros(int(counts[0]), dtype=np.uint64)
+        f = np.zeros((int(counts[1]), 3), dtype=np.uint32)
+        check(L.vh_mesh_weld_accum_download(h, v.ctypes.data, k.ctypes.data, f.ctypes.data, len(v), len(f), stream), "vh_mesh_weld_accum_download")
+    finally:
+        L.vh_mesh_weld_accum_destroy(h)
+        for b in buffers:
+            b.free()
+    return dict(vertices=np.ascontiguousarray(v["p"]), colors=np.ascontiguousarray(v["c"]), keys=k, faces=f,
+                counts=(int(counts[0]), int(counts[1])), stats={n: int(counts[i]) for i, n in enumerate(T.WELD_ACCUM_COUNTS)},
+                status=int(counts[2]), code=int(code))
 
 
 # ---- sensor pre-processing (DSC/CameraUtil.cu) over the C ABI: numpy in, numpy out (tests, tools) ----

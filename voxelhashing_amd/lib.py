@@ -232,6 +232,17 @@ PROTOTYPES = {
     "vh_mesh_weld": (C.c_int, [_VP, _VP, C.c_uint32, P(T.MeshWeldData), C.c_uint32, _VP]),
     "vh_mesh_weld_get_counts": (C.c_int, [P(T.MeshWeldData), P(C.c_uint32), _VP]),
     "vh_mesh_weld_download": (C.c_int, [P(T.MeshWeldData), _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP]),
+    "vh_mesh_weld_accum_create": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, P(_VP)]),
+    "vh_mesh_weld_accum_destroy": (None, [_VP]),
+    "vh_mesh_weld_accum_begin": (C.c_int, [_VP, _VP]),
+    "vh_mesh_weld_accum_append": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP]),
+    "vh_mesh_weld_accum_get_counts": (C.c_int, [_VP, P(C.c_uint32), _VP]),
+    "vh_mesh_weld_accum_download": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP]),
+    "vh_marching_cubes_begin_indexed": (C.c_int, [_VP]),
+    "vh_marching_cubes_append_indexed": (C.c_int, [_VP, P(T.HashData), P(T.HashParams), P(C.c_float), P(C.c_float), C.c_int]),
+    "vh_marching_cubes_finish_indexed": (C.c_int, [_VP]),
+    "vh_marching_cubes_extract_iso_surface_indexed_chunk_grid": (C.c_int, [_VP, _VP, P(C.c_float), C.c_float]),
+    "vh_marching_cubes_get_indexed_stats": (C.c_int, [_VP, P(C.c_uint32)]),
     "vh_marching_cubes_extract_iso_surface_indexed": (C.c_int, [_VP, P(T.HashData), P(T.HashParams), P(C.c_float), P(C.c_float), C.c_int]),
     "vh_marching_cubes_get_indexed_counts": (C.c_int, [_VP, P(C.c_uint32)]),
     "vh_marching_cubes_download_indexed": (C.c_int, [_VP, _VP, _VP, _VP]),

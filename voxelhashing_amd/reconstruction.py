@@ -576,8 +576,9 @@ class Reconstruction:
     def extractIsoSurface(self, filename=None, indexed=False):
         """StopScanningAndExtractIsoSurfaceMC: marching cubes over the whole scene (through the chunk grid when
         streaming is on) -> (vertices, colours, faces); written as a PLY when a file name is given.  indexed (not in the
-        reference): weld the triangles on the device instead of merging them on the host; the chunk-grid extraction
-        has no such path (its boxes overlap), so with streaming on this is refused before any GPU work."""
+        reference): weld the triangles on the device instead of merging them on the host.  With streaming on that is
+        refused here before any GPU work: extractIsoSurfaceIndexed() is the indexed extraction that also walks the
+        chunk grid."""
         if indexed and self.chunk_grid is not None:
             raise ValueError("indexed extraction is not available with streaming enabled (the chunk grid extracts per chunk)")
         if self.marching_cubes is None:
@@ -597,4 +598,23 @@ class Reconstruction:
         mesh = mc.mesh()
         if filename:
             mc.saveMesh(filename, None, True)  # merges close vertices, writes the PLY and clears the buffer (.cpp:126-144)
+        return mesh
+
+    def extractIsoSurfaceIndexed(self, filename=None):
+        """The indexed extraction with and without streaming (not in the reference): marching cubes with the triangles
+        welded on the device -> (vertices, colours, faces); written as a PLY when a file name is given.  Without
+        streaming this is extractIsoSurface(indexed=True); with streaming it walks the chunk grid as extractIsoSurface()
+        does and welds every chunk's triangles into one mesh (the overlap of the chunks' boxes is taken once), so
+        nothing is merged on the host.  marching_cubes.indexed() has the mesh with its keys, indexed_stats() the counts."""
+        if self.chunk_grid is None:
+            return self.extractIsoSurface(filename, indexed=True)
+        if self.marching_cubes is None:
+            self.marching_cubes = E.CUDAMarchingCubesHashSDF(self.mp)
+            self.marching_cubes.setOfflineProcessing(bool(self.gas.s_offlineProcessing))
+        mc = self.marching_cubes
+        pos = (self.scene.getLastRigidTransform().reshape(4, 4) @ np.array(list(self.gas.s_streamingPos) + [1.0], dtype=np.float32))[:3]
+        mc.extractIsoSurfaceIndexedChunkGrid(self.chunk_grid, pos, self.gas.s_streamingRadius)
+        mesh = mc.mesh()
+        if filename:
+            mc.saveMesh(filename, None, True)  # the mesh is welded: written as it is, and the buffer cleared
         return mesh
