@@ -690,7 +690,9 @@ struct MeshData {
     std::vector<vec3f> m_Vertices;
     std::vector<float> m_Colors;                      // 4 per vertex
     std::vector<unsigned int> m_FaceIndicesVertices;  // 3 per face; empty = triangle soup (face i = 3i, 3i+1, 3i+2)
-    void clear() { m_Vertices.clear(); m_Colors.clear(); m_FaceIndicesVertices.clear(); }
+    std::vector<float> m_Normals;                     // 3 per vertex, or none (the indexed extraction with setIndexedNormals)
+    void clear() { m_Vertices.clear(); m_Colors.clear(); m_FaceIndicesVertices.clear(); m_Normals.clear(); }
+    bool hasNormals() const { return !m_Vertices.empty() && m_Normals.size() == 3 * m_Vertices.size(); }
     bool hasVertexIndices() const { return !m_FaceIndicesVertices.empty(); }
     void makeTriangleSoupIndices();
     // MeshData::mergeCloseVertices(thresh, approx = true) / removeDuplicateFaces() / merge() / applyTransform() of the
@@ -698,8 +700,11 @@ struct MeshData {
     void mergeCloseVertices(float thresh);
     void removeDuplicateFaces();
     void merge(const MeshData& other);
+    // normals go by the cofactor matrix of the upper-left 3x3 times the sign of its determinant, renormalised in double
+    // (mLib's own rule divides them by a w that holds the translation: DESIGN.md, fenced reference defects)
     void applyTransform(const mat4f& t);
-    void saveToPLY(const std::string& filename) const; // binary little endian, x y z red green blue alpha + faces
+    // binary little endian, x y z [nx ny nz] red green blue alpha + faces (MLIB/core-mesh/meshIO.cpp:485-556)
+    void saveToPLY(const std::string& filename) const;
 };
 } // namespace vh
 
@@ -714,7 +719,7 @@ public:
     static MarchingCubesParams parameters(unsigned int marchingCubesMaxNumTriangles, float SDFMarchingCubeThreshFactor,
                                           float SDFVoxelSize, unsigned int hashNumBuckets);
 
-    void clearMeshBuffer() { m_meshData.clear(); m_welded = false; }
+    void clearMeshBuffer() { m_meshData.clear(); m_welded = false; } // (MeshData::clear takes the normals with it)
     // copies the result of the last extraction to the host and appends it to the mesh (.cpp:31-86); throws when the
     // triangle buffer overflowed.  offlineProcessing (GlobalAppState::s_offlineProcessing): merge each batch first.
     void copyTrianglesToCPU();
@@ -754,6 +759,12 @@ public:
     bool isWelded() const { return m_welded; }
     void getIndexedCounts(unsigned int out[3]) const { out[0] = m_indexedCounts[0]; out[1] = m_indexedCounts[1]; out[2] = m_indexedCounts[2]; }
     void downloadIndexed(VhVertex* vertices, uint64_t* keys, uint32_t* faces); // device mesh of the last indexed extraction
+    // Vertex normals of the indexed mesh ("Vertex normals"), off by default.  When on, the three
+    // indexed extractions run vh_mesh_vertex_normals after the weld -- finishIndexed over the whole accumulation -- with
+    // the default scale of hashParams' voxel size, and put them into the mesh buffer's m_Normals, which saveMesh
+    // writes.  A status of the pass throws VH_ERR_BAD_ARGUMENT and leaves the buffer empty.
+    void setIndexedNormals(bool on) { m_indexedNormals = on; }
+    void downloadIndexedNormals(float* normals); // 3 per vertex, in downloadIndexed's order; throws if that extraction had none
     void downloadSources(VhTriangleSource* out, unsigned int n);               // source records of the last indexed extraction
 
     const vh::MeshData& getMeshData() const { return m_meshData; }
@@ -784,6 +795,14 @@ private:
     bool m_indexedIsAccumulated = false;           // downloadIndexed reads m_accum, not m_weld
     unsigned int m_indexedStats[6] = { 0, 0, 0, 0, 0, 0 };
     void resetIndexed();                           // empty buffer, zero counts: the state an error leaves
+    // vertex normals: the buffers of the one-shot extraction are made by its first call with the option on
+    bool m_indexedNormals = false;
+    bool m_indexedHasNormals = false;              // the last indexed extraction computed them
+    float m_indexedVoxelSize = 0.0f;               // of the last appendIndexed: finishIndexed's scale
+    vh::DevicePtr<int64_t> d_normalAcc;
+    vh::DevicePtr<float> d_normals;
+    vh::DevicePtr<uint32_t> d_normalStatus;
+    size_t m_normalsCapacity = 0;                  // vertices
 };
 
 

@@ -55,7 +55,7 @@ int vh_memset(void* dst, int value, size_t bytes, vhStream_t stream);
 int vh_time_next_launch(void* startEvent, void* stopEvent);
 /* the same for an entry point that launches several kernels: `skip` of the calling thread's timed launches pass first.
  * vh_extract_iso_surface_pass2[_sourced] launch one kernel; vh_mesh_weld launches insert, number, faces (skip 0, 1, 2),
- * vh_mesh_weld_accum_append insert, settle, faces. */
+ * vh_mesh_weld_accum_append insert, settle, faces; vh_mesh_vertex_normals and vh_mesh_weld_accum_normals faces, finish. */
 int vh_time_launch_after(uint32_t skip, void* startEvent, void* stopEvent);
 int vh_stream_create(vhStream_t* out);   /* a non-blocking HIP stream, for FFI users without a HIP binding */
 int vh_stream_destroy(vhStream_t stream);
@@ -718,6 +718,31 @@ int vh_mesh_weld_get_counts(const VhMeshWeldData* data, uint32_t out[3], vhStrea
 int vh_mesh_weld_download(const VhMeshWeldData* data, VhVertex* vertices, uint64_t* keys, uint32_t* faces, uint32_t numVertices,
                           uint32_t numFaces, vhStream_t stream);
 
+/* ---- vertex normals of an indexed mesh (csrc/vh_mesh.hip; DESIGN.md section 4, "Vertex normals"): area-weighted, summed
+ * per vertex in 64-bit fixed point, so that the result does not depend on the order of the faces, of the indices within
+ * a face, or of the atomics.  Per face (one with a repeated index is skipped), rotated so that the vertex with the
+ * smallest key comes first: a = p1 - p0, b = p2 - p0, c = a x b in float32 with one rounding per operation,
+ * q = rint(c * 2^scaleLog2) added to the accumulators of the face's three vertices.  Per vertex: the sums as doubles,
+ * normalised in double with correctly rounded sqrt and division, rounded to float; a zero sum gives (0, 0, 0).
+ *   d_vertices, d_keys   numVertices of each        d_faces   numFaces index triples
+ *   scaleLog2            in [-100, 100]; vh_mesh_normals_default_scale_log2 gives the one for a marching-cubes mesh
+ *   d_acc                3 int64 per vertex (scratch; zeroed here)      d_normals   3 float per vertex
+ *   d_status             one word: 0, or VH_NORMALS_RANGE | VH_NORMALS_BAD_INDEX, and then every normal is (0, 0, 0)
+ * Asynchronous on `stream`: two memsets, k_mesh_normals_faces (not launched when numFaces is 0), k_mesh_normals_finish
+ * (vh_time_launch_after skip 0, 1); numVertices = 0 launches nothing.  Callers map a status to VH_ERR_BAD_ARGUMENT. */
+int vh_mesh_vertex_normals(const VhVertex* d_vertices, const uint64_t* d_keys, const uint32_t* d_faces, uint32_t numVertices, uint32_t numFaces,
+                           int32_t scaleLog2, int64_t* d_acc, float* d_normals, uint32_t* d_status, vhStream_t stream);
+/* 38 - ceil(log2(v)), v the double product of voxelSize with itself: a marching-cubes triangle lies in one cell, so
+ * |a x b| <= 3 voxelSize^2 and the scaled components stay below 2^40.  VH_ERR_BAD_ARGUMENT for a voxel size that is
+ * not finite or not positive. */
+int vh_mesh_normals_default_scale_log2(float voxelSize, int32_t* scaleLog2);
+/* Host only: vh::MeshData::applyTransform (when transform is not NULL) and saveToPLY on the caller's arrays.
+ *   vertices3, colors4 (may be NULL), normals3 (may be NULL)   numVertices rows each
+ *   faceIndices   numFaceIndices = 3 per face; 0 = a triangle soup
+ * With normals the file has nx, ny, nz between z and red, and 28-byte vertex records. */
+int vh_mesh_save_ply(const float* vertices3, const float* colors4, const float* normals3, uint64_t numVertices, const uint32_t* faceIndices,
+                     uint64_t numFaceIndices, const float transform[16], const char* filename);
+
 /* ---- the accumulating weld: one indexed mesh out of several soups (csrc/vh_mesh.hip; DESIGN.md section 4, "Indexed
  * mesh over several extractions").  begin, then any number of appends, then get_counts / download.
  *   - a cell (VhTriangleSource::cell) belongs to the first append it occurs in: its triangles in a later append are
@@ -749,6 +774,15 @@ int vh_mesh_weld_accum_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStr
 /* as vh_mesh_weld_download */
 int vh_mesh_weld_accum_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint64_t* keys, uint32_t* faces, uint32_t numVertices,
                                 uint32_t numFaces, vhStream_t stream);
+
+/* Vertex normals of the accumulated mesh (vh_mesh_vertex_normals over ALL its faces with the vertex bits the appends
+ * left: a pass at the end, never per append).  Waits for the appends, then launches and returns; the buffers are the
+ * accumulator's own (36 B per welded vertex more).  A weld that failed returns its error here. */
+int vh_mesh_weld_accum_normals(VhMeshWeldAccum* accum, int32_t scaleLog2, vhStream_t stream);
+/* Waits and copies 3 floats per vertex.  VH_ERR_BAD_ARGUMENT when no pass has run since the last begin or append (its
+ * result would be stale), when numVertices exceeds what the pass saw, or when the pass left a status (the normals are
+ * then all zero). */
+int vh_mesh_weld_accum_download_normals(VhMeshWeldAccum* accum, float* normals, uint32_t numVertices, vhStream_t stream);
 
 /* handle level: CUDAMarchingCubesHashSDF (DSC/CUDAMarchingCubesHashSDF.h:8-67) */
 typedef struct VhMarchingCubes VhMarchingCubes;
@@ -791,6 +825,16 @@ int vh_marching_cubes_get_indexed_counts(VhMarchingCubes* mc, uint32_t out[3]);
 /* the device mesh of the last indexed extraction; each of vertices (position + colour), keys and faces may be NULL.
  * The arrays hold what vh_marching_cubes_get_indexed_counts reports. */
 int vh_marching_cubes_download_indexed(VhMarchingCubes* mc, VhVertex* vertices, uint64_t* keys, uint32_t* faces);
+/* Vertex normals for the indexed extractions (off by default): when on, the three indexed extractions run
+ * vh_mesh_vertex_normals after the weld with the default scale of hp's voxel size, the host mesh holds them, and
+ * save_mesh writes them.  A status of the pass: VH_ERR_BAD_ARGUMENT, the host mesh empty. */
+int vh_marching_cubes_set_indexed_normals(VhMarchingCubes* mc, int enabled);
+/* 3 floats per vertex of the last indexed extraction, in the order of vh_marching_cubes_download_indexed;
+ * VH_ERR_BAD_ARGUMENT when that extraction ran without normals */
+int vh_marching_cubes_download_indexed_normals(VhMarchingCubes* mc, float* normals);
+/* the host mesh's normals: out = number of floats (3 per vertex, or 0), then the array */
+int vh_marching_cubes_get_mesh_normals_size(VhMarchingCubes* mc, uint64_t* out);
+int vh_marching_cubes_get_mesh_normals(VhMarchingCubes* mc, float* normals3);
 /* the first n source records of the last indexed extraction (n <= min(triangles produced, m_maxNumTriangles)) */
 int vh_marching_cubes_download_sources(VhMarchingCubes* mc, VhTriangleSource* out, uint32_t n);
 int vh_marching_cubes_copy_triangles_to_cpu(VhMarchingCubes* mc);

@@ -222,6 +222,10 @@ typedef struct VhTriangleSource {
 #define VH_WELD_TABLE_FULL 1u /* a vertex found no slot: the table has fewer slots than there are distinct keys */
 #define VH_WELD_KEY_RANGE 2u  /* a lattice coordinate outside [-2^19, 2^19), or a malformed source record */
 
+/* status word of the vertex-normal pass (vh_mesh_vertex_normals); either bit leaves every normal (0, 0, 0) */
+#define VH_NORMALS_RANGE 1u     /* a scaled face normal is not finite or exceeds 2^40 in a component: scaleLog2 is too large */
+#define VH_NORMALS_BAD_INDEX 2u /* a face index >= numVertices (nothing was read through it) */
+
 /* Device buffers of the weld (vh_mesh_weld): an open-addressing table of numSlots = 1 << m_slotsLog2 slots, and the
  * indexed mesh it produces.  Sized for m_maxTriangles triangles, that is 3 * m_maxTriangles vertices at worst. */
 typedef struct VhMeshWeldData {

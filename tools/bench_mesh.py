@@ -19,6 +19,13 @@ walk (extractIsoSurface(chunkGrid)) and of saveMesh's merge of that soup, the wa
 the resident scene -- each append's three kernels by vh_time_launch_after (one accumulation per kernel; --reps of them).
 
     python tools/bench_mesh.py --indexed --streamed [--config cfg3] [--frames 100] [--reps 5]
+
+--normals (with --indexed, also with --streamed) adds the vertex-normal pass ("Vertex normals"): the
+two kernels' own durations over the welded mesh (over the finished accumulation with --streamed), the bytes the normals
+add to the download, and the wall time of the extraction (of the indexed walk) with the option on beside the one with it
+off.
+
+    python tools/bench_mesh.py --indexed --normals [--streamed] [--config cfg3]
 """
 import argparse
 import ctypes as C
@@ -83,6 +90,16 @@ def indexed_report(args, scene, hp):
     out.update(triangles=n, vertices=V, faces=F, slots_log2=int(w.m_slotsLog2),
                weld_device_bytes=16 * (1 << w.m_slotsLog2) + 40 * 3 * n + 16 * n,
                download_bytes_soup=72 * n, download_bytes_indexed=24 * V + 12 * F)
+    if args.normals:
+        scale = E.mesh_normals_default_scale_log2(hp.m_virtualVoxelSize)
+        acc, nrm, st = lib.DeviceBuffer(24 * V), lib.DeviceBuffer(12 * V), lib.DeviceBuffer(4)
+        normals = lambda: lib.check(L.vh_mesh_vertex_normals(w.d_vertices, w.d_keys, w.d_faces, V, F, scale, acc.ptr, nrm.ptr, st.ptr, None), "vh_mesh_vertex_normals")
+        for skip, name in enumerate(("normals_faces_us", "normals_finish_us")):
+            out[name] = timed(skip, normals)
+        assert int(st.download(np.uint32, 1)[0]) == 0, "the default scale left a status"
+        out.update(normals_scale_log2=scale, normals_device_bytes=36 * V + 4, download_bytes_normals=12 * V)
+        for b in (acc, nrm, st):
+            b.free()
     L.vh_mesh_weld_data_free(C.byref(w))
     L.vh_marching_cubes_data_free(C.byref(data))
     # the host merge on the same soup: saveMesh = merge + PLY; the PLY alone is timed on the indexed mesh and taken off
@@ -98,6 +115,16 @@ def indexed_report(args, scene, hp):
         t0 = time.perf_counter()
         mc.saveMesh(os.path.join(d, "indexed.ply"), None, True)
         t_ply = time.perf_counter() - t0
+        if args.normals:  # the whole extraction, option off and on, alternating (the first pair sizes the buffers)
+            walls = {False: [], True: []}
+            for rep in range(1 + max(args.reps, 3)):
+                for on in (False, True):
+                    mc.setIndexedNormals(on)
+                    t0 = time.perf_counter()
+                    mc.extractIsoSurfaceIndexed(hd, hpp)
+                    if rep > 0:
+                        walls[on].append(time.perf_counter() - t0)
+            out.update(extract_indexed_off_wall_s=round(float(np.median(walls[False])), 5), extract_indexed_normals_wall_s=round(float(np.median(walls[True])), 5))
     out.update(host_merge_s=round(t_soup - t_ply, 4), ply_write_s=round(t_ply, 4), extract_indexed_wall_s=round(t_indexed, 4))
     return out
 
@@ -163,6 +190,20 @@ def streamed_report(args, scene, hp):
             else:
                 per_append[name].append(us)
     lib.check(L.vh_mesh_weld_accum_get_counts(accum, counts, None), "vh_mesh_weld_accum_get_counts")
+    if args.normals:  # over the finished accumulation (the last one above); the first pass makes the buffers
+        scale = E.mesh_normals_default_scale_log2(hp.m_virtualVoxelSize)
+        for skip, name in enumerate(("normals_faces_us", "normals_finish_us")):
+            us = []
+            for rep in range(3 + args.reps):
+                lib.check(L.vh_time_launch_after(skip, e0, e1), "vh_time_launch_after")
+                lib.check(L.vh_mesh_weld_accum_normals(accum, scale, None), "vh_mesh_weld_accum_normals")
+                lib.check(L.vh_stream_synchronize(None), "synchronize")
+                ms = C.c_float()
+                assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0, "the launch did not take the events"
+                if rep >= 3:
+                    us.append(1e3 * ms.value)
+            out[name] = round(float(np.median(us)), 2)
+        out.update(normals_scale_log2=scale, download_bytes_normals=12 * int(counts[0]))
     L.vh_mesh_weld_accum_destroy(accum)
     L.vh_marching_cubes_data_free(C.byref(data))
     for name in names:
@@ -179,6 +220,7 @@ def streamed_report(args, scene, hp):
     try:
         with tempfile.TemporaryDirectory() as d:
             walls = dict(soup_walk_s=[], soup_save_s=[], indexed_walk_s=[], indexed_save_s=[])
+            normal_walks = []
             for rep in range(1 + max(args.reps, 3)):  # the first pair of walks sizes every buffer
                 t0 = time.perf_counter()
                 mc.extractIsoSurfaceChunkGrid(grid, pos, radius)
@@ -196,6 +238,14 @@ def streamed_report(args, scene, hp):
                 if rep > 0:
                     for k, v in zip(walls, (t1 - t0, t3 - t2, t4 - t3, t6 - t5)):
                         walls[k].append(v)
+                if args.normals:
+                    mc.setIndexedNormals(True)
+                    t7 = time.perf_counter()
+                    mc.extractIsoSurfaceIndexedChunkGrid(grid, pos, radius)
+                    if rep > 0:
+                        normal_walks.append(time.perf_counter() - t7)
+                    mc.setIndexedNormals(False)
+                    mc.clearMeshBuffer()
     finally:
         grid.close()
     w = {k: float(np.median(v)) for k, v in walls.items()}
@@ -206,6 +256,8 @@ def streamed_report(args, scene, hp):
                soup_route_s=round(w["soup_walk_s"] + w["soup_save_s"] - w["indexed_save_s"], 4),
                soup_triangles=n_soup, download_bytes_soup=72 * n_soup,
                download_bytes_indexed=24 * stats["vertices"] + 12 * stats["faces"], walk=stats)
+    if args.normals:
+        out.update(indexed_walk_normals_s=round(float(np.median(normal_walks)), 4), indexed_walk_normals_min_s=round(min(normal_walks), 4))
     return out
 
 
@@ -217,7 +269,10 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--indexed", action="store_true", help="measure the indexed extraction stage by stage instead")
     ap.add_argument("--streamed", action="store_true", help="--indexed: the scene behind a chunk grid; soup walk + host merge against the indexed walk")
+    ap.add_argument("--normals", action="store_true", help="--indexed: add the vertex-normal pass: its two kernels, its download, the extraction with it on and off")
     args = ap.parse_args()
+    if args.normals and not args.indexed:
+        ap.error("--normals needs --indexed")
 
     import torch
     from voxelhashing_amd import engine as E, synth, vhtypes as T

@@ -3,7 +3,7 @@
 parameter file, optional mesh at the end) and prints one JSON line with the timing.
 
     python tools/replay.py --params zParameters.txt [--tracking zParametersTracking.txt] [--rgbd-tracking] [--sens a.sens b.sens]
-                           [--mesh scan.ply [--indexed-mesh]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
+                           [--mesh scan.ply [--indexed-mesh [--mesh-normals]]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
                            [--native [--batch N] [--native-tracking]] [--weighted-colour]
 
 Without --sens the files named by s_binaryDumpSensorFile[i] in the parameter file are played.  The rendering keys
@@ -40,6 +40,7 @@ def main():
     ap.add_argument("--sens", nargs="*", default=None)
     ap.add_argument("--mesh", default=None)
     ap.add_argument("--indexed-mesh", action="store_true", help="--mesh: weld the triangles on the device instead of merging them on the host; with s_streamingEnabled the chunks' triangles are welded into one mesh as the chunk grid is walked")
+    ap.add_argument("--mesh-normals", action="store_true", help="--indexed-mesh: compute vertex normals on the device after the weld and write nx, ny, nz into the PLY")
     ap.add_argument("--record", default=None, help="write what was processed, with the poses used, to this .sens file")
     ap.add_argument("--max-frames", type=int, default=None)
     ap.add_argument("--render-to", default=None, help="renderToFile: the shaded model and the input of every frame as PNGs under this directory")
@@ -49,6 +50,8 @@ def main():
     ap.add_argument("--native-tracking", action="store_true", help="--native: let the native loop track the camera (plain ICP, or RGB-D ICP with --rgbd-tracking) when the poses are not recorded")
     ap.add_argument("--weighted-colour", action="store_true", help="fuse colours weighted by the voxel weights instead of the reference's running 50/50 average")
     args = ap.parse_args()
+    if args.mesh_normals and not args.indexed_mesh:
+        ap.error("--mesh-normals needs --indexed-mesh: only the welded mesh has vertices that faces share")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU (there is no CPU fallback)")
@@ -94,8 +97,10 @@ def main():
     if args.record:
         out["recorded"] = rec.saveRecordedFramesToFile(args.record)
     if args.mesh:
-        m = rec.extractIsoSurfaceIndexed(args.mesh) if args.indexed_mesh else rec.extractIsoSurface(args.mesh)
+        m = rec.extractIsoSurfaceIndexed(args.mesh, normals=args.mesh_normals) if args.indexed_mesh else rec.extractIsoSurface(args.mesh)
         out["mesh"] = dict(file=args.mesh, indexed=bool(args.indexed_mesh), vertices=int(len(m["vertices"])), faces=int(len(m["faces"])))
+        if args.mesh_normals:
+            out["mesh"]["normals"] = int(len(m["normals"]))
     print(json.dumps(out))
 
 

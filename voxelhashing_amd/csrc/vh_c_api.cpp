@@ -417,6 +417,47 @@ int vh_marching_cubes_download_indexed(VhMarchingCubes* mc, VhVertex* vertices, 
     if (!mc) return VH_ERR_BAD_ARGUMENT;
     return guarded([&] { mc->impl.downloadIndexed(vertices, keys, faces); });
 }
+int vh_marching_cubes_set_indexed_normals(VhMarchingCubes* mc, int enabled)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    mc->impl.setIndexedNormals(enabled != 0);
+    return VH_OK;
+}
+int vh_marching_cubes_download_indexed_normals(VhMarchingCubes* mc, float* normals)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.downloadIndexedNormals(normals); });
+}
+int vh_marching_cubes_get_mesh_normals_size(VhMarchingCubes* mc, uint64_t* out)
+{
+    if (!mc || !out) return VH_ERR_BAD_ARGUMENT;
+    *out = mc->impl.getMeshData().hasNormals() ? mc->impl.getMeshData().m_Normals.size() : 0;
+    return VH_OK;
+}
+int vh_marching_cubes_get_mesh_normals(VhMarchingCubes* mc, float* normals3)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    const vh::MeshData& m = mc->impl.getMeshData();
+    if (normals3 && m.hasNormals()) std::memcpy(normals3, m.m_Normals.data(), sizeof(float) * m.m_Normals.size());
+    return VH_OK;
+}
+int vh_mesh_save_ply(const float* vertices3, const float* colors4, const float* normals3, uint64_t numVertices, const uint32_t* faceIndices,
+                     uint64_t numFaceIndices, const float transform[16], const char* filename)
+{
+    if (!filename || (numVertices != 0 && !vertices3) || (numFaceIndices != 0 && !faceIndices) || numFaceIndices % 3 != 0) return VH_ERR_BAD_ARGUMENT;
+    for (uint64_t i = 0; i < numFaceIndices; i++)
+        if (faceIndices[i] >= numVertices) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] {
+        vh::MeshData md;
+        md.m_Vertices.resize(numVertices);
+        if (numVertices) std::memcpy(md.m_Vertices.data(), vertices3, sizeof(vh::vec3f) * numVertices);
+        if (colors4) md.m_Colors.assign(colors4, colors4 + 4 * numVertices);
+        if (normals3) md.m_Normals.assign(normals3, normals3 + 3 * numVertices);
+        if (numFaceIndices) md.m_FaceIndicesVertices.assign(faceIndices, faceIndices + numFaceIndices);
+        if (transform) md.applyTransform(toMat(transform));
+        md.saveToPLY(filename);
+    });
+}
 int vh_marching_cubes_download_sources(VhMarchingCubes* mc, VhTriangleSource* out, uint32_t n)
 {
     if (!mc) return VH_ERR_BAD_ARGUMENT;

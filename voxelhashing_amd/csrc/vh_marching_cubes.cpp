@@ -168,6 +168,8 @@ void vh::MeshData::merge(const MeshData& other)
     if (other.m_Vertices.empty()) return;
     if (m_Vertices.empty()) { *this = other; return; }
     if (hasVertexIndices() != other.hasVertexIndices()) throw vh::Error(VH_ERR_BAD_ARGUMENT, "invalid mesh conversion");
+    if (hasNormals() && other.hasNormals()) m_Normals.insert(m_Normals.end(), other.m_Normals.begin(), other.m_Normals.end());
+    else m_Normals.clear(); // normals for a part of the vertices are none
     const unsigned int base = (unsigned int)m_Vertices.size();
     m_Vertices.insert(m_Vertices.end(), other.m_Vertices.begin(), other.m_Vertices.end());
     m_Colors.insert(m_Colors.end(), other.m_Colors.begin(), other.m_Colors.end());
@@ -175,9 +177,33 @@ void vh::MeshData::merge(const MeshData& other)
 }
 
 // MLIB/core-mesh/meshData.h:471-479 with Matrix4x4 * point3d = implicit w = 1 and de-homogenisation
-// (MLIB/core-math/matrix4x4.h:459-468)
+// (MLIB/core-math/matrix4x4.h:459-468).  mLib sends normals through the same operator with the inverse transpose, whose
+// fourth row holds the translation: it ends up in w, and the normal is divided by it (fenced reference
+// defects); here a normal
+// goes by the cofactor matrix of the upper-left 3x3 -- det(A) times the inverse transpose of A -- times the sign of the
+// determinant, renormalised in double; zero stays zero.  The normal then stays on the side of the surface it was on:
+// it turns with a rotation and is mirrored by a mirror.  (The faces keep their index order, so after a mirror the
+// winding gives the opposite side: a x b of the transformed edges is cof(A) (a x b), without the sign.)
 void vh::MeshData::applyTransform(const mat4f& t)
 {
+    if (hasNormals()) {
+        const double a[3][3] = { { t.m[0], t.m[1], t.m[2] }, { t.m[4], t.m[5], t.m[6] }, { t.m[8], t.m[9], t.m[10] } };
+        double c[3][3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+                c[i][j] = a[i1][j1] * a[i2][j2] - a[i1][j2] * a[i2][j1];
+            }
+        const double det = a[0][0] * c[0][0] + a[0][1] * c[0][1] + a[0][2] * c[0][2];
+        const double sign = det < 0.0 ? -1.0 : 1.0;
+        for (size_t v = 0; v < m_Vertices.size(); v++) {
+            const double n[3] = { m_Normals[3 * v], m_Normals[3 * v + 1], m_Normals[3 * v + 2] };
+            double r[3];
+            for (int i = 0; i < 3; i++) r[i] = sign * (c[i][0] * n[0] + c[i][1] * n[1] + c[i][2] * n[2]);
+            const double l = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+            for (int i = 0; i < 3; i++) m_Normals[3 * v + i] = l > 0.0 ? (float)(r[i] / l) : 0.0f;
+        }
+    }
     for (auto& v : m_Vertices) {
         const float x = t.m[0] * v.x + t.m[1] * v.y + t.m[2] * v.z + t.m[3];
         const float y = t.m[4] * v.x + t.m[5] * v.y + t.m[6] * v.z + t.m[7];
@@ -192,13 +218,15 @@ void vh::MeshData::saveToPLY(const std::string& filename) const
 {
     std::ofstream f(filename, std::ios::binary);
     if (!f) throw vh::Error(VH_ERR_IO, "cannot write " + filename);
-    const bool hasColors = m_Colors.size() == 4 * m_Vertices.size();
+    const bool hasColors = m_Colors.size() == 4 * m_Vertices.size(), withNormals = hasNormals();
     const size_t nFaces = hasVertexIndices() ? m_FaceIndicesVertices.size() / 3 : m_Vertices.size() / 3;
     f << "ply\nformat binary_little_endian 1.0\ncomment MLIB generated\nelement vertex " << m_Vertices.size() << "\nproperty float x\nproperty float y\nproperty float z\n";
+    if (withNormals) f << "property float nx\nproperty float ny\nproperty float nz\n"; // meshIO.cpp:499-503
     if (hasColors) f << "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n";
     f << "element face " << nFaces << "\nproperty list uchar int vertex_indices\nend_header\n";
     for (size_t i = 0; i < m_Vertices.size(); i++) {
         f.write((const char*)&m_Vertices[i], 12);
+        if (withNormals) f.write((const char*)&m_Normals[3 * i], 12); // meshIO.cpp:527-538
         if (hasColors) {
             unsigned char c[4];
             for (int k = 0; k < 4; k++) c[k] = (unsigned char)(int)std::min(255.0f, std::max(0.0f, m_Colors[4 * i + k] * 255)); // vec4uc(c * 255)
@@ -325,6 +353,25 @@ void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(const HashData& hashData
     check(rc, "vh_mesh_weld_get_counts");
     std::vector<VhVertex> verts(counts[0]);
     vh::MeshData md;
+    if (m_indexedNormals) {
+        if (!d_normalStatus) d_normalStatus = vh::deviceAlloc<uint32_t>(1, "vertex normal status");
+        if (counts[0] > m_normalsCapacity) {
+            const size_t cap = counts[0] + counts[0] / 4u;
+            d_normalAcc = vh::deviceAlloc<int64_t>(3 * cap, "vertex normal accumulators");
+            d_normals = vh::deviceAlloc<float>(3 * cap, "vertex normals");
+            m_normalsCapacity = cap;
+        }
+        int32_t scaleLog2 = 0;
+        check(vh_mesh_normals_default_scale_log2(hashParams.m_virtualVoxelSize, &scaleLog2), "vh_mesh_normals_default_scale_log2");
+        check(vh_mesh_vertex_normals(m_weld.d_vertices, m_weld.d_keys, m_weld.d_faces, counts[0], counts[1], scaleLog2, d_normalAcc.get(),
+                                     d_normals.get(), d_normalStatus.get(), m_stream), "vh_mesh_vertex_normals");
+        unsigned int status = 0;
+        md.m_Normals.resize(3 * (size_t)counts[0]);
+        checkHip(hipMemcpyAsync(&status, d_normalStatus.get(), sizeof(status), hipMemcpyDeviceToHost, (hipStream_t)m_stream), "normal status");
+        if (counts[0]) checkHip(hipMemcpyAsync(md.m_Normals.data(), d_normals.get(), sizeof(float) * 3 * (size_t)counts[0], hipMemcpyDeviceToHost, (hipStream_t)m_stream), "normals");
+        checkHip(hipStreamSynchronize((hipStream_t)m_stream), "normals");
+        if (status != 0u) throw vh::Error(VH_ERR_BAD_ARGUMENT, "vertex normals: a face normal is out of the fixed-point range, or a face index out of bounds");
+    }
     md.m_FaceIndicesVertices.resize(3 * (size_t)counts[1]);
     check(vh_mesh_weld_download(&m_weld, verts.data(), nullptr, md.m_FaceIndicesVertices.data(), counts[0], counts[1], m_stream), "vh_mesh_weld_download");
     md.m_Vertices.resize(counts[0]);
@@ -335,6 +382,7 @@ void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(const HashData& hashData
     }
     m_meshData = std::move(md);
     m_indexedCounts[0] = counts[0]; m_indexedCounts[1] = counts[1];
+    m_indexedHasNormals = m_indexedNormals;
     m_welded = true;
 }
 
@@ -346,6 +394,7 @@ void CUDAMarchingCubesHashSDF::resetIndexed()
     m_indexedCounts[0] = m_indexedCounts[1] = m_indexedCounts[2] = 0;
     for (unsigned int& v : m_indexedStats) v = 0;
     m_numSourced = 0;
+    m_indexedHasNormals = false;
 }
 
 void CUDAMarchingCubesHashSDF::beginIndexed()
@@ -364,6 +413,7 @@ void CUDAMarchingCubesHashSDF::appendIndexed(const HashData& hashData, const Has
                                              const vh::vec3f& maxCorner, bool boxEnabled)
 {
     if (!m_accum || !m_indexedIsAccumulated) throw vh::Error(VH_ERR_BAD_ARGUMENT, "appendIndexed: no beginIndexed");
+    m_indexedVoxelSize = hashParams.m_virtualVoxelSize;
     try {
         if (!d_sources) d_sources = vh::deviceAlloc<VhTriangleSource>(m_params.m_maxNumTriangles, "triangle sources");
         check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
@@ -404,6 +454,22 @@ void CUDAMarchingCubesHashSDF::finishIndexed()
     const unsigned int nv = stats[VH_WELD_ACCUM_VERTICES], nf = stats[VH_WELD_ACCUM_FACES];
     std::vector<VhVertex> verts(nv);
     vh::MeshData md;
+    m_indexedHasNormals = false;
+    if (m_indexedNormals) {
+        // over all the faces, with the bits the last append left: a pass of the finish, never of an append.  (Without an
+        // append there is no voxel size, and no vertex either: any scale serves.)
+        int32_t scaleLog2 = 0;
+        if (m_indexedVoxelSize > 0.0f) check(vh_mesh_normals_default_scale_log2(m_indexedVoxelSize, &scaleLog2), "vh_mesh_normals_default_scale_log2");
+        check(vh_mesh_weld_accum_normals(m_accum.get(), scaleLog2, m_stream), "vh_mesh_weld_accum_normals");
+        md.m_Normals.resize(3 * (size_t)nv);
+        const int nrc = vh_mesh_weld_accum_download_normals(m_accum.get(), md.m_Normals.data(), nv, m_stream);
+        if (nrc == VH_ERR_BAD_ARGUMENT) {
+            m_indexedStats[VH_WELD_ACCUM_STATUS] = 0;
+            m_indexedCounts[2] = 0;
+            throw vh::Error(nrc, "vertex normals: a face normal is out of the fixed-point range, or a face index out of bounds");
+        }
+        check(nrc, "vh_mesh_weld_accum_download_normals");
+    }
     md.m_FaceIndicesVertices.resize(3 * (size_t)nf);
     check(vh_mesh_weld_accum_download(m_accum.get(), verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_download");
     md.m_Vertices.resize(nv);
@@ -415,6 +481,7 @@ void CUDAMarchingCubesHashSDF::finishIndexed()
     m_meshData = std::move(md);
     m_indexedCounts[0] = nv; m_indexedCounts[1] = nf;
     for (int i = 0; i < 6; i++) m_indexedStats[i] = stats[i];
+    m_indexedHasNormals = m_indexedNormals;
     m_welded = true;
 }
 
@@ -478,6 +545,19 @@ void CUDAMarchingCubesHashSDF::downloadIndexed(VhVertex* vertices, uint64_t* key
     check(vh_mesh_weld_download(&m_weld, vertices, keys, faces, m_indexedCounts[0], m_indexedCounts[1], m_stream), "vh_mesh_weld_download");
 }
 
+void CUDAMarchingCubesHashSDF::downloadIndexedNormals(float* normals)
+{
+    if (!m_indexedHasNormals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexedNormals: the last indexed extraction computed none (setIndexedNormals)");
+    if (m_indexedCounts[0] == 0) return;
+    if (!normals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexedNormals");
+    if (m_indexedIsAccumulated) {
+        check(vh_mesh_weld_accum_download_normals(m_accum.get(), normals, m_indexedCounts[0], m_stream), "vh_mesh_weld_accum_download_normals");
+        return;
+    }
+    checkHip(hipMemcpyAsync(normals, d_normals.get(), sizeof(float) * 3 * (size_t)m_indexedCounts[0], hipMemcpyDeviceToHost, (hipStream_t)m_stream), "normals");
+    checkHip(hipStreamSynchronize((hipStream_t)m_stream), "normals");
+}
+
 void CUDAMarchingCubesHashSDF::downloadSources(VhTriangleSource* out, unsigned int n)
 {
     if (n == 0) return;
@@ -494,6 +574,7 @@ void CUDAMarchingCubesHashSDF::copyTrianglesToCPU()
         throw vh::Error(VH_ERR_STAGING_OVERFLOW, "not enough memory to store triangles for chunk; increase s_marchingCubesMaxNumTriangles");
     if (nTriangles == 0) return;
     m_welded = false; // the buffer is about to hold something the weld did not make
+    m_meshData.m_Normals.clear(); // (and the soup that joins it has no normals)
     std::vector<VhTriangle> tris(nTriangles);
     downloadTriangles(tris.data(), nTriangles);
     vh::MeshData md;

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 
@@ -298,6 +299,69 @@ __global__ __launch_bounds__(256) void k_weld_rehash(const uint64_t* oldKeys, co
     else w.slotVals[slot] = oldVals[s];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Vertex normals of a welded mesh (vh_mesh_vertex_normals; DESIGN.md section 4, "Vertex normals"): area-weighted face
+// normals summed per vertex in 64-bit fixed point, so that the sums do not depend on the order the atomics ran in.
+// Two launches: faces (one lane per face), finish (one lane per vertex).
+
+// One lane per face.  An index >= numVertices is reported before anything is read through it; a face with a repeated
+// index adds nothing.  The triple is rotated, winding kept, so that the vertex with the smallest key comes first: face
+// order and vertex numbers come from atomics, keys do not.  Then float32, one rounding per operation (the build has
+// -ffp-contract=off): a = p1 - p0, b = p2 - p0, c = a x b, s = c * scale (a power of two), q = rint(s) added to the
+// three accumulators of each of the three vertices -- nine atomics whose results nobody reads.  A component of s that is
+// not finite or above 2^40 reports the face instead.  The lanes' reports go into the status word with one atomic per wave.
+__global__ __launch_bounds__(256) void k_mesh_normals_faces(const VhVertex* vertices, const uint64_t* keys, const uint32_t* faces, uint32_t numVertices,
+                                                            uint32_t numFaces, float scale, unsigned long long* acc, uint32_t* statusWord)
+{
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t status = 0u;
+    if (f < numFaces) {
+        uint32_t i0 = faces[3u * f], i1 = faces[3u * f + 1u], i2 = faces[3u * f + 2u];
+        if (i0 >= numVertices || i1 >= numVertices || i2 >= numVertices) status = VH_NORMALS_BAD_INDEX;
+        else if (i0 != i1 && i1 != i2 && i0 != i2) {
+            const uint64_t k0 = keys[i0], k1 = keys[i1], k2 = keys[i2];
+            if (k1 < k0 && k1 <= k2) { const uint32_t t = i0; i0 = i1; i1 = i2; i2 = t; }
+            else if (k2 < k0 && k2 < k1) { const uint32_t t = i0; i0 = i2; i2 = i1; i1 = t; }
+            const VhVertex v0 = vertices[i0], v1 = vertices[i1], v2 = vertices[i2];
+            const float ax = v1.p[0] - v0.p[0], ay = v1.p[1] - v0.p[1], az = v1.p[2] - v0.p[2];
+            const float bx = v2.p[0] - v0.p[0], by = v2.p[1] - v0.p[1], bz = v2.p[2] - v0.p[2];
+            const float sx = (ay * bz - az * by) * scale, sy = (az * bx - ax * bz) * scale, sz = (ax * by - ay * bx) * scale;
+            const float limit = 1099511627776.0f; // 2^40
+            if (!(fabsf(sx) <= limit && fabsf(sy) <= limit && fabsf(sz) <= limit)) status = VH_NORMALS_RANGE; // (NaN fails every comparison)
+            else {
+                const unsigned long long qx = (unsigned long long)(long long)rintf(sx), qy = (unsigned long long)(long long)rintf(sy),
+                                         qz = (unsigned long long)(long long)rintf(sz);
+                atomicAdd(&acc[3ull * i0], qx); atomicAdd(&acc[3ull * i0 + 1ull], qy); atomicAdd(&acc[3ull * i0 + 2ull], qz);
+                atomicAdd(&acc[3ull * i1], qx); atomicAdd(&acc[3ull * i1 + 1ull], qy); atomicAdd(&acc[3ull * i1 + 2ull], qz);
+                atomicAdd(&acc[3ull * i2], qx); atomicAdd(&acc[3ull * i2 + 1ull], qy); atomicAdd(&acc[3ull * i2 + 2ull], qz);
+            }
+        }
+    }
+    const uint64_t range = __ballot((status & VH_NORMALS_RANGE) != 0u), bad = __ballot((status & VH_NORMALS_BAD_INDEX) != 0u);
+    if ((range | bad) == 0ull) return;
+    if ((int)lane_id() == __ffsll((unsigned long long)(range | bad)) - 1)
+        atomicOr(statusWord, (range != 0ull ? VH_NORMALS_RANGE : 0u) | (bad != 0ull ? VH_NORMALS_BAD_INDEX : 0u));
+}
+
+// One lane per vertex: the three sums as doubles, normalised with correctly rounded double arithmetic and rounded to
+// float once.  A zero sum (no face, collapsed faces only, contributions that cancel) gives (0, 0, 0), and so does every
+// vertex once the face pass, which ran before this launch on the stream, has left a status.
+__global__ __launch_bounds__(256) void k_mesh_normals_finish(const unsigned long long* acc, uint32_t numVertices, const uint32_t* statusWord, float* normals)
+{
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= numVertices) return;
+    float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+    if (*statusWord == 0u) { // uniform
+        const double dx = (double)(long long)acc[3ull * v], dy = (double)(long long)acc[3ull * v + 1ull], dz = (double)(long long)acc[3ull * v + 2ull];
+        const double l2 = (dx * dx + dy * dy) + dz * dz;
+        if (l2 != 0.0) {
+            const double l = __dsqrt_rn(l2);
+            nx = (float)__ddiv_rn(dx, l); ny = (float)__ddiv_rn(dy, l); nz = (float)__ddiv_rn(dz, l);
+        }
+    }
+    normals[3ull * v] = nx; normals[3ull * v + 1ull] = ny; normals[3ull * v + 2ull] = nz;
+}
+
 // the smallest power of two >= 6 n (twice the 3 n keys n triangles can have), 64 slots at least
 uint32_t defaultSlotsLog2(uint32_t n)
 {
@@ -408,6 +472,36 @@ int vh_mesh_weld_download(const VhMeshWeldData* data, VhVertex* vertices, uint64
     return VH_OK;
 }
 
+int vh_mesh_normals_default_scale_log2(float voxelSize, int32_t* scaleLog2)
+{
+    if (!scaleLog2 || !(voxelSize > 0.0f) || !std::isfinite(voxelSize)) return VH_ERR_BAD_ARGUMENT;
+    // ceil(log2(v)) from the exponent: v = m 2^e with m in [1/2, 1), so the ceiling is e unless v is the power of two 2^(e-1)
+    int e = 0;
+    const double m = std::frexp((double)voxelSize * (double)voxelSize, &e);
+    *scaleLog2 = 38 - (m == 0.5 ? e - 1 : e);
+    return VH_OK;
+}
+
+int vh_mesh_vertex_normals(const VhVertex* d_vertices, const uint64_t* d_keys, const uint32_t* d_faces, uint32_t numVertices, uint32_t numFaces,
+                           int32_t scaleLog2, int64_t* d_acc, float* d_normals, uint32_t* d_status, vhStream_t stream)
+{
+    if (!d_status || scaleLog2 < -100 || scaleLog2 > 100) return VH_ERR_BAD_ARGUMENT;
+    if (numVertices != 0 && (!d_vertices || !d_keys || !d_acc || !d_normals)) return VH_ERR_BAD_ARGUMENT;
+    if (numFaces != 0 && !d_faces) return VH_ERR_BAD_ARGUMENT;
+    if (numFaces > 0x55555555u) return VH_ERR_BAD_ARGUMENT; // 3 numFaces face offsets in 32 bits
+    hipStream_t s = (hipStream_t)stream;
+    VH_HIP(hipMemsetAsync(d_status, 0, sizeof(uint32_t), s));
+    if (numVertices == 0) return VH_OK; // no vertex, no normal; and no launch with an empty grid
+    VH_HIP(hipMemsetAsync(d_acc, 0, sizeof(int64_t) * 3 * (size_t)numVertices, s));
+    if (numFaces != 0) {
+        VH_LAUNCH_TIMED(k_mesh_normals_faces, cdiv(numFaces, 256), 256, s, d_vertices, d_keys, d_faces, numVertices, numFaces, std::ldexp(1.0f, scaleLog2),
+                        reinterpret_cast<unsigned long long*>(d_acc), d_status);
+        VH_TRY(vh_last_launch_error());
+    }
+    VH_LAUNCH_TIMED(k_mesh_normals_finish, cdiv(numVertices, 256), 256, s, reinterpret_cast<const unsigned long long*>(d_acc), numVertices, d_status, d_normals);
+    return vh_last_launch_error();
+}
+
 } // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -422,6 +516,13 @@ struct VhMeshWeldAccum {
     vh::DevicePtr<uint64_t> keys;
     vh::DevicePtr<uint8_t> ranks;
     vh::DevicePtr<uint32_t> faces;
+    // vertex normals (vh_mesh_weld_accum_normals): made by the first pass, for m_normalsCapacity vertices
+    vh::DevicePtr<int64_t> normalAcc;   // 3 per vertex
+    vh::DevicePtr<float> normals;       // 3 per vertex
+    vh::DevicePtr<uint32_t> normalStatus;
+    size_t m_normalsCapacity = 0;
+    uint32_t m_normalsVertices = 0;     // of the pass that m_normalsValid speaks of
+    bool m_normalsValid = false;        // the pass has run, and no begin or append since
     size_t m_soupCapacity = 0, m_vertexCapacity = 0, m_faceCapacity = 0; // in soup vertices, welded vertices, faces
     uint32_t m_slotsLog2 = 6, m_firstSlotsLog2 = 6;
     bool m_fixed = false, m_begun = false;
@@ -521,6 +622,7 @@ int vh_mesh_weld_accum_begin(VhMeshWeldAccum* accum, vhStream_t stream)
     accum->m_appends = 0;
     accum->m_rehashes = 0;
     accum->m_begun = true;
+    accum->m_normalsValid = false;
     return VH_OK;
 }
 
@@ -529,6 +631,7 @@ int vh_mesh_weld_accum_append(VhMeshWeldAccum* accum, const VhTriangle* d_triang
 {
     if (!accum || !accum->m_begun) return VH_ERR_BAD_ARGUMENT;
     if (numTriangles > 0x55555555u / 2u || (numTriangles != 0 && (!d_triangles || !d_sources))) return VH_ERR_BAD_ARGUMENT;
+    accum->m_normalsValid = false; // normals are of all faces with the final vertex bits: a pass before this append is stale
     if (numTriangles == 0) return VH_OK; // nothing to take, and no launch with an empty grid
     if (accum->m_appends >= VH_WELD_ACCUM_MAX_APPENDS - 1u) return VH_ERR_BAD_ARGUMENT;
     hipStream_t s = (hipStream_t)stream;
@@ -613,6 +716,41 @@ int vh_mesh_weld_accum_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint
     if (faces && numFaces) VH_HIP(hipMemcpyAsync(faces, accum->faces.get(), sizeof(uint32_t) * 3 * (size_t)numFaces, hipMemcpyDeviceToHost, s));
     VH_HIP(hipStreamSynchronize(s));
     return VH_OK;
+}
+
+int vh_mesh_weld_accum_normals(VhMeshWeldAccum* accum, int32_t scaleLog2, vhStream_t stream)
+{
+    if (!accum || !accum->m_begun || scaleLog2 < -100 || scaleLog2 > 100) return VH_ERR_BAD_ARGUMENT;
+    return accumGuarded([&]() -> int {
+        VhMeshWeldAccum& a = *accum;
+        a.m_normalsValid = false;
+        uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
+        VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream)); // waits for the appends; a weld that failed has no normals
+        const uint32_t nv = have[VH_WELD_ACCUM_VERTICES], nf = have[VH_WELD_ACCUM_FACES];
+        if (!a.normalStatus) a.normalStatus = vh::deviceAlloc<uint32_t>(1, "vertex normal status");
+        if (nv > a.m_normalsCapacity) {
+            const size_t cap = std::max((size_t)nv, 2 * a.m_normalsCapacity);
+            a.normalAcc = vh::deviceAlloc<int64_t>(3 * cap, "vertex normal accumulators");
+            a.normals = vh::deviceAlloc<float>(3 * cap, "vertex normals");
+            a.m_normalsCapacity = cap;
+        }
+        VH_TRY(vh_mesh_vertex_normals(a.vertices.get(), a.keys.get(), a.faces.get(), nv, nf, scaleLog2, a.normalAcc.get(), a.normals.get(),
+                                      a.normalStatus.get(), stream));
+        a.m_normalsVertices = nv;
+        a.m_normalsValid = true;
+        return VH_OK;
+    });
+}
+
+int vh_mesh_weld_accum_download_normals(VhMeshWeldAccum* accum, float* normals, uint32_t numVertices, vhStream_t stream)
+{
+    if (!accum || !accum->m_normalsValid || numVertices > accum->m_normalsVertices || (numVertices != 0 && !normals)) return VH_ERR_BAD_ARGUMENT;
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t status = 0u;
+    VH_HIP(hipMemcpyAsync(&status, accum->normalStatus.get(), sizeof(status), hipMemcpyDeviceToHost, s));
+    if (numVertices) VH_HIP(hipMemcpyAsync(normals, accum->normals.get(), sizeof(float) * 3 * (size_t)numVertices, hipMemcpyDeviceToHost, s));
+    VH_HIP(hipStreamSynchronize(s));
+    return status != 0u ? VH_ERR_BAD_ARGUMENT : VH_OK;
 }
 
 } // extern "C"

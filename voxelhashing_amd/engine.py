@@ -728,6 +728,7 @@ class CUDAMarchingCubesHashSDF:
         h = C.c_void_p()
         check(self.L.vh_marching_cubes_create(C.byref(params), stream, C.byref(h)), "vh_marching_cubes_create")
         self.handle = h
+        self._indexed_normals = False
 
     def close(self):
         if getattr(self, "handle", None):
@@ -742,6 +743,12 @@ class CUDAMarchingCubesHashSDF:
 
     def setOfflineProcessing(self, on):
         check(self.L.vh_marching_cubes_set_offline_processing(self.handle, 1 if on else 0), "setOfflineProcessing")
+
+    def setIndexedNormals(self, on):
+        """vertex normals for the indexed extractions (off by default): computed on the device after the weld; indexed()
+        and mesh() then have a "normals" entry and saveMesh writes nx, ny, nz"""
+        check(self.L.vh_marching_cubes_set_indexed_normals(self.handle, 1 if on else 0), "setIndexedNormals")
+        self._indexed_normals = bool(on)
 
     def extractIsoSurface(self, hashData, hashParams, minCorner=(0, 0, 0), maxCorner=(0, 0, 0), boxEnabled=False, copy=True):
         check(self.L.vh_marching_cubes_extract_iso_surface(self.handle, C.byref(hashData), C.byref(hashParams), f16(minCorner),
@@ -793,13 +800,18 @@ class CUDAMarchingCubesHashSDF:
         return dict(vertices=int(out[0]), faces=int(out[1]), status=int(out[2]))
 
     def indexed(self):
-        """device mesh of the last indexed extraction -> vertices (V,3) f32, colors (V,3) f32, keys (V,) u64, faces (F,3) u32"""
+        """device mesh of the last indexed extraction -> vertices (V,3) f32, colors (V,3) f32, keys (V,) u64, faces (F,3) u32;
+        with setIndexedNormals(True), and an extraction made since, also normals (V,3) f32"""
         n = self.indexed_counts()
         v = np.zeros(n["vertices"], dtype=T.VERTEX_DTYPE)
         k = np.zeros(n["vertices"], dtype=np.uint64)
         f = np.zeros((n["faces"], 3), dtype=np.uint32)
         check(self.L.vh_marching_cubes_download_indexed(self.handle, v.ctypes.data, k.ctypes.data, f.ctypes.data), "download_indexed")
-        return dict(vertices=np.ascontiguousarray(v["p"]), colors=np.ascontiguousarray(v["c"]), keys=k, faces=f)
+        out = dict(vertices=np.ascontiguousarray(v["p"]), colors=np.ascontiguousarray(v["c"]), keys=k, faces=f)
+        if self._indexed_normals:
+            out["normals"] = np.zeros((n["vertices"], 3), dtype=np.float32)
+            check(self.L.vh_marching_cubes_download_indexed_normals(self.handle, out["normals"].ctypes.data), "download_indexed_normals")
+        return out
 
     def sources(self):
         """source records of the last indexed extraction, beside triangles() -> numpy array of T.TRIANGLE_SOURCE_DTYPE"""
@@ -835,7 +847,13 @@ class CUDAMarchingCubesHashSDF:
         c = np.zeros((int(sz[0]), 4), dtype=np.float32)
         f = np.zeros(int(sz[1]), dtype=np.uint32)
         check(self.L.vh_marching_cubes_get_mesh(self.handle, v.ctypes.data, c.ctypes.data, f.ctypes.data), "get_mesh")
-        return dict(vertices=v, colors=c, faces=f.reshape(-1, 3))
+        out = dict(vertices=v, colors=c, faces=f.reshape(-1, 3))
+        if self._indexed_normals:  # (3 per vertex, or none: whatever appended to the buffer since has dropped them)
+            nn = C.c_uint64()
+            check(self.L.vh_marching_cubes_get_mesh_normals_size(self.handle, C.byref(nn)), "get_mesh_normals_size")
+            out["normals"] = np.zeros((int(nn.value) // 3, 3), dtype=np.float32)
+            check(self.L.vh_marching_cubes_get_mesh_normals(self.handle, out["normals"].ctypes.data), "get_mesh_normals")
+        return out
 
     def saveMesh(self, filename, transform=None, overwriteExistingFile=False):
         t = f16(transform) if transform is not None else None
@@ -881,11 +899,65 @@ def mesh_weld(triangles, sources, slots_log2=0, raise_on_status=True, stream=Non
                 counts=(int(counts[0]), int(counts[1])), status=int(counts[2]), code=int(code), slots_log2=slots)
 
 
-def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, raise_on_status=True, stream=None):
+def mesh_normals_default_scale_log2(voxel_size):
+    """vh_mesh_normals_default_scale_log2 (host side, no GPU); raises VhError for a voxel size it refuses"""
+    out = C.c_int32()
+    check(load().vh_mesh_normals_default_scale_log2(float(voxel_size), C.byref(out)), "vh_mesh_normals_default_scale_log2")
+    return int(out.value)
+
+
+def mesh_vertex_normals(vertices, keys, faces, scale_log2, raise_on_status=True, stream=None):
+    """vh_mesh_vertex_normals on hand-made input: vertices (V,3) f32 positions, or T.VERTEX_DTYPE records; keys (V,) u64;
+    faces (F,3) u32 -> normals (V,3) f32, acc (V,3) i64 (the fixed-point sums), status, code.  A status raises VhError
+    (VH_ERR_BAD_ARGUMENT), or with raise_on_status=False comes back as `code` beside the all-zero normals."""
+    L = load()
+    v = np.asarray(vertices)
+    if v.dtype != T.VERTEX_DTYPE:
+        p = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3)
+        v = np.zeros(len(p), dtype=T.VERTEX_DTYPE)
+        v["p"] = p
+    v = np.ascontiguousarray(v).ravel()
+    k = np.ascontiguousarray(keys, dtype=np.uint64).ravel()
+    f = np.ascontiguousarray(faces, dtype=np.uint32).reshape(-1, 3)
+    if len(k) != len(v):
+        raise ValueError("one key per vertex")
+    nv, nf = len(v), len(f)
+    bufs = [DeviceBuffer.from_numpy(v, stream), DeviceBuffer.from_numpy(k, stream), DeviceBuffer.from_numpy(f, stream),
+            DeviceBuffer(24 * nv), DeviceBuffer(12 * nv), DeviceBuffer(4)]
+    try:
+        d_v, d_k, d_f, d_acc, d_n, d_st = bufs
+        check(L.vh_mesh_vertex_normals(d_v.ptr, d_k.ptr, d_f.ptr, nv, nf, int(scale_log2), d_acc.ptr, d_n.ptr, d_st.ptr, stream), "vh_mesh_vertex_normals")
+        status = int(d_st.download(np.uint32, 1, stream)[0])
+        normals = d_n.download(np.float32, 3 * nv, stream).reshape(-1, 3)
+        acc = d_acc.download(np.int64, 3 * nv, stream).reshape(-1, 3)
+    finally:
+        for b in bufs:
+            b.free()
+    code = 4 if status else 0  # VH_ERR_BAD_ARGUMENT for either bit, as for the weld's key range
+    if code and raise_on_status:
+        check(code, f"vh_mesh_vertex_normals (status {status})")
+    return dict(normals=normals, acc=acc, status=status, code=code)
+
+
+def mesh_save_ply(filename, vertices, colors=None, normals=None, faces=None, transform=None):
+    """vh_mesh_save_ply (host side, no GPU): the mesh container's applyTransform (when a transform is given) and
+    saveToPLY on numpy arrays: vertices (V,3), colors (V,4) or None, normals (V,3) or None, faces (F,3) or None"""
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    c = None if colors is None else np.ascontiguousarray(colors, dtype=np.float32).reshape(len(v), 4)
+    n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(len(v), 3)
+    f = np.zeros(0, dtype=np.uint32) if faces is None else np.ascontiguousarray(faces, dtype=np.uint32).ravel()
+    check(load().vh_mesh_save_ply(v.ctypes.data, None if c is None else c.ctypes.data, None if n is None else n.ctypes.data, len(v),
+                                  f.ctypes.data if len(f) else None, len(f), f16(transform) if transform is not None else None,
+                                  str(filename).encode()), "vh_mesh_save_ply")
+
+
+def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, raise_on_status=True, stream=None, normals_scale_log2=None):
     """vh_mesh_weld_accum_* on hand-made input: parts is a sequence of (soup, records), appended in order to one
     accumulation -> vertices, colors, keys, faces as mesh_weld(), counts (vertices, faces), stats (the six counts by
     name), status and code.  slots_log2 is the table's FIRST size (0: the smallest), reserve_triangles that of the
-    vertex and face arrays; fixed keeps the table from growing.  Errors as mesh_weld()."""
+    vertex and face arrays; fixed keeps the table from growing.  Errors as mesh_weld().
+    normals_scale_log2: run the vertex-normal pass over the finished accumulation -> also normals (V,3) f32 and
+    normals_code (what the download returned: 4 when the pass left a status)."""
     L = load()
     h = C.c_void_p()
     check(L.vh_mesh_weld_accum_create(slots_log2, reserve_triangles, int(fixed), C.byref(h)), "vh_mesh_weld_accum_create")
@@ -908,13 +980,21 @@ def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, rai
         k = np.zeros(int(counts[0]), dtype=np.uint64)
         f = np.zeros((int(counts[1]), 3), dtype=np.uint32)
         check(L.vh_mesh_weld_accum_download(h, v.ctypes.data, k.ctypes.data, f.ctypes.data, len(v), len(f), stream), "vh_mesh_weld_accum_download")
+        extra = {}
+        if normals_scale_log2 is not None and counts[2] == 0:
+            check(L.vh_mesh_weld_accum_normals(h, int(normals_scale_log2), stream), "vh_mesh_weld_accum_normals")
+            nrm = np.zeros((len(v), 3), dtype=np.float32)
+            ncode = L.vh_mesh_weld_accum_download_normals(h, nrm.ctypes.data, len(v), stream)
+            if ncode < 0 or (ncode != 0 and raise_on_status):
+                check(ncode, "vh_mesh_weld_accum_download_normals")
+            extra = dict(normals=nrm, normals_code=int(ncode))
     finally:
         L.vh_mesh_weld_accum_destroy(h)
         for b in buffers:
             b.free()
     return dict(vertices=np.ascontiguousarray(v["p"]), colors=np.ascontiguousarray(v["c"]), keys=k, faces=f,
                 counts=(int(counts[0]), int(counts[1])), stats={n: int(counts[i]) for i, n in enumerate(T.WELD_ACCUM_COUNTS)},
-                status=int(counts[2]), code=int(code))
+                status=int(counts[2]), code=int(code), **extra)
 
 
 # ---- sensor pre-processing (DSC/CameraUtil.cu) over the C ABI: numpy in, numpy out (tests, tools) ----

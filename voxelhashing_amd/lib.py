@@ -238,6 +238,15 @@ PROTOTYPES = {
     "vh_mesh_weld_accum_append": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP]),
     "vh_mesh_weld_accum_get_counts": (C.c_int, [_VP, P(C.c_uint32), _VP]),
     "vh_mesh_weld_accum_download": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP]),
+    "vh_mesh_vertex_normals": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_int32, _VP, _VP, _VP, _VP]),
+    "vh_mesh_normals_default_scale_log2": (C.c_int, [C.c_float, P(C.c_int32)]),
+    "vh_mesh_save_ply": (C.c_int, [_VP, _VP, _VP, C.c_uint64, _VP, C.c_uint64, P(C.c_float), C.c_char_p]),
+    "vh_mesh_weld_accum_normals": (C.c_int, [_VP, C.c_int32, _VP]),
+    "vh_mesh_weld_accum_download_normals": (C.c_int, [_VP, _VP, C.c_uint32, _VP]),
+    "vh_marching_cubes_set_indexed_normals": (C.c_int, [_VP, C.c_int]),
+    "vh_marching_cubes_download_indexed_normals": (C.c_int, [_VP, _VP]),
+    "vh_marching_cubes_get_mesh_normals_size": (C.c_int, [_VP, P(C.c_uint64)]),
+    "vh_marching_cubes_get_mesh_normals": (C.c_int, [_VP, _VP]),
     "vh_marching_cubes_begin_indexed": (C.c_int, [_VP]),
     "vh_marching_cubes_append_indexed": (C.c_int, [_VP, P(T.HashData), P(T.HashParams), P(C.c_float), P(C.c_float), C.c_int]),
     "vh_marching_cubes_finish_indexed": (C.c_int, [_VP]),

@@ -573,12 +573,15 @@ class Reconstruction:
                 h.m_depthShift, bytes(h.m_sensorName).decode(), h.m_colorCompressionType, h.m_depthCompressionType,
                 np.array(h.m_depthExtrinsic[:]), np.array(h.m_colorExtrinsic[:]))
 
-    def extractIsoSurface(self, filename=None, indexed=False):
+    def extractIsoSurface(self, filename=None, indexed=False, normals=False):
         """StopScanningAndExtractIsoSurfaceMC: marching cubes over the whole scene (through the chunk grid when
         streaming is on) -> (vertices, colours, faces); written as a PLY when a file name is given.  indexed (not in the
         reference): weld the triangles on the device instead of merging them on the host.  With streaming on that is
         refused here before any GPU work: extractIsoSurfaceIndexed() is the indexed extraction that also walks the
-        chunk grid."""
+        chunk grid.  normals (with indexed): vertex normals computed on the device after the weld, returned as
+        "normals" and written into the PLY."""
+        if normals and not indexed:
+            raise ValueError("vertex normals need the indexed extraction: only the welded mesh has vertices that faces share")
         if indexed and self.chunk_grid is not None:
             raise ValueError("indexed extraction is not available with streaming enabled (the chunk grid extracts per chunk)")
         if self.marching_cubes is None:
@@ -588,6 +591,7 @@ class Reconstruction:
             self.marching_cubes.setOfflineProcessing(bool(self.gas.s_offlineProcessing))
         mc = self.marching_cubes
         mc.clearMeshBuffer()
+        mc.setIndexedNormals(bool(normals))
         if self.chunk_grid is not None:
             pos = (self.scene.getLastRigidTransform().reshape(4, 4) @ np.array(list(self.gas.s_streamingPos) + [1.0], dtype=np.float32))[:3]
             mc.extractIsoSurfaceChunkGrid(self.chunk_grid, pos, self.gas.s_streamingRadius)
@@ -600,18 +604,21 @@ class Reconstruction:
             mc.saveMesh(filename, None, True)  # merges close vertices, writes the PLY and clears the buffer (.cpp:126-144)
         return mesh
 
-    def extractIsoSurfaceIndexed(self, filename=None):
+    def extractIsoSurfaceIndexed(self, filename=None, normals=False):
         """The indexed extraction with and without streaming (not in the reference): marching cubes with the triangles
         welded on the device -> (vertices, colours, faces); written as a PLY when a file name is given.  Without
         streaming this is extractIsoSurface(indexed=True); with streaming it walks the chunk grid as extractIsoSurface()
         does and welds every chunk's triangles into one mesh (the overlap of the chunks' boxes is taken once), so
-        nothing is merged on the host.  marching_cubes.indexed() has the mesh with its keys, indexed_stats() the counts."""
+        nothing is merged on the host.  marching_cubes.indexed() has the mesh with its keys, indexed_stats() the counts.
+        normals: vertex normals computed on the device over the finished mesh, returned as "normals" and written into
+        the PLY."""
         if self.chunk_grid is None:
-            return self.extractIsoSurface(filename, indexed=True)
+            return self.extractIsoSurface(filename, indexed=True, normals=normals)
         if self.marching_cubes is None:
             self.marching_cubes = E.CUDAMarchingCubesHashSDF(self.mp)
             self.marching_cubes.setOfflineProcessing(bool(self.gas.s_offlineProcessing))
         mc = self.marching_cubes
+        mc.setIndexedNormals(bool(normals))
         pos = (self.scene.getLastRigidTransform().reshape(4, 4) @ np.array(list(self.gas.s_streamingPos) + [1.0], dtype=np.float32))[:3]
         mc.extractIsoSurfaceIndexedChunkGrid(self.chunk_grid, pos, self.gas.s_streamingRadius)
         mesh = mc.mesh()

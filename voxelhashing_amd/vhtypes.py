@@ -143,6 +143,7 @@ class TriangleSource(C.Structure):
 # edges: 8 bits per vertex, bits 0-3 the edge 0..11 (vertlist order), bits 4-5 the snap code 0 / 1 / 2
 TRIANGLE_SOURCE_DTYPE = np.dtype([("cell", np.int32, 3), ("edges", np.uint32)])
 WELD_TABLE_FULL, WELD_KEY_RANGE = 1, 2  # bits of the weld's status word
+NORMALS_RANGE, NORMALS_BAD_INDEX = 1, 2  # bits of the vertex-normal pass's status word (VH_NORMALS_*)
 WELD_ACCUM_COUNTS = ("vertices", "faces", "status", "cells", "dropped", "rehashes")  # VH_WELD_ACCUM_*: what the accumulating weld reports
 WELD_ACCUM_MAX_APPENDS = 1 << 28
 
