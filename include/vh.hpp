@@ -220,7 +220,7 @@ private:
     vhStream_t m_stream;
     unsigned int m_numIntegratedFrames;
     int32_t m_lockEpoch;
-    vh::Mapped<uint32_t> m_occupied; // the fused integrate kernel mirrors {block count, frame number} here
+    vh::Mapped<uint32_t> m_occupied; // the fused integrate kernel mirrors {block count, frame number} here (DESIGN.md "What the device tells the host")
     bool m_occupiedPending;   // a frame was enqueued since the host value was last known exact
     bool m_counterCleared;    // d_hashCompactifiedCounter is known to be 0 (k_alloc clears it)
     std::unique_ptr<VhStageTimer> m_timer;
@@ -286,6 +286,7 @@ private:
     vh::Mapped<uint32_t> m_longestList;      // longest tile list the ray caster met lately
     bool m_largeTables;        // current choice of table size
     uint32_t m_quietFrames, m_tileCapacity;
+    uint32_t chooseTileCapacity(); // large tables as soon as a list outgrew the small ones, back after 30 frames without one
     vh::DevicePtr<uint32_t> d_schedule; // tiles by cost class, for the launch order of the next render()
     uint32_t m_phase;          // render() calls with intervals so far
     unsigned int m_preSplatsUsed;
@@ -479,7 +480,7 @@ private:
     enum { kPipelineBlocks = 4096 }; // staging capacity of a pipelined pass (16 MB per buffer)
     struct PipelineJob {
         bool haveOut, haveNext;
-        uint32_t outTag, outMost;
+        uint32_t outMost;
         int outSlot, inSlot;
         vh::vec3f nextPos;
         float nextRadius;
@@ -488,10 +489,12 @@ private:
     void pipelineStop();
     void pipelineWorker();
     void pipelineCheckInsert(int slot, bool block);
+    void pipelineAwaitWorker(); // until the worker has finished every job posted so far; VH_ERR_TIMEOUT after 40 s
     std::thread m_plThread;
     std::mutex m_plMutex;
     std::condition_variable m_plCv;
-    bool m_plStarted, m_plQuit;
+    bool m_plStarted;
+    std::atomic<bool> m_plQuit; // (the worker looks at it in its spin, without the mutex)
     PipelineJob m_plJob;
     std::atomic<unsigned int> m_plPosted, m_plDone; // jobs handed to / finished by the worker
     std::atomic<int> m_plError;                     // a vh error code the worker ran into (reported by the next call)
@@ -501,24 +504,23 @@ private:
     float m_plDecisionRadius;
     unsigned int m_plFrame;                         // frames the pipeline has run (slot = frame & 1)
     bool m_plOutThisFrame;                          // pipelineStreamOut() of the current frame launched a pass
-    uint32_t m_plOutTag, m_plOutMost;
-    struct { bool pending; uint32_t tag; unsigned int nIn; } m_plInsert[2]; // per staging slot: an insert whose outcome has not been looked at
+    uint32_t m_plOutMost;
+    struct { bool pending; unsigned int nIn; } m_plInsert[2]; // per staging slot: an insert whose outcome has not been looked at
     std::atomic<unsigned long long> m_plBlocksOut, m_plBlocksIn;
     vh::DevicePtr<SDFBlockDesc> d_plOutDesc[2];  // pass 1 -> pass 2 (device)
     vh::Mapped<SDFBlockDesc> m_plOutDesc[2];     // pass 2 writes the blocks it moves straight to the host
     vh::Mapped<vh::SDFBlock> m_plOutBlocks[2];
-    vh::Mapped<uint32_t> m_plOutMirror[2];       // {count, 0, tag}
+    vh::Published m_plOut[2]; // {count, 0, tag}: drawn by the main thread, awaited by the worker (never both: pipelineDecision() / pipelineDrain() lie between)
     vh::PinnedPtr<SDFBlockDesc> h_plInDesc[2];   // pinned staging of the worker's upload
     vh::PinnedPtr<vh::SDFBlock> h_plInBlocks[2];
     vh::DevicePtr<SDFBlockDesc> d_plInDesc[2];
     vh::DevicePtr<vh::SDFBlock> d_plInBlocks[2];
-    uint32_t m_plTag;
     void streamInLaunches();
     unsigned int m_numFailedInserts;
     // the outcome of a stream-in pass (vh_stream_in_device), mapped pinned {failed, 0, tag, exhausted, failed indices ...}: one
-    // per pipeline slot, and kSyncInSlot for the passes of streamInLaunches()
+    // per pipeline slot, and kSyncInSlot for the passes of streamInLaunches() (DESIGN.md "What the device tells the host")
     enum { kSyncInSlot = 2 };
-    vh::Mapped<uint32_t> m_inMirror[3];
+    vh::Published m_in[3];
 
     unsigned int m_maxNumberOfSDFBlocksIntegrateFromGlobalHash;
 
@@ -526,12 +528,12 @@ private:
     vh::PinnedPtr<vh::SDFBlock> h_SDFBlockOutput;
     vh::PinnedPtr<SDFBlockDesc> h_SDFBlockDescInput; // staging for the worker's H2D
     vh::PinnedPtr<vh::SDFBlock> h_SDFBlockInput;
-    vh::Mapped<uint32_t> m_mirror;      // {word 0, word 1, tag} published by the device (vh_publish_words)
-    uint32_t m_mirrorTag;
-    vh::Mapped<uint32_t> m_probe;       // {count, 0, tag} of the stream-out probe
-    uint32_t m_probeTag;
+    vh::Published m_mirror;             // {word 0, word 1, tag} published by the device (vh_publish_words)
+    vh::Published m_probe;              // {count, 0, tag} of the stream-out probe
     vh::DevicePtr<unsigned int> d_probeCounter;
     std::unique_lock<std::mutex> m_streamInLock; // held between streamInWait() and streamInFinish()
+    // returns once the device has published `record`'s tag on the scene's stream (spinSeconds 0: synchronises at once); throws whatIfNot if it never does
+    void awaitPublished(const vh::Published& record, const char* whatIfNot, double spinSeconds = vh::kPublishSyncSeconds);
     // values of up to two device words once the stream has reached this point, without a blocking driver call
     void readBack(const unsigned int* d_word0, const unsigned int* d_word1, unsigned int* out0, unsigned int* out1);
     vh::DevicePtr<SDFBlockDesc> d_SDFBlockDescOutput;
@@ -556,6 +558,8 @@ private:
     mutable std::mutex m_gridMutex;
 
     unsigned int m_currentPart;
+    struct PartWindow { unsigned int threadsPerPart, start; }; // hash entries the NEXT stream-out pass scans: the same for the pass, its probe and the pipelined pass
+    PartWindow nextPartWindow(const HashParams& hp, bool useParts) const;
     unsigned int m_streamOutParts;
 
     std::thread m_thread;

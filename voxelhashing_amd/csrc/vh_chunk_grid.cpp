@@ -15,7 +15,6 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -48,11 +47,7 @@ void CUDASceneRepChunkGrid::AutoResetEvent::wait()
     // Frames come every 100-250 us and each hands over to the other thread four times: a condition variable's wake-up
     // (tens of microseconds) would be most of the frame's slack.  So the waiter looks at the flag for a frame or two first
     // and only then goes to sleep.
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned int spins = 0;
-    while (!signaled.load(std::memory_order_acquire)) {
-        if ((++spins & 0xffu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(300)) break;
-    }
+    (void)vh::spinUntil([this] { return signaled.load(std::memory_order_acquire); }, vh::kSpinBeforeSleepSeconds, false);
     std::unique_lock<std::mutex> l(mtx);
     cv.wait(l, [this] { return signaled.load(std::memory_order_acquire); });
     signaled.store(false, std::memory_order_release);
@@ -77,7 +72,6 @@ CUDASceneRepChunkGrid::CUDASceneRepChunkGrid(CUDASceneRepHashSDF* sceneRepHashSD
     m_numFailedInserts = 0;
     m_streamOutParts = streamOutParts ? streamOutParts : 1;
     m_maxNumberOfSDFBlocksIntegrateFromGlobalHash = 100000; // DSC/CUDASceneRepChunkGrid.h:162
-    m_mirrorTag = 0; m_probeTag = 0;
     s_terminateThread = true; // by default the thread is disabled
     s_nStreamdInBlocks = 0; s_nStreamdOutBlocks = 0;
     s_posCamera = { 0.0f, 0.0f, 0.0f };
@@ -89,9 +83,9 @@ CUDASceneRepChunkGrid::CUDASceneRepChunkGrid(CUDASceneRepHashSDF* sceneRepHashSD
     m_plDecisionValid = false;
     m_plDecisionPos = { 0.0f, 0.0f, 0.0f };
     m_plDecisionRadius = 0.0f;
-    m_plFrame = 0; m_plOutThisFrame = false; m_plOutTag = 0; m_plOutMost = 0;
-    for (int i = 0; i < 2; i++) { m_plInsert[i].pending = false; m_plInsert[i].tag = 0; m_plInsert[i].nIn = 0; }
-    m_plBlocksOut = 0; m_plBlocksIn = 0; m_plTag = 0;
+    m_plFrame = 0; m_plOutThisFrame = false; m_plOutMost = 0;
+    for (int i = 0; i < 2; i++) { m_plInsert[i].pending = false; m_plInsert[i].nIn = 0; }
+    m_plBlocksOut = 0; m_plBlocksIn = 0;
     create(voxelExtends, gridDimensions, minGridPos, initialChunkListSize, streamingEnabled);
 }
 
@@ -114,10 +108,8 @@ void CUDASceneRepChunkGrid::create(const vh::vec3f& voxelExtends, const vh::vec3
     h_SDFBlockOutput = vh::pinnedAlloc<vh::SDFBlock>(n, "hipHostMalloc");
     h_SDFBlockDescInput = vh::pinnedAlloc<SDFBlockDesc>(n, "hipHostMalloc");
     h_SDFBlockInput = vh::pinnedAlloc<vh::SDFBlock>(n, "hipHostMalloc");
-    m_mirror = vh::Mapped<uint32_t>(4, "hipHostMalloc");
-    std::memset(m_mirror.host(), 0, sizeof(uint32_t) * 4);
-    m_probe = vh::Mapped<uint32_t>(4, "hipHostMalloc");
-    std::memset(m_probe.host(), 0, sizeof(uint32_t) * 4);
+    m_mirror = vh::Published(4, "hipHostMalloc");
+    m_probe = vh::Published(4, "hipHostMalloc");
     d_probeCounter = vh::deviceAlloc<unsigned int>(1, "hipMalloc");
     checkHip(hipMemset(d_probeCounter.get(), 0, sizeof(unsigned int)), "hipMemset");
     d_SDFBlockDescOutput = vh::deviceAlloc<SDFBlockDesc>(n, "hipMalloc");
@@ -127,11 +119,7 @@ void CUDASceneRepChunkGrid::create(const vh::vec3f& voxelExtends, const vh::vec3
     d_SDFBlockCounter = vh::deviceAlloc<unsigned int>(1, "hipMalloc");
     d_insertFailed = vh::deviceAlloc<unsigned int>(1 + 2 * n, "hipMalloc");
     checkHip(hipMemset(d_insertFailed.get(), 0, sizeof(unsigned int)), "hipMemset");
-    for (int i = 0; i < 3; i++) {
-        const size_t words = 4 + (i == kSyncInSlot ? n : (size_t)kPipelineBlocks);
-        m_inMirror[i] = vh::Mapped<uint32_t>(words, "hipHostMalloc");
-        std::memset(m_inMirror[i].host(), 0, sizeof(uint32_t) * words);
-    }
+    for (int i = 0; i < 3; i++) m_in[i] = vh::Published(4 + (i == kSyncInSlot ? n : (size_t)kPipelineBlocks), "hipHostMalloc");
     d_bitMask = vh::deviceAlloc<unsigned int>(m_bitMask.size(), "hipMalloc");
     checkHip(hipGetDevice(&m_device), "hipGetDevice"); // one instance is bound to one device
     m_copyStream = vh::makeStream("hipStreamCreate");
@@ -405,25 +393,28 @@ void CUDASceneRepChunkGrid::streamOutToCPU(const vh::vec3f& posCamera, float rad
 
 // The reference reads its counters back with a blocking cudaMemcpy (DSC/CUDASceneRepChunkGrid.cu:88, :140).  Here a
 // one-thread kernel publishes them to mapped host memory behind the work already in the stream and the host polls the
-// tag: no synchronisation call, no copy.  (After two seconds without the tag it synchronises and copies after all.)
+// tag: no synchronisation call, no copy.  (After spinSeconds without the tag it synchronises and looks again.)
+void CUDASceneRepChunkGrid::awaitPublished(const vh::Published& record, const char* whatIfNot, double spinSeconds)
+{
+    if (record.wait(spinSeconds).ok) return;
+    checkHip(hipStreamSynchronize((hipStream_t)m_sceneRepHashSDF->getStream()), "hipStreamSynchronize");
+    if (!record.arrived()) throw vh::Error(-(int)hipErrorUnknown, whatIfNot);
+}
+
 void CUDASceneRepChunkGrid::readBack(const unsigned int* d_word0, const unsigned int* d_word1, unsigned int* out0, unsigned int* out1)
 {
-    vhStream_t stream = m_sceneRepHashSDF->getStream();
-    const uint32_t tag = ++m_mirrorTag ? m_mirrorTag : ++m_mirrorTag; // never 0
-    check(vh_publish_words(d_word0, d_word1, m_mirror.device(), tag, stream), "vh_publish_words");
-    volatile uint32_t* m = m_mirror.host();
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned int spins = 0;
-    while (m[2] != tag) {
-        if ((++spins & 0x3ffu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-            checkHip(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
-            if (m[2] != tag) throw vh::Error(-(int)hipErrorUnknown, "read-back: the device did not publish its counters");
-            break;
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (out0) *out0 = m[0];
-    if (out1) *out1 = m[1];
+    check(vh_publish_words(d_word0, d_word1, m_mirror.device(), m_mirror.nextTag(), m_sceneRepHashSDF->getStream()), "vh_publish_words");
+    awaitPublished(m_mirror, "read-back: the device did not publish its counters");
+    if (out0) *out0 = m_mirror.word(0);
+    if (out1) *out1 = m_mirror.word(1);
+}
+
+CUDASceneRepChunkGrid::PartWindow CUDASceneRepChunkGrid::nextPartWindow(const HashParams& hp, bool useParts) const
+{
+    const unsigned int numEntries = hp.m_hashNumBuckets * hp.m_hashBucketSize;
+    if (!useParts) return { numEntries, 0u };
+    const unsigned int threadsPerPart = (numEntries + m_streamOutParts - 1) / m_streamOutParts;
+    return { threadsPerPart, m_currentPart * threadsPerPart };
 }
 
 // DSC/CUDASceneRepChunkGrid.cpp:55-105
@@ -447,13 +438,9 @@ void CUDASceneRepChunkGrid::streamOutToCPUPass0GPU(const vh::vec3f& posCamera, f
     m_sceneRepHashSDF->noteTableEdited();
     check(vh_memset(d_SDFBlockCounter.get(), 0, sizeof(unsigned int), stream), "clearSDFBlockCounter");
 
-    const unsigned int numEntries = hp.m_hashNumBuckets * hp.m_hashBucketSize;
-    unsigned int threadsPerPart = (numEntries + m_streamOutParts - 1) / m_streamOutParts;
-    if (!useParts) threadsPerPart = numEntries;
-    const unsigned int start = useParts ? m_currentPart * threadsPerPart : 0;
-
+    const PartWindow w = nextPartWindow(hp, useParts);
     const float cam[3] = { posCamera.x, posCamera.y, posCamera.z };
-    check(vh_stream_out_pass1(&hd, &hp, threadsPerPart, start, radius, cam, d_SDFBlockCounter.get(), d_SDFBlockDescOutput.get(),
+    check(vh_stream_out_pass1(&hd, &hp, w.threadsPerPart, w.start, radius, cam, d_SDFBlockCounter.get(), d_SDFBlockDescOutput.get(),
                               m_maxNumberOfSDFBlocksIntegrateFromGlobalHash, token, stream), "integrateFromGlobalHashPass1CUDA");
     unsigned int nSDFBlockDescs = 0;
     readBack(d_SDFBlockCounter.get(), nullptr, &nSDFBlockDescs, nullptr);
@@ -482,30 +469,16 @@ void CUDASceneRepChunkGrid::probeStreamOut(const vh::vec3f& posCamera, float rad
 {
     const HashParams& hp = m_sceneRepHashSDF->getHashParams();
     HashData& hd = m_sceneRepHashSDF->getHashData();
-    const unsigned int numEntries = hp.m_hashNumBuckets * hp.m_hashBucketSize;
-    unsigned int threadsPerPart = (numEntries + m_streamOutParts - 1) / m_streamOutParts;
-    if (!useParts) threadsPerPart = numEntries;
-    const unsigned int start = useParts ? m_currentPart * threadsPerPart : 0; // the part the NEXT pass 0 scans
+    const PartWindow w = nextPartWindow(hp, useParts); // the part the NEXT pass 0 scans
     const float cam[3] = { posCamera.x, posCamera.y, posCamera.z };
-    m_probeTag = ++m_probeTag ? m_probeTag : 1u;
-    check(vh_stream_out_probe(&hd, &hp, threadsPerPart, start, radius, cam, d_probeCounter.get(), m_probe.device(), m_probeTag, m_sceneRepHashSDF->getStream()),
+    check(vh_stream_out_probe(&hd, &hp, w.threadsPerPart, w.start, radius, cam, d_probeCounter.get(), m_probe.device(), m_probe.nextTag(), m_sceneRepHashSDF->getStream()),
           "vh_stream_out_probe");
 }
 
 unsigned int CUDASceneRepChunkGrid::probeResult()
 {
-    volatile uint32_t* m = m_probe.host();
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned int spins = 0;
-    while (m[2] != m_probeTag) {
-        if ((++spins & 0x3ffu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-            checkHip(hipStreamSynchronize((hipStream_t)m_sceneRepHashSDF->getStream()), "hipStreamSynchronize");
-            if (m[2] != m_probeTag) throw vh::Error(-(int)hipErrorUnknown, "stream-out probe: the device did not publish its count");
-            break;
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return m[0];
+    awaitPublished(m_probe, "stream-out probe: the device did not publish its count");
+    return m_probe.word(0);
 }
 
 // streamOutToCPUPass0GPU(multiThreaded = true) of a part the probe found nothing to move out of
@@ -691,13 +664,11 @@ void CUDASceneRepChunkGrid::streamInLaunches()
     vhStream_t stream = m_sceneRepHashSDF->getStream();
     const int32_t token = m_sceneRepHashSDF->nextLockToken();
     m_sceneRepHashSDF->noteTableEdited();
-    const uint32_t tag = ++m_plTag ? m_plTag : ++m_plTag;
     // (no chunk bit: the host's copy of the bit mask is the one that counts here)
     check(vh_stream_in_device(&hd, &hp, s_nStreamdInBlocks, d_SDFBlockDescInput.get(), (const VhVoxel*)d_SDFBlockInput.get(), token, d_insertFailed.get(), nullptr,
-                              0xffffffffu, m_inMirror[kSyncInSlot].device(), tag, stream), "chunkToGlobalHashPass1CUDA + Pass2CUDA");
+                              0xffffffffu, m_in[kSyncInSlot].device(), m_in[kSyncInSlot].nextTag(), stream), "chunkToGlobalHashPass1CUDA + Pass2CUDA");
     checkHip(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
-    if (((volatile uint32_t*)m_inMirror[kSyncInSlot].host())[2] != tag) throw vh::Error(-(int)hipErrorUnknown, "stream-in: the device did not publish its pass");
-    std::atomic_thread_fence(std::memory_order_acquire);
+    if (!m_in[kSyncInSlot].arrived()) throw vh::Error(-(int)hipErrorUnknown, "stream-in: the device did not publish its pass");
     if (refileFailedInserts(kSyncInSlot, h_SDFBlockDescInput.get(), h_SDFBlockInput.get(), s_nStreamdInBlocks))
         throw vh::Error(VH_ERR_HEAP_EXHAUSTED, "stream-in: not enough free SDF blocks");
 }
@@ -709,15 +680,15 @@ void CUDASceneRepChunkGrid::streamInLaunches()
 // the union of heap and table.  They come in again with a later pass.  Returns true if the heap was exhausted.
 bool CUDASceneRepChunkGrid::refileFailedInserts(int slot, const SDFBlockDesc* descs, const vh::SDFBlock* blocks, unsigned int& nIn)
 {
-    const volatile uint32_t* m = m_inMirror[slot].host();
-    const bool exhausted = m[3] != 0u;
-    const unsigned int nFailed = exhausted ? nIn : m[0];
+    const vh::Published& m = m_in[slot]; // (arrived: the callers have looked)
+    const bool exhausted = m.word(3) != 0u;
+    const unsigned int nFailed = exhausted ? nIn : m.word(0);
     if (exhausted) {
         integrateInChunkGrid(descs, blocks, nIn);
     } else {
         if (nFailed > nIn) throw vh::Error(VH_ERR_INSERT_FAILED, "stream-in: corrupt list of failed inserts");
         for (unsigned int k = 0; k < nFailed; k++) {
-            const unsigned int i = m[4 + k];
+            const unsigned int i = m.word(4 + k);
             if (i >= nIn) throw vh::Error(VH_ERR_INSERT_FAILED, "stream-in: corrupt list of failed inserts");
             integrateInChunkGrid(&descs[i], &blocks[i], 1);
         }
@@ -825,8 +796,7 @@ void CUDASceneRepChunkGrid::pipelineStart()
         d_plOutDesc[i] = vh::deviceAlloc<SDFBlockDesc>(n, "hipMalloc");
         m_plOutDesc[i] = vh::Mapped<SDFBlockDesc>(n, "hipHostMalloc");
         m_plOutBlocks[i] = vh::Mapped<vh::SDFBlock>(n, "hipHostMalloc");
-        m_plOutMirror[i] = vh::Mapped<uint32_t>(4, "hipHostMalloc");
-        std::memset(m_plOutMirror[i].host(), 0, sizeof(uint32_t) * 4);
+        m_plOut[i] = vh::Published(4, "hipHostMalloc");
         h_plInDesc[i] = vh::pinnedAlloc<SDFBlockDesc>(n, "hipHostMalloc");
         h_plInBlocks[i] = vh::pinnedAlloc<vh::SDFBlock>(n, "hipHostMalloc");
         d_plInDesc[i] = vh::deviceAlloc<SDFBlockDesc>(n, "hipMalloc");
@@ -858,11 +828,7 @@ void CUDASceneRepChunkGrid::pipelineWorker()
         PipelineJob job;
         {
             // frames come every 100-200 us: look at the counter for a while before going to sleep (AutoResetEvent::wait)
-            const auto t0 = std::chrono::steady_clock::now();
-            unsigned int spins = 0;
-            while (m_plPosted.load(std::memory_order_acquire) == done && !m_plQuit) {
-                if ((++spins & 0xffu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(300)) break;
-            }
+            (void)vh::spinUntil([&] { return m_plPosted.load(std::memory_order_acquire) != done || m_plQuit; }, vh::kSpinBeforeSleepSeconds, false);
             std::unique_lock<std::mutex> l(m_plMutex);
             m_plCv.wait(l, [&] { return m_plQuit || m_plPosted.load(std::memory_order_acquire) != done; });
             if (m_plQuit) return;
@@ -871,15 +837,9 @@ void CUDASceneRepChunkGrid::pipelineWorker()
         try {
             if (job.haveOut) {
                 // the blocks that left: in the mapped staging buffer once the device has published the pass's tag
-                volatile uint32_t* m = m_plOutMirror[job.outSlot].host();
-                const auto t0 = std::chrono::steady_clock::now();
-                unsigned int spins = 0;
-                while (m[2] != job.outTag) {
-                    if ((++spins & 0xfffu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(30))
-                        throw vh::Error(VH_ERR_TIMEOUT, "streaming pipeline: the device did not publish its stream-out pass for 30 s");
-                }
-                std::atomic_thread_fence(std::memory_order_acquire);
-                const unsigned int n = m[0];
+                if (!m_plOut[job.outSlot].wait(vh::kDeviceSilentSeconds).ok)
+                    throw vh::Error(VH_ERR_TIMEOUT, "streaming pipeline: the device did not publish its stream-out pass for 30 s");
+                const unsigned int n = m_plOut[job.outSlot].word(0);
                 if (n > job.outMost)
                     throw vh::Error(VH_ERR_STAGING_OVERFLOW, "streaming pipeline: the stream-out pass found more blocks than its probe (blocks are lost)");
                 if (n != 0) integrateInChunkGrid(m_plOutDesc[job.outSlot].host(), m_plOutBlocks[job.outSlot].host(), n);
@@ -910,13 +870,8 @@ bool CUDASceneRepChunkGrid::pipelineHasDecision(const vh::vec3f& posCamera, floa
 void CUDASceneRepChunkGrid::pipelineCheckInsert(int slot, bool block)
 {
     if (!m_plInsert[slot].pending) return;
-    volatile uint32_t* m = m_inMirror[slot].host();
-    if (m[2] != m_plInsert[slot].tag) {
-        if (!block) return;
-        checkHip(hipStreamSynchronize((hipStream_t)m_sceneRepHashSDF->getStream()), "hipStreamSynchronize");
-        if (m[2] != m_plInsert[slot].tag) throw vh::Error(-(int)hipErrorUnknown, "streaming pipeline: the device did not publish its stream-in pass");
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
+    if (!block && !m_in[slot].arrived()) return;
+    awaitPublished(m_in[slot], "streaming pipeline: the device did not publish its stream-in pass", 0.0);
     m_plInsert[slot].pending = false;
     unsigned int nIn = m_plInsert[slot].nIn;
     // (on exhaustion the chunk's bit is set again in the host's copy; the device's copy was not touched)
@@ -924,17 +879,18 @@ void CUDASceneRepChunkGrid::pipelineCheckInsert(int slot, bool block)
     m_plBlocksIn += nIn;
 }
 
+void CUDASceneRepChunkGrid::pipelineAwaitWorker()
+{
+    const unsigned int posted = m_plPosted.load(std::memory_order_acquire);
+    if (!vh::spinUntil([&] { return m_plDone.load(std::memory_order_acquire) == posted; }, vh::kWorkerSilentSeconds, false).ok)
+        throw vh::Error(VH_ERR_TIMEOUT, "streaming pipeline: the worker thread did not finish its job for 40 s");
+}
+
 CUDASceneRepChunkGrid::StreamDecision CUDASceneRepChunkGrid::pipelineDecision()
 {
     if (!m_plStarted || !m_plDecisionValid) throw vh::Error(VH_ERR_BAD_ARGUMENT, "pipelineDecision(): pipelineAsk() has not asked for one");
     // the worker has had the rest of the previous frame's device time
-    const unsigned int posted = m_plPosted.load(std::memory_order_acquire);
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned int spins = 0;
-    while (m_plDone.load(std::memory_order_acquire) != posted) {
-        if ((++spins & 0xfffu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(40))
-            throw vh::Error(VH_ERR_TIMEOUT, "streaming pipeline: the worker thread did not answer for 40 s");
-    }
+    pipelineAwaitWorker();
     const int err = m_plError.exchange(0, std::memory_order_acq_rel);
     if (err != 0) {
         m_plDecisionValid = false;
@@ -960,18 +916,14 @@ bool CUDASceneRepChunkGrid::pipelineStreamOut(const vh::vec3f& posCamera, float 
         vhStream_t stream = m_sceneRepHashSDF->getStream();
         const int32_t token = m_sceneRepHashSDF->nextLockToken(); // = resetHashBucketMutexCUDA
         m_sceneRepHashSDF->noteTableEdited();
-        const unsigned int numEntries = hp.m_hashNumBuckets * hp.m_hashBucketSize;
-        unsigned int threadsPerPart = (numEntries + m_streamOutParts - 1) / m_streamOutParts;
-        if (!useParts) threadsPerPart = numEntries;
-        const unsigned int start = useParts ? m_currentPart * threadsPerPart : 0;
+        const PartWindow w = nextPartWindow(hp, useParts);
         const float cam[3] = { posCamera.x, posCamera.y, posCamera.z };
         // pass 1 lists into device memory (pass 2 reads the list back); pass 2 writes blocks AND descriptors to the host
-        check(vh_stream_out_device(&hd, &hp, threadsPerPart, start, radius, cam, d_SDFBlockCounter.get(), d_plOutDesc[slot].get(), (VhVoxel*)m_plOutBlocks[slot].device(),
+        check(vh_stream_out_device(&hd, &hp, w.threadsPerPart, w.start, radius, cam, d_SDFBlockCounter.get(), d_plOutDesc[slot].get(), (VhVoxel*)m_plOutBlocks[slot].device(),
                                    mostBlocks, token, d_bitMask.get(), stream), "vh_stream_out_device");
         checkHip(hipMemcpyAsync(m_plOutDesc[slot].host(), d_plOutDesc[slot].get(), sizeof(SDFBlockDesc) * mostBlocks, hipMemcpyDeviceToHost, (hipStream_t)stream), "descs to host");
-        m_plOutTag = ++m_plTag ? m_plTag : ++m_plTag;
         m_plOutMost = mostBlocks;
-        check(vh_publish_count(d_SDFBlockCounter.get(), m_plOutMirror[slot].device(), m_plOutTag, stream), "vh_publish_count");
+        check(vh_publish_count(d_SDFBlockCounter.get(), m_plOut[slot].device(), m_plOut[slot].nextTag(), stream), "vh_publish_count");
         m_plOutThisFrame = true;
     } else {
         (void)m_sceneRepHashSDF->nextLockToken(); // (the pass draws one: keep the sequence of tokens the same)
@@ -990,10 +942,9 @@ void CUDASceneRepChunkGrid::pipelineStreamIn(const StreamDecision& d)
     HashData& hd = m_sceneRepHashSDF->getHashData();
     const int32_t token = m_sceneRepHashSDF->nextLockToken();
     m_sceneRepHashSDF->noteTableEdited();
-    const uint32_t tag = ++m_plTag ? m_plTag : ++m_plTag;
     check(vh_stream_in_device(&hd, &hp, d.nIn, d_plInDesc[d.slot].get(), (const VhVoxel*)d_plInBlocks[d.slot].get(), token, d_insertFailed.get(), d_bitMask.get(), d.chunkBit,
-                              m_inMirror[d.slot].device(), tag, m_sceneRepHashSDF->getStream()), "vh_stream_in_device");
-    m_plInsert[d.slot].pending = true; m_plInsert[d.slot].tag = tag; m_plInsert[d.slot].nIn = d.nIn;
+                              m_in[d.slot].device(), m_in[d.slot].nextTag(), m_sceneRepHashSDF->getStream()), "vh_stream_in_device");
+    m_plInsert[d.slot].pending = true; m_plInsert[d.slot].nIn = d.nIn;
 }
 
 void CUDASceneRepChunkGrid::pipelineAsk(bool haveNext, const vh::vec3f& nextPosCamera, float nextRadius)
@@ -1006,7 +957,6 @@ void CUDASceneRepChunkGrid::pipelineAsk(bool haveNext, const vh::vec3f& nextPosC
     {
         std::lock_guard<std::mutex> l(m_plMutex);
         m_plJob.haveOut = m_plOutThisFrame;
-        m_plJob.outTag = m_plOutTag;
         m_plJob.outMost = m_plOutMost;
         m_plJob.outSlot = (int)(m_plFrame & 1u);
         m_plJob.haveNext = haveNext;
@@ -1034,13 +984,7 @@ void CUDASceneRepChunkGrid::pipelineReturn(const StreamDecision& d, const vh::ve
 void CUDASceneRepChunkGrid::pipelineDrain(bool undo)
 {
     if (!m_plStarted) return;
-    const unsigned int posted = m_plPosted.load(std::memory_order_acquire);
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned int spins = 0;
-    while (m_plDone.load(std::memory_order_acquire) != posted) {
-        if ((++spins & 0xfffu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(40))
-            throw vh::Error(VH_ERR_TIMEOUT, "streaming pipeline: the worker thread did not finish for 40 s");
-    }
+    pipelineAwaitWorker();
     if (undo && m_plDecisionValid) {
         // a choice nobody will use: the chunk goes back into the grid (its bit with it; the device's copy still has it set)
         m_plDecisionValid = false;

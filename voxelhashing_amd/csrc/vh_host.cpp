@@ -448,7 +448,7 @@ void CUDASceneRepHashSDF::pollOccupiedCount(bool block)
     }
     // the fused integrate kernel stores the count of its frame into the mapped word; without blocking this is
     // the count of the most recent frame whose kernel has run
-    m_hashParams.m_numOccupiedBlocks = ((volatile uint32_t*)m_occupied.host())[0];
+    m_hashParams.m_numOccupiedBlocks = vh::loadRelaxed(&m_occupied.host()[0]);
 }
 
 const HashParams& CUDASceneRepHashSDF::getHashParams()
@@ -475,7 +475,7 @@ unsigned int CUDASceneRepHashSDF::getHeapFreeCount()
     return count + 1;
 }
 
-unsigned int CUDASceneRepHashSDF::getNumFramesStartedOnDevice() const { return ((volatile uint32_t*)m_occupied.host())[1]; }
+unsigned int CUDASceneRepHashSDF::getNumFramesStartedOnDevice() const { return vh::loadRelaxed(&m_occupied.host()[1]); }
 
 // the alloc + compactify passes of the frame whose pose has just been set, as a job
 void CUDASceneRepHashSDF::prepareJob(const DepthCameraData& cam, const DepthCameraParams& cp, const unsigned int* d_bitMask)
@@ -820,6 +820,16 @@ void CUDARayCastSDF::castRays(const HashData& hashData, const HashParams& hashPa
           "castRays");
 }
 
+// Table size for a splat, from what the ray caster reported two frames ago (mapped host word, no synchronisation):
+// large tables as soon as a list outgrew the small ones, back after 30 frames without one.
+uint32_t CUDARayCastSDF::chooseTileCapacity()
+{
+    const uint32_t longest = vh::loadRelaxed(m_longestList.host());
+    if (longest > (uint32_t)VH_TILE_LIST_CAPACITY) { m_largeTables = true; m_quietFrames = 0; }
+    else if (m_largeTables && ++m_quietFrames > 30) m_largeTables = false;
+    return m_largeTables ? VH_TILE_LIST_CAPACITY_LARGE : VH_TILE_LIST_CAPACITY;
+}
+
 // DSC/CUDARayCastSDF.cpp:38-72 with rayIntervalSplatting :84-100 (view matrices only)
 void CUDARayCastSDF::render(const HashData& hashData, const HashParams& hashParams, const DepthCameraParams& cp,
                             const vh::mat4f& lastRigidTransform, VhFrameJob* coLaunch)
@@ -851,12 +861,7 @@ void CUDARayCastSDF::render(const HashData& hashData, const HashParams& hashPara
     } else if (m_useIntervals) {
         if (timedAll) m_timer->start(ST_SPLAT, (hipStream_t)m_stream);
         ++m_phase;
-        // Table size for this frame, from what the ray caster reported two frames ago (mapped host word, no
-        // synchronisation): large tables as soon as a list outgrew the small ones, back after 30 frames without one.
-        const uint32_t longest = *(volatile uint32_t*)m_longestList.host();
-        if (longest > (uint32_t)VH_TILE_LIST_CAPACITY) { m_largeTables = true; m_quietFrames = 0; }
-        else if (m_largeTables && ++m_quietFrames > 30) m_largeTables = false;
-        m_tileCapacity = m_largeTables ? VH_TILE_LIST_CAPACITY_LARGE : VH_TILE_LIST_CAPACITY;
+        m_tileCapacity = chooseTileCapacity();
         check(vh_ray_interval_splat(&hashData, &hashParams, &cp, &m_params, d_tileHeads.get(), d_tileBlocks.get(), m_tileCapacity, d_schedule.get(), m_phase, m_longestList.device(), m_stream), "rayIntervalSplatCUDA");
         if (timedAll) m_timer->stop(ST_SPLAT, (hipStream_t)m_stream);
     }
@@ -889,10 +894,7 @@ void CUDARayCastSDF::render(const HashData& hashData, const HashParams& hashPara
             RayCastParams next = m_params;
             std::memcpy(next.m_viewMatrix, coLaunch->hashParams.m_rigidTransformInverse, sizeof(next.m_viewMatrix));
             std::memcpy(next.m_viewMatrixInverse, coLaunch->hashParams.m_rigidTransform, sizeof(next.m_viewMatrixInverse));
-            const uint32_t longest = *(volatile uint32_t*)m_longestList.host();
-            if (longest > (uint32_t)VH_TILE_LIST_CAPACITY) { m_largeTables = true; m_quietFrames = 0; }
-            else if (m_largeTables && ++m_quietFrames > 30) m_largeTables = false;
-            const uint32_t capacity = m_largeTables ? VH_TILE_LIST_CAPACITY_LARGE : VH_TILE_LIST_CAPACITY;
+            const uint32_t capacity = chooseTileCapacity();
             check(vh_compute_normals_co2(m_data.d_normals, m_data.d_depth4, m_params.m_width, m_params.m_height, coLaunch, &next, d_tileHeads.get(), d_tileBlocks.get(),
                                          capacity, d_schedule.get(), m_phase + 1u, m_longestList.device(), m_stream), "computeNormals");
             m_preSplat.valid = true;

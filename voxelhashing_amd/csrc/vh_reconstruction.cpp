@@ -35,7 +35,6 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include <thread>
 
 #include "vh_handles.hpp"
 #include "vh_host_util.hpp"
@@ -313,20 +312,16 @@ DepthCameraData Reconstruction::upload(const SequenceFrame& f)
     if (m_slotSceneFrame[slot] != 0 && !m_tracking) {
         // the slot's last frame was the scene's frame number m_slotSceneFrame[slot]: done once a later frame's pass has started
         const unsigned int need = m_slotSceneFrame[slot] + 1u;
-        const double w0 = now();
-        bool waited = false;
         const VhSceneOptions& so = m_sceneRep->getOptions();
         const bool mirrored = m_opt.s_integrationEnabled && !so.s_useReferenceLaunchSequence; // only the fused pass keeps the counter
-        while (m_sceneRep->getNumFramesStartedOnDevice() < need) {
-            if (!mirrored || m_sceneRep->getNumIntegratedFrames() < need) { // nothing later has been enqueued: only a synchronisation tells
-                checkHip(hipStreamSynchronize(ms), "hipStreamSynchronize");
-                break;
-            }
-            std::this_thread::yield();
-            waited = true;
-            if (now() - w0 > 30.0) throw vh::Error(VH_ERR_TIMEOUT, "Reconstruction: the device made no progress for 30 s");
+        auto started = [&] { return m_sceneRep->getNumFramesStartedOnDevice() >= need; };
+        if (!mirrored || m_sceneRep->getNumIntegratedFrames() < need) { // nothing later has been enqueued: only a synchronisation tells
+            if (!started()) checkHip(hipStreamSynchronize(ms), "hipStreamSynchronize");
+        } else {
+            const vh::Waited w = vh::spinUntil(started, vh::kDeviceSilentSeconds, true);
+            if (!w.ok) throw vh::Error(VH_ERR_TIMEOUT, "Reconstruction: the device made no progress for 30 s");
+            m_stats.hostWaitSeconds += w.seconds;
         }
-        if (waited) m_stats.hostWaitSeconds += now() - w0;
     }
     auto timerEvent = [&]() {
         if (m_timerPool.empty()) return vh::makeEvent(true);
@@ -608,7 +603,7 @@ void Reconstruction::frameTracked(const SequenceFrame& f)
         m_rayCast->render(m_sceneRep->getHashData(), m_sceneRep->getHashParams(), m_cp, lastTransform, nullptr); // :763
         const RayCastData& rd = m_rayCast->getRayCastData();
         const vh::IcpPyramid in = vh::icpPyramid(d_trkInput[slot][0].get(), d_trkInputNormal[slot][0].get(), d_trkInput[slot], d_trkInputNormal[slot]);
-        const uint32_t tag = ++m_trkTag;
+        const uint32_t tag = vh::nextTag(m_trkTag);
         // one launch per iteration where a level allows it; the last step stores the result and the tag into mapped memory
         if (m_icpRGBD) {
             const vh::IcpPyramid mdl = vh::icpPyramid(rd.d_depth4, rd.d_normals, m_icpRGBD->model, m_icpRGBD->modelNormal);
@@ -621,12 +616,9 @@ void Reconstruction::frameTracked(const SequenceFrame& f)
             m_icp->align(in, mdl, m_trackingState, m_cp, true, m_trkResult.device(), tag, stream);
         }
         // the one wait of the frame
-        const double w0 = now();
-        while (__atomic_load_n(&m_trkResult.host()->tag, __ATOMIC_ACQUIRE) != tag) {
-            std::this_thread::yield();
-            if (now() - w0 > 30.0) throw vh::Error(VH_ERR_TIMEOUT, "Reconstruction: no tracking result from the device for 30 s");
-        }
-        m_stats.hostWaitSeconds += now() - w0;
+        const vh::Waited w = vh::waitArrived(&m_trkResult.host()->tag, tag, vh::kDeviceSilentSeconds, true);
+        if (!w.ok) throw vh::Error(VH_ERR_TIMEOUT, "Reconstruction: no tracking result from the device for 30 s");
+        m_stats.hostWaitSeconds += w.seconds;
         if (m_trkResult.host()->lost) { // "!!! TRACKING LOST !!!": the frame is not integrated, the scene keeps its pose
             m_lostFrames++;
             m_frameNumber++;
@@ -660,14 +652,12 @@ void Reconstruction::run(const SequenceFrame* frames, unsigned int n, const Sequ
     // mirrors the scene's frame counter into mapped host memory when it starts.  Only that (fused) pass does so.
     const VhSceneOptions& so = m_sceneRep->getOptions();
     const bool bounded = m_opt.s_maxFramesInFlight && m_opt.s_integrationEnabled && !so.s_useReferenceLaunchSequence;
+    auto room = [&] { return m_sceneRep->getNumIntegratedFrames() - m_sceneRep->getNumFramesStartedOnDevice() < m_opt.s_maxFramesInFlight; };
     for (unsigned int i = 0; i < n; i++) {
-        if (bounded && m_sceneRep->getNumIntegratedFrames() - m_sceneRep->getNumFramesStartedOnDevice() >= m_opt.s_maxFramesInFlight) {
-            const double w0 = now();
-            while (m_sceneRep->getNumIntegratedFrames() - m_sceneRep->getNumFramesStartedOnDevice() >= m_opt.s_maxFramesInFlight) {
-                std::this_thread::yield();
-                if (now() - w0 > 30.0) throw vh::Error(VH_ERR_TIMEOUT, "Reconstruction::run: the device made no progress for 30 s");
-            }
-            waited += now() - w0;
+        if (bounded) {
+            const vh::Waited w = vh::spinUntil(room, vh::kDeviceSilentSeconds, true);
+            if (!w.ok) throw vh::Error(VH_ERR_TIMEOUT, "Reconstruction::run: the device made no progress for 30 s");
+            waited += w.seconds;
         }
         if (m_tracking) frameTracked(frames[i]); // (the pose of the next frame is not known ahead: nothing to look at)
         else frame(frames[i], i + 1 < n ? &frames[i + 1] : after);
