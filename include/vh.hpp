@@ -712,6 +712,8 @@ struct MeshData {
 };
 } // namespace vh
 
+struct VhMeshNormals; // opaque: the buffers of the vertex-normal pass (csrc/vh_mesh_normals.hpp)
+
 class CUDAMarchingCubesHashSDF {
 public:
     explicit CUDAMarchingCubesHashSDF(const MarchingCubesParams& params, vhStream_t stream = nullptr);
@@ -759,9 +761,9 @@ public:
     // end, the mesh buffer is empty, the indexed counts are 0, and the error goes on to the caller.
     void extractIsoSurfaceIndexed(CUDASceneRepChunkGrid& chunkGrid, const vh::vec3f& camPos, float radius);
     // of the last accumulated extraction: the VH_WELD_ACCUM_NUM_COUNTS counts of vh_types.h; 0 after a one-shot one
-    void getIndexedStats(unsigned int out[6]) const { for (int i = 0; i < 6; i++) out[i] = m_indexedStats[i]; }
+    void getIndexedStats(unsigned int out[6]) const { for (int i = 0; i < 6; i++) out[i] = m_indexed.accumulated ? m_indexed.counts[i] : 0u; }
     bool isWelded() const { return m_welded; }
-    void getIndexedCounts(unsigned int out[3]) const { out[0] = m_indexedCounts[0]; out[1] = m_indexedCounts[1]; out[2] = m_indexedCounts[2]; }
+    void getIndexedCounts(unsigned int out[3]) const { for (int i = 0; i < 3; i++) out[i] = m_indexed.counts[i]; }
     void downloadIndexed(VhVertex* vertices, uint64_t* keys, uint32_t* faces); // device mesh of the last indexed extraction
     // Vertex normals of the indexed mesh ("Vertex normals"), off by default.  When on, the three
     // indexed extractions run vh_mesh_vertex_normals after the weld -- finishIndexed over the whole accumulation -- with
@@ -785,28 +787,36 @@ private:
     vh::MeshData m_meshData;
     vhStream_t m_stream;
     bool m_offline;
+    // the steps the extractions share: reset, the box into m_params, pass 1 and pass 2 -- or the sourced pass 2, whose
+    // records go to d_sources; then the triangle count (and that of the records if sourced), which throws when the buffer overflowed
+    void runPasses(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner, const vh::vec3f& maxCorner, bool boxEnabled, bool sourced);
+    unsigned int countTriangles(bool sourced);
+    // the walk of .cpp:149-192: perChunk(hashData, hashParams, minCorner, maxCorner) for every chunk that has blocks, with
+    // its neighbourhood streamed in.  restoreOnError: when a chunk throws, the scene goes back as the normal end puts it.
+    template <class F> void walkChunks(CUDASceneRepChunkGrid& chunkGrid, const vh::vec3f& camPos, float radius, bool restoreOnError, F&& perChunk);
     // indexed extraction: made by its first call
     bool m_welded = false;                      // m_meshData is the weld's mesh, untouched since
     vh::DevicePtr<VhTriangleSource> d_sources;  // m_maxNumTriangles records beside m_data.d_triangles
     VhMeshWeldData m_weld;                      // from vh_mesh_weld_data_alloc; m_weldOwner gives it back
     struct WeldFree { void operator()(VhMeshWeldData* d) const noexcept; };
     std::unique_ptr<VhMeshWeldData, WeldFree> m_weldOwner;
-    unsigned int m_indexedCounts[3] = { 0, 0, 0 }; // {vertices, faces, status}
-    unsigned int m_numSourced = 0;                 // triangles of the last indexed extraction that are in the buffer
     // accumulated indexed extraction: made by the first beginIndexed
     struct AccumFree { void operator()(VhMeshWeldAccum* a) const noexcept; };
     std::unique_ptr<VhMeshWeldAccum, AccumFree> m_accum;
-    bool m_indexedIsAccumulated = false;           // downloadIndexed reads m_accum, not m_weld
-    unsigned int m_indexedStats[6] = { 0, 0, 0, 0, 0, 0 };
-    void resetIndexed();                           // empty buffer, zero counts: the state an error leaves
-    // vertex normals: the buffers of the one-shot extraction are made by its first call with the option on
+    // vertex normals: the one-shot extraction's buffers (csrc/vh_mesh_normals.hpp) are made by its first call with the option on
     bool m_indexedNormals = false;
-    bool m_indexedHasNormals = false;              // the last indexed extraction computed them
-    float m_indexedVoxelSize = 0.0f;               // of the last appendIndexed: finishIndexed's scale
-    vh::DevicePtr<int64_t> d_normalAcc;
-    vh::DevicePtr<float> d_normals;
-    vh::DevicePtr<uint32_t> d_normalStatus;
-    size_t m_normalsCapacity = 0;                  // vertices
+    std::unique_ptr<VhMeshNormals> m_normals;   // (complete where the constructor and the destructor are: vh_marching_cubes.cpp)
+    struct IndexedResult {                      // what the last indexed extraction left; the empty one is the state after an error
+        unsigned int counts[VH_WELD_ACCUM_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 }; // {vertices, faces, status}, then the accumulation's three
+        unsigned int numSourced = 0;            // triangles of its last sourced pass 2 that are in the buffer
+        bool accumulated = false;               // begun by beginIndexed: downloadIndexed reads m_accum, not m_weld
+        bool hasNormals = false;                // it computed them
+        float voxelSize = 0.0f;                 // of the last appendIndexed: finishIndexed's scale
+    } m_indexed;
+    void resetIndexed() { clearMeshBuffer(); m_indexed = IndexedResult(); }
+    // the welded mesh on the device (m_accum's, or m_weld's) into the mesh buffer, with normals at that scale if the
+    // option is on; then its counts and marks
+    void readBackIndexed(unsigned int numVertices, unsigned int numFaces, bool accumulated, int32_t scaleLog2);
 };
 
 

@@ -400,6 +400,56 @@ def test_chunk_grid_walk_normals_are_the_direct_extractions(vh):
     assert "normals" not in off and "normals" not in off_mesh and MW.same_mesh(MW.canonical(off), m)
 
 
+def test_one_object_switches_between_one_shot_and_accumulated_with_normals(vh):
+    """The scene of test_two_overlapping_boxes_give_the_direct_mesh (tests/test_gpu_mesh_weld_appends.py): a few hundred
+    faces.  The one-shot extraction and the accumulation have normals buffers of their own behind one read-back: one
+    object that goes from one to the other and back gives the same mesh and the same normals each time, and turning the
+    option off afterwards leaves the mesh and takes only the normals away."""
+    from voxelhashing_amd import engine as E, lib
+    hp, cp, _ = small_config(64, 48, params="P2")
+    scene = E.CUDASceneRepHashSDF(hp, T.make_scene_options(offline=True, gc=False))
+    frame = E.DepthFrame(cp)
+    for pose in [synth.orbit_pose(k, 100) for k in range(2)]:
+        E.synth_frame(synth.S1_SPHERES, 0, pose, cp, out=frame)
+        scene.integrate(pose, frame, cp, None)
+    hd, hpp = scene.getHashData(), scene.getHashParams()
+    mc = E.CUDAMarchingCubesHashSDF(T.make_marching_cubes_params(hp, MAX_TRIANGLES))
+    empty = dict(vertices=0, faces=0, status=0)
+    with pytest.raises(lib.VhError) as e:  # an append without a begin
+        mc.appendIndexed(hd, hpp)
+    assert e.value.code == BAD_ARGUMENT and mc.indexed_counts() == empty and set(mc.indexed_stats().values()) == {0}
+    mc.setIndexedNormals(True)
+
+    def accumulated():
+        mc.beginIndexed()
+        mc.appendIndexed(hd, hpp)
+        mc.finishIndexed()
+
+    seen = []
+    for extract in (lambda: mc.extractIsoSurfaceIndexed(hd, hpp), accumulated, lambda: mc.extractIsoSurfaceIndexed(hd, hpp)):
+        extract()
+        ind, mesh = mc.indexed(), mc.mesh()
+        assert same_bits(mesh["normals"], ind["normals"]) and mesh["vertices"].tobytes() == ind["vertices"].tobytes()
+        seen.append((MW.canonical(ind), by_key(ind), mc.indexed_counts(), mc.indexed_stats()))
+    first, normals, counts, _ = seen[0]
+    assert len(first["faces"]) > 500 and counts == dict(vertices=len(first["keys"]), faces=len(first["faces"]), status=0)
+    assert same_bits(normals, restated(first, E.mesh_normals_default_scale_log2(hp.m_virtualVoxelSize))["normals"]) and normals.any()
+    for m, n, c, _ in seen[1:]:
+        assert MW.same_mesh(m, first) and same_bits(n, normals) and c == counts
+    # the stats are the accumulation's alone
+    assert set(seen[0][3].values()) == {0} == set(seen[2][3].values()) and seen[1][3]["vertices"] == counts["vertices"] and seen[1][3]["cells"] > 0
+    mc.setIndexedNormals(False)
+    mc.extractIsoSurfaceIndexed(hd, hpp)
+    ind = mc.indexed()
+    assert "normals" not in ind and "normals" not in mc.mesh() and MW.same_mesh(MW.canonical(ind), first)
+    with pytest.raises(lib.VhError) as e:
+        lib.check(mc.L.vh_marching_cubes_download_indexed_normals(mc.handle, None), "download_indexed_normals")
+    assert e.value.code == BAD_ARGUMENT
+    with pytest.raises(lib.VhError) as e:  # still no begin: refused before anything is touched
+        mc.appendIndexed(hd, hpp)
+    assert e.value.code == BAD_ARGUMENT and mc.indexed_counts() == counts and set(mc.indexed_stats().values()) == {0}
+
+
 # ---------------------------------------------------------------------------- 6. Reconstruction
 
 RW, RH, RN = 80, 60, 3

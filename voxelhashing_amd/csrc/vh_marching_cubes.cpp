@@ -18,6 +18,7 @@
 
 #include "../../include/vh.hpp"
 #include "vh_host_util.hpp"
+#include "vh_mesh_normals.hpp"
 
 // ---------------------------------------------------------------------------
 // launcher-level buffers
@@ -299,17 +300,38 @@ void CUDAMarchingCubesHashSDF::downloadTriangles(VhTriangle* out, unsigned int n
     checkHip(hipStreamSynchronize((hipStream_t)m_stream), "triangles");
 }
 
-// .cpp:194-224
-void CUDAMarchingCubesHashSDF::extractIsoSurfaceWithoutCopy(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner,
-                                                            const vh::vec3f& maxCorner, bool boxEnabled)
+// reset, the box, pass 1, pass 2 (.cpp:194-224) -- or the sourced pass 2, which says where every vertex came from
+void CUDAMarchingCubesHashSDF::runPasses(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner, const vh::vec3f& maxCorner,
+                                         bool boxEnabled, bool sourced)
 {
+    if (sourced && !d_sources) d_sources = vh::deviceAlloc<VhTriangleSource>(m_params.m_maxNumTriangles, "triangle sources");
     check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
     m_params.m_maxCorner[0] = maxCorner.x; m_params.m_maxCorner[1] = maxCorner.y; m_params.m_maxCorner[2] = maxCorner.z;
     m_params.m_minCorner[0] = minCorner.x; m_params.m_minCorner[1] = minCorner.y; m_params.m_minCorner[2] = minCorner.z;
     m_params.m_boxEnabled = boxEnabled ? 1u : 0u;
     check(vh_marching_cubes_update_params(&m_data, &m_params, m_stream), "MarchingCubesData::updateParams");
     check(vh_extract_iso_surface_pass1(&hashData, &hashParams, &m_data, m_stream), "extractIsoSurfacePass1CUDA");
-    check(vh_extract_iso_surface_pass2(&hashData, &hashParams, &m_data, getNumOccupiedBlocks(), m_stream), "extractIsoSurfacePass2CUDA");
+    if (sourced)
+        check(vh_extract_iso_surface_pass2_sourced(&hashData, &hashParams, &m_data, d_sources.get(), getNumOccupiedBlocks(), m_stream),
+              "extractIsoSurfacePass2CUDA (sourced)");
+    else
+        check(vh_extract_iso_surface_pass2(&hashData, &hashParams, &m_data, getNumOccupiedBlocks(), m_stream), "extractIsoSurfacePass2CUDA");
+}
+
+// the overflow test of copyTrianglesToCPU (.cpp:35-38); after a sourced pass 2 the records in the buffer are counted first
+unsigned int CUDAMarchingCubesHashSDF::countTriangles(bool sourced)
+{
+    const unsigned int nTriangles = getNumTriangles();
+    if (sourced) m_indexed.numSourced = std::min(nTriangles, m_params.m_maxNumTriangles);
+    if (nTriangles >= m_params.m_maxNumTriangles)
+        throw vh::Error(VH_ERR_STAGING_OVERFLOW, "not enough memory to store triangles for chunk; increase s_marchingCubesMaxNumTriangles");
+    return nTriangles;
+}
+
+void CUDAMarchingCubesHashSDF::extractIsoSurfaceWithoutCopy(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner,
+                                                            const vh::vec3f& maxCorner, bool boxEnabled)
+{
+    runPasses(hashData, hashParams, minCorner, maxCorner, boxEnabled, false);
 }
 
 void CUDAMarchingCubesHashSDF::extractIsoSurface(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner,
@@ -319,25 +341,63 @@ void CUDAMarchingCubesHashSDF::extractIsoSurface(const HashData& hashData, const
     copyTrianglesToCPU();
 }
 
+namespace {
+// a weld's get_counts code as the exception the indexed extractions throw
+void checkWeld(int rc, const char* what)
+{
+    if (rc == VH_ERR_STAGING_OVERFLOW) throw vh::Error(rc, "mesh weld: the table is full");
+    if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "mesh weld: a voxel coordinate is outside the key range of +-2^19");
+    check(rc, what);
+}
+
+// n vertex records as the mesh container has them: positions, and rgb with alpha 1
+void recordsToMeshData(const VhVertex* v, size_t n, vh::MeshData& md)
+{
+    md.m_Vertices.resize(n);
+    md.m_Colors.resize(4 * n);
+    for (size_t i = 0; i < n; i++) {
+        md.m_Vertices[i] = { v[i].p[0], v[i].p[1], v[i].p[2] };
+        md.m_Colors[4 * i + 0] = v[i].c[0]; md.m_Colors[4 * i + 1] = v[i].c[1]; md.m_Colors[4 * i + 2] = v[i].c[2]; md.m_Colors[4 * i + 3] = 1.0f;
+    }
+}
+} // namespace
+
+void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf, bool accumulated, int32_t scaleLog2)
+{
+    vh::MeshData md;
+    if (m_indexedNormals) {
+        // over all the faces, with the bits the last append left: a pass of the finish, never of an append
+        md.m_Normals.resize(3 * (size_t)nv);
+        int rc = VH_OK;
+        if (accumulated) {
+            check(vh_mesh_weld_accum_normals(m_accum.get(), scaleLog2, m_stream), "vh_mesh_weld_accum_normals");
+            rc = vh_mesh_weld_accum_download_normals(m_accum.get(), md.m_Normals.data(), nv, m_stream);
+        } else {
+            if (!m_normals) m_normals.reset(new VhMeshNormals);
+            check(m_normals->run(m_weld.d_vertices, m_weld.d_keys, m_weld.d_faces, nv, nf, scaleLog2, m_stream), "vh_mesh_vertex_normals");
+            rc = m_normals->download(md.m_Normals.data(), nv, true, m_stream);
+        }
+        if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "vertex normals: a face normal is out of the fixed-point range, or a face index out of bounds");
+        check(rc, "vertex normals");
+    }
+    std::vector<VhVertex> verts(nv);
+    md.m_FaceIndicesVertices.resize(3 * (size_t)nf);
+    if (accumulated) check(vh_mesh_weld_accum_download(m_accum.get(), verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_download");
+    else check(vh_mesh_weld_download(&m_weld, verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_download");
+    recordsToMeshData(verts.data(), verts.size(), md);
+    m_meshData = std::move(md);
+    m_indexed.counts[0] = nv; m_indexed.counts[1] = nf;
+    m_indexed.hasNormals = m_indexedNormals;
+    m_welded = true;
+}
+
 // Not in the reference.  The soup stays on the device; what comes back is the welded mesh.
 void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner,
                                                         const vh::vec3f& maxCorner, bool boxEnabled)
 {
     resetIndexed(); // nothing partial is left behind by an error
-    m_indexedIsAccumulated = false;
-    if (!d_sources) d_sources = vh::deviceAlloc<VhTriangleSource>(m_params.m_maxNumTriangles, "triangle sources");
-    check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
-    m_params.m_maxCorner[0] = maxCorner.x; m_params.m_maxCorner[1] = maxCorner.y; m_params.m_maxCorner[2] = maxCorner.z;
-    m_params.m_minCorner[0] = minCorner.x; m_params.m_minCorner[1] = minCorner.y; m_params.m_minCorner[2] = minCorner.z;
-    m_params.m_boxEnabled = boxEnabled ? 1u : 0u;
-    check(vh_marching_cubes_update_params(&m_data, &m_params, m_stream), "MarchingCubesData::updateParams");
-    check(vh_extract_iso_surface_pass1(&hashData, &hashParams, &m_data, m_stream), "extractIsoSurfacePass1CUDA");
-    check(vh_extract_iso_surface_pass2_sourced(&hashData, &hashParams, &m_data, d_sources.get(), getNumOccupiedBlocks(), m_stream),
-          "extractIsoSurfacePass2CUDA (sourced)");
-    const unsigned int nTriangles = getNumTriangles();
-    m_numSourced = std::min(nTriangles, m_params.m_maxNumTriangles);
-    if (nTriangles >= m_params.m_maxNumTriangles) // the test of copyTrianglesToCPU
-        throw vh::Error(VH_ERR_STAGING_OVERFLOW, "not enough memory to store triangles for chunk; increase s_marchingCubesMaxNumTriangles");
+    runPasses(hashData, hashParams, minCorner, maxCorner, boxEnabled, true);
+    const unsigned int nTriangles = countTriangles(true);
     // the table is sized by the triangles there are, not by the buffer: it grows, and is kept for the next call
     if (!m_weldOwner || m_weld.m_maxTriangles < nTriangles) {
         m_weldOwner.reset();
@@ -347,60 +407,19 @@ void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(const HashData& hashData
     check(vh_mesh_weld(m_data.d_triangles, d_sources.get(), nTriangles, &m_weld, 0, m_stream), "vh_mesh_weld");
     unsigned int counts[3] = { 0, 0, 0 };
     const int rc = vh_mesh_weld_get_counts(&m_weld, counts, m_stream);
-    m_indexedCounts[2] = counts[2];
-    if (rc == VH_ERR_STAGING_OVERFLOW) throw vh::Error(rc, "mesh weld: the table is full");
-    if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "mesh weld: a voxel coordinate is outside the key range of +-2^19");
-    check(rc, "vh_mesh_weld_get_counts");
-    std::vector<VhVertex> verts(counts[0]);
-    vh::MeshData md;
-    if (m_indexedNormals) {
-        if (!d_normalStatus) d_normalStatus = vh::deviceAlloc<uint32_t>(1, "vertex normal status");
-        if (counts[0] > m_normalsCapacity) {
-            const size_t cap = counts[0] + counts[0] / 4u;
-            d_normalAcc = vh::deviceAlloc<int64_t>(3 * cap, "vertex normal accumulators");
-            d_normals = vh::deviceAlloc<float>(3 * cap, "vertex normals");
-            m_normalsCapacity = cap;
-        }
-        int32_t scaleLog2 = 0;
-        check(vh_mesh_normals_default_scale_log2(hashParams.m_virtualVoxelSize, &scaleLog2), "vh_mesh_normals_default_scale_log2");
-        check(vh_mesh_vertex_normals(m_weld.d_vertices, m_weld.d_keys, m_weld.d_faces, counts[0], counts[1], scaleLog2, d_normalAcc.get(),
-                                     d_normals.get(), d_normalStatus.get(), m_stream), "vh_mesh_vertex_normals");
-        unsigned int status = 0;
-        md.m_Normals.resize(3 * (size_t)counts[0]);
-        checkHip(hipMemcpyAsync(&status, d_normalStatus.get(), sizeof(status), hipMemcpyDeviceToHost, (hipStream_t)m_stream), "normal status");
-        if (counts[0]) checkHip(hipMemcpyAsync(md.m_Normals.data(), d_normals.get(), sizeof(float) * 3 * (size_t)counts[0], hipMemcpyDeviceToHost, (hipStream_t)m_stream), "normals");
-        checkHip(hipStreamSynchronize((hipStream_t)m_stream), "normals");
-        if (status != 0u) throw vh::Error(VH_ERR_BAD_ARGUMENT, "vertex normals: a face normal is out of the fixed-point range, or a face index out of bounds");
-    }
-    md.m_FaceIndicesVertices.resize(3 * (size_t)counts[1]);
-    check(vh_mesh_weld_download(&m_weld, verts.data(), nullptr, md.m_FaceIndicesVertices.data(), counts[0], counts[1], m_stream), "vh_mesh_weld_download");
-    md.m_Vertices.resize(counts[0]);
-    md.m_Colors.resize(4 * (size_t)counts[0]);
-    for (size_t i = 0; i < verts.size(); i++) {
-        md.m_Vertices[i] = { verts[i].p[0], verts[i].p[1], verts[i].p[2] };
-        md.m_Colors[4 * i + 0] = verts[i].c[0]; md.m_Colors[4 * i + 1] = verts[i].c[1]; md.m_Colors[4 * i + 2] = verts[i].c[2]; md.m_Colors[4 * i + 3] = 1.0f;
-    }
-    m_meshData = std::move(md);
-    m_indexedCounts[0] = counts[0]; m_indexedCounts[1] = counts[1];
-    m_indexedHasNormals = m_indexedNormals;
-    m_welded = true;
+    m_indexed.counts[2] = counts[2];
+    checkWeld(rc, "vh_mesh_weld_get_counts");
+    int32_t scaleLog2 = 0;
+    if (m_indexedNormals) check(vh_mesh_normals_default_scale_log2(hashParams.m_virtualVoxelSize, &scaleLog2), "vh_mesh_normals_default_scale_log2");
+    readBackIndexed(counts[0], counts[1], false, scaleLog2);
 }
 
 void CUDAMarchingCubesHashSDF::AccumFree::operator()(VhMeshWeldAccum* a) const noexcept { vh_mesh_weld_accum_destroy(a); }
 
-void CUDAMarchingCubesHashSDF::resetIndexed()
-{
-    clearMeshBuffer();
-    m_indexedCounts[0] = m_indexedCounts[1] = m_indexedCounts[2] = 0;
-    for (unsigned int& v : m_indexedStats) v = 0;
-    m_numSourced = 0;
-    m_indexedHasNormals = false;
-}
-
 void CUDAMarchingCubesHashSDF::beginIndexed()
 {
     resetIndexed();
-    m_indexedIsAccumulated = true;
+    m_indexed.accumulated = true;
     if (!m_accum) {
         VhMeshWeldAccum* a = nullptr;
         check(vh_mesh_weld_accum_create(0, 0, 0, &a), "vh_mesh_weld_accum_create");
@@ -412,87 +431,48 @@ void CUDAMarchingCubesHashSDF::beginIndexed()
 void CUDAMarchingCubesHashSDF::appendIndexed(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner,
                                              const vh::vec3f& maxCorner, bool boxEnabled)
 {
-    if (!m_accum || !m_indexedIsAccumulated) throw vh::Error(VH_ERR_BAD_ARGUMENT, "appendIndexed: no beginIndexed");
-    m_indexedVoxelSize = hashParams.m_virtualVoxelSize;
+    if (!m_accum || !m_indexed.accumulated) throw vh::Error(VH_ERR_BAD_ARGUMENT, "appendIndexed: no beginIndexed");
+    m_indexed.voxelSize = hashParams.m_virtualVoxelSize;
     try {
-        if (!d_sources) d_sources = vh::deviceAlloc<VhTriangleSource>(m_params.m_maxNumTriangles, "triangle sources");
-        check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
-        m_params.m_maxCorner[0] = maxCorner.x; m_params.m_maxCorner[1] = maxCorner.y; m_params.m_maxCorner[2] = maxCorner.z;
-        m_params.m_minCorner[0] = minCorner.x; m_params.m_minCorner[1] = minCorner.y; m_params.m_minCorner[2] = minCorner.z;
-        m_params.m_boxEnabled = boxEnabled ? 1u : 0u;
-        check(vh_marching_cubes_update_params(&m_data, &m_params, m_stream), "MarchingCubesData::updateParams");
-        check(vh_extract_iso_surface_pass1(&hashData, &hashParams, &m_data, m_stream), "extractIsoSurfacePass1CUDA");
-        check(vh_extract_iso_surface_pass2_sourced(&hashData, &hashParams, &m_data, d_sources.get(), getNumOccupiedBlocks(), m_stream),
-              "extractIsoSurfacePass2CUDA (sourced)");
-        const unsigned int nTriangles = getNumTriangles();
-        m_numSourced = std::min(nTriangles, m_params.m_maxNumTriangles);
-        if (nTriangles >= m_params.m_maxNumTriangles) // the test of copyTrianglesToCPU
-            throw vh::Error(VH_ERR_STAGING_OVERFLOW, "not enough memory to store triangles for chunk; increase s_marchingCubesMaxNumTriangles");
+        runPasses(hashData, hashParams, minCorner, maxCorner, boxEnabled, true);
+        const unsigned int nTriangles = countTriangles(true);
         check(vh_mesh_weld_accum_append(m_accum.get(), m_data.d_triangles, d_sources.get(), nTriangles, m_stream), "vh_mesh_weld_accum_append");
     } catch (...) {
-        const unsigned int sourced = m_numSourced;
+        // the accumulation is over: finishIndexed wants a new beginIndexed.  The records in the buffer stay readable.
+        const unsigned int sourced = m_indexed.numSourced;
         resetIndexed();
-        m_numSourced = sourced;
-        m_indexedIsAccumulated = false; // the accumulation is over: finishIndexed wants a new beginIndexed
+        m_indexed.numSourced = sourced;
         throw;
     }
 }
 
 void CUDAMarchingCubesHashSDF::finishIndexed()
 {
-    if (!m_accum || !m_indexedIsAccumulated) throw vh::Error(VH_ERR_BAD_ARGUMENT, "finishIndexed: no beginIndexed");
+    if (!m_accum || !m_indexed.accumulated) throw vh::Error(VH_ERR_BAD_ARGUMENT, "finishIndexed: no beginIndexed");
     clearMeshBuffer();
-    unsigned int stats[6] = { 0, 0, 0, 0, 0, 0 };
+    unsigned int stats[VH_WELD_ACCUM_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
     const int rc = vh_mesh_weld_accum_get_counts(m_accum.get(), stats, m_stream);
-    m_indexedCounts[0] = m_indexedCounts[1] = 0;
-    m_indexedCounts[2] = stats[VH_WELD_ACCUM_STATUS];
-    for (int i = 0; i < 6; i++) m_indexedStats[i] = 0;
-    m_indexedStats[VH_WELD_ACCUM_STATUS] = stats[VH_WELD_ACCUM_STATUS];
-    if (rc == VH_ERR_STAGING_OVERFLOW) throw vh::Error(rc, "mesh weld: the table is full");
-    if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "mesh weld: a voxel coordinate is outside the key range of +-2^19");
-    check(rc, "vh_mesh_weld_accum_get_counts");
-    const unsigned int nv = stats[VH_WELD_ACCUM_VERTICES], nf = stats[VH_WELD_ACCUM_FACES];
-    std::vector<VhVertex> verts(nv);
-    vh::MeshData md;
-    m_indexedHasNormals = false;
-    if (m_indexedNormals) {
-        // over all the faces, with the bits the last append left: a pass of the finish, never of an append.  (Without an
-        // append there is no voxel size, and no vertex either: any scale serves.)
-        int32_t scaleLog2 = 0;
-        if (m_indexedVoxelSize > 0.0f) check(vh_mesh_normals_default_scale_log2(m_indexedVoxelSize, &scaleLog2), "vh_mesh_normals_default_scale_log2");
-        check(vh_mesh_weld_accum_normals(m_accum.get(), scaleLog2, m_stream), "vh_mesh_weld_accum_normals");
-        md.m_Normals.resize(3 * (size_t)nv);
-        const int nrc = vh_mesh_weld_accum_download_normals(m_accum.get(), md.m_Normals.data(), nv, m_stream);
-        if (nrc == VH_ERR_BAD_ARGUMENT) {
-            m_indexedStats[VH_WELD_ACCUM_STATUS] = 0;
-            m_indexedCounts[2] = 0;
-            throw vh::Error(nrc, "vertex normals: a face normal is out of the fixed-point range, or a face index out of bounds");
-        }
-        check(nrc, "vh_mesh_weld_accum_download_normals");
-    }
-    md.m_FaceIndicesVertices.resize(3 * (size_t)nf);
-    check(vh_mesh_weld_accum_download(m_accum.get(), verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_download");
-    md.m_Vertices.resize(nv);
-    md.m_Colors.resize(4 * (size_t)nv);
-    for (size_t i = 0; i < verts.size(); i++) {
-        md.m_Vertices[i] = { verts[i].p[0], verts[i].p[1], verts[i].p[2] };
-        md.m_Colors[4 * i + 0] = verts[i].c[0]; md.m_Colors[4 * i + 1] = verts[i].c[1]; md.m_Colors[4 * i + 2] = verts[i].c[2]; md.m_Colors[4 * i + 3] = 1.0f;
-    }
-    m_meshData = std::move(md);
-    m_indexedCounts[0] = nv; m_indexedCounts[1] = nf;
-    for (int i = 0; i < 6; i++) m_indexedStats[i] = stats[i];
-    m_indexedHasNormals = m_indexedNormals;
-    m_welded = true;
+    for (unsigned int& c : m_indexed.counts) c = 0;
+    m_indexed.counts[VH_WELD_ACCUM_STATUS] = stats[VH_WELD_ACCUM_STATUS];
+    m_indexed.hasNormals = false;
+    checkWeld(rc, "vh_mesh_weld_accum_get_counts");
+    // (without an append there is no voxel size, and no vertex either: any scale serves)
+    int32_t scaleLog2 = 0;
+    if (m_indexedNormals && m_indexed.voxelSize > 0.0f)
+        check(vh_mesh_normals_default_scale_log2(m_indexed.voxelSize, &scaleLog2), "vh_mesh_normals_default_scale_log2");
+    readBackIndexed(stats[VH_WELD_ACCUM_VERTICES], stats[VH_WELD_ACCUM_FACES], true, scaleLog2);
+    std::copy(stats, stats + VH_WELD_ACCUM_NUM_COUNTS, m_indexed.counts);
 }
 
-// the walk of extractIsoSurface(chunkGrid, ...) below, box for box
-void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(CUDASceneRepChunkGrid& chunkGrid, const vh::vec3f& camPos, float radius)
+// .cpp:149-192; the box of a chunk is padded by one block
+template <class F>
+void CUDAMarchingCubesHashSDF::walkChunks(CUDASceneRepChunkGrid& chunkGrid, const vh::vec3f& camPos, float radius, bool restoreOnError, F&& perChunk)
 {
     chunkGrid.stopMultiThreading();
     const vh::vec3i minGridPos = chunkGrid.getMinGridPos(), maxGridPos = chunkGrid.getMaxGridPos();
+    unsigned int nStreamedBlocks = 0;
     bool walking = false;
     try {
-        beginIndexed();
         chunkGrid.streamOutToCPUAll();
         walking = true;
         for (int x = minGridPos.x; x < maxGridPos.x; x++)
@@ -506,62 +486,71 @@ void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(CUDASceneRepChunkGrid& c
                     const float pad = hp.m_virtualVoxelSize * (float)hp.m_SDFBlockSize;
                     const vh::vec3f minCorner = { c.x - e.x / 2.0f - pad, c.y - e.y / 2.0f - pad, c.z - e.z / 2.0f - pad };
                     const vh::vec3f maxCorner = { c.x + e.x / 2.0f + pad, c.y + e.y / 2.0f + pad, c.z + e.z / 2.0f + pad };
-                    appendIndexed(chunkGrid.getHashData(), hp, minCorner, maxCorner, true);
+                    perChunk(chunkGrid.getHashData(), hp, minCorner, maxCorner);
                     chunkGrid.streamOutToCPUAll();
                 }
         walking = false;
-        unsigned int nStreamedBlocks = 0;
         chunkGrid.streamInToGPUAll(camPos, radius, true, nStreamedBlocks);
-        chunkGrid.startMultiThreading();
     } catch (...) {
-        // a chunk failed with its neighbourhood on the device: the scene goes back as the normal end puts it
-        resetIndexed();
-        m_indexedIsAccumulated = false;
-        if (walking) {
+        if (!restoreOnError) throw; // the reference's walk leaves the scene where the error found it
+        if (walking) { // a chunk failed with its neighbourhood on the device
             chunkGrid.streamOutToCPUAll();
-            unsigned int nStreamedBlocks = 0;
             chunkGrid.streamInToGPUAll(camPos, radius, true, nStreamedBlocks);
         }
         chunkGrid.startMultiThreading();
         throw;
     }
+    chunkGrid.startMultiThreading();
+}
+
+void CUDAMarchingCubesHashSDF::extractIsoSurface(CUDASceneRepChunkGrid& chunkGrid, const vh::vec3f& camPos, float radius)
+{
+    clearMeshBuffer();
+    walkChunks(chunkGrid, camPos, radius, false, [this](const HashData& hd, const HashParams& hp, const vh::vec3f& lo, const vh::vec3f& hi) {
+        extractIsoSurface(hd, hp, lo, hi, true);
+    });
+}
+
+// the same walk, every chunk appended to one accumulation
+void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(CUDASceneRepChunkGrid& chunkGrid, const vh::vec3f& camPos, float radius)
+{
     try {
+        beginIndexed();
+        walkChunks(chunkGrid, camPos, radius, true, [this](const HashData& hd, const HashParams& hp, const vh::vec3f& lo, const vh::vec3f& hi) {
+            appendIndexed(hd, hp, lo, hi, true);
+        });
         finishIndexed();
     } catch (...) {
-        resetIndexed();
-        m_indexedIsAccumulated = false;
+        resetIndexed(); // the one reset of the walk: also of the records' count, which a failed appendIndexed alone keeps
         throw;
     }
 }
 
 void CUDAMarchingCubesHashSDF::downloadIndexed(VhVertex* vertices, uint64_t* keys, uint32_t* faces)
 {
-    if (m_indexedCounts[0] == 0 && m_indexedCounts[1] == 0) return;
-    if (m_indexedIsAccumulated) {
-        check(vh_mesh_weld_accum_download(m_accum.get(), vertices, keys, faces, m_indexedCounts[0], m_indexedCounts[1], m_stream), "vh_mesh_weld_accum_download");
+    const unsigned int nv = m_indexed.counts[0], nf = m_indexed.counts[1];
+    if (nv == 0 && nf == 0) return;
+    if (m_indexed.accumulated) {
+        check(vh_mesh_weld_accum_download(m_accum.get(), vertices, keys, faces, nv, nf, m_stream), "vh_mesh_weld_accum_download");
         return;
     }
     if (!m_weldOwner) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexed: no indexed extraction");
-    check(vh_mesh_weld_download(&m_weld, vertices, keys, faces, m_indexedCounts[0], m_indexedCounts[1], m_stream), "vh_mesh_weld_download");
+    check(vh_mesh_weld_download(&m_weld, vertices, keys, faces, nv, nf, m_stream), "vh_mesh_weld_download");
 }
 
 void CUDAMarchingCubesHashSDF::downloadIndexedNormals(float* normals)
 {
-    if (!m_indexedHasNormals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexedNormals: the last indexed extraction computed none (setIndexedNormals)");
-    if (m_indexedCounts[0] == 0) return;
+    if (!m_indexed.hasNormals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexedNormals: the last indexed extraction computed none (setIndexedNormals)");
+    if (m_indexed.counts[0] == 0) return;
     if (!normals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexedNormals");
-    if (m_indexedIsAccumulated) {
-        check(vh_mesh_weld_accum_download_normals(m_accum.get(), normals, m_indexedCounts[0], m_stream), "vh_mesh_weld_accum_download_normals");
-        return;
-    }
-    checkHip(hipMemcpyAsync(normals, d_normals.get(), sizeof(float) * 3 * (size_t)m_indexedCounts[0], hipMemcpyDeviceToHost, (hipStream_t)m_stream), "normals");
-    checkHip(hipStreamSynchronize((hipStream_t)m_stream), "normals");
+    if (m_indexed.accumulated) check(vh_mesh_weld_accum_download_normals(m_accum.get(), normals, m_indexed.counts[0], m_stream), "vh_mesh_weld_accum_download_normals");
+    else check(m_normals->download(normals, m_indexed.counts[0], false, m_stream), "normals");
 }
 
 void CUDAMarchingCubesHashSDF::downloadSources(VhTriangleSource* out, unsigned int n)
 {
     if (n == 0) return;
-    if (!out || !d_sources || n > m_numSourced) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadSources");
+    if (!out || !d_sources || n > m_indexed.numSourced) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadSources");
     checkHip(hipMemcpyAsync(out, d_sources.get(), sizeof(VhTriangleSource) * (size_t)n, hipMemcpyDeviceToHost, (hipStream_t)m_stream), "sources");
     checkHip(hipStreamSynchronize((hipStream_t)m_stream), "sources");
 }
@@ -569,22 +558,14 @@ void CUDAMarchingCubesHashSDF::downloadSources(VhTriangleSource* out, unsigned i
 // .cpp:31-86
 void CUDAMarchingCubesHashSDF::copyTrianglesToCPU()
 {
-    const unsigned int nTriangles = getNumTriangles();
-    if (nTriangles >= m_params.m_maxNumTriangles)
-        throw vh::Error(VH_ERR_STAGING_OVERFLOW, "not enough memory to store triangles for chunk; increase s_marchingCubesMaxNumTriangles");
+    const unsigned int nTriangles = countTriangles(false);
     if (nTriangles == 0) return;
     m_welded = false; // the buffer is about to hold something the weld did not make
     m_meshData.m_Normals.clear(); // (and the soup that joins it has no normals)
     std::vector<VhTriangle> tris(nTriangles);
     downloadTriangles(tris.data(), nTriangles);
     vh::MeshData md;
-    md.m_Vertices.resize(3 * (size_t)nTriangles);
-    md.m_Colors.resize(12 * (size_t)nTriangles);
-    const VhVertex* vc = reinterpret_cast<const VhVertex*>(tris.data());
-    for (size_t i = 0; i < 3 * (size_t)nTriangles; i++) {
-        md.m_Vertices[i] = { vc[i].p[0], vc[i].p[1], vc[i].p[2] };
-        md.m_Colors[4 * i + 0] = vc[i].c[0]; md.m_Colors[4 * i + 1] = vc[i].c[1]; md.m_Colors[4 * i + 2] = vc[i].c[2]; md.m_Colors[4 * i + 3] = 1.0f;
-    }
+    recordsToMeshData(reinterpret_cast<const VhVertex*>(tris.data()), 3 * (size_t)nTriangles, md);
     if (!m_offline) {
         // triangle soup appended as it is
         if (m_meshData.hasVertexIndices()) { md.makeTriangleSoupIndices(); m_meshData.merge(md); }
@@ -624,30 +605,4 @@ void CUDAMarchingCubesHashSDF::saveMesh(const std::string& filename, const vh::m
     if (transform) m_meshData.applyTransform(*transform);
     m_meshData.saveToPLY(actual);
     clearMeshBuffer();
-}
-
-// .cpp:149-192
-void CUDAMarchingCubesHashSDF::extractIsoSurface(CUDASceneRepChunkGrid& chunkGrid, const vh::vec3f& camPos, float radius)
-{
-    chunkGrid.stopMultiThreading();
-    const vh::vec3i minGridPos = chunkGrid.getMinGridPos(), maxGridPos = chunkGrid.getMaxGridPos();
-    clearMeshBuffer();
-    chunkGrid.streamOutToCPUAll();
-    for (int x = minGridPos.x; x < maxGridPos.x; x++)
-        for (int y = minGridPos.y; y < maxGridPos.y; y++)
-            for (int z = minGridPos.z; z < maxGridPos.z; z++) {
-                const vh::vec3i chunk = { x, y, z };
-                if (!chunkGrid.containsSDFBlocksChunk(chunk)) continue;
-                chunkGrid.streamInToGPUChunkNeighborhood(chunk, 1);
-                const vh::vec3f c = chunkGrid.getWorldPosChunk(chunk), e = chunkGrid.getVoxelExtends();
-                const HashParams hp = chunkGrid.getHashParams();
-                const float pad = hp.m_virtualVoxelSize * (float)hp.m_SDFBlockSize;
-                const vh::vec3f minCorner = { c.x - e.x / 2.0f - pad, c.y - e.y / 2.0f - pad, c.z - e.z / 2.0f - pad };
-                const vh::vec3f maxCorner = { c.x + e.x / 2.0f + pad, c.y + e.y / 2.0f + pad, c.z + e.z / 2.0f + pad };
-                extractIsoSurface(chunkGrid.getHashData(), hp, minCorner, maxCorner, true);
-                chunkGrid.streamOutToCPUAll();
-            }
-    unsigned int nStreamedBlocks = 0;
-    chunkGrid.streamInToGPUAll(camPos, radius, true, nStreamedBlocks);
-    chunkGrid.startMultiThreading();
 }

@@ -17,6 +17,7 @@
 #include "vh_device.hpp"
 #include "vh_host_util.hpp"
 #include "vh_mesh_key.hpp"
+#include "vh_mesh_normals.hpp"
 
 using namespace vhd;
 
@@ -45,8 +46,23 @@ VHD uint32_t wave_append(bool keep, uint32_t* counter)
 
 constexpr uint32_t kNoSlot = 0xffffffffu;
 
+// the slot of `key`, claimed if the table does not have it; kNoSlot after numSlots steps without one
+VHD uint32_t weld_find_or_claim(unsigned long long* slotKeys, uint64_t key, uint32_t slotsLog2)
+{
+    const uint32_t numSlots = 1u << slotsLog2, mask = numSlots - 1u;
+    uint32_t slot = weld_home(key, mask);
+#pragma unroll 1
+    for (uint32_t step = 0; step < numSlots; step++) {
+        unsigned long long have = slotKeys[slot];
+        if (have == kMeshKeyEmpty) have = atomicCAS(&slotKeys[slot], (unsigned long long)kMeshKeyEmpty, (unsigned long long)key);
+        if (have == kMeshKeyEmpty || have == key) return slot;
+        slot = (slot + 1u) & mask;
+    }
+    return kNoSlot;
+}
+
 // One lane per soup vertex i = 3 * triangle + corner: claim the slot of its key, bid for the slot's vertex with
-// rank << 32 | i (the smallest wins), remember the slot.  The probe walks at most numSlots steps.
+// rank << 32 | i (the smallest wins), remember the slot.
 __global__ __launch_bounds__(256) void k_weld_insert(const VhTriangleSource* sources, uint32_t numVertices, VhMeshWeldData w, uint32_t slotsLog2)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -62,16 +78,7 @@ __global__ __launch_bounds__(256) void k_weld_insert(const VhTriangleSource* sou
         w.d_vertexSlot[i] = kNoSlot;
         return;
     }
-    const uint32_t numSlots = 1u << slotsLog2, mask = numSlots - 1u;
-    uint32_t slot = weld_home(key, mask), found = kNoSlot;
-    unsigned long long* slotKeys = reinterpret_cast<unsigned long long*>(w.d_slotKeys);
-#pragma unroll 1
-    for (uint32_t step = 0; step < numSlots; step++) {
-        unsigned long long have = slotKeys[slot];
-        if (have == kMeshKeyEmpty) have = atomicCAS(&slotKeys[slot], (unsigned long long)kMeshKeyEmpty, (unsigned long long)key);
-        if (have == kMeshKeyEmpty || have == key) { found = slot; break; }
-        slot = (slot + 1u) & mask;
-    }
+    const uint32_t found = weld_find_or_claim(reinterpret_cast<unsigned long long*>(w.d_slotKeys), key, slotsLog2);
     if (found == kNoSlot) atomicOr(&w.d_counts[2], VH_WELD_TABLE_FULL);
     else atomicMin(reinterpret_cast<unsigned long long*>(&w.d_slotWinner[found]), ((unsigned long long)rank << 32) | i);
     w.d_vertexSlot[i] = found;
@@ -172,21 +179,6 @@ VHD void wave_count(bool flag, uint32_t* counter)
     if ((int)lane_id() == __ffsll((unsigned long long)m) - 1) atomicAdd(counter, (uint32_t)__popcll(m));
 }
 
-// the slot of `key`, claimed if the table does not have it; kNoSlot after numSlots steps without one
-VHD uint32_t accum_find_or_claim(unsigned long long* slotKeys, uint64_t key, uint32_t slotsLog2)
-{
-    const uint32_t numSlots = 1u << slotsLog2, mask = numSlots - 1u;
-    uint32_t slot = weld_home(key, mask);
-#pragma unroll 1
-    for (uint32_t step = 0; step < numSlots; step++) {
-        unsigned long long have = slotKeys[slot];
-        if (have == kMeshKeyEmpty) have = atomicCAS(&slotKeys[slot], (unsigned long long)kMeshKeyEmpty, (unsigned long long)key);
-        if (have == kMeshKeyEmpty || have == key) return slot;
-        slot = (slot + 1u) & mask;
-    }
-    return kNoSlot;
-}
-
 // One lane per triangle.  Claims the cell for this append (a cell an earlier append owns drops the triangle here,
 // before any of its keys is looked at), then for each of the three vertices the slot of its key, and bids for it.
 __global__ __launch_bounds__(256) void k_weld_accum_insert(const VhTriangleSource* sources, uint32_t numTriangles, WeldAccumView w, uint32_t ordinal)
@@ -210,7 +202,7 @@ __global__ __launch_bounds__(256) void k_weld_accum_insert(const VhTriangleSourc
     bool kept = false, first = false;
     uint32_t slots[3] = { kNoSlot, kNoSlot, kNoSlot };
     if (valid && status == 0u) {
-        const uint32_t cellSlot = accum_find_or_claim(slotKeys, cellKey, w.slotsLog2);
+        const uint32_t cellSlot = weld_find_or_claim(slotKeys, cellKey, w.slotsLog2);
         if (cellSlot == kNoSlot) status = VH_WELD_TABLE_FULL;
         else {
             const uint32_t owner = atomicCAS(&w.slotVals[cellSlot], kNoValue, ordinal);
@@ -222,7 +214,7 @@ __global__ __launch_bounds__(256) void k_weld_accum_insert(const VhTriangleSourc
         const uint64_t high = (uint64_t)(VH_WELD_ACCUM_MAX_APPENDS - ordinal) << 35;
 #pragma unroll 1
         for (uint32_t k = 0; k < 3u; k++) {
-            const uint32_t slot = accum_find_or_claim(slotKeys, key[k], w.slotsLog2);
+            const uint32_t slot = weld_find_or_claim(slotKeys, key[k], w.slotsLog2);
             if (slot == kNoSlot) { status = VH_WELD_TABLE_FULL; break; }
             atomicMin(reinterpret_cast<unsigned long long*>(&w.slotBids[slot]), (unsigned long long)(high | ((uint64_t)rank[k] << 32) | (3u * t + k)));
             slots[k] = slot;
@@ -294,7 +286,7 @@ __global__ __launch_bounds__(256) void k_weld_rehash(const uint64_t* oldKeys, co
     if (s >= (1u << oldSlotsLog2)) return;
     const uint64_t key = oldKeys[s];
     if (key == kMeshKeyEmpty) return;
-    const uint32_t slot = accum_find_or_claim(reinterpret_cast<unsigned long long*>(w.slotKeys), key, w.slotsLog2);
+    const uint32_t slot = weld_find_or_claim(reinterpret_cast<unsigned long long*>(w.slotKeys), key, w.slotsLog2);
     if (slot == kNoSlot) atomicOr(&w.counts[VH_WELD_ACCUM_STATUS], VH_WELD_TABLE_FULL); // (a larger table always has room)
     else w.slotVals[slot] = oldVals[s];
 }
@@ -368,6 +360,25 @@ uint32_t defaultSlotsLog2(uint32_t n)
     uint32_t l = 6;
     while (l < 63 && (1ull << l) < 6ull * n) l++;
     return l;
+}
+
+// a weld's status word as the code the get_counts functions return
+int weldStatusCode(uint32_t status)
+{
+    if (status & VH_WELD_KEY_RANGE) return VH_ERR_BAD_ARGUMENT;
+    if (status & VH_WELD_TABLE_FULL) return VH_ERR_STAGING_OVERFLOW;
+    return VH_OK;
+}
+
+// a welded mesh on the device to the host; an array that is not asked for is not copied
+int weldDownload(const VhVertex* d_vertices, const uint64_t* d_keys, const uint32_t* d_faces, VhVertex* vertices, uint64_t* keys, uint32_t* faces,
+                 uint32_t numVertices, uint32_t numFaces, hipStream_t s)
+{
+    if (vertices && numVertices) VH_HIP(hipMemcpyAsync(vertices, d_vertices, sizeof(VhVertex) * (size_t)numVertices, hipMemcpyDeviceToHost, s));
+    if (keys && numVertices) VH_HIP(hipMemcpyAsync(keys, d_keys, sizeof(uint64_t) * (size_t)numVertices, hipMemcpyDeviceToHost, s));
+    if (faces && numFaces) VH_HIP(hipMemcpyAsync(faces, d_faces, sizeof(uint32_t) * 3 * (size_t)numFaces, hipMemcpyDeviceToHost, s));
+    VH_HIP(hipStreamSynchronize(s));
+    return VH_OK;
 }
 
 } // namespace
@@ -454,9 +465,7 @@ int vh_mesh_weld_get_counts(const VhMeshWeldData* data, uint32_t out[3], vhStrea
     if (!data || !data->d_counts || !out) return VH_ERR_BAD_ARGUMENT;
     VH_HIP(hipMemcpyAsync(out, data->d_counts, sizeof(uint32_t) * 3, hipMemcpyDeviceToHost, (hipStream_t)stream));
     VH_HIP(hipStreamSynchronize((hipStream_t)stream));
-    if (out[2] & VH_WELD_KEY_RANGE) return VH_ERR_BAD_ARGUMENT;
-    if (out[2] & VH_WELD_TABLE_FULL) return VH_ERR_STAGING_OVERFLOW;
-    return VH_OK;
+    return weldStatusCode(out[2]);
 }
 
 int vh_mesh_weld_download(const VhMeshWeldData* data, VhVertex* vertices, uint64_t* keys, uint32_t* faces, uint32_t numVertices,
@@ -464,12 +473,7 @@ int vh_mesh_weld_download(const VhMeshWeldData* data, VhVertex* vertices, uint64
 {
     if (!data || !data->d_vertices) return VH_ERR_BAD_ARGUMENT;
     if (numVertices > 3ull * data->m_maxTriangles || numFaces > data->m_maxTriangles) return VH_ERR_BAD_ARGUMENT;
-    hipStream_t s = (hipStream_t)stream;
-    if (vertices && numVertices) VH_HIP(hipMemcpyAsync(vertices, data->d_vertices, sizeof(VhVertex) * (size_t)numVertices, hipMemcpyDeviceToHost, s));
-    if (keys && numVertices) VH_HIP(hipMemcpyAsync(keys, data->d_keys, sizeof(uint64_t) * (size_t)numVertices, hipMemcpyDeviceToHost, s));
-    if (faces && numFaces) VH_HIP(hipMemcpyAsync(faces, data->d_faces, sizeof(uint32_t) * 3 * (size_t)numFaces, hipMemcpyDeviceToHost, s));
-    VH_HIP(hipStreamSynchronize(s));
-    return VH_OK;
+    return weldDownload(data->d_vertices, data->d_keys, data->d_faces, vertices, keys, faces, numVertices, numFaces, (hipStream_t)stream);
 }
 
 int vh_mesh_normals_default_scale_log2(float voxelSize, int32_t* scaleLog2)
@@ -516,11 +520,7 @@ struct VhMeshWeldAccum {
     vh::DevicePtr<uint64_t> keys;
     vh::DevicePtr<uint8_t> ranks;
     vh::DevicePtr<uint32_t> faces;
-    // vertex normals (vh_mesh_weld_accum_normals): made by the first pass, for m_normalsCapacity vertices
-    vh::DevicePtr<int64_t> normalAcc;   // 3 per vertex
-    vh::DevicePtr<float> normals;       // 3 per vertex
-    vh::DevicePtr<uint32_t> normalStatus;
-    size_t m_normalsCapacity = 0;
+    VhMeshNormals normals;              // vertex normals (vh_mesh_weld_accum_normals): made by the first pass
     uint32_t m_normalsVertices = 0;     // of the pass that m_normalsValid speaks of
     bool m_normalsValid = false;        // the pass has run, and no begin or append since
     size_t m_soupCapacity = 0, m_vertexCapacity = 0, m_faceCapacity = 0; // in soup vertices, welded vertices, faces
@@ -700,9 +700,7 @@ int vh_mesh_weld_accum_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStr
     out[VH_WELD_ACCUM_REHASHES] = accum->m_rehashes;
     if (out[VH_WELD_ACCUM_STATUS] != 0u)
         out[VH_WELD_ACCUM_VERTICES] = out[VH_WELD_ACCUM_FACES] = out[VH_WELD_ACCUM_CELLS] = out[VH_WELD_ACCUM_DROPPED] = 0u; // nothing of it is a mesh
-    if (out[VH_WELD_ACCUM_STATUS] & VH_WELD_KEY_RANGE) return VH_ERR_BAD_ARGUMENT;
-    if (out[VH_WELD_ACCUM_STATUS] & VH_WELD_TABLE_FULL) return VH_ERR_STAGING_OVERFLOW;
-    return VH_OK;
+    return weldStatusCode(out[VH_WELD_ACCUM_STATUS]);
 }
 
 int vh_mesh_weld_accum_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint64_t* keys, uint32_t* faces, uint32_t numVertices,
@@ -710,12 +708,7 @@ int vh_mesh_weld_accum_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint
 {
     if (!accum) return VH_ERR_BAD_ARGUMENT;
     if (numVertices > accum->m_vertexCapacity || numFaces > accum->m_faceCapacity) return VH_ERR_BAD_ARGUMENT;
-    hipStream_t s = (hipStream_t)stream;
-    if (vertices && numVertices) VH_HIP(hipMemcpyAsync(vertices, accum->vertices.get(), sizeof(VhVertex) * (size_t)numVertices, hipMemcpyDeviceToHost, s));
-    if (keys && numVertices) VH_HIP(hipMemcpyAsync(keys, accum->keys.get(), sizeof(uint64_t) * (size_t)numVertices, hipMemcpyDeviceToHost, s));
-    if (faces && numFaces) VH_HIP(hipMemcpyAsync(faces, accum->faces.get(), sizeof(uint32_t) * 3 * (size_t)numFaces, hipMemcpyDeviceToHost, s));
-    VH_HIP(hipStreamSynchronize(s));
-    return VH_OK;
+    return weldDownload(accum->vertices.get(), accum->keys.get(), accum->faces.get(), vertices, keys, faces, numVertices, numFaces, (hipStream_t)stream);
 }
 
 int vh_mesh_weld_accum_normals(VhMeshWeldAccum* accum, int32_t scaleLog2, vhStream_t stream)
@@ -727,15 +720,7 @@ int vh_mesh_weld_accum_normals(VhMeshWeldAccum* accum, int32_t scaleLog2, vhStre
         uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
         VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream)); // waits for the appends; a weld that failed has no normals
         const uint32_t nv = have[VH_WELD_ACCUM_VERTICES], nf = have[VH_WELD_ACCUM_FACES];
-        if (!a.normalStatus) a.normalStatus = vh::deviceAlloc<uint32_t>(1, "vertex normal status");
-        if (nv > a.m_normalsCapacity) {
-            const size_t cap = std::max((size_t)nv, 2 * a.m_normalsCapacity);
-            a.normalAcc = vh::deviceAlloc<int64_t>(3 * cap, "vertex normal accumulators");
-            a.normals = vh::deviceAlloc<float>(3 * cap, "vertex normals");
-            a.m_normalsCapacity = cap;
-        }
-        VH_TRY(vh_mesh_vertex_normals(a.vertices.get(), a.keys.get(), a.faces.get(), nv, nf, scaleLog2, a.normalAcc.get(), a.normals.get(),
-                                      a.normalStatus.get(), stream));
+        VH_TRY(a.normals.run(a.vertices.get(), a.keys.get(), a.faces.get(), nv, nf, scaleLog2, stream));
         a.m_normalsVertices = nv;
         a.m_normalsValid = true;
         return VH_OK;
@@ -745,12 +730,7 @@ int vh_mesh_weld_accum_normals(VhMeshWeldAccum* accum, int32_t scaleLog2, vhStre
 int vh_mesh_weld_accum_download_normals(VhMeshWeldAccum* accum, float* normals, uint32_t numVertices, vhStream_t stream)
 {
     if (!accum || !accum->m_normalsValid || numVertices > accum->m_normalsVertices || (numVertices != 0 && !normals)) return VH_ERR_BAD_ARGUMENT;
-    hipStream_t s = (hipStream_t)stream;
-    uint32_t status = 0u;
-    VH_HIP(hipMemcpyAsync(&status, accum->normalStatus.get(), sizeof(status), hipMemcpyDeviceToHost, s));
-    if (numVertices) VH_HIP(hipMemcpyAsync(normals, accum->normals.get(), sizeof(float) * 3 * (size_t)numVertices, hipMemcpyDeviceToHost, s));
-    VH_HIP(hipStreamSynchronize(s));
-    return status != 0u ? VH_ERR_BAD_ARGUMENT : VH_OK;
+    return accum->normals.download(normals, numVertices, true, stream);
 }
 
 } // extern "C"

@@ -803,11 +803,8 @@ class CUDAMarchingCubesHashSDF:
         """device mesh of the last indexed extraction -> vertices (V,3) f32, colors (V,3) f32, keys (V,) u64, faces (F,3) u32;
         with setIndexedNormals(True), and an extraction made since, also normals (V,3) f32"""
         n = self.indexed_counts()
-        v = np.zeros(n["vertices"], dtype=T.VERTEX_DTYPE)
-        k = np.zeros(n["vertices"], dtype=np.uint64)
-        f = np.zeros((n["faces"], 3), dtype=np.uint32)
-        check(self.L.vh_marching_cubes_download_indexed(self.handle, v.ctypes.data, k.ctypes.data, f.ctypes.data), "download_indexed")
-        out = dict(vertices=np.ascontiguousarray(v["p"]), colors=np.ascontiguousarray(v["c"]), keys=k, faces=f)
+        out = _welded_arrays(n["vertices"], n["faces"], "download_indexed",
+                             lambda v, k, f, nv, nf: self.L.vh_marching_cubes_download_indexed(self.handle, v, k, f))
         if self._indexed_normals:
             out["normals"] = np.zeros((n["vertices"], 3), dtype=np.float32)
             check(self.L.vh_marching_cubes_download_indexed_normals(self.handle, out["normals"].ctypes.data), "download_indexed_normals")
@@ -867,17 +864,36 @@ def mesh_weld_key(cell, edge, snap):
     return int(key.value)
 
 
+def _upload_soup(triangles, sources, stream):
+    """a soup (T.TRIANGLE_DTYPE) and its records (T.TRIANGLE_SOURCE_DTYPE) on the device -> the two buffers and the triangle count"""
+    tris = np.ascontiguousarray(triangles, dtype=T.TRIANGLE_DTYPE).ravel()
+    srcs = np.ascontiguousarray(sources, dtype=T.TRIANGLE_SOURCE_DTYPE).ravel()
+    if len(tris) != len(srcs):
+        raise ValueError("one source record per triangle")
+    return DeviceBuffer.from_numpy(tris, stream), DeviceBuffer.from_numpy(srcs, stream), len(tris)
+
+
+def _check_weld(code, status, raise_on_status, what):
+    """what a weld's get_counts returned: a HIP error always raises; a status raises if asked to, and a code without one always"""
+    if code < 0 or (code != 0 and (raise_on_status or status == 0)):
+        check(code, what)
+
+
+def _welded_arrays(nv, nf, what, download):
+    """the arrays of a welded mesh of nv vertices and nf faces, filled by download(vertices, keys, faces, nv, nf) -> dict"""
+    v = np.zeros(int(nv), dtype=T.VERTEX_DTYPE)
+    k = np.zeros(int(nv), dtype=np.uint64)
+    f = np.zeros((int(nf), 3), dtype=np.uint32)
+    check(download(v.ctypes.data, k.ctypes.data, f.ctypes.data, len(v), len(f)), what)
+    return dict(vertices=np.ascontiguousarray(v["p"]), colors=np.ascontiguousarray(v["c"]), keys=k, faces=f)
+
+
 def mesh_weld(triangles, sources, slots_log2=0, raise_on_status=True, stream=None):
     """vh_mesh_weld on hand-made input: a soup (T.TRIANGLE_DTYPE) and its records (T.TRIANGLE_SOURCE_DTYPE) ->
     vertices, colors, keys, faces as CUDAMarchingCubesHashSDF.indexed(), and counts / status / code of the weld.  A full
     table or a key out of range raises VhError, or with raise_on_status=False comes back as `code` beside empty arrays."""
     L = load()
-    tris = np.ascontiguousarray(triangles, dtype=T.TRIANGLE_DTYPE).ravel()
-    srcs = np.ascontiguousarray(sources, dtype=T.TRIANGLE_SOURCE_DTYPE).ravel()
-    if len(tris) != len(srcs):
-        raise ValueError("one source record per triangle")
-    n = len(tris)
-    d_tris, d_srcs = DeviceBuffer.from_numpy(tris, stream), DeviceBuffer.from_numpy(srcs, stream)
+    d_tris, d_srcs, n = _upload_soup(triangles, sources, stream)
     w = T.MeshWeldData()
     check(L.vh_mesh_weld_data_alloc(C.byref(w), n, slots_log2), "vh_mesh_weld_data_alloc")
     slots = int(w.m_slotsLog2)
@@ -885,18 +901,14 @@ def mesh_weld(triangles, sources, slots_log2=0, raise_on_status=True, stream=Non
         check(L.vh_mesh_weld(d_tris.ptr, d_srcs.ptr, n, C.byref(w), slots_log2, stream), "vh_mesh_weld")
         counts = (C.c_uint32 * 3)()
         code = L.vh_mesh_weld_get_counts(C.byref(w), counts, stream)
-        if code < 0 or (code != 0 and (raise_on_status or counts[2] == 0)):
-            check(code, "vh_mesh_weld")
-        v = np.zeros(int(counts[0]), dtype=T.VERTEX_DTYPE)
-        k = np.zeros(int(counts[0]), dtype=np.uint64)
-        f = np.zeros((int(counts[1]), 3), dtype=np.uint32)
-        check(L.vh_mesh_weld_download(C.byref(w), v.ctypes.data, k.ctypes.data, f.ctypes.data, len(v), len(f), stream), "vh_mesh_weld_download")
+        _check_weld(code, counts[2], raise_on_status, "vh_mesh_weld")
+        out = _welded_arrays(counts[0], counts[1], "vh_mesh_weld_download",
+                             lambda v, k, f, nv, nf: L.vh_mesh_weld_download(C.byref(w), v, k, f, nv, nf, stream))
     finally:
         L.vh_mesh_weld_data_free(C.byref(w))
         d_tris.free()
         d_srcs.free()
-    return dict(vertices=np.ascontiguousarray(v["p"]), colors=np.ascontiguousarray(v["c"]), keys=k, faces=f,
-                counts=(int(counts[0]), int(counts[1])), status=int(counts[2]), code=int(code), slots_log2=slots)
+    return dict(out, counts=(int(counts[0]), int(counts[1])), status=int(counts[2]), code=int(code), slots_log2=slots)
 
 
 def mesh_normals_default_scale_log2(voxel_size):
@@ -965,26 +977,19 @@ def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, rai
     try:
         check(L.vh_mesh_weld_accum_begin(h, stream), "vh_mesh_weld_accum_begin")
         for triangles, sources in parts:
-            tris = np.ascontiguousarray(triangles, dtype=T.TRIANGLE_DTYPE).ravel()
-            srcs = np.ascontiguousarray(sources, dtype=T.TRIANGLE_SOURCE_DTYPE).ravel()
-            if len(tris) != len(srcs):
-                raise ValueError("one source record per triangle")
-            d_tris, d_srcs = DeviceBuffer.from_numpy(tris, stream), DeviceBuffer.from_numpy(srcs, stream)
+            d_tris, d_srcs, n = _upload_soup(triangles, sources, stream)
             buffers += [d_tris, d_srcs]
-            check(L.vh_mesh_weld_accum_append(h, d_tris.ptr, d_srcs.ptr, len(tris), stream), "vh_mesh_weld_accum_append")
+            check(L.vh_mesh_weld_accum_append(h, d_tris.ptr, d_srcs.ptr, n, stream), "vh_mesh_weld_accum_append")
         counts = (C.c_uint32 * 6)()
         code = L.vh_mesh_weld_accum_get_counts(h, counts, stream)
-        if code < 0 or (code != 0 and (raise_on_status or counts[2] == 0)):
-            check(code, "vh_mesh_weld_accum")
-        v = np.zeros(int(counts[0]), dtype=T.VERTEX_DTYPE)
-        k = np.zeros(int(counts[0]), dtype=np.uint64)
-        f = np.zeros((int(counts[1]), 3), dtype=np.uint32)
-        check(L.vh_mesh_weld_accum_download(h, v.ctypes.data, k.ctypes.data, f.ctypes.data, len(v), len(f), stream), "vh_mesh_weld_accum_download")
+        _check_weld(code, counts[2], raise_on_status, "vh_mesh_weld_accum")
+        out = _welded_arrays(counts[0], counts[1], "vh_mesh_weld_accum_download",
+                             lambda v, k, f, nv, nf: L.vh_mesh_weld_accum_download(h, v, k, f, nv, nf, stream))
         extra = {}
         if normals_scale_log2 is not None and counts[2] == 0:
             check(L.vh_mesh_weld_accum_normals(h, int(normals_scale_log2), stream), "vh_mesh_weld_accum_normals")
-            nrm = np.zeros((len(v), 3), dtype=np.float32)
-            ncode = L.vh_mesh_weld_accum_download_normals(h, nrm.ctypes.data, len(v), stream)
+            nrm = np.zeros((int(counts[0]), 3), dtype=np.float32)
+            ncode = L.vh_mesh_weld_accum_download_normals(h, nrm.ctypes.data, len(nrm), stream)
             if ncode < 0 or (ncode != 0 and raise_on_status):
                 check(ncode, "vh_mesh_weld_accum_download_normals")
             extra = dict(normals=nrm, normals_code=int(ncode))
@@ -992,8 +997,7 @@ def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, rai
         L.vh_mesh_weld_accum_destroy(h)
         for b in buffers:
             b.free()
-    return dict(vertices=np.ascontiguousarray(v["p"]), colors=np.ascontiguousarray(v["c"]), keys=k, faces=f,
-                counts=(int(counts[0]), int(counts[1])), stats={n: int(counts[i]) for i, n in enumerate(T.WELD_ACCUM_COUNTS)},
+    return dict(out, counts=(int(counts[0]), int(counts[1])), stats={n: int(counts[i]) for i, n in enumerate(T.WELD_ACCUM_COUNTS)},
                 status=int(counts[2]), code=int(code), **extra)
 
 
