@@ -123,6 +123,31 @@ def properties(mesh, soup, sources):
     return dict(repeated=repeated, duplicates=duplicates, faces_per_edge=per_edge, spread=spread, snapped_vertices=snapped)
 
 
+def assert_sources_name_their_edges(tris, srcs, voxel_size):
+    """every vertex of a sourced extraction against the end points of the edge its record names, recomputed in float32
+    the way the kernel does: worldPos = float(cell) * voxelSize, corner = worldPos +- voxelSize / 2
+    -> the snap codes (n, 3)"""
+    vs = np.float32(voxel_size)
+    P = vs / np.float32(2.0)
+    world = srcs["cell"].astype(np.float32) * vs  # (n, 3)
+    code8 = (srcs["edges"][:, None] >> (8 * np.arange(3, dtype=np.uint32))[None, :]) & 0xff
+    edge, snap = (code8 & 0xf).astype(np.int64), (code8 >> 4).astype(np.int64)
+    assert edge.max() <= 11 and snap.max() <= 2
+    p1 = world[:, None, :] + np.where(EDGE_P1[edge] == 1, P, -P).astype(np.float32)
+    p2 = world[:, None, :] + np.where(EDGE_P2[edge] == 1, P, -P).astype(np.float32)
+    assert p1.dtype == np.float32
+    pos = tris["v"]["p"]  # (n, 3, 3)
+    on_axis = EDGE_P1[edge] != EDGE_P2[edge]
+    assert np.all(on_axis.sum(axis=-1) == 1)
+    b = lambda a: np.ascontiguousarray(a).view(np.uint32)
+    assert np.array_equal(b(pos)[~on_axis], b(p1)[~on_axis]) and np.array_equal(b(pos)[~on_axis], b(p2)[~on_axis])
+    lo, hi = np.minimum(p1, p2)[on_axis], np.maximum(p1, p2)[on_axis]
+    assert np.all((pos[on_axis] >= lo) & (pos[on_axis] <= hi))
+    at1, at2 = np.all(b(pos) == b(p1), axis=-1), np.all(b(pos) == b(p2), axis=-1)
+    assert np.array_equal(snap == 1, at1) and np.array_equal(snap == 2, at2)
+    return snap
+
+
 # ---------------------------------------------------------------------------- hand-made input
 
 def source_record(cell, codes):

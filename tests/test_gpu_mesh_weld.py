@@ -92,28 +92,8 @@ def test_sourced_pass_writes_the_same_triangles_and_names_their_edges(extraction
     want_b, nb = o.extract_iso_surface(mp)
     assert 0 < nb < n and same_triangle_set(x["boxed"]["triangles"], x["boxed"]["plain"]) and same_triangle_set(x["boxed"]["triangles"], want_b)
 
-    # every vertex against the end points of the edge its record names, recomputed in float32 the way the kernel does:
-    # worldPos = float(cell) * voxelSize, corner = worldPos +- voxelSize / 2
     for part in (x["full"], x["boxed"]):
-        tris, srcs = part["triangles"], part["sources"]
-        vs = np.float32(x["hp"].m_virtualVoxelSize)
-        P = vs / np.float32(2.0)
-        world = srcs["cell"].astype(np.float32) * vs  # (n, 3)
-        code8 = (srcs["edges"][:, None] >> (8 * np.arange(3, dtype=np.uint32))[None, :]) & 0xff
-        edge, snap = (code8 & 0xf).astype(np.int64), (code8 >> 4).astype(np.int64)
-        assert edge.max() <= 11 and snap.max() <= 2
-        p1 = world[:, None, :] + np.where(MW.EDGE_P1[edge] == 1, P, -P).astype(np.float32)
-        p2 = world[:, None, :] + np.where(MW.EDGE_P2[edge] == 1, P, -P).astype(np.float32)
-        assert p1.dtype == np.float32
-        pos = tris["v"]["p"]  # (n, 3, 3)
-        on_axis = MW.EDGE_P1[edge] != MW.EDGE_P2[edge]
-        assert np.all(on_axis.sum(axis=-1) == 1)
-        b = lambda a: np.ascontiguousarray(a).view(np.uint32)
-        assert np.array_equal(b(pos)[~on_axis], b(p1)[~on_axis]) and np.array_equal(b(pos)[~on_axis], b(p2)[~on_axis])
-        lo, hi = np.minimum(p1, p2)[on_axis], np.maximum(p1, p2)[on_axis]
-        assert np.all((pos[on_axis] >= lo) & (pos[on_axis] <= hi))
-        at1, at2 = np.all(b(pos) == b(p1), axis=-1), np.all(b(pos) == b(p2), axis=-1)
-        assert np.array_equal(snap == 1, at1) and np.array_equal(snap == 2, at2)
+        snap = MW.assert_sources_name_their_edges(part["triangles"], part["sources"], x["hp"].m_virtualVoxelSize)
         if name == "S2" and part is x["full"]:
             assert (snap != 0).sum() > 0  # the scene that is here for its snapped vertices
 

@@ -410,6 +410,44 @@ def test_marching_cubes(libs, name, off):
     assert np.array_equal(got.view(np.uint8), want.view(np.uint8))
 
 
+def test_marching_cubes_on_crafted_fields(libs):
+    """The fields of tests/mc_fields.py: every cube case with the edge-mask-255 rule, far coordinates, the threshold
+    comparison stepped over its rounding edge, unobserved taps and snapped vertices.  The state is the oracle's after
+    its stream-in, copied; the reference's own extraction on it against the oracle's, bit for bit."""
+    import mc_fields as F
+
+    def compare(name, descs, blocks, what, count=None):
+        hp, cp, mp, vs = F.config(name)
+        a, b = O.OracleScene(hp, cp), O.OracleScene(hp, cp)
+        assert a.stream_in(descs, blocks) == 0
+        _copy_state(a, b)
+        rb = R.RefScene(b)
+        want, n = a.extract_iso_surface(mp)
+        assert count is None or n == count, f"{what}: {n} triangles, {count} expected"
+        for two in (True, False):
+            got, m = rb.extract_iso_surface(mp, two_pass=two)
+            assert m == n, f"{what}: {m} != {n} triangles"
+            if two:
+                assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), what
+            assert np.array_equal(_mc_sorted(got), _mc_sorted(want)), what
+        return n
+
+    for name in ("P2", "P4"):
+        vs = f32(synth.PARAM_SETS[name]["voxel_size"])
+        thres = f32(10.0) * vs
+        for origin in (F.NEAR, (131070, -2, -1)):
+            n = compare(name, *F.planted(origin, vs, f32(10.0) * vs), f"{name} planted at {origin}")
+            assert n > 10000
+        for origin in (F.NEAR, F.FAR):
+            for k, count in zip(F.SWEEP_KS, F.SWEEP_COUNTS[origin]):
+                compare(name, *F.planted(origin, vs, F.sweep_amplitude(thres, k)), f"{name} sweep {k} at {origin}", count)
+    for name, seed in F.RANDOM_SEEDS:
+        thres = f32(10.0) * f32(synth.PARAM_SETS[name]["voxel_size"])
+        descs, blocks = F.random_field(F.block_ids(), seed, float(thres), **F.RANDOM)
+        assert compare(name, descs, blocks, f"{name} random {seed}") > 5000
+        assert compare(name, *F.without(descs, blocks, F.LEFT_OUT), f"{name} random {seed}, 18 blocks") > 2000
+
+
 # ------------------------------------------------------------------------------------------------------ sensor maps
 
 SIZES = [(1, 1), (7, 5), (33, 9), (101, 77), (640, 480)]
