@@ -712,7 +712,8 @@ struct MeshData {
 };
 } // namespace vh
 
-struct VhMeshNormals; // opaque: the buffers of the vertex-normal pass (csrc/vh_mesh_normals.hpp)
+struct VhMeshNormals;    // opaque: the buffers of the vertex-normal pass (csrc/vh_mesh_normals.hpp)
+struct VhMeshComponents; // opaque: the buffers of the component pass (csrc/vh_mesh_components.hpp)
 
 class CUDAMarchingCubesHashSDF {
 public:
@@ -725,7 +726,7 @@ public:
     static MarchingCubesParams parameters(unsigned int marchingCubesMaxNumTriangles, float SDFMarchingCubeThreshFactor,
                                           float SDFVoxelSize, unsigned int hashNumBuckets);
 
-    void clearMeshBuffer() { m_meshData.clear(); m_welded = false; } // (MeshData::clear takes the normals with it)
+    void clearMeshBuffer() { m_meshData.clear(); clearWeldedMark(); } // (MeshData::clear takes the normals with it)
     // copies the result of the last extraction to the host and appends it to the mesh (.cpp:31-86); throws when the
     // triangle buffer overflowed.  offlineProcessing (GlobalAppState::s_offlineProcessing): merge each batch first.
     void copyTrianglesToCPU();
@@ -763,7 +764,7 @@ public:
     // of the last accumulated extraction: the VH_WELD_ACCUM_NUM_COUNTS counts of vh_types.h; 0 after a one-shot one
     void getIndexedStats(unsigned int out[6]) const { for (int i = 0; i < 6; i++) out[i] = m_indexed.accumulated ? m_indexed.counts[i] : 0u; }
     bool isWelded() const { return m_welded; }
-    void getIndexedCounts(unsigned int out[3]) const { for (int i = 0; i < 3; i++) out[i] = m_indexed.counts[i]; }
+    void getIndexedCounts(unsigned int out[3]) const { for (int i = 0; i < 3; i++) out[i] = i < 2 && m_indexed.filtered ? m_indexed.kept[i] : m_indexed.counts[i]; }
     void downloadIndexed(VhVertex* vertices, uint64_t* keys, uint32_t* faces); // device mesh of the last indexed extraction
     // Vertex normals of the indexed mesh ("Vertex normals"), off by default.  When on, the three
     // indexed extractions run vh_mesh_vertex_normals after the weld -- finishIndexed over the whole accumulation -- with
@@ -771,6 +772,15 @@ public:
     // writes.  A status of the pass throws VH_ERR_BAD_ARGUMENT and leaves the buffer empty.
     void setIndexedNormals(bool on) { m_indexedNormals = on; }
     void downloadIndexedNormals(float* normals); // 3 per vertex, in downloadIndexed's order; throws if that extraction had none
+    // The component filter of the indexed mesh ("Mesh components"), off by default (0, false).
+    // When on, readBackIndexed -- the one-shot extraction, finishIndexed and the chunk-grid walk alike -- labels the
+    // welded mesh's connected components after the weld and the normals and keeps those of at least minFaces faces, with
+    // largestOnly the largest of them alone: getIndexedCounts, downloadIndexed, downloadIndexedNormals, the mesh buffer
+    // and saveMesh then describe the FILTERED mesh; what the unfiltered one held is in the component stats.  A status of
+    // the labelling throws VH_ERR_BAD_ARGUMENT and leaves the buffer empty.
+    void setIndexedComponentFilter(unsigned int minFaces, bool largestOnly) { m_componentMinFaces = minFaces; m_componentLargestOnly = largestOnly; }
+    // the VH_COMPONENTS_NUM_COUNTS counts of the mesh in the buffer; 0 when it was made with the filter off, or is no longer the weld's
+    void getIndexedComponentStats(unsigned int out[6]) const { for (int i = 0; i < 6; i++) out[i] = m_indexed.componentStats[i]; }
     void downloadSources(VhTriangleSource* out, unsigned int n);               // source records of the last indexed extraction
 
     const vh::MeshData& getMeshData() const { return m_meshData; }
@@ -806,13 +816,21 @@ private:
     // vertex normals: the one-shot extraction's buffers (csrc/vh_mesh_normals.hpp) are made by its first call with the option on
     bool m_indexedNormals = false;
     std::unique_ptr<VhMeshNormals> m_normals;   // (complete where the constructor and the destructor are: vh_marching_cubes.cpp)
+    // component filter: the one-shot extraction's buffers (csrc/vh_mesh_components.hpp) are made by its first call with the filter on
+    unsigned int m_componentMinFaces = 0;
+    bool m_componentLargestOnly = false;
+    std::unique_ptr<VhMeshComponents> m_components;
     struct IndexedResult {                      // what the last indexed extraction left; the empty one is the state after an error
         unsigned int counts[VH_WELD_ACCUM_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 }; // {vertices, faces, status}, then the accumulation's three
         unsigned int numSourced = 0;            // triangles of its last sourced pass 2 that are in the buffer
         bool accumulated = false;               // begun by beginIndexed: downloadIndexed reads m_accum, not m_weld
         bool hasNormals = false;                // it computed them
         float voxelSize = 0.0f;                 // of the last appendIndexed: finishIndexed's scale
+        bool filtered = false;                  // the component filter ran: the mesh is kept[] = {vertices, faces} of the filter's own buffers
+        unsigned int kept[2] = { 0, 0 };
+        unsigned int componentStats[VH_COMPONENTS_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
     } m_indexed;
+    void clearWeldedMark() { m_welded = false; for (unsigned int& c : m_indexed.componentStats) c = 0; }
     void resetIndexed() { clearMeshBuffer(); m_indexed = IndexedResult(); }
     // the welded mesh on the device (m_accum's, or m_weld's) into the mesh buffer, with normals at that scale if the
     // option is on; then its counts and marks

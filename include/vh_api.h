@@ -55,7 +55,10 @@ int vh_memset(void* dst, int value, size_t bytes, vhStream_t stream);
 int vh_time_next_launch(void* startEvent, void* stopEvent);
 /* the same for an entry point that launches several kernels: `skip` of the calling thread's timed launches pass first.
  * vh_extract_iso_surface_pass2[_sourced] launch one kernel; vh_mesh_weld launches insert, number, faces (skip 0, 1, 2),
- * vh_mesh_weld_accum_append insert, settle, faces; vh_mesh_vertex_normals and vh_mesh_weld_accum_normals faces, finish. */
+ * vh_mesh_weld_accum_append insert, settle, faces; vh_mesh_vertex_normals and vh_mesh_weld_accum_normals faces, finish;
+ * vh_mesh_components init, hook, flatten, count (init alone without faces); vh_mesh_components_filter stats, with
+ * largestOnly pick by key and pick by index, compact vertices, compact faces (not without faces);
+ * vh_mesh_weld_accum_components the launches of vh_mesh_components, then those of vh_mesh_components_filter. */
 int vh_time_launch_after(uint32_t skip, void* startEvent, void* stopEvent);
 int vh_stream_create(vhStream_t* out);   /* a non-blocking HIP stream, for FFI users without a HIP binding */
 int vh_stream_destroy(vhStream_t stream);
@@ -736,6 +739,32 @@ int vh_mesh_vertex_normals(const VhVertex* d_vertices, const uint64_t* d_keys, c
  * |a x b| <= 3 voxelSize^2 and the scaled components stay below 2^40.  VH_ERR_BAD_ARGUMENT for a voxel size that is
  * not finite or not positive. */
 int vh_mesh_normals_default_scale_log2(float voxelSize, int32_t* scaleLog2);
+/* ---- connected components of an indexed mesh (csrc/vh_mesh.hip; DESIGN.md section 4, "Mesh components").  Vertex a
+ * comes before b when (key[a], a) < (key[b], b).  Two vertices are joined when a face names both; a component's root
+ * is its first vertex.  A lock-free union-find: init, hook (one lane per face), flatten, count.
+ *   d_keys        numVertices keys                  d_faces   numFaces index triples
+ *   d_root        one per vertex: the index of its component's root (a vertex without a face is its own)
+ *   d_faceCount   one per vertex: at a root the number of in-range faces whose first index lies in its component, else 0
+ *   d_status      one word: 0, or VH_COMPONENTS_BAD_INDEX (a face with an index >= numVertices: it joins nothing and
+ *                 counts nowhere) | VH_COMPONENTS_STEPS
+ * A face with a repeated index joins its distinct vertices and counts as one face.  Asynchronous on `stream`;
+ * numVertices = 0 launches nothing, numFaces = 0 the init alone.  Callers map a status to VH_ERR_BAD_ARGUMENT. */
+int vh_mesh_components(const uint64_t* d_keys, const uint32_t* d_faces, uint32_t numVertices, uint32_t numFaces, uint32_t* d_root, uint32_t* d_faceCount,
+                       uint32_t* d_status, vhStream_t stream);
+/* Keeps the components of at least minFaces faces and, with largestOnly, of those only the largest (the greatest face
+ * count; among equals the root that comes first), compacted into the caller's output arrays: nothing is compacted in
+ * place.  Vertex and face order of the output come from atomics; winding and rotation of a face are left alone.
+ *   d_vertices, d_keys, d_faces, numVertices, numFaces   the mesh that vh_mesh_components labelled
+ *   d_normals / d_outNormals   3 floats per vertex, or NULL: normals ride along
+ *   d_root, d_faceCount, d_status   what vh_mesh_components left; with a status set nothing is kept and all counts read 0
+ *   d_newIndex   scratch, one word per vertex         d_best   scratch, two 64-bit words
+ *   d_outVertices, d_outKeys   room for numVertices   d_outFaces   room for numFaces triples
+ *   d_counts     VH_COMPONENTS_NUM_COUNTS words (vh_types.h)
+ * minFaces = 0 and largestOnly = 0 keep everything.  With minFaces >= 1 the vertices without a face go. */
+int vh_mesh_components_filter(const VhVertex* d_vertices, const uint64_t* d_keys, const float* d_normals, const uint32_t* d_faces, uint32_t numVertices,
+                              uint32_t numFaces, const uint32_t* d_root, const uint32_t* d_faceCount, const uint32_t* d_status, uint32_t minFaces,
+                              uint32_t largestOnly, uint32_t* d_newIndex, uint64_t* d_best, VhVertex* d_outVertices, uint64_t* d_outKeys,
+                              float* d_outNormals, uint32_t* d_outFaces, uint32_t* d_counts, vhStream_t stream);
 /* Host only: vh::MeshData::applyTransform (when transform is not NULL) and saveToPLY on the caller's arrays.
  *   vertices3, colors4 (may be NULL), normals3 (may be NULL)   numVertices rows each
  *   faceIndices   numFaceIndices = 3 per face; 0 = a triangle soup
@@ -783,6 +812,19 @@ int vh_mesh_weld_accum_normals(VhMeshWeldAccum* accum, int32_t scaleLog2, vhStre
  * result would be stale), when numVertices exceeds what the pass saw, or when the pass left a status (the normals are
  * then all zero). */
 int vh_mesh_weld_accum_download_normals(VhMeshWeldAccum* accum, float* normals, uint32_t numVertices, vhStream_t stream);
+
+/* The component filter over the accumulated mesh (vh_mesh_components, then vh_mesh_components_filter): a pass at the
+ * end, never per append, because a component spans appends.  Waits for the appends, then launches and returns; the
+ * buffers are the accumulator's own (44 B per welded vertex and 12 B per face more), and its own mesh, counts and
+ * downloads stay what they are.  Normals ride along when vh_mesh_weld_accum_normals has run since the last append. */
+int vh_mesh_weld_accum_components(VhMeshWeldAccum* accum, uint32_t minFaces, uint32_t largestOnly, vhStream_t stream);
+/* Waits and reads the VH_COMPONENTS_NUM_COUNTS counts.  VH_ERR_BAD_ARGUMENT when no pass has run since the last begin
+ * or append (its result would be stale), or when the labelling left a status (the counts are then 0). */
+int vh_mesh_weld_accum_components_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream);
+/* The filtered mesh; each array may be NULL.  numVertices / numFaces: the kept ones of the counts.  Refused as above,
+ * and when normals are asked for that the pass did not carry. */
+int vh_mesh_weld_accum_components_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint64_t* keys, float* normals, uint32_t* faces,
+                                           uint32_t numVertices, uint32_t numFaces, vhStream_t stream);
 
 /* handle level: CUDAMarchingCubesHashSDF (DSC/CUDAMarchingCubesHashSDF.h:8-67) */
 typedef struct VhMarchingCubes VhMarchingCubes;
@@ -835,6 +877,14 @@ int vh_marching_cubes_download_indexed_normals(VhMarchingCubes* mc, float* norma
 /* the host mesh's normals: out = number of floats (3 per vertex, or 0), then the array */
 int vh_marching_cubes_get_mesh_normals_size(VhMarchingCubes* mc, uint64_t* out);
 int vh_marching_cubes_get_mesh_normals(VhMarchingCubes* mc, float* normals3);
+/* The component filter for the indexed extractions (off by default: minFaces = 0 and largestOnly = 0).  When on, the
+ * three indexed extractions run vh_mesh_components and vh_mesh_components_filter after the weld and the normals -- the
+ * accumulated ones at the finish -- and get_indexed_counts, download_indexed, download_indexed_normals, the host mesh
+ * and save_mesh all describe the FILTERED mesh.  A status of the labelling: VH_ERR_BAD_ARGUMENT, the host mesh empty. */
+int vh_marching_cubes_set_indexed_component_filter(VhMarchingCubes* mc, uint32_t minFaces, uint32_t largestOnly);
+/* of the last indexed extraction with the filter on: the VH_COMPONENTS_NUM_COUNTS counts, which say what the
+ * unfiltered mesh held; all 0 when it ran with the filter off */
+int vh_marching_cubes_get_indexed_component_stats(VhMarchingCubes* mc, uint32_t out[6]);
 /* the first n source records of the last indexed extraction (n <= min(triangles produced, m_maxNumTriangles)) */
 int vh_marching_cubes_download_sources(VhMarchingCubes* mc, VhTriangleSource* out, uint32_t n);
 int vh_marching_cubes_copy_triangles_to_cpu(VhMarchingCubes* mc);

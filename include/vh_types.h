@@ -226,6 +226,20 @@ typedef struct VhTriangleSource {
 #define VH_NORMALS_RANGE 1u     /* a scaled face normal is not finite or exceeds 2^40 in a component: scaleLog2 is too large */
 #define VH_NORMALS_BAD_INDEX 2u /* a face index >= numVertices (nothing was read through it) */
 
+/* status word of the component labelling (vh_mesh_components); either bit makes the filter keep nothing */
+#define VH_COMPONENTS_BAD_INDEX 1u /* a face index >= numVertices (nothing was read through it; the face joins nothing) */
+#define VH_COMPONENTS_STEPS 2u     /* a walk to a root took more steps than there are vertices (unreachable; defended) */
+/* what vh_mesh_components_filter counts */
+enum {
+    VH_COMPONENTS_WITH_FACES = 0,     /* components of at least one face */
+    VH_COMPONENTS_FACELESS = 1,       /* vertices that no in-range face names */
+    VH_COMPONENTS_KEPT = 2,           /* components with a face that the filter kept */
+    VH_COMPONENTS_KEPT_VERTICES = 3,
+    VH_COMPONENTS_KEPT_FACES = 4,
+    VH_COMPONENTS_LARGEST_FACES = 5,  /* faces of the largest component */
+    VH_COMPONENTS_NUM_COUNTS = 6
+};
+
 /* Device buffers of the weld (vh_mesh_weld): an open-addressing table of numSlots = 1 << m_slotsLog2 slots, and the
  * indexed mesh it produces.  Sized for m_maxTriangles triangles, that is 3 * m_maxTriangles vertices at worst. */
 typedef struct VhMeshWeldData {

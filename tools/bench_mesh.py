@@ -26,6 +26,13 @@ add to the download, and the wall time of the extraction (of the indexed walk) w
 off.
 
     python tools/bench_mesh.py --indexed --normals [--streamed] [--config cfg3]
+
+--components (with --indexed) adds the component pass ("Mesh components"): each of its kernels by
+vh_time_launch_after, the pass as a share of the indexed extraction's kernels, the serial alternative it replaces (the
+download of the welded mesh and the labelling of tests/mesh_components.py on the host), and the wall time of the
+extraction with the filter on beside the one with it off.
+
+    python tools/bench_mesh.py --indexed --components [--normals] [--config cfg3]
 """
 import argparse
 import ctypes as C
@@ -100,6 +107,39 @@ def indexed_report(args, scene, hp):
         out.update(normals_scale_log2=scale, normals_device_bytes=36 * V + 4, download_bytes_normals=12 * V)
         for b in (acc, nrm, st):
             b.free()
+    if args.components:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import mesh_components as MC  # the numpy restatement: the host pass a user would run on the downloaded mesh
+        bufs = [lib.DeviceBuffer(4 * V), lib.DeviceBuffer(4 * V), lib.DeviceBuffer(4), lib.DeviceBuffer(4 * V), lib.DeviceBuffer(16),
+                lib.DeviceBuffer(24 * V), lib.DeviceBuffer(8 * V), lib.DeviceBuffer(12 * F), lib.DeviceBuffer(24)]
+        root, cnt, st, newi, best, ov, ok, of, cc = bufs
+        label = lambda: lib.check(L.vh_mesh_components(w.d_keys, w.d_faces, V, F, root.ptr, cnt.ptr, st.ptr, None), "vh_mesh_components")
+        names = ["components_init_us", "components_hook_us", "components_flatten_us", "components_count_us"]
+        for skip, name in enumerate(names):
+            out[name] = timed(skip, label)
+        filt = lambda: lib.check(L.vh_mesh_components_filter(w.d_vertices, w.d_keys, None, w.d_faces, V, F, root.ptr, cnt.ptr, st.ptr, args.min_component, 1, newi.ptr,
+                                                             best.ptr, ov.ptr, ok.ptr, None, of.ptr, cc.ptr, None), "vh_mesh_components_filter")
+        more = ["components_stats_us", "components_pick_key_us", "components_pick_index_us", "components_compact_vertices_us", "components_compact_faces_us"]
+        for skip, name in enumerate(more):
+            out[name] = timed(skip, filt)
+        assert int(st.download(np.uint32, 1)[0]) == 0, "the labelling left a status"
+        stats = {k: int(v) for k, v in zip(T.COMPONENTS_COUNTS, cc.download(np.uint32, 6))}
+        total = sum(out[k] for k in names + more)
+        kernels = out["pass2_sourced_us"] + out["weld_insert_us"] + out["weld_number_us"] + out["weld_faces_us"] + out.get("normals_faces_us", 0.0) + out.get("normals_finish_us", 0.0)
+        out.update(components=stats, components_min_faces=args.min_component, components_pass_us=round(total, 2),
+                   components_share_of_indexed_kernels=round(total / (kernels + total), 4), components_device_bytes=44 * V + 12 * F + 44)
+        # the serial alternative: the welded mesh to the host, labelled there
+        keys, faces = np.zeros(V, dtype=np.uint64), np.zeros((F, 3), dtype=np.uint32)
+        t0 = time.perf_counter()
+        lib.check(L.vh_mesh_weld_download(C.byref(w), None, keys.ctypes.data, faces.ctypes.data, V, F, None), "vh_mesh_weld_download")
+        t_down = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        h_root, h_count, h_status = MC.components(keys, faces)
+        t_host = time.perf_counter() - t0
+        assert h_status == 0 and np.array_equal(h_root, root.download(np.uint32, V)) and np.array_equal(h_count, cnt.download(np.uint32, V))
+        out.update(host_labelling_download_s=round(t_down, 5), host_labelling_s=round(t_host, 5))
+        for b in bufs:
+            b.free()
     L.vh_mesh_weld_data_free(C.byref(w))
     L.vh_marching_cubes_data_free(C.byref(data))
     # the host merge on the same soup: saveMesh = merge + PLY; the PLY alone is timed on the indexed mesh and taken off
@@ -125,6 +165,18 @@ def indexed_report(args, scene, hp):
                     if rep > 0:
                         walls[on].append(time.perf_counter() - t0)
             out.update(extract_indexed_off_wall_s=round(float(np.median(walls[False])), 5), extract_indexed_normals_wall_s=round(float(np.median(walls[True])), 5))
+        if args.components:  # the whole extraction, filter off and on, alternating (the first pair sizes the buffers)
+            mc.setIndexedNormals(bool(args.normals))
+            walls = {False: [], True: []}
+            for rep in range(1 + max(args.reps, 3)):
+                for on in (False, True):
+                    mc.setIndexedComponentFilter(args.min_component if on else 0, False)
+                    t0 = time.perf_counter()
+                    mc.extractIsoSurfaceIndexed(hd, hpp)
+                    if rep > 0:
+                        walls[on].append(time.perf_counter() - t0)
+            spread = lambda v: [round(float(np.min(v)), 5), round(float(np.median(v)), 5), round(float(np.max(v)), 5)]
+            out.update(extract_indexed_filter_off_wall_s=spread(walls[False]), extract_indexed_filter_on_wall_s=spread(walls[True]))
     out.update(host_merge_s=round(t_soup - t_ply, 4), ply_write_s=round(t_ply, 4), extract_indexed_wall_s=round(t_indexed, 4))
     return out
 
@@ -270,9 +322,13 @@ def main():
     ap.add_argument("--indexed", action="store_true", help="measure the indexed extraction stage by stage instead")
     ap.add_argument("--streamed", action="store_true", help="--indexed: the scene behind a chunk grid; soup walk + host merge against the indexed walk")
     ap.add_argument("--normals", action="store_true", help="--indexed: add the vertex-normal pass: its two kernels, its download, the extraction with it on and off")
+    ap.add_argument("--components", action="store_true", help="--indexed: add the component pass: its kernels, its share of the extraction, the labelling on the host beside it")
+    ap.add_argument("--min-component", type=int, default=100, help="--components: the filter's minFaces")
     args = ap.parse_args()
     if args.normals and not args.indexed:
         ap.error("--normals needs --indexed")
+    if args.components and (not args.indexed or args.streamed):
+        ap.error("--components needs --indexed, without --streamed")
 
     import torch
     from voxelhashing_amd import engine as E, synth, vhtypes as T

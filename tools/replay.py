@@ -3,7 +3,7 @@
 parameter file, optional mesh at the end) and prints one JSON line with the timing.
 
     python tools/replay.py --params zParameters.txt [--tracking zParametersTracking.txt] [--rgbd-tracking] [--sens a.sens b.sens]
-                           [--mesh scan.ply [--indexed-mesh [--mesh-normals]]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
+                           [--mesh scan.ply [--indexed-mesh [--mesh-normals] [--mesh-min-component N] [--mesh-largest-component]]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
                            [--native [--batch N] [--native-tracking]] [--weighted-colour]
 
 Without --sens the files named by s_binaryDumpSensorFile[i] in the parameter file are played.  The rendering keys
@@ -41,6 +41,8 @@ def main():
     ap.add_argument("--mesh", default=None)
     ap.add_argument("--indexed-mesh", action="store_true", help="--mesh: weld the triangles on the device instead of merging them on the host; with s_streamingEnabled the chunks' triangles are welded into one mesh as the chunk grid is walked")
     ap.add_argument("--mesh-normals", action="store_true", help="--indexed-mesh: compute vertex normals on the device after the weld and write nx, ny, nz into the PLY")
+    ap.add_argument("--mesh-min-component", type=int, default=0, metavar="N", help="--indexed-mesh: drop the connected components of fewer than N faces on the device before the mesh is written")
+    ap.add_argument("--mesh-largest-component", action="store_true", help="--indexed-mesh: keep only the connected component with the most faces")
     ap.add_argument("--record", default=None, help="write what was processed, with the poses used, to this .sens file")
     ap.add_argument("--max-frames", type=int, default=None)
     ap.add_argument("--render-to", default=None, help="renderToFile: the shaded model and the input of every frame as PNGs under this directory")
@@ -52,6 +54,12 @@ def main():
     args = ap.parse_args()
     if args.mesh_normals and not args.indexed_mesh:
         ap.error("--mesh-normals needs --indexed-mesh: only the welded mesh has vertices that faces share")
+    if args.mesh_min_component and not args.indexed_mesh:
+        ap.error("--mesh-min-component needs --indexed-mesh: a triangle soup has no connectivity")
+    if args.mesh_largest_component and not args.indexed_mesh:
+        ap.error("--mesh-largest-component needs --indexed-mesh: a triangle soup has no connectivity")
+    if args.mesh_min_component < 0:
+        ap.error("--mesh-min-component: a number of faces")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU (there is no CPU fallback)")
@@ -97,10 +105,15 @@ def main():
     if args.record:
         out["recorded"] = rec.saveRecordedFramesToFile(args.record)
     if args.mesh:
-        m = rec.extractIsoSurfaceIndexed(args.mesh, normals=args.mesh_normals) if args.indexed_mesh else rec.extractIsoSurface(args.mesh)
+        if args.indexed_mesh:
+            m = rec.extractIsoSurfaceIndexed(args.mesh, normals=args.mesh_normals, min_component_faces=args.mesh_min_component, largest_component=args.mesh_largest_component)
+        else:
+            m = rec.extractIsoSurface(args.mesh)
         out["mesh"] = dict(file=args.mesh, indexed=bool(args.indexed_mesh), vertices=int(len(m["vertices"])), faces=int(len(m["faces"])))
         if args.mesh_normals:
             out["mesh"]["normals"] = int(len(m["normals"]))
+        if args.mesh_min_component or args.mesh_largest_component:
+            out["mesh"]["components"] = m["components"]
     print(json.dumps(out))
 
 

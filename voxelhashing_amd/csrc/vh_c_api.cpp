@@ -423,6 +423,18 @@ int vh_marching_cubes_set_indexed_normals(VhMarchingCubes* mc, int enabled)
     mc->impl.setIndexedNormals(enabled != 0);
     return VH_OK;
 }
+int vh_marching_cubes_set_indexed_component_filter(VhMarchingCubes* mc, uint32_t minFaces, uint32_t largestOnly)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    mc->impl.setIndexedComponentFilter(minFaces, largestOnly != 0);
+    return VH_OK;
+}
+int vh_marching_cubes_get_indexed_component_stats(VhMarchingCubes* mc, uint32_t out[6])
+{
+    if (!mc || !out) return VH_ERR_BAD_ARGUMENT;
+    mc->impl.getIndexedComponentStats(out);
+    return VH_OK;
+}
 int vh_marching_cubes_download_indexed_normals(VhMarchingCubes* mc, float* normals)
 {
     if (!mc) return VH_ERR_BAD_ARGUMENT;

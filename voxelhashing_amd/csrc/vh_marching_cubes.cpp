@@ -18,6 +18,7 @@
 
 #include "../../include/vh.hpp"
 #include "vh_host_util.hpp"
+#include "vh_mesh_components.hpp"
 #include "vh_mesh_normals.hpp"
 
 // ---------------------------------------------------------------------------
@@ -365,29 +366,56 @@ void recordsToMeshData(const VhVertex* v, size_t n, vh::MeshData& md)
 void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf, bool accumulated, int32_t scaleLog2)
 {
     vh::MeshData md;
+    const bool filter = m_componentMinFaces != 0 || m_componentLargestOnly;
     if (m_indexedNormals) {
-        // over all the faces, with the bits the last append left: a pass of the finish, never of an append
-        md.m_Normals.resize(3 * (size_t)nv);
+        // over all the faces, with the bits the last append left: a pass of the finish, never of an append.  With the
+        // filter on only the pass's status comes back here: the normals come with the filtered mesh.
+        const unsigned int toHost = filter ? 0u : nv;
+        md.m_Normals.resize(3 * (size_t)toHost);
         int rc = VH_OK;
         if (accumulated) {
             check(vh_mesh_weld_accum_normals(m_accum.get(), scaleLog2, m_stream), "vh_mesh_weld_accum_normals");
-            rc = vh_mesh_weld_accum_download_normals(m_accum.get(), md.m_Normals.data(), nv, m_stream);
+            rc = vh_mesh_weld_accum_download_normals(m_accum.get(), md.m_Normals.data(), toHost, m_stream);
         } else {
             if (!m_normals) m_normals.reset(new VhMeshNormals);
             check(m_normals->run(m_weld.d_vertices, m_weld.d_keys, m_weld.d_faces, nv, nf, scaleLog2, m_stream), "vh_mesh_vertex_normals");
-            rc = m_normals->download(md.m_Normals.data(), nv, true, m_stream);
+            rc = m_normals->download(md.m_Normals.data(), toHost, true, m_stream);
         }
         if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "vertex normals: a face normal is out of the fixed-point range, or a face index out of bounds");
         check(rc, "vertex normals");
     }
-    std::vector<VhVertex> verts(nv);
-    md.m_FaceIndicesVertices.resize(3 * (size_t)nf);
-    if (accumulated) check(vh_mesh_weld_accum_download(m_accum.get(), verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_download");
+    unsigned int stats[VH_COMPONENTS_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 }, mv = nv, mf = nf; // mv, mf: the mesh that goes to the host
+    if (filter) {
+        // a component spans chunks: like the normals a pass of the finish.  The unfiltered mesh stays where it is.
+        int rc = VH_OK;
+        if (accumulated) {
+            check(vh_mesh_weld_accum_components(m_accum.get(), m_componentMinFaces, m_componentLargestOnly ? 1u : 0u, m_stream), "vh_mesh_weld_accum_components");
+            rc = vh_mesh_weld_accum_components_get_counts(m_accum.get(), stats, m_stream);
+        } else {
+            if (!m_components) m_components.reset(new VhMeshComponents);
+            check(m_components->run(m_weld.d_vertices, m_weld.d_keys, m_indexedNormals ? m_normals->normals.get() : nullptr, m_weld.d_faces, nv, nf,
+                                    m_componentMinFaces, m_componentLargestOnly ? 1u : 0u, m_stream), "vh_mesh_components");
+            rc = m_components->counts(stats, m_stream);
+        }
+        if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "mesh components: a face index out of bounds");
+        check(rc, "mesh components");
+        mv = stats[VH_COMPONENTS_KEPT_VERTICES]; mf = stats[VH_COMPONENTS_KEPT_FACES];
+        if (m_indexedNormals) md.m_Normals.resize(3 * (size_t)mv);
+    }
+    std::vector<VhVertex> verts(mv);
+    md.m_FaceIndicesVertices.resize(3 * (size_t)mf);
+    float* normals = filter && m_indexedNormals ? md.m_Normals.data() : nullptr;
+    if (filter && accumulated) check(vh_mesh_weld_accum_components_download(m_accum.get(), verts.data(), nullptr, normals, md.m_FaceIndicesVertices.data(), mv, mf, m_stream), "vh_mesh_weld_accum_components_download");
+    else if (filter) check(m_components->download(verts.data(), nullptr, normals, md.m_FaceIndicesVertices.data(), mv, mf, m_stream), "mesh components");
+    else if (accumulated) check(vh_mesh_weld_accum_download(m_accum.get(), verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_download");
     else check(vh_mesh_weld_download(&m_weld, verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_download");
     recordsToMeshData(verts.data(), verts.size(), md);
     m_meshData = std::move(md);
     m_indexed.counts[0] = nv; m_indexed.counts[1] = nf;
     m_indexed.hasNormals = m_indexedNormals;
+    m_indexed.filtered = filter;
+    m_indexed.kept[0] = mv; m_indexed.kept[1] = mf;
+    std::copy(stats, stats + VH_COMPONENTS_NUM_COUNTS, m_indexed.componentStats);
     m_welded = true;
 }
 
@@ -455,6 +483,7 @@ void CUDAMarchingCubesHashSDF::finishIndexed()
     for (unsigned int& c : m_indexed.counts) c = 0;
     m_indexed.counts[VH_WELD_ACCUM_STATUS] = stats[VH_WELD_ACCUM_STATUS];
     m_indexed.hasNormals = false;
+    m_indexed.filtered = false;
     checkWeld(rc, "vh_mesh_weld_accum_get_counts");
     // (without an append there is no voxel size, and no vertex either: any scale serves)
     int32_t scaleLog2 = 0;
@@ -528,6 +557,13 @@ void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(CUDASceneRepChunkGrid& c
 
 void CUDAMarchingCubesHashSDF::downloadIndexed(VhVertex* vertices, uint64_t* keys, uint32_t* faces)
 {
+    if (m_indexed.filtered) { // the filter's own buffers: the unfiltered mesh is still where the weld left it
+        const unsigned int kv = m_indexed.kept[0], kf = m_indexed.kept[1];
+        if (kv == 0 && kf == 0) return;
+        if (m_indexed.accumulated) check(vh_mesh_weld_accum_components_download(m_accum.get(), vertices, keys, nullptr, faces, kv, kf, m_stream), "vh_mesh_weld_accum_components_download");
+        else check(m_components->download(vertices, keys, nullptr, faces, kv, kf, m_stream), "mesh components");
+        return;
+    }
     const unsigned int nv = m_indexed.counts[0], nf = m_indexed.counts[1];
     if (nv == 0 && nf == 0) return;
     if (m_indexed.accumulated) {
@@ -541,6 +577,13 @@ void CUDAMarchingCubesHashSDF::downloadIndexed(VhVertex* vertices, uint64_t* key
 void CUDAMarchingCubesHashSDF::downloadIndexedNormals(float* normals)
 {
     if (!m_indexed.hasNormals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexedNormals: the last indexed extraction computed none (setIndexedNormals)");
+    if (m_indexed.filtered) {
+        if (m_indexed.kept[0] == 0) return;
+        if (!normals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexedNormals");
+        if (m_indexed.accumulated) check(vh_mesh_weld_accum_components_download(m_accum.get(), nullptr, nullptr, normals, nullptr, m_indexed.kept[0], 0, m_stream), "vh_mesh_weld_accum_components_download");
+        else check(m_components->download(nullptr, nullptr, normals, nullptr, m_indexed.kept[0], 0, m_stream), "mesh components");
+        return;
+    }
     if (m_indexed.counts[0] == 0) return;
     if (!normals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexedNormals");
     if (m_indexed.accumulated) check(vh_mesh_weld_accum_download_normals(m_accum.get(), normals, m_indexed.counts[0], m_stream), "vh_mesh_weld_accum_download_normals");
@@ -560,7 +603,7 @@ void CUDAMarchingCubesHashSDF::copyTrianglesToCPU()
 {
     const unsigned int nTriangles = countTriangles(false);
     if (nTriangles == 0) return;
-    m_welded = false; // the buffer is about to hold something the weld did not make
+    clearWeldedMark(); // the buffer is about to hold something the weld did not make
     m_meshData.m_Normals.clear(); // (and the soup that joins it has no normals)
     std::vector<VhTriangle> tris(nTriangles);
     downloadTriangles(tris.data(), nTriangles);

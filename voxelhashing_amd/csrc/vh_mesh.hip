@@ -17,6 +17,7 @@
 #include "vh_device.hpp"
 #include "vh_host_util.hpp"
 #include "vh_mesh_key.hpp"
+#include "vh_mesh_components.hpp"
 #include "vh_mesh_normals.hpp"
 
 using namespace vhd;
@@ -354,6 +355,232 @@ __global__ __launch_bounds__(256) void k_mesh_normals_finish(const unsigned long
     normals[3ull * v] = nx; normals[3ull * v + 1ull] = ny; normals[3ull * v + 2ull] = nz;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Connected components of a welded mesh (vh_mesh_components, vh_mesh_components_filter; DESIGN.md section 4, "Mesh
+// components").  Vertices are ordered by (key, index); a component is named by its first vertex.  Labelling is a
+// lock-free union-find: init, hook (one lane per face), flatten (one lane per vertex), count (one lane per face).  The
+// filter then keeps the components of at least minFaces faces, or the largest one alone, and compacts vertices and
+// faces into buffers of its own.
+//
+// parent[v] is v, or a vertex before v in the order: it leaves v once, by the one compare-and-swap that succeeds on
+// it, and is afterwards only ever replaced by a proper ancestor.  So the parents never form a cycle, every chain ends
+// in the first vertex of what has been joined, and once an ancestor is always an ancestor.  A load of parent[] inside
+// the hook launch may be stale (the L2s of the XCDs are not coherent): a stale "I am a root" only makes the
+// compare-and-swap fail, which returns the real parent, and a stale parent is still an ancestor.  Nothing but the
+// results of the compare-and-swaps is relied on.
+
+VHD uint32_t comp_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+VHD void comp_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Moves c up to a vertex whose parent reads as itself, halving the path behind it: the grandparent that replaces a
+// parent is a proper ancestor, and the word it goes into has left its own vertex for good, so no compare-and-swap can
+// succeed on it any more.  false when the steps ran out.
+VHD bool comp_walk(uint32_t* parent, uint32_t& c, uint32_t& steps, uint32_t limit)
+{
+#pragma unroll 1
+    for (; steps < limit; steps++) {
+        const uint32_t p = comp_load(&parent[c]);
+        if (p == c) return true;
+        const uint32_t g = comp_load(&parent[p]);
+        if (g != p) comp_store(&parent[c], g);
+        c = g;
+    }
+    return false;
+}
+
+// Joins the components of a and b: both cursors to what reads as a root, the later of the two under the earlier.  A
+// compare-and-swap that fails returns y's real parent, and the walk goes on from there.  Every step and every failure
+// moves one of the two cursors to a vertex strictly before it, so 2 V steps are never reached; false if they are.
+// a comes back as the vertex the two ended under: a member of the joined component near its root, from which the
+// face's next union starts instead of walking up again.
+VHD bool comp_union(uint32_t* parent, const uint64_t* keys, uint32_t& a, uint32_t b, uint32_t limit)
+{
+    uint32_t x = a, y = b, steps = 0u;
+#pragma unroll 1
+    for (; steps < limit; steps++) {
+        if (!comp_walk(parent, x, steps, limit) || !comp_walk(parent, y, steps, limit)) return false;
+        a = x;
+        if (x == y) return true;
+        const uint64_t kx = keys[x], ky = keys[y];
+        if (ky < kx || (ky == kx && y < x)) { const uint32_t t = x; x = y; y = t; }
+        a = x;
+        const uint32_t old = atomicCAS(&parent[y], y, x);
+        if (old == y) return true;
+        y = old;
+    }
+    return false;
+}
+
+// the lanes' status bits into the word: one atomic per wave that has any.  Every lane of the wave calls it.
+VHD void wave_status(uint32_t status, uint32_t* statusWord)
+{
+    const uint64_t any = __ballot(status != 0u);
+    if (any == 0ull) return;
+    uint32_t bits = 0u;
+    for (uint32_t b = 1u; b <= 2u; b <<= 1) bits |= __ballot((status & b) != 0u) != 0ull ? b : 0u;
+    if ((int)lane_id() == __ffsll((unsigned long long)any) - 1) atomicOr(statusWord, bits);
+}
+
+__global__ __launch_bounds__(256) void k_components_init(uint32_t numVertices, uint32_t* parent)
+{
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < numVertices) parent[v] = v;
+}
+
+// One lane per face: an index >= numVertices is reported before anything is read through it, and the face joins nothing;
+// the others join (i0, i1) and then (where that ended, i2).
+__global__ __launch_bounds__(256) void k_components_hook(const uint64_t* keys, const uint32_t* faces, uint32_t numVertices, uint32_t numFaces,
+                                                         uint32_t* parent, uint32_t* statusWord)
+{
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t status = 0u;
+    if (f < numFaces) {
+        const uint32_t i0 = faces[3u * f], i1 = faces[3u * f + 1u], i2 = faces[3u * f + 2u];
+        if (i0 >= numVertices || i1 >= numVertices || i2 >= numVertices) status = VH_COMPONENTS_BAD_INDEX;
+        else {
+            const uint32_t limit = 2u * numVertices + 4u; // (numVertices <= 2^31 - 16: the launcher)
+            uint32_t at = i0;
+            if (!comp_union(parent, keys, at, i1, limit) || !comp_union(parent, keys, at, i2, limit)) status = VH_COMPONENTS_STEPS;
+        }
+    }
+    wave_status(status, statusWord);
+}
+
+// One lane per vertex, in a launch of its own, so that what it reads is what the hook launch left: the end of v's chain
+// over parent[v].  Lanes that pass through v meanwhile read its old parent or its root; both lead to the root.
+__global__ __launch_bounds__(256) void k_components_flatten(uint32_t numVertices, uint32_t* parent, uint32_t* statusWord)
+{
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t status = 0u;
+    if (v < numVertices) {
+        uint32_t c = v, p = comp_load(&parent[v]), steps = 0u;
+#pragma unroll 1
+        for (; p != c && steps < numVertices; steps++) { c = p; p = comp_load(&parent[c]); }
+        if (p != c) status = VH_COMPONENTS_STEPS;
+        else if (c != v) comp_store(&parent[v], c);
+    }
+    wave_status(status, statusWord);
+}
+
+// One lane per face: an in-range face counts for the root of its first index; the lanes of a wave that agree on the
+// root share one atomic.
+__global__ __launch_bounds__(256) void k_components_count(const uint32_t* faces, uint32_t numVertices, uint32_t numFaces, const uint32_t* root,
+                                                          uint32_t* faceCount)
+{
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    bool pending = false;
+    uint32_t r = 0u;
+    if (f < numFaces) {
+        const uint32_t i0 = faces[3u * f], i1 = faces[3u * f + 1u], i2 = faces[3u * f + 2u];
+        pending = i0 < numVertices && i1 < numVertices && i2 < numVertices;
+        if (pending) r = root[i0];
+    }
+#pragma unroll 1
+    for (int round = 0; round < kWave; round++) { // a round retires the leader's root: at most one per lane
+        const uint64_t m = __ballot(pending);
+        if (m == 0ull) break;
+        const int leader = __ffsll((unsigned long long)m) - 1;
+        const uint32_t lr = (uint32_t)__builtin_amdgcn_readlane((int)r, leader);
+        const uint64_t same = __ballot(pending && r == lr);
+        if ((int)lane_id() == leader) atomicAdd(&faceCount[lr], (uint32_t)__popcll(same));
+        if (r == lr) pending = false;
+    }
+}
+
+// One lane per vertex: the components with a face, the vertices without one, the largest face count (one atomic per
+// wave each).  Nothing is counted once the labelling has left a status.
+__global__ __launch_bounds__(256) void k_components_stats(uint32_t numVertices, const uint32_t* root, const uint32_t* faceCount, const uint32_t* statusWord,
+                                                          uint32_t* counts)
+{
+    if (*statusWord != 0u) return; // written by a launch before this one: uniform
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool isRoot = v < numVertices && root[v] == v;
+    const uint32_t n = isRoot ? faceCount[v] : 0u;
+    wave_count(isRoot && n != 0u, &counts[VH_COMPONENTS_WITH_FACES]);
+    wave_count(isRoot && n == 0u, &counts[VH_COMPONENTS_FACELESS]);
+    uint32_t most = n;
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) most = max(most, (uint32_t)__shfl_xor((int)most, off));
+    if (most != 0u && lane_id() == 0u) atomicMax(&counts[VH_COMPONENTS_LARGEST_FACES], most);
+}
+
+// The largest component among equals: the root first in the order.  Two launches of one lane per vertex: the smallest
+// key among the roots that reach the largest count into best[0], then the smallest index among those with that key
+// into best[1] (welded keys are distinct; the index settles hand-made input).
+__global__ __launch_bounds__(256) void k_components_pick(uint32_t numVertices, const uint64_t* keys, const uint32_t* root, const uint32_t* faceCount,
+                                                         const uint32_t* statusWord, const uint32_t* counts, unsigned long long* best, uint32_t byIndex)
+{
+    if (*statusWord != 0u) return; // (as k_components_stats)
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t most = counts[VH_COMPONENTS_LARGEST_FACES];
+    bool mine = most != 0u && v < numVertices && root[v] == v && faceCount[v] == most;
+    if (byIndex != 0u) mine = mine && keys[v] == best[0];
+    unsigned long long bid = !mine ? ~0ull : byIndex != 0u ? (unsigned long long)v : (unsigned long long)keys[v];
+    if (__ballot(mine) == 0ull) return; // wave-uniform
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        const unsigned long long other = (unsigned long long)__shfl_xor((long long)bid, off);
+        bid = other < bid ? other : bid;
+    }
+    if (lane_id() == 0u) atomicMin(&best[byIndex], bid);
+}
+
+struct ComponentFilterView {
+    const VhVertex* vertices;
+    const uint64_t* keys;
+    const float* normals;      // 3 per vertex, or null
+    const uint32_t* faces;
+    const uint32_t* root;
+    const uint32_t* faceCount;
+    const uint32_t* statusWord;
+    const unsigned long long* best;
+    uint32_t* counts;
+    uint32_t* newIndex;        // one per vertex: its index in the output, or all ones
+    VhVertex* outVertices;
+    uint64_t* outKeys;
+    float* outNormals;
+    uint32_t* outFaces;
+    uint32_t numVertices, numFaces, minFaces, largestOnly;
+};
+
+// One lane per vertex: kept when its component has minFaces faces and, with largestOnly, is the one picked.  The kept
+// ones get their new indices by a wave scan and one atomic per wave, and go into the output with key and normal.
+__global__ __launch_bounds__(256) void k_components_compact_vertices(ComponentFilterView c)
+{
+    if (*c.statusWord != 0u) return; // (as k_components_stats)
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    bool keep = false, keptRoot = false;
+    if (v < c.numVertices) {
+        const uint32_t r = c.root[v], n = c.faceCount[r];
+        keep = n >= c.minFaces && (c.largestOnly == 0u || (unsigned long long)r == c.best[1]);
+        keptRoot = keep && r == v && n != 0u;
+    }
+    const uint32_t at = wave_append(keep, &c.counts[VH_COMPONENTS_KEPT_VERTICES]);
+    wave_count(keptRoot, &c.counts[VH_COMPONENTS_KEPT]);
+    if (v >= c.numVertices) return;
+    c.newIndex[v] = keep ? at : kNoValue;
+    if (!keep) return;
+    c.outVertices[at] = c.vertices[v];
+    c.outKeys[at] = c.keys[v];
+    if (c.normals) { c.outNormals[3ull * at] = c.normals[3ull * v]; c.outNormals[3ull * at + 1ull] = c.normals[3ull * v + 1ull]; c.outNormals[3ull * at + 2ull] = c.normals[3ull * v + 2ull]; }
+}
+
+// One lane per face: kept with its first vertex (all three are of one component), renumbered, winding and rotation left alone.
+__global__ __launch_bounds__(256) void k_components_compact_faces(ComponentFilterView c)
+{
+    if (*c.statusWord != 0u) return; // (as k_components_stats)
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t a = kNoValue, b = kNoValue, d = kNoValue;
+    if (f < c.numFaces) {
+        const uint32_t i0 = c.faces[3u * f], i1 = c.faces[3u * f + 1u], i2 = c.faces[3u * f + 2u];
+        if (i0 < c.numVertices && i1 < c.numVertices && i2 < c.numVertices) { a = c.newIndex[i0]; b = c.newIndex[i1]; d = c.newIndex[i2]; }
+    }
+    const bool keep = a != kNoValue && b != kNoValue && d != kNoValue;
+    const uint32_t at = wave_append(keep, &c.counts[VH_COMPONENTS_KEPT_FACES]);
+    if (!keep) return;
+    c.outFaces[3u * at] = a; c.outFaces[3u * at + 1u] = b; c.outFaces[3u * at + 2u] = d;
+}
+
 // the smallest power of two >= 6 n (twice the 3 n keys n triangles can have), 64 slots at least
 uint32_t defaultSlotsLog2(uint32_t n)
 {
@@ -506,6 +733,61 @@ int vh_mesh_vertex_normals(const VhVertex* d_vertices, const uint64_t* d_keys, c
     return vh_last_launch_error();
 }
 
+int vh_mesh_components(const uint64_t* d_keys, const uint32_t* d_faces, uint32_t numVertices, uint32_t numFaces, uint32_t* d_root, uint32_t* d_faceCount,
+                       uint32_t* d_status, vhStream_t stream)
+{
+    if (!d_status) return VH_ERR_BAD_ARGUMENT;
+    if (numVertices != 0 && (!d_keys || !d_root || !d_faceCount)) return VH_ERR_BAD_ARGUMENT;
+    if (numFaces != 0 && !d_faces) return VH_ERR_BAD_ARGUMENT;
+    if (numVertices > 0x7ffffff0u || numFaces > 0x55555555u) return VH_ERR_BAD_ARGUMENT; // 2 V + 4 steps and 3 F face offsets in 32 bits
+    hipStream_t s = (hipStream_t)stream;
+    VH_HIP(hipMemsetAsync(d_status, 0, sizeof(uint32_t), s));
+    if (numVertices == 0) return VH_OK; // nothing to label, and no launch with an empty grid
+    VH_HIP(hipMemsetAsync(d_faceCount, 0, sizeof(uint32_t) * (size_t)numVertices, s));
+    VH_LAUNCH_TIMED(k_components_init, cdiv(numVertices, 256), 256, s, numVertices, d_root);
+    VH_TRY(vh_last_launch_error());
+    if (numFaces == 0) return VH_OK; // every vertex is its own root
+    VH_LAUNCH_TIMED(k_components_hook, cdiv(numFaces, 256), 256, s, d_keys, d_faces, numVertices, numFaces, d_root, d_status);
+    VH_TRY(vh_last_launch_error());
+    VH_LAUNCH_TIMED(k_components_flatten, cdiv(numVertices, 256), 256, s, numVertices, d_root, d_status);
+    VH_TRY(vh_last_launch_error());
+    VH_LAUNCH_TIMED(k_components_count, cdiv(numFaces, 256), 256, s, d_faces, numVertices, numFaces, d_root, d_faceCount);
+    return vh_last_launch_error();
+}
+
+int vh_mesh_components_filter(const VhVertex* d_vertices, const uint64_t* d_keys, const float* d_normals, const uint32_t* d_faces, uint32_t numVertices,
+                              uint32_t numFaces, const uint32_t* d_root, const uint32_t* d_faceCount, const uint32_t* d_status, uint32_t minFaces,
+                              uint32_t largestOnly, uint32_t* d_newIndex, uint64_t* d_best, VhVertex* d_outVertices, uint64_t* d_outKeys,
+                              float* d_outNormals, uint32_t* d_outFaces, uint32_t* d_counts, vhStream_t stream)
+{
+    if (!d_status || !d_counts || !d_best) return VH_ERR_BAD_ARGUMENT;
+    if (numVertices != 0 && (!d_vertices || !d_keys || !d_root || !d_faceCount || !d_newIndex || !d_outVertices || !d_outKeys)) return VH_ERR_BAD_ARGUMENT;
+    if (numVertices != 0 && d_normals && !d_outNormals) return VH_ERR_BAD_ARGUMENT;
+    if (numFaces != 0 && (!d_faces || !d_outFaces)) return VH_ERR_BAD_ARGUMENT;
+    if (numVertices > 0x7ffffff0u || numFaces > 0x55555555u) return VH_ERR_BAD_ARGUMENT; // (as vh_mesh_components)
+    hipStream_t s = (hipStream_t)stream;
+    VH_HIP(hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * VH_COMPONENTS_NUM_COUNTS, s));
+    if (numVertices == 0) return VH_OK; // nothing to keep, and no launch with an empty grid
+    const uint32_t grid = cdiv(numVertices, 256);
+    unsigned long long* best = reinterpret_cast<unsigned long long*>(d_best);
+    VH_LAUNCH_TIMED(k_components_stats, grid, 256, s, numVertices, d_root, d_faceCount, d_status, d_counts);
+    VH_TRY(vh_last_launch_error());
+    if (largestOnly != 0) {
+        VH_HIP(hipMemsetAsync(d_best, 0xff, sizeof(uint64_t) * 2, s));
+        VH_LAUNCH_TIMED(k_components_pick, grid, 256, s, numVertices, d_keys, d_root, d_faceCount, d_status, d_counts, best, 0u);
+        VH_TRY(vh_last_launch_error());
+        VH_LAUNCH_TIMED(k_components_pick, grid, 256, s, numVertices, d_keys, d_root, d_faceCount, d_status, d_counts, best, 1u);
+        VH_TRY(vh_last_launch_error());
+    }
+    const ComponentFilterView c = { d_vertices, d_keys, d_normals, d_faces, d_root, d_faceCount, d_status, best, d_counts, d_newIndex,
+                                    d_outVertices, d_outKeys, d_outNormals, d_outFaces, numVertices, numFaces, minFaces, largestOnly != 0 ? 1u : 0u };
+    VH_LAUNCH_TIMED(k_components_compact_vertices, grid, 256, s, c);
+    VH_TRY(vh_last_launch_error());
+    if (numFaces == 0) return VH_OK;
+    VH_LAUNCH_TIMED(k_components_compact_faces, cdiv(numFaces, 256), 256, s, c);
+    return vh_last_launch_error();
+}
+
 } // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -523,6 +805,8 @@ struct VhMeshWeldAccum {
     VhMeshNormals normals;              // vertex normals (vh_mesh_weld_accum_normals): made by the first pass
     uint32_t m_normalsVertices = 0;     // of the pass that m_normalsValid speaks of
     bool m_normalsValid = false;        // the pass has run, and no begin or append since
+    VhMeshComponents components;        // the component filter (vh_mesh_weld_accum_components): made by the first pass
+    bool m_componentsValid = false;     // the pass has run, and no begin or append since
     size_t m_soupCapacity = 0, m_vertexCapacity = 0, m_faceCapacity = 0; // in soup vertices, welded vertices, faces
     uint32_t m_slotsLog2 = 6, m_firstSlotsLog2 = 6;
     bool m_fixed = false, m_begun = false;
@@ -623,6 +907,7 @@ int vh_mesh_weld_accum_begin(VhMeshWeldAccum* accum, vhStream_t stream)
     accum->m_rehashes = 0;
     accum->m_begun = true;
     accum->m_normalsValid = false;
+    accum->m_componentsValid = false;
     return VH_OK;
 }
 
@@ -632,6 +917,7 @@ int vh_mesh_weld_accum_append(VhMeshWeldAccum* accum, const VhTriangle* d_triang
     if (!accum || !accum->m_begun) return VH_ERR_BAD_ARGUMENT;
     if (numTriangles > 0x55555555u / 2u || (numTriangles != 0 && (!d_triangles || !d_sources))) return VH_ERR_BAD_ARGUMENT;
     accum->m_normalsValid = false; // normals are of all faces with the final vertex bits: a pass before this append is stale
+    accum->m_componentsValid = false; // and a component spans appends
     if (numTriangles == 0) return VH_OK; // nothing to take, and no launch with an empty grid
     if (accum->m_appends >= VH_WELD_ACCUM_MAX_APPENDS - 1u) return VH_ERR_BAD_ARGUMENT;
     hipStream_t s = (hipStream_t)stream;
@@ -731,6 +1017,36 @@ int vh_mesh_weld_accum_download_normals(VhMeshWeldAccum* accum, float* normals, 
 {
     if (!accum || !accum->m_normalsValid || numVertices > accum->m_normalsVertices || (numVertices != 0 && !normals)) return VH_ERR_BAD_ARGUMENT;
     return accum->normals.download(normals, numVertices, true, stream);
+}
+
+int vh_mesh_weld_accum_components(VhMeshWeldAccum* accum, uint32_t minFaces, uint32_t largestOnly, vhStream_t stream)
+{
+    if (!accum || !accum->m_begun) return VH_ERR_BAD_ARGUMENT;
+    return accumGuarded([&]() -> int {
+        VhMeshWeldAccum& a = *accum;
+        a.m_componentsValid = false;
+        uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
+        VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream)); // waits for the appends; a weld that failed has no components
+        const uint32_t nv = have[VH_WELD_ACCUM_VERTICES], nf = have[VH_WELD_ACCUM_FACES];
+        // normals ride along when their pass has run over this very mesh (it leaves zeros, not garbage, behind a status)
+        const float* d_normals = a.m_normalsValid && a.m_normalsVertices == nv ? a.normals.normals.get() : nullptr;
+        VH_TRY(a.components.run(a.vertices.get(), a.keys.get(), d_normals, a.faces.get(), nv, nf, minFaces, largestOnly, stream));
+        a.m_componentsValid = true;
+        return VH_OK;
+    });
+}
+
+int vh_mesh_weld_accum_components_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream)
+{
+    if (!accum || !out || !accum->m_componentsValid) return VH_ERR_BAD_ARGUMENT;
+    return accum->components.counts(out, stream);
+}
+
+int vh_mesh_weld_accum_components_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint64_t* keys, float* normals, uint32_t* faces,
+                                           uint32_t numVertices, uint32_t numFaces, vhStream_t stream)
+{
+    if (!accum || !accum->m_componentsValid) return VH_ERR_BAD_ARGUMENT;
+    return accum->components.download(vertices, keys, normals, faces, numVertices, numFaces, stream);
 }
 
 } // extern "C"

@@ -750,6 +750,20 @@ class CUDAMarchingCubesHashSDF:
         check(self.L.vh_marching_cubes_set_indexed_normals(self.handle, 1 if on else 0), "setIndexedNormals")
         self._indexed_normals = bool(on)
 
+    def setIndexedComponentFilter(self, minFaces=0, largestOnly=False):
+        """the component filter for the indexed extractions (off by default: 0, False): after the weld and the normals
+        the mesh's connected components are labelled on the device and those of fewer than minFaces faces dropped, with
+        largestOnly all but the largest; indexed_counts(), indexed(), mesh() and saveMesh then describe the filtered
+        mesh, and indexed_component_stats() says what the unfiltered one held"""
+        check(self.L.vh_marching_cubes_set_indexed_component_filter(self.handle, int(minFaces), 1 if largestOnly else 0), "setIndexedComponentFilter")
+
+    def indexed_component_stats(self):
+        """of the last indexed extraction: components (with a face), faceless_vertices, kept_components, kept_vertices,
+        kept_faces, largest_faces; all 0 when it ran with the filter off"""
+        out = (C.c_uint32 * 6)()
+        check(self.L.vh_marching_cubes_get_indexed_component_stats(self.handle, out), "get_indexed_component_stats")
+        return {k: int(out[i]) for i, k in enumerate(T.COMPONENTS_COUNTS)}
+
     def extractIsoSurface(self, hashData, hashParams, minCorner=(0, 0, 0), maxCorner=(0, 0, 0), boxEnabled=False, copy=True):
         check(self.L.vh_marching_cubes_extract_iso_surface(self.handle, C.byref(hashData), C.byref(hashParams), f16(minCorner),
                                                            f16(maxCorner), int(boxEnabled), int(copy)), "extractIsoSurface")
@@ -951,6 +965,85 @@ def mesh_vertex_normals(vertices, keys, faces, scale_log2, raise_on_status=True,
     return dict(normals=normals, acc=acc, status=status, code=code)
 
 
+def _vertex_records(vertices, colors=None):
+    """(V,3) positions with (V,3) colours or none, or T.VERTEX_DTYPE records -> contiguous records"""
+    v = np.asarray(vertices)
+    if v.dtype != T.VERTEX_DTYPE:
+        p = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3)
+        v = np.zeros(len(p), dtype=T.VERTEX_DTYPE)
+        v["p"] = p
+        if colors is not None:
+            v["c"] = np.ascontiguousarray(colors, dtype=np.float32).reshape(len(p), 3)
+    return np.ascontiguousarray(v).ravel()
+
+
+def mesh_components(keys, faces, stream=None, guard=0):
+    """vh_mesh_components on hand-made input: keys (V,) u64, faces (F,3) u32 -> root (V,) u32 (the index of each
+    vertex's component's first vertex by (key, index)), face_count (V,) u32 (at the roots), status, code (4 =
+    VH_ERR_BAD_ARGUMENT for either status bit).  guard: the last `guard` keys are not vertices but room behind them, with
+    that many words of 0xa5a5a5a5 behind root and face_count on the device, returned as root_guard / count_guard."""
+    L = load()
+    k = np.ascontiguousarray(keys, dtype=np.uint64).ravel()
+    f = np.ascontiguousarray(faces, dtype=np.uint32).reshape(-1, 3)
+    nv, nf = len(k) - guard, len(f)
+    fill = np.full(nv + guard, 0xa5a5a5a5, dtype=np.uint32)
+    bufs = [DeviceBuffer.from_numpy(k, stream), DeviceBuffer.from_numpy(f, stream), DeviceBuffer.from_numpy(fill, stream), DeviceBuffer.from_numpy(fill, stream),
+            DeviceBuffer(4)]
+    try:
+        d_k, d_f, d_root, d_cnt, d_st = bufs
+        check(L.vh_mesh_components(d_k.ptr, d_f.ptr, nv, nf, d_root.ptr, d_cnt.ptr, d_st.ptr, stream), "vh_mesh_components")
+        status = int(d_st.download(np.uint32, 1, stream)[0])
+        root = d_root.download(np.uint32, nv + guard, stream)
+        cnt = d_cnt.download(np.uint32, nv + guard, stream)
+    finally:
+        for b in bufs:
+            b.free()
+    return dict(root=root[:nv], face_count=cnt[:nv], root_guard=root[nv:], count_guard=cnt[nv:], status=status, code=4 if status else 0)
+
+
+def mesh_components_filter(vertices, colors, keys, faces, min_faces=0, largest_only=False, normals=None, raise_on_status=True, stream=None):
+    """vh_mesh_components, then vh_mesh_components_filter, on hand-made input: vertices (V,3) f32 with colors (V,3) f32
+    or None, or T.VERTEX_DTYPE records; keys (V,) u64; faces (F,3) u32; normals (V,3) f32 or None -> the filtered
+    vertices, colors, keys, faces (and normals) as mesh_weld(), root and face_count of the labelling, counts (the six by
+    name), status, code.  A status raises VhError (VH_ERR_BAD_ARGUMENT), or with raise_on_status=False comes back as
+    `code` beside an empty mesh."""
+    L = load()
+    v = _vertex_records(vertices, colors)
+    k = np.ascontiguousarray(keys, dtype=np.uint64).ravel()
+    f = np.ascontiguousarray(faces, dtype=np.uint32).reshape(-1, 3)
+    if len(k) != len(v):
+        raise ValueError("one key per vertex")
+    nv, nf = len(v), len(f)
+    n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(nv, 3)
+    bufs = [DeviceBuffer.from_numpy(v, stream), DeviceBuffer.from_numpy(k, stream), DeviceBuffer.from_numpy(f, stream),
+            DeviceBuffer(4 * nv), DeviceBuffer(4 * nv), DeviceBuffer(4), DeviceBuffer(4 * nv), DeviceBuffer(16),
+            DeviceBuffer(24 * nv), DeviceBuffer(8 * nv), DeviceBuffer(12 * nf), DeviceBuffer(24)]
+    if n is not None:
+        bufs += [DeviceBuffer.from_numpy(n, stream), DeviceBuffer(12 * nv)]
+    try:
+        d_v, d_k, d_f, d_root, d_cnt, d_st, d_new, d_best, d_ov, d_ok, d_of, d_counts = bufs[:12]
+        d_n, d_on = (bufs[12].ptr, bufs[13].ptr) if n is not None else (None, None)
+        check(L.vh_mesh_components(d_k.ptr, d_f.ptr, nv, nf, d_root.ptr, d_cnt.ptr, d_st.ptr, stream), "vh_mesh_components")
+        check(L.vh_mesh_components_filter(d_v.ptr, d_k.ptr, d_n, d_f.ptr, nv, nf, d_root.ptr, d_cnt.ptr, d_st.ptr, int(min_faces), 1 if largest_only else 0,
+                                          d_new.ptr, d_best.ptr, d_ov.ptr, d_ok.ptr, d_on, d_of.ptr, d_counts.ptr, stream), "vh_mesh_components_filter")
+        status = int(d_st.download(np.uint32, 1, stream)[0])
+        counts = d_counts.download(np.uint32, 6, stream)
+        kv, kf = int(counts[3]), int(counts[4])
+        ov = d_ov.download(T.VERTEX_DTYPE, kv, stream)
+        out = dict(vertices=np.ascontiguousarray(ov["p"]), colors=np.ascontiguousarray(ov["c"]), keys=d_ok.download(np.uint64, kv, stream),
+                   faces=d_of.download(np.uint32, 3 * kf, stream).reshape(-1, 3),
+                   root=d_root.download(np.uint32, nv, stream), face_count=d_cnt.download(np.uint32, nv, stream))
+        if n is not None:
+            out["normals"] = bufs[13].download(np.float32, 3 * kv, stream).reshape(-1, 3)
+    finally:
+        for b in bufs:
+            b.free()
+    code = 4 if status else 0  # VH_ERR_BAD_ARGUMENT for either bit, as for the normals
+    if code and raise_on_status:
+        check(code, f"vh_mesh_components (status {status})")
+    return dict(out, counts={name: int(counts[i]) for i, name in enumerate(T.COMPONENTS_COUNTS)}, status=status, code=code)
+
+
 def mesh_save_ply(filename, vertices, colors=None, normals=None, faces=None, transform=None):
     """vh_mesh_save_ply (host side, no GPU): the mesh container's applyTransform (when a transform is given) and
     saveToPLY on numpy arrays: vertices (V,3), colors (V,4) or None, normals (V,3) or None, faces (F,3) or None"""
@@ -963,13 +1056,18 @@ def mesh_save_ply(filename, vertices, colors=None, normals=None, faces=None, tra
                                   str(filename).encode()), "vh_mesh_save_ply")
 
 
-def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, raise_on_status=True, stream=None, normals_scale_log2=None):
+def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, raise_on_status=True, stream=None, normals_scale_log2=None,
+                      min_component_faces=0, largest_component=False, append_after_components=None):
     """vh_mesh_weld_accum_* on hand-made input: parts is a sequence of (soup, records), appended in order to one
     accumulation -> vertices, colors, keys, faces as mesh_weld(), counts (vertices, faces), stats (the six counts by
     name), status and code.  slots_log2 is the table's FIRST size (0: the smallest), reserve_triangles that of the
     vertex and face arrays; fixed keeps the table from growing.  Errors as mesh_weld().
     normals_scale_log2: run the vertex-normal pass over the finished accumulation -> also normals (V,3) f32 and
-    normals_code (what the download returned: 4 when the pass left a status)."""
+    normals_code (what the download returned: 4 when the pass left a status).
+    min_component_faces, largest_component: run the component filter over the finished accumulation (after the normals,
+    which then ride along) -> also `filtered` (vertices, colors, keys, faces, normals if any) and component_counts (the
+    six by name); the unfiltered mesh comes back as without.  append_after_components: one more (soup, records) appended
+    after the pass -> stale_code, what the filter's download then returns (4: refused)."""
     L = load()
     h = C.c_void_p()
     check(L.vh_mesh_weld_accum_create(slots_log2, reserve_triangles, int(fixed), C.byref(h)), "vh_mesh_weld_accum_create")
@@ -993,6 +1091,22 @@ def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, rai
             if ncode < 0 or (ncode != 0 and raise_on_status):
                 check(ncode, "vh_mesh_weld_accum_download_normals")
             extra = dict(normals=nrm, normals_code=int(ncode))
+        if (min_component_faces or largest_component) and counts[2] == 0:
+            check(L.vh_mesh_weld_accum_components(h, int(min_component_faces), 1 if largest_component else 0, stream), "vh_mesh_weld_accum_components")
+            cc = (C.c_uint32 * 6)()
+            check(L.vh_mesh_weld_accum_components_get_counts(h, cc, stream), "vh_mesh_weld_accum_components_get_counts")
+            with_n = "normals" in extra and extra["normals_code"] == 0
+            fn = np.zeros((int(cc[3]), 3), dtype=np.float32)
+            filtered = _welded_arrays(cc[3], cc[4], "vh_mesh_weld_accum_components_download",
+                                      lambda v, k, f, nv, nf: L.vh_mesh_weld_accum_components_download(h, v, k, fn.ctypes.data if with_n else None, f, nv, nf, stream))
+            if with_n:
+                filtered["normals"] = fn
+            extra.update(filtered=filtered, component_counts={name: int(cc[i]) for i, name in enumerate(T.COMPONENTS_COUNTS)})
+            if append_after_components is not None:
+                d_tris, d_srcs, n = _upload_soup(*append_after_components, stream)
+                buffers += [d_tris, d_srcs]
+                check(L.vh_mesh_weld_accum_append(h, d_tris.ptr, d_srcs.ptr, n, stream), "vh_mesh_weld_accum_append")
+                extra["stale_code"] = int(L.vh_mesh_weld_accum_components_download(h, None, None, None, None, 0, 0, stream))
     finally:
         L.vh_mesh_weld_accum_destroy(h)
         for b in buffers:

@@ -243,6 +243,13 @@ PROTOTYPES = {
     "vh_mesh_save_ply": (C.c_int, [_VP, _VP, _VP, C.c_uint64, _VP, C.c_uint64, P(C.c_float), C.c_char_p]),
     "vh_mesh_weld_accum_normals": (C.c_int, [_VP, C.c_int32, _VP]),
     "vh_mesh_weld_accum_download_normals": (C.c_int, [_VP, _VP, C.c_uint32, _VP]),
+    "vh_mesh_components": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP]),
+    "vh_mesh_components_filter": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "vh_mesh_weld_accum_components": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP]),
+    "vh_mesh_weld_accum_components_get_counts": (C.c_int, [_VP, P(C.c_uint32), _VP]),
+    "vh_mesh_weld_accum_components_download": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP]),
+    "vh_marching_cubes_set_indexed_component_filter": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
+    "vh_marching_cubes_get_indexed_component_stats": (C.c_int, [_VP, P(C.c_uint32)]),
     "vh_marching_cubes_set_indexed_normals": (C.c_int, [_VP, C.c_int]),
     "vh_marching_cubes_download_indexed_normals": (C.c_int, [_VP, _VP]),
     "vh_marching_cubes_get_mesh_normals_size": (C.c_int, [_VP, P(C.c_uint64)]),

@@ -144,6 +144,9 @@ class TriangleSource(C.Structure):
 TRIANGLE_SOURCE_DTYPE = np.dtype([("cell", np.int32, 3), ("edges", np.uint32)])
 WELD_TABLE_FULL, WELD_KEY_RANGE = 1, 2  # bits of the weld's status word
 NORMALS_RANGE, NORMALS_BAD_INDEX = 1, 2  # bits of the vertex-normal pass's status word (VH_NORMALS_*)
+COMPONENTS_BAD_INDEX, COMPONENTS_STEPS = 1, 2  # bits of the component labelling's status word (VH_COMPONENTS_*)
+# VH_COMPONENTS_*: what the component filter counts
+COMPONENTS_COUNTS = ("components", "faceless_vertices", "kept_components", "kept_vertices", "kept_faces", "largest_faces")
 WELD_ACCUM_COUNTS = ("vertices", "faces", "status", "cells", "dropped", "rehashes")  # VH_WELD_ACCUM_*: what the accumulating weld reports
 WELD_ACCUM_MAX_APPENDS = 1 << 28
 
