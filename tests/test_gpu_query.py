@@ -170,26 +170,63 @@ def test_camera_rays_match_the_restatement(world):
                 "without a normal array", normals=False)
 
 
-def test_camera_rays_match_the_device_render(world, E):
-    """the identities of tests/test_query_reference.py against the device's own maps (full-range march and tile tables)"""
-    w = world
-    cam, rp = w["cam"], w["rp"]
-    got = query_rays(w["hd"], w["hp"], rp, cam["origins"], cam["directions"], cam["t_min"], cam["t_max"])
-    n = rp.m_width * rp.m_height
+def maps_of_rays(got, cam, rp):
+    """what the render's maps hold for query results `got` of the view's camera rays (the identities of
+    tests/test_query_reference.py) -> (hit [n], depth [n], rgb [n, 3], camera-space normals of the hits)"""
     hit = got["status"] == RQ.HIT
     with np.errstate(all="ignore"):
         depth = got["t"] / cam["depth_to_ray_length"]
     rgb = np.stack([got["color"] & 0xff, (got["color"] >> 8) & 0xff, (got["color"] >> 16) & 0xff], axis=-1).astype(f32) / f32(255)
     normals = np.stack([RQ.mat_mul_d(rp.m_viewMatrix, v) for v in got["normal"][hit]])
+    return hit, depth, rgb, normals
+
+
+def assert_maps_match_rays(maps, want, n, what):
+    hit, depth, rgb, normals = want
+    assert np.array_equal(hit, maps["depth"].reshape(n) != -np.inf), f"{what}: a miss is a miss"
+    assert np.array_equal(bits(depth[hit]), bits(maps["depth"].reshape(n)[hit])), f"{what}: depth bits"
+    assert np.array_equal(bits(rgb[hit]), bits(maps["colors"].reshape(n, 4)[hit, :3])), f"{what}: colour bits"
+    assert np.array_equal(bits(normals), bits(maps["normals"].reshape(n, 4)[hit, :3])), f"{what}: normal bits"
+
+
+def test_camera_rays_match_the_device_render(world, E):
+    """the identities of tests/test_query_reference.py against the device's own maps (full-range march and tile tables)"""
+    w = world
+    cam, rp = w["cam"], w["rp"]
+    got = query_rays(w["hd"], w["hp"], rp, cam["origins"], cam["directions"], cam["t_min"], cam["t_max"])
+    want = maps_of_rays(got, cam, rp)
     for intervals in (False, True):
         ray = E.CUDARayCastSDF(rp)
         ray.setIntervalSplatting(intervals)
         ray.render(w["hd"], w["hp"], w["cp"], w["view"])
-        maps = ray.download()
-        assert np.array_equal(hit, maps["depth"].reshape(n) != -np.inf), "a miss is a miss"
-        assert np.array_equal(bits(depth[hit]), bits(maps["depth"].reshape(n)[hit]))
-        assert np.array_equal(bits(rgb[hit]), bits(maps["colors"].reshape(n, 4)[hit, :3]))
-        assert np.array_equal(bits(normals), bits(maps["normals"].reshape(n, 4)[hit, :3]))
+        assert_maps_match_rays(ray.download(), want, rp.m_width * rp.m_height, f"intervals={intervals}")
+
+
+def test_rejected_sign_changes_resume_the_march(world, E, vh):
+    """Both acceptance thresholds tightened to the scale of one ray increment (the defaults, 50.5 and 50 increments,
+    accept practically every sign change): a sample pair further apart than one increment (rays that meet the surface
+    head-on) or a sample deeper than half an increment behind the surface is rejected, the march sample becomes the last
+    sample and the march goes on.  The query and the three marches of the render must all do so as the restatement does."""
+    import tile_intervals as TI
+    from test_gpu_render_lookups import render_hash, render_intervals
+    w = world
+    cam, host = w["cam"], w["host"]
+    rp = type(w["rp"]).from_buffer_copy(w["rp"])
+    inc = f32(rp.m_rayIncrement)
+    rp.m_thresSampleDist, rp.m_thresDist = float(inc), float(f32(0.5) * inc)
+    want = RQ.rays(host.L, host.hd, host.hp, rp, cam["origins"], cam["directions"], cam["t_min"], cam["t_max"])
+    moved = (want["status"] != w["ref"]["status"]) | (bits(want["t"]) != bits(w["ref"]["t"]))
+    n_moved, n_hit = int(moved.sum()), int((want["status"] == RQ.HIT).sum())
+    print(f"\ntightened thresholds: {n_moved} rays changed status or t, {n_hit} still hit")
+    assert n_moved >= 100 and n_hit >= 100
+    got = query_rays(w["hd"], w["hp"], rp, cam["origins"], cam["directions"], cam["t_min"], cam["t_max"])
+    assert_rays(got, want, "tightened thresholds")
+    maps = maps_of_rays(got, cam, rp)
+    W, H = rp.m_width, rp.m_height
+    ray = E.CUDARayCastSDF(rp)
+    assert_maps_match_rays(render_hash(vh, lib, ray, w["hd"], w["hp"], w["cp"], rp, W, H), maps, W * H, "hash-table render")
+    for cap, what in ((TI.CAP_SMALL, "small tables"), (TI.CAP_LARGE, "large tables (pipelined march)")):
+        assert_maps_match_rays(render_intervals(vh, lib, ray, w["hd"], w["hp"], w["cp"], rp, W, H, cap)[0], maps, W * H, what)
 
 
 def test_rays_with_differing_sample_phases(world):

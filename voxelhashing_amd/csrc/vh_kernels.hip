@@ -1931,11 +1931,9 @@ VHD F3 gradient_for_point(const VhHashData& hd, const VhHashParams& hp, F3 pos)
 // Tap voxel coordinates of the sample at ray parameter t.
 // Division-free when possible: q ~ pos/voxel is evaluated approximately (one fma per axis).  The lower tap
 // of an axis is round_half_away((pos - voxel/2)/voxel) = floor(pos/voxel) and the upper tap is that + 1
-// whenever pos/voxel is not within rounding distance of an integer.  With u = 2^-24 and Q a bound on
-// |pos/voxel| along the ray, the approximate q is off by <= 3uQ and the reference's own quotient (two
-// products, two sums, a division and the +-0.5) by <= 5uQ; a fractional part at least 32uQ away from 0
-// and 1 therefore settles both taps.  Anything closer takes the exact path with the reference's
-// arithmetic.  The decision is made per WAVE-iteration in practice (one uncertain lane sends the whole
+// whenever pos/voxel is not within rounding distance of an integer: a fractional part further than the ray's
+// margin (ray_setup, below) from 0 and 1 settles both taps.  Anything closer takes the exact path with the
+// reference's arithmetic.  The decision is made per WAVE-iteration in practice (one uncertain lane sends the whole
 // wave through the exact code), hence the tight margin: ~0.3 % per lane at Q = 256.
 struct RayQ {
     F3 cam, dir;   // exact ray (world)
@@ -1962,6 +1960,64 @@ VHD void tap_coords(const RayQ& rq, float t, Taps& tp)
         tp.bxa = vvp_to_block1(tp.x0); tp.bya = vvp_to_block1(tp.y0); tp.bza = vvp_to_block1(tp.z0);
         tp.bxb = vvp_to_block1(tp.x1); tp.byb = vvp_to_block1(tp.y1); tp.bzb = vvp_to_block1(tp.z1);
     }
+}
+
+// The constants of the ray cam + t dir, for samples at parameters |t| <= tFar (the caller's bound: march and bisection
+// parameters lie inside the marched range).
+VHD RayQ ray_setup(F3 cam, F3 dir, float voxel, float tFar)
+{
+    RayQ rq;
+    rq.cam = cam; rq.dir = dir;
+    rq.vs = voxel;
+    rq.rvs = 1.0f / rq.vs; // IEEE reciprocal for div_exact
+    rq.halfVoxel = rq.vs / 2.0f;
+    rq.camq = mk3(cam.x * rq.rvs, cam.y * rq.rvs, cam.z * rq.rvs);
+    rq.dirq = mk3(dir.x * rq.rvs, dir.y * rq.rvs, dir.z * rq.rvs);
+    // Q bounds |pos/voxel| for every sample of this ray
+    const float Q = 1.0f + (fabsf(rq.camq.x) + fabsf(rq.camq.y) + fabsf(rq.camq.z)) +
+                    tFar * (fabsf(rq.dirq.x) + fabsf(rq.dirq.y) + fabsf(rq.dirq.z));
+    // Margin: 16 u Q with u = 2^-24.  Per axis, with S = (|cam| + t |dir|) / voxel <= Q - 1: the fused route
+    // q = fma(t, dir * r, cam * r), r = fl(1 / voxel), is within 3 u S of the real (cam + t dir) / voxel (r, the
+    // two scaled operands, the fma); the reference's route -- fl(t dir), + cam, - half, / voxel, +- 0.5, and for
+    // the upper tap + voxel before the division -- within u (6 S + 5.5) of the same number.  Both take the floor:
+    // they agree when q is further than u (9 S + 5.5) < 16 u Q from an integer.
+    const float margin = Q * (16.0f / 16777216.0f);
+    rq.certLim = (Q < 65536.0f) ? 0.5f - margin : -1.0f; // NaN/inf Q compare false: exact path
+    return rq;
+}
+
+// findIntersectionBisection :149-170 on [lastAlpha, t] -- the last valid sample (lastAlpha, lastSdf) and the march sample
+// (t, dist) -- and the acceptance of its result (:227-229, the two thresholds).  `color` is the last bisection sample's.
+// By value, `success = false; break;` kept: with reference outputs and an early return k_render_large<true, *> loses a wave per SIMD.
+// (a -DVH_RENDER_STATS build counts the plain march only, which has this text in place)
+struct Bisected {
+    float alpha;
+    uint32_t color;
+    bool accepted;
+};
+template <class LK>
+VHD Bisected bisect(LK& lk, const VhHashData& hd, const RayQ& rq, float lastAlpha, float lastSdf, float t, float dist,
+                    float thresSampleDist, float thresDist, uint32_t& cost)
+{
+    float a = lastAlpha, aDist = lastSdf, b = t, bDist = dist, c = 0.0f;
+    uint32_t color = 0u;
+    bool success = true;
+#pragma unroll 1
+    for (int i = 0; i < 3; i++) {
+        cost += kCostSample;
+        c = a + (aDist / (aDist - bDist)) * (b - a); // findIntersectionLinear :140-143
+        Taps ctp;
+        tap_coords(rq, c, ctp);
+        float cDist = 0.0f;
+        if (!trilinear<true>(hd, rq.vs, lk, kPtrUnknown, ctp, mk3(rq.cam.x + c * rq.dir.x, rq.cam.y + c * rq.dir.y, rq.cam.z + c * rq.dir.z), rq.rvs, cDist, color)) { success = false; break; }
+        if (aDist * cDist > 0.0f) { a = c; aDist = cDist; }
+        else { b = c; bDist = cDist; }
+    }
+    Bisected r;
+    r.alpha = c;
+    r.color = color;
+    r.accepted = success && fabsf(lastSdf - dist) < thresSampleDist && fabsf(dist) < thresDist;
+    return r;
 }
 
 #ifndef VH_PIPELINE_SMALL // (measurement builds: the pipelined march with the small tables too)
@@ -2000,25 +2056,7 @@ VHD void march_ray(LK& lk, const VhHashData& hd, const VhHashParams& hp, const V
     out.depthToRayLength = depthToRayLength;
     const float rayEnd = depthToRayLength * fminf(rp.m_maxDepth, maxInterval);
     const float inc = rp.m_rayIncrement;
-    RayQ rq;
-    rq.cam = worldCamPos; rq.dir = worldDir;
-    rq.vs = hp.m_virtualVoxelSize;
-    rq.rvs = 1.0f / rq.vs; // IEEE reciprocal for div_exact
-    rq.halfVoxel = rq.vs / 2.0f;
-    rq.camq = mk3(worldCamPos.x * rq.rvs, worldCamPos.y * rq.rvs, worldCamPos.z * rq.rvs);
-    rq.dirq = mk3(worldDir.x * rq.rvs, worldDir.y * rq.rvs, worldDir.z * rq.rvs);
-    {
-        // Q bounds |pos/voxel| for every sample of this ray (march and bisection parameters are <= rayEnd)
-        const float Q = 1.0f + (fabsf(rq.camq.x) + fabsf(rq.camq.y) + fabsf(rq.camq.z)) +
-                        fabsf(rayEnd) * (fabsf(rq.dirq.x) + fabsf(rq.dirq.y) + fabsf(rq.dirq.z));
-        // Margin: 16 u Q with u = 2^-24.  Per axis, with S = (|cam| + t |dir|) / voxel <= Q - 1: the fused route
-        // q = fma(t, dir * r, cam * r), r = fl(1 / voxel), is within 3 u S of the real (cam + t dir) / voxel (r, the
-        // two scaled operands, the fma); the reference's route -- fl(t dir), + cam, - half, / voxel, +- 0.5, and for
-        // the upper tap + voxel before the division -- within u (6 S + 5.5) of the same number.  Both take the floor:
-        // they agree when q is further than u (9 S + 5.5) < 16 u Q from an integer.
-        const float margin = Q * (16.0f / 16777216.0f);
-        rq.certLim = (Q < 65536.0f) ? 0.5f - margin : -1.0f; // NaN/inf Q compare false: exact path
-    }
+    const RayQ rq = ray_setup(worldCamPos, worldDir, hp.m_virtualVoxelSize, fabsf(rayEnd)); // (march and bisection parameters are <= rayEnd)
 
     float rcur = depthToRayLength * fmaxf(rp.m_minDepth, minInterval); // rayCurrent
     float lastSdf = 0.0f, lastAlpha = 0.0f;
@@ -2102,28 +2140,13 @@ VHD void march_ray(LK& lk, const VhHashData& hd, const VhHashParams& hp, const V
                 P = N;
             }
             if (!candidate) break;
-            // ---- findIntersectionBisection :149-170 on [lastAlpha, rcur] (as below)
-            float a = lastAlpha, aDist = lastSdf, b = rcur, bDist = dist, c = 0.0f;
-            uint32_t color2 = 0u;
-            bool success = true;
-#pragma unroll 1
-            for (int i = 0; i < 3; i++) {
-                cost += kCostSample;
-                c = a + (aDist / (aDist - bDist)) * (b - a); // findIntersectionLinear :140-143
-                Taps ctp;
-                tap_coords(rq, c, ctp);
-                const F3 cpos = mk3(worldCamPos.x + c * worldDir.x, worldCamPos.y + c * worldDir.y, worldCamPos.z + c * worldDir.z);
-                float cDist = 0.0f;
-                if (!trilinear<true>(hd, rq.vs, lk, kPtrUnknown, ctp, cpos, rq.rvs, cDist, color2)) { success = false; break; }
-                if (aDist * cDist > 0.0f) { a = c; aDist = cDist; }
-                else { b = c; bDist = cDist; }
-            }
-            if (success && fabsf(lastSdf - dist) < rp.m_thresSampleDist && fabsf(dist) < rp.m_thresDist) {
+            const Bisected bs = bisect(lk, hd, rq, lastAlpha, lastSdf, rcur, dist, rp.m_thresSampleDist, rp.m_thresDist, cost);
+            if (bs.accepted) {
                 out.hit = true;
-                out.alpha = c;
-                out.color = color2;
+                out.alpha = bs.alpha;
+                out.color = bs.color;
                 if (GRADIENTS) {
-                    const F3 iso = mk3(worldCamPos.x + c * worldDir.x, worldCamPos.y + c * worldDir.y, worldCamPos.z + c * worldDir.z);
+                    const F3 iso = mk3(worldCamPos.x + bs.alpha * worldDir.x, worldCamPos.y + bs.alpha * worldDir.y, worldCamPos.z + bs.alpha * worldDir.z);
                     const F3 g = gradient_for_point(hd, hp, iso);
                     out.normal = mat_mul_d(rp.m_viewMatrix, mk3(-g.x, -g.y, -g.z));
                 }
@@ -2192,7 +2215,8 @@ VHD void march_ray(LK& lk, const VhHashData& hd, const VhHashParams& hp, const V
         }
         if (!candidate) break;
 
-        // ---- findIntersectionBisection :149-170 on [lastAlpha, rcur]
+        // ---- findIntersectionBisection :149-170 on [lastAlpha, rcur]: bisect()'s text, in place.  Called as bisect() it gives
+        // k_render<false, true> fewer instructions and no scratch, and the cfg2 frame 1.7 % less (profiles/README.md)
         float a = lastAlpha, aDist = lastSdf, b = rcur, bDist = dist, c = 0.0f;
         uint32_t color2 = 0u;
         bool success = true;
@@ -2348,9 +2372,10 @@ __global__ __launch_bounds__(256) void k_query_points(VhHashData hd, VhHashParam
 #endif
 
 // traverseCoarseGridSimpleSampleAll, DSC/RayCastSDFUtil.h:198-262, for rays given in world space: worldCamPos = origin,
-// worldDir = direction (as given), rayCurrent = tMin, rayEnd = tMax.  The march of march_ray without its tile interval,
-// its cost accounting and its camera: the same samples, sign-change test, bisection and thresholds, written as
-// march-until-sign-change / bisect / resume.  Lanes of a wave finish at different times (a wave lasts as long as its
+// worldDir = direction (as given), rayCurrent = tMin, rayEnd = tMax.  The plain march of march_ray without its tile
+// interval, its cost accounting and its camera.  Shared with it: ray_setup, tap_coords, trilinear and bisect (with the
+// thresholds; its cost counter is thrown away here).  Restated here: the march loop with its limits (tMax and the sample
+// count), the sign-change test and the carry of the last sample.  Lanes of a wave finish at different times (a wave lasts as long as its
 // longest ray): rays in a coherent order -- neighbours in space next to each other -- are the caller's gain.
 // The march counts its samples and stops at VH_QUERY_MAX_SAMPLES, so no caller data can spin a wave (t + inc == t).
 __global__ __launch_bounds__(256) VH_QUERY_RAYS_OCCUPANCY void k_query_rays(VhHashData hd, VhHashParams hp, float inc, float thresSampleDist, float thresDist,
@@ -2375,27 +2400,14 @@ __global__ __launch_bounds__(256) VH_QUERY_RAYS_OCCUPANCY void k_query_rays(VhHa
     if (refused) {
         st = 2u;
     } else {
-        RayQ rq;
-        rq.cam = cam; rq.dir = dir;
-        rq.vs = hp.m_virtualVoxelSize;
-        rq.rvs = 1.0f / rq.vs; // IEEE reciprocal for div_exact
-        rq.halfVoxel = rq.vs / 2.0f;
-        rq.camq = mk3(cam.x * rq.rvs, cam.y * rq.rvs, cam.z * rq.rvs);
-        rq.dirq = mk3(dir.x * rq.rvs, dir.y * rq.rvs, dir.z * rq.rvs);
-        {
-            // Q bounds |pos/voxel| for every sample of this ray: march and bisection parameters lie in [tMin, tMax)
-            // (march_ray has the error analysis of the margin)
-            const float Q = 1.0f + (fabsf(rq.camq.x) + fabsf(rq.camq.y) + fabsf(rq.camq.z)) +
-                            fmaxf(fabsf(t0), fabsf(rayEnd)) * (fabsf(rq.dirq.x) + fabsf(rq.dirq.y) + fabsf(rq.dirq.z));
-            const float margin = Q * (16.0f / 16777216.0f);
-            rq.certLim = (Q < 65536.0f) ? 0.5f - margin : -1.0f; // NaN/inf Q compare false: exact path
-        }
+        const RayQ rq = ray_setup(cam, dir, hp.m_virtualVoxelSize, fmaxf(fabsf(t0), fabsf(rayEnd))); // (parameters lie in [tMin, tMax))
         HashLookup lk{ hd, hp, hm, {} };
         cache_init(lk.bc);
         float rcur = t0;
         float lastSdf = 0.0f, lastAlpha = 0.0f;
         int lastValid = 0;
         uint32_t samples = 0u;
+        uint32_t cost = 0u; // (bisect's accounting, thrown away here)
 #pragma unroll 1
         for (;;) {
             // ---- march until a sign change, the end of the range or the sample cap
@@ -2429,27 +2441,13 @@ __global__ __launch_bounds__(256) VH_QUERY_RAYS_OCCUPANCY void k_query_rays(VhHa
             }
             if (!candidate) break;
 
-            // ---- findIntersectionBisection :149-170 on [lastAlpha, rcur]
-            float a = lastAlpha, aDist = lastSdf, b = rcur, bDist = dist, c = 0.0f;
-            uint32_t color2 = 0u;
-            bool success = true;
-#pragma unroll 1
-            for (int k = 0; k < 3; k++) {
-                c = a + (aDist / (aDist - bDist)) * (b - a); // findIntersectionLinear :140-143
-                Taps ctp;
-                tap_coords(rq, c, ctp);
-                const F3 cpos = mk3(cam.x + c * dir.x, cam.y + c * dir.y, cam.z + c * dir.z);
-                float cDist = 0.0f;
-                if (!trilinear<true>(hd, rq.vs, lk, kPtrUnknown, ctp, cpos, rq.rvs, cDist, color2)) { success = false; break; }
-                if (aDist * cDist > 0.0f) { a = c; aDist = cDist; }
-                else { b = c; bDist = cDist; }
-            }
-            if (success && fabsf(lastSdf - dist) < thresSampleDist && fabsf(dist) < thresDist) {
+            const Bisected bs = bisect(lk, hd, rq, lastAlpha, lastSdf, rcur, dist, thresSampleDist, thresDist, cost);
+            if (bs.accepted) {
                 st = 1u;
-                alpha = c;
-                col = color2;
+                alpha = bs.alpha;
+                col = bs.color;
                 if (normals) { // always from the gradient: there is no depth map to difference
-                    const F3 g = gradient_for_point(hd, hp, mk3(cam.x + c * dir.x, cam.y + c * dir.y, cam.z + c * dir.z));
+                    const F3 g = gradient_for_point(hd, hp, mk3(cam.x + bs.alpha * dir.x, cam.y + bs.alpha * dir.y, cam.z + bs.alpha * dir.z));
                     nrm = mk3(-g.x, -g.y, -g.z);
                 }
                 break;
