@@ -646,6 +646,8 @@ VHD uint64_t lanemask_lt() { return (1ull << lane_id()) - 1ull; }
 
 // workgroups of b that cover a (host side: the launchers' grid sizes)
 inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+// the 8x8-pixel tiles of an image: a wave each in alloc, the interval splat's heads and lists, the tile ray caster
+inline uint32_t image_tiles(uint32_t width, uint32_t height) { return cdiv(width, 8) * cdiv(height, 8); }
 
 VHD float4 f4_scale(float a, float4 v) { return make_float4(a * v.x, a * v.y, a * v.z, a * v.w); }
 VHD float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }

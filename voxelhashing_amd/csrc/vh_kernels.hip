@@ -1,10 +1,15 @@
 // vh_kernels.hip -- the frame loop's kernels: reset, alloc, compactify, integrate, garbage collection, the interval
 // splat, the ray caster, the queries and normals, with their launcher-level C ABI (include/vh_api.h).  They are one
 // translation unit because they ride on one another: k_render carries alloc, and k_compute_normals carries compactify,
-// the splat and integrate, so those device functions must be visible together.  The checks of integrate's arithmetic
-// (k_check_refined_division, k_check_weighted_colour) stay with the functions they check, and k_debug_hash_ops with the
-// kernels whose hash operations it runs one by one.  What shares only vh_device.hpp with the frame loop has a unit of
-// its own: vh_image.hip, vh_streaming.hip, vh_mc.hip, vh_util.hip.
+// the splat and integrate, so those device functions must be visible together.  They are written a stage to a header
+// (vh_frame_*.hpp, included in their order of definition; a header's includes say on whom its stage rides) but for the
+// ray caster -- the march, the queries and the tile ray caster, which carries alloc -- which stands here, between the
+// includes, until it is moved in a change of its own.  The checks of integrate's arithmetic (k_check_refined_division,
+// k_check_weighted_colour) stay with the functions they check, and k_debug_hash_ops with the kernels whose hash
+// operations it runs one by one.  What shares only vh_device.hpp with the frame loop has a unit of its own:
+// vh_image.hip, vh_streaming.hip, vh_mc.hip, vh_util.hip.
+// A stage's launch shape is a host function beside its kernel; the launchers, whether they launch the stage alone or as
+// a rider, call it.
 //
 // Reference behaviour: DSC/CUDASceneRepHashSDF.cu, DSC/CUDARayCastSDF.cu, DSC/RayCastSDFUtil.h, DSC/CameraUtil.cu:669-711
 // (DSC/ = DepthSensingCUDA/Source/ of the reference).  Nothing here is derived from those kernels' structure: launch
@@ -24,1515 +29,12 @@
 
 using namespace vhd;
 
+#include "vh_frame_alloc.hpp"
+#include "vh_frame_compactify.hpp"
+#include "vh_frame_integrate.hpp"
+#include "vh_frame_splat.hpp"
+
 namespace {
-
-// ---------------------------------------------------------------------------
-// reset (resetHeapKernel / resetHashKernel / resetHashBucketMutexKernel,
-// DSC/CUDASceneRepHashSDF.cu:23-61).  Voxels and summaries are cleared with
-// hipMemsetAsync; these kernels write the non-zero patterns, 16 B per lane.
-// ---------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256) void k_reset_heap(uint32_t* heap, uint32_t* heapCounter, uint32_t n)
-{
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx == 0) heapCounter[0] = n - 1;
-    if (idx < n) heap[idx] = n - idx - 1;
-}
-
-__global__ __launch_bounds__(256) void k_reset_hash(VhHashEntry* a, VhHashEntry* b, uint32_t ne)
-{
-    // one 16-byte half-entry per lane: even lanes {0,0,0,FREE}, odd lanes {offset=0,pad}
-    const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < 2ull * ne) {
-        const int4 v = (idx & 1) ? make_int4(0, 0, 0, 0) : make_int4(0, 0, 0, VH_FREE_ENTRY);
-        reinterpret_cast<int4*>(a)[idx] = v;
-        reinterpret_cast<int4*>(b)[idx] = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_fill_i32(int32_t* p, int32_t v, uint32_t n)
-{
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < n) p[idx] = v;
-}
-
-// ---------------------------------------------------------------------------
-// alloc (allocKernel, DSC/CUDASceneRepHashSDF.cu:158-243)
-//
-// One wave per 8x8 pixel tile.  Each lane walks its ray's SDF blocks with the
-// reference's DDA; at every step the wave de-duplicates the block ids its
-// lanes ask for (neighbouring rays hit the same 8^3 block) and ONE lane probes
-// the table per distinct id, so the table sees ~1/64 of the reference's probes.
-// ---------------------------------------------------------------------------
-
-// What integrateDepthMapKernel reads of a pixel (DSC/CUDASceneRepHashSDF.cu:436-470), formed once per pixel instead
-// of once per voxel that projects onto it: the depth, the colour as the bytes the kernel would make of it
-// (uchar(255 * c), :466) and the weight of the sample (:463-464, a function of the depth alone).  Weight 0 marks a
-// pixel that integrates nothing: invalid depth or colour, or beyond the integration distance (:443-445); a valid
-// sample weighs at least 1.
-VHD uint2 pack_pixel(const VhHashParams& hp, const VhDepthCameraParams& cp, float depth, bool hasColor, float4 c)
-{
-    uint32_t cw = 0u;
-    if (hasColor && c.x != minf() && depth != minf() && depth < hp.m_maxIntegrationDistance) {
-        const float depthZeroOne = cam_to_proj_z(cp, depth);
-        const float weightUpdate = fmaxf((float)hp.m_integrationWeightSample * 1.5f * (1.0f - depthZeroOne), 1.0f);
-        cw = pack_cw(f2uc(255.0f * c.x), f2uc(255.0f * c.y), f2uc(255.0f * c.z), f2uc(weightUpdate));
-    }
-    return make_uint2(__float_as_uint(depth), cw);
-}
-
-// one wave, one 8x8 pixel tile
-VHD void alloc_tile(const VhHashData& hd, const VhHashParams& hp, const VhDepthCameraData& cam, const VhDepthCameraParams& cp,
-                    const uint32_t* bitMask, int32_t lockToken, HashMod hm, uint2* packed, uint32_t tile)
-{
-    const uint32_t lane = lane_id();
-    const uint32_t W = cp.m_imageWidth, H = cp.m_imageHeight;
-    const uint32_t tilesX = (W + 7) / 8, tilesY = (H + 7) / 8;
-    if (tile >= tilesX * tilesY) return; // wave-uniform
-    const uint32_t x = (tile % tilesX) * 8 + (lane & 7), y = (tile / tilesX) * 8 + (lane >> 3);
-    const float vs = hp.m_virtualVoxelSize;
-
-    bool active = (x < W) && (y < H);
-    float d = active ? cam.d_depthData[y * W + x] : minf();
-    if (packed && active) { // the frame as the integrate pass reads it (a 128-byte row segment per 8 lanes)
-        float4 c = make_float4(minf(), minf(), minf(), minf());
-        if (cam.d_colorData) c = reinterpret_cast<const float4*>(cam.d_colorData)[y * W + x];
-        packed[y * W + x] = pack_pixel(hp, cp, d, cam.d_colorData != nullptr, c);
-    }
-    if (d == minf() || d == 0.0f) active = false;
-    if (d >= hp.m_maxIntegrationDistance) active = false;
-    const float t = get_truncation(hp, d);
-    const float minDepth = fminf(hp.m_maxIntegrationDistance, d - t);
-    const float maxDepth = fminf(hp.m_maxIntegrationDistance, d + t);
-    if (minDepth >= maxDepth) active = false;
-    if (!__any(active)) return; // a tile without a measurement
-
-    const F3 rayMin = mat_mul_p(hp.m_rigidTransform, depth_to_skeleton(cp, x, y, minDepth));
-    const F3 rayMax = mat_mul_p(hp.m_rigidTransform, depth_to_skeleton(cp, x, y, maxDepth));
-    const F3 rayDir = normalize3(mk3(rayMax.x - rayMin.x, rayMax.y - rayMin.y, rayMax.z - rayMin.z));
-
-    // (world_to_block with the division by the voxel size as div_exact: five vector instructions instead of eleven, the same
-    // quotient bit for bit -- tests/test_gpu_parity.py::test_exact_shortcuts; the ray caster's tap coordinates do the same)
-    const float rvs = 1.0f / vs;
-    I3 id = vvp_to_block(mki3(world_to_vvp1_rb(rayMin.x, vs, rvs), world_to_vvp1_rb(rayMin.y, vs, rvs), world_to_vvp1_rb(rayMin.z, vs, rvs)));
-    const I3 idEnd = vvp_to_block(mki3(world_to_vvp1_rb(rayMax.x, vs, rvs), world_to_vvp1_rb(rayMax.y, vs, rvs), world_to_vvp1_rb(rayMax.z, vs, rvs)));
-
-    const F3 step = mk3((float)signi(rayDir.x), (float)signi(rayDir.y), (float)signi(rayDir.z));
-    const I3 cl = mki3(f2i(fmaxf(0.0f, fminf(step.x, 1.0f))), f2i(fmaxf(0.0f, fminf(step.y, 1.0f))), f2i(fmaxf(0.0f, fminf(step.z, 1.0f))));
-    F3 boundaryPos = block_to_world(vs, mki3(id.x + cl.x, id.y + cl.y, id.z + cl.z));
-    const float half = 0.5f * vs;
-    boundaryPos.x -= half; boundaryPos.y -= half; boundaryPos.z -= half;
-    F3 tMax = mk3((boundaryPos.x - rayMin.x) / rayDir.x, (boundaryPos.y - rayMin.y) / rayDir.y, (boundaryPos.z - rayMin.z) / rayDir.z);
-    F3 tDelta = mk3((step.x * (float)VH_SDF_BLOCK_SIZE * vs) / rayDir.x, (step.y * (float)VH_SDF_BLOCK_SIZE * vs) / rayDir.y,
-                    (step.z * (float)VH_SDF_BLOCK_SIZE * vs) / rayDir.z);
-    const I3 idBound = mki3(f2i((float)idEnd.x + step.x), f2i((float)idEnd.y + step.y), f2i((float)idEnd.z + step.z));
-
-    if (rayDir.x == 0.0f) { tMax.x = pinf(); tDelta.x = pinf(); }
-    if (boundaryPos.x - rayMin.x == 0.0f) { tMax.x = pinf(); tDelta.x = pinf(); }
-    if (rayDir.y == 0.0f) { tMax.y = pinf(); tDelta.y = pinf(); }
-    if (boundaryPos.y - rayMin.y == 0.0f) { tMax.y = pinf(); tDelta.y = pinf(); }
-    if (rayDir.z == 0.0f) { tMax.z = pinf(); tDelta.z = pinf(); }
-    if (boundaryPos.z - rayMin.z == 0.0f) { tMax.z = pinf(); tDelta.z = pinf(); }
-
-    uint32_t iter = 0;
-    while (__any(active)) {
-        // Steady state: the block exists and sits in the first slot of its bucket.  Every lane checks that for
-        // its own block with ONE load (all lanes in flight together); only the rest -- new blocks and blocks
-        // further down a bucket -- goes through the serial allocBlock below.  The reference asks "in the frustum?
-        // not streamed out?" first; the tests are independent and a block that exists needs nothing, so the cheap
-        // one goes first and the projection runs only for a block that is not where it is expected.
-        bool want = active;
-        if (want) {
-            const int4 q0 = load_quad(&hd.d_hash[hash_pos_fast(hm, id) * VH_HASH_BUCKET_SIZE]);
-            want = !quad_matches(q0, id);
-        }
-        if (want) want = block_in_frustum(hp, cp, id) && !block_streamed_out(hp, id, bitMask);
-        // wave-level de-duplication of the requested block ids: one lane per distinct id, and those lanes allocate
-        // side by side -- the chain lock -> heap counter -> heap slot -> entry is four trips to memory, walked once
-        // for all the new blocks of this step instead of once per block
-        uint64_t pending = __ballot(want);
-        bool leads = false;
-        while (pending) {
-            const int leader = __ffsll((unsigned long long)pending) - 1;
-            const int bx = __builtin_amdgcn_readlane(id.x, leader);
-            const int by = __builtin_amdgcn_readlane(id.y, leader);
-            const int bz = __builtin_amdgcn_readlane(id.z, leader);
-            const bool same = want && id.x == bx && id.y == by && id.z == bz;
-            pending &= ~__ballot(same);
-            leads = leads || (int)lane == leader;
-        }
-        if (leads) alloc_block(hd, hp, id, lockToken);
-        if (active) {
-            if (tMax.x < tMax.y && tMax.x < tMax.z) {
-                id.x = f2i((float)id.x + step.x);
-                if (id.x == idBound.x) active = false;
-                tMax.x += tDelta.x;
-            } else if (tMax.z < tMax.y) {
-                id.z = f2i((float)id.z + step.z);
-                if (id.z == idBound.z) active = false;
-                tMax.z += tDelta.z;
-            } else {
-                id.y = f2i((float)id.y + step.y);
-                if (id.y == idBound.y) active = false;
-                tMax.y += tDelta.y;
-            }
-            iter++;
-            if (iter >= 1024u) active = false;
-        }
-    }
-}
-
-__global__ __launch_bounds__(512) void k_alloc(VhHashData hd, VhHashParams hp, VhDepthCameraData cam,
-                                               VhDepthCameraParams cp, const uint32_t* bitMask, int32_t lockToken, HashMod hm, uint2* packed)
-{
-    // the compaction that follows needs its counter at zero: cleared here instead of by a separate memset
-    if (blockIdx.x == 0 && threadIdx.x == 0) hd.d_hashCompactifiedCounter[0] = 0;
-    alloc_tile(hd, hp, cam, cp, bitMask, lockToken, hm, packed, blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
-}
-
-// ---------------------------------------------------------------------------
-// compactify (compactifyHashAllInOneKernel, DSC/CUDASceneRepHashSDF.cu:317-359)
-//
-// The reference scans all Ne entries (32 B each) every frame.  Here the
-// 1-bit-per-bucket summary is scanned instead (Nb/8 bytes) and only non-empty
-// buckets are opened; kept entries queue up in LDS and the workgroup appends
-// them to the list with ONE atomic (compactify_group below).
-// ---------------------------------------------------------------------------
-
-// v_cvt_i32_f32 truncates, saturates and sends NaN to 0 by itself: f2i() without the v_trunc_f32 the compiler puts in front
-VHD int cvt_rz(float v)
-{
-    int r;
-    asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(v));
-    return r;
-}
-
-constexpr uint32_t kIntegrateTile = 32;        // a block's screen footprint of up to 32 x 29 pixels is staged in LDS,
-constexpr uint32_t kIntegrateTileRows = 29;    // rows 34 pixels apart (272 B: vertical neighbours fall into different banks):
-constexpr uint32_t kIntegrateTileStride = 34;  // 31.6 KB per workgroup = 25 allocation units of 1280 B, five workgroups per compute
-                                               // unit (30 rows are 26 units: per-wave time stamps showed four resident, the fifth waiting)
-
-// What the fused integrate pass wants to know of a block before it touches a voxel, worked out once per block by the
-// compactify pass (one lane per block there; in the integrate pass it would be ~160 instructions of every wave) and
-// kept in the three spare words of the block's entry in the compactified list:
-//   box: the block's screen footprint for the frame being integrated -- the hull of its eight corner voxels' pixels, one
-//     pixel wider all round (a perspective projection maps the block into the hull of its corners when all of them lie
-//     in front of the camera; the extra pixel covers rounding), clipped to the image, starting at an even pixel.  The
-//     corners are projected with a hardware reciprocal: the box only decides WHERE a pixel is read from (the tile
-//     staged in LDS or the frame itself), never which pixel;
-//   VH_BOX_STAGED: the box is worth staging (in front of the camera, at most 32 x 29 pixels, even image width);
-//   VH_BOX_CERTIFIED: the range certificate of integrate_block_certified holds at all eight corners (exact arithmetic,
-//     the same expressions the voxels go through);
-//   tag: which transform / camera / voxel size that was worked out for.  A pass that runs with another one works it
-//     out again itself.
-constexpr uint32_t VH_BOX_STAGED = 1u, VH_BOX_CERTIFIED = 2u;
-struct BlockBox {
-    uint32_t x0, y0, w, h, flags;
-};
-VHD uint32_t frame_tag(const VhHashParams& hp, const VhDepthCameraParams& cp)
-{
-    uint32_t t = 0x9E3779B9u;
-#pragma unroll
-    for (int i = 0; i < 12; i++) t = (t ^ __float_as_uint(hp.m_rigidTransformInverse[i])) * 0x01000193u + (t >> 15);
-    const uint32_t more[7] = { __float_as_uint(hp.m_virtualVoxelSize), __float_as_uint(cp.fx), __float_as_uint(cp.fy), __float_as_uint(cp.mx),
-                               __float_as_uint(cp.my), cp.m_imageWidth, cp.m_imageHeight };
-#pragma unroll
-    for (int i = 0; i < 7; i++) t = (t ^ more[i]) * 0x01000193u + (t >> 15);
-    return (t & 0x7fffffffu) | 1u; // never 0: a zeroed entry carries no box; bit 31 is the mark of a rider_tag
-}
-// The tag of a list made and read within ONE launch (the pass over the voxels as a rider): the frame's number.  The reader
-// takes an entry for this frame's when it carries this tag (CoIntegrate), so the tag must not repeat from one frame to the
-// next as frame_tag does when the camera stands still, and must not collide with one by chance.
-VHD uint32_t rider_tag(uint32_t frameNumber) { return 0x80000000u | frameNumber; }
-struct BoxCorners { // what the eight corners add up to
-    int bx0, bx1, by0, by1;
-    float cz;
-    bool fine;
-};
-VHD BoxCorners box_no_corner()
-{
-    BoxCorners a;
-    a.bx0 = 0x7fffffff; a.bx1 = (int)0x80000000; a.by0 = 0x7fffffff; a.by1 = (int)0x80000000;
-    a.cz = pinf();
-    a.fine = true;
-    return a;
-}
-VHD void box_add_corner(const VhHashParams& hp, const VhDepthCameraParams& cp, int ex, int ey, int ez, uint32_t c, BoxCorners& a)
-{
-    const I3 pc = mki3(ex * VH_SDF_BLOCK_SIZE + ((c & 1u) ? 7 : 0), ey * VH_SDF_BLOCK_SIZE + ((c & 2u) ? 7 : 0), ez * VH_SDF_BLOCK_SIZE + ((c & 4u) ? 7 : 0));
-    const F3 pf = mat_mul_p(hp.m_rigidTransformInverse, vvp_to_world(hp.m_virtualVoxelSize, pc));
-    const float rz = __builtin_amdgcn_rcpf(pf.z);
-    const int cx = cvt_rz((pf.x * cp.fx * rz + cp.mx) + 0.5f), cy = cvt_rz((pf.y * cp.fy * rz + cp.my) + 0.5f); // (saturating; NaN -> 0)
-    a.bx0 = min(a.bx0, cx); a.bx1 = max(a.bx1, cx);
-    a.by0 = min(a.by0, cy); a.by1 = max(a.by1, cy);
-    a.cz = fminf(a.cz, pf.z);
-    a.fine = a.fine && pf.z >= 0x1p-20f && pf.z <= 0x1p20f && fabsf(pf.x * cp.fx) <= 0x1p60f && fabsf(pf.y * cp.fy) <= 0x1p60f;
-}
-VHD BlockBox box_of_corners(const VhDepthCameraParams& cp, const BoxCorners& a)
-{
-    const bool inFront = a.cz > 1e-3f;
-    // (coordinates beyond +-2^30 would overflow the arithmetic below: such a block is simply not staged)
-    const bool sane = a.bx0 > -(1 << 30) && a.bx1 < (1 << 30) && a.by0 > -(1 << 30) && a.by1 < (1 << 30);
-    const int x0i = max(a.bx0 - 1, 0) & ~1, x1i = min(a.bx1 + 1, (int)cp.m_imageWidth - 1);
-    const int y0i = max(a.by0 - 1, 0), y1i = min(a.by1 + 1, (int)cp.m_imageHeight - 1);
-    const bool staged = inFront && sane && x0i <= x1i && y0i <= y1i && (x1i - x0i) < (int)kIntegrateTile && (y1i - y0i) < (int)kIntegrateTileRows &&
-                        (cp.m_imageWidth & 1u) == 0u && cp.m_imageWidth <= 0xffffu && cp.m_imageHeight <= 0xffffu;
-    BlockBox b;
-    b.x0 = staged ? (uint32_t)x0i : 0u;
-    b.y0 = staged ? (uint32_t)y0i : 0u;
-    b.w = staged ? (uint32_t)(x1i - x0i + 1) : 0u;
-    b.h = staged ? (uint32_t)(y1i - y0i + 1) : 0u;
-    b.flags = (staged ? VH_BOX_STAGED : 0u) | (a.fine ? VH_BOX_CERTIFIED : 0u);
-    return b;
-}
-VHD BlockBox block_box(const VhHashParams& hp, const VhDepthCameraParams& cp, int ex, int ey, int ez)
-{
-    BoxCorners a = box_no_corner();
-#pragma unroll
-    for (uint32_t c = 0; c < 8u; c++) box_add_corner(hp, cp, ex, ey, ez, c, a);
-    return box_of_corners(cp, a);
-}
-// the same by eight neighbouring lanes, a corner each (every lane gets the box)
-VHD BlockBox block_box_by_eight_lanes(const VhHashParams& hp, const VhDepthCameraParams& cp, int ex, int ey, int ez)
-{
-    BoxCorners a = box_no_corner();
-    box_add_corner(hp, cp, ex, ey, ez, lane_id() & 7u, a);
-    int fine = a.fine ? 1 : 0;
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        a.bx0 = min(a.bx0, __shfl_xor(a.bx0, o)); a.bx1 = max(a.bx1, __shfl_xor(a.bx1, o));
-        a.by0 = min(a.by0, __shfl_xor(a.by0, o)); a.by1 = max(a.by1, __shfl_xor(a.by1, o));
-        a.cz = fminf(a.cz, __shfl_xor(a.cz, o));
-        fine &= __shfl_xor(fine, o);
-    }
-    a.fine = fine != 0;
-    return box_of_corners(cp, a);
-}
-// the spare words of a compactified entry: {x0 | y0 << 16, w | h << 8 | flags << 16, tag}
-VHD uint4 pack_box(uint32_t offset, const BlockBox& b, uint32_t tag) { return make_uint4(offset, b.x0 | (b.y0 << 16), b.w | (b.h << 8) | (b.flags << 16), tag); }
-
-// A workgroup takes 256 words of 32 occupancy bits.  It first gathers its non-empty buckets (a lane per word), then reads
-// their slots a lane per slot, four slots in flight per lane: the loads do not depend on each other, so the workgroup's life
-// is a few trips to memory -- with a lane per word and a loop over the word's bits it was one trip per set bit of the fullest
-// word of the wave, 5-6 us where the launch's other riders need 2 (and the pass over the voxels, when it rides in the same
-// launch, waits for the list).  What the workgroup keeps is queued in LDS and appended to the list with ONE atomic per
-// workgroup (agent-scope atomics on one address are served one after the other at the memory side of the eight L2s, ~12 ns
-// each: with one per wave and slot the dense scene's 8 700 blocks cost 40 us).  The queued entries then get their boxes, one
-// lane each.  Entries beyond the queue's capacity take the list directly.
-constexpr uint32_t kCompactQueue = 768;
-struct CompactShared {
-    int4 q[kCompactQueue];
-    uint32_t off[kCompactQueue];
-    uint32_t n, base, nBuckets;
-    uint16_t buckets[256 * 32]; // the non-empty buckets, relative to the workgroup's first
-};
-// An entry of the compactified list, written and read within ONE launch (the pass over the voxels as a rider of the launch
-// that makes its list, k_compute_normals): the L2s of the eight XCDs are not coherent with each other, so such an entry is
-// written through and read at the agent's coherence point (relaxed agent-scope atomics: the sc1 forms of the instructions)
-// instead of the writers writing their whole L2 back and the readers dropping theirs (a release / acquire pair at agent
-// scope costs exactly that, buffer_wbl2 / buffer_inv: measured, +30 us a frame).
-template <bool COHERENT> VHD void list_store(VhHashEntry* o, const int4 q, const uint4 box)
-{
-    if (COHERENT) {
-        uint64_t* const w = reinterpret_cast<uint64_t*>(o);
-        __hip_atomic_store(w + 0, (uint64_t)(uint32_t)q.x | ((uint64_t)(uint32_t)q.y << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(w + 1, (uint64_t)(uint32_t)q.z | ((uint64_t)(uint32_t)q.w << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(w + 2, (uint64_t)box.x | ((uint64_t)box.y << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // the word with the tag goes last, when the others have arrived: a reader that finds the tag finds the entry
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __hip_atomic_store(w + 3, (uint64_t)box.z | ((uint64_t)box.w << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        *(reinterpret_cast<uint4*>(o) + 1) = box;
-        store_quad(o, q);
-    }
-}
-template <bool COHERENT> VHD int4 list_quad(const VhHashEntry* e)
-{
-    if (COHERENT) {
-        const uint64_t* const w = reinterpret_cast<const uint64_t*>(e);
-        const uint64_t a = __hip_atomic_load(w + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), b = __hip_atomic_load(w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return make_int4((int)(uint32_t)a, (int)(uint32_t)(a >> 32), (int)(uint32_t)b, (int)(uint32_t)(b >> 32));
-    }
-    return load_quad(e);
-}
-template <bool COHERENT> VHD uint4 list_box(const VhHashEntry* e)
-{
-    if (COHERENT) {
-        const uint64_t* const w = reinterpret_cast<const uint64_t*>(e);
-        const uint64_t a = __hip_atomic_load(w + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), b = __hip_atomic_load(w + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
-    }
-    return *(reinterpret_cast<const uint4*>(e) + 1);
-}
-
-template <bool COHERENT = false>
-__device__ void compactify_group(const VhHashData& hd, const VhHashParams& hp, const VhDepthCameraParams& cp, uint32_t wordIdx, CompactShared& sh, const uint32_t riderTag = 0u)
-{
-    const uint32_t nWords = (hp.m_hashNumBuckets + 31) / 32;
-    const uint32_t tag = COHERENT ? riderTag : frame_tag(hp, cp);
-    const uint32_t lane = lane_id();
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 42 // measurement build: the phases of a compactify workgroup (tools/riders_stamps.py)
-    uint32_t phase[6];
-    phase[0] = (uint32_t)__builtin_amdgcn_s_memrealtime();
-#define VH_COMPACT_PHASE(I) phase[I] = (uint32_t)__builtin_amdgcn_s_memrealtime();
-#define VH_COMPACT_PHASES_OUT { __syncthreads(); if (threadIdx.x == 0) { uint4* const at = reinterpret_cast<uint4*>(hd.d_hashCompactified) + (hp.m_hashNumBuckets * VH_HASH_BUCKET_SIZE) / 2u + 8192u + 2u * (wordIdx / 256u); \
-        at[0] = make_uint4(phase[0], phase[1], phase[2], 0x5743u); at[1] = make_uint4(phase[3], phase[4], (uint32_t)__builtin_amdgcn_s_memrealtime(), sh.n | (sh.nBuckets << 16)); } }
-#else
-#define VH_COMPACT_PHASE(I)
-#define VH_COMPACT_PHASES_OUT
-#endif
-    if (threadIdx.x == 0) { sh.n = 0u; sh.nBuckets = 0u; }
-    __syncthreads();
-    // the non-empty buckets, gathered (their order does not matter)
-    uint32_t bits = (wordIdx < nWords) ? hd.d_bucketBits[wordIdx] : 0u;
-    {
-        const uint32_t mine = (uint32_t)__popc(bits);
-        uint32_t incl = mine;
-#pragma unroll
-        for (uint32_t d = 1; d < kWave; d <<= 1) {
-            const uint32_t t = (uint32_t)__shfl_up((int)incl, d);
-            if (lane >= d) incl += t;
-        }
-        const uint32_t total = (uint32_t)__shfl((int)incl, kWave - 1);
-        uint32_t at = 0;
-        if (lane == 0 && total != 0u) at = atomicAdd(&sh.nBuckets, total);
-        at = (uint32_t)__shfl((int)at, 0) + incl - mine;
-        while (bits != 0u) {
-            sh.buckets[at++] = (uint16_t)(threadIdx.x * 32u + (uint32_t)(__ffs((int)bits) - 1));
-            bits &= bits - 1u;
-        }
-    }
-    __syncthreads();
-    VH_COMPACT_PHASE(1)
-    const uint32_t nSlots = sh.nBuckets * VH_HASH_BUCKET_SIZE;
-    const uint64_t firstBucket = (uint64_t)(wordIdx - threadIdx.x) * 32u;
-    constexpr uint32_t kInFlight = 4; // (eight: 20 registers more for the launch's every wave, and no sooner done)
-    for (uint32_t s0 = threadIdx.x; s0 < nSlots; s0 += 256u * kInFlight) { // (s0 < nSlots for all or none of a wave's lanes but in its last trip)
-        int4 qs[kInFlight];
-        uint32_t offs[kInFlight];
-#pragma unroll
-        for (uint32_t j = 0; j < kInFlight; j++) {
-            const uint32_t slot = s0 + 256u * j;
-            qs[j] = make_int4(0, 0, 0, VH_FREE_ENTRY);
-            offs[j] = 0;
-            if (slot < nSlots) {
-                const VhHashEntry* e = &hd.d_hash[(firstBucket + sh.buckets[slot / VH_HASH_BUCKET_SIZE]) * VH_HASH_BUCKET_SIZE + slot % VH_HASH_BUCKET_SIZE];
-                qs[j] = load_quad(e);
-                offs[j] = e->offset;
-            }
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kInFlight; j++) {
-            const int4 q = qs[j];
-            const bool keep = q.w != VH_FREE_ENTRY && block_in_frustum(hp, cp, mki3(q.x, q.y, q.z));
-            const uint64_t kept = __ballot(keep); // one LDS atomic per wave
-            if (kept == 0ull) continue;
-            uint32_t at = 0;
-            if (lane == 0) at = atomicAdd(&sh.n, (uint32_t)__popcll(kept));
-            at = (uint32_t)__shfl((int)at, 0) + (uint32_t)__popcll(kept & lanemask_lt());
-            if (keep) {
-                if (at < kCompactQueue) {
-                    sh.q[at] = q;
-                    sh.off[at] = offs[j];
-                } else { // the queue is full: straight to the list
-                    VhHashEntry* o = &hd.d_hashCompactified[(uint32_t)atomicAdd(hd.d_hashCompactifiedCounter, 1)];
-                    list_store<COHERENT>(o, q, pack_box(offs[j], block_box(hp, cp, q.x, q.y, q.z), tag));
-                }
-            }
-        }
-    }
-    __syncthreads();
-    VH_COMPACT_PHASE(2)
-    const uint32_t n = min(sh.n, kCompactQueue);
-    if (n == 0u) return; // (the same for every thread)
-    // the workgroup's place in the list: asked for now, needed when the first boxes are done (a trip to memory)
-    uint32_t place = 0;
-    if (threadIdx.x == 0) place = (uint32_t)atomicAdd(hd.d_hashCompactifiedCounter, (int)n);
-    if (COHERENT) {
-        // (the pass that reads this list in the same launch gives a workgroup to every block and never looks at a box: the
-        // entries go out as soon as the place is known, the tag in their last word)
-        if (threadIdx.x == 0) sh.base = place;
-        __syncthreads();
-        VH_COMPACT_PHASE(3)
-        const uint32_t base = sh.base;
-        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) list_store<true>(&hd.d_hashCompactified[base + i], sh.q[i], make_uint4(sh.off[i], 0u, 0u, tag));
-        VH_COMPACT_PHASE(4)
-        VH_COMPACT_PHASES_OUT
-        return;
-    }
-    // the boxes, eight lanes per entry (a corner each: one lane per entry is ~300 instructions in a row, 1 us on a busy unit)
-    constexpr uint32_t kBoxRounds = 2; // (rounds of 32 entries whose boxes wait in registers for the place; more entries: after it)
-    uint4 boxes[kBoxRounds];
-    const uint32_t mine = threadIdx.x >> 3;
-#pragma unroll
-    for (uint32_t r = 0; r < kBoxRounds; r++) {
-        const uint32_t i = min(r * 32u + mine, n - 1u); // (whole groups of eight lanes compute or idle; an idle group repeats the last entry)
-        if (r * 32u < n) {
-            const int4 q = sh.q[i];
-            boxes[r] = pack_box(sh.off[i], block_box_by_eight_lanes(hp, cp, q.x, q.y, q.z), tag);
-        }
-    }
-    if (threadIdx.x == 0) sh.base = place;
-    __syncthreads();
-    VH_COMPACT_PHASE(3)
-    const uint32_t base = sh.base;
-#pragma unroll
-    for (uint32_t r = 0; r < kBoxRounds; r++) {
-        const uint32_t i = r * 32u + mine;
-        if (i < n && (threadIdx.x & 7u) == 0u) list_store<COHERENT>(&hd.d_hashCompactified[base + i], sh.q[i], boxes[r]);
-    }
-    for (uint32_t r = kBoxRounds; r * 32u < n; r++) {
-        const uint32_t i = r * 32u + mine;
-        const int4 q = sh.q[min(i, n - 1u)];
-        const BlockBox b = block_box_by_eight_lanes(hp, cp, q.x, q.y, q.z);
-        if (i < n && (threadIdx.x & 7u) == 0u) list_store<COHERENT>(&hd.d_hashCompactified[base + i], q, pack_box(sh.off[i], b, tag));
-    }
-    VH_COMPACT_PHASE(4)
-    VH_COMPACT_PHASES_OUT
-}
-
-__global__ __launch_bounds__(256) void k_compactify(VhHashData hd, VhHashParams hp, VhDepthCameraParams cp)
-{
-    __shared__ CompactShared sh;
-    compactify_group(hd, hp, cp, blockIdx.x * blockDim.x + threadIdx.x, sh);
-}
-
-// ---------------------------------------------------------------------------
-// integrate / starve / garbage collection
-// (integrateDepthMapKernel :412-492, starveVoxelsKernel :512-521,
-//  garbageCollectIdentifyKernel :543-590, garbageCollectFreeKernel :608-628)
-//
-// One 256-thread workgroup per SDF block, two x-adjacent voxels (16 B) per
-// lane: a block is 4 waves x 1 KiB fully coalesced.  The fused kernel keeps the
-// block in registers across integrate -> starve -> identify -> free, so every
-// voxel is read once and written once per frame; min/max are reduced with
-// wave64 shuffles and a 4-entry LDS combine.
-// ---------------------------------------------------------------------------
-
-VHD Vox integrate_voxel(const VhHashParams& hp, const VhDepthCameraParams& cp, const VhDepthCameraData& cam, I3 pi, Vox stored)
-{
-    F3 pf = mat_mul_p(hp.m_rigidTransformInverse, vvp_to_world(hp.m_virtualVoxelSize, pi));
-    // cameraToKinectScreenInt, DSC/DepthCameraUtil.h:74-85 -> uint2
-    const uint32_t sx = (uint32_t)f2i((pf.x * cp.fx / pf.z + cp.mx) + 0.5f);
-    const uint32_t sy = (uint32_t)f2i((pf.y * cp.fy / pf.z + cp.my) + 0.5f);
-    if (sx < cp.m_imageWidth && sy < cp.m_imageHeight) {
-        const uint32_t pix = sy * cp.m_imageWidth + sx;
-        const float depth = cam.d_depthData[pix];
-        float cr = minf(), cg = minf(), cb = minf();
-        if (cam.d_colorData) {
-            const float4 c = reinterpret_cast<const float4*>(cam.d_colorData)[pix];
-            cr = c.x; cg = c.y; cb = c.z;
-        }
-        if (cr != minf() && depth != minf()) {
-            if (depth < hp.m_maxIntegrationDistance) {
-                const float depthZeroOne = cam_to_proj_z(cp, depth);
-                float sdf = depth - pf.z;
-                const float truncation = get_truncation(hp, depth);
-                if (sdf > -truncation) {
-                    if (sdf >= 0.0f) sdf = fminf(truncation, sdf);
-                    else sdf = fmaxf(-truncation, sdf);
-                    const float weightUpdate = fmaxf((float)hp.m_integrationWeightSample * 1.5f * (1.0f - depthZeroOne), 1.0f);
-                    Vox curr;
-                    curr.sdf = sdf;
-                    if (cam.d_colorData) curr.cw = pack_cw(f2uc(255.0f * cr), f2uc(255.0f * cg), f2uc(255.0f * cb), f2uc(weightUpdate));
-                    else curr.cw = pack_cw(0, 255, 0, f2uc(weightUpdate));
-                    return combine_voxel(hp, stored, curr);
-                }
-            }
-        }
-    }
-    return stored;
-}
-
-VHD Vox starve_voxel(Vox v)
-{
-    uint32_t w = v.weight();
-    w = (w > 0u) ? w - 1u : 0u;
-    v.cw = (v.cw & 0x00ffffffu) | (w << 24);
-    return v;
-}
-
-// block-wide min(|sdf| of weighted voxels) / max(weight): wave shuffle tree,
-// then one LDS slot per wave.  Every lane returns the block result.
-VHD void block_min_max(float& minSdf, uint32_t& maxW, float* sMin, uint32_t* sMax)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        minSdf = fminf(minSdf, __shfl_xor(minSdf, o));
-        maxW = max(maxW, (uint32_t)__shfl_xor((int)maxW, o));
-    }
-    const uint32_t wave = threadIdx.x / kWave;
-    if (lane_id() == 0) { sMin[wave] = minSdf; sMax[wave] = maxW; }
-    __syncthreads();
-    float m = sMin[0];
-    uint32_t w = sMax[0];
-    for (uint32_t i = 1; i < blockDim.x / kWave; i++) { m = fminf(m, sMin[i]); w = max(w, sMax[i]); }
-    minSdf = m; maxW = w;
-}
-
-VHD float gc_key(Vox v) { return (v.weight() == 0u) ? pinf() : fabsf(v.sdf); }
-
-template <bool FUSED>
-__global__ __launch_bounds__(256) void k_integrate(VhHashData hd, VhHashParams hp, VhDepthCameraData cam,
-                                                   VhDepthCameraParams cp, uint32_t flags, int32_t lockToken, uint32_t* countMirror)
-{
-    __shared__ float sMin[4];
-    __shared__ uint32_t sMax[4];
-    __shared__ int sFreed;
-
-    const uint32_t count = FUSED ? (uint32_t)hd.d_hashCompactifiedCounter[0] : hp.m_numOccupiedBlocks;
-    // host-visible copy of the block count (mapped pinned memory): replaces a per-frame device->host copy
-    if (FUSED && countMirror && blockIdx.x == 0 && threadIdx.x == 0) *countMirror = count;
-    const uint32_t t = threadIdx.x;
-    // voxel pair (2t, 2t+1): x = (2t)%8 (+1), y = (2t%64)/8, z = 2t/64  (delinearizeVoxelIndex, DSC/VoxelUtilHashSDF.h:313-318)
-    const int lx = (int)((2u * t) & 7u), ly = (int)(((2u * t) & 63u) >> 3), lz = (int)((2u * t) >> 6);
-
-    for (uint32_t b = blockIdx.x; b < count; b += gridDim.x) {
-        const int4 q = load_quad(&hd.d_hashCompactified[b]);
-        const int ex = __builtin_amdgcn_readfirstlane(q.x), ey = __builtin_amdgcn_readfirstlane(q.y);
-        const int ez = __builtin_amdgcn_readfirstlane(q.z), ptr = __builtin_amdgcn_readfirstlane(q.w);
-
-        uint4* vp = reinterpret_cast<uint4*>(&hd.d_SDFBlocks[(uint32_t)ptr]) + t;
-        const uint4 raw = *vp;
-        Vox v0 = unpack_vox(make_uint2(raw.x, raw.y)), v1 = unpack_vox(make_uint2(raw.z, raw.w));
-
-        const I3 p0 = mki3(ex * VH_SDF_BLOCK_SIZE + lx, ey * VH_SDF_BLOCK_SIZE + ly, ez * VH_SDF_BLOCK_SIZE + lz);
-        v0 = integrate_voxel(hp, cp, cam, p0, v0);
-        v1 = integrate_voxel(hp, cp, cam, mki3(p0.x + 1, p0.y, p0.z), v1);
-        // Pin the four result words in VGPRs here.  Without this, hipcc (ROCm 7.2, gfx950, -O3) merges the
-        // "not integrated" path of the second voxel with a register that the colour fetch has already
-        // overwritten (found by the parity tests: sdf of skipped odd voxels came back as the colour's MINF).
-        asm volatile("" : "+v"(v0.sdf), "+v"(v0.cw), "+v"(v1.sdf), "+v"(v1.cw));
-
-        bool freed = false;
-        if (FUSED && (flags & VH_FUSED_GC)) {
-            if (flags & VH_FUSED_STARVE) { v0 = starve_voxel(v0); v1 = starve_voxel(v1); }
-            float minSdf = fminf(gc_key(v0), gc_key(v1));
-            uint32_t maxW = max(v0.weight(), v1.weight());
-            __syncthreads(); // LDS slots of the previous block iteration are consumed
-            block_min_max(minSdf, maxW, sMin, sMax);
-            const float thr = get_truncation(hp, cp.m_sensorDepthWorldMax);
-            const bool decide = (minSdf >= thr) || (maxW == 0u);
-            if (t == 0) {
-                hd.d_hashDecision[b] = decide ? 1 : 0;
-                sFreed = (decide && delete_hash_entry_element(hd, hp, mki3(ex, ey, ez), lockToken)) ? 1 : 0;
-            }
-            __syncthreads();
-            freed = sFreed != 0;
-        }
-        if (freed) {
-            *vp = make_uint4(0u, 0u, 0u, 0u);
-        } else {
-            const uint2 a = pack_vox(v0), c = pack_vox(v1);
-            *vp = make_uint4(a.x, a.y, c.x, c.y);
-        }
-    }
-}
-
-// integrate_voxel on a frame packed by alloc_tile / pack_pixel, in two steps: where the voxel projects to, and what
-// the pixel found there makes of the stored voxel
-VHD bool project_voxel(const VhHashParams& hp, const VhDepthCameraParams& cp, I3 pi, uint32_t& sx, uint32_t& sy, float& pz)
-{
-    F3 pf = mat_mul_p(hp.m_rigidTransformInverse, vvp_to_world(hp.m_virtualVoxelSize, pi));
-    sx = (uint32_t)f2i((pf.x * cp.fx / pf.z + cp.mx) + 0.5f);
-    sy = (uint32_t)f2i((pf.y * cp.fy / pf.z + cp.my) + 0.5f);
-    pz = pf.z;
-    return sx < cp.m_imageWidth && sy < cp.m_imageHeight;
-}
-VHD Vox apply_pixel(const VhHashParams& hp, uint2 px, float pz, Vox stored)
-{
-    // Without branches: every lane forms the blend, a select keeps or drops it (the lanes of a wave rarely agree, and
-    // straight-line code lets the eight voxels of a lane overlap: measured 6 % on the dense scene).  The arithmetic of a
-    // kept blend is integrateDepthMapKernel's (:447-472); a dropped one may be anything, NaN included.
-    const float depth = __uint_as_float(px.x);
-    float sdf = depth - pz;
-    const float truncation = get_truncation(hp, depth);
-    // a sample: valid depth within the integration distance, valid colour (weight byte, pack_pixel), not behind the band
-    const bool use = ((px.y >> 24) != 0u) && (sdf > -truncation);
-    const float lo = fmaxf(-truncation, sdf), hi = fminf(truncation, sdf);
-    Vox curr;
-    curr.sdf = (sdf >= 0.0f) ? hi : lo;
-    curr.cw = px.y;
-    const Vox c = combine_voxel(hp, stored, curr);
-    Vox out;
-    out.sdf = use ? c.sdf : stored.sdf;
-    out.cw = use ? c.cw : stored.cw;
-    return out;
-}
-VHD Vox integrate_voxel_packed(const VhHashParams& hp, const VhDepthCameraParams& cp, const uint2* packed, I3 pi, Vox stored)
-{
-    uint32_t sx, sy;
-    float pz;
-    if (project_voxel(hp, cp, pi, sx, sy, pz)) return apply_pixel(hp, packed[sy * cp.m_imageWidth + sx], pz, stored);
-    return stored;
-}
-
-// The fused pass: integrate -> starve -> identify -> free with every voxel read once and written once.  The block count
-// lives on the device (no host round trip), so the grid is fixed and the kernel picks its shape from the count:
-//   * few blocks (count <= workgroups): one WORKGROUP per block, two x-adjacent voxels (16 B) per lane -- the frame is
-//     a latency chain (entry -> voxels -> gather -> table edit), and four waves per block keep it short;
-//   * many blocks: one WAVE per block (4 KB = four 16-byte loads per lane), at most 5120 waves (five per SIMD; the
-//     active waves fill whole workgroups); wave w takes blocks w, w + 5120, ... -- dealt statically (a ticket counter
-//     was measured: 165 us, agent-scope atomics on one address are served one after the other).  min |sdf| / max weight are a
-//     wave reduction (no LDS, no barrier); lane 0 edits the table; the block's screen footprint is staged in LDS and
-//     blocks whose corners pass a range certificate take the packed arithmetic of integrate_block_certified (below).
-// Load j of lane l of a wave that holds a whole block: voxels 128 j + 2 l and + 1, i.e. x = 2l mod 8 (+1),
-// y = (l / 4) mod 8, z = 2j + l / 32 (delinearizeVoxelIndex, DSC/VoxelUtilHashSDF.h:313-318).
-template <bool PACKED>
-VHD void integrate_pair(const VhHashParams& hp, const VhDepthCameraParams& cp, const VhDepthCameraData& cam, const uint2* packed,
-                        uint32_t flags, I3 p0, uint4& raw, float& minSdf, uint32_t& maxW)
-{
-    Vox v0 = unpack_vox(make_uint2(raw.x, raw.y)), v1 = unpack_vox(make_uint2(raw.z, raw.w));
-    if (PACKED) {
-        v0 = integrate_voxel_packed(hp, cp, packed, p0, v0);
-        v1 = integrate_voxel_packed(hp, cp, packed, mki3(p0.x + 1, p0.y, p0.z), v1);
-    } else {
-        v0 = integrate_voxel(hp, cp, cam, p0, v0);
-        v1 = integrate_voxel(hp, cp, cam, mki3(p0.x + 1, p0.y, p0.z), v1);
-    }
-    // Pin the result words in VGPRs here.  Without this, hipcc (ROCm 7.2, gfx950, -O3) merges the "not integrated" path
-    // of the second voxel with a register that the gather has already overwritten (found by the parity tests: sdf of
-    // skipped odd voxels came back as the colour's MINF).
-    asm volatile("" : "+v"(v0.sdf), "+v"(v0.cw), "+v"(v1.sdf), "+v"(v1.cw));
-    if (flags & VH_FUSED_STARVE) { v0 = starve_voxel(v0); v1 = starve_voxel(v1); }
-    minSdf = fminf(minSdf, fminf(gc_key(v0), gc_key(v1)));
-    maxW = max(maxW, max(v0.weight(), v1.weight()));
-    const uint2 a = pack_vox(v0), c = pack_vox(v1);
-    raw = make_uint4(a.x, a.y, c.x, c.y);
-}
-
-// ---- the voxel pair of a lane as a two-vector: packed fp32 instructions (v_pk_mul/add/fma_f32: two IEEE operations per
-// issue slot; each component is the scalar instruction's result)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-VHD f32x2 both(float v) { return (f32x2){ v, v }; }
-VHD f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-// The reciprocal the compiler's own expansion of an fp32 division forms when v_div_scale_f32 leaves its operands alone:
-// v_rcp_f32 and one Newton step.
-VHD f32x2 rcp_refined2(f32x2 d)
-{
-    const f32x2 y0 = (f32x2){ __builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y) };
-    const f32x2 e = fma2(-d, y0, both(1.0f));
-    return fma2(e, y0, y0);
-}
-// n / d with y = rcp_refined2(d): the rest of that expansion (product, two residual corrections), instruction for
-// instruction, minus v_div_scale / v_div_fmas' scaling / v_div_fixup.  Those three only act when an operand is zero,
-// infinite, NaN or denormal, when |n| < 2^-103, when |d| >= 2^126 or when the exponents of n and d are 96 or more apart
-// (the ISA's v_div_scale_f32 cases); outside of that the result is the division's, bit for bit.  Callers guard the range.
-VHD f32x2 div_refined2(f32x2 n, f32x2 d, f32x2 y)
-{
-    f32x2 q = n * y;
-    f32x2 r = fma2(-d, q, n);
-    q = fma2(r, y, q);
-    r = fma2(-d, q, n);
-    return fma2(r, y, q);
-}
-
-// One block by one wave, the hot shape of the dense case: integrate_voxel_packed for the eight voxels of a lane (four
-// x-adjacent pairs) with ~60 instead of ~110 vector instructions per voxel.  Only for blocks the caller has certified:
-//   * the block's footprint is staged in LDS (tile, x0, y0, w, h);
-//   * at all eight CORNER voxels 2^-20 <= pf.z <= 2^20 and |pf.x fx|, |pf.y fy| <= 2^60.  Every voxel of the block then
-//     satisfies the same: each float operation of the transform is monotone in each of its operands, so pf.x, pf.y,
-//     pf.z and the two products, as computed, take their extremes over the block at corner voxels;
-//   * m_truncation > 0, m_truncScale >= 0 (so that a pixel that integrates has truncation > 0: the reference's
-//     two-sided clamp is then the median of {sdf, -truncation, truncation}).
-// What changes against the plain code, none of it in the results:
-//   * the two divisions by pf.z share one refined reciprocal (div_refined2; a numerator below 2^-60, where the
-//     argument above stops, gives a quotient below 2^-38 by either route, which the following "+ mx, + 0.5, truncate"
-//     cannot see);
-//   * the blend's division by the weight sum (1..510) takes the same route, with the exact division for any numerator
-//     outside [2^-100, 2^90) (never seen with voxels this library wrote; a crafted .hashgrid could hold one);
-//   * the pixel comes from the staged tile by an LDS read; a voxel that projects outside the staged box (not seen: the
-//     box is the hull of the corners' pixels and a margin) is gathered from the frame as before;
-//   * everything is written for the pair of a lane, so that the compiler can issue packed fp32.
-VHD void integrate_block_certified(const VhHashParams& hp, const VhDepthCameraParams& cp, const uint2* packed, const uint2* tile, uint32_t tileStride,
-                                   uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, int ex, int ey, int ez, uint32_t lane, uint32_t flags,
-                                   uint4 (&raw)[4], float& minSdf, uint32_t& maxW)
-{
-    // (The transform as values of this function's own: packed instructions want their uniform operands in vector registers,
-    // and copies shared with the kernel's other code paths live from the top of the kernel to its end -- the compiler
-    // parks them in scratch memory, a store per lane of every wave of the launch.)
-    float vs = hp.m_virtualVoxelSize;
-    float m[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) m[i] = hp.m_rigidTransformInverse[i];
-    asm volatile("" : "+s"(vs), "+s"(m[0]), "+s"(m[1]), "+s"(m[2]), "+s"(m[3]), "+s"(m[4]), "+s"(m[5]), "+s"(m[6]), "+s"(m[7]), "+s"(m[8]), "+s"(m[9]),
-                      "+s"(m[10]), "+s"(m[11]));
-    const int lx = (int)((2u * lane) & 7u), ly = (int)((lane >> 2) & 7u), lz0 = (int)(lane >> 5);
-    // vvp_to_world, mat_mul_p: ((m0 x + m1 y) + m2 z) + m3 per row; the first sum does not depend on z
-    const f32x2 xw = (f32x2){ (float)(ex * VH_SDF_BLOCK_SIZE + lx), (float)(ex * VH_SDF_BLOCK_SIZE + lx + 1) } * vs;
-    const float yw = (float)(ey * VH_SDF_BLOCK_SIZE + ly) * vs;
-    f32x2 ab[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) ab[r] = m[4 * r] * xw + both(m[4 * r + 1] * yw);
-    uint32_t maxCw = 0u;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const float zw = (float)(ez * VH_SDF_BLOCK_SIZE + 2 * j + lz0) * vs;
-        f32x2 pf[3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) pf[r] = (ab[r] + both(m[4 * r + 2] * zw)) + both(m[4 * r + 3] * 1.0f);
-        // cameraToKinectScreenInt: int((pf.x fx / pf.z + mx) + 0.5f), likewise y
-        const f32x2 y = rcp_refined2(pf[2]);
-        const f32x2 fsx = (div_refined2(pf[0] * cp.fx, pf[2], y) + cp.mx) + 0.5f;
-        const f32x2 fsy = (div_refined2(pf[1] * cp.fy, pf[2], y) + cp.my) + 0.5f;
-        uint2 px[2]; // the pixel of each voxel; weight byte 0: nothing to integrate (pack_pixel), or no pixel at all
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const uint32_t sx = (uint32_t)cvt_rz(fsx[k]), sy = (uint32_t)cvt_rz(fsy[k]);
-            const uint32_t tx = sx - x0, ty = sy - y0; // unsigned: a pixel left of / above the box wraps to a huge number
-            const bool inBox = (tx < w) & (ty < h);    // the box lies inside the image
-            // (one ballot per comparison: the ballot of their conjunction goes through a register and back)
-            const bool allInBox = (__builtin_amdgcn_ballot_w64(tx < w) & __builtin_amdgcn_ballot_w64(ty < h)) == ~0ull; // (every lane is active here)
-            // (as one indivisible 8-byte read: left alone the compiler splits it in two)
-            // (no clamp of the index: an LDS read beyond the workgroup's allocation returns zero, one inside it some other
-            // pixel, and the weight byte of a voxel outside the box is cleared below either way)
-            const unsigned long long t = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(&tile[__umul24(ty, tileStride) + tx]),
-                                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            px[k] = make_uint2((uint32_t)t, inBox ? (uint32_t)(t >> 32) : 0u);
-            if (__builtin_expect(!allInBox, 0)) {
-                if (!inBox && sx < cp.m_imageWidth && sy < cp.m_imageHeight) px[k] = packed[sy * cp.m_imageWidth + sx];
-            }
-        }
-        // integrateDepthMapKernel :447-472 and combineVoxel :229-250 (apply_pixel / combine_voxel above) for the pair
-        const Vox s0 = unpack_vox(make_uint2(raw[j].x, raw[j].y)), s1 = unpack_vox(make_uint2(raw[j].z, raw[j].w));
-        const f32x2 depth = (f32x2){ __uint_as_float(px[0].x), __uint_as_float(px[1].x) };
-        const f32x2 sdf = depth - pf[2];
-        const f32x2 truncation = both(hp.m_truncation) + hp.m_truncScale * depth;
-        const bool use0 = ((px[0].y >> 24) != 0u) & (sdf.x > -truncation.x);
-        const bool use1 = ((px[1].y >> 24) != 0u) & (sdf.y > -truncation.y);
-        const f32x2 clamped = (f32x2){ __builtin_amdgcn_fmed3f(sdf.x, -truncation.x, truncation.x), __builtin_amdgcn_fmed3f(sdf.y, -truncation.y, truncation.y) };
-        const f32x2 wOld = (f32x2){ (float)(s0.cw >> 24), (float)(s1.cw >> 24) }, wNew = (f32x2){ (float)(px[0].y >> 24), (float)(px[1].y >> 24) };
-        const f32x2 num = (f32x2){ s0.sdf, s1.sdf } * wOld + clamped * wNew;
-        const f32x2 den = wOld + wNew; // exact: integers up to 510
-        const f32x2 yDen = rcp_refined2(den);
-        f32x2 q = div_refined2(num, den, yDen);
-        const bool odd0 = use0 & !((fabsf(num.x) >= 0x1p-100f) & (fabsf(num.x) < 0x1p90f));
-        const bool odd1 = use1 & !((fabsf(num.y) >= 0x1p-100f) & (fabsf(num.y) < 0x1p90f));
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(odd0 | odd1) != 0ull, 0)) {
-            if (odd0) q.x = num.x / den.x;
-            if (odd1) q.y = num.y / den.y;
-        }
-        Vox v[2];
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const Vox st = k ? s1 : s0;
-            // colour: the byte-wise average rounded up (combine_voxel) is v_lerp_u8 with the rounding bit set; the weight
-            // byte comes in by v_perm_b32 (the top byte of the average is not used)
-            // (m_colorIntegration: the average weighted by the voxel weights instead, with the reciprocal of the sdf's
-            // division; the same for every voxel of the launch, a scalar branch)
-            uint32_t rgb = __builtin_amdgcn_lerp(st.cw, px[k].y, 0x01010101u);
-            if (hp.m_colorIntegration != VH_COLOR_RUNNING_AVERAGE) rgb = weighted_colour(st.cw, px[k].y, den[k], yDen[k]);
-            const uint32_t wSum = min(hp.m_integrationWeightMax, (st.cw >> 24) + (px[k].y >> 24));
-            const bool use = k ? use1 : use0;
-            v[k].sdf = use ? q[k] : st.sdf;
-            v[k].cw = use ? __builtin_amdgcn_perm(wSum, rgb, 0x04020100u) : st.cw;
-        }
-        if (flags & VH_FUSED_STARVE) { v[0] = starve_voxel(v[0]); v[1] = starve_voxel(v[1]); }
-        minSdf = fminf(minSdf, fminf(gc_key(v[0]), gc_key(v[1])));
-        maxCw = max(maxCw, max(v[0].cw, v[1].cw)); // the weight is the top byte: the largest word has the largest weight
-        const uint2 a = pack_vox(v[0]), c = pack_vox(v[1]);
-        raw[j] = make_uint4(a.x, a.y, c.x, c.y);
-    }
-    maxW = max(maxW, maxCw >> 24);
-}
-
-constexpr uint32_t kIntegrateWavesMost = 5120; // waves that take blocks when there are many: five per SIMD
-// The kernel's one argument.  The pass that frees a block (a handful of blocks per frame, one lane each) wants a dozen
-// table pointers and sizes that nothing else in the kernel needs; as ordinary kernel arguments they are loaded at the top
-// of the kernel and kept in scalar registers throughout -- or, as measured, parked in scratch memory by every wave of
-// the launch (4.5 MB of stores per launch at cfg2).  cold_args() hands that pass the argument block as memory the
-// compiler knows nothing about, so it loads what it needs where it needs it.
-struct FusedArgs {
-    VhHashData hd;
-    VhHashParams hp;
-    VhDepthCameraData cam;
-    VhDepthCameraParams cp;
-    uint32_t flags;
-    int32_t lockToken;
-    uint32_t* countMirror;
-    uint32_t mirrorTag;
-    const uint2* packed;
-};
-// A rider waits for a flag another rider of the launch raises (rider_done): VH_RIDER_DONE_COUNTERS copies 128 bytes apart, set
-// to a number that only grows (compared modulo 2^32).  An exit every wave reaches: after ~1 s of polling the wait gives up
-// (never seen; the caller says so in the status words and the grid drains whatever happens).  Every lane of the wave calls it.
-VHD bool rider_wait(const uint32_t* flags, uint32_t expected)
-{
-    const uint32_t* const flag = flags + (blockIdx.x % VH_RIDER_DONE_COUNTERS) * 32u;
-    for (uint32_t polls = 0; polls < (1u << 22); polls++) {
-        const uint32_t v = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (the same word for every lane: one request)
-        if ((int32_t)(v - expected) >= 0) return true;
-        __builtin_amdgcn_s_sleep(4);
-    }
-    return false;
-}
-template <uint32_t KERNARG_OFFSET> // where the kernel's argument block holds the FusedArgs (0: it is the kernel's only argument)
-VHD const FusedArgs* cold_args()
-{
-    typedef const char __attribute__((address_space(4))) * KernargPtr;
-    KernargPtr p = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr() + KERNARG_OFFSET;
-    asm volatile("" : "+s"(p));
-    return (const FusedArgs*)p;
-}
-template <uint32_t KERNARG_OFFSET>
-VHD bool free_block_cold(int ex, int ey, int ez, uint32_t lane) // every lane of the wave calls it
-{
-    const FusedArgs* a = cold_args<KERNARG_OFFSET>();
-    const VhHashData hd = a->hd;
-    const VhHashParams hp = a->hp;
-    // (As a rider of k_compute_normals the pass frees blocks while that launch's splat workgroups read the table.  That needs no
-    // order: the delete never moves an entry -- it overwrites the freed one with one 16-byte store, clears counters and unlinks --
-    // and the splat reads every slot once, so it lists every live block, and the freed one or not.  Either is what the splat made
-    // BEFORE the pass, in a launch of its own, always was for the ray cast that uses it: a freed block that is still listed
-    // has all-zero voxels by then (weight 0: no sample reads it), see CoSplat.)
-    return delete_hash_entry_element_wave(hd, hp, mki3(ex, ey, ez), a->lockToken, lane);
-}
-
-// the fused pass's shared memory (a kernel that carries the pass as a rider overlays it with its other riders')
-template <bool PACKED>
-struct FusedShared {
-    float sMin[4];
-    uint32_t sMax[4];
-    int sFreed;
-    __attribute__((aligned(16))) uint2 sTile[PACKED ? 256 / kWave : 1][PACKED ? kIntegrateTileRows * kIntegrateTileStride : 2];
-};
-
-// One block by one workgroup, a voxel pair per thread: the pass's shape for up to 2048 blocks (integrate_fused_body), and the
-// pass as a rider of k_compute_normals (pass_rider_group).  q: the block's entry, b: its place in the list.
-template <bool PACKED, uint32_t KERNARG_OFFSET, class Shared> // Shared: a FusedShared (its sMin, sMax, sFreed)
-VHD void integrate_block_by_workgroup(const FusedArgs& args, Shared& sh, const int4 q, const uint32_t b, const float thr)
-{
-    const VhHashData& hd = args.hd;
-    const VhHashParams& hp = args.hp;
-    const uint32_t flags = args.flags;
-    const uint32_t lane = lane_id();
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 43 // measurement build: every workgroup's life in this shape, read by tools/integrate_stamps.py
-    const uint32_t stampA = (uint32_t)__builtin_amdgcn_s_memrealtime();
-    uint32_t stampB = 0u, stampFreed = 0u;
-#endif
-    const uint32_t t = threadIdx.x;
-    const int ex = __builtin_amdgcn_readfirstlane(q.x), ey = __builtin_amdgcn_readfirstlane(q.y);
-    const int ez = __builtin_amdgcn_readfirstlane(q.z), ptr = __builtin_amdgcn_readfirstlane(q.w);
-    uint4* vp = reinterpret_cast<uint4*>(&hd.d_SDFBlocks[(uint32_t)ptr]) + t;
-    uint4 raw = *vp;
-    // voxel pair (2t, 2t+1): x = (2t)%8 (+1), y = (2t%64)/8, z = 2t/64
-    const I3 p0 = mki3(ex * VH_SDF_BLOCK_SIZE + (int)((2u * t) & 7u), ey * VH_SDF_BLOCK_SIZE + (int)(((2u * t) & 63u) >> 3), ez * VH_SDF_BLOCK_SIZE + (int)((2u * t) >> 6));
-    float minSdf = pinf();
-    uint32_t maxW = 0u;
-    integrate_pair<PACKED>(hp, args.cp, args.cam, args.packed, flags, p0, raw, minSdf, maxW);
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 43
-    asm volatile("" : "+v"(raw.x));
-    stampB = (uint32_t)__builtin_amdgcn_s_memrealtime();
-#endif
-    if (flags & VH_FUSED_GC) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            minSdf = fminf(minSdf, __shfl_xor(minSdf, o));
-            maxW = max(maxW, (uint32_t)__shfl_xor((int)maxW, o));
-        }
-        if (lane == 0) { sh.sMin[wave] = minSdf; sh.sMax[wave] = maxW; }
-        __syncthreads();
-        minSdf = fminf(fminf(sh.sMin[0], sh.sMin[1]), fminf(sh.sMin[2], sh.sMin[3]));
-        maxW = max(max(sh.sMax[0], sh.sMax[1]), max(sh.sMax[2], sh.sMax[3]));
-        const bool decide = (minSdf >= thr) || (maxW == 0u); // the same in every thread of the workgroup
-        if (t == 0) hd.d_hashDecision[b] = decide ? 1 : 0;
-        if (decide) {
-            if (wave == 0u) {
-                const bool f = free_block_cold<KERNARG_OFFSET>(ex, ey, ez, lane);
-                if (lane == 0u) sh.sFreed = f ? 1 : 0;
-            }
-            __syncthreads();
-            if (sh.sFreed != 0) raw = make_uint4(0u, 0u, 0u, 0u);
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 43
-            stampFreed = 1u + (uint32_t)sh.sFreed;
-#endif
-        }
-    }
-    *vp = raw;
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 43
-    if (t == 0) reinterpret_cast<uint4*>(hd.d_hashCompactified)[(hp.m_hashNumBuckets * VH_HASH_BUCKET_SIZE) / 2u + b] = make_uint4(stampA, stampB, (uint32_t)__builtin_amdgcn_s_memrealtime(), 0x57430000u | stampFreed);
-#endif
-}
-
-// The pass in a launch of its own (k_integrate_fused), as a function of (workgroup index, number of workgroups).  As a rider of
-// k_compute_normals it is pass_rider_group (below), which shares the workgroup-per-block code above.
-template <bool PACKED, uint32_t KERNARG_OFFSET>
-VHD void integrate_fused_body(const FusedArgs& args, const uint32_t groupIdx, const uint32_t numGroups, FusedShared<PACKED>& sh)
-{
-    const VhHashData& hd = args.hd;
-    const VhHashParams& hp = args.hp;
-    const VhDepthCameraData& cam = args.cam;
-    const VhDepthCameraParams& cp = args.cp;
-    const uint32_t flags = args.flags;
-    uint32_t* const countMirror = args.countMirror;
-    const uint32_t mirrorTag = args.mirrorTag;
-    const uint2* const packed = args.packed;
-    float (&sMin)[4] = sh.sMin;
-    uint32_t (&sMax)[4] = sh.sMax;
-    int& sFreed = sh.sFreed;
-    auto& sTile = sh.sTile;
-    const uint32_t lane = lane_id();
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-    const uint32_t nEntries = hp.m_hashNumBuckets * VH_HASH_BUCKET_SIZE;
-    // the count and the entry this workgroup / wave would start with in one trip (the list is Ne entries long: reading
-    // beyond the count is reading stale entries, which are not used)
-    const uint32_t count = (uint32_t)hd.d_hashCompactifiedCounter[0];
-    // first block of this wave when waves take blocks: the active waves fill whole workgroups (the others leave at
-    // once and free their slot: a workgroup's LDS and registers are held until its last wave is done)
-    const uint32_t wFirst = groupIdx * (256u / kWave) + wave;
-    int4 qg = make_int4(0, 0, 0, 0), qw = make_int4(0, 0, 0, 0);
-    uint4 boxw = make_uint4(0u, 0u, 0u, 0u); // the entry's second half: {offset, box, box, tag} (compactify_group)
-    if (groupIdx < nEntries) qg = load_quad(&hd.d_hashCompactified[groupIdx]);
-    if (wFirst < nEntries) {
-        qw = load_quad(&hd.d_hashCompactified[wFirst]);
-        if (PACKED) boxw = list_box<false>(&hd.d_hashCompactified[wFirst]);
-    }
-    // host-visible copy of the block count and the caller's tag (mapped pinned memory): replaces a per-frame
-    // device->host copy, and lets the host see how far the device has come
-    if (countMirror && groupIdx == 0 && threadIdx.x == 0) *reinterpret_cast<uint2*>(countMirror) = make_uint2(count, mirrorTag);
-    const float thr = get_truncation(hp, cp.m_sensorDepthWorldMax);
-
-    if (count <= numGroups) {
-        // ---- one workgroup per block
-        if (groupIdx < count) integrate_block_by_workgroup<PACKED, KERNARG_OFFSET>(args, sh, qg, groupIdx, thr);
-        return;
-    }
-
-    // ---- one wave per block: the first min(count, 5120) waves (five per SIMD; the hardware deals workgroups to the
-    // compute units evenly) take blocks w, w + 5120, ...: no SIMD gets more than a block or two above the mean.
-    // Measured and dropped: ceil(count / rounds) waves with `rounds` blocks each (SIMDs with five waves finished 3 us
-    // after those with four: 27 us for 8 600 blocks), and a ticket counter (agent-scope atomics on one address are
-    // served at the memory side of the eight L2s, ~12 ns each: 165 us).
-    const uint32_t nActive = min(min(count, kIntegrateWavesMost), numGroups * (256u / kWave));
-    if (wFirst >= nActive) return;
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 9 // measurement build: shader clock over one wave's lifetime
-    const uint64_t stampC0 = __builtin_amdgcn_s_memtime(), stampR0 = __builtin_amdgcn_s_memrealtime();
-    uint32_t stamps[6] = { 0u, 0u, 0u, 0u, 0u, 0u }, stampN = 0u; // per block: staged, voxels arrived, computed (two blocks)
-#endif
-    uint32_t b = wFirst, round = 0u;
-    // this wave's place in the later rounds: the SIMD it sits on (unit g mod 256, wave of the workgroup) bit-reversed, then
-    // the workgroup's turn on that unit -- a permutation of 0 .. 5119 whose every prefix is spread evenly over the SIMDs
-    // (used as is when all 5 120 waves are active; with fewer waves, which happens below 5 120 blocks, there is one round)
-    const uint32_t simdOfMachine = ((groupIdx & 255u) << 2) | wave; // (as a rider the workgroups sit elsewhere: the order is then only a permutation)
-    const uint32_t scattered = nActive == kIntegrateWavesMost ? (__brev(simdOfMachine) >> 22) + (groupIdx >> 8) * 1024u : wFirst;
-    int4 q = qw;
-    uint4 qbox = boxw;
-    uint2* tile = sTile[wave];
-    const uint32_t tagNow = frame_tag(hp, cp);
-    for (;;) {
-        // What depends on the lane alone is formed again for every block (a dozen cheap instructions): hoisted out of the
-        // loop it is a dozen registers that live through everything, and the compiler parks them in scratch memory.
-        uint32_t lane = lane_id();
-        asm volatile("" : "+v"(lane));
-        const int lx = (int)((2u * lane) & 7u), ly = (int)((lane >> 2) & 7u), lz0 = (int)(lane >> 5);
-        const int ex = __builtin_amdgcn_readfirstlane(q.x), ey = __builtin_amdgcn_readfirstlane(q.y);
-        const int ez = __builtin_amdgcn_readfirstlane(q.z), ptr = __builtin_amdgcn_readfirstlane(q.w);
-        uint4* vp = reinterpret_cast<uint4*>(&hd.d_SDFBlocks[(uint32_t)ptr]) + lane;
-        uint4 raw[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) raw[j] = vp[j * kWave];
-        const uint32_t boxA = (uint32_t)__builtin_amdgcn_readfirstlane((int)qbox.y), boxB = (uint32_t)__builtin_amdgcn_readfirstlane((int)qbox.z);
-        const uint32_t boxTag = (uint32_t)__builtin_amdgcn_readfirstlane((int)qbox.w);
-        // The wave's next block.  Rounds of nActive blocks; within a round the blocks go to the waves in an order that
-        // scatters a partial last round over the compute units (workgroup g sits on unit g mod 256: with the plain order
-        // w + round * nActive the first units get all of the last round's blocks -- 36 blocks against 32 at 8 600).
-        round += 1u;
-        const uint32_t bNext = round * nActive + scattered;
-        const bool hasNext = scattered < nActive && bNext < count;
-        if (hasNext) { // its entry (both halves) behind this block's voxels
-            q = load_quad(&hd.d_hashCompactified[bNext]);
-            if (PACKED) qbox = list_box<false>(&hd.d_hashCompactified[bNext]);
-        }
-        // (Requesting the next block's voxels here as well was measured: slower.  The waves do not wait for the stream --
-        // the kernel is bound by instruction issue, ~1000 vector instructions per block at 4 cycles each.)
-
-        float minSdf = pinf();
-        uint32_t maxW = 0u;
-        bool wrote = false; // the plain code has put the block back itself
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 1 // measurement build: the voxel stream alone (read, write back)
-        if (false) {
-#else
-        if (PACKED) {
-#endif
-            // A voxel's gather from the frame is one cache access per LANE -- 64 tag look-ups per wave instruction, the
-            // bound of this shape before staging (1 cm voxels: 13 us of a 33 us launch).  So the block's screen
-            // footprint is staged in LDS first, four image rows per load instruction (whole lines), while the voxel
-            // loads are in flight.  The box comes with the block's entry (block_box, worked out by the compactify pass
-            // for this very transform: the tag says so; a list made for another one goes through the plain code, every
-            // voxel gathered from the frame).  A voxel that projects outside the staged box all the same is gathered
-            // from the frame itself: the box decides where a pixel is read, never which.
-            BlockBox bb;
-            bb.x0 = boxA & 0xffffu; bb.y0 = boxA >> 16;
-            bb.w = boxB & 0xffu; bb.h = (boxB >> 8) & 0xffu;
-            bb.flags = boxTag == tagNow ? boxB >> 16 : 0u; // a box made for another transform: neither staged nor certified
-            // (a box that does not fit this image -- it cannot come from block_box for this frame -- is not used)
-            const bool staged = (bb.flags & VH_BOX_STAGED) != 0u && bb.w <= kIntegrateTile && bb.h <= kIntegrateTileRows && (bb.x0 & 1u) == 0u &&
-                                bb.x0 + bb.w <= cp.m_imageWidth && bb.y0 + bb.h <= cp.m_imageHeight && (cp.m_imageWidth & 1u) == 0u;
-            const uint32_t x0 = bb.x0, y0 = bb.y0;
-            const uint32_t w = staged ? bb.w : 0u, h = staged ? bb.h : 0u;
-            if (staged) {
-                // lane -> (row r + lane / 16, pixels 2 (lane % 16) and + 1): four rows per load instruction.  An even image
-                // width and an even x0 keep a pixel pair inside its row.
-                const uint32_t col2 = (lane & 15u) * 2u, rowInQuad = lane >> 4;
-                const uint4* src = reinterpret_cast<const uint4*>(packed + (size_t)(y0 + rowInQuad) * cp.m_imageWidth + x0 + col2);
-                uint4* dst = reinterpret_cast<uint4*>(tile + rowInQuad * kIntegrateTileStride + col2);
-                __builtin_amdgcn_wave_barrier(); // the previous block's reads of the tile are done (they fed its stores)
-#pragma unroll 4
-                for (uint32_t r = 0; r < h; r += 4u) {
-                    if (r + rowInQuad < h && col2 < w) dst[(size_t)r * (kIntegrateTileStride / 2u)] = src[(size_t)r * (cp.m_imageWidth / 2u)];
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
-#if !defined(VH_INTEGRATE_PLAIN) // (measurement / test builds: every block through the plain code)
-            const bool certified = staged && (bb.flags & VH_BOX_CERTIFIED) != 0u && hp.m_truncation > 0.0f && hp.m_truncScale >= 0.0f;
-#else
-            const bool certified = false;
-#endif
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 9
-            if (stampN < 6u) stamps[stampN++] = (uint32_t)__builtin_amdgcn_s_memrealtime(); // staged
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (stampN < 6u) stamps[stampN++] = (uint32_t)__builtin_amdgcn_s_memrealtime(); // voxels here
-#endif
-            if (__builtin_amdgcn_readfirstlane(certified ? 1 : 0) != 0) {
-                integrate_block_certified(hp, cp, packed, tile, kIntegrateTileStride, x0, y0, w, h, ex, ey, ez, lane, flags, raw, minSdf, maxW);
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 9
-                asm volatile("" : "+v"(raw[3].x), "+v"(raw[0].x));
-                if (stampN < 6u) stamps[stampN++] = (uint32_t)__builtin_amdgcn_s_memrealtime(); // computed
-#endif
-            } else {
-                // The plain code, for the blocks without a certificate or a staged footprint (near the camera, behind it,
-                // on the image's edge): a compact loop that takes its voxels from memory again and puts them back itself.
-                // Unrolled and on the registers of the loads above it costs the whole kernel 30 registers and its
-                // fifth wave per SIMD (measured: 99 against 65); the voxels are in the cache.
-                wrote = true;
-#pragma unroll 1
-                for (int j = 0; j < 4; j++) {
-                    const uint4 r = vp[j * kWave];
-                    Vox v[2] = { unpack_vox(make_uint2(r.x, r.y)), unpack_vox(make_uint2(r.z, r.w)) };
-#pragma unroll
-                    for (int k = 0; k < 2; k++) {
-                        uint32_t sx, sy;
-                        float pz;
-                        if (project_voxel(hp, cp, mki3(ex * VH_SDF_BLOCK_SIZE + lx + k, ey * VH_SDF_BLOCK_SIZE + ly, ez * VH_SDF_BLOCK_SIZE + 2 * j + lz0), sx, sy, pz)) {
-                            const uint32_t tx = sx - x0, ty = sy - y0; // unsigned: a pixel left of / above the box wraps to a huge number
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 2 // measurement build: projection only
-                            v[k].cw ^= (tx + ty + __float_as_uint(pz)) & 1u;
-#elif defined(VH_KNOCKOUT) && VH_KNOCKOUT == 3 // measurement build: projection + the pixel, no blend
-                            const uint2 px = (tx < w && ty < h) ? tile[ty * kIntegrateTileStride + tx] : packed[sy * cp.m_imageWidth + sx];
-                            v[k].cw ^= (px.x + px.y + __float_as_uint(pz)) & 1u;
-#else
-                            const uint2 px = (tx < w && ty < h) ? tile[ty * kIntegrateTileStride + tx] : packed[sy * cp.m_imageWidth + sx];
-                            v[k] = apply_pixel(hp, px, pz, v[k]);
-#endif
-                        }
-                    }
-                    asm volatile("" : "+v"(v[0].sdf), "+v"(v[0].cw), "+v"(v[1].sdf), "+v"(v[1].cw)); // see integrate_pair
-                    if (flags & VH_FUSED_STARVE) { v[0] = starve_voxel(v[0]); v[1] = starve_voxel(v[1]); }
-                    minSdf = fminf(minSdf, fminf(gc_key(v[0]), gc_key(v[1])));
-                    maxW = max(maxW, max(v[0].weight(), v[1].weight()));
-                    const uint2 a = pack_vox(v[0]), c = pack_vox(v[1]);
-                    vp[j * kWave] = make_uint4(a.x, a.y, c.x, c.y);
-                }
-            }
-        } else {
-#if !(defined(VH_KNOCKOUT) && VH_KNOCKOUT == 1)
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                integrate_pair<PACKED>(hp, cp, cam, packed, flags, mki3(ex * VH_SDF_BLOCK_SIZE + lx, ey * VH_SDF_BLOCK_SIZE + ly, ez * VH_SDF_BLOCK_SIZE + 2 * j + lz0),
-                                       raw[j], minSdf, maxW);
-#endif
-        }
-        bool freed = false;
-        if (flags & VH_FUSED_GC) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                minSdf = fminf(minSdf, __shfl_xor(minSdf, o));
-                maxW = max(maxW, (uint32_t)__shfl_xor((int)maxW, o));
-            }
-            const bool decide = (minSdf >= thr) || (maxW == 0u);
-            if (lane == 0) hd.d_hashDecision[b] = decide ? 1 : 0;
-            // (the same decision in every lane: the reduction left every lane with the block's minimum and maximum)
-            if (__builtin_amdgcn_readfirstlane(decide ? 1 : 0) != 0) freed = free_block_cold<KERNARG_OFFSET>(ex, ey, ez, lane);
-        }
-        if (freed) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) vp[j * kWave] = make_uint4(0u, 0u, 0u, 0u);
-        } else if (!wrote) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) vp[j * kWave] = raw[j];
-        }
-        if (!hasNext) break;
-        b = bNext;
-    }
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 9
-    if (wFirst == 0u && lane == 0u) {
-        const uint64_t c = __builtin_amdgcn_s_memtime() - stampC0, r = __builtin_amdgcn_s_memrealtime() - stampR0;
-        hd.d_state[8] = (uint32_t)c; hd.d_state[9] = (uint32_t)r; hd.d_state[10] = (count + nActive - 1u) / nActive; hd.d_state[11] = nActive;
-    }
-    if (lane == 0u) { // every wave's life in the unused upper half of the compactified list: {start, end (100 MHz ticks), hardware id, xcc id}
-        const uint32_t hwid = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        reinterpret_cast<uint4*>(hd.d_hashCompactified)[nEntries / 2u + 3u * wFirst] =
-            make_uint4((uint32_t)stampR0, (uint32_t)__builtin_amdgcn_s_memrealtime(), hwid, xcc);
-        reinterpret_cast<uint4*>(hd.d_hashCompactified)[nEntries / 2u + 3u * wFirst + 1u] = make_uint4(stamps[0], stamps[1], stamps[2], stamps[3]);
-        reinterpret_cast<uint4*>(hd.d_hashCompactified)[nEntries / 2u + 3u * wFirst + 2u] = make_uint4(stamps[4], stamps[5], 0u, 0u);
-    }
-#endif
-}
-
-template <bool PACKED>
-__global__ __launch_bounds__(256)
-void k_integrate_fused(FusedArgs args)
-{
-    __shared__ FusedShared<PACKED> sh;
-    integrate_fused_body<PACKED, 0u>(args, blockIdx.x, gridDim.x, sh);
-}
-
-__global__ __launch_bounds__(256) void k_starve(VhHashData hd, VhHashParams hp)
-{
-    const uint32_t b = blockIdx.x;
-    if (b >= hp.m_numOccupiedBlocks) return;
-    const int ptr = __builtin_amdgcn_readfirstlane(load_quad(&hd.d_hashCompactified[b]).w);
-    uint4* vp = reinterpret_cast<uint4*>(&hd.d_SDFBlocks[(uint32_t)ptr]) + threadIdx.x;
-    uint4 raw = *vp;
-    Vox v0 = starve_voxel(unpack_vox(make_uint2(raw.x, raw.y))), v1 = starve_voxel(unpack_vox(make_uint2(raw.z, raw.w)));
-    raw.y = v0.cw; raw.w = v1.cw;
-    *vp = raw;
-}
-
-__global__ __launch_bounds__(256) void k_gc_identify(VhHashData hd, VhHashParams hp, VhDepthCameraParams cp)
-{
-    __shared__ float sMin[4];
-    __shared__ uint32_t sMax[4];
-    const uint32_t b = blockIdx.x;
-    if (b >= hp.m_numOccupiedBlocks) return;
-    const int ptr = __builtin_amdgcn_readfirstlane(load_quad(&hd.d_hashCompactified[b]).w);
-    const uint4 raw = *(reinterpret_cast<const uint4*>(&hd.d_SDFBlocks[(uint32_t)ptr]) + threadIdx.x);
-    const Vox v0 = unpack_vox(make_uint2(raw.x, raw.y)), v1 = unpack_vox(make_uint2(raw.z, raw.w));
-    float minSdf = fminf(gc_key(v0), gc_key(v1));
-    uint32_t maxW = max(v0.weight(), v1.weight());
-    block_min_max(minSdf, maxW, sMin, sMax);
-    if (threadIdx.x == 0) {
-        const float thr = get_truncation(hp, cp.m_sensorDepthWorldMax);
-        hd.d_hashDecision[b] = ((minSdf >= thr) || (maxW == 0u)) ? 1 : 0;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_gc_free(VhHashData hd, VhHashParams hp, int32_t lockToken)
-{
-    __shared__ int sFreed;
-    const uint32_t b = blockIdx.x;
-    if (b >= hp.m_numOccupiedBlocks) return;
-    if (hd.d_hashDecision[b] == 0) return; // block-uniform
-    const int4 q = load_quad(&hd.d_hashCompactified[b]);
-    if (threadIdx.x == 0) sFreed = delete_hash_entry_element(hd, hp, mki3(q.x, q.y, q.z), lockToken) ? 1 : 0;
-    __syncthreads();
-    if (sFreed) {
-        const int ptr = __builtin_amdgcn_readfirstlane(q.w);
-        *(reinterpret_cast<uint4*>(&hd.d_SDFBlocks[(uint32_t)ptr]) + threadIdx.x) = make_uint4(0u, 0u, 0u, 0u);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// ray-interval splatting as a compute pass (the reference rasterises block quads with D3D11 into min/max depth
-// textures, DSC/DX11RayIntervalSplatting.cpp:150-220 + rayIntervalSplatKernel DSC/CUDARayCastSDF.cu:101-167, and
-// this fork then ignores them: DSC/CUDARayCastSDF.cu:36-42).  Here every ALLOCATED block (not only the ones the
-// approximate frustum test keeps) is projected, one wave per block, and folded into the 8x8-pixel tiles it can
-// matter to:
-//   * head {min depth, max depth, count}: camera-depth range of those blocks (positive float bits: uint order =
-//     float order) and how many there are;
-//   * list: their {block position, voxel pointer}, up to `cap` per tile.
-// Both are conservative supersets, so rendering with them cannot change a result: a sample reads voxels within one
-// voxel of its position (two for the gradient), the box of a block is grown by more than that, and a perspective
-// projection maps a box in front of the camera into the hull of its projected corners.  A tile whose list is
-// complete therefore knows every block its rays can read: k_render resolves block -> pointer in LDS instead of
-// probing the hash table in HBM (and a block missing from the list is unallocated, as a failed probe would say).
-// ---------------------------------------------------------------------------
-
-constexpr uint32_t kSplatWordsPerGroup = 32; // occupancy words (x32 buckets) per workgroup
-constexpr uint32_t kSplatQueue = 128;        // blocks a workgroup queues per round
-
-// (i / nx, i % nx) for i < 2^22 without the integer-division sequence: float estimate, corrected by one step
-VHD void divmod_small(uint32_t i, uint32_t nx, float rnx, uint32_t& q, uint32_t& r)
-{
-    q = (uint32_t)((float)i * rnx);
-    int rem = (int)i - (int)(q * nx);
-    if (rem < 0) { q--; rem += (int)nx; }
-    if (rem >= (int)nx) { q++; rem -= (int)nx; }
-    r = (uint32_t)rem;
-}
-
-// Three steps per workgroup, each one trip to memory: occupancy words -> bucket queue (LDS); slots of the queued
-// buckets -> block queue (LDS); one wave per queued block folds it into its tiles.  The queues balance the waves: a
-// block costs a wave a few thousand cycles, and the kernel is as long as its busiest wave.
-// Cost of a tile in units of one empty-space step; a full sample (8 taps) weighs kCostSample of them.  The wave's
-// cost is its busiest lane's: k_render stores the tile's cost class for the next frame's launch order.
-constexpr uint32_t kCostSample = 6;
-constexpr uint32_t kCostClasses = 32;
-constexpr uint32_t kCostClassWidth = 8;
-// The dearest tiles of a frame are marched by TWO waves of one workgroup, each one half of the tile's depth interval:
-// a wave alone on its SIMD runs at the pace of its own chain of dependent loads, and the few tiles with the longest
-// rays (a silhouette grazing the truncation band) are the tail of the kernel.  A sample's state is the previous
-// sample's alone, so the far half starts at the last sample before the middle with nothing remembered and arrives at
-// the middle in the state the whole march would have; the near half's hit, if any, is the first along the ray.
-#ifndef VH_SPLIT_TILES
-#define VH_SPLIT_TILES 256
-#endif
-constexpr uint32_t kSplitTiles = VH_SPLIT_TILES;     // at most (even: two split tiles fill a workgroup); measured at 640x480: 64 -> 37.8 us, 256 -> 37.0, 512 -> 37.8
-constexpr uint32_t kSplitMinTiles = 1024; // smaller images are not split
-__host__ __device__ inline uint32_t split_tiles(uint32_t nTiles) // one tile in sixteen, dearest first
-{
-#ifndef VH_SPLIT_DIV
-#define VH_SPLIT_DIV 16
-#endif
-    const uint32_t n = (nTiles / VH_SPLIT_DIV) & ~1u;
-    return nTiles >= kSplitMinTiles ? (n < kSplitTiles ? n : kSplitTiles) : 0u;
-}
-
-// Launch order of the next k_render (one workgroup of k_interval_splat, beside the others): tiles sorted by the cost
-// class the previous k_render stored, dearest first, dealt to the workgroups (4 tiles each) in rows of numCUs that
-// alternate direction.  The hardware places workgroup g on compute unit g mod numCUs (all of them are resident), so
-// a compute unit receives one workgroup of every row: the dearest of one row with the cheapest of the next.
-// The sort was ONE workgroup's and the longest chain of its launch (per-workgroup time stamps, tools/riders_stamps.py: it
-// ended at 8.4 us of a 9.9 us launch at 640x480, at 50 of 50 us at 1920x1080, everything else long done).  Now kSchedGroups
-// workgroups sort a share of the tiles each -- the quads of four tiles q = part (mod parts): shares that look alike --
-// and deal their sorted shares into the launch order in turns (the tile of rank i in share w comes after rank i of the
-// shares before it): the dearest first as before, to within the difference between the shares.
-constexpr uint32_t kSchedGroups = 8;
-__host__ __device__ inline uint32_t sched_groups(uint32_t nTiles) { return nTiles >= kSplitMinTiles ? kSchedGroups : 1u; }
-
-__device__ void schedule_tiles(uint32_t* sched, uint32_t* feedback, uint32_t nTiles, uint32_t phase, uint32_t numCUs, uint32_t part, uint32_t parts,
-                               uint32_t* sCount /*[2 * 256]*/)
-{
-    // layout: {phase the slots were made for, -, -, -}, cost class per tile, {tile, phase} per launch slot
-    const uint32_t* cls = sched + 4;
-    uint2* slots = reinterpret_cast<uint2*>(sched + 4 + 4u * ((nTiles + 3u) / 4u));
-    const uint32_t nSplit = split_tiles(nTiles);
-    if (threadIdx.x == 0 && part == 0u) {
-        sched[0] = phase;
-        if (feedback) *feedback = sched[1]; // longest tile list the previous k_render met (0: none near the small capacity)
-        sched[1] = 0u;
-    }
-    // counting sort with kSub sub-bins per class (keyed by the thread): 64 lanes adding to one LDS word serialise
-    constexpr uint32_t kSub = 8, kBins = kCostClasses * kSub;
-    static_assert(kBins == 4u * kWave, "the scan below gives four bins to each lane of one wave");
-    for (uint32_t i = threadIdx.x; i < 2u * kBins; i += blockDim.x) sCount[i] = 0u;
-    __syncthreads();
-    const uint32_t sub = threadIdx.x % kSub;
-    // four tiles per load, kBatch loads in flight: this workgroup is alone with its trips to memory
-    constexpr uint32_t kBatch = 5;
-    const uint32_t nQuads = (nTiles + 3u) / 4u; // the cost array is padded to whole quads (vh_render_schedule_bytes)
-    const uint4* cls4 = reinterpret_cast<const uint4*>(cls);
-    const uint32_t myQuads = part < nQuads ? (nQuads - part + parts - 1u) / parts : 0u; // quads part, part + parts, ...
-    // tiles in each share (the image's last quad may be short), for the turn-taking below
-    uint32_t nShare[kSchedGroups];
-#pragma unroll
-    for (uint32_t w = 0; w < kSchedGroups; w++) {
-        const uint32_t nq = (w < parts && w < nQuads) ? (nQuads - w + parts - 1u) / parts : 0u;
-        nShare[w] = 4u * nq - ((nq != 0u && (nQuads - 1u) % parts == w) ? 4u * nQuads - nTiles : 0u);
-    }
-    for (uint32_t q0 = threadIdx.x; q0 < myQuads; q0 += blockDim.x * kBatch) {
-        uint4 c[kBatch];
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; j++) {
-            const uint32_t q = q0 + j * blockDim.x;
-            c[j] = q < myQuads ? cls4[q * parts + part] : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; j++) {
-            const uint32_t t = ((q0 + j * blockDim.x) * parts + part) * 4u;
-            if (t + 0u < nTiles) atomicAdd(&sCount[min(c[j].x, kCostClasses - 1u) * kSub + sub], 1u);
-            if (t + 1u < nTiles) atomicAdd(&sCount[min(c[j].y, kCostClasses - 1u) * kSub + sub], 1u);
-            if (t + 2u < nTiles) atomicAdd(&sCount[min(c[j].z, kCostClasses - 1u) * kSub + sub], 1u);
-            if (t + 3u < nTiles) atomicAdd(&sCount[min(c[j].w, kCostClasses - 1u) * kSub + sub], 1u);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < kWave) { // start of each bin in the sorted order, dearest class first: one wave scans the 256 bins
-        const uint32_t lane = threadIdx.x;
-        uint32_t n[4], mine = 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < 4u; j++) { n[j] = sCount[kBins - 1u - (lane * 4u + j)]; mine += n[j]; } // bins in descending order
-        uint32_t incl = mine;
-#pragma unroll
-        for (int off = 1; off < (int)kWave; off <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, off);
-            if ((int)lane >= off) incl += up;
-        }
-        uint32_t start = incl - mine;
-#pragma unroll
-        for (uint32_t j = 0; j < 4u; j++) { sCount[kBins + kBins - 1u - (lane * 4u + j)] = start; start += n[j]; }
-    }
-    __syncthreads();
-    // launch slots: the nSplit dearest tiles take two each (near half, far half; two tiles to a workgroup), the others one
-    const uint32_t nGroups = (nTiles + nSplit + 3u) / 4u, fullRows = nGroups / numCUs;
-    for (uint32_t q0 = threadIdx.x; q0 < myQuads; q0 += blockDim.x * kBatch) {
-        uint4 c[kBatch];
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; j++) {
-            const uint32_t q = q0 + j * blockDim.x;
-            c[j] = q < myQuads ? cls4[q * parts + part] : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kBatch; j++) {
-            const uint32_t cc[4] = { c[j].x, c[j].y, c[j].z, c[j].w };
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; k++) {
-                const uint32_t t = ((q0 + j * blockDim.x) * parts + part) * 4u + k;
-                if (t < nTiles) {
-                    const uint32_t mine = atomicAdd(&sCount[kBins + min(cc[k], kCostClasses - 1u) * kSub + sub], 1u); // rank of tile t in this share
-                    // its rank overall: the shares take turns, a share that has run out is skipped
-                    uint32_t i = 0u;
-#pragma unroll
-                    for (uint32_t w = 0; w < kSchedGroups; w++) i += min(mine, nShare[w]) + ((w < part && nShare[w] > mine) ? 1u : 0u);
-                    if (i < nSplit) {
-                        const uint32_t at = (i / 2u) * 4u + (i & 1u) * 2u;
-                        slots[at] = make_uint2(t | (1u << 24), phase);
-                        slots[at + 1u] = make_uint2(t | (2u << 24), phase);
-                    } else {
-                        const uint32_t j = i + nSplit;
-                        uint32_t g = j / 4u;
-                        const uint32_t row = g / numCUs, col = g % numCUs;
-                        // (a row that also holds split tiles keeps its order: their slots are fixed)
-                        if ((row & 1u) && row < fullRows && row * numCUs >= nSplit / 2u) g = row * numCUs + (numCUs - 1u - col);
-                        slots[g * 4u + (j & 3u)] = make_uint2(t, phase);
-                    }
-                }
-            }
-        }
-    }
-}
-
-struct SplatShared {
-    uint32_t sBuckets[kSplatWordsPerGroup * 32];
-    int4 sBlocks[kSplatQueue];
-    uint32_t sNumBuckets, sNumBlocks;
-};
-
-// one workgroup of the splat: `group` < nSplatGroups takes 32 occupancy words, group == nSplatGroups makes the schedule
-__device__ void interval_splat_group(const VhHashData& hd, const VhHashParams& hp, const VhDepthCameraParams& cp, const VhRayCastParams& rp,
-                                     uint4* heads, int4* lists, uint32_t cap, uint32_t* sched, uint32_t phase, uint32_t numCUs,
-                                     uint32_t nSplatGroups, uint32_t* feedback, uint32_t group, SplatShared& sh)
-{
-    uint32_t (&sBuckets)[kSplatWordsPerGroup * 32] = sh.sBuckets;
-    int4 (&sBlocks)[kSplatQueue] = sh.sBlocks;
-    uint32_t& sNumBuckets = sh.sNumBuckets;
-    uint32_t& sNumBlocks = sh.sNumBlocks;
-    const uint32_t nWords = (hp.m_hashNumBuckets + 31) / 32;
-    const uint32_t lane = lane_id(), wave = threadIdx.x / kWave;
-    const int tilesX = (int)((rp.m_width + 7) / 8), tilesY = (int)((rp.m_height + 7) / 8);
-    const float vs = hp.m_virtualVoxelSize;
-    // voxel indices a sample at p can read along one axis: floor(p/vs) and floor(p/vs)+1 (+-1/2 more for the
-    // gradient's offset samples); block b holds indices 8b..8b+7  =>  p/vs in [8b-1, 8b+8) (+-1/2).  A quarter
-    // voxel on top covers every rounding on the way (|p/vs| < 2^16 where the quotient is resolved to 2^-8).
-    const float growLo = (rp.m_useGradients ? 1.75f : 1.25f) * vs, growHi = (rp.m_useGradients ? 0.75f : 0.25f) * vs;
-
-    if (group >= nSplatGroups) { // the extra workgroups (launched only with a schedule)
-        schedule_tiles(sched, feedback, (uint32_t)(tilesX * tilesY), phase, numCUs, group - nSplatGroups, sched_groups((uint32_t)(tilesX * tilesY)), sBuckets);
-        return;
-    }
-    if (threadIdx.x == 0) { sNumBuckets = 0u; sNumBlocks = 0u; }
-    __syncthreads();
-    // 1: occupied buckets of this group's words
-    if (threadIdx.x < kSplatWordsPerGroup) {
-        const uint32_t wordIdx = group * kSplatWordsPerGroup + threadIdx.x;
-        uint32_t bits = wordIdx < nWords ? hd.d_bucketBits[wordIdx] : 0u;
-        while (bits) {
-            const uint32_t bucket = wordIdx * 32u + (uint32_t)(__ffs((int)bits) - 1);
-            bits &= bits - 1u;
-            sBuckets[atomicAdd(&sNumBuckets, 1u)] = bucket;
-        }
-    }
-    __syncthreads();
-    const uint32_t nBuckets = sNumBuckets;
-    // 2+3 in rounds of 12 buckets (120 slots, within the block queue)
-    for (uint32_t b0 = 0; b0 < nBuckets; b0 += 12u) {
-        const uint32_t bi = b0 + threadIdx.x / 16u, sl = threadIdx.x % 16u;
-        if (threadIdx.x < 12u * 16u && bi < nBuckets && sl < VH_HASH_BUCKET_SIZE) {
-            const int4 q = load_quad(&hd.d_hash[(uint64_t)sBuckets[bi] * VH_HASH_BUCKET_SIZE + sl]);
-            if (q.w != VH_FREE_ENTRY) sBlocks[atomicAdd(&sNumBlocks, 1u)] = q;
-        }
-        __syncthreads();
-        const uint32_t nBlocks = sNumBlocks;
-        for (uint32_t k = wave; k < nBlocks; k += 256 / kWave) {
-            const int4 q = sBlocks[k];
-            const int bx = q.x, by = q.y, bz = q.z, ptr = q.w;
-            const float lox = (float)(bx * VH_SDF_BLOCK_SIZE) * vs - growLo, hix = (float)(bx * VH_SDF_BLOCK_SIZE + VH_SDF_BLOCK_SIZE) * vs + growHi;
-            const float loy = (float)(by * VH_SDF_BLOCK_SIZE) * vs - growLo, hiy = (float)(by * VH_SDF_BLOCK_SIZE + VH_SDF_BLOCK_SIZE) * vs + growHi;
-            const float loz = (float)(bz * VH_SDF_BLOCK_SIZE) * vs - growLo, hiz = (float)(bz * VH_SDF_BLOCK_SIZE + VH_SDF_BLOCK_SIZE) * vs + growHi;
-            float zmin = pinf(), zmax = minf(), xmin = pinf(), xmax = minf(), ymin = pinf(), ymax = minf();
-#pragma unroll
-            for (int c = 0; c < 8; c++) {
-                const F3 pc = mat_mul_p(rp.m_viewMatrix, mk3((c & 1) ? hix : lox, (c & 2) ? hiy : loy, (c & 4) ? hiz : loz));
-                zmin = fminf(zmin, pc.z); zmax = fmaxf(zmax, pc.z);
-                const float iz = 1.0f / fmaxf(pc.z, 1e-6f);
-                const float sx = pc.x * cp.fx * iz + cp.mx, sy = pc.y * cp.fy * iz + cp.my;
-                xmin = fminf(xmin, sx); xmax = fmaxf(xmax, sx);
-                ymin = fminf(ymin, sy); ymax = fmaxf(ymax, sy);
-            }
-            if (!(zmax > 0.0f)) continue; // entirely behind the camera: no sample (depth > 0) lies in it
-            int tx0 = 0, ty0 = 0, tx1 = tilesX - 1, ty1 = tilesY - 1;
-            if (zmin > 0.05f) { // box in front of the camera; otherwise it may project anywhere: every tile
-                const float slop = 1.0f + 1e-3f * fmaxf(fmaxf(fabsf(xmin), fabsf(xmax)), fmaxf(fabsf(ymin), fabsf(ymax)));
-                // clamp in float first: the float -> int conversion of a huge coordinate is not defined
-                tx0 = (int)fminf(fmaxf(floorf((xmin - slop) * 0.125f), 0.0f), (float)tilesX);
-                ty0 = (int)fminf(fmaxf(floorf((ymin - slop) * 0.125f), 0.0f), (float)tilesY);
-                tx1 = (int)fminf(fmaxf(floorf((xmax + slop) * 0.125f), -1.0f), (float)(tilesX - 1));
-                ty1 = (int)fminf(fmaxf(floorf((ymax + slop) * 0.125f), -1.0f), (float)(tilesY - 1));
-            }
-            if (tx1 < tx0 || ty1 < ty0) continue; // off screen
-            const float zs = 1e-3f * fabsf(zmax) + 0.5f * vs;
-            const uint32_t lo = __float_as_uint(fmaxf(zmin - zs, 0.0f)), hi = __float_as_uint(fmaxf(zmax + zs, 0.0f));
-            const uint32_t nx = (uint32_t)(tx1 - tx0 + 1), n = nx * (uint32_t)(ty1 - ty0 + 1);
-            const float rnx = 1.0f / (float)nx;
-            constexpr uint32_t kInFlight = 4; // tiles per lane in flight: the list slots come back from L2 together
-            for (uint32_t base = 0; base < n; base += kInFlight * kWave) {
-                uint32_t t[kInFlight], slot[kInFlight];
-#pragma unroll
-                for (uint32_t j = 0; j < kInFlight; j++) {
-                    const uint32_t i = base + j * kWave + lane;
-                    uint32_t qy, qx;
-                    divmod_small(i, nx, rnx, qy, qx);
-                    t[j] = (uint32_t)(ty0 + (int)qy) * (uint32_t)tilesX + (uint32_t)(tx0 + (int)qx);
-                    slot[j] = 0xffffffffu;
-                    if (i < n) {
-                        slot[j] = atomicAdd(&heads[t[j]].z, 1u);
-                    }
-                }
-#pragma unroll
-                for (uint32_t j = 0; j < kInFlight; j++) {
-                    if (slot[j] < cap) {
-                        lists[(size_t)t[j] * cap + slot[j]] = make_int4(bx, by, bz, ptr);
-                    } else if (slot[j] != 0xffffffffu) {
-                        // the head's depth range covers the blocks that are NOT listed (all of them without lists);
-                        // k_render forms the range of the listed ones itself: two atomics per tile and block less
-                        atomicMin(&heads[t[j]].x, lo);
-                        atomicMax(&heads[t[j]].y, hi);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) sNumBlocks = 0u;
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void k_interval_splat(VhHashData hd, VhHashParams hp, VhDepthCameraParams cp,
-                                                        VhRayCastParams rp, uint4* heads, int4* lists, uint32_t cap,
-                                                        uint32_t* sched, uint32_t phase, uint32_t numCUs, uint32_t nSplatGroups, uint32_t* feedback)
-{
-    __shared__ SplatShared sh;
-    interval_splat_group(hd, hp, cp, rp, heads, lists, cap, sched, phase, numCUs, nSplatGroups, feedback, blockIdx.x, sh);
-}
-
-__global__ __launch_bounds__(256) void k_interval_clear(uint4* heads, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) heads[i] = make_uint4(0x7f800000u, 0u, 0u, 0u); // empty: {+inf, 0, no blocks}
-}
 
 // ---------------------------------------------------------------------------
 // ray caster (renderKernel DSC/CUDARayCastSDF.cu:18-57,
@@ -2740,6 +1242,8 @@ VHD bool co_alloc(const CoAlloc& job)
     alloc_tile(job.hd, job.hp, job.cam, job.cp, job.bitMask, job.lockToken, job.hm, job.packed, g * (256u / kWave) + (threadIdx.x / kWave));
     return true;
 }
+// alloc's workgroups as a rider (host): the ray caster's workgroups of 256, four tiles each (on its own: alloc_groups)
+inline uint32_t co_alloc_groups(uint32_t tiles) { return cdiv(tiles, 256u / kWave); }
 
 // small tables: all tiles of a 640x480 frame resident at once (4800 + 256 waves <= 6 x 4 x 256) -- the march is a
 // latency chain, and a second round of waves costs as much as the first -- and the riders behind them find free
@@ -2769,331 +1273,26 @@ void k_render_large(VhHashData hd, VhHashParams hp, VhRayCastData rd, VhDepthCam
     render_tile<GRADIENTS, VH_TILE_LIST_CAPACITY_LARGE, OFFSETS32>(hd, hp, rd, cp, rp, heads, lists, cap, sched, phase, tileTab);
 }
 
-// Riders of computeNormals' launch.  They come FIRST in the grid (the schedule workgroup, the splat, the compactify
-// pass, then the image): each of them is a chain of dependent trips to memory, and what starts first ends first.
-struct CoCompactify {
-    VhHashData hd;
-    VhHashParams hp;
-    VhDepthCameraParams cp;
-    uint32_t groups; // 0: nothing to co-launch
-};
-
-// The interval splat of the NEXT render, for the pose of the frame being integrated.  It lists the table as it stands
-// before that frame's pass over the voxels: what the pass frees stays listed with all-zero voxels (weight 0: read
-// like an absent block), what the next alloc adds is not listed and is empty anyway.
-struct CoSplat {
-    VhRayCastParams rp; // view of the next render
-    VhDepthCameraParams cp;
-    uint4* heads;
-    int4* lists;
-    uint32_t* sched;
-    uint32_t* feedback;
-    uint32_t cap, phase, numCUs, nSplatGroups;
-    uint32_t groups; // nSplatGroups (+ sched_groups() with a schedule); 0: nothing to co-launch
-};
-
-// The frame's pass over the voxels (integrate + starve + GC) as a third rider: the LAST workgroups of the launch, two launches
-// a frame instead of three.  The pass needs the compactified list, which this launch's compactify workgroups make, and it
-// frees blocks, which edits the table this launch's splat workgroups read.
-//   * A workgroup of the pass polls ITS entry of the list (pass_rider_group): the entry is there as soon as the compactify
-//     workgroup that found the block has written it, and its last word says so (rider_tag).  The compactify workgroups also
-//     count themselves off when their part of the list is out (rider_done), and the last one raises flags (rider_wait): that
-//     is how the pass learns that the list is complete -- for its length, which it needs afterwards -- and how a workgroup
-//     beyond the end of the list learns that it has nothing to do.  (The first version waited for the flags before it read
-//     anything: 1.4 us a frame more.)
-//   * The frees and the splat need no order (free_block_cold): the splat lists every live block whatever happens, and a freed
-//     one or not -- which is all the same to the ray cast it is made for.  (The first version had the splat workgroups count
-//     themselves off too and the frees wait for them: 0.4 us a frame for nothing.)
-// A wait cannot be in vain: the hardware starts a launch's workgroups in grid order, so what a workgroup of the pass waits
-// for is running or done when it starts (and every wait gives up after ~1 s: VH_STATE_RIDER_GAVE_UP, never seen).
-// Between workgroups of ONE launch the eight XCDs' L2s are not coherent, and a release / acquire pair at agent scope is the
-// writer writing its whole L2 back and the reader dropping its own (buffer_wbl2 / buffer_inv per workgroup: measured, +30 us
-// a frame).  The list is the only data that crosses: it is written through and read at the coherence point (list_store), the
-// counters and flags are relaxed agent-scope atomics, and the writers wait for their stores before they count.
-// What it buys (cfg2, tools/riders_stamps.py): the compactify workgroups are done 1.6 - 4.9 us into the launch (four trips to
-// memory each, ~1 us on a busy machine), the pass's workgroups 6.4 - 8.9 us, beside the splat's 8.1; the launch alone ended at
-// ~8 us and a launch of the pass would then ramp up and take its own ~6 us: 4.8 us less per frame at 640x480 (350 blocks in
-// view), 5 us at 1080p (1200 blocks).  With more blocks than the launch has workgroups for the pass (2048) a workgroup takes
-// several, one after the other: at 2500 - 5800 blocks (cfg3) that costs 1.4 us a frame more than it saves, at 8600 (the dense
-// scene) it saves 2.3 -- the scene keeps the pass in a launch of its own, whose wave-per-block shape is made for such lists.
-struct CoIntegrate {
-    FusedArgs args;
-    uint32_t* done;          // VH_RIDER_DONE_WORDS words: flags, class counters, top counter (rider_done; never reset)
-    uint32_t listExpected, listClassExpected;   // what the compactify workgroups' top counter / class counters read once this launch's are done: the flags are set to the first then
-    uint32_t riderTag;       // the tag of this launch's list entries (rider_tag)
-    uint32_t first;          // the pass's first workgroup in the grid
-    uint32_t groups;         // 0: nothing to co-launch
-};
-struct NormalsKernargs { // (the argument block of k_compute_normals, for the offset of the pass's arguments in it)
-    float4* out; const float4* in; uint32_t width, height; CoCompactify job; CoSplat splat; CoIntegrate integ;
-};
-// A compactify workgroup, the i-th of n, has made its part of the list and counts itself off.  Counting on one word would
-// not do: same-address atomics are served one after the other, ~12 ns each, and a launch has up to 1 000 of them (measured
-// with the splat's 2 000 workgroups counting too: the launch twice as long).  So the workgroups count in
-// VH_RIDER_DONE_COUNTERS classes (i mod 32, a counter each, 128 bytes apart), the last of a class counts the class off on a
-// top counter, and the last class raises the flags.  Nothing is ever reset -- the host keeps what each word reads when all
-// launches so far are done -- so every class must grow by the same amount in every launch: n rounded up to a multiple of 32,
-// the workgroups whose i + 32 falls into the padding counting for two (n > 32 there).  A stage of few
-// workgroups counts on the top counter alone.
-constexpr uint32_t kRiderFewGroups = 128; // a stage of up to this many workgroups counts on one word (the launcher's totals follow: rider_totals)
-VHD void rider_done(const CoIntegrate& integ, const uint32_t i, const uint32_t n)
-{
-    if (integ.groups == 0u) return;
-    // every thread's stores to the list have arrived (written through, list_store: waiting for them is all a release has to
-    // do here)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    if (threadIdx.x < kWave) {
-        uint32_t* const words = integ.done; // flags, class counters, top counter
-        const uint32_t padded = (n + VH_RIDER_DONE_COUNTERS - 1u) / VH_RIDER_DONE_COUNTERS * VH_RIDER_DONE_COUNTERS;
-        const uint32_t add = (i + VH_RIDER_DONE_COUNTERS >= n && i + VH_RIDER_DONE_COUNTERS < padded) ? 2u : 1u;
-        uint32_t last = 0;
-        if (threadIdx.x == 0) {
-            if (n <= kRiderFewGroups) { // few enough to count on the top counter itself: a trip to memory less before the flags go up
-                last = __hip_atomic_fetch_add(&words[2u * VH_RIDER_DONE_COUNTERS * 32u], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == integ.listExpected ? 1u : 0u;
-            } else {
-                const uint32_t before = __hip_atomic_fetch_add(&words[(VH_RIDER_DONE_COUNTERS + i % VH_RIDER_DONE_COUNTERS) * 32u], add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (before + add == integ.listClassExpected)
-                    last = __hip_atomic_fetch_add(&words[2u * VH_RIDER_DONE_COUNTERS * 32u], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == integ.listExpected ? 1u : 0u;
-            }
-        }
-        last = (uint32_t)__shfl((int)last, 0);
-        if (last && threadIdx.x < (uint32_t)VH_RIDER_DONE_COUNTERS)
-            __hip_atomic_store(&words[threadIdx.x * 32u], integ.listExpected, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// A workgroup of the pass as a rider: block `group` of the list, then (with more than `groups` blocks) group + groups, ...
-// It does not wait for the list to be complete before it starts: it polls ITS entry, which is there as soon as the compactify
-// workgroup that found the block has written it (the entry's tag says so: rider_tag, the last word list_store writes) -- on
-// average a microsecond before the slowest compactify workgroup is done, and without the trip for the count and the flag's own
-// way through memory (0.9 us).  The count it needs only afterwards: to know whether the list goes on beyond the launch's
-// workgroups, and, in workgroup 0, for the host's mirror.
-struct PassRiderShared {
-    FusedShared<false> fused;
-    int4 q;
-    uint32_t have, count;
-};
-template <uint32_t KERNARG_OFFSET>
-VHD void pass_rider_group(const CoIntegrate& integ, const uint32_t group, PassRiderShared& sh)
-{
-    const FusedArgs& args = integ.args;
-    const VhHashEntry* const list = args.hd.d_hashCompactified;
-    const uint32_t nEntries = args.hp.m_hashNumBuckets * VH_HASH_BUCKET_SIZE;
-    const float thr = get_truncation(args.hp, args.cp.m_sensorDepthWorldMax);
-    // 1. this workgroup's entry, or the end of the list (every lane of the wave reads the same words: one request each)
-    if (threadIdx.x < kWave) {
-        uint32_t have = 0u;
-        if (group < nEntries) {
-            const uint32_t* const flag = integ.done + (blockIdx.x % VH_RIDER_DONE_COUNTERS) * 32u;
-            const uint64_t* const tagWord = reinterpret_cast<const uint64_t*>(&list[group]) + 3;
-            for (uint32_t polls = 0; polls < (1u << 22); polls++) { // (an exit every wave reaches, as rider_wait)
-                // both words in flight together: a poll is one trip to memory
-                const uint64_t w = __hip_atomic_load(tagWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const uint32_t f = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((uint32_t)(w >> 32) == integ.riderTag) { have = 1u; break; }
-                if ((int32_t)(f - integ.listExpected) >= 0) break; // the list is complete (step 2 looks again)
-                __builtin_amdgcn_s_sleep(2);
-            }
-        }
-        int4 q = make_int4(0, 0, 0, 0);
-        if (have) q = list_quad<true>(&list[group]);
-        if (threadIdx.x == 0) { sh.q = q; sh.have = have; }
-    }
-    __syncthreads();
-    const bool early = sh.have != 0u;
-    if (early) integrate_block_by_workgroup<true, KERNARG_OFFSET>(args, sh.fused, sh.q, group, thr);
-    // 2. the whole list
-    if (threadIdx.x < kWave) {
-        uint32_t count = 0u;
-        if (rider_wait(integ.done, integ.listExpected)) count = (uint32_t)__hip_atomic_load(args.hd.d_hashCompactifiedCounter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else if (threadIdx.x == 0) atomicAdd(&args.hd.d_state[VH_STATE_RIDER_GAVE_UP], 1u); // (what is left of its share stays undone)
-        if (threadIdx.x == 0) sh.count = count;
-    }
-    __syncthreads();
-    const uint32_t count = sh.count;
-    // host-visible copy of the block count and the caller's tag (as integrate_fused_body)
-    if (args.countMirror && group == 0u && threadIdx.x == 0) *reinterpret_cast<uint2*>(args.countMirror) = make_uint2(count, args.mirrorTag);
-    for (uint32_t b = group; b < count; b += integ.groups) {
-        if (b == group && early) continue;
-        __syncthreads(); // (the previous block's reads of the shared words are done)
-        integrate_block_by_workgroup<true, KERNARG_OFFSET>(args, sh.fused, list_quad<true>(&list[b]), b, thr);
-    }
-}
-
-// computeNormalsDevice, DSC/CameraUtil.cu:669-697
-__global__ __launch_bounds__(256) void k_compute_normals(float4* out, const float4* in, uint32_t width, uint32_t height, CoCompactify job, CoSplat splat, CoIntegrate integ)
-{
-    __shared__ union RiderShared { SplatShared splat; CompactShared compact; PassRiderShared pass; } shared;
-    SplatShared& sh = shared.splat;
-    uint32_t g = blockIdx.x;
-    if (integ.groups != 0u && g >= integ.first) {
-        static_assert(kRiderFewGroups >= VH_RIDER_DONE_COUNTERS && VH_RIDER_DONE_COUNTERS <= kWave, "one lane per flag");
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 42
-        const uint32_t riderStamp0 = (uint32_t)__builtin_amdgcn_s_memrealtime();
-        uint4* const riderStampAt = reinterpret_cast<uint4*>(job.hd.d_hashCompactified) + (job.hp.m_hashNumBuckets * VH_HASH_BUCKET_SIZE) / 2u + blockIdx.x;
-#endif
-        pass_rider_group<(uint32_t)(offsetof(NormalsKernargs, integ) + offsetof(CoIntegrate, args))>(integ, g - integ.first, shared.pass);
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 42
-        __syncthreads();
-        if (threadIdx.x == 0) *riderStampAt = make_uint4(riderStamp0, (uint32_t)__builtin_amdgcn_s_memrealtime(), 5u, 0x5742u);
-#endif
-        return;
-    }
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 42 // measurement build: every workgroup's life by kind, read by tools/riders_stamps.py
-    const uint32_t stamp0 = (uint32_t)__builtin_amdgcn_s_memrealtime();
-    uint4* const stampAt = reinterpret_cast<uint4*>(job.hd.d_hashCompactified) + (job.hp.m_hashNumBuckets * VH_HASH_BUCKET_SIZE) / 2u + blockIdx.x;
-#define VH_GROUP_STAMP(KIND) { __syncthreads(); if (threadIdx.x == 0) *stampAt = make_uint4(stamp0, (uint32_t)__builtin_amdgcn_s_memrealtime(), (KIND), 0x5742u); }
-#else
-#define VH_GROUP_STAMP(KIND)
-#endif
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT >= 31 && VH_KNOCKOUT <= 34 // measurement builds: the riders of this launch, one at a time
-    {
-        const uint32_t nSchedK = splat.groups - splat.nSplatGroups;
-        const bool isSched = g < nSchedK, isCompact = !isSched && g - nSchedK < job.groups, isSplat = !isSched && !isCompact && g < splat.groups + job.groups;
-        if (VH_KNOCKOUT == 31 && isSched) return;               // no schedule workgroups
-        if (VH_KNOCKOUT == 32 && (isSched || isSplat)) return;  // no splat at all
-        if (VH_KNOCKOUT == 33 && isCompact) return;             // no compactify
-        if (VH_KNOCKOUT == 34 && !isSched && !isCompact && !isSplat) return; // no normals
-    }
-#endif
-    // the schedule workgroups first (the longest chains), then compactify (the pass over the voxels, if it rides, waits for
-    // its list), then the table's slices
-    const uint32_t nSched = splat.groups - splat.nSplatGroups;
-    if (g >= nSched && g - nSched < job.groups) {
-        g -= nSched;
-        if (integ.groups != 0u) compactify_group<true>(job.hd, job.hp, job.cp, g * blockDim.x + threadIdx.x, shared.compact, integ.riderTag);
-        else compactify_group<false>(job.hd, job.hp, job.cp, g * blockDim.x + threadIdx.x, shared.compact);
-        VH_GROUP_STAMP(3u)
-        rider_done(integ, g, job.groups);
-        return;
-    }
-    if (g >= nSched) g -= job.groups;
-    if (g < splat.groups) {
-        const uint32_t group = g < nSched ? splat.nSplatGroups + g : g - nSched;
-        interval_splat_group(job.hd, job.hp, splat.cp, splat.rp, splat.heads, splat.lists, splat.cap, splat.sched, splat.phase, splat.numCUs,
-                             splat.nSplatGroups, splat.feedback, group, sh);
-        VH_GROUP_STAMP(group >= splat.nSplatGroups ? 1u : 2u)
-        return;
-    }
-    g -= splat.groups;
-    const uint32_t idx = g * blockDim.x + threadIdx.x;
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 42
-    if (job.groups != 0u && idx < width * height) {
-#else
-    if (idx >= width * height) return;
-    {
-#endif
-    const uint32_t x = idx % width, y = idx / width;
-    const float mi = minf();
-    float4 o = make_float4(mi, mi, mi, mi);
-    if (x > 0 && x < width - 1 && y > 0 && y < height - 1) {
-        const float4 CC = in[idx], PC = in[idx + width], CP = in[idx + 1], MC = in[idx - width], CM = in[idx - 1];
-        if (CC.x != mi && PC.x != mi && CP.x != mi && MC.x != mi && CM.x != mi) {
-            const F3 a = mk3(PC.x - MC.x, PC.y - MC.y, PC.z - MC.z), b = mk3(CP.x - CM.x, CP.y - CM.y, CP.z - CM.z);
-            const F3 n = mk3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
-            const float l = sqrtf(dot3(n, n));
-            if (l > 0.0f) o = make_float4(n.x / -l, n.y / -l, n.z / -l, 1.0f);
-        }
-    }
-    out[idx] = o;
-    }
-#if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 42
-    if (job.groups != 0u) VH_GROUP_STAMP(4u)
-#endif
-}
-#undef VH_GROUP_STAMP
-
-// ---------------------------------------------------------------------------
-// the hash operations one by one, and checks of integrate's arithmetic
-// ---------------------------------------------------------------------------
-
-// serial hash-operation interpreter (tests of the collision paths)
-__global__ void k_debug_hash_ops(VhHashData hd, VhHashParams hp, const int32_t* ops, int32_t* results, uint32_t n)
-{
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    int32_t token = 1;
-    for (uint32_t i = 0; i < n; i++) {
-        const int32_t op = ops[5 * i + 0];
-        const I3 p = mki3(ops[5 * i + 1], ops[5 * i + 2], ops[5 * i + 3]);
-        const int32_t arg = ops[5 * i + 4];
-        int32_t r = 0;
-        switch (op) {
-        case VH_OP_ALLOC: r = alloc_block(hd, hp, p, token); break;
-        case VH_OP_DELETE: r = delete_hash_entry_element(hd, hp, p, token) ? 1 : 0; break;
-        case VH_OP_INSERT: r = insert_hash_entry(hd, hp, p, arg, token) ? 1 : 0; break;
-        case VH_OP_LOOKUP: r = lookup_ptr(hd, hp, p); break;
-        case VH_OP_NEW_PASS: token++; break;
-        default: break;
-        }
-        // ops are "passes" of one launch here: drop this CU's L1 so that plain loads of the next op see what the
-        // atomics of this one did at L2 (between real launches the hardware does that)
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
-        results[i] = r;
-    }
-}
-
-// checks div_refined2 (integrate_block_certified's division) against `/` inside the ranges its callers certify:
-// [0] the projection: divisor in [2^-20, 2^20], |numerator| in [2^-100, 2^60] or zero; [1] the blend: divisor an integer
-// in 1..510, |numerator| in [2^-100, 2^90)
-__global__ __launch_bounds__(256) void k_check_refined_division(uint32_t n, uint32_t seed, uint32_t* mismatches)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t s = (i + 1u) * 2654435761u ^ seed;
-    s ^= s >> 15; s *= 2246822519u; s ^= s >> 13; s *= 3266489917u; s ^= s >> 16;
-    const uint32_t u = s * 747796405u + 2891336453u, t = u * 2654435761u + 40503u;
-    // sign and mantissa from the random words, exponents spread evenly over the certified ranges
-    const uint32_t dExp = 127u - 20u + (s >> 8) % 41u, nExpP = 127u - 100u + (u >> 8) % 161u, nExpB = 127u - 100u + (t >> 8) % 190u;
-    float d = __uint_as_float((dExp << 23) | (s & 0x7fffffu));
-    if (dExp == 127u + 20u) d = 0x1p20f; // the closed end of the range
-    float nP = __uint_as_float((u & 0x80000000u) | (nExpP << 23) | (u & 0x7fffffu));
-    if (nExpP == 127u + 60u) nP = copysignf(0x1p60f, nP);
-    if ((i & 1023u) == 0u) nP = (i & 1024u) ? 0.0f : -0.0f;
-    if ((i & 1023u) == 1u) { d = 1.0f + (float)(i >> 10) * 0x1p-23f; nP = __uint_as_float(0x3fffffffu - (s & 0xffu)); } // mantissas near all-ones
-    const float dB = (float)(1u + (s >> 3) % 510u);
-    const float nB = __uint_as_float((t & 0x80000000u) | (nExpB << 23) | (t & 0x7fffffu));
-    const f32x2 dd = (f32x2){ d, dB }, nn = (f32x2){ nP, nB };
-    const f32x2 q = div_refined2(nn, dd, rcp_refined2(dd));
-    const float wantP = nP / d, wantB = nB / dB;
-    // (a zero numerator: the projection takes either zero -- "+ mx, + 0.5" cannot tell them apart)
-    if (__float_as_uint(q.x) != __float_as_uint(wantP) && !(wantP == 0.0f && q.x == 0.0f)) atomicAdd(&mismatches[0], 1u);
-    if (__float_as_uint(q.y) != __float_as_uint(wantB)) atomicAdd(&mismatches[1], 1u);
-}
-
-// weighted_colour (combine_voxel's and integrate_block_certified's colour step with m_colorIntegration = 1) against the
-// integer formula floor((2 n + d) / (2 d)), n = c0 w0 + c1 w1, d = w0 + w1, for EVERY (c0, w0, c1, w1) with w1 >= 1 of one
-// channel (the channels share the arithmetic; the other two carry the value's complement and its swap with c1, so a
-// mix-up of bytes shows too), with each reciprocal a caller hands it: [0] 1.0f / d (combine_voxel), [1] rcp_refined2
-// (the certified path).  Workgroup (c0, c1), thread w0, a loop over w1.  out: {mismatches [0], [1], first mismatch as
-// c0 | w0 << 8 | c1 << 16 | w1 << 24 (the smallest such word; 0xffffffff if none), 0}
-__global__ __launch_bounds__(256) void k_check_weighted_colour(uint32_t* out)
-{
-    const uint32_t c0 = blockIdx.x & 255u, c1 = blockIdx.x >> 8, w0 = threadIdx.x;
-    uint32_t bad0 = 0u, bad1 = 0u, first = 0xffffffffu;
-    for (uint32_t w1 = 1u; w1 < 256u; w1++) {
-        const uint32_t d = w0 + w1;
-        const uint32_t want = (2u * (c0 * w0 + c1 * w1) + d) / (2u * d);
-        const uint32_t o0 = 255u - c0, o1 = 255u - c1;
-        const uint32_t wantO = (2u * (o0 * w0 + o1 * w1) + d) / (2u * d), wantX = (2u * (c1 * w0 + c0 * w1) + d) / (2u * d);
-        const uint32_t cw0 = pack_cw(c0, o0, c1, w0), cw1 = pack_cw(c1, o1, c0, w1), wantRgb = pack_cw(want, wantO, wantX, 0u);
-        const float den = (float)d;
-        const f32x2 y = rcp_refined2(both(den));
-        const bool m0 = weighted_colour(cw0, cw1, den, 1.0f / den) != wantRgb, m1 = weighted_colour(cw0, cw1, den, y.x) != wantRgb;
-        bad0 += m0 ? 1u : 0u;
-        bad1 += m1 ? 1u : 0u;
-        if (m0 || m1) first = min(first, c0 | (w0 << 8) | (c1 << 16) | (w1 << 24));
-    }
-    if (bad0) atomicAdd(&out[0], bad0);
-    if (bad1) atomicAdd(&out[1], bad1);
-    if (first != 0xffffffffu) atomicMin(&out[2], first);
-}
-
 } // namespace
+
+#include "vh_frame_normals.hpp"
+#include "vh_frame_checks.hpp"
 
 // ---------------------------------------------------------------------------
 // launcher-level C ABI
 // ---------------------------------------------------------------------------
+
+static uint32_t device_num_cus() // of the current device (one device per process: INTEGRATION.md)
+{
+    static int numCUs = 0;
+    if (numCUs == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&numCUs, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || numCUs <= 0)
+            numCUs = 256;
+    }
+    return (uint32_t)numCUs;
+}
+static uint32_t schedule_num_cus(const uint32_t* d_schedule) { return d_schedule ? device_num_cus() : 256u; } // (no schedule: the device is not asked)
 
 extern "C" {
 
@@ -3125,22 +1324,22 @@ int vh_alloc(const VhHashData* hd, const VhHashParams* hp, const VhDepthCameraDa
              const VhDepthCameraParams* cp, const uint32_t* d_bitMask, int32_t lockToken, vhStream_t stream)
 {
     if (!hd || !hp || !cam || !cp || !cam->d_depthData) return VH_ERR_BAD_ARGUMENT;
-    const uint32_t tiles = cdiv(cp->m_imageWidth, 8) * cdiv(cp->m_imageHeight, 8);
+    const uint32_t tiles = image_tiles(cp->m_imageWidth, cp->m_imageHeight);
     if (tiles == 0) return VH_OK;
     if (hp->m_hashNumBuckets < 2) return VH_ERR_BAD_ARGUMENT;
-    k_alloc<<<cdiv(tiles, 8), 512, 0, (hipStream_t)stream>>>(*hd, *hp, *cam, *cp, d_bitMask, lockToken, make_hash_mod(hp->m_hashNumBuckets), nullptr);
+    k_alloc<<<alloc_groups(tiles), kAllocThreads, 0, (hipStream_t)stream>>>(*hd, *hp, *cam, *cp, d_bitMask, lockToken, make_hash_mod(hp->m_hashNumBuckets), nullptr);
     return vh_last_launch_error();
 }
 
 int vh_alloc_job(VhFrameJob* job, vhStream_t stream)
 {
     if (!job || !job->cam.d_depthData || !job->hashData.d_hash) return VH_ERR_BAD_ARGUMENT;
-    const uint32_t tiles = cdiv(job->cp.m_imageWidth, 8) * cdiv(job->cp.m_imageHeight, 8);
+    const uint32_t tiles = image_tiles(job->cp.m_imageWidth, job->cp.m_imageHeight);
     if (job->hashParams.m_hashNumBuckets < 2) return VH_ERR_BAD_ARGUMENT;
     job->allocLaunched = 1;
     if (tiles == 0) return VH_OK;
-    k_alloc<<<cdiv(tiles, 8), 512, 0, (hipStream_t)stream>>>(job->hashData, job->hashParams, job->cam, job->cp, job->d_bitMask, job->lockToken,
-                                                             make_hash_mod(job->hashParams.m_hashNumBuckets), reinterpret_cast<uint2*>(job->d_packedFrame));
+    k_alloc<<<alloc_groups(tiles), kAllocThreads, 0, (hipStream_t)stream>>>(job->hashData, job->hashParams, job->cam, job->cp, job->d_bitMask, job->lockToken,
+                                                                            make_hash_mod(job->hashParams.m_hashNumBuckets), reinterpret_cast<uint2*>(job->d_packedFrame));
     return vh_last_launch_error();
 }
 
@@ -3148,8 +1347,7 @@ int vh_compactify_job(VhFrameJob* job, vhStream_t stream)
 {
     if (!job || !job->hashData.d_hash) return VH_ERR_BAD_ARGUMENT;
     job->compactifyLaunched = 1;
-    const uint32_t nWords = (job->hashParams.m_hashNumBuckets + 31) / 32;
-    k_compactify<<<cdiv(nWords, 256), 256, 0, (hipStream_t)stream>>>(job->hashData, job->hashParams, job->cp);
+    k_compactify<<<compactify_groups(job->hashParams), kCompactifyThreads, 0, (hipStream_t)stream>>>(job->hashData, job->hashParams, job->cp);
     return vh_last_launch_error();
 }
 
@@ -3159,8 +1357,7 @@ int vh_compactify(const VhHashData* hd, const VhHashParams* hp, const VhDepthCam
     if (!hd || !hp || !cp) return VH_ERR_BAD_ARGUMENT;
     hipStream_t s = (hipStream_t)stream;
     if (!(flags & VH_COMPACT_COUNTER_IS_ZERO)) VH_HIP(hipMemsetAsync(hd->d_hashCompactifiedCounter, 0, sizeof(int32_t), s));
-    const uint32_t nWords = (hp->m_hashNumBuckets + 31) / 32;
-    k_compactify<<<cdiv(nWords, 256), 256, 0, s>>>(*hd, *hp, *cp);
+    k_compactify<<<compactify_groups(*hp), kCompactifyThreads, 0, s>>>(*hd, *hp, *cp);
     int err = vh_last_launch_error();
     if (err) return err;
     if (numOccupied) {
@@ -3179,24 +1376,15 @@ int vh_integrate(const VhHashData* hd, const VhHashParams* hp, const VhDepthCame
     return vh_last_launch_error();
 }
 
-static uint32_t device_num_cus();
-
 int vh_integrate_fused(const VhHashData* hd, const VhHashParams* hp, const VhDepthCameraData* cam,
                        const VhDepthCameraParams* cp, uint32_t flags, int32_t lockToken, uint32_t* d_countMirror, uint32_t mirrorTag,
                        const void* d_packedFrame, vhStream_t stream)
 {
     if (!hd || !hp || !cam || !cp || !cam->d_depthData) return VH_ERR_BAD_ARGUMENT;
     if (cp->m_imageWidth > 0xffffu || cp->m_imageHeight > 0xffffu) return VH_ERR_BAD_ARGUMENT;
-    // persistent grid: the block count lives on the device, so no host read-back is needed (the kernel picks its shape
-    // from the count)
-    const uint32_t want = cdiv(hp->m_numSDFBlocks, 4), most = device_num_cus() * 8u;
-    const uint32_t grid = want < most ? want : most;
-    const uint2* packed = reinterpret_cast<const uint2*>(d_packedFrame);
-    FusedArgs args;
-    args.hd = *hd; args.hp = *hp; args.cam = *cam; args.cp = *cp;
-    args.flags = flags; args.lockToken = lockToken; args.countMirror = d_countMirror; args.mirrorTag = mirrorTag;
-    args.packed = reinterpret_cast<const uint2*>(packed);
-    if (packed) VH_LAUNCH_TIMED(k_integrate_fused<true>, grid, 256, (hipStream_t)stream, args);
+    const uint32_t grid = fused_pass_groups(*hp, device_num_cus());
+    const FusedArgs args = fused_args(*hd, *hp, *cam, *cp, flags, lockToken, d_countMirror, mirrorTag, d_packedFrame);
+    if (args.packed) VH_LAUNCH_TIMED(k_integrate_fused<true>, grid, 256, (hipStream_t)stream, args);
     else VH_LAUNCH_TIMED(k_integrate_fused<false>, grid, 256, (hipStream_t)stream, args);
     return vh_last_launch_error();
 }
@@ -3235,7 +1423,7 @@ int vh_render(const VhHashData* hd, const VhHashParams* hp, const VhRayCastData*
               const VhDepthCameraParams* cp, const VhRayCastParams* rp, vhStream_t stream)
 {
     if (!hd || !hp || !rd || !cp || !rp || !rd->d_depth) return VH_ERR_BAD_ARGUMENT;
-    const uint32_t tiles = cdiv(rp->m_width, 8) * cdiv(rp->m_height, 8);
+    const uint32_t tiles = image_tiles(rp->m_width, rp->m_height);
     if (tiles == 0) return VH_OK;
     if (hp->m_hashNumBuckets < 2) return VH_ERR_BAD_ARGUMENT;
     const HashMod hm = make_hash_mod(hp->m_hashNumBuckets);
@@ -3270,25 +1458,14 @@ int vh_query_rays(const VhHashData* hd, const VhHashParams* hp, const VhRayCastP
     return vh_last_launch_error();
 }
 
-static uint32_t device_num_cus() // of the current device (one device per process: INTEGRATION.md)
-{
-    static int numCUs = 0;
-    if (numCUs == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&numCUs, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || numCUs <= 0)
-            numCUs = 256;
-    }
-    return (uint32_t)numCUs;
-}
-
 size_t vh_render_schedule_bytes(uint32_t width, uint32_t height)
 {
-    const size_t tiles = (size_t)cdiv(width, 8) * cdiv(height, 8);
+    const size_t tiles = image_tiles(width, height);
     // header, cost classes, launch slots (one per wave: the tiles, and a second one for each split tile)
     return (4u + 4u * ((tiles + 3u) / 4u) + 2u * 4u * ((tiles + kSplitTiles + 3u) / 4u)) * sizeof(uint32_t);
 }
 
-uint32_t vh_render_split_tiles(uint32_t width, uint32_t height) { return split_tiles(cdiv(width, 8) * cdiv(height, 8)); }
+uint32_t vh_render_split_tiles(uint32_t width, uint32_t height) { return split_tiles(image_tiles(width, height)); }
 
 static std::atomic<int> g_forceOffsets64{ 0 };
 
@@ -3301,7 +1478,7 @@ int vh_render_intervals_co(const VhHashData* hd, const VhHashParams* hp, const V
                            uint32_t* d_schedule, uint32_t phase, VhFrameJob* fj, vhStream_t stream)
 {
     if (!hd || !hp || !rd || !cp || !rp || !rd->d_depth || !d_tileHeads) return VH_ERR_BAD_ARGUMENT;
-    const uint32_t tiles = cdiv(rp->m_width, 8) * cdiv(rp->m_height, 8);
+    const uint32_t tiles = image_tiles(rp->m_width, rp->m_height);
     if (tiles == 0) return VH_OK;
     uint4* h = reinterpret_cast<uint4*>(d_tileHeads);
     const int4* l = reinterpret_cast<const int4*>(d_tileBlocks);
@@ -3312,14 +1489,13 @@ int vh_render_intervals_co(const VhHashData* hd, const VhHashParams* hp, const V
     CoAlloc job;
     std::memset(&job, 0, sizeof(job));
     if (fj && !fj->allocLaunched && fj->cam.d_depthData && fj->hashData.d_hash && fj->hashParams.m_hashNumBuckets >= 2) {
-        const uint32_t allocTiles = cdiv(fj->cp.m_imageWidth, 8) * cdiv(fj->cp.m_imageHeight, 8);
         job.hd = fj->hashData; job.hp = fj->hashParams; job.cam = fj->cam; job.cp = fj->cp;
         job.bitMask = fj->d_bitMask;
         job.packed = reinterpret_cast<uint2*>(fj->d_packedFrame);
         job.hm = make_hash_mod(fj->hashParams.m_hashNumBuckets);
         job.lockToken = fj->lockToken;
         job.firstGroup = groups;
-        groups += cdiv(allocTiles, 4);
+        groups += co_alloc_groups(image_tiles(fj->cp.m_imageWidth, fj->cp.m_imageHeight));
         fj->allocLaunched = 1;
     }
     const dim3 grid(groups);
@@ -3350,7 +1526,7 @@ int vh_render_intervals(const VhHashData* hd, const VhHashParams* hp, const VhRa
 int vh_ray_interval_clear(uint32_t* d_tileHeads, uint32_t width, uint32_t height, vhStream_t stream)
 {
     if (!d_tileHeads) return VH_ERR_BAD_ARGUMENT;
-    const uint32_t tiles = cdiv(width, 8) * cdiv(height, 8);
+    const uint32_t tiles = image_tiles(width, height);
     if (tiles == 0) return VH_OK;
     k_interval_clear<<<cdiv(tiles, 256), 256, 0, (hipStream_t)stream>>>(reinterpret_cast<uint4*>(d_tileHeads), tiles);
     return vh_last_launch_error();
@@ -3362,13 +1538,10 @@ int vh_ray_interval_splat(const VhHashData* hd, const VhHashParams* hp, const Vh
 {
     if (!hd || !hp || !cp || !rp || !d_tileHeads) return VH_ERR_BAD_ARGUMENT;
     if (rp->m_width == 0 || rp->m_height == 0) return VH_OK;
-    const uint32_t numCUs = d_schedule ? device_num_cus() : 256u;
-    const uint32_t nWords = (hp->m_hashNumBuckets + 31) / 32;
-    const uint32_t groups = cdiv(nWords, kSplatWordsPerGroup);
-    const uint32_t nSched = d_schedule ? sched_groups(cdiv(rp->m_width, 8) * cdiv(rp->m_height, 8)) : 0u;
-    k_interval_splat<<<groups + nSched, 256, 0, (hipStream_t)stream>>>(*hd, *hp, *cp, *rp, reinterpret_cast<uint4*>(d_tileHeads),
-                                                                                 reinterpret_cast<int4*>(d_tileBlocks), d_tileBlocks ? tileCapacity : 0u,
-                                                                                 d_schedule, phase, numCUs, groups, d_longestList);
+    const uint32_t groups = splat_groups(*hp);
+    k_interval_splat<<<groups + splat_sched_groups(*rp, d_schedule), kSplatThreads, 0, (hipStream_t)stream>>>(
+        *hd, *hp, *cp, *rp, reinterpret_cast<uint4*>(d_tileHeads), reinterpret_cast<int4*>(d_tileBlocks), d_tileBlocks ? tileCapacity : 0u,
+        d_schedule, phase, schedule_num_cus(d_schedule), groups, d_longestList);
     return vh_last_launch_error();
 }
 
@@ -3385,7 +1558,7 @@ int vh_compute_normals_co2(float* d_output4, const float* d_input4, uint32_t wid
     std::memset(&sp, 0, sizeof(sp));
     if (fj && fj->allocLaunched && !fj->compactifyLaunched && fj->hashData.d_hash) {
         job.hd = fj->hashData; job.hp = fj->hashParams; job.cp = fj->cp;
-        job.groups = cdiv((fj->hashParams.m_hashNumBuckets + 31) / 32, 256);
+        job.groups = compactify_groups(fj->hashParams);
         groups += job.groups;
         fj->compactifyLaunched = 1;
         if (nextView && d_tileHeads && nextView->m_width != 0 && nextView->m_height != 0) { // needs the job's table (job.hd / job.hp)
@@ -3395,9 +1568,9 @@ int vh_compute_normals_co2(float* d_output4, const float* d_input4, uint32_t wid
             sp.sched = d_schedule; sp.feedback = d_longestList;
             sp.cap = d_tileBlocks ? tileCapacity : 0u;
             sp.phase = phase;
-            sp.numCUs = d_schedule ? device_num_cus() : 256u;
-            sp.nSplatGroups = cdiv((fj->hashParams.m_hashNumBuckets + 31) / 32, kSplatWordsPerGroup);
-            sp.groups = sp.nSplatGroups + (d_schedule ? sched_groups(cdiv(nextView->m_width, 8) * cdiv(nextView->m_height, 8)) : 0u);
+            sp.numCUs = schedule_num_cus(d_schedule);
+            sp.nSplatGroups = splat_groups(fj->hashParams);
+            sp.groups = sp.nSplatGroups + splat_sched_groups(*nextView, d_schedule);
             groups += sp.groups;
         }
     }
@@ -3408,25 +1581,14 @@ int vh_compute_normals_co2(float* d_output4, const float* d_input4, uint32_t wid
     if (fj && job.groups != 0u &&
         fj->fusedPrepared && !fj->fusedLaunched && fj->d_riderDone && fj->d_packedFrame && fj->cam.d_depthData &&
         fj->cp.m_imageWidth <= 0xffffu && fj->cp.m_imageHeight <= 0xffffu) {
-        integ.args.hd = fj->hashData; integ.args.hp = fj->hashParams; integ.args.cam = fj->cam; integ.args.cp = fj->cp;
-        integ.args.flags = fj->fusedFlags; integ.args.lockToken = fj->fusedLockToken;
-        integ.args.countMirror = fj->d_countMirror; integ.args.mirrorTag = fj->mirrorTag;
-        integ.args.packed = reinterpret_cast<const uint2*>(fj->d_packedFrame);
+        integ.args = fused_args(fj->hashData, fj->hashParams, fj->cam, fj->cp, fj->fusedFlags, fj->fusedLockToken, fj->d_countMirror, fj->mirrorTag, fj->d_packedFrame);
         integ.done = fj->d_riderDone;
         integ.riderTag = 0x80000000u | fj->mirrorTag; // (rider_tag of the frame's number)
-        // (rider_done: a class of a stage grows by the stage's workgroups rounded up to 32s, over 32, and the top counter by 32;
-        // a stage of few workgroups counts on the top counter alone)
-        if (job.groups <= kRiderFewGroups) {
-            fj->listDoneTotal += job.groups;
-        } else {
-            fj->listClassTotal += cdiv(job.groups, VH_RIDER_DONE_COUNTERS);
-            fj->listDoneTotal += VH_RIDER_DONE_COUNTERS;
-        }
+        rider_totals(job.groups, fj->listDoneTotal, fj->listClassTotal);
         integ.listExpected = fj->listDoneTotal;
         integ.listClassExpected = fj->listClassTotal;
         integ.first = groups;
-        const uint32_t want = cdiv(fj->hashParams.m_numSDFBlocks, 4), most = device_num_cus() * 8u;
-        integ.groups = want < most ? want : most; // (as vh_integrate_fused)
+        integ.groups = fused_pass_groups(fj->hashParams, device_num_cus());
         groups += integ.groups;
         fj->fusedLaunched = 1;
     }
