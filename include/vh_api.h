@@ -283,8 +283,16 @@ int vh_debug_hash_ops(const VhHashData* hd, const VhHashParams* hp, const int32_
 /* Self-check of the two exact shortcuts the ray caster uses: division by the
  * voxel size through a reciprocal with two correction steps, and modulo by the
  * bucket count through a multiply-shift.  d_mismatches[0] / [1] = number of
- * operands (of n pseudo-random ones) where the shortcut differs from `/` / `%`. */
+ * operands (of n pseudo-random ones) where the shortcut differs from `/` / `%`.
+ * The first 256 operands also check the ray caster's colour bytes: c / 255 for
+ * every byte c through the same shortcut (counted in d_mismatches[0]). */
 int vh_debug_check_fast_math(float divisor, uint32_t modulus, uint32_t n, uint32_t seed, uint32_t* d_mismatches, vhStream_t stream);
+
+/* The ray caster's wave reductions (minimum and maximum of 64 floats, maximum of
+ * 64 unsigned words) run by one wave on the 64 words of d_in64: d_out192[0..63] =
+ * what each lane got back as the float minimum, [64..127] the float maximum,
+ * [128..191] the unsigned maximum.  All 64 of a helper are the same word. */
+int vh_debug_wave_reduce(const uint32_t* d_in64, uint32_t* d_out192, vhStream_t stream);
 
 /* Self-check of the division the fused integrate pass uses for blocks it has certified (one refined reciprocal shared by
  * the two perspective divisions of a voxel; the same for the blend's division by the weight sum): n pseudo-random

@@ -644,6 +644,42 @@ constexpr int kWave = 64;
 VHD uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
 VHD uint64_t lanemask_lt() { return (1ull << lane_id()) - 1ull; }
 
+// Minimum / maximum over the 64 lanes of a wave, in a scalar register.  For a caller that runs with ALL 64 lanes enabled
+// (a lane without data holds the identity): a disabled lane's register would be read as it stands.  The steps are DPP
+// operands inside the vector unit -- row_shr 1, 2, 4, 8 gather each row of 16 into its lane 15, row_bcast:15 into rows 1
+// and 3 and row_bcast:31 into rows 2 and 3 carry the rows' results on to lane 63, which is read -- one instruction per
+// step where __shfl_xor takes four for the lane address, a trip through LDS and a wait.  A lane the step has no source
+// for (the first lanes of a row, the rows the mask leaves out) is not written and keeps its value.  Written as
+// instructions: from __builtin_amdgcn_update_dpp the compiler makes a copy, a v_mov_b32_dpp and a canonicalising
+// v_max_f32 beside each min or max (four instructions a step).  It does not see into the text, so each step brings the
+// two wait states a DPP operand needs behind the vector instruction that wrote it.  For min and max over values
+// without NaN the order in which lanes meet changes nothing.
+#define VH_WAVE_REDUCE(OP, CONSTRAINT)                                                                        \
+    {                                                                                                         \
+        asm("s_nop 1\n\t" OP " %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf" : CONSTRAINT(v));             \
+        asm("s_nop 1\n\t" OP " %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf" : CONSTRAINT(v));             \
+        asm("s_nop 1\n\t" OP " %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf" : CONSTRAINT(v));             \
+        asm("s_nop 1\n\t" OP " %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf" : CONSTRAINT(v));             \
+        asm("s_nop 1\n\t" OP " %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf" : CONSTRAINT(v));          \
+        asm("s_nop 1\n\t" OP " %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : CONSTRAINT(v));          \
+    }
+VHD float wave_min_f32(float v)
+{
+    VH_WAVE_REDUCE("v_min_f32_dpp", "+v")
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), kWave - 1));
+}
+VHD float wave_max_f32(float v)
+{
+    VH_WAVE_REDUCE("v_max_f32_dpp", "+v")
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), kWave - 1));
+}
+VHD uint32_t wave_max_u32(uint32_t v)
+{
+    VH_WAVE_REDUCE("v_max_u32_dpp", "+v")
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, kWave - 1);
+}
+#undef VH_WAVE_REDUCE
+
 // workgroups of b that cover a (host side: the launchers' grid sizes)
 inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 // the 8x8-pixel tiles of an image: a wave each in alloc, the interval splat's heads and lists, the tile ray caster

@@ -92,6 +92,7 @@ struct HashLookup {
     HashMod hm;
     BlockCache bc;
     static constexpr bool kOffsets32 = false; // (load_voxel)
+    static constexpr bool kGeneral = true;    // a miss may end in the hash table (march_ray, split tiles)
     VHD int find(int bx, int by, int bz) { return cached_lookup(hd, hp, hm, bc, bx, by, bz); }
     // may the sample whose first tap lies in this block be valid?  (occupancy bit of the bucket: one cached dword)
     VHD bool first_tap(int bx, int by, int bz, int& handle)
@@ -153,6 +154,7 @@ struct TileLookup {
     const VhHashData& hd;
     const VhHashParams& hp;
     static constexpr bool kOffsets32 = OFFSETS32;
+    static constexpr bool kGeneral = true;
     VHD static uint32_t slot_of(int bx, int by, int bz)
     {
         // Multiply-shift hash, three full-rate 24-bit multiplies.  The blocks of a tile are a dense slab along its beam;
@@ -217,6 +219,7 @@ template <uint32_t kTileTabSlots, bool OFFSETS32>
 struct TileLookupComplete {
     const int* tab;
     static constexpr bool kOffsets32 = OFFSETS32;
+    static constexpr bool kGeneral = false;
     // handle: the slot of the block (>= 0), or kPtrUnknown
     VHD bool first_tap(int bx, int by, int bz, int& handle) const
     {
@@ -492,6 +495,32 @@ VHD RayQ ray_setup(F3 cam, F3 dir, float voxel, float tFar)
 // (t, dist) -- and the acceptance of its result (:227-229, the two thresholds).  `color` is the last bisection sample's.
 // By value, `success = false; break;` kept: with reference outputs and an early return k_render_large<true, *> loses a wave per SIMD.
 // (a -DVH_RENDER_STATS build counts the plain march only, which has this text in place)
+//
+// One step of the bisection, for a loop or a `do ... while (0)` around it (it leaves with `break` when the sample is invalid).
+// COLOR: blend the sample's colour into COLOUR; STAT: the counters of a -DVH_RENDER_STATS build (the plain march's alone).  The reference reads the colour of the LAST sample alone (trilinear), and a
+// bisection whose sample fails ends in "no hit": the first two steps blend none, the third is peeled off the loop.  (As a
+// scalar branch on the step number inside one loop -- two copies of the blend, or one with the colour part behind a flag --
+// k_render<false, *> went from 8 / 16 to 24..44 bytes of scratch: profiles/README.md.)
+#ifdef VH_RENDER_STATS
+#define VH_STAT_BISECT_SAMPLE statTri += 1.0f; statIter += 1.0f / (float)__popcll(__ballot(1));
+#else
+#define VH_STAT_BISECT_SAMPLE
+#endif
+// CAUTION: the step holds a `break`.  It has to stand directly in the loop (or `do ... while (0)`) it is to leave, never
+// inside another loop or a switch, and `success` has to be tested before any step that follows the loop.
+#define VH_BISECT_STEP(COLOR, CAM, DIR, COLOUR, STAT)                                                                               \
+    {                                                                                                                               \
+        STAT                                                                                                                        \
+        cost += kCostSample;                                                                                                        \
+        c = a + (aDist / (aDist - bDist)) * (b - a); /* findIntersectionLinear :140-143 */                                          \
+        Taps ctp;                                                                                                                   \
+        tap_coords(rq, c, ctp);                                                                                                     \
+        const F3 cpos = mk3((CAM).x + c * (DIR).x, (CAM).y + c * (DIR).y, (CAM).z + c * (DIR).z);                                   \
+        float cDist = 0.0f;                                                                                                         \
+        if (!trilinear<COLOR>(hd, rq.vs, lk, kPtrUnknown, ctp, cpos, rq.rvs, cDist, COLOUR)) { success = false; break; }            \
+        if (aDist * cDist > 0.0f) { a = c; aDist = cDist; }                                                                         \
+        else { b = c; bDist = cDist; }                                                                                              \
+    }
 struct Bisected {
     float alpha;
     uint32_t color;
@@ -505,16 +534,8 @@ VHD Bisected bisect(LK& lk, const VhHashData& hd, const RayQ& rq, float lastAlph
     uint32_t color = 0u;
     bool success = true;
 #pragma unroll 1
-    for (int i = 0; i < 3; i++) {
-        cost += kCostSample;
-        c = a + (aDist / (aDist - bDist)) * (b - a); // findIntersectionLinear :140-143
-        Taps ctp;
-        tap_coords(rq, c, ctp);
-        float cDist = 0.0f;
-        if (!trilinear<true>(hd, rq.vs, lk, kPtrUnknown, ctp, mk3(rq.cam.x + c * rq.dir.x, rq.cam.y + c * rq.dir.y, rq.cam.z + c * rq.dir.z), rq.rvs, cDist, color)) { success = false; break; }
-        if (aDist * cDist > 0.0f) { a = c; aDist = cDist; }
-        else { b = c; bDist = cDist; }
-    }
+    for (int i = 0; i < 2; i++) VH_BISECT_STEP(false, rq.cam, rq.dir, color, )
+    if (success) do VH_BISECT_STEP(true, rq.cam, rq.dir, color, ) while (0);
     Bisected r;
     r.alpha = c;
     r.color = color;
@@ -581,6 +602,21 @@ VHD void march_ray(LK& lk, const VhHashData& hd, const VhHashParams& hp, const V
                 const float nxt = rcur + inc; // the same additions the march makes
                 if (!(nxt < tMid) || !(nxt < rayEnd)) break;
                 rcur = nxt;
+            }
+            // That sample is the near half's last, taken here again for its distance (a sign change across tMid) and paid
+            // for there: what it will be charged below is taken off in advance, so that a lane's two parts add up to the
+            // cost of its ray in a whole tile.  (The counter may wrap below 0: it is only ever added to the near half's.)
+            // For tiles with complete lists and without gradients only: the general lookup's probe brings a copy of the hash
+            // table walk (k_render<false, true> 76 -> 80 registers, the cfg2 frame 1 % slower), and with gradients it costs
+            // k_render<true, *> 32 bytes of scratch and k_render_large<true, *> 14 registers; there a split tile stays dearer
+            // by that one sample at most.
+            if (!LK::kGeneral && !GRADIENTS && rcur < tMid && rcur < tStop) {
+                // (the block of the sample's first tap by tap_coords' exact route alone: this runs once per ray)
+                const F3 pd = mk3((rq.cam.x + rcur * rq.dir.x) - rq.halfVoxel, (rq.cam.y + rcur * rq.dir.y) - rq.halfVoxel, (rq.cam.z + rcur * rq.dir.z) - rq.halfVoxel);
+                int h0 = kPtrUnknown;
+                const bool there = lk.first_tap(vvp_to_block1(world_to_vvp1_rb(pd.x, rq.vs, rq.rvs)), vvp_to_block1(world_to_vvp1_rb(pd.y, rq.vs, rq.rvs)),
+                                                vvp_to_block1(world_to_vvp1_rb(pd.z, rq.vs, rq.rvs)), h0);
+                cost -= 1u + (there ? kCostSample : 0u);
             }
         }
     }
@@ -725,21 +761,14 @@ VHD void march_ray(LK& lk, const VhHashData& hd, const VhHashParams& hp, const V
 #ifdef VH_RENDER_STATS
         const long long tC0 = clock64();
 #endif
+        // (with gradients the three steps stay one loop that blends the colour each time: peeled, k_render<true, *> spills more)
+        if constexpr (GRADIENTS) {
 #pragma unroll 1
-        for (int i = 0; i < 3; i++) {
-#ifdef VH_RENDER_STATS
-            statTri += 1.0f;
-            statIter += 1.0f / (float)__popcll(__ballot(1));
-#endif
-            cost += kCostSample;
-            c = a + (aDist / (aDist - bDist)) * (b - a); // findIntersectionLinear :140-143
-            Taps ctp;
-            tap_coords(rq, c, ctp);
-            const F3 cpos = mk3(worldCamPos.x + c * worldDir.x, worldCamPos.y + c * worldDir.y, worldCamPos.z + c * worldDir.z);
-            float cDist = 0.0f;
-            if (!trilinear<true>(hd, rq.vs, lk, kPtrUnknown, ctp, cpos, rq.rvs, cDist, color2)) { success = false; break; }
-            if (aDist * cDist > 0.0f) { a = c; aDist = cDist; }
-            else { b = c; bDist = cDist; }
+            for (int i = 0; i < 3; i++) VH_BISECT_STEP(true, worldCamPos, worldDir, color2, VH_STAT_BISECT_SAMPLE)
+        } else {
+#pragma unroll 1
+            for (int i = 0; i < 2; i++) VH_BISECT_STEP(false, worldCamPos, worldDir, color2, VH_STAT_BISECT_SAMPLE)
+            if (success) do VH_BISECT_STEP(true, worldCamPos, worldDir, color2, VH_STAT_BISECT_SAMPLE) while (0);
         }
 #ifdef VH_RENDER_STATS
         statCyc[2] += (float)(clock64() - tC0);
@@ -763,6 +792,9 @@ VHD void march_ray(LK& lk, const VhHashData& hd, const VhHashParams& hp, const V
     }
 }
 
+#undef VH_BISECT_STEP
+#undef VH_STAT_BISECT_SAMPLE
+
 // the maps of one pixel (renderKernel DSC/CUDARayCastSDF.cu:18-57; outputs of traverseCoarseGridSimpleSampleAll :236-247)
 VHD void store_ray(const VhRayCastData& rd, const VhDepthCameraParams& cp, size_t pix, uint32_t x, uint32_t y, const RayHit& r, bool gradients)
 {
@@ -773,7 +805,10 @@ VHD void store_ray(const VhRayCastData& rd, const VhDepthCameraParams& cp, size_
         depth = r.alpha / r.depthToRayLength;
         const F3 sk = depth_to_skeleton(cp, x, y, depth);
         depth4 = make_float4(sk.x, sk.y, sk.z, 1.0f);
-        color = make_float4((float)(r.color & 0xffu) / 255.f, (float)((r.color >> 8) & 0xffu) / 255.f, (float)((r.color >> 16) & 0xffu) / 255.f, 1.0f);
+        // (a byte over 255 through the constant's reciprocal: half the instructions of `/`, the same bits for all 256 -- vh_debug_check_fast_math)
+        constexpr float r255 = 1.0f / 255.0f;
+        color = make_float4(div_exact((float)(r.color & 0xffu), 255.0f, r255), div_exact((float)((r.color >> 8) & 0xffu), 255.0f, r255),
+                            div_exact((float)((r.color >> 16) & 0xffu), 255.0f, r255), 1.0f);
         if (gradients) normal = make_float4(r.normal.x, r.normal.y, r.normal.z, 1.0f);
     }
     rd.d_depth[pix] = depth;
@@ -995,16 +1030,22 @@ VHD void render_tile(const VhHashData& hd, const VhHashParams& hp, const VhRayCa
     const uint32_t W = rp.m_width, H = rp.m_height;
     const uint32_t tilesX = (W + 7) / 8, tilesY = (H + 7) / 8;
     const uint32_t nTiles = tilesX * tilesY;
-    const uint32_t waveIdx = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave)));
+    const uint32_t waveIdx = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (256u / kWave) + (threadIdx.x / kWave))); // (workgroups of 256: tileTab)
     // Launch order.  The kernel is as long as its busiest SIMD, and a SIMD's waves are the workgroups i, i+numCUs,
     // i+2 numCUs, ... in launch order.  k_interval_splat sorts the tiles by the cost the previous frame measured
     // (it differs little) and deals them to the workgroups so that the sums come out even.  The schedule carries the
     // phase it was made for: one that was not refreshed for this call is ignored (raster order).
     uint32_t tile = waveIdx, half = 0u; // half: 0 whole tile, 1 / 2 near / far half of a split tile (all four waves of a workgroup or none)
-    if (sched && sched[0] == phase) {
-        const uint2 e = reinterpret_cast<const uint2*>(sched + 4 + 4u * ((nTiles + 3u) / 4u))[waveIdx];
-        tile = e.y == phase ? (e.x & 0xffffffu) : nTiles; // a slot the dealing left empty (last, partial workgroup)
-        half = e.y == phase ? (e.x >> 24) : 0u;
+    if (sched) {
+        // The wave's slot is asked for together with the schedule's phase, not behind it: where the slot lies depends on the
+        // image and the wave alone (the launcher has seen to it that it lies inside the schedule for every wave of the grid,
+        // whatever the schedule holds).  Both are used without a branch between them, so neither load waits for the other.
+        const uint32_t made = sched[0];
+        const unsigned long long ev = reinterpret_cast<const unsigned long long*>(sched + 4 + 4u * ((nTiles + 3u) / 4u))[waveIdx]; // {tile | half << 24, phase}
+        const uint2 e = make_uint2((uint32_t)ev, (uint32_t)(ev >> 32));
+        const bool fresh = made == phase, dealt = e.y == phase;
+        tile = fresh ? (dealt ? (e.x & 0xffffffu) : nTiles) : waveIdx; // (nTiles: a slot the dealing left empty -- last, partial workgroup)
+        half = fresh && dealt ? (e.x >> 24) : 0u;
     }
     if (tile >= nTiles) return;
 #if defined(VH_KNOCKOUT) && VH_KNOCKOUT == 41 // measurement build: every wave's life, read by tools/render_stamps.py
@@ -1139,17 +1180,14 @@ VHD void render_tile(const VhHashData& hd, const VhHashParams& hp, const VhRayCa
                     zhi = fmaxf(zhi, b + zs);
                 }
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                zlo = fminf(zlo, __shfl_xor(zlo, off));
-                zhi = fmaxf(zhi, __shfl_xor(zhi, off));
-            }
             if (!complete) { // {+inf, 0} if nothing overflowed
                 zlo = fminf(zlo, __uint_as_float(head.x));
                 zhi = fmaxf(zhi, __uint_as_float(head.y));
             }
-            tileZmin = fmaxf(zlo, 0.0f);  // an empty list leaves {+inf, -inf}: nothing to march
-            tileZmax = zhi;
+            // (all 64 lanes are here, those without an entry with the identity.  The clamp at 0 comes before the reduction:
+            // behind it, k_render<true, true> puts one more scalar register aside)
+            tileZmin = wave_min_f32(fmaxf(zlo, 0.0f)); // an empty list leaves {+inf, -inf}: nothing to march
+            tileZmax = wave_max_f32(zhi);
         }
     }
     // (the same in every lane: kept in scalar registers while the rays are set up)
@@ -1174,8 +1212,10 @@ VHD void render_tile(const VhHashData& hd, const VhHashParams& hp, const VhRayCa
             march_ray<GRADIENTS, kPipelined>(lk, hd, hp, cp, rp, x, y, tileZmin, tileZmax, half, 0.5f * (tileZmin + tileZmax), out, cost VH_STAT_ARGS);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cost = max(cost, (uint32_t)__shfl_xor((int)cost, off));
+    // A tile's cost is its dearest ray's.  Without gradients a split tile's is formed below, per lane over both halves, so that
+    // it leaves the same class whether it was split or not.  With gradients the halves' dearest rays are added up, as they
+    // always were: formed per lane, k_render<true, true> spills 16 registers more (2 352 bytes of scratch against 2 336).
+    if constexpr (GRADIENTS) cost = wave_max_u32(cost); // (all 64 lanes are here: those outside the image or the interval hold 0)
     // The pixel is worked out again rather than kept: every vector register that lives across the march is one the
     // march cannot use, and at this budget one it spills.  (lane_id_again: the same number from instructions of its own.)
     const uint32_t laneAfter = lane_id_again();
@@ -1191,23 +1231,28 @@ VHD void render_tile(const VhHashData& hd, const VhHashParams& hp, const VhRayCa
             mine[laneAfter * 8u + 1u] = __float_as_int(out.alpha);
             mine[laneAfter * 8u + 2u] = (int)out.color;
             if (GRADIENTS) { mine[laneAfter * 8u + 3u] = __float_as_int(out.normal.x); mine[laneAfter * 8u + 4u] = __float_as_int(out.normal.y); mine[laneAfter * 8u + 5u] = __float_as_int(out.normal.z); }
-            if (laneAfter == 0) mine[64u * 8u] = (int)cost;
+            if constexpr (GRADIENTS) { if (laneAfter == 0) mine[64u * 8u] = (int)cost; }
+            else mine[laneAfter * 8u + 6u] = (int)cost;
         }
         __syncthreads(); // all four waves of this workgroup are halves of split tiles (schedule_tiles)
         if (half == 2u) { VH_WAVE_STAMP(cost) return; }
+        // a lane adds the far half's part of its ray to its own, unless the ray ended in the near half (a whole tile would not
+        // have marched it further)
+        if constexpr (!GRADIENTS) { if (!out.hit) cost += (uint32_t)other[laneAfter * 8u + 6u]; }
         if (!out.hit && other[laneAfter * 8u + 0u] != 0) {
             out.hit = true;
             out.alpha = __int_as_float(other[laneAfter * 8u + 1u]);
             out.color = (uint32_t)other[laneAfter * 8u + 2u];
             if (GRADIENTS) out.normal = mk3(__int_as_float(other[laneAfter * 8u + 3u]), __int_as_float(other[laneAfter * 8u + 4u]), __int_as_float(other[laneAfter * 8u + 5u]));
         }
-        cost += (uint32_t)other[64u * 8u];
+        if constexpr (GRADIENTS) cost += (uint32_t)other[64u * 8u];
         if (laneAfter == 0) heads[tile] = make_uint4(0x7f800000u, 0u, 0u, 0u);
     }
     if (inImage) {
         store_ray(rd, cp, pix, x, y, out, GRADIENTS);
         VH_STAT_STORE
     }
+    if constexpr (!GRADIENTS) cost = wave_max_u32(cost); // (all 64 lanes again; the far half of a split tile has left)
     VH_WAVE_STAMP(cost)
     if (sched && laneAfter == 0) sched[4 + tile] = min(cost / kCostClassWidth, kCostClasses - 1u); // plain store: nobody waits for it
 }
@@ -1234,16 +1279,27 @@ struct CoAlloc {
     uint32_t firstGroup; // 0: nothing to co-launch
 };
 
-VHD bool co_alloc(const CoAlloc& job)
+VHD bool co_alloc(const CoAlloc& job, uint32_t firstGroup)
 {
-    if (job.firstGroup == 0u || blockIdx.x < job.firstGroup) return false;
-    const uint32_t g = blockIdx.x - job.firstGroup;
+    if (firstGroup == 0u || blockIdx.x < firstGroup) return false;
+    const uint32_t g = blockIdx.x - firstGroup;
     if (g == 0u && threadIdx.x == 0) job.hd.d_hashCompactifiedCounter[0] = 0; // as k_alloc
     alloc_tile(job.hd, job.hp, job.cam, job.cp, job.bitMask, job.lockToken, job.hm, job.packed, g * (256u / kWave) + (threadIdx.x / kWave));
     return true;
 }
 // alloc's workgroups as a rider (host): the ray caster's workgroups of 256, four tiles each (on its own: alloc_groups)
 inline uint32_t co_alloc_groups(uint32_t tiles) { return cdiv(tiles, 256u / kWave); }
+
+// The kernel arguments a ray-casting wave reads before it knows its tile, asked for in one go at the kernel's entry, beside
+// the one that tells a rider from a ray caster: left to the compiler each is loaded where it is first used, behind the
+// branch before it, and the wave waits for one after the other (entry -> image size and schedule -> phase -> heads and
+// lists -> capacity).  (An empty statement that names them as scalar-register operands: they have to be there by then.)
+VHD uint32_t render_start(const VhRayCastParams& rp, uint4* heads, const int4* lists, uint32_t cap, uint32_t* sched, uint32_t phase, const CoAlloc& job)
+{
+    uint32_t firstGroup = job.firstGroup;
+    asm("" : "+s"(firstGroup) : "s"(rp.m_width), "s"(rp.m_height), "s"(heads), "s"(lists), "s"(cap), "s"(sched), "s"(phase));
+    return firstGroup;
+}
 
 // small tables: all tiles of a 640x480 frame resident at once (4800 + 256 waves <= 6 x 4 x 256) -- the march is a
 // latency chain, and a second round of waves costs as much as the first -- and the riders behind them find free
@@ -1258,7 +1314,7 @@ void k_render(VhHashData hd, VhHashParams hp, VhRayCastData rd, VhDepthCameraPar
               uint4* heads, const int4* lists, uint32_t cap, uint32_t* sched, uint32_t phase, CoAlloc job)
 {
     __shared__ int tileTab[256 / kWave][2u * VH_TILE_LIST_CAPACITY * kTileSlotWords];
-    if (co_alloc(job)) return;
+    if (co_alloc(job, render_start(rp, heads, lists, cap, sched, phase, job))) return;
     render_tile<GRADIENTS, VH_TILE_LIST_CAPACITY, OFFSETS32>(hd, hp, rd, cp, rp, heads, lists, cap, sched, phase, tileTab);
 }
 
@@ -1269,7 +1325,7 @@ void k_render_large(VhHashData hd, VhHashParams hp, VhRayCastData rd, VhDepthCam
                     uint4* heads, const int4* lists, uint32_t cap, uint32_t* sched, uint32_t phase, CoAlloc job)
 {
     __shared__ int tileTab[256 / kWave][2u * VH_TILE_LIST_CAPACITY_LARGE * kTileSlotWords];
-    if (co_alloc(job)) return;
+    if (co_alloc(job, render_start(rp, heads, lists, cap, sched, phase, job))) return;
     render_tile<GRADIENTS, VH_TILE_LIST_CAPACITY_LARGE, OFFSETS32>(hd, hp, rd, cp, rp, heads, lists, cap, sched, phase, tileTab);
 }
 
@@ -1486,6 +1542,11 @@ int vh_render_intervals_co(const VhHashData* hd, const VhHashParams* hp, const V
     // the capacity of the lists picks the table size: up to VH_TILE_LIST_CAPACITY the small tables, beyond it the large ones
     const bool large = cap > (uint32_t)VH_TILE_LIST_CAPACITY;
     uint32_t groups = cdiv(tiles + (d_schedule ? split_tiles(tiles) : 0u), 4);
+    // Every ray-casting wave reads its launch slot, whatever phase the schedule holds -- a stale schedule's slots are read
+    // too, and only then ignored.  The size of the caller's buffer is not known here: the contract is that d_schedule holds
+    // vh_render_schedule_bytes(width, height), and this keeps the grid inside that figure should either formula change.
+    if (d_schedule && (size_t)(4u + 4u * cdiv(tiles, 4) + 2u * 4u * groups) * sizeof(uint32_t) > vh_render_schedule_bytes(rp->m_width, rp->m_height))
+        return VH_ERR_BAD_ARGUMENT;
     CoAlloc job;
     std::memset(&job, 0, sizeof(job));
     if (fj && !fj->allocLaunched && fj->cam.d_depthData && fj->hashData.d_hash && fj->hashParams.m_hashNumBuckets >= 2) {

@@ -81,11 +81,25 @@ __global__ __launch_bounds__(256) void k_check_fast_math(float b, HashMod hm, ui
     if (__float_as_uint(q0) != __float_as_uint(q1) && !(q0 == 0.0f && q1 == 0.0f)) atomicAdd(&mismatches[0], 1u);
     if ((s % hm.d) != umod_fast(s, hm)) atomicAdd(&mismatches[1], 1u);
     if ((u % hm.d) != umod_fast(u, hm)) atomicAdd(&mismatches[1], 1u);
+    if (i < 256u) { // every colour byte over 255 (store_ray)
+        const float c = (float)i;
+        if (__float_as_uint(c / 255.f) != __float_as_uint(div_exact(c, 255.0f, 1.0f / 255.0f))) atomicAdd(&mismatches[0], 1u);
+    }
     if (i < 64u) { // extremes of the unsigned range
         const uint32_t e = 0xffffffffu - i;
         if ((e % hm.d) != umod_fast(e, hm)) atomicAdd(&mismatches[1], 1u);
         if ((i % hm.d) != umod_fast(i, hm)) atomicAdd(&mismatches[1], 1u);
     }
+}
+
+// the wave reductions of vh_device.hpp on one wave's 64 words: what each lane got back from each helper
+__global__ __launch_bounds__(64) void k_wave_reduce(const uint32_t* __restrict__ in, uint32_t* __restrict__ out)
+{
+    const uint32_t lane = lane_id();
+    const uint32_t w = in[lane];
+    out[lane] = __float_as_uint(wave_min_f32(__uint_as_float(w)));
+    out[kWave + lane] = __float_as_uint(wave_max_f32(__uint_as_float(w)));
+    out[2 * kWave + lane] = wave_max_u32(w);
 }
 
 } // namespace
@@ -113,6 +127,13 @@ int vh_debug_check_fast_math(float divisor, uint32_t modulus, uint32_t n, uint32
     VH_HIP(hipMemsetAsync(d_mismatches, 0, 2 * sizeof(uint32_t), (hipStream_t)stream));
     if (n == 0) return VH_OK;
     k_check_fast_math<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(divisor, make_hash_mod(modulus), n, seed, d_mismatches);
+    return vh_last_launch_error();
+}
+
+int vh_debug_wave_reduce(const uint32_t* d_in64, uint32_t* d_out192, vhStream_t stream)
+{
+    if (!d_in64 || !d_out192) return VH_ERR_BAD_ARGUMENT;
+    k_wave_reduce<<<1, kWave, 0, (hipStream_t)stream>>>(d_in64, d_out192);
     return vh_last_launch_error();
 }
 

@@ -75,6 +75,7 @@ PROTOTYPES = {
     "vh_synth_frame": (C.c_int, [_VP, C.c_int, C.c_int, _F16, P(T.DepthCameraParams), _VP, _VP, _VP]),
     "vh_debug_hash_ops": (C.c_int, [P(T.HashData), P(T.HashParams), _VP, _VP, C.c_uint32, _VP]),
     "vh_debug_check_fast_math": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, _VP, _VP]),
+    "vh_debug_wave_reduce": (C.c_int, [_VP, _VP, _VP]),
     "vh_debug_valu_probe": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _VP, P(C.c_uint32), _VP]),
     "vh_debug_check_refined_division": (C.c_int, [C.c_uint32, C.c_uint32, _VP, _VP]),
     "vh_debug_check_weighted_colour": (C.c_int, [_VP, _VP]),
