@@ -714,6 +714,7 @@ struct MeshData {
 
 struct VhMeshNormals;    // opaque: the buffers of the vertex-normal pass (csrc/vh_mesh_normals.hpp)
 struct VhMeshComponents; // opaque: the buffers of the component pass (csrc/vh_mesh_components.hpp)
+struct VhMeshCluster;    // opaque: the buffers of the vertex clustering (csrc/vh_mesh_cluster.hpp)
 
 class CUDAMarchingCubesHashSDF {
 public:
@@ -764,7 +765,7 @@ public:
     // of the last accumulated extraction: the VH_WELD_ACCUM_NUM_COUNTS counts of vh_types.h; 0 after a one-shot one
     void getIndexedStats(unsigned int out[6]) const { for (int i = 0; i < 6; i++) out[i] = m_indexed.accumulated ? m_indexed.counts[i] : 0u; }
     bool isWelded() const { return m_welded; }
-    void getIndexedCounts(unsigned int out[3]) const { for (int i = 0; i < 3; i++) out[i] = i < 2 && m_indexed.filtered ? m_indexed.kept[i] : m_indexed.counts[i]; }
+    void getIndexedCounts(unsigned int out[3]) const { for (int i = 0; i < 3; i++) out[i] = i < 2 && m_indexed.filtered ? m_indexed.kept[i] : i < 2 && m_indexed.clustered ? m_indexed.clusterStats[i] : m_indexed.counts[i]; }
     void downloadIndexed(VhVertex* vertices, uint64_t* keys, uint32_t* faces); // device mesh of the last indexed extraction
     // Vertex normals of the indexed mesh ("Vertex normals"), off by default.  When on, the three
     // indexed extractions run vh_mesh_vertex_normals after the weld -- finishIndexed over the whole accumulation -- with
@@ -781,6 +782,15 @@ public:
     void setIndexedComponentFilter(unsigned int minFaces, bool largestOnly) { m_componentMinFaces = minFaces; m_componentLargestOnly = largestOnly; }
     // the VH_COMPONENTS_NUM_COUNTS counts of the mesh in the buffer; 0 when it was made with the filter off, or is no longer the weld's
     void getIndexedComponentStats(unsigned int out[6]) const { for (int i = 0; i < 6; i++) out[i] = m_indexed.componentStats[i]; }
+    // Decimation of the indexed mesh by vertex clustering ("Mesh clustering"), off by default (0).
+    // With cellsPerCluster = 1 ... 64, readBackIndexed -- the one-shot extraction, finishIndexed and the chunk-grid walk
+    // alike -- runs vh_mesh_cluster after the weld and BEFORE normals and components, which then work on the clustered
+    // mesh: getIndexedCounts, downloadIndexed, downloadIndexedNormals, the mesh buffer and saveMesh describe the
+    // clustered mesh (the filtered one, when the component filter is on too).  A status of the pass throws and leaves
+    // the buffer empty.  Throws VH_ERR_BAD_ARGUMENT above 64.
+    void setIndexedClustering(unsigned int cellsPerCluster);
+    // the VH_CLUSTER_NUM_COUNTS counts of the mesh in the buffer; 0 when it was made with clustering off, or is no longer the weld's
+    void getIndexedClusterStats(unsigned int out[6]) const { for (int i = 0; i < 6; i++) out[i] = m_indexed.clusterStats[i]; }
     void downloadSources(VhTriangleSource* out, unsigned int n);               // source records of the last indexed extraction
 
     const vh::MeshData& getMeshData() const { return m_meshData; }
@@ -820,6 +830,9 @@ private:
     unsigned int m_componentMinFaces = 0;
     bool m_componentLargestOnly = false;
     std::unique_ptr<VhMeshComponents> m_components;
+    // vertex clustering: the one-shot extraction's buffers (csrc/vh_mesh_cluster.hpp) are made by its first call with the option on
+    unsigned int m_clusterCells = 0;
+    std::unique_ptr<VhMeshCluster> m_cluster;
     struct IndexedResult {                      // what the last indexed extraction left; the empty one is the state after an error
         unsigned int counts[VH_WELD_ACCUM_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 }; // {vertices, faces, status}, then the accumulation's three
         unsigned int numSourced = 0;            // triangles of its last sourced pass 2 that are in the buffer
@@ -829,12 +842,14 @@ private:
         bool filtered = false;                  // the component filter ran: the mesh is kept[] = {vertices, faces} of the filter's own buffers
         unsigned int kept[2] = { 0, 0 };
         unsigned int componentStats[VH_COMPONENTS_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
+        bool clustered = false;                 // the clustering ran: normals and components are of ITS mesh, clusterStats[0 .. 1] vertices and faces
+        unsigned int clusterStats[VH_CLUSTER_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
     } m_indexed;
-    void clearWeldedMark() { m_welded = false; for (unsigned int& c : m_indexed.componentStats) c = 0; }
+    void clearWeldedMark() { m_welded = false; for (unsigned int& c : m_indexed.componentStats) c = 0; for (unsigned int& c : m_indexed.clusterStats) c = 0; }
     void resetIndexed() { clearMeshBuffer(); m_indexed = IndexedResult(); }
-    // the welded mesh on the device (m_accum's, or m_weld's) into the mesh buffer, with normals at that scale if the
-    // option is on; then its counts and marks
-    void readBackIndexed(unsigned int numVertices, unsigned int numFaces, bool accumulated, int32_t scaleLog2);
+    // the welded mesh on the device (m_accum's, or m_weld's) through the passes that are on -- clustering, normals,
+    // components, at the scales of that voxel size -- into the mesh buffer; then its counts and marks
+    void readBackIndexed(unsigned int numVertices, unsigned int numFaces, bool accumulated, float voxelSize);
 };
 
 

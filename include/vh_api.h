@@ -58,7 +58,8 @@ int vh_time_next_launch(void* startEvent, void* stopEvent);
  * vh_mesh_weld_accum_append insert, settle, faces; vh_mesh_vertex_normals and vh_mesh_weld_accum_normals faces, finish;
  * vh_mesh_components init, hook, flatten, count (init alone without faces); vh_mesh_components_filter stats, with
  * largestOnly pick by key and pick by index, compact vertices, compact faces (not without faces);
- * vh_mesh_weld_accum_components the launches of vh_mesh_components, then those of vh_mesh_components_filter. */
+ * vh_mesh_weld_accum_components the launches of vh_mesh_components, then those of vh_mesh_components_filter;
+ * vh_mesh_cluster and vh_mesh_weld_accum_cluster insert, faces, number, emit (insert and number alone without faces). */
 int vh_time_launch_after(uint32_t skip, void* startEvent, void* stopEvent);
 int vh_stream_create(vhStream_t* out);   /* a non-blocking HIP stream, for FFI users without a HIP binding */
 int vh_stream_destroy(vhStream_t stream);
@@ -773,6 +774,34 @@ int vh_mesh_components_filter(const VhVertex* d_vertices, const uint64_t* d_keys
                               uint32_t numFaces, const uint32_t* d_root, const uint32_t* d_faceCount, const uint32_t* d_status, uint32_t minFaces,
                               uint32_t largestOnly, uint32_t* d_newIndex, uint64_t* d_best, VhVertex* d_outVertices, uint64_t* d_outKeys,
                               float* d_outNormals, uint32_t* d_outFaces, uint32_t* d_counts, vhStream_t stream);
+/* ---- decimation of an indexed mesh by vertex clustering (csrc/vh_mesh_cluster.hip; DESIGN.md section 4, "Mesh
+ * clustering").  The lattice of voxel corners is cut into cubes of cellsPerCluster = m points a side (1 <= m <= 64).
+ * A vertex belongs to the cube of its key's lattice point L, whatever the key's code: k = floor(L / m) per component
+ * (floor, not truncation), and the cube's key is k packed as a lattice point with code 3.  All vertices of a cube
+ * become one vertex, at the integer mean floor((2 sum + n) / (2 n)) of q = rint(p * 2^scaleLog2) (colours: 2^16),
+ * turned back into a float with one rounding; its key is the cube's.  A face with two corners in one cube is dropped
+ * (collapsed); of the faces over the same three cubes one is kept (the others: duplicates) -- if both windings occur,
+ * the one which, rotated so that the smallest cube key comes first, has the smaller key second.  A cube that no kept
+ * face names gives no vertex (unused).  No float is added anywhere: the result does not depend on the order of the
+ * input or of the atomics; vertex and face order of the output do.
+ * vh_mesh_cluster_key: the cube's key of a vertex key.  VH_ERR_BAD_ARGUMENT for m outside 1 ... 64 and for a key with
+ * bit 62 or 63 set. */
+int vh_mesh_cluster_key(uint64_t vertexKey, uint32_t cellsPerCluster, uint64_t* key);
+/* 16 - floor(log2(voxelSize)): lattice positions within the key range, scaled, then stay under 2^36 and a quantum is
+ * below 2^-16 voxel.  4 cm -> 21, 1 cm -> 23.  VH_ERR_BAD_ARGUMENT for a voxel size that is not finite or not positive. */
+int vh_mesh_cluster_default_scale_log2(float voxelSize, int32_t* scaleLog2);
+/* log2 of the table size the pass wants for `count` vertices (cluster table) or faces (face table): the smallest power
+ * of two >= 2 count, 64 slots at least.  VH_ERR_BAD_ARGUMENT above 2^30. */
+int vh_mesh_cluster_default_slots_log2(uint32_t count, uint32_t* slotsLog2);
+/* The pass, over the caller's mesh and the caller's buffers (VhMeshClusterData, vh_types.h): insert (one lane per
+ * vertex), faces (one lane per face; not without faces), number (one lane per cluster slot), emit (one lane per face
+ * slot; not without faces).  data->m_clusterSlotsLog2 / m_faceSlotsLog2 say how much of the tables is used (a smaller
+ * value than the default fills a table: VH_CLUSTER_TABLE_FULL).  data->d_counts: the VH_CLUSTER_NUM_COUNTS counts;
+ * with a status set (VH_CLUSTER_*) the other five are 0 and nothing was written.  Callers map VH_CLUSTER_TABLE_FULL to
+ * VH_ERR_STAGING_OVERFLOW and every other bit to VH_ERR_BAD_ARGUMENT.  Asynchronous on `stream`; numVertices = 0
+ * launches nothing.  The mesh that went in stays as it is. */
+int vh_mesh_cluster(const VhVertex* d_vertices, const uint64_t* d_keys, const uint32_t* d_faces, uint32_t numVertices, uint32_t numFaces,
+                    uint32_t cellsPerCluster, int32_t scaleLog2, const VhMeshClusterData* data, vhStream_t stream);
 /* Host only: vh::MeshData::applyTransform (when transform is not NULL) and saveToPLY on the caller's arrays.
  *   vertices3, colors4 (may be NULL), normals3 (may be NULL)   numVertices rows each
  *   faceIndices   numFaceIndices = 3 per face; 0 = a triangle soup
@@ -834,6 +863,21 @@ int vh_mesh_weld_accum_components_get_counts(VhMeshWeldAccum* accum, uint32_t ou
 int vh_mesh_weld_accum_components_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint64_t* keys, float* normals, uint32_t* faces,
                                            uint32_t numVertices, uint32_t numFaces, vhStream_t stream);
 
+/* The vertex clustering over the accumulated mesh (vh_mesh_cluster): a pass at the end, never per append, because a
+ * cluster spans appends.  Waits for the appends, launches, and waits for the counts; the buffers are the
+ * accumulator's own, and its welded mesh, counts and downloads stay what they are.  After a pass without a status,
+ * vh_mesh_weld_accum_normals and vh_mesh_weld_accum_components work on the CLUSTERED mesh until the next begin or
+ * append; a pass makes earlier normals and components stale.  cellsPerCluster = 0 launches nothing and forgets the last
+ * pass: normals and components are of the welded mesh again, and the pass's reads are refused. */
+int vh_mesh_weld_accum_cluster(VhMeshWeldAccum* accum, uint32_t cellsPerCluster, int32_t scaleLog2, vhStream_t stream);
+/* Waits and reads the VH_CLUSTER_NUM_COUNTS counts.  VH_ERR_BAD_ARGUMENT when no pass has run since the last begin or
+ * append (its result would be stale) or the pass left a status, VH_ERR_STAGING_OVERFLOW when that status is a full
+ * table alone; the other five counts are then 0. */
+int vh_mesh_weld_accum_cluster_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream);
+/* The clustered mesh; each array may be NULL.  numVertices / numFaces: at most those of the counts.  Refused as above. */
+int vh_mesh_weld_accum_cluster_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint64_t* keys, uint32_t* faces, uint32_t numVertices,
+                                        uint32_t numFaces, vhStream_t stream);
+
 /* handle level: CUDAMarchingCubesHashSDF (DSC/CUDAMarchingCubesHashSDF.h:8-67) */
 typedef struct VhMarchingCubes VhMarchingCubes;
 int vh_marching_cubes_create(const VhMarchingCubesParams* params, vhStream_t stream, VhMarchingCubes** out);
@@ -893,6 +937,15 @@ int vh_marching_cubes_set_indexed_component_filter(VhMarchingCubes* mc, uint32_t
 /* of the last indexed extraction with the filter on: the VH_COMPONENTS_NUM_COUNTS counts, which say what the
  * unfiltered mesh held; all 0 when it ran with the filter off */
 int vh_marching_cubes_get_indexed_component_stats(VhMarchingCubes* mc, uint32_t out[6]);
+/* The vertex clustering for the indexed extractions (off by default: cellsPerCluster = 0; 1 ... 64 turn it on).  When
+ * on, the three indexed extractions run vh_mesh_cluster after the weld and BEFORE normals and components -- the
+ * accumulated ones at the finish -- at vh_mesh_cluster_default_scale_log2(voxelSize); normals (at the scale of
+ * 2 cellsPerCluster voxelSize) and components are then of the clustered mesh, and get_indexed_counts, download_indexed,
+ * download_indexed_normals, the host mesh and save_mesh all describe it.  A status of the pass: VH_ERR_BAD_ARGUMENT or
+ * VH_ERR_STAGING_OVERFLOW, the host mesh empty.  VH_ERR_BAD_ARGUMENT for cellsPerCluster > 64. */
+int vh_marching_cubes_set_indexed_clustering(VhMarchingCubes* mc, uint32_t cellsPerCluster);
+/* of the last indexed extraction with clustering on: the VH_CLUSTER_NUM_COUNTS counts; all 0 when it ran with it off */
+int vh_marching_cubes_get_indexed_cluster_stats(VhMarchingCubes* mc, uint32_t out[6]);
 /* the first n source records of the last indexed extraction (n <= min(triangles produced, m_maxNumTriangles)) */
 int vh_marching_cubes_download_sources(VhMarchingCubes* mc, VhTriangleSource* out, uint32_t n);
 int vh_marching_cubes_copy_triangles_to_cpu(VhMarchingCubes* mc);

@@ -240,6 +240,42 @@ enum {
     VH_COMPONENTS_NUM_COUNTS = 6
 };
 
+/* status word of the vertex clustering (vh_mesh_cluster); any bit leaves the output empty and the other counts 0 */
+#define VH_CLUSTER_TABLE_FULL 1u /* the cluster table or the face table has no free slot left */
+#define VH_CLUSTER_BAD_KEY 2u    /* a vertex key with bit 62 or 63 set: no vertex key */
+#define VH_CLUSTER_RANGE 4u      /* a scaled position or colour is not finite or exceeds 2^40 in a component: scaleLog2 is too large */
+#define VH_CLUSTER_BAD_INDEX 8u  /* a face index >= numVertices (nothing was read through it; the face contributes nothing) */
+#define VH_CLUSTER_MAX_CELLS 64u /* cellsPerCluster is 1 ... 64: a cluster then holds at most 2^20 keys and its sums stay below 2^60 */
+/* what vh_mesh_cluster counts */
+enum {
+    VH_CLUSTER_VERTICES = 0,   /* vertices of the clustered mesh: the clusters that a kept face names */
+    VH_CLUSTER_FACES = 1,      /* faces of the clustered mesh */
+    VH_CLUSTER_STATUS = 2,
+    VH_CLUSTER_COLLAPSED = 3,  /* faces dropped because two of their vertices fell into one cluster */
+    VH_CLUSTER_DUPLICATES = 4, /* faces dropped because another face over the same three clusters was kept */
+    VH_CLUSTER_UNUSED = 5,     /* clusters that no kept face names: they give no vertex */
+    VH_CLUSTER_NUM_COUNTS = 6
+};
+/* Device buffers of the vertex clustering (vh_mesh_cluster): the caller's, sized for the mesh that goes in.  The
+ * cluster table has 1 << m_clusterSlotsLog2 slots (at least twice the vertices), the face table 1 << m_faceSlotsLog2
+ * (at least twice the faces); the launcher empties what it uses of them. */
+typedef struct VhMeshClusterData {
+    uint64_t* d_clusterKeys;   /* per cluster slot: the cluster key, all ones = empty */
+    int64_t* d_clusterSums;    /* 6 per cluster slot: position and colour of the members in fixed point */
+    uint32_t* d_clusterCount;  /* per cluster slot: its members */
+    uint32_t* d_clusterIndex;  /* per cluster slot: named by a kept face (0 / 1), then its vertex in the output or all ones */
+    uint32_t* d_vertexSlot;    /* per vertex of the input: its cluster's slot */
+    uint64_t* d_facePairs;     /* per face slot: the two smaller cluster slots of the triple, all ones = empty */
+    uint32_t* d_faceThirds;    /* per face slot: the largest cluster slot of the triple, all ones = empty */
+    uint32_t* d_faceWindings;  /* per face slot: bit 0 / bit 1 = a face of this / the other winding fell here */
+    uint32_t* d_work;          /* 2 words */
+    VhVertex* d_vertices;      /* out: room for as many vertices as go in */
+    uint64_t* d_keys;          /* out: the cluster keys of d_vertices */
+    uint32_t* d_faces;         /* out: room for as many faces as go in */
+    uint32_t* d_counts;        /* VH_CLUSTER_NUM_COUNTS words */
+    uint32_t m_clusterSlotsLog2, m_faceSlotsLog2;
+} VhMeshClusterData;
+
 /* Device buffers of the weld (vh_mesh_weld): an open-addressing table of numSlots = 1 << m_slotsLog2 slots, and the
  * indexed mesh it produces.  Sized for m_maxTriangles triangles, that is 3 * m_maxTriangles vertices at worst. */
 typedef struct VhMeshWeldData {

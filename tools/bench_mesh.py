@@ -33,6 +33,13 @@ download of the welded mesh and the labelling of tests/mesh_components.py on the
 extraction with the filter on beside the one with it off.
 
     python tools/bench_mesh.py --indexed --components [--normals] [--config cfg3]
+
+--cluster M (with --indexed) adds the vertex clustering ("Mesh clustering") at M lattice points a
+side: each of its four kernels by vh_time_launch_after, the pass as a share of the indexed extraction's kernels,
+vertices, faces and download size before and after, and the wall time of the extraction with clustering on beside the
+one with it off.  With --streamed: the pass over the finished accumulation, and the indexed walk with it on.
+
+    python tools/bench_mesh.py --indexed --cluster 2 [--streamed] [--config cfg3]
 """
 import argparse
 import ctypes as C
@@ -140,6 +147,28 @@ def indexed_report(args, scene, hp):
         out.update(host_labelling_download_s=round(t_down, 5), host_labelling_s=round(t_host, 5))
         for b in bufs:
             b.free()
+    if args.cluster:
+        scale = E.mesh_cluster_default_scale_log2(hp.m_virtualVoxelSize)
+        logs = [C.c_uint32(), C.c_uint32()]
+        for count, log in zip((V, F), logs):
+            lib.check(L.vh_mesh_cluster_default_slots_log2(count, C.byref(log)), "vh_mesh_cluster_default_slots_log2")
+        logs = [int(log.value) for log in logs]
+        cs, fs = 1 << logs[0], 1 << logs[1]
+        bufs = [lib.DeviceBuffer(n) for n in (8 * cs, 48 * cs, 4 * cs, 4 * cs, 4 * V, 8 * fs, 4 * fs, 4 * fs, 8, 24 * V, 8 * V, 12 * F, 24)]
+        cd = T.MeshClusterData(*[b.ptr for b in bufs], logs[0], logs[1])
+        run = lambda: lib.check(L.vh_mesh_cluster(w.d_vertices, w.d_keys, w.d_faces, V, F, args.cluster, scale, C.byref(cd), None), "vh_mesh_cluster")
+        names = ["cluster_insert_us", "cluster_faces_us", "cluster_number_us", "cluster_emit_us"]
+        for skip, name in enumerate(names):
+            out[name] = timed(skip, run)
+        stats = {k: int(v) for k, v in zip(T.CLUSTER_COUNTS, bufs[12].download(np.uint32, 6))}
+        assert stats["status"] == 0, "the clustering left a status"
+        total = sum(out[k] for k in names)
+        kernels = out["pass2_sourced_us"] + out["weld_insert_us"] + out["weld_number_us"] + out["weld_faces_us"]
+        out.update(cluster=stats, cluster_cells=args.cluster, cluster_scale_log2=scale, cluster_pass_us=round(total, 2),
+                   cluster_share_of_indexed_kernels=round(total / (kernels + total), 4),
+                   cluster_device_bytes=sum(b.nbytes for b in bufs), download_bytes_clustered=24 * stats["vertices"] + 12 * stats["faces"])
+        for b in bufs:
+            b.free()
     L.vh_mesh_weld_data_free(C.byref(w))
     L.vh_marching_cubes_data_free(C.byref(data))
     # the host merge on the same soup: saveMesh = merge + PLY; the PLY alone is timed on the indexed mesh and taken off
@@ -177,6 +206,19 @@ def indexed_report(args, scene, hp):
                         walls[on].append(time.perf_counter() - t0)
             spread = lambda v: [round(float(np.min(v)), 5), round(float(np.median(v)), 5), round(float(np.max(v)), 5)]
             out.update(extract_indexed_filter_off_wall_s=spread(walls[False]), extract_indexed_filter_on_wall_s=spread(walls[True]))
+        if args.cluster:  # the whole extraction, clustering off and on, alternating (the first pair sizes the buffers)
+            mc.setIndexedNormals(bool(args.normals))
+            walls = {False: [], True: []}
+            for rep in range(1 + max(args.reps, 3)):
+                for on in (False, True):
+                    mc.setIndexedClustering(args.cluster if on else 0)
+                    t0 = time.perf_counter()
+                    mc.extractIsoSurfaceIndexed(hd, hpp)
+                    if rep > 0:
+                        walls[on].append(time.perf_counter() - t0)
+            mc.setIndexedClustering(0)
+            spread = lambda v: [round(float(np.min(v)), 5), round(float(np.median(v)), 5), round(float(np.max(v)), 5)]
+            out.update(extract_indexed_cluster_off_wall_s=spread(walls[False]), extract_indexed_cluster_on_wall_s=spread(walls[True]))
     out.update(host_merge_s=round(t_soup - t_ply, 4), ply_write_s=round(t_ply, 4), extract_indexed_wall_s=round(t_indexed, 4))
     return out
 
@@ -256,6 +298,23 @@ def streamed_report(args, scene, hp):
                     us.append(1e3 * ms.value)
             out[name] = round(float(np.median(us)), 2)
         out.update(normals_scale_log2=scale, download_bytes_normals=12 * int(counts[0]))
+    if args.cluster:  # over the finished accumulation (the last one above); the first pass makes the buffers
+        scale = E.mesh_cluster_default_scale_log2(hp.m_virtualVoxelSize)
+        for skip, name in enumerate(("cluster_insert_us", "cluster_faces_us", "cluster_number_us", "cluster_emit_us")):
+            us = []
+            for rep in range(3 + args.reps):
+                lib.check(L.vh_time_launch_after(skip, e0, e1), "vh_time_launch_after")
+                lib.check(L.vh_mesh_weld_accum_cluster(accum, args.cluster, scale, None), "vh_mesh_weld_accum_cluster")
+                lib.check(L.vh_stream_synchronize(None), "synchronize")
+                ms = C.c_float()
+                assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0, "the launch did not take the events"
+                if rep >= 3:
+                    us.append(1e3 * ms.value)
+            out[name] = round(float(np.median(us)), 2)
+        kc = (C.c_uint32 * 6)()
+        lib.check(L.vh_mesh_weld_accum_cluster_get_counts(accum, kc, None), "vh_mesh_weld_accum_cluster_get_counts")
+        out.update(cluster={k: int(kc[i]) for i, k in enumerate(T.CLUSTER_COUNTS)}, cluster_cells=args.cluster, cluster_scale_log2=scale,
+                   download_bytes_clustered=24 * int(kc[0]) + 12 * int(kc[1]))
     L.vh_mesh_weld_accum_destroy(accum)
     L.vh_marching_cubes_data_free(C.byref(data))
     for name in names:
@@ -272,7 +331,7 @@ def streamed_report(args, scene, hp):
     try:
         with tempfile.TemporaryDirectory() as d:
             walls = dict(soup_walk_s=[], soup_save_s=[], indexed_walk_s=[], indexed_save_s=[])
-            normal_walks = []
+            normal_walks, cluster_walks = [], []
             for rep in range(1 + max(args.reps, 3)):  # the first pair of walks sizes every buffer
                 t0 = time.perf_counter()
                 mc.extractIsoSurfaceChunkGrid(grid, pos, radius)
@@ -298,6 +357,14 @@ def streamed_report(args, scene, hp):
                         normal_walks.append(time.perf_counter() - t7)
                     mc.setIndexedNormals(False)
                     mc.clearMeshBuffer()
+                if args.cluster:
+                    mc.setIndexedClustering(args.cluster)
+                    t8 = time.perf_counter()
+                    mc.extractIsoSurfaceIndexedChunkGrid(grid, pos, radius)
+                    if rep > 0:
+                        cluster_walks.append(time.perf_counter() - t8)
+                    mc.setIndexedClustering(0)
+                    mc.clearMeshBuffer()
     finally:
         grid.close()
     w = {k: float(np.median(v)) for k, v in walls.items()}
@@ -310,6 +377,8 @@ def streamed_report(args, scene, hp):
                download_bytes_indexed=24 * stats["vertices"] + 12 * stats["faces"], walk=stats)
     if args.normals:
         out.update(indexed_walk_normals_s=round(float(np.median(normal_walks)), 4), indexed_walk_normals_min_s=round(min(normal_walks), 4))
+    if args.cluster:
+        out.update(indexed_walk_cluster_s=round(float(np.median(cluster_walks)), 4), indexed_walk_cluster_min_s=round(min(cluster_walks), 4))
     return out
 
 
@@ -324,7 +393,10 @@ def main():
     ap.add_argument("--normals", action="store_true", help="--indexed: add the vertex-normal pass: its two kernels, its download, the extraction with it on and off")
     ap.add_argument("--components", action="store_true", help="--indexed: add the component pass: its kernels, its share of the extraction, the labelling on the host beside it")
     ap.add_argument("--min-component", type=int, default=100, help="--components: the filter's minFaces")
+    ap.add_argument("--cluster", type=int, default=0, metavar="M", help="--indexed: add the vertex clustering at M (1 ... 64) lattice points a side: its kernels, the mesh before and after, the extraction with it on and off")
     args = ap.parse_args()
+    if args.cluster and (not args.indexed or not 1 <= args.cluster <= 64):
+        ap.error("--cluster needs --indexed, and 1 ... 64 lattice points a side")
     if args.normals and not args.indexed:
         ap.error("--normals needs --indexed")
     if args.components and (not args.indexed or args.streamed):

@@ -3,7 +3,7 @@
 parameter file, optional mesh at the end) and prints one JSON line with the timing.
 
     python tools/replay.py --params zParameters.txt [--tracking zParametersTracking.txt] [--rgbd-tracking] [--sens a.sens b.sens]
-                           [--mesh scan.ply [--indexed-mesh [--mesh-normals] [--mesh-min-component N] [--mesh-largest-component]]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
+                           [--mesh scan.ply [--indexed-mesh [--mesh-normals] [--mesh-min-component N] [--mesh-largest-component] [--mesh-cluster M]]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
                            [--native [--batch N] [--native-tracking]] [--weighted-colour]
 
 Without --sens the files named by s_binaryDumpSensorFile[i] in the parameter file are played.  The rendering keys
@@ -43,6 +43,7 @@ def main():
     ap.add_argument("--mesh-normals", action="store_true", help="--indexed-mesh: compute vertex normals on the device after the weld and write nx, ny, nz into the PLY")
     ap.add_argument("--mesh-min-component", type=int, default=0, metavar="N", help="--indexed-mesh: drop the connected components of fewer than N faces on the device before the mesh is written")
     ap.add_argument("--mesh-largest-component", action="store_true", help="--indexed-mesh: keep only the connected component with the most faces")
+    ap.add_argument("--mesh-cluster", type=int, default=0, metavar="M", help="--indexed-mesh: decimate the mesh on the device before it is written: the vertices in one cube of M (2 ... 64) voxel-lattice points a side become one")
     ap.add_argument("--record", default=None, help="write what was processed, with the poses used, to this .sens file")
     ap.add_argument("--max-frames", type=int, default=None)
     ap.add_argument("--render-to", default=None, help="renderToFile: the shaded model and the input of every frame as PNGs under this directory")
@@ -58,6 +59,10 @@ def main():
         ap.error("--mesh-min-component needs --indexed-mesh: a triangle soup has no connectivity")
     if args.mesh_largest_component and not args.indexed_mesh:
         ap.error("--mesh-largest-component needs --indexed-mesh: a triangle soup has no connectivity")
+    if args.mesh_cluster and not args.indexed_mesh:
+        ap.error("--mesh-cluster needs --indexed-mesh: clustering works on the welded mesh's vertex keys")
+    if args.mesh_cluster and not 2 <= args.mesh_cluster <= 64:
+        ap.error("--mesh-cluster: 2 ... 64 lattice points a side")
     if args.mesh_min_component < 0:
         ap.error("--mesh-min-component: a number of faces")
     import torch
@@ -106,7 +111,8 @@ def main():
         out["recorded"] = rec.saveRecordedFramesToFile(args.record)
     if args.mesh:
         if args.indexed_mesh:
-            m = rec.extractIsoSurfaceIndexed(args.mesh, normals=args.mesh_normals, min_component_faces=args.mesh_min_component, largest_component=args.mesh_largest_component)
+            m = rec.extractIsoSurfaceIndexed(args.mesh, normals=args.mesh_normals, min_component_faces=args.mesh_min_component, largest_component=args.mesh_largest_component,
+                                             cluster_cells=args.mesh_cluster)
         else:
             m = rec.extractIsoSurface(args.mesh)
         out["mesh"] = dict(file=args.mesh, indexed=bool(args.indexed_mesh), vertices=int(len(m["vertices"])), faces=int(len(m["faces"])))
@@ -114,6 +120,8 @@ def main():
             out["mesh"]["normals"] = int(len(m["normals"]))
         if args.mesh_min_component or args.mesh_largest_component:
             out["mesh"]["components"] = m["components"]
+        if args.mesh_cluster:
+            out["mesh"]["clustering"] = m["clustering"]
     print(json.dumps(out))
 
 

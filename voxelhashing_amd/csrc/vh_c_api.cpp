@@ -435,6 +435,17 @@ int vh_marching_cubes_get_indexed_component_stats(VhMarchingCubes* mc, uint32_t 
     mc->impl.getIndexedComponentStats(out);
     return VH_OK;
 }
+int vh_marching_cubes_set_indexed_clustering(VhMarchingCubes* mc, uint32_t cellsPerCluster)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.setIndexedClustering(cellsPerCluster); });
+}
+int vh_marching_cubes_get_indexed_cluster_stats(VhMarchingCubes* mc, uint32_t out[6])
+{
+    if (!mc || !out) return VH_ERR_BAD_ARGUMENT;
+    mc->impl.getIndexedClusterStats(out);
+    return VH_OK;
+}
 int vh_marching_cubes_download_indexed_normals(VhMarchingCubes* mc, float* normals)
 {
     if (!mc) return VH_ERR_BAD_ARGUMENT;

@@ -18,6 +18,7 @@
 
 #include "../../include/vh.hpp"
 #include "vh_host_util.hpp"
+#include "vh_mesh_cluster.hpp"
 #include "vh_mesh_components.hpp"
 #include "vh_mesh_normals.hpp"
 
@@ -363,10 +364,51 @@ void recordsToMeshData(const VhVertex* v, size_t n, vh::MeshData& md)
 }
 } // namespace
 
-void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf, bool accumulated, int32_t scaleLog2)
+void CUDAMarchingCubesHashSDF::setIndexedClustering(unsigned int cellsPerCluster)
+{
+    if (cellsPerCluster > VH_CLUSTER_MAX_CELLS) throw vh::Error(VH_ERR_BAD_ARGUMENT, "setIndexedClustering: at most 64 cells per cluster");
+    m_clusterCells = cellsPerCluster;
+}
+
+void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf, bool accumulated, float voxelSize)
 {
     vh::MeshData md;
-    const bool filter = m_componentMinFaces != 0 || m_componentLargestOnly;
+    const bool filter = m_componentMinFaces != 0 || m_componentLargestOnly, cluster = m_clusterCells != 0;
+    // (an accumulation without an append has no voxel size, and no vertex either: any scale serves)
+    const bool sized = voxelSize > 0.0f || !accumulated;
+    unsigned int clusterStats[VH_CLUSTER_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
+    // the mesh the later passes and the download work on: the weld's (the accumulator knows its own), or the clustered one
+    const VhVertex* d_vertices = accumulated ? nullptr : m_weld.d_vertices;
+    const uint64_t* d_keys = accumulated ? nullptr : m_weld.d_keys;
+    const uint32_t* d_faces = accumulated ? nullptr : m_weld.d_faces;
+    if (cluster) {
+        // a cluster spans chunks: a pass of the finish.  The welded mesh stays where it is.
+        int32_t clusterScale = 0;
+        if (sized) check(vh_mesh_cluster_default_scale_log2(voxelSize, &clusterScale), "vh_mesh_cluster_default_scale_log2");
+        int rc = VH_OK;
+        if (accumulated) {
+            check(vh_mesh_weld_accum_cluster(m_accum.get(), m_clusterCells, clusterScale, m_stream), "vh_mesh_weld_accum_cluster");
+            rc = vh_mesh_weld_accum_cluster_get_counts(m_accum.get(), clusterStats, m_stream);
+        } else {
+            if (!m_cluster) m_cluster.reset(new VhMeshCluster);
+            check(m_cluster->run(d_vertices, d_keys, d_faces, nv, nf, m_clusterCells, clusterScale, m_stream), "vh_mesh_cluster");
+            rc = m_cluster->counts(clusterStats, m_stream);
+            d_vertices = m_cluster->vertices.get(); d_keys = m_cluster->keys.get(); d_faces = m_cluster->faces.get();
+        }
+        if (rc == VH_ERR_STAGING_OVERFLOW) throw vh::Error(rc, "mesh clustering: a table is full");
+        if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "mesh clustering: a key that is no vertex key, a value out of the fixed-point range, or a face index out of bounds");
+        check(rc, "mesh clustering");
+    } else if (accumulated) {
+        // a finish of these appends with clustering on may have gone before: the passes below are of the welded mesh
+        check(vh_mesh_weld_accum_cluster(m_accum.get(), 0, 0, m_stream), "vh_mesh_weld_accum_cluster");
+    }
+    const unsigned int weldedVertices = nv, weldedFaces = nf;
+    if (cluster) { nv = clusterStats[VH_CLUSTER_VERTICES]; nf = clusterStats[VH_CLUSTER_FACES]; }
+    int32_t scaleLog2 = 0;
+    // the vertices of a welded face lie in adjacent clusters and inside their clusters' boxes: an edge of a clustered
+    // face stays under 2 m voxels in every component, and the normals' scale is that of a voxel of 2 m voxelSize
+    if (m_indexedNormals && sized)
+        check(vh_mesh_normals_default_scale_log2(cluster ? 2.0f * (float)m_clusterCells * voxelSize : voxelSize, &scaleLog2), "vh_mesh_normals_default_scale_log2");
     if (m_indexedNormals) {
         // over all the faces, with the bits the last append left: a pass of the finish, never of an append.  With the
         // filter on only the pass's status comes back here: the normals come with the filtered mesh.
@@ -378,7 +420,7 @@ void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf,
             rc = vh_mesh_weld_accum_download_normals(m_accum.get(), md.m_Normals.data(), toHost, m_stream);
         } else {
             if (!m_normals) m_normals.reset(new VhMeshNormals);
-            check(m_normals->run(m_weld.d_vertices, m_weld.d_keys, m_weld.d_faces, nv, nf, scaleLog2, m_stream), "vh_mesh_vertex_normals");
+            check(m_normals->run(d_vertices, d_keys, d_faces, nv, nf, scaleLog2, m_stream), "vh_mesh_vertex_normals");
             rc = m_normals->download(md.m_Normals.data(), toHost, true, m_stream);
         }
         if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "vertex normals: a face normal is out of the fixed-point range, or a face index out of bounds");
@@ -393,7 +435,7 @@ void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf,
             rc = vh_mesh_weld_accum_components_get_counts(m_accum.get(), stats, m_stream);
         } else {
             if (!m_components) m_components.reset(new VhMeshComponents);
-            check(m_components->run(m_weld.d_vertices, m_weld.d_keys, m_indexedNormals ? m_normals->normals.get() : nullptr, m_weld.d_faces, nv, nf,
+            check(m_components->run(d_vertices, d_keys, m_indexedNormals ? m_normals->normals.get() : nullptr, d_faces, nv, nf,
                                     m_componentMinFaces, m_componentLargestOnly ? 1u : 0u, m_stream), "vh_mesh_components");
             rc = m_components->counts(stats, m_stream);
         }
@@ -407,11 +449,15 @@ void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf,
     float* normals = filter && m_indexedNormals ? md.m_Normals.data() : nullptr;
     if (filter && accumulated) check(vh_mesh_weld_accum_components_download(m_accum.get(), verts.data(), nullptr, normals, md.m_FaceIndicesVertices.data(), mv, mf, m_stream), "vh_mesh_weld_accum_components_download");
     else if (filter) check(m_components->download(verts.data(), nullptr, normals, md.m_FaceIndicesVertices.data(), mv, mf, m_stream), "mesh components");
+    else if (cluster && accumulated) check(vh_mesh_weld_accum_cluster_download(m_accum.get(), verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_cluster_download");
+    else if (cluster) check(m_cluster->download(verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "mesh clustering");
     else if (accumulated) check(vh_mesh_weld_accum_download(m_accum.get(), verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_download");
     else check(vh_mesh_weld_download(&m_weld, verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_download");
     recordsToMeshData(verts.data(), verts.size(), md);
     m_meshData = std::move(md);
-    m_indexed.counts[0] = nv; m_indexed.counts[1] = nf;
+    m_indexed.counts[0] = weldedVertices; m_indexed.counts[1] = weldedFaces;
+    m_indexed.clustered = cluster;
+    std::copy(clusterStats, clusterStats + VH_CLUSTER_NUM_COUNTS, m_indexed.clusterStats);
     m_indexed.hasNormals = m_indexedNormals;
     m_indexed.filtered = filter;
     m_indexed.kept[0] = mv; m_indexed.kept[1] = mf;
@@ -437,9 +483,7 @@ void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(const HashData& hashData
     const int rc = vh_mesh_weld_get_counts(&m_weld, counts, m_stream);
     m_indexed.counts[2] = counts[2];
     checkWeld(rc, "vh_mesh_weld_get_counts");
-    int32_t scaleLog2 = 0;
-    if (m_indexedNormals) check(vh_mesh_normals_default_scale_log2(hashParams.m_virtualVoxelSize, &scaleLog2), "vh_mesh_normals_default_scale_log2");
-    readBackIndexed(counts[0], counts[1], false, scaleLog2);
+    readBackIndexed(counts[0], counts[1], false, hashParams.m_virtualVoxelSize);
 }
 
 void CUDAMarchingCubesHashSDF::AccumFree::operator()(VhMeshWeldAccum* a) const noexcept { vh_mesh_weld_accum_destroy(a); }
@@ -484,12 +528,9 @@ void CUDAMarchingCubesHashSDF::finishIndexed()
     m_indexed.counts[VH_WELD_ACCUM_STATUS] = stats[VH_WELD_ACCUM_STATUS];
     m_indexed.hasNormals = false;
     m_indexed.filtered = false;
+    m_indexed.clustered = false;
     checkWeld(rc, "vh_mesh_weld_accum_get_counts");
-    // (without an append there is no voxel size, and no vertex either: any scale serves)
-    int32_t scaleLog2 = 0;
-    if (m_indexedNormals && m_indexed.voxelSize > 0.0f)
-        check(vh_mesh_normals_default_scale_log2(m_indexed.voxelSize, &scaleLog2), "vh_mesh_normals_default_scale_log2");
-    readBackIndexed(stats[VH_WELD_ACCUM_VERTICES], stats[VH_WELD_ACCUM_FACES], true, scaleLog2);
+    readBackIndexed(stats[VH_WELD_ACCUM_VERTICES], stats[VH_WELD_ACCUM_FACES], true, m_indexed.voxelSize);
     std::copy(stats, stats + VH_WELD_ACCUM_NUM_COUNTS, m_indexed.counts);
 }
 
@@ -564,6 +605,13 @@ void CUDAMarchingCubesHashSDF::downloadIndexed(VhVertex* vertices, uint64_t* key
         else check(m_components->download(vertices, keys, nullptr, faces, kv, kf, m_stream), "mesh components");
         return;
     }
+    if (m_indexed.clustered) { // the clustering's own buffers, as above
+        const unsigned int cv = m_indexed.clusterStats[VH_CLUSTER_VERTICES], cf = m_indexed.clusterStats[VH_CLUSTER_FACES];
+        if (cv == 0 && cf == 0) return;
+        if (m_indexed.accumulated) check(vh_mesh_weld_accum_cluster_download(m_accum.get(), vertices, keys, faces, cv, cf, m_stream), "vh_mesh_weld_accum_cluster_download");
+        else check(m_cluster->download(vertices, keys, faces, cv, cf, m_stream), "mesh clustering");
+        return;
+    }
     const unsigned int nv = m_indexed.counts[0], nf = m_indexed.counts[1];
     if (nv == 0 && nf == 0) return;
     if (m_indexed.accumulated) {
@@ -584,10 +632,11 @@ void CUDAMarchingCubesHashSDF::downloadIndexedNormals(float* normals)
         else check(m_components->download(nullptr, nullptr, normals, nullptr, m_indexed.kept[0], 0, m_stream), "mesh components");
         return;
     }
-    if (m_indexed.counts[0] == 0) return;
+    const unsigned int nv = m_indexed.clustered ? m_indexed.clusterStats[VH_CLUSTER_VERTICES] : m_indexed.counts[0]; // the pass ran over the clustered mesh
+    if (nv == 0) return;
     if (!normals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexedNormals");
-    if (m_indexed.accumulated) check(vh_mesh_weld_accum_download_normals(m_accum.get(), normals, m_indexed.counts[0], m_stream), "vh_mesh_weld_accum_download_normals");
-    else check(m_normals->download(normals, m_indexed.counts[0], false, m_stream), "normals");
+    if (m_indexed.accumulated) check(vh_mesh_weld_accum_download_normals(m_accum.get(), normals, nv, m_stream), "vh_mesh_weld_accum_download_normals");
+    else check(m_normals->download(normals, nv, false, m_stream), "normals");
 }
 
 void CUDAMarchingCubesHashSDF::downloadSources(VhTriangleSource* out, unsigned int n)

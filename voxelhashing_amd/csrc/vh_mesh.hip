@@ -17,50 +17,14 @@
 #include "vh_device.hpp"
 #include "vh_host_util.hpp"
 #include "vh_mesh_key.hpp"
+#include "vh_mesh_table.hpp"
+#include "vh_mesh_cluster.hpp"
 #include "vh_mesh_components.hpp"
 #include "vh_mesh_normals.hpp"
 
 using namespace vhd;
 
 namespace {
-
-// the slot a key starts probing at (the 64-bit finaliser of MurmurHash3)
-VHD uint32_t weld_home(uint64_t k, uint32_t mask)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return (uint32_t)k & mask;
-}
-
-// base of `keep` lanes' run in a list that *counter counts: one atomic per wave.  Every lane of the wave calls it.
-VHD uint32_t wave_append(bool keep, uint32_t* counter)
-{
-    const uint64_t m = __ballot(keep);
-    if (m == 0ull) return 0u;
-    const int leader = __ffsll((unsigned long long)m) - 1;
-    uint32_t base = 0u;
-    if ((int)lane_id() == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-    return base + (uint32_t)__popcll(m & lanemask_lt());
-}
-
-constexpr uint32_t kNoSlot = 0xffffffffu;
-
-// the slot of `key`, claimed if the table does not have it; kNoSlot after numSlots steps without one
-VHD uint32_t weld_find_or_claim(unsigned long long* slotKeys, uint64_t key, uint32_t slotsLog2)
-{
-    const uint32_t numSlots = 1u << slotsLog2, mask = numSlots - 1u;
-    uint32_t slot = weld_home(key, mask);
-#pragma unroll 1
-    for (uint32_t step = 0; step < numSlots; step++) {
-        unsigned long long have = slotKeys[slot];
-        if (have == kMeshKeyEmpty) have = atomicCAS(&slotKeys[slot], (unsigned long long)kMeshKeyEmpty, (unsigned long long)key);
-        if (have == kMeshKeyEmpty || have == key) return slot;
-        slot = (slot + 1u) & mask;
-    }
-    return kNoSlot;
-}
 
 // One lane per soup vertex i = 3 * triangle + corner: claim the slot of its key, bid for the slot's vertex with
 // rank << 32 | i (the smallest wins), remember the slot.
@@ -171,14 +135,6 @@ struct WeldAccumView {
 
 constexpr uint32_t kNoValue = 0xffffffffu;
 constexpr uint32_t kDroppedSlot = 0xfffffffeu; // in vertexSlot: the triangle's cell belongs to an earlier append
-
-// counts the lanes with `flag` into *counter: one atomic per wave.  Every lane of the wave calls it.
-VHD void wave_count(bool flag, uint32_t* counter)
-{
-    const uint64_t m = __ballot(flag);
-    if (m == 0ull) return;
-    if ((int)lane_id() == __ffsll((unsigned long long)m) - 1) atomicAdd(counter, (uint32_t)__popcll(m));
-}
 
 // One lane per triangle.  Claims the cell for this append (a cell an earlier append owns drops the triangle here,
 // before any of its keys is looked at), then for each of the three vertices the slot of its key, and bids for it.
@@ -807,6 +763,10 @@ struct VhMeshWeldAccum {
     bool m_normalsValid = false;        // the pass has run, and no begin or append since
     VhMeshComponents components;        // the component filter (vh_mesh_weld_accum_components): made by the first pass
     bool m_componentsValid = false;     // the pass has run, and no begin or append since
+    VhMeshCluster cluster;              // the vertex clustering (vh_mesh_weld_accum_cluster): made by the first pass
+    bool m_clusterRan = false;          // the pass has run, and no begin or append since
+    bool m_clusterValid = false;        // ... and left no status: normals and components are then of ITS mesh,
+    uint32_t m_clusterVertices = 0, m_clusterFaces = 0; // which has this size
     size_t m_soupCapacity = 0, m_vertexCapacity = 0, m_faceCapacity = 0; // in soup vertices, welded vertices, faces
     uint32_t m_slotsLog2 = 6, m_firstSlotsLog2 = 6;
     bool m_fixed = false, m_begun = false;
@@ -819,6 +779,20 @@ struct VhMeshWeldAccum {
 };
 
 namespace {
+
+// the mesh that the passes of the finish work on: the clustered one once vh_mesh_weld_accum_cluster has run over these
+// appends, else the weld's own, whose counts are `have`
+struct AccumMesh {
+    const VhVertex* vertices;
+    const uint64_t* keys;
+    const uint32_t* faces;
+    uint32_t numVertices, numFaces;
+};
+AccumMesh accumMesh(const VhMeshWeldAccum& a, const uint32_t have[VH_WELD_ACCUM_NUM_COUNTS])
+{
+    if (a.m_clusterValid) return AccumMesh{ a.cluster.vertices.get(), a.cluster.keys.get(), a.cluster.faces.get(), a.m_clusterVertices, a.m_clusterFaces };
+    return AccumMesh{ a.vertices.get(), a.keys.get(), a.faces.get(), have[VH_WELD_ACCUM_VERTICES], have[VH_WELD_ACCUM_FACES] };
+}
 
 // errors of the owner types (vh::deviceAlloc throws) become codes, as at the handle level
 template <class F> int accumGuarded(F&& f)
@@ -908,6 +882,7 @@ int vh_mesh_weld_accum_begin(VhMeshWeldAccum* accum, vhStream_t stream)
     accum->m_begun = true;
     accum->m_normalsValid = false;
     accum->m_componentsValid = false;
+    accum->m_clusterValid = accum->m_clusterRan = false;
     return VH_OK;
 }
 
@@ -918,6 +893,7 @@ int vh_mesh_weld_accum_append(VhMeshWeldAccum* accum, const VhTriangle* d_triang
     if (numTriangles > 0x55555555u / 2u || (numTriangles != 0 && (!d_triangles || !d_sources))) return VH_ERR_BAD_ARGUMENT;
     accum->m_normalsValid = false; // normals are of all faces with the final vertex bits: a pass before this append is stale
     accum->m_componentsValid = false; // and a component spans appends
+    accum->m_clusterValid = accum->m_clusterRan = false; // and so does a cluster
     if (numTriangles == 0) return VH_OK; // nothing to take, and no launch with an empty grid
     if (accum->m_appends >= VH_WELD_ACCUM_MAX_APPENDS - 1u) return VH_ERR_BAD_ARGUMENT;
     hipStream_t s = (hipStream_t)stream;
@@ -1005,8 +981,9 @@ int vh_mesh_weld_accum_normals(VhMeshWeldAccum* accum, int32_t scaleLog2, vhStre
         a.m_normalsValid = false;
         uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
         VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream)); // waits for the appends; a weld that failed has no normals
-        const uint32_t nv = have[VH_WELD_ACCUM_VERTICES], nf = have[VH_WELD_ACCUM_FACES];
-        VH_TRY(a.normals.run(a.vertices.get(), a.keys.get(), a.faces.get(), nv, nf, scaleLog2, stream));
+        const AccumMesh m = accumMesh(a, have);
+        const uint32_t nv = m.numVertices, nf = m.numFaces;
+        VH_TRY(a.normals.run(m.vertices, m.keys, m.faces, nv, nf, scaleLog2, stream));
         a.m_normalsVertices = nv;
         a.m_normalsValid = true;
         return VH_OK;
@@ -1027,13 +1004,52 @@ int vh_mesh_weld_accum_components(VhMeshWeldAccum* accum, uint32_t minFaces, uin
         a.m_componentsValid = false;
         uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
         VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream)); // waits for the appends; a weld that failed has no components
-        const uint32_t nv = have[VH_WELD_ACCUM_VERTICES], nf = have[VH_WELD_ACCUM_FACES];
+        const AccumMesh m = accumMesh(a, have);
+        const uint32_t nv = m.numVertices, nf = m.numFaces;
         // normals ride along when their pass has run over this very mesh (it leaves zeros, not garbage, behind a status)
         const float* d_normals = a.m_normalsValid && a.m_normalsVertices == nv ? a.normals.normals.get() : nullptr;
-        VH_TRY(a.components.run(a.vertices.get(), a.keys.get(), d_normals, a.faces.get(), nv, nf, minFaces, largestOnly, stream));
+        VH_TRY(a.components.run(m.vertices, m.keys, d_normals, m.faces, nv, nf, minFaces, largestOnly, stream));
         a.m_componentsValid = true;
         return VH_OK;
     });
+}
+
+int vh_mesh_weld_accum_cluster(VhMeshWeldAccum* accum, uint32_t cellsPerCluster, int32_t scaleLog2, vhStream_t stream)
+{
+    if (!accum || !accum->m_begun || cellsPerCluster > VH_CLUSTER_MAX_CELLS || scaleLog2 < -100 || scaleLog2 > 100) return VH_ERR_BAD_ARGUMENT;
+    if (cellsPerCluster == 0u) { // forget the pass: the passes of the finish are of the welded mesh again
+        if (accum->m_clusterRan) accum->m_clusterValid = accum->m_clusterRan = accum->m_normalsValid = accum->m_componentsValid = false;
+        return VH_OK;
+    }
+    return accumGuarded([&]() -> int {
+        VhMeshWeldAccum& a = *accum;
+        // normals and components of the mesh before this pass are not of the mesh after it
+        a.m_clusterValid = a.m_clusterRan = a.m_normalsValid = a.m_componentsValid = false;
+        uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
+        VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream)); // waits for the appends; a weld that failed has nothing to cluster
+        VH_TRY(a.cluster.run(a.vertices.get(), a.keys.get(), a.faces.get(), have[VH_WELD_ACCUM_VERTICES], have[VH_WELD_ACCUM_FACES], cellsPerCluster, scaleLog2, stream));
+        a.m_clusterRan = true;
+        uint32_t counts[VH_CLUSTER_NUM_COUNTS] = {};
+        if (a.cluster.counts(counts, stream) == VH_OK) { // (what it was is vh_mesh_weld_accum_cluster_get_counts' to report)
+            a.m_clusterVertices = counts[VH_CLUSTER_VERTICES];
+            a.m_clusterFaces = counts[VH_CLUSTER_FACES];
+            a.m_clusterValid = true;
+        }
+        return VH_OK;
+    });
+}
+
+int vh_mesh_weld_accum_cluster_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream)
+{
+    if (!accum || !out || !accum->m_clusterRan) return VH_ERR_BAD_ARGUMENT;
+    return accum->cluster.counts(out, stream);
+}
+
+int vh_mesh_weld_accum_cluster_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint64_t* keys, uint32_t* faces, uint32_t numVertices, uint32_t numFaces,
+                                        vhStream_t stream)
+{
+    if (!accum || !accum->m_clusterValid || numVertices > accum->m_clusterVertices || numFaces > accum->m_clusterFaces) return VH_ERR_BAD_ARGUMENT;
+    return accum->cluster.download(vertices, keys, faces, numVertices, numFaces, stream);
 }
 
 int vh_mesh_weld_accum_components_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream)

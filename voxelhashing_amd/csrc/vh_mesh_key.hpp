@@ -54,3 +54,21 @@ VH_KEY_FN bool vh_mesh_cell_key(int32_t cx, int32_t cy, int32_t cz, uint64_t* ke
     *key = (uint64_t)(cx + kMeshKeyBias) | ((uint64_t)(cy + kMeshKeyBias) << 20) | ((uint64_t)(cz + kMeshKeyBias) << 40) | kMeshKeyCell;
     return true;
 }
+
+// The key of the cluster a vertex key falls into when the lattice is cut into cubes of m points a side (the vertex
+// clustering of vh_mesh_cluster; DESIGN.md section 4, "Mesh clustering"): the key's lattice point L, whatever its code,
+// gives k = floor(L / m) per component -- floor, not truncation: L = -1, m = 2 is k = -1 -- packed as a lattice point
+// with code 3.  |k| <= |L|, so k is in range whenever L was.
+// -> false when m is 0 or bit 62 or 63 of the key is set (a cell key, the empty word: no vertex key)
+VH_KEY_FN bool vh_mesh_cluster_key_of(uint64_t vertexKey, uint32_t m, uint64_t* key)
+{
+    if (m == 0u || (vertexKey >> 62) != 0ull) return false;
+    uint64_t out = 3ull << 60;
+    for (uint32_t axis = 0; axis < 3u; axis++) {
+        const int32_t l = (int32_t)((vertexKey >> (20u * axis)) & 0xfffffull) - kMeshKeyBias, d = (int32_t)m;
+        const int32_t k = l >= 0 ? l / d : -((-l + d - 1) / d);
+        out |= (uint64_t)(k + kMeshKeyBias) << (20u * axis);
+    }
+    *key = out;
+    return true;
+}

@@ -757,6 +757,20 @@ class CUDAMarchingCubesHashSDF:
         mesh, and indexed_component_stats() says what the unfiltered one held"""
         check(self.L.vh_marching_cubes_set_indexed_component_filter(self.handle, int(minFaces), 1 if largestOnly else 0), "setIndexedComponentFilter")
 
+    def setIndexedClustering(self, cellsPerCluster=0):
+        """decimation by vertex clustering for the indexed extractions (off by default: 0; 1 ... 64 turn it on): after
+        the weld, and before normals and components, the vertices that fall into one cube of cellsPerCluster lattice
+        points a side become one vertex at their mean; indexed_counts(), indexed(), mesh() and saveMesh then describe the
+        clustered mesh, and indexed_cluster_stats() says what the pass did"""
+        check(self.L.vh_marching_cubes_set_indexed_clustering(self.handle, int(cellsPerCluster)), "setIndexedClustering")
+
+    def indexed_cluster_stats(self):
+        """of the last indexed extraction: vertices, faces, status, collapsed, duplicates, unused_clusters; all 0 when
+        it ran with clustering off"""
+        out = (C.c_uint32 * 6)()
+        check(self.L.vh_marching_cubes_get_indexed_cluster_stats(self.handle, out), "get_indexed_cluster_stats")
+        return {k: int(out[i]) for i, k in enumerate(T.CLUSTER_COUNTS)}
+
     def indexed_component_stats(self):
         """of the last indexed extraction: components (with a face), faceless_vertices, kept_components, kept_vertices,
         kept_faces, largest_faces; all 0 when it ran with the filter off"""
@@ -1044,6 +1058,69 @@ def mesh_components_filter(vertices, colors, keys, faces, min_faces=0, largest_o
     return dict(out, counts={name: int(counts[i]) for i, name in enumerate(T.COMPONENTS_COUNTS)}, status=status, code=code)
 
 
+def mesh_cluster_key(vertex_key, cells_per_cluster):
+    """vh_mesh_cluster_key (host side, no GPU): the key of the cluster a vertex key falls into"""
+    out = C.c_uint64()
+    check(load().vh_mesh_cluster_key(int(vertex_key), int(cells_per_cluster), C.byref(out)), "vh_mesh_cluster_key")
+    return int(out.value)
+
+
+def mesh_cluster_default_scale_log2(voxel_size):
+    """vh_mesh_cluster_default_scale_log2 (host side, no GPU)"""
+    out = C.c_int32()
+    check(load().vh_mesh_cluster_default_scale_log2(float(voxel_size), C.byref(out)), "vh_mesh_cluster_default_scale_log2")
+    return int(out.value)
+
+
+def mesh_cluster(vertices, colors, keys, faces, cells_per_cluster, scale_log2, cluster_slots_log2=0, face_slots_log2=0, raise_on_status=True,
+                 stream=None, guard=0):
+    """vh_mesh_cluster on hand-made input: vertices (V,3) f32 with colors (V,3) f32 or None, or T.VERTEX_DTYPE records;
+    keys (V,) u64; faces (F,3) u32 -> the clustered vertices, colors, keys, faces as mesh_weld(), counts (the six by
+    name), status, code.  cluster_slots_log2 / face_slots_log2: the tables' sizes (0: the default, twice the vertices
+    and faces); smaller ones fill.  A status raises VhError (VH_ERR_STAGING_OVERFLOW for a full table alone, else
+    VH_ERR_BAD_ARGUMENT), or with raise_on_status=False comes back as `code` beside an empty mesh.  guard: that many
+    words of 0xa5a5a5a5 behind the per-vertex slot array on the device, returned as slot_guard: where a face index >= V
+    would lead."""
+    L = load()
+    v = _vertex_records(vertices, colors)
+    k = np.ascontiguousarray(keys, dtype=np.uint64).ravel()
+    f = np.ascontiguousarray(faces, dtype=np.uint32).reshape(-1, 3)
+    if len(k) != len(v):
+        raise ValueError("one key per vertex")
+    nv, nf = len(v), len(f)
+
+    def log2_for(n, given):
+        out = C.c_uint32()
+        check(L.vh_mesh_cluster_default_slots_log2(n, C.byref(out)), "vh_mesh_cluster_default_slots_log2")
+        return int(given) if given else int(out.value)
+    cl, fl = log2_for(nv, cluster_slots_log2), log2_for(nf, face_slots_log2)
+    cs, fs = 1 << cl, 1 << fl
+    sizes = [8 * cs, 48 * cs, 4 * cs, 4 * cs, 4 * max(nv, 1), 8 * fs, 4 * fs, 4 * fs, 8, 24 * max(nv, 1), 8 * max(nv, 1), 12 * max(nf, 1), 24]
+    bufs = [DeviceBuffer.from_numpy(v, stream), DeviceBuffer.from_numpy(k, stream), DeviceBuffer.from_numpy(f if nf else np.zeros((1, 3), np.uint32), stream)]
+    bufs += [DeviceBuffer(n) for n in sizes]
+    try:
+        d_v, d_k, d_f = bufs[:3]
+        if guard:
+            bufs[7].free()
+            bufs[7] = DeviceBuffer.from_numpy(np.full(nv + guard, 0xa5a5a5a5, dtype=np.uint32), stream)
+        data = T.MeshClusterData(*[b.ptr for b in bufs[3:]], cl, fl)
+        check(L.vh_mesh_cluster(d_v.ptr, d_k.ptr, d_f.ptr, nv, nf, int(cells_per_cluster), int(scale_log2), C.byref(data), stream), "vh_mesh_cluster")
+        counts = bufs[15].download(np.uint32, 6, stream)
+        status = int(counts[2])
+        ov = bufs[12].download(T.VERTEX_DTYPE, int(counts[0]), stream)
+        out = dict(vertices=np.ascontiguousarray(ov["p"]), colors=np.ascontiguousarray(ov["c"]), keys=bufs[13].download(np.uint64, int(counts[0]), stream),
+                   faces=bufs[14].download(np.uint32, 3 * int(counts[1]), stream).reshape(-1, 3))
+        if guard:
+            out["slot_guard"] = bufs[7].download(np.uint32, nv + guard, stream)[nv:]
+    finally:
+        for b in bufs:
+            b.free()
+    code = 0 if status == 0 else 2 if status == T.CLUSTER_TABLE_FULL else 4  # VH_ERR_STAGING_OVERFLOW, VH_ERR_BAD_ARGUMENT
+    if code and raise_on_status:
+        check(code, f"vh_mesh_cluster (status {status})")
+    return dict(out, counts={name: int(counts[i]) for i, name in enumerate(T.CLUSTER_COUNTS)}, status=status, code=code)
+
+
 def mesh_save_ply(filename, vertices, colors=None, normals=None, faces=None, transform=None):
     """vh_mesh_save_ply (host side, no GPU): the mesh container's applyTransform (when a transform is given) and
     saveToPLY on numpy arrays: vertices (V,3), colors (V,4) or None, normals (V,3) or None, faces (F,3) or None"""
@@ -1057,7 +1134,8 @@ def mesh_save_ply(filename, vertices, colors=None, normals=None, faces=None, tra
 
 
 def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, raise_on_status=True, stream=None, normals_scale_log2=None,
-                      min_component_faces=0, largest_component=False, append_after_components=None):
+                      min_component_faces=0, largest_component=False, append_after_components=None, cluster_cells=0, cluster_scale_log2=0,
+                      append_after_cluster=None):
     """vh_mesh_weld_accum_* on hand-made input: parts is a sequence of (soup, records), appended in order to one
     accumulation -> vertices, colors, keys, faces as mesh_weld(), counts (vertices, faces), stats (the six counts by
     name), status and code.  slots_log2 is the table's FIRST size (0: the smallest), reserve_triangles that of the
@@ -1067,7 +1145,12 @@ def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, rai
     min_component_faces, largest_component: run the component filter over the finished accumulation (after the normals,
     which then ride along) -> also `filtered` (vertices, colors, keys, faces, normals if any) and component_counts (the
     six by name); the unfiltered mesh comes back as without.  append_after_components: one more (soup, records) appended
-    after the pass -> stale_code, what the filter's download then returns (4: refused)."""
+    after the pass -> stale_code, what the filter's download then returns (4: refused).
+    cluster_cells (1 ... 64), cluster_scale_log2: run the vertex clustering over the finished accumulation, BEFORE the
+    normals and the components, which are then of the clustered mesh -> also `clustered` (vertices, colors, keys, faces),
+    cluster_counts (the six by name) and cluster_code (what the counts' read returned: 4 or 2 when the pass left a
+    status).  append_after_cluster: one more (soup, records) appended after the pass -> stale_cluster_code, what the
+    counts' read then returns (4: refused); not with the normals or the filter."""
     L = load()
     h = C.c_void_p()
     check(L.vh_mesh_weld_accum_create(slots_log2, reserve_triangles, int(fixed), C.byref(h)), "vh_mesh_weld_accum_create")
@@ -1084,13 +1167,30 @@ def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, rai
         out = _welded_arrays(counts[0], counts[1], "vh_mesh_weld_accum_download",
                              lambda v, k, f, nv, nf: L.vh_mesh_weld_accum_download(h, v, k, f, nv, nf, stream))
         extra = {}
+        mesh_vertices = int(counts[0])  # of the mesh the normals are of
+        if cluster_cells and counts[2] == 0:
+            check(L.vh_mesh_weld_accum_cluster(h, int(cluster_cells), int(cluster_scale_log2), stream), "vh_mesh_weld_accum_cluster")
+            kc = (C.c_uint32 * 6)()
+            ccode = L.vh_mesh_weld_accum_cluster_get_counts(h, kc, stream)
+            if ccode < 0 or (ccode != 0 and raise_on_status):
+                check(ccode, f"vh_mesh_weld_accum_cluster (status {kc[2]})")
+            extra.update(cluster_counts={name: int(kc[i]) for i, name in enumerate(T.CLUSTER_COUNTS)}, cluster_code=int(ccode))
+            if ccode == 0:
+                extra["clustered"] = _welded_arrays(kc[0], kc[1], "vh_mesh_weld_accum_cluster_download",
+                                                    lambda v, k, f, nv, nf: L.vh_mesh_weld_accum_cluster_download(h, v, k, f, nv, nf, stream))
+                mesh_vertices = int(kc[0])
+            if append_after_cluster is not None:
+                d_tris, d_srcs, n = _upload_soup(*append_after_cluster, stream)
+                buffers += [d_tris, d_srcs]
+                check(L.vh_mesh_weld_accum_append(h, d_tris.ptr, d_srcs.ptr, n, stream), "vh_mesh_weld_accum_append")
+                extra["stale_cluster_code"] = int(L.vh_mesh_weld_accum_cluster_get_counts(h, kc, stream))
         if normals_scale_log2 is not None and counts[2] == 0:
             check(L.vh_mesh_weld_accum_normals(h, int(normals_scale_log2), stream), "vh_mesh_weld_accum_normals")
-            nrm = np.zeros((int(counts[0]), 3), dtype=np.float32)
+            nrm = np.zeros((mesh_vertices, 3), dtype=np.float32)
             ncode = L.vh_mesh_weld_accum_download_normals(h, nrm.ctypes.data, len(nrm), stream)
             if ncode < 0 or (ncode != 0 and raise_on_status):
                 check(ncode, "vh_mesh_weld_accum_download_normals")
-            extra = dict(normals=nrm, normals_code=int(ncode))
+            extra.update(normals=nrm, normals_code=int(ncode))
         if (min_component_faces or largest_component) and counts[2] == 0:
             check(L.vh_mesh_weld_accum_components(h, int(min_component_faces), 1 if largest_component else 0, stream), "vh_mesh_weld_accum_components")
             cc = (C.c_uint32 * 6)()

@@ -251,6 +251,15 @@ PROTOTYPES = {
     "vh_mesh_weld_accum_components_download": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP]),
     "vh_marching_cubes_set_indexed_component_filter": (C.c_int, [_VP, C.c_uint32, C.c_uint32]),
     "vh_marching_cubes_get_indexed_component_stats": (C.c_int, [_VP, P(C.c_uint32)]),
+    "vh_mesh_cluster_key": (C.c_int, [C.c_uint64, C.c_uint32, P(C.c_uint64)]),
+    "vh_mesh_cluster_default_scale_log2": (C.c_int, [C.c_float, P(C.c_int32)]),
+    "vh_mesh_cluster_default_slots_log2": (C.c_int, [C.c_uint32, P(C.c_uint32)]),
+    "vh_mesh_cluster": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, _VP, _VP]),
+    "vh_mesh_weld_accum_cluster": (C.c_int, [_VP, C.c_uint32, C.c_int32, _VP]),
+    "vh_mesh_weld_accum_cluster_get_counts": (C.c_int, [_VP, P(C.c_uint32), _VP]),
+    "vh_mesh_weld_accum_cluster_download": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP]),
+    "vh_marching_cubes_set_indexed_clustering": (C.c_int, [_VP, C.c_uint32]),
+    "vh_marching_cubes_get_indexed_cluster_stats": (C.c_int, [_VP, P(C.c_uint32)]),
     "vh_marching_cubes_set_indexed_normals": (C.c_int, [_VP, C.c_int]),
     "vh_marching_cubes_download_indexed_normals": (C.c_int, [_VP, _VP]),
     "vh_marching_cubes_get_mesh_normals_size": (C.c_int, [_VP, P(C.c_uint64)]),

@@ -573,7 +573,7 @@ class Reconstruction:
                 h.m_depthShift, bytes(h.m_sensorName).decode(), h.m_colorCompressionType, h.m_depthCompressionType,
                 np.array(h.m_depthExtrinsic[:]), np.array(h.m_colorExtrinsic[:]))
 
-    def extractIsoSurface(self, filename=None, indexed=False, normals=False, min_component_faces=0, largest_component=False):
+    def extractIsoSurface(self, filename=None, indexed=False, normals=False, min_component_faces=0, largest_component=False, cluster_cells=0):
         """StopScanningAndExtractIsoSurfaceMC: marching cubes over the whole scene (through the chunk grid when
         streaming is on) -> (vertices, colours, faces); written as a PLY when a file name is given.  indexed (not in the
         reference): weld the triangles on the device instead of merging them on the host.  With streaming on that is
@@ -582,7 +582,12 @@ class Reconstruction:
         "normals" and written into the PLY.  min_component_faces, largest_component (with indexed): the mesh's
         connected components are labelled on the device after the weld and those of fewer faces dropped, or all but the
         largest; what is returned and written is the filtered mesh, and its "components" entry (indexed_component_stats)
-        says what the unfiltered one held."""
+        says what the unfiltered one held.  cluster_cells (with indexed; 1 ... 64): the welded mesh is decimated on the
+        device by vertex clustering -- the vertices in one cube of that many lattice points a side become one -- before
+        the normals and the filter; what is returned and written is the clustered mesh, and its "clustering" entry
+        (indexed_cluster_stats) says what the pass did."""
+        if cluster_cells and not indexed:
+            raise ValueError("clustering needs the indexed extraction: it works on the welded mesh's vertex keys")
         if (min_component_faces or largest_component) and not indexed:
             raise ValueError("the component filter needs the indexed extraction: a triangle soup has no connectivity")
         if normals and not indexed:
@@ -598,6 +603,7 @@ class Reconstruction:
         mc.clearMeshBuffer()
         mc.setIndexedNormals(bool(normals))
         mc.setIndexedComponentFilter(int(min_component_faces), bool(largest_component))
+        mc.setIndexedClustering(int(cluster_cells))
         if self.chunk_grid is not None:
             pos = (self.scene.getLastRigidTransform().reshape(4, 4) @ np.array(list(self.gas.s_streamingPos) + [1.0], dtype=np.float32))[:3]
             mc.extractIsoSurfaceChunkGrid(self.chunk_grid, pos, self.gas.s_streamingRadius)
@@ -608,11 +614,13 @@ class Reconstruction:
         mesh = mc.mesh()
         if min_component_faces or largest_component:
             mesh["components"] = mc.indexed_component_stats()  # (saveMesh clears them with the buffer)
+        if cluster_cells:
+            mesh["clustering"] = mc.indexed_cluster_stats()
         if filename:
             mc.saveMesh(filename, None, True)  # merges close vertices, writes the PLY and clears the buffer (.cpp:126-144)
         return mesh
 
-    def extractIsoSurfaceIndexed(self, filename=None, normals=False, min_component_faces=0, largest_component=False):
+    def extractIsoSurfaceIndexed(self, filename=None, normals=False, min_component_faces=0, largest_component=False, cluster_cells=0):
         """The indexed extraction with and without streaming (not in the reference): marching cubes with the triangles
         welded on the device -> (vertices, colours, faces); written as a PLY when a file name is given.  Without
         streaming this is extractIsoSurface(indexed=True); with streaming it walks the chunk grid as extractIsoSurface()
@@ -620,20 +628,25 @@ class Reconstruction:
         nothing is merged on the host.  marching_cubes.indexed() has the mesh with its keys, indexed_stats() the counts.
         normals: vertex normals computed on the device over the finished mesh, returned as "normals" and written into
         the PLY.  min_component_faces, largest_component: the component filter, over the finished mesh (a component
-        spans chunks), as extractIsoSurface describes it."""
+        spans chunks), as extractIsoSurface describes it.  cluster_cells: the vertex clustering, over the finished mesh
+        too, before the other two."""
         if self.chunk_grid is None:
-            return self.extractIsoSurface(filename, indexed=True, normals=normals, min_component_faces=min_component_faces, largest_component=largest_component)
+            return self.extractIsoSurface(filename, indexed=True, normals=normals, min_component_faces=min_component_faces, largest_component=largest_component,
+                                          cluster_cells=cluster_cells)
         if self.marching_cubes is None:
             self.marching_cubes = E.CUDAMarchingCubesHashSDF(self.mp)
             self.marching_cubes.setOfflineProcessing(bool(self.gas.s_offlineProcessing))
         mc = self.marching_cubes
         mc.setIndexedNormals(bool(normals))
         mc.setIndexedComponentFilter(int(min_component_faces), bool(largest_component))
+        mc.setIndexedClustering(int(cluster_cells))
         pos = (self.scene.getLastRigidTransform().reshape(4, 4) @ np.array(list(self.gas.s_streamingPos) + [1.0], dtype=np.float32))[:3]
         mc.extractIsoSurfaceIndexedChunkGrid(self.chunk_grid, pos, self.gas.s_streamingRadius)
         mesh = mc.mesh()
         if min_component_faces or largest_component:
             mesh["components"] = mc.indexed_component_stats()  # (saveMesh clears them with the buffer)
+        if cluster_cells:
+            mesh["clustering"] = mc.indexed_cluster_stats()
         if filename:
             mc.saveMesh(filename, None, True)  # the mesh is welded: written as it is, and the buffer cleared
         return mesh

@@ -147,6 +147,18 @@ NORMALS_RANGE, NORMALS_BAD_INDEX = 1, 2  # bits of the vertex-normal pass's stat
 COMPONENTS_BAD_INDEX, COMPONENTS_STEPS = 1, 2  # bits of the component labelling's status word (VH_COMPONENTS_*)
 # VH_COMPONENTS_*: what the component filter counts
 COMPONENTS_COUNTS = ("components", "faceless_vertices", "kept_components", "kept_vertices", "kept_faces", "largest_faces")
+# VH_CLUSTER_*: bits of the vertex clustering's status word, the limit of cellsPerCluster, what the pass counts
+CLUSTER_TABLE_FULL, CLUSTER_BAD_KEY, CLUSTER_RANGE, CLUSTER_BAD_INDEX = 1, 2, 4, 8
+CLUSTER_MAX_CELLS = 64
+CLUSTER_COUNTS = ("vertices", "faces", "status", "collapsed", "duplicates", "unused_clusters")
+
+
+class MeshClusterData(C.Structure):  # VhMeshClusterData
+    _fields_ = [(n, C.c_void_p) for n in ("d_clusterKeys", "d_clusterSums", "d_clusterCount", "d_clusterIndex", "d_vertexSlot", "d_facePairs", "d_faceThirds",
+                                         "d_faceWindings", "d_work", "d_vertices", "d_keys", "d_faces", "d_counts")] + \
+               [("m_clusterSlotsLog2", C.c_uint32), ("m_faceSlotsLog2", C.c_uint32)]
+
+
 WELD_ACCUM_COUNTS = ("vertices", "faces", "status", "cells", "dropped", "rehashes")  # VH_WELD_ACCUM_*: what the accumulating weld reports
 WELD_ACCUM_MAX_APPENDS = 1 << 28
 
