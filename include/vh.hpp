@@ -715,6 +715,7 @@ struct MeshData {
 struct VhMeshNormals;    // opaque: the buffers of the vertex-normal pass (csrc/vh_mesh_normals.hpp)
 struct VhMeshComponents; // opaque: the buffers of the component pass (csrc/vh_mesh_components.hpp)
 struct VhMeshCluster;    // opaque: the buffers of the vertex clustering (csrc/vh_mesh_cluster.hpp)
+struct VhMeshSmooth;     // opaque: the buffers of the Taubin smoothing (csrc/vh_mesh_smooth.hpp)
 
 class CUDAMarchingCubesHashSDF {
 public:
@@ -791,6 +792,17 @@ public:
     void setIndexedClustering(unsigned int cellsPerCluster);
     // the VH_CLUSTER_NUM_COUNTS counts of the mesh in the buffer; 0 when it was made with clustering off, or is no longer the weld's
     void getIndexedClusterStats(unsigned int out[6]) const { for (int i = 0; i < 6; i++) out[i] = m_indexed.clusterStats[i]; }
+    // Taubin smoothing of the indexed mesh ("Mesh smoothing"), off by default (0 iterations).  With
+    // iterations = 1 ... 100, readBackIndexed -- the one-shot extraction, finishIndexed and the chunk-grid walk alike --
+    // runs vh_mesh_smooth AFTER the clustering and BEFORE normals and components, at the clustering's default scale of
+    // the voxel size: downloadIndexed, the mesh buffer and saveMesh carry the smoothed positions, and the normals are
+    // those of the smoothed surface (at the scale of twice the edge bound used without smoothing).  lambda and mu go to
+    // units of 2^-16 by rint.  A status of the pass throws and leaves the buffer empty.  Throws VH_ERR_BAD_ARGUMENT
+    // above 100 iterations and for a factor above 1 in magnitude.
+    void setIndexedSmoothing(unsigned int iterations, float lambda = 0.5f, float mu = -0.53f, bool keepBoundary = true);
+    void setIndexedSmoothingQ16(unsigned int iterations, int32_t lambdaQ16, int32_t muQ16, bool keepBoundary); // the same, the factors as the launcher takes them
+    // the VH_SMOOTH_NUM_COUNTS counts of the mesh in the buffer; 0 when it was made with smoothing off, or is no longer the weld's
+    void getIndexedSmoothStats(unsigned int out[6]) const { for (int i = 0; i < 6; i++) out[i] = m_indexed.smoothStats[i]; }
     void downloadSources(VhTriangleSource* out, unsigned int n);               // source records of the last indexed extraction
 
     const vh::MeshData& getMeshData() const { return m_meshData; }
@@ -833,6 +845,11 @@ private:
     // vertex clustering: the one-shot extraction's buffers (csrc/vh_mesh_cluster.hpp) are made by its first call with the option on
     unsigned int m_clusterCells = 0;
     std::unique_ptr<VhMeshCluster> m_cluster;
+    // Taubin smoothing: the one-shot extraction's buffers (csrc/vh_mesh_smooth.hpp) are made by its first call with the option on
+    unsigned int m_smoothIterations = 0;
+    int32_t m_smoothLambdaQ16 = VH_SMOOTH_DEFAULT_LAMBDA_Q16, m_smoothMuQ16 = VH_SMOOTH_DEFAULT_MU_Q16;
+    bool m_smoothKeepBoundary = true;
+    std::unique_ptr<VhMeshSmooth> m_smooth;
     struct IndexedResult {                      // what the last indexed extraction left; the empty one is the state after an error
         unsigned int counts[VH_WELD_ACCUM_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 }; // {vertices, faces, status}, then the accumulation's three
         unsigned int numSourced = 0;            // triangles of its last sourced pass 2 that are in the buffer
@@ -844,10 +861,12 @@ private:
         unsigned int componentStats[VH_COMPONENTS_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
         bool clustered = false;                 // the clustering ran: normals and components are of ITS mesh, clusterStats[0 .. 1] vertices and faces
         unsigned int clusterStats[VH_CLUSTER_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
+        bool smoothed = false;                  // the smoothing ran: the vertices are those of ITS buffers, over the clustered or the welded mesh
+        unsigned int smoothStats[VH_SMOOTH_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
     } m_indexed;
-    void clearWeldedMark() { m_welded = false; for (unsigned int& c : m_indexed.componentStats) c = 0; for (unsigned int& c : m_indexed.clusterStats) c = 0; }
+    void clearWeldedMark() { m_welded = false; for (unsigned int& c : m_indexed.componentStats) c = 0; for (unsigned int& c : m_indexed.clusterStats) c = 0; for (unsigned int& c : m_indexed.smoothStats) c = 0; }
     void resetIndexed() { clearMeshBuffer(); m_indexed = IndexedResult(); }
-    // the welded mesh on the device (m_accum's, or m_weld's) through the passes that are on -- clustering, normals,
+    // the welded mesh on the device (m_accum's, or m_weld's) through the passes that are on -- clustering, smoothing, normals,
     // components, at the scales of that voxel size -- into the mesh buffer; then its counts and marks
     void readBackIndexed(unsigned int numVertices, unsigned int numFaces, bool accumulated, float voxelSize);
 };

@@ -59,7 +59,9 @@ int vh_time_next_launch(void* startEvent, void* stopEvent);
  * vh_mesh_components init, hook, flatten, count (init alone without faces); vh_mesh_components_filter stats, with
  * largestOnly pick by key and pick by index, compact vertices, compact faces (not without faces);
  * vh_mesh_weld_accum_components the launches of vh_mesh_components, then those of vh_mesh_components_filter;
- * vh_mesh_cluster and vh_mesh_weld_accum_cluster insert, faces, number, emit (insert and number alone without faces). */
+ * vh_mesh_cluster and vh_mesh_weld_accum_cluster insert, faces, number, emit (insert and number alone without faces);
+ * vh_mesh_smooth and vh_mesh_weld_accum_smooth edges, degree, prepare, then gather and step per half step (two half
+ * steps an iteration), finish: 4 N + 4 launches (prepare and finish alone without faces). */
 int vh_time_launch_after(uint32_t skip, void* startEvent, void* stopEvent);
 int vh_stream_create(vhStream_t* out);   /* a non-blocking HIP stream, for FFI users without a HIP binding */
 int vh_stream_destroy(vhStream_t stream);
@@ -802,6 +804,35 @@ int vh_mesh_cluster_default_slots_log2(uint32_t count, uint32_t* slotsLog2);
  * launches nothing.  The mesh that went in stays as it is. */
 int vh_mesh_cluster(const VhVertex* d_vertices, const uint64_t* d_keys, const uint32_t* d_faces, uint32_t numVertices, uint32_t numFaces,
                     uint32_t cellsPerCluster, int32_t scaleLog2, const VhMeshClusterData* data, vhStream_t stream);
+/* ---- Taubin smoothing of an indexed mesh in fixed point (csrc/vh_mesh_smooth.hip; DESIGN.md section 4, "Mesh
+ * smoothing").  Vertex count, keys, colours and faces stay; the positions are replaced by `iterations` = N (1 ... 100)
+ * iterations of the lambda | mu scheme under the uniform umbrella operator, in 64-bit integers: the result does not
+ * depend on the order of the input or of the atomics.
+ * Edges: a face with an index >= numVertices sets VH_SMOOTH_BAD_INDEX and contributes nothing, a face with a repeated
+ * index contributes no edge, every other face names three undirected edges; the distinct edges are the neighbour
+ * relation, the faces that name an edge its use count, a vertex's distinct neighbours its degree n (above
+ * VH_SMOOTH_MAX_DEGREE: VH_SMOOTH_DEGREE).  An edge of use count 1 is a boundary edge, its ends boundary vertices.
+ * A vertex moves if n > 0 and, with keepBoundary = 1, it is no boundary vertex; every other vertex keeps its input
+ * bits (and still lends its position to its neighbours).
+ * q = rint(p * 2^scaleLog2) per component of every vertex (not finite or above 2^40: VH_SMOOTH_RANGE).  Half step
+ * k = 0 ... 2 N - 1 with f = lambdaQ16 (k even) or muQ16 (k odd), for a moved vertex, from the q of the half step
+ * before: d = sum over the neighbours of q_j - n q_i, u = floor((2 d + n) / (2 n)), q_i' = q_i + ((f u + 2^15) >> 16)
+ * (arithmetic shift); |q'| > 2^40: VH_SMOOTH_RANGE.  A moved vertex comes back as (float)((double) q * 2^-scaleLog2).
+ * vh_mesh_smooth_default_slots_log2: log2 of the edge table the pass wants for numFaces faces: the smallest power of
+ * two >= 6 numFaces, 64 slots at least.  VH_ERR_BAD_ARGUMENT above 0x15555555 faces. */
+int vh_mesh_smooth_default_slots_log2(uint32_t numFaces, uint32_t* slotsLog2);
+/* The pass, over the caller's mesh and the caller's buffers (VhMeshSmoothData, vh_types.h): edges (one lane per face),
+ * degree (one lane per edge slot), prepare (one lane per vertex), gather (one lane per edge slot) and step (one lane
+ * per vertex) per half step, finish (one lane per vertex); prepare and finish alone without faces.  lambdaQ16, muQ16:
+ * factors in units of 2^-16, |f| <= 65536.  data->m_edgeSlotsLog2 says how much of the table is used (a smaller value
+ * than the default fills it: VH_SMOOTH_TABLE_FULL).  data->d_counts: the VH_SMOOTH_NUM_COUNTS counts; with a status set
+ * (VH_SMOOTH_*) the other five are 0 and no vertex was written.  Callers map VH_SMOOTH_TABLE_FULL to
+ * VH_ERR_STAGING_OVERFLOW and every other bit to VH_ERR_BAD_ARGUMENT.  Asynchronous on `stream`; numVertices = 0
+ * launches nothing.  The mesh that went in stays as it is.  VH_ERR_BAD_ARGUMENT for iterations outside 1 ... 100, a
+ * factor above 1 in magnitude, keepBoundary above 1 and scaleLog2 outside -100 ... 100. */
+int vh_mesh_smooth(const VhVertex* d_vertices, const uint64_t* d_keys, const uint32_t* d_faces, uint32_t numVertices, uint32_t numFaces,
+                   uint32_t iterations, int32_t lambdaQ16, int32_t muQ16, uint32_t keepBoundary, int32_t scaleLog2, const VhMeshSmoothData* data,
+                   vhStream_t stream);
 /* Host only: vh::MeshData::applyTransform (when transform is not NULL) and saveToPLY on the caller's arrays.
  *   vertices3, colors4 (may be NULL), normals3 (may be NULL)   numVertices rows each
  *   faceIndices   numFaceIndices = 3 per face; 0 = a triangle soup
@@ -878,6 +909,20 @@ int vh_mesh_weld_accum_cluster_get_counts(VhMeshWeldAccum* accum, uint32_t out[6
 int vh_mesh_weld_accum_cluster_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint64_t* keys, uint32_t* faces, uint32_t numVertices,
                                         uint32_t numFaces, vhStream_t stream);
 
+/* The Taubin smoothing over the accumulated mesh (vh_mesh_smooth): a pass of the finish, never of an append, over the
+ * clustered mesh if a cluster pass is current, else over the welded one, into buffers of the accumulator's own.  Waits
+ * for the appends, launches, and waits for the counts.  After a pass without a status, vh_mesh_weld_accum_normals and
+ * vh_mesh_weld_accum_components work on the SMOOTHED vertices; a pass makes earlier normals and components stale.  A
+ * begin, an append or a later cluster pass makes it stale.  iterations = 0 launches nothing and forgets the last pass. */
+int vh_mesh_weld_accum_smooth(VhMeshWeldAccum* accum, uint32_t iterations, int32_t lambdaQ16, int32_t muQ16, uint32_t keepBoundary, int32_t scaleLog2,
+                              vhStream_t stream);
+/* Waits and reads the VH_SMOOTH_NUM_COUNTS counts.  VH_ERR_BAD_ARGUMENT when no pass is current or the pass left a
+ * status, VH_ERR_STAGING_OVERFLOW when that status is a full table alone; the other five counts are then 0. */
+int vh_mesh_weld_accum_smooth_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream);
+/* The smoothed vertices (keys and faces are the source mesh's: the clustered one's, or the welded one's).  numVertices:
+ * at most those of the source mesh.  Refused as above. */
+int vh_mesh_weld_accum_smooth_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint32_t numVertices, vhStream_t stream);
+
 /* handle level: CUDAMarchingCubesHashSDF (DSC/CUDAMarchingCubesHashSDF.h:8-67) */
 typedef struct VhMarchingCubes VhMarchingCubes;
 int vh_marching_cubes_create(const VhMarchingCubesParams* params, vhStream_t stream, VhMarchingCubes** out);
@@ -946,6 +991,16 @@ int vh_marching_cubes_get_indexed_component_stats(VhMarchingCubes* mc, uint32_t 
 int vh_marching_cubes_set_indexed_clustering(VhMarchingCubes* mc, uint32_t cellsPerCluster);
 /* of the last indexed extraction with clustering on: the VH_CLUSTER_NUM_COUNTS counts; all 0 when it ran with it off */
 int vh_marching_cubes_get_indexed_cluster_stats(VhMarchingCubes* mc, uint32_t out[6]);
+/* The Taubin smoothing for the indexed extractions (off by default: iterations = 0; 1 ... 100 turn it on).  When on, the
+ * three indexed extractions run vh_mesh_smooth after the clustering and BEFORE normals and components -- the
+ * accumulated ones at the finish -- at vh_mesh_cluster_default_scale_log2(voxelSize); normals (at the scale of twice
+ * the edge bound used without smoothing: a margin, not a proof) and components are then of the smoothed mesh, and
+ * download_indexed, the host mesh and save_mesh carry the smoothed positions.  A status of the pass:
+ * VH_ERR_BAD_ARGUMENT or VH_ERR_STAGING_OVERFLOW, the host mesh empty.  VH_ERR_BAD_ARGUMENT for iterations > 100, a
+ * factor above 1 in magnitude and keepBoundary above 1. */
+int vh_marching_cubes_set_indexed_smoothing(VhMarchingCubes* mc, uint32_t iterations, int32_t lambdaQ16, int32_t muQ16, uint32_t keepBoundary);
+/* of the last indexed extraction with smoothing on: the VH_SMOOTH_NUM_COUNTS counts; all 0 when it ran with it off */
+int vh_marching_cubes_get_indexed_smooth_stats(VhMarchingCubes* mc, uint32_t out[6]);
 /* the first n source records of the last indexed extraction (n <= min(triangles produced, m_maxNumTriangles)) */
 int vh_marching_cubes_download_sources(VhMarchingCubes* mc, VhTriangleSource* out, uint32_t n);
 int vh_marching_cubes_copy_triangles_to_cpu(VhMarchingCubes* mc);

@@ -276,6 +276,42 @@ typedef struct VhMeshClusterData {
     uint32_t m_clusterSlotsLog2, m_faceSlotsLog2;
 } VhMeshClusterData;
 
+/* status word of the Taubin smoothing (vh_mesh_smooth); any bit leaves the output unwritten and the other counts 0 */
+#define VH_SMOOTH_TABLE_FULL 1u /* the edge table has no free slot left */
+#define VH_SMOOTH_RANGE 2u      /* a scaled position is not finite or exceeds 2^40 in a component, before or after a half step */
+#define VH_SMOOTH_BAD_INDEX 4u  /* a face index >= numVertices (nothing was read through it; the face contributes nothing) */
+#define VH_SMOOTH_DEGREE 8u     /* a vertex with more than VH_SMOOTH_MAX_DEGREE distinct neighbours */
+#define VH_SMOOTH_MAX_DEGREE 65536u   /* 2^16 neighbours of at most 2^40 each: a sum stays below 2^56, sum - n q below 2^57 */
+#define VH_SMOOTH_MAX_ITERATIONS 100u /* iterations are 1 ... 100; each is two half steps */
+#define VH_SMOOTH_MAX_FACTOR_Q16 65536 /* |lambdaQ16|, |muQ16| <= 2^16: factors in [-1, 1] */
+#define VH_SMOOTH_DEFAULT_LAMBDA_Q16 32768   /* 0.5 */
+#define VH_SMOOTH_DEFAULT_MU_Q16 (-34734)    /* rint(-0.53 * 2^16) */
+/* what vh_mesh_smooth counts */
+enum {
+    VH_SMOOTH_MOVED = 0,          /* vertices that the pass moves */
+    VH_SMOOTH_BOUNDARY = 1,       /* vertices at an end of an edge that exactly one face names */
+    VH_SMOOTH_ISOLATED = 2,       /* vertices without an edge */
+    VH_SMOOTH_STATUS = 3,
+    VH_SMOOTH_EDGES = 4,          /* distinct undirected edges */
+    VH_SMOOTH_BOUNDARY_EDGES = 5, /* of them, those that exactly one face names */
+    VH_SMOOTH_NUM_COUNTS = 6
+};
+/* Device buffers of the Taubin smoothing (vh_mesh_smooth): the caller's, sized for the mesh that goes in.  The edge
+ * table has 1 << m_edgeSlotsLog2 slots (at least six times the faces: twice the edges at worst); the launcher empties
+ * what it uses of it. */
+typedef struct VhMeshSmoothData {
+    uint64_t* d_edgeKeys;      /* per edge slot: lo | hi << 32 with lo < hi, all ones = empty */
+    uint32_t* d_edgeUses;      /* per edge slot: the faces that name the edge */
+    uint32_t* d_degree;        /* per vertex: its distinct neighbours */
+    uint32_t* d_flags;         /* per vertex: a boundary vertex (0 / 1) from the degree pass; bit 1 = moves, from the prepare pass on */
+    int64_t* d_positions;      /* 2 x 3 per vertex: the fixed-point positions, half step in and half step out */
+    int64_t* d_sums;           /* 3 per vertex: the neighbours' positions summed */
+    uint32_t* d_work;          /* 5 words */
+    VhVertex* d_vertices;      /* out: as many vertices as go in */
+    uint32_t* d_counts;        /* VH_SMOOTH_NUM_COUNTS words */
+    uint32_t m_edgeSlotsLog2, m_pad;
+} VhMeshSmoothData;
+
 /* Device buffers of the weld (vh_mesh_weld): an open-addressing table of numSlots = 1 << m_slotsLog2 slots, and the
  * indexed mesh it produces.  Sized for m_maxTriangles triangles, that is 3 * m_maxTriangles vertices at worst. */
 typedef struct VhMeshWeldData {

@@ -40,6 +40,15 @@ vertices, faces and download size before and after, and the wall time of the ext
 one with it off.  With --streamed: the pass over the finished accumulation, and the indexed walk with it on.
 
     python tools/bench_mesh.py --indexed --cluster 2 [--streamed] [--config cfg3]
+
+--smooth N (with --indexed) adds N iterations of the Taubin smoothing ("Mesh smoothing"), over the
+clustered mesh with --cluster M and else over the welded one: its edge, degree, prepare and finish kernels and the
+first half step's gather and step by vh_time_launch_after, the whole pass of 4 N + 4 launches between two events and
+what that makes per launch, the edge table's slots beside the edges there are, and the wall time of the extraction
+with smoothing on beside the one with it off.  With --streamed: the pass over the finished accumulation (wall clock,
+the wait for the counts included), and the indexed walk with it on.
+
+    python tools/bench_mesh.py --indexed --smooth 10 [--cluster 2] [--streamed] [--config cfg3]
 """
 import argparse
 import ctypes as C
@@ -167,7 +176,46 @@ def indexed_report(args, scene, hp):
         out.update(cluster=stats, cluster_cells=args.cluster, cluster_scale_log2=scale, cluster_pass_us=round(total, 2),
                    cluster_share_of_indexed_kernels=round(total / (kernels + total), 4),
                    cluster_device_bytes=sum(b.nbytes for b in bufs), download_bytes_clustered=24 * stats["vertices"] + 12 * stats["faces"])
-        for b in bufs:
+        if args.smooth:  # the smoothing below runs over the clustered mesh
+            clustered = (bufs[9].ptr, bufs[10].ptr, bufs[11].ptr, stats["vertices"], stats["faces"])
+            held = bufs
+        else:
+            for b in bufs:
+                b.free()
+    if args.smooth:
+        sv, sk, sf, SV, SF = clustered if args.cluster else (w.d_vertices, w.d_keys, w.d_faces, V, F)
+        scale = E.mesh_cluster_default_scale_log2(hp.m_virtualVoxelSize)
+        log = C.c_uint32()
+        lib.check(L.vh_mesh_smooth_default_slots_log2(SF, C.byref(log)), "vh_mesh_smooth_default_slots_log2")
+        es = 1 << int(log.value)
+        bufs = [lib.DeviceBuffer(n) for n in (8 * es, 4 * es, 4 * SV, 4 * SV, 48 * SV, 24 * SV, 20, 24 * SV, 24)]
+        sd = T.MeshSmoothData(*[b.ptr for b in bufs], int(log.value), 0)
+        lam, mu = T.SMOOTH_DEFAULT_LAMBDA_Q16, T.SMOOTH_DEFAULT_MU_Q16
+        run = lambda: lib.check(L.vh_mesh_smooth(sv, sk, sf, SV, SF, args.smooth, lam, mu, 1, scale, C.byref(sd), None), "vh_mesh_smooth")
+        launches = 4 * args.smooth + 4
+        for skip, name in ((0, "smooth_edges_us"), (1, "smooth_degree_us"), (2, "smooth_prepare_us"), (3, "smooth_gather_us"), (4, "smooth_step_us"),
+                           (launches - 1, "smooth_finish_us")):
+            out[name] = timed(skip, run)
+        hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+        whole = []
+        for i in range(3 + args.reps):  # the pass between two events on the null stream, the launches' gaps included
+            assert hip.hipEventRecord(e0, None) == 0
+            run()
+            assert hip.hipEventRecord(e1, None) == 0
+            lib.check(L.vh_stream_synchronize(None), "synchronize")
+            ms = C.c_float()
+            assert hip.hipEventElapsedTime(C.byref(ms), e0, e1) == 0
+            if i >= 3:
+                whole.append(1e3 * ms.value)
+        stats = {k: int(v) for k, v in zip(T.SMOOTH_COUNTS, bufs[8].download(np.uint32, 6))}
+        assert stats["status"] == 0, "the smoothing left a status"
+        total = round(float(np.median(whole)), 2)
+        kernels = out["pass2_sourced_us"] + out["weld_insert_us"] + out["weld_number_us"] + out["weld_faces_us"] + out.get("cluster_pass_us", 0.0)
+        out.update(smooth=stats, smooth_iterations=args.smooth, smooth_scale_log2=scale, smooth_vertices=SV, smooth_faces=SF, smooth_launches=launches,
+                   smooth_pass_us=total, smooth_pass_us_range=[round(min(whole), 2), round(max(whole), 2)], smooth_us_per_launch=round(total / launches, 2),
+                   smooth_half_step_kernels_us=round(out["smooth_gather_us"] + out["smooth_step_us"], 2),
+                   smooth_share_of_indexed=round(total / (kernels + total), 4), smooth_edge_slots=es, smooth_device_bytes=sum(b.nbytes for b in bufs))
+        for b in bufs + (held if args.cluster else []):
             b.free()
     L.vh_mesh_weld_data_free(C.byref(w))
     L.vh_marching_cubes_data_free(C.byref(data))
@@ -219,6 +267,21 @@ def indexed_report(args, scene, hp):
             mc.setIndexedClustering(0)
             spread = lambda v: [round(float(np.min(v)), 5), round(float(np.median(v)), 5), round(float(np.max(v)), 5)]
             out.update(extract_indexed_cluster_off_wall_s=spread(walls[False]), extract_indexed_cluster_on_wall_s=spread(walls[True]))
+        if args.smooth:  # the whole extraction (clustered with --cluster), smoothing off and on, alternating (the first pair sizes the buffers)
+            mc.setIndexedNormals(bool(args.normals))
+            mc.setIndexedClustering(args.cluster)
+            walls = {False: [], True: []}
+            for rep in range(1 + max(args.reps, 3)):
+                for on in (False, True):
+                    mc.setIndexedSmoothing(args.smooth if on else 0)
+                    t0 = time.perf_counter()
+                    mc.extractIsoSurfaceIndexed(hd, hpp)
+                    if rep > 0:
+                        walls[on].append(time.perf_counter() - t0)
+            mc.setIndexedSmoothing(0)
+            mc.setIndexedClustering(0)
+            spread = lambda v: [round(float(np.min(v)), 5), round(float(np.median(v)), 5), round(float(np.max(v)), 5)]
+            out.update(extract_indexed_smooth_off_wall_s=spread(walls[False]), extract_indexed_smooth_on_wall_s=spread(walls[True]))
     out.update(host_merge_s=round(t_soup - t_ply, 4), ply_write_s=round(t_ply, 4), extract_indexed_wall_s=round(t_indexed, 4))
     return out
 
@@ -315,6 +378,19 @@ def streamed_report(args, scene, hp):
         lib.check(L.vh_mesh_weld_accum_cluster_get_counts(accum, kc, None), "vh_mesh_weld_accum_cluster_get_counts")
         out.update(cluster={k: int(kc[i]) for i, k in enumerate(T.CLUSTER_COUNTS)}, cluster_cells=args.cluster, cluster_scale_log2=scale,
                    download_bytes_clustered=24 * int(kc[0]) + 12 * int(kc[1]))
+    if args.smooth:  # over the finished accumulation (clustered above with --cluster); the first pass makes the buffers
+        scale = E.mesh_cluster_default_scale_log2(hp.m_virtualVoxelSize)
+        us = []
+        for rep in range(3 + args.reps):
+            lib.check(L.vh_stream_synchronize(None), "synchronize")
+            t0 = time.perf_counter()
+            lib.check(L.vh_mesh_weld_accum_smooth(accum, args.smooth, T.SMOOTH_DEFAULT_LAMBDA_Q16, T.SMOOTH_DEFAULT_MU_Q16, 1, scale, None), "vh_mesh_weld_accum_smooth")
+            if rep >= 3:
+                us.append(1e6 * (time.perf_counter() - t0))
+        sc = (C.c_uint32 * 6)()
+        lib.check(L.vh_mesh_weld_accum_smooth_get_counts(accum, sc, None), "vh_mesh_weld_accum_smooth_get_counts")
+        out.update(smooth={k: int(sc[i]) for i, k in enumerate(T.SMOOTH_COUNTS)}, smooth_iterations=args.smooth, smooth_scale_log2=scale,
+                   smooth_launches=4 * args.smooth + 4, accum_smooth_wall_us=round(float(np.median(us)), 1))
     L.vh_mesh_weld_accum_destroy(accum)
     L.vh_marching_cubes_data_free(C.byref(data))
     for name in names:
@@ -331,7 +407,7 @@ def streamed_report(args, scene, hp):
     try:
         with tempfile.TemporaryDirectory() as d:
             walls = dict(soup_walk_s=[], soup_save_s=[], indexed_walk_s=[], indexed_save_s=[])
-            normal_walks, cluster_walks = [], []
+            normal_walks, cluster_walks, smooth_walks = [], [], []
             for rep in range(1 + max(args.reps, 3)):  # the first pair of walks sizes every buffer
                 t0 = time.perf_counter()
                 mc.extractIsoSurfaceChunkGrid(grid, pos, radius)
@@ -365,6 +441,16 @@ def streamed_report(args, scene, hp):
                         cluster_walks.append(time.perf_counter() - t8)
                     mc.setIndexedClustering(0)
                     mc.clearMeshBuffer()
+                if args.smooth:
+                    mc.setIndexedClustering(args.cluster)
+                    mc.setIndexedSmoothing(args.smooth)
+                    t9 = time.perf_counter()
+                    mc.extractIsoSurfaceIndexedChunkGrid(grid, pos, radius)
+                    if rep > 0:
+                        smooth_walks.append(time.perf_counter() - t9)
+                    mc.setIndexedSmoothing(0)
+                    mc.setIndexedClustering(0)
+                    mc.clearMeshBuffer()
     finally:
         grid.close()
     w = {k: float(np.median(v)) for k, v in walls.items()}
@@ -379,6 +465,8 @@ def streamed_report(args, scene, hp):
         out.update(indexed_walk_normals_s=round(float(np.median(normal_walks)), 4), indexed_walk_normals_min_s=round(min(normal_walks), 4))
     if args.cluster:
         out.update(indexed_walk_cluster_s=round(float(np.median(cluster_walks)), 4), indexed_walk_cluster_min_s=round(min(cluster_walks), 4))
+    if args.smooth:
+        out.update(indexed_walk_smooth_s=round(float(np.median(smooth_walks)), 4), indexed_walk_smooth_min_s=round(min(smooth_walks), 4))
     return out
 
 
@@ -394,7 +482,10 @@ def main():
     ap.add_argument("--components", action="store_true", help="--indexed: add the component pass: its kernels, its share of the extraction, the labelling on the host beside it")
     ap.add_argument("--min-component", type=int, default=100, help="--components: the filter's minFaces")
     ap.add_argument("--cluster", type=int, default=0, metavar="M", help="--indexed: add the vertex clustering at M (1 ... 64) lattice points a side: its kernels, the mesh before and after, the extraction with it on and off")
+    ap.add_argument("--smooth", type=int, default=0, metavar="N", help="--indexed: add N (1 ... 100) iterations of the Taubin smoothing, over the clustered mesh with --cluster: its kernels, the pass, the extraction with it on and off")
     args = ap.parse_args()
+    if args.smooth and (not args.indexed or not 1 <= args.smooth <= 100):
+        ap.error("--smooth needs --indexed, and 1 ... 100 iterations")
     if args.cluster and (not args.indexed or not 1 <= args.cluster <= 64):
         ap.error("--cluster needs --indexed, and 1 ... 64 lattice points a side")
     if args.normals and not args.indexed:

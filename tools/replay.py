@@ -3,7 +3,8 @@
 parameter file, optional mesh at the end) and prints one JSON line with the timing.
 
     python tools/replay.py --params zParameters.txt [--tracking zParametersTracking.txt] [--rgbd-tracking] [--sens a.sens b.sens]
-                           [--mesh scan.ply [--indexed-mesh [--mesh-normals] [--mesh-min-component N] [--mesh-largest-component] [--mesh-cluster M]]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
+                           [--mesh scan.ply [--indexed-mesh [--mesh-normals] [--mesh-min-component N] [--mesh-largest-component] [--mesh-cluster M]
+                           [--mesh-smooth N [--mesh-smooth-lambda L] [--mesh-smooth-mu M] [--mesh-smooth-free-boundary]]]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
                            [--native [--batch N] [--native-tracking]] [--weighted-colour]
 
 Without --sens the files named by s_binaryDumpSensorFile[i] in the parameter file are played.  The rendering keys
@@ -44,6 +45,10 @@ def main():
     ap.add_argument("--mesh-min-component", type=int, default=0, metavar="N", help="--indexed-mesh: drop the connected components of fewer than N faces on the device before the mesh is written")
     ap.add_argument("--mesh-largest-component", action="store_true", help="--indexed-mesh: keep only the connected component with the most faces")
     ap.add_argument("--mesh-cluster", type=int, default=0, metavar="M", help="--indexed-mesh: decimate the mesh on the device before it is written: the vertices in one cube of M (2 ... 64) voxel-lattice points a side become one")
+    ap.add_argument("--mesh-smooth", type=int, default=None, metavar="N", help="--indexed-mesh: N (1 ... 100) iterations of Taubin smoothing on the device, after the clustering and before the normals")
+    ap.add_argument("--mesh-smooth-lambda", type=float, default=0.5, metavar="L", help="--mesh-smooth: the shrinking factor (0.5)")
+    ap.add_argument("--mesh-smooth-mu", type=float, default=-0.53, metavar="M", help="--mesh-smooth: the inflating factor (-0.53)")
+    ap.add_argument("--mesh-smooth-free-boundary", action="store_true", help="--mesh-smooth: move the vertices of the mesh's open boundary too")
     ap.add_argument("--record", default=None, help="write what was processed, with the poses used, to this .sens file")
     ap.add_argument("--max-frames", type=int, default=None)
     ap.add_argument("--render-to", default=None, help="renderToFile: the shaded model and the input of every frame as PNGs under this directory")
@@ -63,6 +68,13 @@ def main():
         ap.error("--mesh-cluster needs --indexed-mesh: clustering works on the welded mesh's vertex keys")
     if args.mesh_cluster and not 2 <= args.mesh_cluster <= 64:
         ap.error("--mesh-cluster: 2 ... 64 lattice points a side")
+    if args.mesh_smooth is not None and not args.indexed_mesh:
+        ap.error("--mesh-smooth needs --indexed-mesh: a triangle soup has no neighbours")
+    if args.mesh_smooth is not None and not 1 <= args.mesh_smooth <= 100:
+        ap.error("--mesh-smooth: 1 ... 100 iterations")
+    args.mesh_smooth = args.mesh_smooth or 0  # (not given: off)
+    if not (abs(args.mesh_smooth_lambda) <= 1.0 and abs(args.mesh_smooth_mu) <= 1.0):
+        ap.error("--mesh-smooth-lambda, --mesh-smooth-mu: factors in [-1, 1]")
     if args.mesh_min_component < 0:
         ap.error("--mesh-min-component: a number of faces")
     import torch
@@ -112,7 +124,8 @@ def main():
     if args.mesh:
         if args.indexed_mesh:
             m = rec.extractIsoSurfaceIndexed(args.mesh, normals=args.mesh_normals, min_component_faces=args.mesh_min_component, largest_component=args.mesh_largest_component,
-                                             cluster_cells=args.mesh_cluster)
+                                             cluster_cells=args.mesh_cluster, smooth_iterations=args.mesh_smooth, smooth_lambda=args.mesh_smooth_lambda,
+                                             smooth_mu=args.mesh_smooth_mu, keep_boundary=not args.mesh_smooth_free_boundary)
         else:
             m = rec.extractIsoSurface(args.mesh)
         out["mesh"] = dict(file=args.mesh, indexed=bool(args.indexed_mesh), vertices=int(len(m["vertices"])), faces=int(len(m["faces"])))
@@ -122,6 +135,8 @@ def main():
             out["mesh"]["components"] = m["components"]
         if args.mesh_cluster:
             out["mesh"]["clustering"] = m["clustering"]
+        if args.mesh_smooth:
+            out["mesh"]["smoothing"] = m["smoothing"]
     print(json.dumps(out))
 
 

@@ -446,6 +446,17 @@ int vh_marching_cubes_get_indexed_cluster_stats(VhMarchingCubes* mc, uint32_t ou
     mc->impl.getIndexedClusterStats(out);
     return VH_OK;
 }
+int vh_marching_cubes_set_indexed_smoothing(VhMarchingCubes* mc, uint32_t iterations, int32_t lambdaQ16, int32_t muQ16, uint32_t keepBoundary)
+{
+    if (!mc || keepBoundary > 1u) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.setIndexedSmoothingQ16(iterations, lambdaQ16, muQ16, keepBoundary != 0u); });
+}
+int vh_marching_cubes_get_indexed_smooth_stats(VhMarchingCubes* mc, uint32_t out[6])
+{
+    if (!mc || !out) return VH_ERR_BAD_ARGUMENT;
+    mc->impl.getIndexedSmoothStats(out);
+    return VH_OK;
+}
 int vh_marching_cubes_download_indexed_normals(VhMarchingCubes* mc, float* normals)
 {
     if (!mc) return VH_ERR_BAD_ARGUMENT;

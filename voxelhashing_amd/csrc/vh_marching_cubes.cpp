@@ -21,6 +21,7 @@
 #include "vh_mesh_cluster.hpp"
 #include "vh_mesh_components.hpp"
 #include "vh_mesh_normals.hpp"
+#include "vh_mesh_smooth.hpp"
 
 // ---------------------------------------------------------------------------
 // launcher-level buffers
@@ -370,10 +371,25 @@ void CUDAMarchingCubesHashSDF::setIndexedClustering(unsigned int cellsPerCluster
     m_clusterCells = cellsPerCluster;
 }
 
+void CUDAMarchingCubesHashSDF::setIndexedSmoothing(unsigned int iterations, float lambda, float mu, bool keepBoundary)
+{
+    if (iterations > VH_SMOOTH_MAX_ITERATIONS) throw vh::Error(VH_ERR_BAD_ARGUMENT, "setIndexedSmoothing: at most 100 iterations");
+    if (!(std::fabs(lambda) <= 1.0f) || !(std::fabs(mu) <= 1.0f)) throw vh::Error(VH_ERR_BAD_ARGUMENT, "setIndexedSmoothing: factors in [-1, 1]");
+    setIndexedSmoothingQ16(iterations, (int32_t)std::rint((double)lambda * 65536.0), (int32_t)std::rint((double)mu * 65536.0), keepBoundary);
+}
+
+void CUDAMarchingCubesHashSDF::setIndexedSmoothingQ16(unsigned int iterations, int32_t lambdaQ16, int32_t muQ16, bool keepBoundary)
+{
+    if (iterations > VH_SMOOTH_MAX_ITERATIONS) throw vh::Error(VH_ERR_BAD_ARGUMENT, "setIndexedSmoothing: at most 100 iterations");
+    if (lambdaQ16 < -VH_SMOOTH_MAX_FACTOR_Q16 || lambdaQ16 > VH_SMOOTH_MAX_FACTOR_Q16 || muQ16 < -VH_SMOOTH_MAX_FACTOR_Q16 || muQ16 > VH_SMOOTH_MAX_FACTOR_Q16)
+        throw vh::Error(VH_ERR_BAD_ARGUMENT, "setIndexedSmoothing: factors in [-1, 1]");
+    m_smoothIterations = iterations; m_smoothLambdaQ16 = lambdaQ16; m_smoothMuQ16 = muQ16; m_smoothKeepBoundary = keepBoundary;
+}
+
 void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf, bool accumulated, float voxelSize)
 {
     vh::MeshData md;
-    const bool filter = m_componentMinFaces != 0 || m_componentLargestOnly, cluster = m_clusterCells != 0;
+    const bool filter = m_componentMinFaces != 0 || m_componentLargestOnly, cluster = m_clusterCells != 0, smooth = m_smoothIterations != 0;
     // (an accumulation without an append has no voxel size, and no vertex either: any scale serves)
     const bool sized = voxelSize > 0.0f || !accumulated;
     unsigned int clusterStats[VH_CLUSTER_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
@@ -404,11 +420,37 @@ void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf,
     }
     const unsigned int weldedVertices = nv, weldedFaces = nf;
     if (cluster) { nv = clusterStats[VH_CLUSTER_VERTICES]; nf = clusterStats[VH_CLUSTER_FACES]; }
+    unsigned int smoothStats[VH_SMOOTH_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
+    if (smooth) {
+        // a vertex's neighbours span chunks: a pass of the finish, over the mesh as it stands here, at the clustering's scale
+        int32_t smoothScale = 0;
+        if (sized) check(vh_mesh_cluster_default_scale_log2(voxelSize, &smoothScale), "vh_mesh_cluster_default_scale_log2");
+        int rc = VH_OK;
+        if (accumulated) {
+            check(vh_mesh_weld_accum_smooth(m_accum.get(), m_smoothIterations, m_smoothLambdaQ16, m_smoothMuQ16, m_smoothKeepBoundary ? 1u : 0u, smoothScale, m_stream),
+                  "vh_mesh_weld_accum_smooth");
+            rc = vh_mesh_weld_accum_smooth_get_counts(m_accum.get(), smoothStats, m_stream);
+        } else {
+            if (!m_smooth) m_smooth.reset(new VhMeshSmooth);
+            check(m_smooth->run(d_vertices, d_keys, d_faces, nv, nf, m_smoothIterations, m_smoothLambdaQ16, m_smoothMuQ16, m_smoothKeepBoundary ? 1u : 0u, smoothScale,
+                                m_stream), "vh_mesh_smooth");
+            rc = m_smooth->counts(smoothStats, m_stream);
+            d_vertices = m_smooth->vertices.get();
+        }
+        if (rc == VH_ERR_STAGING_OVERFLOW) throw vh::Error(rc, "mesh smoothing: the edge table is full");
+        if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "mesh smoothing: a value out of the fixed-point range, a face index out of bounds, or a vertex of more than 65536 neighbours");
+        check(rc, "mesh smoothing");
+    } else if (accumulated) {
+        // a finish of these appends with smoothing on may have gone before: the passes below take the vertices as they were
+        check(vh_mesh_weld_accum_smooth(m_accum.get(), 0, 0, 0, 0, 0, m_stream), "vh_mesh_weld_accum_smooth");
+    }
     int32_t scaleLog2 = 0;
     // the vertices of a welded face lie in adjacent clusters and inside their clusters' boxes: an edge of a clustered
-    // face stays under 2 m voxels in every component, and the normals' scale is that of a voxel of 2 m voxelSize
+    // face stays under 2 m voxels in every component, and the normals' scale is that of a voxel of 2 m voxelSize.
+    // Smoothing can lengthen an edge: twice that bound again, which is a margin and not a proof (VH_NORMALS_RANGE says so)
     if (m_indexedNormals && sized)
-        check(vh_mesh_normals_default_scale_log2(cluster ? 2.0f * (float)m_clusterCells * voxelSize : voxelSize, &scaleLog2), "vh_mesh_normals_default_scale_log2");
+        check(vh_mesh_normals_default_scale_log2((smooth ? 2.0f : 1.0f) * (cluster ? 2.0f * (float)m_clusterCells * voxelSize : voxelSize), &scaleLog2),
+              "vh_mesh_normals_default_scale_log2");
     if (m_indexedNormals) {
         // over all the faces, with the bits the last append left: a pass of the finish, never of an append.  With the
         // filter on only the pass's status comes back here: the normals come with the filtered mesh.
@@ -447,7 +489,16 @@ void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf,
     std::vector<VhVertex> verts(mv);
     md.m_FaceIndicesVertices.resize(3 * (size_t)mf);
     float* normals = filter && m_indexedNormals ? md.m_Normals.data() : nullptr;
-    if (filter && accumulated) check(vh_mesh_weld_accum_components_download(m_accum.get(), verts.data(), nullptr, normals, md.m_FaceIndicesVertices.data(), mv, mf, m_stream), "vh_mesh_weld_accum_components_download");
+    if (smooth && !filter) { // the smoothed vertices with the faces of the mesh they were made from
+        VhVertex* none = nullptr;
+        if (accumulated) check(vh_mesh_weld_accum_smooth_download(m_accum.get(), verts.data(), nv, m_stream), "vh_mesh_weld_accum_smooth_download");
+        else check(m_smooth->download(verts.data(), nv, m_stream), "mesh smoothing");
+        if (cluster && accumulated) check(vh_mesh_weld_accum_cluster_download(m_accum.get(), none, nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_cluster_download");
+        else if (cluster) check(m_cluster->download(none, nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "mesh clustering");
+        else if (accumulated) check(vh_mesh_weld_accum_download(m_accum.get(), none, nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_download");
+        else check(vh_mesh_weld_download(&m_weld, none, nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_download");
+    }
+    else if (filter && accumulated) check(vh_mesh_weld_accum_components_download(m_accum.get(), verts.data(), nullptr, normals, md.m_FaceIndicesVertices.data(), mv, mf, m_stream), "vh_mesh_weld_accum_components_download");
     else if (filter) check(m_components->download(verts.data(), nullptr, normals, md.m_FaceIndicesVertices.data(), mv, mf, m_stream), "mesh components");
     else if (cluster && accumulated) check(vh_mesh_weld_accum_cluster_download(m_accum.get(), verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_cluster_download");
     else if (cluster) check(m_cluster->download(verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "mesh clustering");
@@ -458,6 +509,8 @@ void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf,
     m_indexed.counts[0] = weldedVertices; m_indexed.counts[1] = weldedFaces;
     m_indexed.clustered = cluster;
     std::copy(clusterStats, clusterStats + VH_CLUSTER_NUM_COUNTS, m_indexed.clusterStats);
+    m_indexed.smoothed = smooth;
+    std::copy(smoothStats, smoothStats + VH_SMOOTH_NUM_COUNTS, m_indexed.smoothStats);
     m_indexed.hasNormals = m_indexedNormals;
     m_indexed.filtered = filter;
     m_indexed.kept[0] = mv; m_indexed.kept[1] = mf;
@@ -529,6 +582,7 @@ void CUDAMarchingCubesHashSDF::finishIndexed()
     m_indexed.hasNormals = false;
     m_indexed.filtered = false;
     m_indexed.clustered = false;
+    m_indexed.smoothed = false;
     checkWeld(rc, "vh_mesh_weld_accum_get_counts");
     readBackIndexed(stats[VH_WELD_ACCUM_VERTICES], stats[VH_WELD_ACCUM_FACES], true, m_indexed.voxelSize);
     std::copy(stats, stats + VH_WELD_ACCUM_NUM_COUNTS, m_indexed.counts);
@@ -604,6 +658,14 @@ void CUDAMarchingCubesHashSDF::downloadIndexed(VhVertex* vertices, uint64_t* key
         if (m_indexed.accumulated) check(vh_mesh_weld_accum_components_download(m_accum.get(), vertices, keys, nullptr, faces, kv, kf, m_stream), "vh_mesh_weld_accum_components_download");
         else check(m_components->download(vertices, keys, nullptr, faces, kv, kf, m_stream), "mesh components");
         return;
+    }
+    if (m_indexed.smoothed) { // the smoothing's own vertices; keys and faces are those of the mesh it ran over, below
+        const unsigned int sv = m_indexed.clustered ? m_indexed.clusterStats[VH_CLUSTER_VERTICES] : m_indexed.counts[0];
+        if (vertices && sv != 0) {
+            if (m_indexed.accumulated) check(vh_mesh_weld_accum_smooth_download(m_accum.get(), vertices, sv, m_stream), "vh_mesh_weld_accum_smooth_download");
+            else check(m_smooth->download(vertices, sv, m_stream), "mesh smoothing");
+        }
+        vertices = nullptr;
     }
     if (m_indexed.clustered) { // the clustering's own buffers, as above
         const unsigned int cv = m_indexed.clusterStats[VH_CLUSTER_VERTICES], cf = m_indexed.clusterStats[VH_CLUSTER_FACES];

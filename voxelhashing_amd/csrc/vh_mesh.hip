@@ -21,6 +21,7 @@
 #include "vh_mesh_cluster.hpp"
 #include "vh_mesh_components.hpp"
 #include "vh_mesh_normals.hpp"
+#include "vh_mesh_smooth.hpp"
 
 using namespace vhd;
 
@@ -767,6 +768,10 @@ struct VhMeshWeldAccum {
     bool m_clusterRan = false;          // the pass has run, and no begin or append since
     bool m_clusterValid = false;        // ... and left no status: normals and components are then of ITS mesh,
     uint32_t m_clusterVertices = 0, m_clusterFaces = 0; // which has this size
+    VhMeshSmooth smooth;                // the Taubin smoothing (vh_mesh_weld_accum_smooth): made by the first pass
+    bool m_smoothRan = false;           // the pass has run, and no begin, append or cluster pass since
+    bool m_smoothValid = false;         // ... and left no status: normals and components then take ITS vertices,
+    uint32_t m_smoothVertices = 0;      // as many as the mesh it ran over has
     size_t m_soupCapacity = 0, m_vertexCapacity = 0, m_faceCapacity = 0; // in soup vertices, welded vertices, faces
     uint32_t m_slotsLog2 = 6, m_firstSlotsLog2 = 6;
     bool m_fixed = false, m_begun = false;
@@ -780,7 +785,8 @@ struct VhMeshWeldAccum {
 
 namespace {
 
-// the mesh that the passes of the finish work on: the clustered one once vh_mesh_weld_accum_cluster has run over these
+// the mesh that the passes of the finish work on (`smoothed`: with the vertices of vh_mesh_weld_accum_smooth once that
+// has run over it): the clustered one once vh_mesh_weld_accum_cluster has run over these
 // appends, else the weld's own, whose counts are `have`
 struct AccumMesh {
     const VhVertex* vertices;
@@ -788,10 +794,12 @@ struct AccumMesh {
     const uint32_t* faces;
     uint32_t numVertices, numFaces;
 };
-AccumMesh accumMesh(const VhMeshWeldAccum& a, const uint32_t have[VH_WELD_ACCUM_NUM_COUNTS])
+AccumMesh accumMesh(const VhMeshWeldAccum& a, const uint32_t have[VH_WELD_ACCUM_NUM_COUNTS], bool smoothed = true)
 {
-    if (a.m_clusterValid) return AccumMesh{ a.cluster.vertices.get(), a.cluster.keys.get(), a.cluster.faces.get(), a.m_clusterVertices, a.m_clusterFaces };
-    return AccumMesh{ a.vertices.get(), a.keys.get(), a.faces.get(), have[VH_WELD_ACCUM_VERTICES], have[VH_WELD_ACCUM_FACES] };
+    AccumMesh m = a.m_clusterValid ? AccumMesh{ a.cluster.vertices.get(), a.cluster.keys.get(), a.cluster.faces.get(), a.m_clusterVertices, a.m_clusterFaces }
+                                   : AccumMesh{ a.vertices.get(), a.keys.get(), a.faces.get(), have[VH_WELD_ACCUM_VERTICES], have[VH_WELD_ACCUM_FACES] };
+    if (smoothed && a.m_smoothValid && a.m_smoothVertices == m.numVertices) m.vertices = a.smooth.vertices.get();
+    return m;
 }
 
 // errors of the owner types (vh::deviceAlloc throws) become codes, as at the handle level
@@ -883,6 +891,7 @@ int vh_mesh_weld_accum_begin(VhMeshWeldAccum* accum, vhStream_t stream)
     accum->m_normalsValid = false;
     accum->m_componentsValid = false;
     accum->m_clusterValid = accum->m_clusterRan = false;
+    accum->m_smoothValid = accum->m_smoothRan = false;
     return VH_OK;
 }
 
@@ -894,6 +903,7 @@ int vh_mesh_weld_accum_append(VhMeshWeldAccum* accum, const VhTriangle* d_triang
     accum->m_normalsValid = false; // normals are of all faces with the final vertex bits: a pass before this append is stale
     accum->m_componentsValid = false; // and a component spans appends
     accum->m_clusterValid = accum->m_clusterRan = false; // and so does a cluster
+    accum->m_smoothValid = accum->m_smoothRan = false;   // and a vertex's neighbours
     if (numTriangles == 0) return VH_OK; // nothing to take, and no launch with an empty grid
     if (accum->m_appends >= VH_WELD_ACCUM_MAX_APPENDS - 1u) return VH_ERR_BAD_ARGUMENT;
     hipStream_t s = (hipStream_t)stream;
@@ -1018,13 +1028,14 @@ int vh_mesh_weld_accum_cluster(VhMeshWeldAccum* accum, uint32_t cellsPerCluster,
 {
     if (!accum || !accum->m_begun || cellsPerCluster > VH_CLUSTER_MAX_CELLS || scaleLog2 < -100 || scaleLog2 > 100) return VH_ERR_BAD_ARGUMENT;
     if (cellsPerCluster == 0u) { // forget the pass: the passes of the finish are of the welded mesh again
-        if (accum->m_clusterRan) accum->m_clusterValid = accum->m_clusterRan = accum->m_normalsValid = accum->m_componentsValid = false;
+        if (accum->m_clusterRan)
+            accum->m_clusterValid = accum->m_clusterRan = accum->m_smoothValid = accum->m_smoothRan = accum->m_normalsValid = accum->m_componentsValid = false;
         return VH_OK;
     }
     return accumGuarded([&]() -> int {
         VhMeshWeldAccum& a = *accum;
         // normals and components of the mesh before this pass are not of the mesh after it
-        a.m_clusterValid = a.m_clusterRan = a.m_normalsValid = a.m_componentsValid = false;
+        a.m_clusterValid = a.m_clusterRan = a.m_smoothValid = a.m_smoothRan = a.m_normalsValid = a.m_componentsValid = false; // (a smoothing too)
         uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
         VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream)); // waits for the appends; a weld that failed has nothing to cluster
         VH_TRY(a.cluster.run(a.vertices.get(), a.keys.get(), a.faces.get(), have[VH_WELD_ACCUM_VERTICES], have[VH_WELD_ACCUM_FACES], cellsPerCluster, scaleLog2, stream));
@@ -1050,6 +1061,46 @@ int vh_mesh_weld_accum_cluster_download(VhMeshWeldAccum* accum, VhVertex* vertic
 {
     if (!accum || !accum->m_clusterValid || numVertices > accum->m_clusterVertices || numFaces > accum->m_clusterFaces) return VH_ERR_BAD_ARGUMENT;
     return accum->cluster.download(vertices, keys, faces, numVertices, numFaces, stream);
+}
+
+int vh_mesh_weld_accum_smooth(VhMeshWeldAccum* accum, uint32_t iterations, int32_t lambdaQ16, int32_t muQ16, uint32_t keepBoundary, int32_t scaleLog2,
+                              vhStream_t stream)
+{
+    if (!accum || !accum->m_begun || iterations > VH_SMOOTH_MAX_ITERATIONS || keepBoundary > 1u || scaleLog2 < -100 || scaleLog2 > 100) return VH_ERR_BAD_ARGUMENT;
+    if (lambdaQ16 < -VH_SMOOTH_MAX_FACTOR_Q16 || lambdaQ16 > VH_SMOOTH_MAX_FACTOR_Q16 || muQ16 < -VH_SMOOTH_MAX_FACTOR_Q16 || muQ16 > VH_SMOOTH_MAX_FACTOR_Q16)
+        return VH_ERR_BAD_ARGUMENT;
+    if (iterations == 0u) { // forget the pass: the passes of the finish take the vertices as they were again
+        if (accum->m_smoothRan) accum->m_smoothValid = accum->m_smoothRan = accum->m_normalsValid = accum->m_componentsValid = false;
+        return VH_OK;
+    }
+    return accumGuarded([&]() -> int {
+        VhMeshWeldAccum& a = *accum;
+        // normals and components of the mesh before this pass are not of the mesh after it
+        a.m_smoothValid = a.m_smoothRan = a.m_normalsValid = a.m_componentsValid = false;
+        uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
+        VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream)); // waits for the appends; a weld that failed has nothing to smooth
+        const AccumMesh m = accumMesh(a, have, false);
+        VH_TRY(a.smooth.run(m.vertices, m.keys, m.faces, m.numVertices, m.numFaces, iterations, lambdaQ16, muQ16, keepBoundary, scaleLog2, stream));
+        a.m_smoothRan = true;
+        uint32_t counts[VH_SMOOTH_NUM_COUNTS] = {};
+        if (a.smooth.counts(counts, stream) == VH_OK) { // (what it was is vh_mesh_weld_accum_smooth_get_counts' to report)
+            a.m_smoothVertices = m.numVertices;
+            a.m_smoothValid = true;
+        }
+        return VH_OK;
+    });
+}
+
+int vh_mesh_weld_accum_smooth_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream)
+{
+    if (!accum || !out || !accum->m_smoothRan) return VH_ERR_BAD_ARGUMENT;
+    return accum->smooth.counts(out, stream);
+}
+
+int vh_mesh_weld_accum_smooth_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint32_t numVertices, vhStream_t stream)
+{
+    if (!accum || !accum->m_smoothValid || numVertices > accum->m_smoothVertices) return VH_ERR_BAD_ARGUMENT;
+    return accum->smooth.download(vertices, numVertices, stream);
 }
 
 int vh_mesh_weld_accum_components_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream)

@@ -771,6 +771,21 @@ class CUDAMarchingCubesHashSDF:
         check(self.L.vh_marching_cubes_get_indexed_cluster_stats(self.handle, out), "get_indexed_cluster_stats")
         return {k: int(out[i]) for i, k in enumerate(T.CLUSTER_COUNTS)}
 
+    def setIndexedSmoothing(self, iterations=0, lam=0.5, mu=-0.53, keepBoundary=True):
+        """Taubin smoothing for the indexed extractions (off by default: 0; 1 ... 100 iterations turn it on): after the
+        clustering, and before normals and components, the positions are replaced by that many lambda | mu iterations
+        in fixed point; indexed(), mesh() and saveMesh then carry the smoothed positions, and indexed_smooth_stats()
+        says what the pass did.  The factors go to units of 2^-16 by rint; ValueError above 1 in magnitude"""
+        check(self.L.vh_marching_cubes_set_indexed_smoothing(self.handle, int(iterations), T.smooth_factor_q16(lam), T.smooth_factor_q16(mu), 1 if keepBoundary else 0),
+              "setIndexedSmoothing")
+
+    def indexed_smooth_stats(self):
+        """of the last indexed extraction: moved, boundary_vertices, isolated_vertices, status, edges, boundary_edges;
+        all 0 when it ran with smoothing off"""
+        out = (C.c_uint32 * 6)()
+        check(self.L.vh_marching_cubes_get_indexed_smooth_stats(self.handle, out), "get_indexed_smooth_stats")
+        return {k: int(out[i]) for i, k in enumerate(T.SMOOTH_COUNTS)}
+
     def indexed_component_stats(self):
         """of the last indexed extraction: components (with a face), faceless_vertices, kept_components, kept_vertices,
         kept_faces, largest_faces; all 0 when it ran with the filter off"""
@@ -1121,6 +1136,57 @@ def mesh_cluster(vertices, colors, keys, faces, cells_per_cluster, scale_log2, c
     return dict(out, counts={name: int(counts[i]) for i, name in enumerate(T.CLUSTER_COUNTS)}, status=status, code=code)
 
 
+def mesh_smooth(vertices, colors, keys, faces, iterations, lam=0.5, mu=-0.53, keep_boundary=True, scale_log2=21, edge_slots_log2=None, raise_on_status=True,
+                stream=None, guard=0, factors_q16=None):
+    """vh_mesh_smooth on hand-made input: vertices (V,3) f32 with colors (V,3) f32 or None, or T.VERTEX_DTYPE records;
+    keys (V,) u64; faces (F,3) u32 -> the mesh with the smoothed vertices (vertices, colors, keys, faces as mesh_weld();
+    keys and faces are the input's), counts (the six by name), status, code.  lam, mu go to units of 2^-16 by rint, or
+    factors_q16 = (lambdaQ16, muQ16) gives them as they are.  edge_slots_log2: the edge table's size (None: the
+    default, six times the faces); a smaller one fills.  A status raises VhError (VH_ERR_STAGING_OVERFLOW for a full
+    table alone, else VH_ERR_BAD_ARGUMENT), or with raise_on_status=False comes back as `code` beside an empty mesh.
+    guard: that many words of 0xa5a5a5a5 behind the per-vertex degree, flag, position and sum arrays on the device,
+    returned as guards: where a face index >= V would lead."""
+    L = load()
+    v = _vertex_records(vertices, colors)
+    k = np.ascontiguousarray(keys, dtype=np.uint64).ravel()
+    f = np.ascontiguousarray(faces, dtype=np.uint32).reshape(-1, 3)
+    if len(k) != len(v):
+        raise ValueError("one key per vertex")
+    nv, nf = len(v), len(f)
+    lq, mq = (int(factors_q16[0]), int(factors_q16[1])) if factors_q16 is not None else (T.smooth_factor_q16(lam), T.smooth_factor_q16(mu))
+    log2 = C.c_uint32()
+    check(L.vh_mesh_smooth_default_slots_log2(nf, C.byref(log2)), "vh_mesh_smooth_default_slots_log2")
+    el = int(log2.value) if edge_slots_log2 is None else int(edge_slots_log2)
+    es = 1 << el
+    per_vertex = [4, 4, 48, 24]  # degree, flags, positions, sums: bytes per vertex
+    sizes = [8 * es, 4 * es] + [b * max(nv, 1) for b in per_vertex] + [20, 24 * max(nv, 1), 24]
+    bufs = [DeviceBuffer.from_numpy(v, stream), DeviceBuffer.from_numpy(k, stream), DeviceBuffer.from_numpy(f if nf else np.zeros((1, 3), np.uint32), stream)]
+    bufs += [DeviceBuffer(n) for n in sizes]
+    try:
+        d_v, d_k, d_f = bufs[:3]
+        if guard:
+            for i, b in zip(range(5, 9), per_vertex):
+                bufs[i].free()
+                bufs[i] = DeviceBuffer.from_numpy(np.full(b // 4 * nv + guard, 0xa5a5a5a5, dtype=np.uint32), stream)
+        data = T.MeshSmoothData(*[b.ptr for b in bufs[3:]], el, 0)
+        check(L.vh_mesh_smooth(d_v.ptr, d_k.ptr, d_f.ptr, nv, nf, int(iterations), lq, mq, 1 if keep_boundary else 0, int(scale_log2), C.byref(data), stream),
+              "vh_mesh_smooth")
+        counts = bufs[11].download(np.uint32, 6, stream)
+        status = int(counts[3])
+        n_out = nv if status == 0 else 0
+        ov = bufs[10].download(T.VERTEX_DTYPE, n_out, stream)
+        out = dict(vertices=np.ascontiguousarray(ov["p"]), colors=np.ascontiguousarray(ov["c"]), keys=k[:n_out].copy(), faces=f.copy() if status == 0 else f[:0].copy())
+        if guard:
+            out["guards"] = [bufs[i].download(np.uint32, b // 4 * nv + guard, stream)[b // 4 * nv:] for i, b in zip(range(5, 9), per_vertex)]
+    finally:
+        for b in bufs:
+            b.free()
+    code = 0 if status == 0 else 2 if status == T.SMOOTH_TABLE_FULL else 4  # VH_ERR_STAGING_OVERFLOW, VH_ERR_BAD_ARGUMENT
+    if code and raise_on_status:
+        check(code, f"vh_mesh_smooth (status {status})")
+    return dict(out, counts={name: int(counts[i]) for i, name in enumerate(T.SMOOTH_COUNTS)}, status=status, code=code)
+
+
 def mesh_save_ply(filename, vertices, colors=None, normals=None, faces=None, transform=None):
     """vh_mesh_save_ply (host side, no GPU): the mesh container's applyTransform (when a transform is given) and
     saveToPLY on numpy arrays: vertices (V,3), colors (V,4) or None, normals (V,3) or None, faces (F,3) or None"""
@@ -1135,7 +1201,8 @@ def mesh_save_ply(filename, vertices, colors=None, normals=None, faces=None, tra
 
 def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, raise_on_status=True, stream=None, normals_scale_log2=None,
                       min_component_faces=0, largest_component=False, append_after_components=None, cluster_cells=0, cluster_scale_log2=0,
-                      append_after_cluster=None):
+                      append_after_cluster=None, smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, keep_boundary=True, smooth_scale_log2=21,
+                      append_after_smooth=None):
     """vh_mesh_weld_accum_* on hand-made input: parts is a sequence of (soup, records), appended in order to one
     accumulation -> vertices, colors, keys, faces as mesh_weld(), counts (vertices, faces), stats (the six counts by
     name), status and code.  slots_log2 is the table's FIRST size (0: the smallest), reserve_triangles that of the
@@ -1150,7 +1217,12 @@ def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, rai
     normals and the components, which are then of the clustered mesh -> also `clustered` (vertices, colors, keys, faces),
     cluster_counts (the six by name) and cluster_code (what the counts' read returned: 4 or 2 when the pass left a
     status).  append_after_cluster: one more (soup, records) appended after the pass -> stale_cluster_code, what the
-    counts' read then returns (4: refused); not with the normals or the filter."""
+    counts' read then returns (4: refused); not with the normals or the filter.
+    smooth_iterations (1 ... 100), smooth_lambda, smooth_mu, keep_boundary, smooth_scale_log2: run the Taubin smoothing
+    over the finished accumulation, AFTER the clustering and before the normals and the components, which then take the
+    smoothed vertices -> also `smoothed` (the vertices and colors; keys and faces of the clustered mesh if there is one,
+    else the welded one's), smooth_counts (the six by name) and smooth_code.  append_after_smooth: one more (soup,
+    records) appended after the pass -> stale_smooth_code, what the counts' read then returns (4: refused)."""
     L = load()
     h = C.c_void_p()
     check(L.vh_mesh_weld_accum_create(slots_log2, reserve_triangles, int(fixed), C.byref(h)), "vh_mesh_weld_accum_create")
@@ -1184,6 +1256,24 @@ def mesh_weld_appends(parts, slots_log2=0, fixed=False, reserve_triangles=0, rai
                 buffers += [d_tris, d_srcs]
                 check(L.vh_mesh_weld_accum_append(h, d_tris.ptr, d_srcs.ptr, n, stream), "vh_mesh_weld_accum_append")
                 extra["stale_cluster_code"] = int(L.vh_mesh_weld_accum_cluster_get_counts(h, kc, stream))
+        if smooth_iterations and counts[2] == 0:
+            check(L.vh_mesh_weld_accum_smooth(h, int(smooth_iterations), T.smooth_factor_q16(smooth_lambda), T.smooth_factor_q16(smooth_mu), 1 if keep_boundary else 0,
+                                              int(smooth_scale_log2), stream), "vh_mesh_weld_accum_smooth")
+            sc = (C.c_uint32 * 6)()
+            scode = L.vh_mesh_weld_accum_smooth_get_counts(h, sc, stream)
+            if scode < 0 or (scode != 0 and raise_on_status):
+                check(scode, f"vh_mesh_weld_accum_smooth (status {sc[3]})")
+            extra.update(smooth_counts={name: int(sc[i]) for i, name in enumerate(T.SMOOTH_COUNTS)}, smooth_code=int(scode))
+            if scode == 0:
+                base = extra.get("clustered", out)
+                sv = np.zeros(mesh_vertices, dtype=T.VERTEX_DTYPE)
+                check(L.vh_mesh_weld_accum_smooth_download(h, sv.ctypes.data, mesh_vertices, stream), "vh_mesh_weld_accum_smooth_download")
+                extra["smoothed"] = dict(vertices=np.ascontiguousarray(sv["p"]), colors=np.ascontiguousarray(sv["c"]), keys=base["keys"], faces=base["faces"])
+            if append_after_smooth is not None:
+                d_tris, d_srcs, n = _upload_soup(*append_after_smooth, stream)
+                buffers += [d_tris, d_srcs]
+                check(L.vh_mesh_weld_accum_append(h, d_tris.ptr, d_srcs.ptr, n, stream), "vh_mesh_weld_accum_append")
+                extra["stale_smooth_code"] = int(L.vh_mesh_weld_accum_smooth_get_counts(h, sc, stream))
         if normals_scale_log2 is not None and counts[2] == 0:
             check(L.vh_mesh_weld_accum_normals(h, int(normals_scale_log2), stream), "vh_mesh_weld_accum_normals")
             nrm = np.zeros((mesh_vertices, 3), dtype=np.float32)

@@ -260,6 +260,13 @@ PROTOTYPES = {
     "vh_mesh_weld_accum_cluster_download": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP]),
     "vh_marching_cubes_set_indexed_clustering": (C.c_int, [_VP, C.c_uint32]),
     "vh_marching_cubes_get_indexed_cluster_stats": (C.c_int, [_VP, P(C.c_uint32)]),
+    "vh_mesh_smooth_default_slots_log2": (C.c_int, [C.c_uint32, P(C.c_uint32)]),
+    "vh_mesh_smooth": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, _VP, _VP]),
+    "vh_mesh_weld_accum_smooth": (C.c_int, [_VP, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, _VP]),
+    "vh_mesh_weld_accum_smooth_get_counts": (C.c_int, [_VP, P(C.c_uint32), _VP]),
+    "vh_mesh_weld_accum_smooth_download": (C.c_int, [_VP, _VP, C.c_uint32, _VP]),
+    "vh_marching_cubes_set_indexed_smoothing": (C.c_int, [_VP, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32]),
+    "vh_marching_cubes_get_indexed_smooth_stats": (C.c_int, [_VP, P(C.c_uint32)]),
     "vh_marching_cubes_set_indexed_normals": (C.c_int, [_VP, C.c_int]),
     "vh_marching_cubes_download_indexed_normals": (C.c_int, [_VP, _VP]),
     "vh_marching_cubes_get_mesh_normals_size": (C.c_int, [_VP, P(C.c_uint64)]),

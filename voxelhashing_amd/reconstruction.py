@@ -573,7 +573,8 @@ class Reconstruction:
                 h.m_depthShift, bytes(h.m_sensorName).decode(), h.m_colorCompressionType, h.m_depthCompressionType,
                 np.array(h.m_depthExtrinsic[:]), np.array(h.m_colorExtrinsic[:]))
 
-    def extractIsoSurface(self, filename=None, indexed=False, normals=False, min_component_faces=0, largest_component=False, cluster_cells=0):
+    def extractIsoSurface(self, filename=None, indexed=False, normals=False, min_component_faces=0, largest_component=False, cluster_cells=0,
+                          smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, keep_boundary=True):
         """StopScanningAndExtractIsoSurfaceMC: marching cubes over the whole scene (through the chunk grid when
         streaming is on) -> (vertices, colours, faces); written as a PLY when a file name is given.  indexed (not in the
         reference): weld the triangles on the device instead of merging them on the host.  With streaming on that is
@@ -585,7 +586,12 @@ class Reconstruction:
         says what the unfiltered one held.  cluster_cells (with indexed; 1 ... 64): the welded mesh is decimated on the
         device by vertex clustering -- the vertices in one cube of that many lattice points a side become one -- before
         the normals and the filter; what is returned and written is the clustered mesh, and its "clustering" entry
-        (indexed_cluster_stats) says what the pass did."""
+        (indexed_cluster_stats) says what the pass did.  smooth_iterations (with indexed; 1 ... 100), smooth_lambda,
+        smooth_mu, keep_boundary: that many iterations of Taubin smoothing in fixed point on the device, after the
+        clustering and before the normals and the filter; what is returned and written carries the smoothed positions,
+        and its "smoothing" entry (indexed_smooth_stats) says what the pass did."""
+        if smooth_iterations and not indexed:
+            raise ValueError("smoothing needs the indexed extraction: a triangle soup has no neighbours")
         if cluster_cells and not indexed:
             raise ValueError("clustering needs the indexed extraction: it works on the welded mesh's vertex keys")
         if (min_component_faces or largest_component) and not indexed:
@@ -604,6 +610,7 @@ class Reconstruction:
         mc.setIndexedNormals(bool(normals))
         mc.setIndexedComponentFilter(int(min_component_faces), bool(largest_component))
         mc.setIndexedClustering(int(cluster_cells))
+        mc.setIndexedSmoothing(int(smooth_iterations), smooth_lambda, smooth_mu, bool(keep_boundary))
         if self.chunk_grid is not None:
             pos = (self.scene.getLastRigidTransform().reshape(4, 4) @ np.array(list(self.gas.s_streamingPos) + [1.0], dtype=np.float32))[:3]
             mc.extractIsoSurfaceChunkGrid(self.chunk_grid, pos, self.gas.s_streamingRadius)
@@ -616,11 +623,14 @@ class Reconstruction:
             mesh["components"] = mc.indexed_component_stats()  # (saveMesh clears them with the buffer)
         if cluster_cells:
             mesh["clustering"] = mc.indexed_cluster_stats()
+        if smooth_iterations:
+            mesh["smoothing"] = mc.indexed_smooth_stats()
         if filename:
             mc.saveMesh(filename, None, True)  # merges close vertices, writes the PLY and clears the buffer (.cpp:126-144)
         return mesh
 
-    def extractIsoSurfaceIndexed(self, filename=None, normals=False, min_component_faces=0, largest_component=False, cluster_cells=0):
+    def extractIsoSurfaceIndexed(self, filename=None, normals=False, min_component_faces=0, largest_component=False, cluster_cells=0,
+                                 smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, keep_boundary=True):
         """The indexed extraction with and without streaming (not in the reference): marching cubes with the triangles
         welded on the device -> (vertices, colours, faces); written as a PLY when a file name is given.  Without
         streaming this is extractIsoSurface(indexed=True); with streaming it walks the chunk grid as extractIsoSurface()
@@ -629,10 +639,12 @@ class Reconstruction:
         normals: vertex normals computed on the device over the finished mesh, returned as "normals" and written into
         the PLY.  min_component_faces, largest_component: the component filter, over the finished mesh (a component
         spans chunks), as extractIsoSurface describes it.  cluster_cells: the vertex clustering, over the finished mesh
-        too, before the other two."""
+        too, before the other two.  smooth_iterations, smooth_lambda, smooth_mu, keep_boundary: the Taubin smoothing,
+        over the finished mesh after the clustering and before the other two."""
         if self.chunk_grid is None:
             return self.extractIsoSurface(filename, indexed=True, normals=normals, min_component_faces=min_component_faces, largest_component=largest_component,
-                                          cluster_cells=cluster_cells)
+                                          cluster_cells=cluster_cells, smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
+                                          keep_boundary=keep_boundary)
         if self.marching_cubes is None:
             self.marching_cubes = E.CUDAMarchingCubesHashSDF(self.mp)
             self.marching_cubes.setOfflineProcessing(bool(self.gas.s_offlineProcessing))
@@ -640,6 +652,7 @@ class Reconstruction:
         mc.setIndexedNormals(bool(normals))
         mc.setIndexedComponentFilter(int(min_component_faces), bool(largest_component))
         mc.setIndexedClustering(int(cluster_cells))
+        mc.setIndexedSmoothing(int(smooth_iterations), smooth_lambda, smooth_mu, bool(keep_boundary))
         pos = (self.scene.getLastRigidTransform().reshape(4, 4) @ np.array(list(self.gas.s_streamingPos) + [1.0], dtype=np.float32))[:3]
         mc.extractIsoSurfaceIndexedChunkGrid(self.chunk_grid, pos, self.gas.s_streamingRadius)
         mesh = mc.mesh()
@@ -647,6 +660,8 @@ class Reconstruction:
             mesh["components"] = mc.indexed_component_stats()  # (saveMesh clears them with the buffer)
         if cluster_cells:
             mesh["clustering"] = mc.indexed_cluster_stats()
+        if smooth_iterations:
+            mesh["smoothing"] = mc.indexed_smooth_stats()
         if filename:
             mc.saveMesh(filename, None, True)  # the mesh is welded: written as it is, and the buffer cleared
         return mesh

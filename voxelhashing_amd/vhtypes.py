@@ -159,6 +159,25 @@ class MeshClusterData(C.Structure):  # VhMeshClusterData
                [("m_clusterSlotsLog2", C.c_uint32), ("m_faceSlotsLog2", C.c_uint32)]
 
 
+# VH_SMOOTH_*: bits of the Taubin smoothing's status word, its limits and defaults, what the pass counts
+SMOOTH_TABLE_FULL, SMOOTH_RANGE, SMOOTH_BAD_INDEX, SMOOTH_DEGREE = 1, 2, 4, 8
+SMOOTH_MAX_DEGREE, SMOOTH_MAX_ITERATIONS, SMOOTH_MAX_FACTOR_Q16 = 1 << 16, 100, 1 << 16
+SMOOTH_DEFAULT_LAMBDA_Q16, SMOOTH_DEFAULT_MU_Q16 = 32768, -34734
+SMOOTH_COUNTS = ("moved", "boundary_vertices", "isolated_vertices", "status", "edges", "boundary_edges")
+
+
+class MeshSmoothData(C.Structure):  # VhMeshSmoothData
+    _fields_ = [(n, C.c_void_p) for n in ("d_edgeKeys", "d_edgeUses", "d_degree", "d_flags", "d_positions", "d_sums", "d_work", "d_vertices", "d_counts")] + \
+               [("m_edgeSlotsLog2", C.c_uint32), ("m_pad", C.c_uint32)]
+
+
+def smooth_factor_q16(f):
+    """a smoothing factor in units of 2^-16, by rint; ValueError above 1 in magnitude"""
+    if not abs(float(f)) <= 1.0:
+        raise ValueError("a smoothing factor lies in [-1, 1]")
+    return int(np.rint(np.float64(np.float32(f)) * 65536.0))
+
+
 WELD_ACCUM_COUNTS = ("vertices", "faces", "status", "cells", "dropped", "rehashes")  # VH_WELD_ACCUM_*: what the accumulating weld reports
 WELD_ACCUM_MAX_APPENDS = 1 << 28
 
