@@ -74,21 +74,31 @@ VHD uint32_t hash_pos(uint32_t numBuckets, I3 p)
     return r % numBuckets;
 }
 
+// The reference's rounding of a quotient, (int)(p + sign(p) * 0.5f) with sign(p) in {-1, 0, 1} (:266-270, and
+// worldToChunks), as p + copysignf(0.5f, p): a v_bfi_b32 and an add where the sign takes two compares, a select, a
+// subtract, a conversion and a multiply.  The two differ only where sign(p) is 0: for p = +-0 the sum is +-0.5 here and
+// 0 there, and both truncate to 0; for a NaN both sums are NaN, which converts to 0.  Every other p, the infinities
+// included, gets the same sum.  k_check_fast_math (vh_util.hip) holds the two against each other on the device,
+// tests/test_exact_voxel_coords.py in numpy.
+VHD int round_half_away(float p) { return f2i(p + copysignf(0.5f, p)); }
+
 // worldToVirtualVoxelPos :266-270, one component
 VHD int world_to_vvp1(float pos, float voxelSize)
 {
-    float p = pos / voxelSize;
-    return f2i(p + (float)signi(p) * 0.5f);
+    return round_half_away(pos / voxelSize);
 }
 VHD I3 world_to_vvp(float voxelSize, F3 pos)
 {
     return mki3(world_to_vvp1(pos.x, voxelSize), world_to_vvp1(pos.y, voxelSize), world_to_vvp1(pos.z, voxelSize));
 }
-// virtualVoxelPosToSDFBlock :273-282 (floor division by 8)
+// virtualVoxelPosToSDFBlock :273-282: (v < 0 ? v - 7 : v) / 8 with C's division, which is floor(v / 8), which is the
+// arithmetic shift -- for every v >= INT_MIN + 7.  Below that the reference's v - 7 overflows (undefined in C; the
+// wrapped value is a positive block no voxel of the scene is near), and such a v is only ever the saturated conversion
+// of a position 2^31 voxels away.  (One instruction for seven; k_check_fast_math and tests/test_exact_voxel_coords.py.)
+static_assert(VH_SDF_BLOCK_SIZE == 8, "vvp_to_block1");
 VHD int vvp_to_block1(int v)
 {
-    if (v < 0) v -= VH_SDF_BLOCK_SIZE - 1;
-    return v / VH_SDF_BLOCK_SIZE;
+    return v >> 3;
 }
 VHD I3 vvp_to_block(I3 v) { return mki3(vvp_to_block1(v.x), vvp_to_block1(v.y), vvp_to_block1(v.z)); }
 // SDFBlockToVirtualVoxelPos :286 / virtualVoxelPosToWorld :291 / SDFBlockToWorld :296
@@ -133,8 +143,7 @@ VHD float div_exact(float a, float b, float rb)
 }
 VHD int world_to_vvp1_rb(float pos, float voxelSize, float rVoxelSize)
 {
-    float p = div_exact(pos, voxelSize, rVoxelSize);
-    return f2i(p + (float)signi(p) * 0.5f);
+    return round_half_away(div_exact(pos, voxelSize, rVoxelSize));
 }
 
 // n % d for an invariant d through a host-computed multiply-shift
@@ -219,7 +228,7 @@ VHD uint32_t chunk_bit_of_block(const VhHashParams& hp, I3 blk)
 {
     const F3 pw = block_to_world(hp.m_virtualVoxelSize, blk);
     const F3 p = mk3(pw.x / hp.m_streamingVoxelExtents[0], pw.y / hp.m_streamingVoxelExtents[1], pw.z / hp.m_streamingVoxelExtents[2]);
-    const I3 c = mki3(f2i(p.x + (float)signi(p.x) * 0.5f), f2i(p.y + (float)signi(p.y) * 0.5f), f2i(p.z + (float)signi(p.z) * 0.5f));
+    const I3 c = mki3(round_half_away(p.x), round_half_away(p.y), round_half_away(p.z));
     const int qx = c.x - hp.m_streamingMinGridPos[0], qy = c.y - hp.m_streamingMinGridPos[1], qz = c.z - hp.m_streamingMinGridPos[2];
     if (qx < 0 || qy < 0 || qz < 0 || qx >= hp.m_streamingGridDimensions[0] || qy >= hp.m_streamingGridDimensions[1] || qz >= hp.m_streamingGridDimensions[2])
         return 0xffffffffu;

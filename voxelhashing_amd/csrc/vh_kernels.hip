@@ -147,7 +147,9 @@ constexpr uint32_t kTileSlotWords = 12;
 // pointers nor the bucket modulus nor the second block of a tap pair in registers.  TileLookup is the general one, for
 // the tile whose list overflowed.  render_tile picks one per wave.
 // OFFSETS32: voxel loads take a 32-bit byte offset on the pool's base (load_voxel).
-template <uint32_t kTileTabSlots, bool OFFSETS32> // 2 x the list capacity (load factor <= 1/2), a power of two
+// ONE_READ: a probe's four words are asked for together (slot_find).  For the kernels without gradients, where it was
+// measured; with it k_render_large<true, *> takes 177 registers for 161 and loses a wave per SIMD.
+template <uint32_t kTileTabSlots, bool OFFSETS32, bool ONE_READ> // 2 x the list capacity (load factor <= 1/2), a power of two
 struct TileLookup {
     const int* tab;
     bool complete;
@@ -157,17 +159,23 @@ struct TileLookup {
     static constexpr bool kGeneral = true;
     VHD static uint32_t slot_of(int bx, int by, int bz)
     {
-        // Multiply-shift hash, three full-rate 24-bit multiplies.  The blocks of a tile are a dense slab along its beam;
+        // Multiply-shift hash.  The blocks of a tile are a dense slab along its beam;
         // a linear form like x + 5y + 24z packs such a slab into ONE contiguous run of slots, and a probe for a block
         // that is not in the table (every empty-space step of a ray) then walks the whole run: 100 probes instead
         // of one on the long lists of fine voxels.
+        // (The compiler makes three v_mul_lo_u32 of it, a quarter-rate instruction: only bits below 24 of the sum are used,
+        // so it drops the 24-bit form and then cannot show that the operands have 24 bits.  v_mul_u32_u24 / v_mad_u32_u24
+        // written as instructions are fewer issue cycles and were slower on the device: profiles/README.md.)
         return ((__umul24((uint32_t)bx, 0x9E3779u) + __umul24((uint32_t)by, 0x7F4A7Du) + __umul24((uint32_t)bz, 0x85EBCBu)) >> 10) & (kTileTabSlots - 1u);
     }
     VHD static int slot_find(const int* tab, int bx, int by, int bz)
     {
         uint32_t h = slot_of(bx, by, bz);
         for (;;) {
-            const int4 e = *reinterpret_cast<const int4*>(&tab[h * kTileSlotWords]); // one 16-byte LDS read
+            int4 e = *reinterpret_cast<const int4*>(&tab[h * kTileSlotWords]);
+            // one 16-byte LDS read, said so: left alone the compiler asks for e.w, waits, tests it and only then asks for
+            // the other three words -- two trips in a row for every probe that finds its block
+            if (ONE_READ) asm volatile("" : "+v"(e.x), "+v"(e.y), "+v"(e.z), "+v"(e.w));
             if (e.w == VH_FREE_ENTRY) return -1;
             if ((int)(e.x == bx) & (int)(e.y == by) & (int)(e.z == bz)) return (int)h;
             h = (h + 1u) & (kTileTabSlots - 1u);
@@ -215,7 +223,7 @@ struct TileLookup {
     }
 };
 
-template <uint32_t kTileTabSlots, bool OFFSETS32>
+template <uint32_t kTileTabSlots, bool OFFSETS32, bool ONE_READ>
 struct TileLookupComplete {
     const int* tab;
     static constexpr bool kOffsets32 = OFFSETS32;
@@ -223,7 +231,7 @@ struct TileLookupComplete {
     // handle: the slot of the block (>= 0), or kPtrUnknown
     VHD bool first_tap(int bx, int by, int bz, int& handle) const
     {
-        handle = TileLookup<kTileTabSlots, OFFSETS32>::slot_find(tab, bx, by, bz);
+        handle = TileLookup<kTileTabSlots, OFFSETS32, ONE_READ>::slot_find(tab, bx, by, bz);
         if (handle >= 0) return true;
         handle = kPtrUnknown;
         return false;
@@ -231,7 +239,7 @@ struct TileLookupComplete {
     // (only the first tap's block and `straddle` are read: the second block's coordinates die where straddle is formed)
     VHD bool resolve(int handle, int bxa, int bya, int bza, int, int, int, uint32_t straddle, int (&p)[8]) const
     {
-        const int sl = handle >= 0 ? handle : TileLookup<kTileTabSlots, OFFSETS32>::slot_find(tab, bxa, bya, bza);
+        const int sl = handle >= 0 ? handle : TileLookup<kTileTabSlots, OFFSETS32, ONE_READ>::slot_find(tab, bxa, bya, bza);
         if (sl < 0) return false; // the first tap reads the zero voxel (weight 0)
         // the tap pair of an axis lies in one block or in two adjacent ones: combo j reads neighbour (j & straddle)
         const int* e = &tab[(uint32_t)sl * kTileSlotWords + 3u];
@@ -455,16 +463,13 @@ VHD void tap_coords(const RayQ& rq, float t, Taps& tp)
     if (dev < rq.certLim) {
         tp.x0 = (int)gx; tp.y0 = (int)gy; tp.z0 = (int)gz;
         tp.x1 = tp.x0 + 1; tp.y1 = tp.y0 + 1; tp.z1 = tp.z0 + 1;
-        // |coordinates| < 2^16 here: the arithmetic shift is the reference's floor division by 8
-        tp.bxa = tp.x0 >> 3; tp.bya = tp.y0 >> 3; tp.bza = tp.z0 >> 3;
-        tp.bxb = tp.x1 >> 3; tp.byb = tp.y1 >> 3; tp.bzb = tp.z1 >> 3;
     } else {
         const F3 pd = mk3((rq.cam.x + t * rq.dir.x) - rq.halfVoxel, (rq.cam.y + t * rq.dir.y) - rq.halfVoxel, (rq.cam.z + t * rq.dir.z) - rq.halfVoxel);
         tp.x0 = world_to_vvp1_rb(pd.x, rq.vs, rq.rvs); tp.y0 = world_to_vvp1_rb(pd.y, rq.vs, rq.rvs); tp.z0 = world_to_vvp1_rb(pd.z, rq.vs, rq.rvs);
         tp.x1 = world_to_vvp1_rb(pd.x + rq.vs, rq.vs, rq.rvs); tp.y1 = world_to_vvp1_rb(pd.y + rq.vs, rq.vs, rq.rvs); tp.z1 = world_to_vvp1_rb(pd.z + rq.vs, rq.vs, rq.rvs);
-        tp.bxa = vvp_to_block1(tp.x0); tp.bya = vvp_to_block1(tp.y0); tp.bza = vvp_to_block1(tp.z0);
-        tp.bxb = vvp_to_block1(tp.x1); tp.byb = vvp_to_block1(tp.y1); tp.bzb = vvp_to_block1(tp.z1);
     }
+    tp.bxa = vvp_to_block1(tp.x0); tp.bya = vvp_to_block1(tp.y0); tp.bza = vvp_to_block1(tp.z0);
+    tp.bxb = vvp_to_block1(tp.x1); tp.byb = vvp_to_block1(tp.y1); tp.bzb = vvp_to_block1(tp.z1);
 }
 
 // The constants of the ray cam + t dir, for samples at parameters |t| <= tFar (the caller's bound: march and bisection
@@ -1023,8 +1028,8 @@ VHD void render_tile(const VhHashData& hd, const VhHashParams& hp, const VhRayCa
     // three workgroups per compute unit; for fine voxels, where a few tiles see more than 64 blocks and would
     // otherwise probe the hash table for every block the table could not hold)
     constexpr uint32_t kTileTabSlots = 2u * CAP;
-    typedef TileLookup<kTileTabSlots, OFFSETS32> Lookup;
-    typedef TileLookupComplete<kTileTabSlots, OFFSETS32> LookupComplete;
+    typedef TileLookup<kTileTabSlots, OFFSETS32, !GRADIENTS> Lookup;
+    typedef TileLookupComplete<kTileTabSlots, OFFSETS32, !GRADIENTS> LookupComplete;
     static_assert(kTileSlotWords == 12u, "tileTab row size");
     const uint32_t lane = lane_id();
     const uint32_t W = rp.m_width, H = rp.m_height;

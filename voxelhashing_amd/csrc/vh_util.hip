@@ -2,6 +2,7 @@
 // the synthetic scene and the check of that header's exact arithmetic, with their launchers (include/vh_api.h).
 // MUST be compiled with -ffp-contract=off (see vh_device.hpp).
 #include <hip/hip_runtime.h>
+#include <limits.h>
 
 #include "../../include/vh_api.h"
 #include "vh_device.hpp"
@@ -58,7 +59,17 @@ __global__ __launch_bounds__(256) void k_synth(SynthArgs a, VhDepthCameraParams 
     }
 }
 
-// checks div_exact against `/` and umod_fast against `%` on pseudo-random operands
+// the reference's own expressions (worldToVirtualVoxelPos, virtualVoxelPosToSDFBlock, DSC/VoxelUtilHashSDF.h:266-282) as
+// they were written before round_half_away and the shift of vvp_to_block1: what k_check_fast_math holds those against
+__device__ int round_by_sign(float p) { return f2i(p + (float)signi(p) * 0.5f); }
+__device__ int block_by_division(int v)
+{
+    if (v < 0) v -= VH_SDF_BLOCK_SIZE - 1;
+    return v / VH_SDF_BLOCK_SIZE;
+}
+
+// checks div_exact against `/`, round_half_away and vvp_to_block1 against the reference's expressions (word 0) and umod_fast
+// against `%` (word 1) on pseudo-random operands
 __global__ __launch_bounds__(256) void k_check_fast_math(float b, HashMod hm, uint32_t n, uint32_t seed, uint32_t* mismatches)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -79,11 +90,22 @@ __global__ __launch_bounds__(256) void k_check_fast_math(float b, HashMod hm, ui
     const float rb = 1.0f / b;
     const float q0 = a / b, q1 = div_exact(a, b, rb);
     if (__float_as_uint(q0) != __float_as_uint(q1) && !(q0 == 0.0f && q1 == 0.0f)) atomicAdd(&mismatches[0], 1u);
+    // the quotient rounded to a voxel, the voxel's block, and the block of any 32-bit pattern (but the seven lowest,
+    // where the reference's v - 7 overflows: of the voxels that is INT_MIN, what a quotient below -2^31 saturates to)
+    const int v0 = round_by_sign(q0), v1 = round_half_away(q0);
+    if (v0 != v1) atomicAdd(&mismatches[0], 1u);
+    if (v0 > INT_MIN + 6 && block_by_division(v0) != vvp_to_block1(v0)) atomicAdd(&mismatches[0], 1u);
+    if ((int)u > INT_MIN + 6 && block_by_division((int)u) != vvp_to_block1((int)u)) atomicAdd(&mismatches[0], 1u);
     if ((s % hm.d) != umod_fast(s, hm)) atomicAdd(&mismatches[1], 1u);
     if ((u % hm.d) != umod_fast(u, hm)) atomicAdd(&mismatches[1], 1u);
     if (i < 256u) { // every colour byte over 255 (store_ray)
         const float c = (float)i;
         if (__float_as_uint(c / 255.f) != __float_as_uint(div_exact(c, 255.0f, 1.0f / 255.0f))) atomicAdd(&mismatches[0], 1u);
+    }
+    if (i < 16u) { // the quotients where the sign is 0, the halves, and what the conversion saturates or sends to 0
+        const uint32_t special[8] = { 0x00000000u, 0x3effffffu, 0x3f000000u, 0x3f000001u, 0x00000001u, 0x4f000000u, 0x7f800000u, 0x7fc00000u };
+        const float p = __uint_as_float(special[i & 7u] | ((i & 8u) << 28));
+        if (round_by_sign(p) != round_half_away(p)) atomicAdd(&mismatches[0], 1u);
     }
     if (i < 64u) { // extremes of the unsigned range
         const uint32_t e = 0xffffffffu - i;
