@@ -14,6 +14,10 @@ are the code object's own metadata (the amdhsa.kernels note); the instruction li
 are given: kernels may have moved between files) and says per kernel whether its instruction sequence -- comments,
 directives, labels and the numbers of local labels aside -- is identical, differs, or exists on one side only.
 
+Every file is compiled with the flags the library's build gives it (`build.flags(source)`: the common flags and the extra
+ones of `build.SOURCE_FLAGS` by file name), the other checkout's files with this checkout's flags: --against compares
+sources, like with like.  (What the other checkout's own build makes of them, its own copy of this tool says.)
+
 `resources(asm_text)`, `instruction_sequences(asm_text)` and `library_resources(lib)` are importable: the last reads the
 same metadata out of a built library (tests/test_kernel_resources.py).
 """
@@ -138,7 +142,7 @@ def device_assembly(source, extra=()):
     from voxelhashing_amd import build as vh_build
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "kernels.s")
-        cmd = [vh_build.hipcc()] + vh_build.flags() + list(extra) + ["--cuda-device-only", "-S", source, "-o", out]
+        cmd = [vh_build.hipcc()] + vh_build.flags(source) + list(extra) + ["--cuda-device-only", "-S", source, "-o", out]
         subprocess.check_call(cmd)
         with open(out) as f:
             return f.read()

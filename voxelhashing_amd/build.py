@@ -23,6 +23,11 @@ HEADERS = ["vh_device.hpp", "vh_frame_alloc.hpp", "vh_frame_compactify.hpp", "vh
            os.path.join(ROOT, "include", "vh.hpp"), os.path.join(ROOT, "include", "vh_owners.hpp"),
            os.path.join(ROOT, "include", "vh_mc_tables.h")]
 ARCH = "gfx950"
+# Extra flags by source, after the common ones (build(), build_variant() and tools/kernel_resources.py all go through
+# flags(source)).  vh_kernels.hip: the SLP vectorizer stays out of the frame-loop kernels.  Their packed fp32 is the
+# f32x2 code written in the source; what the vectorizer packed besides cost the ray march moves and wait states to form
+# the pairs, and its choices changed with unrelated statements nearby (profiles/README.md).
+SOURCE_FLAGS = {"vh_kernels.hip": ["-fno-slp-vectorize"]}
 
 
 def hipcc():
@@ -32,10 +37,11 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
-def flags():
+def flags(source=None):
+    """the compiler's flags for one source (its file name or path), or the common ones alone"""
     return ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
             "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function",
-            "-I", os.path.join(ROOT, "include")]
+            "-I", os.path.join(ROOT, "include")] + (SOURCE_FLAGS.get(os.path.basename(source), []) if source else [])
 
 
 def up_to_date():
@@ -67,7 +73,7 @@ def build(force=False, verbose=False, extra=(), out=None):
         # an object is reused when it is newer than its source and every header (and no extra flags are given)
         if not force and not extra and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_t):
             continue
-        jobs.append([cc] + flags() + list(extra) + ["-c", src, "-o", obj])
+        jobs.append([cc] + flags(s) + list(extra) + ["-c", src, "-o", obj])
     procs = []
     for cmd in jobs:  # the translation units compile side by side (the kernels' one takes the longest)
         if verbose:
@@ -91,7 +97,7 @@ def build_variant(out, extra, verbose=False):
     for s in SOURCES:
         obj = os.path.join(objdir, os.path.splitext(s)[0] + ".o")
         objs.append(obj)
-        cmd = [cc] + flags() + extra + ["-c", os.path.join(CSRC, s), "-o", obj]
+        cmd = [cc] + flags(s) + extra + ["-c", os.path.join(CSRC, s), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((cmd, subprocess.Popen(cmd)))

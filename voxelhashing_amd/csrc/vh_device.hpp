@@ -141,6 +141,23 @@ VHD float div_exact(float a, float b, float rb)
     q = __fmaf_rn(e, rb, q);
     return q;
 }
+// ---- two fp32 values as a two-vector: packed fp32 instructions (v_pk_mul/add/fma_f32: two IEEE operations per issue
+// slot; each component is the scalar instruction's result).  The frame-loop unit is compiled without the SLP vectorizer
+// (build.py): what is packed there is what is written with these.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+VHD f32x2 both(float v) { return (f32x2){ v, v }; }
+VHD f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+// div_exact for two dividends
+VHD f32x2 div_exact2(f32x2 a, float b, float rb)
+{
+    const f32x2 b2 = both(b), rb2 = both(rb);
+    f32x2 q = a * rb2;
+    f32x2 e = fma2(-b2, q, a);
+    q = fma2(e, rb2, q);
+    e = fma2(-b2, q, a);
+    q = fma2(e, rb2, q);
+    return q;
+}
 VHD int world_to_vvp1_rb(float pos, float voxelSize, float rVoxelSize)
 {
     return round_half_away(div_exact(pos, voxelSize, rVoxelSize));

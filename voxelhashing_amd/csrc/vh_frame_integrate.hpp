@@ -217,11 +217,7 @@ VHD void integrate_pair(const VhHashParams& hp, const VhDepthCameraParams& cp, c
     raw = make_uint4(a.x, a.y, c.x, c.y);
 }
 
-// ---- the voxel pair of a lane as a two-vector: packed fp32 instructions (v_pk_mul/add/fma_f32: two IEEE operations per
-// issue slot; each component is the scalar instruction's result)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-VHD f32x2 both(float v) { return (f32x2){ v, v }; }
-VHD f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+// ---- the voxel pair of a lane as a two-vector (f32x2, both, fma2: vh_device.hpp)
 // The reciprocal the compiler's own expansion of an fp32 division forms when v_div_scale_f32 leaves its operands alone:
 // v_rcp_f32 and one Newton step.
 VHD f32x2 rcp_refined2(f32x2 d)

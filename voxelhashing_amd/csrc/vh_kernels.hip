@@ -284,6 +284,45 @@ struct Taps {
     int bxa, bya, bza, bxb, byb, bzb; // their SDF blocks (virtualVoxelPosToSDFBlock)
 };
 
+// The eight tap weights of trilinearInterpolationSimpleFastFast at `pos`, in the reference's tap order
+// (000,100,010,001,110,011,101,111) and with its arithmetic: (wx' * wy') * wz' per tap, w = frac(pos / voxel), 1 - w.
+// PACKED: x and y as f32x2 pairs, for the kernels that address voxels by 32-bit offsets (LK::kOffsets32).  With 64-bit
+// addresses the packed form is ten instructions shorter per sample as well, adds no move -- and k_render<false, false> ran
+// 2 % slower with it (the cfg3 frame 0.9 % below the scalar form's, profiles/README.md), so those kernels keep the scalar one.
+template <bool PACKED>
+VHD void tap_weights(F3 pos, float vs, float rvs, float (&s)[8])
+{
+    if constexpr (!PACKED) {
+        const float fx = div_exact(pos.x, vs, rvs), fy = div_exact(pos.y, vs, rvs), fz = div_exact(pos.z, vs, rvs);
+        const float wx = fx - floorf(fx), wy = fy - floorf(fy), wz = fz - floorf(fz);
+        const float ux = 1.0f - wx, uy = 1.0f - wy, uz = 1.0f - wz;
+        s[0] = (ux * uy) * uz; s[1] = (wx * uy) * uz; s[2] = (ux * wy) * uz; s[3] = (ux * uy) * wz;
+        s[4] = (wx * wy) * uz; s[5] = (ux * wy) * wz; s[6] = (wx * uy) * wz; s[7] = (wx * wy) * wz;
+        return;
+    }
+    // Packed where two operations find their operands side by side without a move (the unit is compiled without the SLP
+    // vectorizer; what it packed here cost a v_mov or v_pk_mov per pair and a wait state before the next packed
+    // instruction): the x and y divisions as one chain, then {ux, wx} -- which the two scalar subtractions write next to
+    // each other -- times uy and times wy, and those two pairs times uz and times wz.  Each component is the scalar
+    // instruction's result.  The eight products with the distances and their sum stay scalar in trilinear / taps_finish:
+    // a voxel load returns {sdf, colour and weight}, so no two distances are neighbours, and the sum's order is the reference's.
+    const f32x2 fxy = div_exact2((f32x2){ pos.x, pos.y }, vs, rvs);
+    const float fz = div_exact(pos.z, vs, rvs);
+    const float wx = fxy.x - floorf(fxy.x), wy = fxy.y - floorf(fxy.y), wz = fz - floorf(fz);
+    const float uy = 1.0f - wy, uz = 1.0f - wz;
+    const f32x2 xs = (f32x2){ 1.0f - wx, wx };
+    const f32x2 xu = xs * both(uy), xw = xs * both(wy); // {ux uy, wx uy}, {ux wy, wx wy}
+    const f32x2 a = xu * both(uz), b = xw * both(uz), c = xu * both(wz), d = xw * both(wz);
+    s[0] = a.x; s[1] = a.y; s[2] = b.x; s[3] = c.x; s[4] = b.y; s[5] = d.x; s[6] = c.y; s[7] = d.y;
+}
+
+// The point cam + t dir of a ray, with the reference's arithmetic (a product and a sum per axis).  (x and y as one packed
+// product and one packed sum were measured: 9 % off the cfg2 frame on top of the packed weights -- profiles/README.md.)
+VHD F3 ray_point(F3 cam, F3 dir, float t)
+{
+    return mk3(cam.x + t * dir.x, cam.y + t * dir.y, cam.z + t * dir.z);
+}
+
 // trilinearInterpolationSimpleFastFast, DSC/RayCastSDFUtil.h:97-116, for tap
 // voxel coordinates (x0..z1) the caller has already resolved.
 // Returns false exactly when the reference does (some tap, in tap order, has
@@ -324,24 +363,22 @@ VHD bool trilinear(const VhHashData& hd, float vs, LK& lk, int p0in, const Taps&
     const uint32_t wmin = min(min(min(v000.cw, v100.cw), min(v010.cw, v001.cw)), min(min(v110.cw, v011.cw), min(v101.cw, v111.cw)));
     if ((wmin >> 24) == 0u) return false;
 
-    const float fx = div_exact(pos.x, vs, rvs), fy = div_exact(pos.y, vs, rvs), fz = div_exact(pos.z, vs, rvs);
-    const float wx = fx - floorf(fx), wy = fy - floorf(fy), wz = fz - floorf(fz);
-    const float ux = 1.0f - wx, uy = 1.0f - wy, uz = 1.0f - wz;
+    float s[8];
+    tap_weights<LK::kOffsets32>(pos, vs, rvs, s);
     float d = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-#define VH_ACC(V, WX, WY, WZ)                                           \
+#define VH_ACC(V, S)                                                    \
     {                                                                   \
-        const float s = (WX) * (WY) * (WZ);                             \
-        d += s * (V).sdf;                                               \
-        if (COLOR) { cr += s * (float)(V).r(); cg += s * (float)(V).g(); cb += s * (float)(V).b(); } \
+        d += (S) * (V).sdf;                                             \
+        if (COLOR) { cr += (S) * (float)(V).r(); cg += (S) * (float)(V).g(); cb += (S) * (float)(V).b(); } \
     }
-    VH_ACC(v000, ux, uy, uz)
-    VH_ACC(v100, wx, uy, uz)
-    VH_ACC(v010, ux, wy, uz)
-    VH_ACC(v001, ux, uy, wz)
-    VH_ACC(v110, wx, wy, uz)
-    VH_ACC(v011, ux, wy, wz)
-    VH_ACC(v101, wx, uy, wz)
-    VH_ACC(v111, wx, wy, wz)
+    VH_ACC(v000, s[0])
+    VH_ACC(v100, s[1])
+    VH_ACC(v010, s[2])
+    VH_ACC(v001, s[3])
+    VH_ACC(v110, s[4])
+    VH_ACC(v011, s[5])
+    VH_ACC(v101, s[6])
+    VH_ACC(v111, s[7])
 #undef VH_ACC
     dist = d;
     if (COLOR) colorOut = (uint32_t)f2uc(cr) | ((uint32_t)f2uc(cg) << 8) | ((uint32_t)f2uc(cb) << 16);
@@ -369,6 +406,7 @@ VHD bool taps_issue(const VhHashData& hd, LK& lk, int p0in, const Taps& tp, TapL
     L.r101 = load_voxel<O32>(hd, p[5], lx1, ly0, lz1); L.r111 = load_voxel<O32>(hd, p[7], lx1, ly1, lz1);
     return true;
 }
+template <bool PACKED>
 VHD bool taps_finish(TapLoads& L, float vs, float rvs, F3 pos, float& dist)
 {
     // (all eight have arrived together: see trilinear)
@@ -378,19 +416,18 @@ VHD bool taps_finish(TapLoads& L, float vs, float rvs, F3 pos, float& dist)
     const Vox v110 = unpack_vox(L.r110), v011 = unpack_vox(L.r011), v101 = unpack_vox(L.r101), v111 = unpack_vox(L.r111);
     const uint32_t wmin = min(min(min(v000.cw, v100.cw), min(v010.cw, v001.cw)), min(min(v110.cw, v011.cw), min(v101.cw, v111.cw)));
     if ((wmin >> 24) == 0u) return false;
-    const float fx = div_exact(pos.x, vs, rvs), fy = div_exact(pos.y, vs, rvs), fz = div_exact(pos.z, vs, rvs);
-    const float wx = fx - floorf(fx), wy = fy - floorf(fy), wz = fz - floorf(fz);
-    const float ux = 1.0f - wx, uy = 1.0f - wy, uz = 1.0f - wz;
+    float s[8];
+    tap_weights<PACKED>(pos, vs, rvs, s);
     float d = 0.0f;
     // (the reference's tap order and arithmetic: trilinear)
-    d += ((ux * uy) * uz) * v000.sdf;
-    d += ((wx * uy) * uz) * v100.sdf;
-    d += ((ux * wy) * uz) * v010.sdf;
-    d += ((ux * uy) * wz) * v001.sdf;
-    d += ((wx * wy) * uz) * v110.sdf;
-    d += ((ux * wy) * wz) * v011.sdf;
-    d += ((wx * uy) * wz) * v101.sdf;
-    d += ((wx * wy) * wz) * v111.sdf;
+    d += s[0] * v000.sdf;
+    d += s[1] * v100.sdf;
+    d += s[2] * v010.sdf;
+    d += s[3] * v001.sdf;
+    d += s[4] * v110.sdf;
+    d += s[5] * v011.sdf;
+    d += s[6] * v101.sdf;
+    d += s[7] * v111.sdf;
     dist = d;
     return true;
 }
@@ -457,9 +494,12 @@ struct RayQ {
 
 VHD void tap_coords(const RayQ& rq, float t, Taps& tp)
 {
-    const float qx = __fmaf_rn(t, rq.dirq.x, rq.camq.x), qy = __fmaf_rn(t, rq.dirq.y, rq.camq.y), qz = __fmaf_rn(t, rq.dirq.z, rq.camq.z);
-    const float gx = floorf(qx), gy = floorf(qy), gz = floorf(qz);
-    const float dev = fmaxf(fmaxf(fabsf((qx - gx) - 0.5f), fabsf((qy - gy) - 0.5f)), fabsf((qz - gz) - 0.5f));
+    // (x and y as a pair: the fma, the distance from the floor and from one half)
+    const f32x2 qxy = fma2(both(t), (f32x2){ rq.dirq.x, rq.dirq.y }, (f32x2){ rq.camq.x, rq.camq.y });
+    const float qz = __fmaf_rn(t, rq.dirq.z, rq.camq.z);
+    const float gx = floorf(qxy.x), gy = floorf(qxy.y), gz = floorf(qz);
+    const f32x2 dxy = (qxy - (f32x2){ gx, gy }) - both(0.5f);
+    const float dev = fmaxf(fmaxf(fabsf(dxy.x), fabsf(dxy.y)), fabsf((qz - gz) - 0.5f));
     if (dev < rq.certLim) {
         tp.x0 = (int)gx; tp.y0 = (int)gy; tp.z0 = (int)gz;
         tp.x1 = tp.x0 + 1; tp.y1 = tp.y0 + 1; tp.z1 = tp.z0 + 1;
@@ -520,7 +560,7 @@ VHD RayQ ray_setup(F3 cam, F3 dir, float voxel, float tFar)
         c = a + (aDist / (aDist - bDist)) * (b - a); /* findIntersectionLinear :140-143 */                                          \
         Taps ctp;                                                                                                                   \
         tap_coords(rq, c, ctp);                                                                                                     \
-        const F3 cpos = mk3((CAM).x + c * (DIR).x, (CAM).y + c * (DIR).y, (CAM).z + c * (DIR).z);                                   \
+        const F3 cpos = ray_point(CAM, DIR, c);                                                                                     \
         float cDist = 0.0f;                                                                                                         \
         if (!trilinear<COLOR>(hd, rq.vs, lk, kPtrUnknown, ctp, cpos, rq.rvs, cDist, COLOUR)) { success = false; break; }            \
         if (aDist * cDist > 0.0f) { a = c; aDist = cDist; }                                                                         \
@@ -675,7 +715,7 @@ VHD void march_ray(LK& lk, const VhHashData& hd, const VhHashParams& hp, const V
                 rcur = P.r;
                 lastValid = P.skipped ? 0 : lastValid;
                 bool ok = false;
-                if (P.state == 1) ok = taps_finish(P.L, rq.vs, rq.rvs, mk3(worldCamPos.x + rcur * worldDir.x, worldCamPos.y + rcur * worldDir.y, worldCamPos.z + rcur * worldDir.z), dist);
+                if (P.state == 1) ok = taps_finish<LK::kOffsets32>(P.L, rq.vs, rq.rvs, ray_point(worldCamPos, worldDir, rcur), dist);
                 if (ok & (lastValid != 0) & (lastSdf > 0.0f) & (dist < 0.0f)) { candidate = true; break; }
                 lastSdf = ok ? dist : lastSdf;
                 lastAlpha = ok ? rcur : lastAlpha;
@@ -745,7 +785,7 @@ VHD void march_ray(LK& lk, const VhHashData& hd, const VhHashParams& hp, const V
 #endif
             cost += kCostSample;
             uint32_t colorUnused = 0u;
-            const F3 pos = mk3(worldCamPos.x + rcur * worldDir.x, worldCamPos.y + rcur * worldDir.y, worldCamPos.z + rcur * worldDir.z);
+            const F3 pos = ray_point(worldCamPos, worldDir, rcur);
             const bool ok = trilinear<false>(hd, rq.vs, lk, p0, tp, pos, rq.rvs, dist, colorUnused);
 #ifdef VH_RENDER_STATS
             statCyc[1] += (float)(clock64() - tB0);
@@ -1323,9 +1363,11 @@ void k_render(VhHashData hd, VhHashParams hp, VhRayCastData rd, VhDepthCameraPar
     render_tile<GRADIENTS, VH_TILE_LIST_CAPACITY, OFFSETS32>(hd, hp, rd, cp, rp, heads, lists, cap, sched, phase, tileTab);
 }
 
-// large tables (48 KB of LDS per workgroup: three workgroups per compute unit)
+// large tables (48 KB of LDS per workgroup: three workgroups per compute unit -- three waves per SIMD, said to the compiler
+// as the least it has to leave room for: 168 registers.  Without gradients the kernel takes 113 either way; with them it
+// took 161 of its own accord while the SLP vectorizer ran over this unit and takes 177 without it when not told)
 template <bool GRADIENTS, bool OFFSETS32>
-__global__ __launch_bounds__(256)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3)))
 void k_render_large(VhHashData hd, VhHashParams hp, VhRayCastData rd, VhDepthCameraParams cp, VhRayCastParams rp,
                     uint4* heads, const int4* lists, uint32_t cap, uint32_t* sched, uint32_t phase, CoAlloc job)
 {
