@@ -196,6 +196,24 @@ public:
     // semantics) on the scene's stream.  Device pointers.  Read-only, on the blocks resident on the device (blocks
     // streamed out to the host grid are absent); the caller must not run it beside an integrate on another stream.
     void queryPoints(const float* d_points, unsigned int n, float* d_sdf, uint32_t* d_color, float* d_gradient, uint8_t* d_valid);
+    // Scene merge (DESIGN.md section 4 "Scene merge"; vh_api.h has the semantics of vh_merge_blocks): every block resident
+    // in `other`'s table, shifted by a whole-block offset, is fused into this scene -- allocated where this scene lacks
+    // the position, then merged voxel by voxel (unobserved source voxels change nothing, an unobserved voxel here takes
+    // the source's with its weight capped, two observed ones go through combineVoxel with THIS scene's weight cap and
+    // colour mode).  mergeBlocks takes a block list in device memory instead ({desc, 512 voxels} as the streaming
+    // passes move them; d_leftOut: n device words or nullptr).  Both block until the merge is done, and leave the
+    // compactified list stale as a stream-in does: compactify before the next ray cast.  Throw VH_ERR_BAD_ARGUMENT (and
+    // do nothing) for two voxel sizes, other == this and a frame in flight in either scene (integrateAhead without
+    // integrateFinish), VH_ERR_HEAP_EXHAUSTED (and do nothing) when the positions this scene lacks outnumber its free
+    // blocks.  Blocks for which the table had no slot are left out whole and counted; *counts (may be nullptr) is
+    // filled before any throw.  No block of this scene may be streamed out to a chunk grid (not checked here).
+    struct MergeCounts {
+        unsigned int c[VH_MERGE_NUM_COUNTS]; // indexed by VH_MERGE_*
+        unsigned int status() const { return c[VH_MERGE_STATUS]; }
+    };
+    void mergeScene(const CUDASceneRepHashSDF& other, const int32_t blockOffset[3], MergeCounts* counts = nullptr);
+    void mergeBlocks(const SDFBlockDesc* d_descs, const Voxel* d_blocks, unsigned int n, const int32_t blockOffset[3], uint32_t* d_leftOut = nullptr,
+                     MergeCounts* counts = nullptr);
     const VhSceneOptions& getOptions() const { return m_options; }
     vhStream_t getStream() const { return m_stream; }
     int32_t nextLockToken(); // fresh bucket-lock epoch (replaces resetHashBucketMutexCUDA)

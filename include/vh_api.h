@@ -269,6 +269,31 @@ int vh_stream_in_pass1(const VhHashData* hd, const VhHashParams* hp, uint32_t n,
 int vh_stream_in_pass2(const VhHashData* hd, const VhHashParams* hp, uint32_t n, uint32_t heapCountPrev,
                        const VhSDFBlockDesc* d_descs, const VhVoxel* d_blocks, vhStream_t stream);
 
+/* ---- scene merge (not in the reference; DESIGN.md section 4 "Scene merge") -----
+ * vh_merge_blocks fuses n source blocks into the table: block i, at d_descs[i].pos + blockOffset, is allocated if the
+ * table does not hold that position, and its 512 voxels are merged voxel by voxel: a source voxel of weight 0 changes
+ * nothing; onto a destination voxel of weight 0 the source voxel is copied with its weight capped at
+ * m_integrationWeightMax; two observed voxels go through combineVoxel as integrate uses it (hp's m_integrationWeightMax
+ * and m_colorIntegration).  The voxels are d_blocks[i * 512 ...] (a block list as the streaming passes move it), or
+ * srcSDFBlocks[d_descs[i].ptr ...] (another scene's pool, its entries listed by vh_merge_gather): exactly one of the
+ * two is given.  The positions must be distinct, and no block of the destination may be streamed out.
+ * All or nothing on the heap: if the positions missing from the table outnumber its free blocks, nothing is changed
+ * and the status word is VH_MERGE_HEAP_SHORT.  A block allocBlock finds no room for is left out whole
+ * (VH_MERGE_NO_SLOT): no entry, no heap block, its index in d_leftOut (may be NULL; room for n words, the first
+ * counts_out[VH_MERGE_LEFT_OUT] are written).  Alloc passes repeat, the bucket mutexes reset before each, while blocks
+ * lose lock races, at most (missing + 8) times; what is pending then is left out too (VH_MERGE_NOT_SETTLED).
+ * d_work: vh_merge_work_bytes(n) bytes of device scratch.  counts_out: VH_MERGE_NUM_COUNTS host words.  Returns VH_OK
+ * with a status set: the caller looks at counts_out[VH_MERGE_STATUS].  One-shot and BLOCKING: the call reads a few
+ * words back after the classification, after every alloc pass and at the end.  n = 0 launches nothing and reports zeros.
+ * vh_time_launch_after: classify, decide, one launch per alloc pass, (give up), combine.
+ * vh_merge_gather: every occupied entry of a table as {pos, ptr}, in no particular order, *d_counter = their number
+ * (cleared first; entries beyond `capacity` are counted but not written).  Asynchronous. */
+size_t vh_merge_work_bytes(uint32_t n);
+int vh_merge_gather(const VhHashData* hd, const VhHashParams* hp, VhSDFBlockDesc* d_descs, uint32_t capacity, uint32_t* d_counter, vhStream_t stream);
+int vh_merge_blocks(const VhHashData* hd, const VhHashParams* hp, uint32_t n, const VhSDFBlockDesc* d_descs, const VhVoxel* d_blocks /* or NULL */,
+                    const VhVoxel* srcSDFBlocks /* or NULL */, const int32_t blockOffset[3], int32_t lockToken, uint32_t* d_work,
+                    uint32_t* d_leftOut /* may be NULL */, uint32_t* counts_out, vhStream_t stream);
+
 /* ---- utilities that are not in the reference -------------------------------- */
 /* Synthetic analytic-sphere depth+colour frame,
  * generated on the device so benchmark inputs are HBM-resident. */
@@ -351,6 +376,18 @@ int vh_scene_rep_set_color_integration(VhSceneRep* s, uint32_t mode);
 /* queryPoints (include/vh.hpp): vh_query_points on the scene's table and stream; device pointers, d_gradient3 may be NULL */
 int vh_scene_rep_query_points(VhSceneRep* s, const float* d_points3, uint32_t n, float* d_sdf, uint32_t* d_color, float* d_gradient3,
                               uint8_t* d_valid);
+
+/* mergeScene / mergeBlocks (include/vh.hpp): vh_merge_blocks on the scene's table and stream with a lock token of the
+ * scene's, after which the compactified list is stale as after a stream-in (compactify before the next ray cast).
+ * merge_scene takes every block resident in src's table (vh_merge_gather; src's stream is ordered before dst's by an
+ * event) and reads its voxels in place; merge_blocks takes a block list in device memory (d_leftOut: device, n words,
+ * may be NULL).  VH_ERR_BAD_ARGUMENT, and nothing done, when the two voxel sizes differ (merge_scene), dst == src, or
+ * either scene is between integrateAhead and integrateFinish; VH_ERR_HEAP_EXHAUSTED, and nothing done, on
+ * VH_MERGE_HEAP_SHORT.  Every other status returns VH_OK: it is in counts[VH_MERGE_STATUS].  counts is filled in
+ * either case.  Blocking. */
+int vh_scene_rep_merge_scene(VhSceneRep* dst, VhSceneRep* src, const int32_t blockOffset[3], uint32_t counts[VH_MERGE_NUM_COUNTS]);
+int vh_scene_rep_merge_blocks(VhSceneRep* dst, const VhSDFBlockDesc* d_descs, const VhVoxel* d_blocks, uint32_t n, const int32_t blockOffset[3],
+                              uint32_t* d_leftOut /* may be NULL */, uint32_t counts[VH_MERGE_NUM_COUNTS]);
 
 /* integrateAhead / integrateFinish: the two halves of integrate() (include/vh.hpp).  *job receives the frame's alloc +
  * compactify passes for vh_raycast_render_co (NULL when the scene's options rule a co-launch out); it belongs to the

@@ -142,6 +142,23 @@ enum {
     VH_STATE_WORDS = 16
 };
 
+/* Scene merge (vh_merge_blocks): bits of its status word, and what the call counts.  Any status leaves the scene a
+ * scene; VH_MERGE_HEAP_SHORT leaves it untouched. */
+#define VH_MERGE_HEAP_SHORT 1u  /* the source names more absent positions than the heap has free blocks: nothing was done */
+#define VH_MERGE_NO_SLOT 2u     /* allocBlock found no room for a block (bucket and list limit): that block was left out whole */
+#define VH_MERGE_NOT_SETTLED 4u /* blocks still lost their lock races at the bound on alloc passes: they were left out whole */
+enum {
+    VH_MERGE_SOURCE_BLOCKS = 0, /* n */
+    VH_MERGE_PRESENT = 1,       /* source blocks whose position the destination already held */
+    VH_MERGE_ALLOCATED = 2,     /* source blocks the call allocated */
+    VH_MERGE_LEFT_OUT = 3,      /* source blocks left out whole (depends on the order the allocs ran in) */
+    VH_MERGE_COMBINED = 4,      /* voxels with both weights > 0: combineVoxel */
+    VH_MERGE_COPIED = 5,        /* voxels with destination weight 0 and source weight > 0: the source's, weight capped */
+    VH_MERGE_ALLOC_PASSES = 6,  /* alloc passes run (depends on the order the allocs ran in) */
+    VH_MERGE_STATUS = 7,
+    VH_MERGE_NUM_COUNTS = 8
+};
+
 /* DepthCameraData, DSC/DepthCameraUtil.h:17-159: the two image buffers the
  * path reads (the cudaArray/texture twins of the reference are not needed:
  * images are read with plain cached loads). */

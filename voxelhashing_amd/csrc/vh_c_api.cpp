@@ -115,6 +115,25 @@ int vh_scene_rep_query_points(VhSceneRep* s, const float* d_points3, uint32_t n,
     if (!s || !d_points3 || !d_sdf || !d_color || !d_valid) return VH_ERR_BAD_ARGUMENT;
     return guarded([&] { s->impl.queryPoints(d_points3, n, d_sdf, d_color, d_gradient3, d_valid); });
 }
+int vh_scene_rep_merge_scene(VhSceneRep* dst, VhSceneRep* src, const int32_t blockOffset[3], uint32_t counts[VH_MERGE_NUM_COUNTS])
+{
+    if (!dst || !src || !blockOffset || !counts) return VH_ERR_BAD_ARGUMENT;
+    CUDASceneRepHashSDF::MergeCounts c;
+    std::memset(&c, 0, sizeof(c));
+    const int rc = guarded([&] { dst->impl.mergeScene(src->impl, blockOffset, &c); });
+    std::memcpy(counts, c.c, sizeof(c.c));
+    return rc;
+}
+int vh_scene_rep_merge_blocks(VhSceneRep* dst, const VhSDFBlockDesc* d_descs, const VhVoxel* d_blocks, uint32_t n, const int32_t blockOffset[3],
+                              uint32_t* d_leftOut, uint32_t counts[VH_MERGE_NUM_COUNTS])
+{
+    if (!dst || !blockOffset || !counts || (n != 0 && (!d_descs || !d_blocks))) return VH_ERR_BAD_ARGUMENT;
+    CUDASceneRepHashSDF::MergeCounts c;
+    std::memset(&c, 0, sizeof(c));
+    const int rc = guarded([&] { dst->impl.mergeBlocks(d_descs, d_blocks, n, blockOffset, d_leftOut, &c); });
+    std::memcpy(counts, c.c, sizeof(c.c));
+    return rc;
+}
 int vh_scene_rep_set_options(VhSceneRep* s, const VhSceneOptions* opt)
 {
     if (!s || !opt) return VH_ERR_BAD_ARGUMENT;

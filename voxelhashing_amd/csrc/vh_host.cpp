@@ -680,6 +680,59 @@ void CUDASceneRepHashSDF::queryPoints(const float* d_points, unsigned int n, flo
     check(vh_query_points(&m_hashData, &m_hashParams, d_points, n, d_sdf, d_color, d_gradient, d_valid, m_stream), "queryPoints");
 }
 
+// ---- scene merge (vh_merge.hip; DESIGN.md section 4 "Scene merge")
+
+void CUDASceneRepHashSDF::mergeBlocks(const SDFBlockDesc* d_descs, const Voxel* d_blocks, unsigned int n, const int32_t blockOffset[3],
+                                      uint32_t* d_leftOut, MergeCounts* counts)
+{
+    MergeCounts local;
+    MergeCounts& c = counts ? *counts : local;
+    std::memset(&c, 0, sizeof(c));
+    if (!blockOffset || (n != 0 && (!d_descs || !d_blocks))) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeBlocks: null argument");
+    if (m_aheadPending) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeBlocks: between integrateAhead() and integrateFinish()");
+    if (n == 0) return;
+    vh::DevicePtr<unsigned char> work = vh::deviceAlloc<unsigned char>(vh_merge_work_bytes(n), "merge scratch");
+    const int32_t token = nextLockToken();
+    noteTableEdited(); // (as a stream-in: what was prepared from the table before is void, the compactified list stale)
+    check(vh_merge_blocks(&m_hashData, &m_hashParams, n, d_descs, d_blocks, nullptr, blockOffset, token, reinterpret_cast<uint32_t*>(work.get()), d_leftOut,
+                          c.c, m_stream), "vh_merge_blocks");
+    if (c.status() & VH_MERGE_HEAP_SHORT) throw vh::Error(VH_ERR_HEAP_EXHAUSTED, "mergeBlocks: the source names more new blocks than the heap has free");
+}
+
+void CUDASceneRepHashSDF::mergeScene(const CUDASceneRepHashSDF& other, const int32_t blockOffset[3], MergeCounts* counts)
+{
+    MergeCounts local;
+    MergeCounts& c = counts ? *counts : local;
+    std::memset(&c, 0, sizeof(c));
+    if (!blockOffset) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeScene: null argument");
+    if (&other == this) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeScene: a scene cannot be merged into itself");
+    if (std::memcmp(&other.m_hashParams.m_virtualVoxelSize, &m_hashParams.m_virtualVoxelSize, sizeof(float)) != 0)
+        throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeScene: the two scenes have different voxel sizes");
+    if (m_aheadPending || other.m_aheadPending) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeScene: between integrateAhead() and integrateFinish()");
+    // what the source's stream has enqueued comes first: an event, no device-wide synchronisation
+    vh::Event done;
+    if (other.m_stream != m_stream) {
+        done = vh::makeEvent(false);
+        checkHip(hipEventRecord((hipEvent_t)done.get(), (hipStream_t)other.m_stream), "hipEventRecord");
+        checkHip(hipStreamWaitEvent((hipStream_t)m_stream, (hipEvent_t)done.get(), 0), "hipStreamWaitEvent");
+    }
+    // the source's entries as a block list: at most one per block of its pool
+    const uint32_t capacity = other.m_hashParams.m_numSDFBlocks;
+    vh::DevicePtr<SDFBlockDesc> descs = vh::deviceAlloc<SDFBlockDesc>(capacity, "merge block list");
+    vh::DevicePtr<uint32_t> counter = vh::deviceAlloc<uint32_t>(1, "merge block count");
+    check(vh_merge_gather(&other.m_hashData, &other.m_hashParams, descs.get(), capacity, counter.get(), m_stream), "vh_merge_gather");
+    uint32_t n = 0;
+    check(vh_memcpy_d2h(&n, counter.get(), sizeof(n), m_stream), "mergeScene");
+    if (n > capacity) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeScene: the source's table holds more entries than its pool has blocks");
+    if (n == 0) return;
+    vh::DevicePtr<unsigned char> work = vh::deviceAlloc<unsigned char>(vh_merge_work_bytes(n), "merge scratch");
+    const int32_t token = nextLockToken();
+    noteTableEdited();
+    check(vh_merge_blocks(&m_hashData, &m_hashParams, n, descs.get(), nullptr, other.m_hashData.d_SDFBlocks, blockOffset, token,
+                          reinterpret_cast<uint32_t*>(work.get()), nullptr, c.c, m_stream), "vh_merge_blocks");
+    if (c.status() & VH_MERGE_HEAP_SHORT) throw vh::Error(VH_ERR_HEAP_EXHAUSTED, "mergeScene: the source holds more new blocks than the heap has free");
+}
+
 void CUDASceneRepHashSDF::getTimings(double out[4])
 {
     m_timer->resolve((hipStream_t)m_stream);

@@ -69,6 +69,36 @@ def synth_frame(spheres, inside, cam_to_world, cam_params, out=None, stream=None
     return fr
 
 
+def _merge_upload(descs, blocks, stream):
+    """-> (descs, blocks) in device memory and n; numpy arrays are checked for repeated positions first"""
+    if isinstance(descs, DeviceBuffer):
+        return descs, blocks, descs.nbytes // T.DESC_DTYPE.itemsize
+    descs = np.ascontiguousarray(descs, dtype=T.DESC_DTYPE)
+    n = len(descs)
+    blocks = np.ascontiguousarray(blocks, dtype=T.VOXEL_DTYPE).reshape(n, T.SDF_BLOCK_VOXELS)
+    if n and len(np.unique(descs["pos"].reshape(n, 3), axis=0)) != n:
+        raise ValueError("merge: the block list names a position more than once")
+    if n == 0:
+        return DeviceBuffer(16), DeviceBuffer(8), 0
+    return DeviceBuffer.from_numpy(descs, stream), DeviceBuffer.from_numpy(blocks, stream), n
+
+
+def _merge_result(code, counts, left, what):
+    """the counts by name plus left_out_indices, read from (buffer, stream), or None; an error code raises VhError with
+    .counts"""
+    out = {k: int(v) for k, v in zip(T.MERGE_COUNTS, counts)}
+    out["left_out_indices"] = None
+    if left is not None:
+        out["left_out_indices"] = np.sort(left[0].download(np.uint32, out["left_out"], left[1]).astype(np.int64))
+    if code != 0:
+        try:
+            check(code, what)
+        except Exception as e:
+            e.counts = out
+            raise
+    return out
+
+
 class CUDASceneRepHashSDF:
     def __init__(self, params, options=None, stream=None):
         self.L = load()
@@ -168,6 +198,28 @@ class CUDASceneRepHashSDF:
         return dict(sdf=d_sdf.download(np.float32, n, s), color=_unpack_rgb(d_col.download(np.uint32, n, s)),
                     gradient=d_grad.download(np.float32, 3 * n, s).reshape(n, 3) if gradient else None,
                     valid=d_val.download(np.uint8, n, s).astype(bool))
+
+    # ---- scene merge (DESIGN.md section 4 "Scene merge") ----------------------------------------------------------
+    def mergeScene(self, other, block_offset=(0, 0, 0)):
+        """Fuses every block resident in `other`'s table into this scene, shifted by whole blocks (vh_api.h has the
+        semantics of vh_merge_blocks) -> the counts by name (vhtypes.MERGE_COUNTS), left_out_indices None.  Raises VhError:
+        VH_ERR_BAD_ARGUMENT for two voxel sizes, other is self, a frame in flight; VH_ERR_HEAP_EXHAUSTED when the new
+        positions outnumber the free blocks -- nothing was done then, and the exception carries the counts (.counts).
+        Compactify before the next ray cast."""
+        counts = (C.c_uint32 * len(T.MERGE_COUNTS))()
+        off = (C.c_int32 * 3)(*[int(v) for v in block_offset])
+        return _merge_result(self.L.vh_scene_rep_merge_scene(self.handle, other.handle, off, counts), counts, None, "CUDASceneRepHashSDF::mergeScene")
+
+    def mergeBlocks(self, descs, blocks, block_offset=(0, 0, 0)):
+        """mergeScene for a block list: descs (DESC_DTYPE [n], ptr ignored) and blocks (VOXEL_DTYPE [n, 512]) as numpy
+        arrays -- repeated positions raise ValueError before anything is uploaded -- or as DeviceBuffers with n =
+        descs.nbytes / 16 -> the counts by name plus left_out_indices, the indices of the blocks the table had no slot for"""
+        off = (C.c_int32 * 3)(*[int(v) for v in block_offset])
+        d_desc, d_blocks, n = _merge_upload(descs, blocks, self.stream)
+        d_left = DeviceBuffer(4 * max(n, 1))
+        counts = (C.c_uint32 * len(T.MERGE_COUNTS))()
+        rc = self.L.vh_scene_rep_merge_blocks(self.handle, d_desc.ptr, d_blocks.ptr, n, off, d_left.ptr, counts)
+        return _merge_result(rc, counts, (d_left, self.stream), "CUDASceneRepHashSDF::mergeBlocks")
 
     def getState(self):
         out = (C.c_uint32 * T.STATE_WORDS)()
@@ -690,6 +742,32 @@ class LauncherScene:
         if out[2] != 1 or d_failed.download(np.uint32, 1 + 2 * n, self.stream)[0] != 0:
             raise RuntimeError("vh_stream_in_device: the pass did not settle (no tag published, or the scratch words were not cleared)")
         return out[4:4 + int(out[0])].astype(np.int64), bool(out[3])
+
+    def merge_gather(self):
+        """vh_merge_gather -> (descs in device memory, n): every occupied entry of this table as {pos, ptr}"""
+        cap = int(self.hp.m_numSDFBlocks)
+        d_desc, cnt = DeviceBuffer(16 * cap), DeviceBuffer(4)
+        check(self.L.vh_merge_gather(C.byref(self.hd), C.byref(self.hp), d_desc.ptr, cap, cnt.ptr, self.stream), "vh_merge_gather")
+        return d_desc, int(cnt.download(np.uint32, 1, self.stream)[0])
+
+    def merge_blocks(self, descs, blocks, lock_token, block_offset=(0, 0, 0), source=None, n=None):
+        """vh_merge_blocks: descs / blocks as numpy arrays (or DeviceBuffers); with source (a LauncherScene) the voxels
+        are read from that scene's pool at descs' ptr and blocks is ignored (n: how many of a DeviceBuffer's descs count) -> the counts by name plus left_out_indices
+        (the status is in the counts: nothing raises for it)"""
+        off = (C.c_int32 * 3)(*[int(v) for v in block_offset])
+        n_given = n
+        if source is not None:
+            d_desc, n = (descs, descs.nbytes // 16) if isinstance(descs, DeviceBuffer) else (DeviceBuffer.from_numpy(np.ascontiguousarray(descs, dtype=T.DESC_DTYPE), self.stream), len(descs))
+            d_blocks, n = None, n_given if n_given is not None else n
+        else:
+            d_desc, d_blocks, n = _merge_upload(descs, blocks, self.stream)
+        d_work = DeviceBuffer(self.L.vh_merge_work_bytes(n))
+        d_left = DeviceBuffer(4 * max(n, 1))
+        counts = (C.c_uint32 * len(T.MERGE_COUNTS))()
+        check(self.L.vh_merge_blocks(C.byref(self.hd), C.byref(self.hp), n, d_desc.ptr, d_blocks.ptr if d_blocks is not None else None,
+                                     source.hd.d_SDFBlocks if source is not None else None, off, lock_token, d_work.ptr, d_left.ptr, counts, self.stream),
+              "vh_merge_blocks")
+        return _merge_result(0, counts, (d_left, self.stream), "vh_merge_blocks")
 
     def download(self, with_voxels=True):
         hp, hd, s = self.hp, self.hd, self.stream

@@ -547,6 +547,24 @@ class Reconstruction:
         return read
 
     # -- around the loop ------------------------------------------------------------------------------------------
+    def mergeFrom(self, other, block_offset=(0, 0, 0)):
+        """Fuses another reconstruction's model into this one (not in the reference; DESIGN.md section 4 "Scene merge"):
+        the blocks resident in other's table (CUDASceneRepHashSDF.mergeScene) and, if other streams, the blocks its chunk
+        grid holds on the host (downloadHostBlocks, upload, mergeBlocks), all shifted by whole blocks.  This scene must
+        hold every block of its own on the device: stream everything in first (ValueError otherwise).  A native loop of
+        either side is synchronised first.  -> [the counts of each merge]; compactify before the next ray cast."""
+        for r in (self, other):
+            if r.native is not None:
+                r.native.synchronize()
+        if self.chunk_grid is not None and self.chunk_grid.getStatistics()["blocks"] != 0:
+            raise ValueError("mergeFrom: the destination's chunk grid holds blocks on the host; stream them in first")
+        out = [self.scene.mergeScene(other.scene, block_offset)]
+        if other.chunk_grid is not None:
+            descs, blocks = other.chunk_grid.downloadHostBlocks()
+            if len(descs):
+                out.append(self.scene.mergeBlocks(descs, blocks, block_offset))
+        return out
+
     def saveRecordedFramesToFile(self, filename=None):
         """RGBDSensor.cpp:339-389: poses from the run, time stamps and IMU records from the input"""
         if self.recorded is None:

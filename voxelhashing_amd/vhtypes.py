@@ -164,6 +164,9 @@ SMOOTH_TABLE_FULL, SMOOTH_RANGE, SMOOTH_BAD_INDEX, SMOOTH_DEGREE = 1, 2, 4, 8
 SMOOTH_MAX_DEGREE, SMOOTH_MAX_ITERATIONS, SMOOTH_MAX_FACTOR_Q16 = 1 << 16, 100, 1 << 16
 SMOOTH_DEFAULT_LAMBDA_Q16, SMOOTH_DEFAULT_MU_Q16 = 32768, -34734
 SMOOTH_COUNTS = ("moved", "boundary_vertices", "isolated_vertices", "status", "edges", "boundary_edges")
+# VH_MERGE_*: bits of the scene merge's status word, what the call counts
+MERGE_HEAP_SHORT, MERGE_NO_SLOT, MERGE_NOT_SETTLED = 1, 2, 4
+MERGE_COUNTS = ("source_blocks", "present", "allocated", "left_out", "combined", "copied", "alloc_passes", "status")
 
 
 class MeshSmoothData(C.Structure):  # VhMeshSmoothData
