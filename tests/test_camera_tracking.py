@@ -50,10 +50,14 @@ def setup_small(w=160, h=120):
 # ---------------------------------------------------------------------------- CPU
 
 def test_oracle_icp_recovers_a_known_motion(oracle_lib):
+    oracle_icp_recovers_a_known_motion(oracle_lib, *setup_small())
+
+
+def oracle_icp_recovers_a_known_motion(O, hp, cp, rp, aim=np.eye(4)):
+    """aim: a rotation every pose is multiplied by from the right (an off-centre camera turned towards the scene)"""
     from oracle import icp
-    O = oracle_lib
-    hp, cp, rp = setup_small()
-    poses = [synth.orbit_pose(k, n_frames=400) for k in range(4)]  # 0.9 degrees / 3.9 cm per frame
+    poses = [(np.asarray(synth.orbit_pose(k, n_frames=400), np.float64).reshape(4, 4) @ aim).astype(np.float32).reshape(16)
+             for k in range(4)]  # 0.9 degrees / 3.9 cm per frame
     sc = oracle_model(O, hp, cp, rp, poses[:3], TRACK_SPHERES)
     model = sc.render(poses[2])
     _, cam, nrm = maps_for(O, TRACK_SPHERES, poses[3], cp)
@@ -266,12 +270,19 @@ def test_gpu_icp_steps_match_oracle_on_every_level(vh, oracle_lib, W, H):
     exactly, its sums within the float32 bound of every term.  202x154 gives 101x77 and 50x38: odd widths and no level
     a whole number of 64 * 12 pixel waves.  The target is the previous frame's own maps (launcher level: any float4
     maps do)."""
+    icp_steps_on_every_level(vh, oracle_lib, T.make_depth_camera_params(W, H))
+
+
+def icp_steps_on_every_level(vh, oracle_lib, cp, aim=np.eye(4)):
+    """test_gpu_icp_steps_match_oracle_on_every_level under the camera `cp` (tests/test_gpu_camera_models.py runs it
+    under cameras with fx != fy and an off-centre principal point; aim: a rotation every pose is multiplied by from the
+    right, which turns such a camera towards the scene)"""
     from oracle import icp
     from voxelhashing_amd import lib
     O = oracle_lib
     L = vh
-    cp = T.make_depth_camera_params(W, H)
-    poses = [synth.orbit_pose(k, n_frames=400) for k in range(3)]
+    W, H = cp.m_imageWidth, cp.m_imageHeight
+    poses = [(np.asarray(synth.orbit_pose(k, n_frames=400), np.float64).reshape(4, 4) @ aim).astype(np.float32).reshape(16) for k in range(3)]
     _, cam, nrm = maps_for(O, TRACK_SPHERES, poses[2], cp)
     _, tcam, tnrm = maps_for(O, TRACK_SPHERES, poses[1], cp)
     ins = [(cam, nrm)] + icp.pyramid(cam, 3)

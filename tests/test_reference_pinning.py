@@ -150,10 +150,13 @@ def _pose(rng, spread=1.0):
 
 @pytest.mark.parametrize("size", [(64, 48), (160, 120), (640, 480)])
 def test_block_in_frustum(libs, size):
+    check_block_in_frustum(libs, hparams("P4"), T.make_depth_camera_params(*size), size[0], 2 if size[0] == 640 else 1)
+
+
+def check_block_in_frustum(libs, hp, cp, seed, stride=1):
+    """isSDFBlockInCameraFrustumApprox of both, on every stride-th block of a box around six cameras"""
     Lo, Lr = libs
-    hp = hparams("P4")
-    cp = T.make_depth_camera_params(*size)
-    rng = np.random.default_rng(size[0])
+    rng = np.random.default_rng(seed)
     inside = 0
     for k in range(6):
         M = _pose(rng) if k else np.eye(4, dtype=np.float32)
@@ -163,7 +166,7 @@ def test_block_in_frustum(libs, size):
         # every block of a box around the camera: the image border and both depth limits are crossed many times
         c = np.floor(M[:3, 3] / (8 * hp.m_virtualVoxelSize)).astype(int)
         r = int(np.ceil(cp.m_sensorDepthWorldMax / (8 * hp.m_virtualVoxelSize))) + 1
-        g = np.arange(-r, r + 1, 2 if size[0] == 640 else 1)
+        g = np.arange(-r, r + 1, stride)
         for blk in np.stack(np.meshgrid(g, g, g), -1).reshape(-1, 3) + c:
             blk = np.ascontiguousarray(blk, dtype=np.int32)
             a = Lo.vho_is_block_in_frustum(C.byref(hp), C.byref(cp), ip(blk))
@@ -171,15 +174,20 @@ def test_block_in_frustum(libs, size):
             assert a == b, (k, blk)
             inside += b
     assert inside > 100
+    return inside
 
 
 @pytest.mark.parametrize("size", [(64, 48), (640, 480)])
 def test_projection_and_back_projection(libs, size):
+    check_projection_and_back_projection(libs, T.make_depth_camera_params(*size))
+
+
+def check_projection_and_back_projection(libs, cp, n=20000):
+    """cameraToKinectScreen (float and int), kinectDepthToSkeleton and the two z maps of both, on n points spread over
+    the image and half a pixel beyond it, and on the image's border"""
     Lo, Lr = libs
-    cp = T.make_depth_camera_params(*size)
-    W, H = size
+    W, H = cp.m_imageWidth, cp.m_imageHeight
     rng = np.random.default_rng(W)
-    n = 20000
     z = np.concatenate([rng.uniform(0.05, 12.0, n - 6), [cp.m_sensorDepthWorldMin, cp.m_sensorDepthWorldMax,
                                                           1e-3, 1.0, 4.0, 8.0]]).astype(np.float32)
     u = rng.uniform(-0.6, W - 0.4, n).astype(np.float32)
@@ -476,15 +484,25 @@ def _maps_equal(x, y, what):
 def test_kernels_on_one_state(libs, name, size, off):
     hp = hparams(name, buckets=1 << 15, blocks=1 << 13)
     cp = T.make_depth_camera_params(*size)
-    a, b = O.OracleScene(hp, cp), O.OracleScene(hp, cp)
-    rb = R.RefScene(b)
     off = np.array(off)
     spheres = synth.S1_SPHERES.copy()
     spheres[:, :3] += off
-    hits = 0
+    poses = []
     for k in range(4):
         q = np.array(synth.orbit_pose(k, 90), dtype=np.float32).copy()
         q[3] += f32(off[0]); q[7] += f32(off[1]); q[11] += f32(off[2])
+        poses.append(q)
+    hits = check_kernels_on_one_state(hp, cp, spheres, poses)
+    assert hits > size[0] * size[1] // 10
+
+
+def check_kernels_on_one_state(hp, cp, spheres, poses):
+    """alloc, integrate, starve, GC free, render and normals of the reference against the oracle's, each on the oracle's
+    state, over the frames at `poses`; then the offline block set of the first two.  -> the most ray hits of a frame"""
+    a, b = O.OracleScene(hp, cp), O.OracleScene(hp, cp)
+    rb = R.RefScene(b)
+    hits = 0
+    for k, q in enumerate(poses):
         d, c = O.synth_frame(spheres, 0, q, cp)
         a.set_transform(q)
         b.set_transform(q)
@@ -508,14 +526,11 @@ def test_kernels_on_one_state(libs, name, size, off):
         got["normals"] = R.compute_normals(got["depth4"])
         _maps_equal(want, got, f"frame {k}")
         hits = max(hits, int((want["depth"] != -np.inf).sum()))
-    assert hits > size[0] * size[1] // 10
     # the same frames with the reference's own launcher (8x8 tiles, a different thread order) and alloc passes until
     # nothing changes: the same block set as the oracle's fixed point
     c2, d2 = O.OracleScene(hp, cp), O.OracleScene(hp, cp)
     r2 = R.RefScene(d2)
-    for k in range(2):
-        q = np.array(synth.orbit_pose(k, 90), dtype=np.float32).copy()
-        q[3] += f32(off[0]); q[7] += f32(off[1]); q[11] += f32(off[2])
+    for k, q in enumerate(poses[:2]):
         d, c = O.synth_frame(spheres, 0, q, cp)
         for s, alloc in ((c2, c2.alloc), (d2, lambda dd, cc: r2.alloc(dd, cc, raster=False))):
             s.set_transform(q)
@@ -526,6 +541,7 @@ def test_kernels_on_one_state(libs, name, size, off):
                 alloc(d, c)
         blocks = lambda s: sorted(tuple(e["pos"]) for e in s.hash_table() if e["ptr"] != T.FREE_ENTRY)
         assert blocks(c2) == blocks(d2), f"frame {k}: offline block set"
+    return hits
 
 
 def _render_variant(name, size, tweak):

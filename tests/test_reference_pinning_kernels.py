@@ -249,19 +249,24 @@ def test_frame_loop_with_gc_run_by_the_reference(libs, off):
     against the oracle's frame loop, after every frame"""
     hp = T.make_hash_params(1 << 14, 1 << 13, **synth.PARAM_SETS["P4"])
     cp = T.make_depth_camera_params(160, 120)
-    opt = T.make_scene_options(offline=False, gc=True, starve=2)
+    freed, _, _ = check_frame_loop_with_gc(hp, cp, _spheres(off), [_pose(k, off, step=12) for k in range(7)])
+    assert freed > 0
+
+
+def check_frame_loop_with_gc(hp, cp, spheres, poses, starve=2):
+    """the online frame loop with GC by the reference's kernels (b) and by the oracle (a), compared after every frame
+    -> (blocks GC freed, a, b)"""
+    opt = T.make_scene_options(offline=False, gc=True, starve=starve)
     a, b = O.OracleScene(hp, cp, options=opt), O.OracleScene(hp, cp, options=opt)
     rb = R.RefScene(b)
-    spheres = _spheres(off)
     freed = 0
-    for k in range(7):
-        q = _pose(k, off, step=12)
+    for k, q in enumerate(poses):
         d, c = O.synth_frame(spheres, 0, q, cp)
         a.integrate(q, d, c)
         freed += rb.integrate(q, d, c)
         canonical.assert_same_scene(a.state(), b.state(), f"frame {k}")
         _assert_same_scene(a, b, f"frame {k}")
-    assert freed > 0
+    return freed, a, b
 
 
 # ------------------------------------------------------------------------------------------------------- stream out

@@ -156,9 +156,12 @@ def plane_maps(cp, tx_prev, tx_cur):
 
 
 def test_restatement_tracks_in_plane_motion_that_geometry_misses(oracle_lib):
+    restatement_tracks_in_plane_motion(T.make_depth_camera_params(160, 120))
+
+
+def restatement_tracks_in_plane_motion(cp, tx=0.02):
     from oracle import icp
-    cp = T.make_depth_camera_params(160, 120)
-    prev, cur, (i, inn, ic), (m, mn, mc) = plane_maps(cp, 0.0, 0.02)
+    prev, cur, (i, inn, ic), (m, mn, mc) = plane_maps(cp, 0.0, tx)
     eye = np.eye(4, dtype=np.float32)
     got, info = G.apply_ct(i, inn, ic, m, mn, mc, prev, all_colour_settings(), eye, cp, 3)
     assert got is not None and info["numCorr"] > 10000
@@ -427,9 +430,15 @@ def test_gpu_rgbd_build_step_on_every_level(vh, oracle_lib, W, H):
     30 sums within the float32 error bound of its summation.  202x154 gives 101x77 and 50x38: odd widths, and no level
     a whole number of waves.  The identity and a translation-only estimate keep the Euler angles exactly 0, so which
     rows pair up is exact."""
+    rgbd_build_step_on_every_level(vh, T.make_depth_camera_params(W, H))
+
+
+def rgbd_build_step_on_every_level(vh, cp):
+    """test_gpu_rgbd_build_step_on_every_level under the camera `cp` (tests/test_gpu_camera_models.py runs it under
+    cameras with fx != fy and an off-centre principal point)"""
     from voxelhashing_amd import lib
     from test_camera_tracking import assert_sums_within_float32_bound
-    cp = T.make_depth_camera_params(W, H)
+    W, H = cp.m_imageWidth, cp.m_imageHeight
     _, _, (i, inn, ic), (m, mn, mc) = plane_maps(cp, 0.0, 0.02)
     pyr = G.pyramids(i, inn, ic, m, mn, mc, 3)
     ts = all_colour_settings()
