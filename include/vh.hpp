@@ -214,6 +214,19 @@ public:
     void mergeScene(const CUDASceneRepHashSDF& other, const int32_t blockOffset[3], MergeCounts* counts = nullptr);
     void mergeBlocks(const SDFBlockDesc* d_descs, const Voxel* d_blocks, unsigned int n, const int32_t blockOffset[3], uint32_t* d_leftOut = nullptr,
                      MergeCounts* counts = nullptr);
+    // Resampled merge (DESIGN.md section 4 "Resampled merge"; vh_api.h has the rule of vh_resample_blocks): `other`, whose
+    // world frame and voxel size may differ from this scene's, is sampled at this scene's voxel centres under the rigid
+    // transform dstFromSrc (4x4 row-major, metres, this scene's frame from other's) and the resulting block list is fused
+    // by the plain merge.  Only destination blocks with an observed voxel are listed: a source block of unobserved voxels
+    // allocates nothing here, where mergeScene allocates its block.  Blocks; nothing of this scene is written before the
+    // merge stage, so a refusal leaves it as it was: VH_ERR_BAD_ARGUMENT for a matrix that is not rigid, a ratio of voxel
+    // sizes outside [1/2, 2], other == this, a frame in flight in either scene, and a block outside [-2^20, 2^20)
+    // (VH_RESAMPLE_OUT_OF_RANGE); VH_ERR_HEAP_EXHAUSTED as mergeScene.  Both counts (may be nullptr) are filled before a throw.
+    struct ResampleCounts {
+        unsigned int c[VH_RESAMPLE_NUM_COUNTS]; // indexed by VH_RESAMPLE_*
+        unsigned int status() const { return c[VH_RESAMPLE_STATUS]; }
+    };
+    void mergeSceneTransformed(const CUDASceneRepHashSDF& other, const double dstFromSrc[16], MergeCounts* counts = nullptr, ResampleCounts* resampled = nullptr);
     const VhSceneOptions& getOptions() const { return m_options; }
     vhStream_t getStream() const { return m_stream; }
     int32_t nextLockToken(); // fresh bucket-lock epoch (replaces resetHashBucketMutexCUDA)

@@ -294,6 +294,37 @@ int vh_merge_blocks(const VhHashData* hd, const VhHashParams* hp, uint32_t n, co
                     const VhVoxel* srcSDFBlocks /* or NULL */, const int32_t blockOffset[3], int32_t lockToken, uint32_t* d_work,
                     uint32_t* d_leftOut /* may be NULL */, uint32_t* counts_out, vhStream_t stream);
 
+/* ---- resampled merge (not in the reference; DESIGN.md section 4 "Resampled merge") -----
+ * A source scene sampled at the voxel centres of another lattice: the block list that vh_merge_blocks then fuses.
+ * All geometry is in voxel index space.  vh_resample_voxel_transforms makes the two 3x4 row-major float matrices from a
+ * rigid 4x4 row-major dstFromSrc (metres) and the two voxel sizes, in double, rounded once:
+ *   srcVoxFromDstVox = [R^T (vsDst / vsSrc) | -R^T t / vsSrc]      dstVoxFromSrcVox = [R (vsSrc / vsDst) | t / vsDst]
+ * and returns VH_ERR_BAD_ARGUMENT for a bottom row other than (0, 0, 0, 1), max |R^T R - I| > 1e-4, det R <= 0, a
+ * non-finite entry or voxel size, or vsSrc / vsDst outside [1/2, 2].  Host only.
+ * vh_resample_blocks, per destination voxel (i, j, k) of a candidate block: q_r = ((m_r0 i + m_r1 j) + m_r2 k) + m_r3
+ * with m = srcVoxFromDstVox in float; b = floor(q), f = q - b, g = 1 - f; the eight taps b + (bit 0, bit 1, bit 2) of
+ * t = 0..7 weigh w_t = (a_x a_y) a_z, a = f where the bit is set and g where not; a tap of weight 0 is not read.  The
+ * voxel is unobserved (all zero) if some |q_r| is not below 2^24, or a used tap lies in a block the source does not
+ * hold or has weight 0; otherwise its sdf and each colour channel are the used taps' w * value summed in tap order
+ * from the first product, the colour rounded as (int)(sum + 0.5f) and capped at 255, its weight the least of the used
+ * taps'.  Candidate blocks are those a source block d_srcDescs[i].pos may reach (a superset, made distinct in a table of
+ * 2^slotsLog2 slots); the staged list holds exactly the candidates with an observed voxel, each once, in no order.
+ * Two calls, both BLOCKING (each reads a few words back):
+ *   count: d_staging NULL.  Finds the candidates; counts_out[VH_RESAMPLE_CANDIDATES] and the status are final.
+ *   fill:  d_work as the count call left it, d_outDescs and d_staging with room for stagingBlocks >= candidates blocks.
+ *          Block c is written whole to d_staging + c * 512; d_outDescs[0 .. staged) = {pos, ptr = c * 512}: a list for
+ *          vh_merge_blocks with srcSDFBlocks = d_staging.  Staging needs no clearing: only listed blocks are read.
+ * With a status bit set the fill call does nothing.  VH_ERR_BAD_ARGUMENT for a matrix that is not finite or stretches
+ * beyond what ratio 2 allows (6 candidate blocks, 5 source blocks per axis), slotsLog2 outside [4, 28], staging too
+ * small.  d_work: vh_resample_work_bytes(slotsLog2) bytes.  counts_out: VH_RESAMPLE_NUM_COUNTS host words.
+ * vh_time_launch_after: count: candidates; fill: resample. */
+int vh_resample_voxel_transforms(const double* dstFromSrc16, float vsSrc, float vsDst, float* srcVoxFromDstVox12, float* dstVoxFromSrcVox12);
+size_t vh_resample_work_bytes(uint32_t slotsLog2);
+int vh_resample_blocks(const VhHashData* srcHd, const VhHashParams* srcHp, uint32_t n, const VhSDFBlockDesc* d_srcDescs,
+                       const float* srcVoxFromDstVox12, const float* dstVoxFromSrcVox12, uint32_t slotsLog2, uint32_t* d_work,
+                       VhSDFBlockDesc* d_outDescs /* NULL: count */, VhVoxel* d_staging /* NULL: count */, uint32_t stagingBlocks,
+                       uint32_t* counts_out, vhStream_t stream);
+
 /* ---- utilities that are not in the reference -------------------------------- */
 /* Synthetic analytic-sphere depth+colour frame,
  * generated on the device so benchmark inputs are HBM-resident. */
@@ -388,6 +419,17 @@ int vh_scene_rep_query_points(VhSceneRep* s, const float* d_points3, uint32_t n,
 int vh_scene_rep_merge_scene(VhSceneRep* dst, VhSceneRep* src, const int32_t blockOffset[3], uint32_t counts[VH_MERGE_NUM_COUNTS]);
 int vh_scene_rep_merge_blocks(VhSceneRep* dst, const VhSDFBlockDesc* d_descs, const VhVoxel* d_blocks, uint32_t n, const int32_t blockOffset[3],
                               uint32_t* d_leftOut /* may be NULL */, uint32_t counts[VH_MERGE_NUM_COUNTS]);
+/* mergeSceneTransformed (include/vh.hpp): src, in another world frame and possibly at another voxel size, sampled at
+ * dst's voxel centres under dstFromSrc16 (rigid, 4x4 row-major doubles, metres: a point of src's frame in dst's) and
+ * fused by the plain merge: vh_merge_gather on src, vh_resample_blocks (count, with a table that grows while it fills;
+ * fill into a staging pool), vh_merge_blocks with the staging pool as its source.  dst is not written before the last
+ * stage.  Only destination blocks with an observed voxel are merged (merge_scene allocates a block of unobserved voxels
+ * too).  VH_ERR_BAD_ARGUMENT, and nothing done, for a matrix vh_resample_voxel_transforms refuses, voxel sizes further
+ * apart than a factor of 2, dst == src, a frame in flight in either scene, or a resample status
+ * (VH_RESAMPLE_OUT_OF_RANGE); VH_ERR_HEAP_EXHAUSTED, and nothing done, on VH_MERGE_HEAP_SHORT.  Both counts are filled
+ * in either case.  Blocking; compactify before the next ray cast. */
+int vh_scene_rep_merge_scene_transformed(VhSceneRep* dst, VhSceneRep* src, const double* dstFromSrc16, uint32_t mergeCounts[VH_MERGE_NUM_COUNTS],
+                                         uint32_t resampleCounts[VH_RESAMPLE_NUM_COUNTS]);
 
 /* integrateAhead / integrateFinish: the two halves of integrate() (include/vh.hpp).  *job receives the frame's alloc +
  * compactify passes for vh_raycast_render_co (NULL when the scene's options rule a co-launch out); it belongs to the

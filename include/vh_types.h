@@ -159,6 +159,20 @@ enum {
     VH_MERGE_NUM_COUNTS = 8
 };
 
+/* Resampled merge (vh_resample_blocks): bits of its status word, and what the call counts.  Any status bit means that
+ * nothing was staged: there is nothing to merge and the destination is untouched.  No count depends on the order in
+ * which the device's atomics ran. */
+#define VH_RESAMPLE_OUT_OF_RANGE 1u /* a source block, or a destination block it reaches, lies outside [-2^20, 2^20) */
+#define VH_RESAMPLE_TABLE_FULL 2u   /* the table that makes the candidates distinct had no slot left: call again with more slots */
+enum {
+    VH_RESAMPLE_SOURCE_BLOCKS = 0, /* n */
+    VH_RESAMPLE_CANDIDATES = 1,    /* distinct destination blocks some source block may reach */
+    VH_RESAMPLE_STAGED = 2,        /* candidates with an observed voxel: the blocks handed to the merge */
+    VH_RESAMPLE_OBSERVED = 3,      /* observed voxels in the staged blocks */
+    VH_RESAMPLE_STATUS = 4,
+    VH_RESAMPLE_NUM_COUNTS = 5
+};
+
 /* DepthCameraData, DSC/DepthCameraUtil.h:17-159: the two image buffers the
  * path reads (the cudaArray/texture twins of the reference are not needed:
  * images are read with plain cached loads). */

@@ -17,7 +17,19 @@ one kernel per alloc pass, combine).  The merge changes its destination, so ever
 a sample whose merge took another number of alloc passes than the first one is dropped (the skip count would name
 another kernel).
 
-    python tools/bench_merge.py [--frames 24] [--reps 7] [--config cfg2] [--scene S1] [--out FILE]"""
+With --transform the second scene is resampled into the first under a rigid motion (0.6 rad about (1, 2, 3) through the
+world's origin, which the orbit circles, and a shift of a few voxels and a fraction: CUDASceneRepHashSDF.mergeSceneTransformed,
+vh_resample.hip).
+The call launches gather, candidates, resample and then the merge's kernels on the staged list; added to the line are
+
+  resample                candidates, staged blocks, observed voxels
+  candidates_us, resample_us   the two new kernels' own durations [median, least]
+  stage_us                the three stages the issue names: candidates, resample, merge (classify + alloc + combine)
+  bytes                   the source read once by the resample kernel (4 KB per source block), the staging pool written
+                          (4 KB per staged block; an empty candidate leaves before it writes) and read again by the
+                          combine, the destination read and written (8 KB per shared block, 4 KB per new one)
+
+    python tools/bench_merge.py [--frames 24] [--reps 7] [--config cfg2] [--scene S1] [--transform] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -38,6 +50,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--config", default="cfg2", choices=["cfg1", "cfg2", "cfg3", "cfg4"])
     ap.add_argument("--scene", default="S1", help="S1, or the dense S2 (thousands of blocks: the combine kernel's rate with the device filled)")
+    ap.add_argument("--transform", action="store_true", help="resample the second scene into the first under a rigid motion (mergeSceneTransformed)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
     from voxelhashing_amd import engine as E, lib, synth, vhtypes as T
@@ -64,6 +77,16 @@ def main():
         scene.synchronize()
 
     build(src, half, a.frames)
+    motion = None
+    if a.transform:
+        # about the origin, which the orbit circles, so that the two halves still overlap
+        th, ax = 0.6, np.array([1.0, 2.0, 3.0]) / np.sqrt(14.0)
+        K = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+        R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+        vs = float(hp.m_virtualVoxelSize)
+        motion = np.eye(4)
+        motion[:3, :3] = R
+        motion[:3, 3] = np.array([3.3, -5.4, 10.7]) * vs
 
     def merge(skip=None):
         """a fresh destination, one merge -> (counts, the armed kernel's us or None, the call's ms)"""
@@ -71,7 +94,7 @@ def main():
         if skip is not None:
             lib.check(L.vh_time_launch_after(skip, e0, e1), "vh_time_launch_after")
         t0 = time.perf_counter()
-        counts = dst.mergeScene(src)
+        counts = dst.mergeSceneTransformed(src, motion) if a.transform else dst.mergeScene(src)
         ms_call = 1e3 * (time.perf_counter() - t0)
         us = None
         if skip is not None:
@@ -84,6 +107,11 @@ def main():
     passes = first["alloc_passes"]
     assert first["status"] == 0, first
     phases = [("gather", 0), ("classify", 1)] + [(f"alloc{p}", 3 + p) for p in range(passes)] + [("combine", 3 + passes)]
+    if a.transform:
+        rs = first["resample"]
+        # (a table that filled and grew would have run the candidates kernel again and shifted every later launch)
+        assert rs["candidates"] <= 16 * rs["source_blocks"], rs
+        phases = [("gather", 0), ("candidates", 1), ("resample", 2), ("classify", 3)] + [(f"alloc{p}", 5 + p) for p in range(passes)] + [("combine", 5 + passes)]
     res = dict(lib=os.path.basename(lib.LIB_PATH), config=a.config, scene=a.scene, frames=a.frames, reps=a.reps,
                blocks=dict(source=first["source_blocks"], present=first["present"], allocated=first["allocated"], left_out=first["left_out"]),
                voxels=dict(combined=first["combined"], copied=first["copied"]), alloc_passes=passes)
@@ -106,6 +134,14 @@ def main():
     res["samples_dropped"] = dropped
     res["call_ms"] = [round(float(np.median(calls)), 3), round(float(np.min(calls)), 3)] if calls else None
     nbytes = 12288 * first["present"] + 8192 * first["allocated"]
+    if a.transform:
+        res["transform"] = [[float(v) for v in row] for row in motion]
+        res["resample"] = dict(candidates=rs["candidates"], staged=rs["staged"], observed=rs["observed"])
+        merge_us = sum(res[k][0] for k in ("classify_us", "combine_us") if res[k]) + res["alloc_us"]
+        res["stage_us"] = dict(candidates=res["candidates_us"] and res["candidates_us"][0], resample=res["resample_us"] and res["resample_us"][0],
+                               merge=round(merge_us, 1))
+        res["bytes"] = dict(source_read=4096 * rs["source_blocks"], staging_written=4096 * rs["staged"], staging_read=4096 * rs["staged"],
+                            destination_read=4096 * first["present"], destination_written=4096 * (first["present"] + first["allocated"]))
     res["combine_bytes"] = nbytes
     if res["combine_us"]:
         rate = nbytes / (res["combine_us"][0] * 1e-6)

@@ -124,6 +124,19 @@ int vh_scene_rep_merge_scene(VhSceneRep* dst, VhSceneRep* src, const int32_t blo
     std::memcpy(counts, c.c, sizeof(c.c));
     return rc;
 }
+int vh_scene_rep_merge_scene_transformed(VhSceneRep* dst, VhSceneRep* src, const double* dstFromSrc16, uint32_t mergeCounts[VH_MERGE_NUM_COUNTS],
+                                         uint32_t resampleCounts[VH_RESAMPLE_NUM_COUNTS])
+{
+    if (!dst || !src || !dstFromSrc16 || !mergeCounts || !resampleCounts) return VH_ERR_BAD_ARGUMENT;
+    CUDASceneRepHashSDF::MergeCounts c;
+    CUDASceneRepHashSDF::ResampleCounts r;
+    std::memset(&c, 0, sizeof(c));
+    std::memset(&r, 0, sizeof(r));
+    const int rc = guarded([&] { dst->impl.mergeSceneTransformed(src->impl, dstFromSrc16, &c, &r); });
+    std::memcpy(mergeCounts, c.c, sizeof(c.c));
+    std::memcpy(resampleCounts, r.c, sizeof(r.c));
+    return rc;
+}
 int vh_scene_rep_merge_blocks(VhSceneRep* dst, const VhSDFBlockDesc* d_descs, const VhVoxel* d_blocks, uint32_t n, const int32_t blockOffset[3],
                               uint32_t* d_leftOut, uint32_t counts[VH_MERGE_NUM_COUNTS])
 {

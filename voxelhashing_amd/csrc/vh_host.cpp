@@ -10,6 +10,7 @@
 // of a per-pass mutex reset, parameters are kernel arguments.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <array>
 #include <climits>
 #include <cstring>
@@ -731,6 +732,79 @@ void CUDASceneRepHashSDF::mergeScene(const CUDASceneRepHashSDF& other, const int
     check(vh_merge_blocks(&m_hashData, &m_hashParams, n, descs.get(), nullptr, other.m_hashData.d_SDFBlocks, blockOffset, token,
                           reinterpret_cast<uint32_t*>(work.get()), nullptr, c.c, m_stream), "vh_merge_blocks");
     if (c.status() & VH_MERGE_HEAP_SHORT) throw vh::Error(VH_ERR_HEAP_EXHAUSTED, "mergeScene: the source holds more new blocks than the heap has free");
+}
+
+// ---- resampled merge (vh_resample.hip; DESIGN.md section 4 "Resampled merge")
+
+static uint32_t log2_at_least(uint64_t v)
+{
+    uint32_t l = 0;
+    while (((uint64_t)1 << l) < v) l++;
+    return l;
+}
+
+void CUDASceneRepHashSDF::mergeSceneTransformed(const CUDASceneRepHashSDF& other, const double dstFromSrc[16], MergeCounts* counts, ResampleCounts* resampled)
+{
+    MergeCounts local;
+    ResampleCounts localR;
+    MergeCounts& c = counts ? *counts : local;
+    ResampleCounts& rc = resampled ? *resampled : localR;
+    std::memset(&c, 0, sizeof(c));
+    std::memset(&rc, 0, sizeof(rc));
+    if (!dstFromSrc) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeSceneTransformed: null argument");
+    if (&other == this) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeSceneTransformed: a scene cannot be merged into itself");
+    if (m_aheadPending || other.m_aheadPending) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeSceneTransformed: between integrateAhead() and integrateFinish()");
+    float srcFromDst[12], dstFromSrcVox[12];
+    check(vh_resample_voxel_transforms(dstFromSrc, other.m_hashParams.m_virtualVoxelSize, m_hashParams.m_virtualVoxelSize, srcFromDst, dstFromSrcVox),
+          "mergeSceneTransformed: the transform is not rigid, or the voxel sizes differ by more than a factor of 2");
+    vh::Event done;
+    if (other.m_stream != m_stream) {
+        done = vh::makeEvent(false);
+        checkHip(hipEventRecord((hipEvent_t)done.get(), (hipStream_t)other.m_stream), "hipEventRecord");
+        checkHip(hipStreamWaitEvent((hipStream_t)m_stream, (hipEvent_t)done.get(), 0), "hipStreamWaitEvent");
+    }
+    // stage 1: the source's entries as a block list
+    const uint32_t capacity = other.m_hashParams.m_numSDFBlocks;
+    vh::DevicePtr<SDFBlockDesc> descs = vh::deviceAlloc<SDFBlockDesc>(capacity, "resample block list");
+    vh::DevicePtr<uint32_t> counter = vh::deviceAlloc<uint32_t>(1, "resample block count");
+    check(vh_merge_gather(&other.m_hashData, &other.m_hashParams, descs.get(), capacity, counter.get(), m_stream), "vh_merge_gather");
+    uint32_t n = 0;
+    check(vh_memcpy_d2h(&n, counter.get(), sizeof(n), m_stream), "mergeSceneTransformed");
+    if (n > capacity) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeSceneTransformed: the source's table holds more entries than its pool has blocks");
+    if (n == 0) return;
+    // stage 2: the candidates.  The table starts at 16 slots per source block and grows fourfold while it fills, up to
+    // two slots for each of the 6^3 candidates a source block can name at most: that one cannot fill.  Four tries at most.
+    const uint32_t most = log2_at_least(2ull * 216ull * n);
+    uint32_t slotsLog2 = std::max(4u, log2_at_least(16ull * n));
+    vh::DevicePtr<unsigned char> work;
+    for (int attempt = 0; attempt < 4; attempt++) {
+        slotsLog2 = std::min(slotsLog2, most);
+        if (slotsLog2 > 28u) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeSceneTransformed: the source holds too many blocks");
+        work = vh::deviceAlloc<unsigned char>(vh_resample_work_bytes(slotsLog2), "resample scratch");
+        check(vh_resample_blocks(&other.m_hashData, &other.m_hashParams, n, descs.get(), srcFromDst, dstFromSrcVox, slotsLog2,
+                                 reinterpret_cast<uint32_t*>(work.get()), nullptr, nullptr, 0, rc.c, m_stream), "vh_resample_blocks");
+        if (!(rc.status() & VH_RESAMPLE_TABLE_FULL) || slotsLog2 == most) break;
+        slotsLog2 += 2u;
+    }
+    if (rc.status() != 0u) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeSceneTransformed: a block lies outside the lattice's range");
+    const uint32_t numCandidates = rc.c[VH_RESAMPLE_CANDIDATES];
+    if (numCandidates == 0) return;
+    // stage 3: the candidates' voxels into a staging pool (not cleared: only listed blocks are read)
+    vh::DevicePtr<SDFBlockDesc> staged = vh::deviceAlloc<SDFBlockDesc>(numCandidates, "resample staged list");
+    vh::DevicePtr<Voxel> staging = vh::deviceAlloc<Voxel>((size_t)numCandidates * VH_SDF_BLOCK_VOXELS, "resample staging pool");
+    check(vh_resample_blocks(&other.m_hashData, &other.m_hashParams, n, descs.get(), srcFromDst, dstFromSrcVox, slotsLog2,
+                             reinterpret_cast<uint32_t*>(work.get()), staged.get(), staging.get(), numCandidates, rc.c, m_stream), "vh_resample_blocks");
+    if (rc.status() != 0u) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeSceneTransformed: a block lies outside the lattice's range");
+    const uint32_t numStaged = rc.c[VH_RESAMPLE_STAGED];
+    if (numStaged == 0) return;
+    // stage 4: the plain merge of the staged list; nothing of this scene was written before
+    vh::DevicePtr<unsigned char> mergeWork = vh::deviceAlloc<unsigned char>(vh_merge_work_bytes(numStaged), "merge scratch");
+    const int32_t zero[3] = { 0, 0, 0 };
+    const int32_t token = nextLockToken();
+    noteTableEdited();
+    check(vh_merge_blocks(&m_hashData, &m_hashParams, numStaged, staged.get(), nullptr, staging.get(), zero, token,
+                          reinterpret_cast<uint32_t*>(mergeWork.get()), nullptr, c.c, m_stream), "vh_merge_blocks");
+    if (c.status() & VH_MERGE_HEAP_SHORT) throw vh::Error(VH_ERR_HEAP_EXHAUSTED, "mergeSceneTransformed: the resampled source holds more new blocks than the heap has free");
 }
 
 void CUDASceneRepHashSDF::getTimings(double out[4])

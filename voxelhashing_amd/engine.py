@@ -99,6 +99,17 @@ def _merge_result(code, counts, left, what):
     return out
 
 
+def resample_voxel_transforms(dst_from_src, vs_src, vs_dst):
+    """vh_resample_voxel_transforms: a rigid 4x4 (metres, the destination's frame from the source's) and the two voxel
+    sizes -> (srcVoxFromDstVox, dstVoxFromSrcVox), float32 [3, 4] in voxel index space.  Raises VhError
+    (VH_ERR_BAD_ARGUMENT) for a matrix that is not rigid or sizes further apart than a factor of 2.  No device is needed."""
+    m = np.ascontiguousarray(dst_from_src, dtype=np.float64).reshape(16)
+    a, b = np.zeros(12, np.float32), np.zeros(12, np.float32)
+    check(load().vh_resample_voxel_transforms(m.ctypes.data, C.c_float(vs_src), C.c_float(vs_dst), a.ctypes.data, b.ctypes.data),
+          "vh_resample_voxel_transforms")
+    return a.reshape(3, 4), b.reshape(3, 4)
+
+
 class CUDASceneRepHashSDF:
     def __init__(self, params, options=None, stream=None):
         self.L = load()
@@ -220,6 +231,27 @@ class CUDASceneRepHashSDF:
         counts = (C.c_uint32 * len(T.MERGE_COUNTS))()
         rc = self.L.vh_scene_rep_merge_blocks(self.handle, d_desc.ptr, d_blocks.ptr, n, off, d_left.ptr, counts)
         return _merge_result(rc, counts, (d_left, self.stream), "CUDASceneRepHashSDF::mergeBlocks")
+
+    def mergeSceneTransformed(self, other, dst_from_src):
+        """Fuses `other`, in another world frame and possibly at another voxel size, into this scene: other is sampled at
+        this scene's voxel centres under the rigid 4x4 dst_from_src (metres; a point of other's frame in this scene's) and
+        the blocks with an observed voxel are merged as mergeScene merges (DESIGN.md section 4 "Resampled merge")
+        -> the merge's counts by name, with "resample": the counts of vhtypes.RESAMPLE_COUNTS.  Raises VhError with
+        .counts: VH_ERR_BAD_ARGUMENT (nothing done) for a matrix that is not rigid, voxel sizes further apart than a
+        factor of 2, other is self, a frame in flight, a block outside the lattice's range; VH_ERR_HEAP_EXHAUSTED
+        (nothing done) as mergeScene.  Compactify before the next ray cast."""
+        m = np.ascontiguousarray(dst_from_src, dtype=np.float64).reshape(16)
+        counts = (C.c_uint32 * len(T.MERGE_COUNTS))()
+        resampled = (C.c_uint32 * len(T.RESAMPLE_COUNTS))()
+        rc = self.L.vh_scene_rep_merge_scene_transformed(self.handle, other.handle, m.ctypes.data, counts, resampled)
+        extra = {"resample": {k: int(v) for k, v in zip(T.RESAMPLE_COUNTS, resampled)}}
+        try:
+            out = _merge_result(rc, counts, None, "CUDASceneRepHashSDF::mergeSceneTransformed")
+        except Exception as e:
+            e.counts.update(extra)
+            raise
+        out.update(extra)
+        return out
 
     def getState(self):
         out = (C.c_uint32 * T.STATE_WORDS)()
@@ -768,6 +800,45 @@ class LauncherScene:
                                      source.hd.d_SDFBlocks if source is not None else None, off, lock_token, d_work.ptr, d_left.ptr, counts, self.stream),
               "vh_merge_blocks")
         return _merge_result(0, counts, (d_left, self.stream), "vh_merge_blocks")
+
+    def resample_blocks(self, src_vox_from_dst_vox, dst_vox_from_src_vox, slots_log2=None):
+        """vh_merge_gather on this table, then vh_resample_blocks, count and fill: this scene sampled on another lattice
+        (the matrices of resample_voxel_transforms) -> the counts by name (vhtypes.RESAMPLE_COUNTS) plus "descs"
+        (DESC_DTYPE [staged], ptr = 512 * the block's place in the staging pool) and "voxels" (VOXEL_DTYPE [staged, 512],
+        in the descs' order): a list for merge_blocks.  slots_log2: the candidate table's size (default: 16 slots per
+        source block).  A status is in the counts, with nothing staged: nothing raises for it."""
+        a = np.ascontiguousarray(src_vox_from_dst_vox, dtype=np.float32).reshape(12)
+        b = np.ascontiguousarray(dst_vox_from_src_vox, dtype=np.float32).reshape(12)
+        d_src, n = self.merge_gather()
+        counts = (C.c_uint32 * len(T.RESAMPLE_COUNTS))()
+
+        def call(d_out, d_staging, room):
+            check(self.L.vh_resample_blocks(C.byref(self.hd), C.byref(self.hp), n, d_src.ptr, a.ctypes.data, b.ctypes.data, slots_log2, d_work.ptr,
+                                            d_out.ptr if d_out else None, d_staging.ptr if d_staging else None, room, counts, self.stream), "vh_resample_blocks")
+            return {k: int(v) for k, v in zip(T.RESAMPLE_COUNTS, counts)}
+
+        # without a size: as mergeSceneTransformed, 16 slots per source block, four times as many while the table fills, up
+        # to two for each of the 6^3 candidates a source block can name
+        grow = slots_log2 is None
+        most = max(4, int(2 * 216 * max(n, 1) - 1).bit_length())
+        if grow:
+            slots_log2 = min(most, max(4, int(16 * max(n, 1) - 1).bit_length()))
+        for _ in range(4):
+            d_work = DeviceBuffer(self.L.vh_resample_work_bytes(slots_log2))
+            out = call(None, None, 0)
+            if not grow or not (out["status"] & T.RESAMPLE_TABLE_FULL) or slots_log2 == most:
+                break
+            slots_log2 = min(most, slots_log2 + 2)
+        out.update(descs=np.zeros(0, T.DESC_DTYPE), voxels=np.zeros((0, T.SDF_BLOCK_VOXELS), T.VOXEL_DTYPE))
+        room = out["candidates"]
+        if out["status"] != 0 or room == 0:
+            return out
+        d_out, d_staging = DeviceBuffer(16 * room), DeviceBuffer(8 * T.SDF_BLOCK_VOXELS * room)
+        out = call(d_out, d_staging, room)
+        descs = d_out.download(T.DESC_DTYPE, out["staged"], self.stream)
+        pool = d_staging.download(T.VOXEL_DTYPE, room * T.SDF_BLOCK_VOXELS, self.stream).reshape(room, T.SDF_BLOCK_VOXELS)
+        out.update(descs=descs, voxels=np.ascontiguousarray(pool[descs["ptr"] // T.SDF_BLOCK_VOXELS]))
+        return out
 
     def download(self, with_voxels=True):
         hp, hd, s = self.hp, self.hd, self.stream

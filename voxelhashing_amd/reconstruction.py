@@ -547,17 +547,27 @@ class Reconstruction:
         return read
 
     # -- around the loop ------------------------------------------------------------------------------------------
-    def mergeFrom(self, other, block_offset=(0, 0, 0)):
+    def mergeFrom(self, other, block_offset=(0, 0, 0), transform=None):
         """Fuses another reconstruction's model into this one (not in the reference; DESIGN.md section 4 "Scene merge"):
         the blocks resident in other's table (CUDASceneRepHashSDF.mergeScene) and, if other streams, the blocks its chunk
         grid holds on the host (downloadHostBlocks, upload, mergeBlocks), all shifted by whole blocks.  This scene must
         hold every block of its own on the device: stream everything in first (ValueError otherwise).  A native loop of
-        either side is synchronised first.  -> [the counts of each merge]; compactify before the next ray cast."""
+        either side is synchronised first.  -> [the counts of each merge]; compactify before the next ray cast.
+        With transform (a rigid 4x4, metres: a point of other's world frame in this one's) other is resampled onto this
+        scene's lattice instead (mergeSceneTransformed; DESIGN.md section 4 "Resampled merge"; the voxel sizes may differ by
+        up to a factor of 2, block_offset must be zero).  Then other, too, must hold every block on the device
+        (ValueError otherwise): a tap that crosses from a device block into a host block would read as unobserved."""
         for r in (self, other):
             if r.native is not None:
                 r.native.synchronize()
         if self.chunk_grid is not None and self.chunk_grid.getStatistics()["blocks"] != 0:
             raise ValueError("mergeFrom: the destination's chunk grid holds blocks on the host; stream them in first")
+        if transform is not None:
+            if tuple(int(v) for v in block_offset) != (0, 0, 0):
+                raise ValueError("mergeFrom: a transform and a block offset exclude each other; put the shift into the transform")
+            if other.chunk_grid is not None and other.chunk_grid.getStatistics()["blocks"] != 0:
+                raise ValueError("mergeFrom: with a transform the source's chunk grid must hold no blocks on the host; stream them in first")
+            return [self.scene.mergeSceneTransformed(other.scene, transform)]
         out = [self.scene.mergeScene(other.scene, block_offset)]
         if other.chunk_grid is not None:
             descs, blocks = other.chunk_grid.downloadHostBlocks()

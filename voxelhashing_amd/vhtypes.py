@@ -167,6 +167,9 @@ SMOOTH_COUNTS = ("moved", "boundary_vertices", "isolated_vertices", "status", "e
 # VH_MERGE_*: bits of the scene merge's status word, what the call counts
 MERGE_HEAP_SHORT, MERGE_NO_SLOT, MERGE_NOT_SETTLED = 1, 2, 4
 MERGE_COUNTS = ("source_blocks", "present", "allocated", "left_out", "combined", "copied", "alloc_passes", "status")
+# VH_RESAMPLE_*: bits of the resampled merge's status word, what vh_resample_blocks counts
+RESAMPLE_OUT_OF_RANGE, RESAMPLE_TABLE_FULL = 1, 2
+RESAMPLE_COUNTS = ("source_blocks", "candidates", "staged", "observed", "status")
 
 
 class MeshSmoothData(C.Structure):  # VhMeshSmoothData
