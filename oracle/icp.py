@@ -1,7 +1,9 @@
 """Oracle twin of the camera tracking: CUDACameraTrackingMultiRes::applyCT
 (DSC/CUDACameraTrackingMultiRes.cpp:241-321) in numpy -- per-pixel arithmetic in float32 as the kernels do it, the
-sums of the linear system in float64, the 6x6 solve by numpy's SVD.  TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (the
-reference ships no fixtures for this path and cannot be built here: see oracle/vh_oracle.h).
+sums of the linear system in float64, the 6x6 solve by numpy's SVD.  TEST INFRASTRUCTURE ONLY.  PARITY: correspondences
+(positions, normals and the pair weight) and pixel_terms / lane_sums in float32 are pinned bit for bit to the reference's own
+kernels, compiled for the CPU (tests/test_tracker_pinning.py through oracle/reference.py); the applyCT loop around them is
+restated from the reference's host code, whose .cpp files need D3D headers and are not built.
 """
 import numpy as np
 
@@ -88,28 +90,46 @@ def build_system(inp, corr, corr_n, delta):
     return ata, atb, float(np.sum(wgt * dn * dn)), float(np.sum(wgt)), int(sel.sum())
 
 
-def pixel_terms(inp, corr, corr_n, delta):
-    """build_system's per-pixel contributions -> (H*W, 30) float64 in the kernel's term order (21 upper-triangle ATA
-    terms, 6 ATb, residual, weight, count), zero where a pixel has no correspondence; for error bounds on the sums"""
+def pixel_terms(inp, corr, corr_n, delta, dtype=np.float64):
+    """build_system's per-pixel contributions -> (H*W, 30) in the kernel's term order (21 upper-triangle ATA terms,
+    6 ATb, residual, weight, count), zero where a pixel has no correspondence.  The operations stand in the order of
+    scanScanElementsCS / addToLocalSystem (DSC/CUDABuildLinearSystem.cu:71-114, 153-162); dtype float64 (the transformed
+    point still rounded to float32) is for error bounds on the sums, dtype float32 is the reference's own arithmetic:
+    tests/test_tracker_pinning.py holds it bit for bit to the reference's kernel, compiled for the CPU."""
     m = np.asarray(delta, dtype=np.float32).reshape(16)
     h, w = inp.shape[:2]
     sel = ((corr[..., 0] != MINF) & (inp[..., 0] != MINF) & (corr_n[..., 0] != MINF)).reshape(-1)
-    out = np.zeros((h * w, 30))
-    q = _mul_p(m, inp.reshape(-1, 4)[sel, :3]).astype(np.float64)
-    p, n = corr.reshape(-1, 4)[sel, :3].astype(np.float64), corr_n.reshape(-1, 4)[sel, :3].astype(np.float64)
-    wgt = corr_n.reshape(-1, 4)[sel, 3].astype(np.float64)
-    row = np.stack([n[:, 0] * q[:, 1] - n[:, 1] * q[:, 0], n[:, 2] * q[:, 0] - n[:, 0] * q[:, 2],
-                    n[:, 1] * q[:, 2] - n[:, 2] * q[:, 1], -n[:, 0], -n[:, 1], -n[:, 2]], 1)
-    b = np.sum(n * (q - p), axis=1)
-    at = 0
-    for r in range(6):
-        for c in range(r, 6):
-            out[sel, at + c - r] = wgt * row[:, r] * row[:, c]
-        at += 6 - r
-        out[sel, 21 + r] = wgt * row[:, r] * b
-    dn = np.sum((p - q) * n, axis=1)
-    out[sel, 27], out[sel, 28], out[sel, 29] = wgt * dn * dn, wgt, 1.0
+    out = np.zeros((h * w, 30), dtype=dtype)
+    q = _mul_p(m, inp.reshape(-1, 4)[sel, :3]).astype(dtype)
+    p, n = corr.reshape(-1, 4)[sel, :3].astype(dtype), corr_n.reshape(-1, 4)[sel, :3].astype(dtype)
+    wgt = corr_n.reshape(-1, 4)[sel, 3].astype(dtype)
+    with np.errstate(all="ignore"):
+        row = np.stack([n[:, 0] * q[:, 1] - n[:, 1] * q[:, 0], n[:, 2] * q[:, 0] - n[:, 0] * q[:, 2],
+                        n[:, 1] * q[:, 2] - n[:, 2] * q[:, 1], -n[:, 0], -n[:, 1], -n[:, 2]], 1)
+        b = (n[:, 0] * (q[:, 0] - p[:, 0]) + n[:, 1] * (q[:, 1] - p[:, 1])) + n[:, 2] * (q[:, 2] - p[:, 2])
+        at = 0
+        for r in range(6):
+            for c in range(r, 6):
+                out[sel, at + c - r] = wgt * row[:, r] * row[:, c]
+            at += 6 - r
+            out[sel, 21 + r] = wgt * row[:, r] * b
+        d = p - q
+        dn = (d[:, 0] * n[:, 0] + d[:, 1] * n[:, 1]) + d[:, 2] * n[:, 2]
+        out[sel, 27], out[sel, 28], out[sel, 29] = wgt * dn * dn, wgt, 1.0
     return out
+
+
+def lane_sums(terms, window):
+    """(N, 30) per-pixel terms -> (ceil(N / window), 30): each lane's window summed in order in the terms' own type,
+    from zero, as a thread of the reference's build kernels sums its pixels"""
+    n = len(terms)
+    lanes = -(-n // window)
+    padded = np.zeros((lanes * window, terms.shape[1]), dtype=terms.dtype)
+    padded[:n] = terms
+    acc = np.zeros((lanes, terms.shape[1]), dtype=terms.dtype)
+    for k in range(window):
+        acc += padded.reshape(lanes, window, -1)[:, k]
+    return acc
 
 
 def is_zero(ata):

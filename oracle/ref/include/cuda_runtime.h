@@ -84,9 +84,13 @@ void vhr_barrier();
 
 template <class F> inline void vhr_call(void* f) { (*static_cast<F*>(f))(); }
 
-/* Runs every workgroup of a launch in order: blocks z, y, x (vhr_run_workgroup). */
-template <class K, class... A>
-inline void vhr_launch(dim3 grid, dim3 block, K kernel, const A&... args)
+/* Runs every workgroup of a launch in order: blocks z, y, x (vhr_run_workgroup).  The arguments of a launch are
+ * converted to the kernel's parameter types as those of a function call are (CUDA programming guide, execution
+ * configuration: "the arguments to the function are passed as in a normal call"), so a literal NULL becomes a null
+ * pointer of the parameter's type: the parameter types are taken from the kernel, never deduced from the arguments. */
+template <class T> struct vhr_identity { typedef T type; };
+template <class... P>
+inline void vhr_launch(dim3 grid, dim3 block, void (*kernel)(P...), const typename vhr_identity<P>::type&... args)
 {
     gridDim = grid;
     blockDim = block;

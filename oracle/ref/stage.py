@@ -12,7 +12,11 @@ reference:
   * `__align__(n) struct Name` becomes `struct __align__(n) Name`: the stand-in spells __align__ as a GNU attribute,
     which applies to the type only after the class key (nvcc's spelling is MSVC's __declspec, which goes before it);
   * an out-of-class definition of a member of an explicit class-template specialisation (`inline ... X<3, 1>::...`)
-    gets the `template<>` that nvcc lets it omit and clang does not.
+    gets the `template<>` that nvcc lets it omit and clang does not;
+  * in the two files of _CONST_REF_FILES only (the RGB-D build unit and the matrix header it uses), a matrix parameter
+    `matNxM<..>& NAME` / `mat1x6& NAME` whose NAME is in _READ_ONLY_REF_PARAMS becomes a const reference: the host
+    compiler the reference was built with (MSVC) binds a temporary to a non-const reference, the tracker's kernel
+    passes products of matrices to such parameters, and the functions only read them.
 
 The reference's own mLib.h is not copied: a quoted include searches the including file's directory first, so a copy
 next to the sources would win over the stand-in in oracle/ref/include.
@@ -27,7 +31,9 @@ FILES = [("DepthSensingCUDA/Source", n) for n in (
     "VoxelUtilHashSDF.h", "RayCastSDFUtil.h", "DepthCameraUtil.h", "CUDAHashParams.h", "CUDARayCastParams.h",
     "CUDADepthCameraParams.h", "cuda_SimpleMatrixUtil.h", "cudaUtil.h",
     "CUDASceneRepHashSDF.cu", "CUDARayCastSDF.cu", "CameraUtil.cu", "CUDASceneRepChunkGrid.cu",
-    "CUDAMarchingCubesSDF.cu", "MarchingCubesSDFUtil.h", "Tables.h")] + [
+    "CUDAMarchingCubesSDF.cu", "MarchingCubesSDFUtil.h", "Tables.h",
+    "CUDAImageHelper.cu", "CUDABuildLinearSystem.cu", "CUDABuildLinearSystemRGBD.cu", "ICPUtil.h",
+    "CameraTrackingInput.h")] + [
     ("DepthSensingCUDA/Include/cutil/inc", "cutil_math.h")]
 
 # `name <<< a, b >>> ( args ) ;` -- nvcc accepts blanks between the angle brackets, so the tokens are matched one by one
@@ -38,6 +44,12 @@ _SPEC_MEMBER = re.compile(r"^\s*inline\b[^;{(]*\w+\s*<\s*\d+\s*(,\s*\d+\s*)*>\s*
 
 # `__align__(n)` (and comments or blanks) directly before `struct Name`
 _ALIGN_STRUCT = re.compile(r"__align__\((\d+)\)(?P<gap>(\s|//[^\n]*)*)struct\s+(?P<name>\w+)")
+
+
+# reference parameters that receive temporaries and are only read (setBlock's source, addToLocalSystem's two rows)
+_CONST_REF_FILES = ("cuda_SimpleMatrixUtil.h", "CUDABuildLinearSystemRGBD.cu")
+_READ_ONLY_REF_PARAMS = ("input", "jacobianBlockRow", "residualsBlockRow")
+_REF_PARAM = re.compile(r"(?<!const )\b(mat\w+(?:<[^<>]*>)?)&\s*(%s)\b" % "|".join(_READ_ONLY_REF_PARAMS))
 
 
 def _split_top(s):
@@ -65,9 +77,11 @@ def _launch(m):
     return f"vhr_launch(dim3({cfg[0]}), dim3({cfg[1]}), {m.group(1)}{', ' + args if args else ''});"
 
 
-def edit(text):
+def edit(text, name=""):
     text = _LAUNCH.sub(_launch, text)
     text = _ALIGN_STRUCT.sub(lambda m: f"{m.group('gap')}struct __align__({m.group(1)}) {m.group('name')}", text)
+    if name in _CONST_REF_FILES:
+        text = _REF_PARAM.sub(r"const \1& \2", text)
     lines = text.split("\n")
     out = []
     for ln in lines:
@@ -88,7 +102,7 @@ def main(ref_root, out_dir):
         dst = os.path.join(out_dir, name)
         tmp = dst + ".tmp"
         with open(tmp, "w", encoding="latin-1") as f:
-            f.write(edit(text))
+            f.write(edit(text, name))
         os.replace(tmp, dst)
     # a stale copy of a file dropped from FILES must not linger
     keep = {n for _, n in FILES}

@@ -78,6 +78,11 @@ def lib():
         "vhr_bilateral_filter_float_map": ([vp, vp, f, f, u32, u32], None),
         "vhr_erode_depth_map": ([vp, vp, C.c_int, u32, u32, f, f], None),
         "vhr_compute_intensity_and_derivatives": ([vp, vp, u32, u32], None),
+        "vhr_icp_correspondences": ([vp, vp, vp, vp, vp, vp, u32, u32, f, f, f, P(f), CP], None),
+        "vhr_icp_lane_sums": ([u32, u32, vp, vp, vp, vp, P(f), u32], None),
+        "vhr_icp_rgbd_lane_sums": ([u32, u32, vp, vp, vp, vp, vp, vp, vp, P(f), P(f), P(f), P(f), u32], None),
+        "vhr_icp_solve": ([P(f), P(f), P(f), P(C.c_int)], C.c_int),
+        "vhr_rotation_angle": ([P(f)], f),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -109,6 +114,85 @@ def compute_intensity_and_derivatives(intensity):
     out = np.empty((H, W, 4), dtype=np.float32)
     lib().vhr_compute_intensity_and_derivatives(out.ctypes.data, src.ctypes.data, W, H)
     return out
+
+
+# ---- the camera trackers (oracle/ref/vh_ref_track.cpp): the same arrays as their twins in oracle/icp.py and
+# tests/rgbd_icp.py.  A 4x4 transform is row-major everywhere in this project, and so it is here.
+
+def _fp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _map(a, channels):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    assert a.shape[-1] == channels if channels > 1 else a.ndim == 2, a.shape
+    return a
+
+
+def icp_correspondences(inp, inp_n, tgt, tgt_n, delta, dist_thres, normal_thres, level_factor, cp):
+    """projectiveCorrespondences -> (positions, normals with the pair weight in .w), as oracle.icp.correspondences.  The
+    launcher takes a float4x4, which is row-major: delta goes in as it is."""
+    inp, inp_n, tgt, tgt_n = (_map(a, 4) for a in (inp, inp_n, tgt, tgt_n))
+    h, w = inp.shape[:2]
+    corr, corr_n = np.empty_like(inp), np.empty_like(inp)
+    m = np.ascontiguousarray(delta, dtype=np.float32).reshape(16)
+    lib().vhr_icp_correspondences(inp.ctypes.data, inp_n.ctypes.data, tgt.ctypes.data, tgt_n.ctypes.data, corr.ctypes.data,
+                                  corr_n.ctypes.data, w, h, dist_thres, normal_thres, level_factor, _fp(m), C.byref(cp))
+    return corr, corr_n
+
+
+def _lanes(n, window):
+    return -(-n // window)
+
+
+def icp_lane_sums(inp, corr, corr_n, delta, window=1):
+    """buildLinearSystem with one thread per block -> (ceil(H W / window), 30) float32: row b is the in-order sum of the
+    30 terms over pixels [b window, (b + 1) window), as a lane of the reference's kernel sums them; with window 1, one
+    pixel's terms, as oracle.icp.pixel_terms.
+
+    THE TRANSFORM'S STORAGE ORDER is settled here and nowhere else: the reference's host code hands the launcher
+    Eigen::Matrix4f::data(), which is column-major, and the kernel reads those 16 floats as a row-major float4x4 and
+    multiplies by its transpose.  `delta` is row-major like every transform of this project, so it is transposed here
+    into what data() would hold."""
+    inp, corr, corr_n = (_map(a, 4) for a in (inp, corr, corr_n))
+    h, w = inp.shape[:2]
+    out = np.empty((_lanes(w * h, window), 30), dtype=np.float32)
+    col_major = np.ascontiguousarray(np.asarray(delta, dtype=np.float32).reshape(4, 4).T).reshape(16)
+    lib().vhr_icp_lane_sums(w, h, out.ctypes.data, inp.ctypes.data, corr.ctypes.data, corr_n.ctypes.data, _fp(col_major), window)
+    return out
+
+
+def icp_rgbd_lane_sums(inp, inp_n, inp_i, tgt, tgt_n, tgt_iad, angles, trans, prm, window=1):
+    """computeNormalEquations with one thread per block -> (ceil(H W / window), 30) float32 lane sums (depth row, then
+    colour row per pixel), arguments as tests/rgbd_icp.pixel_terms.  The intrinsics go in as the row-major 3x3 the
+    host code makes by transposing its Eigen matrix."""
+    inp, inp_n, tgt, tgt_n, tgt_iad = (_map(a, 4) for a in (inp, inp_n, tgt, tgt_n, tgt_iad))
+    inp_i = _map(inp_i, 1)
+    h, w = inp.shape[:2]
+    out = np.empty((_lanes(w * h, window), 30), dtype=np.float32)
+    k = np.array([prm["fx"], 0, prm["mx"], 0, prm["fy"], prm["my"], 0, 0, 1], dtype=np.float32)
+    p = np.array([prm[n] for n in ("weightDepth", "weightColor", "distThres", "normalThres", "sensorMaxDepth",
+                                   "colorGradientMin", "colorThres")], dtype=np.float32)
+    a, t = np.ascontiguousarray(angles, dtype=np.float32), np.ascontiguousarray(trans, dtype=np.float32)
+    lib().vhr_icp_rgbd_lane_sums(w, h, out.ctypes.data, inp.ctypes.data, inp_n.ctypes.data, inp_i.ctypes.data, tgt.ctypes.data,
+                                 tgt_n.ctypes.data, tgt_iad.ctypes.data, _fp(k), _fp(p), _fp(a), _fp(t), window)
+    return out
+
+
+def icp_solve(terms):
+    """the reference's solve step in its own float32 Eigen on a row of 30 summed terms -> (x (6,) float32, condition
+    s_0 / s_5 (float32), rank, ATA.isZero())"""
+    t = np.ascontiguousarray(terms, dtype=np.float32).reshape(30)
+    x = np.empty(6, dtype=np.float32)
+    cond, zero = C.c_float(), C.c_int()
+    rank = lib().vhr_icp_solve(_fp(t), _fp(x), C.byref(cond), C.byref(zero))
+    return x, np.float32(cond.value), int(rank), bool(zero.value)
+
+
+def rotation_angle(R):
+    """Eigen::AngleAxisf(R).angle() of a 3x3 rotation"""
+    m = np.ascontiguousarray(R, dtype=np.float32).reshape(9)
+    return np.float32(lib().vhr_rotation_angle(_fp(m)))
 
 
 def mat4_inverse(m):

@@ -2,6 +2,7 @@
 with scanNormalEquationsDevice, DSC/CUDABuildLinearSystemRGBD.cu:106-201), in the style of oracle/icp.py: per-pixel
 arithmetic in float32 in the kernels' order, each lane's window summed in order, the +32 ... +1 wave tree, the wave
 partials summed in order in float32 (reductionSystemCPU), the 6x6 solve by oracle.icp.solve.  TEST INFRASTRUCTURE ONLY.
+pixel_terms and lane_sums are pinned to the reference's own kernel, compiled for the CPU (tests/test_tracker_pinning.py).
 
 Also the textured-plane scene the RGB-D tests use: a fronto-parallel plane with a smooth procedural texture, where a
 geometric tracker cannot see an in-plane motion and the photometric term can.
@@ -263,23 +264,29 @@ def _row_terms(J, r, w):
     return out
 
 
+def lane_sums(dterm, cterm, win, lanes=None):
+    """each lane's window of `win` pixels summed in order from zero, per pixel the depth row and then the colour row, the
+    J^T F products subtracted (.cu:92-103) -> (lanes, 30) float32; lanes defaults to ceil(N / win)"""
+    N = len(dterm)
+    lanes = -(-N // win) if lanes is None else lanes
+    D = np.zeros((lanes * win, TERMS), np.float32)
+    Cc = np.zeros((lanes * win, TERMS), np.float32)
+    D[:N], Cc[:N] = dterm, cterm
+    D, Cc = D.reshape(lanes, win, TERMS), Cc.reshape(lanes, win, TERMS)
+    acc = np.zeros((lanes, TERMS), np.float32)
+    for w in range(win):
+        for T in (D, Cc):
+            acc[:, :21] += T[:, w, :21]
+            acc[:, 21:27] -= T[:, w, 21:27]
+            acc[:, 27:] += T[:, w, 27:]
+    return acc
+
+
 def build_partials(H, W, level, dterm, cterm):
     """the lanes' windows in order (depth row, then colour row per pixel), the wave tree -> (nP, 30) float32"""
     win = window(level)
     nP = -(-(W * H) // (64 * win))
-    n = nP * 64 * win
-    D = np.zeros((n, TERMS), np.float32)
-    Cc = np.zeros((n, TERMS), np.float32)
-    D[:W * H], Cc[:W * H] = dterm, cterm
-    D, Cc = D.reshape(nP, 64, win, TERMS), Cc.reshape(nP, 64, win, TERMS)
-    acc = np.zeros((nP, 64, TERMS), np.float32)
-    sign = np.ones(TERMS, np.float32)
-    sign[21:27] = -1.0
-    for w in range(win):
-        for T in (D, Cc):
-            acc[..., :21] += T[:, :, w, :21]
-            acc[..., 21:27] -= T[:, :, w, 21:27]
-            acc[..., 27:] += T[:, :, w, 27:]
+    acc = lane_sums(dterm, cterm, win, lanes=nP * 64).reshape(nP, 64, TERMS)
     off = 32
     while off > 0:
         acc[:, :off] += acc[:, off:2 * off]
