@@ -227,6 +227,30 @@ public:
         unsigned int status() const { return c[VH_RESAMPLE_STATUS]; }
     };
     void mergeSceneTransformed(const CUDASceneRepHashSDF& other, const double dstFromSrc[16], MergeCounts* counts = nullptr, ResampleCounts* resampled = nullptr);
+    // Scene cut (DESIGN.md section 4 "Scene cut"; vh_api.h has the rule of vh_cut_blocks): the opposite of the merge, on
+    // the blocks resident in this scene's table.  eraseRegion zeroes the voxels inside the region and frees the blocks
+    // in which no observed voxel is left; cropToRegion does that to everything that is not inside.  extractRegion copies
+    // the region out and writes nothing here: the blocks with an observed voxel in the region, the voxels outside it
+    // zero, into d_descs / d_blocks (device memory with room for `capacity` blocks; block i at d_blocks[i * 512 ...]: a
+    // list for mergeBlocks) -> their number; capacity 0 only counts, too little room throws VH_ERR_BAD_ARGUMENT with
+    // counts->c[VH_CUT_LIFTED] what is needed.  moveRegionTo extracts, merges the list into `dst` shifted by whole blocks
+    // and erases the region here only if the merge left no block out: VH_ERR_HEAP_EXHAUSTED is thrown with both scenes
+    // as they were, and after a merge status that leaves blocks out (VH_MERGE_NO_SLOT, VH_MERGE_NOT_SETTLED, in *merged)
+    // it returns with this scene untouched.  All block until done, leave the compactified list stale after a write
+    // (compactify before the next ray cast) and throw VH_ERR_BAD_ARGUMENT, with nothing done, for a region
+    // vh_cut_region_transform refuses, a frame in flight and, for the move, dst == this and two voxel sizes.  *counts
+    // (may be nullptr) is filled before any throw.  No block of this scene may be streamed out to a chunk grid (not
+    // checked here: such blocks are not seen).
+    typedef VhCutRegion CutRegion;
+    struct CutCounts {
+        unsigned int c[VH_CUT_NUM_COUNTS]; // indexed by VH_CUT_*
+        unsigned int status() const { return c[VH_CUT_STATUS]; }
+    };
+    void eraseRegion(const CutRegion& region, CutCounts* counts = nullptr);
+    void cropToRegion(const CutRegion& region, CutCounts* counts = nullptr);
+    unsigned int extractRegion(const CutRegion& region, SDFBlockDesc* d_descs, Voxel* d_blocks, unsigned int capacity, CutCounts* counts = nullptr);
+    void moveRegionTo(CUDASceneRepHashSDF& dst, const CutRegion& region, const int32_t blockOffset[3], CutCounts* counts = nullptr,
+                      MergeCounts* merged = nullptr);
     const VhSceneOptions& getOptions() const { return m_options; }
     vhStream_t getStream() const { return m_stream; }
     int32_t nextLockToken(); // fresh bucket-lock epoch (replaces resetHashBucketMutexCUDA)
@@ -236,6 +260,8 @@ public:
 
 private:
     void create(const HashParams& params);
+    void cutRegion(const CutRegion& region, uint32_t flags, SDFBlockDesc* d_outDescs, Voxel* d_staging, unsigned int stagingBlocks, CutCounts& c,
+                   const char* what);
     void alloc(const DepthCameraData&, const DepthCameraParams&, const unsigned int* d_bitMask, bool jobPrepared); // :247
     void compactifyHashEntries(const DepthCameraParams&);                                        // :282
     void integrateFused(const DepthCameraData&, const DepthCameraParams&);

@@ -325,6 +325,46 @@ int vh_resample_blocks(const VhHashData* srcHd, const VhHashParams* srcHp, uint3
                        VhSDFBlockDesc* d_outDescs /* NULL: count */, VhVoxel* d_staging /* NULL: count */, uint32_t stagingBlocks,
                        uint32_t* counts_out, vhStream_t stream);
 
+/* ---- scene cut (not in the reference; DESIGN.md section 4 "Scene cut") -----
+ * The opposite of the merge: the voxels of a region erased from the table, lifted out as a block list, or both.
+ * All geometry is in voxel index space.  Voxel l of the block at pos is the integer triple (i, j, k) = 8 pos +
+ * (l & 7, (l >> 3) & 7, l >> 6); with the float 3x4 row-major matrix m12 (regionFromVox), per row r
+ *   u_r = ((m_r0 i + m_r1 j) + m_r2 k) + m_r3      in float32, in that order, no contraction.
+ * VH_CUT_BOX: the voxel is inside iff |u_x| <= 1 && |u_y| <= 1 && |u_z| <= 1; VH_CUT_ELLIPSOID: iff (u_x u_x + u_y u_y) +
+ * u_z u_z <= 1.  A comparison with a NaN is false: outside.  The selected voxels are the inside ones, with
+ * VH_CUT_SELECT_OUTSIDE those that are not inside.  vh_cut_region_transform (host only, in double, each value rounded
+ * once) makes m12 from a rigid 4x4 row-major worldFromRegion [R | t] in metres, three half extents h_r > 0 in metres and
+ * the scene's voxel size: m[r][c] = (R[c][r] vs) / h_r, m[r][3] = -(((R[0][r] t_0 + R[1][r] t_1) + R[2][r] t_2) / h_r);
+ * VH_ERR_BAD_ARGUMENT for what vh_resample_voxel_transforms refuses (bottom row, max |R^T R - I| > 1e-4, det R <= 0, a
+ * non-finite entry) and a half extent or voxel size that is not finite and positive.
+ *
+ * vh_cut_blocks, per block i of the n listed: the block is touched iff one of its 512 voxels is selected, whatever its
+ * weight; a block that is not touched is unchanged byte for byte.
+ *   erase (default): every selected voxel of a touched block becomes 8 zero bytes; a touched block in which no unselected
+ *          voxel has weight > 0 is freed: zeroed whole, then, in a later launch, its entry removed by
+ *          deleteHashEntryElement (the block id back on the heap, which holds all-zero blocks only).
+ *   lift (VH_CUT_LIFT): every touched block with a selected voxel of weight > 0 is written whole to d_staging at a slot c,
+ *          each once, in no particular order -- selected voxels as they are, the others zero -- with d_outDescs[c] =
+ *          {pos, c * 512}: a list vh_merge_blocks takes with d_blocks = d_staging or srcSDFBlocks = d_staging.
+ *   keep (VH_CUT_KEEP, only with VH_CUT_LIFT): nothing in the table is written.
+ *   count (VH_CUT_COUNT_ONLY): nothing is written anywhere but d_work; the counts are those the call without the flag gives.
+ * The blocks are a table's entries (d_descs from vh_merge_gather, d_blocks NULL: the voxels are hd's pool at the descs'
+ * ptr) or, with VH_CUT_KEEP only, a plain list d_blocks[i * 512 ...] (hd may be NULL).  All or nothing: when lifting
+ * and stagingBlocks is less than the blocks to lift, nothing is written, the status is VH_CUT_STAGING_SHORT and the
+ * call returns VH_ERR_BAD_ARGUMENT with the counts filled (the classification's: what a large enough pool would have
+ * seen done; VH_CUT_LIFTED is the room needed).  Deletes that lose a bucket-lock race are run again, the
+ * bucket mutexes reset before every pass but the first, at most (freed + 8) times; a block pending then stays
+ * allocated, all zero (VH_CUT_NOT_SETTLED, counted in VH_CUT_UNSETTLED).  d_work: vh_cut_work_bytes(n) bytes of device
+ * scratch.  counts_out: VH_CUT_NUM_COUNTS host words.  One-shot and BLOCKING: the call reads a few words back after its
+ * first stage and after every delete pass.  n = 0 launches nothing and reports zeros.  The caller compactifies before
+ * the next ray cast.  vh_time_launch_after: select (which erases too when nothing is lifted); when lifting: decide,
+ * lift, (erase); then one launch per delete pass. */
+int vh_cut_region_transform(const double* worldFromRegion16, const float* halfExtents3, float voxelSize, float* m12);
+size_t vh_cut_work_bytes(uint32_t n);
+int vh_cut_blocks(const VhHashData* hd, const VhHashParams* hp, uint32_t n, const VhSDFBlockDesc* d_descs, const VhVoxel* d_blocks /* or NULL */,
+                  const float* m12, uint32_t shape, uint32_t flags, int32_t lockToken, uint32_t* d_work, VhSDFBlockDesc* d_outDescs,
+                  VhVoxel* d_staging, uint32_t stagingBlocks, uint32_t* counts_out, vhStream_t stream);
+
 /* ---- utilities that are not in the reference -------------------------------- */
 /* Synthetic analytic-sphere depth+colour frame,
  * generated on the device so benchmark inputs are HBM-resident. */
@@ -430,6 +470,26 @@ int vh_scene_rep_merge_blocks(VhSceneRep* dst, const VhSDFBlockDesc* d_descs, co
  * in either case.  Blocking; compactify before the next ray cast. */
 int vh_scene_rep_merge_scene_transformed(VhSceneRep* dst, VhSceneRep* src, const double* dstFromSrc16, uint32_t mergeCounts[VH_MERGE_NUM_COUNTS],
                                          uint32_t resampleCounts[VH_RESAMPLE_NUM_COUNTS]);
+/* eraseRegion / cropToRegion / extractRegion / moveRegionTo (include/vh.hpp): vh_cut_blocks on the blocks resident in
+ * the scene's table (vh_merge_gather), on the scene's stream, with a lock token of the scene's own.  erase_region zeroes
+ * the region's voxels and frees the blocks that hold nothing any more; crop_to_region does that to everything outside.
+ * extract_region copies the region out and leaves the scene as it is: the blocks with an observed voxel in the region,
+ * the voxels outside it zero, as a list for vh_scene_rep_merge_blocks in d_descs / d_blocks (device memory, room for
+ * capacity blocks; block i at d_blocks[i * 512 ...]); *numBlocks receives their number.  With capacity 0 it only
+ * counts (the pointers may be NULL); with too little room it returns VH_ERR_BAD_ARGUMENT, *numBlocks what is needed.
+ * move_region_to extracts, merges the list into dst shifted by whole blocks (vh_scene_rep_merge_blocks) and then
+ * erases the region from src -- but only if the merge left no block out: VH_ERR_HEAP_EXHAUSTED on VH_MERGE_HEAP_SHORT
+ * (both scenes untouched), and with VH_MERGE_NO_SLOT / VH_MERGE_NOT_SETTLED in mergeCounts the call returns VH_OK with
+ * src untouched and cutCounts[VH_CUT_VOXELS_ERASED] == 0: the caller decides.  All: VH_ERR_BAD_ARGUMENT, and nothing
+ * done, for a region vh_cut_region_transform refuses, a shape that is none, a frame in flight (integrateAhead without
+ * integrateFinish), and for the move dst == src and differing voxel sizes.  The counts are filled in either case.
+ * Blocking; compactify before the next ray cast. */
+int vh_scene_rep_erase_region(VhSceneRep* s, const VhCutRegion* region, uint32_t counts[VH_CUT_NUM_COUNTS]);
+int vh_scene_rep_crop_to_region(VhSceneRep* s, const VhCutRegion* region, uint32_t counts[VH_CUT_NUM_COUNTS]);
+int vh_scene_rep_extract_region(VhSceneRep* s, const VhCutRegion* region, VhSDFBlockDesc* d_descs, VhVoxel* d_blocks, uint32_t capacity,
+                                uint32_t* numBlocks, uint32_t counts[VH_CUT_NUM_COUNTS]);
+int vh_scene_rep_move_region_to(VhSceneRep* src, VhSceneRep* dst, const VhCutRegion* region, const int32_t blockOffset[3],
+                                uint32_t cutCounts[VH_CUT_NUM_COUNTS], uint32_t mergeCounts[VH_MERGE_NUM_COUNTS]);
 
 /* integrateAhead / integrateFinish: the two halves of integrate() (include/vh.hpp).  *job receives the frame's alloc +
  * compactify passes for vh_raycast_render_co (NULL when the scene's options rule a co-launch out); it belongs to the

@@ -173,6 +173,37 @@ enum {
     VH_RESAMPLE_NUM_COUNTS = 5
 };
 
+/* Scene cut (vh_cut_blocks): the region's shape, the call's flags, bits of its status word, and what the call counts.
+ * VH_CUT_STAGING_SHORT means that nothing was written anywhere; VH_CUT_NOT_SETTLED leaves a valid table in which some
+ * blocks that were to be freed are still allocated, all zero. */
+#define VH_CUT_BOX 0u       /* inside: |u_x| <= 1 && |u_y| <= 1 && |u_z| <= 1 */
+#define VH_CUT_ELLIPSOID 1u /* inside: (u_x u_x + u_y u_y) + u_z u_z <= 1 */
+#define VH_CUT_SELECT_OUTSIDE 1u /* the selected voxels are those that are not inside */
+#define VH_CUT_LIFT 2u           /* blocks with a selected observed voxel are written to the staging pool */
+#define VH_CUT_KEEP 4u           /* (with VH_CUT_LIFT) nothing in the table is written: the region is copied out */
+#define VH_CUT_COUNT_ONLY 8u     /* classify and count; write nothing to table, pool or staging */
+#define VH_CUT_STAGING_SHORT 1u /* more blocks to lift than the staging pool has room for: nothing was done */
+#define VH_CUT_NOT_SETTLED 2u   /* freed blocks still lost their lock races at the bound on delete passes: they stay allocated, all zero */
+enum {
+    VH_CUT_BLOCKS_IN = 0,     /* n */
+    VH_CUT_TOUCHED = 1,       /* blocks with a selected voxel, whatever its weight */
+    VH_CUT_FREED = 2,         /* touched blocks without an unselected observed voxel: their entries are removed (0 with VH_CUT_KEEP) */
+    VH_CUT_LIFTED = 3,        /* touched blocks with a selected observed voxel: written to the staging pool (0 without VH_CUT_LIFT) */
+    VH_CUT_VOXELS_ERASED = 4, /* selected voxels of weight > 0 (0 with VH_CUT_KEEP) */
+    VH_CUT_VOXELS_LIFTED = 5, /* selected voxels of weight > 0 (0 without VH_CUT_LIFT) */
+    VH_CUT_DELETE_PASSES = 6, /* delete passes run (depends on the order the deletes ran in) */
+    VH_CUT_UNSETTLED = 7,     /* freed blocks still pending at the bound on passes (depends on that order too) */
+    VH_CUT_STATUS = 8,
+    VH_CUT_NUM_COUNTS = 9
+};
+/* A region in the world: a box or an ellipsoid with the given half extents along the axes of its own frame (a sphere
+ * is an ellipsoid with three equal extents, an axis-aligned box has R = I). */
+typedef struct VhCutRegion {
+    double worldFromRegion[16]; /* rigid 4x4 row-major [R | t], metres */
+    float halfExtents[3];       /* > 0, metres */
+    uint32_t shape;             /* VH_CUT_BOX / VH_CUT_ELLIPSOID */
+} VhCutRegion;
+
 /* DepthCameraData, DSC/DepthCameraUtil.h:17-159: the two image buffers the
  * path reads (the cudaArray/texture twins of the reference are not needed:
  * images are read with plain cached loads). */

@@ -6,6 +6,7 @@ parameter file, optional mesh at the end) and prints one JSON line with the timi
                            [--mesh scan.ply [--indexed-mesh [--mesh-normals] [--mesh-min-component N] [--mesh-largest-component] [--mesh-cluster M]
                            [--mesh-smooth N [--mesh-smooth-lambda L] [--mesh-smooth-mu M] [--mesh-smooth-free-boundary]]]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
                            [--native [--batch N] [--native-tracking]] [--weighted-colour]
+                           [--crop-box CX CY CZ HX HY HZ [RX RY RZ]] [--erase-box CX CY CZ HX HY HZ [RX RY RZ]]
 
 Without --sens the files named by s_binaryDumpSensorFile[i] in the parameter file are played.  The rendering keys
 (light, material, discontinuity thresholds, s_renderToFile, s_renderToFileDir) come from --params; --render-to switches
@@ -22,7 +23,12 @@ host wait per frame, for the pose; with plain projective ICP, or with --rgbd-tra
 
 --weighted-colour fuses colours weighted by the voxel weights (CUDASceneRepHashSDF::setColorIntegration) instead of the
 reference's running 50/50 average, in either loop: what the RGB-D tracker needs to follow its own reconstruction.  It is
-not a key of the parameter file; the JSON line names the rule as "colour_rule"."""
+not a key of the parameter file; the JSON line names the rule as "colour_rule".
+
+--erase-box takes a box out of the model after the last frame and before --mesh (Reconstruction.eraseRegion), --crop-box
+everything but a box (cropToRegion): the centre and the half extents in metres and, optionally, a rotation vector in
+radians (axis times angle) that turns the box's axes.  The erase runs first when both are given.  With s_streamingEnabled
+the blocks on the host must be streamed in first: the tool says so and stops.  The JSON line has the counts as "cut"."""
 import argparse
 import json
 import os
@@ -31,6 +37,21 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def box_region(values):
+    """centre, half extents and an optional rotation vector (Rodrigues) -> vhtypes.CutRegion"""
+    import numpy as np
+    from voxelhashing_amd import vhtypes as T
+    R = np.eye(3)
+    if len(values) == 9:
+        w = np.asarray(values[6:9], np.float64)
+        th = float(np.linalg.norm(w))
+        if th > 0.0:
+            k = w / th
+            K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+            R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+    return T.make_cut_region(values[0:3], values[3:6], R, T.CUT_BOX)
 
 
 def main():
@@ -56,6 +77,8 @@ def main():
     ap.add_argument("--native", action="store_true", help="play through the native frame loop, fed with raw frames")
     ap.add_argument("--batch", type=int, default=64, help="--native: frames decoded and handed over per call")
     ap.add_argument("--native-tracking", action="store_true", help="--native: let the native loop track the camera (plain ICP, or RGB-D ICP with --rgbd-tracking) when the poses are not recorded")
+    ap.add_argument("--crop-box", type=float, nargs="+", default=None, metavar="V", help="keep only a box of the model before --mesh: centre x y z, half extents x y z (metres) and optionally a rotation vector (radians)")
+    ap.add_argument("--erase-box", type=float, nargs="+", default=None, metavar="V", help="take a box out of the model before --mesh: centre, half extents and optionally a rotation vector, as --crop-box")
     ap.add_argument("--weighted-colour", action="store_true", help="fuse colours weighted by the voxel weights instead of the reference's running 50/50 average")
     args = ap.parse_args()
     if args.mesh_normals and not args.indexed_mesh:
@@ -77,6 +100,9 @@ def main():
         ap.error("--mesh-smooth-lambda, --mesh-smooth-mu: factors in [-1, 1]")
     if args.mesh_min_component < 0:
         ap.error("--mesh-min-component: a number of faces")
+    for name, box in (("--crop-box", args.crop_box), ("--erase-box", args.erase_box)):
+        if box is not None and (len(box) not in (6, 9) or not all(h > 0 for h in box[3:6])):
+            ap.error(name + ": centre x y z, half extents x y z (> 0) and optionally a rotation vector x y z")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU (there is no CPU fallback)")
@@ -121,6 +147,16 @@ def main():
         out["render_to"] = bytes(rs.s_renderToFileDir).decode()
     if args.record:
         out["recorded"] = rec.saveRecordedFramesToFile(args.record)
+    cuts = {}
+    for name, box, cut in (("erase", args.erase_box, rec.eraseRegion), ("crop", args.crop_box, rec.cropToRegion)):
+        if box is not None:
+            try:
+                cuts[name] = cut(box_region(box))
+            except ValueError as e:
+                raise SystemExit(str(e))
+    if cuts:
+        out["cut"] = cuts
+        out["blocks_after_cut"] = rec.scene.getNumOccupiedBlocks()
     if args.mesh:
         if args.indexed_mesh:
             m = rec.extractIsoSurfaceIndexed(args.mesh, normals=args.mesh_normals, min_component_faces=args.mesh_min_component, largest_component=args.mesh_largest_component,

@@ -147,6 +147,48 @@ int vh_scene_rep_merge_blocks(VhSceneRep* dst, const VhSDFBlockDesc* d_descs, co
     std::memcpy(counts, c.c, sizeof(c.c));
     return rc;
 }
+int vh_scene_rep_erase_region(VhSceneRep* s, const VhCutRegion* region, uint32_t counts[VH_CUT_NUM_COUNTS])
+{
+    if (!s || !region || !counts) return VH_ERR_BAD_ARGUMENT;
+    CUDASceneRepHashSDF::CutCounts c;
+    std::memset(&c, 0, sizeof(c));
+    const int rc = guarded([&] { s->impl.eraseRegion(*region, &c); });
+    std::memcpy(counts, c.c, sizeof(c.c));
+    return rc;
+}
+int vh_scene_rep_crop_to_region(VhSceneRep* s, const VhCutRegion* region, uint32_t counts[VH_CUT_NUM_COUNTS])
+{
+    if (!s || !region || !counts) return VH_ERR_BAD_ARGUMENT;
+    CUDASceneRepHashSDF::CutCounts c;
+    std::memset(&c, 0, sizeof(c));
+    const int rc = guarded([&] { s->impl.cropToRegion(*region, &c); });
+    std::memcpy(counts, c.c, sizeof(c.c));
+    return rc;
+}
+int vh_scene_rep_extract_region(VhSceneRep* s, const VhCutRegion* region, VhSDFBlockDesc* d_descs, VhVoxel* d_blocks, uint32_t capacity,
+                                uint32_t* numBlocks, uint32_t counts[VH_CUT_NUM_COUNTS])
+{
+    if (!s || !region || !numBlocks || !counts || (capacity != 0 && (!d_descs || !d_blocks))) return VH_ERR_BAD_ARGUMENT;
+    CUDASceneRepHashSDF::CutCounts c;
+    std::memset(&c, 0, sizeof(c));
+    const int rc = guarded([&] { s->impl.extractRegion(*region, d_descs, d_blocks, capacity, &c); });
+    std::memcpy(counts, c.c, sizeof(c.c));
+    *numBlocks = c.c[VH_CUT_LIFTED];
+    return rc;
+}
+int vh_scene_rep_move_region_to(VhSceneRep* src, VhSceneRep* dst, const VhCutRegion* region, const int32_t blockOffset[3],
+                                uint32_t cutCounts[VH_CUT_NUM_COUNTS], uint32_t mergeCounts[VH_MERGE_NUM_COUNTS])
+{
+    if (!src || !dst || !region || !blockOffset || !cutCounts || !mergeCounts) return VH_ERR_BAD_ARGUMENT;
+    CUDASceneRepHashSDF::CutCounts c;
+    CUDASceneRepHashSDF::MergeCounts m;
+    std::memset(&c, 0, sizeof(c));
+    std::memset(&m, 0, sizeof(m));
+    const int rc = guarded([&] { src->impl.moveRegionTo(dst->impl, *region, blockOffset, &c, &m); });
+    std::memcpy(cutCounts, c.c, sizeof(c.c));
+    std::memcpy(mergeCounts, m.c, sizeof(m.c));
+    return rc;
+}
 int vh_scene_rep_set_options(VhSceneRep* s, const VhSceneOptions* opt)
 {
     if (!s || !opt) return VH_ERR_BAD_ARGUMENT;

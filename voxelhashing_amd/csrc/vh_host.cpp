@@ -807,6 +807,90 @@ void CUDASceneRepHashSDF::mergeSceneTransformed(const CUDASceneRepHashSDF& other
     if (c.status() & VH_MERGE_HEAP_SHORT) throw vh::Error(VH_ERR_HEAP_EXHAUSTED, "mergeSceneTransformed: the resampled source holds more new blocks than the heap has free");
 }
 
+// ---- scene cut (vh_cut.hip; DESIGN.md section 4 "Scene cut")
+
+// vh_cut_blocks on the blocks resident in the table; c is filled before any throw
+void CUDASceneRepHashSDF::cutRegion(const CutRegion& region, uint32_t flags, SDFBlockDesc* d_outDescs, Voxel* d_staging, unsigned int stagingBlocks,
+                                    CutCounts& c, const char* what)
+{
+    std::memset(&c, 0, sizeof(c));
+    const std::string name(what);
+    if (m_aheadPending) throw vh::Error(VH_ERR_BAD_ARGUMENT, name + ": between integrateAhead() and integrateFinish()");
+    if (region.shape != VH_CUT_BOX && region.shape != VH_CUT_ELLIPSOID) throw vh::Error(VH_ERR_BAD_ARGUMENT, name + ": the region's shape is neither a box nor an ellipsoid");
+    float m[12];
+    if (vh_cut_region_transform(region.worldFromRegion, region.halfExtents, m_hashParams.m_virtualVoxelSize, m) != VH_OK)
+        throw vh::Error(VH_ERR_BAD_ARGUMENT, name + ": the region's frame is not rigid, or a half extent is not positive");
+    // the table's entries as a block list: at most one per block of the pool
+    const uint32_t capacity = m_hashParams.m_numSDFBlocks;
+    vh::DevicePtr<SDFBlockDesc> descs = vh::deviceAlloc<SDFBlockDesc>(capacity, "cut block list");
+    vh::DevicePtr<uint32_t> counter = vh::deviceAlloc<uint32_t>(1, "cut block count");
+    check(vh_merge_gather(&m_hashData, &m_hashParams, descs.get(), capacity, counter.get(), m_stream), "vh_merge_gather");
+    uint32_t n = 0;
+    check(vh_memcpy_d2h(&n, counter.get(), sizeof(n), m_stream), what);
+    if (n > capacity) throw vh::Error(VH_ERR_BAD_ARGUMENT, name + ": the table holds more entries than the pool has blocks");
+    if (n == 0) return;
+    vh::DevicePtr<unsigned char> work = vh::deviceAlloc<unsigned char>(vh_cut_work_bytes(n), "cut scratch");
+    const int32_t token = nextLockToken();
+    if (!(flags & (VH_CUT_KEEP | VH_CUT_COUNT_ONLY))) noteTableEdited(); // (as a stream-out: the compactified list is stale)
+    const int rc = vh_cut_blocks(&m_hashData, &m_hashParams, n, descs.get(), nullptr, m, region.shape, flags, token, reinterpret_cast<uint32_t*>(work.get()),
+                                 d_outDescs, d_staging, stagingBlocks, c.c, m_stream);
+    if (c.status() & VH_CUT_STAGING_SHORT) throw vh::Error(VH_ERR_BAD_ARGUMENT, name + ": the region holds more blocks than there is room for");
+    check(rc, "vh_cut_blocks");
+}
+
+void CUDASceneRepHashSDF::eraseRegion(const CutRegion& region, CutCounts* counts)
+{
+    CutCounts local;
+    cutRegion(region, 0u, nullptr, nullptr, 0, counts ? *counts : local, "eraseRegion");
+}
+
+void CUDASceneRepHashSDF::cropToRegion(const CutRegion& region, CutCounts* counts)
+{
+    CutCounts local;
+    cutRegion(region, VH_CUT_SELECT_OUTSIDE, nullptr, nullptr, 0, counts ? *counts : local, "cropToRegion");
+}
+
+unsigned int CUDASceneRepHashSDF::extractRegion(const CutRegion& region, SDFBlockDesc* d_descs, Voxel* d_blocks, unsigned int capacity, CutCounts* counts)
+{
+    CutCounts local;
+    CutCounts& c = counts ? *counts : local;
+    std::memset(&c, 0, sizeof(c));
+    if (capacity != 0 && (!d_descs || !d_blocks)) throw vh::Error(VH_ERR_BAD_ARGUMENT, "extractRegion: null argument");
+    const uint32_t flags = VH_CUT_LIFT | VH_CUT_KEEP | (capacity == 0 ? VH_CUT_COUNT_ONLY : 0u);
+    cutRegion(region, flags, d_descs, d_blocks, capacity, c, "extractRegion");
+    return c.c[VH_CUT_LIFTED];
+}
+
+void CUDASceneRepHashSDF::moveRegionTo(CUDASceneRepHashSDF& dst, const CutRegion& region, const int32_t blockOffset[3], CutCounts* counts, MergeCounts* merged)
+{
+    CutCounts local;
+    MergeCounts localM;
+    CutCounts& c = counts ? *counts : local;
+    MergeCounts& mc = merged ? *merged : localM;
+    std::memset(&c, 0, sizeof(c));
+    std::memset(&mc, 0, sizeof(mc));
+    if (!blockOffset) throw vh::Error(VH_ERR_BAD_ARGUMENT, "moveRegionTo: null argument");
+    if (&dst == this) throw vh::Error(VH_ERR_BAD_ARGUMENT, "moveRegionTo: a region cannot be moved into its own scene");
+    if (std::memcmp(&dst.m_hashParams.m_virtualVoxelSize, &m_hashParams.m_virtualVoxelSize, sizeof(float)) != 0)
+        throw vh::Error(VH_ERR_BAD_ARGUMENT, "moveRegionTo: the two scenes have different voxel sizes");
+    if (m_aheadPending || dst.m_aheadPending) throw vh::Error(VH_ERR_BAD_ARGUMENT, "moveRegionTo: between integrateAhead() and integrateFinish()");
+    // 1. count, 2. lift with keep: this scene is not written
+    const unsigned int n = extractRegion(region, nullptr, nullptr, 0, &c);
+    if (n != 0) {
+        vh::DevicePtr<SDFBlockDesc> descs = vh::deviceAlloc<SDFBlockDesc>(n, "move block list");
+        vh::DevicePtr<Voxel> blocks = vh::deviceAlloc<Voxel>((size_t)n * VH_SDF_BLOCK_VOXELS, "move staging pool");
+        extractRegion(region, descs.get(), blocks.get(), n, &c);
+        // 3. the merge (the lift has finished: the cut blocks).  A refusal throws from here with both scenes untouched.
+        dst.mergeBlocks(descs.get(), blocks.get(), n, blockOffset, nullptr, &mc);
+        if (mc.status() != 0u) return; // blocks were left out: nothing is erased, the caller decides
+    }
+    // 4. the erase; the counts keep what was lifted
+    const unsigned int lifted = c.c[VH_CUT_LIFTED], voxelsLifted = c.c[VH_CUT_VOXELS_LIFTED];
+    cutRegion(region, 0u, nullptr, nullptr, 0, c, "moveRegionTo");
+    c.c[VH_CUT_LIFTED] = lifted;
+    c.c[VH_CUT_VOXELS_LIFTED] = voxelsLifted;
+}
+
 void CUDASceneRepHashSDF::getTimings(double out[4])
 {
     m_timer->resolve((hipStream_t)m_stream);

@@ -110,6 +110,65 @@ def resample_voxel_transforms(dst_from_src, vs_src, vs_dst):
     return a.reshape(3, 4), b.reshape(3, 4)
 
 
+def cut_region_transform(world_from_region, half_extents, voxel_size):
+    """vh_cut_region_transform: a region's rigid frame (4x4, metres), its three half extents (metres) and a scene's voxel
+    size -> regionFromVox, float32 [3, 4] in voxel index space (a voxel is inside a box iff every |row . (i, j, k, 1)| <=
+    1).  Raises VhError (VH_ERR_BAD_ARGUMENT) for a frame that is not rigid or an extent that is not positive.  No
+    device is needed."""
+    m = np.ascontiguousarray(world_from_region, dtype=np.float64).reshape(16)
+    h = np.ascontiguousarray(half_extents, dtype=np.float32).reshape(3)
+    out = np.zeros(12, np.float32)
+    check(load().vh_cut_region_transform(m.ctypes.data, h.ctypes.data, C.c_float(voxel_size), out.ctypes.data), "vh_cut_region_transform")
+    return out.reshape(3, 4)
+
+
+def _cut_result(code, counts, what, extra=None):
+    """the counts by name (vhtypes.CUT_COUNTS) plus `extra`; an error code raises VhError with .counts"""
+    out = {k: int(v) for k, v in zip(T.CUT_COUNTS, counts)}
+    out.update(extra or {})
+    if code != 0:
+        try:
+            check(code, what)
+        except Exception as e:
+            e.counts = out
+            raise
+    return out
+
+
+def _staged_list(d_descs, d_blocks, n, stream):
+    """a lifted list read back: (descs DESC_DTYPE [n], voxels VOXEL_DTYPE [n, 512]), block i of the list at slot i"""
+    if n == 0:
+        return np.zeros(0, T.DESC_DTYPE), np.zeros((0, T.SDF_BLOCK_VOXELS), T.VOXEL_DTYPE)
+    descs = d_descs.download(T.DESC_DTYPE, n, stream)
+    pool = d_blocks.download(T.VOXEL_DTYPE, n * T.SDF_BLOCK_VOXELS, stream).reshape(n, T.SDF_BLOCK_VOXELS)
+    return descs, np.ascontiguousarray(pool[descs["ptr"] // T.SDF_BLOCK_VOXELS])
+
+
+def extract_from_block_list(descs, blocks, region_from_vox, shape, select_outside=False, stream=None):
+    """vh_cut_blocks in its list form (count, then lift with keep): the region copied out of a plain block list -- a
+    streamed scene's host blocks, say -- which is uploaded and left as it is -> the counts by name plus "descs" and
+    "voxels", the blocks with an observed voxel in the region, the voxels outside it zero"""
+    L = load()
+    m = np.ascontiguousarray(region_from_vox, dtype=np.float32).reshape(12)
+    descs = np.ascontiguousarray(descs, dtype=T.DESC_DTYPE)
+    n = len(descs)
+    blocks = np.ascontiguousarray(blocks, dtype=T.VOXEL_DTYPE).reshape(n, T.SDF_BLOCK_VOXELS)
+    counts = (C.c_uint32 * len(T.CUT_COUNTS))()
+    if n == 0:
+        return _cut_result(0, counts, "vh_cut_blocks", dict(zip(("descs", "voxels"), _staged_list(None, None, 0, stream))))
+    d_desc, d_blocks = DeviceBuffer.from_numpy(descs, stream), DeviceBuffer.from_numpy(blocks, stream)
+    d_work = DeviceBuffer(L.vh_cut_work_bytes(n))
+    hp = T.HashParams()
+    flags = T.CUT_LIFT | T.CUT_KEEP | (T.CUT_SELECT_OUTSIDE if select_outside else 0)
+    check(L.vh_cut_blocks(None, C.byref(hp), n, d_desc.ptr, d_blocks.ptr, m.ctypes.data, int(shape), flags | T.CUT_COUNT_ONLY, 0, d_work.ptr, None, None, 0,
+                          counts, stream), "vh_cut_blocks")
+    room = int(counts[T.CUT_COUNTS.index("lifted")])
+    d_out, d_staging = DeviceBuffer(16 * max(room, 1)), DeviceBuffer(8 * T.SDF_BLOCK_VOXELS * max(room, 1))
+    check(L.vh_cut_blocks(None, C.byref(hp), n, d_desc.ptr, d_blocks.ptr, m.ctypes.data, int(shape), flags, 0, d_work.ptr, d_out.ptr, d_staging.ptr, room,
+                          counts, stream), "vh_cut_blocks")
+    return _cut_result(0, counts, "vh_cut_blocks", dict(zip(("descs", "voxels"), _staged_list(d_out, d_staging, room, stream))))
+
+
 class CUDASceneRepHashSDF:
     def __init__(self, params, options=None, stream=None):
         self.L = load()
@@ -252,6 +311,49 @@ class CUDASceneRepHashSDF:
             raise
         out.update(extra)
         return out
+
+    # ---- scene cut (DESIGN.md section 4 "Scene cut") ---------------------------------------------------------------
+    def eraseRegion(self, region):
+        """Zeroes the voxels inside `region` (a vhtypes.CutRegion: make_cut_region) and frees the blocks in which no
+        observed voxel is left (vh_api.h has the rule of vh_cut_blocks) -> the counts by name (vhtypes.CUT_COUNTS).
+        Raises VhError (VH_ERR_BAD_ARGUMENT, nothing done) for a region that is not rigid or has no size and for a frame
+        in flight.  Compactify before the next ray cast."""
+        counts = (C.c_uint32 * len(T.CUT_COUNTS))()
+        return _cut_result(self.L.vh_scene_rep_erase_region(self.handle, C.byref(region), counts), counts, "CUDASceneRepHashSDF::eraseRegion")
+
+    def cropToRegion(self, region):
+        """eraseRegion of everything that is not inside `region`"""
+        counts = (C.c_uint32 * len(T.CUT_COUNTS))()
+        return _cut_result(self.L.vh_scene_rep_crop_to_region(self.handle, C.byref(region), counts), counts, "CUDASceneRepHashSDF::cropToRegion")
+
+    def extractRegion(self, region, download=True):
+        """Copies the region out and leaves the scene as it is: the blocks with an observed voxel in the region, the
+        voxels outside it zero -> the counts by name plus "descs" and "voxels", a list for mergeBlocks: numpy arrays
+        (DESC_DTYPE [n], VOXEL_DTYPE [n, 512]) or, with download=False, DeviceBuffers and "n"."""
+        counts = (C.c_uint32 * len(T.CUT_COUNTS))()
+        n = C.c_uint32()
+        what = "CUDASceneRepHashSDF::extractRegion"
+        _cut_result(self.L.vh_scene_rep_extract_region(self.handle, C.byref(region), None, None, 0, C.byref(n), counts), counts, what)
+        room = n.value
+        d_descs, d_blocks = DeviceBuffer(16 * max(room, 1)), DeviceBuffer(8 * T.SDF_BLOCK_VOXELS * max(room, 1))
+        if room:
+            _cut_result(self.L.vh_scene_rep_extract_region(self.handle, C.byref(region), d_descs.ptr, d_blocks.ptr, room, C.byref(n), counts), counts, what)
+        if not download:
+            return _cut_result(0, counts, what, dict(descs=d_descs, voxels=d_blocks, n=room))
+        descs, voxels = _staged_list(d_descs, d_blocks, room, self.stream)
+        return _cut_result(0, counts, what, dict(descs=descs, voxels=voxels))
+
+    def moveRegionTo(self, dst, region, block_offset=(0, 0, 0)):
+        """Moves the region's voxels into `dst`, shifted by whole blocks: extractRegion, dst.mergeBlocks of the list,
+        eraseRegion here -- the erase only if the merge left no block out -> the cut's counts by name, with "merge":
+        the merge's.  Raises VhError with .counts: VH_ERR_HEAP_EXHAUSTED when dst's pool is too small (both scenes
+        untouched), VH_ERR_BAD_ARGUMENT for dst is self, two voxel sizes, a frame in flight.  A merge status that leaves
+        blocks out (MERGE_NO_SLOT, MERGE_NOT_SETTLED) is in "merge"; this scene is then untouched (voxels_erased 0)."""
+        counts = (C.c_uint32 * len(T.CUT_COUNTS))()
+        merged = (C.c_uint32 * len(T.MERGE_COUNTS))()
+        off = (C.c_int32 * 3)(*[int(v) for v in block_offset])
+        rc = self.L.vh_scene_rep_move_region_to(self.handle, dst.handle, C.byref(region), off, counts, merged)
+        return _cut_result(rc, counts, "CUDASceneRepHashSDF::moveRegionTo", {"merge": {k: int(v) for k, v in zip(T.MERGE_COUNTS, merged)}})
 
     def getState(self):
         out = (C.c_uint32 * T.STATE_WORDS)()
@@ -800,6 +902,48 @@ class LauncherScene:
                                      source.hd.d_SDFBlocks if source is not None else None, off, lock_token, d_work.ptr, d_left.ptr, counts, self.stream),
               "vh_merge_blocks")
         return _merge_result(0, counts, (d_left, self.stream), "vh_merge_blocks")
+
+    def cut_blocks(self, region_from_vox, shape, flags, lock_token, descs=None, blocks=None, staging_blocks=None, poison=None):
+        """vh_cut_blocks on this table's entries (vh_merge_gather) or, with descs / blocks (numpy arrays, VH_CUT_KEEP
+        only), on a plain block list.  region_from_vox: float32 [3, 4] (cut_region_transform).  A lifting call counts
+        first and sizes the staging pool by the count unless staging_blocks says otherwise; poison: a byte the staging
+        pool and its list are filled with before.  -> the counts by name (vhtypes.CUT_COUNTS) plus "code" (the call's
+        return code: nothing raises), "descs" / "voxels" (the lifted list; empty unless the call lifted) and
+        "staging_raw" (the list's and the pool's bytes after the call, or None)"""
+        m = np.ascontiguousarray(region_from_vox, dtype=np.float32).reshape(12)
+        if descs is None:
+            (d_desc, n), d_blocks = self.merge_gather(), None
+        else:
+            descs = np.ascontiguousarray(descs, dtype=T.DESC_DTYPE)
+            n = len(descs)
+            blocks = np.ascontiguousarray(blocks, dtype=T.VOXEL_DTYPE).reshape(n, T.SDF_BLOCK_VOXELS)
+            d_desc = DeviceBuffer.from_numpy(descs, self.stream) if n else DeviceBuffer(16)
+            d_blocks = DeviceBuffer.from_numpy(blocks, self.stream) if n else DeviceBuffer(8)
+        d_work = DeviceBuffer(self.L.vh_cut_work_bytes(n))
+        counts = (C.c_uint32 * len(T.CUT_COUNTS))()
+
+        def call(fl, d_out, d_staging, room):
+            rc = self.L.vh_cut_blocks(C.byref(self.hd), C.byref(self.hp), n, d_desc.ptr, d_blocks.ptr if d_blocks is not None else None, m.ctypes.data,
+                                      int(shape), int(fl), lock_token, d_work.ptr, d_out.ptr if d_out else None, d_staging.ptr if d_staging else None,
+                                      room, counts, self.stream)
+            out = {k: int(v) for k, v in zip(T.CUT_COUNTS, counts)}
+            out.update(code=rc, descs=np.zeros(0, T.DESC_DTYPE), voxels=np.zeros((0, T.SDF_BLOCK_VOXELS), T.VOXEL_DTYPE), staging_raw=None)
+            return out
+
+        if not (flags & T.CUT_LIFT) or (flags & T.CUT_COUNT_ONLY):
+            return call(flags, None, None, 0)
+        if staging_blocks is None:
+            staging_blocks = call(flags | T.CUT_COUNT_ONLY, None, None, 0)["lifted"]
+        room = int(staging_blocks)
+        d_out, d_staging = DeviceBuffer(16 * max(room, 1)), DeviceBuffer(8 * T.SDF_BLOCK_VOXELS * max(room, 1))
+        if poison is not None:
+            check(self.L.vh_memset(d_out.ptr, int(poison), d_out.nbytes, self.stream), "memset")
+            check(self.L.vh_memset(d_staging.ptr, int(poison), d_staging.nbytes, self.stream), "memset")
+        out = call(flags, d_out, d_staging, room)
+        out["staging_raw"] = (d_out.download(np.uint8, None, self.stream), d_staging.download(np.uint8, None, self.stream))
+        if out["code"] == 0:
+            out["descs"], out["voxels"] = _staged_list(d_out, d_staging, out["lifted"], self.stream)
+        return out
 
     def resample_blocks(self, src_vox_from_dst_vox, dst_vox_from_src_vox, slots_log2=None):
         """vh_merge_gather on this table, then vh_resample_blocks, count and fill: this scene sampled on another lattice

@@ -105,6 +105,14 @@ PROTOTYPES = {
     "vh_resample_work_bytes": (C.c_size_t, [C.c_uint32]),
     "vh_resample_blocks": (C.c_int, [P(T.HashData), P(T.HashParams), C.c_uint32, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, C.c_uint32, _VP, _VP]),
     "vh_scene_rep_merge_scene_transformed": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "vh_cut_region_transform": (C.c_int, [_VP, _VP, C.c_float, _VP]),
+    "vh_cut_work_bytes": (C.c_size_t, [C.c_uint32]),
+    "vh_cut_blocks": (C.c_int, [P(T.HashData), P(T.HashParams), C.c_uint32, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_int32, _VP, _VP, _VP, C.c_uint32,
+                                _VP, _VP]),
+    "vh_scene_rep_erase_region": (C.c_int, [_VP, P(T.CutRegion), _VP]),
+    "vh_scene_rep_crop_to_region": (C.c_int, [_VP, P(T.CutRegion), _VP]),
+    "vh_scene_rep_extract_region": (C.c_int, [_VP, P(T.CutRegion), _VP, _VP, C.c_uint32, _VP, _VP]),
+    "vh_scene_rep_move_region_to": (C.c_int, [_VP, _VP, P(T.CutRegion), _VP, _VP, _VP]),
     "vh_ray_cast_cast_rays": (C.c_int, [_VP, P(T.HashData), P(T.HashParams), _VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP]),
     "vh_scene_rep_integrate_ahead": (C.c_int, [_VP, _F16, P(T.DepthCameraData), P(T.DepthCameraParams), _VP, P(P(T.FrameJob))]),
     "vh_scene_rep_integrate_finish": (C.c_int, [_VP, P(T.DepthCameraData), P(T.DepthCameraParams)]),

@@ -575,6 +575,49 @@ class Reconstruction:
                 out.append(self.scene.mergeBlocks(descs, blocks, block_offset))
         return out
 
+    def _before_cut(self, what, modifies, others=()):
+        for r in (self,) + tuple(others):
+            if r.native is not None:
+                r.native.synchronize()
+        if modifies and self.chunk_grid is not None and self.chunk_grid.getStatistics()["blocks"] != 0:
+            raise ValueError(f"{what}: the chunk grid holds blocks on the host; stream them in first")
+
+    def eraseRegion(self, region):
+        """Takes the voxels inside a region (vhtypes.make_cut_region: a box or an ellipsoid in the world) out of the
+        model (not in the reference; DESIGN.md section 4 "Scene cut"; CUDASceneRepHashSDF.eraseRegion) -> the counts.
+        This scene must hold every block on the device: stream everything in first (ValueError otherwise).  A native
+        loop is synchronised first; compactify before the next ray cast."""
+        self._before_cut("eraseRegion", True)
+        return self.scene.eraseRegion(region)
+
+    def cropToRegion(self, region):
+        """eraseRegion of everything that is not inside the region: what is left is the region's content"""
+        self._before_cut("cropToRegion", True)
+        return self.scene.cropToRegion(region)
+
+    def extractRegion(self, region):
+        """Copies a region out and leaves the model as it is -> [the block lists, each a dict with "descs", "voxels" and
+        the counts]: the one of the blocks resident on the device (CUDASceneRepHashSDF.extractRegion) and, if this scene
+        streams and its chunk grid holds blocks on the host, the one of those (downloadHostBlocks through vh_cut_blocks'
+        list form).  A block is on the device or on the host, never both: the lists name no position twice."""
+        self._before_cut("extractRegion", False)
+        out = [self.scene.extractRegion(region)]
+        if self.chunk_grid is not None:
+            descs, blocks = self.chunk_grid.downloadHostBlocks()
+            if len(descs):
+                m = E.cut_region_transform(list(region.worldFromRegion), list(region.halfExtents), self.scene.getHashParams().m_virtualVoxelSize)
+                out.append(E.extract_from_block_list(descs, blocks, m, region.shape, stream=self.scene.stream))
+        return out
+
+    def moveRegionTo(self, other, region, block_offset=(0, 0, 0)):
+        """Moves a region's voxels into another reconstruction's model, shifted by whole blocks
+        (CUDASceneRepHashSDF.moveRegionTo: nothing is erased here unless everything arrived there) -> the counts.  Both
+        scenes must hold every block on the device (ValueError otherwise)."""
+        self._before_cut("moveRegionTo", True, (other,))
+        if other.chunk_grid is not None and other.chunk_grid.getStatistics()["blocks"] != 0:
+            raise ValueError("moveRegionTo: the destination's chunk grid holds blocks on the host; stream them in first")
+        return self.scene.moveRegionTo(other.scene, region, block_offset)
+
     def saveRecordedFramesToFile(self, filename=None):
         """RGBDSensor.cpp:339-389: poses from the run, time stamps and IMU records from the input"""
         if self.recorded is None:

@@ -170,6 +170,33 @@ MERGE_COUNTS = ("source_blocks", "present", "allocated", "left_out", "combined",
 # VH_RESAMPLE_*: bits of the resampled merge's status word, what vh_resample_blocks counts
 RESAMPLE_OUT_OF_RANGE, RESAMPLE_TABLE_FULL = 1, 2
 RESAMPLE_COUNTS = ("source_blocks", "candidates", "staged", "observed", "status")
+# VH_CUT_*: the scene cut's shapes, flags, bits of its status word, what vh_cut_blocks counts
+CUT_BOX, CUT_ELLIPSOID = 0, 1
+CUT_SELECT_OUTSIDE, CUT_LIFT, CUT_KEEP, CUT_COUNT_ONLY = 1, 2, 4, 8
+CUT_STAGING_SHORT, CUT_NOT_SETTLED = 1, 2
+CUT_COUNTS = ("blocks_in", "touched", "freed", "lifted", "voxels_erased", "voxels_lifted", "delete_passes", "unsettled", "status")
+
+
+class CutRegion(C.Structure):  # VhCutRegion
+    _fields_ = [("worldFromRegion", C.c_double * 16), ("halfExtents", C.c_float * 3), ("shape", C.c_uint32)]
+
+
+def make_cut_region(centre=(0.0, 0.0, 0.0), half_extents=(1.0, 1.0, 1.0), rotation=None, shape=CUT_BOX, world_from_region=None):
+    """a box or an ellipsoid in the world: its centre and half extents in metres, its axes the columns of `rotation`
+    (3x3, default the world's); or its whole frame as a rigid 4x4 world_from_region"""
+    import numpy as np
+    m = np.eye(4)
+    if world_from_region is not None:
+        m = np.asarray(world_from_region, np.float64).reshape(4, 4)
+    else:
+        if rotation is not None:
+            m[:3, :3] = np.asarray(rotation, np.float64).reshape(3, 3)
+        m[:3, 3] = centre
+    r = CutRegion()
+    r.worldFromRegion[:] = [float(v) for v in m.reshape(16)]
+    r.halfExtents[:] = [float(v) for v in half_extents]
+    r.shape = int(shape)
+    return r
 
 
 class MeshSmoothData(C.Structure):  # VhMeshSmoothData
