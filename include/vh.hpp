@@ -251,6 +251,24 @@ public:
     unsigned int extractRegion(const CutRegion& region, SDFBlockDesc* d_descs, Voxel* d_blocks, unsigned int capacity, CutCounts* counts = nullptr);
     void moveRegionTo(CUDASceneRepHashSDF& dst, const CutRegion& region, const int32_t blockOffset[3], CutCounts* counts = nullptr,
                       MergeCounts* merged = nullptr);
+    // Frame de-integration (DESIGN.md section 4 "Frame de-integration"; vh_api.h has the rule of vh_deintegrate_blocks):
+    // deintegrate takes the frame that integrate() fused at `rigidTransform` back out of the blocks resident in this
+    // scene's table -- same maps, same camera -- and frees the blocks left without an observed voxel.  It works on a copy
+    // of the hash parameters that carries the frame's pose: the scene's last rigid transform is not changed, nor is
+    // the number of integrated frames.  reintegrate is deintegrate(oldTransform) followed by integrate(newTransform),
+    // which counts as a frame.  Both block until done, leave the compactified list stale (compactify before the next
+    // ray cast) and throw VH_ERR_BAD_ARGUMENT, with nothing done, for a frame in flight, a null depth or colour map and
+    // an image without pixels.  *counts (may be nullptr) is filled before any throw.  The take-out is the inverse below
+    // the weight cap and without a starve pass in between, and never for colours in the running-average mode.  No
+    // block of this scene may be streamed out to a chunk grid (not checked here: such blocks are not seen).
+    struct DeintegrateCounts {
+        unsigned int c[VH_DEINT_NUM_COUNTS]; // indexed by VH_DEINT_*
+        unsigned int status() const { return c[VH_DEINT_STATUS]; }
+    };
+    void deintegrate(const vh::mat4f& rigidTransform, const DepthCameraData& depthCameraData, const DepthCameraParams& depthCameraParams,
+                     DeintegrateCounts* counts = nullptr);
+    void reintegrate(const vh::mat4f& oldTransform, const vh::mat4f& newTransform, const DepthCameraData& depthCameraData,
+                     const DepthCameraParams& depthCameraParams, const unsigned int* d_bitMask, DeintegrateCounts* counts = nullptr);
     const VhSceneOptions& getOptions() const { return m_options; }
     vhStream_t getStream() const { return m_stream; }
     int32_t nextLockToken(); // fresh bucket-lock epoch (replaces resetHashBucketMutexCUDA)

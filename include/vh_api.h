@@ -365,6 +365,42 @@ int vh_cut_blocks(const VhHashData* hd, const VhHashParams* hp, uint32_t n, cons
                   const float* m12, uint32_t shape, uint32_t flags, int32_t lockToken, uint32_t* d_work, VhSDFBlockDesc* d_outDescs,
                   VhVoxel* d_staging, uint32_t stagingBlocks, uint32_t* counts_out, vhStream_t stream);
 
+/* ---- frame de-integration (not in the reference; DESIGN.md section 4 "Frame de-integration") -----
+ * A fused depth frame taken back out of the table.  The frame is its float depth map and float4 colour map (cam), the
+ * camera (cp) and its pose, in hp->m_rigidTransform / m_rigidTransformInverse.
+ * The observation of voxel l of the block at pos, pi = 8 pos + (l & 7, (l >> 3) & 7, l >> 6) in wrapping int32, is what
+ * the integrate pass hands to combineVoxel for it, the same float32 operations in the same order: pf = inverse * (pi *
+ * voxelSize); the pixel (uint)cvt_rz((pf.x fx / pf.z + mx) + 0.5f), likewise y; it must lie inside the image; its colour
+ * c (MINF without a colour map) must have c.x != MINF and its depth d must be != MINF, < m_maxIntegrationDistance and
+ * have sdf = d - pf.z > -T, T = m_truncation + m_truncScale d.  Then o = sdf clamped to [-T, T], wo =
+ * uchar(fmaxf(m_integrationWeightSample * 1.5f * (1 - (d - depthMin) / (depthMax - depthMin)), 1)), co = uchar(255 c)
+ * per channel.  A voxel that fails a gate has no observation.  (As in the reference, a frame without a colour map puts
+ * nothing in, so it has no observation to take out.)
+ * The take-out of (o, co, wo) from the stored voxel (s, c, w):
+ *   no observation, w == 0 or wo == 0: unchanged, byte for byte;
+ *   wo >= w: 8 zero bytes;
+ *   else w' = w - wo, s' = (s (float)w - o (float)wo) / (float)w' in float32, in that order, IEEE division, no contraction;
+ *        colour with m_colorIntegration == VH_COLOR_RUNNING_AVERAGE: unchanged (a 50/50 average cannot be inverted);
+ *        otherwise per channel n = c w - co wo (signed), c' = clamp(floor((2 n + w') / (2 w')), 0, 255).
+ * A changed voxel whose w was m_integrationWeightMax is counted as at the cap: its weight was not the sum of what went
+ * in, and the take-out is not the inverse there (nor after a starve pass).
+ * vh_deintegrate_blocks, per block i of the n listed (d_descs from vh_merge_gather: the voxels are hd's pool at the
+ * descs' ptr): the block is processed iff isSDFBlockInCameraFrustumApprox holds for it at the frame's pose (the test
+ * compactify used when the frame went in); a block that is not processed is unchanged byte for byte.  A processed block
+ * left without a voxel of weight > 0 is freed whether or not the call changed it: zeroed whole, then, in a later
+ * launch, its entry removed by deleteHashEntryElement (the block id back on the heap, which holds all-zero blocks
+ * only).  Deletes that lose a bucket-lock race are run again, the bucket mutexes reset before every pass but the
+ * first, at most (freed + 8) times; a block pending then stays allocated, all zero (VH_DEINT_NOT_SETTLED, counted in
+ * VH_DEINT_UNSETTLED).  VH_DEINT_COUNT_ONLY classifies and writes nothing but d_work; the counts are those of the call
+ * without the flag.  d_work: vh_deintegrate_work_bytes(n) bytes of device scratch.  counts_out: VH_DEINT_NUM_COUNTS host
+ * words.  The maps must hold cp->m_imageWidth * m_imageHeight pixels.  One-shot and BLOCKING: the call reads a few
+ * words back after the apply launch and after every delete pass.  n = 0 launches nothing and reports zeros.  The
+ * caller compactifies before the next ray cast.  vh_time_launch_after: apply; then one launch per delete pass
+ * (vh_reset_bucket_mutex's launch between two passes is not a timed one and is not counted). */
+size_t vh_deintegrate_work_bytes(uint32_t n);
+int vh_deintegrate_blocks(const VhHashData* hd, const VhHashParams* hp, uint32_t n, const VhSDFBlockDesc* d_descs, const VhDepthCameraData* cam,
+                          const VhDepthCameraParams* cp, uint32_t flags, int32_t lockToken, uint32_t* d_work, uint32_t* counts_out, vhStream_t stream);
+
 /* ---- utilities that are not in the reference -------------------------------- */
 /* Synthetic analytic-sphere depth+colour frame,
  * generated on the device so benchmark inputs are HBM-resident. */
@@ -403,6 +439,9 @@ int vh_debug_check_refined_division(uint32_t n, uint32_t seed, uint32_t* d_misma
  * d_out: four words.  [0] mismatches with 1.0f / d (combineVoxel), [1] with the refined reciprocal of the pass's
  * certified blocks, [2] the first mismatching case as c0 | w0 << 8 | c1 << 16 | w1 << 24 (0xffffffff: none), [3] 0. */
 int vh_debug_check_weighted_colour(uint32_t* d_out, vhStream_t stream);
+/* The take-out rule of vh_deintegrate_blocks alone, on arrays of voxels: d_out[i] = d_observed[i] taken out of
+ * d_stored[i] under hp's colour mode (an observation of weight 0 is no observation).  No camera is needed. */
+int vh_debug_deintegrate_rule(const VhVoxel* d_stored, const VhVoxel* d_observed, VhVoxel* d_out, uint32_t n, const VhHashParams* hp, vhStream_t stream);
 /* measurement, not part of the path: every SIMD of the device runs `wavesPerSimd` waves (1..8), each a chain-free stream of
  * 32 * iters vector instructions (mode 0 v_fma_f32, 1 v_pk_fma_f32, 2 v_add_u32, 3 v_mul_lo_u32); per wave
  * {start, end in 100 MHz ticks, s_memtime ticks spent, HW_ID[19:0] | XCC_ID << 20} into d_stamps (4 words per wave, *numWaves waves: room for
@@ -490,6 +529,19 @@ int vh_scene_rep_extract_region(VhSceneRep* s, const VhCutRegion* region, VhSDFB
                                 uint32_t* numBlocks, uint32_t counts[VH_CUT_NUM_COUNTS]);
 int vh_scene_rep_move_region_to(VhSceneRep* src, VhSceneRep* dst, const VhCutRegion* region, const int32_t blockOffset[3],
                                 uint32_t cutCounts[VH_CUT_NUM_COUNTS], uint32_t mergeCounts[VH_MERGE_NUM_COUNTS]);
+/* getNumIntegratedFrames (include/vh.hpp): the frames integrate() has fused; a de-integration does not change it */
+int vh_scene_rep_get_num_integrated_frames(VhSceneRep* s, uint32_t* out);
+/* deintegrate / reintegrate (include/vh.hpp): vh_deintegrate_blocks on the blocks resident in the scene's table
+ * (vh_merge_gather), on the scene's stream, with a lock token of the scene's own and a copy of the hash parameters that
+ * carries the frame's pose: the scene's last rigid transform and its frame count are not changed.  cam / cp: the maps
+ * and the camera the frame was integrated with.  reintegrate is deintegrate at oldTransform followed by
+ * vh_scene_rep_integrate at newTransform (which counts as a frame; d_bitMask as there).  VH_ERR_BAD_ARGUMENT, and nothing
+ * done, for a frame in flight (integrateAhead without integrateFinish), a null depth or colour map and an image
+ * without pixels.  The counts are filled in either case.  Blocking; compactify before the next ray cast. */
+int vh_scene_rep_deintegrate(VhSceneRep* s, const float rigidTransform[16], const VhDepthCameraData* cam, const VhDepthCameraParams* cp,
+                             uint32_t counts[VH_DEINT_NUM_COUNTS]);
+int vh_scene_rep_reintegrate(VhSceneRep* s, const float oldTransform[16], const float newTransform[16], const VhDepthCameraData* cam,
+                             const VhDepthCameraParams* cp, const uint32_t* d_bitMask, uint32_t counts[VH_DEINT_NUM_COUNTS]);
 
 /* integrateAhead / integrateFinish: the two halves of integrate() (include/vh.hpp).  *job receives the frame's alloc +
  * compactify passes for vh_raycast_render_co (NULL when the scene's options rule a co-launch out); it belongs to the

@@ -204,6 +204,24 @@ typedef struct VhCutRegion {
     uint32_t shape;             /* VH_CUT_BOX / VH_CUT_ELLIPSOID */
 } VhCutRegion;
 
+/* Frame de-integration (vh_deintegrate_blocks): the call's flag, the bit of its status word, and what the call counts.
+ * VH_DEINT_NOT_SETTLED leaves a valid table in which some blocks that were to be freed are still allocated, all zero. */
+#define VH_DEINT_COUNT_ONLY 1u  /* classify and count; write nothing but the work buffer */
+#define VH_DEINT_NOT_SETTLED 1u /* freed blocks still lost their lock races at the bound on delete passes: they stay allocated, all zero */
+enum {
+    VH_DEINT_BLOCKS_IN = 0,      /* n */
+    VH_DEINT_PROCESSED = 1,      /* listed blocks in the frame's frustum */
+    VH_DEINT_CHANGED = 2,        /* processed blocks in which the take-out changed a voxel */
+    VH_DEINT_FREED = 3,          /* processed blocks left without a voxel of weight > 0, changed or not: their entries are removed */
+    VH_DEINT_VOXELS_CHANGED = 4, /* voxels of weight > 0 with an observation: the take-out applied (the next two are among them) */
+    VH_DEINT_VOXELS_RESET = 5,   /* ... whose observation weighs at least what the voxel does: 8 zero bytes now */
+    VH_DEINT_VOXELS_AT_CAP = 6,  /* ... whose weight was m_integrationWeightMax before the call: the take-out is not the inverse there */
+    VH_DEINT_DELETE_PASSES = 7,  /* delete passes run (depends on the order the deletes ran in) */
+    VH_DEINT_UNSETTLED = 8,      /* freed blocks still pending at the bound on passes (depends on that order too) */
+    VH_DEINT_STATUS = 9,
+    VH_DEINT_NUM_COUNTS = 10
+};
+
 /* DepthCameraData, DSC/DepthCameraUtil.h:17-159: the two image buffers the
  * path reads (the cudaArray/texture twins of the reference are not needed:
  * images are read with plain cached loads). */

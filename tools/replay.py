@@ -7,6 +7,7 @@ parameter file, optional mesh at the end) and prints one JSON line with the timi
                            [--mesh-smooth N [--mesh-smooth-lambda L] [--mesh-smooth-mu M] [--mesh-smooth-free-boundary]]]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
                            [--native [--batch N] [--native-tracking]] [--weighted-colour]
                            [--crop-box CX CY CZ HX HY HZ [RX RY RZ]] [--erase-box CX CY CZ HX HY HZ [RX RY RZ]]
+                           [--corrected-trajectory FILE]
 
 Without --sens the files named by s_binaryDumpSensorFile[i] in the parameter file are played.  The rendering keys
 (light, material, discontinuity thresholds, s_renderToFile, s_renderToFileDir) come from --params; --render-to switches
@@ -28,7 +29,13 @@ not a key of the parameter file; the JSON line names the rule as "colour_rule".
 --erase-box takes a box out of the model after the last frame and before --mesh (Reconstruction.eraseRegion), --crop-box
 everything but a box (cropToRegion): the centre and the half extents in metres and, optionally, a rotation vector in
 radians (axis times angle) that turns the box's axes.  The erase runs first when both are given.  With s_streamingEnabled
-the blocks on the host must be streamed in first: the tool says so and stops.  The JSON line has the counts as "cut"."""
+the blocks on the host must be streamed in first: the tool says so and stops.  The JSON line has the counts as "cut".
+
+--corrected-trajectory FILE: FILE holds one camera-to-world pose per frame as text, 16 numbers per line (4x4, row-major).
+After the replay a second pass over the recording takes every frame whose corrected pose differs from the pose it went in
+at back out of the model and integrates it again at the corrected one (Reconstruction.reintegrateCorrected; DESIGN.md
+section 4 "Frame de-integration" has what the take-out is worth), before any cut, mesh or record.  Not with
+s_streamingEnabled and not with --native.  The JSON line has the tally as "reintegrated"."""
 import argparse
 import json
 import os
@@ -79,6 +86,7 @@ def main():
     ap.add_argument("--native-tracking", action="store_true", help="--native: let the native loop track the camera (plain ICP, or RGB-D ICP with --rgbd-tracking) when the poses are not recorded")
     ap.add_argument("--crop-box", type=float, nargs="+", default=None, metavar="V", help="keep only a box of the model before --mesh: centre x y z, half extents x y z (metres) and optionally a rotation vector (radians)")
     ap.add_argument("--erase-box", type=float, nargs="+", default=None, metavar="V", help="take a box out of the model before --mesh: centre, half extents and optionally a rotation vector, as --crop-box")
+    ap.add_argument("--corrected-trajectory", default=None, metavar="FILE", help="after the replay, re-integrate every frame whose pose in FILE (one 4x4 row-major pose per frame, 16 numbers per line) differs from the pose it went in at")
     ap.add_argument("--weighted-colour", action="store_true", help="fuse colours weighted by the voxel weights instead of the reference's running 50/50 average")
     args = ap.parse_args()
     if args.mesh_normals and not args.indexed_mesh:
@@ -103,6 +111,8 @@ def main():
     for name, box in (("--crop-box", args.crop_box), ("--erase-box", args.erase_box)):
         if box is not None and (len(box) not in (6, 9) or not all(h > 0 for h in box[3:6])):
             ap.error(name + ": centre x y z, half extents x y z (> 0) and optionally a rotation vector x y z")
+    if args.corrected_trajectory and args.native:
+        ap.error("--corrected-trajectory: not with --native")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU (there is no CPU fallback)")
@@ -147,6 +157,16 @@ def main():
         out["render_to"] = bytes(rs.s_renderToFileDir).decode()
     if args.record:
         out["recorded"] = rec.saveRecordedFramesToFile(args.record)
+    if args.corrected_trajectory:
+        import numpy as np
+        poses = np.loadtxt(args.corrected_trajectory, dtype=np.float64, ndmin=2)
+        if poses.shape[1] != 16:
+            raise SystemExit("--corrected-trajectory: 16 numbers per line")
+        try:
+            out["reintegrated"] = rec.reintegrateCorrected(poses.reshape(-1, 4, 4))
+        except ValueError as e:
+            raise SystemExit(str(e))
+        out["blocks_after_reintegration"] = rec.scene.getNumOccupiedBlocks()
     cuts = {}
     for name, box, cut in (("erase", args.erase_box, rec.eraseRegion), ("crop", args.crop_box, rec.cropToRegion)):
         if box is not None:

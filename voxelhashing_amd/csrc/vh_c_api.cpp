@@ -189,6 +189,32 @@ int vh_scene_rep_move_region_to(VhSceneRep* src, VhSceneRep* dst, const VhCutReg
     std::memcpy(mergeCounts, m.c, sizeof(m.c));
     return rc;
 }
+int vh_scene_rep_get_num_integrated_frames(VhSceneRep* s, uint32_t* out)
+{
+    if (!s || !out) return VH_ERR_BAD_ARGUMENT;
+    *out = s->impl.getNumIntegratedFrames();
+    return VH_OK;
+}
+int vh_scene_rep_deintegrate(VhSceneRep* s, const float rigidTransform[16], const VhDepthCameraData* cam, const VhDepthCameraParams* cp,
+                             uint32_t counts[VH_DEINT_NUM_COUNTS])
+{
+    if (!s || !rigidTransform || !cam || !cp || !counts) return VH_ERR_BAD_ARGUMENT;
+    CUDASceneRepHashSDF::DeintegrateCounts c;
+    std::memset(&c, 0, sizeof(c));
+    const int rc = guarded([&] { s->impl.deintegrate(toMat(rigidTransform), *cam, *cp, &c); });
+    std::memcpy(counts, c.c, sizeof(c.c));
+    return rc;
+}
+int vh_scene_rep_reintegrate(VhSceneRep* s, const float oldTransform[16], const float newTransform[16], const VhDepthCameraData* cam,
+                             const VhDepthCameraParams* cp, const uint32_t* d_bitMask, uint32_t counts[VH_DEINT_NUM_COUNTS])
+{
+    if (!s || !oldTransform || !newTransform || !cam || !cp || !counts) return VH_ERR_BAD_ARGUMENT;
+    CUDASceneRepHashSDF::DeintegrateCounts c;
+    std::memset(&c, 0, sizeof(c));
+    const int rc = guarded([&] { s->impl.reintegrate(toMat(oldTransform), toMat(newTransform), *cam, *cp, d_bitMask, &c); });
+    std::memcpy(counts, c.c, sizeof(c.c));
+    return rc;
+}
 int vh_scene_rep_set_options(VhSceneRep* s, const VhSceneOptions* opt)
 {
     if (!s || !opt) return VH_ERR_BAD_ARGUMENT;

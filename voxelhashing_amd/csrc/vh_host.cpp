@@ -891,6 +891,44 @@ void CUDASceneRepHashSDF::moveRegionTo(CUDASceneRepHashSDF& dst, const CutRegion
     c.c[VH_CUT_VOXELS_LIFTED] = voxelsLifted;
 }
 
+// ---- frame de-integration (vh_deintegrate.hip; DESIGN.md section 4 "Frame de-integration")
+
+void CUDASceneRepHashSDF::deintegrate(const vh::mat4f& rigidTransform, const DepthCameraData& cam, const DepthCameraParams& cp, DeintegrateCounts* counts)
+{
+    DeintegrateCounts local;
+    DeintegrateCounts& c = counts ? *counts : local;
+    std::memset(&c, 0, sizeof(c));
+    if (m_aheadPending) throw vh::Error(VH_ERR_BAD_ARGUMENT, "deintegrate: between integrateAhead() and integrateFinish()");
+    if (!cam.d_depthData || !cam.d_colorData) throw vh::Error(VH_ERR_BAD_ARGUMENT, "deintegrate: null depth or colour map");
+    if (cp.m_imageWidth == 0 || cp.m_imageHeight == 0) throw vh::Error(VH_ERR_BAD_ARGUMENT, "deintegrate: an image without pixels");
+    // the frame's pose travels in a copy: the scene's last rigid transform stays
+    HashParams hp = m_hashParams;
+    std::memcpy(hp.m_rigidTransform, rigidTransform.m, sizeof(rigidTransform.m));
+    const vh::mat4f inv = rigidTransform.getInverse();
+    std::memcpy(hp.m_rigidTransformInverse, inv.m, sizeof(inv.m));
+    // the table's entries as a block list: at most one per block of the pool
+    const uint32_t capacity = m_hashParams.m_numSDFBlocks;
+    vh::DevicePtr<SDFBlockDesc> descs = vh::deviceAlloc<SDFBlockDesc>(capacity, "deintegrate block list");
+    vh::DevicePtr<uint32_t> counter = vh::deviceAlloc<uint32_t>(1, "deintegrate block count");
+    check(vh_merge_gather(&m_hashData, &m_hashParams, descs.get(), capacity, counter.get(), m_stream), "vh_merge_gather");
+    uint32_t n = 0;
+    check(vh_memcpy_d2h(&n, counter.get(), sizeof(n), m_stream), "deintegrate");
+    if (n > capacity) throw vh::Error(VH_ERR_BAD_ARGUMENT, "deintegrate: the table holds more entries than the pool has blocks");
+    if (n == 0) return;
+    vh::DevicePtr<unsigned char> work = vh::deviceAlloc<unsigned char>(vh_deintegrate_work_bytes(n), "deintegrate scratch");
+    const int32_t token = nextLockToken();
+    noteTableEdited(); // (as a stream-out: the compactified list is stale)
+    check(vh_deintegrate_blocks(&m_hashData, &hp, n, descs.get(), &cam, &cp, 0u, token, reinterpret_cast<uint32_t*>(work.get()), c.c, m_stream),
+          "vh_deintegrate_blocks");
+}
+
+void CUDASceneRepHashSDF::reintegrate(const vh::mat4f& oldTransform, const vh::mat4f& newTransform, const DepthCameraData& cam, const DepthCameraParams& cp,
+                                      const unsigned int* d_bitMask, DeintegrateCounts* counts)
+{
+    deintegrate(oldTransform, cam, cp, counts);
+    integrate(newTransform, cam, cp, d_bitMask);
+}
+
 void CUDASceneRepHashSDF::getTimings(double out[4])
 {
     m_timer->resolve((hipStream_t)m_stream);

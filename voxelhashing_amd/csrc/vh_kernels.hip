@@ -1475,7 +1475,8 @@ int vh_integrate(const VhHashData* hd, const VhHashParams* hp, const VhDepthCame
 {
     if (!hd || !hp || !cam || !cp || !cam->d_depthData) return VH_ERR_BAD_ARGUMENT;
     if (hp->m_numOccupiedBlocks == 0) return VH_OK; // DSC/CUDASceneRepHashSDF.cu:501
-    k_integrate<false><<<hp->m_numOccupiedBlocks, 256, 0, (hipStream_t)stream>>>(*hd, *hp, *cam, *cp, 0u, VH_LOCK_ENTRY, nullptr);
+    // (a timed launch: this kernel is the yardstick of tools/bench_deintegrate.py)
+    VH_LAUNCH_TIMED(k_integrate<false>, hp->m_numOccupiedBlocks, 256, (hipStream_t)stream, *hd, *hp, *cam, *cp, 0u, VH_LOCK_ENTRY, nullptr);
     return vh_last_launch_error();
 }
 

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import canonical
 from . import vhtypes as T
-from .lib import DeviceBuffer, check, download, f16, load
+from .lib import DeviceBuffer, VhError, check, download, f16, load
 
 
 def _copy_struct(s):
@@ -167,6 +167,43 @@ def extract_from_block_list(descs, blocks, region_from_vox, shape, select_outsid
     check(L.vh_cut_blocks(None, C.byref(hp), n, d_desc.ptr, d_blocks.ptr, m.ctypes.data, int(shape), flags, 0, d_work.ptr, d_out.ptr, d_staging.ptr, room,
                           counts, stream), "vh_cut_blocks")
     return _cut_result(0, counts, "vh_cut_blocks", dict(zip(("descs", "voxels"), _staged_list(d_out, d_staging, room, stream))))
+
+
+def _deint_result(code, counts, what):
+    """the counts by name (vhtypes.DEINT_COUNTS); an error code raises VhError with .counts"""
+    out = {k: int(v) for k, v in zip(T.DEINT_COUNTS, counts)}
+    if code != 0:
+        try:
+            check(code, what)
+        except Exception as e:
+            e.counts = out
+            raise
+    return out
+
+
+def _frame_data(frame, cp, what):
+    """a DepthFrame's DepthCameraData, refused (VH_ERR_BAD_ARGUMENT) when the frame's image size is not cp's"""
+    if not isinstance(frame, DepthFrame):
+        return frame
+    if (frame.cp.m_imageWidth, frame.cp.m_imageHeight) != (cp.m_imageWidth, cp.m_imageHeight):
+        e = VhError(4, f"{what}: the frame is {frame.cp.m_imageWidth}x{frame.cp.m_imageHeight}, the camera {cp.m_imageWidth}x{cp.m_imageHeight}")
+        e.counts = {k: 0 for k in T.DEINT_COUNTS}
+        raise e
+    return frame.data
+
+
+def deintegrate_rule(stored, observed, hp, stream=None):
+    """vh_debug_deintegrate_rule: the take-out rule of the frame de-integration on two VOXEL_DTYPE arrays of one shape
+    (an observation of weight 0 is no observation) -> the voxels afterwards"""
+    stored = np.ascontiguousarray(stored, dtype=T.VOXEL_DTYPE)
+    observed = np.ascontiguousarray(observed, dtype=T.VOXEL_DTYPE)
+    assert stored.shape == observed.shape
+    n = stored.size
+    if n == 0:
+        return stored.copy()
+    d_s, d_o, d_out = DeviceBuffer.from_numpy(stored, stream), DeviceBuffer.from_numpy(observed, stream), DeviceBuffer(8 * n)
+    check(load().vh_debug_deintegrate_rule(d_s.ptr, d_o.ptr, d_out.ptr, n, C.byref(hp), stream), "vh_debug_deintegrate_rule")
+    return d_out.download(T.VOXEL_DTYPE, n, stream).reshape(stored.shape)
 
 
 class CUDASceneRepHashSDF:
@@ -354,6 +391,32 @@ class CUDASceneRepHashSDF:
         off = (C.c_int32 * 3)(*[int(v) for v in block_offset])
         rc = self.L.vh_scene_rep_move_region_to(self.handle, dst.handle, C.byref(region), off, counts, merged)
         return _cut_result(rc, counts, "CUDASceneRepHashSDF::moveRegionTo", {"merge": {k: int(v) for k, v in zip(T.MERGE_COUNTS, merged)}})
+
+    # ---- frame de-integration (DESIGN.md section 4 "Frame de-integration") ------------------------------------------
+    def deintegrate(self, rigidTransform, depthCameraData, depthCameraParams):
+        """Takes the frame that integrate() fused at `rigidTransform` -- the same maps, the same camera -- back out of
+        the blocks resident in the table and frees the blocks left without an observed voxel (vh_api.h has the rule of
+        vh_deintegrate_blocks) -> the counts by name (vhtypes.DEINT_COUNTS).  The scene's last rigid transform and its
+        frame count stay.  Raises VhError (VH_ERR_BAD_ARGUMENT, nothing done) for a frame in flight, a null map and a
+        frame whose image size is not the camera's.  Compactify before the next ray cast."""
+        what = "CUDASceneRepHashSDF::deintegrate"
+        data = _frame_data(depthCameraData, depthCameraParams, what)
+        counts = (C.c_uint32 * len(T.DEINT_COUNTS))()
+        return _deint_result(self.L.vh_scene_rep_deintegrate(self.handle, f16(rigidTransform), C.byref(data), C.byref(depthCameraParams), counts), counts, what)
+
+    def getNumIntegratedFrames(self):
+        """the frames integrate() has fused; a de-integration does not change it"""
+        n = C.c_uint32()
+        check(self.L.vh_scene_rep_get_num_integrated_frames(self.handle, C.byref(n)), "getNumIntegratedFrames")
+        return n.value
+
+    def reintegrate(self, oldTransform, newTransform, depthCameraData, depthCameraParams, d_bitMask=None):
+        """deintegrate(oldTransform) followed by integrate(newTransform), which counts as a frame -> the take-out's counts"""
+        what = "CUDASceneRepHashSDF::reintegrate"
+        data = _frame_data(depthCameraData, depthCameraParams, what)
+        counts = (C.c_uint32 * len(T.DEINT_COUNTS))()
+        return _deint_result(self.L.vh_scene_rep_reintegrate(self.handle, f16(oldTransform), f16(newTransform), C.byref(data), C.byref(depthCameraParams),
+                                                             d_bitMask, counts), counts, what)
 
     def getState(self):
         out = (C.c_uint32 * T.STATE_WORDS)()
@@ -943,6 +1006,22 @@ class LauncherScene:
         out["staging_raw"] = (d_out.download(np.uint8, None, self.stream), d_staging.download(np.uint8, None, self.stream))
         if out["code"] == 0:
             out["descs"], out["voxels"] = _staged_list(d_out, d_staging, out["lifted"], self.stream)
+        return out
+
+    def deintegrate_blocks(self, frame, cp, transform, inverse, lock_token, flags=0):
+        """vh_merge_gather on this table, then vh_deintegrate_blocks with the frame's pose and its inverse in a copy of the
+        hash parameters -> the counts by name (vhtypes.DEINT_COUNTS) plus "code" (the call's return code: nothing raises)"""
+        d_desc, n = self.merge_gather()
+        hp = T.HashParams()
+        C.memmove(C.byref(hp), C.byref(self.hp), C.sizeof(hp))
+        hp.m_rigidTransform = T.mat16(transform)
+        hp.m_rigidTransformInverse = T.mat16(inverse)
+        d_work = DeviceBuffer(self.L.vh_deintegrate_work_bytes(n))
+        counts = (C.c_uint32 * len(T.DEINT_COUNTS))()
+        rc = self.L.vh_deintegrate_blocks(C.byref(self.hd), C.byref(hp), n, d_desc.ptr, C.byref(frame.data), C.byref(cp), int(flags), lock_token, d_work.ptr,
+                                          counts, self.stream)
+        out = {k: int(v) for k, v in zip(T.DEINT_COUNTS, counts)}
+        out["code"] = rc
         return out
 
     def resample_blocks(self, src_vox_from_dst_vox, dst_vox_from_src_vox, slots_log2=None):

@@ -113,6 +113,13 @@ PROTOTYPES = {
     "vh_scene_rep_crop_to_region": (C.c_int, [_VP, P(T.CutRegion), _VP]),
     "vh_scene_rep_extract_region": (C.c_int, [_VP, P(T.CutRegion), _VP, _VP, C.c_uint32, _VP, _VP]),
     "vh_scene_rep_move_region_to": (C.c_int, [_VP, _VP, P(T.CutRegion), _VP, _VP, _VP]),
+    "vh_deintegrate_work_bytes": (C.c_size_t, [C.c_uint32]),
+    "vh_deintegrate_blocks": (C.c_int, [P(T.HashData), P(T.HashParams), C.c_uint32, _VP, P(T.DepthCameraData), P(T.DepthCameraParams), C.c_uint32, C.c_int32,
+                                        _VP, _VP, _VP]),
+    "vh_debug_deintegrate_rule": (C.c_int, [_VP, _VP, _VP, C.c_uint32, P(T.HashParams), _VP]),
+    "vh_scene_rep_get_num_integrated_frames": (C.c_int, [_VP, _VP]),
+    "vh_scene_rep_deintegrate": (C.c_int, [_VP, _F16, P(T.DepthCameraData), P(T.DepthCameraParams), _VP]),
+    "vh_scene_rep_reintegrate": (C.c_int, [_VP, _F16, _F16, P(T.DepthCameraData), P(T.DepthCameraParams), _VP, _VP]),
     "vh_ray_cast_cast_rays": (C.c_int, [_VP, P(T.HashData), P(T.HashParams), _VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP]),
     "vh_scene_rep_integrate_ahead": (C.c_int, [_VP, _F16, P(T.DepthCameraData), P(T.DepthCameraParams), _VP, P(P(T.FrameJob))]),
     "vh_scene_rep_integrate_finish": (C.c_int, [_VP, P(T.DepthCameraData), P(T.DepthCameraParams)]),

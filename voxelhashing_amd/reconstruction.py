@@ -291,6 +291,7 @@ class Reconstruction:
         self.native = None     # the native frame loop, once run_native has played frames
         self.frame_number = 0  # g_RGBDAdapter.getFrameNumber()
         self.trajectory = []   # the pose every processed frame was integrated at (recordTrajectory)
+        self.frame_poses = []  # per frame read: the pose it was integrated at, or None (invalid, lost): for reintegrateCorrected
         self.recorded = None
         self.lost_frames = 0
         self.render_state = render_state
@@ -415,6 +416,7 @@ class Reconstruction:
         E.write_png_rgba8(os.path.join(dirs["input_depth"], name), depth_image_rgba8(depth))
 
     def _done(self, pose):
+        self.frame_poses.append(pose if pose is not None and self.gas.s_integrationEnabled else None)
         if self.gas.s_recordData:
             self.trajectory.append(pose if pose is not None else np.full((4, 4), MINF, dtype=np.float32))
         elif pose is not None:
@@ -617,6 +619,57 @@ class Reconstruction:
         if other.chunk_grid is not None and other.chunk_grid.getStatistics()["blocks"] != 0:
             raise ValueError("moveRegionTo: the destination's chunk grid holds blocks on the host; stream them in first")
         return self.scene.moveRegionTo(other.scene, region, block_offset)
+
+    def deintegrateFrame(self, depth, color, pose):
+        """Takes a frame back out of the model (not in the reference; DESIGN.md section 4 "Frame de-integration";
+        CUDASceneRepHashSDF.deintegrate) -> the counts.  depth, color: the frame as the reader gave it when it was
+        integrated at `pose`; it goes through the sensor's pre-processing again, so that the maps are the ones that
+        were integrated (the sensor's maps hold this frame afterwards).  This scene must hold every block on the device:
+        stream everything in first (ValueError otherwise).  A native loop is synchronised first; compactify before the
+        next ray cast.  The take-out is the inverse below the weight cap and without a starve pass in between."""
+        self._before_cut("deintegrateFrame", True)
+        self.sensor.process(depth, color)
+        return self.scene.deintegrate(pose, self.frame_data, self.cp)
+
+    def reintegrateFrame(self, depth, color, old_pose, new_pose):
+        """deintegrateFrame at old_pose, then the frame integrated again at new_pose (CUDASceneRepHashSDF.reintegrate;
+        counts as a frame) -> the take-out's counts"""
+        self._before_cut("reintegrateFrame", True)
+        self.sensor.process(depth, color)
+        return self.scene.reintegrate(old_pose, new_pose, self.frame_data, self.cp)
+
+    def reintegrateCorrected(self, corrected_poses):
+        """A second pass over the recording with a corrected trajectory (one 4x4 camera-to-world pose per frame read, in
+        order): every frame that was integrated and whose corrected pose differs from the pose it went in at is taken
+        out and integrated again at the corrected one (reintegrateFrame) -> dict(frames, reintegrated, voxels_changed,
+        voxels_reset, voxels_at_cap, blocks_freed).  For a sequence played by the Python loop without streaming
+        (ValueError otherwise)."""
+        if self.native is not None:
+            raise ValueError("reintegrateCorrected: this sequence was played by the native loop")
+        if self.chunk_grid is not None:
+            raise ValueError("reintegrateCorrected: not with streaming")
+        corrected = np.asarray(corrected_poses, dtype=np.float32).reshape(-1, 4, 4)
+        out = dict(frames=len(self.frame_poses), reintegrated=0, voxels_changed=0, voxels_reset=0, voxels_at_cap=0, blocks_freed=0)
+        files = iter(self.sens_files)
+        reader = SD.SensorDataReader(next(files))
+        try:
+            for i, pose in enumerate(self.frame_poses):
+                got = reader.processDepth()
+                while got is None:
+                    reader.close()
+                    reader = SD.SensorDataReader(next(files))
+                    got = reader.processDepth()
+                if pose is None or i >= len(corrected) or np.array_equal(corrected[i], np.asarray(pose, np.float32).reshape(4, 4)):
+                    continue
+                c = self.reintegrateFrame(got[0], got[1], pose, corrected[i])
+                self.frame_poses[i] = corrected[i].copy()
+                out["reintegrated"] += 1
+                out["blocks_freed"] += c["freed"]
+                for k in ("voxels_changed", "voxels_reset", "voxels_at_cap"):
+                    out[k] += c[k]
+        finally:
+            reader.close()
+        return out
 
     def saveRecordedFramesToFile(self, filename=None):
         """RGBDSensor.cpp:339-389: poses from the run, time stamps and IMU records from the input"""

@@ -176,6 +176,10 @@ CUT_SELECT_OUTSIDE, CUT_LIFT, CUT_KEEP, CUT_COUNT_ONLY = 1, 2, 4, 8
 CUT_STAGING_SHORT, CUT_NOT_SETTLED = 1, 2
 CUT_COUNTS = ("blocks_in", "touched", "freed", "lifted", "voxels_erased", "voxels_lifted", "delete_passes", "unsettled", "status")
 
+# VH_DEINT_*: the frame de-integration's flag, the bit of its status word, what vh_deintegrate_blocks counts
+DEINT_COUNT_ONLY = 1
+DEINT_NOT_SETTLED = 1
+DEINT_COUNTS = ("blocks_in", "processed", "changed", "freed", "voxels_changed", "voxels_reset", "voxels_at_cap", "delete_passes", "unsettled", "status")
 
 class CutRegion(C.Structure):  # VhCutRegion
     _fields_ = [("worldFromRegion", C.c_double * 16), ("halfExtents", C.c_float * 3), ("shape", C.c_uint32)]
