@@ -275,6 +275,8 @@ public:
     void getState(uint32_t out[VH_STATE_WORDS]);
     void getTimings(double out[4]); // ms: alloc, compactify, integrate(+gc), frames
     unsigned int getNumIntegratedFrames() const { return m_numIntegratedFrames; }
+    // between integrateAhead() and integrateFinish(): what the editing calls above refuse, for a caller that must refuse too
+    bool frameInFlight() const { return m_aheadPending != 0; }
 
 private:
     void create(const HashParams& params);
@@ -880,6 +882,25 @@ public:
     void getIndexedSmoothStats(unsigned int out[6]) const { for (int i = 0; i < 6; i++) out[i] = m_indexed.smoothStats[i]; }
     void downloadSources(VhTriangleSource* out, unsigned int n);               // source records of the last indexed extraction
 
+    // Not in the reference: the live mesh ("Live mesh").  Between liveBegin and liveEnd the object's
+    // triangle buffer and source records are a cache that liveUpdate brings to exactly what the sourced pass 2 of
+    // extractIsoSurfaceIndexed without a box would give on the table now (as a set; buffer order is free), re-extracting
+    // only the resident blocks within one block of a block that changed since the last update (vh_live_mesh_update).
+    // liveBegin empties the mesh buffer and the cache; every extraction on the object is then refused with
+    // VH_ERR_BAD_ARGUMENT, with nothing done, until liveEnd.  liveUpdate fills counts (may be null) with the
+    // VH_LIVE_NUM_COUNTS counts and the status word; it throws VH_ERR_STAGING_OVERFLOW when the cache overflowed and
+    // VH_ERR_BAD_ARGUMENT when a block is out of range or the table malformed -- the cache is then invalid and the next
+    // update starts from nothing -- and VH_ERR_BAD_ARGUMENT without liveBegin, with boxEnabled, or for hash parameters
+    // other than the earlier updates', the cache then as it was.  liveInvalidate makes the next update a full one (the
+    // digests can collide).  liveIndexed welds the cache and runs the indexed passes that are on, as
+    // extractIsoSurfaceIndexed does after its pass 2: it REPLACES the mesh buffer and marks it welded; the cache stays.
+    void liveBegin();
+    void liveUpdate(const HashData& hashData, const HashParams& hashParams, unsigned int counts[VH_LIVE_NUM_COUNTS + 1] = nullptr, bool boxEnabled = false);
+    void liveInvalidate();
+    void liveIndexed();
+    void liveEnd();
+    bool isLive() const { return m_live; }
+
     const vh::MeshData& getMeshData() const { return m_meshData; }
     const MarchingCubesData& getMarchingCubesData() const { return m_data; }
     unsigned int getNumTriangles();       // of the last extraction (blocks); may exceed m_maxNumTriangles on overflow
@@ -944,6 +965,15 @@ private:
     // the welded mesh on the device (m_accum's, or m_weld's) through the passes that are on -- clustering, smoothing, normals,
     // components, at the scales of that voxel size -- into the mesh buffer; then its counts and marks
     void readBackIndexed(unsigned int numVertices, unsigned int numFaces, bool accumulated, float voxelSize);
+    // the one-shot weld of the nTriangles triangles and records in the buffers, then readBackIndexed
+    void weldAndReadBack(unsigned int nTriangles, float voxelSize);
+    // live mesh: the buffers are made by the first liveBegin
+    bool m_live = false, m_liveValid = false;   // between liveBegin and liveEnd; the last update ended without a status
+    float m_liveVoxelSize = 0.0f;               // of the last update: liveIndexed's scale
+    VhLiveMeshData m_liveData;                  // from vh_live_mesh_data_alloc; m_liveOwner gives it back
+    struct LiveFree { void operator()(VhLiveMeshData* d) const noexcept; };
+    std::unique_ptr<VhLiveMeshData, LiveFree> m_liveOwner;
+    void refuseWhileLive(const char* what) const;
 };
 
 

@@ -61,7 +61,9 @@ int vh_time_next_launch(void* startEvent, void* stopEvent);
  * vh_mesh_weld_accum_components the launches of vh_mesh_components, then those of vh_mesh_components_filter;
  * vh_mesh_cluster and vh_mesh_weld_accum_cluster insert, faces, number, emit (insert and number alone without faces);
  * vh_mesh_smooth and vh_mesh_weld_accum_smooth edges, degree, prepare, then gather and step per half step (two half
- * steps an iteration), finish: 4 N + 4 launches (prepare and finish alone without faces). */
+ * steps an iteration), finish: 4 N + 4 launches (prepare and finish alone without faces);
+ * vh_live_mesh_update digest, vanished, dilate, then drop (when something changed and the cache held triangles) and
+ * pass 2 (when there is a block to re-mesh); vh_live_mesh_digest one kernel. */
 int vh_time_launch_after(uint32_t skip, void* startEvent, void* stopEvent);
 int vh_stream_create(vhStream_t* out);   /* a non-blocking HIP stream, for FFI users without a HIP binding */
 int vh_stream_destroy(vhStream_t stream);
@@ -531,6 +533,9 @@ int vh_scene_rep_move_region_to(VhSceneRep* src, VhSceneRep* dst, const VhCutReg
                                 uint32_t cutCounts[VH_CUT_NUM_COUNTS], uint32_t mergeCounts[VH_MERGE_NUM_COUNTS]);
 /* getNumIntegratedFrames (include/vh.hpp): the frames integrate() has fused; a de-integration does not change it */
 int vh_scene_rep_get_num_integrated_frames(VhSceneRep* s, uint32_t* out);
+/* *out = 1 between vh_scene_rep_integrate_ahead and vh_scene_rep_integrate_finish (a frame in flight: what merge, cut and
+ * de-integration refuse), else 0 */
+int vh_scene_rep_frame_in_flight(VhSceneRep* s, int* out);
 /* deintegrate / reintegrate (include/vh.hpp): vh_deintegrate_blocks on the blocks resident in the scene's table
  * (vh_merge_gather), on the scene's stream, with a lock token of the scene's own and a copy of the hash parameters that
  * carries the frame's pose: the scene's last rigid transform and its frame count are not changed.  cam / cp: the maps
@@ -893,6 +898,40 @@ int vh_extract_iso_surface_pass2(const VhHashData* hd, const VhHashParams* hp, c
 int vh_extract_iso_surface_pass2_sourced(const VhHashData* hd, const VhHashParams* hp, const VhMarchingCubesData* data,
                                          VhTriangleSource* d_sources, uint32_t numOccupiedBlocks, vhStream_t stream);
 
+/* ---- live mesh: the sourced soup kept on the device and brought up to date (csrc/vh_live_mesh.hip; DESIGN.md section 4,
+ * "Live mesh"; not in the reference).  The cache is data->d_triangles with the records *d_sources beside it and
+ * data->d_numTriangles its count; one update makes it, as a set of (triangle, record) pairs, what reset, pass 1 and the
+ * sourced pass 2 without a box would give on the same table, and runs pass 2 only over the resident blocks within one
+ * block of a block whose voxels, position or presence changed since the last update.  What changed is found from the
+ * table and the pool alone, by a 64-bit digest per block (vh_live_mesh_digest): a changed block is missed only where
+ * two contents of one block share a digest; vh_live_mesh_reset makes the next update a full one.
+ * Buffers for a pool of numSDFBlocks blocks (below 2^22) and a cache of maxNumTriangles: 64 B per block (record, two
+ * positions, mark, list entry) and 88 B per triangle for the spare pair. */
+int vh_live_mesh_data_alloc(VhLiveMeshData* live, uint32_t numSDFBlocks, uint32_t maxNumTriangles);
+void vh_live_mesh_data_free(VhLiveMeshData* live);
+/* invalidate: forgets every record and the cache, so that the next update re-extracts everything.  Asynchronous. */
+int vh_live_mesh_reset(VhLiveMeshData* live, vhStream_t stream);
+/* One update.  Waits once for the device, for the size of pass 2's grid.
+ *   data       its d_params must hold the thresholds of the earlier updates, m_boxEnabled 0 and the m_maxNumTriangles of
+ *              `live`; its block list and its counters are overwritten.  data->d_triangles and *d_sources are rewritten to
+ *              name the buffers that hold the cache afterwards: the drop pass compacts into live's spare pair, which
+ *              then changes places with them (all four are allocations of the same size, freed by whoever holds them)
+ *   live       from vh_live_mesh_data_alloc with hp->m_numSDFBlocks and that m_maxNumTriangles
+ * VH_ERR_BAD_ARGUMENT, with nothing launched and the cache as it was, when hp's bucket count, list limit or voxel size
+ * differ from those of the updates since the last reset.  What the device finds -- an overflow, a block out of range --
+ * is a status that vh_live_mesh_get_counts reports. */
+int vh_live_mesh_update(const VhHashData* hd, const VhHashParams* hp, VhMarchingCubesData* data, VhTriangleSource** d_sources, VhLiveMeshData* live,
+                        vhStream_t stream);
+/* Waits for the update and reads the VH_LIVE_NUM_COUNTS counts and, in out[VH_LIVE_NUM_COUNTS], the status.  out is
+ * filled whenever the copy succeeded; the return value restates the status: VH_ERR_STAGING_OVERFLOW for
+ * VH_LIVE_OVERFLOW, VH_ERR_BAD_ARGUMENT for VH_LIVE_RANGE and VH_LIVE_BAD_TABLE.  After a status the cache and every
+ * record are invalid (the device has seen to it): the next update starts from nothing. */
+int vh_live_mesh_get_counts(const VhLiveMeshData* live, uint32_t out[9], vhStream_t stream);
+/* The digest alone: d_out[i] for the block of hash entry d_entryIndices[i] (device arrays of n), 0 for a free entry or an
+ * index outside the table.  With w_j the 8 bytes of voxel j (0 .. 511, memory order) as a little-endian 64-bit word:
+ * the sum over j of fmix64(w_j + (j + 1) * 0x9E3779B97F4A7C15) modulo 2^64, fmix64 the finaliser of MurmurHash3. */
+int vh_live_mesh_digest(const VhHashData* hd, const VhHashParams* hp, const uint32_t* d_entryIndices, uint32_t n, uint64_t* d_out, vhStream_t stream);
+
 /* ---- indexed mesh: the soup welded on the device (csrc/vh_mesh.hip; DESIGN.md section 4, "Indexed mesh") -----------
  * The key a vertex is welded under: three 20-bit lattice coordinates biased by 2^19 (x in bits 0-19, y 20-39, z 40-59)
  * and a code in bits 60-61 (the lattice edge's axis, or 3 for a lattice point); bits 62-63 are 0.
@@ -1143,6 +1182,20 @@ int vh_marching_cubes_begin_indexed(VhMarchingCubes* mc);
 int vh_marching_cubes_append_indexed(VhMarchingCubes* mc, const VhHashData* hd, const VhHashParams* hp, const float minCorner[3],
                                      const float maxCorner[3], int boxEnabled);
 int vh_marching_cubes_finish_indexed(VhMarchingCubes* mc);
+/* The live mesh on the object (not in the reference; liveBegin ... liveEnd of include/vh.hpp).  Between live_begin and
+ * live_end the object's triangle buffer and its source records are the cache of vh_live_mesh_update: get_counts,
+ * download_triangles and download_sources read it, and every extraction is refused with VH_ERR_BAD_ARGUMENT, with nothing
+ * done.  live_update brings the cache up to date with the table and fills counts_out (may be NULL) with the
+ * VH_LIVE_NUM_COUNTS counts and the status; VH_ERR_STAGING_OVERFLOW / VH_ERR_BAD_ARGUMENT as vh_live_mesh_get_counts,
+ * the cache then invalid until the next update; VH_ERR_BAD_ARGUMENT without live_begin, with boxEnabled, or for hash
+ * parameters other than the earlier updates', the cache then as it was.  live_invalidate makes the next update a full
+ * one.  live_indexed welds the cache and runs the passes that are on, as extract_iso_surface_indexed does after its
+ * pass 2, and REPLACES the host mesh; VH_ERR_BAD_ARGUMENT when the cache is not valid. */
+int vh_marching_cubes_live_begin(VhMarchingCubes* mc);
+int vh_marching_cubes_live_update(VhMarchingCubes* mc, const VhHashData* hd, const VhHashParams* hp, int boxEnabled, uint32_t counts_out[9]);
+int vh_marching_cubes_live_invalidate(VhMarchingCubes* mc);
+int vh_marching_cubes_live_indexed(VhMarchingCubes* mc);
+int vh_marching_cubes_live_end(VhMarchingCubes* mc);
 /* The walk of vh_marching_cubes_extract_iso_surface_chunk_grid with the same boxes, every chunk appended to one
  * accumulation: the indexed mesh of a streamed scene.  When a chunk fails (VH_ERR_STAGING_OVERFLOW, VH_ERR_BAD_ARGUMENT
  * as above) the scene is streamed back in around camPos and the streaming thread restarted as at the normal end, the

@@ -421,6 +421,49 @@ enum {
 /* appends between two vh_mesh_weld_accum_begin: a bid carries the append's ordinal above the rank and the soup index */
 #define VH_WELD_ACCUM_MAX_APPENDS (1u << 28)
 
+/* ---- live mesh (not in the reference; DESIGN.md section 4, "Live mesh") ----
+ * status word of an update (vh_live_mesh_get_counts: out[VH_LIVE_NUM_COUNTS]); any bit leaves the cache and every record
+ * invalid, so that the next update starts from nothing */
+#define VH_LIVE_OVERFLOW 1u  /* more triangles than m_maxNumTriangles */
+#define VH_LIVE_RANGE 2u     /* a resident block outside [-2^16, 2^16) in a coordinate: voxels outside [-2^19, 2^19) */
+#define VH_LIVE_BAD_TABLE 4u /* an entry whose ptr names no block of the pool, or two entries with one block */
+/* what an update counts */
+enum {
+    VH_LIVE_VISITED = 0,  /* resident entries */
+    VH_LIVE_CHANGED = 1,  /* of them: no valid record, another position than the record's, or another digest */
+    VH_LIVE_VANISHED = 2, /* positions that a valid record held and no longer holds: moved ids and ids not visited */
+    VH_LIVE_REMESHED = 3, /* |R|: resident blocks within Chebyshev distance 1 of a changed or vanished position */
+    VH_LIVE_DROPPED = 4,  /* cached triangles whose owner is not resident or lies in R */
+    VH_LIVE_KEPT = 5,
+    VH_LIVE_ADDED = 6,    /* triangles of the sourced pass 2 over R */
+    VH_LIVE_TOTAL = 7,    /* kept + added */
+    VH_LIVE_NUM_COUNTS = 8
+};
+/* one per heap block id (ptr / 512); epoch 0 = invalid.  24 B. */
+typedef struct VhLiveMeshRecord {
+    int32_t pos[3];
+    uint32_t epoch;
+    uint64_t digest;
+} VhLiveMeshRecord;
+/* Device buffers of the live mesh (vh_live_mesh_data_alloc) and, in the m_ fields, what the host remembers between
+ * updates.  The cache itself is the VhMarchingCubesData's d_triangles and the records beside it; the spare pair is what
+ * the drop pass compacts into, and changes places with them. */
+typedef struct VhLiveMeshData {
+    VhLiveMeshRecord* d_records;      /* m_numSDFBlocks */
+    int32_t* d_positions;             /* C: {x, y, z, tag} per changed (0), moved-from (1) or abandoned (2) position, 2 m_numSDFBlocks of them */
+    uint32_t* d_marks;                /* per heap block id: the epoch of the last update that had the block in R */
+    uint32_t* d_remesh;               /* R: hash entry indices, m_numSDFBlocks */
+    VhTriangle* d_spareTriangles;     /* m_maxNumTriangles */
+    VhTriangleSource* d_spareSources; /* m_maxNumTriangles */
+    uint32_t* d_counts;               /* 16 words: the VH_LIVE_NUM_COUNTS counts, the status, |C|, the triangles that went in */
+    uint32_t m_numSDFBlocks, m_maxNumTriangles;
+    uint32_t m_epoch;                 /* of the last update */
+    uint32_t m_fresh;                 /* no update since the allocation or the last reset */
+    uint32_t m_hashNumBuckets, m_hashMaxCollisionLinkedListSize; /* of the updates since then */
+    float m_virtualVoxelSize;
+    uint32_t m_pad;
+} VhLiveMeshData;
+
 /* The five GlobalAppState flags the reference host classes read
  * (DSC/CUDASceneRepHashSDF.h:249,251,329,331; DSC/CUDASceneRepChunkGrid.cpp:13). */
 typedef struct VhSceneOptions {

@@ -4,7 +4,7 @@ parameter file, optional mesh at the end) and prints one JSON line with the timi
 
     python tools/replay.py --params zParameters.txt [--tracking zParametersTracking.txt] [--rgbd-tracking] [--sens a.sens b.sens]
                            [--mesh scan.ply [--indexed-mesh [--mesh-normals] [--mesh-min-component N] [--mesh-largest-component] [--mesh-cluster M]
-                           [--mesh-smooth N [--mesh-smooth-lambda L] [--mesh-smooth-mu M] [--mesh-smooth-free-boundary]]]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
+                           [--mesh-smooth N [--mesh-smooth-lambda L] [--mesh-smooth-mu M] [--mesh-smooth-free-boundary]] [--live-mesh-every N]]] [--max-frames N] [--record out.sens] [--render-to DIR] [--camera-calibration]
                            [--native [--batch N] [--native-tracking]] [--weighted-colour]
                            [--crop-box CX CY CZ HX HY HZ [RX RY RZ]] [--erase-box CX CY CZ HX HY HZ [RX RY RZ]]
                            [--corrected-trajectory FILE]
@@ -77,6 +77,7 @@ def main():
     ap.add_argument("--mesh-smooth-lambda", type=float, default=0.5, metavar="L", help="--mesh-smooth: the shrinking factor (0.5)")
     ap.add_argument("--mesh-smooth-mu", type=float, default=-0.53, metavar="M", help="--mesh-smooth: the inflating factor (-0.53)")
     ap.add_argument("--mesh-smooth-free-boundary", action="store_true", help="--mesh-smooth: move the vertices of the mesh's open boundary too")
+    ap.add_argument("--live-mesh-every", type=int, default=0, metavar="N", help="--mesh --indexed-mesh: keep a live mesh, update it every N frames at the cost of what the frames changed, and write the final mesh from it")
     ap.add_argument("--record", default=None, help="write what was processed, with the poses used, to this .sens file")
     ap.add_argument("--max-frames", type=int, default=None)
     ap.add_argument("--render-to", default=None, help="renderToFile: the shaded model and the input of every frame as PNGs under this directory")
@@ -111,6 +112,10 @@ def main():
     for name, box in (("--crop-box", args.crop_box), ("--erase-box", args.erase_box)):
         if box is not None and (len(box) not in (6, 9) or not all(h > 0 for h in box[3:6])):
             ap.error(name + ": centre x y z, half extents x y z (> 0) and optionally a rotation vector x y z")
+    if args.live_mesh_every < 0 or (args.live_mesh_every and not (args.mesh and args.indexed_mesh)):
+        ap.error("--live-mesh-every: a number of frames, with --mesh and --indexed-mesh")
+    if args.live_mesh_every and args.native:
+        ap.error("--live-mesh-every: not with --native (the update is not part of the native loop)")
     if args.corrected_trajectory and args.native:
         ap.error("--corrected-trajectory: not with --native")
     import torch
@@ -140,6 +145,17 @@ def main():
     if args.native:
         n = rec.run_native(args.max_frames, batch=args.batch, tracking=args.native_tracking, tracking_rgbd=args.native_tracking and args.rgbd_tracking)
         rec.native.synchronize()
+    elif args.live_mesh_every:
+        try:
+            rec.liveMeshBegin()
+        except ValueError as e:
+            raise SystemExit(str(e))
+        n, live_updates = 0, []
+        while (args.max_frames is None or n < args.max_frames) and rec.frame() is not None:
+            n += 1
+            if n % args.live_mesh_every == 0:
+                live_updates.append(dict(frame=n, **rec.liveMeshUpdate()))
+        rec.scene.synchronize()
     else:
         n = rec.run(args.max_frames)
         rec.scene.synchronize()
@@ -178,10 +194,15 @@ def main():
         out["cut"] = cuts
         out["blocks_after_cut"] = rec.scene.getNumOccupiedBlocks()
     if args.mesh:
-        if args.indexed_mesh:
-            m = rec.extractIsoSurfaceIndexed(args.mesh, normals=args.mesh_normals, min_component_faces=args.mesh_min_component, largest_component=args.mesh_largest_component,
-                                             cluster_cells=args.mesh_cluster, smooth_iterations=args.mesh_smooth, smooth_lambda=args.mesh_smooth_lambda,
-                                             smooth_mu=args.mesh_smooth_mu, keep_boundary=not args.mesh_smooth_free_boundary)
+        mesh_options = dict(normals=args.mesh_normals, min_component_faces=args.mesh_min_component, largest_component=args.mesh_largest_component,
+                            cluster_cells=args.mesh_cluster, smooth_iterations=args.mesh_smooth, smooth_lambda=args.mesh_smooth_lambda,
+                            smooth_mu=args.mesh_smooth_mu, keep_boundary=not args.mesh_smooth_free_boundary)
+        if args.live_mesh_every:  # whatever happened since the last update (frames, a cut, a re-integration) is picked up by one more
+            live_updates.append(dict(frame=n, **rec.liveMeshUpdate()))
+            out["live_mesh"] = dict(every=args.live_mesh_every, updates=live_updates)
+            m = rec.liveMesh(args.mesh, **mesh_options)
+        elif args.indexed_mesh:
+            m = rec.extractIsoSurfaceIndexed(args.mesh, **mesh_options)
         else:
             m = rec.extractIsoSurface(args.mesh)
         out["mesh"] = dict(file=args.mesh, indexed=bool(args.indexed_mesh), vertices=int(len(m["vertices"])), faces=int(len(m["faces"])))

@@ -195,6 +195,12 @@ int vh_scene_rep_get_num_integrated_frames(VhSceneRep* s, uint32_t* out)
     *out = s->impl.getNumIntegratedFrames();
     return VH_OK;
 }
+int vh_scene_rep_frame_in_flight(VhSceneRep* s, int* out)
+{
+    if (!s || !out) return VH_ERR_BAD_ARGUMENT;
+    *out = s->impl.frameInFlight() ? 1 : 0;
+    return VH_OK;
+}
 int vh_scene_rep_deintegrate(VhSceneRep* s, const float rigidTransform[16], const VhDepthCameraData* cam, const VhDepthCameraParams* cp,
                              uint32_t counts[VH_DEINT_NUM_COUNTS])
 {
@@ -494,6 +500,31 @@ int vh_marching_cubes_finish_indexed(VhMarchingCubes* mc)
 {
     if (!mc) return VH_ERR_BAD_ARGUMENT;
     return guarded([&] { mc->impl.finishIndexed(); });
+}
+int vh_marching_cubes_live_begin(VhMarchingCubes* mc)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.liveBegin(); });
+}
+int vh_marching_cubes_live_update(VhMarchingCubes* mc, const VhHashData* hd, const VhHashParams* hp, int boxEnabled, uint32_t counts_out[9])
+{
+    if (!mc || !hd || !hp) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.liveUpdate(*hd, *hp, counts_out, boxEnabled != 0); });
+}
+int vh_marching_cubes_live_invalidate(VhMarchingCubes* mc)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.liveInvalidate(); });
+}
+int vh_marching_cubes_live_indexed(VhMarchingCubes* mc)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.liveIndexed(); });
+}
+int vh_marching_cubes_live_end(VhMarchingCubes* mc)
+{
+    if (!mc) return VH_ERR_BAD_ARGUMENT;
+    return guarded([&] { mc->impl.liveEnd(); });
 }
 int vh_marching_cubes_extract_iso_surface_indexed_chunk_grid(VhMarchingCubes* mc, VhChunkGrid* grid, const float camPos[3], float radius)
 {

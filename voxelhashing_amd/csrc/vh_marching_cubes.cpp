@@ -270,6 +270,7 @@ CUDAMarchingCubesHashSDF::CUDAMarchingCubesHashSDF(const MarchingCubesParams& pa
 {
     std::memset(&m_data, 0, sizeof(m_data));
     std::memset(&m_weld, 0, sizeof(m_weld));
+    std::memset(&m_liveData, 0, sizeof(m_liveData));
     check(vh_marching_cubes_data_alloc(&m_data, &m_params), "MarchingCubesData::allocate");
     m_dataOwner.reset(&m_data);
     check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
@@ -278,6 +279,7 @@ CUDAMarchingCubesHashSDF::CUDAMarchingCubesHashSDF(const MarchingCubesParams& pa
 CUDAMarchingCubesHashSDF::~CUDAMarchingCubesHashSDF() { (void)hipStreamSynchronize((hipStream_t)m_stream); }
 void CUDAMarchingCubesHashSDF::DataFree::operator()(MarchingCubesData* d) const noexcept { vh_marching_cubes_data_free(d); }
 void CUDAMarchingCubesHashSDF::WeldFree::operator()(VhMeshWeldData* d) const noexcept { vh_mesh_weld_data_free(d); }
+void CUDAMarchingCubesHashSDF::LiveFree::operator()(VhLiveMeshData* d) const noexcept { vh_live_mesh_data_free(d); }
 
 unsigned int CUDAMarchingCubesHashSDF::getNumTriangles()
 {
@@ -334,6 +336,7 @@ unsigned int CUDAMarchingCubesHashSDF::countTriangles(bool sourced)
 void CUDAMarchingCubesHashSDF::extractIsoSurfaceWithoutCopy(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner,
                                                             const vh::vec3f& maxCorner, bool boxEnabled)
 {
+    refuseWhileLive("extractIsoSurface");
     runPasses(hashData, hashParams, minCorner, maxCorner, boxEnabled, false);
 }
 
@@ -522,9 +525,14 @@ void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf,
 void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner,
                                                         const vh::vec3f& maxCorner, bool boxEnabled)
 {
+    refuseWhileLive("extractIsoSurfaceIndexed");
     resetIndexed(); // nothing partial is left behind by an error
     runPasses(hashData, hashParams, minCorner, maxCorner, boxEnabled, true);
-    const unsigned int nTriangles = countTriangles(true);
+    weldAndReadBack(countTriangles(true), hashParams.m_virtualVoxelSize);
+}
+
+void CUDAMarchingCubesHashSDF::weldAndReadBack(unsigned int nTriangles, float voxelSize)
+{
     // the table is sized by the triangles there are, not by the buffer: it grows, and is kept for the next call
     if (!m_weldOwner || m_weld.m_maxTriangles < nTriangles) {
         m_weldOwner.reset();
@@ -536,13 +544,89 @@ void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(const HashData& hashData
     const int rc = vh_mesh_weld_get_counts(&m_weld, counts, m_stream);
     m_indexed.counts[2] = counts[2];
     checkWeld(rc, "vh_mesh_weld_get_counts");
-    readBackIndexed(counts[0], counts[1], false, hashParams.m_virtualVoxelSize);
+    readBackIndexed(counts[0], counts[1], false, voxelSize);
+}
+
+// ---------------------------------------------------------------------------
+// live mesh
+// ---------------------------------------------------------------------------
+
+void CUDAMarchingCubesHashSDF::refuseWhileLive(const char* what) const
+{
+    if (m_live) throw vh::Error(VH_ERR_BAD_ARGUMENT, std::string(what) + ": the object holds a live mesh (liveEnd first)");
+}
+
+void CUDAMarchingCubesHashSDF::liveBegin()
+{
+    refuseWhileLive("liveBegin");
+    if (!d_sources) d_sources = vh::deviceAlloc<VhTriangleSource>(m_params.m_maxNumTriangles, "triangle sources");
+    resetIndexed();
+    m_params.m_boxEnabled = 0u;
+    check(vh_marching_cubes_update_params(&m_data, &m_params, m_stream), "MarchingCubesData::updateParams");
+    check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
+    if (m_liveOwner) check(vh_live_mesh_reset(&m_liveData, m_stream), "vh_live_mesh_reset");
+    m_live = true;
+    m_liveValid = false;
+}
+
+void CUDAMarchingCubesHashSDF::liveUpdate(const HashData& hashData, const HashParams& hashParams, unsigned int counts[VH_LIVE_NUM_COUNTS + 1], bool boxEnabled)
+{
+    if (!m_live) throw vh::Error(VH_ERR_BAD_ARGUMENT, "liveUpdate: no liveBegin");
+    if (boxEnabled) throw vh::Error(VH_ERR_BAD_ARGUMENT, "liveUpdate: a live mesh has no box");
+    if (m_liveOwner && m_liveData.m_numSDFBlocks != hashParams.m_numSDFBlocks) {
+        if (!m_liveData.m_fresh) throw vh::Error(VH_ERR_BAD_ARGUMENT, "liveUpdate: the hash parameters are not those of the earlier updates");
+        m_liveOwner.reset();
+    }
+    if (!m_liveOwner) { // the records are sized by the pool, which only the hash parameters name
+        check(vh_live_mesh_data_alloc(&m_liveData, hashParams.m_numSDFBlocks, m_params.m_maxNumTriangles), "vh_live_mesh_data_alloc");
+        m_liveOwner.reset(&m_liveData);
+    }
+    VhTriangleSource* sources = d_sources.get();
+    const int rc = vh_live_mesh_update(&hashData, &hashParams, &m_data, &sources, &m_liveData, m_stream);
+    if (sources != d_sources.get()) { (void)d_sources.release(); d_sources.reset(sources); } // the cache changed places with the spare pair
+    if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "liveUpdate: the hash parameters are not those of the earlier updates");
+    m_liveValid = false;
+    check(rc, "vh_live_mesh_update");
+    unsigned int stats[VH_LIVE_NUM_COUNTS + 1] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    const int st = vh_live_mesh_get_counts(&m_liveData, stats, m_stream);
+    if (counts) std::copy(stats, stats + VH_LIVE_NUM_COUNTS + 1, counts);
+    if (st == VH_ERR_STAGING_OVERFLOW) throw vh::Error(st, "live mesh: not enough memory to store the triangles; increase s_marchingCubesMaxNumTriangles");
+    if (st == VH_ERR_BAD_ARGUMENT) throw vh::Error(st, "live mesh: a block outside the range of +-2^16, or a table that names a block twice or none of the pool");
+    check(st, "vh_live_mesh_get_counts");
+    m_liveVoxelSize = hashParams.m_virtualVoxelSize;
+    m_liveValid = true;
+}
+
+void CUDAMarchingCubesHashSDF::liveInvalidate()
+{
+    if (!m_live) throw vh::Error(VH_ERR_BAD_ARGUMENT, "liveInvalidate: no liveBegin");
+    if (m_liveOwner) check(vh_live_mesh_reset(&m_liveData, m_stream), "vh_live_mesh_reset");
+    check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
+    m_liveValid = false;
+}
+
+void CUDAMarchingCubesHashSDF::liveIndexed()
+{
+    if (!m_live || !m_liveValid) throw vh::Error(VH_ERR_BAD_ARGUMENT, "liveIndexed: no valid live mesh (liveBegin, liveUpdate)");
+    resetIndexed();
+    const unsigned int nTriangles = getNumTriangles(); // the cache's count: within the buffer after an update without a status
+    m_indexed.numSourced = nTriangles;
+    weldAndReadBack(nTriangles, m_liveVoxelSize);
+}
+
+void CUDAMarchingCubesHashSDF::liveEnd()
+{
+    if (!m_live) throw vh::Error(VH_ERR_BAD_ARGUMENT, "liveEnd: no liveBegin");
+    m_live = false;
+    m_liveValid = false;
+    check(vh_reset_marching_cubes(&m_data, m_stream), "resetMarchingCubesCUDA");
 }
 
 void CUDAMarchingCubesHashSDF::AccumFree::operator()(VhMeshWeldAccum* a) const noexcept { vh_mesh_weld_accum_destroy(a); }
 
 void CUDAMarchingCubesHashSDF::beginIndexed()
 {
+    refuseWhileLive("beginIndexed");
     resetIndexed();
     m_indexed.accumulated = true;
     if (!m_accum) {
@@ -556,6 +640,7 @@ void CUDAMarchingCubesHashSDF::beginIndexed()
 void CUDAMarchingCubesHashSDF::appendIndexed(const HashData& hashData, const HashParams& hashParams, const vh::vec3f& minCorner,
                                              const vh::vec3f& maxCorner, bool boxEnabled)
 {
+    refuseWhileLive("appendIndexed");
     if (!m_accum || !m_indexed.accumulated) throw vh::Error(VH_ERR_BAD_ARGUMENT, "appendIndexed: no beginIndexed");
     m_indexed.voxelSize = hashParams.m_virtualVoxelSize;
     try {
@@ -629,6 +714,7 @@ void CUDAMarchingCubesHashSDF::walkChunks(CUDASceneRepChunkGrid& chunkGrid, cons
 
 void CUDAMarchingCubesHashSDF::extractIsoSurface(CUDASceneRepChunkGrid& chunkGrid, const vh::vec3f& camPos, float radius)
 {
+    refuseWhileLive("extractIsoSurface");
     clearMeshBuffer();
     walkChunks(chunkGrid, camPos, radius, false, [this](const HashData& hd, const HashParams& hp, const vh::vec3f& lo, const vh::vec3f& hi) {
         extractIsoSurface(hd, hp, lo, hi, true);
@@ -638,6 +724,7 @@ void CUDAMarchingCubesHashSDF::extractIsoSurface(CUDASceneRepChunkGrid& chunkGri
 // the same walk, every chunk appended to one accumulation
 void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(CUDASceneRepChunkGrid& chunkGrid, const vh::vec3f& camPos, float radius)
 {
+    refuseWhileLive("extractIsoSurfaceIndexed");
     try {
         beginIndexed();
         walkChunks(chunkGrid, camPos, radius, true, [this](const HashData& hd, const HashParams& hp, const vh::vec3f& lo, const vh::vec3f& hi) {
@@ -704,7 +791,9 @@ void CUDAMarchingCubesHashSDF::downloadIndexedNormals(float* normals)
 void CUDAMarchingCubesHashSDF::downloadSources(VhTriangleSource* out, unsigned int n)
 {
     if (n == 0) return;
-    if (!out || !d_sources || n > m_indexed.numSourced) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadSources");
+    // (while live the records are the cache's: as many as it holds triangles)
+    const unsigned int have = m_live ? std::min(getNumTriangles(), m_params.m_maxNumTriangles) : m_indexed.numSourced;
+    if (!out || !d_sources || n > have) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadSources");
     checkHip(hipMemcpyAsync(out, d_sources.get(), sizeof(VhTriangleSource) * (size_t)n, hipMemcpyDeviceToHost, (hipStream_t)m_stream), "sources");
     checkHip(hipStreamSynchronize((hipStream_t)m_stream), "sources");
 }

@@ -410,6 +410,12 @@ class CUDASceneRepHashSDF:
         check(self.L.vh_scene_rep_get_num_integrated_frames(self.handle, C.byref(n)), "getNumIntegratedFrames")
         return n.value
 
+    def frameInFlight(self):
+        """True between integrateAhead() and integrateFinish(): what merge, cut and de-integration refuse"""
+        out = C.c_int()
+        check(self.L.vh_scene_rep_frame_in_flight(self.handle, C.byref(out)), "frameInFlight")
+        return bool(out.value)
+
     def reintegrate(self, oldTransform, newTransform, depthCameraData, depthCameraParams, d_bitMask=None):
         """deintegrate(oldTransform) followed by integrate(newTransform), which counts as a frame -> the take-out's counts"""
         what = "CUDASceneRepHashSDF::reintegrate"
@@ -1202,6 +1208,33 @@ class CUDAMarchingCubesHashSDF:
         check(self.L.vh_marching_cubes_extract_iso_surface_indexed_chunk_grid(self.handle, chunkGrid.handle, f16(camPos), radius),
               "extractIsoSurfaceIndexed(chunkGrid)")
 
+    def liveBegin(self):
+        """starts a live mesh: until liveEnd the object's triangles() and sources() are a cache that liveUpdate brings
+        up to date with the table, and every extraction on the object raises VhError (VH_ERR_BAD_ARGUMENT)"""
+        check(self.L.vh_marching_cubes_live_begin(self.handle), "liveBegin")
+
+    def liveUpdate(self, hashData, hashParams, boxEnabled=False, raise_on_status=True):
+        """one update of the live mesh: re-extracts the resident blocks within one block of a block that changed since
+        the last update -> the counts of T.LIVE_COUNTS and `status`.  An overflow or a block out of range raises VhError
+        and leaves the cache invalid (the next update is a full one); with raise_on_status=False it comes back as `code`"""
+        out = (C.c_uint32 * 9)()
+        code = self.L.vh_marching_cubes_live_update(self.handle, C.byref(hashData), C.byref(hashParams), int(boxEnabled), out)
+        if code != 0 and (raise_on_status or out[8] == 0):
+            check(code, "liveUpdate")
+        return dict({k: int(out[i]) for i, k in enumerate(T.LIVE_COUNTS)}, status=int(out[8]), code=int(code))
+
+    def liveInvalidate(self):
+        """forgets every record and the cache: the next liveUpdate is a full extraction (the digests can collide)"""
+        check(self.L.vh_marching_cubes_live_invalidate(self.handle), "liveInvalidate")
+
+    def liveIndexed(self):
+        """welds the cache and runs the indexed passes that are on: REPLACES the mesh buffer as extractIsoSurfaceIndexed
+        does (indexed(), mesh(), saveMesh); the cache stays"""
+        check(self.L.vh_marching_cubes_live_indexed(self.handle), "liveIndexed")
+
+    def liveEnd(self):
+        check(self.L.vh_marching_cubes_live_end(self.handle), "liveEnd")
+
     def indexed_stats(self):
         """of the last accumulated extraction: vertices, faces, status, cells, dropped (triangles of cells an earlier
         append had), rehashes (doublings of the table); all 0 after a one-shot extraction"""
@@ -1270,6 +1303,82 @@ class CUDAMarchingCubesHashSDF:
     def saveMesh(self, filename, transform=None, overwriteExistingFile=False):
         t = f16(transform) if transform is not None else None
         check(self.L.vh_marching_cubes_save_mesh(self.handle, filename.encode(), t, int(overwriteExistingFile)), "saveMesh")
+
+
+def live_mesh_digest(hashData, hashParams, entry_indices, stream=None):
+    """vh_live_mesh_digest: the 64-bit digests of the blocks of the listed hash entries (0 for a free entry) -> (n,) u64"""
+    idx = np.ascontiguousarray(entry_indices, dtype=np.uint32).ravel()
+    if len(idx) == 0:
+        return np.zeros(0, dtype=np.uint64)
+    d_idx, d_out = DeviceBuffer.from_numpy(idx, stream), DeviceBuffer(8 * len(idx))
+    try:
+        check(load().vh_live_mesh_digest(C.byref(hashData), C.byref(hashParams), d_idx.ptr, len(idx), d_out.ptr, stream), "vh_live_mesh_digest")
+        return d_out.download(np.uint64, len(idx), stream)
+    finally:
+        d_idx.free()
+        d_out.free()
+
+
+class LiveMesh:
+    """The live mesh at launcher level: vh_live_mesh_* over buffers of its own (vh_marching_cubes_data_alloc, the source
+    records, vh_live_mesh_data_alloc).  params: T.MarchingCubesParams with the box off."""
+
+    def __init__(self, params, numSDFBlocks, stream=None):
+        self.L = load()
+        self.stream = stream
+        self._params = _copy_struct(params)
+        self._params.m_boxEnabled = 0
+        self.data, self.live, self.d_sources = T.MarchingCubesData(), T.LiveMeshData(), C.c_void_p()
+        check(self.L.vh_marching_cubes_data_alloc(C.byref(self.data), C.byref(self._params)), "vh_marching_cubes_data_alloc")
+        check(self.L.vh_reset_marching_cubes(C.byref(self.data), stream), "vh_reset_marching_cubes")
+        check(self.L.vh_malloc(C.byref(self.d_sources), 16 * int(self._params.m_maxNumTriangles)), "vh_malloc")
+        check(self.L.vh_live_mesh_data_alloc(C.byref(self.live), int(numSDFBlocks), int(self._params.m_maxNumTriangles)), "vh_live_mesh_data_alloc")
+
+    def close(self):
+        if getattr(self, "live", None) is not None:
+            self.L.vh_live_mesh_data_free(C.byref(self.live))
+            self.L.vh_marching_cubes_data_free(C.byref(self.data))
+            self.L.vh_free(self.d_sources)
+            self.live = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        check(self.L.vh_live_mesh_reset(C.byref(self.live), self.stream), "vh_live_mesh_reset")
+        check(self.L.vh_reset_marching_cubes(C.byref(self.data), self.stream), "vh_reset_marching_cubes")
+
+    def enqueue(self, hashData, hashParams):
+        """vh_live_mesh_update alone: the counts are read by counts()"""
+        check(self.L.vh_live_mesh_update(C.byref(hashData), C.byref(hashParams), C.byref(self.data), C.byref(self.d_sources), C.byref(self.live), self.stream),
+              "vh_live_mesh_update")
+
+    def counts(self, raise_on_status=True):
+        out = (C.c_uint32 * 9)()
+        code = self.L.vh_live_mesh_get_counts(C.byref(self.live), out, self.stream)
+        if code != 0 and (raise_on_status or out[8] == 0):
+            check(code, "vh_live_mesh_get_counts")
+        return dict({k: int(out[i]) for i, k in enumerate(T.LIVE_COUNTS)}, status=int(out[8]), code=int(code))
+
+    def update(self, hashData, hashParams, raise_on_status=True):
+        self.enqueue(hashData, hashParams)
+        return self.counts(raise_on_status)
+
+    def soup(self, n):
+        """the first n triangles of the cache and their records (n: the last update's total)"""
+        tris, srcs = np.zeros(int(n), dtype=T.TRIANGLE_DTYPE), np.zeros(int(n), dtype=T.TRIANGLE_SOURCE_DTYPE)
+        if n:
+            check(self.L.vh_memcpy_d2h(tris.ctypes.data, self.data.d_triangles, tris.nbytes, self.stream), "vh_memcpy_d2h")
+            check(self.L.vh_memcpy_d2h(srcs.ctypes.data, self.d_sources, srcs.nbytes, self.stream), "vh_memcpy_d2h")
+        return tris, srcs
+
+    def records(self):
+        out = np.zeros(int(self.live.m_numSDFBlocks), dtype=T.LIVE_RECORD_DTYPE)
+        check(self.L.vh_memcpy_d2h(out.ctypes.data, self.live.d_records, out.nbytes, self.stream), "vh_memcpy_d2h")
+        return out
 
 
 def mesh_weld_key(cell, edge, snap):

@@ -118,6 +118,7 @@ PROTOTYPES = {
                                         _VP, _VP, _VP]),
     "vh_debug_deintegrate_rule": (C.c_int, [_VP, _VP, _VP, C.c_uint32, P(T.HashParams), _VP]),
     "vh_scene_rep_get_num_integrated_frames": (C.c_int, [_VP, _VP]),
+    "vh_scene_rep_frame_in_flight": (C.c_int, [_VP, _VP]),
     "vh_scene_rep_deintegrate": (C.c_int, [_VP, _F16, P(T.DepthCameraData), P(T.DepthCameraParams), _VP]),
     "vh_scene_rep_reintegrate": (C.c_int, [_VP, _F16, _F16, P(T.DepthCameraData), P(T.DepthCameraParams), _VP, _VP]),
     "vh_ray_cast_cast_rays": (C.c_int, [_VP, P(T.HashData), P(T.HashParams), _VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP]),
@@ -250,6 +251,17 @@ PROTOTYPES = {
     "vh_extract_iso_surface_pass1": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.MarchingCubesData), _VP]),
     "vh_extract_iso_surface_pass2": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.MarchingCubesData), C.c_uint32, _VP]),
     "vh_extract_iso_surface_pass2_sourced": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.MarchingCubesData), _VP, C.c_uint32, _VP]),
+    "vh_live_mesh_data_alloc": (C.c_int, [P(T.LiveMeshData), C.c_uint32, C.c_uint32]),
+    "vh_live_mesh_data_free": (None, [P(T.LiveMeshData)]),
+    "vh_live_mesh_reset": (C.c_int, [P(T.LiveMeshData), _VP]),
+    "vh_live_mesh_update": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.MarchingCubesData), P(C.c_void_p), P(T.LiveMeshData), _VP]),
+    "vh_live_mesh_get_counts": (C.c_int, [P(T.LiveMeshData), P(C.c_uint32), _VP]),
+    "vh_live_mesh_digest": (C.c_int, [P(T.HashData), P(T.HashParams), _VP, C.c_uint32, _VP, _VP]),
+    "vh_marching_cubes_live_begin": (C.c_int, [_VP]),
+    "vh_marching_cubes_live_update": (C.c_int, [_VP, P(T.HashData), P(T.HashParams), C.c_int, P(C.c_uint32)]),
+    "vh_marching_cubes_live_invalidate": (C.c_int, [_VP]),
+    "vh_marching_cubes_live_indexed": (C.c_int, [_VP]),
+    "vh_marching_cubes_live_end": (C.c_int, [_VP]),
     "vh_mesh_weld_key": (C.c_int, [P(C.c_int32), C.c_uint32, C.c_uint32, P(C.c_uint64)]),
     "vh_mesh_weld_default_slots_log2": (C.c_int, [C.c_uint32, P(C.c_uint32)]),
     "vh_mesh_weld_data_alloc": (C.c_int, [P(T.MeshWeldData), C.c_uint32, C.c_uint32]),

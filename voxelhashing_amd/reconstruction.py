@@ -284,6 +284,7 @@ class Reconstruction:
         if self.tracking_rgbd is not None:
             self.tracker_rgbd = E.CUDACameraTrackingMultiResRGBD(self.adapter_size[0], self.adapter_size[1], self.tracking.s_maxLevels, stream=stream)
         self.marching_cubes = None
+        self.live_marching_cubes = None  # the extractor that holds the live mesh, once liveMeshBegin has made it
         cam = self.sensor.getDepthCameraData()
         self.frame_data = E.DepthFrame(self.cp, depth_ptr=cam.d_depthData, color_ptr=cam.d_colorData)
         self.calibration_state = calibration_state
@@ -696,6 +697,57 @@ class Reconstruction:
         return ((h.m_depthWidth, h.m_depthHeight), (h.m_colorWidth, h.m_colorHeight), np.array(h.m_depthIntrinsic[:]), np.array(h.m_colorIntrinsic[:]),
                 h.m_depthShift, bytes(h.m_sensorName).decode(), h.m_colorCompressionType, h.m_depthCompressionType,
                 np.array(h.m_depthExtrinsic[:]), np.array(h.m_colorExtrinsic[:]))
+
+    # -- live mesh (not in the reference; DESIGN.md section 4 "Live mesh") --------------------------------------------
+    def _live_check(self, what):
+        if self.chunk_grid is not None:
+            raise ValueError(f"{what}: not with streaming (a live mesh is of what is resident; the chunk-grid walk is not covered)")
+        if self.native is not None:  # frames the native loop still has in flight, as deintegrateFrame treats them
+            self.native.synchronize()
+        if self.scene.frameInFlight():  # the model is about to change under an update: refused, as a de-integration is
+            raise ValueError(f"{what}: a frame is in flight (between integrateAhead and integrateFinish)")
+
+    def liveMeshBegin(self):
+        """Starts a live mesh on an extractor of its own (live_marching_cubes): liveMeshUpdate then brings it up to date
+        with the model at the cost of what changed, and liveMesh reads it.  ValueError with streaming on."""
+        self._live_check("liveMeshBegin")
+        if self.live_marching_cubes is None:
+            self.live_marching_cubes = E.CUDAMarchingCubesHashSDF(self.mp)
+        else:
+            self.live_marching_cubes.liveEnd()
+        self.live_marching_cubes.liveBegin()
+
+    def liveMeshUpdate(self):
+        """One update of the live mesh (CUDAMarchingCubesHashSDF.liveUpdate) -> its counts.  A native loop is
+        synchronised first.  ValueError, with the cache as it was, without liveMeshBegin, with streaming on and with a
+        frame in flight (the scene between integrateAhead and integrateFinish)."""
+        self._live_check("liveMeshUpdate")
+        if self.live_marching_cubes is None:
+            raise ValueError("liveMeshUpdate: no liveMeshBegin")
+        return self.live_marching_cubes.liveUpdate(self.scene.getHashData(), self.scene.getHashParams())
+
+    def liveMesh(self, filename=None, normals=False, min_component_faces=0, largest_component=False, cluster_cells=0, smooth_iterations=0,
+                 smooth_lambda=0.5, smooth_mu=-0.53, keep_boundary=True):
+        """The live mesh as it stands after the last update, welded on the device and through the indexed passes asked
+        for (as extractIsoSurface(indexed=True) describes them) -> the mesh; written as a PLY when a file name is given"""
+        if self.live_marching_cubes is None:
+            raise ValueError("liveMesh: no liveMeshBegin")
+        mc = self.live_marching_cubes
+        mc.setIndexedNormals(bool(normals))
+        mc.setIndexedComponentFilter(int(min_component_faces), bool(largest_component))
+        mc.setIndexedClustering(int(cluster_cells))
+        mc.setIndexedSmoothing(int(smooth_iterations), smooth_lambda, smooth_mu, bool(keep_boundary))
+        mc.liveIndexed()
+        mesh = mc.mesh()
+        if min_component_faces or largest_component:
+            mesh["components"] = mc.indexed_component_stats()
+        if cluster_cells:
+            mesh["clustering"] = mc.indexed_cluster_stats()
+        if smooth_iterations:
+            mesh["smoothing"] = mc.indexed_smooth_stats()
+        if filename:
+            mc.saveMesh(filename, None, True)
+        return mesh
 
     def extractIsoSurface(self, filename=None, indexed=False, normals=False, min_component_faces=0, largest_component=False, cluster_cells=0,
                           smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, keep_boundary=True):

@@ -227,6 +227,22 @@ class MeshWeldData(C.Structure):
     ]
 
 
+# VH_LIVE_*: what an update of the live mesh counts (the status word follows them), and the bits of that word
+LIVE_COUNTS = ("visited", "changed", "vanished", "remeshed", "dropped", "kept", "added", "total")
+LIVE_OVERFLOW, LIVE_RANGE, LIVE_BAD_TABLE = 1, 2, 4
+LIVE_RECORD_DTYPE = np.dtype([("pos", np.int32, 3), ("epoch", np.uint32), ("digest", np.uint64)])  # VhLiveMeshRecord, 24 B
+
+
+class LiveMeshData(C.Structure):  # VhLiveMeshData
+    _fields_ = [
+        ("d_records", C.c_void_p), ("d_positions", C.c_void_p), ("d_marks", C.c_void_p), ("d_remesh", C.c_void_p),
+        ("d_spareTriangles", C.c_void_p), ("d_spareSources", C.c_void_p), ("d_counts", C.c_void_p),
+        ("m_numSDFBlocks", C.c_uint32), ("m_maxNumTriangles", C.c_uint32), ("m_epoch", C.c_uint32), ("m_fresh", C.c_uint32),
+        ("m_hashNumBuckets", C.c_uint32), ("m_hashMaxCollisionLinkedListSize", C.c_uint32), ("m_virtualVoxelSize", C.c_float),
+        ("m_pad", C.c_uint32),
+    ]
+
+
 class AppState(C.Structure):
     _fields_ = [
         ("s_adapterWidth", C.c_uint32), ("s_adapterHeight", C.c_uint32),
