@@ -32,6 +32,27 @@ PARAMETER_SETS = {
     "saturating": dict(camera={}, hash=lambda voxel: dict(weight_sample=5, weight_max=12), back=0.0),
 }
 
+# wider bands than the default one (5 voxels + 2.5 per metre), apart from PARAMETER_SETS, whose keys parametrize tests
+# with literal bounds of their own.  thick: 9.6 voxels + 4 per metre -- wider than a block's edge from the first metre on,
+# so alloc's ray walk, the interval splat and the fused pass meet other block counts per pixel
+BAND_SETS = {
+    "thick": dict(camera={}, hash=lambda voxel: dict(truncation=9.6 * voxel, trunc_scale=4.0 * voxel), back=0.0),
+}
+
+# name -> (ray increment / truncation, sample-distance threshold / increment, distance threshold / increment): the ray
+# caster's step and the two gates a zero crossing passes before it counts, fabsf(lastSdf - dist) < m_thresSampleDist and
+# fabsf(dist) < m_thresDist.  The builders' defaults (0.8, 50.5, 50.0) put both thresholds at forty truncations, where
+# neither comparison can be false.
+MARCH_SETS = {
+    "sample_gate": (0.8, 1.0, 50.0),        # rejects by abs(lastSdf - dist) alone
+    "dist_gate": (0.8, 50.5, 0.5),          # rejects by abs(dist) alone
+    "both_gates": (0.8, 0.9, 0.45),         # both rejections at once
+    "fine": (0.25, 50.5, 0.5),              # about four samples in the band, several per block
+    "fine_sample_gate": (0.25, 0.9, 50.0),  # the sample gate at the fine step
+    "coarse": (2.5, 50.5, 50.0),            # the step is longer than the band
+    "coarse_dist_gate": (2.5, 50.5, 0.3),   # the distance gate at the coarse step
+}
+
 # the reference's hash sends (x, y, z) and (-x, -y, z) to one bucket; away from the origin an online alloc pass is
 # deterministic (tests/test_gpu_frame_loop.py)
 OFFSET = np.array([7.3, 5.1, 3.7])
@@ -47,19 +68,36 @@ def intrinsics(name, width, height):
 
 
 def camera(name, width, height, **limits):
+    """DepthCameraParams of a named camera (None: the builder's default one)"""
+    if name is None:
+        return T.make_depth_camera_params(width, height, **limits)
     return T.make_depth_camera_params(width, height, **limits, **intrinsics(name, width, height))
 
 
-def config(name, size, voxels="P4", pset=None, buckets=1 << 14, blocks=1 << 13, gradients=False):
-    """-> (HashParams, DepthCameraParams, RayCastParams) of a named camera, with a named parameter set on top"""
+def parameter_set(pset):
+    """a set of PARAMETER_SETS or BAND_SETS by its name"""
+    return PARAMETER_SETS[pset] if pset in PARAMETER_SETS else BAND_SETS[pset]
+
+
+def march_factors(march):
+    """keyword arguments of make_raycast_params for a set of MARCH_SETS (None: the builder's defaults)"""
+    if march is None:
+        return {}
+    inc, sample, dist = MARCH_SETS[march]
+    return dict(ray_increment_factor=inc, thres_sample_dist_factor=sample, thres_dist_factor=dist)
+
+
+def config(name, size, voxels="P4", pset=None, buckets=1 << 14, blocks=1 << 13, gradients=False, march=None):
+    """-> (HashParams, DepthCameraParams, RayCastParams) of a named camera, with a named parameter set (PARAMETER_SETS or
+    BAND_SETS) and a named march set (MARCH_SETS) on top"""
     ps = dict(synth.PARAM_SETS[voxels])
     limits = {}
     if pset is not None:
-        ps.update(PARAMETER_SETS[pset]["hash"](ps["voxel_size"]))
-        limits = PARAMETER_SETS[pset]["camera"]
+        ps.update(parameter_set(pset)["hash"](ps["voxel_size"]))
+        limits = parameter_set(pset)["camera"]
     hp = T.make_hash_params(buckets, blocks, **ps)
     cp = camera(name, *size, **limits)
-    return hp, cp, T.make_raycast_params(hp, cp, use_gradients=gradients)
+    return hp, cp, T.make_raycast_params(hp, cp, use_gradients=gradients, **march_factors(march))
 
 
 def aim(cp):

@@ -62,7 +62,7 @@ KERNEL_COUNTS = {"tum": (150, 33000, 2000), "tall": (131, 29000, 2300), "wide": 
 
 
 def frames_for(cp, n, seed, pset=None):
-    back = CM.PARAMETER_SETS[pset]["back"] if pset else 0.0
+    back = CM.parameter_set(pset)["back"] if pset else 0.0
     return CM.place(general_poses(n, seed), cp, back)
 
 

@@ -31,7 +31,7 @@ def E(vh):
 
 
 def frames_for(cp, n, seed, pset=None):
-    back = CM.PARAMETER_SETS[pset]["back"] if pset else 0.0
+    back = CM.parameter_set(pset)["back"] if pset else 0.0
     return CM.place(general_poses(n, seed), cp, back)
 
 
@@ -55,11 +55,13 @@ LOOP = {
 }
 
 
-def loop_inputs(O, key):
-    """-> hp, cp, rp, poses, the oracle's frames of a LOOP case"""
+def loop_inputs(O, key, cases=None, march=None):
+    """-> hp, cp, rp, poses, the oracle's frames of a LOOP case (or of a case of another table of that layout, under a
+    march set of tests/camera_models.py)"""
     name, size, voxels, pset = key
-    buckets, seed = LOOP[key][:2]
-    hp, cp, rp = CM.config(name, size, voxels, pset, buckets=buckets, blocks=1 << 12 if voxels == "P2" else 1 << 11)
+    buckets, seed = (LOOP if cases is None else cases)[key][:2]
+    blocks = 1 << 12 if voxels == "P2" else 1 << 11
+    hp, cp, rp = CM.config(name, size, voxels, pset, buckets=buckets, blocks=blocks, march=march)
     poses = frames_for(cp, 4, seed, pset)
     return hp, cp, rp, poses, [O.synth_frame(CM.SPHERES, 0, p, cp) for p in poses]
 
@@ -80,9 +82,13 @@ def test_native_loop_under_a_camera(E, oracle_lib, key):
     """vh_reconstruction_run frame by frame with its riders -- alloc in the ray caster's launch, compactify and the next
     frame's splat in computeNormals', the pass over the voxels with GC behind them -- against the oracle after every
     frame: the canonical scene and the four ray-cast maps"""
+    native_loop_under_a_camera(E, oracle_lib, key)
+
+
+def native_loop_under_a_camera(E, O, key, cases=None, march=None):
+    """test_native_loop_under_a_camera's body, for a case of LOOP or of another table of its layout"""
     from test_gpu_frame_loop import oracle_online_is_deterministic
-    O = oracle_lib
-    hp, cp, rp, poses, host = loop_inputs(O, key)
+    hp, cp, rp, poses, host = loop_inputs(O, key, cases, march)
     n = len(poses)
     assert oracle_online_is_deterministic(O, hp, cp, rp, poses, host, True, 2), "pick poses without same-pass bucket sharing"
     frames = [E.synth_frame(CM.SPHERES, 0, p, cp) for p in poses]
@@ -104,8 +110,9 @@ def test_native_loop_under_a_camera(E, oracle_lib, key):
         ref.integrate(poses[k], *host[k])
         canonical.assert_same_scene(scene.state(), ref.state(), f"{key} frame {k}")
     blocks = ref.state()["num_occupied"]
-    print(f"{key}: {blocks} blocks, {hits} hits")
-    assert blocks >= LOOP[key][2] and hits >= LOOP[key][3], (blocks, hits)
+    print(f"{key} {march or ''}: {blocks} blocks, {hits} hits")
+    want = (LOOP if cases is None else cases)[key]
+    assert blocks >= want[2] and hits >= want[3], (blocks, hits)
     st = recon.getStats()
     assert st["frames"] == n and st["invalidFrames"] == 0
     assert st["framesWithRiders"] == n - 1 and st["splatsMadeAheadUsed"] == n - 2, st

@@ -122,7 +122,8 @@ def eye_pose(x, y, z):
 
 
 class Renderer:
-    """splat + vh_render_intervals + vh_compute_normals (CUDARayCastSDF::render's steps) on a launcher scene -> maps, heads"""
+    """splat + vh_render_intervals + vh_compute_normals (CUDARayCastSDF::render's steps: the normals from the depth map only
+    without gradients, with them the march has written them) on a launcher scene -> maps, heads"""
 
     def __init__(self, vh, E, g, cp, rpv):
         from voxelhashing_amd import lib
@@ -143,7 +144,8 @@ class Renderer:
         heads = self.heads.download(np.uint32).reshape(self.n_tiles, 4)
         lib.check(vh.vh_render_intervals(C.byref(g.hd), C.byref(g.hp), C.byref(self.rd), C.byref(self.cp), C.byref(self.rp), self.heads.ptr, self.lists.ptr,
                                          CAP_SMALL, render_sched, phase, None))
-        lib.check(vh.vh_compute_normals(self.rd.d_normals, self.rd.d_depth4, self.W, self.H, None))  # (no gradients: normals from the depth map)
+        if not self.rp.m_useGradients:  # (no gradients: normals from the depth map)
+            lib.check(vh.vh_compute_normals(self.rd.d_normals, self.rd.d_depth4, self.W, self.H, None))
         return self.ray.download(), heads
 
 

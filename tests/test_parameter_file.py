@@ -110,3 +110,39 @@ s_reconstructionEnabled = true;
     assert bytes(g.s_binaryDumpSensorFile[0].value) == b"./DumpOutput/a_0.sens" and bytes(g.s_binaryDumpSensorFile[1].value) == b"./DumpOutput/a_1.sens"
     assert (g.s_binaryDumpSensorUseTrajectory, g.s_binaryDumpSensorUseTrajectoryOnlyInit, g.s_playData, g.s_recordData, g.s_reconstructionEnabled) == (1, 0, 1, 0, 1)
     assert g.numKeysFound == 7  # the list counts once
+
+
+@pytest.mark.parametrize("factors", [(0.25, 0.9, 50.0), (0.8, 50.5, 0.5), (2.5, 50.5, 0.3)], ids=["fine_sample_gate", "dist_gate", "coarse_dist_gate"])
+def test_ray_march_factors_arrive_in_the_raycast_params(tmp_path, factors):
+    """s_SDFRayIncrementFactor, s_SDFRayThresSampleDistFactor and s_SDFRayThresDistFactor other than 0.8 / 50.5 / 50.0
+    (three of tests/camera_models.py's march sets), with a truncation other than the sample file's: the increment is factor *
+    truncation, both thresholds are factor * increment, in float32 -- through the C++ reader and through
+    reconstruction.py's read_app_state (a wrapper over the same parser: what is checked is that both of its ways in arrive
+    there), from the text and from a file"""
+    from voxelhashing_amd import reconstruction as REC
+    L = lib.load()
+    inc_f, sample_f, dist_f = factors
+    with open(os.path.join(ROOT, "tests", "data", "zParametersSample.txt"), "rb") as fh:
+        text = fh.read()
+    text += (f"\ns_SDFTruncation = 0.096f;\ns_SDFTruncationScale = 0.04f;\ns_SDFRayIncrementFactor = {inc_f}f;\n"
+             f"s_SDFRayThresSampleDistFactor = {sample_f}f;\ns_SDFRayThresDistFactor = {dist_f}f;\n").encode()  # (the later line wins)
+    path = tmp_path / "zParametersMarch.txt"
+    path.write_bytes(text)
+    parsed = T.AppState()
+    lib.check(L.vh_app_state_parse(text, C.byref(parsed)), "parse")
+    states = {"vh_app_state_parse": parsed, "vh_app_state_read": read(str(path))[1],
+              "read_app_state(text)": REC.read_app_state(text), "read_app_state(path)": REC.read_app_state(path)}
+    inc = f32(inc_f) * f32(0.096)
+    for what, g in states.items():
+        assert (g.s_SDFRayIncrementFactor, g.s_SDFRayThresSampleDistFactor, g.s_SDFRayThresDistFactor) == (f32(inc_f), f32(sample_f), f32(dist_f)), what
+        assert g.s_SDFTruncation == f32(0.096) and g.s_SDFTruncationScale == f32(0.04), what
+        hp, rp = T.HashParams(), T.RayCastParams()
+        L.vh_hash_params_from_app_state(C.byref(g), C.byref(hp))
+        L.vh_raycast_params_from_app_state(C.byref(g), None, None, C.byref(rp))
+        assert hp.m_truncation == f32(0.096) and hp.m_truncScale == f32(0.04), what
+        assert rp.m_rayIncrement == inc and rp.m_thresSampleDist == f32(sample_f) * inc and rp.m_thresDist == f32(dist_f) * inc, what
+        # the struct the tests' own builder makes from these factors: the three march words, bit for bit
+        cp = T.make_depth_camera_params(640, 480, depth_min=0.4, depth_max=4.5)
+        want = T.make_raycast_params(hp, cp, ray_increment_factor=inc_f, thres_sample_dist_factor=sample_f, thres_dist_factor=dist_f)
+        assert [f32(v).view(np.uint32) for v in (rp.m_rayIncrement, rp.m_thresSampleDist, rp.m_thresDist)] == \
+               [f32(v).view(np.uint32) for v in (want.m_rayIncrement, want.m_thresSampleDist, want.m_thresDist)], what
