@@ -227,6 +227,22 @@ public:
         unsigned int status() const { return c[VH_RESAMPLE_STATUS]; }
     };
     void mergeSceneTransformed(const CUDASceneRepHashSDF& other, const double dstFromSrc[16], MergeCounts* counts = nullptr, ResampleCounts* resampled = nullptr);
+    // Scene registration (DESIGN.md section 4 "Scene registration"; vh_api.h has the rule of vh_align_step): refines the
+    // rigid transform `guess` (4x4 row-major, metres, this scene's frame from other's) so that `other`'s near-surface
+    // voxels fall where this scene's field has their distance: direct SDF-to-SDF Gauss-Newton on the device, up to
+    // options.maxIterations steps enqueued back to back and one read of the state at the end.  Neither scene is written.
+    // result->status tells how it ended (VH_ALIGN_*): only with VH_ALIGN_CONVERGED is result->dstFromSrc an answer; a
+    // scene that leaves a motion free (a lone plane, a lone sphere) ends with VH_ALIGN_ILL_CONDITIONED and the guess
+    // unchanged.  The basin is a few voxels and a few degrees around the guess (the truncation band bounds it; there is
+    // no pyramid); blocks streamed out to a chunk grid are absent; colours are not used.  Throws VH_ERR_BAD_ARGUMENT,
+    // with nothing done, for other == this, a frame in flight in either scene, a guess or a ratio of voxel sizes that
+    // vh_resample_voxel_transforms refuses, options that are not finite and positive or exceed their bounds, and a source
+    // of more than VH_ALIGN_MOST_BLOCKS blocks.
+    struct AlignOptions : VhAlignOptions {
+        AlignOptions() { band = 2.0f; condThres = 1e4f; rotThres = 1e-5; transThres = 1e-3; minCount = 200u; maxIterations = 30u; }
+    };
+    typedef VhAlignState AlignResult;
+    void alignScene(const CUDASceneRepHashSDF& other, const double guess[16], const AlignOptions& options, AlignResult* result);
     // Scene cut (DESIGN.md section 4 "Scene cut"; vh_api.h has the rule of vh_cut_blocks): the opposite of the merge, on
     // the blocks resident in this scene's table.  eraseRegion zeroes the voxels inside the region and frees the blocks
     // in which no observed voxel is left; cropToRegion does that to everything that is not inside.  extractRegion copies

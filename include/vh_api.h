@@ -327,6 +327,42 @@ int vh_resample_blocks(const VhHashData* srcHd, const VhHashParams* srcHp, uint3
                        VhSDFBlockDesc* d_outDescs /* NULL: count */, VhVoxel* d_staging /* NULL: count */, uint32_t stagingBlocks,
                        uint32_t* counts_out, vhStream_t stream);
 
+/* ---- scene registration (not in the reference; DESIGN.md section 4 "Scene registration") -----
+ * The rigid motion that lays a source scene onto a destination scene, by direct SDF-to-SDF Gauss-Newton; neither scene
+ * is written.  The estimate lives in a VhAlignState in device memory; a step is one kernel that reads and updates it.
+ * All geometry is in the destination's voxel index space; the matrices are those of vh_resample_voxel_transforms.
+ * Per voxel v = (i, j, k) of a listed source block with weight > 0 and |sdf_S(v)| <= band * vsSrc (one float product):
+ *   q = dstVoxFromSrcVox v as vh_resample_blocks forms it; dropped unless every |q_r| < 2^24
+ *   seven samples of the destination by the blend of vh_resample_blocks: at q and at q +- 1/2 along each axis
+ *   (q_c + 0.5f, q_c - 0.5f); dropped unless every used tap of all seven is observed
+ *   e = (phi(q) - sdf_S(v)) / vsDst        g_c = (phi(q + e_c / 2) - phi(q - e_c / 2)) / vsDst
+ *   dropped unless |phi(q)| <= band * vsDst and every |g_c| <= 2
+ *   u_c = (q_c - pivot_c) * invRadius; dropped unless every |u_c| <= 1 (pivot and radius are chosen so that this
+ *   drops nothing; the gate is what bounds the terms whatever the estimate does)
+ *   J = (u_y g_z - u_z g_y, u_z g_x - u_x g_z, u_x g_y - u_y g_x, g_x, g_y, g_z)
+ *   29 terms in float, one rounding each: J_a J_b (a <= b, by rows), J_a e, e e, 1; each summed as the 64-bit integer
+ *   rint(term * 2^26) (exact scaling, ties to even): the totals do not depend on the order of the sums.
+ * The step, by one lane, in double: total / 2^26; (J^T J) y = -J^T e by the trackers' 6x6 solve; no step with
+ * VH_ALIGN_TOO_FEW when the count is below minCount, with VH_ALIGN_ILL_CONDITIONED when the solve's condition number is
+ * not <= condThres; otherwise w = y[0..3) * invRadius (radians), tau = y[3..6) (destination voxels),
+ * R = exp([w]x) by Rodrigues, the motion q -> pivot + R (q - pivot) + tau of the destination's voxel space, in metres,
+ * composed onto dstFromSrc from the left, and the voxel matrices derived again; VH_ALIGN_CONVERGED when |w| < rotThres
+ * and |tau| < transThres.
+ * vh_align_begin (BLOCKING): writes the whole state.  VH_ERR_BAD_ARGUMENT for a guess or voxel sizes that
+ * vh_resample_voxel_transforms refuses, a pivot that is not finite, a radius that is not a positive power of two.
+ * vh_align_step: one launch, max(n, 1) workgroups; *d_ticket must be 0 (it is left 0).  VH_ERR_BAD_ARGUMENT, with nothing
+ * launched, for band outside (0, VH_ALIGN_MOST_BAND], thresholds that are not finite and positive, voxel sizes that are
+ * not the state's; for n > VH_ALIGN_MOST_BLOCKS the state's status gets VH_ALIGN_TOO_MANY as well.
+ * vh_time_next_launch applies to vh_align_step. */
+int vh_align_begin(VhAlignState* d_state, const double* dstFromSrcGuess16, float vsSrc, float vsDst, const float pivot3[3], float radius, vhStream_t stream);
+int vh_align_step(const VhHashData* dstHd, const VhHashParams* dstHp, const VhHashData* srcHd, const VhHashParams* srcHp, uint32_t n,
+                  const VhSDFBlockDesc* d_srcDescs, float band, uint32_t minCount, float condThres, double rotThres, double transThres,
+                  VhAlignState* d_state, uint32_t* d_ticket, vhStream_t stream);
+/* The box of the listed blocks: d_box6 = {least x, y, z, greatest x, y, z} of the positions of the first
+ * min(n, *d_count) blocks (d_count NULL: n; a device word, so that a list's length need not be read back first).
+ * d_box6 must hold INT_MAX thrice and INT_MIN thrice before. */
+int vh_align_bounds(uint32_t n, const VhSDFBlockDesc* d_descs, const uint32_t* d_count /* may be NULL */, int32_t* d_box6, vhStream_t stream);
+
 /* ---- scene cut (not in the reference; DESIGN.md section 4 "Scene cut") -----
  * The opposite of the merge: the voxels of a region erased from the table, lifted out as a block list, or both.
  * All geometry is in voxel index space.  Voxel l of the block at pos is the integer triple (i, j, k) = 8 pos +
@@ -444,6 +480,11 @@ int vh_debug_check_weighted_colour(uint32_t* d_out, vhStream_t stream);
 /* The take-out rule of vh_deintegrate_blocks alone, on arrays of voxels: d_out[i] = d_observed[i] taken out of
  * d_stored[i] under hp's colour mode (an observation of weight 0 is no observation).  No camera is needed. */
 int vh_debug_deintegrate_rule(const VhVoxel* d_stored, const VhVoxel* d_observed, VhVoxel* d_out, uint32_t n, const VhHashParams* hp, vhStream_t stream);
+/* The per-voxel rule of vh_align_step alone: per voxel l of listed block b, record (b * 512 + l) of d_out, 37 words:
+ * [0] 1 if the voxel contributes, else 0 and the rest 0; [1..4) q; [4] e; [5..8) g; [8..37) the 29 float terms. */
+int vh_debug_align_rule(const VhHashData* dstHd, const VhHashParams* dstHp, const VhHashData* srcHd, const VhHashParams* srcHp, uint32_t n,
+                        const VhSDFBlockDesc* d_srcDescs, const float* dstVoxFromSrcVox12, const float pivot3[3], float invRadius, float band,
+                        float* d_out, vhStream_t stream);
 /* measurement, not part of the path: every SIMD of the device runs `wavesPerSimd` waves (1..8), each a chain-free stream of
  * 32 * iters vector instructions (mode 0 v_fma_f32, 1 v_pk_fma_f32, 2 v_add_u32, 3 v_mul_lo_u32); per wave
  * {start, end in 100 MHz ticks, s_memtime ticks spent, HW_ID[19:0] | XCC_ID << 20} into d_stamps (4 words per wave, *numWaves waves: room for
@@ -511,6 +552,14 @@ int vh_scene_rep_merge_blocks(VhSceneRep* dst, const VhSDFBlockDesc* d_descs, co
  * in either case.  Blocking; compactify before the next ray cast. */
 int vh_scene_rep_merge_scene_transformed(VhSceneRep* dst, VhSceneRep* src, const double* dstFromSrc16, uint32_t mergeCounts[VH_MERGE_NUM_COUNTS],
                                          uint32_t resampleCounts[VH_RESAMPLE_NUM_COUNTS]);
+/* alignScene (include/vh.hpp): the rigid transform that lays src onto dst, refined from guess16 on the device:
+ * vh_merge_gather on src, vh_align_bounds and one read-back for the pivot and the radius, vh_align_begin, up to
+ * options->maxIterations vh_align_step launches back to back, one read of the state into *result.  src's stream is
+ * ordered before dst's, as for the merge.  Neither scene is written.  VH_ERR_BAD_ARGUMENT, with nothing done, for
+ * src == dst, a guess or voxel sizes that vh_resample_voxel_transforms refuses, options that are not finite and positive
+ * or beyond their bounds, a frame in flight, more than VH_ALIGN_MOST_BLOCKS source blocks.  How the registration ended
+ * is in result->status. */
+int vh_scene_rep_align_scene(VhSceneRep* dst, VhSceneRep* src, const double* guess16, const VhAlignOptions* options, VhAlignState* result);
 /* eraseRegion / cropToRegion / extractRegion / moveRegionTo (include/vh.hpp): vh_cut_blocks on the blocks resident in
  * the scene's table (vh_merge_gather), on the scene's stream, with a lock token of the scene's own.  erase_region zeroes
  * the region's voxels and frees the blocks that hold nothing any more; crop_to_region does that to everything outside.

@@ -222,6 +222,58 @@ enum {
     VH_DEINT_NUM_COUNTS = 10
 };
 
+/* Scene registration (vh_align_begin / vh_align_step; DESIGN.md section 4 "Scene registration"): bits of the state's
+ * status word, the places of the 29 totals, and the state itself.  A state whose status has any bit set takes no
+ * further step: a launch that finds it so returns at once and changes no word of it. */
+#define VH_ALIGN_CONVERGED 1u        /* the last step's rotation and translation were below the thresholds (the step was taken) */
+#define VH_ALIGN_TOO_FEW 2u          /* fewer than minCount voxels contributed: no step */
+#define VH_ALIGN_ILL_CONDITIONED 4u  /* the condition number of J^T J exceeds condThres (or is not a number): no step */
+#define VH_ALIGN_OUT_OF_RANGE 8u     /* a listed block lies outside [-2^20, 2^20), or its samples reach more destination blocks than the bound: no step */
+#define VH_ALIGN_TOO_MANY 16u        /* more than VH_ALIGN_MOST_BLOCKS listed blocks: nothing was launched (a total could wrap) */
+#define VH_ALIGN_ITERATIONS_SPENT 32u /* VH_ALIGN_MAX_ITERATIONS steps were taken */
+#define VH_ALIGN_MAX_ITERATIONS 64u
+#define VH_ALIGN_MOST_BLOCKS (1u << 19)
+#define VH_ALIGN_MOST_BAND 4.0f      /* the band in voxels: bounds the residual, and with it every term */
+#define VH_ALIGN_QUANTUM_LOG2 26     /* a term t is summed as the integer rint(t * 2^26) */
+#define VH_ALIGN_NUM_STRIPES 32u
+enum {
+    VH_ALIGN_JTJ = 0,    /* 21 words: the upper triangle of J^T J by rows (00 01 .. 05 11 12 ..) */
+    VH_ALIGN_JTE = 21,   /* 6 words: J^T e */
+    VH_ALIGN_EE = 27,    /* e e */
+    VH_ALIGN_COUNT = 28, /* the contributing voxels (each adds 1.0, that is 2^26) */
+    VH_ALIGN_NUM_TERMS = 29
+};
+typedef struct VhAlignState {
+    double dstFromSrc[16];      /* the current estimate, metres, row-major [R | t] */
+    float srcVoxFromDstVox[12]; /* the two voxel matrices of the estimate, by the formulas of vh_resample_voxel_transforms */
+    float dstVoxFromSrcVox[12];
+    float pivot[3];             /* destination voxel index space */
+    float invRadius;            /* a power of two */
+    float vsSrc, vsDst;
+    uint32_t iterations;        /* steps attempted (a refused one counts) */
+    uint32_t status;
+    uint32_t raised;            /* status bits raised by the workgroups of the launch in flight; 0 between launches */
+    uint32_t reserved;
+    /* per attempted step k < iterations */
+    uint32_t count[VH_ALIGN_MAX_ITERATIONS];          /* contributing voxels */
+    float condition[VH_ALIGN_MAX_ITERATIONS];         /* of J^T J, as vh's 6x6 solve reports it */
+    double sumSquares[VH_ALIGN_MAX_ITERATIONS];       /* sum of e e, voxels squared */
+    double stepRotation[VH_ALIGN_MAX_ITERATIONS];     /* radians (0 for a refused step) */
+    double stepTranslation[VH_ALIGN_MAX_ITERATIONS];  /* destination voxels */
+    long long totals[32];       /* the last attempted step's 29 integer totals */
+    long long stripes[VH_ALIGN_NUM_STRIPES * 32]; /* where the launch in flight adds; all zero between launches */
+} VhAlignState;
+/* what vh_scene_rep_align_scene takes: every field finite and positive, band <= VH_ALIGN_MOST_BAND, maxIterations <=
+ * VH_ALIGN_MAX_ITERATIONS */
+typedef struct VhAlignOptions {
+    float band;             /* voxels: a voxel contributes while |sdf| <= band * voxel size, in both scenes (default 2) */
+    float condThres;        /* the largest condition number of J^T J that is answered with a step (default 1e4) */
+    double rotThres;        /* radians: converged when a step turns by less ... (default 1e-5) */
+    double transThres;      /* destination voxels: ... and moves by less (default 1e-3) */
+    uint32_t minCount;      /* the fewest contributing voxels that are answered with a step (default 200) */
+    uint32_t maxIterations; /* launches enqueued (default 30) */
+} VhAlignOptions;
+
 /* DepthCameraData, DSC/DepthCameraUtil.h:17-159: the two image buffers the
  * path reads (the cudaArray/texture twins of the reference are not needed:
  * images are read with plain cached loads). */

@@ -137,6 +137,13 @@ int vh_scene_rep_merge_scene_transformed(VhSceneRep* dst, VhSceneRep* src, const
     std::memcpy(resampleCounts, r.c, sizeof(r.c));
     return rc;
 }
+int vh_scene_rep_align_scene(VhSceneRep* dst, VhSceneRep* src, const double* guess16, const VhAlignOptions* options, VhAlignState* result)
+{
+    if (!dst || !src || !guess16 || !options || !result) return VH_ERR_BAD_ARGUMENT;
+    CUDASceneRepHashSDF::AlignOptions o;
+    static_cast<VhAlignOptions&>(o) = *options;
+    return guarded([&] { dst->impl.alignScene(src->impl, guess16, o, result); });
+}
 int vh_scene_rep_merge_blocks(VhSceneRep* dst, const VhSDFBlockDesc* d_descs, const VhVoxel* d_blocks, uint32_t n, const int32_t blockOffset[3],
                               uint32_t* d_leftOut, uint32_t counts[VH_MERGE_NUM_COUNTS])
 {

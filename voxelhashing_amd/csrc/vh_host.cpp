@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <array>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <unordered_set>
@@ -805,6 +806,68 @@ void CUDASceneRepHashSDF::mergeSceneTransformed(const CUDASceneRepHashSDF& other
     check(vh_merge_blocks(&m_hashData, &m_hashParams, numStaged, staged.get(), nullptr, staging.get(), zero, token,
                           reinterpret_cast<uint32_t*>(mergeWork.get()), nullptr, c.c, m_stream), "vh_merge_blocks");
     if (c.status() & VH_MERGE_HEAP_SHORT) throw vh::Error(VH_ERR_HEAP_EXHAUSTED, "mergeSceneTransformed: the resampled source holds more new blocks than the heap has free");
+}
+
+// ---- scene registration (vh_align.hip; DESIGN.md section 4 "Scene registration")
+
+void CUDASceneRepHashSDF::alignScene(const CUDASceneRepHashSDF& other, const double guess[16], const AlignOptions& o, AlignResult* result)
+{
+    if (!guess || !result) throw vh::Error(VH_ERR_BAD_ARGUMENT, "alignScene: null argument");
+    if (&other == this) throw vh::Error(VH_ERR_BAD_ARGUMENT, "alignScene: a scene cannot be aligned to itself");
+    if (m_aheadPending || other.m_aheadPending) throw vh::Error(VH_ERR_BAD_ARGUMENT, "alignScene: between integrateAhead() and integrateFinish()");
+    if (!std::isfinite(o.band) || !(o.band > 0.0f) || !(o.band <= VH_ALIGN_MOST_BAND) || !std::isfinite(o.condThres) || !(o.condThres > 0.0f) ||
+        !std::isfinite(o.rotThres) || !(o.rotThres > 0.0) || !std::isfinite(o.transThres) || !(o.transThres > 0.0) || o.minCount == 0u ||
+        o.maxIterations == 0u || o.maxIterations > VH_ALIGN_MAX_ITERATIONS)
+        throw vh::Error(VH_ERR_BAD_ARGUMENT, "alignScene: an option is not finite and positive, or exceeds its bound");
+    const float vsSrc = other.m_hashParams.m_virtualVoxelSize, vsDst = m_hashParams.m_virtualVoxelSize;
+    float srcFromDst[12], dstFromSrcVox[12];
+    check(vh_resample_voxel_transforms(guess, vsSrc, vsDst, srcFromDst, dstFromSrcVox),
+          "alignScene: the guess is not rigid, or the voxel sizes differ by more than a factor of 2");
+    vh::Event done;
+    if (other.m_stream != m_stream) {
+        done = vh::makeEvent(false);
+        checkHip(hipEventRecord((hipEvent_t)done.get(), (hipStream_t)other.m_stream), "hipEventRecord");
+        checkHip(hipStreamWaitEvent((hipStream_t)m_stream, (hipEvent_t)done.get(), 0), "hipStreamWaitEvent");
+    }
+    // the source's entries as a block list, and their box: one read-back for both
+    const uint32_t capacity = other.m_hashParams.m_numSDFBlocks;
+    vh::DevicePtr<SDFBlockDesc> descs = vh::deviceAlloc<SDFBlockDesc>(capacity, "align block list");
+    vh::DevicePtr<int32_t> words = vh::deviceAlloc<int32_t>(8, "align block count and box"); // n, the ticket, the box
+    int32_t h[8] = { 0, 0, INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN };
+    check(vh_memcpy_h2d(words.get(), h, sizeof(h), m_stream), "alignScene");
+    uint32_t* counter = reinterpret_cast<uint32_t*>(words.get());
+    check(vh_merge_gather(&other.m_hashData, &other.m_hashParams, descs.get(), capacity, counter, m_stream), "vh_merge_gather");
+    check(vh_align_bounds(capacity, descs.get(), counter, words.get() + 2, m_stream), "vh_align_bounds");
+    check(vh_memcpy_d2h(h, words.get(), sizeof(h), m_stream), "alignScene");
+    const uint32_t n = (uint32_t)h[0];
+    if (n > capacity) throw vh::Error(VH_ERR_BAD_ARGUMENT, "alignScene: the source's table holds more entries than its pool has blocks");
+    if (n > VH_ALIGN_MOST_BLOCKS) throw vh::Error(VH_ERR_BAD_ARGUMENT, "alignScene: the source holds more blocks than the fixed-point totals allow");
+    // pivot: the image of the box's centre under the guess, a whole voxel; radius: the power of two that holds the box's
+    // image about the pivot with a quarter to spare and 16 voxels for the way the estimate may go
+    float pivot[3] = { 0.0f, 0.0f, 0.0f };
+    double reach = 0.0;
+    if (n != 0) {
+        double centre[3], half[3];
+        for (int c = 0; c < 3; c++) {
+            const double lo = 8.0 * (double)h[2 + c], hi = 8.0 * (double)h[5 + c] + 7.0;
+            centre[c] = 0.5 * (lo + hi);
+            half[c] = 0.5 * (hi - lo);
+        }
+        for (int r = 0; r < 3; r++) {
+            const float* m = &dstFromSrcVox[4 * r];
+            pivot[r] = (float)std::nearbyint((double)m[0] * centre[0] + (double)m[1] * centre[1] + (double)m[2] * centre[2] + (double)m[3]);
+            reach = std::max(reach, std::fabs((double)m[0]) * half[0] + std::fabs((double)m[1]) * half[1] + std::fabs((double)m[2]) * half[2] + 0.5);
+        }
+    }
+    float radius = 32.0f;
+    while ((double)radius < 1.25 * reach + 16.0) radius *= 2.0f;
+    vh::DevicePtr<VhAlignState> state = vh::deviceAlloc<VhAlignState>(1, "align state");
+    check(vh_align_begin(state.get(), guess, vsSrc, vsDst, pivot, radius, m_stream), "vh_align_begin");
+    uint32_t* ticket = counter + 1; // (0 since the upload above; every launch leaves it 0)
+    for (uint32_t k = 0; k < o.maxIterations; k++)
+        check(vh_align_step(&m_hashData, &m_hashParams, &other.m_hashData, &other.m_hashParams, n, descs.get(), o.band, o.minCount, o.condThres, o.rotThres,
+                            o.transThres, state.get(), ticket, m_stream), "vh_align_step");
+    check(vh_memcpy_d2h(result, state.get(), sizeof(*result), m_stream), "alignScene");
 }
 
 // ---- scene cut (vh_cut.hip; DESIGN.md section 4 "Scene cut")

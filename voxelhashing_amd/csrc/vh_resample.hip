@@ -12,6 +12,7 @@
 #include "vh_device.hpp"
 #include "vh_host_util.hpp"
 #include "vh_mesh_table.hpp"
+#include "vh_resample_blend.hpp"
 
 using namespace vhd;
 
@@ -33,10 +34,7 @@ enum {
 
 constexpr int kBlockLimit = 1 << 20;   // block coordinates in [-2^20, 2^20): voxel coordinates below 2^23, exact in a float
 constexpr uint32_t kMostSpan = 6;      // candidate blocks per axis and source block (ratio 2)
-constexpr int kMostReach = 5;          // source blocks per axis a destination block's taps reach (ratio 1/2)
-constexpr float kMostCoord = 16777216.0f;
-
-struct M34 { float m[12]; }; // row-major 3x4, voxel index space
+// (kMostReach, the source blocks per axis a destination block's taps reach, kMostCoord and M34: vh_resample_blend.hpp)
 
 struct Work {
     uint32_t* header;
@@ -55,11 +53,6 @@ Work carve(uint32_t* d_work, uint32_t slotsLog2)
     return w;
 }
 
-// one row of the rule's position: ((m0 i + m1 j) + m2 k) + m3, one rounding per operation.  Every operation is monotone
-// in its arguments, so the row is monotone in each of i, j, k: over a box of voxels it takes its least and its greatest
-// value at corners of the box, in float as in exact arithmetic.
-VHD float row(const float* r, float i, float j, float k) { return ((r[0] * i + r[1] * j) + r[2] * k) + r[3]; }
-
 VHD bool block_in_range(I3 p)
 {
     return p.x >= -kBlockLimit && p.x < kBlockLimit && p.y >= -kBlockLimit && p.y < kBlockLimit && p.z >= -kBlockLimit && p.z < kBlockLimit;
@@ -73,19 +66,6 @@ VHD unsigned long long block_key(I3 p)
 VHD I3 key_block(unsigned long long k)
 {
     return mki3((int)(k & 0x1fffffull) - kBlockLimit, (int)((k >> 21) & 0x1fffffull) - kBlockLimit, (int)((k >> 42) & 0x1fffffull) - kBlockLimit);
-}
-
-// the least and the greatest of a row over the eight corners of the box [lo, hi]^3 of voxel coordinates
-VHD void row_range(const float* r, const float* lo, const float* hi, float& least, float& most)
-{
-    least = pinf();
-    most = minf();
-#pragma unroll
-    for (int c = 0; c < 8; c++) {
-        const float q = row(r, (c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]);
-        least = fminf(least, q);
-        most = fmaxf(most, q);
-    }
 }
 
 // A wave per source block, a lane per candidate.  Positions with a tap in block b are those of [8b - 1, 8b + 8)^3; the
@@ -147,53 +127,13 @@ __global__ __launch_bounds__(256) void k_resample_candidates(uint32_t n, const V
     if (status != 0u) atomicOr(&w.header[W_STATUS], status);
 }
 
-// One destination voxel by the rule.  s_ptr: the pointers of the source blocks [loB, loB + dim) the workgroup resolved.
-// The eight loads are issued before the first is used.
+// One destination voxel by the rule: its position in the source, then the blend the registration shares
+// (vh_resample_blend.hpp).  s_ptr: the pointers of the source blocks [loB, loB + dim) the workgroup resolved.
 VHD uint2 resample_voxel(const VhVoxel* __restrict__ pool, const int* s_ptr, I3 loB, I3 dim, const M34& m, float i, float j, float k)
 {
     const float qx = row(&m.m[0], i, j, k), qy = row(&m.m[4], i, j, k), qz = row(&m.m[8], i, j, k);
     if (!(fabsf(qx) < kMostCoord) || !(fabsf(qy) < kMostCoord) || !(fabsf(qz) < kMostCoord)) return make_uint2(0u, 0u);
-    const float bx = floorf(qx), by = floorf(qy), bz = floorf(qz);
-    const float fx = qx - bx, fy = qy - by, fz = qz - bz;
-    const float gx = 1.0f - fx, gy = 1.0f - fy, gz = 1.0f - fz;
-    const int ix = (int)bx, iy = (int)by, iz = (int)bz;
-    float wt[8];
-    uint2 v[8];
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        wt[t] = (((t & 1) ? fx : gx) * ((t & 2) ? fy : gy)) * ((t & 4) ? fz : gz);
-        v[t] = make_uint2(0u, 0u); // (a tap in a block the source does not hold reads as unobserved)
-        if (wt[t] != 0.0f) {
-            const int vx = ix + (t & 1), vy = iy + ((t >> 1) & 1), vz = iz + ((t >> 2) & 1);
-            const int tx = (vx >> 3) - loB.x, ty = (vy >> 3) - loB.y, tz = (vz >> 3) - loB.z;
-            int ptr = VH_FREE_ENTRY;
-            if ((uint32_t)tx < (uint32_t)dim.x && (uint32_t)ty < (uint32_t)dim.y && (uint32_t)tz < (uint32_t)dim.z) ptr = s_ptr[(tz * dim.y + ty) * dim.x + tx];
-            if (ptr != VH_FREE_ENTRY)
-                v[t] = *reinterpret_cast<const uint2*>(&pool[(uint32_t)ptr + (uint32_t)(((vz & 7) * 8 + (vy & 7)) * 8 + (vx & 7))]);
-        }
-    }
-    bool first = true, ok = true;
-    float sdf = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-    uint32_t weight = 255u;
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        if (wt[t] != 0.0f) {
-            const uint32_t cw = v[t].y;
-            ok = ok && (cw >> 24) != 0u;
-            weight = min(weight, cw >> 24);
-            const float ps = wt[t] * __uint_as_float(v[t].x);
-            const float pr = wt[t] * (float)(cw & 0xffu), pg = wt[t] * (float)((cw >> 8) & 0xffu), pb = wt[t] * (float)((cw >> 16) & 0xffu);
-            // from the first product, not from 0: -0 stays -0
-            sdf = first ? ps : sdf + ps;
-            cr = first ? pr : cr + pr;
-            cg = first ? pg : cg + pg;
-            cb = first ? pb : cb + pb;
-            first = false;
-        }
-    }
-    if (!ok || first) return make_uint2(0u, 0u);
-    const uint32_t r = (uint32_t)min(255, f2i(cr + 0.5f)), g = (uint32_t)min(255, f2i(cg + 0.5f)), bl = (uint32_t)min(255, f2i(cb + 0.5f));
-    return make_uint2(__float_as_uint(sdf), pack_cw(r, g, bl, weight));
+    return blend_taps(pool, s_ptr, loB, dim, qx, qy, qz);
 }
 
 // The hot path: one workgroup of 256 per candidate block, one 16-byte pair of voxels per lane (voxels 2t and 2t + 1 of
@@ -323,14 +263,7 @@ int vh_resample_voxel_transforms(const double* T, float vsSrc, float vsDst, floa
     const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
                        R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
     if (!(det > 0.0)) return VH_ERR_BAD_ARGUMENT;
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) {
-            srcVoxFromDstVox[4 * r + c] = (float)(R[c][r] * (d / s));
-            dstVoxFromSrcVox[4 * r + c] = (float)(R[r][c] * (s / d));
-        }
-        srcVoxFromDstVox[4 * r + 3] = (float)(-((R[0][r] * t[0] + R[1][r] * t[1]) + R[2][r] * t[2]) / s);
-        dstVoxFromSrcVox[4 * r + 3] = (float)(t[r] / d);
-    }
+    voxel_matrices(T, s, d, srcVoxFromDstVox, dstVoxFromSrcVox);
     return VH_OK;
 }
 

@@ -349,6 +349,22 @@ class CUDASceneRepHashSDF:
         out.update(extra)
         return out
 
+    # ---- scene registration (DESIGN.md section 4 "Scene registration") ----------------------------------------------
+    def alignScene(self, other, guess=None, options=None, **overrides):
+        """Refines the rigid 4x4 `guess` (metres; a point of other's frame in this scene's; default the identity) so that
+        other's near-surface voxels fall where this scene's field has their distance: direct SDF-to-SDF Gauss-Newton on
+        the device (vh_api.h has the rule of vh_align_step).  Neither scene is written.  options: a vhtypes.AlignOptions
+        (make_align_options), or its fields by keyword -> vhtypes.align_state_dict of the state: "dst_from_src" is an
+        answer only where "converged"; "status" tells how it ended otherwise (vhtypes.ALIGN_*).  The basin is a few
+        voxels and a few degrees around the guess.  Raises VhError (VH_ERR_BAD_ARGUMENT, nothing done) for other is
+        self, a guess that is not rigid, voxel sizes further apart than a factor of 2, options that are not finite and
+        positive or beyond their bounds, a frame in flight."""
+        m = np.ascontiguousarray(np.eye(4) if guess is None else guess, dtype=np.float64).reshape(16)
+        o = options if options is not None else T.make_align_options(**overrides)
+        st = T.AlignState()
+        check(self.L.vh_scene_rep_align_scene(self.handle, other.handle, m.ctypes.data, C.byref(o), C.byref(st)), "CUDASceneRepHashSDF::alignScene")
+        return T.align_state_dict(st)
+
     # ---- scene cut (DESIGN.md section 4 "Scene cut") ---------------------------------------------------------------
     def eraseRegion(self, region):
         """Zeroes the voxels inside `region` (a vhtypes.CutRegion: make_cut_region) and frees the blocks in which no
@@ -1029,6 +1045,64 @@ class LauncherScene:
         out = {k: int(v) for k, v in zip(T.DEINT_COUNTS, counts)}
         out["code"] = rc
         return out
+
+    def align_begin(self, source, guess, pivot, radius):
+        """vh_align_begin for `source` (a LauncherScene) against this scene -> (the state in device memory, the ticket
+        word, the call's return code)"""
+        m = np.ascontiguousarray(guess, dtype=np.float64).reshape(16)
+        p = np.ascontiguousarray(pivot, dtype=np.float32).reshape(3)
+        d_state, d_ticket = DeviceBuffer(C.sizeof(T.AlignState)), DeviceBuffer(4)
+        check(self.L.vh_memset(d_state.ptr, 0, d_state.nbytes, self.stream), "memset")
+        check(self.L.vh_memset(d_ticket.ptr, 0, 4, self.stream), "memset")
+        rc = self.L.vh_align_begin(d_state.ptr, m.ctypes.data, float(source.hp.m_virtualVoxelSize), float(self.hp.m_virtualVoxelSize), p.ctypes.data,
+                                   float(radius), self.stream)
+        return d_state, d_ticket, rc
+
+    def align_state(self, d_state, d_ticket=None):
+        """the state read back -> vhtypes.align_state_dict, with "ticket" where the word is given"""
+        st = T.AlignState.from_buffer_copy(d_state.download(np.uint8, C.sizeof(T.AlignState), self.stream).tobytes())
+        out = T.align_state_dict(st)
+        out["stripes"] = np.array(st.stripes[:], np.int64)
+        out["raised"] = int(st.raised)
+        if d_ticket is not None:
+            out["ticket"] = int(d_ticket.download(np.uint32, 1, self.stream)[0])
+        return out
+
+    def align_step(self, source, d_state, d_ticket, descs=None, n=None, band=2.0, min_count=200, cond_thres=1e4, rot_thres=1e-5, trans_thres=1e-3,
+                   steps=1):
+        """vh_align_step, `steps` launches back to back: `source`'s blocks (vh_merge_gather on it, or descs: a
+        DESC_DTYPE array or a DeviceBuffer with n) against this scene -> (align_state afterwards, the last return code)"""
+        if descs is None:
+            d_desc, n = source.merge_gather()
+        elif isinstance(descs, DeviceBuffer):
+            d_desc, n = descs, (descs.nbytes // 16 if n is None else n)
+        else:
+            descs = np.ascontiguousarray(descs, dtype=T.DESC_DTYPE)
+            d_desc, n = (DeviceBuffer.from_numpy(descs, self.stream) if len(descs) else DeviceBuffer(16)), len(descs)
+        rc = 0
+        for _ in range(steps):
+            rc = self.L.vh_align_step(C.byref(self.hd), C.byref(self.hp), C.byref(source.hd), C.byref(source.hp), n, d_desc.ptr, float(band), int(min_count),
+                                      float(cond_thres), float(rot_thres), float(trans_thres), d_state.ptr, d_ticket.ptr, self.stream)
+        return self.align_state(d_state, d_ticket), rc
+
+    def align_rule(self, source, dst_vox_from_src_vox, pivot, inv_radius, band=2.0, descs=None):
+        """vh_debug_align_rule: the per-voxel rule on `source`'s blocks (descs: DESC_DTYPE with the blocks' ptr, default
+        vh_merge_gather on it) against this scene -> dict descs, kept [n, 512] bool, q [n, 512, 3], e [n, 512],
+        g [n, 512, 3], terms [n, 512, 29] (float32; all zero where not kept)"""
+        b = np.ascontiguousarray(dst_vox_from_src_vox, dtype=np.float32).reshape(12)
+        p = np.ascontiguousarray(pivot, dtype=np.float32).reshape(3)
+        if descs is None:
+            d_desc, n = source.merge_gather()
+        else:
+            descs = np.ascontiguousarray(descs, dtype=T.DESC_DTYPE)
+            d_desc, n = DeviceBuffer.from_numpy(descs, self.stream), len(descs)
+        W, V = T.ALIGN_RULE_WORDS, T.SDF_BLOCK_VOXELS
+        d_out = DeviceBuffer(4 * W * V * max(n, 1))
+        check(self.L.vh_debug_align_rule(C.byref(self.hd), C.byref(self.hp), C.byref(source.hd), C.byref(source.hp), n, d_desc.ptr, b.ctypes.data, p.ctypes.data,
+                                         float(inv_radius), float(band), d_out.ptr, self.stream), "vh_debug_align_rule")
+        rec = d_out.download(np.float32, W * V * n, self.stream).reshape(n, V, W)
+        return dict(descs=d_desc.download(T.DESC_DTYPE, n, self.stream), kept=rec[:, :, 0].view(np.uint32) != 0, q=rec[:, :, 1:4], e=rec[:, :, 4],
+                    g=rec[:, :, 5:8], terms=rec[:, :, 8:])
 
     def resample_blocks(self, src_vox_from_dst_vox, dst_vox_from_src_vox, slots_log2=None):
         """vh_merge_gather on this table, then vh_resample_blocks, count and fill: this scene sampled on another lattice

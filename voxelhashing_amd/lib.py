@@ -105,6 +105,13 @@ PROTOTYPES = {
     "vh_resample_work_bytes": (C.c_size_t, [C.c_uint32]),
     "vh_resample_blocks": (C.c_int, [P(T.HashData), P(T.HashParams), C.c_uint32, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, C.c_uint32, _VP, _VP]),
     "vh_scene_rep_merge_scene_transformed": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "vh_align_begin": (C.c_int, [_VP, _VP, C.c_float, C.c_float, _VP, C.c_float, _VP]),
+    "vh_align_step": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.HashData), P(T.HashParams), C.c_uint32, _VP, C.c_float, C.c_uint32, C.c_float,
+                                C.c_double, C.c_double, _VP, _VP, _VP]),
+    "vh_align_bounds": (C.c_int, [C.c_uint32, _VP, _VP, _VP, _VP]),
+    "vh_debug_align_rule": (C.c_int, [P(T.HashData), P(T.HashParams), P(T.HashData), P(T.HashParams), C.c_uint32, _VP, _VP, _VP, C.c_float, C.c_float,
+                                      _VP, _VP]),
+    "vh_scene_rep_align_scene": (C.c_int, [_VP, _VP, _VP, P(T.AlignOptions), P(T.AlignState)]),
     "vh_cut_region_transform": (C.c_int, [_VP, _VP, C.c_float, _VP]),
     "vh_cut_work_bytes": (C.c_size_t, [C.c_uint32]),
     "vh_cut_blocks": (C.c_int, [P(T.HashData), P(T.HashParams), C.c_uint32, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_int32, _VP, _VP, _VP, C.c_uint32,

@@ -550,7 +550,19 @@ class Reconstruction:
         return read
 
     # -- around the loop ------------------------------------------------------------------------------------------
-    def mergeFrom(self, other, block_offset=(0, 0, 0), transform=None):
+    def alignTo(self, other, guess=None, **options):
+        """The rigid transform that lays this reconstruction's model onto `other`'s (not in the reference; DESIGN.md
+        section 4 "Scene registration"): other.scene.alignScene(self.scene, guess) -> its result: "dst_from_src" (4x4,
+        metres: a point of this world frame in other's) is an answer only where "converged".  Neither model is written.
+        guess: a rough transform (odometry, a marker, an earlier session's pose; default the identity): the basin is a few
+        voxels and a few degrees around it.  Blocks either chunk grid holds on the host are absent, as for every query.
+        options: the fields of vhtypes.make_align_options.  A native loop of either side is synchronised first."""
+        for r in (self, other):
+            if r.native is not None:
+                r.native.synchronize()
+        return other.scene.alignScene(self.scene, guess, **options)
+
+    def mergeFrom(self, other, block_offset=(0, 0, 0), transform=None, align=False, **align_options):
         """Fuses another reconstruction's model into this one (not in the reference; DESIGN.md section 4 "Scene merge"):
         the blocks resident in other's table (CUDASceneRepHashSDF.mergeScene) and, if other streams, the blocks its chunk
         grid holds on the host (downloadHostBlocks, upload, mergeBlocks), all shifted by whole blocks.  This scene must
@@ -559,17 +571,27 @@ class Reconstruction:
         With transform (a rigid 4x4, metres: a point of other's world frame in this one's) other is resampled onto this
         scene's lattice instead (mergeSceneTransformed; DESIGN.md section 4 "Resampled merge"; the voxel sizes may differ by
         up to a factor of 2, block_offset must be zero).  Then other, too, must hold every block on the device
-        (ValueError otherwise): a tap that crosses from a device block into a host block would read as unobserved."""
+        (ValueError otherwise): a tap that crosses from a device block into a host block would read as unobserved.
+        With align=True the transform (default the identity) is only a guess: it is refined first (other.alignTo(self,
+        transform); DESIGN.md section 4 "Scene registration") and other is merged under the result, which is appended to
+        the returned list under "align"; a registration that does not converge raises ValueError with nothing merged."""
         for r in (self, other):
             if r.native is not None:
                 r.native.synchronize()
         if self.chunk_grid is not None and self.chunk_grid.getStatistics()["blocks"] != 0:
             raise ValueError("mergeFrom: the destination's chunk grid holds blocks on the host; stream them in first")
+        if align and transform is None:
+            transform = np.eye(4)
         if transform is not None:
             if tuple(int(v) for v in block_offset) != (0, 0, 0):
                 raise ValueError("mergeFrom: a transform and a block offset exclude each other; put the shift into the transform")
             if other.chunk_grid is not None and other.chunk_grid.getStatistics()["blocks"] != 0:
                 raise ValueError("mergeFrom: with a transform the source's chunk grid must hold no blocks on the host; stream them in first")
+            if align:
+                found = self.scene.alignScene(other.scene, transform, **align_options)
+                if not found["converged"]:
+                    raise ValueError(f"mergeFrom: the registration did not converge (status {found['status']}, {found['iterations']} steps); nothing was merged")
+                return [self.scene.mergeSceneTransformed(other.scene, found["dst_from_src"]), {"align": found}]
             return [self.scene.mergeSceneTransformed(other.scene, transform)]
         out = [self.scene.mergeScene(other.scene, block_offset)]
         if other.chunk_grid is not None:

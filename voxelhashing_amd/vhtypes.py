@@ -181,6 +181,51 @@ DEINT_COUNT_ONLY = 1
 DEINT_NOT_SETTLED = 1
 DEINT_COUNTS = ("blocks_in", "processed", "changed", "freed", "voxels_changed", "voxels_reset", "voxels_at_cap", "delete_passes", "unsettled", "status")
 
+# VH_ALIGN_*: bits of the scene registration's status word, its limits, the places of its 29 totals
+ALIGN_CONVERGED, ALIGN_TOO_FEW, ALIGN_ILL_CONDITIONED, ALIGN_OUT_OF_RANGE, ALIGN_TOO_MANY, ALIGN_ITERATIONS_SPENT = 1, 2, 4, 8, 16, 32
+ALIGN_MAX_ITERATIONS, ALIGN_MOST_BLOCKS, ALIGN_MOST_BAND, ALIGN_QUANTUM_LOG2, ALIGN_NUM_STRIPES = 64, 1 << 19, 4.0, 26, 32
+ALIGN_JTJ, ALIGN_JTE, ALIGN_EE, ALIGN_COUNT, ALIGN_NUM_TERMS = 0, 21, 27, 28, 29
+ALIGN_RULE_WORDS = 37  # vh_debug_align_rule's record: kept, q[3], e, g[3], the 29 float terms
+
+
+class AlignState(C.Structure):  # VhAlignState
+    _fields_ = [
+        ("dstFromSrc", C.c_double * 16), ("srcVoxFromDstVox", C.c_float * 12), ("dstVoxFromSrcVox", C.c_float * 12),
+        ("pivot", C.c_float * 3), ("invRadius", C.c_float), ("vsSrc", C.c_float), ("vsDst", C.c_float),
+        ("iterations", C.c_uint32), ("status", C.c_uint32), ("raised", C.c_uint32), ("reserved", C.c_uint32),
+        ("count", C.c_uint32 * ALIGN_MAX_ITERATIONS), ("condition", C.c_float * ALIGN_MAX_ITERATIONS),
+        ("sumSquares", C.c_double * ALIGN_MAX_ITERATIONS), ("stepRotation", C.c_double * ALIGN_MAX_ITERATIONS),
+        ("stepTranslation", C.c_double * ALIGN_MAX_ITERATIONS),
+        ("totals", C.c_longlong * 32), ("stripes", C.c_longlong * (ALIGN_NUM_STRIPES * 32)),
+    ]
+
+
+class AlignOptions(C.Structure):  # VhAlignOptions
+    _fields_ = [("band", C.c_float), ("condThres", C.c_float), ("rotThres", C.c_double), ("transThres", C.c_double),
+                ("minCount", C.c_uint32), ("maxIterations", C.c_uint32)]
+
+
+def make_align_options(band=2.0, cond_thres=1e4, rot_thres=1e-5, trans_thres=1e-3, min_count=200, max_iterations=30):
+    """the defaults of CUDASceneRepHashSDF::AlignOptions (include/vh.hpp)"""
+    return AlignOptions(float(band), float(cond_thres), float(rot_thres), float(trans_thres), int(min_count), int(max_iterations))
+
+
+def align_state_dict(st):
+    """an AlignState as plain Python: the pose [4, 4], the matrices [3, 4], the status, and the per-step records cut to
+    the steps attempted"""
+    import numpy as np
+    k = int(st.iterations)
+    return dict(
+        dst_from_src=np.array(st.dstFromSrc[:], np.float64).reshape(4, 4),
+        src_vox_from_dst_vox=np.array(st.srcVoxFromDstVox[:], np.float32).reshape(3, 4),
+        dst_vox_from_src_vox=np.array(st.dstVoxFromSrcVox[:], np.float32).reshape(3, 4),
+        pivot=np.array(st.pivot[:], np.float32), inv_radius=float(st.invRadius), iterations=k, status=int(st.status),
+        converged=bool(st.status & ALIGN_CONVERGED),
+        count=[int(v) for v in st.count[:k]], condition=[float(v) for v in st.condition[:k]], sum_squares=[float(v) for v in st.sumSquares[:k]],
+        step_rotation=[float(v) for v in st.stepRotation[:k]], step_translation=[float(v) for v in st.stepTranslation[:k]],
+        totals=np.array(st.totals[:ALIGN_NUM_TERMS], np.int64), raw=bytes(st))
+
+
 class CutRegion(C.Structure):  # VhCutRegion
     _fields_ = [("worldFromRegion", C.c_double * 16), ("halfExtents", C.c_float * 3), ("shape", C.c_uint32)]
 
