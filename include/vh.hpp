@@ -298,6 +298,15 @@ private:
     void create(const HashParams& params);
     void cutRegion(const CutRegion& region, uint32_t flags, SDFBlockDesc* d_outDescs, Voxel* d_staging, unsigned int stagingBlocks, CutCounts& c,
                    const char* what);
+    // what the scene operations start from: a table's entries as a block list, after another scene's stream
+    struct BlockList {
+        vh::DevicePtr<SDFBlockDesc> descs;
+        vh::DevicePtr<uint32_t> counter; // the helper's own count word: lives as long as the list, as it always has
+        uint32_t capacity, n;
+    };
+    BlockList gatherBlockList(const CUDASceneRepHashSDF& of, const char* what, uint32_t* d_counter = nullptr);
+    void refuseOverfull(uint32_t n, uint32_t capacity, const CUDASceneRepHashSDF& of, const char* what) const;
+    vh::Event waitForStreamOf(const CUDASceneRepHashSDF& other);
     void alloc(const DepthCameraData&, const DepthCameraParams&, const unsigned int* d_bitMask, bool jobPrepared); // :247
     void compactifyHashEntries(const DepthCameraParams&);                                        // :282
     void integrateFused(const DepthCameraData&, const DepthCameraParams&);

@@ -13,27 +13,25 @@
 #include "../../include/vh_api.h"
 #include "vh_device.hpp"
 #include "vh_host_util.hpp"
+#include "vh_resample_blend.hpp"
+#include "vh_scene_ops.hpp"
 
 using namespace vhd;
 
 namespace {
 
-// d_work: kHeader words, then three arrays of n words (a state word per block, two pending lists)
+// d_work: kHeader words, then three arrays of n words (a state word per block, two pending lists: vh_scene_ops.hpp)
 enum {
     W_STATUS = 0,
     W_PENDING = 1,  // two words: the pending lists' lengths (a delete pass reads one list and fills the other)
     W_STAGED = 3,   // staging slots handed out
     W_LIFTABLE = 4, // the stripes' sum, by k_cut_decide
-    // The counts: kStripes groups of words {selected observed voxels, blocks touched, blocks freeable, blocks liftable},
-    // each group in a cache line of its own, a workgroup adding to the one its index picks (one word for all costs a
-    // merge twelve times what its voxels take: DESIGN.md section 6 "Scene merge").
+    // the counts, striped: {selected observed voxels, blocks touched, blocks freeable, blocks liftable}
     W_COUNTS = 16,
     C_VOXELS = 0,
     C_TOUCHED = 1,
     C_FREEABLE = 2,
     C_LIFTABLE = 3,
-    kStripes = 32,
-    kStripeWords = 16,
     kHeader = W_COUNTS + kStripes * kStripeWords
 };
 // per source block, in the first array behind the header
@@ -45,22 +43,7 @@ enum : uint32_t {
 // per wave, in LDS
 enum : uint32_t { kAnySelected = 1u, kAnyUnselectedObserved = 2u, kAnySelectedObserved = 4u };
 
-struct M34 { float m[12]; }; // row-major 3x4, voxel index space: regionFromVox
-
-// `v` appended to list[*counter ...] by every lane with `take`, one atomic per wave; every lane of the wave calls it
-VHD void wave_append(bool take, uint32_t v, uint32_t* counter, uint32_t* list)
-{
-    const unsigned long long m = __ballot(take);
-    if (m == 0ull) return;
-    uint32_t base = 0u;
-    const int leader = __ffsll((long long)m) - 1;
-    if ((int)lane_id() == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-    if (take) list[base + (uint32_t)__popcll(m & lanemask_lt())] = v;
-}
-
-// one row of the rule: ((m0 i + m1 j) + m2 k) + m3, one rounding per operation
-VHD float row(const float* r, float i, float j, float k) { return ((r[0] * i + r[1] * j) + r[2] * k) + r[3]; }
+// (M34, here regionFromVox, and row(), one row of the rule with one rounding per operation: vh_resample_blend.hpp)
 
 // the per-voxel rule: is voxel (i, j, k) selected?  A comparison with a NaN is false: such a voxel is not inside.
 VHD bool selected(const M34& m, uint32_t shape, bool outside, float i, float j, float k)
@@ -105,7 +88,7 @@ __global__ __launch_bounds__(256) void k_cut_select(VhHashData hd, uint32_t n, c
     const bool o0 = (v.y >> 24) != 0u, o1 = (v.w >> 24) != 0u;
     const unsigned long long anySel = __ballot(s0 || s1), anyKept = __ballot((!s0 && o0) || (!s1 && o1));
     const uint32_t nGone = (uint32_t)__popcll(__ballot(s0 && o0)) + (uint32_t)__popcll(__ballot(s1 && o1));
-    uint32_t* stripe = &work[W_COUNTS + (b % kStripes) * kStripeWords];
+    uint32_t* stripe = stripe_of(&work[W_COUNTS], b);
     if (lane_id() == 0u) {
         s_facts[t / kWave] = (anySel != 0ull ? kAnySelected : 0u) | (anyKept != 0ull ? kAnyUnselectedObserved : 0u) | (nGone != 0u ? kAnySelectedObserved : 0u);
         if (nGone != 0u) atomicAdd(&stripe[C_VOXELS], nGone); // one atomic per wave
@@ -182,34 +165,11 @@ __global__ __launch_bounds__(256) void k_cut_erase(VhHashData hd, uint32_t n, co
     if (s1) at[1] = make_uint2(0u, 0u);
 }
 
-// One lane per block still pending: deleteHashEntryElement, which puts the block (all zero since an earlier launch)
-// back on the heap.  The first pass (pendingIn == nullptr) looks at every source block's state word.  A delete that
-// loses a bucket lock is pending for the next pass.
+// the delete pass (vh_scene_ops.hpp) over the freeable blocks
 __global__ __launch_bounds__(64) void k_cut_delete(VhHashData hd, VhHashParams hp, const VhSDFBlockDesc* descs, int32_t lockToken, uint32_t* work,
                                                    const uint32_t* blockState, const uint32_t* pendingIn, uint32_t nIn, uint32_t* pendingOut, uint32_t outSel)
 {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    bool lost = false;
-    uint32_t i = 0u;
-    if (t < nIn) {
-        i = pendingIn ? pendingIn[t] : t;
-        if (blockState[i] & kFreeable) lost = !delete_hash_entry_element(hd, hp, mki3(descs[i].pos[0], descs[i].pos[1], descs[i].pos[2]), lockToken);
-    }
-    wave_append(lost, i, &work[W_PENDING + outSel], pendingOut);
-}
-
-int read_header(const uint32_t* d_work, uint32_t* h, hipStream_t s)
-{
-    VH_HIP(hipMemcpyAsync(h, d_work, kHeader * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    VH_HIP(hipStreamSynchronize(s));
-    return VH_OK;
-}
-
-uint32_t stripes_sum(const uint32_t* h, int which)
-{
-    uint32_t sum = 0u;
-    for (uint32_t k = 0; k < kStripes; k++) sum += h[W_COUNTS + k * kStripeWords + which];
-    return sum;
+    delete_listed(hd, hp, descs, lockToken, blockState, kFreeable, pendingIn, nIn, pendingOut, &work[W_PENDING + outSel]);
 }
 
 // what the classification says the call does (or, refused or only counting, would do)
@@ -217,11 +177,11 @@ void fill_counts(uint32_t n, uint32_t flags, const uint32_t* h, uint32_t* counts
 {
     const bool lift = (flags & VH_CUT_LIFT) != 0u, keep = (flags & VH_CUT_KEEP) != 0u;
     counts_out[VH_CUT_BLOCKS_IN] = n;
-    counts_out[VH_CUT_TOUCHED] = stripes_sum(h, C_TOUCHED);
-    counts_out[VH_CUT_FREED] = keep ? 0u : stripes_sum(h, C_FREEABLE);
-    counts_out[VH_CUT_LIFTED] = lift ? stripes_sum(h, C_LIFTABLE) : 0u;
-    counts_out[VH_CUT_VOXELS_ERASED] = keep ? 0u : stripes_sum(h, C_VOXELS);
-    counts_out[VH_CUT_VOXELS_LIFTED] = lift ? stripes_sum(h, C_VOXELS) : 0u;
+    counts_out[VH_CUT_TOUCHED] = stripes_sum(h, W_COUNTS, C_TOUCHED);
+    counts_out[VH_CUT_FREED] = keep ? 0u : stripes_sum(h, W_COUNTS, C_FREEABLE);
+    counts_out[VH_CUT_LIFTED] = lift ? stripes_sum(h, W_COUNTS, C_LIFTABLE) : 0u;
+    counts_out[VH_CUT_VOXELS_ERASED] = keep ? 0u : stripes_sum(h, W_COUNTS, C_VOXELS);
+    counts_out[VH_CUT_VOXELS_LIFTED] = lift ? stripes_sum(h, W_COUNTS, C_VOXELS) : 0u;
     counts_out[VH_CUT_STATUS] = h[W_STATUS];
 }
 
@@ -233,24 +193,14 @@ int vh_cut_region_transform(const double* T, const float* halfExtents3, float vo
 {
     if (!T || !halfExtents3 || !m12) return VH_ERR_BAD_ARGUMENT;
     if (!std::isfinite(voxelSize) || !(voxelSize > 0.0f)) return VH_ERR_BAD_ARGUMENT;
-    for (int k = 0; k < 16; k++)
-        if (!std::isfinite(T[k])) return VH_ERR_BAD_ARGUMENT;
     for (int r = 0; r < 3; r++)
         if (!std::isfinite(halfExtents3[r]) || !(halfExtents3[r] > 0.0f)) return VH_ERR_BAD_ARGUMENT;
-    if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return VH_ERR_BAD_ARGUMENT;
+    VH_TRY(vh_rigid_or_refuse(T));
     double R[3][3], t[3];
     for (int r = 0; r < 3; r++) {
         for (int c = 0; c < 3; c++) R[r][c] = T[4 * r + c];
         t[r] = T[4 * r + 3];
     }
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) {
-            const double dot = (R[0][a] * R[0][b] + R[1][a] * R[1][b]) + R[2][a] * R[2][b];
-            if (!(std::fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-4)) return VH_ERR_BAD_ARGUMENT;
-        }
-    const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
-                       R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
-    if (!(det > 0.0)) return VH_ERR_BAD_ARGUMENT;
     const double vs = (double)voxelSize;
     for (int r = 0; r < 3; r++) {
         const double h = (double)halfExtents3[r];
@@ -260,7 +210,7 @@ int vh_cut_region_transform(const double* T, const float* halfExtents3, float vo
     return VH_OK;
 }
 
-size_t vh_cut_work_bytes(uint32_t n) { return ((size_t)kHeader + 3u * (size_t)n) * sizeof(uint32_t); }
+size_t vh_cut_work_bytes(uint32_t n) { return settle_work_bytes(kHeader, n); }
 
 int vh_cut_blocks(const VhHashData* hd, const VhHashParams* hp, uint32_t n, const VhSDFBlockDesc* d_descs, const VhVoxel* d_blocks, const float* m12,
                   uint32_t shape, uint32_t flags, int32_t lockToken, uint32_t* d_work, VhSDFBlockDesc* d_outDescs, VhVoxel* d_staging,
@@ -280,8 +230,8 @@ int vh_cut_blocks(const VhHashData* hd, const VhHashParams* hp, uint32_t n, cons
     const VhHashData& table = hd ? *hd : noTable;
     VhVoxel* blocks = const_cast<VhVoxel*>(d_blocks); // (only read: nothing erases a list)
     const uint32_t outside = (flags & VH_CUT_SELECT_OUTSIDE) ? 1u : 0u;
-    uint32_t* blockState = d_work + kHeader;
-    uint32_t* pending[2] = { blockState + n, blockState + 2u * (size_t)n };
+    const SettleArrays a = settle_arrays(d_work, kHeader, n);
+    uint32_t* blockState = a.blockState;
     uint32_t h[kHeader];
     M34 m;
     for (int k = 0; k < 12; k++) m.m[k] = m12[k];
@@ -298,31 +248,23 @@ int vh_cut_blocks(const VhHashData* hd, const VhHashParams* hp, uint32_t n, cons
         if (!keep) VH_LAUNCH_TIMED(k_cut_erase, n, 256, s, table, n, d_descs, m, shape, outside, d_work, blockState);
     }
     VH_TRY(vh_last_launch_error());
-    VH_TRY(read_header(d_work, h, s));
+    VH_TRY(read_header(d_work, h, kHeader, s));
     fill_counts(n, flags, h, counts_out);
     if (countOnly || keep) return (h[W_STATUS] & VH_CUT_STAGING_SHORT) ? VH_ERR_BAD_ARGUMENT : VH_OK;
     if (h[W_STATUS] & VH_CUT_STAGING_SHORT) return VH_ERR_BAD_ARGUMENT; // nothing was written
 
-    // Stage 2: delete passes while deletes lose their lock races, the mutexes reset before each but the first (the
-    // caller's token is fresh again).  The blocks were zeroed by an earlier launch.  One list element per bucket and
-    // pass gets through its bucket's mutex, and a pass may make no progress, so the bound is not one block per pass.
+    // Stage 2: delete passes while deletes lose their lock races.  The blocks were zeroed by an earlier launch; the first
+    // pass walks every block's state word.
     const uint32_t freeable = counts_out[VH_CUT_FREED];
-    const uint32_t mostPasses = freeable + 8u;
-    uint32_t passes = 0u, in = 0u, nPending = freeable != 0u ? n : 0u;
-    while (nPending != 0u && passes < mostPasses) {
-        if (passes != 0u) VH_TRY(vh_reset_bucket_mutex(hd, hp, stream));
-        VH_HIP(hipMemsetAsync(&d_work[W_PENDING + (in ^ 1u)], 0, sizeof(uint32_t), s));
-        VH_LAUNCH_TIMED(k_cut_delete, cdiv(nPending, 64), 64, s, table, *hp, d_descs, lockToken, d_work, blockState, passes == 0u ? nullptr : pending[in],
-                        nPending, pending[in ^ 1u], in ^ 1u);
-        VH_TRY(vh_last_launch_error());
-        VH_TRY(read_header(d_work, h, s));
-        in ^= 1u;
-        nPending = h[W_PENDING + in];
-        passes++;
-    }
-    counts_out[VH_CUT_DELETE_PASSES] = passes;
-    counts_out[VH_CUT_UNSETTLED] = nPending;
-    if (nPending != 0u) counts_out[VH_CUT_STATUS] |= VH_CUT_NOT_SETTLED;
+    Settled st;
+    VH_TRY(settle_passes<kHeader>(hd, hp, stream, d_work, a, W_PENDING, freeable != 0u ? n : 0u, freeable + 8u,
+                                  [&](const uint32_t* pendingIn, uint32_t nIn, uint32_t* pendingOut, uint32_t outSel, uint32_t pass) {
+                                      VH_LAUNCH_TIMED(k_cut_delete, cdiv(nIn, 64), 64, s, table, *hp, d_descs, lockToken, d_work, blockState,
+                                                      pass == 0u ? nullptr : pendingIn, nIn, pendingOut, outSel);
+                                  }, &st));
+    counts_out[VH_CUT_DELETE_PASSES] = st.passes;
+    counts_out[VH_CUT_UNSETTLED] = st.nPending;
+    if (st.nPending != 0u) counts_out[VH_CUT_STATUS] |= VH_CUT_NOT_SETTLED;
     return VH_OK;
 }
 

@@ -12,26 +12,24 @@
 #include "../../include/vh_api.h"
 #include "vh_device.hpp"
 #include "vh_host_util.hpp"
+#include "vh_scene_ops.hpp"
 
 using namespace vhd;
 
 namespace {
 
-// d_work: kHeader words, then three arrays of n words (a state word per block, two pending lists)
+// d_work: kHeader words, then three arrays of n words (a state word per block, two pending lists: vh_scene_ops.hpp)
 enum {
     W_STATUS = 0,
     W_PENDING = 1, // two words: the pending lists' lengths (a delete pass reads one list and fills the other)
-    // The counts: kStripes groups of words, each group in a cache line of its own, a workgroup adding to the one its
-    // index picks (the cut's scheme: DESIGN.md section 6 "Scene merge" has what one word for all costs).
-    W_COUNTS = 16,
+    W_COUNTS = 16, // the counts, striped
+
     C_PROCESSED = 0,
     C_CHANGED = 1,
     C_FREED = 2,
     C_VOXELS_CHANGED = 3,
     C_VOXELS_RESET = 4,
     C_VOXELS_AT_CAP = 5,
-    kStripes = 32,
-    kStripeWords = 16,
     kHeader = W_COUNTS + kStripes * kStripeWords
 };
 // per listed block, in the first array behind the header
@@ -42,18 +40,6 @@ enum : uint32_t {
 };
 // per wave, in LDS
 enum : uint32_t { kAnyLeft = 1u, kAnyChanged = 2u };
-
-// `v` appended to list[*counter ...] by every lane with `take`, one atomic per wave; every lane of the wave calls it
-VHD void wave_append(bool take, uint32_t v, uint32_t* counter, uint32_t* list)
-{
-    const unsigned long long m = __ballot(take);
-    if (m == 0ull) return;
-    uint32_t base = 0u;
-    const int leader = __ffsll((long long)m) - 1;
-    if ((int)lane_id() == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-    if (take) list[base + (uint32_t)__popcll(m & lanemask_lt())] = v;
-}
 
 // The observation the frame makes of voxel pi: what integrate_voxel (vh_frame_integrate.hpp) hands to combine_voxel, the
 // same operations in the same order.  A voxel that fails a gate has no observation: weight 0 (an observation's weight is
@@ -156,7 +142,7 @@ __global__ __launch_bounds__(256) void k_deint_apply(VhHashData hd, VhHashParams
     const uint32_t nChanged = (uint32_t)__popcll(__ballot(c0)) + (uint32_t)__popcll(__ballot(c1));
     const uint32_t nReset = (uint32_t)__popcll(__ballot(z0)) + (uint32_t)__popcll(__ballot(z1));
     const uint32_t nCap = (uint32_t)__popcll(__ballot(k0)) + (uint32_t)__popcll(__ballot(k1));
-    uint32_t* stripe = &work[W_COUNTS + (b % kStripes) * kStripeWords];
+    uint32_t* stripe = stripe_of(&work[W_COUNTS], b);
     if (lane_id() == 0u) {
         s_facts[t / kWave] = (anyLeft != 0ull ? kAnyLeft : 0u) | (nChanged != 0u ? kAnyChanged : 0u);
         // per wave: one atomic for the voxels it changed, and one each for the rare kinds among them
@@ -183,20 +169,11 @@ __global__ __launch_bounds__(256) void k_deint_apply(VhHashData hd, VhHashParams
     }
 }
 
-// One lane per block still pending: deleteHashEntryElement, which puts the block (all zero since an earlier launch)
-// back on the heap.  The first pass (pendingIn == nullptr) looks at every listed block's state word.  A delete that
-// loses a bucket lock is pending for the next pass.  (The shape of k_cut_delete.)
+// the delete pass (vh_scene_ops.hpp) over the freed blocks
 __global__ __launch_bounds__(64) void k_deint_delete(VhHashData hd, VhHashParams hp, const VhSDFBlockDesc* descs, int32_t lockToken, uint32_t* work,
                                                      const uint32_t* blockState, const uint32_t* pendingIn, uint32_t nIn, uint32_t* pendingOut, uint32_t outSel)
 {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    bool lost = false;
-    uint32_t i = 0u;
-    if (t < nIn) {
-        i = pendingIn ? pendingIn[t] : t;
-        if (blockState[i] & kFreed) lost = !delete_hash_entry_element(hd, hp, mki3(descs[i].pos[0], descs[i].pos[1], descs[i].pos[2]), lockToken);
-    }
-    wave_append(lost, i, &work[W_PENDING + outSel], pendingOut);
+    delete_listed(hd, hp, descs, lockToken, blockState, kFreed, pendingIn, nIn, pendingOut, &work[W_PENDING + outSel]);
 }
 
 // the rule alone: out[i] = observed[i] taken out of stored[i]
@@ -206,25 +183,11 @@ __global__ __launch_bounds__(256) void k_deint_rule(const uint2* stored, const u
     if (i < n) out[i] = pack_vox(take_out(hp, unpack_vox(stored[i]), unpack_vox(observed[i])));
 }
 
-int read_header(const uint32_t* d_work, uint32_t* h, hipStream_t s)
-{
-    VH_HIP(hipMemcpyAsync(h, d_work, kHeader * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    VH_HIP(hipStreamSynchronize(s));
-    return VH_OK;
-}
-
-uint32_t stripes_sum(const uint32_t* h, int which)
-{
-    uint32_t sum = 0u;
-    for (uint32_t k = 0; k < kStripes; k++) sum += h[W_COUNTS + k * kStripeWords + which];
-    return sum;
-}
-
 } // namespace
 
 extern "C" {
 
-size_t vh_deintegrate_work_bytes(uint32_t n) { return ((size_t)kHeader + 3u * (size_t)n) * sizeof(uint32_t); }
+size_t vh_deintegrate_work_bytes(uint32_t n) { return settle_work_bytes(kHeader, n); }
 
 int vh_deintegrate_blocks(const VhHashData* hd, const VhHashParams* hp, uint32_t n, const VhSDFBlockDesc* d_descs, const VhDepthCameraData* cam,
                           const VhDepthCameraParams* cp, uint32_t flags, int32_t lockToken, uint32_t* d_work, uint32_t* counts_out, vhStream_t stream)
@@ -237,8 +200,8 @@ int vh_deintegrate_blocks(const VhHashData* hd, const VhHashParams* hp, uint32_t
     if (!d_descs) return VH_ERR_BAD_ARGUMENT;
     hipStream_t s = (hipStream_t)stream;
     const bool countOnly = (flags & VH_DEINT_COUNT_ONLY) != 0u;
-    uint32_t* blockState = d_work + kHeader;
-    uint32_t* pending[2] = { blockState + n, blockState + 2u * (size_t)n };
+    const SettleArrays a = settle_arrays(d_work, kHeader, n);
+    uint32_t* blockState = a.blockState;
     uint32_t h[kHeader];
 
     // Stage 1: the take-out, the state words and the counts
@@ -246,37 +209,29 @@ int vh_deintegrate_blocks(const VhHashData* hd, const VhHashParams* hp, uint32_t
     if (countOnly) VH_LAUNCH_TIMED(k_deint_apply<false>, n, 256, s, *hd, *hp, *cam, *cp, n, d_descs, d_work, blockState);
     else VH_LAUNCH_TIMED(k_deint_apply<true>, n, 256, s, *hd, *hp, *cam, *cp, n, d_descs, d_work, blockState);
     VH_TRY(vh_last_launch_error());
-    VH_TRY(read_header(d_work, h, s));
+    VH_TRY(read_header(d_work, h, kHeader, s));
     counts_out[VH_DEINT_BLOCKS_IN] = n;
-    counts_out[VH_DEINT_PROCESSED] = stripes_sum(h, C_PROCESSED);
-    counts_out[VH_DEINT_CHANGED] = stripes_sum(h, C_CHANGED);
-    counts_out[VH_DEINT_FREED] = stripes_sum(h, C_FREED);
-    counts_out[VH_DEINT_VOXELS_CHANGED] = stripes_sum(h, C_VOXELS_CHANGED);
-    counts_out[VH_DEINT_VOXELS_RESET] = stripes_sum(h, C_VOXELS_RESET);
-    counts_out[VH_DEINT_VOXELS_AT_CAP] = stripes_sum(h, C_VOXELS_AT_CAP);
+    counts_out[VH_DEINT_PROCESSED] = stripes_sum(h, W_COUNTS, C_PROCESSED);
+    counts_out[VH_DEINT_CHANGED] = stripes_sum(h, W_COUNTS, C_CHANGED);
+    counts_out[VH_DEINT_FREED] = stripes_sum(h, W_COUNTS, C_FREED);
+    counts_out[VH_DEINT_VOXELS_CHANGED] = stripes_sum(h, W_COUNTS, C_VOXELS_CHANGED);
+    counts_out[VH_DEINT_VOXELS_RESET] = stripes_sum(h, W_COUNTS, C_VOXELS_RESET);
+    counts_out[VH_DEINT_VOXELS_AT_CAP] = stripes_sum(h, W_COUNTS, C_VOXELS_AT_CAP);
     counts_out[VH_DEINT_STATUS] = h[W_STATUS];
     if (countOnly) return VH_OK;
 
-    // Stage 2: delete passes while deletes lose their lock races, the mutexes reset before each but the first (the
-    // caller's token is fresh again).  The blocks were zeroed by an earlier launch.  One list element per bucket and
-    // pass gets through its bucket's mutex, and a pass may make no progress, so the bound is not one block per pass.
+    // Stage 2: delete passes while deletes lose their lock races.  The blocks were zeroed by an earlier launch; the first
+    // pass walks every block's state word.
     const uint32_t freed = counts_out[VH_DEINT_FREED];
-    const uint32_t mostPasses = freed + 8u;
-    uint32_t passes = 0u, in = 0u, nPending = freed != 0u ? n : 0u;
-    while (nPending != 0u && passes < mostPasses) {
-        if (passes != 0u) VH_TRY(vh_reset_bucket_mutex(hd, hp, stream));
-        VH_HIP(hipMemsetAsync(&d_work[W_PENDING + (in ^ 1u)], 0, sizeof(uint32_t), s));
-        VH_LAUNCH_TIMED(k_deint_delete, cdiv(nPending, 64), 64, s, *hd, *hp, d_descs, lockToken, d_work, blockState, passes == 0u ? nullptr : pending[in],
-                        nPending, pending[in ^ 1u], in ^ 1u);
-        VH_TRY(vh_last_launch_error());
-        VH_TRY(read_header(d_work, h, s));
-        in ^= 1u;
-        nPending = h[W_PENDING + in];
-        passes++;
-    }
-    counts_out[VH_DEINT_DELETE_PASSES] = passes;
-    counts_out[VH_DEINT_UNSETTLED] = nPending;
-    if (nPending != 0u) counts_out[VH_DEINT_STATUS] |= VH_DEINT_NOT_SETTLED;
+    Settled st;
+    VH_TRY(settle_passes<kHeader>(hd, hp, stream, d_work, a, W_PENDING, freed != 0u ? n : 0u, freed + 8u,
+                                  [&](const uint32_t* pendingIn, uint32_t nIn, uint32_t* pendingOut, uint32_t outSel, uint32_t pass) {
+                                      VH_LAUNCH_TIMED(k_deint_delete, cdiv(nIn, 64), 64, s, *hd, *hp, d_descs, lockToken, d_work, blockState,
+                                                      pass == 0u ? nullptr : pendingIn, nIn, pendingOut, outSel);
+                                  }, &st));
+    counts_out[VH_DEINT_DELETE_PASSES] = st.passes;
+    counts_out[VH_DEINT_UNSETTLED] = st.nPending;
+    if (st.nPending != 0u) counts_out[VH_DEINT_STATUS] |= VH_DEINT_NOT_SETTLED;
     return VH_OK;
 }
 

@@ -684,6 +684,43 @@ void CUDASceneRepHashSDF::queryPoints(const float* d_points, unsigned int n, flo
 
 // ---- scene merge (vh_merge.hip; DESIGN.md section 4 "Scene merge")
 
+// what `other`'s stream has enqueued comes before what this scene's stream gets from here on: an event (the caller keeps
+// it while it enqueues), no device-wide synchronisation
+vh::Event CUDASceneRepHashSDF::waitForStreamOf(const CUDASceneRepHashSDF& other)
+{
+    vh::Event done;
+    if (other.m_stream != m_stream) {
+        done = vh::makeEvent(false);
+        checkHip(hipEventRecord((hipEvent_t)done.get(), (hipStream_t)other.m_stream), "hipEventRecord");
+        checkHip(hipStreamWaitEvent((hipStream_t)m_stream, (hipEvent_t)done.get(), 0), "hipStreamWaitEvent");
+    }
+    return done;
+}
+
+void CUDASceneRepHashSDF::refuseOverfull(uint32_t n, uint32_t capacity, const CUDASceneRepHashSDF& of, const char* what) const
+{
+    if (n > capacity)
+        throw vh::Error(VH_ERR_BAD_ARGUMENT, std::string(what) + (&of == this ? ": the table holds more entries than the pool has blocks"
+                                                                               : ": the source's table holds more entries than its pool has blocks"));
+}
+
+// The entries of `of`'s table (this scene's or another's) as a block list on this scene's stream: at most one per block
+// of its pool.  The count is read back and checked here, unless the caller gives the word that counts (d_counter): then
+// it reads n back itself, with what else it needs, and calls refuseOverfull.
+CUDASceneRepHashSDF::BlockList CUDASceneRepHashSDF::gatherBlockList(const CUDASceneRepHashSDF& of, const char* what, uint32_t* d_counter)
+{
+    BlockList list;
+    list.capacity = of.m_hashParams.m_numSDFBlocks;
+    list.n = 0;
+    list.descs = vh::deviceAlloc<SDFBlockDesc>(list.capacity, "scene block list");
+    if (!d_counter) list.counter = vh::deviceAlloc<uint32_t>(1, "scene block count");
+    check(vh_merge_gather(&of.m_hashData, &of.m_hashParams, list.descs.get(), list.capacity, d_counter ? d_counter : list.counter.get(), m_stream), "vh_merge_gather");
+    if (d_counter) return list;
+    check(vh_memcpy_d2h(&list.n, list.counter.get(), sizeof(list.n), m_stream), what);
+    refuseOverfull(list.n, list.capacity, of, what);
+    return list;
+}
+
 void CUDASceneRepHashSDF::mergeBlocks(const SDFBlockDesc* d_descs, const Voxel* d_blocks, unsigned int n, const int32_t blockOffset[3],
                                       uint32_t* d_leftOut, MergeCounts* counts)
 {
@@ -711,26 +748,14 @@ void CUDASceneRepHashSDF::mergeScene(const CUDASceneRepHashSDF& other, const int
     if (std::memcmp(&other.m_hashParams.m_virtualVoxelSize, &m_hashParams.m_virtualVoxelSize, sizeof(float)) != 0)
         throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeScene: the two scenes have different voxel sizes");
     if (m_aheadPending || other.m_aheadPending) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeScene: between integrateAhead() and integrateFinish()");
-    // what the source's stream has enqueued comes first: an event, no device-wide synchronisation
-    vh::Event done;
-    if (other.m_stream != m_stream) {
-        done = vh::makeEvent(false);
-        checkHip(hipEventRecord((hipEvent_t)done.get(), (hipStream_t)other.m_stream), "hipEventRecord");
-        checkHip(hipStreamWaitEvent((hipStream_t)m_stream, (hipEvent_t)done.get(), 0), "hipStreamWaitEvent");
-    }
-    // the source's entries as a block list: at most one per block of its pool
-    const uint32_t capacity = other.m_hashParams.m_numSDFBlocks;
-    vh::DevicePtr<SDFBlockDesc> descs = vh::deviceAlloc<SDFBlockDesc>(capacity, "merge block list");
-    vh::DevicePtr<uint32_t> counter = vh::deviceAlloc<uint32_t>(1, "merge block count");
-    check(vh_merge_gather(&other.m_hashData, &other.m_hashParams, descs.get(), capacity, counter.get(), m_stream), "vh_merge_gather");
-    uint32_t n = 0;
-    check(vh_memcpy_d2h(&n, counter.get(), sizeof(n), m_stream), "mergeScene");
-    if (n > capacity) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeScene: the source's table holds more entries than its pool has blocks");
+    const vh::Event done = waitForStreamOf(other);
+    const BlockList list = gatherBlockList(other, "mergeScene");
+    const uint32_t n = list.n;
     if (n == 0) return;
     vh::DevicePtr<unsigned char> work = vh::deviceAlloc<unsigned char>(vh_merge_work_bytes(n), "merge scratch");
     const int32_t token = nextLockToken();
     noteTableEdited();
-    check(vh_merge_blocks(&m_hashData, &m_hashParams, n, descs.get(), nullptr, other.m_hashData.d_SDFBlocks, blockOffset, token,
+    check(vh_merge_blocks(&m_hashData, &m_hashParams, n, list.descs.get(), nullptr, other.m_hashData.d_SDFBlocks, blockOffset, token,
                           reinterpret_cast<uint32_t*>(work.get()), nullptr, c.c, m_stream), "vh_merge_blocks");
     if (c.status() & VH_MERGE_HEAP_SHORT) throw vh::Error(VH_ERR_HEAP_EXHAUSTED, "mergeScene: the source holds more new blocks than the heap has free");
 }
@@ -758,20 +783,10 @@ void CUDASceneRepHashSDF::mergeSceneTransformed(const CUDASceneRepHashSDF& other
     float srcFromDst[12], dstFromSrcVox[12];
     check(vh_resample_voxel_transforms(dstFromSrc, other.m_hashParams.m_virtualVoxelSize, m_hashParams.m_virtualVoxelSize, srcFromDst, dstFromSrcVox),
           "mergeSceneTransformed: the transform is not rigid, or the voxel sizes differ by more than a factor of 2");
-    vh::Event done;
-    if (other.m_stream != m_stream) {
-        done = vh::makeEvent(false);
-        checkHip(hipEventRecord((hipEvent_t)done.get(), (hipStream_t)other.m_stream), "hipEventRecord");
-        checkHip(hipStreamWaitEvent((hipStream_t)m_stream, (hipEvent_t)done.get(), 0), "hipStreamWaitEvent");
-    }
+    const vh::Event done = waitForStreamOf(other);
     // stage 1: the source's entries as a block list
-    const uint32_t capacity = other.m_hashParams.m_numSDFBlocks;
-    vh::DevicePtr<SDFBlockDesc> descs = vh::deviceAlloc<SDFBlockDesc>(capacity, "resample block list");
-    vh::DevicePtr<uint32_t> counter = vh::deviceAlloc<uint32_t>(1, "resample block count");
-    check(vh_merge_gather(&other.m_hashData, &other.m_hashParams, descs.get(), capacity, counter.get(), m_stream), "vh_merge_gather");
-    uint32_t n = 0;
-    check(vh_memcpy_d2h(&n, counter.get(), sizeof(n), m_stream), "mergeSceneTransformed");
-    if (n > capacity) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeSceneTransformed: the source's table holds more entries than its pool has blocks");
+    const BlockList list = gatherBlockList(other, "mergeSceneTransformed");
+    const uint32_t n = list.n;
     if (n == 0) return;
     // stage 2: the candidates.  The table starts at 16 slots per source block and grows fourfold while it fills, up to
     // two slots for each of the 6^3 candidates a source block can name at most: that one cannot fill.  Four tries at most.
@@ -782,7 +797,7 @@ void CUDASceneRepHashSDF::mergeSceneTransformed(const CUDASceneRepHashSDF& other
         slotsLog2 = std::min(slotsLog2, most);
         if (slotsLog2 > 28u) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeSceneTransformed: the source holds too many blocks");
         work = vh::deviceAlloc<unsigned char>(vh_resample_work_bytes(slotsLog2), "resample scratch");
-        check(vh_resample_blocks(&other.m_hashData, &other.m_hashParams, n, descs.get(), srcFromDst, dstFromSrcVox, slotsLog2,
+        check(vh_resample_blocks(&other.m_hashData, &other.m_hashParams, n, list.descs.get(), srcFromDst, dstFromSrcVox, slotsLog2,
                                  reinterpret_cast<uint32_t*>(work.get()), nullptr, nullptr, 0, rc.c, m_stream), "vh_resample_blocks");
         if (!(rc.status() & VH_RESAMPLE_TABLE_FULL) || slotsLog2 == most) break;
         slotsLog2 += 2u;
@@ -793,7 +808,7 @@ void CUDASceneRepHashSDF::mergeSceneTransformed(const CUDASceneRepHashSDF& other
     // stage 3: the candidates' voxels into a staging pool (not cleared: only listed blocks are read)
     vh::DevicePtr<SDFBlockDesc> staged = vh::deviceAlloc<SDFBlockDesc>(numCandidates, "resample staged list");
     vh::DevicePtr<Voxel> staging = vh::deviceAlloc<Voxel>((size_t)numCandidates * VH_SDF_BLOCK_VOXELS, "resample staging pool");
-    check(vh_resample_blocks(&other.m_hashData, &other.m_hashParams, n, descs.get(), srcFromDst, dstFromSrcVox, slotsLog2,
+    check(vh_resample_blocks(&other.m_hashData, &other.m_hashParams, n, list.descs.get(), srcFromDst, dstFromSrcVox, slotsLog2,
                              reinterpret_cast<uint32_t*>(work.get()), staged.get(), staging.get(), numCandidates, rc.c, m_stream), "vh_resample_blocks");
     if (rc.status() != 0u) throw vh::Error(VH_ERR_BAD_ARGUMENT, "mergeSceneTransformed: a block lies outside the lattice's range");
     const uint32_t numStaged = rc.c[VH_RESAMPLE_STAGED];
@@ -823,24 +838,17 @@ void CUDASceneRepHashSDF::alignScene(const CUDASceneRepHashSDF& other, const dou
     float srcFromDst[12], dstFromSrcVox[12];
     check(vh_resample_voxel_transforms(guess, vsSrc, vsDst, srcFromDst, dstFromSrcVox),
           "alignScene: the guess is not rigid, or the voxel sizes differ by more than a factor of 2");
-    vh::Event done;
-    if (other.m_stream != m_stream) {
-        done = vh::makeEvent(false);
-        checkHip(hipEventRecord((hipEvent_t)done.get(), (hipStream_t)other.m_stream), "hipEventRecord");
-        checkHip(hipStreamWaitEvent((hipStream_t)m_stream, (hipEvent_t)done.get(), 0), "hipStreamWaitEvent");
-    }
+    const vh::Event done = waitForStreamOf(other);
     // the source's entries as a block list, and their box: one read-back for both
-    const uint32_t capacity = other.m_hashParams.m_numSDFBlocks;
-    vh::DevicePtr<SDFBlockDesc> descs = vh::deviceAlloc<SDFBlockDesc>(capacity, "align block list");
     vh::DevicePtr<int32_t> words = vh::deviceAlloc<int32_t>(8, "align block count and box"); // n, the ticket, the box
     int32_t h[8] = { 0, 0, INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN };
     check(vh_memcpy_h2d(words.get(), h, sizeof(h), m_stream), "alignScene");
     uint32_t* counter = reinterpret_cast<uint32_t*>(words.get());
-    check(vh_merge_gather(&other.m_hashData, &other.m_hashParams, descs.get(), capacity, counter, m_stream), "vh_merge_gather");
-    check(vh_align_bounds(capacity, descs.get(), counter, words.get() + 2, m_stream), "vh_align_bounds");
+    const BlockList list = gatherBlockList(other, "alignScene", counter);
+    check(vh_align_bounds(list.capacity, list.descs.get(), counter, words.get() + 2, m_stream), "vh_align_bounds");
     check(vh_memcpy_d2h(h, words.get(), sizeof(h), m_stream), "alignScene");
     const uint32_t n = (uint32_t)h[0];
-    if (n > capacity) throw vh::Error(VH_ERR_BAD_ARGUMENT, "alignScene: the source's table holds more entries than its pool has blocks");
+    refuseOverfull(n, list.capacity, other, "alignScene");
     if (n > VH_ALIGN_MOST_BLOCKS) throw vh::Error(VH_ERR_BAD_ARGUMENT, "alignScene: the source holds more blocks than the fixed-point totals allow");
     // pivot: the image of the box's centre under the guess, a whole voxel; radius: the power of two that holds the box's
     // image about the pivot with a quarter to spare and 16 voxels for the way the estimate may go
@@ -865,7 +873,7 @@ void CUDASceneRepHashSDF::alignScene(const CUDASceneRepHashSDF& other, const dou
     check(vh_align_begin(state.get(), guess, vsSrc, vsDst, pivot, radius, m_stream), "vh_align_begin");
     uint32_t* ticket = counter + 1; // (0 since the upload above; every launch leaves it 0)
     for (uint32_t k = 0; k < o.maxIterations; k++)
-        check(vh_align_step(&m_hashData, &m_hashParams, &other.m_hashData, &other.m_hashParams, n, descs.get(), o.band, o.minCount, o.condThres, o.rotThres,
+        check(vh_align_step(&m_hashData, &m_hashParams, &other.m_hashData, &other.m_hashParams, n, list.descs.get(), o.band, o.minCount, o.condThres, o.rotThres,
                             o.transThres, state.get(), ticket, m_stream), "vh_align_step");
     check(vh_memcpy_d2h(result, state.get(), sizeof(*result), m_stream), "alignScene");
 }
@@ -883,19 +891,13 @@ void CUDASceneRepHashSDF::cutRegion(const CutRegion& region, uint32_t flags, SDF
     float m[12];
     if (vh_cut_region_transform(region.worldFromRegion, region.halfExtents, m_hashParams.m_virtualVoxelSize, m) != VH_OK)
         throw vh::Error(VH_ERR_BAD_ARGUMENT, name + ": the region's frame is not rigid, or a half extent is not positive");
-    // the table's entries as a block list: at most one per block of the pool
-    const uint32_t capacity = m_hashParams.m_numSDFBlocks;
-    vh::DevicePtr<SDFBlockDesc> descs = vh::deviceAlloc<SDFBlockDesc>(capacity, "cut block list");
-    vh::DevicePtr<uint32_t> counter = vh::deviceAlloc<uint32_t>(1, "cut block count");
-    check(vh_merge_gather(&m_hashData, &m_hashParams, descs.get(), capacity, counter.get(), m_stream), "vh_merge_gather");
-    uint32_t n = 0;
-    check(vh_memcpy_d2h(&n, counter.get(), sizeof(n), m_stream), what);
-    if (n > capacity) throw vh::Error(VH_ERR_BAD_ARGUMENT, name + ": the table holds more entries than the pool has blocks");
+    const BlockList list = gatherBlockList(*this, what);
+    const uint32_t n = list.n;
     if (n == 0) return;
     vh::DevicePtr<unsigned char> work = vh::deviceAlloc<unsigned char>(vh_cut_work_bytes(n), "cut scratch");
     const int32_t token = nextLockToken();
     if (!(flags & (VH_CUT_KEEP | VH_CUT_COUNT_ONLY))) noteTableEdited(); // (as a stream-out: the compactified list is stale)
-    const int rc = vh_cut_blocks(&m_hashData, &m_hashParams, n, descs.get(), nullptr, m, region.shape, flags, token, reinterpret_cast<uint32_t*>(work.get()),
+    const int rc = vh_cut_blocks(&m_hashData, &m_hashParams, n, list.descs.get(), nullptr, m, region.shape, flags, token, reinterpret_cast<uint32_t*>(work.get()),
                                  d_outDescs, d_staging, stagingBlocks, c.c, m_stream);
     if (c.status() & VH_CUT_STAGING_SHORT) throw vh::Error(VH_ERR_BAD_ARGUMENT, name + ": the region holds more blocks than there is room for");
     check(rc, "vh_cut_blocks");
@@ -969,19 +971,13 @@ void CUDASceneRepHashSDF::deintegrate(const vh::mat4f& rigidTransform, const Dep
     std::memcpy(hp.m_rigidTransform, rigidTransform.m, sizeof(rigidTransform.m));
     const vh::mat4f inv = rigidTransform.getInverse();
     std::memcpy(hp.m_rigidTransformInverse, inv.m, sizeof(inv.m));
-    // the table's entries as a block list: at most one per block of the pool
-    const uint32_t capacity = m_hashParams.m_numSDFBlocks;
-    vh::DevicePtr<SDFBlockDesc> descs = vh::deviceAlloc<SDFBlockDesc>(capacity, "deintegrate block list");
-    vh::DevicePtr<uint32_t> counter = vh::deviceAlloc<uint32_t>(1, "deintegrate block count");
-    check(vh_merge_gather(&m_hashData, &m_hashParams, descs.get(), capacity, counter.get(), m_stream), "vh_merge_gather");
-    uint32_t n = 0;
-    check(vh_memcpy_d2h(&n, counter.get(), sizeof(n), m_stream), "deintegrate");
-    if (n > capacity) throw vh::Error(VH_ERR_BAD_ARGUMENT, "deintegrate: the table holds more entries than the pool has blocks");
+    const BlockList list = gatherBlockList(*this, "deintegrate");
+    const uint32_t n = list.n;
     if (n == 0) return;
     vh::DevicePtr<unsigned char> work = vh::deviceAlloc<unsigned char>(vh_deintegrate_work_bytes(n), "deintegrate scratch");
     const int32_t token = nextLockToken();
     noteTableEdited(); // (as a stream-out: the compactified list is stale)
-    check(vh_deintegrate_blocks(&m_hashData, &hp, n, descs.get(), &cam, &cp, 0u, token, reinterpret_cast<uint32_t*>(work.get()), c.c, m_stream),
+    check(vh_deintegrate_blocks(&m_hashData, &hp, n, list.descs.get(), &cam, &cp, 0u, token, reinterpret_cast<uint32_t*>(work.get()), c.c, m_stream),
           "vh_deintegrate_blocks");
 }
 

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <string>
 
 #include "../../include/vh_api.h"
@@ -35,6 +36,26 @@ static inline int vh_last_launch_error()
 {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : -(int)e;
+}
+
+// Is the row-major 4x4 T a rigid transform?  Finite entries, the last row (0, 0, 0, 1), a rotation orthonormal to 1e-4
+// with a positive determinant: VH_OK, or VH_ERR_BAD_ARGUMENT.
+static inline int vh_rigid_or_refuse(const double* T)
+{
+    for (int k = 0; k < 16; k++)
+        if (!std::isfinite(T[k])) return VH_ERR_BAD_ARGUMENT;
+    if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return VH_ERR_BAD_ARGUMENT;
+    double R[3][3];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) R[r][c] = T[4 * r + c];
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) {
+            const double dot = (R[0][a] * R[0][b] + R[1][a] * R[1][b]) + R[2][a] * R[2][b];
+            if (!(std::fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-4)) return VH_ERR_BAD_ARGUMENT;
+        }
+    const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
+                       R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
+    return det > 0.0 ? VH_OK : VH_ERR_BAD_ARGUMENT;
 }
 
 // Timing one launch by the dispatch's own begin / end time stamps (what rocprofv3's kernel trace reports), instead of a

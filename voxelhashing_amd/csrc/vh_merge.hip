@@ -8,12 +8,13 @@
 #include "../../include/vh_api.h"
 #include "vh_device.hpp"
 #include "vh_host_util.hpp"
+#include "vh_scene_ops.hpp"
 
 using namespace vhd;
 
 namespace {
 
-// d_work: kHeader words, then three arrays of n words
+// d_work: kHeader words, then three arrays of n words (vh_scene_ops.hpp has the scheme)
 enum {
     W_PRESENT = 0,
     W_MISSING = 1,
@@ -21,13 +22,9 @@ enum {
     W_PENDING = 3,   // two words: the pending lists' lengths (a pass reads one list and fills the other)
     W_LEFT_OUT = 5,
     W_ALLOCATED = 6,
-    // The voxel counts: kStripes 64-bit words {combined, copied << 32}, each in a cache line of its own, a workgroup
-    // adding to the one its index picks.  (On one word the 35 000 atomics of a merge of 8 800 blocks queued up behind
-    // each other for 0.37 ms, twelve times what the voxels take: DESIGN.md section 6.  Fewer than 2^31 voxels can be merged -- a pool's blocks
-    // are indexed by an int -- so the low half never carries into the high one.)
+    // The voxel counts, striped: 64-bit words {combined, copied << 32}.  (Fewer than 2^31 voxels can be merged -- a pool's
+    // blocks are indexed by an int -- so the low half never carries into the high one.)
     W_VOXELS = 16,
-    kStripes = 32,
-    kStripeWords = 16,
     kHeader = W_VOXELS + kStripes * kStripeWords
 };
 // per source block, in the first array behind the header
@@ -37,24 +34,6 @@ VHD I3 shifted(const VhSDFBlockDesc& d, I3 o)
 {
     // (wrapping, as the table's hash does its products)
     return mki3((int)((uint32_t)d.pos[0] + (uint32_t)o.x), (int)((uint32_t)d.pos[1] + (uint32_t)o.y), (int)((uint32_t)d.pos[2] + (uint32_t)o.z));
-}
-
-// `v` appended to list[*counter ...] by every lane with `take`, one atomic per wave; every lane of the wave calls it
-VHD void wave_append(bool take, uint32_t v, uint32_t* counter, uint32_t* list)
-{
-    const unsigned long long m = __ballot(take);
-    if (m == 0ull) return;
-    uint32_t base = 0u;
-    const int leader = __ffsll((long long)m) - 1;
-    if ((int)lane_id() == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-    if (take) list[base + (uint32_t)__popcll(m & lanemask_lt())] = v;
-}
-// the lanes with `take` counted into *counter, one atomic per wave
-VHD void wave_count(bool take, uint32_t* counter)
-{
-    const unsigned long long m = __ballot(take);
-    if (m != 0ull && (int)lane_id() == __ffsll((long long)m) - 1) atomicAdd(counter, (uint32_t)__popcll(m));
 }
 
 // The occupied entries of a table as a block list {pos, ptr}, in whatever order the atomics give (nothing downstream
@@ -67,13 +46,9 @@ __global__ __launch_bounds__(256) void k_merge_gather(VhHashData hd, uint32_t nu
     int4 q = make_int4(0, 0, 0, VH_FREE_ENTRY);
     if (idx < numEntries && bucket_maybe_occupied(hd, idx / VH_HASH_BUCKET_SIZE)) q = load_quad(&hd.d_hash[idx]);
     const bool take = q.w != VH_FREE_ENTRY;
-    const unsigned long long m = __ballot(take);
+    const uint64_t m = __ballot(take);
     if (m == 0ull) return;
-    uint32_t base = 0u;
-    const int leader = __ffsll((long long)m) - 1;
-    if ((int)lane_id() == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-    const uint32_t at = base + (uint32_t)__popcll(m & lanemask_lt());
+    const uint32_t at = wave_run(m, counter);
     if (take && at < capacity) *reinterpret_cast<int4*>(&out[at]) = q;
 }
 
@@ -178,21 +153,14 @@ __global__ __launch_bounds__(256) void k_merge_combine(VhHashData hd, VhHashPara
     const uint32_t nComb = (uint32_t)__popcll(__ballot(comb0)) + (uint32_t)__popcll(__ballot(comb1));
     const uint32_t nCopy = (uint32_t)__popcll(__ballot(copy0)) + (uint32_t)__popcll(__ballot(copy1));
     if (lane_id() == 0u && (nComb | nCopy) != 0u) // one atomic per wave
-        atomicAdd(reinterpret_cast<unsigned long long*>(&work[W_VOXELS + (b % kStripes) * kStripeWords]), (unsigned long long)nComb | ((unsigned long long)nCopy << 32));
-}
-
-int read_header(const uint32_t* d_work, uint32_t* h, hipStream_t s)
-{
-    VH_HIP(hipMemcpyAsync(h, d_work, kHeader * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    VH_HIP(hipStreamSynchronize(s));
-    return VH_OK;
+        atomicAdd(reinterpret_cast<unsigned long long*>(stripe_of(&work[W_VOXELS], b)), (unsigned long long)nComb | ((unsigned long long)nCopy << 32));
 }
 
 } // namespace
 
 extern "C" {
 
-size_t vh_merge_work_bytes(uint32_t n) { return ((size_t)kHeader + 3u * (size_t)n) * sizeof(uint32_t); }
+size_t vh_merge_work_bytes(uint32_t n) { return settle_work_bytes(kHeader, n); }
 
 int vh_merge_gather(const VhHashData* hd, const VhHashParams* hp, VhSDFBlockDesc* d_descs, uint32_t capacity, uint32_t* d_counter, vhStream_t stream)
 {
@@ -217,46 +185,35 @@ int vh_merge_blocks(const VhHashData* hd, const VhHashParams* hp, uint32_t n, co
     hipStream_t s = (hipStream_t)stream;
     I3 off;
     off.x = blockOffset[0]; off.y = blockOffset[1]; off.z = blockOffset[2];
-    uint32_t* blockState = d_work + kHeader;
-    uint32_t* pending[2] = { blockState + n, blockState + 2u * (size_t)n };
+    const SettleArrays a = settle_arrays(d_work, kHeader, n);
+    uint32_t* blockState = a.blockState;
     uint32_t h[kHeader];
 
     VH_HIP(hipMemsetAsync(d_work, 0, kHeader * sizeof(uint32_t), s));
-    VH_LAUNCH_TIMED(k_merge_classify, cdiv(n, 256), 256, s, *hd, *hp, n, d_descs, off, d_work, blockState, pending[0]);
+    VH_LAUNCH_TIMED(k_merge_classify, cdiv(n, 256), 256, s, *hd, *hp, n, d_descs, off, d_work, blockState, a.pending[0]);
     VH_LAUNCH_TIMED(k_merge_decide, 1, 1, s, *hd, d_work);
     VH_TRY(vh_last_launch_error());
-    VH_TRY(read_header(d_work, h, s));
+    VH_TRY(read_header(d_work, h, kHeader, s));
 
-    // Alloc passes while blocks lose their lock races, the mutexes reset before each (resetHashBucketMutexCUDA: the
-    // caller's token is fresh again).  A pass may make no progress -- two list inserts each holding the other's second
-    // mutex -- so the bound is not one block per pass.
-    const uint32_t mostPasses = h[W_MISSING] + 8u;
-    uint32_t passes = 0u, in = 0u, nPending = h[W_PENDING];
-    while (nPending != 0u && passes < mostPasses) {
-        if (passes != 0u) VH_TRY(vh_reset_bucket_mutex(hd, hp, stream));
-        VH_HIP(hipMemsetAsync(&d_work[W_PENDING + (in ^ 1u)], 0, sizeof(uint32_t), s));
-        VH_LAUNCH_TIMED(k_merge_alloc, cdiv(nPending, 64), 64, s, *hd, *hp, d_descs, off, lockToken, d_work, blockState, pending[in], nPending,
-                        pending[in ^ 1u], in ^ 1u, d_leftOut);
-        VH_TRY(vh_last_launch_error());
-        VH_TRY(read_header(d_work, h, s));
-        in ^= 1u;
-        nPending = h[W_PENDING + in];
-        passes++;
-    }
-    if (nPending != 0u) VH_LAUNCH_TIMED(k_merge_give_up, cdiv(nPending, 64), 64, s, d_work, blockState, pending[in], nPending, d_leftOut);
+    // alloc passes while blocks lose their lock races, starting from the list the classification left
+    Settled st;
+    VH_TRY(settle_passes<kHeader>(hd, hp, stream, d_work, a, W_PENDING, h[W_PENDING], h[W_MISSING] + 8u,
+                                  [&](const uint32_t* pendingIn, uint32_t nIn, uint32_t* pendingOut, uint32_t outSel, uint32_t) {
+                                      VH_LAUNCH_TIMED(k_merge_alloc, cdiv(nIn, 64), 64, s, *hd, *hp, d_descs, off, lockToken, d_work, blockState, pendingIn, nIn,
+                                                      pendingOut, outSel, d_leftOut);
+                                  }, &st));
+    if (st.nPending != 0u) VH_LAUNCH_TIMED(k_merge_give_up, cdiv(st.nPending, 64), 64, s, d_work, blockState, a.pending[st.in], st.nPending, d_leftOut);
     if (!(h[W_STATUS] & VH_MERGE_HEAP_SHORT)) VH_LAUNCH_TIMED(k_merge_combine, n, 256, s, *hd, *hp, n, d_descs, d_blocks, srcSDFBlocks, off, d_work, blockState);
     VH_TRY(vh_last_launch_error());
-    VH_TRY(read_header(d_work, h, s));
+    VH_TRY(read_header(d_work, h, kHeader, s));
 
     counts_out[VH_MERGE_SOURCE_BLOCKS] = n;
     counts_out[VH_MERGE_PRESENT] = h[W_PRESENT];
     counts_out[VH_MERGE_ALLOCATED] = h[W_ALLOCATED];
     counts_out[VH_MERGE_LEFT_OUT] = h[W_LEFT_OUT];
-    for (uint32_t k = 0; k < kStripes; k++) {
-        counts_out[VH_MERGE_COMBINED] += h[W_VOXELS + k * kStripeWords];
-        counts_out[VH_MERGE_COPIED] += h[W_VOXELS + k * kStripeWords + 1];
-    }
-    counts_out[VH_MERGE_ALLOC_PASSES] = passes;
+    counts_out[VH_MERGE_COMBINED] = stripes_sum(h, W_VOXELS, 0);
+    counts_out[VH_MERGE_COPIED] = stripes_sum(h, W_VOXELS, 1);
+    counts_out[VH_MERGE_ALLOC_PASSES] = st.passes;
     counts_out[VH_MERGE_STATUS] = h[W_STATUS];
     return VH_OK;
 }

@@ -1,9 +1,11 @@
 // vh_mesh_table.hpp -- what the indexed-mesh passes share on the device: the open-addressing table of 64-bit keys that the
-// weld (vh_mesh.hip) and the clustering (vh_mesh_cluster.hip) probe, and the one-atomic-per-wave list helpers.  Device only.
+// weld (vh_mesh.hip) and the clustering (vh_mesh_cluster.hip) probe; the one-atomic-per-wave list helpers they use come
+// with vh_scene_ops.hpp.
 #pragma once
 
 #include "vh_device.hpp"
 #include "vh_mesh_key.hpp"
+#include "vh_scene_ops.hpp"
 
 namespace {
 
@@ -14,26 +16,6 @@ VHD uint32_t weld_home(uint64_t k, uint32_t mask)
     k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
     k ^= k >> 33;
     return (uint32_t)k & mask;
-}
-
-// base of `keep` lanes' run in a list that *counter counts: one atomic per wave.  Every lane of the wave calls it.
-VHD uint32_t wave_append(bool keep, uint32_t* counter)
-{
-    const uint64_t m = __ballot(keep);
-    if (m == 0ull) return 0u;
-    const int leader = __ffsll((unsigned long long)m) - 1;
-    uint32_t base = 0u;
-    if ((int)vhd::lane_id() == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-    return base + (uint32_t)__popcll(m & vhd::lanemask_lt());
-}
-
-// counts the lanes with `flag` into *counter: one atomic per wave.  Every lane of the wave calls it.
-VHD void wave_count(bool flag, uint32_t* counter)
-{
-    const uint64_t m = __ballot(flag);
-    if (m == 0ull) return;
-    if ((int)vhd::lane_id() == __ffsll((unsigned long long)m) - 1) atomicAdd(counter, (uint32_t)__popcll(m));
 }
 
 constexpr uint32_t kNoSlot = 0xffffffffu;

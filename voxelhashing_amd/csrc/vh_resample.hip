@@ -13,6 +13,7 @@
 #include "vh_host_util.hpp"
 #include "vh_mesh_table.hpp"
 #include "vh_resample_blend.hpp"
+#include "vh_scene_ops.hpp"
 
 using namespace vhd;
 
@@ -24,11 +25,7 @@ enum {
     W_CANDIDATES = 0,
     W_STATUS = 1,
     W_STAGED = 2,
-    // observed voxels: kStripes words, each in a cache line of its own, a workgroup adding to the one its index picks (as
-    // the merge's voxel counts: DESIGN.md section 6 "Scene merge")
-    W_OBSERVED = 16,
-    kStripes = 32,
-    kStripeWords = 16,
+    W_OBSERVED = 16, // observed voxels, striped (vh_scene_ops.hpp)
     kHeader = W_OBSERVED + kStripes * kStripeWords
 };
 
@@ -187,7 +184,7 @@ __global__ __launch_bounds__(256) void k_resample_blocks(VhHashData hd, VhHashPa
     const uint32_t seen = (uint32_t)__popcll(__ballot((r0.y >> 24) != 0u)) + (uint32_t)__popcll(__ballot((r1.y >> 24) != 0u));
     if (lane_id() == 0u) {
         s_observed[t / kWave] = seen;
-        if (seen != 0u) atomicAdd(&w.header[W_OBSERVED + (c % kStripes) * kStripeWords], seen); // one atomic per wave
+        if (seen != 0u) atomicAdd(stripe_of(&w.header[W_OBSERVED], c), seen); // one atomic per wave
     }
     __syncthreads();
     if (t == 0u && (s_observed[0] | s_observed[1] | s_observed[2] | s_observed[3]) != 0u) {
@@ -199,20 +196,12 @@ __global__ __launch_bounds__(256) void k_resample_blocks(VhHashData hd, VhHashPa
     }
 }
 
-int read_header(const uint32_t* d_work, uint32_t* h, hipStream_t s)
-{
-    VH_HIP(hipMemcpyAsync(h, d_work, kHeader * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    VH_HIP(hipStreamSynchronize(s));
-    return VH_OK;
-}
-
 void fill_counts(uint32_t n, const uint32_t* h, uint32_t* counts_out)
 {
     counts_out[VH_RESAMPLE_SOURCE_BLOCKS] = n;
     counts_out[VH_RESAMPLE_CANDIDATES] = h[W_CANDIDATES];
     counts_out[VH_RESAMPLE_STAGED] = h[W_STAGED];
-    counts_out[VH_RESAMPLE_OBSERVED] = 0u;
-    for (uint32_t k = 0; k < kStripes; k++) counts_out[VH_RESAMPLE_OBSERVED] += h[W_OBSERVED + k * kStripeWords];
+    counts_out[VH_RESAMPLE_OBSERVED] = stripes_sum(h, W_OBSERVED, 0);
     counts_out[VH_RESAMPLE_STATUS] = h[W_STATUS];
 }
 
@@ -245,24 +234,9 @@ int vh_resample_voxel_transforms(const double* T, float vsSrc, float vsDst, floa
 {
     if (!T || !srcVoxFromDstVox || !dstVoxFromSrcVox) return VH_ERR_BAD_ARGUMENT;
     if (!std::isfinite(vsSrc) || !std::isfinite(vsDst) || !(vsSrc > 0.0f) || !(vsDst > 0.0f)) return VH_ERR_BAD_ARGUMENT;
-    for (int k = 0; k < 16; k++)
-        if (!std::isfinite(T[k])) return VH_ERR_BAD_ARGUMENT;
-    if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return VH_ERR_BAD_ARGUMENT;
+    VH_TRY(vh_rigid_or_refuse(T));
     const double s = (double)vsSrc, d = (double)vsDst;
     if (s / d < 0.5 || s / d > 2.0) return VH_ERR_BAD_ARGUMENT;
-    double R[3][3], t[3];
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) R[r][c] = T[4 * r + c];
-        t[r] = T[4 * r + 3];
-    }
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) {
-            const double dot = (R[0][a] * R[0][b] + R[1][a] * R[1][b]) + R[2][a] * R[2][b];
-            if (!(std::fabs(dot - (a == b ? 1.0 : 0.0)) <= 1e-4)) return VH_ERR_BAD_ARGUMENT;
-        }
-    const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
-                       R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
-    if (!(det > 0.0)) return VH_ERR_BAD_ARGUMENT;
     voxel_matrices(T, s, d, srcVoxFromDstVox, dstVoxFromSrcVox);
     return VH_OK;
 }
@@ -300,20 +274,20 @@ int vh_resample_blocks(const VhHashData* srcHd, const VhHashParams* srcHp, uint3
             VH_LAUNCH_TIMED(k_resample_candidates, cdiv(n, wavesPerGroup), 256, s, n, d_srcDescs, m, span, cdiv(span * span * span, kWave), slotsLog2, w);
             VH_TRY(vh_last_launch_error());
         }
-        VH_TRY(read_header(d_work, h, s));
+        VH_TRY(read_header(d_work, h, kHeader, s));
         fill_counts(n, h, counts_out);
         return VH_OK;
     }
 
     // fill: the voxels of the candidates the count call left in d_work
-    VH_TRY(read_header(d_work, h, s));
+    VH_TRY(read_header(d_work, h, kHeader, s));
     const uint32_t numCandidates = h[W_CANDIDATES];
     if (numCandidates > S || numCandidates > stagingBlocks || (uint64_t)numCandidates * VH_SDF_BLOCK_VOXELS > 0x7fffffffull) return VH_ERR_BAD_ARGUMENT;
     if (h[W_STATUS] == 0u && numCandidates != 0u) {
         for (int k = 0; k < 12; k++) m.m[k] = srcVoxFromDstVox[k];
         VH_LAUNCH_TIMED(k_resample_blocks, numCandidates, 256, s, *srcHd, *srcHp, m, numCandidates, w, d_staging, d_outDescs);
         VH_TRY(vh_last_launch_error());
-        VH_TRY(read_header(d_work, h, s));
+        VH_TRY(read_header(d_work, h, kHeader, s));
     }
     fill_counts(n, h, counts_out);
     return VH_OK;

@@ -83,20 +83,26 @@ def _merge_upload(descs, blocks, stream):
     return DeviceBuffer.from_numpy(descs, stream), DeviceBuffer.from_numpy(blocks, stream), n
 
 
-def _merge_result(code, counts, left, what):
-    """the counts by name plus left_out_indices, read from (buffer, stream), or None; an error code raises VhError with
-    .counts"""
-    out = {k: int(v) for k, v in zip(T.MERGE_COUNTS, counts)}
-    out["left_out_indices"] = None
-    if left is not None:
-        out["left_out_indices"] = np.sort(left[0].download(np.uint32, out["left_out"], left[1]).astype(np.int64))
-    if code != 0:
+def _counts_result(names, code, counts, what, extra=None):
+    """the counts by name (a list of vhtypes: MERGE_COUNTS, CUT_COUNTS, DEINT_COUNTS) plus `extra`; with `what`, an
+    error code raises VhError with .counts"""
+    out = {k: int(v) for k, v in zip(names, counts)}
+    out.update(extra or {})
+    if what is not None and code != 0:
         try:
             check(code, what)
         except Exception as e:
             e.counts = out
             raise
     return out
+
+
+def _merge_result(code, counts, left, what):
+    """the merge's counts plus left_out_indices, read from (buffer, stream), or None"""
+    idx = None
+    if left is not None:
+        idx = np.sort(left[0].download(np.uint32, int(counts[T.MERGE_COUNTS.index("left_out")]), left[1]).astype(np.int64))
+    return _counts_result(T.MERGE_COUNTS, code, counts, what, {"left_out_indices": idx})
 
 
 def resample_voxel_transforms(dst_from_src, vs_src, vs_dst):
@@ -123,16 +129,7 @@ def cut_region_transform(world_from_region, half_extents, voxel_size):
 
 
 def _cut_result(code, counts, what, extra=None):
-    """the counts by name (vhtypes.CUT_COUNTS) plus `extra`; an error code raises VhError with .counts"""
-    out = {k: int(v) for k, v in zip(T.CUT_COUNTS, counts)}
-    out.update(extra or {})
-    if code != 0:
-        try:
-            check(code, what)
-        except Exception as e:
-            e.counts = out
-            raise
-    return out
+    return _counts_result(T.CUT_COUNTS, code, counts, what, extra)
 
 
 def _staged_list(d_descs, d_blocks, n, stream):
@@ -170,15 +167,7 @@ def extract_from_block_list(descs, blocks, region_from_vox, shape, select_outsid
 
 
 def _deint_result(code, counts, what):
-    """the counts by name (vhtypes.DEINT_COUNTS); an error code raises VhError with .counts"""
-    out = {k: int(v) for k, v in zip(T.DEINT_COUNTS, counts)}
-    if code != 0:
-        try:
-            check(code, what)
-        except Exception as e:
-            e.counts = out
-            raise
-    return out
+    return _counts_result(T.DEINT_COUNTS, code, counts, what)
 
 
 def _frame_data(frame, cp, what):
@@ -1011,9 +1000,8 @@ class LauncherScene:
             rc = self.L.vh_cut_blocks(C.byref(self.hd), C.byref(self.hp), n, d_desc.ptr, d_blocks.ptr if d_blocks is not None else None, m.ctypes.data,
                                       int(shape), int(fl), lock_token, d_work.ptr, d_out.ptr if d_out else None, d_staging.ptr if d_staging else None,
                                       room, counts, self.stream)
-            out = {k: int(v) for k, v in zip(T.CUT_COUNTS, counts)}
-            out.update(code=rc, descs=np.zeros(0, T.DESC_DTYPE), voxels=np.zeros((0, T.SDF_BLOCK_VOXELS), T.VOXEL_DTYPE), staging_raw=None)
-            return out
+            return _counts_result(T.CUT_COUNTS, rc, counts, None, dict(code=rc, descs=np.zeros(0, T.DESC_DTYPE),
+                                                                       voxels=np.zeros((0, T.SDF_BLOCK_VOXELS), T.VOXEL_DTYPE), staging_raw=None))
 
         if not (flags & T.CUT_LIFT) or (flags & T.CUT_COUNT_ONLY):
             return call(flags, None, None, 0)
@@ -1042,9 +1030,7 @@ class LauncherScene:
         counts = (C.c_uint32 * len(T.DEINT_COUNTS))()
         rc = self.L.vh_deintegrate_blocks(C.byref(self.hd), C.byref(hp), n, d_desc.ptr, C.byref(frame.data), C.byref(cp), int(flags), lock_token, d_work.ptr,
                                           counts, self.stream)
-        out = {k: int(v) for k, v in zip(T.DEINT_COUNTS, counts)}
-        out["code"] = rc
-        return out
+        return _counts_result(T.DEINT_COUNTS, rc, counts, None, {"code": rc})
 
     def align_begin(self, source, guess, pivot, radius):
         """vh_align_begin for `source` (a LauncherScene) against this scene -> (the state in device memory, the ticket
