@@ -814,10 +814,8 @@ struct MeshData {
 };
 } // namespace vh
 
-struct VhMeshNormals;    // opaque: the buffers of the vertex-normal pass (csrc/vh_mesh_normals.hpp)
-struct VhMeshComponents; // opaque: the buffers of the component pass (csrc/vh_mesh_components.hpp)
-struct VhMeshCluster;    // opaque: the buffers of the vertex clustering (csrc/vh_mesh_cluster.hpp)
-struct VhMeshSmooth;     // opaque: the buffers of the Taubin smoothing (csrc/vh_mesh_smooth.hpp)
+struct VhMeshFinish;     // opaque: the passes over a welded mesh and their buffers (csrc/vh_mesh_finish.hpp)
+struct VhMeshView;       // opaque: an indexed mesh on the device
 
 class CUDAMarchingCubesHashSDF {
 public:
@@ -947,7 +945,10 @@ private:
     // the walk of .cpp:149-192: perChunk(hashData, hashParams, minCorner, maxCorner) for every chunk that has blocks, with
     // its neighbourhood streamed in.  restoreOnError: when a chunk throws, the scene goes back as the normal end puts it.
     template <class F> void walkChunks(CUDASceneRepChunkGrid& chunkGrid, const vh::vec3f& camPos, float radius, bool restoreOnError, F&& perChunk);
-    // indexed extraction: made by its first call
+    // indexed extraction: made by its first call.  The finish is one chain of passes over the welded mesh -- clustering,
+    // smoothing, normals, components (csrc/vh_mesh_finish.hpp; DESIGN.md section 4, "The finish as one chain") -- which
+    // owns every pass's buffers, each made by the first run with its option on: m_finish for the one-shot weld, the
+    // accumulation's own for m_accum
     bool m_welded = false;                      // m_meshData is the weld's mesh, untouched since
     vh::DevicePtr<VhTriangleSource> d_sources;  // m_maxNumTriangles records beside m_data.d_triangles
     VhMeshWeldData m_weld;                      // from vh_mesh_weld_data_alloc; m_weldOwner gives it back
@@ -956,25 +957,19 @@ private:
     // accumulated indexed extraction: made by the first beginIndexed
     struct AccumFree { void operator()(VhMeshWeldAccum* a) const noexcept; };
     std::unique_ptr<VhMeshWeldAccum, AccumFree> m_accum;
-    // vertex normals: the one-shot extraction's buffers (csrc/vh_mesh_normals.hpp) are made by its first call with the option on
-    bool m_indexedNormals = false;
-    std::unique_ptr<VhMeshNormals> m_normals;   // (complete where the constructor and the destructor are: vh_marching_cubes.cpp)
-    // component filter: the one-shot extraction's buffers (csrc/vh_mesh_components.hpp) are made by its first call with the filter on
-    unsigned int m_componentMinFaces = 0;
-    bool m_componentLargestOnly = false;
-    std::unique_ptr<VhMeshComponents> m_components;
-    // vertex clustering: the one-shot extraction's buffers (csrc/vh_mesh_cluster.hpp) are made by its first call with the option on
+    std::unique_ptr<VhMeshFinish> m_finish;     // (complete where the constructor and the destructor are: vh_marching_cubes.cpp)
+    // the options of the finish, in the chain's order
     unsigned int m_clusterCells = 0;
-    std::unique_ptr<VhMeshCluster> m_cluster;
-    // Taubin smoothing: the one-shot extraction's buffers (csrc/vh_mesh_smooth.hpp) are made by its first call with the option on
     unsigned int m_smoothIterations = 0;
     int32_t m_smoothLambdaQ16 = VH_SMOOTH_DEFAULT_LAMBDA_Q16, m_smoothMuQ16 = VH_SMOOTH_DEFAULT_MU_Q16;
     bool m_smoothKeepBoundary = true;
-    std::unique_ptr<VhMeshSmooth> m_smooth;
+    bool m_indexedNormals = false;
+    unsigned int m_componentMinFaces = 0;
+    bool m_componentLargestOnly = false;
     struct IndexedResult {                      // what the last indexed extraction left; the empty one is the state after an error
         unsigned int counts[VH_WELD_ACCUM_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 }; // {vertices, faces, status}, then the accumulation's three
         unsigned int numSourced = 0;            // triangles of its last sourced pass 2 that are in the buffer
-        bool accumulated = false;               // begun by beginIndexed: downloadIndexed reads m_accum, not m_weld
+        bool accumulated = false;               // begun by beginIndexed: the mesh and the chain are m_accum's, not m_weld's and m_finish
         bool hasNormals = false;                // it computed them
         float voxelSize = 0.0f;                 // of the last appendIndexed: finishIndexed's scale
         bool filtered = false;                  // the component filter ran: the mesh is kept[] = {vertices, faces} of the filter's own buffers
@@ -987,9 +982,12 @@ private:
     } m_indexed;
     void clearWeldedMark() { m_welded = false; for (unsigned int& c : m_indexed.componentStats) c = 0; for (unsigned int& c : m_indexed.clusterStats) c = 0; for (unsigned int& c : m_indexed.smoothStats) c = 0; }
     void resetIndexed() { clearMeshBuffer(); m_indexed = IndexedResult(); }
-    // the welded mesh on the device (m_accum's, or m_weld's) through the passes that are on -- clustering, smoothing, normals,
-    // components, at the scales of that voxel size -- into the mesh buffer; then its counts and marks
+    // the welded mesh on the device (m_accum's, or m_weld's) through the stages of its chain that are on, at the scales
+    // of that voxel size; one download of the mesh after the last stage into the mesh buffer; then its counts and marks
     void readBackIndexed(unsigned int numVertices, unsigned int numFaces, bool accumulated, float voxelSize);
+    VhMeshFinish& indexedChain(bool accumulated);
+    VhMeshView indexedBase(bool accumulated, unsigned int numVertices, unsigned int numFaces) const;
+    VhMeshView indexedView(const char* what);   // what downloadIndexed and downloadIndexedNormals read
     // the one-shot weld of the nTriangles triangles and records in the buffers, then readBackIndexed
     void weldAndReadBack(unsigned int nTriangles, float voxelSize);
     // live mesh: the buffers are made by the first liveBegin

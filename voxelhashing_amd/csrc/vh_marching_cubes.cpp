@@ -18,10 +18,7 @@
 
 #include "../../include/vh.hpp"
 #include "vh_host_util.hpp"
-#include "vh_mesh_cluster.hpp"
-#include "vh_mesh_components.hpp"
-#include "vh_mesh_normals.hpp"
-#include "vh_mesh_smooth.hpp"
+#include "vh_mesh_finish.hpp"
 
 // ---------------------------------------------------------------------------
 // launcher-level buffers
@@ -356,6 +353,26 @@ void checkWeld(int rc, const char* what)
     check(rc, what);
 }
 
+// What a stage of the finish left as the exception the indexed extractions throw: a launch that failed, or the status the
+// pass wrote (a text of null: that code has none of its own)
+struct StageTexts { const char* launch; const char* pass; const char* overflow; const char* badArgument; };
+const StageTexts kStageTexts[VH_FINISH_NUM_STAGES] = {
+    { "vh_mesh_cluster", "mesh clustering", "mesh clustering: a table is full",
+      "mesh clustering: a key that is no vertex key, a value out of the fixed-point range, or a face index out of bounds" },
+    { "vh_mesh_smooth", "mesh smoothing", "mesh smoothing: the edge table is full",
+      "mesh smoothing: a value out of the fixed-point range, a face index out of bounds, or a vertex of more than 65536 neighbours" },
+    { "vh_mesh_vertex_normals", "vertex normals", nullptr, "vertex normals: a face normal is out of the fixed-point range, or a face index out of bounds" },
+    { "vh_mesh_components", "mesh components", nullptr, "mesh components: a face index out of bounds" },
+};
+void checkStage(VhFinishStage stage, int launched, int status)
+{
+    const StageTexts& t = kStageTexts[stage];
+    check(launched, t.launch);
+    if (status == VH_ERR_STAGING_OVERFLOW && t.overflow) throw vh::Error(status, t.overflow);
+    if (status == VH_ERR_BAD_ARGUMENT && t.badArgument) throw vh::Error(status, t.badArgument);
+    check(status, t.pass);
+}
+
 // n vertex records as the mesh container has them: positions, and rgb with alpha 1
 void recordsToMeshData(const VhVertex* v, size_t n, vh::MeshData& md)
 {
@@ -389,134 +406,74 @@ void CUDAMarchingCubesHashSDF::setIndexedSmoothingQ16(unsigned int iterations, i
     m_smoothIterations = iterations; m_smoothLambdaQ16 = lambdaQ16; m_smoothMuQ16 = muQ16; m_smoothKeepBoundary = keepBoundary;
 }
 
+// the chain of the last indexed extraction, and the welded mesh it runs over
+VhMeshFinish& CUDAMarchingCubesHashSDF::indexedChain(bool accumulated)
+{
+    if (accumulated) return vh_mesh_weld_accum_finish(m_accum.get());
+    if (!m_finish) m_finish.reset(new VhMeshFinish);
+    return *m_finish;
+}
+
+VhMeshView CUDAMarchingCubesHashSDF::indexedBase(bool accumulated, unsigned int nv, unsigned int nf) const
+{
+    if (accumulated) return vh_mesh_weld_accum_base(m_accum.get(), nv, nf);
+    return VhMeshView{ m_weld.d_vertices, m_weld.d_keys, m_weld.d_faces, nullptr, nv, nf };
+}
+
 void CUDAMarchingCubesHashSDF::readBackIndexed(unsigned int nv, unsigned int nf, bool accumulated, float voxelSize)
 {
-    vh::MeshData md;
     const bool filter = m_componentMinFaces != 0 || m_componentLargestOnly, cluster = m_clusterCells != 0, smooth = m_smoothIterations != 0;
     // (an accumulation without an append has no voxel size, and no vertex either: any scale serves)
     const bool sized = voxelSize > 0.0f || !accumulated;
-    unsigned int clusterStats[VH_CLUSTER_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
-    // the mesh the later passes and the download work on: the weld's (the accumulator knows its own), or the clustered one
-    const VhVertex* d_vertices = accumulated ? nullptr : m_weld.d_vertices;
-    const uint64_t* d_keys = accumulated ? nullptr : m_weld.d_keys;
-    const uint32_t* d_faces = accumulated ? nullptr : m_weld.d_faces;
-    if (cluster) {
-        // a cluster spans chunks: a pass of the finish.  The welded mesh stays where it is.
-        int32_t clusterScale = 0;
-        if (sized) check(vh_mesh_cluster_default_scale_log2(voxelSize, &clusterScale), "vh_mesh_cluster_default_scale_log2");
-        int rc = VH_OK;
-        if (accumulated) {
-            check(vh_mesh_weld_accum_cluster(m_accum.get(), m_clusterCells, clusterScale, m_stream), "vh_mesh_weld_accum_cluster");
-            rc = vh_mesh_weld_accum_cluster_get_counts(m_accum.get(), clusterStats, m_stream);
-        } else {
-            if (!m_cluster) m_cluster.reset(new VhMeshCluster);
-            check(m_cluster->run(d_vertices, d_keys, d_faces, nv, nf, m_clusterCells, clusterScale, m_stream), "vh_mesh_cluster");
-            rc = m_cluster->counts(clusterStats, m_stream);
-            d_vertices = m_cluster->vertices.get(); d_keys = m_cluster->keys.get(); d_faces = m_cluster->faces.get();
-        }
-        if (rc == VH_ERR_STAGING_OVERFLOW) throw vh::Error(rc, "mesh clustering: a table is full");
-        if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "mesh clustering: a key that is no vertex key, a value out of the fixed-point range, or a face index out of bounds");
-        check(rc, "mesh clustering");
-    } else if (accumulated) {
-        // a finish of these appends with clustering on may have gone before: the passes below are of the welded mesh
-        check(vh_mesh_weld_accum_cluster(m_accum.get(), 0, 0, m_stream), "vh_mesh_weld_accum_cluster");
-    }
-    const unsigned int weldedVertices = nv, weldedFaces = nf;
-    if (cluster) { nv = clusterStats[VH_CLUSTER_VERTICES]; nf = clusterStats[VH_CLUSTER_FACES]; }
-    unsigned int smoothStats[VH_SMOOTH_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
-    if (smooth) {
-        // a vertex's neighbours span chunks: a pass of the finish, over the mesh as it stands here, at the clustering's scale
-        int32_t smoothScale = 0;
-        if (sized) check(vh_mesh_cluster_default_scale_log2(voxelSize, &smoothScale), "vh_mesh_cluster_default_scale_log2");
-        int rc = VH_OK;
-        if (accumulated) {
-            check(vh_mesh_weld_accum_smooth(m_accum.get(), m_smoothIterations, m_smoothLambdaQ16, m_smoothMuQ16, m_smoothKeepBoundary ? 1u : 0u, smoothScale, m_stream),
-                  "vh_mesh_weld_accum_smooth");
-            rc = vh_mesh_weld_accum_smooth_get_counts(m_accum.get(), smoothStats, m_stream);
-        } else {
-            if (!m_smooth) m_smooth.reset(new VhMeshSmooth);
-            check(m_smooth->run(d_vertices, d_keys, d_faces, nv, nf, m_smoothIterations, m_smoothLambdaQ16, m_smoothMuQ16, m_smoothKeepBoundary ? 1u : 0u, smoothScale,
-                                m_stream), "vh_mesh_smooth");
-            rc = m_smooth->counts(smoothStats, m_stream);
-            d_vertices = m_smooth->vertices.get();
-        }
-        if (rc == VH_ERR_STAGING_OVERFLOW) throw vh::Error(rc, "mesh smoothing: the edge table is full");
-        if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "mesh smoothing: a value out of the fixed-point range, a face index out of bounds, or a vertex of more than 65536 neighbours");
-        check(rc, "mesh smoothing");
-    } else if (accumulated) {
-        // a finish of these appends with smoothing on may have gone before: the passes below take the vertices as they were
-        check(vh_mesh_weld_accum_smooth(m_accum.get(), 0, 0, 0, 0, 0, m_stream), "vh_mesh_weld_accum_smooth");
-    }
-    int32_t scaleLog2 = 0;
-    // the vertices of a welded face lie in adjacent clusters and inside their clusters' boxes: an edge of a clustered
-    // face stays under 2 m voxels in every component, and the normals' scale is that of a voxel of 2 m voxelSize.
-    // Smoothing can lengthen an edge: twice that bound again, which is a margin and not a proof (VH_NORMALS_RANGE says so)
-    if (m_indexedNormals && sized)
-        check(vh_mesh_normals_default_scale_log2((smooth ? 2.0f : 1.0f) * (cluster ? 2.0f * (float)m_clusterCells * voxelSize : voxelSize), &scaleLog2),
-              "vh_mesh_normals_default_scale_log2");
+    VhMeshFinish& chain = indexedChain(accumulated);
+    const VhMeshView base = indexedBase(accumulated, nv, nf);
+    // A stage that is off is forgotten -- a finish of these appends with it on may have gone before --, so that the mesh
+    // after the last stage is the mesh of THIS finish.  The welded mesh stays where it is.
+    unsigned int clusterStats[VH_CLUSTER_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 }, smoothStats[VH_SMOOTH_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
+    int32_t meshScale = 0; // of the clustering, and of the smoothing over the mesh as it then stands
+    if ((cluster || smooth) && sized) check(vh_mesh_cluster_default_scale_log2(voxelSize, &meshScale), "vh_mesh_cluster_default_scale_log2");
+    if (cluster) { // a cluster spans chunks: a pass of the finish
+        const int launched = chain.cluster(base, m_clusterCells, meshScale, m_stream, clusterStats);
+        checkStage(VH_FINISH_CLUSTER, launched, chain.state.code[VH_FINISH_CLUSTER]);
+    } else chain.forget(VH_FINISH_CLUSTER);
+    if (smooth) { // and so do a vertex's neighbours
+        const int launched = chain.smooth(base, m_smoothIterations, m_smoothLambdaQ16, m_smoothMuQ16, m_smoothKeepBoundary ? 1u : 0u, meshScale, m_stream, smoothStats);
+        checkStage(VH_FINISH_SMOOTH, launched, chain.state.code[VH_FINISH_SMOOTH]);
+    } else chain.forget(VH_FINISH_SMOOTH);
     if (m_indexedNormals) {
-        // over all the faces, with the bits the last append left: a pass of the finish, never of an append.  With the
-        // filter on only the pass's status comes back here: the normals come with the filtered mesh.
-        const unsigned int toHost = filter ? 0u : nv;
-        md.m_Normals.resize(3 * (size_t)toHost);
-        int rc = VH_OK;
-        if (accumulated) {
-            check(vh_mesh_weld_accum_normals(m_accum.get(), scaleLog2, m_stream), "vh_mesh_weld_accum_normals");
-            rc = vh_mesh_weld_accum_download_normals(m_accum.get(), md.m_Normals.data(), toHost, m_stream);
-        } else {
-            if (!m_normals) m_normals.reset(new VhMeshNormals);
-            check(m_normals->run(d_vertices, d_keys, d_faces, nv, nf, scaleLog2, m_stream), "vh_mesh_vertex_normals");
-            rc = m_normals->download(md.m_Normals.data(), toHost, true, m_stream);
-        }
-        if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "vertex normals: a face normal is out of the fixed-point range, or a face index out of bounds");
-        check(rc, "vertex normals");
-    }
-    unsigned int stats[VH_COMPONENTS_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 }, mv = nv, mf = nf; // mv, mf: the mesh that goes to the host
-    if (filter) {
-        // a component spans chunks: like the normals a pass of the finish.  The unfiltered mesh stays where it is.
-        int rc = VH_OK;
-        if (accumulated) {
-            check(vh_mesh_weld_accum_components(m_accum.get(), m_componentMinFaces, m_componentLargestOnly ? 1u : 0u, m_stream), "vh_mesh_weld_accum_components");
-            rc = vh_mesh_weld_accum_components_get_counts(m_accum.get(), stats, m_stream);
-        } else {
-            if (!m_components) m_components.reset(new VhMeshComponents);
-            check(m_components->run(d_vertices, d_keys, m_indexedNormals ? m_normals->normals.get() : nullptr, d_faces, nv, nf,
-                                    m_componentMinFaces, m_componentLargestOnly ? 1u : 0u, m_stream), "vh_mesh_components");
-            rc = m_components->counts(stats, m_stream);
-        }
-        if (rc == VH_ERR_BAD_ARGUMENT) throw vh::Error(rc, "mesh components: a face index out of bounds");
-        check(rc, "mesh components");
-        mv = stats[VH_COMPONENTS_KEPT_VERTICES]; mf = stats[VH_COMPONENTS_KEPT_FACES];
-        if (m_indexedNormals) md.m_Normals.resize(3 * (size_t)mv);
-    }
-    std::vector<VhVertex> verts(mv);
-    md.m_FaceIndicesVertices.resize(3 * (size_t)mf);
-    float* normals = filter && m_indexedNormals ? md.m_Normals.data() : nullptr;
-    if (smooth && !filter) { // the smoothed vertices with the faces of the mesh they were made from
-        VhVertex* none = nullptr;
-        if (accumulated) check(vh_mesh_weld_accum_smooth_download(m_accum.get(), verts.data(), nv, m_stream), "vh_mesh_weld_accum_smooth_download");
-        else check(m_smooth->download(verts.data(), nv, m_stream), "mesh smoothing");
-        if (cluster && accumulated) check(vh_mesh_weld_accum_cluster_download(m_accum.get(), none, nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_cluster_download");
-        else if (cluster) check(m_cluster->download(none, nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "mesh clustering");
-        else if (accumulated) check(vh_mesh_weld_accum_download(m_accum.get(), none, nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_download");
-        else check(vh_mesh_weld_download(&m_weld, none, nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_download");
-    }
-    else if (filter && accumulated) check(vh_mesh_weld_accum_components_download(m_accum.get(), verts.data(), nullptr, normals, md.m_FaceIndicesVertices.data(), mv, mf, m_stream), "vh_mesh_weld_accum_components_download");
-    else if (filter) check(m_components->download(verts.data(), nullptr, normals, md.m_FaceIndicesVertices.data(), mv, mf, m_stream), "mesh components");
-    else if (cluster && accumulated) check(vh_mesh_weld_accum_cluster_download(m_accum.get(), verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_cluster_download");
-    else if (cluster) check(m_cluster->download(verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "mesh clustering");
-    else if (accumulated) check(vh_mesh_weld_accum_download(m_accum.get(), verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_accum_download");
-    else check(vh_mesh_weld_download(&m_weld, verts.data(), nullptr, md.m_FaceIndicesVertices.data(), nv, nf, m_stream), "vh_mesh_weld_download");
+        // the vertices of a welded face lie in adjacent clusters and inside their clusters' boxes: an edge of a clustered
+        // face stays under 2 m voxels in every component, and the normals' scale is that of a voxel of 2 m voxelSize.
+        // Smoothing can lengthen an edge: twice that bound again, which is a margin and not a proof (VH_NORMALS_RANGE says so)
+        int32_t scaleLog2 = 0;
+        if (sized)
+            check(vh_mesh_normals_default_scale_log2((smooth ? 2.0f : 1.0f) * (cluster ? 2.0f * (float)m_clusterCells * voxelSize : voxelSize), &scaleLog2),
+                  "vh_mesh_normals_default_scale_log2");
+        // over all the faces, with the bits the last append left: a pass of the finish, never of an append.  Only its
+        // status comes back here: the normals come with the mesh
+        const int launched = chain.normals(base, scaleLog2, m_stream);
+        checkStage(VH_FINISH_NORMALS, launched, launched == VH_OK ? chain.normalsStatus(m_stream) : VH_OK);
+    } else chain.forget(VH_FINISH_NORMALS);
+    unsigned int stats[VH_COMPONENTS_NUM_COUNTS] = { 0, 0, 0, 0, 0, 0 };
+    if (filter) { // a component spans chunks
+        const int launched = chain.components(base, m_componentMinFaces, m_componentLargestOnly ? 1u : 0u, m_stream);
+        checkStage(VH_FINISH_COMPONENTS, launched, launched == VH_OK ? chain.componentsCounts(stats, m_stream) : VH_OK);
+    } else chain.forget(VH_FINISH_COMPONENTS);
+    const VhMeshView mesh = chain.after(VH_FINISH_COMPONENTS, base); // the mesh that goes to the host
+    vh::MeshData md;
+    std::vector<VhVertex> verts(mesh.numVertices);
+    md.m_FaceIndicesVertices.resize(3 * (size_t)mesh.numFaces);
+    if (m_indexedNormals) md.m_Normals.resize(3 * (size_t)mesh.numVertices);
+    check(VhMeshFinish::download(mesh, verts.data(), nullptr, m_indexedNormals ? md.m_Normals.data() : nullptr, md.m_FaceIndicesVertices.data(), m_stream), "indexed mesh download");
     recordsToMeshData(verts.data(), verts.size(), md);
     m_meshData = std::move(md);
-    m_indexed.counts[0] = weldedVertices; m_indexed.counts[1] = weldedFaces;
+    m_indexed.counts[0] = nv; m_indexed.counts[1] = nf;
     m_indexed.clustered = cluster;
     std::copy(clusterStats, clusterStats + VH_CLUSTER_NUM_COUNTS, m_indexed.clusterStats);
     m_indexed.smoothed = smooth;
     std::copy(smoothStats, smoothStats + VH_SMOOTH_NUM_COUNTS, m_indexed.smoothStats);
     m_indexed.hasNormals = m_indexedNormals;
     m_indexed.filtered = filter;
-    m_indexed.kept[0] = mv; m_indexed.kept[1] = mf;
+    m_indexed.kept[0] = mesh.numVertices; m_indexed.kept[1] = mesh.numFaces;
     std::copy(stats, stats + VH_COMPONENTS_NUM_COUNTS, m_indexed.componentStats);
     m_welded = true;
 }
@@ -539,6 +496,7 @@ void CUDAMarchingCubesHashSDF::weldAndReadBack(unsigned int nTriangles, float vo
         check(vh_mesh_weld_data_alloc(&m_weld, nTriangles + nTriangles / 4u, 0), "vh_mesh_weld_data_alloc");
         m_weldOwner.reset(&m_weld);
     }
+    indexedChain(false).invalidateFrom(VH_FINISH_CLUSTER); // a new weld: what the stages made of the last one is stale
     check(vh_mesh_weld(m_data.d_triangles, d_sources.get(), nTriangles, &m_weld, 0, m_stream), "vh_mesh_weld");
     unsigned int counts[3] = { 0, 0, 0 };
     const int rc = vh_mesh_weld_get_counts(&m_weld, counts, m_stream);
@@ -737,55 +695,38 @@ void CUDAMarchingCubesHashSDF::extractIsoSurfaceIndexed(CUDASceneRepChunkGrid& c
     }
 }
 
+// The device mesh of the last indexed extraction, of the size getIndexedCounts reports: its welded mesh through its chain,
+// which has to stand as that extraction left it (an appendIndexed after the finishIndexed makes every stage stale).
+VhMeshView CUDAMarchingCubesHashSDF::indexedView(const char* what)
+{
+    unsigned int n[3];
+    getIndexedCounts(n);
+    if (n[0] == 0 && n[1] == 0) return VhMeshView{ nullptr, nullptr, nullptr, nullptr, 0u, 0u };
+    if (!m_indexed.accumulated && !m_weldOwner) throw vh::Error(VH_ERR_BAD_ARGUMENT, std::string(what) + ": no indexed extraction");
+    const VhMeshFinish& chain = indexedChain(m_indexed.accumulated);
+    const VhMeshView m = chain.after(VH_FINISH_COMPONENTS, indexedBase(m_indexed.accumulated, m_indexed.counts[0], m_indexed.counts[1]));
+    const unsigned ran = m_indexed.filtered ? 1u << VH_FINISH_COMPONENTS
+                                            : (m_indexed.clustered ? 1u << VH_FINISH_CLUSTER : 0u) | (m_indexed.smoothed ? 1u << VH_FINISH_SMOOTH : 0u) |
+                                                  (m_indexed.hasNormals ? 1u << VH_FINISH_NORMALS : 0u);
+    if (chain.state.passes(VH_FINISH_COMPONENTS, m_indexed.counts[0]) != ran || m.numVertices != n[0] || m.numFaces != n[1])
+        throw vh::Error(VH_ERR_BAD_ARGUMENT, std::string(what) + ": the mesh of the last indexed extraction is no longer on the device");
+    return m;
+}
+
 void CUDAMarchingCubesHashSDF::downloadIndexed(VhVertex* vertices, uint64_t* keys, uint32_t* faces)
 {
-    if (m_indexed.filtered) { // the filter's own buffers: the unfiltered mesh is still where the weld left it
-        const unsigned int kv = m_indexed.kept[0], kf = m_indexed.kept[1];
-        if (kv == 0 && kf == 0) return;
-        if (m_indexed.accumulated) check(vh_mesh_weld_accum_components_download(m_accum.get(), vertices, keys, nullptr, faces, kv, kf, m_stream), "vh_mesh_weld_accum_components_download");
-        else check(m_components->download(vertices, keys, nullptr, faces, kv, kf, m_stream), "mesh components");
-        return;
-    }
-    if (m_indexed.smoothed) { // the smoothing's own vertices; keys and faces are those of the mesh it ran over, below
-        const unsigned int sv = m_indexed.clustered ? m_indexed.clusterStats[VH_CLUSTER_VERTICES] : m_indexed.counts[0];
-        if (vertices && sv != 0) {
-            if (m_indexed.accumulated) check(vh_mesh_weld_accum_smooth_download(m_accum.get(), vertices, sv, m_stream), "vh_mesh_weld_accum_smooth_download");
-            else check(m_smooth->download(vertices, sv, m_stream), "mesh smoothing");
-        }
-        vertices = nullptr;
-    }
-    if (m_indexed.clustered) { // the clustering's own buffers, as above
-        const unsigned int cv = m_indexed.clusterStats[VH_CLUSTER_VERTICES], cf = m_indexed.clusterStats[VH_CLUSTER_FACES];
-        if (cv == 0 && cf == 0) return;
-        if (m_indexed.accumulated) check(vh_mesh_weld_accum_cluster_download(m_accum.get(), vertices, keys, faces, cv, cf, m_stream), "vh_mesh_weld_accum_cluster_download");
-        else check(m_cluster->download(vertices, keys, faces, cv, cf, m_stream), "mesh clustering");
-        return;
-    }
-    const unsigned int nv = m_indexed.counts[0], nf = m_indexed.counts[1];
-    if (nv == 0 && nf == 0) return;
-    if (m_indexed.accumulated) {
-        check(vh_mesh_weld_accum_download(m_accum.get(), vertices, keys, faces, nv, nf, m_stream), "vh_mesh_weld_accum_download");
-        return;
-    }
-    if (!m_weldOwner) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexed: no indexed extraction");
-    check(vh_mesh_weld_download(&m_weld, vertices, keys, faces, nv, nf, m_stream), "vh_mesh_weld_download");
+    const VhMeshView m = indexedView("downloadIndexed");
+    if (m.numVertices == 0 && m.numFaces == 0) return;
+    check(VhMeshFinish::download(m, vertices, keys, nullptr, faces, m_stream), "downloadIndexed");
 }
 
 void CUDAMarchingCubesHashSDF::downloadIndexedNormals(float* normals)
 {
     if (!m_indexed.hasNormals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexedNormals: the last indexed extraction computed none (setIndexedNormals)");
-    if (m_indexed.filtered) {
-        if (m_indexed.kept[0] == 0) return;
-        if (!normals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexedNormals");
-        if (m_indexed.accumulated) check(vh_mesh_weld_accum_components_download(m_accum.get(), nullptr, nullptr, normals, nullptr, m_indexed.kept[0], 0, m_stream), "vh_mesh_weld_accum_components_download");
-        else check(m_components->download(nullptr, nullptr, normals, nullptr, m_indexed.kept[0], 0, m_stream), "mesh components");
-        return;
-    }
-    const unsigned int nv = m_indexed.clustered ? m_indexed.clusterStats[VH_CLUSTER_VERTICES] : m_indexed.counts[0]; // the pass ran over the clustered mesh
-    if (nv == 0) return;
+    const VhMeshView m = indexedView("downloadIndexedNormals");
+    if (m.numVertices == 0) return;
     if (!normals) throw vh::Error(VH_ERR_BAD_ARGUMENT, "downloadIndexedNormals");
-    if (m_indexed.accumulated) check(vh_mesh_weld_accum_download_normals(m_accum.get(), normals, nv, m_stream), "vh_mesh_weld_accum_download_normals");
-    else check(m_normals->download(normals, nv, false, m_stream), "normals");
+    check(VhMeshFinish::download(m, nullptr, nullptr, normals, nullptr, m_stream), "downloadIndexedNormals");
 }
 
 void CUDAMarchingCubesHashSDF::downloadSources(VhTriangleSource* out, unsigned int n)

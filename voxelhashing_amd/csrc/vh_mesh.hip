@@ -18,10 +18,7 @@
 #include "vh_host_util.hpp"
 #include "vh_mesh_key.hpp"
 #include "vh_mesh_table.hpp"
-#include "vh_mesh_cluster.hpp"
-#include "vh_mesh_components.hpp"
-#include "vh_mesh_normals.hpp"
-#include "vh_mesh_smooth.hpp"
+#include "vh_mesh_finish.hpp"
 
 using namespace vhd;
 
@@ -554,17 +551,6 @@ int weldStatusCode(uint32_t status)
     return VH_OK;
 }
 
-// a welded mesh on the device to the host; an array that is not asked for is not copied
-int weldDownload(const VhVertex* d_vertices, const uint64_t* d_keys, const uint32_t* d_faces, VhVertex* vertices, uint64_t* keys, uint32_t* faces,
-                 uint32_t numVertices, uint32_t numFaces, hipStream_t s)
-{
-    if (vertices && numVertices) VH_HIP(hipMemcpyAsync(vertices, d_vertices, sizeof(VhVertex) * (size_t)numVertices, hipMemcpyDeviceToHost, s));
-    if (keys && numVertices) VH_HIP(hipMemcpyAsync(keys, d_keys, sizeof(uint64_t) * (size_t)numVertices, hipMemcpyDeviceToHost, s));
-    if (faces && numFaces) VH_HIP(hipMemcpyAsync(faces, d_faces, sizeof(uint32_t) * 3 * (size_t)numFaces, hipMemcpyDeviceToHost, s));
-    VH_HIP(hipStreamSynchronize(s));
-    return VH_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -657,7 +643,7 @@ int vh_mesh_weld_download(const VhMeshWeldData* data, VhVertex* vertices, uint64
 {
     if (!data || !data->d_vertices) return VH_ERR_BAD_ARGUMENT;
     if (numVertices > 3ull * data->m_maxTriangles || numFaces > data->m_maxTriangles) return VH_ERR_BAD_ARGUMENT;
-    return weldDownload(data->d_vertices, data->d_keys, data->d_faces, vertices, keys, faces, numVertices, numFaces, (hipStream_t)stream);
+    return VhMeshFinish::download(VhMeshView{ data->d_vertices, data->d_keys, data->d_faces, nullptr, numVertices, numFaces }, vertices, keys, nullptr, faces, stream);
 }
 
 int vh_mesh_normals_default_scale_log2(float voxelSize, int32_t* scaleLog2)
@@ -759,19 +745,7 @@ struct VhMeshWeldAccum {
     vh::DevicePtr<uint64_t> keys;
     vh::DevicePtr<uint8_t> ranks;
     vh::DevicePtr<uint32_t> faces;
-    VhMeshNormals normals;              // vertex normals (vh_mesh_weld_accum_normals): made by the first pass
-    uint32_t m_normalsVertices = 0;     // of the pass that m_normalsValid speaks of
-    bool m_normalsValid = false;        // the pass has run, and no begin or append since
-    VhMeshComponents components;        // the component filter (vh_mesh_weld_accum_components): made by the first pass
-    bool m_componentsValid = false;     // the pass has run, and no begin or append since
-    VhMeshCluster cluster;              // the vertex clustering (vh_mesh_weld_accum_cluster): made by the first pass
-    bool m_clusterRan = false;          // the pass has run, and no begin or append since
-    bool m_clusterValid = false;        // ... and left no status: normals and components are then of ITS mesh,
-    uint32_t m_clusterVertices = 0, m_clusterFaces = 0; // which has this size
-    VhMeshSmooth smooth;                // the Taubin smoothing (vh_mesh_weld_accum_smooth): made by the first pass
-    bool m_smoothRan = false;           // the pass has run, and no begin, append or cluster pass since
-    bool m_smoothValid = false;         // ... and left no status: normals and components then take ITS vertices,
-    uint32_t m_smoothVertices = 0;      // as many as the mesh it ran over has
+    VhMeshFinish finish;                // the passes over the welded mesh, and what of them holds since the last begin or append
     size_t m_soupCapacity = 0, m_vertexCapacity = 0, m_faceCapacity = 0; // in soup vertices, welded vertices, faces
     uint32_t m_slotsLog2 = 6, m_firstSlotsLog2 = 6;
     bool m_fixed = false, m_begun = false;
@@ -784,23 +758,6 @@ struct VhMeshWeldAccum {
 };
 
 namespace {
-
-// the mesh that the passes of the finish work on (`smoothed`: with the vertices of vh_mesh_weld_accum_smooth once that
-// has run over it): the clustered one once vh_mesh_weld_accum_cluster has run over these
-// appends, else the weld's own, whose counts are `have`
-struct AccumMesh {
-    const VhVertex* vertices;
-    const uint64_t* keys;
-    const uint32_t* faces;
-    uint32_t numVertices, numFaces;
-};
-AccumMesh accumMesh(const VhMeshWeldAccum& a, const uint32_t have[VH_WELD_ACCUM_NUM_COUNTS], bool smoothed = true)
-{
-    AccumMesh m = a.m_clusterValid ? AccumMesh{ a.cluster.vertices.get(), a.cluster.keys.get(), a.cluster.faces.get(), a.m_clusterVertices, a.m_clusterFaces }
-                                   : AccumMesh{ a.vertices.get(), a.keys.get(), a.faces.get(), have[VH_WELD_ACCUM_VERTICES], have[VH_WELD_ACCUM_FACES] };
-    if (smoothed && a.m_smoothValid && a.m_smoothVertices == m.numVertices) m.vertices = a.smooth.vertices.get();
-    return m;
-}
 
 // errors of the owner types (vh::deviceAlloc throws) become codes, as at the handle level
 template <class F> int accumGuarded(F&& f)
@@ -844,7 +801,25 @@ template <class T> int accumGrow(vh::DevicePtr<T>& p, size_t used, size_t capaci
     return VH_OK;
 }
 
+// A pass of the finish over the welded mesh: run(base).  Waits for the appends and reads their counts.  A weld that
+// failed has nothing to pass on: its code comes back, nothing runs, and what the pass held before is gone all the same.
+template <class F> int accumStage(VhMeshWeldAccum* accum, VhFinishStage stage, vhStream_t stream, F&& run)
+{
+    return accumGuarded([&]() -> int {
+        accum->finish.state.start(stage);
+        uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
+        VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream));
+        return run(vh_mesh_weld_accum_base(accum, have[VH_WELD_ACCUM_VERTICES], have[VH_WELD_ACCUM_FACES]));
+    });
+}
+
 } // namespace
+
+VhMeshFinish& vh_mesh_weld_accum_finish(VhMeshWeldAccum* accum) { return accum->finish; }
+VhMeshView vh_mesh_weld_accum_base(const VhMeshWeldAccum* accum, uint32_t numVertices, uint32_t numFaces)
+{
+    return VhMeshView{ accum->vertices.get(), accum->keys.get(), accum->faces.get(), nullptr, numVertices, numFaces };
+}
 
 extern "C" {
 
@@ -888,10 +863,7 @@ int vh_mesh_weld_accum_begin(VhMeshWeldAccum* accum, vhStream_t stream)
     accum->m_appends = 0;
     accum->m_rehashes = 0;
     accum->m_begun = true;
-    accum->m_normalsValid = false;
-    accum->m_componentsValid = false;
-    accum->m_clusterValid = accum->m_clusterRan = false;
-    accum->m_smoothValid = accum->m_smoothRan = false;
+    accum->finish.invalidateFrom(VH_FINISH_CLUSTER);
     return VH_OK;
 }
 
@@ -900,10 +872,9 @@ int vh_mesh_weld_accum_append(VhMeshWeldAccum* accum, const VhTriangle* d_triang
 {
     if (!accum || !accum->m_begun) return VH_ERR_BAD_ARGUMENT;
     if (numTriangles > 0x55555555u / 2u || (numTriangles != 0 && (!d_triangles || !d_sources))) return VH_ERR_BAD_ARGUMENT;
-    accum->m_normalsValid = false; // normals are of all faces with the final vertex bits: a pass before this append is stale
-    accum->m_componentsValid = false; // and a component spans appends
-    accum->m_clusterValid = accum->m_clusterRan = false; // and so does a cluster
-    accum->m_smoothValid = accum->m_smoothRan = false;   // and a vertex's neighbours
+    // a cluster, a vertex's neighbours and a component span appends, and normals are of all faces with the final vertex
+    // bits: every pass before this append is stale
+    accum->finish.invalidateFrom(VH_FINISH_CLUSTER);
     if (numTriangles == 0) return VH_OK; // nothing to take, and no launch with an empty grid
     if (accum->m_appends >= VH_WELD_ACCUM_MAX_APPENDS - 1u) return VH_ERR_BAD_ARGUMENT;
     hipStream_t s = (hipStream_t)stream;
@@ -980,87 +951,53 @@ int vh_mesh_weld_accum_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint
 {
     if (!accum) return VH_ERR_BAD_ARGUMENT;
     if (numVertices > accum->m_vertexCapacity || numFaces > accum->m_faceCapacity) return VH_ERR_BAD_ARGUMENT;
-    return weldDownload(accum->vertices.get(), accum->keys.get(), accum->faces.get(), vertices, keys, faces, numVertices, numFaces, (hipStream_t)stream);
+    return VhMeshFinish::download(vh_mesh_weld_accum_base(accum, numVertices, numFaces), vertices, keys, nullptr, faces, stream);
 }
 
 int vh_mesh_weld_accum_normals(VhMeshWeldAccum* accum, int32_t scaleLog2, vhStream_t stream)
 {
     if (!accum || !accum->m_begun || scaleLog2 < -100 || scaleLog2 > 100) return VH_ERR_BAD_ARGUMENT;
-    return accumGuarded([&]() -> int {
-        VhMeshWeldAccum& a = *accum;
-        a.m_normalsValid = false;
-        uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
-        VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream)); // waits for the appends; a weld that failed has no normals
-        const AccumMesh m = accumMesh(a, have);
-        const uint32_t nv = m.numVertices, nf = m.numFaces;
-        VH_TRY(a.normals.run(m.vertices, m.keys, m.faces, nv, nf, scaleLog2, stream));
-        a.m_normalsVertices = nv;
-        a.m_normalsValid = true;
-        return VH_OK;
-    });
+    return accumStage(accum, VH_FINISH_NORMALS, stream, [&](const VhMeshView& base) { return accum->finish.normals(base, scaleLog2, stream); });
 }
 
 int vh_mesh_weld_accum_download_normals(VhMeshWeldAccum* accum, float* normals, uint32_t numVertices, vhStream_t stream)
 {
-    if (!accum || !accum->m_normalsValid || numVertices > accum->m_normalsVertices || (numVertices != 0 && !normals)) return VH_ERR_BAD_ARGUMENT;
-    return accum->normals.download(normals, numVertices, true, stream);
+    if (!accum || !accum->finish.state.valid(VH_FINISH_NORMALS) || numVertices > accum->finish.state.vertices[VH_FINISH_NORMALS] || (numVertices != 0 && !normals))
+        return VH_ERR_BAD_ARGUMENT;
+    return accum->finish.m_normals.download(normals, numVertices, true, stream);
 }
 
 int vh_mesh_weld_accum_components(VhMeshWeldAccum* accum, uint32_t minFaces, uint32_t largestOnly, vhStream_t stream)
 {
     if (!accum || !accum->m_begun) return VH_ERR_BAD_ARGUMENT;
-    return accumGuarded([&]() -> int {
-        VhMeshWeldAccum& a = *accum;
-        a.m_componentsValid = false;
-        uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
-        VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream)); // waits for the appends; a weld that failed has no components
-        const AccumMesh m = accumMesh(a, have);
-        const uint32_t nv = m.numVertices, nf = m.numFaces;
-        // normals ride along when their pass has run over this very mesh (it leaves zeros, not garbage, behind a status)
-        const float* d_normals = a.m_normalsValid && a.m_normalsVertices == nv ? a.normals.normals.get() : nullptr;
-        VH_TRY(a.components.run(m.vertices, m.keys, d_normals, m.faces, nv, nf, minFaces, largestOnly, stream));
-        a.m_componentsValid = true;
-        return VH_OK;
-    });
+    return accumStage(accum, VH_FINISH_COMPONENTS, stream, [&](const VhMeshView& base) { return accum->finish.components(base, minFaces, largestOnly, stream); });
 }
 
 int vh_mesh_weld_accum_cluster(VhMeshWeldAccum* accum, uint32_t cellsPerCluster, int32_t scaleLog2, vhStream_t stream)
 {
     if (!accum || !accum->m_begun || cellsPerCluster > VH_CLUSTER_MAX_CELLS || scaleLog2 < -100 || scaleLog2 > 100) return VH_ERR_BAD_ARGUMENT;
     if (cellsPerCluster == 0u) { // forget the pass: the passes of the finish are of the welded mesh again
-        if (accum->m_clusterRan)
-            accum->m_clusterValid = accum->m_clusterRan = accum->m_smoothValid = accum->m_smoothRan = accum->m_normalsValid = accum->m_componentsValid = false;
+        accum->finish.forget(VH_FINISH_CLUSTER);
         return VH_OK;
     }
-    return accumGuarded([&]() -> int {
-        VhMeshWeldAccum& a = *accum;
-        // normals and components of the mesh before this pass are not of the mesh after it
-        a.m_clusterValid = a.m_clusterRan = a.m_smoothValid = a.m_smoothRan = a.m_normalsValid = a.m_componentsValid = false; // (a smoothing too)
-        uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
-        VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream)); // waits for the appends; a weld that failed has nothing to cluster
-        VH_TRY(a.cluster.run(a.vertices.get(), a.keys.get(), a.faces.get(), have[VH_WELD_ACCUM_VERTICES], have[VH_WELD_ACCUM_FACES], cellsPerCluster, scaleLog2, stream));
-        a.m_clusterRan = true;
-        uint32_t counts[VH_CLUSTER_NUM_COUNTS] = {};
-        if (a.cluster.counts(counts, stream) == VH_OK) { // (what it was is vh_mesh_weld_accum_cluster_get_counts' to report)
-            a.m_clusterVertices = counts[VH_CLUSTER_VERTICES];
-            a.m_clusterFaces = counts[VH_CLUSTER_FACES];
-            a.m_clusterValid = true;
-        }
-        return VH_OK;
-    });
+    // (a status the pass left is vh_mesh_weld_accum_cluster_get_counts' to report)
+    return accumStage(accum, VH_FINISH_CLUSTER, stream, [&](const VhMeshView& base) { return accum->finish.cluster(base, cellsPerCluster, scaleLog2, stream); });
 }
 
 int vh_mesh_weld_accum_cluster_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream)
 {
-    if (!accum || !out || !accum->m_clusterRan) return VH_ERR_BAD_ARGUMENT;
-    return accum->cluster.counts(out, stream);
+    if (!accum || !out || !accum->finish.state.ran[VH_FINISH_CLUSTER]) return VH_ERR_BAD_ARGUMENT;
+    return accum->finish.m_cluster.counts(out, stream);
 }
 
 int vh_mesh_weld_accum_cluster_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint64_t* keys, uint32_t* faces, uint32_t numVertices, uint32_t numFaces,
                                         vhStream_t stream)
 {
-    if (!accum || !accum->m_clusterValid || numVertices > accum->m_clusterVertices || numFaces > accum->m_clusterFaces) return VH_ERR_BAD_ARGUMENT;
-    return accum->cluster.download(vertices, keys, faces, numVertices, numFaces, stream);
+    if (!accum || !accum->finish.state.valid(VH_FINISH_CLUSTER)) return VH_ERR_BAD_ARGUMENT;
+    const VhMeshFinish& f = accum->finish;
+    if (numVertices > f.state.vertices[VH_FINISH_CLUSTER] || numFaces > f.state.faces[VH_FINISH_CLUSTER]) return VH_ERR_BAD_ARGUMENT;
+    return VhMeshFinish::download(VhMeshView{ f.m_cluster.vertices.get(), f.m_cluster.keys.get(), f.m_cluster.faces.get(), nullptr, numVertices, numFaces }, vertices, keys,
+                                  nullptr, faces, stream);
 }
 
 int vh_mesh_weld_accum_smooth(VhMeshWeldAccum* accum, uint32_t iterations, int32_t lambdaQ16, int32_t muQ16, uint32_t keepBoundary, int32_t scaleLog2,
@@ -1070,50 +1007,41 @@ int vh_mesh_weld_accum_smooth(VhMeshWeldAccum* accum, uint32_t iterations, int32
     if (lambdaQ16 < -VH_SMOOTH_MAX_FACTOR_Q16 || lambdaQ16 > VH_SMOOTH_MAX_FACTOR_Q16 || muQ16 < -VH_SMOOTH_MAX_FACTOR_Q16 || muQ16 > VH_SMOOTH_MAX_FACTOR_Q16)
         return VH_ERR_BAD_ARGUMENT;
     if (iterations == 0u) { // forget the pass: the passes of the finish take the vertices as they were again
-        if (accum->m_smoothRan) accum->m_smoothValid = accum->m_smoothRan = accum->m_normalsValid = accum->m_componentsValid = false;
+        accum->finish.forget(VH_FINISH_SMOOTH);
         return VH_OK;
     }
-    return accumGuarded([&]() -> int {
-        VhMeshWeldAccum& a = *accum;
-        // normals and components of the mesh before this pass are not of the mesh after it
-        a.m_smoothValid = a.m_smoothRan = a.m_normalsValid = a.m_componentsValid = false;
-        uint32_t have[VH_WELD_ACCUM_NUM_COUNTS] = {};
-        VH_TRY(vh_mesh_weld_accum_get_counts(accum, have, stream)); // waits for the appends; a weld that failed has nothing to smooth
-        const AccumMesh m = accumMesh(a, have, false);
-        VH_TRY(a.smooth.run(m.vertices, m.keys, m.faces, m.numVertices, m.numFaces, iterations, lambdaQ16, muQ16, keepBoundary, scaleLog2, stream));
-        a.m_smoothRan = true;
-        uint32_t counts[VH_SMOOTH_NUM_COUNTS] = {};
-        if (a.smooth.counts(counts, stream) == VH_OK) { // (what it was is vh_mesh_weld_accum_smooth_get_counts' to report)
-            a.m_smoothVertices = m.numVertices;
-            a.m_smoothValid = true;
-        }
-        return VH_OK;
+    // (a status the pass left is vh_mesh_weld_accum_smooth_get_counts' to report)
+    return accumStage(accum, VH_FINISH_SMOOTH, stream, [&](const VhMeshView& base) {
+        return accum->finish.smooth(base, iterations, lambdaQ16, muQ16, keepBoundary, scaleLog2, stream);
     });
 }
 
 int vh_mesh_weld_accum_smooth_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream)
 {
-    if (!accum || !out || !accum->m_smoothRan) return VH_ERR_BAD_ARGUMENT;
-    return accum->smooth.counts(out, stream);
+    if (!accum || !out || !accum->finish.state.ran[VH_FINISH_SMOOTH]) return VH_ERR_BAD_ARGUMENT;
+    return accum->finish.m_smooth.counts(out, stream);
 }
 
 int vh_mesh_weld_accum_smooth_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint32_t numVertices, vhStream_t stream)
 {
-    if (!accum || !accum->m_smoothValid || numVertices > accum->m_smoothVertices) return VH_ERR_BAD_ARGUMENT;
-    return accum->smooth.download(vertices, numVertices, stream);
+    if (!accum || !accum->finish.state.valid(VH_FINISH_SMOOTH) || numVertices > accum->finish.state.vertices[VH_FINISH_SMOOTH]) return VH_ERR_BAD_ARGUMENT;
+    return VhMeshFinish::download(VhMeshView{ accum->finish.m_smooth.vertices.get(), nullptr, nullptr, nullptr, numVertices, 0u }, vertices, nullptr, nullptr, nullptr, stream);
 }
 
 int vh_mesh_weld_accum_components_get_counts(VhMeshWeldAccum* accum, uint32_t out[6], vhStream_t stream)
 {
-    if (!accum || !out || !accum->m_componentsValid) return VH_ERR_BAD_ARGUMENT;
-    return accum->components.counts(out, stream);
+    if (!accum || !out || !accum->finish.state.valid(VH_FINISH_COMPONENTS)) return VH_ERR_BAD_ARGUMENT;
+    return accum->finish.m_components.counts(out, stream);
 }
 
 int vh_mesh_weld_accum_components_download(VhMeshWeldAccum* accum, VhVertex* vertices, uint64_t* keys, float* normals, uint32_t* faces,
                                            uint32_t numVertices, uint32_t numFaces, vhStream_t stream)
 {
-    if (!accum || !accum->m_componentsValid) return VH_ERR_BAD_ARGUMENT;
-    return accum->components.download(vertices, keys, normals, faces, numVertices, numFaces, stream);
+    if (!accum || !accum->finish.state.valid(VH_FINISH_COMPONENTS)) return VH_ERR_BAD_ARGUMENT;
+    const VhMeshComponents& c = accum->finish.m_components; // the caller has the kept counts; what bounds them here is the room there is
+    if (numVertices > c.vertexCapacity || numFaces > c.faceCapacity) return VH_ERR_BAD_ARGUMENT;
+    return VhMeshFinish::download(VhMeshView{ c.vertices.get(), c.keys.get(), c.faces.get(), c.hasNormals ? c.normals.get() : nullptr, numVertices, numFaces }, vertices, keys,
+                                  normals, faces, stream);
 }
 
 } // extern "C"

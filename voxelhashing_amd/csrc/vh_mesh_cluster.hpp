@@ -1,6 +1,5 @@
 // vh_mesh_cluster.hpp -- who owns the buffers of the vertex clustering (vh_mesh_cluster; DESIGN.md section 4, "Mesh
-// clustering").  The accumulating weld (vh_mesh.hip) and the one-shot indexed extraction (vh_marching_cubes.cpp) hold
-// one each.
+// clustering").  A stage of the finish's chain (vh_mesh_finish.hpp), which owns one and downloads what it made.
 #pragma once
 
 #include <algorithm>
@@ -84,17 +83,5 @@ struct VhMeshCluster {
         const uint32_t status = out[VH_CLUSTER_STATUS];
         if (status & ~VH_CLUSTER_TABLE_FULL) return VH_ERR_BAD_ARGUMENT;
         return status != 0u ? VH_ERR_STAGING_OVERFLOW : VH_OK;
-    }
-
-    // the clustered mesh to the host; an array that is not asked for is not copied
-    int download(VhVertex* outVertices, uint64_t* outKeys, uint32_t* outFaces, uint32_t nv, uint32_t nf, vhStream_t stream) const
-    {
-        hipStream_t s = (hipStream_t)stream;
-        if (nv > vertexCapacity || nf > faceCapacity) return VH_ERR_BAD_ARGUMENT;
-        if (outVertices && nv) VH_HIP(hipMemcpyAsync(outVertices, vertices.get(), sizeof(VhVertex) * (size_t)nv, hipMemcpyDeviceToHost, s));
-        if (outKeys && nv) VH_HIP(hipMemcpyAsync(outKeys, keys.get(), sizeof(uint64_t) * (size_t)nv, hipMemcpyDeviceToHost, s));
-        if (outFaces && nf) VH_HIP(hipMemcpyAsync(outFaces, faces.get(), sizeof(uint32_t) * 3 * (size_t)nf, hipMemcpyDeviceToHost, s));
-        VH_HIP(hipStreamSynchronize(s));
-        return VH_OK;
     }
 };

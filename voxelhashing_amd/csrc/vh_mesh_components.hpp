@@ -1,6 +1,6 @@
 // vh_mesh_components.hpp -- who owns the buffers of the component pass (vh_mesh_components, vh_mesh_components_filter;
-// DESIGN.md section 4, "Mesh components").  The accumulating weld (vh_mesh.hip) and the one-shot indexed extraction
-// (vh_marching_cubes.cpp) hold one each.
+// DESIGN.md section 4, "Mesh components").  A stage of the finish's chain (vh_mesh_finish.hpp), which owns one and downloads
+// what it made.
 #pragma once
 
 #include <algorithm>
@@ -64,18 +64,5 @@ struct VhMeshComponents {
         VH_HIP(hipStreamSynchronize((hipStream_t)stream));
         std::copy(w + 1, w + 1 + VH_COMPONENTS_NUM_COUNTS, out);
         return w[0] != 0u ? VH_ERR_BAD_ARGUMENT : VH_OK;
-    }
-
-    // the filtered mesh to the host; an array that is not asked for is not copied
-    int download(VhVertex* outVertices, uint64_t* outKeys, float* outNormals, uint32_t* outFaces, uint32_t nv, uint32_t nf, vhStream_t stream) const
-    {
-        hipStream_t s = (hipStream_t)stream;
-        if (nv > vertexCapacity || nf > faceCapacity || (outNormals && nv && !hasNormals)) return VH_ERR_BAD_ARGUMENT;
-        if (outVertices && nv) VH_HIP(hipMemcpyAsync(outVertices, vertices.get(), sizeof(VhVertex) * (size_t)nv, hipMemcpyDeviceToHost, s));
-        if (outKeys && nv) VH_HIP(hipMemcpyAsync(outKeys, keys.get(), sizeof(uint64_t) * (size_t)nv, hipMemcpyDeviceToHost, s));
-        if (outNormals && nv) VH_HIP(hipMemcpyAsync(outNormals, normals.get(), sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, s));
-        if (outFaces && nf) VH_HIP(hipMemcpyAsync(outFaces, faces.get(), sizeof(uint32_t) * 3 * (size_t)nf, hipMemcpyDeviceToHost, s));
-        VH_HIP(hipStreamSynchronize(s));
-        return VH_OK;
     }
 };

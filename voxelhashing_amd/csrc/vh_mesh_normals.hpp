@@ -1,6 +1,5 @@
 // vh_mesh_normals.hpp -- who owns the buffers of the vertex-normal pass (vh_mesh_vertex_normals; DESIGN.md section 4,
-// "Vertex normals").  The accumulating weld (vh_mesh.hip) and the one-shot indexed extraction
-// (vh_marching_cubes.cpp) hold one each.
+// "Vertex normals").  A stage of the finish's chain (vh_mesh_finish.hpp), which owns one.
 #pragma once
 
 #include <algorithm>

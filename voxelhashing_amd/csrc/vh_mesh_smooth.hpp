@@ -1,6 +1,5 @@
 // vh_mesh_smooth.hpp -- who owns the buffers of the Taubin smoothing (vh_mesh_smooth; DESIGN.md section 4, "Mesh
-// smoothing").  The accumulating weld (vh_mesh.hip) and the one-shot indexed extraction (vh_marching_cubes.cpp) hold
-// one each.
+// smoothing").  A stage of the finish's chain (vh_mesh_finish.hpp), which owns one and downloads what it made.
 #pragma once
 
 #include <algorithm>
@@ -71,15 +70,5 @@ struct VhMeshSmooth {
         const uint32_t status = out[VH_SMOOTH_STATUS];
         if (status & ~VH_SMOOTH_TABLE_FULL) return VH_ERR_BAD_ARGUMENT;
         return status != 0u ? VH_ERR_STAGING_OVERFLOW : VH_OK;
-    }
-
-    // the smoothed vertices to the host
-    int download(VhVertex* outVertices, uint32_t nv, vhStream_t stream) const
-    {
-        hipStream_t s = (hipStream_t)stream;
-        if (nv > vertexCapacity) return VH_ERR_BAD_ARGUMENT;
-        if (outVertices && nv) VH_HIP(hipMemcpyAsync(outVertices, vertices.get(), sizeof(VhVertex) * (size_t)nv, hipMemcpyDeviceToHost, s));
-        VH_HIP(hipStreamSynchronize(s));
-        return VH_OK;
     }
 };
