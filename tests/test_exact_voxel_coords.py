@@ -1,4 +1,4 @@
-"""The identities behind three short cuts of the device code (vh_device.hpp, vh_kernels.hip), in numpy's float32 / int32:
+"""The identities behind three short cuts of the device code (vh_device.hpp, vh_ray_lookup.hpp), in numpy's float32 / int32:
 
   * round_half_away:  (int)(p + copysignf(0.5f, p))  ==  (int)(p + sign(p) * 0.5f), the reference's worldToVirtualVoxelPos,
     with the device's conversion (toward zero, saturating, NaN -> 0);

@@ -1,6 +1,6 @@
 """The ray march on its exact route, and the voxel and block coordinates every kernel forms, against the oracle bit for bit.
 
-tap_coords (vh_kernels.hip) takes the fused route for a sample whose position is certainly not within rounding distance of a
+tap_coords (vh_ray_sample.hpp) takes the fused route for a sample whose position is certainly not within rounding distance of a
 voxel boundary, and the reference's own arithmetic -- world_to_vvp1_rb, vvp_to_block1 -- for the others; one uncertain lane
 sends its whole wave there.  The scenes below put the camera where that happens all the time:
 

@@ -1,4 +1,4 @@
-"""The fused integrate pass picks its shape on the device from the block count (vh_kernels.hip, k_integrate_fused):
+"""The fused integrate pass picks its shape on the device from the block count (vh_frame_integrate.hpp, k_integrate_fused):
 one workgroup per block when blocks are few, one wave per block in several rounds when they are many, and in that
 shape a block's screen footprint is staged in LDS when it fits 32 x 31 pixels.  Each shape and each branch against
 the oracle, bit for bit, over frames with garbage collection and starving."""

@@ -252,7 +252,7 @@ def test_cost_classes_of_scheduled_and_stale_run_are_the_same(slot_renders):
     sample the halves share counted once, nothing behind a hit in the near half).
     The property is partial, and this wall is inside it: it holds for tiles with complete lists rendered without gradients.
     A tile whose list overflowed still pays the shared sample twice, and with gradients a split tile's cost is the sum of
-    its halves' dearest rays as before (vh_kernels.hip says why); neither case is asserted here."""
+    its halves' dearest rays as before (vh_ray_march.hpp and vh_ray_tiles.hpp say why); neither case is asserted here."""
     w = slot_renders
     differ = np.nonzero(w["c_fresh"] != w["c_stale"])[0]
     print(f"\ncost classes {np.unique(w['c_fresh']).tolist()}; {len(differ)} tiles differ, {int(np.isin(differ, w['split']).sum())} of them split tiles")

@@ -63,6 +63,28 @@ def test_offsets32_rule(vh):
     assert vh.vh_render_offsets32(1 << 20) == 1
 
 
+# image sizes by their number of 8x8 tiles; from 300 on they are tests/test_gpu_tile_intervals.py's SIZES
+SCHEDULE_SIZES = {0: (0, 0), 1: (8, 8), 300: (160, 120), 1023: (264, 248), 1024: (256, 256), 1056: (264, 256), 1073: (291, 227)}
+
+
+@pytest.mark.parametrize("n_tiles", list(SCHEDULE_SIZES))
+def test_schedule_buffer_size(vh, n_tiles):
+    """the schedule buffer's words as tests/test_gpu_tile_intervals.py::Schedule lays it out: 4 header words, a cost class
+    per tile padded to whole quads, two words per launch slot for 4 * ceil((tiles + 256) / 4) slots -- room for the most
+    tiles any image has split; and the tiles this image has split, against tile_intervals.split_tiles"""
+    import tile_intervals as TI
+    W, H = SCHEDULE_SIZES[n_tiles]
+    assert ((W + 7) // 8) * ((H + 7) // 8) == n_tiles
+    quads = lambda n: (n + 3) // 4  # noqa: E731
+    words = 4 + 4 * quads(n_tiles) + 2 * 4 * quads(n_tiles + 256)
+    nbytes = vh.vh_render_schedule_bytes(W, H)
+    print(n_tiles, "tiles:", nbytes, "bytes, the layout", 4 * words)
+    assert nbytes % 4 == 0 and nbytes // 4 == words
+    assert vh.vh_render_split_tiles(W, H) == TI.split_tiles(n_tiles)
+    # the slots a launch uses lie inside the buffer
+    assert 4 + 4 * quads(n_tiles) + 2 * 4 * quads(n_tiles + TI.split_tiles(n_tiles)) <= words
+
+
 ASM = """
 	.text
 	.globl	_Z3fooPf

@@ -18,7 +18,7 @@ LIB = os.path.join(HERE, "libvoxelhashing_amd.so")
 SOURCES = ["vh_kernels.hip", "vh_icp.hip", "vh_image.hip", "vh_streaming.hip", "vh_mc.hip", "vh_util.hip", "vh_probe.hip", "vh_view.hip", "vh_mesh.hip", "vh_mesh_cluster.hip", "vh_mesh_smooth.hip", "vh_merge.hip", "vh_resample.hip", "vh_cut.hip", "vh_deintegrate.hip", "vh_live_mesh.hip", "vh_align.hip",
            "vh_png.cpp", "vh_host.cpp", "vh_chunk_grid.cpp", "vh_marching_cubes.cpp", "vh_sensor.cpp", "vh_sensor_data.cpp", "vh_params.cpp", "vh_tracking.cpp", "vh_reconstruction.cpp", "vh_c_api.cpp"]
 HEADERS = ["vh_device.hpp", "vh_frame_alloc.hpp", "vh_frame_compactify.hpp", "vh_frame_integrate.hpp", "vh_frame_splat.hpp", "vh_frame_normals.hpp",
-           "vh_frame_checks.hpp", "vh_host_util.hpp", "vh_stage_timer.hpp", "vh_handles.hpp", "vh_params.hpp", "vh_mesh_key.hpp", "vh_mesh_table.hpp", "vh_mesh_normals.hpp", "vh_mesh_components.hpp", "vh_mesh_cluster.hpp", "vh_mesh_smooth.hpp", "vh_mesh_finish.hpp", "vh_resample_blend.hpp", "vh_scene_ops.hpp", "vh_solve_6x6.hpp",
+           "vh_frame_checks.hpp", "vh_ray_lookup.hpp", "vh_ray_sample.hpp", "vh_ray_march.hpp", "vh_ray_query.hpp", "vh_ray_tiles.hpp", "vh_host_util.hpp", "vh_stage_timer.hpp", "vh_handles.hpp", "vh_params.hpp", "vh_mesh_key.hpp", "vh_mesh_table.hpp", "vh_mesh_normals.hpp", "vh_mesh_components.hpp", "vh_mesh_cluster.hpp", "vh_mesh_smooth.hpp", "vh_mesh_finish.hpp", "vh_resample_blend.hpp", "vh_scene_ops.hpp", "vh_solve_6x6.hpp",
            os.path.join(ROOT, "include", "vh_types.h"), os.path.join(ROOT, "include", "vh_api.h"),
            os.path.join(ROOT, "include", "vh.hpp"), os.path.join(ROOT, "include", "vh_owners.hpp"),
            os.path.join(ROOT, "include", "vh_mc_tables.h")]

@@ -1,6 +1,6 @@
 // vh_frame_alloc.hpp -- frame loop, first stage: the reset kernels, and alloc (alloc_tile, k_alloc) with the frame it
 // packs for the integrate pass (pack_pixel).  Included by vh_frame_integrate.hpp (the pass reads the packed frame)
-// and by vh_kernels.hip, where k_render carries alloc_tile as a rider (CoAlloc).
+// and by vh_ray_tiles.hpp, where k_render carries alloc_tile as a rider (CoAlloc).
 #pragma once
 
 #include "vh_device.hpp"

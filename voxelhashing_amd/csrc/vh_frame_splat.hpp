@@ -1,7 +1,8 @@
 // vh_frame_splat.hpp -- frame loop: what the tile ray caster is handed.  The interval splat (tile heads and block lists:
 // interval_splat_group, k_interval_splat, k_interval_clear) and the launch order of the next render (split_tiles,
-// schedule_tiles).  Included by vh_kernels.hip (the march counts in its cost units, the tile ray caster reads the
-// schedule) and by vh_frame_normals.hpp (k_compute_normals carries interval_splat_group as a rider).
+// schedule_tiles; the schedule buffer's layout and size, schedule_words).  Included by vh_kernels.hip, by vh_ray_tiles.hpp
+// (the tile ray caster reads the heads, the lists and the schedule, and leaves the cost classes) and by
+// vh_frame_normals.hpp (k_compute_normals carries interval_splat_group as a rider).
 #pragma once
 
 #include "vh_device.hpp"
@@ -41,9 +42,9 @@ VHD void divmod_small(uint32_t i, uint32_t nx, float rnx, uint32_t& q, uint32_t&
 // Three steps per workgroup, each one trip to memory: occupancy words -> bucket queue (LDS); slots of the queued
 // buckets -> block queue (LDS); one wave per queued block folds it into its tiles.  The queues balance the waves: a
 // block costs a wave a few thousand cycles, and the kernel is as long as its busiest wave.
-// Cost of a tile in units of one empty-space step; a full sample (8 taps) weighs kCostSample of them.  The wave's
-// cost is its busiest lane's: k_render stores the tile's cost class for the next frame's launch order.
-constexpr uint32_t kCostSample = 6;
+// Cost of a tile in units of one empty-space step; a full sample (8 taps) weighs kCostSample of them (vh_ray_march.hpp,
+// where they are counted).  The wave's cost is its busiest lane's: k_render stores the tile's cost class for the next
+// frame's launch order.
 constexpr uint32_t kCostClasses = 32;
 constexpr uint32_t kCostClassWidth = 8;
 // The dearest tiles of a frame are marched by TWO waves of one workgroup, each one half of the tile's depth interval:
@@ -77,10 +78,17 @@ __host__ __device__ inline uint32_t split_tiles(uint32_t nTiles) // one tile in 
 constexpr uint32_t kSchedGroups = 8;
 __host__ __device__ inline uint32_t sched_groups(uint32_t nTiles) { return nTiles >= kSplitMinTiles ? kSchedGroups : 1u; }
 
+// The schedule buffer (host): {phase the slots were made for, longest list, -, -}, a cost class per tile padded to whole
+// quads, then {tile | half << 24, phase} per launch slot -- a slot for each of the four waves of `renderGroups` workgroups
+// of the tile ray caster (render_groups, vh_ray_tiles.hpp).  This is the layout's definition: schedule_tiles below and
+// render_tile spell out where the slots begin.
+inline size_t schedule_words(uint32_t nTiles, uint32_t renderGroups) { return 4u + 4u * (size_t)cdiv(nTiles, 4) + 2u * 4u * (size_t)renderGroups; }
+
 __device__ void schedule_tiles(uint32_t* sched, uint32_t* feedback, uint32_t nTiles, uint32_t phase, uint32_t numCUs, uint32_t part, uint32_t parts,
                                uint32_t* sCount /*[2 * 256]*/)
 {
-    // layout: {phase the slots were made for, -, -, -}, cost class per tile, {tile, phase} per launch slot
+    // layout: {phase the slots were made for, -, -, -}, cost class per tile, {tile, phase} per launch slot (schedule_words
+    // defines it; where the slots begin is spelled out here and in render_tile, vh_ray_tiles.hpp)
     const uint32_t* cls = sched + 4;
     uint2* slots = reinterpret_cast<uint2*>(sched + 4 + 4u * ((nTiles + 3u) / 4u));
     const uint32_t nSplit = split_tiles(nTiles);
